@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on MI355X: frames/sec for (grid-detect + cylinder fit) on a 1920x1200 batch.
 
-    python bench.py --gpus N --steps K --warmup W [--frames F] [--scaling strong|weak] [--chunk C]
+    python bench.py --gpus N --steps K --warmup W [--frames F] [--scaling strong|weak] [--chunk C] [--dump-outputs DIR]
 
 A "step" is one pass of the whole hot path (detect_grid on both images of every stereo frame, chooseIdx +
 triangulate, fitCylinderWPts3 Nelder-Mead, applyCylParamsPrior) over one batch of synthetic frames, inputs resident
@@ -271,6 +271,30 @@ def pmc_traffic(kernel, images_per_launch):
     return None, None
 
 
+DUMP_LIMIT = 64 << 20                               # --dump-outputs: bytes written at most
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT, seed=0):
+    """--dump-outputs: every array of `arrays` (name -> float32 / float64 array, rows = frames) as <dirname>/<name>.npy.
+    If they exceed `limit` bytes together, the same fixed, seeded sample of rows (in ascending order) is kept of each, and
+    the sampled row numbers are written beside them as <dirname>/rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError(f'--dump-outputs: {k} is {v.dtype}, not float32 / float64')
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(v.nbytes // max(len(v), 1) for v in arrays.values())
+    if n * row_bytes > limit:
+        keep = limit // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays['rows'] = rows.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), v)
+
+
 class StubPipeline:
     """CPU stand-in for FramePipeline used by tests/test_dist_cpu.py (--stub): exercises the launcher, the sharding and
     the gather of bench.py with gloo, no GPU and no kernels"""
@@ -388,6 +412,9 @@ def run_rank(args):
     sync(); D.barrier()
     dt = time.perf_counter() - t0
     dt = D.max_over_ranks(dt, dev)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned: the pose records of every frame of the batch (pipeline.REC f64 per frame)
+        dump_outputs(args.dump_outputs, dict(records=allrec.cpu().numpy()))
 
     # ---- the closing collective alone (untimed extra): K all-gathers of the pose records
     t0 = time.perf_counter()
@@ -514,8 +541,13 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--backend', choices=['nccl', 'gloo'], default='nccl', help='nccl = RCCL over xGMI (default); gloo: rehearsal')
     ap.add_argument('--share-gpu', action='store_true', help='rehearsal on a one-GPU box: every rank uses cuda:0 (needs --backend gloo)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the pose records of the last step as DIR/records.npy (f64 [frames, 16]; '
+                         'a fixed, seeded sample of rows if above 64 MB, their row numbers in DIR/rows.npy)')
     ap.add_argument('--stub', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if args.frames is None:
         args.frames = 256 if args.stage == 'detect' else 4096
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:

@@ -169,3 +169,41 @@ def test_bench_batch_does_not_depend_on_the_sharding():
         assert not torch.equal(full[1][6], full[1][0])            # frame 6 = scene 0 with its own noise
     finally:
         bench.H, bench.W = old
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the records the last timed step returned, as DIR/records.npy (f64), the same from run to run and
+    whatever the number of ranks; --steps sets the timed steps and must be at least 1"""
+    import numpy as np
+    a, b = tmp_path / 'a', tmp_path / 'b'
+    rc, out, err = _bench('--gpus', '1', '--stub', '--frames', '11', '--steps', '3', '--warmup', '0', '--dump-outputs', str(a))
+    assert rc == 0, err
+    assert out['steps'] == 3 and sorted(os.listdir(a)) == ['records.npy']
+    rc, out, err = _bench('--gpus', '2', '--stub', '--frames', '11', '--steps', '1', '--warmup', '1', '--dump-outputs', str(b))
+    assert rc == 0, err
+    ra, rb = np.load(a / 'records.npy'), np.load(b / 'records.npy')
+    assert ra.dtype == np.float64 and ra.shape == (11, 16)
+    assert np.array_equal(ra[:, 0], np.arange(11.0)) and ra[:, 1].sum() == out['payload_sum']
+    assert np.array_equal(ra, rb)
+    rc, out, err = _bench('--gpus', '1', '--stub', '--steps', '0')
+    assert rc != 0 and out is None
+
+
+def test_bench_dump_outputs_samples_large_outputs(tmp_path):
+    """above the byte limit the dump keeps one fixed, seeded sample of rows of every array and names them in rows.npy"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    x = np.arange(100 * 16, dtype=np.float64).reshape(100, 16)
+    y = np.arange(100, dtype=np.float32)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), dict(records=x, err=y), limit=1000)
+    got = {f: np.load(tmp_path / 'a' / f) for f in sorted(os.listdir(tmp_path / 'a'))}
+    assert sorted(got) == ['err.npy', 'records.npy', 'rows.npy']
+    assert sum(v.nbytes for v in got.values()) <= 1000
+    rows = got['rows.npy'].astype(np.int64)
+    assert len(rows) > 0 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got['records.npy'], x[rows]) and np.array_equal(got['err.npy'], y[rows])
+    assert all(np.array_equal(v, np.load(tmp_path / 'b' / f)) for f, v in got.items())
+    bench.dump_outputs(str(tmp_path / 'c'), dict(records=x))
+    assert sorted(os.listdir(tmp_path / 'c')) == ['records.npy']

@@ -1,5 +1,5 @@
 """The oracle against golden vectors produced by the REAL reference functions
-(tools/gen_golden.py, generated in the authoring container from /root/reference)."""
+(tools/gen_golden.py, generated once from the reference project's own code)."""
 import json
 import os
 
