@@ -180,22 +180,52 @@ __device__ __forceinline__ unsigned long long col_mask64(int x0, int lo, int hi)
 }
 
 // where the word-level walks read the set from: the u8 image (compare with a threshold) or a one-bit plane of it that
-// already exists (cpe_dev.h BitWin layout: pixel x is bit x + 32 of its row; zero beyond the image) -- an eighth of the bytes
+// already exists (cpe_dev.h tiled layout: the 8 rows of a walk's strip are one 64-byte line; zero beyond the image) -- an
+// eighth of the bytes
 struct ByteSrc {
     const uint8_t *img; int w, thr, invert;
     __device__ __forceinline__ ByteSrc frame(size_t f, int h) const { return ByteSrc{img + f * (size_t)h * w, w, thr, invert}; }
     __device__ __forceinline__ unsigned long long pack(int y, int x0) const { return pack_row64(img + (size_t)y * w, x0, w, thr, invert); }
     __device__ __forceinline__ bool px(int y, int x) const { return pred(img + (size_t)y * w, x, thr, invert); }
+    // rows y8 .. y8 + 7 (y8 = 8 * strip) of word column x0, the rows outside ya .. yb as zero
+    __device__ __forceinline__ void strip(int y8, int ya, int yb, int x0, unsigned long long (&m)[CCL_STRIP]) const
+    {
+#pragma unroll
+        for (int k = 0; k < CCL_STRIP; k++) m[k] = (y8 + k >= ya && y8 + k <= yb) ? pack(y8 + k, x0) : 0ull;
+    }
+    // bit k: pixel x of row y8 + k (rows outside ya .. yb: 0)
+    __device__ __forceinline__ unsigned colbits(int y8, int ya, int yb, int x) const
+    {
+        unsigned b = 0;
+#pragma unroll
+        for (int k = 0; k < CCL_STRIP; k++)
+            if (y8 + k >= ya && y8 + k <= yb && px(y8 + k, x)) b |= 1u << k;
+        return b;
+    }
 };
 struct BitSrc {
-    const uint32_t *plane; int ws;
-    __device__ __forceinline__ BitSrc frame(size_t f, int h) const { return BitSrc{plane + f * (size_t)h * ws, ws}; }
-    __device__ __forceinline__ unsigned long long pack(int y, int x0) const
+    const unsigned long long *plane; int tc; size_t plane_words;
+    __device__ __forceinline__ BitSrc frame(size_t f, int) const { return BitSrc{plane + f * plane_words, tc, plane_words}; }
+    // x0: a multiple of 64
+    __device__ __forceinline__ unsigned long long pack(int y, int x0) const { return plane[bit_word(tc, y, x0 >> 6)]; }
+    __device__ __forceinline__ bool px(int y, int x) const { return (plane[bit_word(tc, y, x >> 6)] >> (x & 63)) & 1ull; }
+    // a strip is one tile: its 8 rows in four 16-byte loads (rows outside ya .. yb are left in, the walks skip them)
+    __device__ __forceinline__ void strip(int y8, int, int, int x0, unsigned long long (&m)[CCL_STRIP]) const
     {
-        typedef unsigned long long u64a4 __attribute__((aligned(4)));
-        return *reinterpret_cast<const u64a4 *>(plane + (size_t)y * ws + (x0 >> 5) + 1);
+        typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+        const u64x2 *t = reinterpret_cast<const u64x2 *>(plane + bit_word(tc, y8, x0 >> 6));
+#pragma unroll
+        for (int q = 0; q < 4; q++) { const u64x2 v = t[q]; m[2 * q] = v.x; m[2 * q + 1] = v.y; }
     }
-    __device__ __forceinline__ bool px(int y, int x) const { return (plane[(size_t)y * ws + ((x + 32) >> 5)] >> ((x + 32) & 31)) & 1u; }
+    __device__ __forceinline__ unsigned colbits(int y8, int ya, int yb, int x) const
+    {
+        unsigned long long m[CCL_STRIP];
+        strip(y8, ya, yb, x & ~63, m);
+        unsigned b = 0;
+#pragma unroll
+        for (int k = 0; k < CCL_STRIP; k++) b |= (unsigned)((m[k] >> (x & 63)) & 1ull) << k;
+        return b;
+    }
 };
 
 // labels of a sparse pass: every pixel of the set points at the first pixel of its run inside the word; a run that
@@ -219,11 +249,21 @@ __global__ __launch_bounds__(256) void k_ccl_init64(SRC src0, int h, int w,
     int *Lf = L + f * N;
     const unsigned long long cmask = col_mask64(x0, r.x0, r.x1);
     const bool hasL = x0 - 1 >= r.x0;
-    for (int y = ya; y <= yb; y++) {
-        unsigned long long m = src.pack(y, x0) & cmask;
+    const int y8 = sy * CCL_STRIP;
+    unsigned long long rows[CCL_STRIP], any = 0;
+    src.strip(y8, ya, yb, x0, rows);
+#pragma unroll
+    for (int k = 0; k < CCL_STRIP; k++) any |= (y8 + k >= ya && y8 + k <= yb) ? rows[k] & cmask : 0ull;
+    // the left neighbours only matter for a run that starts in column 0 of the word
+    const unsigned lb = (hasL && (any & 1ull)) ? src.colbits(y8, ya, yb, x0 - 1) : 0u;
+#pragma unroll
+    for (int k = 0; k < CCL_STRIP; k++) {
+        const int y = y8 + k;
+        if (y < ya || y > yb) continue;
+        unsigned long long m = rows[k] & cmask;
         if (!m) continue;
         const int base = y * w + x0;
-        const bool cL = (m & 1ull) && hasL && src.px(y, x0 - 1);
+        const bool cL = (m & 1ull) && ((lb >> k) & 1u);
         while (m) {
             const unsigned long long low = m & (0ull - m), run = m & ~(m + low);
             const int a = __ffsll((long long)low) - 1, e = a + __popcll(run);
@@ -259,11 +299,27 @@ __global__ __launch_bounds__(256) void k_ccl_merge64(SRC src0, int h, int w,
     int *Lf = L + f * N;
     const unsigned long long cmask = col_mask64(x0, r.x0, r.x1);
     const bool hasL = x0 - 1 >= r.x0, hasR = x0 + 64 <= r.x1;
-    unsigned long long A = src.pack(ya - 1, x0) & cmask;
-    unsigned long long aL = (hasL && src.px(ya - 1, x0 - 1)) ? 1ull : 0ull, aR = (hasR && src.px(ya - 1, x0 + 64)) ? 1ull : 0ull;
-    for (int y = ya; y <= yb; y++) {
-        const unsigned long long C = src.pack(y, x0) & cmask;
-        const unsigned long long cL = (hasL && src.px(y, x0 - 1)) ? 1ull : 0ull, cR = (hasR && src.px(y, x0 + 64)) ? 1ull : 0ull;
+    // rows ya - 1 .. yb: the strip's tile, and the row above it when ya is the strip's first row
+    const int y8 = sy * CCL_STRIP;
+    unsigned long long rows[CCL_STRIP], any = 0;
+    src.strip(y8, ya - 1, yb, x0, rows);
+#pragma unroll
+    for (int k = 0; k < CCL_STRIP; k++) any |= (y8 + k >= ya - 1 && y8 + k <= yb) ? rows[k] & cmask : 0ull;
+    // the neighbour columns only enter at bit 0 (left) / bit 63 (right) of a row of the strip
+    const unsigned lb = (hasL && (any & 1ull)) ? src.colbits(y8, ya - 1, yb, x0 - 1) : 0u;
+    const unsigned rb = (hasR && (any >> 63)) ? src.colbits(y8, ya - 1, yb, x0 + 64) : 0u;
+    unsigned long long A = 0, aL = 0, aR = 0;
+    if (ya == y8) {
+        A = src.pack(ya - 1, x0) & cmask;
+        aL = (hasL && src.px(ya - 1, x0 - 1)) ? 1ull : 0ull; aR = (hasR && src.px(ya - 1, x0 + 64)) ? 1ull : 0ull;
+    }
+#pragma unroll
+    for (int k = 0; k < CCL_STRIP; k++) {
+        const int y = y8 + k;
+        if (y < ya - 1 || y > yb) continue;
+        const unsigned long long C = rows[k] & cmask;
+        const unsigned long long cL = (lb >> k) & 1u, cR = (rb >> k) & 1u;
+        if (y == ya - 1) { A = C; aL = cL; aR = cR; continue; }
         if (C) {
             const unsigned long long Cs = (C << 1) | cL, As = (A << 1) | aL;            // left, up-left
             const int base = y * w + x0;
@@ -302,12 +358,22 @@ __global__ __launch_bounds__(256) void k_ccl_roots64(SRC src0, int h, int w,
     const int ya = live ? max(sy * CCL_STRIP, r.y0) : 0, yb = live ? min(sy * CCL_STRIP + CCL_STRIP - 1, r.y1) : -1;
     const unsigned long long cmask = live ? col_mask64(x0, r.x0, r.x1) : 0ull;
     const bool hasL = live && x0 - 1 >= r.x0;
+    const int y8 = sy * CCL_STRIP;
+    unsigned long long rows[CCL_STRIP], any = 0;
+    unsigned lb = 0;
+    if (live) {
+        src.strip(y8, ya, yb, x0, rows);
+#pragma unroll
+        for (int k = 0; k < CCL_STRIP; k++) any |= (y8 + k >= ya && y8 + k <= yb) ? rows[k] & cmask : 0ull;
+        if (hasL && (any & 1ull)) lb = src.colbits(y8, ya, yb, x0 - 1);
+    }
+#pragma unroll
     for (int k = 0; k < CCL_STRIP; k++) {     // wave-uniform trip count: the appends below are wavefront collectives
-        const int y = ya + k;
+        const int y = y8 + k;
         unsigned long long starts = 0;
-        if (y <= yb) {
-            const unsigned long long C = src.pack(y, x0) & cmask;
-            const unsigned long long cL = (C & 1ull) && hasL && src.px(y, x0 - 1) ? 1ull : 0ull;
+        if (live && y >= ya && y <= yb) {
+            const unsigned long long C = rows[k] & cmask;
+            const unsigned long long cL = (C & 1ull) && ((lb >> k) & 1u) ? 1ull : 0ull;
             starts = C & ~((C << 1) | cL);
         }
         while (__ballot(starts != 0)) {
@@ -525,20 +591,22 @@ __global__ void k_ccl_ctl(FrameState *st, int *nrect, int n, int h, int w, int o
     // op 3: keep crect (a superset of the next, smaller set), accumulator already empty
 }
 
+// Writers of the tiled one-bit planes (cpe_dev.h).  Every row of a plane's last tile row is written, the rows >= h as zeros,
+// and so are the two zero tile columns.
+
 // one wavefront per 512 pixels of a row (8 groups of 64): a ballot per threshold is the 64-bit group of that plane; lane t
-// collects plane t's eight groups and writes them as 64 contiguous bytes
+// collects plane t's eight groups.  rows_total = n * 8 ceil(h / 8) (the padding rows included)
 __global__ __launch_bounds__(256) void k_bitplanes(const uint8_t *__restrict__ img, int rows_total, int h, int w, int thr0, int step,
-                                                   int nplanes, uint32_t *__restrict__ planes)
+                                                   int nplanes, unsigned long long *__restrict__ planes)
 {
     const int lane = threadIdx.x & 63;
-    const int chunks = (w + 63) >> 6, groups = (chunks + 7) >> 3;
+    const int chunks = (w + 63) >> 6, groups = (chunks + 7) >> 3, tc = bit_tile_cols(w), hp = (h + 7) & ~7;
     const long long gw = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= (long long)rows_total * groups) return;
     const int row = (int)(gw / groups), g = (int)(gw - (long long)row * groups);
-    const int f = row / h, y = row - f * h;
-    const int ws = bit_row_words(w);
-    const size_t plane_words = (size_t)h * ws;
-    uint32_t *out = planes + (size_t)f * nplanes * plane_words + (size_t)y * ws;
+    const int f = row / hp, y = row - f * hp;
+    const size_t plane_words = bit_plane_words(h, w);
+    unsigned long long *out = planes + (size_t)f * nplanes * plane_words;
     unsigned long long mine[8];
     const int c0 = g * 8, nc = min(8, chunks - c0);
 #pragma unroll
@@ -546,7 +614,7 @@ __global__ __launch_bounds__(256) void k_bitplanes(const uint8_t *__restrict__ i
         mine[q] = 0;
         if (q < nc) {
             const int x = (c0 + q) * 64 + lane;
-            const int v = x < w ? (int)img[(size_t)row * w + x] : -1;
+            const int v = (x < w && y < h) ? (int)img[((size_t)f * h + y) * w + x] : -1;
             for (int t = 0; t < nplanes; t++) {
                 unsigned long long b = __ballot(v > thr0 + t * step);
                 if (lane == t) mine[q] = b;
@@ -554,64 +622,72 @@ __global__ __launch_bounds__(256) void k_bitplanes(const uint8_t *__restrict__ i
         }
     }
     if (lane < nplanes) {
-        uint32_t *o = out + (size_t)lane * plane_words;
+        unsigned long long *o = out + (size_t)lane * plane_words;
 #pragma unroll
         for (int q = 0; q < 8; q++)
-            if (q < nc) { o[1 + 2 * (c0 + q)] = (uint32_t)mine[q]; o[2 + 2 * (c0 + q)] = (uint32_t)(mine[q] >> 32); }
-        if (g == 0) o[0] = 0;
-        if (g == groups - 1) for (int k = 1 + 2 * chunks; k < ws; k++) o[k] = 0;
+            if (q < nc) o[bit_word(tc, y, c0 + q)] = mine[q];
+        if (g == 0) o[bit_word(tc, y, -1)] = 0ull;
+        if (g == groups - 1) o[bit_word(tc, y, chunks)] = 0ull;
     }
 }
 
 // the same planes when rows start on 16-byte boundaries: a thread loads 64 pixels once (4 x 16 bytes) and makes their word of
-// every plane with SWAR compares -- no ballots, 16 times fewer load instructions
-__global__ __launch_bounds__(256) void k_bitplanes64(const uint8_t *__restrict__ img, int rows_total, int h, int w, int thr0, int step,
-                                                     int nplanes, uint32_t *__restrict__ planes)
+// every plane with SWAR compares -- no ballots, 16 times fewer load instructions.  Thread order (frame, tile row, word
+// column, row in the tile): 8 consecutive lanes write one whole tile of every plane.  A word column's threads of tile
+// column 0 / the last one also write those (zero) tiles.
+__global__ __launch_bounds__(256) void k_bitplanes64(const uint8_t *__restrict__ img, int n, int h, int w, int thr0, int step,
+                                                     int nplanes, unsigned long long *__restrict__ planes)
 {
-    const int chunks = (w + 63) >> 6;
+    const int chunks = (w + 63) >> 6, tc = bit_tile_cols(w), th = (h + 7) >> 3;
     const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (gi >= (long long)rows_total * chunks) return;
-    const int row = (int)(gi / chunks), j = (int)(gi - (long long)row * chunks);
-    const int f = row / h, y = row - f * h;
-    const int ws = bit_row_words(w);
-    const size_t plane_words = (size_t)h * ws;
-    uint32_t *out = planes + (size_t)f * nplanes * plane_words + (size_t)y * ws;
-    const uint8_t *p = img + (size_t)row * w + j * 64;
+    if (gi >= (long long)n * th * chunks * 8) return;
+    const int r = (int)(gi & 7);
+    const long long tile = gi >> 3;
+    const int j = (int)(tile % chunks);
+    const long long ft = tile / chunks;
+    const int f = (int)(ft / th), y = (int)(ft - (long long)f * th) * 8 + r;
+    const size_t plane_words = bit_plane_words(h, w);
+    unsigned long long *out = planes + (size_t)f * nplanes * plane_words;
     unsigned long long v[8];
+    const uint8_t *p = img + ((size_t)f * h + y) * w + j * 64;
 #pragma unroll
     for (int c = 0; c < 4; c++) {
         uint4 q = make_uint4(0, 0, 0, 0);
-        if (j * 64 + 16 * c < w) q = *reinterpret_cast<const uint4 *>(p + 16 * c);   // w % 16 == 0: all 16 inside
+        if (y < h && j * 64 + 16 * c < w) q = *reinterpret_cast<const uint4 *>(p + 16 * c);   // w % 16 == 0: all 16 inside
         v[2 * c] = q.x | ((unsigned long long)q.y << 32);
         v[2 * c + 1] = q.z | ((unsigned long long)q.w << 32);
     }
-    // pixels past the end of the row were loaded as 0 and every threshold is >= 0: their bits stay clear
+    // pixels past the end of the row (and rows past the image) were loaded as 0 and every threshold is >= 0: their bits stay clear
+    const size_t wi = bit_word(tc, y, j);
     for (int t = 0; t < nplanes; t++) {
         const int thr = thr0 + t * step;
         unsigned long long bits = 0;
 #pragma unroll
         for (int c = 0; c < 8; c++) bits |= (unsigned long long)pack8_gt(v[c], thr, 0) << (8 * c);
-        uint32_t *o = out + (size_t)t * plane_words;
-        o[1 + 2 * j] = (uint32_t)bits;
-        o[2 + 2 * j] = (uint32_t)(bits >> 32);
-        if (j == 0) o[0] = 0;
-        if (j == chunks - 1) for (int k = 1 + 2 * chunks; k < ws; k++) o[k] = 0;
+        unsigned long long *o = out + (size_t)t * plane_words;
+        o[wi] = bits;
+        if (j == 0) o[wi - 8] = 0ull;
+        if (j == chunks - 1) o[wi + 8] = 0ull;
     }
 }
 
-// single plane (mask != 0 / image > thr): one thread per 8 pixels = one byte of the plane (pixel x is bit (x + 32) of its
-// row, so byte 4 + x / 8 holds pixels 8 (x / 8) .. + 7), 64 consecutive bytes per wavefront
-__global__ __launch_bounds__(256) void k_bitplane1(const uint8_t *__restrict__ img, int rows_total, int w, int thr,
-                                                   uint32_t *__restrict__ plane)
+// single plane (mask != 0 / image > thr): one thread per byte of the plane = 8 pixels of one row, 64 consecutive bytes (one
+// tile) per 64 threads
+__global__ __launch_bounds__(256) void k_bitplane1(const uint8_t *__restrict__ img, int n, int h, int w, int thr,
+                                                   unsigned long long *__restrict__ plane)
 {
-    const int ws = bit_row_words(w), wb = ws * 4;             // bytes per plane row
+    const int tc = bit_tile_cols(w);
+    const size_t pb = bit_plane_words(h, w) * 8;      // bytes per plane
     const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (gi >= (long long)rows_total * wb) return;
-    const int row = (int)(gi / wb), j = (int)(gi - (long long)row * wb);
-    const int x0 = (j - 4) * 8;
+    if (gi >= (long long)n * pb) return;
+    const int f = (int)(gi / pb);
+    const int rem = (int)(gi - (long long)f * pb);
+    const int tile = rem >> 6, r = (rem >> 3) & 7, bi = rem & 7;
+    const int ty = tile / tc, tx = tile - ty * tc;
+    const int y = ty * 8 + r, x0 = (tx - 1) * 64 + bi * 8;
     unsigned b = 0;
-    if (j >= 4 && x0 < w) {
-        const uint8_t *p = img + (size_t)row * w + x0;
+    if (tx > 0 && y < h && x0 < w) {     // (x0 >= 0 for tx > 0; the last tile column starts at or past w)
+        const uint8_t *p = img + ((size_t)f * h + y) * w + x0;
         if (x0 + 8 <= w && ((((size_t)p) & 3) == 0)) {
             const uint32_t a = *reinterpret_cast<const uint32_t *>(p), c = *reinterpret_cast<const uint32_t *>(p + 4);
 #pragma unroll
@@ -623,7 +699,7 @@ __global__ __launch_bounds__(256) void k_bitplane1(const uint8_t *__restrict__ i
             for (int k = 0; k < 8 && x0 + k < w; k++) b |= ((int)p[k] > thr ? 1u : 0u) << k;
         }
     }
-    reinterpret_cast<uint8_t *>(plane)[(size_t)row * wb + j] = (uint8_t)b;
+    reinterpret_cast<uint8_t *>(plane)[gi] = (uint8_t)b;
 }
 
 }  // namespace
@@ -632,20 +708,22 @@ int build_bitplanes(const uint8_t *img, int n, int h, int w, int thr0, int step,
 {
     CPE_CHECK_ARG(nplanes >= 1 && nplanes <= 64, "build_bitplanes: 1..64 planes");
     CPE_LAUNCH_BEGIN();
+    unsigned long long *pl = reinterpret_cast<unsigned long long *>(planes);
+    const int th = (h + 7) >> 3;
     if (nplanes == 1) {
-        const long long bytes = (long long)n * h * bit_row_words(w) * 4;
-        CPE_KLAUNCH(k_bitplane1, dim3((unsigned)((bytes + 255) / 256)), dim3(256), 0, s, img, n * h, w, thr0, planes);
+        const long long bytes = (long long)n * bit_plane_words(h, w) * 8;
+        CPE_KLAUNCH(k_bitplane1, dim3((unsigned)((bytes + 255) / 256)), dim3(256), 0, s, img, n, h, w, thr0, pl);
         CPE_CHECK_LAUNCH("k_bitplane1");
         return CPE_OK;
     }
     if (w % 16 == 0 && (((size_t)img) & 15) == 0 && thr0 >= 0 && step >= 0 && thr0 + (nplanes - 1) * step <= 255) {
-        const long long words = (long long)n * h * ((w + 63) >> 6);
-        CPE_KLAUNCH(k_bitplanes64, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, img, n * h, h, w, thr0, step, nplanes, planes);
+        const long long words = (long long)n * th * 8 * ((w + 63) >> 6);
+        CPE_KLAUNCH(k_bitplanes64, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, img, n, h, w, thr0, step, nplanes, pl);
         CPE_CHECK_LAUNCH("k_bitplanes64");
         return CPE_OK;
     }
-    const long long waves = (long long)n * h * ((((w + 63) >> 6) + 7) >> 3);
-    CPE_KLAUNCH(k_bitplanes, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, img, n * h, h, w, thr0, step, nplanes, planes);
+    const long long waves = (long long)n * th * 8 * ((((w + 63) >> 6) + 7) >> 3);
+    CPE_KLAUNCH(k_bitplanes, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, img, n * th * 8, h, w, thr0, step, nplanes, pl);
     CPE_CHECK_LAUNCH("k_bitplanes");
     return CPE_OK;
 }
@@ -731,8 +809,8 @@ __global__ __launch_bounds__(64 * FLOOD_BANDS) void k_outside_flood(const uint8_
     const Rect r = get_rect(st, f, use_rect, h, w);
     if (r.x1 < r.x0 || r.y1 < r.y0) return;
     const uint8_t *im = mask + f * (size_t)h * w;
-    const int bws = bit_row_words(w);
-    const uint32_t *bp = bits ? bits + f * (size_t)h * bws : nullptr;
+    const int btc = bit_tile_cols(w);
+    const unsigned long long *bp = bits ? bit_plane(bits, f, h, w) : nullptr;
     unsigned long long *bgw = bgw_all + f * plane_words, *out = out_all + f * plane_words;
     const int x0 = lane * 64;
     const unsigned long long cmask = lane < WW ? col_mask64(x0, r.x0, r.x1) : 0ull;
@@ -764,8 +842,8 @@ __global__ __launch_bounds__(64 * FLOOD_BANDS) void k_outside_flood(const uint8_
             for (int k = 0; k < CHUNK; k++) {
                 const int y = ya + k0 + k;
                 unsigned long long m = 0;
-                if (lane < WW && k0 + k < mine)    // pixel x is bit x + 32 of its plane row: pixels 64 j .. 64 j + 63 are words 1 + 2 j, 2 + 2 j
-                    m = bp ? *reinterpret_cast<const u64_a4 *>(bp + (size_t)y * bws + 1 + 2 * lane) : pack_nonzero64(im + (size_t)y * w, x0, w);
+                if (lane < WW && k0 + k < mine)
+                    m = bp ? bp[bit_word(btc, y, lane)] : pack_nonzero64(im + (size_t)y * w, x0, w);
                 dst[k] = ~m & cmask;
             }
         };
@@ -910,7 +988,7 @@ int ccl_roots_bits(const uint32_t *bits, int n, int h, int w, int *L, int *roots
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, (int *)nullptr, n, h, w, 0, cnt_sel);
     const dim3 gwords((unsigned)((((w + 63) / 64) * ((h + CCL_STRIP - 1) / CCL_STRIP) + 255) / 256), n);
-    const BitSrc src{bits, bit_row_words(w)};
+    const BitSrc src{bit_plane(bits, 0, h, w), bit_tile_cols(w), bit_plane_words(h, w)};
     CPE_KLAUNCH(k_ccl_init64<BitSrc>, gwords, dim3(256), 0, s, src, h, w, (const FrameState *)st, use_rect, L);
     CPE_KLAUNCH(k_ccl_merge64<BitSrc>, gwords, dim3(256), 0, s, src, h, w, 1, (const FrameState *)st, use_rect, L);
     CPE_KLAUNCH(k_ccl_roots64<BitSrc>, gwords, dim3(256), 0, s, src, h, w, st, use_rect, (const int *)L, roots, cnt_sel);

@@ -214,50 +214,82 @@ __device__ __forceinline__ unsigned nbr_mask(Pred &nz, int x, int y)
            (b6 ? 64u : 0u) | (b7 ? 128u : 0u);
 }
 
-// 1-bit planes for border following.  A row is `bit_row_words(w)` u32 words; pixel x is bit (x + 32) of its row: one
-// zero word on the left and at least two on the right, so every 64-column window that starts on a word boundary is
-// one 8-byte load and never wraps into the next row.  BitWin keeps a 16-row x 64-column window around the current
-// border pixel in LDS (one column of `win` per lane): a border step costs three LDS reads, and global memory is
-// touched only when the border leaves the window (every ~10 steps) instead of eight dependent loads per step.
+// 1-bit planes (threshold images, single masks) in 64 x 8 tiles.  A tile is 8 consecutive u64 words = one 64-byte line:
+// word r of tile (ty, tx) holds row 8 ty + r, its bit i pixel 64 (tx - 1) + i.  Tile columns 0 and bit_tile_cols(w) - 1 and
+// the rows >= h of the last tile row are zero, so a 64-column window that starts on a 32-column boundary is one or two
+// words of one row and never needs a horizontal bounds test.  Rows y .. y + 7 of 64 columns are one line: the word-level
+// walks read 8 rows with one request, a 16-row tracer window is 2-4 lines (16 in the row-major layout this replaced).
+// Planes are multiples of 64 bytes; the workspace keeps their bases 256-byte aligned, so every tile is one line.
+__host__ __device__ inline int bit_tile_cols(int w) { return ((w + 63) >> 6) + 2; }
+__host__ __device__ inline size_t bit_plane_words(int h, int w) { return (size_t)((h + 7) >> 3) * bit_tile_cols(w) * 8; }   // u64 words
+// index of the word with pixels 64 j .. 64 j + 63 of row y (0 <= y < 8 ceil(h / 8); j = -1 and j = ceil(w / 64) are the
+// zero columns), tc = bit_tile_cols(w)
+__host__ __device__ inline size_t bit_word(int tc, int y, int j) { return ((size_t)(y >> 3) * tc + (j + 1)) * 8 + (y & 7); }
+// plane i of a run of planes that starts at `base`
+__host__ __device__ inline const unsigned long long *bit_plane(const uint32_t *base, size_t i, int h, int w)
+{
+    return reinterpret_cast<const unsigned long long *>(base) + i * bit_plane_words(h, w);
+}
+__host__ __device__ inline unsigned long long *bit_plane(uint32_t *base, size_t i, int h, int w)
+{
+    return reinterpret_cast<unsigned long long *>(base) + i * bit_plane_words(h, w);
+}
+
+// BitWin keeps a 16-row x 64-column window of a plane around the current border pixel in LDS (one column of `win` per
+// lane): a border step costs three LDS reads, and global memory is touched only when the border leaves the window (every
+// ~10 steps) instead of eight dependent loads per step.  The window starts on a tile row and on a 32-column boundary: a
+// refill reads the 2 tiles of one tile column, or 4 when it straddles two (the halves are funnel-shifted together).
 constexpr int BW_ROWS = 16;
-__host__ __device__ inline int bit_row_words(int w) { return ((w + 31) >> 5) + 4; }
-typedef unsigned long long u64_a4 __attribute__((aligned(4)));
 struct BitWin {
-    const uint32_t *plane;       // this frame's plane
-    int ws, h;
+    const unsigned long long *plane;   // this frame's plane
+    int w, h;
     unsigned long long *win;     // LDS, row r of this lane at win[r * 64]
-    int wx0 = 0, wy0 = INT_MIN / 2;   // padded bit index of window column 0, image row of window row 0
-    // (re)fill the window around (x, y).  The window is put ahead of the border's direction of travel: leaving through
-    // the top / bottom row puts the pixel on the bottom / top side of the new window, leaving through the left / right
-    // columns puts it on the right / left side -- borders keep their heading for a while, so a refill lasts about
-    // twice as many steps as a centred window.
-    __device__ __forceinline__ void load(int x, int y, int row_in_win, int col_lo)
+    int wx0 = 0, wy0 = INT_MIN / 2;   // pixel column of window column 0 (a multiple of 32), image row of window row 0 (a multiple of 8)
+    // (re)fill the window around (x, y): the pixel lands in rows row_lo .. row_lo + 7 and columns col_lo .. col_lo + 31.  The
+    // window is put ahead of the border's direction of travel: leaving through the top / bottom row puts the pixel on the
+    // bottom / top side of the new window, leaving through the left / right columns puts it on the right / left side --
+    // borders keep their heading for a while, so a refill lasts longer than one of a centred window.
+    __device__ __forceinline__ void load(int x, int y, int row_lo, int col_lo)
     {
-        const int k = (x + 32 - col_lo) >> 5;   // the pixel lands in columns col_lo .. col_lo + 31 of the window
+        typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+        const int k = (x - col_lo) >> 5;   // >= -2: window column 0 is at pixel -64 at the least (tile column 0)
         wx0 = 32 * k;
-        wy0 = y - row_in_win;
+        wy0 = (y - row_lo) & ~7;
+        const int tc = bit_tile_cols(w), th = (h + 7) >> 3, j = k >> 1;
 #pragma unroll
-        for (int r = 0; r < BW_ROWS; r++) {
-            const int yy = wy0 + r;
-            const int cy = min(max(yy, 0), h - 1);
-            unsigned long long v = *(const u64_a4 *)(plane + (size_t)cy * ws + k);
-            win[r * 64] = ((unsigned)yy < (unsigned)h) ? v : 0ull;
+        for (int t = 0; t < 2; t++) {
+            const int ty = (wy0 >> 3) + t;
+            u64x2 v[4];
+            if ((unsigned)ty < (unsigned)th) {
+                const u64x2 *a = reinterpret_cast<const u64x2 *>(plane + ((size_t)ty * tc + j + 1) * 8);
+#pragma unroll
+                for (int q = 0; q < 4; q++) v[q] = a[q];
+                if (k & 1) {   // columns 32 .. 63 of word j, 0 .. 31 of word j + 1 (the next tile; j + 2 <= tc - 1)
+#pragma unroll
+                    for (int q = 0; q < 4; q++) v[q] = (v[q] >> 32) | (a[4 + q] << 32);
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; q++) v[q] = 0ull;   // rows outside the image
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++) { win[(8 * t + 2 * q) * 64] = v[q].x; win[(8 * t + 2 * q + 1) * 64] = v[q].y; }
         }
     }
     __device__ __forceinline__ unsigned nbrs(int x, int y)
     {
-        int p = x + 32 - wx0, r = y - wy0;
+        int p = x - wx0, r = y - wy0;
         if (p < 1 || p > 62 || r < 1 || r > BW_ROWS - 2) {
             const bool fresh = wy0 == INT_MIN / 2;
-            int row = BW_ROWS / 2, col = 16;
+            int row = 4, col = 16;
             if (!fresh) {
-                if (r < 1) row = BW_ROWS - 3;          // heading up
-                else if (r > BW_ROWS - 2) row = 2;     // heading down
-                if (p < 1) col = 29;                   // heading left: columns 29..60 (x + 32 >= 32 keeps k >= 0)
-                else if (p > 62) col = 3;              // heading right: columns 3..34
+                if (r < 1) row = 7;            // heading up: rows 7 .. 14
+                else if (r > BW_ROWS - 2) row = 1;   // heading down: rows 1 .. 8
+                if (p < 1) col = 29;           // heading left: columns 29..60
+                else if (p > 62) col = 3;      // heading right: columns 3..34
             }
             load(x, y, row, col);
-            p = x + 32 - wx0; r = y - wy0;
+            p = x - wx0; r = y - wy0;
         }
         const unsigned ta = (unsigned)(win[(r - 1) * 64] >> (p - 1)) & 7u;   // bit 0: x - 1, bit 1: x, bit 2: x + 1
         const unsigned tb = (unsigned)(win[r * 64] >> (p - 1)) & 7u;
@@ -267,13 +299,14 @@ struct BitWin {
     }
     __device__ __forceinline__ bool operator()(int x, int y) const   // single pixel, straight from the plane
     {
-        if ((unsigned)x >= (unsigned)(32 * (ws - 3)) || (unsigned)y >= (unsigned)h) return false;
-        return (plane[(size_t)y * ws + ((x + 32) >> 5)] >> ((x + 32) & 31)) & 1u;
+        if ((unsigned)x >= (unsigned)w || (unsigned)y >= (unsigned)h) return false;
+        return (plane[bit_word(bit_tile_cols(w), y, x >> 6)] >> (x & 63)) & 1ull;
     }
 };
 __device__ __forceinline__ unsigned nbr_mask(BitWin &bw, int x, int y) { return bw.nbrs(x, y); }
 
-// planes[t] = (img > thr0 + t * step), t < nplanes; plane stride per frame = nplanes_alloc * h * bit_row_words(w)
+// planes[t] = (img > thr0 + t * step), t < nplanes, in the tiled layout above; plane t of frame f is
+// bit_plane(planes, f * nplanes + t, h, w)
 int build_bitplanes(const uint8_t *img, int n, int h, int w, int thr0, int step, int nplanes, uint32_t *planes, hipStream_t s);
 int ccl_roots_bits(const uint32_t *bits, int n, int h, int w, int *L, int *roots, int use_rect, FrameState *st, hipStream_t s, int cnt_sel);
 

@@ -93,11 +93,11 @@ Layout make_layout(int n, int h, int w)
     per[P_ROOTSP] = (size_t)MAXROOTS * sizeof(int);
     per[P_ROOTSS] = (size_t)MAXROOTS * sizeof(int);
     per[P_BEST2] = sizeof(unsigned long long);
-    per[P_HPAR] = (size_t)h * bit_row_words(w) * sizeof(uint32_t);   // (slot re-used) one-bit plane of the joints mask, written by k_open20_joints
+    per[P_HPAR] = bit_plane_words(h, w) * 8;   // (slot re-used) one-bit plane of the joints mask, written by k_open20_joints
     per[P_HTIME] = 16;
     per[P_GMID] = (size_t)(MAXG - MAXG_LDS) * 4 * sizeof(double);   // x, y, r, next group in the grid cell
     per[P_FLJ] = (size_t)2 * h * ((w + 63) / 64) * sizeof(unsigned long long);   // joints chain: background / outer-background bit masks
-    per[P_BITS] = (size_t)17 * h * bit_row_words(w) * sizeof(uint32_t);
+    per[P_BITS] = (size_t)17 * bit_plane_words(h, w) * 8;   // 17 one-bit planes (cpe_dev.h tiled layout)
     per[P_HL] = (size_t)sweep_pool(h, w, SWL_DARK) * sizeof(int2);
     per[P_BL] = (size_t)sweep_pool(h, w, SWL_BRIGHT) * sizeof(int2);
     per[P_SUBPIX] = (size_t)2 * MAXL * 2 * (size_t)(std::max(h, w) + 128) * sizeof(float);
@@ -488,9 +488,9 @@ extern "C" int32_t cpe_debug_external_components(const uint8_t *mask, int32_t n,
     CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int *)nullptr);
     CPE_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)n * sizeof(int), s));
     if ((rc = ccl_run(mask, n, h, w, 0, 0, 1, (int *)(base + L.off[P_LAB0]), roots, false, nullptr, 0, nullptr, 0, nullptr, st, s, 1, 1, 0)) != CPE_OK) return rc;
-    const size_t bit_words = (size_t)n * h * bit_row_words(w), fl_words = (size_t)h * bit_row_words(w) / 2;
-    unsigned long long *bgw = (unsigned long long *)(base + L.off[P_BITS]);
-    unsigned long long *out = (unsigned long long *)((uint32_t *)(base + L.off[P_BITS]) + ((bit_words + 1) & ~(size_t)1));
+    const size_t fl_words = bit_plane_words(h, w);   // u64 words per frame of a flood plane (>= h * ceil(w / 64))
+    unsigned long long *bgw = bit_plane((uint32_t *)(base + L.off[P_BITS]), 0, h, w);
+    unsigned long long *out = bit_plane((uint32_t *)(base + L.off[P_BITS]), n, h, w);
     if ((rc = outside_flood(mask, n, h, w, st, 0, bgw, out, fl_words, s)) != CPE_OK) return rc;
     CPE_KLAUNCH(k_list_external, dim3(32, n), dim3(256), 0, s, (const int *)roots, (const FrameState *)st, w, (const unsigned long long *)out, fl_words,
                 first_px, cap, count);

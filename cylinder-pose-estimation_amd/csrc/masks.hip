@@ -68,6 +68,21 @@ __device__ __forceinline__ unsigned long long bytes_of_bits8(unsigned bits)   //
     return v * 255ull;
 }
 
+// rows y0 .. y0 + R - 1 (y0, R: multiples of 8) of a tiled one-bit plane (cpe_dev.h), word(tr, j) = row y0 + tr, pixels
+// 64 j .. 64 j + 63: whole tiles, 8 consecutive threads of the workgroup (256 threads) per 64-byte tile.  The zero tile
+// columns and the rows >= h of the last tile row are written as zeros.
+template <class Word>
+__device__ __forceinline__ void store_plane_band(unsigned long long *plane, int h, int w, int y0, int R, int t, Word word)
+{
+    const int tc = bit_tile_cols(w);
+    const int rows = min(R, ((h + 7) & ~7) - y0);
+    unsigned long long *o = plane + (size_t)(y0 >> 3) * tc * 8;
+    for (int i = t; i < rows * tc; i += 256) {
+        const int tile = i >> 3, tyl = tile / tc, tx = tile - tyl * tc, tr = tyl * 8 + (i & 7);
+        o[i] = (tx == 0 || tx == tc - 1 || y0 + tr >= h) ? 0ull : word(tr, tx - 1);
+    }
+}
+
 constexpr int OB_AP = 20;
 template <int R>
 __global__ __launch_bounds__(256) void k_open20_joints(const uint8_t *__restrict__ bin, int h, int w, int bands,
@@ -173,24 +188,12 @@ __global__ __launch_bounds__(256) void k_open20_joints(const uint8_t *__restrict
                 }
             }
         }
-        // pixel x is bit x + 32 of its plane row: word 0 and the words behind the last pixel are zero
-        const int ws = bit_row_words(w);
-        for (int i = t; i < R * (WW + 1); i += 256) {
-            const int tr = i / (WW + 1), j = i - tr * (WW + 1);
-            const int y = y0 + tr;
-            if (y >= h) continue;
-            uint32_t *row = jbits + ((size_t)f * h + y) * ws;
-            if (j == WW) {
-                row[0] = 0;
-                for (int k = 1 + 2 * WW; k < ws; k++) row[k] = 0;
-                continue;
-            }
+        store_plane_band(bit_plane(jbits, f, h, w), h, w, y0, R, t, [&](int tr, int j) {
             const size_t wi = (size_t)tr * WW + j;
             unsigned long long m = hbuf[wi] & (buf0[wi] | ((tr + 12 < ROWS) ? buf1[wi + (size_t)12 * WW] : 0ull));
             if (64 * j + 64 > w) m &= (1ull << (w - 64 * j)) - 1ull;      // columns past the end of the row
-            row[1 + 2 * j] = (uint32_t)m;
-            row[2 + 2 * j] = (uint32_t)(m >> 32);
-        }
+            return m;
+        });
     }
 }
 
@@ -249,7 +252,7 @@ __global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m,
                                                   const FrameState *__restrict__ st, uint8_t *__restrict__ roi,
                                                   uint8_t *__restrict__ base, uint32_t *__restrict__ bbits)
 {
-    // bbits: `base` once more as a one-bit plane (build_bitplanes layout, one plane per frame): the words are in LDS anyway,
+    // bbits: `base` once more as a one-bit plane (cpe_dev.h tiled layout, one plane per frame): the words are in LDS anyway,
     // and the fragments' labelling, flood and border tracer read the plane
     extern __shared__ unsigned long long s_rb[];
     const int WW = (w + 63) >> 6;
@@ -274,11 +277,7 @@ __global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m,
             const size_t o = f * N + (size_t)y * w + x0;
             store8(roi, o, x0, 0u); store8(base, o, x0, 0u);
         }
-        const int ws = bit_row_words(w);
-        for (int i = t; i < RB_R * ws; i += 256) {
-            const int tr = i / ws, y = y0 + tr;
-            if (y < h) bbits[((size_t)f * h + y) * ws + (i - tr * ws)] = 0u;
-        }
+        store_plane_band(bit_plane(bbits, f, h, w), h, w, y0, RB_R, t, [](int, int) { return 0ull; });
         return;
     }
     // pack (m & cm & mc) != 0 of the rectangle's pixels; everything else (and outside the image) is zero
@@ -344,23 +343,8 @@ __global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m,
     pass(buf0, buf1, true);    // dilate
     pass(buf1, buf0, false);   // erode -> base
     emit(buf0, base);
-    {   // pixel x is bit x + 32 of its plane row: word 0 and the words behind the last pixel are zero
-        const int ws = bit_row_words(w);
-        for (int i = t; i < RB_R * (WW + 1); i += 256) {
-            const int tr = i / (WW + 1), j = i - tr * (WW + 1);
-            const int y = y0 + tr;
-            if (y >= h) continue;
-            uint32_t *row = bbits + ((size_t)f * h + y) * ws;
-            if (j == WW) {
-                row[0] = 0;
-                for (int k = 1 + 2 * WW; k < ws; k++) row[k] = 0;
-                continue;
-            }
-            const unsigned long long m64 = buf0[(size_t)(tr + RB_AP) * WW + j];     // (columns past the row's end are 0: row_valid_word)
-            row[1 + 2 * j] = (uint32_t)m64;
-            row[2 + 2 * j] = (uint32_t)(m64 >> 32);
-        }
-    }
+    // (columns past the row's end are 0: row_valid_word)
+    store_plane_band(bit_plane(bbits, f, h, w), h, w, y0, RB_R, t, [&](int tr, int j) { return buf0[(size_t)(tr + RB_AP) * WW + j]; });
 }
 
 // ---- joints: polygon-moment centroids inside the region rectangle, in cv2.findContours order ----------
@@ -376,8 +360,7 @@ __global__ __launch_bounds__(64) void k_joint_centroids(const uint32_t *__restri
     for (int k = blockIdx.x * 64 + threadIdx.x; k < ncomp; k += gridDim.x * 64) {
         const int root = roots[(size_t)f * MAXROOTS + k];
         if (!comp_is_external(outside + f * plane_words, w, root, 0)) continue;   // RETR_EXTERNAL (:1817): inside a hole of another blob
-        const int ws = bit_row_words(w);
-        BitWin nz{jbits + (size_t)f * h * ws, ws, h, s_win + threadIdx.x};
+        BitWin nz{bit_plane(jbits, f, h, w), w, h, s_win + threadIdx.x};
         StatVisitor sv;
         if (!trace_border(nz, root % w, root / w, false, sv, 4 * (w + h) + 65536)) { set_overflow(st[f], OVF_TRACE); continue; }
         sv.finish();
@@ -1059,8 +1042,7 @@ __global__ __launch_bounds__(64) void k_seg_trace(const uint32_t *__restrict__ b
     for (int k = blockIdx.x * SEG_LPW + threadIdx.x; k < ncomp; k += gridDim.x * SEG_LPW) {
     const int root = roots[(size_t)f * MAXROOTS + k];
     if (!comp_is_external(outside + f * plane_words, w, root, window_x0(st[f], 2))) continue;   // RETR_EXTERNAL (:161)
-    const int ws = bit_row_words(w);
-    BitWin nz{base_bits + (size_t)f * h * ws, ws, h, s_win + threadIdx.x};
+    BitWin nz{bit_plane(base_bits, f, h, w), w, h, s_win + threadIdx.x};
     float *pts = s_pts[threadIdx.x];     // the border's vertices live in LDS: 1.6 KB (5.6 KB planar) per lane were scratch
     SegVisitor sv{pts, MAXVS};
     if (!trace_border(nz, root % w, root / w, false, sv, 8 * (w + h) + (1 << 20))) { set_overflow(st[f], OVF_TRACE); continue; }
@@ -1403,9 +1385,8 @@ int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, 
     CPE_KLAUNCH(k_masks_reset, dim3((n + 63) / 64), dim3(64), 0, s, st, n);
     // scratch of the RETR_EXTERNAL tests: u64 planes carved from the one-bit planes the region stage is done with
     // (planes 0 and 1 hold the fragment masks below; a u64 plane of h * ceil(w/64) words fits one bit plane)
-    const size_t bit_words = (size_t)n * h * bit_row_words(w);
-    const size_t fl_words = (size_t)h * bit_row_words(w) / 2;          // u64 words per frame of one flood plane
-    auto fl_plane = [&](int k) { return reinterpret_cast<unsigned long long *>(B.bits + (size_t)(2 + k) * ((bit_words + 1) & ~(size_t)1)); };
+    const size_t fl_words = bit_plane_words(h, w);          // u64 words per frame of one flood plane = of one bit plane
+    auto fl_plane = [&](int k) { return bit_plane(B.bits, (size_t)(2 + k) * n, h, w); };
     // joints (their outer-background mask comes from the joints chain).  Only the lines kernel reads them: with helper
     // streams they are collected on `sj` beside the two fragment chains instead of in front of them
     const bool jside = side && sj != s;
@@ -1432,7 +1413,7 @@ int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, 
         uint8_t *tmp = which ? B.tmpA : B.tmpB;
         int *lab = which ? B.lab_s : B.lab, *roots = which ? B.roots_s : B.roots;
         const int sel = which ? 2 : 0;
-        uint32_t *bits = B.bits + (which ? bit_words : 0);
+        uint32_t *bits = reinterpret_cast<uint32_t *>(bit_plane(B.bits, which ? (size_t)n : 0, h, w));
         SegRec *segs = B.segs + (size_t)which * n * MAXSEG;
         // roi = open3x3(mask & circle_mask & mask_contour), base = close3x3(roi)
         CPE_KLAUNCH(k_roi_base, dim3((unsigned)(n * rb_bands)), dim3(256), rb_lds, q, lm, (const uint8_t *)B.cm, (const uint8_t *)B.mc,

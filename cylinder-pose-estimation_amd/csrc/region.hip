@@ -366,8 +366,7 @@ __device__ __forceinline__ void blob_trace_one(int f, int slot, int k, int h, in
     BlobRec *blobs = blobs_all + ((size_t)f * NTHR + slot) * MAXB;
     int y0 = root / w, x0 = root - y0 * w;
     if (is_hole) x0 -= 1;
-    const int ws = bit_row_words(w);
-    BitWin nz{bits + ((size_t)f * NTHR + slot) * h * ws, ws, h, s_win + threadIdx.x};   // binarised = cl > 50 + 10 slot
+    BitWin nz{bit_plane(bits, (size_t)f * NTHR + slot, h, w), w, h, s_win + threadIdx.x};   // binarised = cl > 50 + 10 slot
     const int max_steps = 4 * (w + h) + 65536;
     StoreVisitor tv;
     tv.pool = pool_all + ((size_t)f * NTHR + slot) * maxch * 32;
@@ -1213,10 +1212,9 @@ __device__ __forceinline__ void sw_unite_body(const SwBlock vb, const uint32_t *
     const int nb = S[SW_BS + bucket];
     const int *list = bk + f * N + S[SW_BO + bucket];
     const SwRect r = sw_rect(st, f);
-    const int ws = bit_row_words(w);
-    const size_t plane_words = (size_t)h * ws;
-    const uint32_t *bm = bits + (f * NTHR + pm) * plane_words;
-    const uint32_t *bo = bits + (f * NTHR + (po < 0 ? pm : po)) * plane_words;
+    const int tc = bit_tile_cols(w);
+    const unsigned long long *bm = bit_plane(bits, f * NTHR + pm, h, w);
+    const unsigned long long *bo = bit_plane(bits, f * NTHR + (po < 0 ? pm : po), h, w);
     constexpr int FS = DARK ? 1 : 2;              // ints per forest node (the bright forest: {parent, merge-history word})
     int *Pf = P + f * N * FS;
     // A pair of adjacent members is united by the newer pixel (the later one in raster order when both are new).
@@ -1239,14 +1237,16 @@ __device__ __forceinline__ void sw_unite_body(const SwBlock vb, const uint32_t *
         if (i >= 0) {
             const int y = i / w, x = i - y * w;
             const bool Lb = x > r.x0, Rb = x < r.x1, Ub = y > r.y0, Db = y < r.y1;
-            // three-column windows (bit 0: x - 1, bit 1: x, bit 2: x + 1; pixel x is bit x + 32 of its plane row) of the rows
-            // y - 1 .. y + 1; columns / rows outside the rectangle are never members
-            const int sh = (x + 31) & 31;
-            const size_t wo = (size_t)y * ws + ((x + 31) >> 5);
+            // three-column windows (bit 0: x - 1, bit 1: x, bit 2: x + 1) of the rows y - 1 .. y + 1 (cpe_dev.h tiled planes:
+            // one line in 6 of 8 rows); columns / rows outside the rectangle are never members.  Pixel x - 1 is bit sh of
+            // word j; x + 1 is in word j + 1 when sh > 61 (j = -1 and the word past the last pixel are zero columns)
+            const int sh = (x - 1) & 63, j = (x - 1) >> 6;
             const unsigned cm = (Lb ? 1u : 0u) | 2u | (Rb ? 4u : 0u);
-            auto win = [&](const uint32_t *pl, long long drow) -> unsigned {
-                const unsigned long long v = *reinterpret_cast<const u64_a4 *>(pl + wo + drow * ws);
-                const unsigned b = (unsigned)(v >> sh);
+            auto win = [&](const unsigned long long *pl, int dy) -> unsigned {
+                const size_t wi = bit_word(tc, y + dy, j);
+                unsigned long long v = pl[wi] >> sh;
+                if (sh > 61) v |= pl[wi + 8] << (64 - sh);
+                const unsigned b = (unsigned)v;
                 return (DARK ? ~b : b) & cm;
             };
             const unsigned mu = Ub ? win(bm, -1) : 0u, mc = win(bm, 0), md = Db ? win(bm, 1) : 0u;
@@ -1571,7 +1571,6 @@ __global__ __launch_bounds__(64) void k_region_area(const uint32_t *__restrict__
     __shared__ unsigned long long s_win[BW_ROWS * 64];
     const int f = blockIdx.y;
     const int ncomp = min(st[f].n_roots, MAXROOTS);
-    const int ws = bit_row_words(w);
     if (single_is_positive && ncomp == 1) {
         // the usual case of the disc union: one component, so there is nothing to compare and its 3000-step border (one
         // lane, ~1.7 us per step: 5 ms on the critical path of a call) need not be walked.  Its area is positive: a
@@ -1581,7 +1580,7 @@ __global__ __launch_bounds__(64) void k_region_area(const uint32_t *__restrict__
     }
     for (int k = blockIdx.x * 64 + threadIdx.x; k < ncomp; k += gridDim.x * 64) {   // components in turns, one per lane
         const int root = roots[(size_t)f * MAXROOTS + k];
-        BitWin nz{ext_bits + (size_t)f * h * ws, ws, h, s_win + threadIdx.x};
+        BitWin nz{bit_plane(ext_bits, f, h, w), w, h, s_win + threadIdx.x};
         StatVisitor sv;
         if (!trace_border(nz, root % w, root / w, false, sv, 8 * (w + h) + (1 << 20))) { set_overflow(st[f], OVF_TRACE); continue; }
         sv.finish();
@@ -1664,14 +1663,15 @@ __global__ __launch_bounds__(256) void k_hull_fill(const uint32_t *__restrict__ 
     __shared__ uint8_t s_keep[2 * HULL_LDS_W + 2];
     if (t == 0) { s_box[0] = INT_MAX; s_box[1] = INT_MIN; s_box[2] = INT_MAX; s_box[3] = INT_MIN; }
     __syncthreads();
-    const int ws = bit_row_words(w);
     // One component in the mask (the usual case): the column extents of the contour are the column extents of the mask (the
     // top / bottom pixel of a column has only background above / below it up to the frame border, so it lies on the outer
     // border), found by all threads from the bit plane instead of one lane walking the border.
     const bool single = S.n_roots == 1;
     if (single) {
-        const uint32_t *plane = ext_bits + (size_t)f * h * ws;
-        const int nwc = (w + 31) >> 5;              // word columns that hold pixels: words 1 .. nwc of a row
+        // u32 word columns of the tiled plane (cpe_dev.h): column j = pixels 32 j .. 32 j + 31, half j & 1 of u64 word j >> 1
+        const uint32_t *plane = reinterpret_cast<const uint32_t *>(bit_plane(ext_bits, f, h, w));
+        const int nwc = (w + 31) >> 5, tc = bit_tile_cols(w);
+        auto col = [&](int j, int y) { return plane[2 * bit_word(tc, y, j >> 1) + (j & 1)]; };
         constexpr int SEG = 4;                      // row segments per word column
         for (int item = t; item < nwc * SEG; item += 256) {
             const int j = item % nwc, seg = item / nwc;
@@ -1682,7 +1682,7 @@ __global__ __launch_bounds__(256) void k_hull_fill(const uint32_t *__restrict__ 
             for (int yb = y0; yb < y1; yb += HB) {
                 uint32_t v[HB];
 #pragma unroll
-                for (int k = 0; k < HB; k++) v[k] = yb + k < y1 ? plane[(size_t)(yb + k) * ws + 1 + j] : 0u;
+                for (int k = 0; k < HB; k++) v[k] = yb + k < y1 ? col(j, yb + k) : 0u;
 #pragma unroll
                 for (int k = 0; k < HB; k++) {
                     uint32_t nw = v[k] & ~seen;
@@ -1694,7 +1694,7 @@ __global__ __launch_bounds__(256) void k_hull_fill(const uint32_t *__restrict__ 
             for (int yb = y1 - 1; yb >= y0; yb -= HB) {
                 uint32_t v[HB];
 #pragma unroll
-                for (int k = 0; k < HB; k++) v[k] = yb - k >= y0 ? plane[(size_t)(yb - k) * ws + 1 + j] : 0u;
+                for (int k = 0; k < HB; k++) v[k] = yb - k >= y0 ? col(j, yb - k) : 0u;
 #pragma unroll
                 for (int k = 0; k < HB; k++) {
                     uint32_t nw = v[k] & ~seen;
@@ -1716,7 +1716,7 @@ __global__ __launch_bounds__(256) void k_hull_fill(const uint32_t *__restrict__ 
         HullVisitor hv{lo, hi};
         if (single) { hv.minx = s_box[0]; hv.maxx = s_box[1]; hv.miny = s_box[2]; hv.maxy = s_box[3]; }
         else {
-            BitWin nz{ext_bits + (size_t)f * h * ws, ws, h, s_win};
+            BitWin nz{bit_plane(ext_bits, f, h, w), w, h, s_win};
             trace_border(nz, root % w, root / w, false, hv, 8 * (w + h) + (1 << 20));
             s_box[0] = hv.minx; s_box[1] = hv.maxx; s_box[2] = hv.miny; s_box[3] = hv.maxy;
         }

@@ -11,7 +11,7 @@ struct ProbeWin : BitWin {
 };
 __device__ __forceinline__ unsigned nbr_mask(ProbeWin &bw, int x, int y)
 {
-    int p = x + 32 - bw.wx0, r = y - bw.wy0;
+    int p = x - bw.wx0, r = y - bw.wy0;
     if (p < 1 || p > 62 || r < 1 || r > BW_ROWS - 2) {
         long long t0 = clock64();
         unsigned v = bw.nbrs(x, y);
@@ -22,13 +22,13 @@ __device__ __forceinline__ unsigned nbr_mask(ProbeWin &bw, int x, int y)
     return bw.nbrs(x, y);
 }
 
-__global__ void k_probe(const uint32_t *bits, int h, int w, int root, long long *out_all, int lanes)
+__global__ void k_probe(const unsigned long long *bits, int h, int w, int root, long long *out_all, int lanes)
 {
     long long *out = out_all + 8 * blockIdx.x;
     __shared__ unsigned long long s_win[BW_ROWS * 64];
     if ((int)threadIdx.x >= lanes) return;
     ProbeWin nz;
-    nz.plane = bits; nz.ws = bit_row_words(w); nz.h = h; nz.win = s_win + threadIdx.x;
+    nz.plane = bits; nz.w = w; nz.h = h; nz.win = s_win + threadIdx.x;
     StatVisitor sv;
     long long t0 = clock64();
     long long w0 = wall_clock64();
@@ -47,15 +47,15 @@ int main(int argc, char **argv)
     if (!f || fread(&h, 4, 1, f) != 1 || fread(&w, 4, 1, f) != 1) return 1;
     std::vector<uint8_t> m((size_t)h * w);
     if (fread(m.data(), 1, m.size(), f) != m.size()) return 1;
-    const int ws = bit_row_words(w);
-    std::vector<uint32_t> bits((size_t)h * ws, 0);
+    const int tc = bit_tile_cols(w);
+    std::vector<unsigned long long> bits(bit_plane_words(h, w), 0ull);
     int root = -1;
     for (int y = 0; y < h; y++)
         for (int x = 0; x < w; x++)
-            if (m[(size_t)y * w + x]) { bits[(size_t)y * ws + ((x + 32) >> 5)] |= 1u << ((x + 32) & 31); if (root < 0) root = y * w + x; }
-    uint32_t *d; long long *o;
-    hipMalloc(&d, bits.size() * 4); hipMalloc(&o, 64 * 4096);
-    hipMemcpy(d, bits.data(), bits.size() * 4, hipMemcpyHostToDevice);
+            if (m[(size_t)y * w + x]) { bits[bit_word(tc, y, x >> 6)] |= 1ull << (x & 63); if (root < 0) root = y * w + x; }
+    unsigned long long *d; long long *o;
+    hipMalloc(&d, bits.size() * 8); hipMalloc(&o, 64 * 4096);
+    hipMemcpy(d, bits.data(), bits.size() * 8, hipMemcpyHostToDevice);
     const int blocks = argc > 2 ? atoi(argv[2]) : 1, lanes = argc > 3 ? atoi(argv[3]) : 1;
     for (int rep = 0; rep < 3; rep++) {
         hipLaunchKernelGGL(k_probe, dim3(blocks), dim3(64), 0, 0, d, h, w, root, o, lanes);
