@@ -94,8 +94,8 @@ def detect_grid_batch(frames, ws=None, subpixel=False, subpixel_window=7, subpix
         raise TypeError('frames must be a CUDA uint8 tensor [n,h,w] (grey) or [n,h,w,3] (BGR)')
     frames = frames.contiguous()
     colour = frames.dim() == 4
-    if colour and (target != 'cylinder' or subpixel):
-        frames = bgr_to_gray(frames); colour = False       # the planar script / the sub-pixel stage: luma only
+    if colour and subpixel:
+        frames = bgr_to_gray(frames); colour = False       # the sub-pixel stage: luma only
     n, h, w = frames.shape[:3]
     dev = frames.device
     L = _lib.load()

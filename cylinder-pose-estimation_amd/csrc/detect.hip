@@ -260,6 +260,8 @@ __global__ __launch_bounds__(256) void k_bgr2labl(const uint8_t *__restrict__ bg
     }
 }
 __global__ __launch_bounds__(256) void k_bgr2gray(const uint8_t *__restrict__ bgr, size_t npx, uint8_t *__restrict__ gray);
+__global__ __launch_bounds__(256) void k_bgr2gray_any(const uint8_t *__restrict__ bgr, size_t npx, uint8_t *__restrict__ gray,
+                                                      uint8_t *__restrict__ any);
 } }
 
 // the call behind both entry points: grey frames (bgr == null) or true-colour frames (gray == null; the grey plane and the
@@ -276,7 +278,7 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
     CPE_CHECK_ARG(!(prm.target == CPE_TARGET_PLANE && prm.subpixel), "cpe_detect_grid_batch_ex: no sub-pixel refinement for the planar target");
     const int planar = prm.target == CPE_TARGET_PLANE ? 1 : 0;
     CPE_CHECK_ARG((gray || bgr) && xy && id && n_pts && center && status, "cpe_detect_grid_batch: null pointer");
-    CPE_CHECK_ARG(!(bgr && (planar || prm.subpixel)), "cpe_detect_grid_bgr_batch_ex: colour frames: cylinder target without sub-pixel refinement only");
+    CPE_CHECK_ARG(!(bgr && prm.subpixel), "cpe_detect_grid_bgr_batch_ex: colour frames: no sub-pixel refinement");
     CPE_CHECK_ARG(n >= 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096,
                   "cpe_detect_grid_batch: need n>=0 and 64 <= h,w <= 4096 (got %d,%d,%d)", n, h, w);
     if (n == 0) return CPE_OK;
@@ -291,8 +293,10 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
 #define PL(T, p) ((T *)(base + L.off[p]))
     FrameState *st = PL(FrameState, P_STATE);
     // colour input: the grey plane lives in the workspace; the L plane borrows the disc plane of the region stage, which is
-    // first written (cleared) after CLAHE has read L
-    uint8_t *lplane = bgr ? PL(uint8_t, P_EXT) : nullptr;
+    // first written (cleared) after CLAHE has read L.  The planar target reads no L plane: its region stage thresholds the
+    // any-channel plane instead (get_convex_hull of util_plane.py), kept in the CLAHE plane, which that target never uses.
+    uint8_t *lplane = bgr && !planar ? PL(uint8_t, P_EXT) : nullptr;
+    uint8_t *anyplane = bgr && planar ? PL(uint8_t, P_CL) : nullptr;
     if (bgr) gray = PL(uint8_t, P_GRAYIN);
     RegionBuffers R;
     R.cl = PL(uint8_t, P_CL); R.ext = PL(uint8_t, P_EXT); R.mc = PL(uint8_t, P_MASK_CONTOUR); R.touch = PL(uint8_t, P_TOUCH);
@@ -325,7 +329,11 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
         CPE_LAUNCH_BEGIN();
         CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, M.best_s, R.nrect);
         CPE_CHECK_LAUNCH("k_state_init");
-        if (bgr) {      // BGR2GRAY (load_and_preprocess_image, mask_roi_around_center) and the L channel of BGR2LAB (detect_largest_blob)
+        if (bgr && planar) {   // BGR2GRAY and the any-channel threshold of get_convex_hull, from one read of the frame
+            const size_t npx = (size_t)n * h * w;
+            CPE_KLAUNCH(k_bgr2gray_any, dim3((unsigned)(((npx + 3) / 4 + 255) / 256)), dim3(256), 0, s, bgr, npx, PL(uint8_t, P_GRAYIN), anyplane);
+            CPE_CHECK_LAUNCH("colour planes");
+        } else if (bgr) {      // BGR2GRAY (load_and_preprocess_image, mask_roi_around_center) and the L channel of BGR2LAB (detect_largest_blob)
             const size_t npx = (size_t)n * h * w;
             CPE_KLAUNCH(k_bgr2gray, dim3((unsigned)(((npx + 3) / 4 + 255) / 256)), dim3(256), 0, s, bgr, npx, PL(uint8_t, P_GRAYIN));
             CPE_KLAUNCH(k_bgr2labl, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 1 << 16)), dim3(256), 0, s, bgr, npx, lplane);
@@ -346,7 +354,7 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
             CPE_CHECK_HIP(hipEventRecord(X.join2, X.s2));
         }
         RegionSide rside = {X.s3, X.e3a, X.e3b, X.e3c, X.e3d, X.join1, X.join2};
-        if (planar) { if ((rc = region_stage_plane(gray, n, h, w, R, st, s)) != CPE_OK) return rc; }
+        if (planar) { if ((rc = region_stage_plane(bgr ? anyplane : gray, n, h, w, R, st, s)) != CPE_OK) return rc; }
         else if ((rc = region_stage(gray, n, h, w, 4.5, R, st, s, X.ok ? &rside : nullptr, lplane)) != CPE_OK) return rc;
         if (X.ok) {
             CPE_CHECK_HIP(hipStreamWaitEvent(s, X.join1, 0));
@@ -438,6 +446,38 @@ __global__ __launch_bounds__(256) void k_bgr2gray(const uint8_t *__restrict__ bg
     } else {
         for (size_t p = p0; p < npx; p++)
             gray[p] = (uint8_t)((bgr[3 * p] * 3735u + bgr[3 * p + 1] * 19235u + bgr[3 * p + 2] * 9798u + 16384u) >> 15);
+    }
+}
+} }
+
+// the planar target's colour frames: BGR2GRAY as k_bgr2gray, and beside it the mask get_convex_hull thresholds
+// (util_plane.py:2590-2689): cv2.threshold(img, 127, 255, THRESH_BINARY) per channel, then BGR2GRAY of that 0/255 image,
+// which is non-zero exactly where some channel is above 127 -- written as 0 / 255 (the region stage thresholds it at 127)
+namespace cpe { namespace {
+__global__ __launch_bounds__(256) void k_bgr2gray_any(const uint8_t *__restrict__ bgr, size_t npx, uint8_t *__restrict__ gray,
+                                                      uint8_t *__restrict__ any)
+{
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t p0 = q * 4;
+    if (p0 >= npx) return;
+    if (p0 + 4 <= npx) {
+        const uint32_t *src = (const uint32_t *)(bgr + p0 * 3);     // p0 * 3 is a multiple of 12
+        const uint32_t a = src[0], b = src[1], c = src[2];
+        const uint32_t px[4][3] = {{a & 255, (a >> 8) & 255, (a >> 16) & 255}, {a >> 24, b & 255, (b >> 8) & 255},
+                                   {(b >> 16) & 255, b >> 24, c & 255}, {(c >> 8) & 255, (c >> 16) & 255, c >> 24}};
+        uint32_t out = 0, m = 0;
+        for (int k = 0; k < 4; k++) {
+            out |= ((px[k][0] * 3735u + px[k][1] * 19235u + px[k][2] * 9798u + 16384u) >> 15) << (8 * k);
+            if (max(px[k][0], max(px[k][1], px[k][2])) > 127u) m |= 255u << (8 * k);
+        }
+        *(uint32_t *)(gray + p0) = out;
+        *(uint32_t *)(any + p0) = m;
+    } else {
+        for (size_t p = p0; p < npx; p++) {
+            const uint32_t B = bgr[3 * p], G = bgr[3 * p + 1], R = bgr[3 * p + 2];
+            gray[p] = (uint8_t)((B * 3735u + G * 19235u + R * 9798u + 16384u) >> 15);
+            any[p] = max(B, max(G, R)) > 127u ? 255 : 0;
+        }
     }
 }
 } }

@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 103   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants) */
+#define CPE_VERSION 104   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+                             104: cpe_detect_grid_bgr_batch_ex also takes the planar target) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -171,10 +172,18 @@ CPE_API int32_t cpe_detect_line_tables(const void *ws, size_t ws_bytes, int32_t 
  * 8-bit fixed point, gray = (B*3735 + G*19235 + R*9798 + 2^14) >> 15 ([ext] OpenCV 4.5.5; identity on grey-replicated frames);
  * detect_largest_blob takes the L channel of cv2.cvtColor(BGR2LAB) of the COLOUR image (:1840) and indexing_data blurs the colour
  * image 7x7 channel by channel before converting it (:1433-1435).
+ * The planar script (python_grid_detection_plane.py, CPE_TARGET_PLANE) reads the colour planes in two places as well; every other
+ * step of it works on the grey image:
+ *   get_convex_hull(original_img, 5) (python_grid_detection_plane.py:96, utils/util_plane.py:2590-2689) thresholds each channel
+ *     at 127 (cv2.threshold, THRESH_BINARY) and converts that 0/255 image with BGR2GRAY: the first hull round starts from the
+ *     pixels where ANY channel is above 127 (grey frames: gray > 127);
+ *   indexing_data (util_plane.py:1334-1336) blurs the colour image 7x7 channel by channel before converting it, as above.
  *   cpe_bgr2gray_batch             bgr u8[n,h,w,3] interleaved -> gray u8[n,h,w]; both 4-byte aligned device buffers.
  *   cpe_detect_grid_bgr_batch_ex   the whole of detect_grid on true-colour frames: same outputs, workspace and status codes as
- *                                  cpe_detect_grid_batch_ex (cylinder target, no sub-pixel refinement); on grey-replicated
- *                                  frames it returns what cpe_detect_grid_batch returns for the grey plane. */
+ *                                  cpe_detect_grid_batch_ex (cylinder or planar target, no sub-pixel refinement); on
+ *                                  grey-replicated frames it returns what cpe_detect_grid_batch returns for the grey plane.
+ *                                  Planar target: CPE_PLANE_CLAHE (unused by that target) holds the 0/255 any-channel
+ *                                  mask after the call. */
 CPE_API int32_t cpe_detect_grid_bgr_batch_ex(const uint8_t *bgr, int32_t n, int32_t h, int32_t w, const CpeDetectParams *params,
                                              void *ws, size_t ws_bytes, double *xy, int32_t *id, int32_t *n_pts,
                                              double *center, int32_t *status, void *stream);
@@ -192,7 +201,7 @@ CPE_API int32_t cpe_bgr2gray_batch(const uint8_t *bgr, int32_t n, int32_t h, int
 #define CPE_PLANE_EXP_V 7
 #define CPE_PLANE_JOINTS 8        /* i32[CPE_MAXJ,2] cylinder_centroids in contour order */
 #define CPE_PLANE_STATE 9         /* per-frame state record (see csrc/cpe_dev.h FrameState) */
-#define CPE_PLANE_CLAHE 10        /* u8[h,w]  CLAHE'd L channel */
+#define CPE_PLANE_CLAHE 10        /* u8[h,w]  CLAHE'd L channel (planar target: the any-channel mask of colour frames) */
 #define CPE_PLANE_BLUR19 11       /* u8[h,w] */
 #define CPE_PLANE_BLUR7 12        /* u8[h,w] */
 #define CPE_PLANE_SWEEP 14        /* i32[192] blob-sweep counters: [8+k] dark components, [25+k] bright components,
