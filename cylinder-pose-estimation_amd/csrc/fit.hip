@@ -905,6 +905,15 @@ __device__ void fit_write_few_points(int f, int lane, double *__restrict__ o_raw
     }
 }
 
+// a cylinder worth status 0: every parameter and the objective finite (x, f are wave-uniform)
+__device__ __forceinline__ bool fit_finite(const double *x, double f)
+{
+    bool ok = isfinite(f);
+#pragma unroll
+    for (int k = 0; k < 6; k++) ok = ok && isfinite(x[k]);
+    return ok;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(64) void k_fit_cylinder(const double *__restrict__ X, const int *__restrict__ cnt,
                                                      double R, double tolx, double tolf, int maxiter,
@@ -923,15 +932,17 @@ __global__ __launch_bounds__(64) void k_fit_cylinder(const double *__restrict__ 
     __shared__ int sNb[20];
     const int f = blockIdx.x, lane = threadIdx.x;
     const int n = min(max(cnt[f], 0), MAXP);
-    if (n < 3) { fit_write_few_points(f, lane, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status); return; }
+    if (n < CPE_FIT_MIN_POINTS) { fit_write_few_points(f, lane, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status); return; }
     const double *Xf = X + (size_t)f * MAXP * 3;
     for (int i = lane; i < 3 * n; i += 64) sP[i] = Xf[i];
     __syncthreads();
     double x0[6], f0, xf[6], ffinal;
     int itercount, func_evals;
     fit_init(sP, n, R, lane, sD, sNb, x0, f0);
+    if (!fit_finite(x0, f0)) { fit_write_few_points(f, lane, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status); return; }
     if constexpr (MODE == 0) fit_nm(sP, n, R, lane, tolx, tolf, maxiter, maxfun, x0, f0, xf, ffinal, itercount, func_evals);
     else fit_lm(sP, n, R, lane, tolx, tolf, maxiter, x0, f0, xf, ffinal, itercount, func_evals);
+    if (!fit_finite(xf, ffinal)) { fit_write_few_points(f, lane, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status); return; }
     fit_write(f, lane, sP, n, x0, xf, f0, ffinal, itercount, func_evals, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status);
 }
 
@@ -974,16 +985,17 @@ __global__ __launch_bounds__(64) void k_fit_ransac(const double *__restrict__ X,
     const int n = min(max(cnt[f], 0), MAXP);
     uint8_t *mk = o_mask + (size_t)f * MAXP;
     for (int k = lane; k < MAXP; k += 64) mk[k] = 0;
-    if (n < 3) {
+    auto few_points = [&]() {   // status 5, zero outputs, empty mask
         fit_write_few_points(f, lane, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status);
         if (lane == 0) o_ninl[f] = 0;
-        return;
-    }
+    };
+    if (n < CPE_FIT_MIN_POINTS) { few_points(); return; }
     const double *Xf = X + (size_t)f * MAXP * 3;
     for (int i = lane; i < 3 * n; i += 64) sP[i] = Xf[i];
     __syncthreads();
     double x0[6], f0;
     fit_init(sP, n, R, lane, sD, sNb, x0, f0);
+    if (!fit_finite(x0, f0)) { few_points(); return; }
     const double q = (double)S / (double)n;
     const unsigned long long frame = frame0 + (unsigned long long)f;
     int best_cnt = -1;
@@ -1029,17 +1041,15 @@ __global__ __launch_bounds__(64) void k_fit_ransac(const double *__restrict__ X,
     }
     int nq = compact([&](int k) { return ransac_inlier(sP, k, best_x, R, tau); });
     const int n_inl = nq;
-    if (nq < 6) {   // too few inliers to fit: all points, and say so in the mask
-        nq = compact([&](int) { return true; });
-        for (int k = lane; k < n; k += 64) mk[k] = 1;
-    } else {
-        for (int k = lane; k < n; k += 64) mk[k] = ransac_inlier(sP, k, best_x, R, tau) ? 1 : 0;
-    }
+    const bool all_points = nq < 6;   // too few inliers to fit: all points, and say so in the mask
+    if (all_points) nq = compact([&](int) { return true; });
     const double fs = cyl_objective(best_x, Pts{sQ, nq}, R, lane);
     double xf[6], ffinal;
     int itercount, func_evals;
     if constexpr (MODE == 0) fit_nm(sQ, nq, R, lane, tolx, tolf, maxiter, maxfun, best_x, fs, xf, ffinal, itercount, func_evals);
     else fit_lm(sQ, nq, R, lane, tolx, tolf, maxiter, best_x, fs, xf, ffinal, itercount, func_evals);
+    if (!fit_finite(xf, ffinal)) { few_points(); return; }
+    for (int k = lane; k < n; k += 64) mk[k] = all_points ? 1 : (ransac_inlier(sP, k, best_x, R, tau) ? 1 : 0);
     fit_write(f, lane, sQ, nq, x0, xf, f0, ffinal, itercount, func_evals, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status);
     if (lane == 0) o_ninl[f] = n_inl;
 }

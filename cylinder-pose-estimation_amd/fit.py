@@ -13,6 +13,9 @@ from . import lib as _lib
 
 MAXP = _lib.MAXP
 SEL_CHOOSE_IDX, SEL_THRESHOLD, SEL_JOIN = 0, 1, 2
+FLAG_FALLBACK, FLAG_OVERFLOW = 1, 2                 # CPE_FIT_FLAG_*
+ST_OK, ST_FEW_POINTS, ST_OVERFLOW = 0, 5, 6         # CPE_ST_* of the fit
+FIT_MIN_POINTS = 5                                  # CPE_FIT_MIN_POINTS
 
 
 @dataclass
@@ -146,12 +149,15 @@ def fit_cylinder_ransac_batch(pts3, cnt, radius, hypotheses=64, sample=12, tau=0
 def fit_single_cylinder_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, radius, selector=SEL_CHOOSE_IDX,
                               patch=3, th=0.3, ransac=None, **fit_kw):
     """[pts3, cylT, fvals, meanError] = fitSingleCylinder(...) for every frame of the batch.
+    status: the fit's (ST_OK / ST_FEW_POINTS), or ST_OVERFLOW where the selector set FLAG_OVERFLOW (all outputs zero).
     ransac: None (reference behaviour) or a dict of fit_cylinder_ransac_batch keywords (build-defined config 5)."""
     sel = select_triangulate_batch(gp1, gp2, K1, K2, T21, selector, patch, th)
     if ransac is not None:
         fit = fit_cylinder_ransac_batch(sel['pts3'], sel['m'], radius, **ransac, **fit_kw)
     else:
         fit = fit_cylinder_batch(sel['pts3'], sel['m'], radius, **fit_kw)
+    # a frame the selector skipped because its indices do not fit the dense table has m = 0: report it as the overflow it is
+    fit['status'].masked_fill_((sel['flags'] & FLAG_OVERFLOW) != 0, ST_OVERFLOW)
     out = dict(sel)
     out.update(fit)
     return out

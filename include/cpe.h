@@ -235,6 +235,7 @@ CPE_API int32_t cpe_debug_external_components(const uint8_t *mask, int32_t n, in
 
 #define CPE_FIT_FLAG_FALLBACK 1 /* selector found nothing -> plain index join (chooseIdx.m:101-104) */
 #define CPE_FIT_FLAG_OVERFLOW 2 /* index span exceeds CPE_FIT_TABLE_DIM or |index| > 9999: frame skipped */
+#define CPE_FIT_MIN_POINTS 5    /* fewest 3-D points a cylinder is fitted to (the local quadric has 5 unknowns) */
 
 #define CPE_SEL_CHOOSE_IDX 0     /* chooseIdx(gp1,gp2,.,.,patch,th)          fitSingleCylinder.m:12 (live) */
 #define CPE_SEL_THRESHOLD 1      /* triangulateWithThreshold(gp1,gp2,.,.,th) fitSingleCylinder.m:11 */
@@ -250,6 +251,12 @@ CPE_API size_t cpe_fit_workspace_bytes(int32_t n);
  *            points in the camera-1 frame; err f64[n,CPE_MAXP] per-point reprojection error;
  *            m i32[n] number of selected points; mean_err f64[n]; flags i32[n] (CPE_FIT_FLAG_*)
  *   ws       cpe_fit_workspace_bytes(n) bytes of device scratch
+ * cnt1 / cnt2 are clamped to [0, CPE_MAXP]; slots past them are never read.  The (col,row) indices of a frame (both
+ * tables) go through a dense CPE_FIT_TABLE_DIM x CPE_FIT_TABLE_DIM table: a frame whose indices span CPE_FIT_TABLE_DIM
+ * or more in either direction, or has an index outside [-9999, 9999], is skipped with CPE_FIT_FLAG_OVERFLOW, m = 0,
+ * mean_err = 0 and nothing written to the per-point outputs (the reference has no such limit).  A (col,row) that occurs
+ * more than once in a table is looked up through its first occurrence, as find() does in the reference.  An empty table on
+ * either side gives m = 0 with no flag.
  */
 CPE_API int32_t cpe_select_triangulate_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1,
                                              const double *xy2, const int32_t *id2, const int32_t *cnt2, int32_t n,
@@ -264,7 +271,8 @@ CPE_API int32_t cpe_select_triangulate_batch(const double *xy1, const int32_t *i
  *   m, flags as above; ws as above.
  * cpe_triangulate_batch: [worldPoints, reprojectionErrors] = triangulate(cgp1, cgp2, stereoParams) for pairs that are already
  *   matched, and meanError = mean(reprojectionErrors) (fitSingleCylinder.m:15-17).  p1, p2 f64[n,CPE_MAXP,2], cnt i32[n] ->
- *   X f64[n,CPE_MAXP,3] (camera-1 frame), err f64[n,CPE_MAXP], mean_err f64[n]. */
+ *   X f64[n,CPE_MAXP,3] (camera-1 frame), err f64[n,CPE_MAXP], mean_err f64[n].  cnt is clamped to [0, CPE_MAXP]; mean_err of
+ *   an empty frame is 0. */
 CPE_API int32_t cpe_choose_idx_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
                                      const int32_t *id2, const int32_t *cnt2, int32_t n, const double *K1, const double *K2,
                                      const double *T21, int32_t patch, double th, void *ws, size_t ws_bytes, double *p1,
@@ -291,6 +299,11 @@ typedef struct CpeFitParams {
  *   T       f64[n,16]   row-major cylT = cylParams2T(cyl(2,:))
  *   fvals   f64[n,2]    [f0, f]        iters i32[n,2] = [iterations, function evaluations]
  *   status  i32[n]      CPE_ST_OK or CPE_ST_FEW_POINTS
+ * cnt is clamped to [0, CPE_MAXP] (a count above CPE_MAXP fits the first CPE_MAXP points); slots past it are never read.
+ * A frame ends in CPE_ST_FEW_POINTS, with every output of the frame zero, when it has fewer than CPE_FIT_MIN_POINTS points
+ * -- the 5-coefficient quadric of estCurvatures is underdetermined there, and MATLAB's `A \ b` would return a rank-deficient
+ * basic solution -- or when the initial or the final cylinder is not finite.  So CPE_ST_OK implies finite cyl_raw, cyl,
+ * fvals and T.  The reference fits from 3 points on; this is a documented deviation.
  */
 CPE_API int32_t cpe_fit_cylinder_batch(const double *X, const int32_t *cnt, int32_t n, double radius,
                                        const CpeFitParams *params, double *cyl_raw, double *cyl, double *T,
@@ -302,7 +315,8 @@ CPE_API int32_t cpe_fit_cylinder_batch(const double *X, const int32_t *cnt, int3
  * -- scored by the number of points with |dist(point, axis) - radius| < tau; the final fit (`params->mode`) runs on the
  * inliers of the best hypothesis.  Outputs as cpe_fit_cylinder_batch (cyl_raw row 0 = the all-points initial cylinder,
  * fvals[0] = objective there, fvals[1] = objective of the final fit over the inliers) plus
- *   n_inliers i32[n], inlier_mask u8[n,CPE_MAXP] (1 = used by the final fit). */
+ *   n_inliers i32[n], inlier_mask u8[n,CPE_MAXP] (1 = used by the final fit; 0 for every slot >= the point count).
+ * Counts and CPE_ST_FEW_POINTS as cpe_fit_cylinder_batch; such a frame also has n_inliers = 0 and an all-zero mask. */
 typedef struct {
     int32_t hypotheses;   /* default 64 */
     int32_t sample;       /* expected subset size, default 12 (>= 6) */

@@ -120,6 +120,18 @@ def choose_idx(gp1, gp2, K1, K2, T21, patch=3, th=0.3):
     return c1[:m].copy(), c2[:m].copy(), idx[:m].copy(), bool(fb.value)
 
 
+def triangulate_with_threshold(gp1, gp2, K1, K2, T21, th=0.3):
+    """triangulateWithThreshold.m -> (cgp1 (m,2), cgp2 (m,2), idx (m,2) int, used_fallback)"""
+    gp1 = _f64(gp1); gp2 = _f64(gp2); cap = max(len(gp1), len(gp2)) + 1
+    c1 = np.empty((cap, 2)); c2 = np.empty((cap, 2)); idx = np.empty((cap, 2), np.int32)
+    fb = C.c_int(0)
+    K1 = _f64(K1); K2 = _f64(K2); T21 = _f64(T21)
+    m = lib().orc_triangulate_with_threshold(_p(gp1, C.c_double), len(gp1), _p(gp2, C.c_double), len(gp2), _p(K1, C.c_double),
+                                             _p(K2, C.c_double), _p(T21, C.c_double), C.c_double(th), _p(c1, C.c_double),
+                                             _p(c2, C.c_double), _p(idx, C.c_int), C.byref(fb))
+    return c1[:m].copy(), c2[:m].copy(), idx[:m].copy(), bool(fb.value)
+
+
 def find_correspondences(gp1, gp2):
     gp1 = _f64(gp1); gp2 = _f64(gp2); cap = len(gp1) + 1
     c1 = np.empty((cap, 2)); c2 = np.empty((cap, 2)); idx = np.empty((cap, 2), np.int32)

@@ -739,13 +739,35 @@ static void fit_init(const double *P, int n, double R, double *cyl0, double *f0)
     free(tmp);
 }
 
+/* a cylinder worth status 0: every parameter and the objective finite */
+static int fit_finite(const double *x, double f)
+{
+    int ok = isfinite(f);
+    for (int k = 0; k < 6; k++) ok = ok && isfinite(x[k]);
+    return ok;
+}
+
+/* status 5 leaves every output zero */
+static int fit_few_points(double *cyl0, double *cyl, double *fvals, int *iters, int *evals)
+{
+    memset(cyl0, 0, 6 * sizeof(double)); memset(cyl, 0, 6 * sizeof(double));
+    fvals[0] = fvals[1] = 0; *iters = 0; *evals = 0;
+    return 5;
+}
+
+/* FIT_MIN_POINTS (CPE_FIT_MIN_POINTS): the 5-coefficient quadric of estCurvatures needs 5 neighbours; fewer points, or a
+ * non-finite initial / final cylinder, end in status 5 (documented deviation: the reference fits from 3 points on) */
+#define FIT_MIN_POINTS 5
+
 static int fit_cylinder_mode(const double *P, int n, double R, double tolx, double tolf, int maxiter, int maxfun,
                              int mode, double *cyl0, double *cyl, double *fvals, int *iters, int *evals)
 {
-    if (n < 3) return 5;
+    if (n < FIT_MIN_POINTS) return fit_few_points(cyl0, cyl, fvals, iters, evals);
     fit_init(P, n, R, cyl0, &fvals[0]);
+    if (!fit_finite(cyl0, fvals[0])) return fit_few_points(cyl0, cyl, fvals, iters, evals);
     if (mode == 1) lm6(cyl0, fvals[0], P, n, R, tolx, tolf, maxiter, cyl, &fvals[1], iters, evals);
     else nelder_mead6(cyl0, P, n, R, tolx, tolf, maxiter, maxfun, cyl, &fvals[1], iters, evals);
+    if (!fit_finite(cyl, fvals[1])) return fit_few_points(cyl0, cyl, fvals, iters, evals);
     return 0;
 }
 
@@ -768,9 +790,12 @@ ORC_API int orc_fit_cylinder_ransac(const double *P, int n, double R, int H, int
                                     int hyp_iters, double tolx, double tolf, int maxiter, int maxfun, int mode, double *cyl0,
                                     double *cyl, double *fvals, int *iters, int *evals, int *n_inl, uint8_t *mask)
 {
-    if (n < 3) return 5;
-    double *Q = (double *)malloc((size_t)(n + 1) * 3 * sizeof(double)), *d = (double *)malloc((size_t)(n + 1) * sizeof(double));
+    *n_inl = 0;
+    memset(mask, 0, (size_t)(n > 0 ? n : 0));
+    if (n < FIT_MIN_POINTS) return fit_few_points(cyl0, cyl, fvals, iters, evals);
     fit_init(P, n, R, cyl0, &fvals[0]);
+    if (!fit_finite(cyl0, fvals[0])) return fit_few_points(cyl0, cyl, fvals, iters, evals);
+    double *Q = (double *)malloc((size_t)(n + 1) * 3 * sizeof(double)), *d = (double *)malloc((size_t)(n + 1) * sizeof(double));
     const double q = (double)S / (double)n;
     int best_cnt = -1;
     double best_x[6] = {0, 0, 0, 0, 0, 0};
@@ -812,6 +837,11 @@ ORC_API int orc_fit_cylinder_ransac(const double *P, int n, double R, int H, int
     else nelder_mead6(best_x, Q, nq, R, tolx, tolf, maxiter, maxfun, cyl, &fvals[1], iters, evals);
     /* applyCylParamsPrior / cylParams2T are applied by the caller on the points of the final fit (Q) */
     free(Q); free(d);
+    if (!fit_finite(cyl, fvals[1])) {
+        *n_inl = 0;
+        memset(mask, 0, (size_t)n);
+        return fit_few_points(cyl0, cyl, fvals, iters, evals);
+    }
     return 0;
 }
 

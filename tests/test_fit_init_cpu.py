@@ -52,9 +52,20 @@ def _init_numpy(P, R):
     return ctr + rdir * (R - d2s), kdir, np.linalg.cond(A)
 
 
-@pytest.mark.parametrize('seed', range(12))
-def test_initial_cylinder_matches_lapack_restatement(seed):
-    P = _points(seed)
+# 240 is a typical frame; 21 is just above the 20-neighbour quadric, 64 / 65 straddle one wavefront, 1400 is a
+# 3840x2160 frame (BASELINE config 5) and 2048 = CPE_MAXP: the shapes the GPU tests pin to the oracle
+COUNTS = [240, 21, 64, 65, 1400, 2048]
+
+
+def _seeds_counts(seeds):
+    """(seed, n) for every count; n = 240 keeps the ids the seed-only parametrisation had"""
+    return pytest.mark.parametrize('seed,n', [pytest.param(s, n, id=str(s) if n == 240 else f'{s}-n{n}')
+                                              for n in COUNTS for s in seeds])
+
+
+@_seeds_counts(range(12))
+def test_initial_cylinder_matches_lapack_restatement(seed, n):
+    P = _points(seed, n=n)
     got = oracle.fit_cylinder(P, 45.0)
     assert got['status'] == 0
     org, kdir, cond = _init_numpy(P, 45.0)
@@ -65,21 +76,26 @@ def test_initial_cylinder_matches_lapack_restatement(seed):
     assert np.abs(d0 - kdir).max() < 1e-12, (np.abs(d0 - kdir).max(), cond)   # seen: 7e-16 at cond(A) <= 28
 
 
-@pytest.mark.parametrize('seed', range(8))
-def test_nelder_mead_equals_scipy(seed):
+@_seeds_counts(range(8))
+def test_nelder_mead_equals_scipy(seed, n):
     """The oracle's restatement of fminsearch.m (called at fitCylinderWPts3.m:38 with TolX = TolFun = 1e-5) against scipy's
     Nelder-Mead -- an independent implementation of the same published algorithm (Lagarias et al. 1998: 5 % initial simplex,
     rho 1, chi 2, psi 0.5, sigma 0.5, both tolerances required).  Same objective (the oracle's), same start: the two
     walks are identical step by step, so the minimiser, the value and both counters are EQUAL, not close."""
     from scipy.optimize import minimize
-    P = _points(100 + seed, noise=0.05)
+    P = _points(100 + seed, n=n, noise=0.05)
     got = oracle.fit_cylinder(P, 45.0)
     f = lambda x: oracle.cyl_objective(x, P, 45.0)
     assert f(got['cyl0']) == got['fvals'][0]
     r = minimize(f, got['cyl0'], method='Nelder-Mead', options=dict(xatol=1e-5, fatol=1e-5, maxiter=100000, maxfev=100000))
     assert np.array_equal(r.x, got['cyl'])
     assert r.fun == got['fvals'][1]
-    assert (r.nit, r.nfev) == (got['iters'], got['evals'])
+    if got['evals'] >= 100000:
+        # the evaluation budget ran out (seen once, at n = 2048): fminsearch.m tests it only at the top of an iteration and
+        # finishes the one in progress, scipy stops inside it -- one iteration fewer and exactly MaxFunEvals evaluations
+        assert (r.nit, r.nfev, r.status) == (got['iters'] - 1, 100000, 1)
+    else:
+        assert (r.nit, r.nfev) == (got['iters'], got['evals'])
 
 
 def test_triangulation_matches_lapack_svd():
