@@ -95,6 +95,15 @@ struct RegionBuffers {
     unsigned long long *best;
     int *lohi, *hull;
 };
+// test entry of the region stage (cpe_debug_blob_region): null on the product path.  identity: the sweep sees the input
+// image itself (an identity CLAHE table instead of LAB-L + CLAHE); blobs / n_blobs: the blob records of every threshold are
+// copied out after the group merge (their memory is reused by the disc-union labelling); kp / n_kp: the key points of the
+// groups, in group order, as k_discs computes them
+struct RegionProbe {
+    int identity;
+    double *blobs; int blob_cap; int *n_blobs;   // f64 [n, 17, blob_cap, 3] (x, y, r), i32 [n, 17]
+    float *kp; int kp_cap; int *n_kp;            // f32 [n, kp_cap, 3] (x, y, size), i32 [n]
+};
 // grid.x of the kernels that walk a per-frame list (components, blobs, fragments) in turns: enough workgroups per frame
 // to fill the chip when the batch is small, few when it is large (a grid sized for the list capacity would be mostly
 // empty workgroups: hundreds of thousands of them cost more than the work)

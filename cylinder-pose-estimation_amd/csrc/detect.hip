@@ -19,7 +19,7 @@ int ccl_run(const uint8_t *img, int n, int h, int w, int thr, int invert, int co
             uint8_t *touch, int count_mode, int *cnt, int use_rect, int *nrect, FrameState *st, hipStream_t s, int sparse = 0, int flags = 0, int cnt_sel = 0);
 int ccl_ctl(FrameState *st, int *nrect, int n, int h, int w, int op, hipStream_t s);
 int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const RegionBuffers &B, FrameState *st, hipStream_t s,
-                 const RegionSide *side, const uint8_t *lplane);
+                 const RegionSide *side, const uint8_t *lplane, const RegionProbe *probe);
 int joints_mask_stage(int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s);
 int spot_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s, int planar);
 int region_stage_plane(const uint8_t *gray, int n, int h, int w, const RegionBuffers &B, FrameState *st, hipStream_t s);
@@ -210,6 +210,20 @@ SideStreams &side_streams(hipStream_t caller)
     return X;
 }
 
+// the region stage's buffers inside the workspace (cpe_detect_grid_batch*, cpe_debug_blob_region)
+RegionBuffers region_buffers(uint8_t *base, const Layout &L, int h, int w)
+{
+#define PL(T, p) ((T *)(base + L.off[p]))
+    RegionBuffers R;
+    R.cl = PL(uint8_t, P_CL); R.ext = PL(uint8_t, P_EXT); R.mc = PL(uint8_t, P_MASK_CONTOUR); R.touch = PL(uint8_t, P_TOUCH);
+    R.lab = PL(int, P_LAB0); R.cnt = PL(int, P_LAB1); R.roots = PL(int, P_ROOTS); R.nrect = PL(int, P_NRECT); R.lab2 = PL(int, P_LAB2); R.cnt2 = PL(int, P_LAB3);
+    R.sw = PL(int, P_SW); R.hl = PL(int2, P_HL); R.bl = PL(int2, P_BL); R.tl = PL(int2, P_TL); R.bk = PL(int, P_BK); R.bits = PL(uint32_t, P_BITS); R.pool = PL(uint32_t, P_POOL); R.blob_ch = PL(unsigned short, P_BLOB_CH); R.maxch = region_maxch(h, w); R.maxdf = region_maxdf(h, w); R.gmid = PL(double, P_GMID); R.hpar = PL(int, P_HPAR); R.htime = PL(uint8_t, P_HTIME); R.hist = PL(unsigned int, P_HIST); R.lut = PL(uint8_t, P_LUT);
+    R.blobs = PL(BlobRec, P_BLOBS); R.blob_d = PL(int, P_BLOB_D); R.order = PL(int, P_ORDER); R.dists = PL(double, P_DISTS);
+    R.groups = PL(Group, P_GROUPS); R.best = PL(unsigned long long, P_BEST); R.lohi = PL(int, P_LOHI); R.hull = PL(int, P_HULL);
+#undef PL
+    return R;
+}
+
 }  // namespace
 }  // namespace cpe
 
@@ -298,12 +312,7 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
     uint8_t *lplane = bgr && !planar ? PL(uint8_t, P_EXT) : nullptr;
     uint8_t *anyplane = bgr && planar ? PL(uint8_t, P_CL) : nullptr;
     if (bgr) gray = PL(uint8_t, P_GRAYIN);
-    RegionBuffers R;
-    R.cl = PL(uint8_t, P_CL); R.ext = PL(uint8_t, P_EXT); R.mc = PL(uint8_t, P_MASK_CONTOUR); R.touch = PL(uint8_t, P_TOUCH);
-    R.lab = PL(int, P_LAB0); R.cnt = PL(int, P_LAB1); R.roots = PL(int, P_ROOTS); R.nrect = PL(int, P_NRECT); R.lab2 = PL(int, P_LAB2); R.cnt2 = PL(int, P_LAB3);
-    R.sw = PL(int, P_SW); R.hl = PL(int2, P_HL); R.bl = PL(int2, P_BL); R.tl = PL(int2, P_TL); R.bk = PL(int, P_BK); R.bits = PL(uint32_t, P_BITS); R.pool = PL(uint32_t, P_POOL); R.blob_ch = PL(unsigned short, P_BLOB_CH); R.maxch = region_maxch(h, w); R.maxdf = region_maxdf(h, w); R.gmid = PL(double, P_GMID); R.hpar = PL(int, P_HPAR); R.htime = PL(uint8_t, P_HTIME); R.hist = PL(unsigned int, P_HIST); R.lut = PL(uint8_t, P_LUT);
-    R.blobs = PL(BlobRec, P_BLOBS); R.blob_d = PL(int, P_BLOB_D); R.order = PL(int, P_ORDER); R.dists = PL(double, P_DISTS);
-    R.groups = PL(Group, P_GROUPS); R.best = PL(unsigned long long, P_BEST); R.lohi = PL(int, P_LOHI); R.hull = PL(int, P_HULL);
+    RegionBuffers R = region_buffers(base, L, h, w);
     MaskBuffers M;
     M.binary = PL(uint8_t, P_BINARY); M.hmask = PL(uint8_t, P_HMASK); M.vmask = PL(uint8_t, P_VMASK);
     M.joints_mask = PL(uint8_t, P_JOINTS_MASK); M.tmpA = PL(uint8_t, P_TMPA); M.tmpB = PL(uint8_t, P_TMPB);
@@ -355,7 +364,7 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
         }
         RegionSide rside = {X.s3, X.e3a, X.e3b, X.e3c, X.e3d, X.join1, X.join2};
         if (planar) { if ((rc = region_stage_plane(bgr ? anyplane : gray, n, h, w, R, st, s)) != CPE_OK) return rc; }
-        else if ((rc = region_stage(gray, n, h, w, 4.5, R, st, s, X.ok ? &rside : nullptr, lplane)) != CPE_OK) return rc;
+        else if ((rc = region_stage(gray, n, h, w, 4.5, R, st, s, X.ok ? &rside : nullptr, lplane, nullptr)) != CPE_OK) return rc;
         if (X.ok) {
             CPE_CHECK_HIP(hipStreamWaitEvent(s, X.join1, 0));
             CPE_CHECK_HIP(hipStreamWaitEvent(s, X.join2, 0));
@@ -553,4 +562,25 @@ extern "C" int32_t cpe_debug_ccl(const uint8_t *img, int32_t n, int32_t h, int32
     return ccl_run(img, n, h, w, thr, invert, conn8, (int *)(base + L.off[P_LAB0]), want_roots ? (int *)(base + L.off[P_ROOTS]) : nullptr,
                    invert != 0, (uint8_t *)(base + L.off[P_TOUCH]), count_mode, (int *)(base + L.off[P_LAB1]), (want_bbox >> 1) & 1,
                    (want_bbox & 1) ? (int *)(base + L.off[P_NRECT]) : nullptr, st, s);
+}
+
+// The region stage of the cylinder target on a given sweep image (tests): region_stage as the product runs it, serially, with
+// an identity CLAHE table in place of LAB-L + CLAHE, and its blob records and key points copied out (RegionProbe).
+extern "C" int32_t cpe_debug_blob_region(const uint8_t *img, int32_t n, int32_t h, int32_t w, void *ws, size_t ws_bytes,
+                                         float *kp, int32_t kp_cap, int32_t *n_kp, double *blobs, int32_t blob_cap,
+                                         int32_t *n_blobs, void *stream)
+{
+    CPE_CHECK_ARG(img && ws && kp && n_kp && blobs && n_blobs && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096 &&
+                  kp_cap > 0 && blob_cap > 0, "cpe_debug_blob_region: bad argument");
+    Layout L = make_layout(n, h, w);
+    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_debug_blob_region: workspace too small or misaligned");
+    uint8_t *base = (uint8_t *)ws;
+    hipStream_t s = (hipStream_t)stream;
+    FrameState *st = (FrameState *)(base + L.off[P_STATE]);
+    RegionBuffers R = region_buffers(base, L, h, w);
+    RegionProbe probe = {1, blobs, blob_cap, n_blobs, kp, kp_cap, n_kp};
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, (unsigned long long *)(base + L.off[P_BEST2]), R.nrect);
+    CPE_CHECK_LAUNCH("k_state_init");
+    return region_stage(img, n, h, w, 4.5, R, st, s, nullptr, nullptr, &probe);
 }

@@ -1521,6 +1521,17 @@ __global__ __launch_bounds__(256) void k_sw_snap(int n, int g_snap, int2 *__rest
     sw_snap_body(vb, lists, sw, cnt_base, slot, h, w, acc, trace, st);
 }
 
+// the key point of a group (SimpleBlobDetector::detect, blobdetector.cpp): mean of the centres, size = 2 x the radius of the
+// middle centre of the radius-sorted list; f32 as cv::KeyPoint holds it
+__device__ __forceinline__ void group_keypoint(const Group &g, int gn, float &kx, float &ky, float &ksize)
+{
+    double sx = 0, sy = 0, nrm = 0;
+    for (int j = 0; j < gn; j++) { sx += 1.0 * g.c[j][0]; sy += 1.0 * g.c[j][1]; nrm += 1.0; }
+    sx *= (1. / nrm);
+    sy *= (1. / nrm);
+    kx = (float)sx; ky = (float)sy; ksize = (float)(g.c[gn / 2][2]) * 2.0f;
+}
+
 // groups with >= 2 centres -> key points -> filled discs (cv2.circle, Circle() midpoint spans)
 __global__ __launch_bounds__(256) void k_discs(FrameState *__restrict__ st, const Group *__restrict__ groups, int h, int w,
                                                uint8_t *__restrict__ ext)
@@ -1533,11 +1544,8 @@ __global__ __launch_bounds__(256) void k_discs(FrameState *__restrict__ st, cons
         const Group &g = groups[(size_t)f * MAXG + gi];
         const int gn = g.n;
         if (gn < 2) continue;
-        double sx = 0, sy = 0, nrm = 0;
-        for (int j = 0; j < gn; j++) { sx += 1.0 * g.c[j][0]; sy += 1.0 * g.c[j][1]; nrm += 1.0; }
-        sx *= (1. / nrm);
-        sy *= (1. / nrm);
-        float kx = (float)sx, ky = (float)sy, ksize = (float)(g.c[gn / 2][2]) * 2.0f;
+        float kx, ky, ksize;
+        group_keypoint(g, gn, kx, ky, ksize);
         float radius = ksize / 2;
         int er = (int)((double)radius + 4);
         int cx = (int)kx, cy = (int)ky;
@@ -1968,6 +1976,56 @@ __global__ __launch_bounds__(256) void k_dilate_ellipse(const uint8_t *__restric
     }
 }
 
+// ---- RegionProbe (tests): identity CLAHE tables, blob records, key points in group order
+__global__ __launch_bounds__(256) void k_probe_identity_lut(uint8_t *__restrict__ lut)
+{
+    lut[((size_t)blockIdx.y * 16 + blockIdx.x) * 256 + threadIdx.x] = (uint8_t)threadIdx.x;
+}
+
+// grid (NTHR, n): the records of threshold blockIdx.x in their stored order (hole blobs first)
+__global__ __launch_bounds__(256) void k_probe_blobs(const int *__restrict__ sw, const BlobRec *__restrict__ blobs_all, double *__restrict__ out,
+                                                     int cap, int *__restrict__ cnt)
+{
+    const int k = blockIdx.x, f = blockIdx.y;
+    const int nb = min(sw[(size_t)f * SW_STRIDE + SW_NB + k], MAXB);
+    const BlobRec *B = blobs_all + ((size_t)f * NTHR + k) * MAXB;
+    double *o = out + ((size_t)f * NTHR + k) * cap * 3;
+    for (int i = threadIdx.x; i < min(nb, cap); i += 256) { o[3 * i] = B[i].x; o[3 * i + 1] = B[i].y; o[3 * i + 2] = B[i].r; }
+    if (threadIdx.x == 0) cnt[(size_t)f * NTHR + k] = nb;
+}
+
+// one workgroup per frame: the groups with >= 2 centres, compacted in group order (the order k_discs draws them in)
+__global__ __launch_bounds__(256) void k_probe_keypoints(const FrameState *__restrict__ st, const Group *__restrict__ groups, float *__restrict__ kp,
+                                                         int cap, int *__restrict__ cnt)
+{
+    __shared__ int s_pre[256];
+    const int f = blockIdx.x, t = threadIdx.x;
+    const int ng = min(st[f].n_groups, MAXG);
+    int base = 0;
+    for (int g0 = 0; g0 < ng; g0 += 256) {
+        const int gi = g0 + t;
+        const int gn = gi < ng ? groups[(size_t)f * MAXG + gi].n : 0;
+        const int on = gn >= 2 ? 1 : 0;
+        s_pre[t] = on;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {   // inclusive scan
+            const int v = t >= off ? s_pre[t - off] : 0;
+            __syncthreads();
+            s_pre[t] += v;
+            __syncthreads();
+        }
+        const int q = base + s_pre[t] - on;
+        if (on && q < cap) {
+            float kx, ky, ksize;
+            group_keypoint(groups[(size_t)f * MAXG + gi], gn, kx, ky, ksize);
+            kp[((size_t)f * cap + q) * 3] = kx; kp[((size_t)f * cap + q) * 3 + 1] = ky; kp[((size_t)f * cap + q) * 3 + 2] = ksize;
+        }
+        base += s_pre[255];
+        __syncthreads();
+    }
+    if (t == 0) cnt[f] = base;
+}
+
 __global__ void k_best_reset(int n, unsigned long long *best)
 {
     int f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1979,10 +2037,11 @@ __global__ void k_best_reset(int n, unsigned long long *best)
 
 
 // lplane: L channel of BGR2LAB of a colour frame (util_cylinder.py:1840 on a 3-channel image), or null: grey frames, L = LUT[grey]
+// probe: null on the product path (cpe_debug_blob_region: see RegionProbe)
 int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const RegionBuffers &B, FrameState *st, hipStream_t s,
-                 const RegionSide *side, const uint8_t *lplane)
+                 const RegionSide *side, const uint8_t *lplane, const RegionProbe *probe)
 {
-    const int lab_lut = lplane ? 0 : 1;
+    const int lab_lut = (lplane || (probe && probe->identity)) ? 0 : 1;
     if (lplane) gray = lplane;
     const size_t N = (size_t)h * w, total = N * n;
     ClaheGeom g;
@@ -1996,10 +2055,15 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
     g.lutScale = (float)255 / tileTotal;
     CPE_LAUNCH_BEGIN();
     // (st[].n_groups / n_kp, B.best and the bounding-box accumulators B.nrect were reset by k_state_init)
-    (void)hipMemsetAsync(B.hist, 0, (size_t)n * 16 * 256 * sizeof(unsigned int), s);
-    const int strips = 8;
-    CPE_KLAUNCH(k_clahe_hist, dim3(n * 16 * strips), dim3(256), 0, s, gray, n, h, w, g, strips, B.hist, lab_lut);
-    CPE_KLAUNCH(k_clahe_lut, dim3(n * 16), dim3(256), 0, s, B.hist, g, B.lut);
+    if (probe && probe->identity) {
+        // lut[t][v] = v for the 16 tiles: k_clahe_apply interpolates equal values, so the sweep sees the input itself
+        CPE_KLAUNCH(k_probe_identity_lut, dim3(16, n), dim3(256), 0, s, B.lut);
+    } else {
+        (void)hipMemsetAsync(B.hist, 0, (size_t)n * 16 * 256 * sizeof(unsigned int), s);
+        const int strips = 8;
+        CPE_KLAUNCH(k_clahe_hist, dim3(n * 16 * strips), dim3(256), 0, s, gray, n, h, w, g, strips, B.hist, lab_lut);
+        CPE_KLAUNCH(k_clahe_lut, dim3(n * 16), dim3(256), 0, s, B.hist, g, B.lut);
+    }
     (void)hipMemsetAsync(B.sw, 0, (size_t)n * SW_STRIDE * sizeof(int), s);   // the sweep's counters: k_clahe_apply already counts the buckets
     CPE_KLAUNCH(k_clahe_apply, dim3((unsigned)((N + CLAHE_BLK_PX - 1) / CLAHE_BLK_PX), n), dim3(256), 0, s, gray, h, w, g, (const uint8_t *)B.lut, B.cl, B.nrect, lab_lut,
                 B.sw + SW_BS, (int)SW_STRIDE);
@@ -2093,6 +2157,11 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
                     e ? atoi(e) & 3 : 0, B.gmid, h, w);
     }
     CPE_CHECK_LAUNCH("blob merge");
+    if (probe) {   // the records share memory with the label planes the disc union is labelled in
+        CPE_KLAUNCH(k_probe_blobs, dim3(NTHR, n), dim3(256), 0, s, (const int *)B.sw, (const BlobRec *)B.blobs, probe->blobs, probe->blob_cap, probe->n_blobs);
+        CPE_KLAUNCH(k_probe_keypoints, dim3(n), dim3(256), 0, s, (const FrameState *)st, (const Group *)B.groups, probe->kp, probe->kp_cap, probe->n_kp);
+        CPE_CHECK_LAUNCH("region probe");
+    }
     (void)hipMemsetAsync(B.ext, 0, total, s);
     (void)hipMemsetAsync(B.mc, 0, total, s);
     CPE_KLAUNCH(k_discs, dim3(frame_waves(n, 4, MAXG / 4), n), dim3(256), 0, s, st, B.groups, h, w, B.ext);

@@ -36,8 +36,8 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 104   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
-                             104: cpe_detect_grid_bgr_batch_ex also takes the planar target) */
+#define CPE_VERSION 105   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+                             104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -224,6 +224,19 @@ CPE_API int32_t cpe_debug_ccl(const uint8_t *img, int32_t n, int32_t h, int32_t 
  * first_px i32[n,cap], count i32[n] (may exceed cap: then only cap entries were stored).  Test / debugging aid. */
 CPE_API int32_t cpe_debug_external_components(const uint8_t *mask, int32_t n, int32_t h, int32_t w, void *ws, size_t ws_bytes,
                                               int32_t *first_px, int32_t cap, int32_t *count, void *stream);
+
+/* The blob stage of detect_largest_blob (util_cylinder.py:1830-1899) on a given image: the library's region stage, with
+ * img u8[n,h,w] (64 <= h,w <= 4096) as the image its SimpleBlobDetector sweeps -- LAB-L and CLAHE are replaced by an identity
+ * table, so CPE_PLANE_CLAHE holds img afterwards -- run serially on `stream`.  Outputs:
+ *   kp      f32[n,kp_cap,3]      key points (x, y, size) in the detector's group order; n_kp i32[n] their number (may exceed
+ *                                kp_cap: then only kp_cap were stored)
+ *   blobs   f64[n,17,blob_cap,3] accepted blobs (x, y, radius) of threshold 50 + 10 k, hole borders first, otherwise in no
+ *                                defined order; n_blobs i32[n,17] their number (may exceed blob_cap)
+ * and in the workspace, as after cpe_detect_grid_batch: CPE_PLANE_STATE (rect, n_kp, n_groups, overflow, status 0 or
+ * CPE_ST_NO_REGION), CPE_PLANE_MASK_CONTOUR and CPE_PLANE_SWEEP.  Test / debugging aid. */
+CPE_API int32_t cpe_debug_blob_region(const uint8_t *img, int32_t n, int32_t h, int32_t w, void *ws, size_t ws_bytes,
+                                      float *kp, int32_t kp_cap, int32_t *n_kp, double *blobs, int32_t blob_cap,
+                                      int32_t *n_blobs, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Grid-point tables.  One table per image: xy f64[n,CPE_MAXP,2] pixel coordinates, id i32[n,CPE_MAXP,2]

@@ -162,7 +162,8 @@ static int find_blobs(const uint8_t *bin, int h, int w, double minArea, double m
 
 /* SimpleBlobDetector(minArea=10, defaults otherwise).detect(gray) -> key points (x, y, size) as f32 */
 ORC_API int orc_simple_blob_detector(const uint8_t *gray, int h, int w, float *kp /* cap x 3 */, int cap,
-                                     int *stats /* optional 17: blobs per threshold */)
+                                     int *stats /* optional 17: blobs per threshold */,
+                                     double *blobs /* optional 17 x blob_cap x 3: (x, y, radius) of the accepted blobs */, int blob_cap)
 {
     const double minDist = 10.0;
     center_group *groups = NULL;
@@ -175,6 +176,10 @@ ORC_API int orc_simple_blob_detector(const uint8_t *gray, int h, int w, float *k
         blob_center *cur;
         int ncur = find_blobs(bin, h, w, 10.0f, 5000.0f, &cur);
         if (stats) stats[ti] = ncur;
+        for (int i = 0; blobs && i < ncur && i < blob_cap; i++) {
+            double *o = blobs + ((size_t)ti * blob_cap + i) * 3;
+            o[0] = cur[i].x; o[1] = cur[i].y; o[2] = cur[i].radius;
+        }
         int ng0 = ng; /* groups created at this threshold are appended afterwards */
         center_group *newg = NULL;
         int nnew = 0, newcap = 0;
@@ -232,6 +237,7 @@ ORC_API int orc_simple_blob_detector(const uint8_t *gray, int h, int w, float *k
  * returns 0 ok, 1 = no contour (cv2.convexHull(None) raises in the reference). */
 int orc_detect_largest_blob_l(const uint8_t *gray, const uint8_t *l_in, int h, int w, double clip, uint8_t *mask, int *rect,
                               uint8_t *cl_out, int *nkp_out);
+ORC_API int orc_largest_blob_from_sweep(const uint8_t *cl, int h, int w, uint8_t *mask, int *rect, int *nkp_out);
 ORC_API int orc_detect_largest_blob(const uint8_t *gray, int h, int w, double clip, uint8_t *mask, int *rect,
                                     uint8_t *cl_out /* optional: CLAHE'd L */, int *nkp_out)
 {
@@ -247,9 +253,17 @@ int orc_detect_largest_blob_l(const uint8_t *gray, const uint8_t *l_in, int h, i
     else orc_lab_l(gray, h, w, L);
     orc_clahe(L, h, w, clip, 4, 4, cl);
     if (cl_out) memcpy(cl_out, cl, (size_t)h * w);
+    int st = orc_largest_blob_from_sweep(cl, h, w, mask, rect, nkp_out);
+    free(L); free(cl);
+    return st;
+}
+
+/* the part of detect_largest_blob after CLAHE: cl is the image SimpleBlobDetector sweeps */
+ORC_API int orc_largest_blob_from_sweep(const uint8_t *cl, int h, int w, uint8_t *mask, int *rect, int *nkp_out)
+{
     int cap = 65536;
     float *kp = (float *)malloc((size_t)cap * 3 * sizeof(float));
-    int nk = orc_simple_blob_detector(cl, h, w, kp, cap, NULL);
+    int nk = orc_simple_blob_detector(cl, h, w, kp, cap, NULL, NULL, 0);
     if (nk > cap) nk = cap;
     if (nkp_out) *nkp_out = nk;
     uint8_t *ext = (uint8_t *)calloc((size_t)h * w, 1);
@@ -278,6 +292,6 @@ int orc_detect_largest_blob_l(const uint8_t *gray, const uint8_t *l_in, int h, i
         st = 0;
     }
     orc_contours_free(cs);
-    free(ext); free(kp); free(L); free(cl);
+    free(ext); free(kp);
     return st;
 }

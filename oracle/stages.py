@@ -99,11 +99,17 @@ def lab_l(gray):
     return dst
 
 
-def simple_blob_detector(gray, cap=65536):
+def simple_blob_detector(gray, cap=65536, blobs=False, blob_cap=32768):
+    """-> (key points f32 (m,3) x y size, blobs per threshold i32[17]); blobs=True adds the accepted blobs of every threshold:
+    a list of 17 f64 arrays (count, 3) of (x, y, radius), at most blob_cap each"""
     gray = _u8(gray); h, w = gray.shape
     kp = np.zeros((cap, 3), np.float32); stats = np.zeros(17, np.int32)
-    n = lib().orc_simple_blob_detector(_p(gray, C.c_uint8), h, w, _p(kp, C.c_float), cap, _p(stats, C.c_int))
-    return kp[:min(n, cap)].copy(), stats
+    rec = np.zeros((17, blob_cap, 3), np.float64) if blobs else None
+    n = lib().orc_simple_blob_detector(_p(gray, C.c_uint8), h, w, _p(kp, C.c_float), cap, _p(stats, C.c_int),
+                                       _p(rec, C.c_double) if blobs else None, blob_cap)
+    if not blobs:
+        return kp[:min(n, cap)].copy(), stats
+    return kp[:min(n, cap)].copy(), stats, [rec[k, :min(int(stats[k]), blob_cap)].copy() for k in range(17)]
 
 
 def detect_largest_blob(gray, clip=4.5):
@@ -113,6 +119,15 @@ def detect_largest_blob(gray, clip=4.5):
     st = lib().orc_detect_largest_blob(_p(gray, C.c_uint8), h, w, C.c_double(clip), _p(mask, C.c_uint8),
                                        _p(rect, C.c_int), _p(cl, C.c_uint8), C.byref(nk))
     return st, mask, tuple(int(v) for v in rect), cl, nk.value
+
+
+def largest_blob_from_sweep(cl):
+    """detect_largest_blob from the image its SimpleBlobDetector sweeps (the CLAHE'd L channel in the product) ->
+    (status, mask_contour u8, rect (x,y,w,h), n keypoints)"""
+    cl = _u8(cl); h, w = cl.shape
+    mask = np.empty_like(cl); rect = np.zeros(4, np.int32); nk = C.c_int(0)
+    st = lib().orc_largest_blob_from_sweep(_p(cl, C.c_uint8), h, w, _p(mask, C.c_uint8), _p(rect, C.c_int), C.byref(nk))
+    return st, mask, tuple(int(v) for v in rect), nk.value
 
 
 # ---------------------------------------------------------------- masks / expansion / CCL

@@ -24,6 +24,7 @@ def _compare(cpe, orc, gpu, frames, check_planes=True, allow_overflow=None):
     planes = {k: ws.plane(k).cpu().numpy() for k in ('binary', 'hmask', 'vmask', 'mask_contour', 'roi_h', 'roi_v',
                                                      'exp_h', 'exp_v', 'clahe')} if check_planes else {}
     joints = ws.plane('joints').cpu().numpy()
+    sweep = ws.plane('sweep').cpu().numpy()
     state = ws.state()
     npy = frames.numpy()
     n_ok = 0
@@ -36,6 +37,8 @@ def _compare(cpe, orc, gpu, frames, check_planes=True, allow_overflow=None):
             assert np.array_equal(planes['vmask'][i], ref['vmask']), tag
             assert np.array_equal(planes['clahe'][i], S.clahe(S.lab_l(npy[i]))), tag
             assert np.array_equal(planes['mask_contour'][i], ref['mask_contour']), tag
+        _, blobs_per_thr = S.simple_blob_detector(S.clahe(S.lab_l(npy[i])))
+        assert list(sweep[i, 42:42 + 17]) == list(blobs_per_thr), (tag, 'blobs per threshold')
         if allow_overflow and i in allow_overflow and int(det['status'][i]) == 6:
             assert state[i]['overflow'] == allow_overflow[i], (tag, state[i]['overflow'])
             continue            # build-defined: that capacity of the workspace was exceeded (pathological frame)
