@@ -124,9 +124,12 @@ __device__ unsigned long long g_stamps[8][5];
 
 // FAST: the strip's gray window lies inside the frame and its rows are 4-byte aligned (LDS-DMA of dwords); the two forms
 // are separate instantiations so that the byte loads of the other one (ordinary loads into registers, whose hazards the
-// compiler guards with vmcnt waits) put no wait into this one, where a wait would drain the DMA early
-template <bool FAST>
-__device__ __forceinline__ void preprocess_strip(Smem &s, const uint8_t *__restrict__ img, int h, int w, int sx0, uint8_t *__restrict__ out)
+// compiler guards with vmcnt waits) put no wait into this one, where a wait would drain the DMA early.
+// DBG: the debug instantiation (cpe_debug_preprocess) also stores the eigenvalue b and the Sauvola threshold T of every
+// pixel next to its mask byte, into bo / To (f64[h,w]); the product instantiation has no trace of it.
+template <bool FAST, bool DBG>
+__device__ __forceinline__ void preprocess_strip(Smem &s, const uint8_t *__restrict__ img, int h, int w, int sx0, uint8_t *__restrict__ out,
+                                                 double *__restrict__ bo, double *__restrict__ To)
 {
     const int tid0 = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
@@ -359,6 +362,7 @@ __device__ __forceinline__ void preprocess_strip(Smem &s, const uint8_t *__restr
             const int x = sx0 + tid;
             const double *r0 = &s.rs[tid], *r1 = &s.rs[RPL + tid];
             const int y0 = base - L6;
+            double dbg_b = 0.0, dbg_T = 0.0;          // DBG: the planes of the general row below
             auto p6_row = [&](int op, int om, int oe) -> uint8_t {
                 const double s0 = sum0 + r0[op], s1 = sum1 + r1[op];
                 const double m = s0 * (1.0 / 225.0), msq = s1 * (1.0 / 225.0);
@@ -369,6 +373,7 @@ __device__ __forceinline__ void preprocess_strip(Smem &s, const uint8_t *__restr
                 const double sd = sqrt(var);
                 const double T = m * (1 + 0.5 * ((sd / 128) - 1));
                 const double bv = s.e[oe + tid + 7];
+                if constexpr (DBG) { dbg_b = bv; dbg_T = T; }
                 return (bv > T) ? 0 : 255;
             };
             if (y0 >= 8 && y0 + K - 1 + 7 <= h - 1) {      // no clamping, no start of the column: straight-line code
@@ -393,6 +398,7 @@ __device__ __forceinline__ void preprocess_strip(Smem &s, const uint8_t *__restr
                     for (int ry = 0; ry < K; ry++) {
                         const double T = m[ry] * (1 + 0.5 * ((sd[ry] / 128) - 1));
                         out[(size_t)(y0 + ry) * w + x] = (bv[ry] > T) ? 0 : 255;
+                        if constexpr (DBG) { bo[(size_t)(y0 + ry) * w + x] = bv[ry]; To[(size_t)(y0 + ry) * w + x] = T; }
                     }
                 }
             } else {
@@ -408,7 +414,10 @@ __device__ __forceinline__ void preprocess_strip(Smem &s, const uint8_t *__restr
                         }
                     }
                     const uint8_t r = p6_row(((y + 7 < h ? y + 7 : h - 1) % RR) * RST, ((y - 7 > 0 ? y - 7 : 0) % RR) * RST, (y % ER) * EST);
-                    if (x < w) out[(size_t)y * w + x] = r;
+                    if (x < w) {
+                        out[(size_t)y * w + x] = r;
+                        if constexpr (DBG) { bo[(size_t)y * w + x] = dbg_b; To[(size_t)y * w + x] = dbg_T; }
+                    }
                 }
             }
         } else if (wave < 5) {
@@ -503,8 +512,25 @@ __global__ __launch_bounds__(NT, 4) void k_preprocess(const uint8_t *__restrict_
     const uint8_t *img = gray + (size_t)frame * h * w;
     uint8_t *out = mask + (size_t)frame * h * w;
     const bool fast = ((w & 3) == 0) && ((((size_t)img) & 3) == 0) && sx0 - 24 >= 0 && sx0 - 24 + GYW <= w;
-    if (fast) preprocess_strip<true>(s, img, h, w, sx0, out);
-    else preprocess_strip<false>(s, img, h, w, sx0, out);
+    if (fast) preprocess_strip<true, false>(s, img, h, w, sx0, out, nullptr, nullptr);
+    else preprocess_strip<false, false>(s, img, h, w, sx0, out, nullptr, nullptr);
+}
+
+// cpe_debug_preprocess: k_preprocess with the f64 planes b and T stored beside the mask (test aid; its speed is not measured).
+// The same strips and the same selection of the FAST form as k_preprocess, written out again: an inline helper shared by
+// the two kernels reorders k_preprocess's code.
+__global__ __launch_bounds__(NT, 4) void k_preprocess_dbg(const uint8_t *__restrict__ gray, int h, int w, int strips,
+                                                          uint8_t *__restrict__ mask, double *__restrict__ b, double *__restrict__ T)
+{
+    __shared__ Smem s;
+    const int frame = blockIdx.x / strips, strip = blockIdx.x - frame * strips;
+    const int sx0 = strip * SW;
+    const uint8_t *img = gray + (size_t)frame * h * w;
+    uint8_t *out = mask + (size_t)frame * h * w;
+    double *bo = b + (size_t)frame * h * w, *To = T + (size_t)frame * h * w;
+    const bool fast = ((w & 3) == 0) && ((((size_t)img) & 3) == 0) && sx0 - 24 >= 0 && sx0 - 24 + GYW <= w;
+    if (fast) preprocess_strip<true, true>(s, img, h, w, sx0, out, bo, To);
+    else preprocess_strip<false, true>(s, img, h, w, sx0, out, bo, To);
 }
 
 }  // namespace
@@ -520,5 +546,19 @@ extern "C" int32_t cpe_preprocess_batch(const uint8_t *gray, int32_t n, int32_t 
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_preprocess, dim3((unsigned)(n * strips)), dim3(NT), 0, (hipStream_t)stream, gray, h, w, strips, mask);
     CPE_CHECK_LAUNCH("k_preprocess");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_debug_preprocess(const uint8_t *gray, int32_t n, int32_t h, int32_t w, uint8_t *mask, double *b, double *T,
+                                        void *stream)
+{
+    CPE_CHECK_ARG(gray && mask && b && T, "cpe_debug_preprocess: null pointer");
+    CPE_CHECK_ARG(n >= 0 && h >= 8 && w >= 8, "cpe_debug_preprocess: need n>=0, h,w>=8 (got %d,%d,%d)", n, h, w);
+    if (n == 0) return CPE_OK;
+    const int strips = (w + SW - 1) / SW;
+    CPE_CHECK_ARG((long long)n * strips < (1ll << 31), "cpe_debug_preprocess: too many strips (%d x %d)", n, strips);
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_preprocess_dbg, dim3((unsigned)(n * strips)), dim3(NT), 0, (hipStream_t)stream, gray, h, w, strips, mask, b, T);
+    CPE_CHECK_LAUNCH("k_preprocess_dbg");
     return CPE_OK;
 }

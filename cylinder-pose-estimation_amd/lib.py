@@ -29,6 +29,7 @@ _SIGS = {
     'cpe_profile_enable': (None, [C.c_int32]),
     'cpe_profile_report': (C.c_int32, [C.c_char_p, C.c_size_t]),
     'cpe_preprocess_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'cpe_debug_preprocess': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     'cpe_detect_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     'cpe_detect_constants': (C.c_int32, [C.c_int32, C.c_void_p]),
     'cpe_detect_grid_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t] +

@@ -36,8 +36,9 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 105   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
-                             104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region) */
+#define CPE_VERSION 106   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+                             104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
+                             106: cpe_debug_preprocess) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -81,6 +82,13 @@ CPE_API int32_t cpe_profile_report(char *csv, size_t cap);
  */
 CPE_API int32_t cpe_preprocess_batch(const uint8_t *gray, int32_t n, int32_t h, int32_t w, uint8_t *mask,
                              void *stream);
+
+/* cpe_preprocess_batch with the f64 planes of its last stage stored beside the mask: b f64[n,h,w], the smaller Hessian
+ * eigenvalue, and T f64[n,h,w], its Sauvola threshold (mask = 0 where b > T, 255 elsewhere).  The same arguments and
+ * rules as cpe_preprocess_batch; a separate instantiation of the same kernel, so the product kernel stays as it is.
+ * Test / debugging aid. */
+CPE_API int32_t cpe_debug_preprocess(const uint8_t *gray, int32_t n, int32_t h, int32_t w, uint8_t *mask, double *b,
+                                     double *T, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * detect_grid(input_img) for a batch of n grey frames (python_grid_detection_cylinder.py:68-112 ->

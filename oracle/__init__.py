@@ -83,6 +83,14 @@ def sauvola_mask(b):
     return m
 
 
+def sauvola_threshold(b):
+    """the Sauvola threshold plane T f64[h,w] that sauvola_mask compares b with (mask = 0 where b > T, 255 elsewhere)"""
+    b = np.ascontiguousarray(b, np.float64); h, w = b.shape
+    T = np.empty((h, w), np.float64)
+    lib().orc_sauvola_threshold(_p(b, C.c_double), h, w, _p(T, C.c_double))
+    return T
+
+
 def preprocess(gray, want_b=False):
     """load_and_preprocess_image: gray u8 -> (blurred u8, binary mask u8[, b f64])"""
     gray = _u8(gray); h, w = gray.shape

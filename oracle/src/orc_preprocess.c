@@ -144,9 +144,9 @@ ORC_API void orc_hessian_eigs(const double *G, int h, int w, double *emin, doubl
  * whole-row form beside it and counts the mask pixels that differ. */
 #define ORC_BOX_BX 8
 
-/* sauvola_threshold_fast(b, 15, 0.5, 128) and the compare / invert of :1798-1800.
- * mask = 255 where b <= T (ridges), 0 where b > T. */
-ORC_API void orc_sauvola_mask(const double *b, int h, int w, uint8_t *mask)
+/* sauvola_threshold_fast(b, 15, 0.5, 128) -> T (optional) and the compare / invert of :1798-1800 -> mask (optional).
+ * mask = 255 where b <= T (ridges), 0 where b > T.  The one box / threshold evaluation of both exports below. */
+static void sauvola(const double *b, int h, int w, double *T_out, uint8_t *mask)
 {
     /* cv2.boxFilter(b, CV_64F, (15,15), normalize=True, borderType=BORDER_REPLICATE), [ext] OpenCV 4.5.5 box_filter:
      * RowSum (restarted every ORC_BOX_BX columns, see above), then ColumnSum exactly as OpenCV runs it: SUM starts at 0,
@@ -194,11 +194,23 @@ ORC_API void orc_sauvola_mask(const double *b, int h, int w, uint8_t *mask)
             if (var < 0) var = 0;
             double sd = sqrt(var);
             double T = mean * (1 + 0.5 * ((sd / 128) - 1));
-            mask[(size_t)y * w + x] = (b[(size_t)y * w + x] > T) ? 0 : 255;
+            if (T_out) T_out[(size_t)y * w + x] = T;
+            if (mask) mask[(size_t)y * w + x] = (b[(size_t)y * w + x] > T) ? 0 : 255;
         }
     }
     free(rs);
     free(rs2);
+}
+
+ORC_API void orc_sauvola_mask(const double *b, int h, int w, uint8_t *mask)
+{
+    sauvola(b, h, w, NULL, mask);
+}
+
+/* the threshold plane T f64[h,w] of orc_sauvola_mask (mask = b > T ? 0 : 255) */
+ORC_API void orc_sauvola_threshold(const double *b, int h, int w, double *T)
+{
+    sauvola(b, h, w, T, NULL);
 }
 
 /* the whole stage: gray u8 -> blurred u8, binary mask u8 */
