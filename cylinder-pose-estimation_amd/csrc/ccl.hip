@@ -228,6 +228,27 @@ struct BitSrc {
     }
 };
 
+// the complement of a one-bit plane (the dark set of the blob sweep's first labelling is the complement of plane 0) in a stack
+// of planes per frame (frame f's plane at plane + f * frame_words).  Bits past the image read as set here: every walk masks its
+// columns with the rectangle and skips the rows outside it.
+struct NotBitSrc {
+    BitSrc b;
+    size_t frame_words;
+    __device__ __forceinline__ NotBitSrc frame(size_t f, int) const
+    {
+        return NotBitSrc{BitSrc{b.plane + f * frame_words, b.tc, b.plane_words}, frame_words};
+    }
+    __device__ __forceinline__ unsigned long long pack(int y, int x0) const { return ~b.pack(y, x0); }
+    __device__ __forceinline__ bool px(int y, int x) const { return !b.px(y, x); }
+    __device__ __forceinline__ void strip(int y8, int ya, int yb, int x0, unsigned long long (&m)[CCL_STRIP]) const
+    {
+        b.strip(y8, ya, yb, x0, m);
+#pragma unroll
+        for (int k = 0; k < CCL_STRIP; k++) m[k] = ~m[k];
+    }
+    __device__ __forceinline__ unsigned colbits(int y8, int ya, int yb, int x) const { return ~b.colbits(y8, ya, yb, x) & 0xffu; }
+};
+
 // labels of a sparse pass: every pixel of the set points at the first pixel of its run inside the word; a run that
 // continues from the word to the left points at that word's last pixel instead (a chain of at most one link per word,
 // parents always smaller: the same forest the row-wise k_ccl_init builds, a few links deeper)
@@ -392,6 +413,93 @@ __global__ __launch_bounds__(256) void k_ccl_roots64(SRC src0, int h, int w,
                 else set_overflow(st[f], OVF_ROOTS);
             }
         }
+    }
+}
+
+// k_ccl_finish of a sparse pass with pixel counts (count_mode 1; no touch, no bounding box), word-level: the pixels of a run
+// inside a word are one component, so a run costs one uf_find, its labels are stored as the root in 16-byte stores, and its
+// length goes to the root's count once (a thread sums consecutive runs of one root, a wavefront the threads' last sums).
+// Only the first pixel of a run can be a root (roots are the smallest index of their component).
+template <class SRC>
+__global__ __launch_bounds__(256) void k_ccl_finish64(SRC src0, int h, int w, FrameState *__restrict__ st, int use_rect,
+                                                      int *__restrict__ L, int *__restrict__ cnt, int *__restrict__ roots, int cnt_sel)
+{
+    const int WW = (w + 63) >> 6, strips = (h + CCL_STRIP - 1) / CCL_STRIP;
+    const size_t f = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int gi = blockIdx.x * 256 + threadIdx.x;
+    const Rect r = get_rect(st, f, use_rect, h, w);
+    const size_t N = (size_t)h * w;
+    const SRC src = src0.frame(f, h);
+    int *Lf = L + f * N, *cf = cnt + f * N;
+    const int sy = gi / WW, j = gi - sy * WW, x0 = j * 64;
+    const bool live = gi < WW * strips && !(r.x1 < r.x0 || x0 > r.x1 || x0 + 63 < r.x0);
+    if (!__ballot(live)) return;   // (wave-uniform: the appends and sums below are wavefront collectives)
+    const int ya = live ? max(sy * CCL_STRIP, r.y0) : 0, yb = live ? min(sy * CCL_STRIP + CCL_STRIP - 1, r.y1) : -1;
+    const unsigned long long cmask = live ? col_mask64(x0, r.x0, r.x1) : 0ull;
+    const bool hasL = live && x0 - 1 >= r.x0;
+    const int y8 = sy * CCL_STRIP;
+    unsigned long long rows[CCL_STRIP], any = 0;
+    unsigned lb = 0;
+    if (live) {
+        src.strip(y8, ya, yb, x0, rows);
+#pragma unroll
+        for (int k = 0; k < CCL_STRIP; k++) any |= (y8 + k >= ya && y8 + k <= yb) ? rows[k] & cmask : 0ull;
+        if (hasL && (any & 1ull)) lb = src.colbits(y8, ya, yb, x0 - 1);
+    }
+    int key = -1, kc = 0;   // root and pixel count not yet added to cnt
+#pragma unroll
+    for (int k = 0; k < CCL_STRIP; k++) {
+        const int y = y8 + k;
+        unsigned long long m = (live && y >= ya && y <= yb) ? rows[k] & cmask : 0ull;
+        const bool cL = (m & 1ull) && ((lb >> k) & 1u);
+        const int base = y * w + x0;
+        while (__ballot(m != 0)) {
+            int i = -1;
+            if (m) {
+                const unsigned long long low = m & (0ull - m), run = m & ~(m + low);
+                const int a = __ffsll((long long)low) - 1, e = a + __popcll(run);
+                m &= ~run;
+                // read-only walk, as in k_ccl_finish
+                const int root = uf_find(Lf, base + a);
+                if (root == base + a && !(a == 0 && cL)) {
+                    i = root;   // a run whose first pixel is the root: its labels already point there
+                } else {
+                    int b = a;
+                    while (b < e) {
+                        if ((b & 3) == 0 && b + 4 <= e) { *reinterpret_cast<int4 *>(Lf + base + b) = make_int4(root, root, root, root); b += 4; }
+                        else { Lf[base + b] = root; b++; }
+                    }
+                }
+                if (root != key) {
+                    if (key >= 0) atomicAdd(&cf[key], kc);
+                    key = root; kc = 0;
+                }
+                kc += e - a;
+            }
+            const unsigned long long rb = __ballot(i >= 0);
+            if (!rb) continue;
+            int q0 = 0;
+            const int leader = __ffsll((long long)rb) - 1;
+            if (lane == leader) q0 = atomicAdd(root_counter(st[f], cnt_sel), __popcll(rb));
+            q0 = __shfl(q0, leader, 64);
+            if (i >= 0) {
+                const int q = q0 + __popcll(rb & ((1ull << lane) - 1ull));
+                if (q < MAXROOTS) roots[f * MAXROOTS + q] = i;
+                else set_overflow(st[f], OVF_ROOTS);
+            }
+        }
+    }
+    // the threads' last sums: one atomic per root of the wavefront
+    unsigned long long active = __ballot(key >= 0);
+    while (active) {
+        const int leader = __ffsll((long long)active) - 1;
+        const int lk = __shfl(key, leader, 64);
+        const unsigned long long same = __ballot(key == lk) & active;
+        int c = (key == lk) ? kc : 0;
+        for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+        if (lane == leader) atomicAdd(&cf[lk], c);
+        active &= ~same;
     }
 }
 
@@ -976,6 +1084,27 @@ int ccl_run(const uint8_t *img, int n, int h, int w, int thr, int invert, int co
         CPE_KLAUNCH(k_ccl_finish, dim3((unsigned)((N + CCL_FIN_PX - 1) / CCL_FIN_PX), n), dim3(256), 0, s, img, h, w, thr, invert, st, use_rect, L,
                     holes_only ? (const uint8_t *)touch : (const uint8_t *)nullptr, count_mode, cnt, roots, nrect, sparse, flags & 1, cnt_sel);
     CPE_CHECK_LAUNCH("ccl_run");
+    return CPE_OK;
+}
+
+// The first labelling of the blob sweep's dark forest: ccl_run(img, ..., thr, invert 1, 4-connected, roots, count_mode 1,
+// use_rect 1, sparse 3), with the set {img <= thr} read as the complement of `planes` (img > thr as a one-bit plane, the first
+// of nplanes per frame, written on `s` before this) by the merge and the finish, and the word-level finish.  The init still reads the image: the sparse-3
+// links of the pixels outside the set need their grey-level buckets.  Rows that do not start on 16-byte boundaries: ccl_run.
+int ccl_dark_first(const uint8_t *img, const uint32_t *planes, int nplanes, int n, int h, int w, int thr, int *L, int *roots,
+                   int *cnt, FrameState *st, hipStream_t s)
+{
+    const bool words = (w % 16 == 0) && (((size_t)img & 15) == 0) && (((size_t)L & 15) == 0) && planes && nplanes >= 1;
+    if (!words) return ccl_run(img, n, h, w, thr, 1, 0, L, roots, false, nullptr, 1, cnt, 1, nullptr, st, s, 3, 0, 0);
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, (int *)nullptr, n, h, w, 0, 0);
+    CPE_KLAUNCH(k_ccl_init, dim3((n * h + CCL_INIT_ROWS - 1) / CCL_INIT_ROWS), dim3(256), 0, s, img, n * h, h, w, thr, 1, (const FrameState *)st, 1, L,
+                cnt, 3);
+    const dim3 gwords((unsigned)((((w + 63) / 64) * ((h + CCL_STRIP - 1) / CCL_STRIP) + 255) / 256), n);
+    const NotBitSrc src{BitSrc{bit_plane(planes, 0, h, w), bit_tile_cols(w), bit_plane_words(h, w)}, (size_t)nplanes * bit_plane_words(h, w)};
+    CPE_KLAUNCH(k_ccl_merge64<NotBitSrc>, gwords, dim3(256), 0, s, src, h, w, 0, (const FrameState *)st, 1, L);
+    CPE_KLAUNCH(k_ccl_finish64<NotBitSrc>, gwords, dim3(256), 0, s, src, h, w, st, 1, L, cnt, roots, 0);
+    CPE_CHECK_LAUNCH("ccl_dark_first");
     return CPE_OK;
 }
 

@@ -18,6 +18,9 @@ namespace cpe {
 int ccl_run(const uint8_t *img, int n, int h, int w, int thr, int invert, int conn8, int *L, int *roots, bool holes_only,
             uint8_t *touch, int count_mode, int *cnt, int use_rect, int *nrect, FrameState *st, hipStream_t s, int sparse = 0, int flags = 0, int cnt_sel = 0);
 int ccl_ctl(FrameState *st, int *nrect, int n, int h, int w, int op, hipStream_t s);
+int ccl_dark_first(const uint8_t *img, const uint32_t *planes, int nplanes, int n, int h, int w, int thr, int *L, int *roots,
+                   int *cnt, FrameState *st, hipStream_t s);
+int build_bitplanes(const uint8_t *img, int n, int h, int w, int thr0, int step, int nplanes, uint32_t *planes, hipStream_t s);
 int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const RegionBuffers &B, FrameState *st, hipStream_t s,
                  const RegionSide *side, const uint8_t *lplane, const RegionProbe *probe);
 int joints_mask_stage(int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s);
@@ -562,6 +565,58 @@ extern "C" int32_t cpe_debug_ccl(const uint8_t *img, int32_t n, int32_t h, int32
     return ccl_run(img, n, h, w, thr, invert, conn8, (int *)(base + L.off[P_LAB0]), want_roots ? (int *)(base + L.off[P_ROOTS]) : nullptr,
                    invert != 0, (uint8_t *)(base + L.off[P_TOUCH]), count_mode, (int *)(base + L.off[P_LAB1]), (want_bbox >> 1) & 1,
                    (want_bbox & 1) ? (int *)(base + L.off[P_NRECT]) : nullptr, st, s);
+}
+
+namespace cpe { namespace {
+__global__ void k_debug_rect(FrameState *st, int n, const int *rect)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < n) for (int k = 0; k < 4; k++) st[f].crect[k] = rect[4 * f + k];
+}
+__global__ void k_debug_n_roots(const FrameState *st, int n, int *n_roots)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < n) n_roots[f] = st[f].n_roots;
+}
+} }
+
+// The first labelling of the blob sweep's dark forest on a given image (tests): the set img <= thr inside rect (i32[n,4] x0, y0,
+// x1, y1), with the sweep's pre-linked runs outside it.  path 0: the byte-level passes of ccl_run; 1: the passes the region
+// stage runs (ccl_dark_first, reading the one-bit plane of img > thr).  Labels and counts (-1 where not written) go to
+// lab / cnt i32[n,h,w], the root list to roots i32[n,CPE_MAXROOTS_DEBUG] and its length to n_roots i32[n].
+static_assert(CPE_MAXROOTS_DEBUG == cpe::MAXROOTS, "cpe.h and cpe_dev.h disagree on the root-list capacity");
+extern "C" int32_t cpe_debug_dark_labels(const uint8_t *img, int32_t n, int32_t h, int32_t w, int32_t thr, const int32_t *rect,
+                                         int32_t path, void *ws, size_t ws_bytes, int32_t *lab, int32_t *cnt, int32_t *roots,
+                                         int32_t *n_roots, void *stream)
+{
+    CPE_CHECK_ARG(img && rect && ws && lab && cnt && roots && n_roots && n > 0 && h >= 64 && w >= 64 && (path == 0 || path == 1) &&
+                  thr >= 0 && thr + 160 <= 255,
+                  "cpe_debug_dark_labels: bad argument");
+    Layout L = make_layout(n, h, w);
+    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_debug_dark_labels: workspace too small or misaligned");
+    uint8_t *base = (uint8_t *)ws;
+    hipStream_t s = (hipStream_t)stream;
+    FrameState *st = (FrameState *)(base + L.off[P_STATE]);
+    int *lb = (int *)(base + L.off[P_LAB0]), *cb = (int *)(base + L.off[P_LAB1]), *rb = (int *)(base + L.off[P_ROOTS]);
+    uint32_t *bits = (uint32_t *)(base + L.off[P_BITS]);
+    const size_t N = (size_t)h * w;
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int *)nullptr);
+    CPE_KLAUNCH(k_debug_rect, dim3((n + 63) / 64), dim3(64), 0, s, st, n, (const int *)rect);
+    (void)hipMemsetAsync(lb, 0xff, N * n * sizeof(int), s);
+    (void)hipMemsetAsync(cb, 0xff, N * n * sizeof(int), s);
+    CPE_CHECK_LAUNCH("cpe_debug_dark_labels");
+    int rc;
+    if (path == 0) rc = ccl_run(img, n, h, w, thr, 1, 0, lb, rb, false, nullptr, 1, cb, 1, nullptr, st, s, 3);
+    else if ((rc = build_bitplanes(img, n, h, w, thr, 10, 17, bits, s)) == CPE_OK)   // the stack of planes the region stage keeps
+        rc = ccl_dark_first(img, bits, 17, n, h, w, thr, lb, rb, cb, st, s);
+    if (rc != CPE_OK) return rc;
+    (void)hipMemcpyAsync(lab, lb, N * n * sizeof(int), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(cnt, cb, N * n * sizeof(int), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(roots, rb, (size_t)n * MAXROOTS * sizeof(int), hipMemcpyDeviceToDevice, s);
+    CPE_KLAUNCH(k_debug_n_roots, dim3((n + 63) / 64), dim3(64), 0, s, (const FrameState *)st, n, n_roots);
+    CPE_CHECK_LAUNCH("cpe_debug_dark_labels");
+    return CPE_OK;
 }
 
 // The region stage of the cylinder target on a given sweep image (tests): region_stage as the product runs it, serially, with

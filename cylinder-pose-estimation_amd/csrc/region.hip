@@ -18,6 +18,8 @@ namespace cpe {
 int ccl_run(const uint8_t *img, int n, int h, int w, int thr, int invert, int conn8, int *L, int *roots, bool holes_only,
             uint8_t *touch, int count_mode, int *cnt, int use_rect, int *nrect, FrameState *st, hipStream_t s, int sparse = 0, int flags = 0, int cnt_sel = 0);
 int ccl_ctl(FrameState *st, int *nrect, int n, int h, int w, int op, hipStream_t s);
+int ccl_dark_first(const uint8_t *img, const uint32_t *planes, int nplanes, int n, int h, int w, int thr, int *L, int *roots,
+                   int *cnt, FrameState *st, hipStream_t s);
 
 namespace {
 
@@ -29,50 +31,73 @@ __device__ __forceinline__ int sat_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255
 struct ClaheGeom { int tilesX, tilesY, tw, th, eh, ew, clipLimit; float lutScale; };
 
 // lab_lut != 0: `gray` is a grey frame and L = c_lab_l[grey]; 0: `gray` already is the L plane of a colour frame (k_bgr2labl)
+// The histogram is taken of the input values and mapped through the LAB-L table once per bin at the end (the counts of L are
+// sums of counts of grey values).  A thread walks its pixels as runs of equal values held in registers and adds a run to LDS
+// only where the value changes: the background of a frame sits in a dozen bins, and one LDS atomic per pixel serialised on
+// those few addresses.  Each wavefront keeps HIST_COPIES lane-interleaved copies of its histogram, so the lanes that do add
+// in one instruction rarely meet on an address.
+constexpr int HIST_COPIES = 4;
 __global__ __launch_bounds__(256) void k_clahe_hist(const uint8_t *__restrict__ gray, int n, int h, int w, ClaheGeom g,
                                                     int strips, unsigned int *__restrict__ hist, int lab_lut)
 {
-    // one 256-bin histogram per wavefront (the background of a frame sits in a dozen bins: with one histogram for the
-    // workgroup every LDS atomic waited for the other wavefronts' hits on the same few addresses), four pixels per load
-    __shared__ unsigned int sh[4][256];
+    __shared__ unsigned int sh[4 * 256 * HIST_COPIES];   // [wavefront][value][copy]
     int b = blockIdx.x;
     int strip = b % strips; b /= strips;
     int tile = b % (g.tilesX * g.tilesY);
     int f = b / (g.tilesX * g.tilesY);
     int ty = tile / g.tilesX, tx = tile - ty * g.tilesX;
-    for (int k = 0; k < 4; k++) sh[k][threadIdx.x] = 0;
+    for (int k = threadIdx.x; k < 4 * 256 * HIST_COPIES; k += 256) sh[k] = 0;
     __syncthreads();
-    unsigned int *mine = sh[threadIdx.x >> 6];
+    unsigned int *mine = sh + (threadIdx.x >> 6) * 256 * HIST_COPIES + (threadIdx.x & (HIST_COPIES - 1));
     const uint8_t *im = gray + (size_t)f * h * w;
     int rows_per = (g.th + strips - 1) / strips;
     int y0 = strip * rows_per, y1 = min(g.th, y0 + rows_per);
     const int gx0 = tx * g.tw;
-    // the tile lies inside the frame and its rows start on dwords (frames whose size is a multiple of 4: no padding)
-    const bool fast = gx0 + g.tw <= w && ty * g.th + g.th <= h && (g.tw & 3) == 0 && (w & 3) == 0 && (((size_t)im + gx0) & 3) == 0;
-    if (fast) {
+    int cur = 0, run = 0;   // the run of equal values this thread has not added yet
+    auto add = [&](int v) {
+        if (v != cur) {
+            if (run) atomicAdd(&mine[cur * HIST_COPIES], (unsigned)run);
+            cur = v; run = 0;
+        }
+        run++;
+    };
+    // a dword: four pixels equal to the run's value extend it in one step
+    auto add4 = [&](uint32_t v4) {
+        if (v4 == (uint32_t)cur * 0x01010101u) { run += 4; return; }
+#pragma unroll
+        for (int k = 0; k < 4; k++) add((int)((v4 >> (8 * k)) & 255u));
+    };
+    // the tile lies inside the frame and its rows start on 16-byte / dword boundaries (frames whose size is a multiple of 4:
+    // no padding)
+    const bool inside = gx0 + g.tw <= w && ty * g.th + g.th <= h && (w & 3) == 0 && (g.tw & 3) == 0 && (((size_t)im + gx0) & 3) == 0;
+    if (inside && (g.tw & 15) == 0 && (w & 15) == 0 && (((size_t)im + gx0) & 15) == 0) {
+        const int qw = g.tw >> 4;
+        for (int i = threadIdx.x; i < (y1 - y0) * qw; i += 256) {
+            const int yy = i / qw, q = i - yy * qw;
+            const uint4 v = *reinterpret_cast<const uint4 *>(im + (size_t)(ty * g.th + y0 + yy) * w + gx0 + 16 * q);
+            add4(v.x); add4(v.y); add4(v.z); add4(v.w);
+        }
+    } else if (inside) {
         const int qw = g.tw >> 2;
         for (int i = threadIdx.x; i < (y1 - y0) * qw; i += 256) {
             const int yy = i / qw, q = i - yy * qw;
-            const uint32_t v4 = *reinterpret_cast<const uint32_t *>(im + (size_t)(ty * g.th + y0 + yy) * w + gx0 + 4 * q);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int v = (v4 >> (8 * k)) & 255u;
-                atomicAdd(&mine[lab_lut ? (int)c_lab_l[v] : v], 1u);
-            }
+            add4(*reinterpret_cast<const uint32_t *>(im + (size_t)(ty * g.th + y0 + yy) * w + gx0 + 4 * q));
         }
     } else {
         for (int yy = y0; yy < y1; yy++) {
             int gy = reflect101(ty * g.th + yy, h);
             for (int xx = threadIdx.x; xx < g.tw; xx += 256) {
                 int gx = reflect101(gx0 + xx, w);
-                const int v = im[(size_t)gy * w + gx];
-                atomicAdd(&mine[lab_lut ? (int)c_lab_l[v] : v], 1u);
+                add(im[(size_t)gy * w + gx]);
             }
         }
     }
+    if (run) atomicAdd(&mine[cur * HIST_COPIES], (unsigned)run);
     __syncthreads();
-    unsigned int v = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
-    if (v) atomicAdd(&hist[((size_t)f * g.tilesX * g.tilesY + tile) * 256 + threadIdx.x], v);
+    unsigned int v = 0;
+#pragma unroll
+    for (int k = 0; k < 4 * HIST_COPIES; k++) v += sh[((k / HIST_COPIES) * 256 + threadIdx.x) * HIST_COPIES + (k % HIST_COPIES)];
+    if (v) atomicAdd(&hist[((size_t)f * g.tilesX * g.tilesY + tile) * 256 + (lab_lut ? (int)c_lab_l[threadIdx.x] : (int)threadIdx.x)], v);
 }
 
 __global__ __launch_bounds__(256) void k_clahe_lut(unsigned int *__restrict__ hist, ClaheGeom g, uint8_t *__restrict__ lut)
@@ -2096,8 +2121,10 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
     for (int k = 0; k < NTHR; k++) {
         const int thr = 50 + 10 * k, epoch = k + 1;
         if (k == 0) {
-            // the bulk of the dark set: run-based labelling, flattened; pixels outside it start as singletons
-            if ((rc = ccl_run(B.cl, n, h, w, thr, 1, 0, B.lab, B.roots, false, nullptr, 1, B.cnt, 1, nullptr, st, ds, 3)) != CPE_OK) return rc;   // sparse 3: + the sweep's pre-linked runs
+            // the bulk of the dark set: run-based labelling, flattened; pixels outside it start as singletons, or as the
+            // sweep's pre-linked runs (ccl_run sparse 3).  The dark set is the complement of plane 0 (of NTHR per frame),
+            // written on `ds` above.
+            if ((rc = ccl_dark_first(B.cl, B.bits, NTHR, n, h, w, thr, B.lab, B.roots, B.cnt, st, ds)) != CPE_OK) return rc;
             CPE_KLAUNCH(k_sw_touch, dim3(frame_waves(4 * n, 2, 8), n), dim3(256), 0, ds, (const uint8_t *)B.cl, n, h, w, thr,
                         (const FrameState *)st, (const int *)B.lab, B.touch, epoch);
             // first entries of the pixels that join at the next step (bucket 1) | the roots of the labelling that are holes

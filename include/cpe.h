@@ -226,6 +226,18 @@ CPE_API int32_t cpe_debug_ccl(const uint8_t *img, int32_t n, int32_t h, int32_t 
                               int32_t conn8, int32_t count_mode, int32_t want_bbox, int32_t want_roots, void *ws,
                               size_t ws_bytes, void *stream);
 
+/* The first labelling of the blob sweep's dark forest (csrc/region.hip) on img u8[n,h,w]: the 4-connected components of
+ * img <= thr inside rect i32[n,4] (x0, y0, x1, y1 inclusive, device memory), flattened, with per-root pixel counts, the
+ * root list and, outside the set, the sweep's pre-linked runs of one grey-level bucket (0 <= thr <= 95).  path 0: the
+ * byte-level passes, 1: the passes the detector runs (w % 16 == 0: the set read from the first of 17 one-bit planes per
+ * frame, thresholds thr, thr + 10, ..., word-level finish).  Outputs (device
+ * memory): lab, cnt i32[n,h,w] (-1 where a pass writes nothing), roots i32[n,CPE_MAXROOTS_DEBUG] (any order), n_roots i32[n].
+ * Test / debugging aid. */
+#define CPE_MAXROOTS_DEBUG 262144
+CPE_API int32_t cpe_debug_dark_labels(const uint8_t *img, int32_t n, int32_t h, int32_t w, int32_t thr, const int32_t *rect,
+                                      int32_t path, void *ws, size_t ws_bytes, int32_t *lab, int32_t *cnt, int32_t *roots,
+                                      int32_t *n_roots, void *stream);
+
 /* The RETR_EXTERNAL rule of cv2.findContours as the detector applies it (util_cylinder.py:161, 1817; the other two call
  * sites, :1883 and :1968, keep only the largest contour, which is never a nested one): of the 8-connected components of
  * mask != 0, the raster-first pixels (y * w + x, any order) of those that do not lie inside a hole of another component.
