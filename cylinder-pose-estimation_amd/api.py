@@ -116,6 +116,28 @@ def detect_grid_batch(frames, ws=None, subpixel=False, subpixel_window=7, subpix
     return dict(xy=xy, id=ids, n=cnt, center=center, status=status, ws=ws, ws_generation=ws.generation)
 
 
+def debug_masks(binary, gray, mask_contour, rect, region_status, ws=None, target='cylinder'):
+    """the masks stage alone on given inputs (cpe_debug_masks, a test aid): binary, gray, mask_contour u8 [n,h,w], rect i32
+    [n,4] (x, y, w, h), region_status i32 [n] (0 or 1), all CUDA tensors on one device; mask_contour must be zero outside rect.
+    -> the workspace, whose plane() and state() read as after detect_grid_batch"""
+    ins = [binary, gray, mask_contour]
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape == binary.shape
+               for t in ins):
+        raise TypeError('binary, gray and mask_contour must be CUDA uint8 tensors [n,h,w] of one shape')
+    n, h, w = binary.shape
+    dev = binary.device
+    ins = [t.contiguous() for t in ins]
+    rect = rect.to(dev, torch.int32).contiguous().reshape(n, 4)
+    region_status = region_status.to(dev, torch.int32).contiguous().reshape(n)
+    if ws is None or not ws.fits(n, h, w) or ws.view.device != dev:
+        ws = DetectWorkspace(n, h, w, dev)
+    ws.use(n)
+    _lib.check(_lib.load().cpe_debug_masks(ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), rect.data_ptr(),
+                                           region_status.data_ptr(), n, h, w, TARGETS[target], ws.view.data_ptr(), ws.bytes,
+                                           torch.cuda.current_stream().cuda_stream), 'cpe_debug_masks')
+    return ws
+
+
 def tables_of(det):
     """detect_grid_batch output -> GridTables (the N x 4 [x y col row] matrices of makePyGridPts.m:41)"""
     return GridTables(det['xy'], det['id'], det['n'])

@@ -227,6 +227,26 @@ RegionBuffers region_buffers(uint8_t *base, const Layout &L, int h, int w)
     return R;
 }
 
+// the masks stage's buffers inside the workspace (cpe_detect_grid_batch*, cpe_debug_masks); R: region_buffers of the same call
+MaskBuffers mask_buffers(uint8_t *base, const Layout &L, const RegionBuffers &R)
+{
+#define PL(T, p) ((T *)(base + L.off[p]))
+    MaskBuffers M;
+    M.binary = PL(uint8_t, P_BINARY); M.hmask = PL(uint8_t, P_HMASK); M.vmask = PL(uint8_t, P_VMASK);
+    M.joints_mask = PL(uint8_t, P_JOINTS_MASK); M.tmpA = PL(uint8_t, P_TMPA); M.tmpB = PL(uint8_t, P_TMPB);
+    M.g19 = PL(uint8_t, P_G19); M.cm = PL(uint8_t, P_CM); M.mc = R.mc; M.roi_h = PL(uint8_t, P_ROI_H);
+    M.roi_v = PL(uint8_t, P_ROI_V); M.base_h = PL(uint8_t, P_BASE_H); M.base_v = PL(uint8_t, P_BASE_V);
+    M.exp_h = PL(uint8_t, P_EXP_H); M.exp_v = PL(uint8_t, P_EXP_V); M.touch = R.touch; M.bits = R.bits;
+    M.lab = R.lab; M.roots = R.roots; M.jtmp = PL(int, P_JTMP); M.joints = PL(int, P_JOINTS); M.verts = PL(int, P_VERTS);
+    M.best = R.best; M.segs = PL(SegRec, P_SEGS);
+    M.lab_p = PL(int, P_LABP); M.lab_s = PL(int, P_LABS); M.roots_p = PL(int, P_ROOTSP); M.roots_s = PL(int, P_ROOTSS);
+    M.best_s = PL(unsigned long long, P_BEST2);
+    M.fl_j = PL(unsigned long long, P_FLJ); M.jbits = PL(uint32_t, P_HPAR);
+    M.lab_h = nullptr; M.lab_v = nullptr;   // set by the caller once the region stage is done with the label planes
+#undef PL
+    return M;
+}
+
 }  // namespace
 }  // namespace cpe
 
@@ -316,17 +336,7 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
     uint8_t *anyplane = bgr && planar ? PL(uint8_t, P_CL) : nullptr;
     if (bgr) gray = PL(uint8_t, P_GRAYIN);
     RegionBuffers R = region_buffers(base, L, h, w);
-    MaskBuffers M;
-    M.binary = PL(uint8_t, P_BINARY); M.hmask = PL(uint8_t, P_HMASK); M.vmask = PL(uint8_t, P_VMASK);
-    M.joints_mask = PL(uint8_t, P_JOINTS_MASK); M.tmpA = PL(uint8_t, P_TMPA); M.tmpB = PL(uint8_t, P_TMPB);
-    M.g19 = PL(uint8_t, P_G19); M.cm = PL(uint8_t, P_CM); M.mc = R.mc; M.roi_h = PL(uint8_t, P_ROI_H);
-    M.roi_v = PL(uint8_t, P_ROI_V); M.base_h = PL(uint8_t, P_BASE_H); M.base_v = PL(uint8_t, P_BASE_V);
-    M.exp_h = PL(uint8_t, P_EXP_H); M.exp_v = PL(uint8_t, P_EXP_V); M.touch = R.touch; M.bits = R.bits;
-    M.lab = R.lab; M.roots = R.roots; M.jtmp = PL(int, P_JTMP); M.joints = PL(int, P_JOINTS); M.verts = PL(int, P_VERTS);
-    M.best = R.best; M.segs = PL(SegRec, P_SEGS);
-    M.lab_p = PL(int, P_LABP); M.lab_s = PL(int, P_LABS); M.roots_p = PL(int, P_ROOTSP); M.roots_s = PL(int, P_ROOTSS);
-    M.best_s = PL(unsigned long long, P_BEST2);
-    M.fl_j = PL(unsigned long long, P_FLJ); M.jbits = PL(uint32_t, P_HPAR);
+    MaskBuffers M = mask_buffers(base, L, R);
     // three chains that only meet in masks_stage: ridge mask -> line masks -> joints (stream 1), saturated spot
     // (stream 2), region (the caller's stream).  The side chains are mostly ALU / latency bound and fill the CUs the
     // region stage's serial kernels leave idle.  The helper streams and their events are per device and shared by all
@@ -638,4 +648,46 @@ extern "C" int32_t cpe_debug_blob_region(const uint8_t *img, int32_t n, int32_t 
     CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, (unsigned long long *)(base + L.off[P_BEST2]), R.nrect);
     CPE_CHECK_LAUNCH("k_state_init");
     return region_stage(img, n, h, w, 4.5, R, st, s, nullptr, nullptr, &probe);
+}
+
+namespace cpe { namespace {
+// the region stage's verdict as the caller gives it: what masks_stage reads of that stage besides mask_contour
+__global__ void k_debug_region(FrameState *st, int n, const int *rect, const int *status)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    for (int k = 0; k < 4; k++) st[f].rect[k] = rect[4 * f + k];
+    st[f].status = status[f];
+}
+} }
+
+// The masks stage on given inputs (tests): what detect_impl runs between the pre-process and the lines stage, in the same
+// order, serially on `stream`, with binary, mask_contour, rect and the region status taken from the caller.
+extern "C" int32_t cpe_debug_masks(const uint8_t *binary, const uint8_t *gray, const uint8_t *mask_contour, const int32_t *rect,
+                                   const int32_t *region_status, int32_t n, int32_t h, int32_t w, int32_t target, void *ws,
+                                   size_t ws_bytes, void *stream)
+{
+    CPE_CHECK_ARG(binary && gray && mask_contour && rect && region_status && ws && n > 0 && h >= 64 && w >= 64 && h <= 4096 &&
+                  w <= 4096 && (target == CPE_TARGET_CYLINDER || target == CPE_TARGET_PLANE), "cpe_debug_masks: bad argument");
+    Layout L = make_layout(n, h, w);
+    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_debug_masks: workspace too small or misaligned");
+    const int planar = target == CPE_TARGET_PLANE ? 1 : 0;
+    uint8_t *base = (uint8_t *)ws;
+    hipStream_t s = (hipStream_t)stream;
+    FrameState *st = (FrameState *)(base + L.off[P_STATE]);
+    RegionBuffers R = region_buffers(base, L, h, w);
+    MaskBuffers M = mask_buffers(base, L, R);
+    const size_t total = (size_t)n * h * w;
+    int rc;
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, M.best_s, R.nrect);
+    CPE_CHECK_HIP(hipMemcpyAsync(M.binary, binary, total, hipMemcpyDeviceToDevice, s));
+    CPE_CHECK_HIP(hipMemcpyAsync(R.mc, mask_contour, total, hipMemcpyDeviceToDevice, s));
+    CPE_KLAUNCH(k_debug_region, dim3((n + 63) / 64), dim3(64), 0, s, st, n, (const int *)rect, (const int *)region_status);
+    CPE_CHECK_LAUNCH("cpe_debug_masks");
+    if ((rc = joints_mask_stage(n, h, w, M, st, s)) != CPE_OK) return rc;
+    if ((rc = spot_stage(gray, n, h, w, M, st, s, planar)) != CPE_OK) return rc;
+    M.lab_h = (int *)(base + L.off[P_LAB0]); M.lab_v = (int *)(base + L.off[P_LAB1]);
+    if ((rc = masks_stage(gray, n, h, w, M, st, s, nullptr, planar, s)) != CPE_OK) return rc;
+    return blur7_u8(gray, n, h, w, st, (uint8_t *)(base + L.off[P_G7]), s);
 }

@@ -36,9 +36,9 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 106   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 107   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
-                             106: cpe_debug_preprocess) */
+                             106: cpe_debug_preprocess; 107: cpe_debug_masks) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -210,7 +210,9 @@ CPE_API int32_t cpe_bgr2gray_batch(const uint8_t *bgr, int32_t n, int32_t h, int
 #define CPE_PLANE_JOINTS 8        /* i32[CPE_MAXJ,2] cylinder_centroids in contour order */
 #define CPE_PLANE_STATE 9         /* per-frame state record (see csrc/cpe_dev.h FrameState) */
 #define CPE_PLANE_CLAHE 10        /* u8[h,w]  CLAHE'd L channel (planar target: the any-channel mask of colour frames) */
-#define CPE_PLANE_BLUR19 11       /* u8[h,w] */
+#define CPE_PLANE_BLUR19 11       /* u8[h,w]  cv2.GaussianBlur(gray, (19,19), 0) in the 64x32 tiles where it can exceed 240,
+                                     0 elsewhere: the spot chain only asks blurred > 240 (util_cylinder.py:1958), so the
+                                     contract is (plane > 240) == (blurred > 240) on every pixel, not the values below */
 #define CPE_PLANE_BLUR7 12        /* u8[h,w] */
 #define CPE_PLANE_SWEEP 14        /* i32[192] blob-sweep counters: [8+k] dark components, [25+k] bright components,
                                      [42+k] blobs of threshold 50+10k (k < 17); see csrc/region.hip SW_* */
@@ -257,6 +259,24 @@ CPE_API int32_t cpe_debug_external_components(const uint8_t *mask, int32_t n, in
 CPE_API int32_t cpe_debug_blob_region(const uint8_t *img, int32_t n, int32_t h, int32_t w, void *ws, size_t ws_bytes,
                                       float *kp, int32_t kp_cap, int32_t *n_kp, double *blobs, int32_t blob_cap,
                                       int32_t *n_blobs, void *stream);
+
+/* The masks stage of detect_grid on given inputs: extract_joints, the joint filter of find_cylinder_centroids_and_center,
+ * mask_roi_around_center and expands_line_roi (util_cylinder.py:35-237, 1805-2007; util_plane.py for CPE_TARGET_PLANE) --
+ * what cpe_detect_grid_batch_ex runs between the pre-process and the lines stage, in the same order, serially on `stream`
+ * (no helper streams), followed by the 7x7 blur of the indexing step.  Inputs (device memory):
+ *   binary        u8[n,h,w]  the pre-process's ridge mask (CPE_PLANE_BINARY)
+ *   gray          u8[n,h,w]  the grey frame (saturated spot, 7x7 blur)
+ *   mask_contour  u8[n,h,w]  the region stage's mask (CPE_PLANE_MASK_CONTOUR); must be zero outside rect, as the region stage
+ *                            guarantees: the roi kernel reads only the rectangle's pixels
+ *   rect          i32[n,4]   boundingRect (x, y, w, h) of the region, inside the frame (w, h >= 1)
+ *   region_status i32[n]     CPE_ST_OK or CPE_ST_NO_REGION
+ * target: CPE_TARGET_CYLINDER or CPE_TARGET_PLANE.  64 <= h, w <= 4096; ws: cpe_detect_workspace_bytes(n, h, w).  Afterwards
+ * the workspace holds what a cpe_detect_grid_batch_ex call holds there before its lines stage: the planes HMASK, VMASK,
+ * ROI_H / ROI_V, EXP_H / EXP_V, JOINTS, BLUR19, BLUR7 and the state record (status, r0, spot, n_joints, n_joints_all,
+ * n_seg, gang, glen, overflow).  Test / debugging aid. */
+CPE_API int32_t cpe_debug_masks(const uint8_t *binary, const uint8_t *gray, const uint8_t *mask_contour, const int32_t *rect,
+                                const int32_t *region_status, int32_t n, int32_t h, int32_t w, int32_t target, void *ws,
+                                size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Grid-point tables.  One table per image: xy f64[n,CPE_MAXP,2] pixel coordinates, id i32[n,CPE_MAXP,2]

@@ -275,14 +275,16 @@ static int flt_cmp(const void *a, const void *b)
 void orc_expand_line_roi_ex(const uint8_t *mask_roi, const uint8_t *mask_contour, int h, int w, int kernel_size, int minp,
                             int maxp, uint8_t *out, int *dbg);
 ORC_API void orc_expand_line_roi(const uint8_t *mask_roi, const uint8_t *mask_contour, int h, int w, int kernel_size,
-                                 uint8_t *out, int *dbg /* optional: [n_contours, n_valid] */)
+                                 uint8_t *out, int *dbg /* optional: as orc_expand_line_roi_ex */)
 {
     orc_expand_line_roi_ex(mask_roi, mask_contour, h, w, kernel_size, 5, 200, out, dbg);
 }
 
 /* minp / maxp: vertex-count window of the fragments (5..200 in util_cylinder.py:137, 8..700 in util_plane.py:140) */
 ORC_API void orc_expand_line_roi_ex(const uint8_t *mask_roi, const uint8_t *mask_contour, int h, int w, int kernel_size,
-                                    int minp, int maxp, uint8_t *out, int *dbg /* optional: [n_contours, n_valid] */)
+                                    int minp, int maxp, uint8_t *out,
+                                    int *dbg /* optional: [n_contours, n_valid, median angle, longest length] (the last two
+                                                as f32 bits; 0 without valid fragments) */)
 {
     const int patch = 15, half = patch / 2;
     size_t N = (size_t)h * w;
@@ -320,11 +322,14 @@ ORC_API void orc_expand_line_roi_ex(const uint8_t *mask_roi, const uint8_t *mask
         alist[nv++] = ang[i];
         if (length > glen) glen = length;
     }
-    if (dbg) { dbg[0] = nc; dbg[1] = nv; }
+    float gang = 0;
     if (nv > 0) {
         /* np.median of float32 values -> float32 (mean of the two middle ones for even counts) */
         qsort(alist, nv, sizeof(float), flt_cmp);
-        float gang = (nv & 1) ? alist[nv / 2] : (float)(((double)alist[nv / 2 - 1] + (double)alist[nv / 2]) / 2.0);
+        gang = (nv & 1) ? alist[nv / 2] : (float)(((double)alist[nv / 2 - 1] + (double)alist[nv / 2]) / 2.0);
+    }
+    if (dbg) { dbg[0] = nc; dbg[1] = nv; memcpy(&dbg[2], &gang, 4); memcpy(&dbg[3], &glen, 4); }
+    if (nv > 0) {
         uint8_t *ker = (uint8_t *)malloc((size_t)kernel_size * kernel_size);
         int *koff = (int *)malloc((size_t)kernel_size * kernel_size * 2 * sizeof(int));
         uint8_t *dil = (uint8_t *)calloc(N, 1);

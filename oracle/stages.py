@@ -148,12 +148,23 @@ def blur7(src):
     lib().orc_blur7(_p(src, C.c_uint8), src.shape[0], src.shape[1], _p(dst, C.c_uint8)); return dst
 
 
-def mask_roi_around_center(hmask, vmask, mask_contour, gray):
+def joints_in_rect(joints, rect):
+    """the joint filter of find_cylinder_centroids_and_center (util_cylinder.py:1913-1920) as orc_detect.c applies it: the
+    joints (x, y) inside boundingRect (x, y, w, h), half-open, in their contour order (no capacity: a caller compares the
+    count with CPE_MAXJ itself)"""
+    j = np.asarray(joints, np.int32).reshape(-1, 2)
+    x, y, rw, rh = rect
+    keep = (x <= j[:, 0]) & (j[:, 0] < x + rw) & (y <= j[:, 1]) & (j[:, 1] < y + rh)
+    return j[keep].copy()
+
+
+def mask_roi_around_center(hmask, vmask, mask_contour, gray, planar=False):
+    """-> (status 0 / 2, roi_h, roi_v, r0, spot (cx, cy, a, b)); planar: the planar script's plain circle (util_plane.py)"""
     hmask = _u8(hmask); vmask = _u8(vmask); mask_contour = _u8(mask_contour); gray = _u8(gray); h, w = gray.shape
     rh = np.zeros_like(gray); rv = np.zeros_like(gray); r0 = C.c_int(0); spot = np.zeros(4, np.int32)
-    st = lib().orc_mask_roi_around_center(_p(hmask, C.c_uint8), _p(vmask, C.c_uint8), _p(mask_contour, C.c_uint8),
-                                          _p(gray, C.c_uint8), h, w, _p(rh, C.c_uint8), _p(rv, C.c_uint8),
-                                          C.byref(r0), _p(spot, C.c_int))
+    st = lib().orc_mask_roi_around_center_ex(_p(hmask, C.c_uint8), _p(vmask, C.c_uint8), _p(mask_contour, C.c_uint8),
+                                             _p(gray, C.c_uint8), h, w, _p(rh, C.c_uint8), _p(rv, C.c_uint8),
+                                             C.byref(r0), _p(spot, C.c_int), 1 if planar else 0)
     return st, rh, rv, r0.value, tuple(int(v) for v in spot)
 
 
@@ -168,12 +179,19 @@ def rotated_line_kernel(size, angle):
     lib().orc_rotated_line_kernel(size, C.c_double(angle), _p(k, C.c_uint8)); return k
 
 
-def expand_line_roi(mask_roi, mask_contour, kernel_size):
+def expand_line_roi(mask_roi, mask_contour, kernel_size, min_pixels=5, max_pixels=200):
+    """-> (expanded mask, (n_contours, n_valid, median angle, longest length)); the last two as f32 bits (uint32), 0 when no
+    fragment is valid.  min_pixels / max_pixels: the fragments' vertex-count window (util_cylinder.py:137)"""
     mask_roi = _u8(mask_roi); mask_contour = _u8(mask_contour); h, w = mask_roi.shape
-    out = np.empty_like(mask_roi); dbg = np.zeros(2, np.int32)
-    lib().orc_expand_line_roi(_p(mask_roi, C.c_uint8), _p(mask_contour, C.c_uint8), h, w, kernel_size,
-                              _p(out, C.c_uint8), _p(dbg, C.c_int))
-    return out, tuple(int(v) for v in dbg)
+    out = np.empty_like(mask_roi); dbg = np.zeros(4, np.int32)
+    lib().orc_expand_line_roi_ex(_p(mask_roi, C.c_uint8), _p(mask_contour, C.c_uint8), h, w, kernel_size, min_pixels, max_pixels,
+                                 _p(out, C.c_uint8), _p(dbg, C.c_int))
+    return out, (int(dbg[0]), int(dbg[1]), int(dbg[2:3].view(np.uint32)[0]), int(dbg[3:4].view(np.uint32)[0]))
+
+
+def expand_line_roi_plane(mask_roi, mask_contour):
+    """expand_line_roi of util_plane.py (:140-215, called at :2806): kernel 201, 8 .. 700 vertices"""
+    return expand_line_roi(mask_roi, mask_contour, 201, 8, 700)
 
 
 def connected_components(mask):

@@ -8,6 +8,9 @@ import pytest
 import torch
 
 
+OVF_JOINTS = 8          # csrc/cpe_dev.h: more joints inside the region rectangle than CPE_MAXJ
+
+
 def _frames(h, w, n, seed):
     from cpe_amd import synth
     b = synth.render_batch(n, h, w, seed=seed, with_gt=False)
@@ -22,7 +25,7 @@ def _compare(cpe, orc, gpu, frames, check_planes=True, allow_overflow=None):
     torch.cuda.synchronize()
     ws = det['ws']
     planes = {k: ws.plane(k).cpu().numpy() for k in ('binary', 'hmask', 'vmask', 'mask_contour', 'roi_h', 'roi_v',
-                                                     'exp_h', 'exp_v', 'clahe')} if check_planes else {}
+                                                     'exp_h', 'exp_v', 'clahe', 'blur19')} if check_planes else {}
     joints = ws.plane('joints').cpu().numpy()
     sweep = ws.plane('sweep').cpu().numpy()
     state = ws.state()
@@ -37,6 +40,8 @@ def _compare(cpe, orc, gpu, frames, check_planes=True, allow_overflow=None):
             assert np.array_equal(planes['vmask'][i], ref['vmask']), tag
             assert np.array_equal(planes['clahe'][i], S.clahe(S.lab_l(npy[i]))), tag
             assert np.array_equal(planes['mask_contour'][i], ref['mask_contour']), tag
+            # the spot chain's blurred plane: only `> 240` is its contract (include/cpe.h CPE_PLANE_BLUR19), on every pixel
+            assert np.array_equal(planes['blur19'][i] > 240, S.blur19(npy[i]) > 240), tag
         _, blobs_per_thr = S.simple_blob_detector(S.clahe(S.lab_l(npy[i])))
         assert list(sweep[i, 42:42 + 17]) == list(blobs_per_thr), (tag, 'blobs per threshold')
         if allow_overflow and i in allow_overflow and int(det['status'][i]) == 6:
@@ -51,6 +56,10 @@ def _compare(cpe, orc, gpu, frames, check_planes=True, allow_overflow=None):
             continue
         assert state[i]['r0'] == ref['r0'] and (state[i]['spot0'], state[i]['spot1'], state[i]['spot2'], state[i]['spot3']) == tuple(ref['spot']), tag
         assert state[i]['n_joints'] == ref['n_cyl_joints'], tag
+        assert state[i]['n_joints_all'] == ref['n_joints'], tag
+        if not state[i]['overflow'] & OVF_JOINTS:      # the lines stage reads the joints in this order
+            want = S.joints_in_rect(ref['joints'], ref['rect'])
+            assert np.array_equal(joints[i, :state[i]['n_joints']], want), (tag, 'joints inside rect (values, order)')
         if check_planes:
             for k in ('roi_h', 'roi_v', 'exp_h', 'exp_v'):
                 assert np.array_equal(planes[k][i], ref[k]), (tag, k, int((planes[k][i] != ref[k]).sum()))

@@ -22,7 +22,9 @@ def test_plane_detect_matches_oracle(cpe, orc, gpu, h, w, seed):
     det = cpe.api.detect_grid_batch(frames.to(gpu), target='plane')
     torch.cuda.synchronize()
     ws = det['ws']
-    planes = {k: ws.plane(k).cpu().numpy() for k in ('binary', 'hmask', 'vmask', 'mask_contour', 'roi_h', 'roi_v', 'exp_h', 'exp_v')}
+    planes = {k: ws.plane(k).cpu().numpy() for k in ('binary', 'hmask', 'vmask', 'mask_contour', 'roi_h', 'roi_v', 'exp_h', 'exp_v',
+                                                     'blur19')}
+    joints = ws.plane('joints').cpu().numpy()
     state = ws.state()
     npy = frames.numpy()
     n_ok = 0
@@ -31,6 +33,7 @@ def test_plane_detect_matches_oracle(cpe, orc, gpu, h, w, seed):
         tag = f'frame {i}'
         for k in ('binary', 'hmask', 'vmask', 'mask_contour'):
             assert np.array_equal(planes[k][i], ref[k]), (tag, k, int((planes[k][i] != ref[k]).sum()))
+        assert np.array_equal(planes['blur19'][i] > 240, S.blur19(npy[i]) > 240), tag
         assert int(det['status'][i]) == ref['status'], (tag, state[i]['overflow'], ref['status'])
         if ref['status'] == 1:
             continue
@@ -39,6 +42,8 @@ def test_plane_detect_matches_oracle(cpe, orc, gpu, h, w, seed):
             continue
         assert state[i]['r0'] == ref['r0'] and (state[i]['spot0'], state[i]['spot1'], state[i]['spot2'], state[i]['spot3']) == tuple(ref['spot']), tag
         assert state[i]['n_joints'] == ref['n_cyl_joints'], tag
+        assert state[i]['n_joints_all'] == ref['n_joints'], tag
+        assert np.array_equal(joints[i, :state[i]['n_joints']], S.joints_in_rect(ref['joints'], ref['rect'])), (tag, 'joints')
         for k in ('roi_h', 'roi_v', 'exp_h', 'exp_v'):
             assert np.array_equal(planes[k][i], ref[k]), (tag, k, int((planes[k][i] != ref[k]).sum()))
         if ref['status'] != 0:
