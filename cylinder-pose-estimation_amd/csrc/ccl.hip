@@ -11,10 +11,12 @@
 //   touch  : (hole search only) components that reach the border of the working rectangle are flagged
 //   finish : flatten + per-component pixel counts (aggregated per wavefront before the atomic) + root list
 //            + bounding box of the set, all in one read of the label plane
-// When rows start on 16-byte boundaries, init (sparse passes), merge and the roots-only list have word-level forms
-// (k_ccl_init64 / k_ccl_merge64 / k_ccl_roots64): 64 pixels per thread and row as one bit mask, the label plane is
-// touched only where a run starts or two runs start to overlap.
-// A pass can be restricted to a per-frame rectangle (FrameState::crect).  The blob detector uses this:
+// When rows start on 16-byte boundaries, the init of a pass that leaves the labels outside the set untouched, the merge and the
+// component list have word-level forms (k_ccl_init64 / k_ccl_merge64 / k_ccl_roots64): 64 pixels per thread and row as one bit
+// mask, the label plane is touched only where a run starts or two runs start to overlap.
+// Entry points (cpe_dev.h): ccl_components (component list), ccl_unions (links only), ccl_dark_first and the general pass
+// ccl_label; each chooses its kernels.  A pass works inside a window of the frame (Window, cpe_dev.h).  WIN_SWEEP
+// (FrameState::crect) serves the blob detector:
 // every hole of the binarisation at threshold t lies inside the bounding box of the bright pixels at t,
 // which lies inside the box at t-10; a dark pixel on the box border is 4-connected to the outside, so
 // "touches the box" == "is not a hole".  HBM bytes per pixel inside the rectangle: 1 (image) + 4 written,
@@ -30,30 +32,17 @@ __device__ __forceinline__ bool pred(const uint8_t *img, size_t i, int thr, int 
     return (((int)img[i] > thr) ? 1 : 0) != invert;
 }
 
-struct Rect { int x0, y0, x1, y1; };
-__device__ __forceinline__ Rect get_rect(const FrameState *st, size_t f, int use_rect, int h, int w)
-{
-    Rect r;
-    if (use_rect == 1) { r.x0 = st[f].crect[0]; r.y0 = st[f].crect[1]; r.x1 = st[f].crect[2]; r.y1 = st[f].crect[3]; }
-    else if (use_rect == 2) {   // region rectangle (boundingRect of the hull) + 2 px: holds every mask derived from mask_contour
-        const int *q = st[f].rect;
-        r.x0 = max(q[0] - 2, 0); r.y0 = max(q[1] - 2, 0); r.x1 = min(q[0] + q[2] + 1, w - 1); r.y1 = min(q[1] + q[3] + 1, h - 1);
-    } else if (use_rect == 3) { r.x0 = st[f].srect[0]; r.y0 = st[f].srect[1]; r.x1 = st[f].srect[2]; r.y1 = st[f].srect[3]; }   // spot window (may be empty)
-    else { r.x0 = 0; r.y0 = 0; r.x1 = w - 1; r.y1 = h - 1; }
-    return r;
-}
-
 constexpr int CCL_INIT_ROWS = 16;
 __global__ __launch_bounds__(256) void k_ccl_init(const uint8_t *__restrict__ img, int rows_total, int h, int w,
-                                                  int thr, int invert, const FrameState *__restrict__ st, int use_rect,
-                                                  int *__restrict__ L, int *__restrict__ cnt, int sparse)
+                                                  int thr, int invert, const FrameState *__restrict__ st, Window win,
+                                                  int *__restrict__ L, int *__restrict__ cnt, CclOutside outside)
 {
     const int lane = threadIdx.x & 63;
     for (int rr = 0; rr < CCL_INIT_ROWS / 4; rr++) {   // CCL_INIT_ROWS rows per workgroup, one wavefront per row and turn
     const int row = (blockIdx.x * (CCL_INIT_ROWS / 4) + rr) * 4 + (threadIdx.x >> 6);
     if (row >= rows_total) return;
     const int f = row / h, y = row - f * h;
-    const Rect r = get_rect(st, f, use_rect, h, w);
+    const Rect r = window_rect(st, f, win, h, w);
     if (y < r.y0 || y > r.y1 || r.x1 < r.x0) continue;
     const size_t base = (size_t)row * w;  // == frame * h*w + y*w
     int carry_in = 0, carry_start = 0;
@@ -65,10 +54,10 @@ __global__ __launch_bounds__(256) void k_ccl_init(const uint8_t *__restrict__ im
         unsigned long long prev = (b << 1) | (unsigned long long)carry_in;
         unsigned long long starts = b & ~prev;
         if (cnt && valid) cnt[base + x] = 0;
-        // sparse 3: first node of a pixel outside the set = the first pixel of its run of one grey-level bucket inside this
-        // 64-pixel chunk (the run joins the dark forest of the blob sweep as one component; depth 1, like the run labels above)
+        // OUTSIDE_SWEEP_RUNS: first node of a pixel outside the set = the first pixel of its run of one grey-level bucket inside
+        // this 64-pixel chunk (the run joins the dark forest of the blob sweep as one component; depth 1, like the run labels above)
         int pre = -1;
-        if (sparse == 3) {
+        if (outside == OUTSIDE_SWEEP_RUNS) {
             const int lv = (valid && !in) ? sweep_level(img[base + x]) : 0;
             const int lvl_left = __shfl_up(lv, 1, 64);
             const bool same = lv > 0 && lane > 0 && lvl_left == lv;
@@ -79,12 +68,11 @@ __global__ __launch_bounds__(256) void k_ccl_init(const uint8_t *__restrict__ im
             unsigned long long m = starts & ((lane == 63) ? ~0ull : ((2ull << lane) - 1ull));
             int sx = m ? (x0 + 63 - __clzll(m)) : carry_start;
             L[base + x] = y * w + sx;
-        } else if (valid && sparse != 1) {
-            // sparse 1: labels outside the set are never read; 2: singletons (a growing set will absorb them later);
-            // 3 (the dark forest of the blob sweep): singletons, except that the pixels of a run that joins the set at one
-            // threshold (same grey-level bucket) start as children of the run's first pixel -- the run is one component the
-            // moment it joins, and these stores are coalesced, which the per-bucket lists' are not
-            L[base + x] = pre >= 0 ? pre : (sparse ? y * w + x : -1);
+        } else if (valid && outside != OUTSIDE_UNTOUCHED) {
+            // OUTSIDE_SWEEP_RUNS (the dark forest of the blob sweep): singletons, except that the pixels of a run that joins the
+            // set at one threshold (same grey-level bucket) start as children of the run's first pixel -- the run is one
+            // component the moment it joins, and these stores are coalesced, which the per-bucket lists' are not
+            L[base + x] = pre >= 0 ? pre : (outside != OUTSIDE_NONE ? y * w + x : -1);
         }
         bool last_in = (b >> 63) & 1ull;
         if (last_in) {
@@ -102,12 +90,12 @@ __global__ __launch_bounds__(256) void k_ccl_init(const uint8_t *__restrict__ im
 // arithmetic, and the grid stays small enough that workgroup dispatch is not what the pass waits for
 constexpr int CCL_BLK_PX = 8192;
 __global__ __launch_bounds__(256) void k_ccl_merge(const uint8_t *__restrict__ img, int h, int w, int thr,
-                                                   int invert, int conn8, const FrameState *__restrict__ st, int use_rect,
+                                                   int invert, int conn8, const FrameState *__restrict__ st, Window win,
                                                    int *__restrict__ L)
 {
     const int N = h * w;
     const size_t f = blockIdx.y;
-    const Rect r = get_rect(st, f, use_rect, h, w);
+    const Rect r = window_rect(st, f, win, h, w);
     const uint8_t *im = img + f * (size_t)N;
     int *Lf = L + f * (size_t)N;
     const bool aligned = ((((size_t)im) | (size_t)N) & 3) == 0;
@@ -254,14 +242,14 @@ struct NotBitSrc {
 // parents always smaller: the same forest the row-wise k_ccl_init builds, a few links deeper)
 template <class SRC>
 __global__ __launch_bounds__(256) void k_ccl_init64(SRC src0, int h, int w,
-                                                    const FrameState *__restrict__ st, int use_rect, int *__restrict__ L)
+                                                    const FrameState *__restrict__ st, Window win, int *__restrict__ L)
 {
     const int WW = (w + 63) >> 6, strips = (h + CCL_STRIP - 1) / CCL_STRIP;
     const size_t f = blockIdx.y;
     const int gi = blockIdx.x * 256 + threadIdx.x;
     if (gi >= WW * strips) return;
     const int sy = gi / WW, j = gi - sy * WW;
-    const Rect r = get_rect(st, f, use_rect, h, w);
+    const Rect r = window_rect(st, f, win, h, w);
     const int x0 = j * 64;
     if (r.x1 < r.x0 || x0 > r.x1 || x0 + 63 < r.x0) return;
     const int ya = max(sy * CCL_STRIP, r.y0), yb = min(sy * CCL_STRIP + CCL_STRIP - 1, r.y1);
@@ -302,7 +290,7 @@ __global__ __launch_bounds__(256) void k_ccl_init64(SRC src0, int h, int w,
 // same unions as k_ccl_merge
 template <class SRC>
 __global__ __launch_bounds__(256) void k_ccl_merge64(SRC src0, int h, int w,
-                                                     int conn8, const FrameState *__restrict__ st, int use_rect,
+                                                     int conn8, const FrameState *__restrict__ st, Window win,
                                                      int *__restrict__ L)
 {
     const int WW = (w + 63) >> 6, strips = (h + CCL_STRIP - 1) / CCL_STRIP;
@@ -310,7 +298,7 @@ __global__ __launch_bounds__(256) void k_ccl_merge64(SRC src0, int h, int w,
     const int gi = blockIdx.x * 256 + threadIdx.x;
     if (gi >= WW * strips) return;
     const int sy = gi / WW, j = gi - sy * WW;
-    const Rect r = get_rect(st, f, use_rect, h, w);
+    const Rect r = window_rect(st, f, win, h, w);
     const int x0 = j * 64;
     if (r.x1 < r.x0 || x0 > r.x1 || x0 + 63 < r.x0) return;
     const int ya = max(sy * CCL_STRIP, r.y0 + 1), yb = min(sy * CCL_STRIP + CCL_STRIP - 1, r.y1);
@@ -362,14 +350,14 @@ __global__ __launch_bounds__(256) void k_ccl_merge64(SRC src0, int h, int w,
 // component list of a roots-only pass: only the first pixel of a horizontal run can carry its own index
 template <class SRC>
 __global__ __launch_bounds__(256) void k_ccl_roots64(SRC src0, int h, int w,
-                                                     FrameState *__restrict__ st, int use_rect, const int *__restrict__ L,
-                                                     int *__restrict__ roots, int cnt_sel)
+                                                     FrameState *__restrict__ st, Window win, const int *__restrict__ L,
+                                                     int *__restrict__ roots, RootList list)
 {
     const int WW = (w + 63) >> 6, strips = (h + CCL_STRIP - 1) / CCL_STRIP;
     const size_t f = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int gi = blockIdx.x * 256 + threadIdx.x;
-    const Rect r = get_rect(st, f, use_rect, h, w);
+    const Rect r = window_rect(st, f, win, h, w);
     const size_t N = (size_t)h * w;
     const SRC src = src0.frame(f, h);
     const int *Lf = L + f * N;
@@ -405,7 +393,7 @@ __global__ __launch_bounds__(256) void k_ccl_roots64(SRC src0, int h, int w,
             if (!rb) continue;
             int base = 0;
             const int leader = __ffsll((long long)rb) - 1;
-            if (lane == leader) base = atomicAdd(root_counter(st[f], cnt_sel), __popcll(rb));
+            if (lane == leader) base = atomicAdd(root_counter(st[f], list), __popcll(rb));
             base = __shfl(base, leader, 64);
             if (cand) {
                 const int q = base + __popcll(rb & ((1ull << lane) - 1ull));
@@ -416,19 +404,19 @@ __global__ __launch_bounds__(256) void k_ccl_roots64(SRC src0, int h, int w,
     }
 }
 
-// k_ccl_finish of a sparse pass with pixel counts (count_mode 1; no touch, no bounding box), word-level: the pixels of a run
+// k_ccl_finish of a pass with pixel counts (COUNT_ALL; labels outside the set not read, no touch, no bounding box), word-level: the pixels of a run
 // inside a word are one component, so a run costs one uf_find, its labels are stored as the root in 16-byte stores, and its
 // length goes to the root's count once (a thread sums consecutive runs of one root, a wavefront the threads' last sums).
 // Only the first pixel of a run can be a root (roots are the smallest index of their component).
 template <class SRC>
-__global__ __launch_bounds__(256) void k_ccl_finish64(SRC src0, int h, int w, FrameState *__restrict__ st, int use_rect,
-                                                      int *__restrict__ L, int *__restrict__ cnt, int *__restrict__ roots, int cnt_sel)
+__global__ __launch_bounds__(256) void k_ccl_finish64(SRC src0, int h, int w, FrameState *__restrict__ st, Window win,
+                                                      int *__restrict__ L, int *__restrict__ cnt, int *__restrict__ roots, RootList list)
 {
     const int WW = (w + 63) >> 6, strips = (h + CCL_STRIP - 1) / CCL_STRIP;
     const size_t f = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int gi = blockIdx.x * 256 + threadIdx.x;
-    const Rect r = get_rect(st, f, use_rect, h, w);
+    const Rect r = window_rect(st, f, win, h, w);
     const size_t N = (size_t)h * w;
     const SRC src = src0.frame(f, h);
     int *Lf = L + f * N, *cf = cnt + f * N;
@@ -481,7 +469,7 @@ __global__ __launch_bounds__(256) void k_ccl_finish64(SRC src0, int h, int w, Fr
             if (!rb) continue;
             int q0 = 0;
             const int leader = __ffsll((long long)rb) - 1;
-            if (lane == leader) q0 = atomicAdd(root_counter(st[f], cnt_sel), __popcll(rb));
+            if (lane == leader) q0 = atomicAdd(root_counter(st[f], list), __popcll(rb));
             q0 = __shfl(q0, leader, 64);
             if (i >= 0) {
                 const int q = q0 + __popcll(rb & ((1ull << lane) - 1ull));
@@ -505,14 +493,14 @@ __global__ __launch_bounds__(256) void k_ccl_finish64(SRC src0, int h, int w, Fr
 
 // components of the set that reach the border of the working rectangle: touch[root] = 1
 __global__ __launch_bounds__(256) void k_ccl_touch(const int *__restrict__ L, int n, int h, int w,
-                                                   const FrameState *__restrict__ st, int use_rect,
+                                                   const FrameState *__restrict__ st, Window win,
                                                    uint8_t *__restrict__ touch)
 {
     const int per = 2 * w + 2 * h;
     int gi = blockIdx.x * blockDim.x + threadIdx.x;
     if (gi >= n * per) return;
     int f = gi / per, k = gi - f * per;
-    const Rect r = get_rect(st, f, use_rect, h, w);
+    const Rect r = window_rect(st, f, win, h, w);
     if (r.x1 < r.x0) return;
     const int rw = r.x1 - r.x0 + 1, rh = r.y1 - r.y0 + 1;
     int x, y;
@@ -526,18 +514,18 @@ __global__ __launch_bounds__(256) void k_ccl_touch(const int *__restrict__ L, in
     if (v >= 0) touch[f * N + uf_find(Lf, v)] = 1;
 }
 
-// component list only (roots-only passes): a root is a pixel of the set whose label is its own index.  Same walk as
+// component list (ccl_components): a root is a pixel of the set whose label is its own index.  Same walk as
 // k_ccl_merge (CCL_BLK_PX pixels per workgroup, 4 per thread and step, dword reject).
 __global__ __launch_bounds__(256) void k_ccl_roots4(const uint8_t *__restrict__ img, int h, int w, int thr, int invert,
-                                                    FrameState *__restrict__ st, int use_rect, const int *__restrict__ L,
-                                                    int *__restrict__ roots, int cnt_sel)
+                                                    FrameState *__restrict__ st, Window win, const int *__restrict__ L,
+                                                    int *__restrict__ roots, RootList list)
 {
     const int N = h * w;
     const size_t f = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const uint8_t *im = img + f * (size_t)N;
     const int *Lf = L + f * (size_t)N;
-    const Rect r = get_rect(st, f, use_rect, h, w);
+    const Rect r = window_rect(st, f, win, h, w);
     const bool aligned = ((((size_t)im) | (size_t)N) & 3) == 0;
     for (int it = 0; it < CCL_BLK_PX / 1024; it++) {
         const int i0 = blockIdx.x * CCL_BLK_PX + it * 1024 + threadIdx.x * 4;
@@ -570,7 +558,7 @@ __global__ __launch_bounds__(256) void k_ccl_roots4(const uint8_t *__restrict__ 
             if (!rb) continue;
             int base = 0;
             const int leader = __ffsll((long long)rb) - 1;
-            if (lane == leader) base = atomicAdd(root_counter(st[f], cnt_sel), __popcll(rb));
+            if (lane == leader) base = atomicAdd(root_counter(st[f], list), __popcll(rb));
             base = __shfl(base, leader, 64);
             if (cand[k]) {
                 const int q = base + __popcll(rb & ((1ull << lane) - 1ull));
@@ -581,24 +569,22 @@ __global__ __launch_bounds__(256) void k_ccl_roots4(const uint8_t *__restrict__ 
     }
 }
 
-// flatten + count + collect roots + bounding box, one read of the label plane.
-//   count_mode 0: none, 1: all pixels of the component, 2: interior pixels only (8 neighbours in the set, inside
-//   the image).  Exact prune bounds of the blob detector: a hole of >= 5000 pixels, or a bright component with
-//   >= 5000 interior pixels, has border-polygon area >= 5000 (polygon edges only cross the unit squares of their
-//   own end-point pixels).
+// flatten + count (CclCount) + collect roots + bounding box, one read of the label plane.  COUNT_INTERIOR gives exact prune
+// bounds to the blob detector: a hole of >= 5000 pixels, or a bright component with >= 5000 interior pixels, has
+// border-polygon area >= 5000 (polygon edges only cross the unit squares of their own end-point pixels).
 constexpr int CCL_FIN_PX = 8192;
 __global__ __launch_bounds__(256) void k_ccl_finish(const uint8_t *__restrict__ img, int h, int w, int thr,
-                                                    int invert, FrameState *__restrict__ st, int use_rect,
-                                                    int *__restrict__ L, const uint8_t *__restrict__ touch, int count_mode,
-                                                    int *__restrict__ cnt, int *__restrict__ roots, int *__restrict__ nrect, int sparse,
-                                                    int noflatten, int cnt_sel)
+                                                    int invert, FrameState *__restrict__ st, Window win,
+                                                    int *__restrict__ L, const uint8_t *__restrict__ touch, CclCount count,
+                                                    int *__restrict__ cnt, int *__restrict__ roots, int *__restrict__ nrect,
+                                                    CclOutside outside, RootList list)
 {
     // grid = (ceil(N / CCL_FIN_PX), n): a workgroup never straddles two frames, so every wave-level aggregate below is
     // per frame; many steps of 256 pixels per workgroup keep the grid (and its dispatch time) small
     const size_t N = (size_t)h * w;
     const size_t f = blockIdx.y;
     const int lane = threadIdx.x & 63;
-    const Rect r = get_rect(st, f, use_rect, h, w);
+    const Rect r = window_rect(st, f, win, h, w);
     {   // the workgroup's pixels lie in rows ya .. yb: outside the working rectangle there is nothing to flatten, count or list
         const size_t p0 = (size_t)blockIdx.x * CCL_FIN_PX;
         const int ya = (int)(p0 / w), yb = (int)((min(p0 + CCL_FIN_PX, N) - 1) / w);
@@ -611,11 +597,9 @@ __global__ __launch_bounds__(256) void k_ccl_finish(const uint8_t *__restrict__ 
     int root = -1, x = 0, y = 0;
     if ((size_t)i < N) {
         y = i / w; x = i - y * w;
-        if (!(y < r.y0 || y > r.y1 || x < r.x0 || x > r.x1) && (!sparse || pred(img + f * N, i, thr, invert))) {
+        if (!(y < r.y0 || y > r.y1 || x < r.x0 || x > r.x1) && (outside == OUTSIDE_NONE || pred(img + f * N, i, thr, invert))) {
             int v = L[gi];
-            if (noflatten) {
-                root = (v == i) ? i : -1;   // only the component list is wanted: a root is a root, flattened or not
-            } else if (v >= 0) {
+            if (v >= 0) {
                 // read-only walk: the pointer jumping of uf_find_c re-points nodes at *an* ancestor, and such a store from
                 // another thread's walk through this pixel may land after the store below and leave it one hop short
                 root = uf_find(L + f * N, v);
@@ -647,7 +631,7 @@ __global__ __launch_bounds__(256) void k_ccl_finish(const uint8_t *__restrict__ 
         if (rb) {
             int base = 0;
             const int leader = __ffsll((long long)rb) - 1;
-            if (lane == leader) base = atomicAdd(root_counter(st[f], cnt_sel), __popcll(rb));
+            if (lane == leader) base = atomicAdd(root_counter(st[f], list), __popcll(rb));
             base = __shfl(base, leader, 64);
             if (is_root) {
                 int k = base + __popcll(rb & ((1ull << lane) - 1ull));
@@ -656,9 +640,9 @@ __global__ __launch_bounds__(256) void k_ccl_finish(const uint8_t *__restrict__ 
             }
         }
     }
-    if (count_mode == 1 || count_mode == 2) {
+    if (count == COUNT_ALL || count == COUNT_INTERIOR) {
         bool c = in && !touched;
-        if (c && count_mode == 2) {
+        if (c && count == COUNT_INTERIOR) {
             const uint8_t *im = img + f * N;
             bool inter = x > 0 && x < w - 1 && y > 0 && y < h - 1;
             if (inter) {
@@ -681,22 +665,19 @@ __global__ __launch_bounds__(256) void k_ccl_finish(const uint8_t *__restrict__ 
     }
 }
 
-__global__ void k_ccl_ctl(FrameState *st, int *nrect, int n, int h, int w, int op, int cnt_sel)
+enum CtlOp : int { CTL_RESET_ROOTS, CTL_SWEEP_RECT };
+__global__ void k_ccl_ctl(FrameState *st, int *nrect, int n, CtlOp op, RootList list)
 {
     int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n) return;
     FrameState &S = st[f];
-    int *nr = nrect ? nrect + 16 * f : nullptr;
-    if (op == 0) {          // reset the root list
-        *root_counter(S, cnt_sel) = 0;
-    } else if (op == 1) {   // working rectangle = whole frame, accumulator empty
-        S.crect[0] = 0; S.crect[1] = 0; S.crect[2] = w - 1; S.crect[3] = h - 1;
-        nr[0] = INT_MAX; nr[1] = INT_MAX; nr[2] = -1; nr[3] = -1;
-    } else if (op == 2) {   // working rectangle = accumulated bounding box; accumulator emptied
+    if (op == CTL_RESET_ROOTS) {
+        *root_counter(S, list) = 0;
+    } else {   // CTL_SWEEP_RECT: working rectangle = accumulated bounding box; accumulator emptied
+        int *nr = nrect + 16 * f;
         for (int k = 0; k < 4; k++) { S.crect[k] = nr[k]; S.nrect[k] = nr[k]; }
         nr[0] = INT_MAX; nr[1] = INT_MAX; nr[2] = -1; nr[3] = -1;
     }
-    // op 3: keep crect (a superset of the next, smaller set), accumulator already empty
 }
 
 // Writers of the tiled one-bit planes (cpe_dev.h).  Every row of a plane's last tile row is written, the rows >= h as zeros,
@@ -836,15 +817,6 @@ int build_bitplanes(const uint8_t *img, int n, int h, int w, int thr0, int step,
     return CPE_OK;
 }
 
-int ccl_ctl(FrameState *st, int *nrect, int n, int h, int w, int op, hipStream_t s)
-{
-    CPE_LAUNCH_BEGIN();
-    CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, nrect, n, h, w, op, 0);
-    CPE_CHECK_LAUNCH("k_ccl_ctl");
-    return CPE_OK;
-}
-
-
 // ---- RETR_EXTERNAL: which components lie inside a hole of another one ------------------------------------------------
 // cv2.findContours(RETR_EXTERNAL) skips an outer border whose start pixel lies inside the outer border of a component
 // found earlier (icvFindNextContour: the last border mark passed on the row is positive), i.e. every component that sits
@@ -906,7 +878,7 @@ __device__ __forceinline__ unsigned long long flood_row(unsigned long long bg, u
 // knows; what is shadowed from both sides on its own row gets filled from the rows above / below in the next rounds.
 constexpr int FLOOD_BANDS = 16;
 __global__ __launch_bounds__(64 * FLOOD_BANDS) void k_outside_flood(const uint8_t *__restrict__ mask, int h, int w, FrameState *__restrict__ st,
-                                                                   int use_rect, unsigned long long *__restrict__ bgw_all,
+                                                                   Window win, unsigned long long *__restrict__ bgw_all,
                                                                    unsigned long long *__restrict__ out_all, size_t plane_words,
                                                                    const uint32_t *__restrict__ bits)
 {
@@ -914,7 +886,7 @@ __global__ __launch_bounds__(64 * FLOOD_BANDS) void k_outside_flood(const uint8_
     __shared__ int s_any[2];
     const size_t f = blockIdx.x;
     const int lane = threadIdx.x & 63, band = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), WW = (w + 63) >> 6;
-    const Rect r = get_rect(st, f, use_rect, h, w);
+    const Rect r = window_rect(st, f, win, h, w);
     if (r.x1 < r.x0 || r.y1 < r.y0) return;
     const uint8_t *im = mask + f * (size_t)h * w;
     const int btc = bit_tile_cols(w);
@@ -1031,97 +1003,118 @@ __global__ __launch_bounds__(64 * FLOOD_BANDS) void k_outside_flood(const uint8_
     if (!converged && threadIdx.x == 0) set_overflow(st[f], OVF_TRACE);
 }
 
-int outside_flood(const uint8_t *mask, int n, int h, int w, FrameState *st, int use_rect, unsigned long long *bgw,
+int outside_flood(const uint8_t *mask, int n, int h, int w, FrameState *st, Window win, unsigned long long *bgw,
                   unsigned long long *out, size_t plane_words, hipStream_t s, const uint32_t *bits)
 {
     CPE_CHECK_ARG(w <= 4096 && plane_words >= (size_t)h * ((w + 63) >> 6), "outside_flood: frame too wide or scratch too small");
     CPE_LAUNCH_BEGIN();
-    CPE_KLAUNCH(k_outside_flood, dim3(n), dim3(64 * FLOOD_BANDS), 0, s, mask, h, w, st, use_rect, bgw, out, plane_words, bits);
+    CPE_KLAUNCH(k_outside_flood, dim3(n), dim3(64 * FLOOD_BANDS), 0, s, mask, h, w, st, win, bgw, out, plane_words, bits);
     CPE_CHECK_LAUNCH("k_outside_flood");
     return CPE_OK;
 }
 
-// One labelling pass.  roots (optional): component list in st[].n_roots / roots; holes_only drops components
-// that reach the border of the working rectangle (needs `touch`); count_mode/cnt as in k_ccl_finish;
-// count_mode 3 only zeroes cnt inside the set's rectangle; sparse 1: labels of pixels outside the set are left untouched,
-// sparse 2: they are written as singletons (own raster index).
-// use_rect: restrict to st[].crect; nrect (optional, int[n][16]): accumulate the set's bounding box there.
-int ccl_run(const uint8_t *img, int n, int h, int w, int thr, int invert, int conn8, int *L, int *roots, bool holes_only,
-            uint8_t *touch, int count_mode, int *cnt, int use_rect, int *nrect, FrameState *st, hipStream_t s, int sparse, int flags, int cnt_sel)
+// ---- the labelling entry points (cpe_dev.h).  Each picks the kernels itself: word-level walks where rows start on 16-byte
+// boundaries, reading the one-bit plane of the set where the caller has one, the byte-level kernels elsewhere.
+static bool word_rows(const void *img, const int *L, int w) { return w % 16 == 0 && ((size_t)img & 15) == 0 && ((size_t)L & 15) == 0; }
+static dim3 word_grid(int n, int h, int w) { return dim3((unsigned)((((w + 63) / 64) * ((h + CCL_STRIP - 1) / CCL_STRIP) + 255) / 256), n); }
+
+// the links of the 8-connected set img > thr (labels outside it untouched); true: the word-level kernels made them
+static bool links8(const uint8_t *img, int n, int h, int w, int thr, Window win, int *L, FrameState *st, hipStream_t s)
 {
-    // flags: CCL_ROOTS_ONLY (1) = component list without flattening the label plane (needs roots, no counts / touch / bbox);
-    //        CCL_LINKS_ONLY (2) = stop after the unions: the consumer resolves the few labels it needs with uf_find
-    if (flags & 1) { CPE_CHECK_ARG(roots && !holes_only && !count_mode && !nrect, "ccl_run: roots-only pass with extra outputs"); }
-    const size_t N = (size_t)h * w, total = N * n;
-    const int rows = n * h;
-    CPE_LAUNCH_BEGIN();
-    if (roots) CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, (int *)nullptr, n, h, w, 0, cnt_sel);
-    // rows that start on 16-byte boundaries: word-level walks
-    const bool words = (w % 16 == 0) && (((size_t)img & 15) == 0) && (((size_t)L & 15) == 0);
-    const dim3 gwords((unsigned)((((w + 63) / 64) * ((h + CCL_STRIP - 1) / CCL_STRIP) + 255) / 256), n);
-    if (words && sparse == 1 && !count_mode)
-        CPE_KLAUNCH(k_ccl_init64<ByteSrc>, gwords, dim3(256), 0, s, (ByteSrc{img, w, thr, invert}), h, w, (const FrameState *)st, use_rect, L);
-    else
-        CPE_KLAUNCH(k_ccl_init, dim3((rows + CCL_INIT_ROWS - 1) / CCL_INIT_ROWS), dim3(256), 0, s, img, rows, h, w, thr, invert, (const FrameState *)st, use_rect, L,
-                    count_mode ? cnt : (int *)nullptr, sparse);
-    if (words)
-        CPE_KLAUNCH(k_ccl_merge64<ByteSrc>, gwords, dim3(256), 0, s, (ByteSrc{img, w, thr, invert}), h, w, conn8, (const FrameState *)st, use_rect, L);
-    else
-        CPE_KLAUNCH(k_ccl_merge, dim3((unsigned)((N + CCL_BLK_PX - 1) / CCL_BLK_PX), n), dim3(256), 0, s, img, h, w, thr, invert, conn8,
-                    (const FrameState *)st, use_rect, L);
-    if (holes_only) {
-        (void)hipMemsetAsync(touch, 0, total, s);
-        int per = 2 * w + 2 * h;
-        CPE_KLAUNCH(k_ccl_touch, dim3((n * per + 255) / 256), dim3(256), 0, s, (const int *)L, n, h, w, (const FrameState *)st,
-                    use_rect, touch);
+    const size_t N = (size_t)h * w;
+    if (word_rows(img, L, w)) {
+        const ByteSrc src{img, w, thr, 0};
+        CPE_KLAUNCH(k_ccl_init64<ByteSrc>, word_grid(n, h, w), dim3(256), 0, s, src, h, w, (const FrameState *)st, win, L);
+        CPE_KLAUNCH(k_ccl_merge64<ByteSrc>, word_grid(n, h, w), dim3(256), 0, s, src, h, w, 1, (const FrameState *)st, win, L);
+        return true;
     }
-    if ((flags & 1) && words)
-        CPE_KLAUNCH(k_ccl_roots64<ByteSrc>, gwords, dim3(256), 0, s, (ByteSrc{img, w, thr, invert}), h, w, st, use_rect, (const int *)L, roots, cnt_sel);
-    else if (flags & 1)
-        CPE_KLAUNCH(k_ccl_roots4, dim3((unsigned)((N + CCL_BLK_PX - 1) / CCL_BLK_PX), n), dim3(256), 0, s, img, h, w, thr, invert, st, use_rect, (const int *)L,
-                    roots, cnt_sel);
-    else if (!(flags & 2))
-        CPE_KLAUNCH(k_ccl_finish, dim3((unsigned)((N + CCL_FIN_PX - 1) / CCL_FIN_PX), n), dim3(256), 0, s, img, h, w, thr, invert, st, use_rect, L,
-                    holes_only ? (const uint8_t *)touch : (const uint8_t *)nullptr, count_mode, cnt, roots, nrect, sparse, flags & 1, cnt_sel);
-    CPE_CHECK_LAUNCH("ccl_run");
+    CPE_KLAUNCH(k_ccl_init, dim3((n * h + CCL_INIT_ROWS - 1) / CCL_INIT_ROWS), dim3(256), 0, s, img, n * h, h, w, thr, 0, (const FrameState *)st, win, L,
+                (int *)nullptr, OUTSIDE_UNTOUCHED);
+    CPE_KLAUNCH(k_ccl_merge, dim3((unsigned)((N + CCL_BLK_PX - 1) / CCL_BLK_PX), n), dim3(256), 0, s, img, h, w, thr, 0, 1, (const FrameState *)st, win, L);
+    return false;
+}
+
+int ccl_components(const uint8_t *img, const uint32_t *bits, int n, int h, int w, int thr, Window win, int *L, int *roots,
+                   RootList list, FrameState *st, hipStream_t s)
+{
+    const size_t N = (size_t)h * w;
+    const dim3 gw = word_grid(n, h, w);
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, (int *)nullptr, n, CTL_RESET_ROOTS, list);
+    if (bits && w % 16 == 0 && ((size_t)L & 15) == 0) {
+        const BitSrc src{bit_plane(bits, 0, h, w), bit_tile_cols(w), bit_plane_words(h, w)};
+        CPE_KLAUNCH(k_ccl_init64<BitSrc>, gw, dim3(256), 0, s, src, h, w, (const FrameState *)st, win, L);
+        CPE_KLAUNCH(k_ccl_merge64<BitSrc>, gw, dim3(256), 0, s, src, h, w, 1, (const FrameState *)st, win, L);
+        CPE_KLAUNCH(k_ccl_roots64<BitSrc>, gw, dim3(256), 0, s, src, h, w, st, win, (const int *)L, roots, list);
+    } else if (links8(img, n, h, w, thr, win, L, st, s)) {
+        CPE_KLAUNCH(k_ccl_roots64<ByteSrc>, gw, dim3(256), 0, s, (ByteSrc{img, w, thr, 0}), h, w, st, win, (const int *)L, roots, list);
+    } else {
+        CPE_KLAUNCH(k_ccl_roots4, dim3((unsigned)((N + CCL_BLK_PX - 1) / CCL_BLK_PX), n), dim3(256), 0, s, img, h, w, thr, 0, st, win, (const int *)L,
+                    roots, list);
+    }
+    CPE_CHECK_LAUNCH("ccl_components");
     return CPE_OK;
 }
 
-// The first labelling of the blob sweep's dark forest: ccl_run(img, ..., thr, invert 1, 4-connected, roots, count_mode 1,
-// use_rect 1, sparse 3), with the set {img <= thr} read as the complement of `planes` (img > thr as a one-bit plane, the first
-// of nplanes per frame, written on `s` before this) by the merge and the finish, and the word-level finish.  The init still reads the image: the sparse-3
-// links of the pixels outside the set need their grey-level buckets.  Rows that do not start on 16-byte boundaries: ccl_run.
+int ccl_unions(const uint8_t *mask, int n, int h, int w, Window win, int *L, FrameState *st, hipStream_t s)
+{
+    CPE_LAUNCH_BEGIN();
+    links8(mask, n, h, w, 0, win, L, st, s);
+    CPE_CHECK_LAUNCH("ccl_unions");
+    return CPE_OK;
+}
+
+int ccl_label(const uint8_t *img, int n, int h, int w, int *L, const CclPass &p, FrameState *st, hipStream_t s)
+{
+    const size_t N = (size_t)h * w;
+    CPE_LAUNCH_BEGIN();
+    if (p.roots) CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, (int *)nullptr, n, CTL_RESET_ROOTS, ROOTS_MAIN);
+    CPE_KLAUNCH(k_ccl_init, dim3((n * h + CCL_INIT_ROWS - 1) / CCL_INIT_ROWS), dim3(256), 0, s, img, n * h, h, w, p.thr, p.invert, (const FrameState *)st, p.win, L,
+                p.count ? p.cnt : (int *)nullptr, p.outside);
+    if (word_rows(img, L, w))
+        CPE_KLAUNCH(k_ccl_merge64<ByteSrc>, word_grid(n, h, w), dim3(256), 0, s, (ByteSrc{img, w, p.thr, p.invert}), h, w, p.conn8, (const FrameState *)st, p.win, L);
+    else
+        CPE_KLAUNCH(k_ccl_merge, dim3((unsigned)((N + CCL_BLK_PX - 1) / CCL_BLK_PX), n), dim3(256), 0, s, img, h, w, p.thr, p.invert, p.conn8,
+                    (const FrameState *)st, p.win, L);
+    if (p.touch) {
+        (void)hipMemsetAsync(p.touch, 0, N * n, s);
+        const int per = 2 * w + 2 * h;
+        CPE_KLAUNCH(k_ccl_touch, dim3((n * per + 255) / 256), dim3(256), 0, s, (const int *)L, n, h, w, (const FrameState *)st, p.win, p.touch);
+    }
+    CPE_KLAUNCH(k_ccl_finish, dim3((unsigned)((N + CCL_FIN_PX - 1) / CCL_FIN_PX), n), dim3(256), 0, s, img, h, w, p.thr, p.invert, st, p.win, L,
+                (const uint8_t *)p.touch, p.count, p.cnt, p.roots, p.nrect, p.outside, ROOTS_MAIN);
+    CPE_CHECK_LAUNCH("ccl_label");
+    return CPE_OK;
+}
+
+// The set {img <= thr} is read as the complement of plane 0 by the merge and the word-level finish.  The init still reads the
+// image: the links of OUTSIDE_SWEEP_RUNS need the grey-level buckets.  Rows that do not start on 16-byte boundaries: ccl_label.
 int ccl_dark_first(const uint8_t *img, const uint32_t *planes, int nplanes, int n, int h, int w, int thr, int *L, int *roots,
                    int *cnt, FrameState *st, hipStream_t s)
 {
-    const bool words = (w % 16 == 0) && (((size_t)img & 15) == 0) && (((size_t)L & 15) == 0) && planes && nplanes >= 1;
-    if (!words) return ccl_run(img, n, h, w, thr, 1, 0, L, roots, false, nullptr, 1, cnt, 1, nullptr, st, s, 3, 0, 0);
+    if (!(word_rows(img, L, w) && planes && nplanes >= 1)) {
+        CclPass p;
+        p.thr = thr; p.invert = 1; p.conn8 = 0; p.win = WIN_SWEEP; p.outside = OUTSIDE_SWEEP_RUNS;
+        p.count = COUNT_ALL; p.cnt = cnt; p.roots = roots;
+        return ccl_label(img, n, h, w, L, p, st, s);
+    }
     CPE_LAUNCH_BEGIN();
-    CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, (int *)nullptr, n, h, w, 0, 0);
-    CPE_KLAUNCH(k_ccl_init, dim3((n * h + CCL_INIT_ROWS - 1) / CCL_INIT_ROWS), dim3(256), 0, s, img, n * h, h, w, thr, 1, (const FrameState *)st, 1, L,
-                cnt, 3);
-    const dim3 gwords((unsigned)((((w + 63) / 64) * ((h + CCL_STRIP - 1) / CCL_STRIP) + 255) / 256), n);
+    CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, (int *)nullptr, n, CTL_RESET_ROOTS, ROOTS_MAIN);
+    CPE_KLAUNCH(k_ccl_init, dim3((n * h + CCL_INIT_ROWS - 1) / CCL_INIT_ROWS), dim3(256), 0, s, img, n * h, h, w, thr, 1, (const FrameState *)st, WIN_SWEEP, L,
+                cnt, OUTSIDE_SWEEP_RUNS);
+    const dim3 gw = word_grid(n, h, w);
     const NotBitSrc src{BitSrc{bit_plane(planes, 0, h, w), bit_tile_cols(w), bit_plane_words(h, w)}, (size_t)nplanes * bit_plane_words(h, w)};
-    CPE_KLAUNCH(k_ccl_merge64<NotBitSrc>, gwords, dim3(256), 0, s, src, h, w, 0, (const FrameState *)st, 1, L);
-    CPE_KLAUNCH(k_ccl_finish64<NotBitSrc>, gwords, dim3(256), 0, s, src, h, w, st, 1, L, cnt, roots, 0);
+    CPE_KLAUNCH(k_ccl_merge64<NotBitSrc>, gw, dim3(256), 0, s, src, h, w, 0, (const FrameState *)st, WIN_SWEEP, L);
+    CPE_KLAUNCH(k_ccl_finish64<NotBitSrc>, gw, dim3(256), 0, s, src, h, w, st, WIN_SWEEP, L, cnt, roots, ROOTS_MAIN);
     CPE_CHECK_LAUNCH("ccl_dark_first");
     return CPE_OK;
 }
 
-// ccl_run(mask, ..., thr 0, 8-connected, sparse 1, CCL_ROOTS_ONLY) for a mask whose one-bit plane (build_bitplanes, 1 plane)
-// already exists: the three word-level walks read the plane.  Needs w % 16 == 0 and a 16-byte aligned label plane; the caller
-// falls back to ccl_run otherwise (returns CPE_ERR_ARG without launching).
-int ccl_roots_bits(const uint32_t *bits, int n, int h, int w, int *L, int *roots, int use_rect, FrameState *st, hipStream_t s, int cnt_sel)
+int ccl_set_sweep_rect(FrameState *st, int *nrect, int n, hipStream_t s)
 {
-    if (!((w % 16 == 0) && (((size_t)L & 15) == 0) && bits && roots)) return CPE_ERR_ARG;
     CPE_LAUNCH_BEGIN();
-    CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, (int *)nullptr, n, h, w, 0, cnt_sel);
-    const dim3 gwords((unsigned)((((w + 63) / 64) * ((h + CCL_STRIP - 1) / CCL_STRIP) + 255) / 256), n);
-    const BitSrc src{bit_plane(bits, 0, h, w), bit_tile_cols(w), bit_plane_words(h, w)};
-    CPE_KLAUNCH(k_ccl_init64<BitSrc>, gwords, dim3(256), 0, s, src, h, w, (const FrameState *)st, use_rect, L);
-    CPE_KLAUNCH(k_ccl_merge64<BitSrc>, gwords, dim3(256), 0, s, src, h, w, 1, (const FrameState *)st, use_rect, L);
-    CPE_KLAUNCH(k_ccl_roots64<BitSrc>, gwords, dim3(256), 0, s, src, h, w, st, use_rect, (const int *)L, roots, cnt_sel);
-    CPE_CHECK_LAUNCH("ccl_roots_bits");
+    CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, nrect, n, CTL_SWEEP_RECT, ROOTS_MAIN);
+    CPE_CHECK_LAUNCH("k_ccl_ctl");
     return CPE_OK;
 }
 

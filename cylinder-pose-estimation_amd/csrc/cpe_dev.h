@@ -30,17 +30,6 @@ constexpr int MAXL = CPE_MAXL;   // grid lines per direction (label groups of th
 constexpr int MAXLP = CPE_MAXLP; // joints per label group: a limit, not a slot size (the groups share one pool of MAXJ points)
 constexpr int MAXSEG = 2048;     // line fragments per mask in the expansion stage
 
-struct CompRec {        // one traced border
-    int root;           // start pixel (raster index) = discovery key
-    int is_hole;
-    long long a00, a10, a01;  // Green sums (exact integers)
-    int nverts;         // CHAIN_APPROX_SIMPLE vertex count
-    int npts;           // CHAIN_APPROX_NONE point count
-    int minx, maxx, miny, maxy;
-    int voff;           // offset of stored vertices (or -1)
-    int pad;
-};
-
 struct BlobRec { double x, y, r; int key; int pad; };
 struct Group { int n; int pad; double c[GCAP][3]; };
 
@@ -133,23 +122,35 @@ enum { OVF_ROOTS = 1, OVF_LINES = 2, OVF_TRACE = 4, OVF_JOINTS = 8, OVF_VERTS = 
        OVF_EXPAND = 128, OVF_BLOBS = 256, OVF_DISTS = 512, OVF_GROUPS = 1024, OVF_SWEEP = 2048 };
 __device__ __forceinline__ void set_overflow(FrameState &S, int bit) { atomicOr(&S.overflow, bit); }
 
-// which per-frame component counter a labelling pass fills: 0 the main chain, 1 joints chain, 2 spot chain
-__device__ __forceinline__ int *root_counter(FrameState &S, int sel)
+// the per-frame component list a labelling pass fills; its counter is FrameState::n_roots, n_roots_p (joints chain) or n_roots_s
+// (spot chain, whose planes the vertical fragment mask reuses)
+enum RootList : int { ROOTS_MAIN = 0, ROOTS_JOINTS = 1, ROOTS_SPOT = 2 };
+__device__ __forceinline__ int *root_counter(FrameState &S, RootList list)
 {
-    return sel == 0 ? &S.n_roots : (sel == 1 ? &S.n_roots_p : &S.n_roots_s);
+    return list == ROOTS_MAIN ? &S.n_roots : (list == ROOTS_JOINTS ? &S.n_roots_p : &S.n_roots_s);
+}
+
+// the part of a frame that a labelling pass or a RETR_EXTERNAL flood works in: the frame; FrameState::crect, the blob sweep's
+// working rectangle (ccl_set_sweep_rect); the region rectangle (boundingRect of the hull) + 2 px, which holds every mask
+// derived from mask_contour; FrameState::srect, the window of the spot labelling (may be empty)
+enum Window : int { WIN_FRAME = 0, WIN_SWEEP = 1, WIN_REGION = 2, WIN_SPOT = 3 };
+struct Rect { int x0, y0, x1, y1; };   // inclusive; empty when x1 < x0
+__device__ __forceinline__ Rect window_rect(const FrameState *st, size_t f, Window win, int h, int w)   // frame f's window
+{
+    Rect r;
+    if (win == WIN_SWEEP) { r.x0 = st[f].crect[0]; r.y0 = st[f].crect[1]; r.x1 = st[f].crect[2]; r.y1 = st[f].crect[3]; }
+    else if (win == WIN_REGION) {
+        const int *q = st[f].rect;
+        r.x0 = max(q[0] - 2, 0); r.y0 = max(q[1] - 2, 0); r.x1 = min(q[0] + q[2] + 1, w - 1); r.y1 = min(q[1] + q[3] + 1, h - 1);
+    } else if (win == WIN_SPOT) { r.x0 = st[f].srect[0]; r.y0 = st[f].srect[1]; r.x1 = st[f].srect[2]; r.y1 = st[f].srect[3]; }
+    else { r.x0 = 0; r.y0 = 0; r.x1 = w - 1; r.y1 = h - 1; }
+    return r;
 }
 
 // ---------------------------------------------------------------- RETR_EXTERNAL (ccl.hip: k_outside_flood)
-// outer-background mask of every frame's window (use_rect 0: the frame, 2: region rectangle + 2 px): out[f][y][j] bit b = pixel
-// (64 j + b, y) is background and 4-connected to the window border.  bgw / out: n * plane_words u64 of scratch each,
-// plane_words >= h * ceil(w / 64).
-// Frames up to 4096 columns wide (one wavefront holds a row as 64 words of 64 pixels; wider frames are refused with
-// CPE_ERR_ARG by the callers' argument check).  A flood that has not converged after FLOOD_MAX_PASSES sweeps sets OVF_TRACE
-// (a sweep walks one band of rows, a sixteenth of the window: 65536 of them are the 4096 whole-window sweeps of round 2).
+// A flood that has not converged after FLOOD_MAX_PASSES sweeps sets OVF_TRACE (a sweep walks one band of rows, a sixteenth of
+// the window: 65536 of them are the 4096 whole-window sweeps of round 2).
 constexpr int FLOOD_MAX_PASSES = 65536;
-// bits (optional): the mask's one-bit plane (build_bitplanes with one plane per frame); the first sweep reads it instead of the bytes
-int outside_flood(const uint8_t *mask, int n, int h, int w, FrameState *st, int use_rect, unsigned long long *bgw,
-                  unsigned long long *out, size_t plane_words, hipStream_t s, const uint32_t *bits = nullptr);
 // a component (raster-first pixel `root`) is external iff the pixel west of that pixel is outer background
 // (cv2.findContours(RETR_EXTERNAL) drops the components that lie in a hole of another one)
 __device__ __forceinline__ bool comp_is_external(const unsigned long long *out_f, int w, int root, int win_x0)
@@ -157,10 +158,6 @@ __device__ __forceinline__ bool comp_is_external(const unsigned long long *out_f
     const int y = root / w, x = root - y * w;
     if (x - 1 < win_x0) return true;          // the window border / the image border is outer background
     return (out_f[(size_t)y * ((w + 63) >> 6) + ((x - 1) >> 6)] >> ((x - 1) & 63)) & 1ull;
-}
-__device__ __forceinline__ int window_x0(const FrameState &S, int use_rect)
-{
-    return use_rect == 2 ? max(S.rect[0] - 2, 0) : (use_rect == 1 ? S.crect[0] : 0);
 }
 
 // grey-level bucket of a CLAHE value for the blob sweep: 0: v <= 50 (dark at every threshold), b: 50 + 10 (b - 1) < v <= 50 + 10 b,
@@ -314,11 +311,6 @@ struct BitWin {
 };
 __device__ __forceinline__ unsigned nbr_mask(BitWin &bw, int x, int y) { return bw.nbrs(x, y); }
 
-// planes[t] = (img > thr0 + t * step), t < nplanes, in the tiled layout above; plane t of frame f is
-// bit_plane(planes, f * nplanes + t, h, w)
-int build_bitplanes(const uint8_t *img, int n, int h, int w, int thr0, int step, int nplanes, uint32_t *planes, hipStream_t s);
-int ccl_roots_bits(const uint32_t *bits, int n, int h, int w, int *L, int *roots, int use_rect, FrameState *st, hipStream_t s, int cnt_sel);
-
 // direction s = 0..7 counter-clockwise from east (x right, y down): DX = {1,1,0,-1,-1,-1,0,1}, DY = {0,-1,-1,-1,0,1,1,1},
 // stored as 2-bit fields (value + 1) so a step needs no table in memory
 __device__ __forceinline__ int trace_dx(int s) { return (int)((0x901Au >> (2 * s)) & 3u) - 1; }
@@ -357,18 +349,6 @@ __device__ bool trace_border(Pred &nz, int x0, int y0, bool is_hole, Visitor &vi
     return false;
 }
 
-struct MaskPred {
-    const uint8_t *m;
-    int w, h;
-    __device__ __forceinline__ bool operator()(int x, int y) const
-    {
-        // unconditional load from the clamped address: lets the 8 neighbour loads of one border step issue together
-        const bool inb = (unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h;
-        const int cx = min(max(x, 0), w - 1), cy = min(max(y, 0), h - 1);
-        const uint8_t v = m[(size_t)cy * w + cx];
-        return inb & (v != 0);
-    }
-};
 struct ThreshPred {  // binarised = img > t
     const uint8_t *m;
     int w, h, t;
@@ -423,5 +403,74 @@ __device__ __forceinline__ void moments_from_sums(long long a00, long long a10, 
         m01 = (double)a01 * db1_6;
     }
 }
+
+// ================================================================ host entry points shared between the translation units
+// ---- ccl.hip: one-bit planes, connected components, RETR_EXTERNAL
+// planes[t] = (img > thr0 + t * step), t < nplanes, in the tiled layout above; plane t of frame f is
+// bit_plane(planes, f * nplanes + t, h, w)
+int build_bitplanes(const uint8_t *img, int n, int h, int w, int thr0, int step, int nplanes, uint32_t *planes, hipStream_t s);
+
+// Component list: the 8-connected components of img > thr inside window `win` of every frame, listed by their first pixel
+// (raster index) in roots[f * MAXROOTS ...], their number in the counter of `list`.  bits (may be null): the one-bit plane of
+// the same set (build_bitplanes, one plane per frame), which the walks then read instead of img.  The labels of the set are
+// left as union-find links (a root is a pixel whose label is its own index); labels outside the set are not written.
+int ccl_components(const uint8_t *img, const uint32_t *bits, int n, int h, int w, int thr, Window win, int *L, int *roots,
+                   RootList list, FrameState *st, hipStream_t s);
+// Unions only: the links of a component list of mask != 0 (thr 0), for a consumer that resolves the few labels it needs with
+// uf_find (k_lines).
+int ccl_unions(const uint8_t *mask, int n, int h, int w, Window win, int *L, FrameState *st, hipStream_t s);
+// The first labelling of the blob sweep's dark forest: the 4-connected components of img <= thr inside WIN_SWEEP, flattened,
+// with pixel counts in cnt and the list in roots (ROOTS_MAIN); pixels outside the set get the sweep's pre-linked runs
+// (OUTSIDE_SWEEP_RUNS).  planes: img > thr as the first of nplanes one-bit planes per frame, written on `s` before this.
+int ccl_dark_first(const uint8_t *img, const uint32_t *planes, int nplanes, int n, int h, int w, int thr, int *L, int *roots,
+                   int *cnt, FrameState *st, hipStream_t s);
+// labels of the pixels outside the set: -1; not written (never read: component lists, unions); the sweep's pre-linked runs, a
+// singleton or, in a run of one grey-level bucket (sweep_level) inside a 64-pixel chunk, a link to the run's first pixel
+enum CclOutside : int { OUTSIDE_NONE = 0, OUTSIDE_UNTOUCHED = 1, OUTSIDE_SWEEP_RUNS = 3 };
+// pixel counts per root in cnt (zeroed inside the window unless COUNT_NONE): none, every pixel of the component, its interior
+// pixels (8 neighbours in the set, inside the image), none (cnt only zeroed)
+enum CclCount : int { COUNT_NONE = 0, COUNT_ALL = 1, COUNT_INTERIOR = 2, COUNT_ZERO = 3 };
+// options of the general pass; the set is {(img > thr) != invert}, 8-connected if conn8, else 4-connected
+struct CclPass {
+    int thr = 0, invert = 0, conn8 = 1;
+    Window win = WIN_FRAME;
+    CclOutside outside = OUTSIDE_NONE;
+    CclCount count = COUNT_NONE; int *cnt = nullptr;
+    uint8_t *touch = nullptr;   // holes only: components that reach the window's border are dropped (touch: scratch plane)
+    int *roots = nullptr;       // component list (ROOTS_MAIN)
+    int *nrect = nullptr;       // int[n][16]: accumulate the set's bounding box (x0, y0, x1, y1) there
+};
+// The general pass: the label of every pixel of the set flattened to its root (the component's first pixel), and what `p` asks for.
+int ccl_label(const uint8_t *img, int n, int h, int w, int *L, const CclPass &p, FrameState *st, hipStream_t s);
+// The blob sweep's working rectangle (WIN_SWEEP) = the bounding box accumulated in nrect (k_clahe_apply); nrect is emptied.
+int ccl_set_sweep_rect(FrameState *st, int *nrect, int n, hipStream_t s);
+
+// Outer-background mask of every frame's window (WIN_FRAME or WIN_REGION): out[f][y][j] bit b = pixel (64 j + b, y) is
+// background and 4-connected to the window border.  bgw / out: n * plane_words u64 of scratch each, plane_words >=
+// h * ceil(w / 64).  bits (may be null): the mask's one-bit plane (build_bitplanes with one plane per frame); the first sweep
+// reads it instead of the bytes.  Frames up to 4096 columns wide (one wavefront holds a row as 64 words of 64 pixels; wider
+// frames are refused with CPE_ERR_ARG by the callers' argument check).
+int outside_flood(const uint8_t *mask, int n, int h, int w, FrameState *st, Window win, unsigned long long *bgw,
+                  unsigned long long *out, size_t plane_words, hipStream_t s, const uint32_t *bits);
+
+// ---- region.hip
+int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const RegionBuffers &B, FrameState *st, hipStream_t s,
+                 const RegionSide *side, const uint8_t *lplane, const RegionProbe *probe);
+int region_stage_plane(const uint8_t *gray, int n, int h, int w, const RegionBuffers &B, FrameState *st, hipStream_t s);
+
+// ---- masks.hip
+int joints_mask_stage(int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s);
+int spot_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s, int planar);
+int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s,
+                const RegionSide *side, int planar, hipStream_t sj);
+int blur7_u8(const uint8_t *src, int n, int h, int w, const FrameState *st, uint8_t *dst, hipStream_t s);
+int blur7_bgr(const uint8_t *bgr, int n, int h, int w, const FrameState *st, uint8_t *dst, hipStream_t s);
+
+// ---- lines.hip
+size_t lines_ws_bytes();
+int lines_stage(const int *lab_h, const int *lab_v, const uint8_t *exp_h, const uint8_t *exp_v, const uint8_t *g7, int n, int h, int w, const int *joints,
+                FrameState *st, void *lines_ws, double *o_xy, int *o_id, int *o_n, double *o_center, const uint8_t *gray,
+                int subpixel, int sp_window, double sp_step, float *sp_scratch, int sp_cap, hipStream_t s, int planar);
+int lines_export(const void *lines_ws, int f, double *eq, int *npts, double *pts, int *n_lines, hipStream_t s);
 
 }  // namespace cpe

@@ -15,28 +15,6 @@
 
 namespace cpe {
 
-int ccl_run(const uint8_t *img, int n, int h, int w, int thr, int invert, int conn8, int *L, int *roots, bool holes_only,
-            uint8_t *touch, int count_mode, int *cnt, int use_rect, int *nrect, FrameState *st, hipStream_t s, int sparse = 0, int flags = 0, int cnt_sel = 0);
-int ccl_ctl(FrameState *st, int *nrect, int n, int h, int w, int op, hipStream_t s);
-int ccl_dark_first(const uint8_t *img, const uint32_t *planes, int nplanes, int n, int h, int w, int thr, int *L, int *roots,
-                   int *cnt, FrameState *st, hipStream_t s);
-int build_bitplanes(const uint8_t *img, int n, int h, int w, int thr0, int step, int nplanes, uint32_t *planes, hipStream_t s);
-int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const RegionBuffers &B, FrameState *st, hipStream_t s,
-                 const RegionSide *side, const uint8_t *lplane, const RegionProbe *probe);
-int joints_mask_stage(int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s);
-int spot_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s, int planar);
-int region_stage_plane(const uint8_t *gray, int n, int h, int w, const RegionBuffers &B, FrameState *st, hipStream_t s);
-int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s,
-                const RegionSide *side, int planar, hipStream_t sj);
-int blur7_u8(const uint8_t *src, int n, int h, int w, const FrameState *st, uint8_t *dst, hipStream_t s);
-int blur7_bgr(const uint8_t *bgr, int n, int h, int w, const FrameState *st, uint8_t *dst, hipStream_t s);
-size_t lines_ws_bytes();
-int lines_stage(const int *lab_h, const int *lab_v, const uint8_t *exp_h, const uint8_t *exp_v, const uint8_t *g7, int n, int h, int w, const int *joints,
-                FrameState *st, void *lines_ws, double *o_xy, int *o_id, int *o_n, double *o_center, const uint8_t *gray,
-                int subpixel, int sp_window, double sp_step, float *sp_scratch, int sp_cap, hipStream_t s, int planar);
-
-int lines_export(const void *lines_ws, int f, double *eq, int *npts, double *pts, int *n_lines, hipStream_t s);
-
 namespace {
 
 struct Layout {
@@ -549,11 +527,11 @@ extern "C" int32_t cpe_debug_external_components(const uint8_t *mask, int32_t n,
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int *)nullptr);
     CPE_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)n * sizeof(int), s));
-    if ((rc = ccl_run(mask, n, h, w, 0, 0, 1, (int *)(base + L.off[P_LAB0]), roots, false, nullptr, 0, nullptr, 0, nullptr, st, s, 1, 1, 0)) != CPE_OK) return rc;
+    if ((rc = ccl_components(mask, nullptr, n, h, w, 0, WIN_FRAME, (int *)(base + L.off[P_LAB0]), roots, ROOTS_MAIN, st, s)) != CPE_OK) return rc;
     const size_t fl_words = bit_plane_words(h, w);   // u64 words per frame of a flood plane (>= h * ceil(w / 64))
     unsigned long long *bgw = bit_plane((uint32_t *)(base + L.off[P_BITS]), 0, h, w);
     unsigned long long *out = bit_plane((uint32_t *)(base + L.off[P_BITS]), n, h, w);
-    if ((rc = outside_flood(mask, n, h, w, st, 0, bgw, out, fl_words, s)) != CPE_OK) return rc;
+    if ((rc = outside_flood(mask, n, h, w, st, WIN_FRAME, bgw, out, fl_words, s, nullptr)) != CPE_OK) return rc;
     CPE_KLAUNCH(k_list_external, dim3(32, n), dim3(256), 0, s, (const int *)roots, (const FrameState *)st, w, (const unsigned long long *)out, fl_words,
                 first_px, cap, count);
     CPE_CHECK_LAUNCH("k_list_external");
@@ -572,9 +550,13 @@ extern "C" int32_t cpe_debug_ccl(const uint8_t *img, int32_t n, int32_t h, int32
     uint8_t *base = (uint8_t *)ws;
     hipStream_t s = (hipStream_t)stream;
     FrameState *st = (FrameState *)(base + L.off[P_STATE]);
-    return ccl_run(img, n, h, w, thr, invert, conn8, (int *)(base + L.off[P_LAB0]), want_roots ? (int *)(base + L.off[P_ROOTS]) : nullptr,
-                   invert != 0, (uint8_t *)(base + L.off[P_TOUCH]), count_mode, (int *)(base + L.off[P_LAB1]), (want_bbox >> 1) & 1,
-                   (want_bbox & 1) ? (int *)(base + L.off[P_NRECT]) : nullptr, st, s);
+    CclPass p;
+    p.thr = thr; p.invert = invert; p.conn8 = conn8; p.win = (want_bbox >> 1) & 1 ? WIN_SWEEP : WIN_FRAME;
+    p.count = (CclCount)count_mode; p.cnt = (int *)(base + L.off[P_LAB1]);
+    p.touch = invert ? (uint8_t *)(base + L.off[P_TOUCH]) : nullptr;   // the background sets: holes only
+    p.roots = want_roots ? (int *)(base + L.off[P_ROOTS]) : nullptr;
+    p.nrect = (want_bbox & 1) ? (int *)(base + L.off[P_NRECT]) : nullptr;
+    return ccl_label(img, n, h, w, (int *)(base + L.off[P_LAB0]), p, st, s);
 }
 
 namespace cpe { namespace {
@@ -591,8 +573,8 @@ __global__ void k_debug_n_roots(const FrameState *st, int n, int *n_roots)
 } }
 
 // The first labelling of the blob sweep's dark forest on a given image (tests): the set img <= thr inside rect (i32[n,4] x0, y0,
-// x1, y1), with the sweep's pre-linked runs outside it.  path 0: the byte-level passes of ccl_run; 1: the passes the region
-// stage runs (ccl_dark_first, reading the one-bit plane of img > thr).  Labels and counts (-1 where not written) go to
+// x1, y1), with the sweep's pre-linked runs outside it.  path 0: the general pass (ccl_label); 1: the passes the region stage
+// runs (ccl_dark_first, reading the one-bit plane of img > thr).  Labels and counts (-1 where not written) go to
 // lab / cnt i32[n,h,w], the root list to roots i32[n,CPE_MAXROOTS_DEBUG] and its length to n_roots i32[n].
 static_assert(CPE_MAXROOTS_DEBUG == cpe::MAXROOTS, "cpe.h and cpe_dev.h disagree on the root-list capacity");
 extern "C" int32_t cpe_debug_dark_labels(const uint8_t *img, int32_t n, int32_t h, int32_t w, int32_t thr, const int32_t *rect,
@@ -617,8 +599,12 @@ extern "C" int32_t cpe_debug_dark_labels(const uint8_t *img, int32_t n, int32_t 
     (void)hipMemsetAsync(cb, 0xff, N * n * sizeof(int), s);
     CPE_CHECK_LAUNCH("cpe_debug_dark_labels");
     int rc;
-    if (path == 0) rc = ccl_run(img, n, h, w, thr, 1, 0, lb, rb, false, nullptr, 1, cb, 1, nullptr, st, s, 3);
-    else if ((rc = build_bitplanes(img, n, h, w, thr, 10, 17, bits, s)) == CPE_OK)   // the stack of planes the region stage keeps
+    if (path == 0) {
+        CclPass p;
+        p.thr = thr; p.invert = 1; p.conn8 = 0; p.win = WIN_SWEEP; p.outside = OUTSIDE_SWEEP_RUNS;
+        p.count = COUNT_ALL; p.cnt = cb; p.roots = rb;
+        rc = ccl_label(img, n, h, w, lb, p, st, s);
+    } else if ((rc = build_bitplanes(img, n, h, w, thr, 10, 17, bits, s)) == CPE_OK)   // the stack of planes the region stage keeps
         rc = ccl_dark_first(img, bits, 17, n, h, w, thr, lb, rb, cb, st, s);
     if (rc != CPE_OK) return rc;
     (void)hipMemcpyAsync(lab, lb, N * n * sizeof(int), hipMemcpyDeviceToDevice, s);

@@ -11,10 +11,6 @@
 
 namespace cpe {
 
-int ccl_run(const uint8_t *img, int n, int h, int w, int thr, int invert, int conn8, int *L, int *roots, bool holes_only,
-            uint8_t *touch, int count_mode, int *cnt, int use_rect, int *nrect, FrameState *st, hipStream_t s, int sparse = 0, int flags = 0, int cnt_sel = 0);
-int ccl_ctl(FrameState *st, int *nrect, int n, int h, int w, int op, hipStream_t s);
-
 namespace {
 
 // a-2 in one kernel: binary -> open(20x1) -> hmask, open(1x20) -> vmask, joints = hmask & vmask.
@@ -1026,7 +1022,7 @@ struct SegVisitor {
 constexpr int SEG_LPW = 4;
 template <int MINV, int MAXVS>
 __global__ __launch_bounds__(64) void k_seg_trace(const uint32_t *__restrict__ base_bits, int h, int w, int which,
-                                                  const int *__restrict__ roots, int cnt_sel, FrameState *__restrict__ st,
+                                                  const int *__restrict__ roots, RootList list, FrameState *__restrict__ st,
                                                   SegRec *__restrict__ segs /* n*MAXSEG */,
                                                   const unsigned long long *__restrict__ outside, size_t plane_words)
 {
@@ -1034,14 +1030,14 @@ __global__ __launch_bounds__(64) void k_seg_trace(const uint32_t *__restrict__ b
     if (st[f].status != CPE_ST_OK) return;
     __shared__ unsigned long long s_win[BW_ROWS * 64];
     __shared__ float s_pts[SEG_LPW][2 * MAXVS];
-    const int ncomp = min(*root_counter(st[f], cnt_sel), MAXROOTS);
+    const int ncomp = min(*root_counter(st[f], list), MAXROOTS);
     // Few, long borders: a wavefront steps at the pace of its slowest lane, and with 64 borders in flight nearly every
     // step waits for some lane's window refill (one memory round trip).  SEG_LPW borders per wavefront keep most steps
     // LDS-only; the other lanes idle.
     if (threadIdx.x >= SEG_LPW) return;
     for (int k = blockIdx.x * SEG_LPW + threadIdx.x; k < ncomp; k += gridDim.x * SEG_LPW) {
     const int root = roots[(size_t)f * MAXROOTS + k];
-    if (!comp_is_external(outside + f * plane_words, w, root, window_x0(st[f], 2))) continue;   // RETR_EXTERNAL (:161)
+    if (!comp_is_external(outside + f * plane_words, w, root, window_rect(st, f, WIN_REGION, h, w).x0)) continue;   // RETR_EXTERNAL (:161)
     BitWin nz{bit_plane(base_bits, f, h, w), w, h, s_win + threadIdx.x};
     float *pts = s_pts[threadIdx.x];     // the border's vertices live in LDS: 1.6 KB (5.6 KB planar) per lane were scratch
     SegVisitor sv{pts, MAXVS};
@@ -1339,12 +1335,10 @@ int joints_mask_stage(int n, int h, int w, const MaskBuffers &B, FrameState *st,
     }
     CPE_CHECK_LAUNCH("joints_mask_stage");
     int rc;
-    rc = ccl_roots_bits(B.jbits, n, h, w, B.lab_p, B.roots_p, 0, st, s, 1);          // labelling on the one-bit plane
-    if (rc == CPE_ERR_ARG) rc = ccl_run(B.joints_mask, n, h, w, 0, 0, 1, B.lab_p, B.roots_p, false, nullptr, 0, nullptr, 0, nullptr, st, s, 1, 1, 1);
-    if (rc != CPE_OK) return rc;
+    if ((rc = ccl_components(B.joints_mask, B.jbits, n, h, w, 0, WIN_FRAME, B.lab_p, B.roots_p, ROOTS_JOINTS, st, s)) != CPE_OK) return rc;
     // RETR_EXTERNAL (:1817): outer background of the joints mask (whole frame), on this chain, beside the region stage
     const size_t fl_words = (size_t)h * ((w + 63) / 64);
-    return outside_flood(B.joints_mask, n, h, w, st, 0, B.fl_j, B.fl_j + (size_t)n * fl_words, fl_words, s, B.jbits);
+    return outside_flood(B.joints_mask, n, h, w, st, WIN_FRAME, B.fl_j, B.fl_j + (size_t)n * fl_words, fl_words, s, B.jbits);
 }
 
 // a-5 head: saturated spot -> circle_mask, r0 (depends on the grey frame only: own stream)
@@ -1365,8 +1359,8 @@ int spot_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, F
         CPE_KLAUNCH(k_blur19_spot, dim3((unsigned)(n * tiles_y)), dim3(256), 0, s, gray, h, w, tiles_x, tiles_y, t19,
                     (const uint8_t *)flags, fstride, B.g19);
     }
-    // labelling of blurred > 240 inside st[].srect (use_rect 3): the only place it can hold
-    if ((rc = ccl_run(B.g19, n, h, w, 240, 0, 1, B.lab_s, B.roots_s, false, nullptr, 0, nullptr, 3, nullptr, st, s, 1, 1, 2)) != CPE_OK) return rc;
+    // labelling of blurred > 240 inside st[].srect (WIN_SPOT): the only place it can hold
+    if ((rc = ccl_components(B.g19, nullptr, n, h, w, 240, WIN_SPOT, B.lab_s, B.roots_s, ROOTS_SPOT, st, s)) != CPE_OK) return rc;
     CPE_KLAUNCH(k_spot_area, dim3(4, n), dim3(64), 0, s, B.g19, h, w, B.roots_s, st, B.best_s);
     (void)hipMemsetAsync(B.cm, 255, total, s);
     CPE_KLAUNCH(k_spot_ellipse, dim3(n), dim3(64), 0, s, B.g19, n, h, w, B.best_s, st, B.verts, B.cm, planar);
@@ -1412,19 +1406,17 @@ int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, 
         uint8_t *exp = which ? B.exp_v : B.exp_h;
         uint8_t *tmp = which ? B.tmpA : B.tmpB;
         int *lab = which ? B.lab_s : B.lab, *roots = which ? B.roots_s : B.roots;
-        const int sel = which ? 2 : 0;
+        const RootList list = which ? ROOTS_SPOT : ROOTS_MAIN;
         uint32_t *bits = reinterpret_cast<uint32_t *>(bit_plane(B.bits, which ? (size_t)n : 0, h, w));
         SegRec *segs = B.segs + (size_t)which * n * MAXSEG;
         // roi = open3x3(mask & circle_mask & mask_contour), base = close3x3(roi)
         CPE_KLAUNCH(k_roi_base, dim3((unsigned)(n * rb_bands)), dim3(256), rb_lds, q, lm, (const uint8_t *)B.cm, (const uint8_t *)B.mc,
                     h, w, rb_bands, (const FrameState *)st, roi, base, bits);   // + base's one-bit plane
-        rc = ccl_roots_bits(bits, n, h, w, lab, roots, 2, st, q, sel);         // labelling on the one-bit plane
-        if (rc == CPE_ERR_ARG) rc = ccl_run(base, n, h, w, 0, 0, 1, lab, roots, false, nullptr, 0, nullptr, 2, nullptr, st, q, 1, 1, sel);
-        if (rc != CPE_OK) return rc;
+        if ((rc = ccl_components(base, bits, n, h, w, 0, WIN_REGION, lab, roots, list, st, q)) != CPE_OK) return rc;
         unsigned long long *fl_bg = fl_plane(2 + 2 * which), *fl_out = fl_plane(3 + 2 * which);
-        if ((rc = outside_flood(base, n, h, w, st, 2, fl_bg, fl_out, fl_words, q, bits)) != CPE_OK) return rc;
-        if (planar) CPE_KLAUNCH((k_seg_trace<8, 700>), dim3(frame_waves(n, 32, 512), n), dim3(64), 0, q, (const uint32_t *)bits, h, w, which, (const int *)roots, sel, st, segs, (const unsigned long long *)fl_out, fl_words);
-        else CPE_KLAUNCH((k_seg_trace<5, 200>), dim3(frame_waves(n, 32, 512), n), dim3(64), 0, q, (const uint32_t *)bits, h, w, which, (const int *)roots, sel, st, segs, (const unsigned long long *)fl_out, fl_words);
+        if ((rc = outside_flood(base, n, h, w, st, WIN_REGION, fl_bg, fl_out, fl_words, q, bits)) != CPE_OK) return rc;
+        if (planar) CPE_KLAUNCH((k_seg_trace<8, 700>), dim3(frame_waves(n, 32, 512), n), dim3(64), 0, q, (const uint32_t *)bits, h, w, which, (const int *)roots, list, st, segs, (const unsigned long long *)fl_out, fl_words);
+        else CPE_KLAUNCH((k_seg_trace<5, 200>), dim3(frame_waves(n, 32, 512), n), dim3(64), 0, q, (const uint32_t *)bits, h, w, which, (const int *)roots, list, st, segs, (const unsigned long long *)fl_out, fl_words);
         CPE_KLAUNCH(k_seg_global, dim3(n), dim3(256), 0, q, st, which, (const SegRec *)segs);
         (void)hipMemsetAsync(tmp, 0, total, q);
         if (planar) CPE_KLAUNCH(k_seg_expand<EXP_MAXKS_PLANE>, dim3(frame_waves(n, 32, 256), n), dim3(256), 0, q, (const uint8_t *)base, h, w, which, st, (const SegRec *)segs, tmp, 201);
@@ -1433,8 +1425,7 @@ int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, 
                     (const uint8_t *)B.mc, h, w, (const FrameState *)st, exp);
         CPE_CHECK_LAUNCH("masks_stage expand");
         // cv2.connectedComponents of the expanded mask: unions only, k_lines resolves the joints' labels
-        if ((rc = ccl_run(exp, n, h, w, 0, 0, 1, which ? B.lab_v : B.lab_h, nullptr, false, nullptr, 0, nullptr, 2, nullptr, st, q, 1, 2)) != CPE_OK)
-            return rc;
+        if ((rc = ccl_unions(exp, n, h, w, WIN_REGION, which ? B.lab_v : B.lab_h, st, q)) != CPE_OK) return rc;
     }
     if (side) { (void)hipEventRecord(side->traced, side->s); (void)hipStreamWaitEvent(s, side->traced, 0); }
     return CPE_OK;

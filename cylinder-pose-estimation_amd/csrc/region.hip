@@ -15,12 +15,6 @@
 
 namespace cpe {
 
-int ccl_run(const uint8_t *img, int n, int h, int w, int thr, int invert, int conn8, int *L, int *roots, bool holes_only,
-            uint8_t *touch, int count_mode, int *cnt, int use_rect, int *nrect, FrameState *st, hipStream_t s, int sparse = 0, int flags = 0, int cnt_sel = 0);
-int ccl_ctl(FrameState *st, int *nrect, int n, int h, int w, int op, hipStream_t s);
-int ccl_dark_first(const uint8_t *img, const uint32_t *planes, int nplanes, int n, int h, int w, int thr, int *L, int *roots,
-                   int *cnt, FrameState *st, hipStream_t s);
-
 namespace {
 
 __constant__ uint8_t c_lab_l[256] = { 0, 1, 1, 2, 2, 3, 5, 5, 6, 7, 7, 8, 9, 9, 10, 11, 12, 12, 14, 15, 16, 17, 18, 19, 21, 23, 24, 25, 27, 27, 28, 30, 31, 33, 34, 35, 36, 38, 39, 40, 41, 42, 43, 45, 46, 47, 48, 50, 51, 52, 53, 54, 55, 57, 58, 59, 60, 61, 62, 63, 65, 66, 67, 68, 69, 70, 71, 73, 74, 75, 76, 77, 78, 79, 80, 82, 82, 83, 85, 86, 87, 88, 89, 90, 91, 92, 93, 94, 95, 97, 98, 99, 100, 101, 102, 103, 104, 105, 106, 107, 108, 109, 110, 111, 112, 113, 114, 115, 116, 117, 119, 119, 121, 122, 123, 124, 125, 126, 127, 128, 129, 130, 131, 132, 133, 134, 135, 136, 137, 138, 139, 140, 141, 142, 143, 144, 145, 146, 147, 148, 149, 150, 151, 152, 153, 154, 155, 156, 156, 157, 158, 159, 160, 161, 162, 163, 164, 165, 166, 167, 168, 169, 170, 171, 172, 173, 174, 175, 176, 177, 178, 179, 180, 180, 181, 182, 183, 184, 185, 186, 187, 188, 189, 190, 191, 192, 193, 194, 195, 196, 196, 197, 198, 199, 200, 201, 202, 203, 204, 205, 206, 207, 208, 208, 209, 210, 211, 212, 213, 214, 215, 216, 217, 218, 219, 219, 220, 221, 222, 223, 224, 225, 226, 227, 228, 228, 229, 230, 231, 232, 233, 234, 235, 236, 237, 237, 238, 239, 240, 241, 242, 243, 244, 245, 245, 246, 247, 248, 249, 250, 251, 252, 253, 253, 254, 255 };
@@ -2102,7 +2096,7 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
     } else if ((rc = build_bitplanes(B.cl, n, h, w, 50, 10, NTHR, B.bits, s)) != CPE_OK) return rc;
     // working rectangle for all 34 labelling passes = bounding box of the pixels brighter than the lowest threshold:
     // every brighter set and every hole of every binarisation lies inside it
-    if ((rc = ccl_ctl(st, B.nrect, n, h, w, 2, s)) != CPE_OK) return rc;   // crect = the box k_clahe_apply accumulated
+    if ((rc = ccl_set_sweep_rect(st, B.nrect, n, s)) != CPE_OK) return rc;   // crect = the box k_clahe_apply accumulated
     (void)hipMemsetAsync(B.touch, 0, total, s);
     const int swcap = std::max(32768, (int)std::min<long long>(1 << 20, (long long)N / 12));   // grid sizing only: entries one threshold may hold
     const dim3 gpx((unsigned)((N + 255) / 256), n), glist(frame_waves(4 * n, 4, swcap / 256), n), gtrace(frame_waves(n * NTHR, 8, swcap / 64), n, NTHR), gtrace_h(frame_waves(n * NTHR, 4, swcap / 64), n, NTHR), gbk(std::min(SW_GRID, std::max(16, 6144 / n)), n);
@@ -2122,7 +2116,7 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
         const int thr = 50 + 10 * k, epoch = k + 1;
         if (k == 0) {
             // the bulk of the dark set: run-based labelling, flattened; pixels outside it start as singletons, or as the
-            // sweep's pre-linked runs (ccl_run sparse 3).  The dark set is the complement of plane 0 (of NTHR per frame),
+            // sweep's pre-linked runs (OUTSIDE_SWEEP_RUNS).  The dark set is the complement of plane 0 (of NTHR per frame),
             // written on `ds` above.
             if ((rc = ccl_dark_first(B.cl, B.bits, NTHR, n, h, w, thr, B.lab, B.roots, B.cnt, st, ds)) != CPE_OK) return rc;
             CPE_KLAUNCH(k_sw_touch, dim3(frame_waves(4 * n, 2, 8), n), dim3(256), 0, ds, (const uint8_t *)B.cl, n, h, w, thr,
@@ -2193,9 +2187,8 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
     (void)hipMemsetAsync(B.mc, 0, total, s);
     CPE_KLAUNCH(k_discs, dim3(frame_waves(n, 4, MAXG / 4), n), dim3(256), 0, s, st, B.groups, h, w, B.ext);
     if ((rc = build_bitplanes(B.ext, n, h, w, 0, 0, 1, B.bits, s)) != CPE_OK) return rc;
-    rc = ccl_roots_bits(B.bits, n, h, w, B.lab, B.roots, 0, st, s, 0);   // the labelling reads the one-bit plane (1/8 of the bytes)
-    if (rc == CPE_ERR_ARG) rc = ccl_run(B.ext, n, h, w, 0, 0, 1, B.lab, B.roots, false, nullptr, 0, nullptr, 0, nullptr, st, s, 1, 1);
-    if (rc != CPE_OK) return rc;
+    // the labelling reads the one-bit plane (1/8 of the bytes)
+    if ((rc = ccl_components(B.ext, B.bits, n, h, w, 0, WIN_FRAME, B.lab, B.roots, ROOTS_MAIN, st, s)) != CPE_OK) return rc;
     CPE_KLAUNCH(k_region_area, dim3(frame_waves(n, 8, 64), n), dim3(64), 0, s, (const uint32_t *)B.bits, h, w, B.roots, st, B.best, 1);
     CPE_KLAUNCH(k_hull_fill, dim3(n), dim3(256), 0, s, (const uint32_t *)B.bits, h, w, B.best, st, B.lohi, B.hull, B.mc);
     CPE_KLAUNCH(k_hull_rows, dim3((unsigned)((h + HR_ROWS - 1) / HR_ROWS), n), dim3(256), 0, s, h, w, (const unsigned long long *)B.best, (const FrameState *)st, (const int *)B.hull, B.mc);
@@ -2230,7 +2223,7 @@ int region_stage_plane(const uint8_t *gray, int n, int h, int w, const RegionBuf
         const int thr = round == 0 ? 127 : 0;
         uint8_t *dst = round == 0 ? B.ext : B.mc;
         if (round == 1) CPE_KLAUNCH(k_best_reset, dim3((n + 63) / 64), dim3(64), 0, s, n, B.best);
-        if ((rc = ccl_run(img, n, h, w, thr, 0, 1, B.lab, B.roots, false, nullptr, 0, nullptr, 0, nullptr, st, s, 1, 1)) != CPE_OK) return rc;
+        if ((rc = ccl_components(img, nullptr, n, h, w, thr, WIN_FRAME, B.lab, B.roots, ROOTS_MAIN, st, s)) != CPE_OK) return rc;
         if ((rc = build_bitplanes(img, n, h, w, thr, 0, 1, B.bits, s)) != CPE_OK) return rc;
         CPE_KLAUNCH(k_region_area, dim3(frame_waves(n, 8, 64), n), dim3(64), 0, s, (const uint32_t *)B.bits, h, w, B.roots, st, B.best, 0);
         CPE_KLAUNCH(k_hull_fill, dim3(n), dim3(256), 0, s, (const uint32_t *)B.bits, h, w, B.best, st, B.lohi, B.hull, dst);

@@ -1,6 +1,6 @@
 """The first labelling of the blob sweep's dark forest (cpe_debug_dark_labels, include/cpe.h): the passes the region stage
-runs (path 1: the set read as the complement of the one-bit plane of img > thr, word-level finish) against the byte-level
-passes of ccl_run (path 0), bit for bit: labels inside and outside the set (the sweep's pre-linked runs), per-root pixel
+runs (path 1, ccl_dark_first: the set read as the complement of the one-bit plane of img > thr, word-level finish) against the
+general pass ccl_label (path 0, byte-level passes), bit for bit: labels inside and outside the set (the sweep's pre-linked runs), per-root pixel
 counts, the root list (as a set) and its length.  Path 1 reads the first of a stack of 17 planes per frame, as the region
 stage keeps them, and every case has several frames.
 
