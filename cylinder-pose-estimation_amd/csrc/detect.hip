@@ -636,6 +636,24 @@ extern "C" int32_t cpe_debug_blob_region(const uint8_t *img, int32_t n, int32_t 
     return region_stage(img, n, h, w, 4.5, R, st, s, nullptr, nullptr, &probe);
 }
 
+// LAB-L + CLAHE of grey frames and the 17 threshold planes, as the region stage makes them (tests)
+extern "C" int32_t cpe_debug_clahe_planes(const uint8_t *gray, int32_t n, int32_t h, int32_t w, int32_t fused, void *ws, size_t ws_bytes,
+                                          uint8_t *cl, uint32_t *planes, int32_t *buckets, int32_t *box, void *stream)
+{
+    CPE_CHECK_ARG(gray && ws && cl && planes && buckets && box && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096,
+                  "cpe_debug_clahe_planes: bad argument");
+    Layout L = make_layout(n, h, w);
+    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_debug_clahe_planes: workspace too small or misaligned");
+    uint8_t *base = (uint8_t *)ws;
+    hipStream_t s = (hipStream_t)stream;
+    FrameState *st = (FrameState *)(base + L.off[P_STATE]);
+    RegionBuffers R = region_buffers(base, L, h, w);
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, (unsigned long long *)(base + L.off[P_BEST2]), R.nrect);
+    CPE_CHECK_LAUNCH("k_state_init");
+    return clahe_front_probe(gray, n, h, w, fused, R, s, cl, planes, buckets, box);
+}
+
 namespace cpe { namespace {
 // the region stage's verdict as the caller gives it: what masks_stage reads of that stage besides mask_contour
 __global__ void k_debug_region(FrameState *st, int n, const int *rect, const int *status)

@@ -255,6 +255,205 @@ __global__ __launch_bounds__(256) void k_clahe_apply(const uint8_t *__restrict__
     }
 }
 
+// The same pass when rows start on 16-byte boundaries and the CLAHE tiles are at least 128 columns wide and 80 rows high: it
+// also writes the 17 threshold planes (img > 50 + 10 t, the 64 x 8 tiles of cpe_dev.h), which k_bitplanes64 made from a
+// second read of the image.  A thread owns one half (32 pixels) of a 64-pixel word of one row; thread order (word column,
+// half, row in the tile), so 16 consecutive lanes write one tile of every plane (4-byte stores, one 64-byte line).  A
+// workgroup is one wavefront (larger ones waited for whole-CU room beside k_preprocess of the other lane: 9.6 instead of
+// 1.4 ms per launch); it owns CA_WORDS word columns of CA_TROWS tile rows and walks the tile rows one after the other.
+// What the per-pixel form computed again for every pixel is taken once: the column weights (xa, xa1) sit in LDS per column, the row weights once per row, and the four table bytes a pixel
+// interpolates (LAB-L mapping included) are one u32 of a table indexed by the input value and the pair of tile columns /
+// rows -- one LDS read instead of five.  Within a thread's 32 pixels the tile column pair changes at most once (tiles >= 128
+// columns wide): at `split`.  Bucket sizes come from the planes: pixels of bucket b = popcount(plane b - 1) -
+// popcount(plane b), summed in registers, no LDS atomic per pixel.  The f32 expression and its order are those of `one`.
+constexpr int CA_WORDS = 4;       // 64-pixel word columns per workgroup (one wavefront: 4 words x 2 halves x 8 rows)
+constexpr int CA_TROWS = 8;       // 8-row tile rows per workgroup
+constexpr int CA_NPY = 2;         // tile row pairs the rows of one workgroup can need (64 rows, tiles >= 80 rows high)
+__host__ __device__ inline bool clahe_apply64_ok(int w, const ClaheGeom &g) { return w % 16 == 0 && g.tw >= 128 && g.th >= 80; }
+
+__device__ __forceinline__ int clahe_pair(int x, float inv) { return (int)floorf(x * inv - 0.5f) + 1; }   // 0..4
+
+// bit 8 b + k of the result = byte b of s[k] > thr (s[k]: bytes b = pixels 8 b + k of 32); lo = s & 0x7f.., hb = s & 0x80..
+template <int THR>
+__device__ __forceinline__ uint32_t gt32(const uint32_t *lo, const uint32_t *hb)
+{
+    constexpr uint32_t H = 0x80808080u, C = (uint32_t)(0x7f - (THR & 0x7f)) * 0x01010101u;
+    uint32_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint32_t m = THR < 128 ? (((lo[k] + C) & H) | hb[k]) : ((lo[k] + C) & hb[k]);
+        acc |= m >> (7 - k);
+    }
+    return acc;
+}
+
+template <int T>
+__device__ __forceinline__ void planes_of(const uint32_t *lo, const uint32_t *hb, uint32_t *pw)
+{
+    pw[T] = gt32<50 + 10 * T>(lo, hb);
+    if constexpr (T + 1 < 17) planes_of<T + 1>(lo, hb, pw);
+}
+
+__global__ __launch_bounds__(64) void k_clahe_apply64(const uint8_t *__restrict__ gray, int h, int w, ClaheGeom g,
+                                                       const uint8_t *__restrict__ lut, uint8_t *__restrict__ dst,
+                                                       int *__restrict__ nrect, int lab_lut, int *__restrict__ bucket_cnt,
+                                                       int bucket_stride, unsigned long long *__restrict__ planes)
+{
+    constexpr int NP = 17;
+    __shared__ uint32_t s_tab[CA_NPY * 5 * 256];   // [row pair - first][column pair][input value]: bytes (ty1,tx1) (ty1,tx2) (ty2,tx1) (ty2,tx2)
+    __shared__ float2 s_col[CA_WORDS * 66];        // {xa, xa1} per column; one pad entry per 32 columns keeps the reads of a wave on distinct banks
+    __shared__ int s_b[4];
+    __shared__ int s_pop[NP];
+    const int chunks = (w + 63) >> 6, tc = bit_tile_cols(w), th8 = (h + 7) >> 3;
+    const int ncb = (chunks + CA_WORDS - 1) / CA_WORDS;
+    const int cb = blockIdx.x % ncb, rb = blockIdx.x / ncb;
+    const size_t f = blockIdx.y, N = (size_t)h * w;
+    const int t = threadIdx.x, r = t & 7, half = (t >> 3) & 1, jj = t >> 4, j = cb * CA_WORDS + jj;
+    const float inv_tw = 1.0f / g.tw, inv_th = 1.0f / g.th;
+    const int y_first = rb * CA_TROWS * 8, y_last = min(y_first + CA_TROWS * 8, h) - 1;
+    const int py_lo = clahe_pair(y_first, inv_th), npy = min(clahe_pair(y_last, inv_th) - py_lo + 1, CA_NPY);   // (th >= 80: <= 2)
+    if (t < 4) s_b[t] = t < 2 ? INT_MAX : -1;
+    if (t < NP) s_pop[t] = 0;
+    {
+        const uint8_t *L = lut + f * 16 * 256;   // tilesX = tilesY = 4
+        for (int e = t; e < npy * 5 * 256; e += 64) {
+            const int v0 = e & 255, pc = e >> 8, px = pc % 5, py = py_lo + pc / 5;
+            const int v = lab_lut ? (int)c_lab_l[v0] : v0;
+            const int ty1 = max(py - 1, 0), ty2 = min(py, 3), tx1 = max(px - 1, 0), tx2 = min(px, 3);
+            s_tab[e] = (uint32_t)L[(ty1 * 4 + tx1) * 256 + v] | ((uint32_t)L[(ty1 * 4 + tx2) * 256 + v] << 8) |
+                       ((uint32_t)L[(ty2 * 4 + tx1) * 256 + v] << 16) | ((uint32_t)L[(ty2 * 4 + tx2) * 256 + v] << 24);
+        }
+        for (int c = t; c < CA_WORDS * 64; c += 64) {
+            const int x = cb * CA_WORDS * 64 + c;
+            const float txf = x * inv_tw - 0.5f;
+            const int tx1 = (int)floorf(txf);
+            const float xa = txf - tx1;
+            s_col[c + (c >> 5)] = make_float2(xa, 1.0f - xa);
+        }
+    }
+    __syncthreads();
+    const bool live = j < chunks;
+    const int x0 = j * 64 + 32 * half;   // this thread's 32 pixels of the word
+    // column pair of the thread's first pixel, and its first pixel with the next pair (32: none)
+    const int px0 = clahe_pair(x0, inv_tw);
+    int split = 32;
+    if (clahe_pair(x0 + 31, inv_tw) != px0) {
+        int lo = 1, hi = 31;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (clahe_pair(x0 + mid, inv_tw) != px0) hi = mid; else lo = mid + 1;
+        }
+        split = lo;
+    }
+    const size_t pwords = bit_plane_words(h, w);
+    uint32_t *fpl = reinterpret_cast<uint32_t *>(planes + f * NP * pwords);
+    int mnx = INT_MAX, mny = INT_MAX, mxx = -1, mxy = -1;
+    unsigned pop[NP];
+#pragma unroll
+    for (int k = 0; k < NP; k++) pop[k] = 0;
+    for (int it = 0; it < CA_TROWS; it++) {
+        if (rb * CA_TROWS + it >= th8) break;
+        const int y = y_first + it * 8 + r;
+        if (!live) continue;
+        // the column terms are the same in every tile row: kept in LDS, not hoisted into 64 registers
+        int cbase = (jj * 2 + half) * 33, spl = split;
+        asm volatile("" : "+v"(cbase), "+v"(spl));
+        const float2 *col = s_col + cbase;
+        uint32_t s[8];   // s[k] byte b = result of pixel 8 b + k
+#pragma unroll
+        for (int k = 0; k < 8; k++) s[k] = 0;
+        if (y < h && x0 < w) {   // (w % 16 == 0: 16-pixel groups lie inside the row or past it)
+            const uint8_t *src = gray + f * N + (size_t)y * w + x0;
+            uint8_t *out = dst + f * N + (size_t)y * w + x0;
+            const bool two = x0 + 16 < w;
+            uint32_t in[8];
+            {
+                const uint4 v = *reinterpret_cast<const uint4 *>(src);
+                const uint4 u = two ? *reinterpret_cast<const uint4 *>(src + 16) : make_uint4(0, 0, 0, 0);
+                in[0] = v.x; in[1] = v.y; in[2] = v.z; in[3] = v.w; in[4] = u.x; in[5] = u.y; in[6] = u.z; in[7] = u.w;
+            }
+            const float tyf = y * inv_th - 0.5f;
+            const int ty1 = (int)floorf(tyf);
+            const float ya = tyf - ty1, ya1 = 1.0f - ya;
+            const uint32_t *tab = s_tab + ((ty1 + 1 - py_lo) * 5 + px0) * 256;
+#pragma unroll
+            for (int c = 0; c < 32; c++) {
+                if ((c & 15) == 0 && c) __builtin_amdgcn_sched_barrier(0);   // 16 pixels' table reads in flight, not 32
+                const uint32_t e = tab[(c >= spl ? 256 : 0) + ((in[c >> 2] >> (8 * (c & 3))) & 255u)];
+                const float2 cx = col[c];
+                const float a = (float)(e & 255u) * cx.y, b = (float)((e >> 8) & 255u) * cx.x;
+                const float cc = (float)((e >> 16) & 255u) * cx.y, d = (float)(e >> 24) * cx.x;
+                const float res = (a + b) * ya1 + (cc + d) * ya;
+                const uint32_t v = (uint32_t)sat_u8((int)rintf(res));
+                s[c & 7] |= v << (8 * (c >> 3));
+            }
+            // the row's bytes in pixel order: pixels 4 m .. 4 m + 3 = byte m >> 1 of s[4 (m & 1) + 0 .. 3]
+            auto word = [&](int m) -> uint32_t {
+                const uint32_t *sk = s + 4 * (m & 1);
+                const uint32_t b = (uint32_t)(m >> 1);
+                const uint32_t lo2 = __builtin_amdgcn_perm(sk[1], sk[0], (b + 4) << 8 | b | 0x0c0c0000u);
+                const uint32_t hi2 = __builtin_amdgcn_perm(sk[3], sk[2], (b + 4) << 8 | b | 0x0c0c0000u);
+                return lo2 | (hi2 << 16);
+            };
+            *reinterpret_cast<uint4 *>(out) = make_uint4(word(0), word(1), word(2), word(3));
+            if (two) *reinterpret_cast<uint4 *>(out + 16) = make_uint4(word(4), word(5), word(6), word(7));
+            else {   // pixels 16 .. 31 do not exist (bytes 2, 3 of s): no plane bit for them
+#pragma unroll
+                for (int k = 0; k < 8; k++) s[k] &= 0x0000ffffu;
+            }
+        }
+        uint32_t lo[8], hb[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) { lo[k] = s[k] & 0x7f7f7f7fu; hb[k] = s[k] & 0x80808080u; }
+        uint32_t pw[NP];
+        planes_of<0>(lo, hb, pw);
+        if (pw[0]) {   // pixels > 50: the working rectangle
+            mnx = min(mnx, x0 + __ffs((int)pw[0]) - 1); mxx = max(mxx, x0 + 31 - __clz((int)pw[0]));
+            mny = min(mny, y); mxy = max(mxy, y);
+        }
+        // two lanes write the two halves of a plane word; the first also writes the zero tile column beside the frame
+        uint32_t *o = fpl + 2 * bit_word(tc, y, j) + half;
+        const bool z0 = j == 0 && half == 0, z1 = j == chunks - 1 && half == 1;
+#pragma unroll
+        for (int k = 0; k < NP; k++) {
+            o[0] = pw[k];
+            if (z0) *reinterpret_cast<unsigned long long *>(o - 16) = 0ull;
+            if (z1) *reinterpret_cast<unsigned long long *>(o + 15) = 0ull;
+            pop[k] += (unsigned)__popc(pw[k]);
+            o += 2 * pwords;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if (__ballot(mxx >= 0)) {
+        for (int off = 32; off >= 1; off >>= 1) {
+            mnx = min(mnx, __shfl_xor(mnx, off, 64)); mxx = max(mxx, __shfl_xor(mxx, off, 64));
+            mny = min(mny, __shfl_xor(mny, off, 64)); mxy = max(mxy, __shfl_xor(mxy, off, 64));
+        }
+        if ((t & 63) == 0) {
+            atomicMin(&s_b[0], mnx); atomicMin(&s_b[1], mny); atomicMax(&s_b[2], mxx); atomicMax(&s_b[3], mxy);
+        }
+#pragma unroll
+        for (int k = 0; k < NP; k++) {
+            unsigned v = pop[k];
+            for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+            if ((t & 63) == 0 && v) atomicAdd(&s_pop[k], (int)v);
+        }
+    }
+    __syncthreads();
+    // bucket b (1 .. 17) = pixels above threshold b - 1 and not above threshold b
+    if (bucket_cnt && t < NP) {
+        const int c = s_pop[t] - (t + 1 < NP ? s_pop[t + 1] : 0);
+        if (c) atomicAdd(&bucket_cnt[f * bucket_stride + t + 1], c);
+    }
+    if (t == 0 && s_b[2] >= 0) {
+        int *nr = nrect + 16 * f;   // test first: most workgroups lie inside the box already
+        if (s_b[0] < __hip_atomic_load(nr + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(nr + 0, s_b[0]);
+        if (s_b[1] < __hip_atomic_load(nr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(nr + 1, s_b[1]);
+        if (s_b[2] > __hip_atomic_load(nr + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(nr + 2, s_b[2]);
+        if (s_b[3] > __hip_atomic_load(nr + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(nr + 3, s_b[3]);
+    }
+}
+
 // ---- blobs per threshold ----------------------------------------------------------------------------
 struct DistVisitor {
     double cx, cy;
@@ -1130,7 +1329,8 @@ constexpr int BK_CHUNK = 8192;    // pixels per workgroup of the two bucket pass
 // wavefront fall into a few lines.)
 template <bool SCATTER>
 __global__ __launch_bounds__(256) void k_bk_pass(const uint8_t *__restrict__ img, int h, int w, const FrameState *__restrict__ st,
-                                                 int *__restrict__ sw, int *__restrict__ bk, int *__restrict__ bright /* nodes {parent, history} */)
+                                                 int *__restrict__ sw, int *__restrict__ bk, int *__restrict__ bright /* nodes {parent, history} */,
+                                                 uint8_t *__restrict__ touch)
 {
     __shared__ int s_cnt[NBK], s_base[NBK];
     const size_t N = (size_t)h * w, f = blockIdx.y;
@@ -1162,7 +1362,10 @@ __global__ __launch_bounds__(256) void k_bk_pass(const uint8_t *__restrict__ img
         if (i < N) {
             const int y = (int)(i / w);
             x = (int)(i - (size_t)y * w);
-            if (!(y < r.y0 || y > r.y1 || x < r.x0 || x > r.x1)) l = sw_level(im[i]);
+            if (!(y < r.y0 || y > r.y1 || x < r.x0 || x > r.x1)) {
+                l = sw_level(im[i]);
+                if (SCATTER) touch[f * N + i] = 0;   // the dark sweep's epoch marks: only roots inside the rectangle are read
+            }
         }
         if (SCATTER) {
             // first node of the bright forest: the first pixel of the pixel's run of one bucket among this wavefront's 64
@@ -2055,14 +2258,13 @@ __global__ void k_best_reset(int n, unsigned long long *best)
 }  // namespace
 
 
-// lplane: L channel of BGR2LAB of a colour frame (util_cylinder.py:1840 on a 3-channel image), or null: grey frames, L = LUT[grey]
-// probe: null on the product path (cpe_debug_blob_region: see RegionProbe)
-int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const RegionBuffers &B, FrameState *st, hipStream_t s,
-                 const RegionSide *side, const uint8_t *lplane, const RegionProbe *probe)
+// LAB-L + CLAHE of the frames into B.cl, the bucket sizes (B.sw, which it zeroes) and the box of the pixels > 50 (B.nrect); the
+// 17 one-bit planes as well when rows start on 16-byte boundaries (returned: true) -- other widths need build_bitplanes on
+// B.cl.  fused = false: the byte-level apply in any case (tests hold the two equal).
+int clahe_front(const uint8_t *gray, int n, int h, int w, double clip, int lab_lut, bool identity, const RegionBuffers &B,
+                hipStream_t s, bool fused, bool *planes_done)
 {
-    const int lab_lut = (lplane || (probe && probe->identity)) ? 0 : 1;
-    if (lplane) gray = lplane;
-    const size_t N = (size_t)h * w, total = N * n;
+    const size_t N = (size_t)h * w;
     ClaheGeom g;
     g.tilesX = 4; g.tilesY = 4;
     g.ew = (w % 4 == 0 && h % 4 == 0) ? w : w + (4 - (w % 4));
@@ -2073,8 +2275,7 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
     if (clip > 0.0) { g.clipLimit = (int)(clip * tileTotal / 256); if (g.clipLimit < 1) g.clipLimit = 1; }
     g.lutScale = (float)255 / tileTotal;
     CPE_LAUNCH_BEGIN();
-    // (st[].n_groups / n_kp, B.best and the bounding-box accumulators B.nrect were reset by k_state_init)
-    if (probe && probe->identity) {
+    if (identity) {
         // lut[t][v] = v for the 16 tiles: k_clahe_apply interpolates equal values, so the sweep sees the input itself
         CPE_KLAUNCH(k_probe_identity_lut, dim3(16, n), dim3(256), 0, s, B.lut);
     } else {
@@ -2084,25 +2285,67 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
         CPE_KLAUNCH(k_clahe_lut, dim3(n * 16), dim3(256), 0, s, B.hist, g, B.lut);
     }
     (void)hipMemsetAsync(B.sw, 0, (size_t)n * SW_STRIDE * sizeof(int), s);   // the sweep's counters: k_clahe_apply already counts the buckets
-    CPE_KLAUNCH(k_clahe_apply, dim3((unsigned)((N + CLAHE_BLK_PX - 1) / CLAHE_BLK_PX), n), dim3(256), 0, s, gray, h, w, g, (const uint8_t *)B.lut, B.cl, B.nrect, lab_lut,
-                B.sw + SW_BS, (int)SW_STRIDE);
+    *planes_done = fused && clahe_apply64_ok(w, g) && ((((size_t)gray) | ((size_t)B.cl)) & 15) == 0;
+    if (*planes_done) {
+        const int chunks = (w + 63) >> 6, th8 = (h + 7) >> 3;
+        const unsigned blocks = (unsigned)(((chunks + CA_WORDS - 1) / CA_WORDS) * ((th8 + CA_TROWS - 1) / CA_TROWS));
+        CPE_KLAUNCH(k_clahe_apply64, dim3(blocks, n), dim3(64), 0, s, gray, h, w, g, (const uint8_t *)B.lut, B.cl, B.nrect, lab_lut,
+                    B.sw + SW_BS, (int)SW_STRIDE, reinterpret_cast<unsigned long long *>(B.bits));
+    } else {
+        CPE_KLAUNCH(k_clahe_apply, dim3((unsigned)((N + CLAHE_BLK_PX - 1) / CLAHE_BLK_PX), n), dim3(256), 0, s, gray, h, w, g, (const uint8_t *)B.lut, B.cl, B.nrect, lab_lut,
+                    B.sw + SW_BS, (int)SW_STRIDE);
+    }
     CPE_CHECK_LAUNCH("clahe");
+    return CPE_OK;
+}
+
+// the CLAHE front end alone (cpe_debug_clahe_planes): B.cl, the 17 planes, bucket sizes i32[n,18] and box i32[n,4] copied out
+int clahe_front_probe(const uint8_t *gray, int n, int h, int w, int fused, const RegionBuffers &B, hipStream_t s, uint8_t *cl,
+                      uint32_t *planes, int *buckets, int *box)
+{
+    bool done = false;
     int rc;
-    if (side) {   // the 17 one-bit planes only need the CLAHE image
+    if ((rc = clahe_front(gray, n, h, w, 4.5, 1, false, B, s, fused != 0, &done)) != CPE_OK) return rc;
+    if (!done && (rc = build_bitplanes(B.cl, n, h, w, 50, 10, NTHR, B.bits, s)) != CPE_OK) return rc;
+    CPE_LAUNCH_BEGIN();
+    (void)hipMemcpyAsync(cl, B.cl, (size_t)n * h * w, hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(planes, B.bits, (size_t)n * NTHR * bit_plane_words(h, w) * 8, hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpy2DAsync(buckets, NBK * sizeof(int), B.sw + SW_BS, SW_STRIDE * sizeof(int), NBK * sizeof(int), n, hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpy2DAsync(box, 4 * sizeof(int), B.nrect, 16 * sizeof(int), 4 * sizeof(int), n, hipMemcpyDeviceToDevice, s);
+    CPE_CHECK_LAUNCH("clahe_front_probe");
+    return CPE_OK;
+}
+
+// lplane: L channel of BGR2LAB of a colour frame (util_cylinder.py:1840 on a 3-channel image), or null: grey frames, L = LUT[grey]
+// probe: null on the product path (cpe_debug_blob_region: see RegionProbe)
+int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const RegionBuffers &B, FrameState *st, hipStream_t s,
+                 const RegionSide *side, const uint8_t *lplane, const RegionProbe *probe)
+{
+    const int lab_lut = (lplane || (probe && probe->identity)) ? 0 : 1;
+    if (lplane) gray = lplane;
+    const size_t N = (size_t)h * w, total = N * n;
+    CPE_LAUNCH_BEGIN();
+    // (st[].n_groups / n_kp, B.best and the bounding-box accumulators B.nrect were reset by k_state_init)
+    // rows on 16-byte boundaries: the apply pass writes the 17 one-bit planes as well; other widths make them in a pass of
+    // their own (on the helper stream, if any: only the bright sweep waits for them)
+    bool planes_in_apply = false;
+    int rc;
+    if ((rc = clahe_front(gray, n, h, w, clip, lab_lut, probe && probe->identity, B, s, true, &planes_in_apply)) != CPE_OK) return rc;
+    const bool side_planes = side && !planes_in_apply;
+    if (side_planes) {   // the 17 one-bit planes only need the CLAHE image
         (void)hipEventRecord(side->clahe_done, s);
         (void)hipStreamWaitEvent(side->s, side->clahe_done, 0);
         if ((rc = build_bitplanes(B.cl, n, h, w, 50, 10, NTHR, B.bits, side->s)) != CPE_OK) return rc;
         (void)hipEventRecord(side->traced, side->s);   // the bright sweep on `s` reads them too (k_sw_unite_snap)
-    } else if ((rc = build_bitplanes(B.cl, n, h, w, 50, 10, NTHR, B.bits, s)) != CPE_OK) return rc;
+    } else if (!planes_in_apply && (rc = build_bitplanes(B.cl, n, h, w, 50, 10, NTHR, B.bits, s)) != CPE_OK) return rc;
     // working rectangle for all 34 labelling passes = bounding box of the pixels brighter than the lowest threshold:
     // every brighter set and every hole of every binarisation lies inside it
     if ((rc = ccl_set_sweep_rect(st, B.nrect, n, s)) != CPE_OK) return rc;   // crect = the box k_clahe_apply accumulated
-    (void)hipMemsetAsync(B.touch, 0, total, s);
     const int swcap = std::max(32768, (int)std::min<long long>(1 << 20, (long long)N / 12));   // grid sizing only: entries one threshold may hold
     const dim3 gpx((unsigned)((N + 255) / 256), n), glist(frame_waves(4 * n, 4, swcap / 256), n), gtrace(frame_waves(n * NTHR, 8, swcap / 64), n, NTHR), gtrace_h(frame_waves(n * NTHR, 4, swcap / 64), n, NTHR), gbk(std::min(SW_GRID, std::max(16, 6144 / n)), n);
     {
         const dim3 gchunk((unsigned)((N + BK_CHUNK - 1) / BK_CHUNK), n);
-        CPE_KLAUNCH(k_bk_pass<true>, gchunk, dim3(256), 0, s, (const uint8_t *)B.cl, h, w, (const FrameState *)st, B.sw, B.bk, B.lab2);
+        CPE_KLAUNCH(k_bk_pass<true>, gchunk, dim3(256), 0, s, (const uint8_t *)B.cl, h, w, (const FrameState *)st, B.sw, B.bk, B.lab2, B.touch);
         CPE_CHECK_LAUNCH("grey-level buckets");
     }
     // the dark sweep and the hole borders run on the helper stream (if any) beside the bright sweep: the two forests
@@ -2152,7 +2395,7 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
     }
     // ---- descending thresholds: bright components (8-conn); B.bl[k] = (first pixel, pixels of the holes it encloses)
     // (the bright forest's first nodes were written by k_bk_pass)
-    if (side) (void)hipStreamWaitEvent(s, side->traced, 0);
+    if (side_planes) (void)hipStreamWaitEvent(s, side->traced, 0);
     for (int j = 0; j < NTHR; j++) {
         const int k = NTHR - 1 - j;   // members: v > 50 + 10 k (plane k); members before this step: v > 60 + 10 k (plane k + 1; none at j = 0)
         CPE_KLAUNCH(k_sw_unite_snap<false>, dim3(sw_grid(n_grid, g_bk)), dim3(256), 0, s, nx, g_bk, 0, (const uint32_t *)B.bits, k, j == 0 ? -1 : k + 1, h, w, k + 1,

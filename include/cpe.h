@@ -247,6 +247,14 @@ CPE_API int32_t cpe_debug_dark_labels(const uint8_t *img, int32_t n, int32_t h, 
 CPE_API int32_t cpe_debug_external_components(const uint8_t *mask, int32_t n, int32_t h, int32_t w, void *ws, size_t ws_bytes,
                                               int32_t *first_px, int32_t cap, int32_t *count, void *stream);
 
+/* LAB-L + CLAHE(4.5, 4x4) of grey frames u8[n,h,w] and the blob detector's 17 threshold planes (img > 50 + 10 t, 64 x 8
+ * tiles), as the region stage makes them.  fused 1: the passes the detector runs (w % 16 == 0 and wide tiles: the apply pass
+ * writes the planes), 0: the byte-level apply and the planes from a pass of their own.  Outputs (device memory): cl u8[n,h,w],
+ * planes (n * 17 planes of ceil(h / 8) * (ceil(w / 64) + 2) * 8 u64 words), buckets i32[n,18] (pixels per grey-level
+ * bucket, 0 unused), box i32[n,4] (x0, y0, x1, y1 of the pixels > 50).  Test / debugging aid. */
+CPE_API int32_t cpe_debug_clahe_planes(const uint8_t *gray, int32_t n, int32_t h, int32_t w, int32_t fused, void *ws, size_t ws_bytes,
+                                       uint8_t *cl, uint32_t *planes, int32_t *buckets, int32_t *box, void *stream);
+
 /* The blob stage of detect_largest_blob (util_cylinder.py:1830-1899) on a given image: the library's region stage, with
  * img u8[n,h,w] (64 <= h,w <= 4096) as the image its SimpleBlobDetector sweeps -- LAB-L and CLAHE are replaced by an identity
  * table, so CPE_PLANE_CLAHE holds img afterwards -- run serially on `stream`.  Outputs:
