@@ -6,8 +6,10 @@ back as padded point tables; `detect_grid(input_img)` keeps the reference's sing
 return shape, `make_json` its JSON (util_cylinder.py:1674-1727, decoded by makePyGridPts.m:39-41), `save_mat`
 writes the structs the MATLAB side holds after makePyGridPts / fitSingleCylinder.
 There is no CPU fallback: without a GPU and libcpe_hip.so these raise."""
+import collections
 import ctypes as C
 import json
+import threading
 
 import numpy as np
 import torch
@@ -85,10 +87,18 @@ class DetectWorkspace:
         return out
 
 
-def detect_grid_batch(frames, ws=None, subpixel=False, subpixel_window=7, subpixel_step=1.0, target='cylinder'):
+def _output_tables(n, dev):
+    return dict(xy=torch.zeros((n, MAXP, 2), dtype=torch.float64, device=dev), id=torch.zeros((n, MAXP, 2), dtype=torch.int32, device=dev),
+                n=torch.zeros(n, dtype=torch.int32, device=dev), center=torch.zeros((n, 2), dtype=torch.float64, device=dev),
+                status=torch.zeros(n, dtype=torch.int32, device=dev))
+
+
+def detect_grid_batch(frames, ws=None, subpixel=False, subpixel_window=7, subpixel_step=1.0, target='cylinder', out=None):
     """frames: u8 tensor [n,h,w] (grey) or [n,h,w,3] (BGR, as cv2.imread delivers) on the GPU -> dict(xy f64[n,MAXP,2],
     id i32[n,MAXP,2], n i32[n], center f64[n,2], status i32[n], ws).  target='plane': the planar-target script
-    (python_grid_detection_plane.py, row f-2); ids are (row, col) there."""
+    (python_grid_detection_plane.py, row f-2); ids are (row, col) there.
+    out: the tables of an earlier call with the same n on the same device, written again instead of five new zeroed tensors
+    (the earlier result changes with them, and rows of xy / id past n[k] keep what they held)."""
     if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and
             (frames.dim() == 3 or (frames.dim() == 4 and frames.shape[3] == 3))):
         raise TypeError('frames must be a CUDA uint8 tensor [n,h,w] (grey) or [n,h,w,3] (BGR)')
@@ -102,11 +112,11 @@ def detect_grid_batch(frames, ws=None, subpixel=False, subpixel_window=7, subpix
     if ws is None or not ws.fits(n, h, w) or ws.view.device != dev:
         ws = DetectWorkspace(n, h, w, dev)
     ws.use(n)
-    xy = torch.zeros((n, MAXP, 2), dtype=torch.float64, device=dev)
-    ids = torch.zeros((n, MAXP, 2), dtype=torch.int32, device=dev)
-    cnt = torch.zeros(n, dtype=torch.int32, device=dev)
-    center = torch.zeros((n, 2), dtype=torch.float64, device=dev)
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if out is None:
+        out = _output_tables(n, dev)
+    elif out['n'].shape[0] != n or out['n'].device != dev:
+        raise ValueError('detect_grid_batch: `out` holds the tables of another batch size or device')
+    xy, ids, cnt, center, status = out['xy'], out['id'], out['n'], out['center'], out['status']
     prm = _lib.CpeDetectParams(1 if subpixel else 0, subpixel_window, subpixel_step, TARGETS[target], 0)
     entry = L.cpe_detect_grid_bgr_batch_ex if colour else L.cpe_detect_grid_batch_ex
     _lib.check(entry(frames.data_ptr(), n, h, w, C.addressof(prm), ws.view.data_ptr(), ws.bytes,
@@ -207,6 +217,102 @@ def line_tables(det, frame, target='cylinder'):
     return out[0], out[1]
 
 
+FrameRecord = collections.namedtuple('FrameRecord', 'status n center xy id rows cols')
+FrameRecord.__doc__ = """one frame of unpack_results: status (int, CPE_ST_*), n (int), center f64[2], xy f64[n,2], id i32[n,2] (numpy arrays
+that own their data), rows / cols: the dicts line_tables returns"""
+
+_REC_HEAD = 48
+
+
+def record_bytes(n_pts, n_lines, n_line_pts):
+    """bytes of one packed record (include/cpe.h, "Packed results")"""
+    return _REC_HEAD + 24 * n_pts + 48 * n_lines + 8 * ((n_lines + 2) // 2) + 16 * n_line_pts
+
+
+def unpack_results(offsets, payload, target='cylinder'):
+    """offsets int64[n+1], payload uint8[>= offsets[n]] as cpe_detect_results_sizes / cpe_detect_results_pack wrote them (numpy,
+    on the host) -> list of n FrameRecord.  Pure: needs neither the GPU nor the library.  The record layout is the one of
+    include/cpe.h; ids are stored as the detector made them ((col, row), planar target: (row, col)), so `target` only
+    has to name a known target.  Raises ValueError on offsets that are not increasing multiples of 8 from 0, on a payload
+    shorter than offsets[n], and on a record whose counts do not give exactly its size."""
+    if target not in TARGETS:
+        raise ValueError(f'unpack_results: unknown target {target!r}')
+    off = np.asarray(offsets)
+    buf = np.asarray(payload)
+    if off.ndim != 1 or off.size < 1 or off.dtype != np.int64:
+        raise ValueError('unpack_results: offsets must be an int64 vector of n + 1 entries')
+    if buf.ndim != 1 or buf.dtype != np.uint8:
+        raise ValueError('unpack_results: payload must be a uint8 vector')
+    if off[0] != 0 or np.any(off & 7) or np.any(np.diff(off) <= 0):
+        raise ValueError('unpack_results: offsets must start at 0, be multiples of 8 and increase')
+    if buf.size < int(off[-1]):
+        raise ValueError(f'unpack_results: payload of {buf.size} bytes is shorter than offsets[n] = {int(off[-1])} '
+                         '(records that did not fit were not written)')
+    raw = np.ascontiguousarray(buf[:int(off[-1])]).tobytes()        # one copy: what is returned owns its data
+    out = []
+    for k in range(off.size - 1):
+        at, end = int(off[k]), int(off[k + 1])
+        if end - at < _REC_HEAD + 8:
+            raise ValueError(f'unpack_results: record {k} is shorter than an empty record')
+        status, m, nr, nc, npr, npc, z0, z1 = np.frombuffer(raw, '<i4', 8, at).tolist()
+        nl, npt = nr + nc, npr + npc
+        if min(m, nr, nc, npr, npc) < 0 or z0 or z1 or record_bytes(m, nl, npt) != end - at:
+            raise ValueError(f'unpack_results: record {k}: counts {(m, nr, nc, npr, npc)} do not fill its {end - at} bytes')
+        center = np.frombuffer(raw, '<f8', 2, at + 32).copy()
+        p = at + _REC_HEAD
+        xy = np.frombuffer(raw, '<f8', 2 * m, p).reshape(m, 2).copy(); p += 16 * m
+        ids = np.frombuffer(raw, '<i4', 2 * m, p).reshape(m, 2).copy(); p += 8 * m
+        eq = np.frombuffer(raw, '<f8', 6 * nl, p).reshape(nl, 6).tolist(); p += 48 * nl
+        nst = 2 * ((nl + 2) // 2)
+        start = np.frombuffer(raw, '<i4', nst, p).tolist(); p += 4 * nst
+        if start[0] != 0 or start[nr] != npr or start[nl] != npt or any(b < a for a, b in zip(start[:nl], start[1:nl + 1])) or \
+                any(start[nl + 1:]):
+            raise ValueError(f'unpack_results: record {k}: the start table does not match the counts')
+        pts = list(map(tuple, np.frombuffer(raw, '<f8', 2 * npt, p).reshape(npt, 2).tolist()))
+        tables = []
+        for first, cnt, prefix in ((0, nr, 'row'), (nr, nc, 'col')):
+            d = {'points': {}, 'equations': {}}
+            for g in range(cnt):
+                d['points'][f'{prefix}{g + 1}'] = pts[start[first + g]:start[first + g + 1]]
+                d['equations'][f'{prefix}{g + 1}'] = eq[first + g]
+            tables.append(d)
+        out.append(FrameRecord(status, m, center, xy, ids, tables[0], tables[1]))
+    return out
+
+
+def pack_results(det):
+    """the packed records of all frames of a detect_grid_batch result, on the host: (offsets int64[n+1], payload uint8[offsets[n]])
+    as include/cpe.h lays them out.  Two kernels (cpe_detect_results_sizes / _pack); the host reads the n + 1 offsets -- the
+    only way to size the payload -- then the payload: two copies per batch whatever n is.  Like line_tables it refuses a
+    workspace that has served another call."""
+    ws = det['ws']
+    if det.get('ws_generation', ws.generation) != ws.generation:
+        raise RuntimeError('pack_results: the workspace of this result has served another detect call since (its line tables are '
+                           'gone); read them before the next call or give every result its own DetectWorkspace')
+    dev = det['xy'].device
+    n = det['n'].shape[0]
+    L = _lib.load()
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(L.cpe_detect_results_sizes(ws.view.data_ptr(), ws.bytes, ws.n, ws.h, ws.w, det['n'].data_ptr(), det['status'].data_ptr(),
+                                              offsets.data_ptr(), stream), 'cpe_detect_results_sizes')
+        off = offsets.cpu().numpy()
+        payload = torch.empty(int(off[-1]), dtype=torch.uint8, device=dev)
+        _lib.check(L.cpe_detect_results_pack(ws.view.data_ptr(), ws.bytes, ws.n, ws.h, ws.w, det['xy'].data_ptr(), det['id'].data_ptr(),
+                                             det['n'].data_ptr(), det['center'].data_ptr(), det['status'].data_ptr(),
+                                             offsets.data_ptr(), payload.data_ptr(), payload.numel(), stream), 'cpe_detect_results_pack')
+        return off, payload.cpu().numpy()
+
+
+def batch_results(det, target='cylinder'):
+    """everything detect_grid returns beside the picture, for all frames of a detect_grid_batch result: list of FrameRecord
+    (status, n, center, xy, id as in det; rows / cols as line_tables(det, k) gives them) = unpack_results(*pack_results(det))"""
+    if target not in TARGETS:
+        raise ValueError(f'batch_results: unknown target {target!r}')
+    return unpack_results(*pack_results(det), target)
+
+
 def draw_points(gray, xy):
     """the returned picture: BGR copy of the frame with the grid points marked (deterministic; the reference draws random
     colours, util_cylinder.py:1600-1601)"""
@@ -218,29 +324,61 @@ def draw_points(gray, xy):
     return col_img
 
 
-def frame_result(det, k, gray, target='cylinder'):
-    """the 4-tuple detect_grid returns for frame k of a batch result, or None (after printing why) for a failed frame"""
-    st = int(det['status'][k])
+def frame_result(det, k, gray, target='cylinder', results=None):
+    """the 4-tuple detect_grid returns for frame k of a batch result, or None (after printing why) for a failed frame.
+    results: batch_results(det, target), fetched once by a caller that loops over the frames of a detect call (run_folder,
+    detect_grid); without it the frame's status is read and, for a good frame, the batch is fetched for this one call --
+    nothing is kept in `det`."""
+    st = int(det['status'][k]) if results is None else results[k].status
     if st != 0:
         print(f'Error in detect_grid: {STATUS_TEXT.get(st, st)}')
         return None
-    m = int(det['n'][k])
-    xy = det['xy'][k, :m].cpu().numpy(); ids = det['id'][k, :m].cpu().numpy(); center = det['center'][k].cpu().numpy()
-    rows, cols = line_tables(det, k, target)
-    return draw_points(gray, xy), make_json(center, xy, ids), rows, cols
+    r = (batch_results(det, target) if results is None else results)[k]
+    return draw_points(gray, r.xy), make_json(r.center, r.xy, r.id), r.rows, r.cols
+
+
+# detect_grid(input_img) is called once per image (makePyGridPts.m:29): its workspace and output tables are kept between
+# calls, one set per (device, h, w, colour).  Bounded: the _SINGLE_MAX most recently used sets stay on the device
+# (cpe_detect_workspace_bytes(1, h, w): 98 MiB at 640 x 480, 162 MiB at 1920 x 1200, 556 MiB at 3840 x 2160, plus 48 KiB
+# of tables), until release_detect_grid_cache(); calls are serialised by _single_lock, so two threads never share a set
+# in flight.
+_SINGLE_MAX = 4
+_single_sets = collections.OrderedDict()
+_single_lock = threading.Lock()
+
+
+def release_detect_grid_cache():
+    """drop the workspaces and output tables detect_grid keeps between calls (the next call makes its own again)"""
+    with _single_lock:
+        _single_sets.clear()
 
 
 def detect_grid(input_img, device='cuda:0', target='cylinder'):
     """detect_grid(input_img) -> (col_img, result_json, rows_updated, cols_updated)
     (python_grid_detection_cylinder.py:68-110; target='plane': python_grid_detection_plane.py:74-119, whose ids are
-    (row, col)).  On a per-frame failure prints and returns None (:111-112)."""
-    frames = frames_to_device([input_img], device)
-    det = detect_grid_batch(frames, target=target)
-    return frame_result(det, 0, frames[0].cpu().numpy(), target)
+    (row, col)).  On a per-frame failure prints and returns None (:111-112).  What is returned owns its data: a later
+    call does not change it."""
+    img = np.asarray(input_img)
+    frames = frames_to_device([img], device)
+    key = (str(frames.device), frames.shape[1], frames.shape[2], frames.dim() == 4)
+    with _single_lock:
+        held = _single_sets.pop(key, None)              # a call that raises leaves its set out of the cache
+        if held is None:
+            held = (DetectWorkspace(1, frames.shape[1], frames.shape[2], frames.device), _output_tables(1, frames.device))
+        det = detect_grid_batch(frames, held[0], target=target, out=held[1])
+        results = batch_results(det, target)
+        _single_sets[key] = held
+        while len(_single_sets) > _SINGLE_MAX:
+            _single_sets.popitem(last=False)
+    return frame_result(det, 0, img, target, results)
 
 
-def grid_struct(det, k):
-    """gridPts of makePyGridPts.m:39-41 for frame k: center_point (2 x 1), points (N x 4 = [x y colIdx rowIdx])"""
+def grid_struct(det, k, results=None):
+    """gridPts of makePyGridPts.m:39-41 for frame k: center_point (2 x 1), points (N x 4 = [x y colIdx rowIdx]).
+    results: batch_results(det) if the caller has it (no copies then); without it the frame's three tables are copied"""
+    if results is not None:
+        r = results[k]
+        return dict(center_point=r.center.copy().reshape(2, 1), points=np.concatenate([r.xy, r.id.astype(np.float64)], 1).reshape(-1, 4))
     m = int(det['n'][k])
     xy = det['xy'][k, :m].cpu().numpy(); ids = det['id'][k, :m].cpu().numpy().astype(np.float64)
     return dict(center_point=det['center'][k].cpu().numpy().reshape(2, 1), points=np.concatenate([xy, ids], 1).reshape(-1, 4))

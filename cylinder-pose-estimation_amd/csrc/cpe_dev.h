@@ -474,5 +474,9 @@ int lines_stage(const int *lab_h, const int *lab_v, const uint8_t *exp_h, const 
                 FrameState *st, void *lines_ws, double *o_xy, int *o_id, int *o_n, double *o_center, const uint8_t *gray,
                 int subpixel, int sp_window, double sp_step, float *sp_scratch, int sp_cap, hipStream_t s, int planar);
 int lines_export(const void *lines_ws, int f, double *eq, int *npts, double *pts, int *n_lines, hipStream_t s);
+// packed per-frame records of a whole call (include/cpe.h): byte offsets, then the records
+int results_sizes(const void *lines_ws, int n, const int *n_pts, long long *offsets, hipStream_t s);
+int results_pack(const void *lines_ws, int n, const double *xy, const int *id, const int *n_pts, const double *center,
+                 const int *status, const long long *offsets, void *payload, size_t payload_bytes, hipStream_t s);
 
 }  // namespace cpe

@@ -427,6 +427,31 @@ extern "C" int32_t cpe_detect_line_tables(const void *ws, size_t ws_bytes, int32
     return lines_export((const uint8_t *)ws + L.off[P_LINES], frame, eq, npts, pts, n_lines, (hipStream_t)stream);
 }
 
+extern "C" int32_t cpe_detect_results_sizes(const void *ws, size_t ws_bytes, int32_t n, int32_t h, int32_t w, const int32_t *n_pts,
+                                            const int32_t *status, int64_t *offsets, void *stream)
+{
+    CPE_CHECK_ARG(ws && n_pts && status && offsets && n > 0 && h >= 64 && w >= 64 && ((uintptr_t)n_pts & 3) == 0 &&
+                  ((uintptr_t)status & 3) == 0 && ((uintptr_t)offsets & 7) == 0, "cpe_detect_results_sizes: bad argument");
+    Layout L = make_layout(n, h, w);
+    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_detect_results_sizes: not the workspace of an (n,h,w) call");
+    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are 64-bit");
+    return results_sizes((const uint8_t *)ws + L.off[P_LINES], n, n_pts, (long long *)offsets, (hipStream_t)stream);
+}
+
+extern "C" int32_t cpe_detect_results_pack(const void *ws, size_t ws_bytes, int32_t n, int32_t h, int32_t w, const double *xy,
+                                           const int32_t *id, const int32_t *n_pts, const double *center, const int32_t *status,
+                                           const int64_t *offsets, void *payload, size_t payload_bytes, void *stream)
+{
+    CPE_CHECK_ARG(ws && xy && id && n_pts && center && status && offsets && payload && n > 0 && h >= 64 && w >= 64,
+                  "cpe_detect_results_pack: bad argument");
+    CPE_CHECK_ARG((((uintptr_t)xy | (uintptr_t)id | (uintptr_t)center | (uintptr_t)offsets | (uintptr_t)payload) & 7) == 0 &&
+                  (((uintptr_t)n_pts | (uintptr_t)status) & 3) == 0, "cpe_detect_results_pack: a buffer is not aligned (8 bytes; n_pts, status: 4)");
+    Layout L = make_layout(n, h, w);
+    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_detect_results_pack: not the workspace of an (n,h,w) call");
+    return results_pack((const uint8_t *)ws + L.off[P_LINES], n, xy, id, n_pts, center, status, (const long long *)offsets, payload,
+                        payload_bytes, (hipStream_t)stream);
+}
+
 // BGR2GRAY of the entry point for colour input (load_and_preprocess_image, util_cylinder.py:1781-1789)
 namespace cpe { namespace {
 __global__ __launch_bounds__(256) void k_bgr2gray(const uint8_t *__restrict__ bgr, size_t npx, uint8_t *__restrict__ gray)

@@ -6,6 +6,10 @@
 // The arithmetic (operation order of the polynomial fit, the Newton iteration, the means) is the one
 // written in oracle/src/orc_lines.c, which is pinned against the real reference functions.
 // Lines live in per-image workspace slots; every re-ordering is an index list (no data movement).
+#include <algorithm>
+#include <climits>
+#include <cstddef>
+
 #include "cpe_dev.h"
 
 namespace cpe {
@@ -835,7 +839,178 @@ __global__ __launch_bounds__(256) void k_line_tables(const LinesWS *__restrict__
     }
 }
 
+// ---- packed per-frame records (include/cpe.h, "Packed results"): the point tables and the line tables of every frame of
+// a call, variable length, one after the other in one payload.  The kernels only move data.
+constexpr int REC_HEAD = 48;   // i32[8] header + f64[2] centre
+
+// a count read from the workspace or the caller's tables, kept inside what the buffers hold whatever the memory contains
+__device__ __forceinline__ int live_count(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
+
+__device__ __forceinline__ long long record_bytes(int n_pts, int nl, int np)
+{
+    return REC_HEAD + 24ll * n_pts + 48ll * nl + 8ll * ((nl + 2) / 2) + 16ll * np;
+}
+
+// line i of a frame in final order (rows first): its slot and its number of intersections
+__device__ __forceinline__ int line_count(const LinesWS &W, int nr, int i, int *slot_out)
+{
+    const int sd = i < nr ? 0 : 1, pos = i < nr ? i : i - nr;
+    const int slot = live_count(W.fin_ord[sd][pos], MAXL - 1);
+    if (slot_out) *slot_out = slot;
+    return live_count(W.in[sd][slot], MAXL);
+}
+
+// one wavefront per frame: sizes[f + 1] = bytes of frame f's record (sums of integers: no order dependence)
+__global__ __launch_bounds__(256) void k_results_sizes(const LinesWS *__restrict__ wsall, int n, const int *__restrict__ n_pts,
+                                                       long long *__restrict__ offsets)
+{
+    const int f = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (f >= n) return;
+    const LinesWS &W = wsall[f];
+    const int nr = live_count(W.fin_n[0], MAXL), nl = nr + live_count(W.fin_n[1], MAXL);
+    int np = 0;
+    for (int i = lane; i < nl; i += 64) np += line_count(W, nr, i, nullptr);
+    for (int off = 32; off >= 1; off >>= 1) np += __shfl_xor(np, off, 64);
+    if (lane == 0) offsets[f + 1] = record_bytes(live_count(n_pts[f], CPE_MAXP), nl, np);
+}
+
+// one workgroup: offsets[0] = 0, offsets[k + 1] = sum of the sizes of frames 0..k (in place), 256 frames per round
+__global__ __launch_bounds__(256) void k_results_scan(int n, long long *__restrict__ offsets)
+{
+    __shared__ long long s_wave[4], s_carry;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    if (t == 0) { s_carry = 0; offsets[0] = 0; }
+    __syncthreads();
+    for (int base = 0; base < n; base += 256) {
+        const int f = base + t;
+        long long incl = f < n ? offsets[f + 1] : 0;
+        for (int off = 1; off < 64; off <<= 1) { const long long o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+        if (lane == 63) s_wave[wv] = incl;
+        __syncthreads();
+        long long before = s_carry;
+        for (int k = 0; k < wv; k++) before += s_wave[k];
+        if (f < n) offsets[f + 1] = before + incl;
+        __syncthreads();
+        if (t == 255) s_carry = before + incl;
+        __syncthreads();
+    }
+}
+
+// one (x, y) pair: a 16-byte load and store where both sides are 16-byte aligned (wide), two 8-byte ones elsewhere
+__device__ __forceinline__ void store_pair(double *dst, const double *src, bool wide)
+{
+    if (wide) *reinterpret_cast<double2 *>(dst) = *reinterpret_cast<const double2 *>(src);
+    else { const double x = src[0], y = src[1]; dst[0] = x; dst[1] = y; }
+}
+
+// one workgroup per frame writes the frame's whole record, or nothing (a record that does not end inside payload_bytes, or
+// whose size is not the one its offsets leave for it, is skipped)
+__global__ __launch_bounds__(256) void k_results_pack(const LinesWS *__restrict__ wsall, const double *__restrict__ xy,
+                                                      const int *__restrict__ id, const int *__restrict__ n_pts,
+                                                      const double *__restrict__ center, const int *__restrict__ status,
+                                                      const long long *__restrict__ offsets, unsigned char *__restrict__ payload,
+                                                      long long payload_bytes, int src_wide)
+{
+    const int f = blockIdx.x, t = threadIdx.x;
+    const LinesWS &W = wsall[f];
+    __shared__ int s_slot[2 * MAXL], s_start[2 * MAXL + 1];
+    __shared__ int s_ok;
+    __shared__ long long s_at;
+    const int nr = live_count(W.fin_n[0], MAXL), nl = nr + live_count(W.fin_n[1], MAXL);
+    const int m = live_count(n_pts[f], CPE_MAXP);
+    for (int i = t; i < nl; i += 256) {
+        int slot;
+        s_start[i + 1] = line_count(W, nr, i, &slot);
+        s_slot[i] = slot;
+    }
+    if (t == 0) s_start[0] = 0;
+    __syncthreads();
+    // `start`: prefix sums of the (at most 512) counts by the first wavefront, 8 consecutive lines per lane
+    if (t < 64) {
+        int v[8], sum = 0;
+        for (int k = 0; k < 8; k++) { const int i = t * 8 + k; v[k] = i < nl ? s_start[i + 1] : 0; sum += v[k]; }
+        int incl = sum;
+        for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (t >= off) incl += o; }
+        int run = incl - sum;
+        for (int k = 0; k < 8; k++) { const int i = t * 8 + k; run += v[k]; if (i < nl) s_start[i + 1] = run; }
+    }
+    __syncthreads();
+    const int np = s_start[nl];
+    if (t == 0) {
+        const long long at = offsets[f], bytes = record_bytes(m, nl, np);
+        const long long next = offsets[f + 1];
+        // no sum or difference that garbage offsets could overflow: 0 <= at <= payload_bytes before payload_bytes - at
+        s_ok = at >= 0 && (at & 7) == 0 && at <= payload_bytes && bytes <= payload_bytes - at && next >= at && next - at == bytes;
+        s_at = at;
+    }
+    __syncthreads();
+    if (!s_ok) return;
+    unsigned char *rec = payload + s_at;
+    if (t == 0) {
+        const int npr = s_start[nr];
+        int2 *head = reinterpret_cast<int2 *>(rec);
+        head[0] = make_int2(status[f], m);
+        head[1] = make_int2(nr, nl - nr);
+        head[2] = make_int2(npr, np - npr);
+        head[3] = make_int2(0, 0);
+    }
+    else if (t < 3) reinterpret_cast<double *>(rec + 32)[t - 1] = center[2 * f + (t - 1)];
+    double *o_xy = reinterpret_cast<double *>(rec + REC_HEAD);
+    long long *o_id = reinterpret_cast<long long *>(rec + REC_HEAD + 16ll * m);
+    double *o_eq = reinterpret_cast<double *>(rec + REC_HEAD + 24ll * m);
+    int *o_start = reinterpret_cast<int *>(rec + REC_HEAD + 24ll * m + 48ll * nl);
+    double *o_pts = reinterpret_cast<double *>(rec + REC_HEAD + 24ll * m + 48ll * nl + 8ll * ((nl + 2) / 2));
+    {
+        const double *src = xy + (size_t)f * CPE_MAXP * 2;
+        const bool wide = src_wide && ((uintptr_t)o_xy & 15) == 0;
+        for (int i = t; i < m; i += 256) store_pair(o_xy + 2 * i, src + 2 * i, wide);
+        const long long *isrc = reinterpret_cast<const long long *>(id) + (size_t)f * CPE_MAXP;   // (col, row): one 8-byte word
+        for (int i = t; i < m; i += 256) o_id[i] = isrc[i];
+    }
+    for (int i = t; i < 6 * nl; i += 256) {
+        const int ln = i / 6;
+        o_eq[i] = W.eq[ln < nr ? 0 : 1][s_slot[ln]][i - 6 * ln];
+    }
+    for (int i = t; i < 2 * ((nl + 2) / 2); i += 256) o_start[i] = i <= nl ? s_start[i] : 0;
+    {
+        // intersection e of the frame: its line by bisection of `start` (lines without intersections are never the answer),
+        // consecutive lanes read consecutive points of a line and write consecutive pairs
+        // the frames' tables are sizeof(LinesWS) apart, a multiple of 8 but not of 16: where the frame's are not 16-byte
+        // aligned the pairs go as two 8-byte words
+        static_assert(sizeof(LinesWS) % 8 == 0 && offsetof(LinesWS, ipts) % 16 == 0, "alignment of the intersection tables");
+        const bool wide = (((uintptr_t)o_pts | (uintptr_t)&W.ipts[0][0][0][0]) & 15) == 0;
+        for (int e = t; e < np; e += 256) {
+            int lo = 0, hi = nl;                            // start[lo] <= e < start[hi]
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (s_start[mid] <= e) lo = mid; else hi = mid;
+            }
+            store_pair(o_pts + 2 * (size_t)e, W.ipts[lo < nr ? 0 : 1][s_slot[lo]][e - s_start[lo]], wide);
+        }
+    }
+}
+
 }  // namespace
+
+int results_sizes(const void *lines_ws, int n, const int *n_pts, long long *offsets, hipStream_t s)
+{
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_results_sizes, dim3((n + 3) / 4), dim3(256), 0, s, (const LinesWS *)lines_ws, n, n_pts, offsets);
+    CPE_CHECK_LAUNCH("k_results_sizes");
+    CPE_KLAUNCH(k_results_scan, dim3(1), dim3(256), 0, s, n, offsets);
+    CPE_CHECK_LAUNCH("k_results_scan");
+    return CPE_OK;
+}
+
+int results_pack(const void *lines_ws, int n, const double *xy, const int *id, const int *n_pts, const double *center,
+                 const int *status, const long long *offsets, void *payload, size_t payload_bytes, hipStream_t s)
+{
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_results_pack, dim3(n), dim3(256), 0, s, (const LinesWS *)lines_ws, xy, id, n_pts, center, status, offsets,
+                (unsigned char *)payload, (long long)std::min(payload_bytes, (size_t)LLONG_MAX), ((uintptr_t)xy & 15) == 0 ? 1 : 0);
+    CPE_CHECK_LAUNCH("k_results_pack");
+    return CPE_OK;
+}
 
 int lines_export(const void *lines_ws, int f, double *eq, int *npts, double *pts, int *n_lines, hipStream_t s)
 {

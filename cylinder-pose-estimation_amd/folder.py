@@ -97,9 +97,10 @@ def run_folder(json_path, folder_path, output_folder=None, target='cylinder', ch
             if ws is None or not ws.fits(len(members), h, w):
                 ws = ws_cache[(h, w)] = api.DetectWorkspace(len(members), h, w, batch.device)
             det = api.detect_grid_batch(batch, ws, target=target)
+            records = api.batch_results(det, target)    # (reads the line tables of this call before the workspace moves on)
             host = batch.cpu().numpy()
-            for j, i in enumerate(members):             # (reads the line tables of this call before the workspace moves on)
-                results[i] = api.frame_result(det, j, host[j], target)
+            for j, i in enumerate(members):
+                results[i] = api.frame_result(det, j, host[j], target, records)
         for name, res in zip(window, results):
             if res is None:
                 raise TypeError(f'cannot unpack non-iterable NoneType object (detect_grid failed on {name})')

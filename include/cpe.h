@@ -36,9 +36,10 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 107   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 108   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
-                             106: cpe_debug_preprocess; 107: cpe_debug_masks) */
+                             106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
+                             cpe_detect_results_pack) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -174,6 +175,50 @@ CPE_API int32_t cpe_detect_constants(int32_t target, CpeDetectConstants *out);
 #define CPE_MAXLP 1024
 CPE_API int32_t cpe_detect_line_tables(const void *ws, size_t ws_bytes, int32_t n, int32_t h, int32_t w, int32_t frame,
                                        double *eq, int32_t *npts, double *pts, int32_t *n_lines, void *stream);
+
+/* Packed results: everything detect_grid returns beside the picture, for ALL n frames of the last cpe_detect_grid_batch* call
+ * on this workspace, as one variable-length record per frame in one device buffer -- one size read-back and one payload copy
+ * per batch instead of cpe_detect_line_tables' dense 2 MB per frame.  Sequence:
+ *   1. cpe_detect_results_sizes(ws, ws_bytes, n, h, w, n_pts, status, offsets, stream)
+ *        offsets i64[n+1] (device): offsets[k] = byte offset of frame k's record in the payload, offsets[0] = 0, offsets[n] =
+ *        bytes of all records.  Every offset is a multiple of 8 and offsets[k+1] > offsets[k].  The size of a record depends
+ *        on n_pts and the workspace only; status is taken so that both calls are given the same tables.
+ *   2. the caller copies offsets to the host (the one synchronisation of the sequence) and provides payload_bytes >=
+ *      offsets[n] bytes of 8-byte aligned device memory;
+ *   3. cpe_detect_results_pack(ws, ws_bytes, n, h, w, xy, id, n_pts, center, status, offsets, payload, payload_bytes, stream)
+ *        with the tables the detect call wrote and the offsets of step 1 writes every byte of [0, offsets[n]), padding
+ *        included, and nothing else.
+ * Neither call allocates or synchronises; both are asynchronous on `stream` and must be ordered after the detect call and
+ * before the next call that uses the workspace.  A payload_bytes smaller than offsets[n] cannot be seen by the host without
+ * a synchronisation, so it is not an error: the kernel never writes at or beyond payload_bytes, a record that does not end
+ * inside it (or whose offsets do not leave exactly its size) is skipped WHOLE, and its bytes keep what they held.  A
+ * caller learns of it the way it sized the payload: it has read offsets[n]; a reader must refuse a payload shorter than that.
+ *
+ * Record of frame k at payload + offsets[k], little-endian, every array 8-byte aligned, padding bytes zero:
+ *   offset 0   i32 status                  CPE_ST_* of the frame, as in status[k]
+ *          4   i32 n_pts                   points of the xy / id tables, as in n_pts[k] (0 unless status is CPE_ST_OK)
+ *          8   i32 n_rows                  R lines of side 0 ("row1".."rowR")
+ *         12   i32 n_cols                  C lines of side 1 ("col1".."colC")
+ *         16   i32 n_row_pts               intersections on all rows together
+ *         20   i32 n_col_pts               intersections on all columns together
+ *         24   i32 0, 0
+ *         32   f64 center[2]               as in center[k]
+ *         48   f64 xy[n_pts][2]            make_json order, as in the xy table
+ *              i32 id[n_pts][2]            (col, row); (row, col) for the planar target
+ *              f64 eq[R + C][6]            rows first, final order; the six numbers of cpe_detect_line_tables' eq
+ *              i32 start[R + C + 1]        start[i] = intersections on the lines before line i (start[0] = 0, start[R] =
+ *                                          n_row_pts, start[R + C] = n_row_pts + n_col_pts); one zero i32 of padding
+ *                                          follows when R + C + 1 is odd
+ *              f64 pts[n_row_pts + n_col_pts][2]   line i owns pts[start[i] .. start[i+1]): (x, y) in the reference's loop order
+ *   bytes = 48 + 24 n_pts + 48 (R + C) + 8 ((R + C + 2) / 2) + 16 (n_row_pts + n_col_pts)      (integer division)
+ * The line content is what cpe_detect_line_tables reports for the frame -- also for a frame whose status is not CPE_ST_OK
+ * (0 / 0 lines if it failed before the line stage): the two interfaces agree on every frame, and equal frames give equal
+ * records byte for byte. */
+CPE_API int32_t cpe_detect_results_sizes(const void *ws, size_t ws_bytes, int32_t n, int32_t h, int32_t w, const int32_t *n_pts,
+                                         const int32_t *status, int64_t *offsets, void *stream);
+CPE_API int32_t cpe_detect_results_pack(const void *ws, size_t ws_bytes, int32_t n, int32_t h, int32_t w, const double *xy,
+                                        const int32_t *id, const int32_t *n_pts, const double *center, const int32_t *status,
+                                        const int64_t *offsets, void *payload, size_t payload_bytes, void *stream);
 
 /* Colour input.  The reference's CLI hands detect_grid the H x W x 3 BGR array of cv2.imread (python_grid_detection_cylinder.py:34-44);
  * load_and_preprocess_image (util_cylinder.py:1781-1789) and mask_roi_around_center (:1957) work on cv2.cvtColor(BGR2GRAY) of it:
