@@ -7,118 +7,14 @@
 // Everything stays in HBM between the u8 frame read and the point-table write; all scratch lives in the
 // caller-supplied workspace (cpe_detect_workspace_bytes), laid out plane-major so that every kernel
 // streams [n, h, w] planes with fully coalesced accesses.
-#include "cpe_dev.h"
-#include <initializer_list>
+#include "workspace.h"
+#include <ctype.h>
 #include <mutex>
 #include <stdlib.h>
-#include <algorithm>
 
 namespace cpe {
 
 namespace {
-
-struct Layout {
-    size_t off[64];
-    size_t bytes_per_frame[64];
-    size_t total;
-};
-
-enum Plane {
-    P_BINARY = 0, P_HMASK, P_VMASK, P_MASK_CONTOUR, P_ROI_H, P_ROI_V, P_EXP_H, P_EXP_V, P_JOINTS, P_STATE, P_CL, P_G19, P_G7,
-    P_JOINTS_MASK, P_TMPA, P_TMPB, P_CM, P_EXT, P_BASE_H, P_BASE_V, P_TOUCH, P_TMP16, P_LAB0, P_LAB1, P_ROOTS, P_JTMP,
-    P_VERTS, P_BEST, P_SEGS, P_HIST, P_LUT, P_BLOBS, P_BLOB_D, P_ORDER, P_DISTS, P_GROUPS, P_LOHI, P_HULL, P_LINES, P_NRECT, P_LAB2, P_LAB3, P_SW, P_SUBPIX, P_HL, P_BL, P_TL, P_BK, P_BITS, P_POOL, P_BLOB_CH, P_LABP, P_LABS, P_ROOTSP, P_ROOTSS, P_BEST2, P_HPAR, P_HTIME, P_GMID, P_FLJ, P_GRAYIN, P_COUNT
-};
-
-static_assert(P_COUNT <= 64, "Layout arrays too small");
-
-// capacities of the blob sweep that grow with the frame (border points per threshold ~ cells x perimeter)
-static int region_maxch(int h, int w) { long long v = (long long)h * w / 256; return (int)std::min(65535LL, std::max(8192LL, v)); }
-static int region_maxdf(int h, int w) { long long v = (long long)h * w / 16; return (int)std::max(65536LL, v); }   // x 17, pooled
-
-Layout make_layout(int n, int h, int w)
-{
-    Layout L;
-    const size_t N = (size_t)h * w;
-    size_t per[P_COUNT];
-    for (int i = 0; i < P_COUNT; i++) per[i] = N;  // u8 planes by default
-    per[P_JOINTS] = (size_t)MAXJ * 2 * sizeof(int);
-    per[P_STATE] = sizeof(FrameState);
-    per[P_TMP16] = 16;   // (unused)
-    per[P_LAB0] = N * 4;
-    per[P_LAB1] = N * 4;
-    per[P_ROOTS] = (size_t)MAXROOTS * sizeof(int);
-    per[P_JTMP] = (size_t)MAXJ * 3 * sizeof(int);
-    per[P_VERTS] = (size_t)MAXV * 2 * sizeof(int);
-    per[P_BEST] = sizeof(unsigned long long);
-    per[P_SEGS] = (size_t)2 * MAXSEG * sizeof(SegRec);
-    per[P_HIST] = 16 * 256 * sizeof(unsigned int);
-    per[P_LUT] = 16 * 256;
-    per[P_BLOBS] = (size_t)17 * MAXB * sizeof(BlobRec);
-    per[P_BLOB_D] = (size_t)17 * MAXB * 2 * sizeof(int);
-    per[P_ORDER] = (size_t)2 * MAXB * sizeof(int);   // + scratch of k_blob_merge's bucketed ranking
-    per[P_DISTS] = (size_t)17 * region_maxdf(h, w) * sizeof(double);
-    per[P_POOL] = (size_t)17 * region_maxch(h, w) * 128;
-    per[P_BLOB_CH] = (size_t)17 * MAXB * 16 * sizeof(unsigned short);
-    per[P_GROUPS] = (size_t)MAXG * sizeof(Group);
-    per[P_LOHI] = (size_t)2 * w * sizeof(int);
-    per[P_HULL] = (size_t)4 * w * sizeof(int);
-    per[P_LINES] = lines_ws_bytes();
-    per[P_NRECT] = 16 * sizeof(int);
-    per[P_LAB2] = N * 8;   // the bright forest of the blob sweep: {parent, merge-history word} per pixel
-    per[P_LAB3] = N * 4;
-    per[P_SW] = 192 * sizeof(int);
-    per[P_TL] = (size_t)sweep_pool(h, w, SWL_TRACE) * sizeof(int2);
-    per[P_BK] = N * 4;
-    per[P_LABP] = N * 4;
-    per[P_LABS] = N * 4;
-    per[P_ROOTSP] = (size_t)MAXROOTS * sizeof(int);
-    per[P_ROOTSS] = (size_t)MAXROOTS * sizeof(int);
-    per[P_BEST2] = sizeof(unsigned long long);
-    per[P_HPAR] = bit_plane_words(h, w) * 8;   // (slot re-used) one-bit plane of the joints mask, written by k_open20_joints
-    per[P_HTIME] = 16;
-    per[P_GMID] = (size_t)(MAXG - MAXG_LDS) * 4 * sizeof(double);   // x, y, r, next group in the grid cell
-    per[P_FLJ] = (size_t)2 * h * ((w + 63) / 64) * sizeof(unsigned long long);   // joints chain: background / outer-background bit masks
-    per[P_BITS] = (size_t)17 * bit_plane_words(h, w) * 8;   // 17 one-bit planes (cpe_dev.h tiled layout)
-    per[P_HL] = (size_t)sweep_pool(h, w, SWL_DARK) * sizeof(int2);
-    per[P_BL] = (size_t)sweep_pool(h, w, SWL_BRIGHT) * sizeof(int2);
-    per[P_SUBPIX] = (size_t)2 * MAXL * 2 * (size_t)(std::max(h, w) + 128) * sizeof(float);
-    // Buffers whose lifetimes never overlap share memory (the call is three chains -- ridge mask / joints, saturated spot,
-    // region -- that run side by side and meet in the masks stage, then the lines stage; only buffers of ONE chain, or of
-    // stages separated by the join, may be paired):
-    //   border points + distance scratch of the blob tracers (read last by k_blob_median) | blob groups (k_blob_merge .. k_discs)
-    //   bright forest + its accumulator (dead after k_enclosed_all / the outer borders)   | the masks stage's eight u8 planes
-    //   label scratch of the joints and spot chains (the latter again in the masks stage) | the lines stage's tables
-    //   dark forest + its accumulator (dead when the dark sweep ends; the forest plane is used again for the region's own
-    //   labelling after k_discs, the two as the expanded masks' label planes)              | blob records (hole borders .. k_blob_merge)
-    // Planes 0 .. P_G7 are readable after the call (cpe_detect_workspace_plane): nothing is ever written over them later
-    // (mask_contour and blur7 share memory with the bright forest, which is dead before they are written).
-    size_t o = 0;
-    bool placed[P_COUNT] = {};
-    auto put = [&](std::initializer_list<int> a, std::initializer_list<int> b, std::initializer_list<int> c = {}) {
-        size_t oa = o, ob = o, oc = o;
-        for (int p : a) { L.off[p] = oa; oa += align_up(per[p] * (size_t)n, 256); placed[p] = true; }
-        for (int p : b) { L.off[p] = ob; ob += align_up(per[p] * (size_t)n, 256); placed[p] = true; }
-        for (int p : c) { L.off[p] = oc; oc += align_up(per[p] * (size_t)n, 256); placed[p] = true; }
-        o = std::max(oa, std::max(ob, oc));
-    };
-    for (int i = 0; i < P_COUNT; i++) L.bytes_per_frame[i] = per[i];
-    put({P_DISTS, P_POOL}, {P_GROUPS});
-    // (round 3) also on the masks side of the bright forest: the disc-union image, mask_contour and the 7x7 blur -- all first
-    // written after k_enclosed_all, the forest's last reader, on the same stream or behind the join.  The label planes of
-    // the joints and spot chains are only needed inside those chains' own labelling (roots-only passes): the border-chunk
-    // ids / distance offsets of the blob tracers live there between the hole traces and the medians -- the tracers' stream
-    // waits for the two chains (RegionSide::joints_done / spot_done) -- and the lines stage's tables after that.
-    put({P_LAB2, P_LAB3}, {P_ROI_H, P_ROI_V, P_BASE_H, P_BASE_V, P_EXP_H, P_EXP_V, P_TMPA, P_TMPB, P_EXT, P_MASK_CONTOUR, P_G7});
-    put({P_LABP, P_LABS}, {P_LINES, P_SUBPIX}, {P_BLOB_CH, P_BLOB_D});
-    put({P_LAB0, P_LAB1}, {P_BLOBS});
-    for (int i = 0; i < P_COUNT; i++) {
-        if (placed[i]) continue;
-        L.off[i] = o;
-        o += align_up(per[i] * (size_t)n, 256);
-    }
-    L.total = o;
-    return L;
-}
 
 // per-frame state of a call, and the accumulators the three chains start from (one launch in front of the fork instead of a
 // reset kernel at the head of every chain)
@@ -191,37 +87,37 @@ SideStreams &side_streams(hipStream_t caller)
     return X;
 }
 
-// the region stage's buffers inside the workspace (cpe_detect_grid_batch*, cpe_debug_blob_region)
-RegionBuffers region_buffers(uint8_t *base, const Layout &L, int h, int w)
+// the region stage's buffers inside the workspace (cpe_detect_grid_batch*, cpe_debug_blob_region, cpe_debug_clahe_planes)
+RegionBuffers region_buffers(const Workspace &W, int h, int w)
 {
-#define PL(T, p) ((T *)(base + L.off[p]))
     RegionBuffers R;
-    R.cl = PL(uint8_t, P_CL); R.ext = PL(uint8_t, P_EXT); R.mc = PL(uint8_t, P_MASK_CONTOUR); R.touch = PL(uint8_t, P_TOUCH);
-    R.lab = PL(int, P_LAB0); R.cnt = PL(int, P_LAB1); R.roots = PL(int, P_ROOTS); R.nrect = PL(int, P_NRECT); R.lab2 = PL(int, P_LAB2); R.cnt2 = PL(int, P_LAB3);
-    R.sw = PL(int, P_SW); R.hl = PL(int2, P_HL); R.bl = PL(int2, P_BL); R.tl = PL(int2, P_TL); R.bk = PL(int, P_BK); R.bits = PL(uint32_t, P_BITS); R.pool = PL(uint32_t, P_POOL); R.blob_ch = PL(unsigned short, P_BLOB_CH); R.maxch = region_maxch(h, w); R.maxdf = region_maxdf(h, w); R.gmid = PL(double, P_GMID); R.hpar = PL(int, P_HPAR); R.htime = PL(uint8_t, P_HTIME); R.hist = PL(unsigned int, P_HIST); R.lut = PL(uint8_t, P_LUT);
-    R.blobs = PL(BlobRec, P_BLOBS); R.blob_d = PL(int, P_BLOB_D); R.order = PL(int, P_ORDER); R.dists = PL(double, P_DISTS);
-    R.groups = PL(Group, P_GROUPS); R.best = PL(unsigned long long, P_BEST); R.lohi = PL(int, P_LOHI); R.hull = PL(int, P_HULL);
-#undef PL
+    R.cl = W.at<uint8_t>(WS_CLAHE); R.ext = W.at<uint8_t>(WS_DISCS); R.mc = W.at<uint8_t>(WS_MASK_CONTOUR); R.touch = W.at<uint8_t>(WS_TOUCH);
+    R.lab = W.at<int>(WS_LABELS); R.cnt = W.at<int>(WS_LABELS_AUX); R.roots = W.at<int>(WS_ROOTS); R.nrect = W.at<int>(WS_NRECT);
+    R.lab2 = W.at<int>(WS_BRIGHT_NODES); R.cnt2 = W.at<int>(WS_BRIGHT_COUNTS); R.sw = W.at<int>(WS_SWEEP); R.bk = W.at<int>(WS_BUCKET_PIXELS);
+    R.hl = W.at<int2>(WS_LIST_DARK); R.bl = W.at<int2>(WS_LIST_BRIGHT); R.tl = W.at<int2>(WS_LIST_TRACE);
+    R.bits = W.at<uint32_t>(WS_BITS); R.pool = W.at<uint32_t>(WS_POOL); R.blob_ch = W.at<unsigned short>(WS_BLOB_CH);
+    R.maxch = region_maxch(h, w); R.maxdf = region_maxdf(h, w); R.gmid = W.at<double>(WS_GMID);
+    R.hist = W.at<unsigned int>(WS_HIST); R.lut = W.at<uint8_t>(WS_LUT);
+    R.blobs = W.at<BlobRec>(WS_BLOBS); R.blob_d = W.at<int>(WS_BLOB_D); R.order = W.at<int>(WS_ORDER); R.dists = W.at<double>(WS_DISTS);
+    R.groups = W.at<Group>(WS_GROUPS); R.best = W.at<unsigned long long>(WS_BEST); R.lohi = W.at<int>(WS_LOHI); R.hull = W.at<int>(WS_HULL);
     return R;
 }
 
 // the masks stage's buffers inside the workspace (cpe_detect_grid_batch*, cpe_debug_masks); R: region_buffers of the same call
-MaskBuffers mask_buffers(uint8_t *base, const Layout &L, const RegionBuffers &R)
+MaskBuffers mask_buffers(const Workspace &W, const RegionBuffers &R)
 {
-#define PL(T, p) ((T *)(base + L.off[p]))
     MaskBuffers M;
-    M.binary = PL(uint8_t, P_BINARY); M.hmask = PL(uint8_t, P_HMASK); M.vmask = PL(uint8_t, P_VMASK);
-    M.joints_mask = PL(uint8_t, P_JOINTS_MASK); M.tmpA = PL(uint8_t, P_TMPA); M.tmpB = PL(uint8_t, P_TMPB);
-    M.g19 = PL(uint8_t, P_G19); M.cm = PL(uint8_t, P_CM); M.mc = R.mc; M.roi_h = PL(uint8_t, P_ROI_H);
-    M.roi_v = PL(uint8_t, P_ROI_V); M.base_h = PL(uint8_t, P_BASE_H); M.base_v = PL(uint8_t, P_BASE_V);
-    M.exp_h = PL(uint8_t, P_EXP_H); M.exp_v = PL(uint8_t, P_EXP_V); M.touch = R.touch; M.bits = R.bits;
-    M.lab = R.lab; M.roots = R.roots; M.jtmp = PL(int, P_JTMP); M.joints = PL(int, P_JOINTS); M.verts = PL(int, P_VERTS);
-    M.best = R.best; M.segs = PL(SegRec, P_SEGS);
-    M.lab_p = PL(int, P_LABP); M.lab_s = PL(int, P_LABS); M.roots_p = PL(int, P_ROOTSP); M.roots_s = PL(int, P_ROOTSS);
-    M.best_s = PL(unsigned long long, P_BEST2);
-    M.fl_j = PL(unsigned long long, P_FLJ); M.jbits = PL(uint32_t, P_HPAR);
-    M.lab_h = nullptr; M.lab_v = nullptr;   // set by the caller once the region stage is done with the label planes
-#undef PL
+    M.binary = W.at<uint8_t>(WS_BINARY); M.hmask = W.at<uint8_t>(WS_HMASK); M.vmask = W.at<uint8_t>(WS_VMASK);
+    M.joints_mask = W.at<uint8_t>(WS_JOINTS_MASK); M.tmpA = W.at<uint8_t>(WS_TMPA); M.tmpB = W.at<uint8_t>(WS_TMPB);
+    M.g19 = W.at<uint8_t>(WS_BLUR19); M.cm = W.at<uint8_t>(WS_CM); M.mc = R.mc; M.roi_h = W.at<uint8_t>(WS_ROI_H);
+    M.roi_v = W.at<uint8_t>(WS_ROI_V); M.base_h = W.at<uint8_t>(WS_BASE_H); M.base_v = W.at<uint8_t>(WS_BASE_V);
+    M.exp_h = W.at<uint8_t>(WS_EXP_H); M.exp_v = W.at<uint8_t>(WS_EXP_V); M.touch = R.touch; M.bits = R.bits;
+    M.lab = R.lab; M.roots = R.roots; M.jtmp = W.at<int>(WS_JTMP); M.joints = W.at<int>(WS_JOINTS); M.verts = W.at<int>(WS_VERTS);
+    M.best = R.best; M.segs = W.at<SegRec>(WS_SEGS);
+    M.lab_p = W.at<int>(WS_LABELS_JOINTS); M.lab_s = W.at<int>(WS_LABELS_SPOT);
+    M.roots_p = W.at<int>(WS_ROOTS_JOINTS); M.roots_s = W.at<int>(WS_ROOTS_SPOT); M.best_s = W.at<unsigned long long>(WS_BEST_SPOT);
+    M.fl_j = W.at<unsigned long long>(WS_FLJ); M.jbits = W.at<uint32_t>(WS_JOINT_BITS);
+    M.lab_h = nullptr; M.lab_v = nullptr;   // WS_LABELS / WS_LABELS_AUX, set by the caller once the region stage is done with them
     return M;
 }
 
@@ -239,13 +135,29 @@ extern "C" size_t cpe_detect_workspace_bytes(int32_t n, int32_t h, int32_t w)
 extern "C" int32_t cpe_detect_workspace_plane(int32_t n, int32_t h, int32_t w, int32_t plane, size_t *offset,
                                               size_t *bytes_per_frame)
 {
-    CPE_CHECK_ARG(n > 0 && h > 0 && w > 0 && plane >= 0 && plane <= P_G7 + 2 && offset && bytes_per_frame,
+    CPE_CHECK_ARG(n > 0 && h > 0 && w > 0 && plane >= 0 && plane < CPE_PLANE_COUNT && offset && bytes_per_frame,
                   "cpe_detect_workspace_plane: bad argument");
-    Layout L = make_layout(n, h, w);
-    if (plane == P_G7 + 1) plane = P_LAB0;
-    else if (plane == P_G7 + 2) plane = P_SW;
-    *offset = L.off[plane];
-    *bytes_per_frame = L.bytes_per_frame[plane];
+    const Layout L = make_layout(n, h, w);
+    const WsId id = ws_public(plane);
+    *offset = L.off[id];
+    *bytes_per_frame = L.bytes_per_frame[id];
+    return CPE_OK;
+}
+
+// One row of the workspace's table of buffers (CPE_WS_TABLE) for an (n, h, w) call: host code only (tests, debugging).
+extern "C" int32_t cpe_debug_workspace_buffer(int32_t n, int32_t h, int32_t w, int32_t index, char *name_out, size_t name_cap,
+                                              size_t *offset, size_t *bytes_per_frame, int32_t *overlay, int32_t *side,
+                                              int32_t *public_plane)
+{
+    CPE_CHECK_ARG(n > 0 && h > 0 && w > 0 && index >= 0 && index < WS_COUNT && name_out && name_cap > 0 && offset && bytes_per_frame &&
+                  overlay && side && public_plane, "cpe_debug_workspace_buffer: bad argument");
+    const Layout L = make_layout(n, h, w);
+    const WsRow &r = WS_ROWS[index];
+    size_t k = 0;
+    for (; r.name[k] && k + 1 < name_cap; k++) name_out[k] = (char)tolower(r.name[k]);
+    name_out[k] = 0;
+    *offset = L.off[index]; *bytes_per_frame = L.bytes_per_frame[index];
+    *overlay = r.overlay; *side = r.side; *public_plane = r.public_plane;
     return CPE_OK;
 }
 
@@ -297,24 +209,19 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
     CPE_CHECK_ARG(n >= 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096,
                   "cpe_detect_grid_batch: need n>=0 and 64 <= h,w <= 4096 (got %d,%d,%d)", n, h, w);
     if (n == 0) return CPE_OK;
-    Layout L = make_layout(n, h, w);
-    if (!ws || ws_bytes < L.total) {
-        cpe::set_error("cpe_detect_grid_batch: workspace too small (%zu < %zu)", ws_bytes, L.total);
-        return CPE_ERR_WORKSPACE;
-    }
-    CPE_CHECK_ARG(((uintptr_t)ws & 255) == 0, "cpe_detect_grid_batch: workspace must be 256-byte aligned");
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_detect_grid_batch", CPE_ERR_WORKSPACE)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    uint8_t *base = (uint8_t *)ws;
-#define PL(T, p) ((T *)(base + L.off[p]))
-    FrameState *st = PL(FrameState, P_STATE);
+    FrameState *st = W.state();
     // colour input: the grey plane lives in the workspace; the L plane borrows the disc plane of the region stage, which is
     // first written (cleared) after CLAHE has read L.  The planar target reads no L plane: its region stage thresholds the
     // any-channel plane instead (get_convex_hull of util_plane.py), kept in the CLAHE plane, which that target never uses.
-    uint8_t *lplane = bgr && !planar ? PL(uint8_t, P_EXT) : nullptr;
-    uint8_t *anyplane = bgr && planar ? PL(uint8_t, P_CL) : nullptr;
-    if (bgr) gray = PL(uint8_t, P_GRAYIN);
-    RegionBuffers R = region_buffers(base, L, h, w);
-    MaskBuffers M = mask_buffers(base, L, R);
+    uint8_t *lplane = bgr && !planar ? W.at<uint8_t>(WS_DISCS) : nullptr;
+    uint8_t *anyplane = bgr && planar ? W.at<uint8_t>(WS_CLAHE) : nullptr;
+    uint8_t *const grayin = W.at<uint8_t>(WS_GRAYIN), *const g7 = W.at<uint8_t>(WS_BLUR7);
+    if (bgr) gray = grayin;
+    RegionBuffers R = region_buffers(W, h, w);
+    MaskBuffers M = mask_buffers(W, R);
     // three chains that only meet in masks_stage: ridge mask -> line masks -> joints (stream 1), saturated spot
     // (stream 2), region (the caller's stream).  The side chains are mostly ALU / latency bound and fill the CUs the
     // region stage's serial kernels leave idle.  The helper streams and their events are per device and shared by all
@@ -331,11 +238,11 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
         CPE_CHECK_LAUNCH("k_state_init");
         if (bgr && planar) {   // BGR2GRAY and the any-channel threshold of get_convex_hull, from one read of the frame
             const size_t npx = (size_t)n * h * w;
-            CPE_KLAUNCH(k_bgr2gray_any, dim3((unsigned)(((npx + 3) / 4 + 255) / 256)), dim3(256), 0, s, bgr, npx, PL(uint8_t, P_GRAYIN), anyplane);
+            CPE_KLAUNCH(k_bgr2gray_any, dim3((unsigned)(((npx + 3) / 4 + 255) / 256)), dim3(256), 0, s, bgr, npx, grayin, anyplane);
             CPE_CHECK_LAUNCH("colour planes");
         } else if (bgr) {      // BGR2GRAY (load_and_preprocess_image, mask_roi_around_center) and the L channel of BGR2LAB (detect_largest_blob)
             const size_t npx = (size_t)n * h * w;
-            CPE_KLAUNCH(k_bgr2gray, dim3((unsigned)(((npx + 3) / 4 + 255) / 256)), dim3(256), 0, s, bgr, npx, PL(uint8_t, P_GRAYIN));
+            CPE_KLAUNCH(k_bgr2gray, dim3((unsigned)(((npx + 3) / 4 + 255) / 256)), dim3(256), 0, s, bgr, npx, grayin);
             CPE_KLAUNCH(k_bgr2labl, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 1 << 16)), dim3(256), 0, s, bgr, npx, lplane);
             CPE_CHECK_LAUNCH("colour planes");
         }
@@ -361,14 +268,14 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
             CPE_CHECK_HIP(hipStreamWaitEvent(s, X.join2, 0));
             forked = false;
         }
-        M.lab_h = PL(int, P_LAB0); M.lab_v = PL(int, P_LAB1);
+        M.lab_h = W.at<int>(WS_LABELS); M.lab_v = W.at<int>(WS_LABELS_AUX);
         // the 7x7 blur of the indexing step only needs the region rectangle, and only the lines kernel reads the joints: both
         // run on the (now idle) spot stream beside the fragment chains of the masks stage
         if (X.ok) {
             CPE_CHECK_HIP(hipEventRecord(X.fork, s));
             CPE_CHECK_HIP(hipStreamWaitEvent(X.s2, X.fork, 0));
             forked = true;
-            if ((rc = bgr ? blur7_bgr(bgr, n, h, w, st, PL(uint8_t, P_G7), X.s2) : blur7_u8(gray, n, h, w, st, PL(uint8_t, P_G7), X.s2)) != CPE_OK) return rc;
+            if ((rc = bgr ? blur7_bgr(bgr, n, h, w, st, g7, X.s2) : blur7_u8(gray, n, h, w, st, g7, X.s2)) != CPE_OK) return rc;
         }
         if ((rc = masks_stage(gray, n, h, w, M, st, s, X.ok ? &rside : nullptr, planar, X.ok ? X.s2 : s)) != CPE_OK) return rc;   // joints: on s2 too
         if (X.ok) {
@@ -376,9 +283,9 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
             CPE_CHECK_HIP(hipStreamWaitEvent(s, X.join2, 0));
             forked = false;
         }
-        else if ((rc = bgr ? blur7_bgr(bgr, n, h, w, st, PL(uint8_t, P_G7), s) : blur7_u8(gray, n, h, w, st, PL(uint8_t, P_G7), s)) != CPE_OK) return rc;
-        if ((rc = lines_stage(PL(int, P_LAB0), PL(int, P_LAB1), M.exp_h, M.exp_v, PL(uint8_t, P_G7), n, h, w, M.joints, st, PL(void, P_LINES), xy, id,
-                              n_pts, center, gray, prm.subpixel, prm.subpixel_window, prm.subpixel_step, PL(float, P_SUBPIX),
+        else if ((rc = bgr ? blur7_bgr(bgr, n, h, w, st, g7, s) : blur7_u8(gray, n, h, w, st, g7, s)) != CPE_OK) return rc;
+        if ((rc = lines_stage(M.lab_h, M.lab_v, M.exp_h, M.exp_v, g7, n, h, w, M.joints, st, W.at<void>(WS_LINES), xy, id,
+                              n_pts, center, gray, prm.subpixel, prm.subpixel_window, prm.subpixel_step, W.at<float>(WS_SUBPIX),
                               std::max(h, w) + 128, s, planar)) != CPE_OK)
             return rc;
         CPE_LAUNCH_BEGIN();
@@ -397,7 +304,6 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
         (void)hipGetLastError();
     }
     return rc;
-#undef PL
 }
 
 extern "C" int32_t cpe_detect_grid_batch_ex(const uint8_t *gray, int32_t n, int32_t h, int32_t w, const CpeDetectParams *params,
@@ -422,9 +328,9 @@ extern "C" int32_t cpe_detect_line_tables(const void *ws, size_t ws_bytes, int32
     CPE_CHECK_ARG(ws && eq && npts && pts && n_lines && n > 0 && frame >= 0 && frame < n && h >= 64 && w >= 64,
                   "cpe_detect_line_tables: bad argument");
     static_assert(CPE_MAXL == MAXL, "cpe.h and cpe_dev.h disagree on the line capacity");
-    Layout L = make_layout(n, h, w);
-    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_detect_line_tables: not the workspace of an (n,h,w) call");
-    return lines_export((const uint8_t *)ws + L.off[P_LINES], frame, eq, npts, pts, n_lines, (hipStream_t)stream);
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_detect_line_tables")) return rc;
+    return lines_export(W.at<const uint8_t>(WS_LINES), frame, eq, npts, pts, n_lines, (hipStream_t)stream);
 }
 
 extern "C" int32_t cpe_detect_results_sizes(const void *ws, size_t ws_bytes, int32_t n, int32_t h, int32_t w, const int32_t *n_pts,
@@ -432,10 +338,10 @@ extern "C" int32_t cpe_detect_results_sizes(const void *ws, size_t ws_bytes, int
 {
     CPE_CHECK_ARG(ws && n_pts && status && offsets && n > 0 && h >= 64 && w >= 64 && ((uintptr_t)n_pts & 3) == 0 &&
                   ((uintptr_t)status & 3) == 0 && ((uintptr_t)offsets & 7) == 0, "cpe_detect_results_sizes: bad argument");
-    Layout L = make_layout(n, h, w);
-    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_detect_results_sizes: not the workspace of an (n,h,w) call");
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_detect_results_sizes")) return rc;
     static_assert(sizeof(long long) == sizeof(int64_t), "offsets are 64-bit");
-    return results_sizes((const uint8_t *)ws + L.off[P_LINES], n, n_pts, (long long *)offsets, (hipStream_t)stream);
+    return results_sizes(W.at<const uint8_t>(WS_LINES), n, n_pts, (long long *)offsets, (hipStream_t)stream);
 }
 
 extern "C" int32_t cpe_detect_results_pack(const void *ws, size_t ws_bytes, int32_t n, int32_t h, int32_t w, const double *xy,
@@ -446,9 +352,9 @@ extern "C" int32_t cpe_detect_results_pack(const void *ws, size_t ws_bytes, int3
                   "cpe_detect_results_pack: bad argument");
     CPE_CHECK_ARG((((uintptr_t)xy | (uintptr_t)id | (uintptr_t)center | (uintptr_t)offsets | (uintptr_t)payload) & 7) == 0 &&
                   (((uintptr_t)n_pts | (uintptr_t)status) & 3) == 0, "cpe_detect_results_pack: a buffer is not aligned (8 bytes; n_pts, status: 4)");
-    Layout L = make_layout(n, h, w);
-    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_detect_results_pack: not the workspace of an (n,h,w) call");
-    return results_pack((const uint8_t *)ws + L.off[P_LINES], n, xy, id, n_pts, center, status, (const long long *)offsets, payload,
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_detect_results_pack")) return rc;
+    return results_pack(W.at<const uint8_t>(WS_LINES), n, xy, id, n_pts, center, status, (const long long *)offsets, payload,
                         payload_bytes, (hipStream_t)stream);
 }
 
@@ -542,20 +448,19 @@ extern "C" int32_t cpe_debug_external_components(const uint8_t *mask, int32_t n,
                                                  int32_t *first_px, int32_t cap, int32_t *count, void *stream)
 {
     CPE_CHECK_ARG(mask && ws && first_px && count && n > 0 && h >= 64 && w >= 64 && w <= 4096 && cap > 0, "cpe_debug_external_components: bad argument");
-    Layout L = make_layout(n, h, w);
-    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_debug_external_components: workspace too small or misaligned");
-    uint8_t *base = (uint8_t *)ws;
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_external_components")) return rc;
     hipStream_t s = (hipStream_t)stream;
-    FrameState *st = (FrameState *)(base + L.off[P_STATE]);
-    int *roots = (int *)(base + L.off[P_ROOTS]);
+    FrameState *st = W.state();
+    int *roots = W.at<int>(WS_ROOTS);
     int rc;
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int *)nullptr);
     CPE_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)n * sizeof(int), s));
-    if ((rc = ccl_components(mask, nullptr, n, h, w, 0, WIN_FRAME, (int *)(base + L.off[P_LAB0]), roots, ROOTS_MAIN, st, s)) != CPE_OK) return rc;
+    if ((rc = ccl_components(mask, nullptr, n, h, w, 0, WIN_FRAME, W.at<int>(WS_LABELS), roots, ROOTS_MAIN, st, s)) != CPE_OK) return rc;
     const size_t fl_words = bit_plane_words(h, w);   // u64 words per frame of a flood plane (>= h * ceil(w / 64))
-    unsigned long long *bgw = bit_plane((uint32_t *)(base + L.off[P_BITS]), 0, h, w);
-    unsigned long long *out = bit_plane((uint32_t *)(base + L.off[P_BITS]), n, h, w);
+    unsigned long long *bgw = bit_plane(W.at<uint32_t>(WS_BITS), 0, h, w);
+    unsigned long long *out = bit_plane(W.at<uint32_t>(WS_BITS), n, h, w);
     if ((rc = outside_flood(mask, n, h, w, st, WIN_FRAME, bgw, out, fl_words, s, nullptr)) != CPE_OK) return rc;
     CPE_KLAUNCH(k_list_external, dim3(32, n), dim3(256), 0, s, (const int *)roots, (const FrameState *)st, w, (const unsigned long long *)out, fl_words,
                 first_px, cap, count);
@@ -570,18 +475,17 @@ extern "C" int32_t cpe_debug_ccl(const uint8_t *img, int32_t n, int32_t h, int32
                                  size_t ws_bytes, void *stream)
 {
     CPE_CHECK_ARG(img && ws && n > 0 && h >= 64 && w >= 64, "cpe_debug_ccl: bad argument");
-    Layout L = make_layout(n, h, w);
-    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_debug_ccl: workspace too small or misaligned");
-    uint8_t *base = (uint8_t *)ws;
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_ccl")) return rc;
     hipStream_t s = (hipStream_t)stream;
-    FrameState *st = (FrameState *)(base + L.off[P_STATE]);
+    FrameState *st = W.state();
     CclPass p;
     p.thr = thr; p.invert = invert; p.conn8 = conn8; p.win = (want_bbox >> 1) & 1 ? WIN_SWEEP : WIN_FRAME;
-    p.count = (CclCount)count_mode; p.cnt = (int *)(base + L.off[P_LAB1]);
-    p.touch = invert ? (uint8_t *)(base + L.off[P_TOUCH]) : nullptr;   // the background sets: holes only
-    p.roots = want_roots ? (int *)(base + L.off[P_ROOTS]) : nullptr;
-    p.nrect = (want_bbox & 1) ? (int *)(base + L.off[P_NRECT]) : nullptr;
-    return ccl_label(img, n, h, w, (int *)(base + L.off[P_LAB0]), p, st, s);
+    p.count = (CclCount)count_mode; p.cnt = W.at<int>(WS_LABELS_AUX);
+    p.touch = invert ? W.at<uint8_t>(WS_TOUCH) : nullptr;   // the background sets: holes only
+    p.roots = want_roots ? W.at<int>(WS_ROOTS) : nullptr;
+    p.nrect = (want_bbox & 1) ? W.at<int>(WS_NRECT) : nullptr;
+    return ccl_label(img, n, h, w, W.at<int>(WS_LABELS), p, st, s);
 }
 
 namespace cpe { namespace {
@@ -609,13 +513,12 @@ extern "C" int32_t cpe_debug_dark_labels(const uint8_t *img, int32_t n, int32_t 
     CPE_CHECK_ARG(img && rect && ws && lab && cnt && roots && n_roots && n > 0 && h >= 64 && w >= 64 && (path == 0 || path == 1) &&
                   thr >= 0 && thr + 160 <= 255,
                   "cpe_debug_dark_labels: bad argument");
-    Layout L = make_layout(n, h, w);
-    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_debug_dark_labels: workspace too small or misaligned");
-    uint8_t *base = (uint8_t *)ws;
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_dark_labels")) return rc;
     hipStream_t s = (hipStream_t)stream;
-    FrameState *st = (FrameState *)(base + L.off[P_STATE]);
-    int *lb = (int *)(base + L.off[P_LAB0]), *cb = (int *)(base + L.off[P_LAB1]), *rb = (int *)(base + L.off[P_ROOTS]);
-    uint32_t *bits = (uint32_t *)(base + L.off[P_BITS]);
+    FrameState *st = W.state();
+    int *lb = W.at<int>(WS_LABELS), *cb = W.at<int>(WS_LABELS_AUX), *rb = W.at<int>(WS_ROOTS);
+    uint32_t *bits = W.at<uint32_t>(WS_BITS);
     const size_t N = (size_t)h * w;
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int *)nullptr);
@@ -648,15 +551,14 @@ extern "C" int32_t cpe_debug_blob_region(const uint8_t *img, int32_t n, int32_t 
 {
     CPE_CHECK_ARG(img && ws && kp && n_kp && blobs && n_blobs && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096 &&
                   kp_cap > 0 && blob_cap > 0, "cpe_debug_blob_region: bad argument");
-    Layout L = make_layout(n, h, w);
-    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_debug_blob_region: workspace too small or misaligned");
-    uint8_t *base = (uint8_t *)ws;
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_blob_region")) return rc;
     hipStream_t s = (hipStream_t)stream;
-    FrameState *st = (FrameState *)(base + L.off[P_STATE]);
-    RegionBuffers R = region_buffers(base, L, h, w);
+    FrameState *st = W.state();
+    RegionBuffers R = region_buffers(W, h, w);
     RegionProbe probe = {1, blobs, blob_cap, n_blobs, kp, kp_cap, n_kp};
     CPE_LAUNCH_BEGIN();
-    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, (unsigned long long *)(base + L.off[P_BEST2]), R.nrect);
+    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, W.at<unsigned long long>(WS_BEST_SPOT), R.nrect);
     CPE_CHECK_LAUNCH("k_state_init");
     return region_stage(img, n, h, w, 4.5, R, st, s, nullptr, nullptr, &probe);
 }
@@ -667,14 +569,13 @@ extern "C" int32_t cpe_debug_clahe_planes(const uint8_t *gray, int32_t n, int32_
 {
     CPE_CHECK_ARG(gray && ws && cl && planes && buckets && box && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096,
                   "cpe_debug_clahe_planes: bad argument");
-    Layout L = make_layout(n, h, w);
-    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_debug_clahe_planes: workspace too small or misaligned");
-    uint8_t *base = (uint8_t *)ws;
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_clahe_planes")) return rc;
     hipStream_t s = (hipStream_t)stream;
-    FrameState *st = (FrameState *)(base + L.off[P_STATE]);
-    RegionBuffers R = region_buffers(base, L, h, w);
+    FrameState *st = W.state();
+    RegionBuffers R = region_buffers(W, h, w);
     CPE_LAUNCH_BEGIN();
-    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, (unsigned long long *)(base + L.off[P_BEST2]), R.nrect);
+    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, W.at<unsigned long long>(WS_BEST_SPOT), R.nrect);
     CPE_CHECK_LAUNCH("k_state_init");
     return clahe_front_probe(gray, n, h, w, fused, R, s, cl, planes, buckets, box);
 }
@@ -698,14 +599,13 @@ extern "C" int32_t cpe_debug_masks(const uint8_t *binary, const uint8_t *gray, c
 {
     CPE_CHECK_ARG(binary && gray && mask_contour && rect && region_status && ws && n > 0 && h >= 64 && w >= 64 && h <= 4096 &&
                   w <= 4096 && (target == CPE_TARGET_CYLINDER || target == CPE_TARGET_PLANE), "cpe_debug_masks: bad argument");
-    Layout L = make_layout(n, h, w);
-    CPE_CHECK_ARG(ws_bytes >= L.total && ((uintptr_t)ws & 255) == 0, "cpe_debug_masks: workspace too small or misaligned");
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_masks")) return rc;
     const int planar = target == CPE_TARGET_PLANE ? 1 : 0;
-    uint8_t *base = (uint8_t *)ws;
     hipStream_t s = (hipStream_t)stream;
-    FrameState *st = (FrameState *)(base + L.off[P_STATE]);
-    RegionBuffers R = region_buffers(base, L, h, w);
-    MaskBuffers M = mask_buffers(base, L, R);
+    FrameState *st = W.state();
+    RegionBuffers R = region_buffers(W, h, w);
+    MaskBuffers M = mask_buffers(W, R);
     const size_t total = (size_t)n * h * w;
     int rc;
     CPE_LAUNCH_BEGIN();
@@ -716,7 +616,7 @@ extern "C" int32_t cpe_debug_masks(const uint8_t *binary, const uint8_t *gray, c
     CPE_CHECK_LAUNCH("cpe_debug_masks");
     if ((rc = joints_mask_stage(n, h, w, M, st, s)) != CPE_OK) return rc;
     if ((rc = spot_stage(gray, n, h, w, M, st, s, planar)) != CPE_OK) return rc;
-    M.lab_h = (int *)(base + L.off[P_LAB0]); M.lab_v = (int *)(base + L.off[P_LAB1]);
+    M.lab_h = W.at<int>(WS_LABELS); M.lab_v = W.at<int>(WS_LABELS_AUX);
     if ((rc = masks_stage(gray, n, h, w, M, st, s, nullptr, planar, s)) != CPE_OK) return rc;
-    return blur7_u8(gray, n, h, w, st, (uint8_t *)(base + L.off[P_G7]), s);
+    return blur7_u8(gray, n, h, w, st, W.at<uint8_t>(WS_BLUR7), s);
 }

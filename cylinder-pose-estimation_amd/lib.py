@@ -44,6 +44,7 @@ _SIGS = {
                                 [C.c_size_t, C.c_void_p]),
     'cpe_bgr2gray_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'cpe_detect_workspace_plane': (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'cpe_debug_workspace_buffer': (C.c_int32, [C.c_int32] * 4 + [C.c_char_p, C.c_size_t] + [C.c_void_p] * 5),
     'cpe_debug_external_components': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                                                   C.c_void_p, C.c_void_p]),
     'cpe_debug_ccl': (C.c_int32, [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -36,10 +36,10 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 108   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 109   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
-                             cpe_detect_results_pack) */
+                             cpe_detect_results_pack; 109: cpe_debug_workspace_buffer) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -263,6 +263,14 @@ CPE_API int32_t cpe_bgr2gray_batch(const uint8_t *bgr, int32_t n, int32_t h, int
                                      [42+k] blobs of threshold 50+10k (k < 17); see csrc/region.hip SW_* */
 CPE_API int32_t cpe_detect_workspace_plane(int32_t n, int32_t h, int32_t w, int32_t plane, size_t *offset,
                                            size_t *bytes_per_frame);
+
+/* Row `index` (0, 1, ...; CPE_ERR_ARG past the last) of the workspace's table of buffers (csrc/workspace.h) for an (n,h,w)
+ * call: its name (at most name_cap - 1 characters), where it lies, the overlay it belongs to (0: it shares memory with nothing;
+ * buffers of the same overlay on different sides do) and its side, and its CPE_PLANE_* number or -1.  Host code only: no GPU
+ * call.  Offsets are not a contract.  Test / debugging aid. */
+CPE_API int32_t cpe_debug_workspace_buffer(int32_t n, int32_t h, int32_t w, int32_t index, char *name_out, size_t name_cap,
+                                           size_t *offset, size_t *bytes_per_frame, int32_t *overlay, int32_t *side,
+                                           int32_t *public_plane);
 
 /* One stand-alone connected-component pass (cv2.connectedComponents / the front end of cv2.findContours,
  * util_cylinder.py:28,161,1817,1883,1968) over img u8[n,h,w]: set = (img > thr) != invert, 8- or 4-connected;
