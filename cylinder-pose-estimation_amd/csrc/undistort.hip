@@ -194,6 +194,94 @@ __global__ __launch_bounds__(256) void k_remap_cubic(const uint8_t *__restrict__
     }
 }
 
+// ---- preProcessing.m:3-9 in one pass: im2uint8 -> undistortImage(..., 'cubic') per channel -> rgb2gray -> u8 grey.
+// [ext] im2uint8 and rgb2gray are toolbox functions (parity unpinned vs MATLAB, as for the cubic remap): im2uint8 is
+// restated as round(x / 257) for uint16 and round(x * 255), saturated, NaN -> 0, for single / double; rgb2gray as
+// iotool.preprocessing has it.  The kernel is the composition of those with k_remap_cubic and gives the same bytes.
+//
+// im2uint8 is applied to every tap as it is loaded, so the cubic sums see exactly the u8 values the separate passes would
+// have stored; every channel is rounded to u8 before the grey sum, as undistortImage returns u8 planes.
+__device__ __forceinline__ float tap_u8(uint8_t x) { return (float)x; }
+__device__ __forceinline__ float tap_u8(uint16_t x) { return (float)(((unsigned)x + 128u) / 257u); }   // round(x / 257): 257 is odd, no ties
+__device__ __forceinline__ float tap_u8(float x)
+{
+    const float v = x * 255.0f;
+    if (!(v > 0.0f)) return 0.0f;   // NaN, -0, negatives
+    return v >= 255.0f ? 255.0f : roundf(v);
+}
+__device__ __forceinline__ float tap_u8(double x)
+{
+    const double v = x * 255.0;
+    if (!(v > 0.0)) return 0.0f;
+    return v >= 255.0 ? 255.0f : (float)round(v);
+}
+
+// rgb2gray: the first row of inv([1 .956 .621; 1 -.272 -.647; 1 -1.106 1.703]) on R, G, B in f64, left to right, rounded
+__device__ __forceinline__ int gray_u8(int r, int g, int b)
+{
+    const double v = floor((((double)r * 0.298936021293775 + (double)g * 0.587043074451121) + (double)b * 0.114020904255103) + 0.5);
+    return v <= 0.0 ? 0 : (v >= 255.0 ? 255 : (int)v);
+}
+
+// the C adjacent elements of one source pixel in one go (a 3-byte, 6-byte, dwordx3 or 3 x dwordx2 access)
+template <typename T, int C> struct Px { T v[C]; };
+
+// one output pixel per thread, as k_remap_cubic; its map entry and weights are made once and applied to REMAP_FRAMES
+// frames.  As there, the taps are unconditional loads from clamped addresses: no lane reads outside src whatever the map holds.
+template <typename T, int C>
+__global__ __launch_bounds__(256) void k_prestep(const T *__restrict__ src, int n, int h, int w, const float2 *__restrict__ map,
+                                                 int fill, uint8_t *__restrict__ dst, long long dst_stride)
+{
+    const int N = h * w;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= N) return;
+    const float2 m = map[p];
+    const float x = m.x, y = m.y;
+    const bool inside = x >= 0.0f && y >= 0.0f && x <= (float)(w - 1) && y <= (float)(h - 1);
+    const int ix = min(max((int)floorf(x), 0), w - 2);
+    const int iy = min(max((int)floorf(y), 0), h - 2);
+    float wx[4], wy[4];
+    keys_weights(x - (float)ix, wx);
+    keys_weights(y - (float)iy, wy);
+    const int f0 = blockIdx.y * REMAP_FRAMES, f1 = min(f0 + REMAP_FRAMES, n);
+    for (int f = f0; f < f1; f++) {
+        const Px<T, C> *s0 = reinterpret_cast<const Px<T, C> *>(src) + f * (size_t)N;
+        int u[C];
+#pragma unroll
+        for (int ch = 0; ch < C; ch++) u[ch] = fill;
+        if (inside) {
+            float row[C][4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int yy = min(max(iy - 1 + r, 0), h - 1);
+                float s[C][4];
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    const Px<T, C> t = s0[(size_t)yy * w + min(max(ix - 1 + c, 0), w - 1)];
+#pragma unroll
+                    for (int ch = 0; ch < C; ch++) s[ch][c] = tap_u8(t.v[ch]);
+                }
+#pragma unroll
+                for (int ch = 0; ch < C; ch++) {
+                    if (ix - 1 < 0) s[ch][0] = (3.0f * s[ch][1] - 3.0f * s[ch][2]) + s[ch][3];
+                    if (ix + 2 >= w) s[ch][3] = (3.0f * s[ch][2] - 3.0f * s[ch][1]) + s[ch][0];
+                    row[ch][r] = ((s[ch][0] * wx[0] + s[ch][1] * wx[1]) + s[ch][2] * wx[2]) + s[ch][3] * wx[3];
+                }
+            }
+#pragma unroll
+            for (int ch = 0; ch < C; ch++) {
+                if (iy - 1 < 0) row[ch][0] = (3.0f * row[ch][1] - 3.0f * row[ch][2]) + row[ch][3];
+                if (iy + 2 >= h) row[ch][3] = (3.0f * row[ch][2] - 3.0f * row[ch][1]) + row[ch][0];
+                const float v = ((row[ch][0] * wy[0] + row[ch][1] * wy[1]) + row[ch][2] * wy[2]) + row[ch][3] * wy[3];
+                u[ch] = v <= 0.0f ? 0 : (v >= 255.0f ? 255 : (int)floorf(v + 0.5f));
+            }
+        }
+        int out = u[0];
+        if constexpr (C == 3) out = gray_u8(u[0], u[1], u[2]);
+        dst[f * (size_t)dst_stride + p] = (uint8_t)out;
+    }
+}
+
 }  // namespace
 
 extern "C" int32_t cpe_undistort_map(const double *K, const double *dist, int32_t n_dist, int32_t h, int32_t w,
@@ -271,5 +359,49 @@ extern "C" int32_t cpe_remap_cubic_batch(const uint8_t *src, int32_t n, int32_t 
     CPE_KLAUNCH(k_remap_cubic, dim3((unsigned)(((size_t)h * w + 255) / 256), (n + REMAP_FRAMES - 1) / REMAP_FRAMES), dim3(256), 0,
                 (hipStream_t)stream, src, n, h, w, reinterpret_cast<const float2 *>(map), fill, dst);
     CPE_CHECK_LAUNCH("k_remap_cubic");
+    return CPE_OK;
+}
+
+namespace {
+
+template <typename T, int C>
+void launch_prestep(const void *src, int n, int h, int w, const float2 *map, int fill, uint8_t *dst, long long stride, hipStream_t stream)
+{
+    const size_t N = (size_t)h * w;
+    CPE_KLAUNCH((k_prestep<T, C>), dim3((unsigned)((N + 255) / 256), (unsigned)((n + REMAP_FRAMES - 1) / REMAP_FRAMES)), dim3(256), 0, stream,
+                static_cast<const T *>(src), n, h, w, map, fill, dst, stride);
+}
+
+}  // namespace
+
+extern "C" int32_t cpe_matlab_prestep_batch(const void *src, int32_t n, int32_t h, int32_t w, int32_t dtype, int32_t channels,
+                                            const float *map, int32_t fill, uint8_t *dst, int64_t dst_frame_stride, void *stream)
+{
+    CPE_CHECK_ARG(src && dst && map, "cpe_matlab_prestep_batch: null pointer");
+    CPE_CHECK_ARG(src != (const void *)dst, "cpe_matlab_prestep_batch: in-place remap is not possible");
+    CPE_CHECK_ARG(n >= 0 && n <= 65535 * REMAP_FRAMES && h >= 3 && w >= 3 && (long long)h * w < (1ll << 31),
+                  "cpe_matlab_prestep_batch: bad size");
+    CPE_CHECK_ARG(dtype == CPE_PIX_U8 || dtype == CPE_PIX_U16 || dtype == CPE_PIX_F32 || dtype == CPE_PIX_F64,
+                  "cpe_matlab_prestep_batch: element type %d", dtype);
+    CPE_CHECK_ARG(channels == 1 || channels == 3, "cpe_matlab_prestep_batch: %d channels (1 or 3)", channels);
+    CPE_CHECK_ARG(fill >= 0 && fill <= 255 && (((size_t)map) & 7) == 0, "cpe_matlab_prestep_batch: fill value / map alignment");
+    CPE_CHECK_ARG(dst_frame_stride >= (int64_t)h * w, "cpe_matlab_prestep_batch: destination stride below h*w");
+    const size_t esz = dtype == CPE_PIX_U8 ? 1 : (dtype == CPE_PIX_U16 ? 2 : (dtype == CPE_PIX_F32 ? 4 : 8));
+    CPE_CHECK_ARG(((size_t)src) % esz == 0, "cpe_matlab_prestep_batch: source not aligned to its element type");
+    if (n == 0) return CPE_OK;
+    const float2 *m = reinterpret_cast<const float2 *>(map);
+    hipStream_t s = (hipStream_t)stream;
+    CPE_LAUNCH_BEGIN();
+    switch (dtype * 4 + channels) {
+    case CPE_PIX_U8 * 4 + 1: launch_prestep<uint8_t, 1>(src, n, h, w, m, fill, dst, dst_frame_stride, s); break;
+    case CPE_PIX_U8 * 4 + 3: launch_prestep<uint8_t, 3>(src, n, h, w, m, fill, dst, dst_frame_stride, s); break;
+    case CPE_PIX_U16 * 4 + 1: launch_prestep<uint16_t, 1>(src, n, h, w, m, fill, dst, dst_frame_stride, s); break;
+    case CPE_PIX_U16 * 4 + 3: launch_prestep<uint16_t, 3>(src, n, h, w, m, fill, dst, dst_frame_stride, s); break;
+    case CPE_PIX_F32 * 4 + 1: launch_prestep<float, 1>(src, n, h, w, m, fill, dst, dst_frame_stride, s); break;
+    case CPE_PIX_F32 * 4 + 3: launch_prestep<float, 3>(src, n, h, w, m, fill, dst, dst_frame_stride, s); break;
+    case CPE_PIX_F64 * 4 + 1: launch_prestep<double, 1>(src, n, h, w, m, fill, dst, dst_frame_stride, s); break;
+    default: launch_prestep<double, 3>(src, n, h, w, m, fill, dst, dst_frame_stride, s); break;
+    }
+    CPE_CHECK_LAUNCH("k_prestep");
     return CPE_OK;
 }

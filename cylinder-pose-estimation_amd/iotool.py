@@ -8,6 +8,10 @@
     Undistorter(..., interp='cubic') /         the MATLAB entry point's pre-step instead: undistortImage(I, cameraParams,
     undistort_image(..., interp='cubic')        'cubic') of utils/preProcessing.m:3-4 (distortPoints map, cubic convolution)
 
+    StereoPrestep(cam_l, cam_r, h, w, device)   utils/preProcessing.m:3-9 for chunks of raw stereo frames in one kernel per
+    preprocessing(img_l, img_r, cam_l, cam_r)   camera: im2uint8 (uint8 / uint16 / single / double) + cubic undistortion +
+                                                rgb2gray, written as the frame-major pairs FramePipeline reads in place
+
 The planar entry module (python_grid_detection_plane.py) and the cylinder one call the bilinear form for every image of a
 folder.  No CPU fallback: the HIP library does the work."""
 import ctypes as C
@@ -102,16 +106,79 @@ def undistort_image(image, camera_params, device='cuda:0', interp='linear'):
     return out[0] if img.ndim == 2 else np.ascontiguousarray(np.moveaxis(out, 0, 2))
 
 
+_PIX = {torch.uint8: 0, torch.int16: 1, torch.float32: 2, torch.float64: 3}     # CPE_PIX_* of include/cpe.h
+if hasattr(torch, 'uint16'):
+    _PIX[torch.uint16] = 1
+
+
+def _prestep(cubic_map, raw, dst, dst_frame_stride):
+    """one camera: raw frames [n,h,w] / [n,h,w,3] -> u8 grey frames at dst.data_ptr() + f * dst_frame_stride"""
+    h, w = cubic_map.shape[:2]
+    with torch.cuda.device(cubic_map.device):
+        _lib.check(_lib.load().cpe_matlab_prestep_batch(raw.data_ptr(), raw.shape[0], h, w, _PIX[raw.dtype], 3 if raw.dim() == 4 else 1,
+                                                        cubic_map.data_ptr(), 0, dst.data_ptr(), dst_frame_stride,
+                                                        torch.cuda.current_stream().cuda_stream), 'cpe_matlab_prestep_batch')
+
+
+class StereoPrestep:
+    """utils/preProcessing.m:3-9 for chunks of stereo frames, resident on the GPU: im2uint8 + undistortImage(..., 'cubic') +
+    rgb2gray of both cameras in one kernel per camera (cpe_matlab_prestep_batch), written as frame-major pairs [F,2,h,w]:
+    the layout FramePipeline reads in place.  The two MATLAB maps are built once.
+
+    Raw frames are device tensors [F,h,w] or [F,h,w,3] (RGB, channel-last) of dtype uint8, uint16, float32 or float64; an
+    int16 tensor is taken as the uint16 bit pattern.  The two cameras may differ in dtype and channels."""
+
+    def __init__(self, cam_left, cam_right, h, w, device='cuda:0'):
+        self.h, self.w = int(h), int(w)
+        self.maps = tuple(Undistorter(cam, h, w, device, interp='cubic').map for cam in (cam_left, cam_right))
+        self.device = self.maps[0].device           # with its index: 'cuda' names the device the maps were made on
+
+    def _check(self, raw, what):
+        if raw.device != self.device:
+            raise _lib.CpeError(f'StereoPrestep: {what} frames are on {raw.device}, the maps on {self.device}')
+        if not raw.is_contiguous() or raw.dtype not in _PIX or raw.dim() not in (3, 4) \
+                or tuple(raw.shape[1:3]) != (self.h, self.w) or (raw.dim() == 4 and raw.shape[3] != 3):
+            raise _lib.CpeError(f'StereoPrestep: {what} frames must be contiguous [F,{self.h},{self.w}] or [F,{self.h},{self.w},3] '
+                                f'of uint8, uint16 (or int16 bits), float32 or float64')
+
+    def __call__(self, left_raw, right_raw, out=None):
+        """-> u8 [F,2,h,w] (out[:, 0] left, out[:, 1] right): two launches on the current stream, no host synchronisation"""
+        self._check(left_raw, 'left'); self._check(right_raw, 'right')
+        F = left_raw.shape[0]
+        if right_raw.shape[0] != F:
+            raise _lib.CpeError('StereoPrestep: left and right differ in frame count')
+        if out is None:
+            out = torch.empty((F, 2, self.h, self.w), dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (F, 2, self.h, self.w) or not out.is_contiguous() or out.device != self.device:
+            raise _lib.CpeError(f'StereoPrestep: out must be contiguous u8 [{F},2,{self.h},{self.w}] on {self.device}')
+        N = self.h * self.w
+        _prestep(self.maps[0], left_raw, out[:, 0], 2 * N)
+        _prestep(self.maps[1], right_raw, out[:, 1], 2 * N)
+        return out
+
+
+def _raw_image(image, what):
+    img = np.array(image, copy=True, order='C')     # (PIL / MATLAB hand over read-only buffers)
+    if img.dtype.name not in ('uint8', 'uint16', 'float32', 'float64') or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] < 3):
+        raise _lib.CpeError(f'preprocessing: {what} image must be [h,w] or [h,w,3] of uint8, uint16, float32 or float64')
+    if img.ndim == 3 and img.shape[2] > 3:
+        img = np.ascontiguousarray(img[..., :3])    # (further planes, such as alpha, are not part of the grey value)
+    return torch.from_numpy(img.view(np.int16) if img.dtype == np.uint16 else img)[None]
+
+
 def preprocessing(input_img_l, input_img_r, camera_params_l, camera_params_r, device='cuda:0'):
     """utils/preProcessing.m: im2uint8 + undistortImage(..., 'cubic') + rgb2gray for both cameras -> (imgL_uint8, imgR_uint8).
     (Its third and fourth outputs, adapthisteq pictures, feed nothing on the detection path: exp_gridDetection.m:67-68 hands
-    the undistorted images to makePyGridPts.)  Colour input is converted AFTER the undistortion, as in the .m file."""
+    the undistorted images to makePyGridPts.)  Colour input is converted AFTER the undistortion, as in the .m file.
+    Images are numpy [h,w] or [h,w,3] (RGB) of uint8, uint16, float32 or float64, as imread hands them to im2uint8; the two
+    may differ in size.  Of an image with more than 3 planes the first three are taken as R, G, B.
+    Per camera: one upload, one kernel (StereoPrestep's), one download."""
     out = []
-    for img, cam in ((input_img_l, camera_params_l), (input_img_r, camera_params_r)):
-        u = undistort_image(img, cam, device, 'cubic')
-        if u.ndim == 3:   # rgb2gray: the first row of inv([1 .956 .621; 1 -.272 -.647; 1 -1.106 1.703]) on R, G, B, rounded (on the device)
-            t = torch.from_numpy(u).to(device).to(torch.float64)
-            g = t[..., 0] * 0.298936021293775 + t[..., 1] * 0.587043074451121 + t[..., 2] * 0.114020904255103
-            u = torch.floor(g + 0.5).clamp_(0, 255).to(torch.uint8).cpu().numpy()
-        out.append(u)
+    for what, img, cam in (('left', input_img_l, camera_params_l), ('right', input_img_r, camera_params_r)):
+        raw = _raw_image(img, what)
+        h, w = raw.shape[1:3]
+        und = Undistorter(cam, h, w, device, 'cubic')
+        dst = torch.empty((1, h, w), dtype=torch.uint8, device=und.device)
+        _prestep(und.map, raw.to(und.device), dst, h * w)
+        out.append(dst[0].cpu().numpy())
     return out[0], out[1]

@@ -45,6 +45,7 @@ class FramePipeline:
         # run beside the wide kernels of the next
         self.lanes = max(1, int(lanes))
         self._streams = None
+        self._stage = {}                # lane -> u8 [chunk,2,h,w]: where run_raw's pre-step writes the pairs of a chunk
 
     def _ws(self, n_img, lane=0):
         """one workspace per lane, made for the first (largest) chunk it sees; smaller chunks are laid out inside it"""
@@ -96,24 +97,59 @@ class FramePipeline:
 
     def run(self, left, right):
         """left/right: u8 [F,h,w] on the device -> records f64 [F,16]"""
-        F = left.shape[0]
-        recs = torch.empty((F, REC), dtype=torch.float64, device=left.device)
+        return self._for_chunks(left.shape[0], left.device, lambda i0, i1, lane: self.run_chunk(left[i0:i1], right[i0:i1], lane, i0)[0])
+
+    def _for_chunks(self, F, device, body):
+        """the walk over the chunks that run and run_raw share: records f64 [F,16] of body(i0, i1, lane); with lanes > 1
+        every chunk runs on its lane's stream"""
+        recs = torch.empty((F, REC), dtype=torch.float64, device=device)
         n_chunks = (F + self.chunk - 1) // self.chunk
-        if self.lanes == 1 or n_chunks == 1 or left.device.type != 'cuda':
+        if self.lanes == 1 or n_chunks == 1 or device.type != 'cuda':
             for i0 in range(0, F, self.chunk):
                 i1 = min(F, i0 + self.chunk)
-                recs[i0:i1] = self.run_chunk(left[i0:i1], right[i0:i1], 0, i0)[0]
+                recs[i0:i1] = body(i0, i1, 0)
             return recs
         if self._streams is None:
-            self._streams = [torch.cuda.Stream(device=left.device) for _ in range(self.lanes)]
-        main = torch.cuda.current_stream(left.device)
+            self._streams = [torch.cuda.Stream(device=device) for _ in range(self.lanes)]
+        main = torch.cuda.current_stream(device)
         for st in self._streams:
             st.wait_stream(main)                          # inputs and `recs` are ready on the caller's stream
         for k, i0 in enumerate(range(0, F, self.chunk)):
             i1 = min(F, i0 + self.chunk)
             lane = k % self.lanes
             with torch.cuda.stream(self._streams[lane]):
-                recs[i0:i1] = self.run_chunk(left[i0:i1], right[i0:i1], lane, i0)[0]
+                recs[i0:i1] = body(i0, i1, lane)
         for st in self._streams:
             main.wait_stream(st)
         return recs
+
+    def run_raw(self, left_raw, right_raw, prestep, fits=None):
+        """raw camera frames [F,h,w] / [F,h,w,3] on the device (uint8, uint16, float32, float64: iotool.StereoPrestep) ->
+        records f64 [F,16].  Per chunk the pre-step (preProcessing.m:3-9) writes the undistorted grey pairs into the lane's
+        staging tensor [chunk,2,h,w] and the detect call reads them there in place.
+        fits: None, or tensors from alloc_fits(F, device) that receive every frame's fitSingleCylinder outputs."""
+        if (prestep.h, prestep.w) != (self.h, self.w):
+            raise ValueError(f'run_raw: the pre-step is for {prestep.w}x{prestep.h} frames, the pipeline for {self.w}x{self.h}')
+        if fits is not None and self.stage != 'full':
+            raise ValueError("run_raw: fit outputs exist only with stage='full'")
+
+        def body(i0, i1, lane):
+            st = self._stage.get(lane)
+            if st is None:
+                st = self._stage[lane] = torch.empty((self.chunk, 2, self.h, self.w), dtype=torch.uint8, device=left_raw.device)
+            pairs = prestep(left_raw[i0:i1], right_raw[i0:i1], out=st[:i1 - i0])
+            rec, _, out = self.run_chunk(pairs[:, 0], pairs[:, 1], lane, i0)
+            if fits is not None:
+                for k, t in fits.items():
+                    t[i0:i1] = out[k]
+            return rec
+        return self._for_chunks(left_raw.shape[0], left_raw.device, body)
+
+
+FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), m=((), torch.int32), cyl_raw=((2, 6), torch.float64), cyl=((2, 6), torch.float64),
+                   T=((4, 4), torch.float64), fvals=((2,), torch.float64), mean_err=((), torch.float64), status=((), torch.int32))
+
+
+def alloc_fits(F, device):
+    """zeroed [F, ...] tensors for the per-frame outputs of fit.fit_single_cylinder_batch that FramePipeline.run_raw can keep"""
+    return {k: torch.zeros((F,) + shape, dtype=dt, device=device) for k, (shape, dt) in FIT_OUTPUTS.items()}

@@ -469,6 +469,25 @@ CPE_API int32_t cpe_undistort_map_matlab(const double *K, const double *radial, 
 CPE_API int32_t cpe_remap_cubic_batch(const uint8_t *src, int32_t n, int32_t h, int32_t w, const float *map, int32_t fill,
                                       uint8_t *dst, void *stream);
 
+/* Row f-3, the whole of utils/preProcessing.m:3-9 for a batch of frames of ONE camera, in one pass:
+ *   im2uint8 -> undistortImage(..., 'cubic') per channel -> rgb2gray (channels == 3) -> u8 grey
+ * src: [n,h,w] (channels 1) or [n,h,w,3] RGB channel-last (channels 3), contiguous, element type `dtype` (what MATLAB's
+ *   imread / a camera driver hands over: uint8, uint16 of a 16-bit PNG, single, double).
+ * map: f32[h,w,2] from cpe_undistort_map_matlab; dst frame f starts at dst + f * dst_frame_stride (bytes, >= h*w), so the
+ *   left camera of a stereo chunk goes to dst and the right one to dst + h*w, both with stride 2*h*w (frame-major pairs).
+ * The result is byte for byte what the separate steps give:
+ *   im2uint8  [ext, parity unpinned vs MATLAB]  uint8: identity; uint16: round(x / 257) = (x + 128) / 257 in integers;
+ *             single / double: x * 255 in the input's precision, NaN -> 0, saturated to [0, 255], rounded half away from zero
+ *   cubic     cpe_remap_cubic_batch on every channel (each rounded to u8), `fill` outside
+ *   rgb2gray  floor(R * 0.298936021293775 + G * 0.587043074451121 + B * 0.114020904255103 + 0.5) in f64, left to right
+ * h, w >= 3; src != dst; n == 0 is a no-op. */
+#define CPE_PIX_U8 0
+#define CPE_PIX_U16 1
+#define CPE_PIX_F32 2
+#define CPE_PIX_F64 3
+CPE_API int32_t cpe_matlab_prestep_batch(const void *src, int32_t n, int32_t h, int32_t w, int32_t dtype, int32_t channels,
+                                         const float *map, int32_t fill, uint8_t *dst, int64_t dst_frame_stride, void *stream);
+
 /* Row f-1: the per-frame terms of the multi-frame objective of fitCylinderWPts3sAngs.m:82-94 (`dist`):
  * terms[i] = mean((getDistPts3ToLine(Pts3s{i}, line(T * TAGVcyls{i})) - radius)^2), one wavefront per frame.
  * X f64[n,CPE_MAXP,3], cnt i32[n], TAGVcyl f64[n,16] (row-major getTAGVcyl(pan,tilt)), T f64[16] (device, row-major
