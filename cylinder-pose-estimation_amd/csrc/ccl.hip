@@ -1034,6 +1034,8 @@ static bool links8(const uint8_t *img, int n, int h, int w, int thr, Window win,
     return false;
 }
 
+bool ccl_components_reads_bits(const uint32_t *bits, int w, const int *L) { return bits && w % 16 == 0 && ((size_t)L & 15) == 0; }
+
 int ccl_components(const uint8_t *img, const uint32_t *bits, int n, int h, int w, int thr, Window win, int *L, int *roots,
                    RootList list, FrameState *st, hipStream_t s)
 {
@@ -1041,7 +1043,7 @@ int ccl_components(const uint8_t *img, const uint32_t *bits, int n, int h, int w
     const dim3 gw = word_grid(n, h, w);
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, (int *)nullptr, n, CTL_RESET_ROOTS, list);
-    if (bits && w % 16 == 0 && ((size_t)L & 15) == 0) {
+    if (ccl_components_reads_bits(bits, w, L)) {
         const BitSrc src{bit_plane(bits, 0, h, w), bit_tile_cols(w), bit_plane_words(h, w)};
         CPE_KLAUNCH(k_ccl_init64<BitSrc>, gw, dim3(256), 0, s, src, h, w, (const FrameState *)st, win, L);
         CPE_KLAUNCH(k_ccl_merge64<BitSrc>, gw, dim3(256), 0, s, src, h, w, 1, (const FrameState *)st, win, L);

@@ -104,7 +104,7 @@ inline unsigned frame_waves(int lists, int lo, int hi)
 struct RegionSide { hipStream_t s; hipEvent_t clahe_done, dark_done, traced, medians;
                     hipEvent_t joints_done = nullptr, spot_done = nullptr; };   // ends of the joints / spot chains (their label planes hold the tracers' tables afterwards)
 struct MaskBuffers {
-    uint8_t *binary, *hmask, *vmask, *joints_mask, *tmpA, *tmpB, *g19, *cm, *mc, *roi_h, *roi_v, *base_h, *base_v, *exp_h,
+    uint8_t *binary, *hmask, *vmask, *joints_mask, *g19, *cm, *mc, *roi_h, *roi_v, *base_h, *base_v, *exp_h,
         *exp_v, *touch;
     int *lab, *roots, *jtmp, *joints, *verts;
     int *lab_p, *roots_p, *lab_s, *roots_s;
@@ -415,6 +415,9 @@ int build_bitplanes(const uint8_t *img, int n, int h, int w, int thr0, int step,
 // left as union-find links (a root is a pixel whose label is its own index); labels outside the set are not written.
 int ccl_components(const uint8_t *img, const uint32_t *bits, int n, int h, int w, int thr, Window win, int *L, int *roots,
                    RootList list, FrameState *st, hipStream_t s);
+// true: a ccl_components call with these arguments reads the set from `bits` alone and never touches img (a caller that has
+// the plane need not produce the bytes)
+bool ccl_components_reads_bits(const uint32_t *bits, int w, const int *L);
 // Unions only: the links of a component list of mask != 0 (thr 0), for a consumer that resolves the few labels it needs with
 // uf_find (k_lines).
 int ccl_unions(const uint8_t *mask, int n, int h, int w, Window win, int *L, FrameState *st, hipStream_t s);

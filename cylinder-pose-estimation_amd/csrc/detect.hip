@@ -108,7 +108,7 @@ MaskBuffers mask_buffers(const Workspace &W, const RegionBuffers &R)
 {
     MaskBuffers M;
     M.binary = W.at<uint8_t>(WS_BINARY); M.hmask = W.at<uint8_t>(WS_HMASK); M.vmask = W.at<uint8_t>(WS_VMASK);
-    M.joints_mask = W.at<uint8_t>(WS_JOINTS_MASK); M.tmpA = W.at<uint8_t>(WS_TMPA); M.tmpB = W.at<uint8_t>(WS_TMPB);
+    M.joints_mask = W.at<uint8_t>(WS_JOINTS_MASK);
     M.g19 = W.at<uint8_t>(WS_BLUR19); M.cm = W.at<uint8_t>(WS_CM); M.mc = R.mc; M.roi_h = W.at<uint8_t>(WS_ROI_H);
     M.roi_v = W.at<uint8_t>(WS_ROI_V); M.base_h = W.at<uint8_t>(WS_BASE_H); M.base_v = W.at<uint8_t>(WS_BASE_V);
     M.exp_h = W.at<uint8_t>(WS_EXP_H); M.exp_v = W.at<uint8_t>(WS_EXP_V); M.touch = R.touch; M.bits = R.bits;

@@ -193,73 +193,33 @@ __global__ __launch_bounds__(256) void k_open20_joints(const uint8_t *__restrict
     }
 }
 
-// dst = ((a | b) != 0 ? 255 : 0) & c with c = mask_contour, which is zero outside the region rectangle: rows outside it are
-// written as zeros without reading anything.  grid = (ceil(N / 16384), n), 16 bytes per thread and step when rows allow.
-__global__ __launch_bounds__(256) void k_or_and(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b,
-                                                const uint8_t *__restrict__ c, int h, int w, const FrameState *__restrict__ st,
-                                                uint8_t *__restrict__ dst)
-{
-    const int N = h * w;
-    const size_t f = blockIdx.y;
-    const int *r = st[f].rect;
-    const bool none = st[f].status == CPE_ST_NO_REGION;
-    const int y0 = r[1], y1 = r[1] + r[3] - 1;
-    const size_t o = f * (size_t)N;
-    const bool vec = ((((size_t)a | (size_t)b | (size_t)c | (size_t)dst) & 15) == 0) && (N % 16 == 0);
-    for (int it = 0; it < 4; it++) {
-        const int i0 = blockIdx.x * 16384 + it * 4096 + threadIdx.x * 16;
-        if (i0 >= N) break;
-        const int ya = i0 / w, yb = min(i0 + 15, N - 1) / w;
-        const bool outside = none || yb < y0 || ya > y1;
-        if (vec) {
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (!outside) {
-                const uint4 va = *reinterpret_cast<const uint4 *>(a + o + i0), vb = *reinterpret_cast<const uint4 *>(b + o + i0);
-                const uint4 vc = *reinterpret_cast<const uint4 *>(c + o + i0);
-                auto f4 = [](uint32_t x, uint32_t y, uint32_t z) {
-                    uint32_t r4 = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const uint32_t on = (((x | y) >> (8 * k)) & 255u) ? 255u : 0u;
-                        r4 |= (on & ((z >> (8 * k)) & 255u)) << (8 * k);
-                    }
-                    return r4;
-                };
-                v = make_uint4(f4(va.x, vb.x, vc.x), f4(va.y, vb.y, vc.y), f4(va.z, vb.z, vc.z), f4(va.w, vb.w, vc.w));
-            }
-            *reinterpret_cast<uint4 *>(dst + o + i0) = v;
-        } else {
-            for (int k = 0; k < 16 && i0 + k < N; k++) {
-                const size_t gi = o + i0 + k;
-                dst[gi] = outside ? 0 : (uint8_t)(((a[gi] ? 255 : 0) | (b[gi] ? 255 : 0)) & c[gi]);
-            }
-        }
-    }
-}
-
 // a-5 tail + a-6 head in one kernel:  roi = open3x3(mask & circle_mask & mask_contour)  (util_cylinder.py:1995-2005),
 // base = close3x3(roi) (:150-152); out-of-image pixels never erode / dilate.  Bit rows like k_open20_joints: a workgroup
 // holds a band of RB_R + 8 rows (all columns) as 64-pixel words in LDS and runs the four 3x3 passes on words (3 taps
 // along the row by shifts, 3 rows by AND / OR).  mask_contour is zero outside the region rectangle, so only its pixels
 // are read: everything else packs as zero, and bands further than 4 rows from it are written as zeros straight away.
+// The kernel also seeds the expanded mask: exp = base & mask_contour (the closing is extensive, base may stick out of
+// mask_contour), full frame, zeros included -- k_seg_expand only adds 255s to it, and nothing else clears the plane.
 constexpr int RB_R = 64, RB_AP = 4, RB_ROWS = RB_R + 2 * RB_AP;
 __global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m, const uint8_t *__restrict__ cm,
                                                   const uint8_t *__restrict__ mc, int h, int w, int bands,
                                                   const FrameState *__restrict__ st, uint8_t *__restrict__ roi,
-                                                  uint8_t *__restrict__ base, uint32_t *__restrict__ bbits)
+                                                  uint8_t *__restrict__ base, uint8_t *__restrict__ exp,
+                                                  uint32_t *__restrict__ bbits)
 {
-    // bbits: `base` once more as a one-bit plane (cpe_dev.h tiled layout, one plane per frame): the words are in LDS anyway,
-    // and the fragments' labelling, flood and border tracer read the plane
+    // bbits: `base` as a one-bit plane (cpe_dev.h tiled layout, one plane per frame): the fragments' flood, border tracer
+    // and expansion read the plane, and so does their labelling where rows allow the word-level kernels.
+    // base (may be null): the same as bytes, for the byte-level labelling kernels only (masks_stage asks ccl.hip)
     extern __shared__ unsigned long long s_rb[];
     const int WW = (w + 63) >> 6;
-    unsigned long long *buf0 = s_rb, *buf1 = s_rb + (size_t)RB_ROWS * WW;
+    unsigned long long *buf0 = s_rb, *buf1 = s_rb + (size_t)RB_ROWS * WW, *mcb = s_rb + (size_t)2 * RB_ROWS * WW;
     const int t = threadIdx.x;
     const int f = blockIdx.x / bands, band = blockIdx.x - f * bands;
     const int y0 = band * RB_R;
     const size_t N = (size_t)h * w;
     const int *rc = st[f].rect;
     const int rx0 = rc[0], ry0 = rc[1], rx1 = rc[0] + rc[2] - 1, ry1 = rc[1] + rc[3] - 1;
-    const bool al8 = ((w & 7) == 0) && ((((size_t)m | (size_t)cm | (size_t)mc | (size_t)roi | (size_t)base) & 7) == 0);
+    const bool al8 = ((w & 7) == 0) && ((((size_t)m | (size_t)cm | (size_t)mc | (size_t)roi | (size_t)base | (size_t)exp) & 7) == 0);
     const int per_row = WW * 8;
     auto store8 = [&](uint8_t *dst, size_t o, int x0, unsigned bits) {
         if (al8) *reinterpret_cast<unsigned long long *>(dst + o) = bytes_of_bits8(bits);
@@ -271,31 +231,40 @@ __global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m,
             const int y = y0 + tr, x0 = k * 8;
             if (y >= h || x0 >= w) continue;
             const size_t o = f * N + (size_t)y * w + x0;
-            store8(roi, o, x0, 0u); store8(base, o, x0, 0u);
+            store8(roi, o, x0, 0u); store8(exp, o, x0, 0u);
+            if (base) store8(base, o, x0, 0u);
         }
         store_plane_band(bit_plane(bbits, f, h, w), h, w, y0, RB_R, t, [](int, int) { return 0ull; });
         return;
     }
-    // pack (m & cm & mc) != 0 of the rectangle's pixels; everything else (and outside the image) is zero
+    // pack (m & cm & mc) != 0 of the rectangle's pixels, and mc != 0 on its own for the seed of exp; everything else (and
+    // outside the image) is zero
     {
-        uint8_t *pk = reinterpret_cast<uint8_t *>(buf0);
+        uint8_t *pk = reinterpret_cast<uint8_t *>(buf0), *pkc = reinterpret_cast<uint8_t *>(mcb);
+        auto nonzero8 = [](unsigned long long v) {
+            v = (((v & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | v) & 0x8080808080808080ull;
+            return (unsigned)(((v >> 7) * 0x0102040810204080ull) >> 56);
+        };
         for (int i = t; i < RB_ROWS * per_row; i += 256) {
             const int r = i / per_row, k = i - r * per_row;
             const int y = y0 - RB_AP + r, x0 = k * 8;
-            unsigned bits = 0u;
+            unsigned bits = 0u, cbits = 0u;
             if (y >= ry0 && y <= ry1 && y >= 0 && y < h && x0 < w && x0 + 7 >= rx0 && x0 <= rx1) {
                 const size_t o = f * N + (size_t)y * w + x0;
                 if (al8) {
-                    unsigned long long v = *reinterpret_cast<const unsigned long long *>(m + o) &
-                                           *reinterpret_cast<const unsigned long long *>(cm + o) &
-                                           *reinterpret_cast<const unsigned long long *>(mc + o);
-                    v = (((v & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | v) & 0x8080808080808080ull;
-                    bits = (unsigned)(((v >> 7) * 0x0102040810204080ull) >> 56);
+                    const unsigned long long vc = *reinterpret_cast<const unsigned long long *>(mc + o);
+                    bits = nonzero8(*reinterpret_cast<const unsigned long long *>(m + o) &
+                                    *reinterpret_cast<const unsigned long long *>(cm + o) & vc);
+                    cbits = nonzero8(vc);
                 } else {
-                    for (int b = 0; b < 8 && x0 + b < w; b++) bits |= ((m[o + b] & cm[o + b]) & mc[o + b]) ? (1u << b) : 0u;
+                    for (int b = 0; b < 8 && x0 + b < w; b++) {
+                        bits |= ((m[o + b] & cm[o + b]) & mc[o + b]) ? (1u << b) : 0u;
+                        cbits |= mc[o + b] ? (1u << b) : 0u;
+                    }
                 }
             }
             pk[i] = (uint8_t)bits;
+            pkc[i] = (uint8_t)cbits;
         }
     }
     __syncthreads();
@@ -324,21 +293,24 @@ __global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m,
         }
         __syncthreads();
     };
-    auto emit = [&](const unsigned long long *src, uint8_t *dst) {
+    auto emit = [&](const unsigned long long *src, uint8_t *dst, uint8_t *dst2, const unsigned long long *and2) {   // dst2 = src & and2
         for (int i = t; i < RB_R * per_row; i += 256) {
             const int tr = i / per_row, k = i - tr * per_row;
             const int y = y0 + tr, x0 = k * 8;
             if (y >= h || x0 >= w) continue;
-            const unsigned bits = (unsigned)(src[(size_t)(tr + RB_AP) * WW + (k >> 3)] >> ((k & 7) * 8)) & 255u;
-            store8(dst, f * N + (size_t)y * w + x0, x0, bits);
+            const size_t wi = (size_t)(tr + RB_AP) * WW + (k >> 3);
+            const unsigned bits = (unsigned)(src[wi] >> ((k & 7) * 8)) & 255u;
+            const size_t o = f * N + (size_t)y * w + x0;
+            if (dst) store8(dst, o, x0, bits);
+            if (dst2) store8(dst2, o, x0, bits & (unsigned)(and2[wi] >> ((k & 7) * 8)));
         }
     };
     pass(buf0, buf1, false);   // erode
     pass(buf1, buf0, true);    // dilate -> roi
-    emit(buf0, roi);
+    emit(buf0, roi, nullptr, nullptr);
     pass(buf0, buf1, true);    // dilate
     pass(buf1, buf0, false);   // erode -> base
-    emit(buf0, base);
+    emit(buf0, base, exp, mcb);
     // (columns past the row's end are 0: row_valid_word)
     store_plane_band(bit_plane(bbits, f, h, w), h, w, y0, RB_R, t, [&](int tr, int j) { return buf0[(size_t)(tr + RB_AP) * WW + j]; });
 }
@@ -1111,43 +1083,53 @@ __global__ __launch_bounds__(256) void k_seg_global(FrameState *__restrict__ st,
     }
 }
 
-// one workgroup per fragment end point: 15x15 patch of the mask dilated by the rotated line kernel
-// (reflected, as cv2.dilate does), eroded 3x3, OR-ed into exp.  Works on the (15 + ks)^2 support in LDS.
+// one workgroup per fragment: the 15x15 patch of the mask around each end point (read from base's one-bit plane) dilated by
+// the rotated line kernel (reflected, as cv2.dilate does), eroded 3x3.  exp holds base & mask_contour already (k_roi_base);
+// every pixel the erosion keeps is stored as 255 & mask_contour where that is not zero -- ((expansion | base) ? 255 : 0) &
+// mask_contour without a plane in between.  Workgroups whose supports overlap store the same value to the same byte: no
+// read-modify-write.
+// The line kernel is built once per fragment: warpAffine's X0 / Y0 per row and adelta / bdelta per column go into tables
+// (4 ks f64 evaluations), the ks^2 membership test is integer only.  The support of an end point -- (15 + ks + 2)^2 with a
+// 1-px margin for the erosion -- lives in LDS as rows of EXP_WW 64-pixel words, bit 0 = column bx1: the dilation ORs a patch
+// row's 15 bits, shifted, into one or two words per kernel offset, the erosion is shifts and ANDs of three rows.
 constexpr int EXP_MAXKS = 176;       // cylinder script: kernel 91 + r0
 constexpr int EXP_MAXKS_PLANE = 208;  // planar script: fixed 201
+constexpr int EXP_NT = 256, EXP_WW = 4, EXP_MAXOFF = 4096;
 template <int MAXKS>
-__global__ __launch_bounds__(256) void k_seg_expand(const uint8_t *__restrict__ base, int h, int w, int which,
-                                                    FrameState *__restrict__ st, const SegRec *__restrict__ segs,
-                                                    uint8_t *__restrict__ exp, int fixed_ks)
+__global__ __launch_bounds__(EXP_NT) void k_seg_expand(const uint32_t *__restrict__ base_bits, const uint8_t *__restrict__ mc, int h, int w,
+                                                       int which, FrameState *__restrict__ st, const SegRec *__restrict__ segs,
+                                                       uint8_t *__restrict__ exp, int fixed_ks)
 {
     constexpr int EXP_REG = 15 + MAXKS + 2;
-    __shared__ uint8_t dil[EXP_REG * EXP_REG];
-    __shared__ short koff[4096][2];
-    __shared__ short ppix[225][2];
-    __shared__ int s_nk, s_np;
+    static_assert(EXP_REG <= 64 * EXP_WW, "a support row must fit EXP_WW words");
+    __shared__ unsigned long long dil[EXP_REG * EXP_WW];
+    __shared__ short koff[EXP_MAXOFF][2];
+    __shared__ int tX0[MAXKS], tY0[MAXKS], tA[MAXKS], tB[MAXKS];
+    __shared__ unsigned long long vc[EXP_WW];     // the support's columns that lie inside the image
+    __shared__ unsigned prow[15];                 // the patch, one 15-bit row each (bit 0 = column x1)
+    __shared__ int s_nk;
     const int f = blockIdx.y, t = threadIdx.x;
     FrameState &S = st[f];
     if (S.status != CPE_ST_OK) return;
-    const int njobs = 2 * min(S.n_seg[which], MAXSEG);
-    for (int job = blockIdx.x; job < njobs; job += gridDim.x) {   // (fragment, end point) pairs in turns
-    const int seg = job >> 1, e = job & 1;
+    const int nseg = min(S.n_seg[which], MAXSEG);
+    const size_t N = (size_t)h * w;
+    const unsigned long long *bp = bit_plane(base_bits, f, h, w);
+    const int btc = bit_tile_cols(w);
+    const uint8_t *mcf = mc + f * N;
+    uint8_t *ex = exp + f * N;
+    for (int seg = blockIdx.x; seg < nseg; seg += gridDim.x) {   // fragments in turns
     const SegRec r = segs[(size_t)f * MAXSEG + seg];
     const float glen = S.glen[which], gang = S.gang[which];
     if ((double)r.len > 0.8 * (double)glen) continue;
     const int ks = fixed_ks > 0 ? fixed_ks : 91 + S.r0;
     if (ks > MAXKS) { if (t == 0) set_overflow(S, OVF_KERNEL); return; }
-    __syncthreads();   // the previous job's readers of dil / koff / ppix are done
+    __syncthreads();   // the previous fragment's readers of the tables, koff and dil are done
     const float ak = fabsf(r.angle - gang) > 5.0f ? gang : r.angle;
     const int a = ks / 2, half = 7;
-    const size_t N = (size_t)h * w;
-    const uint8_t *bm = base + f * N;
-    const int cx = (int)rint((double)(e ? r.p2x : r.p1x)), cy = (int)rint((double)(e ? r.p2y : r.p1y));
-    const int x1 = max(cx - half, 0), x2 = min(cx + half + 1, w), y1 = max(cy - half, 0), y2 = min(cy + half + 1, h);
-    if (t == 0) { s_nk = 0; s_np = 0; }
-    __syncthreads();
+    if (t == 0) s_nk = 0;
     // rotated line kernel: getRotationMatrix2D + warpAffine(INTER_NEAREST) of the centre row
+    const int c = ks / 2;
     {
-        const int c = ks / 2;
         double ar = (double)ak * 3.1415926535897932384626433832795 / 180.0;
         double alpha = cos(ar), beta = sin(ar);
         double M[6] = {alpha, beta, (1 - alpha) * c - beta * c, -beta, alpha, beta * c + (1 - alpha) * c};
@@ -1159,53 +1141,96 @@ __global__ __launch_bounds__(256) void k_seg_expand(const uint8_t *__restrict__ 
         double b1 = -iM[0] * M[2] - iM[1] * M[5];
         double b2 = -iM[3] * M[2] - iM[4] * M[5];
         iM[2] = b1; iM[5] = b2;
-        for (int i = t; i < ks * ks; i += 256) {
-            int y = i / ks, x = i - y * ks;
-            int X0 = (int)rint((iM[1] * y + iM[2]) * 1024) + 512;
-            int Y0 = (int)rint((iM[4] * y + iM[5]) * 1024) + 512;
-            int adelta = (int)rint(iM[0] * x * 1024), bdelta = (int)rint(iM[3] * x * 1024);
-            int X = (X0 + adelta) >> 10, Y = (Y0 + bdelta) >> 10;
+        for (int i = t; i < ks; i += EXP_NT) {      // i: a row y for X0 / Y0, a column x for adelta / bdelta
+            tX0[i] = (int)rint((iM[1] * i + iM[2]) * 1024) + 512;
+            tY0[i] = (int)rint((iM[4] * i + iM[5]) * 1024) + 512;
+            tA[i] = (int)rint(iM[0] * i * 1024);
+            tB[i] = (int)rint(iM[3] * i * 1024);
+        }
+    }
+    __syncthreads();
+    for (int y = t >> 6; y < ks; y += EXP_NT / 64) {
+        const int X0 = tX0[y], Y0 = tY0[y];
+        for (int x = t & 63; x < ks; x += 64) {
+            const int X = (X0 + tA[x]) >> 10, Y = (Y0 + tB[x]) >> 10;
             if (X >= 0 && X < ks && Y == c) {
                 int q = atomicAdd(&s_nk, 1);
-                if (q < 4096) { koff[q][0] = (short)(x - a); koff[q][1] = (short)(y - a); }
+                if (q < EXP_MAXOFF) { koff[q][0] = (short)(x - a); koff[q][1] = (short)(y - a); }
             }
         }
     }
-    for (int i = t; i < 225; i += 256) {
-        int py = y1 + i / 15, px = x1 + i % 15;
-        if (py < y2 && px < x2 && bm[(size_t)py * w + px]) {
-            int q = atomicAdd(&s_np, 1);
-            ppix[q][0] = (short)px; ppix[q][1] = (short)py;
-        }
-    }
-    // support box (global coords) with a 1-px margin for the erosion
+    __syncthreads();
+    const int nk = min(s_nk, EXP_MAXOFF);
+    if (s_nk > EXP_MAXOFF && t == 0) set_overflow(S, OVF_EXPAND);
+    for (int e = 0; e < 2; e++) {   // the fragment's two end points
+    const int cx = (int)rint((double)(e ? r.p2x : r.p1x)), cy = (int)rint((double)(e ? r.p2y : r.p1y));
+    const int x1 = max(cx - half, 0), x2 = min(cx + half + 1, w), y1 = max(cy - half, 0), y2 = min(cy + half + 1, h);
+    if (x2 <= x1 || y2 <= y1) continue;      // no patch
+    // support box (global coords) with a 1-px margin for the erosion: the dilation sets local columns 1 .. bw - 2 and rows
+    // 1 .. bh - 2 only, so a margin pixel never survives the erosion and nothing outside the box is ever asked for
     const int bx1 = x1 - a - 1, by1 = y1 - a - 1;
-    const int bw = (x2 - x1) + 2 * a + 2, bh = (y2 - y1) + 2 * a + 2;
-    for (int i = t; i < bw * bh; i += 256) dil[i] = 0;
-    __syncthreads();
-    const int nk = min(s_nk, 4096), np = s_np;
-    if (s_nk > 4096 && t == 0) set_overflow(S, OVF_EXPAND);
-    for (int i = t; i < nk * np; i += 256) {
-        int p = i / nk, k = i - p * nk;
-        int xx = ppix[p][0] - koff[k][0], yy = ppix[p][1] - koff[k][1];
-        if (xx >= 0 && xx < w && yy >= 0 && yy < h) dil[(yy - by1) * bw + (xx - bx1)] = 1;
+    const int bh = (y2 - y1) + 2 * a + 2;
+    if (e) __syncthreads();   // the first end point's readers of dil / prow / vc are done
+    for (int i = t; i < bh * EXP_WW; i += EXP_NT) dil[i] = 0ull;
+    if (t < 15) {
+        const int y = y1 + t;
+        unsigned m = 0u;
+        if (y < y2) {
+            const int j = x1 >> 6, sh = x1 & 63;
+            unsigned long long v = bp[bit_word(btc, y, j)] >> sh;
+            if (sh) v |= bp[bit_word(btc, y, j + 1)] << (64 - sh);      // j + 1 may be the plane's zero column
+            m = (unsigned)v & ((1u << (x2 - x1)) - 1u);
+        }
+        prow[t] = m;
+    } else if (t >= 16 && t < 16 + EXP_WW) {
+        const int wd = t - 16;
+        const int lo = min(max(-bx1 - 64 * wd, 0), 64), hi = min(max(w - bx1 - 64 * wd, 0), 64);   // bits [lo, hi) of the word
+        unsigned long long v = 0ull;
+        if (hi > lo) v = (hi == 64 ? ~0ull : ((1ull << hi) - 1ull)) & ~((1ull << lo) - 1ull);
+        vc[wd] = v;
     }
     __syncthreads();
-    uint8_t *ex = exp + f * N;
-    for (int i = t; i < bw * bh; i += 256) {
-        int ly = i / bw, lx = i - ly * bw;
-        int gy = by1 + ly, gx = bx1 + lx;
-        if (gx < 0 || gx >= w || gy < 0 || gy >= h) continue;
-        bool all = true;
-        for (int dy = -1; dy <= 1 && all; dy++)
-            for (int dx = -1; dx <= 1; dx++) {
-                int yy = gy + dy, xx = gx + dx;
-                if (yy < 0 || yy >= h || xx < 0 || xx >= w) continue;
-                int ly2 = ly + dy, lx2 = lx + dx;
-                bool v = (ly2 >= 0 && ly2 < bh && lx2 >= 0 && lx2 < bw) ? dil[ly2 * bw + lx2] != 0 : false;
-                if (!v) { all = false; break; }
-            }
-        if (all) ex[(size_t)gy * w + gx] = 255;
+    // dilation: pixel p - k for every patch pixel p and kernel offset k, inside the image
+    for (int i = t; i < nk * 15; i += EXP_NT) {
+        const int k = i / 15, pr = i - k * 15;
+        const unsigned long long m = prow[pr];
+        const int yy = y1 + pr - koff[k][1];
+        if (!m || yy < 0 || yy >= h) continue;
+        const int sh = a + 1 - koff[k][0];            // local column of the patch's first one: 1 .. 2 a + 1
+        const int wd = sh >> 6, b = sh & 63;
+        unsigned long long *row = dil + (yy - by1) * EXP_WW;
+        const unsigned long long lo = (m << b) & vc[wd];
+        if (lo) atomicOr(&row[wd], lo);
+        if (b > 49) {
+            const unsigned long long hi = (m >> (64 - b)) & vc[wd + 1];
+            if (hi) atomicOr(&row[wd + 1], hi);
+        }
+    }
+    __syncthreads();
+    // 3x3 erosion on words, 16 pixels per step: a neighbour outside the image is the neutral element (cv2.erode)
+    for (int i = t; i < (bh - 2) * EXP_WW * 4; i += EXP_NT) {
+        const int ly = 1 + (i >> 4), wd = (i >> 2) & 3, off = (i & 3) * 16;
+        const int gy = by1 + ly;
+        if (gy < 0 || gy >= h || !((dil[ly * EXP_WW + wd] >> off) & 0xffffull)) continue;
+        unsigned long long acc = vc[wd];
+#pragma unroll
+        for (int dr = -1; dr <= 1; dr++) {
+            if (gy + dr < 0 || gy + dr >= h) continue;
+            const unsigned long long *row = dil + (ly + dr) * EXP_WW;
+            const unsigned long long xb = row[wd] | ~vc[wd];
+            const unsigned long long xa = wd > 0 ? (row[wd - 1] | ~vc[wd - 1]) : 0ull;             // local column -1: only beside the margin
+            const unsigned long long xc = wd + 1 < EXP_WW ? (row[wd + 1] | ~vc[wd + 1]) : 0ull;   // column 256: never reached
+            acc &= xb & ((xb >> 1) | (xc << 63)) & ((xb << 1) | (xa >> 63));
+        }
+        unsigned bits = (unsigned)(acc >> off) & 0xffffu;
+        const size_t o = (size_t)gy * w + (bx1 + wd * 64 + off);
+        while (bits) {
+            const int b = __ffs(bits) - 1;
+            bits &= bits - 1u;
+            const uint8_t cv = mcf[o + b];
+            if (cv) ex[o + b] = 255 & cv;
+        }
+    }
     }
     }
 }
@@ -1373,7 +1398,6 @@ int spot_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, F
 int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s,
                 const RegionSide *side, int planar, hipStream_t sj)
 {
-    const size_t total = (size_t)h * w * n;
     int rc;
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_masks_reset, dim3((n + 63) / 64), dim3(64), 0, s, st, n);
@@ -1394,7 +1418,7 @@ int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, 
     // a-5 tail, a-6 and the labelling of the expanded masks, once per line direction.  The two directions share
     // nothing but their inputs: the vertical one runs on the helper stream (if any) with the spot chain's label plane.
     const int rb_bands = (h + RB_R - 1) / RB_R;
-    const size_t rb_lds = (size_t)2 * RB_ROWS * ((w + 63) / 64) * 8;
+    const size_t rb_lds = (size_t)3 * RB_ROWS * ((w + 63) / 64) * 8;
     CPE_CHECK_ARG(rb_lds <= 160 * 1024, "masks_stage: frame too wide (%d columns)", w);
     CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_roi_base), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (side) { (void)hipEventRecord(side->clahe_done, s); (void)hipStreamWaitEvent(side->s, side->clahe_done, 0); }
@@ -1402,27 +1426,25 @@ int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, 
         hipStream_t q = (which && side) ? side->s : s;
         const uint8_t *lm = which ? B.vmask : B.hmask;
         uint8_t *roi = which ? B.roi_v : B.roi_h;
-        uint8_t *base = which ? B.base_v : B.base_h;
         uint8_t *exp = which ? B.exp_v : B.exp_h;
-        uint8_t *tmp = which ? B.tmpA : B.tmpB;
         int *lab = which ? B.lab_s : B.lab, *roots = which ? B.roots_s : B.roots;
         const RootList list = which ? ROOTS_SPOT : ROOTS_MAIN;
         uint32_t *bits = reinterpret_cast<uint32_t *>(bit_plane(B.bits, which ? (size_t)n : 0, h, w));
         SegRec *segs = B.segs + (size_t)which * n * MAXSEG;
-        // roi = open3x3(mask & circle_mask & mask_contour), base = close3x3(roi)
+        // roi = open3x3(mask & circle_mask & mask_contour), base = close3x3(roi) as a one-bit plane, exp = base & mask_contour.
+        // base's bytes are only written where the labelling will read them (the byte-level kernels)
+        uint8_t *base = ccl_components_reads_bits(bits, w, lab) ? nullptr : (which ? B.base_v : B.base_h);
         CPE_KLAUNCH(k_roi_base, dim3((unsigned)(n * rb_bands)), dim3(256), rb_lds, q, lm, (const uint8_t *)B.cm, (const uint8_t *)B.mc,
-                    h, w, rb_bands, (const FrameState *)st, roi, base, bits);   // + base's one-bit plane
+                    h, w, rb_bands, (const FrameState *)st, roi, base, exp, bits);
         if ((rc = ccl_components(base, bits, n, h, w, 0, WIN_REGION, lab, roots, list, st, q)) != CPE_OK) return rc;
         unsigned long long *fl_bg = fl_plane(2 + 2 * which), *fl_out = fl_plane(3 + 2 * which);
         if ((rc = outside_flood(base, n, h, w, st, WIN_REGION, fl_bg, fl_out, fl_words, q, bits)) != CPE_OK) return rc;
         if (planar) CPE_KLAUNCH((k_seg_trace<8, 700>), dim3(frame_waves(n, 32, 512), n), dim3(64), 0, q, (const uint32_t *)bits, h, w, which, (const int *)roots, list, st, segs, (const unsigned long long *)fl_out, fl_words);
         else CPE_KLAUNCH((k_seg_trace<5, 200>), dim3(frame_waves(n, 32, 512), n), dim3(64), 0, q, (const uint32_t *)bits, h, w, which, (const int *)roots, list, st, segs, (const unsigned long long *)fl_out, fl_words);
         CPE_KLAUNCH(k_seg_global, dim3(n), dim3(256), 0, q, st, which, (const SegRec *)segs);
-        (void)hipMemsetAsync(tmp, 0, total, q);
-        if (planar) CPE_KLAUNCH(k_seg_expand<EXP_MAXKS_PLANE>, dim3(frame_waves(n, 32, 256), n), dim3(256), 0, q, (const uint8_t *)base, h, w, which, st, (const SegRec *)segs, tmp, 201);
-        else CPE_KLAUNCH(k_seg_expand<EXP_MAXKS>, dim3(frame_waves(n, 32, 256), n), dim3(256), 0, q, (const uint8_t *)base, h, w, which, st, (const SegRec *)segs, tmp, 0);
-        CPE_KLAUNCH(k_or_and, dim3((unsigned)(((size_t)h * w + 16383) / 16384), n), dim3(256), 0, q, (const uint8_t *)tmp, (const uint8_t *)base,
-                    (const uint8_t *)B.mc, h, w, (const FrameState *)st, exp);
+        // the expansion adds its pixels to the seed k_roi_base left in exp
+        if (planar) CPE_KLAUNCH(k_seg_expand<EXP_MAXKS_PLANE>, dim3(frame_waves(n, 32, 256), n), dim3(EXP_NT), 0, q, (const uint32_t *)bits, (const uint8_t *)B.mc, h, w, which, st, (const SegRec *)segs, exp, 201);
+        else CPE_KLAUNCH(k_seg_expand<EXP_MAXKS>, dim3(frame_waves(n, 32, 256), n), dim3(EXP_NT), 0, q, (const uint32_t *)bits, (const uint8_t *)B.mc, h, w, which, st, (const SegRec *)segs, exp, 0);
         CPE_CHECK_LAUNCH("masks_stage expand");
         // cv2.connectedComponents of the expanded mask: unions only, k_lines resolves the joints' labels
         if ((rc = ccl_unions(exp, n, h, w, WIN_REGION, which ? B.lab_v : B.lab_h, st, q)) != CPE_OK) return rc;

@@ -53,12 +53,12 @@ static int region_maxdf(int h, int w) { long long v = (long long)h * w / 16; ret
     X(BRIGHT_COUNTS, N * 4, -1, OV_BRIGHT, 0)   /* ... its per-root accumulator */ \
     X(ROI_H,  N, CPE_PLANE_ROI_H, OV_BRIGHT, 1) \
     X(ROI_V,  N, CPE_PLANE_ROI_V, OV_BRIGHT, 1) \
-    X(BASE_H, N, -1, OV_BRIGHT, 1) \
+    X(BASE_H, N, -1, OV_BRIGHT, 1)              /* bytes of the fragment masks' base: written only where the labelling reads bytes */ \
     X(BASE_V, N, -1, OV_BRIGHT, 1) \
     X(EXP_H,  N, CPE_PLANE_EXP_H, OV_BRIGHT, 1) \
     X(EXP_V,  N, CPE_PLANE_EXP_V, OV_BRIGHT, 1) \
-    X(TMPA,   N, -1, OV_BRIGHT, 1) \
-    X(TMPB,   N, -1, OV_BRIGHT, 1) \
+    X(TMPA,   N, -1, OV_BRIGHT, 1)              /* unused since the expansion stores into EXP_* directly (the overlay costs no memory) */ \
+    X(TMPB,   N, -1, OV_BRIGHT, 1)              /* unused, as TMPA */ \
     X(DISCS,  N, -1, OV_BRIGHT, 1)              /* disc-union image; before the sweep, the L plane of colour frames */ \
     X(MASK_CONTOUR, N, CPE_PLANE_MASK_CONTOUR, OV_BRIGHT, 1) \
     X(BLUR7,  N, CPE_PLANE_BLUR7, OV_BRIGHT, 1) \
