@@ -20,6 +20,8 @@ from .fit import GridTables, MAXP
 PLANES = dict(binary=0, hmask=1, vmask=2, mask_contour=3, roi_h=4, roi_v=5, exp_h=6, exp_v=7, joints=8, state=9,
               clahe=10, blur19=11, blur7=12, labels=13, sweep=14)
 TARGETS = dict(cylinder=0, plane=1)
+# debug outputs that no stage reads where rows are a multiple of 16 pixels: undefined after detect_grid_batch(debug_planes=False)
+DEBUG_PLANES = ('hmask', 'vmask', 'roi_h', 'roi_v')
 STATUS_TEXT = {0: 'ok', 1: 'no region (cv2.convexHull(None))', 2: 'no saturated spot (circle_radius0 unbound)',
                3: 'no valid rows/cols', 4: 'empty point list', 5: 'too few points', 6: 'workspace capacity exceeded',
                7: 'sub-pixel refinement raised (line sample above / left of the image)'}
@@ -44,6 +46,7 @@ class DetectWorkspace:
         self.buf = torch.empty(self.bytes + 256, dtype=torch.uint8, device=device)
         off = (-self.buf.data_ptr()) % 256
         self.view = self.buf[off:off + self.bytes]
+        self.skipped_debug_planes = False       # the last call left DEBUG_PLANES unwritten
 
     def fits(self, n, h, w):
         return (h, w) == (self.h, self.w) and n <= self.capacity_n and \
@@ -61,6 +64,8 @@ class DetectWorkspace:
 
     def plane(self, name):
         """intermediate of the last call: u8 [n,h,w] planes, i32 [n,CPE_MAXJ,2] joints, or the state records"""
+        if self.skipped_debug_planes and name in DEBUG_PLANES:
+            raise RuntimeError(f'plane({name!r}): the last call ran with debug_planes=False and did not write it')
         L = _lib.load()
         off = C.c_size_t(); per = C.c_size_t()
         _lib.check(L.cpe_detect_workspace_plane(self.n, self.h, self.w, PLANES[name], C.byref(off), C.byref(per)),
@@ -93,12 +98,15 @@ def _output_tables(n, dev):
                 status=torch.zeros(n, dtype=torch.int32, device=dev))
 
 
-def detect_grid_batch(frames, ws=None, subpixel=False, subpixel_window=7, subpixel_step=1.0, target='cylinder', out=None):
+def detect_grid_batch(frames, ws=None, subpixel=False, subpixel_window=7, subpixel_step=1.0, target='cylinder', out=None,
+                      debug_planes=True):
     """frames: u8 tensor [n,h,w] (grey) or [n,h,w,3] (BGR, as cv2.imread delivers) on the GPU -> dict(xy f64[n,MAXP,2],
     id i32[n,MAXP,2], n i32[n], center f64[n,2], status i32[n], ws).  target='plane': the planar-target script
     (python_grid_detection_plane.py, row f-2); ids are (row, col) there.
     out: the tables of an earlier call with the same n on the same device, written again instead of five new zeroed tensors
-    (the earlier result changes with them, and rows of xy / id past n[k] keep what they held)."""
+    (the earlier result changes with them, and rows of xy / id past n[k] keep what they held).
+    debug_planes=False: a caller that only wants the tables declines the planes DEBUG_PLANES (CPE_DETECT_SKIP_DEBUG_PLANES):
+    where the width is a multiple of 16 they are not written and ws.plane() refuses them; other widths write them anyway."""
     if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and
             (frames.dim() == 3 or (frames.dim() == 4 and frames.shape[3] == 3))):
         raise TypeError('frames must be a CUDA uint8 tensor [n,h,w] (grey) or [n,h,w,3] (BGR)')
@@ -117,12 +125,15 @@ def detect_grid_batch(frames, ws=None, subpixel=False, subpixel_window=7, subpix
     elif out['n'].shape[0] != n or out['n'].device != dev:
         raise ValueError('detect_grid_batch: `out` holds the tables of another batch size or device')
     xy, ids, cnt, center, status = out['xy'], out['id'], out['n'], out['center'], out['status']
-    prm = _lib.CpeDetectParams(1 if subpixel else 0, subpixel_window, subpixel_step, TARGETS[target], 0)
+    prm = _lib.CpeDetectParams(1 if subpixel else 0, subpixel_window, subpixel_step, TARGETS[target],
+                               0 if debug_planes else _lib.DETECT_SKIP_DEBUG_PLANES)
+    ws.skipped_debug_planes = False         # (set once the call has gone through)
     entry = L.cpe_detect_grid_bgr_batch_ex if colour else L.cpe_detect_grid_batch_ex
     _lib.check(entry(frames.data_ptr(), n, h, w, C.addressof(prm), ws.view.data_ptr(), ws.bytes,
                      xy.data_ptr(), ids.data_ptr(), cnt.data_ptr(), center.data_ptr(),
                      status.data_ptr(), torch.cuda.current_stream().cuda_stream),
                'cpe_detect_grid_bgr_batch_ex' if colour else 'cpe_detect_grid_batch_ex')
+    ws.skipped_debug_planes = not debug_planes and w % 16 == 0
     return dict(xy=xy, id=ids, n=cnt, center=center, status=status, ws=ws, ws_generation=ws.generation)
 
 
@@ -142,6 +153,7 @@ def debug_masks(binary, gray, mask_contour, rect, region_status, ws=None, target
     if ws is None or not ws.fits(n, h, w) or ws.view.device != dev:
         ws = DetectWorkspace(n, h, w, dev)
     ws.use(n)
+    ws.skipped_debug_planes = False
     _lib.check(_lib.load().cpe_debug_masks(ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), rect.data_ptr(),
                                            region_status.data_ptr(), n, h, w, TARGETS[target], ws.view.data_ptr(), ws.bytes,
                                            torch.cuda.current_stream().cuda_stream), 'cpe_debug_masks')

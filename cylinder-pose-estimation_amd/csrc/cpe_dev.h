@@ -114,6 +114,9 @@ struct MaskBuffers {
     unsigned long long *fl_j;                 // joints chain: [n][h * ceil(w/64)] background masks, then the same of outer background
     uint32_t *jbits;                          // one-bit plane of the joints mask (build_bitplanes layout, one plane per frame)
     SegRec *segs;
+    // CPE_DETECT_SKIP_DEBUG_PLANES: where the line masks travel as one-bit planes (line_masks_as_bits, masks.hip) the bytes of
+    // hmask / vmask / roi_h / roi_v are not written
+    bool skip_debug = false;
 };
 
 // FrameState::overflow is a bit mask of the fixed capacity that was exceeded (any bit => CPE_ST_OVERFLOW)
@@ -238,6 +241,21 @@ __host__ __device__ inline const unsigned long long *bit_plane(const uint32_t *b
 __host__ __device__ inline unsigned long long *bit_plane(uint32_t *base, size_t i, int h, int w)
 {
     return reinterpret_cast<unsigned long long *>(base) + i * bit_plane_words(h, w);
+}
+
+// rows y0 .. y0 + R - 1 (y0, R: multiples of 8) of a tiled one-bit plane, word(tr, j) = row y0 + tr, pixels
+// 64 j .. 64 j + 63: whole tiles, 8 consecutive threads of the workgroup (256 threads) per 64-byte tile.  The zero tile
+// columns and the rows >= h of the last tile row are written as zeros.
+template <class Word>
+__device__ __forceinline__ void store_plane_band(unsigned long long *plane, int h, int w, int y0, int R, int t, Word word)
+{
+    const int tc = bit_tile_cols(w);
+    const int rows = min(R, ((h + 7) & ~7) - y0);
+    unsigned long long *o = plane + (size_t)(y0 >> 3) * tc * 8;
+    for (int i = t; i < rows * tc; i += 256) {
+        const int tile = i >> 3, tyl = tile / tc, tx = tile - tyl * tc, tr = tyl * 8 + (i & 7);
+        o[i] = (tx == 0 || tx == tc - 1 || y0 + tr >= h) ? 0ull : word(tr, tx - 1);
+    }
 }
 
 // BitWin keeps a 16-row x 64-column window of a plane around the current border pixel in LDS (one column of `win` per

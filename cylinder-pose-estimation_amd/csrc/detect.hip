@@ -203,6 +203,7 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
                   "cpe_detect_grid_batch_ex: bad sub-pixel parameters");
     CPE_CHECK_ARG(prm.target == CPE_TARGET_CYLINDER || prm.target == CPE_TARGET_PLANE, "cpe_detect_grid_batch_ex: unknown target %d", prm.target);
     CPE_CHECK_ARG(!(prm.target == CPE_TARGET_PLANE && prm.subpixel), "cpe_detect_grid_batch_ex: no sub-pixel refinement for the planar target");
+    CPE_CHECK_ARG((prm.flags & ~CPE_DETECT_SKIP_DEBUG_PLANES) == 0, "cpe_detect_grid_batch_ex: unknown flags 0x%x", (unsigned)prm.flags);
     const int planar = prm.target == CPE_TARGET_PLANE ? 1 : 0;
     CPE_CHECK_ARG((gray || bgr) && xy && id && n_pts && center && status, "cpe_detect_grid_batch: null pointer");
     CPE_CHECK_ARG(!(bgr && prm.subpixel), "cpe_detect_grid_bgr_batch_ex: colour frames: no sub-pixel refinement");
@@ -222,6 +223,7 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
     if (bgr) gray = grayin;
     RegionBuffers R = region_buffers(W, h, w);
     MaskBuffers M = mask_buffers(W, R);
+    M.skip_debug = (prm.flags & CPE_DETECT_SKIP_DEBUG_PLANES) != 0;
     // three chains that only meet in masks_stage: ridge mask -> line masks -> joints (stream 1), saturated spot
     // (stream 2), region (the caller's stream).  The side chains are mostly ALU / latency bound and fill the CUs the
     // region stage's serial kernels leave idle.  The helper streams and their events are per device and shared by all

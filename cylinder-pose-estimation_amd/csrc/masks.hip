@@ -20,6 +20,9 @@ namespace {
 // 192-bit window (word and both neighbours) with the window doubled 1 -> 2 -> 4 -> 8 -> 16 (+4) taps; the vertical one is
 // the same doubling across rows, word by word, ping-ponged between two LDS buffers.  ~2 bit operations per pixel instead
 // of 80 byte reads; the masks leave as bytes, 8 pixels per store.
+// Where the consumers read words (hb / vb given: line_masks_as_bits) hmask and vmask leave as one-bit planes as well, the
+// joints mask only as one (jbits): its bytes have no reader there, and the bytes of hmask / vmask are a debug output that the
+// caller may decline (hm, vm null).
 struct W3 { unsigned long long a, b, c; };   // pixels [-64, -1], [0, 63], [64, 127] relative to the word; bit i = pixel i
 template <int K> __device__ __forceinline__ W3 w3_up(const W3 &v, unsigned long long fill)     // r[p] = v[p + K]
 {
@@ -64,26 +67,12 @@ __device__ __forceinline__ unsigned long long bytes_of_bits8(unsigned bits)   //
     return v * 255ull;
 }
 
-// rows y0 .. y0 + R - 1 (y0, R: multiples of 8) of a tiled one-bit plane (cpe_dev.h), word(tr, j) = row y0 + tr, pixels
-// 64 j .. 64 j + 63: whole tiles, 8 consecutive threads of the workgroup (256 threads) per 64-byte tile.  The zero tile
-// columns and the rows >= h of the last tile row are written as zeros.
-template <class Word>
-__device__ __forceinline__ void store_plane_band(unsigned long long *plane, int h, int w, int y0, int R, int t, Word word)
-{
-    const int tc = bit_tile_cols(w);
-    const int rows = min(R, ((h + 7) & ~7) - y0);
-    unsigned long long *o = plane + (size_t)(y0 >> 3) * tc * 8;
-    for (int i = t; i < rows * tc; i += 256) {
-        const int tile = i >> 3, tyl = tile / tc, tx = tile - tyl * tc, tr = tyl * 8 + (i & 7);
-        o[i] = (tx == 0 || tx == tc - 1 || y0 + tr >= h) ? 0ull : word(tr, tx - 1);
-    }
-}
-
 constexpr int OB_AP = 20;
 template <int R>
 __global__ __launch_bounds__(256) void k_open20_joints(const uint8_t *__restrict__ bin, int h, int w, int bands,
                                                        uint8_t *__restrict__ hm, uint8_t *__restrict__ vm,
-                                                       uint8_t *__restrict__ jm, uint32_t *__restrict__ jbits)
+                                                       uint8_t *__restrict__ jm, uint32_t *__restrict__ jbits,
+                                                       unsigned long long *__restrict__ hb, unsigned long long *__restrict__ vb)
 {
     // jbits: the joints mask once more as a one-bit plane (the words are in LDS anyway): its labelling, its RETR_EXTERNAL
     // flood and the border tracer of the joint centroids read an eighth of the bytes
@@ -162,7 +151,7 @@ __global__ __launch_bounds__(256) void k_open20_joints(const uint8_t *__restrict
     // outputs: 8 pixels per step
     {
         const int per_row = WW * 8;
-        for (int i = t; i < R * per_row; i += 256) {
+        for (int i = t; hm && i < R * per_row; i += 256) {
             const int tr = i / per_row, k = i - tr * per_row;
             const int y = y0 + tr, x0 = k * 8;
             if (y >= h || x0 >= w) continue;
@@ -175,21 +164,30 @@ __global__ __launch_bounds__(256) void k_open20_joints(const uint8_t *__restrict
             if (al8 && (((size_t)hm | (size_t)vm | (size_t)jm) & 7) == 0) {
                 *reinterpret_cast<unsigned long long *>(hm + o) = bytes_of_bits8(hb);
                 *reinterpret_cast<unsigned long long *>(vm + o) = bytes_of_bits8(vb);
-                *reinterpret_cast<unsigned long long *>(jm + o) = bytes_of_bits8(hb & vb);
+                if (jm) *reinterpret_cast<unsigned long long *>(jm + o) = bytes_of_bits8(hb & vb);
             } else {
                 for (int b = 0; b < 8 && x0 + b < w; b++) {
                     hm[o + b] = ((hb >> b) & 1u) ? 255 : 0;
                     vm[o + b] = ((vb >> b) & 1u) ? 255 : 0;
-                    jm[o + b] = (((hb & vb) >> b) & 1u) ? 255 : 0;
+                    if (jm) jm[o + b] = (((hb & vb) >> b) & 1u) ? 255 : 0;
                 }
             }
         }
-        store_plane_band(bit_plane(jbits, f, h, w), h, w, y0, R, t, [&](int tr, int j) {
+        // hsel / vsel: which of the two masks go into the word
+        auto plane_word = [&](int tr, int j, bool hsel, bool vsel) {
             const size_t wi = (size_t)tr * WW + j;
-            unsigned long long m = hbuf[wi] & (buf0[wi] | ((tr + 12 < ROWS) ? buf1[wi + (size_t)12 * WW] : 0ull));
+            unsigned long long m = ~0ull;
+            if (hsel) m &= hbuf[wi];
+            if (vsel) m &= buf0[wi] | ((tr + 12 < ROWS) ? buf1[wi + (size_t)12 * WW] : 0ull);
             if (64 * j + 64 > w) m &= (1ull << (w - 64 * j)) - 1ull;      // columns past the end of the row
             return m;
-        });
+        };
+        store_plane_band(bit_plane(jbits, f, h, w), h, w, y0, R, t, [&](int tr, int j) { return plane_word(tr, j, true, true); });
+        if (hb) {
+            const size_t pw = bit_plane_words(h, w);
+            store_plane_band(hb + f * pw, h, w, y0, R, t, [&](int tr, int j) { return plane_word(tr, j, true, false); });
+            store_plane_band(vb + f * pw, h, w, y0, R, t, [&](int tr, int j) { return plane_word(tr, j, false, true); });
+        }
     }
 }
 
@@ -198,6 +196,8 @@ __global__ __launch_bounds__(256) void k_open20_joints(const uint8_t *__restrict
 // holds a band of RB_R + 8 rows (all columns) as 64-pixel words in LDS and runs the four 3x3 passes on words (3 taps
 // along the row by shifts, 3 rows by AND / OR).  mask_contour is zero outside the region rectangle, so only its pixels
 // are read: everything else packs as zero, and bands further than 4 rows from it are written as zeros straight away.
+// The line mask m comes as bytes, or (mb given: line_masks_as_bits) as the one-bit planes k_open20_joints wrote, one per
+// frame; roi's bytes are a debug output (null: not written).
 // The kernel also seeds the expanded mask: exp = base & mask_contour (the closing is extensive, base may stick out of
 // mask_contour), full frame, zeros included -- k_seg_expand only adds 255s to it, and nothing else clears the plane.
 constexpr int RB_R = 64, RB_AP = 4, RB_ROWS = RB_R + 2 * RB_AP;
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m,
                                                   const uint8_t *__restrict__ mc, int h, int w, int bands,
                                                   const FrameState *__restrict__ st, uint8_t *__restrict__ roi,
                                                   uint8_t *__restrict__ base, uint8_t *__restrict__ exp,
-                                                  uint32_t *__restrict__ bbits)
+                                                  uint32_t *__restrict__ bbits, const unsigned long long *__restrict__ mb)
 {
     // bbits: `base` as a one-bit plane (cpe_dev.h tiled layout, one plane per frame): the fragments' flood, border tracer
     // and expansion read the plane, and so does their labelling where rows allow the word-level kernels.
@@ -231,7 +231,8 @@ __global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m,
             const int y = y0 + tr, x0 = k * 8;
             if (y >= h || x0 >= w) continue;
             const size_t o = f * N + (size_t)y * w + x0;
-            store8(roi, o, x0, 0u); store8(exp, o, x0, 0u);
+            if (roi) store8(roi, o, x0, 0u);
+            store8(exp, o, x0, 0u);
             if (base) store8(base, o, x0, 0u);
         }
         store_plane_band(bit_plane(bbits, f, h, w), h, w, y0, RB_R, t, [](int, int) { return 0ull; });
@@ -245,22 +246,28 @@ __global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m,
             v = (((v & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | v) & 0x8080808080808080ull;
             return (unsigned)(((v >> 7) * 0x0102040810204080ull) >> 56);
         };
+        const unsigned long long *mbf = mb ? mb + f * bit_plane_words(h, w) : nullptr;
+        const int btc = bit_tile_cols(w);
         for (int i = t; i < RB_ROWS * per_row; i += 256) {
             const int r = i / per_row, k = i - r * per_row;
             const int y = y0 - RB_AP + r, x0 = k * 8;
             unsigned bits = 0u, cbits = 0u;
             if (y >= ry0 && y <= ry1 && y >= 0 && y < h && x0 < w && x0 + 7 >= rx0 && x0 <= rx1) {
                 const size_t o = f * N + (size_t)y * w + x0;
+                // a line-mask byte is 0 or 255: (m & cm & mc) != 0 is the mask's bit and (cm & mc) != 0
+                const unsigned mbits = mbf ? (unsigned)(mbf[bit_word(btc, y, k >> 3)] >> ((k & 7) * 8)) & 255u : 255u;
                 if (al8) {
                     const unsigned long long vc = *reinterpret_cast<const unsigned long long *>(mc + o);
-                    bits = nonzero8(*reinterpret_cast<const unsigned long long *>(m + o) &
-                                    *reinterpret_cast<const unsigned long long *>(cm + o) & vc);
+                    unsigned long long v = *reinterpret_cast<const unsigned long long *>(cm + o) & vc;
+                    if (!mbf) v &= *reinterpret_cast<const unsigned long long *>(m + o);
+                    bits = nonzero8(v) & mbits;
                     cbits = nonzero8(vc);
                 } else {
                     for (int b = 0; b < 8 && x0 + b < w; b++) {
-                        bits |= ((m[o + b] & cm[o + b]) & mc[o + b]) ? (1u << b) : 0u;
+                        bits |= (((mbf ? 255 : m[o + b]) & cm[o + b]) & mc[o + b]) ? (1u << b) : 0u;
                         cbits |= mc[o + b] ? (1u << b) : 0u;
                     }
+                    bits &= mbits;
                 }
             }
             pk[i] = (uint8_t)bits;
@@ -307,7 +314,7 @@ __global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m,
     };
     pass(buf0, buf1, false);   // erode
     pass(buf1, buf0, true);    // dilate -> roi
-    emit(buf0, roi, nullptr, nullptr);
+    if (roi) emit(buf0, roi, nullptr, nullptr);
     pass(buf0, buf1, true);    // dilate
     pass(buf1, buf0, false);   // erode -> base
     emit(buf0, base, exp, mcb);
@@ -1250,6 +1257,14 @@ __global__ void k_masks_reset(FrameState *st, int n)
 
 inline unsigned grid1(size_t total) { return (unsigned)((total + 255) / 256); }
 
+// true: every reader of the joints mask takes its one-bit plane (ccl_components, outside_flood, the centroid tracer), so the
+// buffer of its bytes is free and holds hmask and vmask as one-bit planes for k_roi_base: n frames of hmask, then n of vmask
+inline bool line_masks_as_bits(const MaskBuffers &B, int w) { return ccl_components_reads_bits(B.jbits, w, B.lab_p); }
+inline unsigned long long *line_mask_bits(const MaskBuffers &B, int which, int n, int h, int w)
+{
+    return reinterpret_cast<unsigned long long *>(B.joints_mask) + (size_t)which * n * bit_plane_words(h, w);
+}
+
 }  // namespace
 
 
@@ -1339,6 +1354,12 @@ int blur7_u8(const uint8_t *src, int n, int h, int w, const FrameState *st, uint
 int joints_mask_stage(int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s)
 {
     CPE_LAUNCH_BEGIN();
+    // word-level consumers: hmask / vmask leave as one-bit planes in the joints-mask buffer, whose bytes nobody reads then
+    const bool as_bits = line_masks_as_bits(B, w);
+    CPE_CHECK_ARG(!as_bits || 2 * bit_plane_words(h, w) * 8 <= (size_t)h * w, "joints_mask_stage: frame too small for its line-mask planes");
+    unsigned long long *hb = as_bits ? line_mask_bits(B, 0, n, h, w) : nullptr, *vb = as_bits ? line_mask_bits(B, 1, n, h, w) : nullptr;
+    uint8_t *hm = as_bits && B.skip_debug ? nullptr : B.hmask, *vm = as_bits && B.skip_debug ? nullptr : B.vmask;
+    uint8_t *jm = as_bits ? nullptr : B.joints_mask;
     {
         // band height by LDS budget: (2 (R + 40) + R) words of 8 bytes per 64 columns
         const int WW = (w + 63) / 64;
@@ -1350,12 +1371,12 @@ int joints_mask_stage(int n, int h, int w, const MaskBuffers &B, FrameState *st,
         if (lds64 <= 96 * 1024) {
             const int bands = (h + 63) / 64;
             CPE_KLAUNCH(k_open20_joints<64>, dim3((unsigned)(n * bands)), dim3(256), lds64, s, (const uint8_t *)B.binary, h, w, bands,
-                        B.hmask, B.vmask, B.joints_mask, B.jbits);
+                        hm, vm, jm, B.jbits, hb, vb);
         } else {
             CPE_CHECK_ARG(lds32 <= 160 * 1024, "joints_mask_stage: frame too wide (%d columns)", w);
             const int bands = (h + 31) / 32;
             CPE_KLAUNCH(k_open20_joints<32>, dim3((unsigned)(n * bands)), dim3(256), lds32, s, (const uint8_t *)B.binary, h, w, bands,
-                        B.hmask, B.vmask, B.joints_mask, B.jbits);
+                        hm, vm, jm, B.jbits, hb, vb);
         }
     }
     CPE_CHECK_LAUNCH("joints_mask_stage");
@@ -1424,8 +1445,10 @@ int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, 
     if (side) { (void)hipEventRecord(side->clahe_done, s); (void)hipStreamWaitEvent(side->s, side->clahe_done, 0); }
     for (int which = 0; which < 2; which++) {
         hipStream_t q = (which && side) ? side->s : s;
-        const uint8_t *lm = which ? B.vmask : B.hmask;
-        uint8_t *roi = which ? B.roi_v : B.roi_h;
+        const bool as_bits = line_masks_as_bits(B, w);
+        const uint8_t *lm = as_bits ? nullptr : (which ? B.vmask : B.hmask);
+        const unsigned long long *lmb = as_bits ? line_mask_bits(B, which, n, h, w) : nullptr;
+        uint8_t *roi = as_bits && B.skip_debug ? nullptr : (which ? B.roi_v : B.roi_h);
         uint8_t *exp = which ? B.exp_v : B.exp_h;
         int *lab = which ? B.lab_s : B.lab, *roots = which ? B.roots_s : B.roots;
         const RootList list = which ? ROOTS_SPOT : ROOTS_MAIN;
@@ -1435,7 +1458,7 @@ int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, 
         // base's bytes are only written where the labelling will read them (the byte-level kernels)
         uint8_t *base = ccl_components_reads_bits(bits, w, lab) ? nullptr : (which ? B.base_v : B.base_h);
         CPE_KLAUNCH(k_roi_base, dim3((unsigned)(n * rb_bands)), dim3(256), rb_lds, q, lm, (const uint8_t *)B.cm, (const uint8_t *)B.mc,
-                    h, w, rb_bands, (const FrameState *)st, roi, base, exp, bits);
+                    h, w, rb_bands, (const FrameState *)st, roi, base, exp, bits, lmb);
         if ((rc = ccl_components(base, bits, n, h, w, 0, WIN_REGION, lab, roots, list, st, q)) != CPE_OK) return rc;
         unsigned long long *fl_bg = fl_plane(2 + 2 * which), *fl_out = fl_plane(3 + 2 * which);
         if ((rc = outside_flood(base, n, h, w, st, WIN_REGION, fl_bg, fl_out, fl_words, q, bits)) != CPE_OK) return rc;

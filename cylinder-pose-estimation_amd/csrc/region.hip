@@ -1793,6 +1793,78 @@ __global__ __launch_bounds__(256) void k_discs(FrameState *__restrict__ st, cons
     }
 }
 
+// The same union where its readers take the one-bit plane (rows a multiple of 16 pixels: disc_union_as_bits), without the
+// byte image in between.  k_disc_keypoints: the key points as compact records {cx | cy << 16, er} (the integers k_discs
+// draws with; centres lie inside the frame, <= 4096 wide and high), in any order -- the union does not depend on it -- and
+// st[].n_kp counts them as it does in k_discs.
+__global__ __launch_bounds__(256) void k_disc_keypoints(FrameState *__restrict__ st, const Group *__restrict__ groups, int2 *__restrict__ recs)
+{
+    const int f = blockIdx.y;
+    const int ng = min(st[f].n_groups, MAXG);
+    for (int gi = blockIdx.x * 256 + threadIdx.x; gi < ng; gi += gridDim.x * 256) {
+        const Group &g = groups[(size_t)f * MAXG + gi];
+        const int gn = g.n;
+        if (gn < 2) continue;
+        float kx, ky, ksize;
+        group_keypoint(g, gn, kx, ky, ksize);
+        float radius = ksize / 2;
+        int er = (int)((double)radius + 4);
+        int cx = (int)kx, cy = (int)ky;
+        const int q = atomicAdd(&st[f].n_kp, 1);          // < MAXG: one per group
+        recs[(size_t)f * MAXG + q] = make_int2((cx & 0xffff) | (cy << 16), er);
+    }
+}
+
+// A workgroup per band of DB_R rows: the band's words are cleared in LDS, every disc that reaches the band ORs the midpoint-
+// circle spans of k_discs (clipped to the frame and to the band) into them, a thread per disc, and the band is stored as
+// whole tiles, zero tiles included: the plane needs no clearing, columns >= w and rows >= h stay zero.
+constexpr int DB_R = 64;
+__global__ __launch_bounds__(256) void k_disc_bands(const FrameState *__restrict__ st, const int2 *__restrict__ recs, int h, int w,
+                                                    int bands, uint32_t *__restrict__ bits)
+{
+    extern __shared__ unsigned long long s_db[];   // DB_R rows of WW words
+    const int WW = (w + 63) >> 6, t = threadIdx.x;
+    const int f = blockIdx.x / bands, band = blockIdx.x - f * bands;
+    const int y0 = band * DB_R, y1 = min(y0 + DB_R, h) - 1;
+    for (int i = t; i < DB_R * WW; i += 256) s_db[i] = 0ull;
+    __syncthreads();
+    const int nk = min(st[f].n_kp, MAXG);
+    const int2 *rc = recs + (size_t)f * MAXG;
+    for (int k = t; k < nk; k += 256) {
+        const int2 v = rc[k];
+        const int cx = (int)(short)(v.x & 0xffff), cy = v.x >> 16, er = v.y;
+        if (er < 0 || (long long)cy + er < y0 || (long long)cy - er > y1) continue;
+        int err = 0, dx = er, dy = 0, plus = 1, minus = (er << 1) - 1;
+        while (dx >= dy) {
+            int ys[4] = {cy - dy, cy + dy, cy - dx, cy + dx};
+            int xa[4] = {cx - dx, cx - dx, cx - dy, cx - dy};
+            int xb[4] = {cx + dx, cx + dx, cx + dy, cx + dy};
+            for (int q = 0; q < 4; q++) {
+                if (ys[q] < y0 || ys[q] > y1) continue;
+                const int x1 = max(xa[q], 0), x2 = min(xb[q], w - 1);
+                if (x1 > x2) continue;
+                unsigned long long *row = s_db + (size_t)(ys[q] - y0) * WW;
+                const int j1 = x1 >> 6, j2 = x2 >> 6;
+                for (int j = j1; j <= j2; j++) {
+                    unsigned long long m = ~0ull;
+                    if (j == j1) m &= ~0ull << (x1 & 63);
+                    if (j == j2) m &= ~0ull >> (63 - (x2 & 63));
+                    atomicOr(&row[j], m);
+                }
+            }
+            dy++;
+            err += plus;
+            plus += 2;
+            int mask = (err <= 0) - 1;
+            err -= minus & mask;
+            dx += mask;
+            minus -= mask & 2;
+        }
+    }
+    __syncthreads();
+    store_plane_band(bit_plane(bits, f, h, w), h, w, y0, DB_R, t, [&](int tr, int j) { return s_db[(size_t)tr * WW + j]; });
+}
+
 // contourArea of every external contour of the disc union; keep the largest (first in OpenCV order on ties)
 __global__ __launch_bounds__(64) void k_region_area(const uint32_t *__restrict__ ext_bits, int h, int w,
                                                     const int *__restrict__ roots, FrameState *__restrict__ st,
@@ -2426,10 +2498,21 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
         CPE_KLAUNCH(k_probe_keypoints, dim3(n), dim3(256), 0, s, (const FrameState *)st, (const Group *)B.groups, probe->kp, probe->kp_cap, probe->n_kp);
         CPE_CHECK_LAUNCH("region probe");
     }
-    (void)hipMemsetAsync(B.ext, 0, total, s);
     (void)hipMemsetAsync(B.mc, 0, total, s);
-    CPE_KLAUNCH(k_discs, dim3(frame_waves(n, 4, MAXG / 4), n), dim3(256), 0, s, st, B.groups, h, w, B.ext);
-    if ((rc = build_bitplanes(B.ext, n, h, w, 0, 0, 1, B.bits, s)) != CPE_OK) return rc;
+    if (ccl_components_reads_bits(B.bits, w, B.lab)) {
+        // every reader of the disc union takes its one-bit plane: the discs are drawn straight into it.  The key-point records
+        // lie in the ranking scratch of k_blob_merge, which is done with it
+        static_assert((size_t)MAXG * sizeof(int2) <= (size_t)2 * MAXB * sizeof(int), "the key-point records fit the ranking scratch");
+        int2 *recs = reinterpret_cast<int2 *>(B.order);
+        const int bands = (h + DB_R - 1) / DB_R;
+        CPE_KLAUNCH(k_disc_keypoints, dim3(frame_waves(n, 4, MAXG / 256), n), dim3(256), 0, s, st, (const Group *)B.groups, recs);
+        CPE_KLAUNCH(k_disc_bands, dim3((unsigned)(n * bands)), dim3(256), (size_t)DB_R * ((w + 63) / 64) * 8, s, (const FrameState *)st,
+                    (const int2 *)recs, h, w, bands, B.bits);
+    } else {
+        (void)hipMemsetAsync(B.ext, 0, total, s);
+        CPE_KLAUNCH(k_discs, dim3(frame_waves(n, 4, MAXG / 4), n), dim3(256), 0, s, st, B.groups, h, w, B.ext);
+        if ((rc = build_bitplanes(B.ext, n, h, w, 0, 0, 1, B.bits, s)) != CPE_OK) return rc;
+    }
     // the labelling reads the one-bit plane (1/8 of the bytes)
     if ((rc = ccl_components(B.ext, B.bits, n, h, w, 0, WIN_FRAME, B.lab, B.roots, ROOTS_MAIN, st, s)) != CPE_OK) return rc;
     CPE_KLAUNCH(k_region_area, dim3(frame_waves(n, 8, 64), n), dim3(64), 0, s, (const uint32_t *)B.bits, h, w, B.roots, st, B.best, 1);

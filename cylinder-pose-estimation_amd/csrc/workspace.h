@@ -59,7 +59,7 @@ static int region_maxdf(int h, int w) { long long v = (long long)h * w / 16; ret
     X(EXP_V,  N, CPE_PLANE_EXP_V, OV_BRIGHT, 1) \
     X(TMPA,   N, -1, OV_BRIGHT, 1)              /* unused since the expansion stores into EXP_* directly (the overlay costs no memory) */ \
     X(TMPB,   N, -1, OV_BRIGHT, 1)              /* unused, as TMPA */ \
-    X(DISCS,  N, -1, OV_BRIGHT, 1)              /* disc-union image; before the sweep, the L plane of colour frames */ \
+    X(DISCS,  N, -1, OV_BRIGHT, 1)              /* disc-union image (widths whose union is not drawn straight into its one-bit plane); before the sweep, the L plane of colour frames */ \
     X(MASK_CONTOUR, N, CPE_PLANE_MASK_CONTOUR, OV_BRIGHT, 1) \
     X(BLUR7,  N, CPE_PLANE_BLUR7, OV_BRIGHT, 1) \
     X(LABELS_JOINTS, N * 4, -1, OV_CHAINS, 0)   /* label plane of the joints chain */ \
@@ -78,7 +78,7 @@ static int region_maxdf(int h, int w) { long long v = (long long)h * w / 16; ret
     X(STATE,  sizeof(FrameState), CPE_PLANE_STATE, OV_NONE, 0) \
     X(CLAHE,  N, CPE_PLANE_CLAHE, OV_NONE, 0)   /* CLAHE'd L channel; planar target, colour frames: the any-channel mask */ \
     X(BLUR19, N, CPE_PLANE_BLUR19, OV_NONE, 0) \
-    X(JOINTS_MASK, N, -1, OV_NONE, 0) \
+    X(JOINTS_MASK, N, -1, OV_NONE, 0)           /* joints mask as bytes; where its readers take JOINT_BITS (rows of 16 k pixels): hmask, vmask as one-bit planes, n frames each */ \
     X(CM,     N, -1, OV_NONE, 0) \
     X(TOUCH,  N, -1, OV_NONE, 0) \
     X(ROOTS,  (size_t)MAXROOTS * sizeof(int), -1, OV_NONE, 0) \
@@ -88,7 +88,7 @@ static int region_maxdf(int h, int w) { long long v = (long long)h * w / 16; ret
     X(SEGS,   (size_t)2 * MAXSEG * sizeof(SegRec), -1, OV_NONE, 0) \
     X(HIST,   16 * 256 * sizeof(unsigned int), -1, OV_NONE, 0) \
     X(LUT,    16 * 256, -1, OV_NONE, 0) \
-    X(ORDER,  (size_t)2 * MAXB * sizeof(int), -1, OV_NONE, 0)   /* + scratch of k_blob_merge's bucketed ranking */ \
+    X(ORDER,  (size_t)2 * MAXB * sizeof(int), -1, OV_NONE, 0)   /* + scratch of k_blob_merge's bucketed ranking; then the key-point records of the disc union */ \
     X(LOHI,   (size_t)2 * w * sizeof(int), -1, OV_NONE, 0) \
     X(HULL,   (size_t)4 * w * sizeof(int), -1, OV_NONE, 0) \
     X(NRECT,  16 * sizeof(int), -1, OV_NONE, 0)             /* CLAHE's bounding box */ \

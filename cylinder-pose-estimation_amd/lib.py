@@ -75,7 +75,10 @@ _SIGS = {
 
 class CpeDetectParams(C.Structure):
     _fields_ = [('subpixel', C.c_int32), ('subpixel_window', C.c_int32), ('subpixel_step', C.c_double),
-                ('target', C.c_int32), ('reserved', C.c_int32)]
+                ('target', C.c_int32), ('flags', C.c_int32)]
+
+
+DETECT_SKIP_DEBUG_PLANES = 1    # CpeDetectParams.flags (include/cpe.h)
 
 
 class CpeDetectConstants(C.Structure):

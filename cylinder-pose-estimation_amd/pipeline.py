@@ -66,14 +66,14 @@ class FramePipeline:
         if c > 0 and self._interleaved(left, right):
             # the pairs already lie one after the other in memory: the detect call reads them in place (L0 R0 L1 R1 ...)
             frames = torch.as_strided(left, (2 * c, self.h, self.w), (self.h * self.w, self.w, 1))
-            det = api.detect_grid_batch(frames, self._ws(2 * c, lane))
+            det = api.detect_grid_batch(frames, self._ws(2 * c, lane), debug_planes=False)   # only the tables are read
             sl = lambda k, o: det[k][o::2].contiguous()
             g1 = fit.GridTables(sl('xy', 0), sl('id', 0), sl('n', 0))
             g2 = fit.GridTables(sl('xy', 1), sl('id', 1), sl('n', 1))
             st_l, st_r = det['status'][0::2], det['status'][1::2]
         else:
             frames = torch.cat([left, right])             # [2c,h,w]: one detect call for both cameras (a copy)
-            det = api.detect_grid_batch(frames, self._ws(2 * c, lane))
+            det = api.detect_grid_batch(frames, self._ws(2 * c, lane), debug_planes=False)   # only the tables are read
             g1 = fit.GridTables(det['xy'][:c], det['id'][:c], det['n'][:c])
             g2 = fit.GridTables(det['xy'][c:], det['id'][c:], det['n'][c:])
             st_l, st_r = det['status'][:c], det['status'][c:]

@@ -117,10 +117,16 @@ typedef struct CpeDetectParams {
     int32_t target;          /* CPE_TARGET_CYLINDER (python_grid_detection_cylinder.py) or CPE_TARGET_PLANE (row f-2:
                                 python_grid_detection_plane.py over utils/util_plane.py; point ids are (row, col) there,
                                 every column is kept, sub-pixel refinement is not available) */
-    int32_t reserved;
+    int32_t flags;           /* CPE_DETECT_* bits; 0 = none.  A bit this build does not know: CPE_ERR_ARG, nothing is launched */
 } CpeDetectParams;
 #define CPE_TARGET_CYLINDER 0
 #define CPE_TARGET_PLANE 1
+/* Four of the public planes are debug outputs that no later stage reads where rows are a multiple of 16 pixels (the stages
+ * then hand the line masks on as one-bit planes): CPE_PLANE_HMASK, CPE_PLANE_VMASK, CPE_PLANE_ROI_H, CPE_PLANE_ROI_V.  With
+ * this bit set they are not written at such widths and their contents are UNDEFINED after the call; every other plane and
+ * every result is what it is without the bit.  Other widths need the bytes and ignore the bit.  A caller that only wants
+ * the point tables (the frame pipeline) sets it and saves four full-frame stores per frame. */
+#define CPE_DETECT_SKIP_DEBUG_PLANES 1
 CPE_API int32_t cpe_detect_grid_batch_ex(const uint8_t *gray, int32_t n, int32_t h, int32_t w, const CpeDetectParams *params,
                                          void *ws, size_t ws_bytes, double *xy, int32_t *id, int32_t *n_pts,
                                          double *center, int32_t *status, void *stream);
@@ -243,7 +249,8 @@ CPE_API int32_t cpe_detect_grid_bgr_batch_ex(const uint8_t *bgr, int32_t n, int3
 CPE_API int32_t cpe_bgr2gray_batch(const uint8_t *bgr, int32_t n, int32_t h, int32_t w, uint8_t *gray, void *stream);
 
 /* Where an intermediate of the last cpe_detect_grid_batch call lives inside the workspace (for
- * stage-by-stage parity tests and debugging): plane-major, frame f at offset + f * bytes_per_frame. */
+ * stage-by-stage parity tests and debugging): plane-major, frame f at offset + f * bytes_per_frame.
+ * After a call with CPE_DETECT_SKIP_DEBUG_PLANES the planes HMASK, VMASK, ROI_H and ROI_V are undefined (see the flag). */
 #define CPE_PLANE_BINARY 0        /* u8[h,w]  load_and_preprocess_image -> binary_img */
 #define CPE_PLANE_HMASK 1         /* u8[h,w]  extract_joints -> horizontal_mask */
 #define CPE_PLANE_VMASK 2         /* u8[h,w]  extract_joints -> vertical_mask */
