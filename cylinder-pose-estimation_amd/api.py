@@ -160,6 +160,44 @@ def debug_masks(binary, gray, mask_contour, rect, region_status, ws=None, target
     return ws
 
 
+def debug_lines(exp_h, exp_v, joints, n_joints, rect, r0, stage_status, g7, gray=None, ws=None, subpixel=False, subpixel_window=7,
+                subpixel_step=1.0, target='cylinder'):
+    """the lines stage alone on given inputs (cpe_debug_lines, a test aid): exp_h, exp_v, g7, gray u8 [n,h,w] CUDA tensors
+    (gray: default g7), joints i32 [n,k,2] (k <= CPE_MAXJ; padded to the table), n_joints, r0, stage_status i32 [n], rect i32
+    [n,4] (x, y, w, h).  -> what detect_grid_batch returns (tables, ws, ws_generation): line_tables, pack_results and
+    ws.state() read it as they read a detect result"""
+    gray = g7 if gray is None else gray
+    ins = [exp_h, exp_v, g7, gray]
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape == exp_h.shape
+               for t in ins):
+        raise TypeError('exp_h, exp_v, g7 and gray must be CUDA uint8 tensors [n,h,w] of one shape')
+    n, h, w = exp_h.shape
+    dev = exp_h.device
+    ins = [t.contiguous() for t in ins]
+    maxj = _lib.detect_constants()['max_joints']
+    joints = joints.to(dev, torch.int32).reshape(n, -1, 2)
+    if joints.shape[1] > maxj:
+        raise ValueError(f'debug_lines: more than CPE_MAXJ = {maxj} joints per frame')
+    table = torch.zeros((n, maxj, 2), dtype=torch.int32, device=dev)
+    table[:, :joints.shape[1]] = joints
+    i32 = lambda t, shape: t.to(dev, torch.int32).contiguous().reshape(shape)
+    n_joints, r0, stage_status, rect = i32(n_joints, n), i32(r0, n), i32(stage_status, n), i32(rect, (n, 4))
+    if ws is None or not ws.fits(n, h, w) or ws.view.device != dev:
+        ws = DetectWorkspace(n, h, w, dev)
+    ws.use(n)
+    ws.skipped_debug_planes = False
+    out = _output_tables(n, dev)
+    prm = _lib.CpeDetectParams(1 if subpixel else 0, subpixel_window, subpixel_step, TARGETS[target], 0)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().cpe_debug_lines(ins[0].data_ptr(), ins[1].data_ptr(), table.data_ptr(), n_joints.data_ptr(),
+                                               rect.data_ptr(), r0.data_ptr(), stage_status.data_ptr(), ins[2].data_ptr(),
+                                               ins[3].data_ptr(), n, h, w, C.addressof(prm), ws.view.data_ptr(), ws.bytes,
+                                               out['xy'].data_ptr(), out['id'].data_ptr(), out['n'].data_ptr(),
+                                               out['center'].data_ptr(), out['status'].data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream), 'cpe_debug_lines')
+    return dict(out, ws=ws, ws_generation=ws.generation)
+
+
 def tables_of(det):
     """detect_grid_batch output -> GridTables (the N x 4 [x y col row] matrices of makePyGridPts.m:41)"""
     return GridTables(det['xy'], det['id'], det['n'])

@@ -622,3 +622,74 @@ extern "C" int32_t cpe_debug_masks(const uint8_t *binary, const uint8_t *gray, c
     if ((rc = masks_stage(gray, n, h, w, M, st, s, nullptr, planar, s)) != CPE_OK) return rc;
     return blur7_u8(gray, n, h, w, st, W.at<uint8_t>(WS_BLUR7), s);
 }
+
+namespace cpe { namespace {
+// what the lines stage reads of the stages in front of it, as the caller gives it
+__global__ void k_debug_lines_state(FrameState *st, int n, const int *rect, const int *r0, const int *n_joints, const int *status)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    for (int k = 0; k < 4; k++) st[f].rect[k] = rect[4 * f + k];
+    st[f].r0 = r0[f];
+    st[f].n_joints = min(max(n_joints[f], 0), MAXJ);
+    st[f].status = status[f];
+}
+// every pixel its own root: a mask pixel outside the labelling window (the product's masks have none, a caller's may) then
+// resolves to itself in k_lines instead of following whatever the plane held
+__global__ __launch_bounds__(256) void k_debug_singletons(int *__restrict__ lab_h, int *__restrict__ lab_v, size_t N, size_t total)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int v = (int)(i % N);
+        lab_h[i] = v; lab_v[i] = v;
+    }
+}
+} }
+
+// The lines stage on given inputs (tests): the label planes of the expanded masks as masks_stage makes them, then lines_stage
+// as detect_impl calls it, serially on `stream`.
+extern "C" int32_t cpe_debug_lines(const uint8_t *exp_h, const uint8_t *exp_v, const int32_t *joints, const int32_t *n_joints,
+                                   const int32_t *rect, const int32_t *r0, const int32_t *stage_status, const uint8_t *g7,
+                                   const uint8_t *gray, int32_t n, int32_t h, int32_t w, const CpeDetectParams *params, void *ws,
+                                   size_t ws_bytes, double *xy, int32_t *id, int32_t *n_pts, double *center, int32_t *status,
+                                   void *stream)
+{
+    CpeDetectParams prm = {0, 7, 1.0, CPE_TARGET_CYLINDER, 0};
+    if (params) prm = *params;
+    CPE_CHECK_ARG(exp_h && exp_v && joints && n_joints && rect && r0 && stage_status && g7 && gray && ws && xy && id && n_pts &&
+                  center && status && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096, "cpe_debug_lines: bad argument");
+    CPE_CHECK_ARG(prm.subpixel == 0 || (prm.subpixel_window >= 1 && prm.subpixel_window <= 13 && prm.subpixel_step > 0),
+                  "cpe_debug_lines: bad sub-pixel parameters");
+    CPE_CHECK_ARG((prm.target == CPE_TARGET_CYLINDER || prm.target == CPE_TARGET_PLANE) && prm.flags == 0 &&
+                  !(prm.target == CPE_TARGET_PLANE && prm.subpixel), "cpe_debug_lines: bad target, flags, or sub-pixel refinement of the planar target");
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_lines")) return rc;
+    const int planar = prm.target == CPE_TARGET_PLANE ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    FrameState *st = W.state();
+    RegionBuffers R = region_buffers(W, h, w);
+    MaskBuffers M = mask_buffers(W, R);
+    M.lab_h = W.at<int>(WS_LABELS); M.lab_v = W.at<int>(WS_LABELS_AUX);
+    uint8_t *const b7 = W.at<uint8_t>(WS_BLUR7);
+    const size_t N = (size_t)h * w, total = N * n;
+    int rc;
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, M.best_s, R.nrect);
+    CPE_KLAUNCH(k_debug_lines_state, dim3((n + 63) / 64), dim3(64), 0, s, st, n, (const int *)rect, (const int *)r0, (const int *)n_joints,
+                (const int *)stage_status);
+    CPE_CHECK_HIP(hipMemcpyAsync(M.exp_h, exp_h, total, hipMemcpyDeviceToDevice, s));
+    CPE_CHECK_HIP(hipMemcpyAsync(M.exp_v, exp_v, total, hipMemcpyDeviceToDevice, s));
+    CPE_CHECK_HIP(hipMemcpyAsync(b7, g7, total, hipMemcpyDeviceToDevice, s));
+    CPE_CHECK_HIP(hipMemcpyAsync(M.joints, joints, (size_t)n * MAXJ * 2 * sizeof(int), hipMemcpyDeviceToDevice, s));
+    CPE_KLAUNCH(k_debug_singletons, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1 << 16)), dim3(256), 0, s, M.lab_h, M.lab_v, N, total);
+    CPE_CHECK_LAUNCH("cpe_debug_lines");
+    if ((rc = ccl_unions(M.exp_h, n, h, w, WIN_REGION, M.lab_h, st, s)) != CPE_OK) return rc;
+    if ((rc = ccl_unions(M.exp_v, n, h, w, WIN_REGION, M.lab_v, st, s)) != CPE_OK) return rc;
+    if ((rc = lines_stage(M.lab_h, M.lab_v, M.exp_h, M.exp_v, b7, n, h, w, M.joints, st, W.at<void>(WS_LINES), xy, id, n_pts, center,
+                          gray, prm.subpixel, prm.subpixel_window, prm.subpixel_step, W.at<float>(WS_SUBPIX), std::max(h, w) + 128, s,
+                          planar)) != CPE_OK)
+        return rc;
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_finish, dim3((n + 63) / 64), dim3(64), 0, s, st, n, status, n_pts);
+    CPE_CHECK_LAUNCH("k_finish");
+    return CPE_OK;
+}

@@ -36,10 +36,10 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 109   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 110   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
-                             cpe_detect_results_pack; 109: cpe_debug_workspace_buffer) */
+                             cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -345,6 +345,34 @@ CPE_API int32_t cpe_debug_blob_region(const uint8_t *img, int32_t n, int32_t h, 
 CPE_API int32_t cpe_debug_masks(const uint8_t *binary, const uint8_t *gray, const uint8_t *mask_contour, const int32_t *rect,
                                 const int32_t *region_status, int32_t n, int32_t h, int32_t w, int32_t target, void *ws,
                                 size_t ws_bytes, void *stream);
+
+/* The lines stage of detect_grid on given inputs: the label lookup of the joints, the per-line fits, remove_label, the optional
+ * sub-pixel refinement, the intersections, clean_and_relabel, indexing_data and make_json's ordering (util_cylinder.py:376-1727;
+ * util_plane.py for CPE_TARGET_PLANE) -- what cpe_detect_grid_batch_ex runs after the masks stage: the unions of the two
+ * expanded masks inside the region rectangle + 2 px, then the lines kernel with the same sample capacity (max(h, w) + 128 per
+ * line), serially on `stream`.  Inputs (device memory):
+ *   exp_h, exp_v  u8[n,h,w]          the expanded masks (CPE_PLANE_EXP_H / _V); their non-zero pixels lie inside rect, as the
+ *                                    masks stage guarantees (a pixel farther than 2 px outside rect is its own component here)
+ *   joints        i32[n,CPE_MAXJ,2]  (x, y) of the joints inside rect, in the order the masks stage leaves them; any values
+ *                                    (a joint outside the frame or on background belongs to no line)
+ *   n_joints      i32[n]             0 .. CPE_MAXJ
+ *   rect          i32[n,4]           boundingRect (x, y, w, h) of the region, x, y >= 0 (it may reach past the right / bottom
+ *                                    edge: the label window is clipped to the frame, the rectangle test of the intersections
+ *                                    is not)
+ *   r0            i32[n]             circle_radius0 (>= 0)
+ *   stage_status  i32[n]             CPE_ST_OK, or the status an earlier stage ended the frame with (the frame is then skipped)
+ *   g7            u8[n,h,w]          the 7x7-blurred image indexing_data takes its window means from
+ *   gray          u8[n,h,w]          the grey frame (read by the sub-pixel refinement only)
+ * params: as for cpe_detect_grid_batch_ex (subpixel, subpixel_window 1 .. 13, subpixel_step, target; flags 0); NULL = defaults.
+ * xy, id, n_pts, center, status: the five tables of cpe_detect_grid_batch.  64 <= h, w <= 4096; ws:
+ * cpe_detect_workspace_bytes(n, h, w).  Afterwards the workspace is what it is after a detect call as far as this stage goes:
+ * the state record (status, n_rows, n_cols, overflow), the planes EXP_H / EXP_V, JOINTS, BLUR7, and the line tables that
+ * cpe_detect_line_tables and cpe_detect_results_sizes / _pack read.  Test / debugging aid. */
+CPE_API int32_t cpe_debug_lines(const uint8_t *exp_h, const uint8_t *exp_v, const int32_t *joints, const int32_t *n_joints,
+                                const int32_t *rect, const int32_t *r0, const int32_t *stage_status, const uint8_t *g7,
+                                const uint8_t *gray, int32_t n, int32_t h, int32_t w, const CpeDetectParams *params, void *ws,
+                                size_t ws_bytes, double *xy, int32_t *id, int32_t *n_pts, double *center, int32_t *status,
+                                void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Grid-point tables.  One table per image: xy f64[n,CPE_MAXP,2] pixel coordinates, id i32[n,CPE_MAXP,2]

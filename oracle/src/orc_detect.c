@@ -16,17 +16,11 @@ int orc_mask_roi_around_center(const uint8_t *hmask, const uint8_t *vmask, const
                                const uint8_t *gray, int h, int w, uint8_t *roi_h, uint8_t *roi_v, int *r0, int *spot);
 void orc_expand_line_roi(const uint8_t *mask_roi, const uint8_t *mask_contour, int h, int w, int kernel_size,
                          uint8_t *out, int *dbg);
-int orc_connected_components(const uint8_t *mask, int h, int w, int32_t *labels);
 void orc_blur7(const uint8_t *src, int h, int w, uint8_t *dst);
-void orc_group_points(const int *cent, int n, const int32_t *labels, int lh, int lw, int x_off, int y_off,
-                      orc_lineset *out);
-void orc_fit_lines(orc_lineset *ls, int is_row);
-void orc_remove_label(orc_lineset *rows, orc_lineset *cols);
-void orc_intersections(orc_lineset *rows, orc_lineset *cols, const int *rect);
-void orc_clean_and_relabel(orc_lineset *rows, orc_lineset *cols);
-int orc_subpixel_refine(const uint8_t *gray, int h, int w, orc_lineset *rows, orc_lineset *cols, int window, double step);
-int orc_index_points(const orc_lineset *rows, const orc_lineset *cols, const uint8_t *gauss7, int h, int w, int r0,
-                     double *center, double *xy, int *id, int cap);
+int orc_lines_core(const uint8_t *exp_h, const uint8_t *exp_v, int h, int w, const int *cyl, int ncyl, const int *rect, int r0,
+                   const uint8_t *gauss7, const uint8_t *gray, int subpixel, int sp_window, double sp_step, int sp_cap,
+                   int planar, double *center, double *xy, int *id, int cap, int *n_out, orc_lineset *rows, orc_lineset *cols,
+                   int *n_groups);
 
 typedef struct {
     /* optional intermediate images (h*w each) for stage-by-stage parity tests; any may be NULL */
@@ -93,8 +87,6 @@ static int detect_grid_impl(const uint8_t *gray, const uint8_t *bgr, int h, int 
     int capj = 1 << 16;
     int *cent = (int *)malloc((size_t)capj * 2 * sizeof(int)), *cyl = (int *)malloc((size_t)capj * 2 * sizeof(int));
     orc_lineset *rows = (orc_lineset *)malloc(sizeof(orc_lineset)), *cols = (orc_lineset *)malloc(sizeof(orc_lineset));
-    int32_t *lab_h = NULL, *lab_v = NULL;
-    uint8_t *crop = NULL;
     int st = 0;
     *n_out = 0;
     orc_capacity_overflow = 0;
@@ -124,41 +116,19 @@ static int detect_grid_impl(const uint8_t *gray, const uint8_t *bgr, int h, int 
         int ks = 91 + r0;
         orc_expand_line_roi(roi_h, mc, h, w, ks, exp_h, NULL);
         orc_expand_line_roi(roi_v, mc, h, w, ks, exp_v, NULL);
-        int x0 = rect[0], y0 = rect[1], cw = rect[2], ch = rect[3];
-        /* numpy slicing clips the crop at the image border */
-        if (x0 + cw > w) cw = w - x0;
-        if (y0 + ch > h) ch = h - y0;
-        crop = (uint8_t *)malloc((size_t)cw * ch);
-        lab_h = (int32_t *)malloc((size_t)cw * ch * sizeof(int32_t));
-        lab_v = (int32_t *)malloc((size_t)cw * ch * sizeof(int32_t));
-        for (int y = 0; y < ch; y++) memcpy(crop + (size_t)y * cw, exp_h + (size_t)(y0 + y) * w + x0, (size_t)cw);
-        orc_connected_components(crop, ch, cw, lab_h);
-        for (int y = 0; y < ch; y++) memcpy(crop + (size_t)y * cw, exp_v + (size_t)(y0 + y) * w + x0, (size_t)cw);
-        orc_connected_components(crop, ch, cw, lab_v);
-        orc_group_points(cyl, ncyl, lab_h, ch, cw, x0, y0, rows);
-        orc_group_points(cyl, ncyl, lab_v, ch, cw, x0, y0, cols);
-        orc_fit_lines(cols, 0);
-        orc_fit_lines(rows, 1);
-        orc_remove_label(rows, cols);
-        if (subpixel) st = orc_subpixel_refine(gray, h, w, rows, cols, sp_window, sp_step);
-        if (st == 0) {
-            orc_intersections(rows, cols, rect);
-            orc_clean_and_relabel(rows, cols);
-            if (bgr) {      /* :1433-1435: GaussianBlur((7,7)) of the colour image, channel by channel, then BGR2GRAY */
-                uint8_t *pl = (uint8_t *)malloc(N), *bl = (uint8_t *)malloc(3 * N);
-                for (int c = 0; c < 3; c++) {
-                    for (size_t i = 0; i < N; i++) pl[i] = bgr[3 * i + c];
-                    orc_blur7(pl, h, w, g7);
-                    for (size_t i = 0; i < N; i++) bl[3 * i + c] = g7[i];
-                }
-                orc_bgr2gray(bl, N, g7);
-                free(pl); free(bl);
-            } else orc_blur7(gray, h, w, g7);
-            int n = orc_index_points(rows, cols, g7, h, w, r0, center, xy, id, cap);
-            if (n < 0) st = -n;
-            else if (n > CPE_MAXP) orc_capacity_overflow = 1;   /* more grid points than a table of the boundary holds */
-            else *n_out = n;
-        }
+        if (bgr) {      /* :1433-1435: GaussianBlur((7,7)) of the colour image, channel by channel, then BGR2GRAY */
+            uint8_t *pl = (uint8_t *)malloc(N), *bl = (uint8_t *)malloc(3 * N);
+            for (int c = 0; c < 3; c++) {
+                for (size_t i = 0; i < N; i++) pl[i] = bgr[3 * i + c];
+                orc_blur7(pl, h, w, g7);
+                for (size_t i = 0; i < N; i++) bl[3 * i + c] = g7[i];
+            }
+            orc_bgr2gray(bl, N, g7);
+            free(pl); free(bl);
+        } else orc_blur7(gray, h, w, g7);
+        /* connectedComponents of the crops .. make_json's ordering (orc_lines_stage.c); no limit on the sub-pixel samples here */
+        st = orc_lines_core(exp_h, exp_v, h, w, cyl, ncyl, rect, r0, g7, gray, subpixel, sp_window, sp_step, 0, 0, center, xy, id,
+                            cap, n_out, rows, cols, NULL);
     }
     if (dbg) {
         if (dbg->binary) memcpy(dbg->binary, binary, N);
@@ -183,7 +153,7 @@ static int detect_grid_impl(const uint8_t *gray, const uint8_t *bgr, int h, int 
         if (dbg->cols_out) { if (have) memcpy(dbg->cols_out, cols, sizeof(orc_lineset)); else dbg->cols_out->nlines = 0; }
     }
     free(blurred); free(binary); free(hmask); free(vmask); free(mc); free(roi_h); free(roi_v); free(exp_h); free(exp_v);
-    free(g7); free(cent); free(cyl); free(rows); free(cols); free(lab_h); free(lab_v); free(crop);
+    free(g7); free(cent); free(cyl); free(rows); free(cols);
     if (orc_capacity_overflow) { st = ORC_ST_OVERFLOW; *n_out = 0; }   /* as the library: any exceeded capacity overrides the status */
     return st;
 }

@@ -33,9 +33,11 @@ int orc_mask_roi_around_center_ex(const uint8_t *hmask, const uint8_t *vmask, co
                                   int h, int w, uint8_t *roi_h, uint8_t *roi_v, int *r0, int *spot, int planar);
 void orc_expand_line_roi_ex(const uint8_t *mask_roi, const uint8_t *mask_contour, int h, int w, int kernel_size, int minp,
                             int maxp, uint8_t *out, int *dbg);
-int orc_connected_components(const uint8_t *mask, int h, int w, int32_t *labels);
 void orc_blur7(const uint8_t *src, int h, int w, uint8_t *dst);
-void orc_group_points(const int *cent, int n, const int32_t *labels, int lh, int lw, int x_off, int y_off, orc_lineset *out);
+int orc_lines_core(const uint8_t *exp_h, const uint8_t *exp_v, int h, int w, const int *cyl, int ncyl, const int *rect, int r0,
+                   const uint8_t *gauss7, const uint8_t *gray, int subpixel, int sp_window, double sp_step, int sp_cap,
+                   int planar, double *center, double *xy, int *id, int cap, int *n_out, orc_lineset *rows, orc_lineset *cols,
+                   int *n_groups);
 
 /* cv2.getStructuringElement(cv2.MORPH_ELLIPSE, (ks, ks)) */
 ORC_API void orc_ellipse_se(int ks, uint8_t *se)
@@ -405,8 +407,6 @@ ORC_API int orc_detect_grid_plane(const uint8_t *gray, int h, int w, double *cen
     int capj = 1 << 16;
     int *cent = (int *)malloc((size_t)capj * 2 * sizeof(int)), *cyl = (int *)malloc((size_t)capj * 2 * sizeof(int));
     orc_lineset *rows = (orc_lineset *)calloc(1, sizeof(orc_lineset)), *cols = (orc_lineset *)calloc(1, sizeof(orc_lineset));
-    int32_t *lab_h = NULL, *lab_v = NULL;
-    uint8_t *crop = NULL;
     *n_out = 0;
     orc_capacity_overflow = 0;
     orc_preprocess(gray, h, w, blurred, binary, NULL);
@@ -428,27 +428,9 @@ ORC_API int orc_detect_grid_plane(const uint8_t *gray, int h, int w, double *cen
     if (st == 0) {
         orc_expand_line_roi_ex(roi_h, mc, h, w, 201, 8, 700, exp_h, NULL);
         orc_expand_line_roi_ex(roi_v, mc, h, w, 201, 8, 700, exp_v, NULL);
-        int x0 = rect[0], y0 = rect[1], cw = rect[2], ch = rect[3];
-        if (x0 + cw > w) cw = w - x0;
-        if (y0 + ch > h) ch = h - y0;
-        crop = (uint8_t *)malloc((size_t)cw * ch);
-        lab_h = (int32_t *)malloc((size_t)cw * ch * sizeof(int32_t));
-        lab_v = (int32_t *)malloc((size_t)cw * ch * sizeof(int32_t));
-        for (int y = 0; y < ch; y++) memcpy(crop + (size_t)y * cw, exp_h + (size_t)(y0 + y) * w + x0, (size_t)cw);
-        orc_connected_components(crop, ch, cw, lab_h);
-        for (int y = 0; y < ch; y++) memcpy(crop + (size_t)y * cw, exp_v + (size_t)(y0 + y) * w + x0, (size_t)cw);
-        orc_connected_components(crop, ch, cw, lab_v);
-        orc_group_points(cyl, ncyl, lab_h, ch, cw, x0, y0, rows);
-        orc_group_points(cyl, ncyl, lab_v, ch, cw, x0, y0, cols);
-        orc_fit_lines_plane(rows, cols);
-        orc_intersections_plane(rows, cols, rect);
-        orc_clean_plane(rows);
-        orc_clean_plane(cols);
         orc_blur7(gray, h, w, g7);
-        int n = orc_index_points_plane(rows, cols, g7, h, w, r0, center, xy, id, cap);
-        if (n < 0) st = -n;
-        else if (n > CPE_MAXP) orc_capacity_overflow = 1;
-        else *n_out = n;
+        st = orc_lines_core(exp_h, exp_v, h, w, cyl, ncyl, rect, r0, g7, gray, 0, 7, 1.0, 0, 1, center, xy, id, cap, n_out, rows, cols,
+                            NULL);
     }
     if (dbg) {
         if (dbg->binary) memcpy(dbg->binary, binary, N);
@@ -470,7 +452,7 @@ ORC_API int orc_detect_grid_plane(const uint8_t *gray, int h, int w, double *cen
         dbg->n_keypoints = 0;
     }
     free(blurred); free(binary); free(hmask); free(vmask); free(mc); free(roi_h); free(roi_v); free(exp_h); free(exp_v);
-    free(g7); free(cent); free(cyl); free(rows); free(cols); free(lab_h); free(lab_v); free(crop);
+    free(g7); free(cent); free(cyl); free(rows); free(cols);
     if (orc_capacity_overflow) { st = ORC_ST_OVERFLOW; *n_out = 0; }
     return st;
 }

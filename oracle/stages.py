@@ -340,6 +340,32 @@ def subpixel_refine(gray, rows, cols, window=7, step=1.0):
     return lib().orc_subpixel_refine(_p(gray, C.c_uint8), h, w, C.byref(rows), C.byref(cols), window, C.c_double(step))
 
 
+def lines_stage(exp_h, exp_v, joints, rect, r0, g7, gray=None, subpixel=False, window=7, step=1.0, planar=False, sp_cap=None,
+                cap=4096):
+    """the lines stage on its own (orc_lines_stage.c: the body detect_grid runs after expand_line_roi): exp_h / exp_v u8
+    [h,w], joints (k,2) (x, y) already filtered to rect, rect (x, y, w, h), r0, g7 the 7x7-blurred image, gray (the sub-pixel
+    refinement's image; default g7).  sp_cap: samples per line of the refinement, default the library's max(h, w) + 128.
+    -> dict(status (6 where a capacity of include/cpe.h is exceeded), overflow, center, xy, id, rows / cols (LineSet as the
+    stage leaves them), n_rows, n_cols, n_groups (label groups per direction before any removal))"""
+    exp_h = _u8(exp_h); exp_v = _u8(exp_v); g7 = _u8(g7); h, w = exp_h.shape
+    gray = g7 if gray is None else _u8(gray)
+    assert exp_v.shape == (h, w) and g7.shape == (h, w) and gray.shape == (h, w)
+    j = np.ascontiguousarray(np.asarray(joints, np.int32).reshape(-1, 2))
+    r = (C.c_int * 4)(*[int(v) for v in rect])
+    center = np.zeros(2); xy = np.zeros((cap, 2)); ids = np.zeros((cap, 2), np.int32); n = C.c_int(0)
+    rows, cols = LineSet(), LineSet()
+    assert C.sizeof(rows) == lib().orc_lineset_size()
+    ng = (C.c_int * 2)(); ovf = C.c_int(0)
+    st = lib().orc_lines_stage(_p(exp_h, C.c_uint8), _p(exp_v, C.c_uint8), h, w, _p(j, C.c_int), len(j), r, int(r0),
+                               _p(g7, C.c_uint8), _p(gray, C.c_uint8), 1 if subpixel else 0, int(window), C.c_double(step),
+                               int(max(h, w) + 128 if sp_cap is None else sp_cap), 1 if planar else 0, _p(center, C.c_double),
+                               _p(xy, C.c_double), _p(ids, C.c_int), cap, C.byref(n), C.byref(rows), C.byref(cols), ng,
+                               C.byref(ovf))
+    have = st in (0, 3, 4)
+    return dict(status=st, overflow=ovf.value, center=center, xy=xy[:n.value].copy(), id=ids[:n.value].copy(), rows=rows, cols=cols,
+                n_rows=rows.nlines if have else 0, n_cols=cols.nlines if have else 0, n_groups=(ng[0], ng[1]))
+
+
 # ---------------------------------------------------------------- row f-2: planar-target variant (orc_plane.c)
 def fit_lines_plane(rows, cols):
     lib().orc_fit_lines_plane(C.byref(rows), C.byref(cols)); return rows, cols

@@ -12,7 +12,9 @@ import ctypes as C
 
 import numpy as np
 
-CPE_MAXJ, CPE_MAXP = 16384, 4096       # include/cpe.h
+from cpe_amd.fit import MAXP as CPE_MAXP        # include/cpe.h
+
+CPE_MAXJ = 16384                                # include/cpe.h
 
 
 def plane_frames(h, w, n, seed):
@@ -57,9 +59,9 @@ def colour_gauss7(bgr):
     return S.bgr2gray(np.stack([S.blur7(np.ascontiguousarray(bgr[..., c])) for c in range(3)], 2))
 
 
-def detect_grid_plane_bgr(bgr, cap=CPE_MAXP):
+def detect_grid_plane_bgr(bgr, cap=2 * CPE_MAXP):
     """orc_detect_grid_plane on a colour frame (see the module docstring) -> dict(status, center, xy, id, rect, r0, mask_contour,
-    gauss7, n_rows, n_cols)"""
+    gauss7, n_rows, n_cols).  cap: rows of the scratch table, more than CPE_MAXP so that a frame beyond the capacity is seen"""
     import oracle
     from oracle import stages as S
     lib = S.lib()
