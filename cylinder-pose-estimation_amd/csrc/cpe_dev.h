@@ -477,8 +477,8 @@ int outside_flood(const uint8_t *mask, int n, int h, int w, FrameState *st, Wind
 int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const RegionBuffers &B, FrameState *st, hipStream_t s,
                  const RegionSide *side, const uint8_t *lplane, const RegionProbe *probe);
 int region_stage_plane(const uint8_t *gray, int n, int h, int w, const RegionBuffers &B, FrameState *st, hipStream_t s);
-int clahe_front_probe(const uint8_t *gray, int n, int h, int w, int fused, const RegionBuffers &B, hipStream_t s, uint8_t *cl,
-                      uint32_t *planes, int *buckets, int *box);
+int clahe_front_probe(const uint8_t *gray, int n, int h, int w, int fused, int lab_lut, const RegionBuffers &B, hipStream_t s,
+                      uint8_t *cl, uint32_t *planes, int *buckets, int *box);
 
 // ---- masks.hip
 int joints_mask_stage(int n, int h, int w, const MaskBuffers &B, FrameState *st, hipStream_t s);

@@ -579,7 +579,30 @@ extern "C" int32_t cpe_debug_clahe_planes(const uint8_t *gray, int32_t n, int32_
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, W.at<unsigned long long>(WS_BEST_SPOT), R.nrect);
     CPE_CHECK_LAUNCH("k_state_init");
-    return clahe_front_probe(gray, n, h, w, fused, R, s, cl, planes, buckets, box);
+    return clahe_front_probe(gray, n, h, w, fused, 1, R, s, cl, planes, buckets, box);
+}
+
+// The same for true-colour frames: the L plane as detect_impl makes it (k_bgr2labl into the disc plane), then CLAHE without
+// the grey LAB-L table (tests)
+extern "C" int32_t cpe_debug_clahe_planes_bgr(const uint8_t *bgr, int32_t n, int32_t h, int32_t w, int32_t fused, void *ws,
+                                              size_t ws_bytes, uint8_t *L, uint8_t *cl, uint32_t *planes, int32_t *buckets,
+                                              int32_t *box, void *stream)
+{
+    CPE_CHECK_ARG(bgr && ws && L && cl && planes && buckets && box && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096,
+                  "cpe_debug_clahe_planes_bgr: bad argument");
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_clahe_planes_bgr")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    FrameState *st = W.state();
+    RegionBuffers R = region_buffers(W, h, w);
+    uint8_t *lplane = W.at<uint8_t>(WS_DISCS);
+    const size_t npx = (size_t)n * h * w;
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, W.at<unsigned long long>(WS_BEST_SPOT), R.nrect);
+    CPE_KLAUNCH(k_bgr2labl, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 1 << 16)), dim3(256), 0, s, bgr, npx, lplane);
+    CPE_CHECK_LAUNCH("cpe_debug_clahe_planes_bgr");
+    (void)hipMemcpyAsync(L, lplane, npx, hipMemcpyDeviceToDevice, s);
+    return clahe_front_probe(lplane, n, h, w, fused, 0, R, s, cl, planes, buckets, box);
 }
 
 namespace cpe { namespace {

@@ -2371,13 +2371,14 @@ int clahe_front(const uint8_t *gray, int n, int h, int w, double clip, int lab_l
     return CPE_OK;
 }
 
-// the CLAHE front end alone (cpe_debug_clahe_planes): B.cl, the 17 planes, bucket sizes i32[n,18] and box i32[n,4] copied out
-int clahe_front_probe(const uint8_t *gray, int n, int h, int w, int fused, const RegionBuffers &B, hipStream_t s, uint8_t *cl,
-                      uint32_t *planes, int *buckets, int *box)
+// the CLAHE front end alone (cpe_debug_clahe_planes, cpe_debug_clahe_planes_bgr): B.cl, the 17 planes, bucket sizes i32[n,18] and
+// box i32[n,4] copied out.  lab_lut as region_stage passes it: 1 grey frames, 0 `gray` is the L plane of colour frames
+int clahe_front_probe(const uint8_t *gray, int n, int h, int w, int fused, int lab_lut, const RegionBuffers &B, hipStream_t s,
+                      uint8_t *cl, uint32_t *planes, int *buckets, int *box)
 {
     bool done = false;
     int rc;
-    if ((rc = clahe_front(gray, n, h, w, 4.5, 1, false, B, s, fused != 0, &done)) != CPE_OK) return rc;
+    if ((rc = clahe_front(gray, n, h, w, 4.5, lab_lut, false, B, s, fused != 0, &done)) != CPE_OK) return rc;
     if (!done && (rc = build_bitplanes(B.cl, n, h, w, 50, 10, NTHR, B.bits, s)) != CPE_OK) return rc;
     CPE_LAUNCH_BEGIN();
     (void)hipMemcpyAsync(cl, B.cl, (size_t)n * h * w, hipMemcpyDeviceToDevice, s);

@@ -36,10 +36,11 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 110   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 111   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
-                             cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines) */
+                             cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
+                             111: cpe_debug_clahe_planes_bgr) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -314,6 +315,13 @@ CPE_API int32_t cpe_debug_external_components(const uint8_t *mask, int32_t n, in
  * bucket, 0 unused), box i32[n,4] (x0, y0, x1, y1 of the pixels > 50).  Test / debugging aid. */
 CPE_API int32_t cpe_debug_clahe_planes(const uint8_t *gray, int32_t n, int32_t h, int32_t w, int32_t fused, void *ws, size_t ws_bytes,
                                        uint8_t *cl, uint32_t *planes, int32_t *buckets, int32_t *box, void *stream);
+
+/* The same front end for true-colour frames bgr u8[n,h,w,3]: the L channel of BGR2LAB as cpe_detect_grid_bgr_batch_ex makes it
+ * (copied out: L u8[n,h,w]), then CLAHE of that plane (no grey LAB-L table) and the planes, bucket sizes and box as above.
+ * Test / debugging aid. */
+CPE_API int32_t cpe_debug_clahe_planes_bgr(const uint8_t *bgr, int32_t n, int32_t h, int32_t w, int32_t fused, void *ws,
+                                           size_t ws_bytes, uint8_t *L, uint8_t *cl, uint32_t *planes, int32_t *buckets,
+                                           int32_t *box, void *stream);
 
 /* The blob stage of detect_largest_blob (util_cylinder.py:1830-1899) on a given image: the library's region stage, with
  * img u8[n,h,w] (64 <= h,w <= 4096) as the image its SimpleBlobDetector sweeps -- LAB-L and CLAHE are replaced by an identity

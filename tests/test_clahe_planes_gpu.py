@@ -7,9 +7,15 @@ the frame, bucket sizes, box of the pixels > 50.
 Sizes: 1920x1200 (the product's frames), 1920x1203 (a partial last tile row; CLAHE pads the frame to 1924 columns),
 656 wide (a multiple of 16 but not of 64), 640x480 (the smoke test's frames), 801 wide (rows not 16-byte aligned: both
 paths are the byte-level ones).  Frames are bright up to their borders, so the box touches the frame's edges."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from clahe_cases import expected as _expected  # noqa: E402  (planes, bucket sizes and box as a CLAHE image defines them)
 
 NTHR = 17
 
@@ -43,28 +49,6 @@ def _run(cpe, gpu, frames, fused):
                                            torch.cuda.current_stream().cuda_stream), 'cpe_debug_clahe_planes')
     torch.cuda.synchronize()
     return cl.cpu().numpy(), planes.cpu().numpy().view(np.uint64), buckets.cpu().numpy(), box.cpu().numpy()
-
-
-def _expected(cl):
-    """planes, bucket sizes and box as the CLAHE image defines them"""
-    n, h, w = cl.shape
-    th8, chunks = (h + 7) // 8, (w + 63) // 64
-    planes = np.zeros((n, NTHR, th8, chunks + 2, 8), np.uint64)
-    pad = np.zeros((n, th8 * 8, chunks * 64), np.uint8)
-    pad[:, :h, :w] = cl
-    for t in range(NTHR):
-        bits = (pad > 50 + 10 * t).reshape(n, th8, 8, chunks, 64)
-        words = np.packbits(bits, axis=-1, bitorder='little').view('<u8')[..., 0]   # (n, th8, 8, chunks)
-        planes[:, t, :, 1:chunks + 1, :] = words.transpose(0, 1, 3, 2)
-    buckets = np.zeros((n, NTHR + 1), np.int32)
-    box = np.zeros((n, 4), np.int32)
-    for f in range(n):
-        v = cl[f].astype(np.int32)
-        lev = np.where(v <= 50, 0, np.minimum((v - 41) // 10, 17))
-        buckets[f, 1:] = np.bincount(lev.ravel(), minlength=NTHR + 1)[1:]
-        ys, xs = np.nonzero(v > 50)
-        box[f] = [xs.min(), ys.min(), xs.max(), ys.max()] if len(xs) else [2 ** 31 - 1, 2 ** 31 - 1, -1, -1]
-    return planes, buckets, box
 
 
 @pytest.mark.gpu
