@@ -617,11 +617,21 @@ __device__ void fit_init(const double *sP, int n, double R, int lane, double *sD
     f0_out = cyl_objective(x0, P, R, lane);
 }
 
-// fminsearch (MATLAB order) from x0
-__device__ void fit_nm(const double *sP, int n, double R, int lane, double tolx, double tolf, int maxiter, int maxfun,
-                       const double *x0, double f0, double *xf, double &ffinal, int &itercount, int &func_evals)
+// the objective of the per-frame fit as fit_nm_on takes it
+struct CylObjective {
+    Pts P;
+    double R;
+    int lane;
+    __device__ double operator()(const double *x) const { return cyl_objective(x, P, R, lane); }
+};
+
+// fminsearch (MATLAB order) from x0 on any objective `double obj(const double *x)` (wave-uniform result); one body for the
+// per-frame fit (CylObjective) and the multi-frame fit (MultiObjective, which holds workgroup barriers: every wave of its
+// workgroup runs this loop on the same numbers, so all of them call obj the same number of times)
+template <class Obj>
+__device__ __forceinline__ void fit_nm_on(Obj &obj, double tolx, double tolf, int maxiter, int maxfun, const double *x0, double f0,
+                                          double *xf, double &ffinal, int &itercount, int &func_evals)
 {
-    Pts P{sP, n};
     // ---- fminsearch (MATLAB order).  simplex is wave-uniform, kept in registers.
     constexpr int N = 6;
     double v[N + 1][N], fv[N + 1];
@@ -634,7 +644,7 @@ __device__ void fit_nm(const double *sP, int n, double R, int lane, double tolx,
         for (int k = 0; k < N; k++) v[j + 1][k] = x0[k];
         if (v[j + 1][j] != 0) v[j + 1][j] = (1 + 0.05) * v[j + 1][j];
         else v[j + 1][j] = 0.00025;
-        fv[j + 1] = cyl_objective(v[j + 1], P, R, lane);
+        fv[j + 1] = obj(v[j + 1]);
     }
     func_evals = N + 1;
     itercount = 1;
@@ -679,13 +689,13 @@ __device__ void fit_nm(const double *sP, int n, double R, int lane, double tolx,
         }
 #pragma unroll
         for (int k = 0; k < N; k++) xr[k] = 2.0 * xbar[k] - 1.0 * v[N][k];
-        double fxr = cyl_objective(xr, P, R, lane);
+        double fxr = obj(xr);
         func_evals++;
         bool shrink = false;
         if (fxr < fv[0]) {
 #pragma unroll
             for (int k = 0; k < N; k++) xt[k] = 3.0 * xbar[k] - 2.0 * v[N][k];
-            double fxe = cyl_objective(xt, P, R, lane);
+            double fxe = obj(xt);
             func_evals++;
             if (fxe < fxr) {
 #pragma unroll
@@ -703,7 +713,7 @@ __device__ void fit_nm(const double *sP, int n, double R, int lane, double tolx,
         } else if (fxr < fv[N]) {
 #pragma unroll
             for (int k = 0; k < N; k++) xt[k] = 1.5 * xbar[k] - 0.5 * v[N][k];
-            double fxc = cyl_objective(xt, P, R, lane);
+            double fxc = obj(xt);
             func_evals++;
             if (fxc <= fxr) {
 #pragma unroll
@@ -713,7 +723,7 @@ __device__ void fit_nm(const double *sP, int n, double R, int lane, double tolx,
         } else {
 #pragma unroll
             for (int k = 0; k < N; k++) xt[k] = 0.5 * xbar[k] + 0.5 * v[N][k];
-            double fxcc = cyl_objective(xt, P, R, lane);
+            double fxcc = obj(xt);
             func_evals++;
             if (fxcc < fv[N]) {
 #pragma unroll
@@ -726,7 +736,7 @@ __device__ void fit_nm(const double *sP, int n, double R, int lane, double tolx,
             for (int j = 1; j <= N; j++) {
 #pragma unroll
                 for (int k = 0; k < N; k++) v[j][k] = v[0][k] + 0.5 * (v[j][k] - v[0][k]);
-                fv[j] = cyl_objective(v[j], P, R, lane);
+                fv[j] = obj(v[j]);
             }
             func_evals += N;
         }
@@ -739,6 +749,14 @@ __device__ void fit_nm(const double *sP, int n, double R, int lane, double tolx,
 #pragma unroll
     for (int k = 0; k < 6; k++) xf[k] = v[0][k];
     ffinal = fv[0];
+}
+
+// the per-frame fit: fminsearch on dist() of fitCylinderWPts3.m:44-49
+__device__ void fit_nm(const double *sP, int n, double R, int lane, double tolx, double tolf, int maxiter, int maxfun,
+                       const double *x0, double f0, double *xf, double &ffinal, int &itercount, int &func_evals)
+{
+    CylObjective obj{Pts{sP, n}, R, lane};
+    fit_nm_on(obj, tolx, tolf, maxiter, maxfun, x0, f0, xf, ffinal, itercount, func_evals);
 }
 
 __device__ void fit_lm(const double *sP, int n, double R, int lane, double tolx, double tolf, int maxiter,
@@ -1210,20 +1228,22 @@ extern "C" int32_t cpe_fit_cylinder_ransac_batch(const double *X, const int32_t 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Row f-1: objective of the multi-frame AGV-pose fit, utils/fitCylinderWPts3sAngs.m:82-94 (`dist`):
+// Row f-1: the multi-frame AGV-pose fit, utils/fitCylinderWPts3sAngs.m.  Its objective (:82-94, `dist`):
 //   v = sum_i mean((d_i - R)^2),  d_i = getDistPts3ToLine(Pts3s{i}, line of T * TAGVcyls{i})
-// One wavefront per frame computes its term (same 64-lane reduction tree as the per-frame fit); the host-side
-// Nelder-Mead (cpe_amd/multiframe.py, MATLAB fminsearch order) adds the F terms in frame order.
+// k_multi_frame_terms : one wavefront per frame computes its term (same 64-lane reduction tree as the per-frame fit) for a
+//                       Nelder-Mead driven from the host (cpe_amd/multiframe.py), which adds the F terms in frame order.
+// k_multi_frame_fit   : the whole of fitCylinderWPts3sAngs for one group of frames per workgroup -- initial pose (:40-69),
+//                       fminsearch (fit_nm_on, the body of the per-frame fit) on the same terms, vec2T of the result.
+// k_pose_vec2T/T2vec  : vec2T.m / T2vec.m for a batch of poses, the device functions the fit itself uses.
 namespace {
-__global__ __launch_bounds__(64) void k_multi_frame_terms(const double *__restrict__ X, const int *__restrict__ cnt,
-                                                          const double *__restrict__ TAGV, const double *__restrict__ T,
-                                                          double R, double *__restrict__ terms)
+// one frame's term: mean((d - R)^2) over its points; T row-major vec2T(agvPose), A row-major getTAGVcyl of the frame.
+// cnt is clamped to [0, MAXP]; a frame without points has the term 0.
+__device__ __forceinline__ double multi_frame_term(const double *__restrict__ P, int cnt, const double *__restrict__ A, const double *T,
+                                                   double R, int lane)
 {
-    const int f = blockIdx.x, lane = threadIdx.x;
-    const int n = min(max(cnt[f], 0), MAXP);
-    if (n == 0) { if (lane == 0) terms[f] = 0.0; return; }
+    const int n = min(max(cnt, 0), MAXP);
+    if (n == 0) return 0.0;
     // T_C1_cyl = T * TAGVcyls{i}: only column 2 (axis) and column 4 (origin) are used
-    const double *A = TAGV + 16 * (size_t)f;
     double org[3], dy[3];
 #pragma unroll
     for (int r = 0; r < 3; r++) {
@@ -1233,7 +1253,6 @@ __global__ __launch_bounds__(64) void k_multi_frame_terms(const double *__restri
     double p2[3] = {org[0] + dy[0], org[1] + dy[1], org[2] + dy[2]};
     double v[3] = {p2[0] - org[0], p2[1] - org[1], p2[2] - org[2]};
     double nv2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
-    const double *P = X + (size_t)f * MAXP * 3;
     double acc = 0.0;
     for (int k = lane; k < n; k += 64) {
         double d = dist_pt_line(P + 3 * k, org, v, nv2);
@@ -1241,7 +1260,317 @@ __global__ __launch_bounds__(64) void k_multi_frame_terms(const double *__restri
         acc = acc + w * w;
     }
     acc = wave_sum(acc);
-    if (lane == 0) terms[f] = acc / (double)n;
+    return acc / (double)n;
+}
+
+__global__ __launch_bounds__(64) void k_multi_frame_terms(const double *__restrict__ X, const int *__restrict__ cnt,
+                                                          const double *__restrict__ TAGV, const double *__restrict__ T,
+                                                          double R, double *__restrict__ terms)
+{
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const double term = multi_frame_term(X + (size_t)f * MAXP * 3, cnt[f], TAGV + 16 * (size_t)f, T, R, lane);
+    if (lane == 0) terms[f] = term;
+}
+
+// vec2T.m: rotvec2mat3d (premultiply form) of x[0..2] beside the translation x[3..5], row-major 4x4.  sin / cos are the
+// device library's; everything else in the order of oracle/src/orc_fit.c::rotvec2mat.
+__device__ __forceinline__ void pose_vec2T(const double *x, double *T)
+{
+    const double th = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+    if (th < 1e-6) {
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int q = 0; q < 3; q++) T[r * 4 + q] = (r == q) ? 1.0 : 0.0;
+    } else {
+        const double u[3] = {x[0] / th, x[1] / th, x[2] / th};
+        const double c = cos(th), s = sin(th), t = 1 - c;
+        const double K[9] = {0, -u[2], u[1], u[2], 0, -u[0], -u[1], u[0], 0};
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int q = 0; q < 3; q++) T[r * 4 + q] = (c * (r == q ? 1.0 : 0.0) + t * (u[r] * u[q])) + s * K[r * 3 + q];
+    }
+#pragma unroll
+    for (int r = 0; r < 3; r++) T[r * 4 + 3] = x[3 + r];
+    T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
+}
+
+// the near-pi branch of rotmat2vec3d with `a` the largest diagonal entry (constant indices: the arrays stay in registers)
+template <int a>
+__device__ __forceinline__ void rotvec_near_pi(const double *T, double th, double *v)
+{
+    constexpr int b = (a + 1) % 3, c = (a + 2) % 3;
+    const double s = sqrt(T[a * 5] - T[b * 5] - T[c * 5] + 1);
+    double w[3];
+    w[a] = s / 2;
+    w[b] = (T[b * 4 + a] + T[a * 4 + b]) / (2 * s);
+    w[c] = (T[c * 4 + a] + T[a * 4 + c]) / (2 * s);
+    const double nw = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+#pragma unroll
+    for (int k = 0; k < 3; k++) v[k] = th * w[k] / nw;
+}
+
+// T2vec.m: rotmat2vec3d (without its SVD re-orthogonalisation) of the rotation of a row-major 4x4, then the translation.
+// Three branches as oracle/src/orc_fit.c::mat2rotvec: sin(theta) >= 1e-4, theta near 0, theta near pi.  acos / sin are the
+// device library's.
+__device__ __forceinline__ void pose_T2vec(const double *T, double *x)
+{
+    const double t = (T[0] + T[5]) + T[10];
+    double ca = (t - 1) / 2;
+    if (ca > 1) ca = 1;
+    if (ca < -1) ca = -1;
+    const double th = acos(ca);
+    const double r[3] = {T[9] - T[6], T[2] - T[8], T[4] - T[1]};
+    const double sth = sin(th);
+    if (sth >= 1e-4) {
+        const double vth = 1 / (2 * sth);
+#pragma unroll
+        for (int k = 0; k < 3; k++) x[k] = th * (r[k] * vth);
+    } else if (t - 1 > 0) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) x[k] = (.5 - (t - 3) / 12) * r[k];
+    } else {
+        int a = 0;
+        double daa = T[0];
+        if (T[5] > daa) { a = 1; daa = T[5]; }
+        if (T[10] > daa) a = 2;
+        if (a == 0) rotvec_near_pi<0>(T, th, x);
+        else if (a == 1) rotvec_near_pi<1>(T, th, x);
+        else rotvec_near_pi<2>(T, th, x);
+    }
+#pragma unroll
+    for (int r_ = 0; r_ < 3; r_++) x[3 + r_] = T[r_ * 4 + 3];
+}
+
+__device__ __forceinline__ void cross3(const double *a, const double *b, double *o)
+{
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// cylParams{i} of fitCylinderWPts3sAngs.m:40-47: the 2x6 [cylParams0; cylParams] indexed linearly (the reproduced quirk of
+// applyCylParamsPrior.m:6-7), then applyCylParamsPrior with ymin over the frame's n >= 1 points (a wave min)
+__device__ __forceinline__ void multi_prior(const double *__restrict__ M, const double *__restrict__ P, int n, int lane, double *cp)
+{
+    double ymin = DBL_MAX;
+    for (int k = lane; k < n; k += 64) ymin = fmin(ymin, P[3 * k + 1]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) ymin = fmin(ymin, __shfl_xor(ymin, off, 64));
+    const double o[3] = {M[0], M[6], M[1]};
+    double d[3] = {M[7], M[2], M[8]};
+    if (d[1] < 0) { d[0] = -d[0]; d[1] = -d[1]; d[2] = -d[2]; }
+    double t = 0;
+    if (!(fabs(d[1]) < DBL_EPSILON)) t = (ymin - o[1]) / d[1];
+#pragma unroll
+    for (int c = 0; c < 3; c++) { cp[c] = o[c] + t * d[c]; cp[3 + c] = d[c]; }
+}
+
+// T0 of fitCylinderWPts3sAngs.m:48-69 as a pose vector: R = [dir1 en c1] / [y1 nd c2] by Gaussian elimination with row
+// pivoting on B' R' = A' (the order of oracle/src/orc_fit.c::orc_multi_init and multiframe.initial_pose), t = origin1 - R p1.
+// cp0 / cp1: multi_prior of the first two frames, A1 / A2 their getTAGVcyl.  Row swaps are written out with constant
+// indices so that the 3x3 systems stay in registers.
+__device__ __forceinline__ void multi_init(const double *cp0, const double *cp1, const double *__restrict__ A1,
+                                           const double *__restrict__ A2, double *x0)
+{
+    const double p1[3] = {A1[3], A1[7], A1[11]}, p2[3] = {A2[3], A2[7], A2[11]};
+    const double y1[3] = {A1[1], A1[5], A1[9]};
+    const double d12[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
+    double nd[3], en[3], c1[3], c2[3];
+    cross3(y1, d12, nd);
+    const double nn = sqrt((nd[0] * nd[0] + nd[1] * nd[1]) + nd[2] * nd[2]);
+#pragma unroll
+    for (int k = 0; k < 3; k++) nd[k] = nd[k] / nn;
+    const double ed12[3] = {cp1[0] - cp0[0], cp1[1] - cp0[1], cp1[2] - cp0[2]};
+    const double dir1[3] = {cp0[3], cp0[4], cp0[5]};
+    cross3(dir1, ed12, en);
+    const double ne = sqrt((en[0] * en[0] + en[1] * en[1]) + en[2] * en[2]);
+#pragma unroll
+    for (int k = 0; k < 3; k++) en[k] = en[k] / ne;
+    cross3(dir1, en, c1);
+    cross3(y1, nd, c2);
+    double Bt[9] = {y1[0], y1[1], y1[2], nd[0], nd[1], nd[2], c2[0], c2[1], c2[2]};
+    double At[9] = {dir1[0], dir1[1], dir1[2], en[0], en[1], en[2], c1[0], c1[1], c1[2]};
+#define SWAP_ROWS(a, b)                                                              \
+    _Pragma("unroll") for (int k = 0; k < 3; k++) {                                  \
+        double t_ = Bt[(a) * 3 + k]; Bt[(a) * 3 + k] = Bt[(b) * 3 + k]; Bt[(b) * 3 + k] = t_; \
+        t_ = At[(a) * 3 + k]; At[(a) * 3 + k] = At[(b) * 3 + k]; At[(b) * 3 + k] = t_; \
+    }
+#define ELIMINATE(c)                                                                 \
+    _Pragma("unroll") for (int r = (c) + 1; r < 3; r++) {                            \
+        const double f = Bt[r * 3 + (c)] / Bt[(c) * 3 + (c)];                        \
+        _Pragma("unroll") for (int k = (c); k < 3; k++) Bt[r * 3 + k] = Bt[r * 3 + k] - f * Bt[(c) * 3 + k]; \
+        _Pragma("unroll") for (int k = 0; k < 3; k++) At[r * 3 + k] = At[r * 3 + k] - f * At[(c) * 3 + k]; \
+    }
+    {   // column 0: pivot = first row of the largest |.|
+        const bool p1_ = fabs(Bt[3]) > fabs(Bt[0]);
+        const bool p2_ = fabs(Bt[6]) > fabs(p1_ ? Bt[3] : Bt[0]);
+        if (p2_) { SWAP_ROWS(0, 2) } else if (p1_) { SWAP_ROWS(0, 1) }
+        ELIMINATE(0)
+    }
+    if (fabs(Bt[7]) > fabs(Bt[4])) { SWAP_ROWS(1, 2) }
+    ELIMINATE(1)
+#undef SWAP_ROWS
+#undef ELIMINATE
+    double Rt[9];
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int r = 2; r >= 0; r--) {
+            double s = At[r * 3 + k];
+#pragma unroll
+            for (int q = r + 1; q < 3; q++) s = s - Bt[r * 3 + q] * Rt[q * 3 + k];
+            Rt[r * 3 + k] = s / Bt[r * 3 + r];
+        }
+    double T0[16];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) T0[r * 4 + c] = Rt[c * 3 + r];
+        const double s = (T0[r * 4] * p1[0] + T0[r * 4 + 1] * p1[1]) + T0[r * 4 + 2] * p1[2];
+        T0[r * 4 + 3] = cp0[r] - s;
+    }
+    T0[12] = 0; T0[13] = 0; T0[14] = 0; T0[15] = 1;
+    pose_T2vec(T0, x0);
+}
+
+constexpr int MF_WAVES = 4;               // wavefronts of a k_multi_frame_fit workgroup (512 VGPRs each: the simplex stays in registers)
+constexpr int MF_MAXF = CPE_MULTI_MAXF;   // kept frames of one group
+
+// dist() of fitCylinderWPts3sAngs.m:82-94 for a workgroup of MF_WAVES wavefronts that all evaluate the same pose: wave w
+// computes the terms of kept frames w, w + MF_WAVES, ... (multi_frame_term: the bits of k_multi_frame_terms) into LDS, one
+// barrier, then every wave adds the nk terms in kept-frame order.  The terms alternate between two LDS rows, so one barrier
+// per evaluation is enough: a wave writes row p again only after the barrier of the evaluation in between, which no wave
+// passes before all of them have read row p.  EVERY wave of the workgroup must make the same sequence of calls.
+struct MultiObjective {
+    const double *X;
+    const int *cnt;
+    const double *TAGV;
+    double R;
+    const int *sIdx;   // LDS, kept frames in order
+    double *sTerms;    // LDS, [2][MF_MAXF]
+    int nk, wave, lane, row;
+    __device__ double operator()(const double *x)
+    {
+        double T[16];
+        pose_vec2T(x, T);
+        double *t = sTerms + row * MF_MAXF;
+        row ^= 1;
+        for (int k = wave; k < nk; k += MF_WAVES) {
+            const int f = sIdx[k];
+            const double term = multi_frame_term(X + (size_t)f * MAXP * 3, cnt[f], TAGV + 16 * (size_t)f, T, R, lane);
+            if (lane == 0) t[k] = term;
+        }
+        __syncthreads();
+        double v = 0.0;
+        for (int k = 0; k < nk; k++) v = v + t[k];   // v = v + (vi*vi')/length(vi), :92
+        return v;
+    }
+};
+
+// a group that is not fitted: its status, every other output zero
+__device__ void multi_write_failed(int g, int status, double *__restrict__ o_x0, double *__restrict__ o_x, double *__restrict__ o_T,
+                                   double *__restrict__ o_fvals, int *__restrict__ o_iters, int *__restrict__ o_nused,
+                                   int *__restrict__ o_status)
+{
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 6; k++) { o_x0[6 * g + k] = 0; o_x[6 * g + k] = 0; }
+        for (int k = 0; k < 16; k++) o_T[16 * g + k] = 0;
+        o_fvals[2 * g] = 0; o_fvals[2 * g + 1] = 0;
+        o_iters[2 * g] = 0; o_iters[2 * g + 1] = 0;
+        o_nused[g] = 0;
+        o_status[g] = status;
+    }
+}
+
+// fitCylinderWPts3sAngs for group g = blockIdx.x: frames [group_start[g], group_start[g+1]) with frame_ok != 0.
+// Barriers: one after the frame list, one per objective evaluation.  Every wave runs the same code on the same numbers --
+// the frame list and the terms come from LDS, everything else each wave computes for itself, and the arithmetic is
+// deterministic -- so every branch below, the simplex's included, goes the same way in all MF_WAVES waves and they execute
+// the same barriers.  No barrier stands under a condition that depends on the wave or the lane.
+__global__ __launch_bounds__(64 * MF_WAVES) void k_multi_frame_fit(
+    const double *__restrict__ X, const int *__restrict__ cnt, const double *__restrict__ TAGV, const double *__restrict__ cyl_raw,
+    const int *__restrict__ frame_ok, const int *__restrict__ group_start, int n, double R, double tolx, double tolf, int maxiter,
+    int maxfun, const double *__restrict__ x0_in, double *__restrict__ o_x0, double *__restrict__ o_x, double *__restrict__ o_T,
+    double *__restrict__ o_fvals, int *__restrict__ o_iters, int *__restrict__ o_nused, int *__restrict__ o_status)
+{
+    __builtin_amdgcn_s_setprio(3);   // a long chain of dependent f64 operations on one CU (see k_fit_cylinder)
+    __shared__ int sIdx[MF_MAXF];
+    __shared__ double sTerms[2 * MF_MAXF];
+    __shared__ int sNk;
+    const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int a = group_start[g], b = group_start[g + 1];
+    const bool range_ok = 0 <= a && a <= b && b <= n;
+    if (wave == 0) {   // kept frames, in order; counted past MF_MAXF, stored up to it
+        int nk = 0;
+        if (range_ok)
+            for (long long base = a; base < b; base += 64) {
+                const long long f = base + lane;
+                const bool keep = f < b && (frame_ok == nullptr || frame_ok[f] != 0);
+                const unsigned long long bal = __ballot(keep);
+                const int pos = nk + __popcll(bal & ((1ull << lane) - 1ull));
+                if (keep && pos < MF_MAXF) sIdx[pos] = (int)f;
+                nk += __popcll(bal);
+            }
+        if (lane == 0) sNk = nk;
+    }
+    __syncthreads();
+    const int nk = sNk;
+    if (!range_ok || nk > MF_MAXF) { multi_write_failed(g, CPE_ST_OVERFLOW, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    if (nk < 2) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }   // assert(nAngles >= 2), :29
+    const int fa = sIdx[0], fb = sIdx[1];
+    const int na = min(max(cnt[fa], 0), MAXP), nb = min(max(cnt[fb], 0), MAXP);
+    if (na < 1 || nb < 1) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    double x0[6];
+    if (x0_in != nullptr) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) x0[k] = x0_in[6 * (size_t)g + k];
+    } else {
+        double cp0[6], cp1[6];
+        multi_prior(cyl_raw + 12 * (size_t)fa, X + (size_t)fa * MAXP * 3, na, lane, cp0);
+        multi_prior(cyl_raw + 12 * (size_t)fb, X + (size_t)fb * MAXP * 3, nb, lane, cp1);
+        multi_init(cp0, cp1, TAGV + 16 * (size_t)fa, TAGV + 16 * (size_t)fb, x0);
+    }
+    MultiObjective obj{X, cnt, TAGV, R, sIdx, sTerms, nk, wave, lane, 0};
+    const double f0 = obj(x0);
+    if (!fit_finite(x0, f0)) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    double xf[6], ffinal;
+    int itercount, func_evals;
+    fit_nm_on(obj, tolx, tolf, maxiter, maxfun, x0, f0, xf, ffinal, itercount, func_evals);
+    if (!fit_finite(xf, ffinal)) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    if (threadIdx.x == 0) {
+        double T[16];
+        pose_vec2T(xf, T);
+        for (int k = 0; k < 6; k++) { o_x0[6 * g + k] = x0[k]; o_x[6 * g + k] = xf[k]; }
+        for (int k = 0; k < 16; k++) o_T[16 * g + k] = T[k];
+        o_fvals[2 * g] = f0; o_fvals[2 * g + 1] = ffinal;
+        o_iters[2 * g] = itercount; o_iters[2 * g + 1] = func_evals;
+        o_nused[g] = nk;
+        o_status[g] = CPE_ST_OK;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_pose_vec2T(const double *__restrict__ x, int n, double *__restrict__ T)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    double xi[6], Ti[16];
+#pragma unroll
+    for (int k = 0; k < 6; k++) xi[k] = x[6 * (size_t)i + k];
+    pose_vec2T(xi, Ti);
+#pragma unroll
+    for (int k = 0; k < 16; k++) T[16 * (size_t)i + k] = Ti[k];
+}
+
+__global__ __launch_bounds__(64) void k_pose_T2vec(const double *__restrict__ T, int n, double *__restrict__ x)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    double Ti[16], xi[6];
+#pragma unroll
+    for (int k = 0; k < 16; k++) Ti[k] = T[16 * (size_t)i + k];
+    pose_T2vec(Ti, xi);
+#pragma unroll
+    for (int k = 0; k < 6; k++) x[6 * (size_t)i + k] = xi[k];
 }
 }  // namespace
 
@@ -1253,5 +1582,48 @@ extern "C" int32_t cpe_multi_frame_terms(const double *X, const int32_t *cnt, in
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_multi_frame_terms, dim3(n), dim3(64), 0, (hipStream_t)stream, X, cnt, TAGVcyl, T, radius, terms);
     CPE_CHECK_LAUNCH("k_multi_frame_terms");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_multi_frame_fit_batch(const double *X, const int32_t *cnt, const double *TAGVcyl, const double *cyl_raw,
+                                             const int32_t *frame_ok, const int32_t *group_start, int32_t G, int32_t n, double radius,
+                                             const CpeFitParams *params, const double *x0_in, double *x0, double *x, double *T,
+                                             double *fvals, int32_t *iters, int32_t *n_used, int32_t *status, void *stream)
+{
+    CPE_CHECK_ARG(X && cnt && TAGVcyl && group_start && x0 && x && T && fvals && iters && n_used && status,
+                  "cpe_multi_frame_fit_batch: null pointer");
+    CPE_CHECK_ARG(cyl_raw || x0_in, "cpe_multi_frame_fit_batch: cyl_raw may be NULL only beside x0_in");
+    CPE_CHECK_ARG(G >= 0 && n >= 0, "cpe_multi_frame_fit_batch: G < 0 or n < 0");
+    CpeFitParams p = {1e-5, 1e-5, 100000, 100000, CPE_FIT_NELDER_MEAD, 0};   // fitCylinderWPts3sAngs.m:75
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.tol_x >= 0 && p.tol_f >= 0 && p.max_iter > 0 && p.max_fun_evals > 0, "cpe_multi_frame_fit_batch: bad CpeFitParams");
+    CPE_CHECK_ARG(p.mode == CPE_FIT_NELDER_MEAD, "cpe_multi_frame_fit_batch: mode %d (the multi-frame fit is Nelder-Mead only)", p.mode);
+    if (G == 0) return CPE_OK;
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_multi_frame_fit, dim3(G), dim3(64 * MF_WAVES), 0, (hipStream_t)stream, X, cnt, TAGVcyl, cyl_raw, frame_ok, group_start,
+                n, radius, p.tol_x, p.tol_f, p.max_iter, p.max_fun_evals, x0_in, x0, x, T, fvals, iters, n_used, status);
+    CPE_CHECK_LAUNCH("k_multi_frame_fit");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_pose_vec2T_batch(const double *x, int32_t n, double *T, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_pose_vec2T_batch: n < 0");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(x && T, "cpe_pose_vec2T_batch: null pointer");
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_pose_vec2T, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, x, n, T);
+    CPE_CHECK_LAUNCH("k_pose_vec2T");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_pose_T2vec_batch(const double *T, int32_t n, double *x, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_pose_T2vec_batch: n < 0");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(T && x, "cpe_pose_T2vec_batch: null pointer");
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_pose_T2vec, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, T, n, x);
+    CPE_CHECK_LAUNCH("k_pose_T2vec");
     return CPE_OK;
 }

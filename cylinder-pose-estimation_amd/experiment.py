@@ -65,7 +65,13 @@ def _upload(images, device):
 
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
-               skipped, T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
+               cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
+               T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
+
+    multi_frame: True = multiframe.fit_multi_frame (simplex on the host, bit-identical to the oracle); 'gpu' =
+    multiframe.fit_multi_frame_gpu (the whole fit resident, device sin / cos: fval agrees to ~1e-12 relative); False = none.
+    The 'gpu' mode fits at most CPE_MULTI_MAXF = 1024 good frames: with more it warns (status 6, CPE_ST_OVERFLOW) and returns
+    None results, where the host mode would fit them.
 
     Every `<stem>L.png` needs its `<stem>R.png`: the reference fails in imread on a missing partner, this raises
     FileNotFoundError naming the file, before any frame is processed.
@@ -106,13 +112,30 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
             right = _upload([p[1] for p in imgs[i0:i1]], dev)
             recs[w0 + i0:w0 + i1] = pipe.run_raw(left, right, pre, {k: t[w0 + i0:w0 + i1] for k, t in fits.items()})
             i0 = i1
-    _, _, st_fit, st_l, st_r = (t.cpu().tolist() for t in pipeline.unpack_counters(recs[:, 15]))
+    _, _, d_fit, d_l, d_r = pipeline.unpack_counters(recs[:, 15])          # device tensors: the 'gpu' mode masks with them
+    st_fit, st_l, st_r = (t.cpu().tolist() for t in (d_fit, d_l, d_r))
     skipped = [dict(index=i, name=names[i], det_left=st_l[i], det_right=st_r[i], fit=st_fit[i])
                for i in range(F) if st_l[i] or st_r[i] or st_fit[i]]
-    res = dict(names=names, angles=angles, records=recs, pts3=fits['pts3'], cnt=fits['m'], skipped=skipped, T_cam_agv=None, fval=None)
+    res = dict(names=names, angles=angles, records=recs, pts3=fits['pts3'], cnt=fits['m'], cyl_raw=fits['cyl_raw'], skipped=skipped,
+               T_cam_agv=None, fval=None)
     if mat_path is not None:
         api.save_mat(mat_path, fits=fits, names=names)
-    if multi_frame:
+    if multi_frame == 'gpu':
+        # resident: the kept frames are named by a device mask made from the records' status words, the whole tables go in
+        # as one group, and T, fval, status and the count of kept frames come back in one copy
+        frame_ok = ((d_fit == 0) & (d_l == 0) & (d_r == 0)).to(torch.int32)
+        mf = multiframe.fit_multi_frame_gpu(fits['pts3'], fits['m'], fits['cyl_raw'], angles, radius, frame_ok=frame_ok,
+                                            group_start=[0, F])
+        back = torch.cat([mf['T'][0], mf['fvals'][0], mf['status'][0:1].to(torch.float64),
+                          frame_ok.sum().to(torch.float64).reshape(1)]).cpu().tolist()
+        n_good, status = int(back[19]), int(back[18])
+        if n_good < 2:
+            warnings.warn(f'{n_good} fitted frame(s): fitCylinderWPts3sAngs needs two')
+        elif status != 0:
+            warnings.warn(f'multi-frame fit ended with status {status} (include/cpe.h: cpe_multi_frame_fit_batch)')
+        else:
+            res['T_cam_agv'], res['fval'] = back[:16], back[17]
+    elif multi_frame:
         bad = {s['index'] for s in skipped}
         good = [i for i in range(F) if i not in bad]
         if len(good) < 2:

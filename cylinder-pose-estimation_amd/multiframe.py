@@ -1,15 +1,22 @@
 """Row f-1: the multi-frame camera<->AGV fit, utils/fitCylinderWPts3sAngs.m (+ getTAGVcyl.m, vec2T.m,
 T2vec.m), the immediate consumer of the per-frame outputs (exp_gridDetection.m:87).
 
-One 6-parameter Nelder-Mead (MATLAB fminsearch order) over  v(agvPose) = sum_i mean((d_i - R)^2).  The data-parallel
-part -- distances of every frame's points to that frame's predicted axis -- is the HIP kernel behind
-cpe_multi_frame_terms (one wavefront per frame, points stay in HBM); the simplex logic is host code in plain Python
-floats (IEEE double, libm sin/cos/acos), which is what MATLAB's interpreter does for the reference.
+One 6-parameter Nelder-Mead (MATLAB fminsearch order) over  v(agvPose) = sum_i mean((d_i - R)^2), in two forms:
+
+fit_multi_frame      the data-parallel part -- distances of every frame's points to that frame's predicted axis -- is the
+                     HIP kernel behind cpe_multi_frame_terms (one wavefront per frame, points stay in HBM); the simplex logic
+                     is host code in plain Python floats (IEEE double, libm sin/cos/acos), which is what MATLAB's interpreter
+                     does for the reference.  Bit-identical to the oracle; one host round trip per objective evaluation.
+fit_multi_frame_gpu  the whole fit in one call of cpe_multi_frame_fit_batch: initial pose, simplex and objective on the
+                     device, one workgroup per group of frames, nothing read back.  Same terms, same simplex order; sin / cos
+                     / acos are the device math library's, so f agrees with the host form to about 1e-12 relative, not bit
+                     for bit.
 
 [ext] rotvec2mat3d / rotmat2vec3d / mrdivide / fminsearch are restated as in oracle/src/orc_fit.c (parity unpinned).
 Reproduced quirk: cylParams{i} is the 2x6 [cylParams0; cylParams] matrix and applyCylParamsPrior indexes it linearly
 (applyCylParamsPrior.m:6-7), so the "origin"/"direction" used for the initial pose mix the two rows.
 """
+import ctypes
 import math
 
 import torch
@@ -270,3 +277,86 @@ def fit_multi_frame(pts3, cnt, cyl_raw, angles, radius):
     f0 = obj(x0)
     x, f, iters, evals = nelder_mead6(obj, x0)
     return dict(T=vec2T(x), x=x, x0=x0, fvals=[f0, f], iters=iters, evals=evals, TAGV=TAGV)
+
+
+def _tol_params(tol_x=1e-5, tol_f=1e-5, max_iter=100000, max_fun_evals=100000):
+    return _lib.CpeFitParams(tol_x, tol_f, max_iter, max_fun_evals, 0, 0)
+
+
+def fit_multi_frame_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=None, group_start=None, x0=None, **tol):
+    """fitCylinderWPts3sAngs for G groups of frames in one resident call (cpe_multi_frame_fit_batch): nothing is read back
+    and the launch is queued on the current stream.  Arguments given on the host -- angles as pan / tilt pairs, a list for
+    group_start or x0 -- are made into tensors here and copied to the device from pageable memory; only the form with
+    device tensors for all of them (angles as the [n,16] table) is free of host copies and graph-capturable.
+    pts3 f64[n,MAXP,3] / cnt i32[n] / cyl_raw f64[n,2,6] as fit_multi_frame takes them (device tensors)
+    angles       n x 2 (pan, tilt) in rad on the host, or a device tensor f64[n,16] of row-major getTAGVcyl matrices
+    frame_ok     None, or i32[n] on the device: a frame with 0 is left out of its group
+    group_start  None = one group of all n frames; G+1 ascending frame offsets (list, or i32 device tensor)
+    x0           None = the initial pose of fitCylinderWPts3sAngs.m:40-69, or f64[G,6] (device tensor or nested list)
+    tol          tol_x, tol_f, max_iter, max_fun_evals (default: the reference's 1e-5 / 1e-5 / 1e5 / 1e5)
+    -> dict of device tensors: x0, x f64[G,6]; T f64[G,16] row-major vec2T(x); fvals f64[G,2] = [f0, f]; iters i32[G,2] =
+       [iterations, evaluations]; n_used i32[G]; status i32[G] (0 = fitted; see include/cpe.h); TAGV f64[n,16].
+       group_result(res, g) is the host view of one group with the keys of fit_multi_frame."""
+    L = _lib.load()
+    dev, n = pts3.device, cnt.shape[0]
+    pts3, cnt, cyl_raw = pts3.contiguous(), cnt.contiguous(), cyl_raw.contiguous()
+    assert pts3.dtype == torch.float64 and cyl_raw.dtype == torch.float64 and cnt.dtype == torch.int32
+    assert pts3.shape == (n, _lib.MAXP, 3) and cyl_raw.shape == (n, 2, 6)
+    if torch.is_tensor(angles):
+        TAGV = angles.to(device=dev, dtype=torch.float64).contiguous()
+        assert TAGV.shape == (n, 16), 'a tensor of angles is the [n,16] table of getTAGVcyl matrices'
+    else:
+        assert len(angles) == n
+        TAGV = torch.tensor([get_TAGVcyl(float(a[0]), float(a[1])) for a in angles], dtype=torch.float64).reshape(n, 16).to(dev)
+    if group_start is None:
+        group_start = [0, n]
+    if not torch.is_tensor(group_start):
+        group_start = torch.tensor(list(group_start), dtype=torch.int32)
+    gs = group_start.to(device=dev, dtype=torch.int32).contiguous()
+    G = gs.numel() - 1
+    assert G >= 0
+    if frame_ok is not None:
+        frame_ok = frame_ok.to(device=dev, dtype=torch.int32).contiguous()
+        assert frame_ok.shape == (n,)
+    if x0 is not None:
+        x0 = torch.as_tensor(x0, dtype=torch.float64).to(dev).reshape(G, 6).contiguous()
+    params = _tol_params(**tol)
+    out = dict(x0=torch.empty((G, 6), dtype=torch.float64, device=dev), x=torch.empty((G, 6), dtype=torch.float64, device=dev),
+               T=torch.empty((G, 16), dtype=torch.float64, device=dev), fvals=torch.empty((G, 2), dtype=torch.float64, device=dev),
+               iters=torch.empty((G, 2), dtype=torch.int32, device=dev), n_used=torch.empty(G, dtype=torch.int32, device=dev),
+               status=torch.empty(G, dtype=torch.int32, device=dev), TAGV=TAGV)
+    _lib.check(L.cpe_multi_frame_fit_batch(pts3.data_ptr(), cnt.data_ptr(), TAGV.data_ptr(), cyl_raw.data_ptr(),
+                                           frame_ok.data_ptr() if frame_ok is not None else None, gs.data_ptr(), G, n, float(radius),
+                                           ctypes.addressof(params), x0.data_ptr() if x0 is not None else None,
+                                           out['x0'].data_ptr(), out['x'].data_ptr(), out['T'].data_ptr(), out['fvals'].data_ptr(),
+                                           out['iters'].data_ptr(), out['n_used'].data_ptr(), out['status'].data_ptr(),
+                                           torch.cuda.current_stream().cuda_stream), 'cpe_multi_frame_fit_batch')
+    return out
+
+
+def group_result(res, g=0):
+    """one group of fit_multi_frame_gpu's result on the host (this synchronises), with the keys of fit_multi_frame --
+    T (flat row-major 4x4), x, x0, fvals [f0, f], iters, evals, TAGV (all frames' matrices) -- plus n_used and status"""
+    it = res['iters'][g].tolist()
+    return dict(T=res['T'][g].tolist(), x=res['x'][g].tolist(), x0=res['x0'][g].tolist(), fvals=res['fvals'][g].tolist(),
+                iters=it[0], evals=it[1], TAGV=res['TAGV'].tolist(), n_used=int(res['n_used'][g]), status=int(res['status'][g]))
+
+
+def vec2T_batch(x):
+    """vec2T.m on the device: x f64[n,6] -> T f64[n,16] row-major (cpe_pose_vec2T_batch; asynchronous)"""
+    x = x.contiguous()
+    assert x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == 6
+    T = torch.empty((x.shape[0], 16), dtype=torch.float64, device=x.device)
+    _lib.check(_lib.load().cpe_pose_vec2T_batch(x.data_ptr(), x.shape[0], T.data_ptr(), torch.cuda.current_stream().cuda_stream),
+               'cpe_pose_vec2T_batch')
+    return T
+
+
+def T2vec_batch(T):
+    """T2vec.m on the device: T f64[n,16] (or [n,4,4]) row-major -> x f64[n,6] (cpe_pose_T2vec_batch; asynchronous)"""
+    T = T.reshape(T.shape[0], 16).contiguous()
+    assert T.dtype == torch.float64
+    x = torch.empty((T.shape[0], 6), dtype=torch.float64, device=T.device)
+    _lib.check(_lib.load().cpe_pose_T2vec_batch(T.data_ptr(), T.shape[0], x.data_ptr(), torch.cuda.current_stream().cuda_stream),
+               'cpe_pose_T2vec_batch')
+    return x

@@ -36,11 +36,12 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 111   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 112   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
-                             111: cpe_debug_clahe_planes_bgr) */
+                             111: cpe_debug_clahe_planes_bgr; 112: cpe_multi_frame_fit_batch, cpe_pose_vec2T_batch,
+                             cpe_pose_T2vec_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -534,9 +535,56 @@ CPE_API int32_t cpe_matlab_prestep_batch(const void *src, int32_t n, int32_t h, 
 /* Row f-1: the per-frame terms of the multi-frame objective of fitCylinderWPts3sAngs.m:82-94 (`dist`):
  * terms[i] = mean((getDistPts3ToLine(Pts3s{i}, line(T * TAGVcyls{i})) - radius)^2), one wavefront per frame.
  * X f64[n,CPE_MAXP,3], cnt i32[n], TAGVcyl f64[n,16] (row-major getTAGVcyl(pan,tilt)), T f64[16] (device, row-major
- * vec2T(agvPose)).  The 6-parameter Nelder-Mead around it runs on the host (cpe_amd/multiframe.py). */
+ * vec2T(agvPose)).  For a 6-parameter Nelder-Mead driven from the host (cpe_amd/multiframe.py: fit_multi_frame); the
+ * resident form of the whole fit is cpe_multi_frame_fit_batch. */
 CPE_API int32_t cpe_multi_frame_terms(const double *X, const int32_t *cnt, int32_t n, const double *TAGVcyl,
                                       const double *T, double radius, double *terms, void *stream);
+
+/* Row f-1, resident: [T, fval] = fitCylinderWPts3sAngs(Pts3s, angs, cylRadius) (exp_gridDetection.m:87) for G groups of
+ * frames in one call, one workgroup per group: initial pose (fitCylinderWPts3sAngs.m:40-69), fminsearch (:75, the loop of
+ * cpe_fit_cylinder_batch) over `dist` (:82-94) and vec2T of the result, all on the device.
+ *   X f64[n,CPE_MAXP,3], cnt i32[n], cyl_raw f64[n,2,6]: the frames' points and [cylParams0; cylParams] as
+ *     cpe_fit_cylinder_batch returns them; TAGVcyl f64[n,16]: row-major getTAGVcyl(pan, tilt) of every frame
+ *   frame_ok i32[n] or NULL: a frame with 0 is left out of its group (a frame whose detection or fit failed: the cell the
+ *     script's try / warning leaves empty)
+ *   group_start i32[G+1], DEVICE memory: group g is made of the frames [group_start[g], group_start[g+1]) that are kept, in
+ *     order; groups may overlap, be empty, and come in any order
+ *   x0_in f64[G,6] or NULL: the initial agvPose [rotation vector, translation] of every group; NULL = :40-69 from the
+ *     first two kept frames of the group (cyl_raw may be NULL when x0_in is given)
+ *   params NULL = the reference's optimset (:75): TolX = TolFun = 1e-5, MaxIter = MaxFunEvals = 1e5.  mode must be
+ *     CPE_FIT_NELDER_MEAD (CPE_ERR_ARG otherwise: there is no LM form of this fit)
+ * Outputs per group: x0, x f64[G,6] (initial and fitted agvPose), T f64[G,16] row-major vec2T(x), fvals f64[G,2] = [f0, f],
+ * iters i32[G,2] = [iterations, function evaluations], n_used i32[G] kept frames, status i32[G]:
+ *   CPE_ST_OVERFLOW    group_start[g] .. group_start[g+1] is not 0 <= a <= b <= n, or more than CPE_MULTI_MAXF frames are kept
+ *   CPE_ST_FEW_POINTS  fewer than two kept frames (assert(nAngles >= 2), :29); one of the first two kept frames has no point
+ *                      (applyCylParamsPrior takes min() of its points; checked with x0_in as well); x0, f0, x or f not finite
+ * With either, every other output of the group is zero (n_used included), so CPE_ST_OK implies finite outputs.  The status is
+ * decided in the kernel (group_start lives on the device); no argument of the call makes it fail after the launch.
+ * cnt is clamped to [0, CPE_MAXP] as in cpe_fit_cylinder_batch.  Deviation: a kept frame without points beyond the first two
+ * contributes the term 0, as in cpe_multi_frame_terms (the reference divides 0 by 0 there and returns NaN).
+ * Arithmetic: a frame's term has the bits of cpe_multi_frame_terms and the terms are added in kept-frame order (:92), the
+ * simplex is the fixed-order fminsearch of the per-frame fit.  sin / cos (vec2T) and acos / sin (T2vec, initial pose only) are
+ * the device math library's, not the host libm's, so against a host-driven fit the objective may differ in its last bits:
+ * x and the iteration path agree where no comparison of the simplex is that close, f to about 1e-12 relative.
+ * Asynchronous on `stream`, no allocation, no workspace, no host synchronisation; G == 0 is a no-op. */
+#define CPE_MULTI_MAXF 1024   /* kept frames of one group */
+CPE_API int32_t cpe_multi_frame_fit_batch(
+    const double *X, const int32_t *cnt, const double *TAGVcyl, const double *cyl_raw, /* [n,MAXP,3] [n] [n,16] [n,2,6] */
+    const int32_t *frame_ok,      /* i32[n] or NULL: a frame with 0 is left out of its group */
+    const int32_t *group_start,   /* i32[G+1], device */
+    int32_t G, int32_t n, double radius, const CpeFitParams *params,
+    const double *x0_in,          /* f64[G,6] or NULL = fitCylinderWPts3sAngs.m:40-69 */
+    double *x0, double *x, double *T, double *fvals, int32_t *iters, int32_t *n_used, int32_t *status, void *stream);
+
+/* vec2T.m / T2vec.m for n poses, one lane per pose: x f64[n,6] = [rotation vector, translation], T f64[n,16] row-major 4x4
+ * (exp_gridDetection.m:92 calls T2vec(T_Cam_cyl) for every frame).  [ext] rotvec2mat3d / rotmat2vec3d restated as in
+ * oracle/src/orc_fit.c (parity unpinned): vec2T gives the identity rotation for |rotation vector| < 1e-6; T2vec has three
+ * branches -- sin(theta) >= 1e-4: theta * r / (2 sin theta); theta near 0: (1/2 - (trace - 3) / 12) * r; theta near pi: from
+ * the largest diagonal entry -- and does not re-orthogonalise its input (rotmat2vec3d's SVD).  These are the device functions
+ * cpe_multi_frame_fit_batch itself uses, with the device math library's sin / cos / acos (a few ulp from the host libm's).
+ * The bottom row of T is written as 0 0 0 1 / not read.  n == 0 is a no-op. */
+CPE_API int32_t cpe_pose_vec2T_batch(const double *x, int32_t n, double *T, void *stream);   /* vec2T.m */
+CPE_API int32_t cpe_pose_T2vec_batch(const double *T, int32_t n, double *x, void *stream);   /* T2vec.m */
 
 #ifdef __cplusplus
 }
