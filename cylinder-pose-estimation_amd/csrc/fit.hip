@@ -1234,6 +1234,8 @@ extern "C" int32_t cpe_fit_cylinder_ransac_batch(const double *X, const int32_t 
 //                       Nelder-Mead driven from the host (cpe_amd/multiframe.py), which adds the F terms in frame order.
 // k_multi_frame_fit   : the whole of fitCylinderWPts3sAngs for one group of frames per workgroup -- initial pose (:40-69),
 //                       fminsearch (fit_nm_on, the body of the per-frame fit) on the same terms, vec2T of the result.
+// k_multi_frame_lm    : build-defined fast mode of the same fit -- an initial pose from all kept frames in closed form, then
+//                       Levenberg-Marquardt on the same objective (a handful of passes over the points).
 // k_pose_vec2T/T2vec  : vec2T.m / T2vec.m for a batch of poses, the device functions the fit itself uses.
 namespace {
 // one frame's term: mean((d - R)^2) over its points; T row-major vec2T(agvPose), A row-major getTAGVcyl of the frame.
@@ -1441,7 +1443,9 @@ constexpr int MF_MAXF = CPE_MULTI_MAXF;   // kept frames of one group
 // barrier, then every wave adds the nk terms in kept-frame order.  The terms alternate between two LDS rows, so one barrier
 // per evaluation is enough: a wave writes row p again only after the barrier of the evaluation in between, which no wave
 // passes before all of them have read row p.  EVERY wave of the workgroup must make the same sequence of calls.
-struct MultiObjective {
+// WAVES: wavefronts of the workgroup (k_multi_frame_fit: MF_WAVES, k_multi_frame_lm: MFLM_WAVES).
+template <int WAVES>
+struct MultiObjectiveT {
     const double *X;
     const int *cnt;
     const double *TAGV;
@@ -1455,7 +1459,7 @@ struct MultiObjective {
         pose_vec2T(x, T);
         double *t = sTerms + row * MF_MAXF;
         row ^= 1;
-        for (int k = wave; k < nk; k += MF_WAVES) {
+        for (int k = wave; k < nk; k += WAVES) {
             const int f = sIdx[k];
             const double term = multi_frame_term(X + (size_t)f * MAXP * 3, cnt[f], TAGV + 16 * (size_t)f, T, R, lane);
             if (lane == 0) t[k] = term;
@@ -1466,6 +1470,23 @@ struct MultiObjective {
         return v;
     }
 };
+using MultiObjective = MultiObjectiveT<MF_WAVES>;
+
+// the kept frames of [a, b) into sIdx, in order (one wavefront): counted past MF_MAXF, stored up to it.  -> the count
+__device__ __forceinline__ int multi_kept_frames(const int *__restrict__ frame_ok, int a, int b, bool range_ok, int lane, int *sIdx)
+{
+    int nk = 0;
+    if (range_ok)
+        for (long long base = a; base < b; base += 64) {
+            const long long f = base + lane;
+            const bool keep = f < b && (frame_ok == nullptr || frame_ok[f] != 0);
+            const unsigned long long bal = __ballot(keep);
+            const int pos = nk + __popcll(bal & ((1ull << lane) - 1ull));
+            if (keep && pos < MF_MAXF) sIdx[pos] = (int)f;
+            nk += __popcll(bal);
+        }
+    return nk;
+}
 
 // a group that is not fitted: its status, every other output zero
 __device__ void multi_write_failed(int g, int status, double *__restrict__ o_x0, double *__restrict__ o_x, double *__restrict__ o_T,
@@ -1500,17 +1521,8 @@ __global__ __launch_bounds__(64 * MF_WAVES) void k_multi_frame_fit(
     const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int a = group_start[g], b = group_start[g + 1];
     const bool range_ok = 0 <= a && a <= b && b <= n;
-    if (wave == 0) {   // kept frames, in order; counted past MF_MAXF, stored up to it
-        int nk = 0;
-        if (range_ok)
-            for (long long base = a; base < b; base += 64) {
-                const long long f = base + lane;
-                const bool keep = f < b && (frame_ok == nullptr || frame_ok[f] != 0);
-                const unsigned long long bal = __ballot(keep);
-                const int pos = nk + __popcll(bal & ((1ull << lane) - 1ull));
-                if (keep && pos < MF_MAXF) sIdx[pos] = (int)f;
-                nk += __popcll(bal);
-            }
+    if (wave == 0) {
+        const int nk = multi_kept_frames(frame_ok, a, b, range_ok, lane, sIdx);
         if (lane == 0) sNk = nk;
     }
     __syncthreads();
@@ -1543,6 +1555,451 @@ __global__ __launch_bounds__(64 * MF_WAVES) void k_multi_frame_fit(
         for (int k = 0; k < 6; k++) { o_x0[6 * g + k] = x0[k]; o_x[6 * g + k] = xf[k]; }
         for (int k = 0; k < 16; k++) o_T[16 * g + k] = T[k];
         o_fvals[2 * g] = f0; o_fvals[2 * g + 1] = ffinal;
+        o_iters[2 * g] = itercount; o_iters[2 * g + 1] = func_evals;
+        o_nused[g] = nk;
+        o_status[g] = CPE_ST_OK;
+    }
+}
+
+// ---- BUILD-DEFINED (nothing like it in the reference, as the LM and RANSAC modes of the per-frame fit): the multi-frame fit by
+// Levenberg-Marquardt from an initial pose made of all kept frames.  Same objective (MultiObjectiveT: the bits of
+// cpe_multi_frame_terms added in kept-frame order), same 6-vector x, a handful of passes over the points instead of thousands.
+#ifndef CPE_MFLM_WAVES
+#define CPE_MFLM_WAVES 8
+#endif
+constexpr int MFLM_WAVES = CPE_MFLM_WAVES;    // wavefronts of a k_multi_frame_lm workgroup (4 / 8 / 16 measured)
+constexpr int MFLM_SUMS = 27;    // upper triangle of J'J (21) and J'r (6)
+
+// exp([w]x) = I + A [w]x + B [w]x^2 (row-major 3x3), A = sin(th)/th and B = (1 - cos th)/th^2 by their series below th = 1e-4:
+// unlike pose_vec2T there is no angle below which the rotation is dropped, an LM step may be that small
+__device__ __forceinline__ void rot_exp(const double *w, double *E)
+{
+    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+    const double th = sqrt(th2);
+    double A, B;
+    if (th < 1e-4) { A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; }
+    else { A = sin(th) / th; B = (1.0 - cos(th)) / th2; }
+    const double K[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const double k2 = (K[r * 3] * K[q] + K[r * 3 + 1] * K[3 + q]) + K[r * 3 + 2] * K[6 + q];
+            E[r * 3 + q] = ((r == q ? 1.0 : 0.0) + A * K[r * 3 + q]) + B * k2;
+        }
+}
+
+// eigenvectors of a symmetric 4x4 by cyclic Jacobi rotations (eig3's sweep on four rows, at most 30 sweeps): V's columns,
+// w unsorted.  Constant indices throughout, so the matrices stay in registers.
+__device__ void eig4(const double *Ain, double *w, double *V)
+{
+    double A[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) { A[i] = Ain[i]; V[i] = (i % 5 == 0) ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < 30; sweep++) {
+        int rotated = 0;
+#pragma unroll
+        for (int p = 0; p < 3; p++)
+#pragma unroll
+            for (int q = p + 1; q < 4; q++) {
+                const double apq = A[p * 4 + q];
+                if (!(fabs(apq) <= 1e-17 * (fabs(A[p * 4 + p]) + fabs(A[q * 4 + q])))) {
+                    rotated = 1;
+                    const double theta = (A[q * 4 + q] - A[p * 4 + p]) / (2.0 * apq);
+                    double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+                    if (theta < 0) t = -t;
+                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const double akp = A[k * 4 + p], akq = A[k * 4 + q];
+                        A[k * 4 + p] = c * akp - s * akq;
+                        A[k * 4 + q] = s * akp + c * akq;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const double apk = A[p * 4 + k], aqk = A[q * 4 + k];
+                        A[p * 4 + k] = c * apk - s * aqk;
+                        A[q * 4 + k] = s * apk + c * aqk;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const double vkp = V[k * 4 + p], vkq = V[k * 4 + q];
+                        V[k * 4 + p] = c * vkp - s * vkq;
+                        V[k * 4 + q] = s * vkp + c * vkq;
+                    }
+                }
+            }
+        if (!rotated) break;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) w[i] = A[i * 5];
+}
+
+// rotation matrix (row-major 3x3) of the quaternion (q0, qx, qy, qz), normalised here
+__device__ __forceinline__ void quat2rot(const double *qin, double *Rm)
+{
+    const double nq = sqrt(((qin[0] * qin[0] + qin[1] * qin[1]) + qin[2] * qin[2]) + qin[3] * qin[3]);
+    const double q0 = qin[0] / nq, qx = qin[1] / nq, qy = qin[2] / nq, qz = qin[3] / nq;
+    Rm[0] = ((q0 * q0 + qx * qx) - qy * qy) - qz * qz; Rm[1] = 2 * (qx * qy - q0 * qz); Rm[2] = 2 * (qx * qz + q0 * qy);
+    Rm[3] = 2 * (qy * qx + q0 * qz); Rm[4] = ((q0 * q0 - qx * qx) + qy * qy) - qz * qz; Rm[5] = 2 * (qy * qz - q0 * qx);
+    Rm[6] = 2 * (qz * qx - q0 * qy); Rm[7] = 2 * (qz * qy + q0 * qx); Rm[8] = ((q0 * q0 - qx * qx) - qy * qy) + qz * qz;
+}
+
+// a kept frame the initial pose can use: at least one point, the fitted row of cyl_raw finite, its direction not zero.
+// -> the origin o and the unit direction d of the fitted axis
+__device__ __forceinline__ bool multi_usable(const int *__restrict__ cnt, const double *__restrict__ cyl_raw, int f, double *o, double *d)
+{
+    const double *row = cyl_raw + 12 * (size_t)f + 6;
+    bool ok = cnt[f] >= 1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { o[k] = row[k]; d[k] = row[3 + k]; ok = ok && isfinite(o[k]) && isfinite(d[k]); }
+    const double nd = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    ok = ok && isfinite(nd) && nd > 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) d[k] = d[k] / nd;
+    return ok;
+}
+
+// The initial pose of the LM form, from all usable kept frames (in place of fitCylinderWPts3sAngs.m:40-69, which uses the first
+// two and the linear-indexing quirk).  With o_i, d_i the fitted axis of frame i (d_i turned to the side of the first usable
+// frame's), a_i / p_i columns 2 / 4 of its getTAGVcyl:
+//   Rot(sigma) = the proper rotation maximising sum (Rot a_i).(sigma d_i): Horn's quaternion, the eigenvector of the largest
+//                eigenvalue of N(S), S = sum a_i d_i'; N(-S) = -N(S), so sigma = -1 takes the smallest eigenvalue's
+//   t(sigma)   = argmin sum |(I - d_i d_i')(Rot p_i + t - o_i)|^2: (sum P_i) t = sum P_i o_i - sum P_i Rot p_i, P_i = I - d_i d_i'
+// Two passes over the kept frames, S first, then sum P_i and both right-hand sides: lane l adds kept frames l, l+64, ... in
+// order, then the 64-lane tree.  Every wave of the workgroup computes the same numbers.  -> the two poses as vectors, the
+// usable count.  (A fitted origin may lie far along its axis -- the simplex does not hold it -- and P_i o_i then carries the
+// rounding of |o_i|: 1e10 mm gives about 1e-6 mm.  It is an initial pose.)
+// A singular (sum P_i) (ridge 1e-12 trace as fit_lm's, then a zero determinant) leaves NaN in that pose.
+__device__ void multi_init_all(const int *__restrict__ cnt, const double *__restrict__ TAGV, const double *__restrict__ cyl_raw,
+                               const int *sIdx, int nk, int lane, double *xp, double *xm, int &n_usable)
+{
+    // the first usable kept frame and the count
+    int first = -1, nus = 0;
+    for (int base = 0; base < nk; base += 64) {
+        const int k = base + lane;
+        double o[3], d[3];
+        const bool us = k < nk && multi_usable(cnt, cyl_raw, sIdx[k], o, d);
+        const unsigned long long bal = __ballot(us);
+        if (first < 0 && bal != 0) first = sIdx[base + __ffsll((long long)bal) - 1];
+        nus += __popcll(bal);
+    }
+    n_usable = nus;
+    if (nus < 2) return;
+    double o1[3], d1[3];
+    multi_usable(cnt, cyl_raw, first, o1, d1);
+    double S[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) S[k] = 0.0;
+    for (int k = lane; k < nk; k += 64) {
+        const int f = sIdx[k];
+        double o[3], d[3];
+        if (!multi_usable(cnt, cyl_raw, f, o, d)) continue;
+        if ((d[0] * d1[0] + d[1] * d1[1]) + d[2] * d1[2] < 0) { d[0] = -d[0]; d[1] = -d[1]; d[2] = -d[2]; }
+        const double *A = TAGV + 16 * (size_t)f;
+        const double a[3] = {A[1], A[5], A[9]};
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) S[r * 3 + c] = S[r * 3 + c] + a[r] * d[c];
+    }
+#pragma unroll
+    for (int k = 0; k < 9; k++) S[k] = wave_sum(S[k]);
+    // Horn's N(S), S[r*3+c] = sum a_r d_c
+    const double N[16] = {(S[0] + S[4]) + S[8], S[5] - S[7], S[6] - S[2], S[1] - S[3],
+                          S[5] - S[7], (S[0] - S[4]) - S[8], S[1] + S[3], S[6] + S[2],
+                          S[6] - S[2], S[1] + S[3], (S[4] - S[0]) - S[8], S[5] + S[7],
+                          S[1] - S[3], S[6] + S[2], S[5] + S[7], (S[8] - S[0]) - S[4]};
+    double w[4], V[16];
+    eig4(N, w, V);
+    double qp[4] = {V[0], V[4], V[8], V[12]}, qm[4] = {V[0], V[4], V[8], V[12]}, wp = w[0], wm = w[0];
+#pragma unroll
+    for (int j = 1; j < 4; j++) {
+        if (w[j] > wp) { wp = w[j]; qp[0] = V[j]; qp[1] = V[4 + j]; qp[2] = V[8 + j]; qp[3] = V[12 + j]; }
+        if (w[j] < wm) { wm = w[j]; qm[0] = V[j]; qm[1] = V[4 + j]; qm[2] = V[8 + j]; qm[3] = V[12 + j]; }
+    }
+    double Rp[9], Rn[9];
+    quat2rot(qp, Rp);
+    quat2rot(qm, Rn);
+    // second pass: sum P_i (upper triangle 00 01 02 11 12 22) and sum P_i (o_i - Rot p_i) for both rotations
+    double M[6], bp[3], bm[3];
+#pragma unroll
+    for (int k = 0; k < 6; k++) M[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { bp[k] = 0.0; bm[k] = 0.0; }
+    for (int k = lane; k < nk; k += 64) {
+        const int f = sIdx[k];
+        double o[3], d[3];
+        if (!multi_usable(cnt, cyl_raw, f, o, d)) continue;   // (the sign of d does not matter to d d')
+        const double *A = TAGV + 16 * (size_t)f;
+        const double p[3] = {A[3], A[7], A[11]};
+        const double Pm[6] = {1.0 - d[0] * d[0], -(d[0] * d[1]), -(d[0] * d[2]), 1.0 - d[1] * d[1], -(d[1] * d[2]), 1.0 - d[2] * d[2]};
+#pragma unroll
+        for (int q = 0; q < 6; q++) M[q] = M[q] + Pm[q];
+#pragma unroll
+        for (int sg = 0; sg < 2; sg++) {
+            const double *Rm = sg == 0 ? Rp : Rn;
+            double *bs = sg == 0 ? bp : bm;
+            double u[3];
+#pragma unroll
+            for (int r = 0; r < 3; r++) u[r] = o[r] - ((Rm[r * 3] * p[0] + Rm[r * 3 + 1] * p[1]) + Rm[r * 3 + 2] * p[2]);
+            bs[0] = bs[0] + ((Pm[0] * u[0] + Pm[1] * u[1]) + Pm[2] * u[2]);
+            bs[1] = bs[1] + ((Pm[1] * u[0] + Pm[3] * u[1]) + Pm[4] * u[2]);
+            bs[2] = bs[2] + ((Pm[2] * u[0] + Pm[4] * u[1]) + Pm[5] * u[2]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++) M[k] = wave_sum(M[k]);
+#pragma unroll
+    for (int k = 0; k < 3; k++) { bp[k] = wave_sum(bp[k]); bm[k] = wave_sum(bm[k]); }
+    // inverse of (sum P_i) + ridge by its adjugate (symmetric 3x3)
+    const double ridge = 1e-12 * ((M[0] + M[3]) + M[5]);
+    const double m00 = M[0] + ridge, m01 = M[1], m02 = M[2], m11 = M[3] + ridge, m12 = M[4], m22 = M[5] + ridge;
+    const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+    const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+    const double det = (m00 * c00 + m01 * c01) + m02 * c02;
+    const double inv = (det == 0) ? NAN : 1.0 / det;
+#pragma unroll
+    for (int sg = 0; sg < 2; sg++) {
+        const double *Rm = sg == 0 ? Rp : Rn, *rhs = sg == 0 ? bp : bm;
+        double T0[16];
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) T0[r * 4 + c] = Rm[r * 3 + c];
+        T0[3] = ((c00 * rhs[0] + c01 * rhs[1]) + c02 * rhs[2]) * inv;
+        T0[7] = ((c01 * rhs[0] + c11 * rhs[1]) + c12 * rhs[2]) * inv;
+        T0[11] = ((c02 * rhs[0] + c12 * rhs[1]) + c22 * rhs[2]) * inv;
+        T0[12] = 0; T0[13] = 0; T0[14] = 0; T0[15] = 1;
+        pose_T2vec(T0, sg == 0 ? xp : xm);
+    }
+}
+
+// J'J (upper triangle, 21) and J'r (6) of the residuals r_ik = (d_ik - R) / sqrt(n_i) at the pose T, for the left perturbation
+// Rot <- exp([dw]x) Rot, t <- t + dt.  With o = Rot p + t, v = Rot a, al = ((P - o).v)/|v|^2, e = (P - o) - v al, d = |e| (the
+// quantities of multi_frame_term):  dr/dt = -e/d,  dr/dw = -((Rot p + al v) x e)/d, both / sqrt(n_i) (fit_lm's dr/do and dr/dv
+// through do = dw x Rot p + dt, dv = dw x v; the bottom row of getTAGVcyl is taken as 0 0 0 1).
+// Fixed order: wave w takes kept frames w, w + WAVES, ... in order, lane l of it their points l, l + 64, ..., all into one set
+// of 27 registers; the 64-lane tree; one row of sJ[WAVES][27] per wave; one barrier; every wave adds the rows in wave order.
+// sJ is written again only after a later objective evaluation (an accepted step), whose barrier every wave passes after it has
+// read the rows.  EVERY wave of the workgroup must make the same sequence of calls.
+template <int WAVES>
+__device__ __forceinline__ void multi_lm_normal(const double *__restrict__ X, const int *__restrict__ cnt, const double *__restrict__ TAGV,
+                                                double R, const int *sIdx, int nk, int wave, int lane, const double *T, double *sJ,
+                                                double *A, double *g)
+{
+    double acc[MFLM_SUMS];
+#pragma unroll
+    for (int k = 0; k < MFLM_SUMS; k++) acc[k] = 0.0;
+    for (int kf = wave; kf < nk; kf += WAVES) {
+        const int f = sIdx[kf];
+        const int n = min(max(cnt[f], 0), MAXP);
+        if (n == 0) continue;
+        const double *P = X + (size_t)f * MAXP * 3, *Am = TAGV + 16 * (size_t)f;
+        double org[3], dy[3], q[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            dy[r] = ((T[r * 4] * Am[1] + T[r * 4 + 1] * Am[5]) + T[r * 4 + 2] * Am[9]) + T[r * 4 + 3] * Am[13];
+            org[r] = ((T[r * 4] * Am[3] + T[r * 4 + 1] * Am[7]) + T[r * 4 + 2] * Am[11]) + T[r * 4 + 3] * Am[15];
+            q[r] = (T[r * 4] * Am[3] + T[r * 4 + 1] * Am[7]) + T[r * 4 + 2] * Am[11];
+        }
+        const double v[3] = {(org[0] + dy[0]) - org[0], (org[1] + dy[1]) - org[1], (org[2] + dy[2]) - org[2]};
+        const double nv2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+        const double sc = 1.0 / sqrt((double)n);
+        for (int k = lane; k < n; k += 64) {
+            const double *pt = P + 3 * k;
+            const double al = (((pt[0] - org[0]) * v[0] + (pt[1] - org[1]) * v[1]) + (pt[2] - org[2]) * v[2]) / nv2;
+            const double e[3] = {pt[0] - (org[0] + v[0] * al), pt[1] - (org[1] + v[1] * al), pt[2] - (org[2] + v[2] * al)};
+            const double dd = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+            if (dd > 0) {
+                const double r = (dd - R) * sc, c1 = -(sc / dd);
+                const double m[3] = {q[0] + v[0] * al, q[1] + v[1] * al, q[2] + v[2] * al};
+                double mxe[3];
+                cross3(m, e, mxe);
+                const double j[6] = {c1 * mxe[0], c1 * mxe[1], c1 * mxe[2], c1 * e[0], c1 * e[1], c1 * e[2]};
+                int i = 0;
+#pragma unroll
+                for (int a = 0; a < 6; a++) {
+#pragma unroll
+                    for (int b = a; b < 6; b++) { acc[i] = acc[i] + j[a] * j[b]; i++; }
+                    acc[21 + a] = acc[21 + a] + j[a] * r;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < MFLM_SUMS; k++) {
+        const double s = wave_sum(acc[k]);
+        if (lane == 0) sJ[wave * MFLM_SUMS + k] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < MFLM_SUMS; k++) {
+        double s = 0.0;
+        for (int w = 0; w < WAVES; w++) s = s + sJ[w * MFLM_SUMS + k];
+        if (k < 21) A[k] = s;
+        else g[k - 21] = s;
+    }
+}
+
+// fit_lm's damped 6x6 system: M = J'J with M_aa (1 + lambda) + 1e-12 trace on the diagonal, M dl = -g by Gaussian elimination
+// with partial pivoting (the first row of the largest |.|, as there).  Row swaps are conditional swaps with constant indices so
+// that the system stays in registers.  false: a zero pivot.
+__device__ __forceinline__ bool multi_lm_solve(const double *A, const double *g, double lambda, double *dl)
+{
+    double M[36], rhs[6];
+    {
+        int i = 0;
+        double trA = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int b = a; b < 6; b++) { M[a * 6 + b] = A[i]; M[b * 6 + a] = A[i]; if (a == b) trA = trA + A[i]; i++; }
+#pragma unroll
+        for (int a = 0; a < 6; a++) { M[a * 6 + a] = M[a * 6 + a] + lambda * M[a * 6 + a] + 1e-12 * trA; rhs[a] = -g[a]; }
+    }
+    bool singular = false;
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        int pv = c;
+        double best = fabs(M[c * 6 + c]);
+#pragma unroll
+        for (int r = c + 1; r < 6; r++) {
+            const double av = fabs(M[r * 6 + c]);
+            if (av > best) { best = av; pv = r; }
+        }
+#pragma unroll
+        for (int r = c + 1; r < 6; r++)
+            if (pv == r) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) { const double t_ = M[c * 6 + k]; M[c * 6 + k] = M[r * 6 + k]; M[r * 6 + k] = t_; }
+                const double t_ = rhs[c]; rhs[c] = rhs[r]; rhs[r] = t_;
+            }
+        singular = singular || M[c * 6 + c] == 0;
+#pragma unroll
+        for (int r = c + 1; r < 6; r++) {
+            const double fct = M[r * 6 + c] / M[c * 6 + c];
+#pragma unroll
+            for (int k = c; k < 6; k++) M[r * 6 + k] = M[r * 6 + k] - fct * M[c * 6 + k];
+            rhs[r] = rhs[r] - fct * rhs[c];
+        }
+    }
+#pragma unroll
+    for (int r = 5; r >= 0; r--) {
+        double sacc = rhs[r];
+#pragma unroll
+        for (int k = r + 1; k < 6; k++) sacc = sacc - M[r * 6 + k] * dl[k];
+        dl[r] = sacc / M[r * 6 + r];
+    }
+    return !singular;
+}
+
+// The LM form of fitCylinderWPts3sAngs for group g = blockIdx.x (frames as in k_multi_frame_fit).  Barriers: one after the
+// frame list, one per objective evaluation, one per Jacobian pass.  As in k_multi_frame_fit every wave runs the same code on
+// the same numbers (frame list, terms and the 27 sums come from LDS), so every branch goes the same way in all waves and no
+// barrier stands under a condition that depends on the wave or the lane.  Every loop is bounded whatever the objective
+// returns: 200 iterations of at most 12 trials, a NaN objective is a rejected trial.
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_multi_frame_lm(
+    const double *__restrict__ X, const int *__restrict__ cnt, const double *__restrict__ TAGV, const double *__restrict__ cyl_raw,
+    const int *__restrict__ frame_ok, const int *__restrict__ group_start, int n, double R, double tolx, double tolf, int maxiter,
+    const double *__restrict__ x0_in, double *__restrict__ o_x0, double *__restrict__ o_x, double *__restrict__ o_T,
+    double *__restrict__ o_fvals, int *__restrict__ o_iters, int *__restrict__ o_nused, int *__restrict__ o_status,
+    double *__restrict__ o_terms)
+{
+    __builtin_amdgcn_s_setprio(3);
+    __shared__ int sIdx[MF_MAXF];
+    __shared__ double sTerms[2 * MF_MAXF];
+    __shared__ double sJ[WAVES * MFLM_SUMS];
+    __shared__ int sNk;
+    const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int a = group_start[g], b = group_start[g + 1];
+    const bool range_ok = 0 <= a && a <= b && b <= n;
+    if (wave == 0) {
+        const int nk = multi_kept_frames(frame_ok, a, b, range_ok, lane, sIdx);
+        if (lane == 0) sNk = nk;
+    }
+    __syncthreads();
+    const int nk = sNk;
+    if (!range_ok || nk > MF_MAXF) { multi_write_failed(g, CPE_ST_OVERFLOW, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    if (nk < 2) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    MultiObjectiveT<WAVES> obj{X, cnt, TAGV, R, sIdx, sTerms, nk, wave, lane, 0};
+    double x0[6], f0;
+    int func_evals;
+    if (x0_in != nullptr) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) x0[k] = x0_in[6 * (size_t)g + k];
+        f0 = obj(x0);
+        func_evals = 1;
+    } else {
+        double xm[6];
+        int n_usable;
+        multi_init_all(cnt, TAGV, cyl_raw, sIdx, nk, lane, x0, xm, n_usable);
+        if (n_usable < 2) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+        f0 = obj(x0);
+        const double fm = obj(xm);
+        func_evals = 2;
+        if (!(f0 <= fm) && fm == fm) {   // the lower objective, a tie to sigma = +1
+#pragma unroll
+            for (int k = 0; k < 6; k++) x0[k] = xm[k];
+            f0 = fm;
+        }
+    }
+    if (!fit_finite(x0, f0)) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    double x[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) x[k] = x0[k];
+    double fx = f0, lambda = 1e-3;
+    int itercount = 0;
+    for (; itercount < maxiter && itercount < 200;) {
+        double T[16], A[21], gr[6];
+        pose_vec2T(x, T);
+        multi_lm_normal<WAVES>(X, cnt, TAGV, R, sIdx, nk, wave, lane, T, sJ, A, gr);
+        itercount++;
+        bool accepted = false;
+        double dmax = 0;
+        const double fprev = fx;
+        for (int tr = 0; tr < 12 && !accepted; tr++) {
+            double dl[6];
+            if (!multi_lm_solve(A, gr, lambda, dl)) { lambda = lambda * 10; continue; }
+            double E[9], Tn[16], xn[6];
+            rot_exp(dl, E);
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) Tn[r * 4 + c] = (E[r * 3] * T[c] + E[r * 3 + 1] * T[4 + c]) + E[r * 3 + 2] * T[8 + c];
+                Tn[r * 4 + 3] = T[r * 4 + 3] + dl[3 + r];
+            }
+            Tn[12] = 0; Tn[13] = 0; Tn[14] = 0; Tn[15] = 1;
+            pose_T2vec(Tn, xn);
+            const double fn = obj(xn);
+            func_evals++;
+            if (fn < fx) {
+                dmax = 0;
+#pragma unroll
+                for (int k = 0; k < 6; k++) { dmax = fmax(dmax, fabs(dl[k])); x[k] = xn[k]; }
+                fx = fn;
+                lambda = fmax(lambda / 10, 1e-12);
+                accepted = true;
+            } else {
+                lambda = lambda * 10;
+            }
+        }
+        if (!accepted) break;
+        if ((fprev - fx) <= tolf * 1e-3 * (1.0 + fx) && dmax <= tolx) break;
+    }
+    if (!fit_finite(x, fx)) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    if (o_terms != nullptr) {   // the terms at the returned pose: one more evaluation (not counted), its row of sTerms
+        const double *t = sTerms + obj.row * MF_MAXF;
+        obj(x);
+        for (int k = threadIdx.x; k < nk; k += 64 * WAVES) o_terms[sIdx[k]] = t[k];
+    }
+    if (threadIdx.x == 0) {
+        double T[16];
+        pose_vec2T(x, T);
+        for (int k = 0; k < 6; k++) { o_x0[6 * g + k] = x0[k]; o_x[6 * g + k] = x[k]; }
+        for (int k = 0; k < 16; k++) o_T[16 * g + k] = T[k];
+        o_fvals[2 * g] = f0; o_fvals[2 * g + 1] = fx;
         o_iters[2 * g] = itercount; o_iters[2 * g + 1] = func_evals;
         o_nused[g] = nk;
         o_status[g] = CPE_ST_OK;
@@ -1603,6 +2060,29 @@ extern "C" int32_t cpe_multi_frame_fit_batch(const double *X, const int32_t *cnt
     CPE_KLAUNCH(k_multi_frame_fit, dim3(G), dim3(64 * MF_WAVES), 0, (hipStream_t)stream, X, cnt, TAGVcyl, cyl_raw, frame_ok, group_start,
                 n, radius, p.tol_x, p.tol_f, p.max_iter, p.max_fun_evals, x0_in, x0, x, T, fvals, iters, n_used, status);
     CPE_CHECK_LAUNCH("k_multi_frame_fit");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_multi_frame_fit_lm_batch(const double *X, const int32_t *cnt, const double *TAGVcyl, const double *cyl_raw,
+                                                const int32_t *frame_ok, const int32_t *group_start, int32_t G, int32_t n, double radius,
+                                                const CpeFitParams *params, const double *x0_in, double *x0, double *x, double *T,
+                                                double *fvals, int32_t *iters, int32_t *n_used, int32_t *status, double *frame_terms,
+                                                void *stream)
+{
+    CPE_CHECK_ARG(X && cnt && TAGVcyl && group_start && x0 && x && T && fvals && iters && n_used && status,
+                  "cpe_multi_frame_fit_lm_batch: null pointer");
+    CPE_CHECK_ARG(cyl_raw || x0_in, "cpe_multi_frame_fit_lm_batch: cyl_raw may be NULL only beside x0_in");
+    CPE_CHECK_ARG(G >= 0 && n >= 0, "cpe_multi_frame_fit_lm_batch: G < 0 or n < 0");
+    CpeFitParams p = {1e-5, 1e-5, 100000, 100000, CPE_FIT_LM, 0};
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.tol_x >= 0 && p.tol_f >= 0 && p.max_iter > 0, "cpe_multi_frame_fit_lm_batch: bad CpeFitParams");
+    CPE_CHECK_ARG(p.mode == CPE_FIT_LM, "cpe_multi_frame_fit_lm_batch: mode %d (this is the LM form; Nelder-Mead is cpe_multi_frame_fit_batch)",
+                  p.mode);
+    if (G == 0) return CPE_OK;
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_multi_frame_lm<MFLM_WAVES>, dim3(G), dim3(64 * MFLM_WAVES), 0, (hipStream_t)stream, X, cnt, TAGVcyl, cyl_raw, frame_ok,
+                group_start, n, radius, p.tol_x, p.tol_f, p.max_iter, x0_in, x0, x, T, fvals, iters, n_used, status, frame_terms);
+    CPE_CHECK_LAUNCH("k_multi_frame_lm");
     return CPE_OK;
 }
 

@@ -69,8 +69,9 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
 
     multi_frame: True = multiframe.fit_multi_frame (simplex on the host, bit-identical to the oracle); 'gpu' =
-    multiframe.fit_multi_frame_gpu (the whole fit resident, device sin / cos: fval agrees to ~1e-12 relative); False = none.
-    The 'gpu' mode fits at most CPE_MULTI_MAXF = 1024 good frames: with more it warns (status 6, CPE_ST_OVERFLOW) and returns
+    multiframe.fit_multi_frame_gpu (the whole fit resident, device sin / cos: fval agrees to ~1e-12 relative); 'lm' = the same
+    call with method='lm' (build-defined: all-frame initial pose + Levenberg-Marquardt, not the reference's path); False = none.
+    The 'gpu' and 'lm' modes fit at most CPE_MULTI_MAXF = 1024 good frames: with more they warn (status 6, CPE_ST_OVERFLOW) and return
     None results, where the host mode would fit them.
 
     Every `<stem>L.png` needs its `<stem>R.png`: the reference fails in imread on a missing partner, this raises
@@ -120,12 +121,12 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
                T_cam_agv=None, fval=None)
     if mat_path is not None:
         api.save_mat(mat_path, fits=fits, names=names)
-    if multi_frame == 'gpu':
+    if multi_frame in ('gpu', 'lm'):
         # resident: the kept frames are named by a device mask made from the records' status words, the whole tables go in
         # as one group, and T, fval, status and the count of kept frames come back in one copy
         frame_ok = ((d_fit == 0) & (d_l == 0) & (d_r == 0)).to(torch.int32)
         mf = multiframe.fit_multi_frame_gpu(fits['pts3'], fits['m'], fits['cyl_raw'], angles, radius, frame_ok=frame_ok,
-                                            group_start=[0, F])
+                                            group_start=[0, F], method='lm' if multi_frame == 'lm' else 'nm')
         back = torch.cat([mf['T'][0], mf['fvals'][0], mf['status'][0:1].to(torch.float64),
                           frame_ok.sum().to(torch.float64).reshape(1)]).cpu().tolist()
         n_good, status = int(back[19]), int(back[18])

@@ -63,6 +63,7 @@ _SIGS = {
     'cpe_triangulate_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 7),
     'cpe_multi_frame_terms': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     'cpe_multi_frame_fit_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p] + [C.c_void_p] * 9),
+    'cpe_multi_frame_fit_lm_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p] + [C.c_void_p] * 10),
     'cpe_pose_vec2T_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'cpe_pose_T2vec_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'cpe_fit_cylinder_ransac_batch': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p] +

@@ -11,6 +11,8 @@ fit_multi_frame_gpu  the whole fit in one call of cpe_multi_frame_fit_batch: ini
                      device, one workgroup per group of frames, nothing read back.  Same terms, same simplex order; sin / cos
                      / acos are the device math library's, so f agrees with the host form to about 1e-12 relative, not bit
                      for bit.
+                     method='lm' (build-defined, cpe_multi_frame_fit_lm_batch): the same objective minimised by
+                     Levenberg-Marquardt from an initial pose made of all frames -- about ten passes over the points.
 
 [ext] rotvec2mat3d / rotmat2vec3d / mrdivide / fminsearch are restated as in oracle/src/orc_fit.c (parity unpinned).
 Reproduced quirk: cylParams{i} is the 2x6 [cylParams0; cylParams] matrix and applyCylParamsPrior indexes it linearly
@@ -283,7 +285,7 @@ def _tol_params(tol_x=1e-5, tol_f=1e-5, max_iter=100000, max_fun_evals=100000):
     return _lib.CpeFitParams(tol_x, tol_f, max_iter, max_fun_evals, 0, 0)
 
 
-def fit_multi_frame_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=None, group_start=None, x0=None, **tol):
+def fit_multi_frame_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=None, group_start=None, x0=None, method='nm', **tol):
     """fitCylinderWPts3sAngs for G groups of frames in one resident call (cpe_multi_frame_fit_batch): nothing is read back
     and the launch is queued on the current stream.  Arguments given on the host -- angles as pan / tilt pairs, a list for
     group_start or x0 -- are made into tensors here and copied to the device from pageable memory; only the form with
@@ -293,10 +295,15 @@ def fit_multi_frame_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=None, group
     frame_ok     None, or i32[n] on the device: a frame with 0 is left out of its group
     group_start  None = one group of all n frames; G+1 ascending frame offsets (list, or i32 device tensor)
     x0           None = the initial pose of fitCylinderWPts3sAngs.m:40-69, or f64[G,6] (device tensor or nested list)
+    method       'nm' = the reference's fminsearch (cpe_multi_frame_fit_batch); 'lm' = the build-defined fast mode
+                 (cpe_multi_frame_fit_lm_batch): Levenberg-Marquardt on the same objective, and with x0 None an initial pose made
+                 of all usable frames instead of :40-69 (see include/cpe.h)
     tol          tol_x, tol_f, max_iter, max_fun_evals (default: the reference's 1e-5 / 1e-5 / 1e5 / 1e5)
     -> dict of device tensors: x0, x f64[G,6]; T f64[G,16] row-major vec2T(x); fvals f64[G,2] = [f0, f]; iters i32[G,2] =
-       [iterations, evaluations]; n_used i32[G]; status i32[G] (0 = fitted; see include/cpe.h); TAGV f64[n,16].
+       [iterations, evaluations]; n_used i32[G]; status i32[G] (0 = fitted; see include/cpe.h); TAGV f64[n,16]; with 'lm' also
+       frame_terms f64[n]: the term of every kept frame of a fitted group at the returned pose, NaN for every other frame.
        group_result(res, g) is the host view of one group with the keys of fit_multi_frame."""
+    assert method in ('nm', 'lm')
     L = _lib.load()
     dev, n = pts3.device, cnt.shape[0]
     pts3, cnt, cyl_raw = pts3.contiguous(), cnt.contiguous(), cyl_raw.contiguous()
@@ -321,25 +328,35 @@ def fit_multi_frame_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=None, group
     if x0 is not None:
         x0 = torch.as_tensor(x0, dtype=torch.float64).to(dev).reshape(G, 6).contiguous()
     params = _tol_params(**tol)
+    if method == 'lm':
+        params.mode = 1                                           # CPE_FIT_LM
     out = dict(x0=torch.empty((G, 6), dtype=torch.float64, device=dev), x=torch.empty((G, 6), dtype=torch.float64, device=dev),
                T=torch.empty((G, 16), dtype=torch.float64, device=dev), fvals=torch.empty((G, 2), dtype=torch.float64, device=dev),
                iters=torch.empty((G, 2), dtype=torch.int32, device=dev), n_used=torch.empty(G, dtype=torch.int32, device=dev),
                status=torch.empty(G, dtype=torch.int32, device=dev), TAGV=TAGV)
-    _lib.check(L.cpe_multi_frame_fit_batch(pts3.data_ptr(), cnt.data_ptr(), TAGV.data_ptr(), cyl_raw.data_ptr(),
-                                           frame_ok.data_ptr() if frame_ok is not None else None, gs.data_ptr(), G, n, float(radius),
-                                           ctypes.addressof(params), x0.data_ptr() if x0 is not None else None,
-                                           out['x0'].data_ptr(), out['x'].data_ptr(), out['T'].data_ptr(), out['fvals'].data_ptr(),
-                                           out['iters'].data_ptr(), out['n_used'].data_ptr(), out['status'].data_ptr(),
-                                           torch.cuda.current_stream().cuda_stream), 'cpe_multi_frame_fit_batch')
+    args = (pts3.data_ptr(), cnt.data_ptr(), TAGV.data_ptr(), cyl_raw.data_ptr(), frame_ok.data_ptr() if frame_ok is not None else None,
+            gs.data_ptr(), G, n, float(radius), ctypes.addressof(params), x0.data_ptr() if x0 is not None else None,
+            out['x0'].data_ptr(), out['x'].data_ptr(), out['T'].data_ptr(), out['fvals'].data_ptr(), out['iters'].data_ptr(),
+            out['n_used'].data_ptr(), out['status'].data_ptr())
+    stream = torch.cuda.current_stream().cuda_stream
+    if method == 'lm':
+        out['frame_terms'] = torch.full((n,), float('nan'), dtype=torch.float64, device=dev)
+        _lib.check(L.cpe_multi_frame_fit_lm_batch(*args, out['frame_terms'].data_ptr(), stream), 'cpe_multi_frame_fit_lm_batch')
+    else:
+        _lib.check(L.cpe_multi_frame_fit_batch(*args, stream), 'cpe_multi_frame_fit_batch')
     return out
 
 
 def group_result(res, g=0):
     """one group of fit_multi_frame_gpu's result on the host (this synchronises), with the keys of fit_multi_frame --
-    T (flat row-major 4x4), x, x0, fvals [f0, f], iters, evals, TAGV (all frames' matrices) -- plus n_used and status"""
+    T (flat row-major 4x4), x, x0, fvals [f0, f], iters, evals, TAGV (all frames' matrices) -- plus n_used and status, and
+    frame_terms (all frames') where the result has them (method='lm')"""
     it = res['iters'][g].tolist()
-    return dict(T=res['T'][g].tolist(), x=res['x'][g].tolist(), x0=res['x0'][g].tolist(), fvals=res['fvals'][g].tolist(),
-                iters=it[0], evals=it[1], TAGV=res['TAGV'].tolist(), n_used=int(res['n_used'][g]), status=int(res['status'][g]))
+    out = dict(T=res['T'][g].tolist(), x=res['x'][g].tolist(), x0=res['x0'][g].tolist(), fvals=res['fvals'][g].tolist(),
+               iters=it[0], evals=it[1], TAGV=res['TAGV'].tolist(), n_used=int(res['n_used'][g]), status=int(res['status'][g]))
+    if 'frame_terms' in res:
+        out['frame_terms'] = res['frame_terms'].tolist()
+    return out
 
 
 def vec2T_batch(x):

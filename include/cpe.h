@@ -36,12 +36,12 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 112   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 113   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
                              111: cpe_debug_clahe_planes_bgr; 112: cpe_multi_frame_fit_batch, cpe_pose_vec2T_batch,
-                             cpe_pose_T2vec_batch) */
+                             cpe_pose_T2vec_batch; 113: cpe_multi_frame_fit_lm_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -552,7 +552,7 @@ CPE_API int32_t cpe_multi_frame_terms(const double *X, const int32_t *cnt, int32
  *   x0_in f64[G,6] or NULL: the initial agvPose [rotation vector, translation] of every group; NULL = :40-69 from the
  *     first two kept frames of the group (cyl_raw may be NULL when x0_in is given)
  *   params NULL = the reference's optimset (:75): TolX = TolFun = 1e-5, MaxIter = MaxFunEvals = 1e5.  mode must be
- *     CPE_FIT_NELDER_MEAD (CPE_ERR_ARG otherwise: there is no LM form of this fit)
+ *     CPE_FIT_NELDER_MEAD (CPE_ERR_ARG otherwise: the LM form is cpe_multi_frame_fit_lm_batch)
  * Outputs per group: x0, x f64[G,6] (initial and fitted agvPose), T f64[G,16] row-major vec2T(x), fvals f64[G,2] = [f0, f],
  * iters i32[G,2] = [iterations, function evaluations], n_used i32[G] kept frames, status i32[G]:
  *   CPE_ST_OVERFLOW    group_start[g] .. group_start[g+1] is not 0 <= a <= b <= n, or more than CPE_MULTI_MAXF frames are kept
@@ -575,6 +575,42 @@ CPE_API int32_t cpe_multi_frame_fit_batch(
     int32_t G, int32_t n, double radius, const CpeFitParams *params,
     const double *x0_in,          /* f64[G,6] or NULL = fitCylinderWPts3sAngs.m:40-69 */
     double *x0, double *x, double *T, double *fvals, int32_t *iters, int32_t *n_used, int32_t *status, void *stream);
+
+/* Row f-1, BUILD-DEFINED fast mode (nothing like it in the reference, as CPE_FIT_LM and RANSAC are for the per-frame fit): the
+ * multi-frame fit by Levenberg-Marquardt from an initial pose made of all kept frames.  Same objective, same 6-vector x and
+ * same groups / frame_ok / statuses as cpe_multi_frame_fit_batch, about ten passes over the points instead of thousands.  The
+ * reference-faithful forms stay cpe_multi_frame_fit_batch and the host-driven simplex.
+ *   x0_in NULL: the initial pose is a closed form over all *usable* kept frames -- cnt >= 1 and the fitted row
+ *     cyl_raw[i,1,:] finite with a non-zero direction -- in place of fitCylinderWPts3sAngs.m:40-69 (first two frames, the
+ *     linear-indexing quirk of applyCylParamsPrior).  o_i = cyl_raw[i,1,0:3]; d_i = cyl_raw[i,1,3:6] normalised and turned so
+ *     that d_i . d_first >= 0 (d_first: the first usable frame's); a_i, p_i = columns 2, 4 of TAGVcyl_i.  For sigma = +1, -1:
+ *     Rot = the proper rotation maximising sum (Rot a_i).(sigma d_i) (Horn's quaternion), t = argmin sum |(I - d_i d_i')(Rot p_i
+ *     + t - o_i)|^2; the sigma with the lower objective is kept (a tie: +1) and x0 = T2vec([Rot t]).  A kept frame that is not
+ *     usable still counts in the objective.
+ *   LM: residuals r_ik = (d_ik - radius) / sqrt(n_i) (their squares sum to the objective), analytic Jacobian for the step
+ *     Rot <- exp([dw]x) Rot, t <- t + dt, the candidate x = T2vec of that pose evaluated by the objective itself.  Damping,
+ *     acceptance, up to 12 trials per iteration, the 6x6 solve and the stop rule are those of the per-frame CPE_FIT_LM:
+ *     (f_prev - f) <= tol_f * 1e-3 * (1 + f) and max |delta| <= tol_x; at most min(max_iter, 200) iterations.
+ *   params NULL = tol_x = tol_f = 1e-5, max_iter 100000; a given mode must be CPE_FIT_LM (CPE_ERR_ARG otherwise);
+ *     max_fun_evals is not used.
+ * Outputs as cpe_multi_frame_fit_batch: fvals = [f(x0), f(x)], iters = [iterations, objective evaluations] (the two candidate
+ * poses of a NULL x0_in are two of them), T = vec2T(x), and
+ *   frame_terms f64[n] or NULL: frame_terms[f] = the term of kept frame f at the returned pose (the bits of
+ *     cpe_multi_frame_terms at T), by one more evaluation that iters does not count.  Written only for the kept frames of
+ *     groups that end CPE_ST_OK: initialise it.  A frame kept by several groups receives the term of one of them.
+ * Statuses: CPE_ST_OVERFLOW as cpe_multi_frame_fit_batch; CPE_ST_FEW_POINTS: fewer than two kept frames, fewer than two
+ * usable frames (x0_in NULL), or x0, f0, x or f not finite.  With either every other per-group output is zero.  With x0_in
+ * no frame needs a point: a frame without points has the term 0.
+ * Arithmetic: f(x0), f(x) and frame_terms have the bits of cpe_pose_vec2T_batch + cpe_multi_frame_terms with the terms added
+ * in kept-frame order; the sums of the initial pose and of the Jacobian are made in a fixed order, so a call repeats its bits.
+ * Asynchronous on `stream`, no allocation, no workspace, no host synchronisation; G == 0 is a no-op. */
+CPE_API int32_t cpe_multi_frame_fit_lm_batch(
+    const double *X, const int32_t *cnt, const double *TAGVcyl, const double *cyl_raw, /* [n,MAXP,3] [n] [n,16] [n,2,6] */
+    const int32_t *frame_ok, const int32_t *group_start, int32_t G, int32_t n, double radius, const CpeFitParams *params,
+    const double *x0_in,          /* f64[G,6] or NULL = the all-frame initial pose */
+    double *x0, double *x, double *T, double *fvals, int32_t *iters, int32_t *n_used, int32_t *status,
+    double *frame_terms,          /* f64[n] or NULL */
+    void *stream);
 
 /* vec2T.m / T2vec.m for n poses, one lane per pose: x f64[n,6] = [rotation vector, translation], T f64[n,16] row-major 4x4
  * (exp_gridDetection.m:92 calls T2vec(T_Cam_cyl) for every frame).  [ext] rotvec2mat3d / rotmat2vec3d restated as in

@@ -1,4 +1,4 @@
-"""Row f-1: time the multi-frame camera-AGV fit (fitCylinderWPts3sAngs) in its two forms on the experiment's own size --
+"""Row f-1: time the multi-frame camera-AGV fit (fitCylinderWPts3sAngs) in its forms on the experiment's own size --
 45 frames of about 250 points each, from the scene generator of tests/multiframe_cases.py.
 
     python tools/time_multiframe.py [--frames 45] [--points 250] [--reps 7] [--procs 3] [--child-timeout 300] [--out FILE]
@@ -7,12 +7,15 @@ Variants, alternated inside one process, wall time around every repetition from 
     host     multiframe.fit_multi_frame: simplex in Python, one copy + launch + read-back per objective evaluation
     gpu      multiframe.fit_multi_frame_gpu + one read-back of T and fvals: the whole fit resident, one launch
     gpu16    the same call for 16 groups (16 scenes of the same size with different seeds), one launch
-For gpu and gpu16 the time between two device events around the launch is reported as well (the kernel alone).
+    lm       the same call with method='lm' (build-defined: all-frame initial pose + Levenberg-Marquardt), one group
+    lm16     the same for the 16 groups
+For the resident variants the time between two device events around the launch is reported as well (the kernel alone).
 Both forms must walk the same simplex path (equal iterations and evaluations) before anything is timed; if they do not, the
 line says so and the times are still reported (the resident form evaluates sin / cos with the device library).
 The parent process starts `--procs` fresh children one after the other and reports the median over the children's medians
-and the host form's run-to-run spread (max - min of its medians).  A child that fails or outlives --child-timeout seconds
-ends the run: nothing more is started on the GPU after it.
+and the run-to-run spreads (max - min of the children's medians) of the host form and of the two one-group resident forms;
+`lm_faster` says whether LM resident beats Nelder-Mead resident by more than the larger of those two.  A child that fails or
+outlives --child-timeout seconds ends the run: nothing more is started on the GPU after it.
 The scenes come from tests/multiframe_cases.py (the generator the GPU tests use), which this file imports by putting tests/
 on sys.path: it has to stay beside the tests."""
 import argparse
@@ -58,14 +61,18 @@ def child(frames, points, reps):
 
     variants = dict(host=lambda: multiframe.fit_multi_frame(P1, c1, r1, angles[:frames], RADIUS),
                     gpu=lambda: resident('gpu', P1, c1, r1, A1, RADIUS),
-                    gpu16=lambda: resident('gpu16', P, cnt, raw, TAGV, RADIUS, group_start=starts))
+                    gpu16=lambda: resident('gpu16', P, cnt, raw, TAGV, RADIUS, group_start=starts),
+                    lm=lambda: resident('lm', P1, c1, r1, A1, RADIUS, method='lm'),
+                    lm16=lambda: resident('lm16', P, cnt, raw, TAGV, RADIUS, group_start=starts, method='lm'))
     first = {k: f() for k, f in variants.items()}                # warm-up
     torch.cuda.synchronize()
     h, g = first['host'], multiframe.group_result(first['gpu'][0])
     same_path = (h['iters'], h['evals']) == (g['iters'], g['evals'])
     info = dict(host_iters=h['iters'], host_evals=h['evals'], gpu_iters=g['iters'], gpu_evals=g['evals'], same_path=same_path,
                 host_fvals=h['fvals'], gpu_fvals=g['fvals'], gpu16_status=first['gpu16'][0]['status'].tolist(),
-                gpu16_evals=first['gpu16'][0]['iters'][:, 1].tolist())
+                gpu16_evals=first['gpu16'][0]['iters'][:, 1].tolist(), lm_fvals=first['lm'][0]['fvals'][0].tolist(),
+                lm_iters=first['lm'][0]['iters'][0].tolist(), lm16_status=first['lm16'][0]['status'].tolist(),
+                lm16_iters=first['lm16'][0]['iters'].tolist(), lm16_fvals=first['lm16'][0]['fvals'][:, 1].tolist())
     event_ms.clear()
     ms = {k: [] for k in variants}
     for _ in range(reps):
@@ -106,13 +113,16 @@ def main():
             if ln.startswith('{'):
                 emit(dict(json.loads(ln), process=p))
     rows = [d for d in lines if d['kind'] == 'case']
-    med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in ('host', 'gpu', 'gpu16')}
-    ev = {k: statistics.median(d['median_event_ms'][k] for d in rows) for k in ('gpu', 'gpu16')}
-    hs = [d['median_ms']['host'] for d in rows]
-    spread = max(hs) - min(hs)
+    med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in ('host', 'gpu', 'gpu16', 'lm', 'lm16')}
+    ev = {k: statistics.median(d['median_event_ms'][k] for d in rows) for k in ('gpu', 'gpu16', 'lm', 'lm16')}
+    spreads = {k: max(d['median_ms'][k] for d in rows) - min(d['median_ms'][k] for d in rows) for k in ('host', 'gpu', 'lm')}
+    spread = spreads['host']
     emit(dict(kind='summary', frames=a.frames, points=a.points, groups=GROUPS, host_ms=med['host'], gpu_ms=med['gpu'], gpu16_ms=med['gpu16'],
               gpu_kernel_ms=ev['gpu'], gpu16_kernel_ms=ev['gpu16'], host_spread_ms=spread, gpu_faster=med['gpu'] + spread < med['host'],
-              evals=rows[0]['host_evals'], same_path=all(d['same_path'] for d in rows)))
+              evals=rows[0]['host_evals'], same_path=all(d['same_path'] for d in rows),
+              lm_ms=med['lm'], lm16_ms=med['lm16'], lm_kernel_ms=ev['lm'], lm16_kernel_ms=ev['lm16'], gpu_spread_ms=spreads['gpu'],
+              lm_spread_ms=spreads['lm'], lm_faster=med['lm'] + max(spreads['gpu'], spreads['lm']) < med['gpu'],
+              lm_iters=rows[0]['lm_iters'], lm_fvals=rows[0]['lm_fvals'], gpu_fvals=rows[0]['gpu_fvals']))
     return 0
 
 
