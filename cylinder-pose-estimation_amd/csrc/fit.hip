@@ -2029,6 +2029,234 @@ __global__ __launch_bounds__(64) void k_pose_T2vec(const double *__restrict__ T,
 #pragma unroll
     for (int k = 0; k < 6; k++) x[6 * (size_t)i + k] = xi[k];
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// BUILD-DEFINED (nothing like it in the reference): pan and tilt of a frame from a calibrated T_Cam_AGV, the inverse of
+// exp_gridDetection.m:90-93, which forms T_Cam_AGV * getTAGVcyl(pan, tilt) from the nominal angles in the file names.
+// agv_chain          : getTAGVcyl.m (default config) on the device, the full product of its five matrices.
+// k_agv_chain        : that for a batch of angle pairs, one lane per pair.
+// k_frame_angles_lm  : one wavefront per frame minimises the frame's term of the multi-frame objective over (pan, tilt) by
+//                      Levenberg-Marquardt with fit_lm's damping, trials and stop rule.
+
+// getTAGVcyl.m: TAP * TPT0 * T01 * T12 * T2C in the operation order of cpe_amd/multiframe.py::get_TAGVcyl -- cos(pan), sin(pan),
+// cos(-tilt), sin(-tilt), -tan(tilt) * L, every entry of a product as ((a*b + c*d) + e*f) + g*h.  sin / cos / tan are the
+// device library's.  All indices are constants after unrolling: the matrices stay in registers.
+__device__ __forceinline__ void agv_chain(double pan, double tilt, double *A)
+{
+    const double cp = cos(pan), sp = sin(pan), ct = cos(-tilt), st = sin(-tilt);
+    const double L = sqrt((-143.1 * -143.1 + 0.0 * 0.0) + 0.0 * 0.0);
+    const double mtr = -tan(tilt) * L;
+    const double TPT0[16] = {1, 0, 0, -143.1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    const double T01[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, mtr, 0, 0, 0, 1};
+    const double T12[16] = {ct, 0, st, 0, 0, 1, 0, 0, -st, 0, ct, 0, 0, 0, 0, 1};
+    const double T2C[16] = {0, -1, 0, 321.1, -1, 0, 0, 0, 0, 0, -1, 110, 0, 0, 0, 1};
+    double acc[16] = {cp, -sp, 0, 0, sp, cp, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, nxt[16];
+#define CHAIN_TIMES(M)                                                                                                    \
+    _Pragma("unroll") for (int r = 0; r < 4; r++) _Pragma("unroll") for (int c = 0; c < 4; c++)                           \
+        nxt[r * 4 + c] = ((acc[r * 4] * M[c] + acc[r * 4 + 1] * M[4 + c]) + acc[r * 4 + 2] * M[8 + c]) + acc[r * 4 + 3] * M[12 + c]; \
+    _Pragma("unroll") for (int k = 0; k < 16; k++) acc[k] = nxt[k];
+    CHAIN_TIMES(TPT0)
+    CHAIN_TIMES(T01)
+    CHAIN_TIMES(T12)
+    CHAIN_TIMES(T2C)
+#undef CHAIN_TIMES
+#pragma unroll
+    for (int k = 0; k < 16; k++) A[k] = acc[k];
+}
+
+__global__ __launch_bounds__(64) void k_agv_chain(const double *__restrict__ angles, int n, double *__restrict__ TAGV)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    double A[16];
+    agv_chain(angles[2 * (size_t)i], angles[2 * (size_t)i + 1], A);
+#pragma unroll
+    for (int k = 0; k < 16; k++) TAGV[16 * (size_t)i + k] = A[k];
+}
+
+// d/dpan and d/dtilt of columns 2 (a) and 4 (p) of getTAGVcyl in closed form, for the Jacobian only (values always come from
+// agv_chain).  With c = cos(-tilt), s = sin(-tilt) (dc/dtilt = s, ds/dtilt = -c):
+//   a = Rz(pan) (-c, 0, s),  p = Rz(pan) (-143.1 + 321.1 c + 110 s, 0, -143.1 tan(tilt) - 321.1 s + 110 c)
+// and d/dpan of Rz(pan) (x, 0, z) is (-sin(pan) x, cos(pan) x, 0).  -> da[0..2] / dp[0..2] by pan, da[3..5] / dp[3..5] by tilt
+__device__ __forceinline__ void agv_chain_derivatives(double pan, double tilt, double *da, double *dp)
+{
+    const double cp = cos(pan), sp = sin(pan), c = cos(-tilt), s = sin(-tilt);
+    const double ax = -c, px = (-143.1 + 321.1 * c) + 110.0 * s;
+    const double dax = -s, daz = -c;
+    const double dpx = 321.1 * s - 110.0 * c, dpz = (-143.1 / (c * c) + 321.1 * c) + 110.0 * s;
+    da[0] = -sp * ax; da[1] = cp * ax; da[2] = 0.0;
+    dp[0] = -sp * px; dp[1] = cp * px; dp[2] = 0.0;
+    da[3] = cp * dax; da[4] = sp * dax; da[5] = daz;
+    dp[3] = cp * dpx; dp[4] = sp * dpx; dp[5] = dpz;
+}
+
+__device__ void frame_angles_write_failed(int f, int lane, int status, double *__restrict__ o_a0, double *__restrict__ o_a,
+                                          double *__restrict__ o_fvals, int *__restrict__ o_iters, double *__restrict__ o_TAGV,
+                                          double *__restrict__ o_Tcyl, int *__restrict__ o_status)
+{
+    if (lane != 0) return;
+    const size_t f2 = 2 * (size_t)f, f16 = 16 * (size_t)f;
+    o_a0[f2] = 0; o_a0[f2 + 1] = 0; o_a[f2] = 0; o_a[f2 + 1] = 0;
+    o_fvals[f2] = 0; o_fvals[f2 + 1] = 0; o_iters[f2] = 0; o_iters[f2 + 1] = 0;
+    if (o_TAGV != nullptr)
+        for (int k = 0; k < 16; k++) o_TAGV[f16 + k] = 0;
+    if (o_Tcyl != nullptr)
+        for (int k = 0; k < 16; k++) o_Tcyl[f16 + k] = 0;
+    o_status[f] = status;
+}
+
+// The frame's objective f(q) = multi_frame_term(P, cnt, agv_chain(q), T, R): the bits of cpe_agv_chain_batch +
+// cpe_multi_frame_terms.  Frame f = blockIdx.x, one wavefront.  Every lane holds the same angles, sums and decisions (the
+// sums come out of the 64-lane tree, everything else is computed from per-frame values), so every branch below goes the
+// same way in all lanes and no wave-level operation stands under a lane-dependent condition.  Every loop is bounded whatever
+// the data: min(maxiter, 200) iterations of at most 12 trials; a non-finite objective or candidate is a rejected trial.
+__global__ __launch_bounds__(64) void k_frame_angles_lm(
+    const double *__restrict__ X, const int *__restrict__ cnt, const double *__restrict__ cyl_raw, const double *__restrict__ Tg,
+    const int *__restrict__ pose_index, int G, double R, double tolx, double tolf, int maxiter, const double *__restrict__ a0_in,
+    double *__restrict__ o_a0, double *__restrict__ o_a, double *__restrict__ o_fvals, int *__restrict__ o_iters,
+    double *__restrict__ o_TAGV, double *__restrict__ o_Tcyl, int *__restrict__ o_status)
+{
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int pi = pose_index != nullptr ? pose_index[f] : 0;
+    if (pi < 0 || pi >= G) { frame_angles_write_failed(f, lane, CPE_ST_OVERFLOW, o_a0, o_a, o_fvals, o_iters, o_TAGV, o_Tcyl, o_status); return; }
+    const int n = min(max(cnt[f], 0), MAXP);
+    if (n < CPE_FIT_MIN_POINTS) { frame_angles_write_failed(f, lane, CPE_ST_FEW_POINTS, o_a0, o_a, o_fvals, o_iters, o_TAGV, o_Tcyl, o_status); return; }
+    const double *P = X + (size_t)f * MAXP * 3;
+    double T[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) T[k] = Tg[16 * (size_t)pi + k];
+    double q0[2];
+    if (a0_in != nullptr) {
+        q0[0] = a0_in[2 * (size_t)f];
+        q0[1] = a0_in[2 * (size_t)f + 1];
+    } else {
+        // the chain's second column is Rz(pan) (-c, 0, s): a = Rot' d, turned to a_x <= 0 (|pan| < pi/2)
+        double o[3], d[3];
+        if (!multi_usable(cnt, cyl_raw, f, o, d)) {
+            frame_angles_write_failed(f, lane, CPE_ST_FEW_POINTS, o_a0, o_a, o_fvals, o_iters, o_TAGV, o_Tcyl, o_status);
+            return;
+        }
+        double a[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) a[k] = (T[k] * d[0] + T[4 + k] * d[1]) + T[8 + k] * d[2];
+        if (a[0] > 0) { a[0] = -a[0]; a[1] = -a[1]; a[2] = -a[2]; }
+        q0[0] = atan2(-a[1], -a[0]);
+        q0[1] = asin(fmin(fmax(-a[2], -1.0), 1.0));
+    }
+    // One call site for the objective (the chain's sin / cos / tan are the large part of this kernel): the candidate (c0, c1)
+    // is first the start, then every trial of the LM.  fit_lm's loop, flattened: a new point (the start, an accepted trial)
+    // gets its Jacobian pass and opens an iteration of up to 12 trials.
+    double A[16], q[2] = {q0[0], q0[1]}, c0 = q0[0], c1 = q0[1];
+    double f0 = 0.0, fx = 0.0, fprev = 0.0, lambda = 1e-3, d0 = 0.0, d1 = 0.0;
+    double s00 = 0.0, s01 = 0.0, s11 = 0.0, g0 = 0.0, g1 = 0.0;
+    int itercount = 0, func_evals = 0, tr = 0;
+    bool started = false;
+    const double sc = 1.0 / sqrt((double)n);
+    for (int step = 0; step < 1 + 12 * 200; step++) {
+        double An[16];
+        agv_chain(c0, c1, An);
+        const double fn = multi_frame_term(P, n, An, T, R, lane);
+        func_evals++;
+        bool fresh = false;
+        if (!started) {
+            f0 = fn;
+            fx = fn;
+            started = true;
+            if (!isfinite(fn)) break;
+            fresh = true;
+        } else if (fn < fx) {   // (false for a NaN objective)
+            q[0] = c0; q[1] = c1;
+            fx = fn;
+            lambda = fmax(lambda / 10, 1e-12);
+            if ((fprev - fx) <= tolf * 1e-3 * (1.0 + fx) && fmax(fabs(d0), fabs(d1)) <= tolx) {
+#pragma unroll
+                for (int k = 0; k < 16; k++) A[k] = An[k];
+                break;
+            }
+            fresh = true;
+        } else {
+            lambda = lambda * 10;
+            tr++;
+        }
+        if (fresh) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) A[k] = An[k];
+            if (!(itercount < maxiter && itercount < 200)) break;
+            // one pass: J'J (3 sums) and J'r (2), r_k = (d_k - R) / sqrt(n), dr/dq = dr/do . do/dq + dr/dv . dv/dq with fit_lm's
+            // dr/do = -e/d, dr/dv = -(al/d) e and do/dq = Rot dp/dq, dv/dq = Rot da/dq
+            double org[3], dy[3], da[6], dp[6], dob[6], dvb[6];
+            agv_chain_derivatives(q[0], q[1], da, dp);
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                dy[r] = ((T[r * 4] * A[1] + T[r * 4 + 1] * A[5]) + T[r * 4 + 2] * A[9]) + T[r * 4 + 3] * A[13];
+                org[r] = ((T[r * 4] * A[3] + T[r * 4 + 1] * A[7]) + T[r * 4 + 2] * A[11]) + T[r * 4 + 3] * A[15];
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    dob[3 * j + r] = (T[r * 4] * dp[3 * j] + T[r * 4 + 1] * dp[3 * j + 1]) + T[r * 4 + 2] * dp[3 * j + 2];
+                    dvb[3 * j + r] = (T[r * 4] * da[3 * j] + T[r * 4 + 1] * da[3 * j + 1]) + T[r * 4 + 2] * da[3 * j + 2];
+                }
+            }
+            const double v[3] = {(org[0] + dy[0]) - org[0], (org[1] + dy[1]) - org[1], (org[2] + dy[2]) - org[2]};
+            const double nv2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+            s00 = 0.0; s01 = 0.0; s11 = 0.0; g0 = 0.0; g1 = 0.0;
+            for (int k = lane; k < n; k += 64) {
+                const double *pt = P + 3 * k;
+                const double al = (((pt[0] - org[0]) * v[0] + (pt[1] - org[1]) * v[1]) + (pt[2] - org[2]) * v[2]) / nv2;
+                const double e[3] = {pt[0] - (org[0] + v[0] * al), pt[1] - (org[1] + v[1] * al), pt[2] - (org[2] + v[2] * al)};
+                const double dd = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+                if (dd > 0) {
+                    const double r = (dd - R) * sc, k1 = -(sc / dd), k2 = k1 * al;
+                    const double j0 = k1 * ((e[0] * dob[0] + e[1] * dob[1]) + e[2] * dob[2]) + k2 * ((e[0] * dvb[0] + e[1] * dvb[1]) + e[2] * dvb[2]);
+                    const double j1 = k1 * ((e[0] * dob[3] + e[1] * dob[4]) + e[2] * dob[5]) + k2 * ((e[0] * dvb[3] + e[1] * dvb[4]) + e[2] * dvb[5]);
+                    s00 = s00 + j0 * j0; s01 = s01 + j0 * j1; s11 = s11 + j1 * j1;
+                    g0 = g0 + j0 * r; g1 = g1 + j1 * r;
+                }
+            }
+            s00 = wave_sum(s00); s01 = wave_sum(s01); s11 = wave_sum(s11);
+            g0 = wave_sum(g0); g1 = wave_sum(g1);
+            itercount++;
+            tr = 0;
+            fprev = fx;
+        }
+        // the next trial: fit_lm's damped system, 2 x 2, solved in closed form.  A singular system or a candidate that is not
+        // finite or has |tilt| >= pi/2 - 1e-3 (tan(tilt) of the chain has its pole at pi/2) is a rejected trial.
+        bool have = false;
+        for (; tr < 12 && !have;) {
+            const double trA = s00 + s11;
+            const double m00 = s00 + lambda * s00 + 1e-12 * trA, m11 = s11 + lambda * s11 + 1e-12 * trA;
+            const double det = m00 * m11 - s01 * s01;
+            d0 = (s01 * g1 - m11 * g0) / det;
+            d1 = (s01 * g0 - m00 * g1) / det;
+            c0 = q[0] + d0;
+            c1 = q[1] + d1;
+            have = det != 0 && isfinite(c0) && isfinite(c1) && fabs(c1) < 1.5707963267948966 - 1e-3;
+            if (!have) { lambda = lambda * 10; tr++; }
+        }
+        if (!have) break;
+    }
+    if (!(isfinite(q0[0]) && isfinite(q0[1]) && isfinite(f0) && isfinite(q[0]) && isfinite(q[1]) && isfinite(fx))) {
+        frame_angles_write_failed(f, lane, CPE_ST_FEW_POINTS, o_a0, o_a, o_fvals, o_iters, o_TAGV, o_Tcyl, o_status);
+        return;
+    }
+    if (lane == 0) {
+        const size_t f2 = 2 * (size_t)f, f16 = 16 * (size_t)f;
+        o_a0[f2] = q0[0]; o_a0[f2 + 1] = q0[1]; o_a[f2] = q[0]; o_a[f2 + 1] = q[1];
+        o_fvals[f2] = f0; o_fvals[f2 + 1] = fx;
+        o_iters[f2] = itercount; o_iters[f2 + 1] = func_evals;
+        if (o_TAGV != nullptr) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) o_TAGV[f16 + k] = A[k];
+        }
+        if (o_Tcyl != nullptr) {   // T * chain, every entry in multi_frame_term's operation order
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                    o_Tcyl[f16 + r * 4 + c] = ((T[r * 4] * A[c] + T[r * 4 + 1] * A[4 + c]) + T[r * 4 + 2] * A[8 + c]) + T[r * 4 + 3] * A[12 + c];
+        }
+        o_status[f] = CPE_ST_OK;
+    }
+}
 }  // namespace
 
 extern "C" int32_t cpe_multi_frame_terms(const double *X, const int32_t *cnt, int32_t n, const double *TAGVcyl,
@@ -2105,5 +2333,36 @@ extern "C" int32_t cpe_pose_T2vec_batch(const double *T, int32_t n, double *x, v
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_pose_T2vec, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, T, n, x);
     CPE_CHECK_LAUNCH("k_pose_T2vec");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_agv_chain_batch(const double *angles, int32_t n, double *TAGVcyl, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_agv_chain_batch: n < 0");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(angles && TAGVcyl, "cpe_agv_chain_batch: null pointer");
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_agv_chain, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, angles, n, TAGVcyl);
+    CPE_CHECK_LAUNCH("k_agv_chain");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_frame_angles_lm_batch(const double *X, const int32_t *cnt, const double *cyl_raw, const double *T,
+                                             const int32_t *pose_index, int32_t G, int32_t n, double radius, const CpeFitParams *params,
+                                             const double *a0_in, double *angles0, double *angles, double *fvals, int32_t *iters,
+                                             double *TAGVcyl, double *Tcyl, int32_t *status, void *stream)
+{
+    CPE_CHECK_ARG(G >= 0 && n >= 0, "cpe_frame_angles_lm_batch: G < 0 or n < 0");
+    CpeFitParams p = {1e-5, 1e-5, 100000, 100000, CPE_FIT_LM, 0};
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.tol_x >= 0 && p.tol_f >= 0 && p.max_iter > 0, "cpe_frame_angles_lm_batch: bad CpeFitParams");
+    CPE_CHECK_ARG(p.mode == CPE_FIT_LM, "cpe_frame_angles_lm_batch: mode %d (the angle solver is Levenberg-Marquardt only)", p.mode);
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(X && cnt && T && angles0 && angles && fvals && iters && status, "cpe_frame_angles_lm_batch: null pointer");
+    CPE_CHECK_ARG(cyl_raw || a0_in, "cpe_frame_angles_lm_batch: cyl_raw may be NULL only beside a0_in");
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_frame_angles_lm, dim3(n), dim3(64), 0, (hipStream_t)stream, X, cnt, cyl_raw, T, pose_index, G, radius, p.tol_x, p.tol_f,
+                p.max_iter, a0_in, angles0, angles, fvals, iters, TAGVcyl, Tcyl, status);
+    CPE_CHECK_LAUNCH("k_frame_angles_lm");
     return CPE_OK;
 }

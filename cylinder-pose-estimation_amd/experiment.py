@@ -63,7 +63,8 @@ def _upload(images, device):
     return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(device)     # (uint16 bits: iotool.StereoPrestep)
 
 
-def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None):
+def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
+                   frame_angles=False):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
@@ -78,7 +79,12 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     FileNotFoundError naming the file, before any frame is processed.
     A frame whose left or right detect status or fit status is non-zero is listed in `skipped` as dict(index, name,
     det_left, det_right, fit) and left out of the multi-frame fit (the script's try / warning leaves such a frame's cell
-    empty).  mat_path: the per-frame results are also written there by api.save_mat (frames, names)."""
+    empty).  mat_path: the per-frame results are also written there by api.save_mat (frames, names).
+
+    frame_angles=True (build-defined, nothing like it in the reference): with a multi-frame result, the good frames go through
+    multiframe.estimate_frame_angles_gpu with T_cam_agv, a self-check of the calibration in degrees.  The dict gains
+    angles_est (F x 2, rad; NaN for a skipped or failed frame), angles_status (F; the solver's status, -1 for a frame that was
+    not given to it) and angles_delta_deg (estimated - nominal); all three are None without a multi-frame result."""
     names = unique_names(input_path)
     if not names:
         raise FileNotFoundError(f'no <name>L.png in {input_path}')
@@ -145,4 +151,16 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
             g = torch.tensor(good, device=dev)
             mf = multiframe.fit_multi_frame(fits['pts3'][g], fits['m'][g], fits['cyl_raw'][g], angles[good], radius)
             res['T_cam_agv'], res['fval'] = mf['T'], mf['fvals'][1]
+    if frame_angles:
+        res.update(angles_est=None, angles_status=None, angles_delta_deg=None)
+        if res['T_cam_agv'] is not None:
+            bad = {s['index'] for s in skipped}
+            good = [i for i in range(F) if i not in bad]
+            g = torch.tensor(good, device=dev)
+            fa = multiframe.estimate_frame_angles_gpu(fits['pts3'][g], fits['m'][g], fits['cyl_raw'][g], res['T_cam_agv'], radius)
+            est, status = np.full((F, 2), np.nan), np.full(F, -1, dtype=np.int32)
+            st = fa['status'].cpu().numpy()
+            status[good] = st
+            est[good] = np.where((st == 0)[:, None], fa['angles'].cpu().numpy(), np.nan)
+            res.update(angles_est=est, angles_status=status, angles_delta_deg=np.rad2deg(est - angles))
     return res

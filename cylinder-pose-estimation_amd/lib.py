@@ -66,6 +66,8 @@ _SIGS = {
     'cpe_multi_frame_fit_lm_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p] + [C.c_void_p] * 10),
     'cpe_pose_vec2T_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'cpe_pose_T2vec_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'cpe_agv_chain_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'cpe_frame_angles_lm_batch': (C.c_int32, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p] + [C.c_void_p] * 9),
     'cpe_fit_cylinder_ransac_batch': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p] +
                                       [C.c_void_p] * 9),
     'cpe_undistort_map': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

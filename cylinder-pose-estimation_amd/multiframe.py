@@ -377,3 +377,59 @@ def T2vec_batch(T):
     _lib.check(_lib.load().cpe_pose_T2vec_batch(T.data_ptr(), T.shape[0], x.data_ptr(), torch.cuda.current_stream().cuda_stream),
                'cpe_pose_T2vec_batch')
     return x
+
+
+def agv_chain_batch(angles):
+    """getTAGVcyl.m on the device: angles f64[n,2] (pan, tilt) in rad -> f64[n,16] row-major (cpe_agv_chain_batch; asynchronous).
+    get_TAGVcyl's operations with the device math library's sin / cos / tan."""
+    angles = angles.contiguous()
+    assert angles.dtype == torch.float64 and angles.dim() == 2 and angles.shape[1] == 2
+    A = torch.empty((angles.shape[0], 16), dtype=torch.float64, device=angles.device)
+    _lib.check(_lib.load().cpe_agv_chain_batch(angles.data_ptr(), angles.shape[0], A.data_ptr(), torch.cuda.current_stream().cuda_stream),
+               'cpe_agv_chain_batch')
+    return A
+
+
+def estimate_frame_angles_gpu(pts3, cnt, cyl_raw, T, radius, pose_index=None, a0=None, **tol):
+    """Build-defined (nothing like it in the reference): pan and tilt of every frame from a calibrated camera-AGV pose, the
+    inverse of exp_gridDetection.m:90-93 (cpe_frame_angles_lm_batch, one wavefront per frame).  Nothing is read back and the
+    launch is queued on the current stream; arguments given on the host (T, pose_index, a0 as lists or arrays) are made into
+    tensors here and copied to the device.
+    pts3 f64[n,MAXP,3] / cnt i32[n] / cyl_raw f64[n,2,6] as fit_cylinder_batch returns them (device tensors); cyl_raw may be
+                 None when a0 is given
+    T            the pose(s) T_Cam_AGV: 16 or G x 16 (or G x 4 x 4) row-major values, e.g. fit_multi_frame_gpu(...)['T']
+    pose_index   None = every frame uses T[0]; i32[n]: the pose of every frame
+    a0           None = the closed-form start from the frame's fitted axis cyl_raw[f,1,3:6] (assumes |pan| < pi/2; a missing
+                 start never means zero: see include/cpe.h); f64[n,2] (pan, tilt) in rad, e.g. the nominal angles
+    tol          tol_x, tol_f, max_iter (default 1e-5 / 1e-5 / 1e5)
+    -> dict of device tensors: angles0, angles f64[n,2]; fvals f64[n,2] = [f(a0), f(a)]; iters i32[n,2] = [iterations,
+       evaluations]; TAGV f64[n,16] getTAGVcyl at the result; Tcyl f64[n,16] = T * TAGV (exp_gridDetection.m:91); status i32[n]
+       (0 = estimated; 5 = too few points / no usable start / not finite; 6 = pose_index out of range; every other output of
+       such a frame is zero)"""
+    L = _lib.load()
+    dev, n = pts3.device, cnt.shape[0]
+    pts3, cnt = pts3.contiguous(), cnt.contiguous()
+    assert pts3.dtype == torch.float64 and cnt.dtype == torch.int32 and pts3.shape == (n, _lib.MAXP, 3)
+    if cyl_raw is not None:
+        cyl_raw = cyl_raw.contiguous()
+        assert cyl_raw.dtype == torch.float64 and cyl_raw.shape == (n, 2, 6)
+    T = torch.as_tensor(T, dtype=torch.float64).to(dev).reshape(-1, 16).contiguous()
+    G = T.shape[0]
+    if pose_index is not None:
+        pose_index = torch.as_tensor(pose_index).to(device=dev, dtype=torch.int32).contiguous()
+        assert pose_index.shape == (n,)
+    if a0 is not None:
+        a0 = torch.as_tensor(a0, dtype=torch.float64).to(dev).reshape(n, 2).contiguous()
+    params = _tol_params(**tol)
+    params.mode = 1                                               # CPE_FIT_LM
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    out = dict(angles0=f64(n, 2), angles=f64(n, 2), fvals=f64(n, 2), iters=torch.empty((n, 2), dtype=torch.int32, device=dev),
+               TAGV=f64(n, 16), Tcyl=f64(n, 16), status=torch.empty(n, dtype=torch.int32, device=dev))
+    _lib.check(L.cpe_frame_angles_lm_batch(pts3.data_ptr(), cnt.data_ptr(), cyl_raw.data_ptr() if cyl_raw is not None else None,
+                                           T.data_ptr(), pose_index.data_ptr() if pose_index is not None else None, G, n,
+                                           float(radius), ctypes.addressof(params), a0.data_ptr() if a0 is not None else None,
+                                           out['angles0'].data_ptr(), out['angles'].data_ptr(), out['fvals'].data_ptr(),
+                                           out['iters'].data_ptr(), out['TAGV'].data_ptr(), out['Tcyl'].data_ptr(),
+                                           out['status'].data_ptr(), torch.cuda.current_stream().cuda_stream),
+               'cpe_frame_angles_lm_batch')
+    return out

@@ -36,12 +36,13 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 113   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 114   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
                              111: cpe_debug_clahe_planes_bgr; 112: cpe_multi_frame_fit_batch, cpe_pose_vec2T_batch,
-                             cpe_pose_T2vec_batch; 113: cpe_multi_frame_fit_lm_batch) */
+                             cpe_pose_T2vec_batch; 113: cpe_multi_frame_fit_lm_batch; 114: cpe_agv_chain_batch,
+                             cpe_frame_angles_lm_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -621,6 +622,60 @@ CPE_API int32_t cpe_multi_frame_fit_lm_batch(
  * The bottom row of T is written as 0 0 0 1 / not read.  n == 0 is a no-op. */
 CPE_API int32_t cpe_pose_vec2T_batch(const double *x, int32_t n, double *T, void *stream);   /* vec2T.m */
 CPE_API int32_t cpe_pose_T2vec_batch(const double *T, int32_t n, double *x, void *stream);   /* T2vec.m */
+
+/* getTAGVcyl.m (default config) for n pairs of angles, one lane per pair: angles f64[n,2] = (pan, tilt) in rad, TAGVcyl
+ * f64[n,16] row-major 4x4 -- the table cpe_multi_frame_terms and the multi-frame fits take, which until now only the host
+ * could make.  The full product TAP * TPT0 * T01 * T12 * T2C of the five matrices in the operation order of
+ * cpe_amd/multiframe.py::get_TAGVcyl: cos(pan), sin(pan), cos(-tilt), sin(-tilt), -tan(tilt) * L, every entry of a product as
+ * ((a*b + c*d) + e*f) + g*h.  It differs from the host only through the device math library's sin / cos / tan (rotation
+ * entries within 16 * 2^-53, column 4 within 1e-12 mm: DESIGN.md §3.7).  This is the device function
+ * cpe_frame_angles_lm_batch itself uses.  n == 0 is a no-op. */
+CPE_API int32_t cpe_agv_chain_batch(const double *angles /*[n,2] pan,tilt rad*/, int32_t n, double *TAGVcyl /*[n,16]*/, void *stream);
+
+/* BUILD-DEFINED (nothing like it in the reference, as CPE_FIT_LM, RANSAC and cpe_multi_frame_fit_lm_batch are): pan and tilt of
+ * every frame from a calibrated camera-AGV pose.  exp_gridDetection.m:90-93 goes the other way: it forms T_Cam_AGV *
+ * getTAGVcyl(pan, tilt) from the nominal angles in the file names.  One wavefront per frame, any n:
+ *     minimise over q = (pan, tilt):  f(q) = mean((d - radius)^2)  of the frame's points against the axis of T * A(q),
+ * A(q) = the chain of cpe_agv_chain_batch; f(q) has the bits of cpe_agv_chain_batch + cpe_multi_frame_terms.
+ *   X f64[n,CPE_MAXP,3], cnt i32[n]: as cpe_fit_cylinder_batch leaves them; cyl_raw f64[n,2,6] its [cylParams0; cylParams]
+ *   T f64[G,16], DEVICE memory: row-major T_Cam_AGV (vec2T of a fitted agvPose); pose_index i32[n] (device) names the pose of
+ *     every frame, NULL = every frame uses T[0]
+ *   a0_in f64[n,2] or NULL: the start.  NULL never means zero (from (0, 0) one frame fit in twelve ends in a second minimum
+ *     0.35-0.46 rad away: DESIGN.md §3.7) but a closed form from the frame's own fitted axis d = cyl_raw[f,1,3:6] (the frame
+ *     must be usable by the rule of cpe_multi_frame_fit_lm_batch: that row finite, its direction not zero): a = Rot' d / |d|,
+ *     negated when a_x > 0, pan = atan2(-a_y, -a_x), tilt = asin(clamp(-a_z, -1, 1)) -- the chain's second column is
+ *     Rz(pan) (-cos tilt, 0, -sin tilt).  This ASSUMES |pan| < pi/2 (the sign of a fitted direction is arbitrary), and it is
+ *     as good as the per-frame fit: five points do not pin a cylinder of known radius down (about a quarter of 5-point frames
+ *     are fitted more than 0.1 rad off their axis), so give a0_in -- the nominal angles -- for frames with few points.
+ *     cyl_raw may be NULL when a0_in is given.
+ *   LM: residuals r_k = (d_k - radius) / sqrt(cnt); Jacobian = the per-frame CPE_FIT_LM's dr/do, dr/dv chained with the
+ *     closed-form derivatives of the chain's columns 2 and 4 (values always come from the full product); five sums per pass
+ *     (J'J, J'r) in the fixed lane-strided order and 64-lane tree; the damped 2 x 2 system with CPE_FIT_LM's (1 + lambda)
+ *     diagonal and 1e-12 * trace ridge solved in closed form; lambda from 1e-3, / 10 on acceptance (floor 1e-12), x 10 on
+ *     rejection, up to 12 trials per iteration; stop when (f_prev - f) <= tol_f * 1e-3 * (1 + f) and max |delta| <= tol_x; at
+ *     most min(max_iter, 200) iterations.  A candidate that is not finite or has |tilt| >= pi/2 - 1e-3 (the chain's tan), or
+ *     whose objective is not finite, is a rejected trial, so every loop is bounded whatever the data.
+ *   params NULL = tol_x = tol_f = 1e-5, max_iter 100000; a given mode must be CPE_FIT_LM (CPE_ERR_ARG otherwise);
+ *     max_fun_evals is not used.
+ * Outputs per frame: angles0, angles f64[n,2] (start and result); fvals f64[n,2] = [f(a0), f(a)]; iters i32[n,2] = [iterations,
+ * objective evaluations]; TAGVcyl f64[n,16] or NULL: the chain at the result (the bits of cpe_agv_chain_batch(angles)); Tcyl
+ * f64[n,16] or NULL: T * TAGVcyl (exp_gridDetection.m:91), every entry as ((a*b + c*d) + e*f) + g*h; status i32[n]:
+ *   CPE_ST_OVERFLOW    pose_index[f] is outside [0, G)
+ *   CPE_ST_FEW_POINTS  cnt < CPE_FIT_MIN_POINTS; no a0_in and the frame is not usable; a start, result or objective not finite
+ * With either, every other output of the frame is zero, so CPE_ST_OK implies finite outputs.  The status is decided in the
+ * kernel.  cnt is clamped to [0, CPE_MAXP].  A call repeats its bits, and a frame's outputs do not depend on its place in the
+ * batch.  Asynchronous on `stream`, no allocation, no workspace, no host synchronisation; n == 0 is a no-op. */
+CPE_API int32_t cpe_frame_angles_lm_batch(
+    const double *X, const int32_t *cnt,      /* [n,CPE_MAXP,3], [n] */
+    const double *cyl_raw,                    /* [n,2,6] or NULL when a0_in is given */
+    const double *T,                          /* f64[G,16] device, row-major T_Cam_AGV */
+    const int32_t *pose_index,                /* i32[n] device or NULL = every frame uses T[0] */
+    int32_t G, int32_t n, double radius, const CpeFitParams *params,
+    const double *a0_in,                      /* f64[n,2] or NULL = closed form from cyl_raw[f,1,3:6] */
+    double *angles0, double *angles,          /* [n,2] start and result (pan, tilt) */
+    double *fvals, int32_t *iters,            /* [n,2] = [f(a0), f(a)], [iterations, objective evaluations] */
+    double *TAGVcyl, double *Tcyl,            /* [n,16] each or NULL */
+    int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }
