@@ -198,6 +198,45 @@ def debug_lines(exp_h, exp_v, joints, n_joints, rect, r0, stage_status, g7, gray
     return dict(out, ws=ws, ws_generation=ws.generation)
 
 
+def workspace_row(n, h, w, name):
+    """(offset, bytes per frame) of a named row of the workspace table of an (n, h, w) call (cpe_debug_workspace_buffer)"""
+    L = _lib.load()
+    buf = C.create_string_buffer(64)
+    off, per = C.c_size_t(), C.c_size_t()
+    ov, side, pub = C.c_int32(), C.c_int32(), C.c_int32()
+    k = 0
+    while L.cpe_debug_workspace_buffer(n, h, w, k, buf, 64, C.byref(off), C.byref(per), C.byref(ov), C.byref(side), C.byref(pub)) == 0:
+        if buf.value.decode() == name:
+            return off.value, per.value
+        k += 1
+    raise KeyError(name)
+
+
+def debug_region_hull(imgs, mode, ws=None):
+    """the hull stage alone (cpe_debug_region_hull, a test aid): imgs u8 [n,h,w] CUDA tensor; mode 0: disc-union images
+    (non-zero = set), the cylinder target's tail; mode 1: grey frames, the planar target's region stage.
+    -> dict(state: list of per-frame dicts, mask: u8 [n,h,w] numpy (mask_contour), hull: list of i32 (hull_n, 2) numpy (x, y)
+    in the order the kernel lists them, ws)"""
+    if not (isinstance(imgs, torch.Tensor) and imgs.is_cuda and imgs.dtype == torch.uint8 and imgs.dim() == 3):
+        raise TypeError('imgs must be a CUDA uint8 tensor [n,h,w]')
+    imgs = imgs.contiguous()
+    n, h, w = imgs.shape
+    dev = imgs.device
+    if ws is None or not ws.fits(n, h, w) or ws.view.device != dev:
+        ws = DetectWorkspace(n, h, w, dev)
+    ws.use(n)
+    ws.skipped_debug_planes = False
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().cpe_debug_region_hull(imgs.data_ptr(), n, h, w, int(mode), ws.view.data_ptr(), ws.bytes,
+                                                     torch.cuda.current_stream().cuda_stream), 'cpe_debug_region_hull')
+        torch.cuda.synchronize(dev)
+    state = ws.state()
+    off, per = workspace_row(n, h, w, 'hull')
+    rows = ws.view[off:off + per * n].view(torch.int32).reshape(n, -1)
+    hull = [rows[f, :2 * max(state[f]['hull_n'], 0)].cpu().numpy().reshape(-1, 2) for f in range(n)]
+    return dict(state=state, mask=ws.plane('mask_contour').cpu().numpy(), hull=hull, ws=ws)
+
+
 def tables_of(det):
     """detect_grid_batch output -> GridTables (the N x 4 [x y col row] matrices of makePyGridPts.m:41)"""
     return GridTables(det['xy'], det['id'], det['n'])

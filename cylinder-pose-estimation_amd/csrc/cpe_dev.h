@@ -477,6 +477,9 @@ int outside_flood(const uint8_t *mask, int n, int h, int w, FrameState *st, Wind
 int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const RegionBuffers &B, FrameState *st, hipStream_t s,
                  const RegionSide *side, const uint8_t *lplane, const RegionProbe *probe);
 int region_stage_plane(const uint8_t *gray, int n, int h, int w, const RegionBuffers &B, FrameState *st, hipStream_t s);
+// largest external contour of img > thr -> convex hull -> filled polygon in dst, st[].rect: the tail of both region stages
+int region_hull(const uint8_t *img, int n, int h, int w, int thr, bool bits_ready, int single_is_positive, uint8_t *dst,
+                const RegionBuffers &B, FrameState *st, hipStream_t s);
 int clahe_front_probe(const uint8_t *gray, int n, int h, int w, int fused, int lab_lut, const RegionBuffers &B, hipStream_t s,
                       uint8_t *cl, uint32_t *planes, int *buckets, int *box);
 

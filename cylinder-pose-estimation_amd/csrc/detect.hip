@@ -605,6 +605,31 @@ extern "C" int32_t cpe_debug_clahe_planes_bgr(const uint8_t *bgr, int32_t n, int
     return clahe_front_probe(lplane, n, h, w, fused, 0, R, s, cl, planes, buckets, box);
 }
 
+// The hull stage on a given image (tests): largest external contour -> convex hull -> filled polygon -> boundingRect, through
+// region_hull as the product calls it.  mode 0: the cylinder target's tail, img a disc-union image (non-zero = set) -- what
+// region_stage does once its discs are drawn, the one-component shortcut included; mode 1: region_stage_plane on grey frames.
+extern "C" int32_t cpe_debug_region_hull(const uint8_t *img, int32_t n, int32_t h, int32_t w, int32_t mode, void *ws, size_t ws_bytes,
+                                         void *stream)
+{
+    CPE_CHECK_ARG(img && ws && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096 && (mode == 0 || mode == 1),
+                  "cpe_debug_region_hull: bad argument");
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_region_hull")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    FrameState *st = W.state();
+    RegionBuffers R = region_buffers(W, h, w);
+    int rc;
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, R.best, W.at<unsigned long long>(WS_BEST_SPOT), R.nrect);
+    CPE_CHECK_LAUNCH("k_state_init");
+    if (mode == 1) return region_stage_plane(img, n, h, w, R, st, s);
+    CPE_CHECK_HIP(hipMemsetAsync(R.mc, 0, (size_t)n * h * w, s));
+    // the union's one-bit plane, which the product draws directly (k_disc_bands) or builds from its byte image; the labelling
+    // reads the plane where ccl_components_reads_bits holds and the caller's bytes elsewhere
+    if ((rc = build_bitplanes(img, n, h, w, 0, 0, 1, R.bits, s)) != CPE_OK) return rc;
+    return region_hull(img, n, h, w, 0, true, 1, R.mc, R, st, s);
+}
+
 namespace cpe { namespace {
 // the region stage's verdict as the caller gives it: what masks_stage reads of that stage besides mask_contour
 __global__ void k_debug_region(FrameState *st, int n, const int *rect, const int *status)

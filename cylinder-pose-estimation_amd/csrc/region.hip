@@ -2389,6 +2389,25 @@ int clahe_front_probe(const uint8_t *gray, int n, int h, int w, int fused, int l
     return CPE_OK;
 }
 
+// The tail both targets share (and cpe_debug_region_hull runs alone): the components of the set img > thr, the largest
+// external contour among them (B.best, reset by the caller), its convex hull, the filled polygon in dst (cleared by the
+// caller) and st[].rect = boundingRect of the contour.  bits_ready: B.bits already holds the set's one-bit plane (one plane
+// per frame) and the labelling may read it instead of img; else the bytes are labelled and the plane is built from them here.
+// single_is_positive: k_region_area's shortcut for a set whose only component is known to have positive area.
+int region_hull(const uint8_t *img, int n, int h, int w, int thr, bool bits_ready, int single_is_positive, uint8_t *dst,
+                const RegionBuffers &B, FrameState *st, hipStream_t s)
+{
+    int rc;
+    CPE_LAUNCH_BEGIN();
+    if ((rc = ccl_components(img, bits_ready ? B.bits : nullptr, n, h, w, thr, WIN_FRAME, B.lab, B.roots, ROOTS_MAIN, st, s)) != CPE_OK) return rc;
+    if (!bits_ready && (rc = build_bitplanes(img, n, h, w, thr, 0, 1, B.bits, s)) != CPE_OK) return rc;
+    CPE_KLAUNCH(k_region_area, dim3(frame_waves(n, 8, 64), n), dim3(64), 0, s, (const uint32_t *)B.bits, h, w, B.roots, st, B.best, single_is_positive);
+    CPE_KLAUNCH(k_hull_fill, dim3(n), dim3(256), 0, s, (const uint32_t *)B.bits, h, w, B.best, st, B.lohi, B.hull, dst);
+    CPE_KLAUNCH(k_hull_rows, dim3((unsigned)((h + HR_ROWS - 1) / HR_ROWS), n), dim3(256), 0, s, h, w, (const unsigned long long *)B.best, (const FrameState *)st, (const int *)B.hull, dst);
+    CPE_CHECK_LAUNCH("region hull");
+    return CPE_OK;
+}
+
 // lplane: L channel of BGR2LAB of a colour frame (util_cylinder.py:1840 on a 3-channel image), or null: grey frames, L = LUT[grey]
 // probe: null on the product path (cpe_debug_blob_region: see RegionProbe)
 int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const RegionBuffers &B, FrameState *st, hipStream_t s,
@@ -2515,12 +2534,7 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
         if ((rc = build_bitplanes(B.ext, n, h, w, 0, 0, 1, B.bits, s)) != CPE_OK) return rc;
     }
     // the labelling reads the one-bit plane (1/8 of the bytes)
-    if ((rc = ccl_components(B.ext, B.bits, n, h, w, 0, WIN_FRAME, B.lab, B.roots, ROOTS_MAIN, st, s)) != CPE_OK) return rc;
-    CPE_KLAUNCH(k_region_area, dim3(frame_waves(n, 8, 64), n), dim3(64), 0, s, (const uint32_t *)B.bits, h, w, B.roots, st, B.best, 1);
-    CPE_KLAUNCH(k_hull_fill, dim3(n), dim3(256), 0, s, (const uint32_t *)B.bits, h, w, B.best, st, B.lohi, B.hull, B.mc);
-    CPE_KLAUNCH(k_hull_rows, dim3((unsigned)((h + HR_ROWS - 1) / HR_ROWS), n), dim3(256), 0, s, h, w, (const unsigned long long *)B.best, (const FrameState *)st, (const int *)B.hull, B.mc);
-    CPE_CHECK_LAUNCH("region hull");
-    return CPE_OK;
+    return region_hull(B.ext, n, h, w, 0, true, 1, B.mc, B, st, s);
 }
 
 // Region stage of the planar script: mask_contour = filled hull of (filled hull of the largest bright blob, dilated by an
@@ -2550,11 +2564,7 @@ int region_stage_plane(const uint8_t *gray, int n, int h, int w, const RegionBuf
         const int thr = round == 0 ? 127 : 0;
         uint8_t *dst = round == 0 ? B.ext : B.mc;
         if (round == 1) CPE_KLAUNCH(k_best_reset, dim3((n + 63) / 64), dim3(64), 0, s, n, B.best);
-        if ((rc = ccl_components(img, nullptr, n, h, w, thr, WIN_FRAME, B.lab, B.roots, ROOTS_MAIN, st, s)) != CPE_OK) return rc;
-        if ((rc = build_bitplanes(img, n, h, w, thr, 0, 1, B.bits, s)) != CPE_OK) return rc;
-        CPE_KLAUNCH(k_region_area, dim3(frame_waves(n, 8, 64), n), dim3(64), 0, s, (const uint32_t *)B.bits, h, w, B.roots, st, B.best, 0);
-        CPE_KLAUNCH(k_hull_fill, dim3(n), dim3(256), 0, s, (const uint32_t *)B.bits, h, w, B.best, st, B.lohi, B.hull, dst);
-        CPE_KLAUNCH(k_hull_rows, dim3((unsigned)((h + HR_ROWS - 1) / HR_ROWS), n), dim3(256), 0, s, h, w, (const unsigned long long *)B.best, (const FrameState *)st, (const int *)B.hull, dst);
+        if ((rc = region_hull(img, n, h, w, thr, false, 0, dst, B, st, s)) != CPE_OK) return rc;
         if (round == 0) {
             const int tiles_x = (w + 63) / 64, tiles_y = (h + 31) / 32;
             CPE_KLAUNCH(k_dilate_ellipse, dim3((unsigned)(n * tiles_x * tiles_y)), dim3(256), 0, s, (const uint8_t *)B.ext, h, w, tiles_x,

@@ -55,6 +55,7 @@ _SIGS = {
     'cpe_debug_clahe_planes_bgr': (C.c_int32, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6),
     'cpe_debug_masks': (C.c_int32, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     'cpe_debug_lines': (C.c_int32, [C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6),
+    'cpe_debug_region_hull': (C.c_int32, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     'cpe_fit_workspace_bytes': (C.c_size_t, [C.c_int32]),
     'cpe_select_triangulate_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3 +
                                      [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_size_t] + [C.c_void_p] * 9),

@@ -36,13 +36,13 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 114   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 115   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
                              111: cpe_debug_clahe_planes_bgr; 112: cpe_multi_frame_fit_batch, cpe_pose_vec2T_batch,
                              cpe_pose_T2vec_batch; 113: cpe_multi_frame_fit_lm_batch; 114: cpe_agv_chain_batch,
-                             cpe_frame_angles_lm_batch) */
+                             cpe_frame_angles_lm_batch; 115: cpe_debug_region_hull) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -383,6 +383,20 @@ CPE_API int32_t cpe_debug_lines(const uint8_t *exp_h, const uint8_t *exp_v, cons
                                 const uint8_t *gray, int32_t n, int32_t h, int32_t w, const CpeDetectParams *params, void *ws,
                                 size_t ws_bytes, double *xy, int32_t *id, int32_t *n_pts, double *center, int32_t *status,
                                 void *stream);
+
+/* The hull stage of detect_grid on a given image: cv2.findContours(RETR_EXTERNAL) -> the contour of largest contourArea ->
+ * cv2.convexHull -> the filled polygon -> cv2.boundingRect, through the one host function both region stages end in.
+ *   mode 0  the cylinder target's tail (detect_largest_blob, util_cylinder.py:1805-1870, after its cv2.circle calls): img
+ *           u8[n,h,w] is a disc-union image, non-zero = set.  A frame whose set is ONE component must give that component
+ *           a contour of positive area (the product's precondition: a union of discs of radius >= 4).
+ *   mode 1  the planar target's region stage (get_convex_hull, util_plane.py:2590-2689) on grey frames img u8[n,h,w]: the set
+ *           img > 127, its hull, the 11 x 11 elliptic dilation, the hull of that.
+ * 64 <= h, w <= 4096; ws: cpe_detect_workspace_bytes(n, h, w).  Afterwards the workspace holds what a detect call holds there
+ * after its region stage: CPE_PLANE_MASK_CONTOUR, the state record (status CPE_ST_OK / CPE_ST_NO_REGION, rect, hull_n,
+ * n_roots, overflow) and, in the workspace row `hull` (cpe_debug_workspace_buffer), the hull_n vertices (x, y) as i32 pairs.
+ * Test / debugging aid. */
+CPE_API int32_t cpe_debug_region_hull(const uint8_t *img, int32_t n, int32_t h, int32_t w, int32_t mode, void *ws, size_t ws_bytes,
+                                      void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Grid-point tables.  One table per image: xy f64[n,CPE_MAXP,2] pixel coordinates, id i32[n,CPE_MAXP,2]

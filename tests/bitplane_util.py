@@ -1,7 +1,5 @@
 """Helpers of the tests that read one-bit planes out of the detect workspace: the tiled layout of csrc/cpe_dev.h restated in
 numpy (as tests/test_bitplane_layout_cpu.py restates it) and the lookup of a row of the workspace table."""
-import ctypes as C
-
 import numpy as np
 
 
@@ -23,13 +21,6 @@ def decode_plane(words, h, w):
 
 
 def workspace_row(L, n, h, w, name):
-    """(offset, bytes per frame) of a row of the workspace table (cpe_debug_workspace_buffer)"""
-    buf = C.create_string_buffer(64)
-    off, per = C.c_size_t(), C.c_size_t()
-    ov, side, pub = C.c_int32(), C.c_int32(), C.c_int32()
-    k = 0
-    while L.cpe_debug_workspace_buffer(n, h, w, k, buf, 64, C.byref(off), C.byref(per), C.byref(ov), C.byref(side), C.byref(pub)) == 0:
-        if buf.value.decode() == name:
-            return off.value, per.value
-        k += 1
-    raise KeyError(name)
+    """(offset, bytes per frame) of a row of the workspace table (cpe_amd.api.workspace_row; L: the loaded library, unused)"""
+    from cpe_amd import api
+    return api.workspace_row(n, h, w, name)
