@@ -2366,3 +2366,230 @@ extern "C" int32_t cpe_frame_angles_lm_batch(const double *X, const int32_t *cnt
     CPE_CHECK_LAUNCH("k_frame_angles_lm");
     return CPE_OK;
 }
+
+// ---- BUILD-DEFINED (nothing like it in the reference): a grid-index shift between the two images of a frame -----------
+// The selectors join the tables on equal (col,row); a detector that numbers one image a column or a row off leaves pairs
+// that still meet the epipolar test (a column shift moves the partner along the epipolar line) at a wrong depth.  The one
+// prior that can tell is the radius: for every candidate shift (dc, dr) of table 1, join, triangulate, keep err < th, fit a
+// cylinder of the known radius (fit_init + hyp_iters of fit_lm) and count the kept points within tau of its surface.
+// k_match_prepare : one wavefront per frame: counts, the refusals of k_select_triangulate, the dense table of image 2.
+// k_match_score   : one wavefront per (frame, candidate); kept points compacted into LDS in join order.  The LDS of a
+//                   workgroup is 32 bytes per point of table 1, so the call launches the kernel once per size class
+//                   (MATCH_TIERS) and a workgroup whose frame belongs to another class leaves at once: the counts are on
+//                   the device, and the host does not wait for them.
+// k_match_pick    : one wavefront per frame: winner by the key (-score, |dc|+|dr|, |dc|, dc, dr), flags, id1 + offset.
+namespace {
+constexpr int MATCH_HDR = 8;                       // ints per frame: ok, cmin, rmin, tw, th, n1 (0 where nothing can pair), n2
+constexpr int MATCH_TIERS[] = {256, 1024, MAXP};   // points of table 1 a workgroup of each launch has LDS for
+constexpr int MATCH_NTIERS = 3;
+
+__host__ __device__ constexpr size_t match_stride(int ncand) { return (size_t)MATCH_HDR + 2 * (size_t)ncand + (size_t)TBL * TBL; }
+
+__global__ __launch_bounds__(64) void k_match_prepare(const int *__restrict__ id1, const int *__restrict__ cnt1,
+                                                      const int *__restrict__ id2, const int *__restrict__ cnt2, int ncand,
+                                                      int *__restrict__ ws)
+{
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int *i1 = id1 + (size_t)f * MAXP * 2, *i2 = id2 + (size_t)f * MAXP * 2;
+    const int n1 = min(max(cnt1[f], 0), MAXP), n2 = min(max(cnt2[f], 0), MAXP);
+    int *hdr = ws + (size_t)f * match_stride(ncand), *tb = hdr + MATCH_HDR + 2 * ncand;
+    int cmin = INT_MAX, cmax = INT_MIN, rmin = INT_MAX, rmax = INT_MIN, lo = INT_MAX, hi = INT_MIN;
+    for (int i = lane; i < n2; i += 64) {
+        int c = i2[2 * i], r = i2[2 * i + 1];
+        cmin = min(cmin, c); cmax = max(cmax, c); rmin = min(rmin, r); rmax = max(rmax, r);
+    }
+    for (int i = lane; i < n1; i += 64) {
+        int c = i1[2 * i], r = i1[2 * i + 1];
+        lo = min(lo, min(c, r)); hi = max(hi, max(c, r));
+    }
+    cmin = wave_min_i(cmin); cmax = wave_max_i(cmax); rmin = wave_min_i(rmin); rmax = wave_max_i(rmax);
+    lo = wave_min_i(min(lo, min(cmin, rmin))); hi = wave_max_i(max(hi, max(cmax, rmax)));
+    const bool pairs = n1 > 0 && n2 > 0;
+    const bool ok = !(pairs && ((long long)cmax - cmin >= TBL || (long long)rmax - rmin >= TBL || lo < -9999 || hi > 9999));
+    const int tw = (pairs && ok) ? cmax - cmin + 1 : 0, thh = (pairs && ok) ? rmax - rmin + 1 : 0;
+    if (lane == 0) {
+        hdr[0] = ok ? 1 : 0; hdr[1] = cmin; hdr[2] = rmin; hdr[3] = tw; hdr[4] = thh;
+        hdr[5] = (pairs && ok) ? n1 : 0; hdr[6] = n2; hdr[7] = 0;
+    }
+    for (int i = lane; i < tw * thh; i += 64) tb[i] = INT_MAX;
+    __syncthreads();
+    if (pairs && ok)
+        for (int i = lane; i < n2; i += 64) atomicMin(&tb[(i2[2 * i + 1] - rmin) * tw + (i2[2 * i] - cmin)], i);
+}
+
+__global__ __launch_bounds__(64) void k_match_score(const double *__restrict__ xy1, const int *__restrict__ id1,
+                                                    const double *__restrict__ xy2, const double *__restrict__ K1,
+                                                    const double *__restrict__ K2, const double *__restrict__ T21, int win_c,
+                                                    int win_r, double R, double th, double tau, int hyp_iters, int cap_lo,
+                                                    int cap_hi, int *__restrict__ ws)
+{
+    const int nr = 2 * win_r + 1, ncand = (2 * win_c + 1) * nr;
+    const int f = blockIdx.x / ncand, cand = blockIdx.x - f * ncand, lane = threadIdx.x;
+    int *hdr = ws + (size_t)f * match_stride(ncand);
+    const int n1 = hdr[5];
+    if (n1 <= cap_lo || n1 > cap_hi) return;       // another launch has the LDS this frame needs
+    double *sP = fit_dyn, *sD = fit_dyn + (size_t)cap_hi * 3;   // dynamic LDS: cap_hi * 4 doubles
+    __shared__ int sNb[20];
+    const int dc = cand / nr - win_c, dr = cand - (cand / nr) * nr - win_r;
+    const int cmin = hdr[1], rmin = hdr[2], tw = hdr[3], thh = hdr[4];
+    const int *tb = hdr + MATCH_HDR + 2 * ncand;
+    const double *a1 = xy1 + (size_t)f * MAXP * 2, *a2 = xy2 + (size_t)f * MAXP * 2;
+    const int *i1 = id1 + (size_t)f * MAXP * 2;
+    int m = 0, score = 0;
+    if (n1 > 0) {
+        double P1[12], P2[12];
+        {
+            const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+            double k1[9], k2[9], tt[16];
+            for (int k = 0; k < 9; k++) { k1[k] = K1[k]; k2[k] = K2[k]; }
+            for (int k = 0; k < 16; k++) tt[k] = T21[k];
+            make_P(k1, I4, P1);
+            make_P(k2, tt, P2);
+        }
+        // join in image-1 order (first occurrence in image 2): the pairs (i, j) go to LDS first, so that the DLT rounds below
+        // have every lane at work (a shifted table 1 finds partners for only a part of its rows).  They lie where fit_init
+        // keeps its distances later: 2 ints = 1 double per point
+        int *sIJ = reinterpret_cast<int *>(sD);
+        int nj = 0;
+        for (int i0 = 0; i0 < n1; i0 += 64) {
+            const int i = i0 + lane;
+            int j = INT_MAX;
+            if (i < n1) {
+                const int c = i1[2 * i] + dc - cmin, r = i1[2 * i + 1] + dr - rmin;
+                if (c >= 0 && c < tw && r >= 0 && r < thh) j = tb[r * tw + c];
+            }
+            const unsigned long long b = __ballot(j != INT_MAX);
+            if (j != INT_MAX) {
+                const int pos = nj + __popcll(b & ((1ull << lane) - 1ull));     // pos < n1 <= cap_hi
+                sIJ[2 * pos] = i; sIJ[2 * pos + 1] = j;
+            }
+            nj += __popcll(b);
+        }
+        __syncthreads();
+        // DLT of every pair, err < th, compaction in join order
+        for (int k0 = 0; k0 < nj; k0 += 64) {
+            const int k = k0 + lane;
+            bool take = false;
+            double X[3] = {0, 0, 0};
+            if (k < nj) {
+                const int i = sIJ[2 * k], j = sIJ[2 * k + 1];
+                double e;
+                triangulate_one(P1, P2, a1[2 * i], a1[2 * i + 1], a2[2 * j], a2[2 * j + 1], X, e);
+                take = e < th;
+            }
+            const unsigned long long b = __ballot(take);
+            if (take) {
+                const int pos = m + __popcll(b & ((1ull << lane) - 1ull));   // pos < nj <= cap_hi
+                sP[3 * pos] = X[0]; sP[3 * pos + 1] = X[1]; sP[3 * pos + 2] = X[2];
+            }
+            m += __popcll(b);
+        }
+        __syncthreads();
+        if (m >= CPE_FIT_MIN_POINTS) {
+            double x0[6], f0, xf[6], ffinal;
+            int it, ev;
+            fit_init(sP, m, R, lane, sD, sNb, x0, f0);
+            if (fit_finite(x0, f0)) {
+                fit_lm(sP, m, R, lane, 1e-5, 1e-5, hyp_iters, x0, f0, xf, ffinal, it, ev);
+                if (fit_finite(xf, ffinal)) {
+                    int c = 0;
+                    for (int k = lane; k < m; k += 64) c += ransac_inlier(sP, k, xf, R, tau) ? 1 : 0;
+                    score = wave_sum_i(c);
+                }
+            }
+        }
+    }
+    if (lane == 0) { hdr[MATCH_HDR + cand] = score; hdr[MATCH_HDR + ncand + cand] = m; }
+}
+
+__global__ __launch_bounds__(64) void k_match_pick(const int *__restrict__ id1, const int *__restrict__ cnt1, int win_c, int win_r,
+                                                   int min_score, const int *__restrict__ ws, int *__restrict__ o_offset,
+                                                   int *__restrict__ o_score, int *__restrict__ o_scores, int *__restrict__ o_flags,
+                                                   int *__restrict__ o_id1)
+{
+    const int nr = 2 * win_r + 1, ncand = (2 * win_c + 1) * nr;
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int *hdr = ws + (size_t)f * match_stride(ncand), *sc = hdr + MATCH_HDR, *kept = sc + ncand;
+    // smallest key (-score, |dc|+|dr|, |dc|, dc, dr) as one integer: (0,0) wins every tie it is part of
+    unsigned long long best = ~0ull;
+    for (int k = lane; k < ncand; k += 64) {
+        const int dc = k / nr - win_c, dr = k - (k / nr) * nr - win_r;
+        const unsigned long long key = ((unsigned long long)(MAXP - sc[k]) << 48) | ((unsigned long long)(abs(dc) + abs(dr)) << 40) |
+                                       ((unsigned long long)abs(dc) << 32) | ((unsigned long long)(dc + CPE_MATCH_MAX_WIN) << 24) |
+                                       ((unsigned long long)(dr + CPE_MATCH_MAX_WIN) << 16) | (unsigned long long)k;
+        best = key < best ? key : best;
+        if (o_scores) o_scores[(size_t)f * ncand + k] = sc[k];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(best, off, 64);
+        best = o < best ? o : best;
+    }
+    const int win = (int)(best & 0xffffull);
+    int second = 0;                                // the second-largest value among all candidates (0 with one candidate)
+    for (int k = lane; k < ncand; k += 64)
+        if (k != win) second = max(second, sc[k]);
+    second = wave_max_i(second);
+    const int wdc = win / nr - win_c, wdr = win - (win / nr) * nr - win_r, top = sc[win];
+    int flags = 0, dc = wdc, dr = wdr;
+    if (!hdr[0]) flags |= CPE_MATCH_FLAG_OVERFLOW;
+    if (top < min_score) { flags |= CPE_MATCH_FLAG_WEAK; dc = 0; dr = 0; }
+    if ((win_c > 0 && abs(wdc) == win_c) || (win_r > 0 && abs(wdr) == win_r)) flags |= CPE_MATCH_FLAG_EDGE;
+    if (dc != 0 || dr != 0) flags |= CPE_MATCH_FLAG_SHIFTED;
+    if (lane == 0) {
+        o_offset[2 * f] = dc; o_offset[2 * f + 1] = dr;
+        o_score[4 * f] = top; o_score[4 * f + 1] = second; o_score[4 * f + 2] = sc[win_c * nr + win_r]; o_score[4 * f + 3] = kept[win];
+        o_flags[f] = flags;
+    }
+    const int n1 = min(max(cnt1[f], 0), MAXP);
+    const int *i1 = id1 + (size_t)f * MAXP * 2;
+    int *o1 = o_id1 + (size_t)f * MAXP * 2;
+    for (int i = lane; i < n1; i += 64) { o1[2 * i] = i1[2 * i] + dc; o1[2 * i + 1] = i1[2 * i + 1] + dr; }
+}
+}  // namespace
+
+extern "C" size_t cpe_match_offset_workspace_bytes(int32_t n, int32_t win_c, int32_t win_r)
+{
+    if (n <= 0 || win_c < 0 || win_r < 0 || win_c > CPE_MATCH_MAX_WIN || win_r > CPE_MATCH_MAX_WIN) return 0;
+    return (size_t)n * match_stride((2 * win_c + 1) * (2 * win_r + 1)) * sizeof(int);
+}
+
+extern "C" int32_t cpe_match_offset_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
+                                          const int32_t *id2, const int32_t *cnt2, int32_t n, const double *K1, const double *K2,
+                                          const double *T21, double radius, const CpeMatchParams *params, void *ws, size_t ws_bytes,
+                                          int32_t *offset, int32_t *score, int32_t *scores, int32_t *flags, int32_t *id1_out,
+                                          void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_match_offset_batch: n < 0");
+    CpeMatchParams p = {4, 4, 0.3, 0.5, 8, 8};
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.win_c >= 0 && p.win_c <= CPE_MATCH_MAX_WIN && p.win_r >= 0 && p.win_r <= CPE_MATCH_MAX_WIN,
+                  "cpe_match_offset_batch: window must be 0..%d in both directions", CPE_MATCH_MAX_WIN);
+    CPE_CHECK_ARG(p.th > 0 && p.tau > 0 && p.hyp_iters >= 1 && p.hyp_iters <= 200 && p.min_score >= 0,
+                  "cpe_match_offset_batch: bad CpeMatchParams (th > 0, tau > 0, hyp_iters 1..200, min_score >= 0)");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(xy1 && id1 && cnt1 && xy2 && id2 && cnt2 && K1 && K2 && T21 && offset && score && flags && id1_out,
+                  "cpe_match_offset_batch: null pointer");
+    CPE_CHECK_ARG(id1_out != id1, "cpe_match_offset_batch: id1_out may not be id1");
+    const int ncand = (2 * p.win_c + 1) * (2 * p.win_r + 1);
+    CPE_CHECK_ARG((long long)n * ncand <= INT_MAX, "cpe_match_offset_batch: n * candidates exceeds 2^31 - 1");
+    if (!ws || ws_bytes < cpe_match_offset_workspace_bytes(n, p.win_c, p.win_r)) {
+        cpe::set_error("cpe_match_offset_batch: workspace too small (%zu < %zu)", ws_bytes,
+                       cpe_match_offset_workspace_bytes(n, p.win_c, p.win_r));
+        return CPE_ERR_WORKSPACE;
+    }
+    CPE_LAUNCH_BEGIN();
+    CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_match_score), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FIT_LDS_BYTES));
+    CPE_KLAUNCH(k_match_prepare, dim3(n), dim3(64), 0, (hipStream_t)stream, id1, cnt1, id2, cnt2, ncand, (int *)ws);
+    CPE_CHECK_LAUNCH("k_match_prepare");
+    for (int t = 0; t < MATCH_NTIERS; t++) {
+        const int cap_lo = t == 0 ? -1 : MATCH_TIERS[t - 1], cap_hi = MATCH_TIERS[t];
+        CPE_KLAUNCH(k_match_score, dim3(n * ncand), dim3(64), (size_t)cap_hi * 4 * sizeof(double), (hipStream_t)stream, xy1, id1, xy2, K1, K2,
+                    T21, p.win_c, p.win_r, radius, p.th, p.tau, p.hyp_iters, cap_lo, cap_hi, (int *)ws);
+        CPE_CHECK_LAUNCH("k_match_score");
+    }
+    CPE_KLAUNCH(k_match_pick, dim3(n), dim3(64), 0, (hipStream_t)stream, id1, cnt1, p.win_c, p.win_r, p.min_score, (const int *)ws, offset,
+                score, scores, flags, id1_out);
+    CPE_CHECK_LAUNCH("k_match_pick");
+    return CPE_OK;
+}

@@ -13,7 +13,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import api, iotool, multiframe, pipeline
+from . import api, fit, iotool, multiframe, pipeline
 from . import lib as _lib
 
 
@@ -64,7 +64,7 @@ def _upload(images, device):
 
 
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
-                   frame_angles=False):
+                   frame_angles=False, match_offset=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
@@ -80,6 +80,12 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     A frame whose left or right detect status or fit status is non-zero is listed in `skipped` as dict(index, name,
     det_left, det_right, fit) and left out of the multi-frame fit (the script's try / warning leaves such a frame's cell
     empty).  mat_path: the per-frame results are also written there by api.save_mat (frames, names).
+
+    match_offset: None, or a dict of fit.match_offset_batch keywords ({} = its defaults; build-defined, nothing like it in the
+    reference): every frame's index shift between the two tables is searched before the selector (FramePipeline(match=...)).
+    The dict gains offset i32 [F,2], match_score i32 [F,4] and match_flags i32 [F].  A frame
+    flagged fit.MATCH_WEAK -- no shift gave a cylinder worth trusting -- is listed in `skipped` (every entry then has a `match`
+    key: the frame's flags) and left out of the multi-frame fit; a frame flagged MATCH_SHIFTED is used.
 
     frame_angles=True (build-defined, nothing like it in the reference): with a multi-frame result, the good frames go through
     multiframe.estimate_frame_angles_gpu with T_cam_agv, a self-check of the calibration in degrees.  The dict gains
@@ -105,7 +111,7 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
         if pipe is None:
             h, w = imgs[0][0].shape[:2]
             pre = iotool.StereoPrestep(cam_l, cam_r, h, w, dev)
-            pipe = pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=chunk, device=dev)
+            pipe = pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=chunk, device=dev, match=match_offset)
         kinds = [tuple((a.dtype, a.shape) for a in pair) for pair in imgs]
         for kd, s in zip(kinds, names[w0:]):
             if any(shape[:2] != (pipe.h, pipe.w) for _, shape in kd):
@@ -121,16 +127,27 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
             i0 = i1
     _, _, d_fit, d_l, d_r = pipeline.unpack_counters(recs[:, 15])          # device tensors: the 'gpu' mode masks with them
     st_fit, st_l, st_r = (t.cpu().tolist() for t in (d_fit, d_l, d_r))
-    skipped = [dict(index=i, name=names[i], det_left=st_l[i], det_right=st_r[i], fit=st_fit[i])
-               for i in range(F) if st_l[i] or st_r[i] or st_fit[i]]
+    if match_offset is None:
+        skipped = [dict(index=i, name=names[i], det_left=st_l[i], det_right=st_r[i], fit=st_fit[i])
+                   for i in range(F) if st_l[i] or st_r[i] or st_fit[i]]
+    else:
+        d_weak = fits['match_flags'] & fit.MATCH_WEAK
+        mfl = fits['match_flags'].cpu().tolist()
+        skipped = [dict(index=i, name=names[i], det_left=st_l[i], det_right=st_r[i], fit=st_fit[i], match=mfl[i])
+                   for i in range(F) if st_l[i] or st_r[i] or st_fit[i] or (mfl[i] & fit.MATCH_WEAK)]
     res = dict(names=names, angles=angles, records=recs, pts3=fits['pts3'], cnt=fits['m'], cyl_raw=fits['cyl_raw'], skipped=skipped,
                T_cam_agv=None, fval=None)
+    if match_offset is not None:
+        res.update(offset=fits['offset'], match_score=fits['match_score'], match_flags=fits['match_flags'])
     if mat_path is not None:
         api.save_mat(mat_path, fits=fits, names=names)
     if multi_frame in ('gpu', 'lm'):
         # resident: the kept frames are named by a device mask made from the records' status words, the whole tables go in
         # as one group, and T, fval, status and the count of kept frames come back in one copy
-        frame_ok = ((d_fit == 0) & (d_l == 0) & (d_r == 0)).to(torch.int32)
+        frame_ok = (d_fit == 0) & (d_l == 0) & (d_r == 0)
+        if match_offset is not None:
+            frame_ok = frame_ok & (d_weak == 0)
+        frame_ok = frame_ok.to(torch.int32)
         mf = multiframe.fit_multi_frame_gpu(fits['pts3'], fits['m'], fits['cyl_raw'], angles, radius, frame_ok=frame_ok,
                                             group_start=[0, F], method='lm' if multi_frame == 'lm' else 'nm')
         back = torch.cat([mf['T'][0], mf['fvals'][0], mf['status'][0:1].to(torch.float64),

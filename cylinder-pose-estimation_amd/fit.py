@@ -146,11 +146,55 @@ def fit_cylinder_ransac_batch(pts3, cnt, radius, hypotheses=64, sample=12, tau=0
     return dict(cyl_raw=raw, cyl=cyl, T=T, fvals=fv, iters=it, status=st, n_inliers=ninl, inlier_mask=mask)
 
 
+MATCH_MAX_WIN = 8                                                                   # CPE_MATCH_MAX_WIN
+MATCH_SHIFTED, MATCH_WEAK, MATCH_EDGE, MATCH_OVERFLOW = 1, 2, 4, 8                  # CPE_MATCH_FLAG_*
+
+
+def match_offset_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, radius, win_c=4, win_r=4, th=0.3, tau=0.5, hyp_iters=8,
+                       min_score=8, want_scores=True):
+    """BUILD-DEFINED (the reference has nothing like it): the (dc, dr) to add to the (col,row) indices of table 1 so that the
+    index join pairs the same grid points in both images, found by scoring every shift of the window with the fixed-radius
+    cylinder; see include/cpe.h cpe_match_offset_batch.
+    -> dict(offset i32[n,2], score i32[n,4] (best, runner-up, at (0,0), pairs kept at the winner), scores i32[n,ncand] (None
+            without want_scores), flags i32[n] (MATCH_*), id1 i32[n,MAXP,2] = gp1.id + offset, tables = gp1 with that id)"""
+    L = _lib.load()
+    dev = gp1.xy.device
+    n = gp1.cnt.shape[0]
+    if not (0 <= win_c <= MATCH_MAX_WIN and 0 <= win_r <= MATCH_MAX_WIN):
+        raise ValueError(f'match_offset_batch: window {win_c} x {win_r} outside 0..{MATCH_MAX_WIN}')
+    K1 = _dev3(K1, dev, (9,)); K2 = _dev3(K2, dev, (9,)); T21 = _dev3(T21, dev, (16,))
+    ncand = (2 * win_c + 1) * (2 * win_r + 1)
+    ws_bytes = L.cpe_match_offset_workspace_bytes(n, win_c, win_r)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    offset = torch.zeros((n, 2), dtype=torch.int32, device=dev); score = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    scores = torch.zeros((n, ncand), dtype=torch.int32, device=dev) if want_scores else None
+    flags = torch.zeros(n, dtype=torch.int32, device=dev); id1 = torch.zeros((n, MAXP, 2), dtype=torch.int32, device=dev)
+    prm = _lib.CpeMatchParams(win_c, win_r, th, tau, hyp_iters, min_score)
+    _lib.check(L.cpe_match_offset_batch(gp1.xy.data_ptr(), gp1.id.data_ptr(), gp1.cnt.data_ptr(), gp2.xy.data_ptr(), gp2.id.data_ptr(),
+                                        gp2.cnt.data_ptr(), n, K1.data_ptr(), K2.data_ptr(), T21.data_ptr(), float(radius),
+                                        C.addressof(prm), ws.data_ptr(), ws_bytes, offset.data_ptr(), score.data_ptr(),
+                                        scores.data_ptr() if want_scores else None, flags.data_ptr(), id1.data_ptr(), _stream()),
+               'cpe_match_offset_batch')
+    return dict(offset=offset, score=score, scores=scores, flags=flags, id1=id1, tables=GridTables(gp1.xy, id1, gp1.cnt), _ws=ws)
+
+
 def fit_single_cylinder_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, radius, selector=SEL_CHOOSE_IDX,
-                              patch=3, th=0.3, ransac=None, **fit_kw):
+                              patch=3, th=0.3, ransac=None, match=None, **fit_kw):
     """[pts3, cylT, fvals, meanError] = fitSingleCylinder(...) for every frame of the batch.
     status: the fit's (ST_OK / ST_FEW_POINTS), or ST_OVERFLOW where the selector set FLAG_OVERFLOW (all outputs zero).
-    ransac: None (reference behaviour) or a dict of fit_cylinder_ransac_batch keywords (build-defined config 5)."""
+    ransac: None (reference behaviour) or a dict of fit_cylinder_ransac_batch keywords (build-defined config 5).
+    match: None (reference behaviour: equal indices are the same grid point) or a dict of match_offset_batch keywords
+    (build-defined; {} = its defaults): the index shift between the two tables is searched first, and the selector and the fit
+    get table 1 with the shift applied (`idx` is then in the numbering of image 2).  The result always holds offset i32[n,2],
+    match_score i32[n,4] and match_flags i32[n]; all zeros when the search is off."""
+    n, dev = gp1.cnt.shape[0], gp1.xy.device
+    if match is not None:
+        mo = match_offset_batch(gp1, gp2, K1, K2, T21, radius, **dict(match, want_scores=False))
+        gp1 = mo['tables']
+        extra = dict(offset=mo['offset'], match_score=mo['score'], match_flags=mo['flags'], _match_ws=mo['_ws'])
+    else:
+        z = torch.zeros((n, 7), dtype=torch.int32, device=dev)       # (one fill: this is the path of every call without the search)
+        extra = dict(offset=z[:, 0:2], match_score=z[:, 2:6], match_flags=z[:, 6])
     sel = select_triangulate_batch(gp1, gp2, K1, K2, T21, selector, patch, th)
     if ransac is not None:
         fit = fit_cylinder_ransac_batch(sel['pts3'], sel['m'], radius, **ransac, **fit_kw)
@@ -160,4 +204,5 @@ def fit_single_cylinder_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, rad
     fit['status'].masked_fill_((sel['flags'] & FLAG_OVERFLOW) != 0, ST_OVERFLOW)
     out = dict(sel)
     out.update(fit)
+    out.update(extra)
     return out

@@ -71,6 +71,9 @@ _SIGS = {
     'cpe_frame_angles_lm_batch': (C.c_int32, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p] + [C.c_void_p] * 9),
     'cpe_fit_cylinder_ransac_batch': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p] +
                                       [C.c_void_p] * 9),
+    'cpe_match_offset_workspace_bytes': (C.c_size_t, [C.c_int32] * 3),
+    'cpe_match_offset_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_double, C.c_void_p, C.c_void_p, C.c_size_t] +
+                               [C.c_void_p] * 6),
     'cpe_undistort_map': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_remap_bilinear_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_undistort_map_matlab': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -119,6 +122,11 @@ class CpeFitParams(C.Structure):
 class CpeRansacParams(C.Structure):
     _fields_ = [('hypotheses', C.c_int32), ('sample', C.c_int32), ('tau', C.c_double), ('seed', C.c_uint64),
                 ('frame0', C.c_uint64), ('hyp_iters', C.c_int32), ('reserved', C.c_int32)]
+
+
+class CpeMatchParams(C.Structure):
+    _fields_ = [('win_c', C.c_int32), ('win_r', C.c_int32), ('th', C.c_double), ('tau', C.c_double), ('hyp_iters', C.c_int32),
+                ('min_score', C.c_int32)]
 
 
 MAXP = 2048

@@ -31,11 +31,12 @@ class FramePipeline:
     """reusable workspaces for chunks of `chunk` stereo frames of size h x w"""
 
     def __init__(self, h, w, K1, K2, T21, radius, chunk=64, device='cuda:0', selector=fit.SEL_CHOOSE_IDX, th=0.3,
-                 fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full'):
+                 fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full', match=None):
         self.h, self.w, self.chunk, self.device = h, w, chunk, torch.device(device)
         self.K1, self.K2, self.T21, self.radius = K1, K2, T21, radius
         self.selector, self.th, self.fit_mode = selector, th, fit_mode
         self.ransac = ransac            # None, or keywords of fit.fit_cylinder_ransac_batch (build-defined config 5)
+        self.match = match              # None, or keywords of fit.match_offset_batch (build-defined: the index-shift search, stage 'full')
         if stage not in ('full', 'detect'):
             raise ValueError("stage is 'full' or 'detect'")
         self.stage = stage              # 'detect': stop after chooseIdx + triangulate (fitSingleCylinder.m:12-17), no cylinder fit
@@ -86,7 +87,7 @@ class FramePipeline:
             return rec, det, out
         rk = None if self.ransac is None else dict(self.ransac, frame0=int(self.ransac.get('frame0', 0)) + frame0)
         out = fit.fit_single_cylinder_batch(g1, g2, self.K1, self.K2, self.T21, self.radius, self.selector, 3, self.th,
-                                            ransac=rk, mode=self.fit_mode)
+                                            ransac=rk, match=self.match, mode=self.fit_mode)
         rec = torch.empty((c, REC), dtype=torch.float64, device=frames.device)
         rec[:, 0:6] = out['cyl'][:, 0]
         rec[:, 6:12] = out['cyl'][:, 1]
@@ -147,7 +148,8 @@ class FramePipeline:
 
 
 FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), m=((), torch.int32), cyl_raw=((2, 6), torch.float64), cyl=((2, 6), torch.float64),
-                   T=((4, 4), torch.float64), fvals=((2,), torch.float64), mean_err=((), torch.float64), status=((), torch.int32))
+                   T=((4, 4), torch.float64), fvals=((2,), torch.float64), mean_err=((), torch.float64), status=((), torch.int32),
+                   offset=((2,), torch.int32), match_score=((4,), torch.int32), match_flags=((), torch.int32))
 
 
 def alloc_fits(F, device):

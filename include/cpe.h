@@ -36,13 +36,14 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 115   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 116   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
                              111: cpe_debug_clahe_planes_bgr; 112: cpe_multi_frame_fit_batch, cpe_pose_vec2T_batch,
                              cpe_pose_T2vec_batch; 113: cpe_multi_frame_fit_lm_batch; 114: cpe_agv_chain_batch,
-                             cpe_frame_angles_lm_batch; 115: cpe_debug_region_hull) */
+                             cpe_frame_angles_lm_batch; 115: cpe_debug_region_hull; 116: cpe_match_offset_batch,
+                             cpe_match_offset_workspace_bytes) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -503,6 +504,65 @@ CPE_API int32_t cpe_fit_cylinder_ransac_batch(const double *X, const int32_t *cn
                                               const CpeFitParams *params, const CpeRansacParams *ransac, double *cyl_raw,
                                               double *cyl, double *T, double *fvals, int32_t *iters, int32_t *status,
                                               int32_t *n_inliers, uint8_t *inlier_mask, void *stream);
+
+/* BUILD-DEFINED extension (nothing like it in the reference): stereo matching that survives a grid-index shift between the
+ * two images of a frame.  The selectors above pair points of equal (col,row); a detector that numbers one image a column or a
+ * row off (a spot ellipse that cuts the centre column) leaves pairs that still pass the reprojection
+ * test -- a column shift moves the partner along the epipolar line -- at a wrong depth.  This call searches the shift of
+ * table 1 under which the triangulated points lie on a cylinder of the known radius, one wavefront per (frame, candidate).
+ *
+ * Score of the candidate (dc, dr), dc in [-win_c, win_c], dr in [-win_r, win_r] (the order is part of the contract):
+ *   1. (dc, dr) is added to every index of table 1;
+ *   2. plain index join with table 2 as findGridCorrespondences does: image-1 order, a duplicate index of table 2 is looked
+ *      up through its first occurrence, every row of table 1 that finds a partner is a pair, no fallback;
+ *   3. every pair is triangulated (the DLT of cpe_triangulate_batch);
+ *   4. the pairs with err < th are kept, in join order;
+ *   5. fewer than CPE_FIT_MIN_POINTS kept pairs: score 0;
+ *   6. otherwise the initial cylinder of cpe_fit_cylinder_batch on the kept points and hyp_iters iterations of its
+ *      CPE_FIT_LM mode (tolerances 1e-5); a non-finite initial or final cylinder: score 0;
+ *   7. score = number of kept points with |dist(point, axis) - radius| < tau (the inlier test of
+ *      cpe_fit_cylinder_ransac_batch).
+ * Winner: the candidate with the smallest key (-score, |dc|+|dr|, |dc|, dc, dr), so (0,0) wins every tie it is part of.
+ *
+ *   inputs   the tables, K1, K2, T21 as cpe_select_triangulate_batch; radius as cpe_fit_cylinder_batch; params NULL = defaults
+ *   ws       cpe_match_offset_workspace_bytes(n, win_c, win_r) bytes of device scratch (0 for a window outside
+ *            0..CPE_MATCH_MAX_WIN)
+ *   offset   i32[n,2]  the shift (dc, dr) applied to table 1
+ *   score    i32[n,4]  best score | runner-up (the second-largest value among all candidates; 0 with a single candidate) |
+ *                      score at (0,0) | pairs kept at the winner
+ *   scores   i32[n,ncand] or NULL: every candidate, ncand = (2 win_c + 1)(2 win_r + 1), dc the outer index, dr the inner,
+ *            both ascending
+ *   flags    i32[n]    CPE_MATCH_FLAG_* (independent bits)
+ *   id1_out  i32[n,CPE_MAXP,2]  id1 + offset in the slots below cnt1 (slots past it are not written); may not be id1.
+ *            cpe_select_triangulate_batch and the fit read it in place of id1: the absolute numbering then follows image
+ *            2, which is harmless because only the correspondence reaches the fit.
+ * cnt1 / cnt2 are clamped to [0, CPE_MAXP]; slots past them are never read.  An empty table on either side scores 0
+ * everywhere (offset (0,0), CPE_MATCH_FLAG_WEAK unless min_score is 0).  Table 2 goes through a dense CPE_FIT_TABLE_DIM x
+ * CPE_FIT_TABLE_DIM table, built once per frame: a frame with two non-empty tables whose table 2 spans CPE_FIT_TABLE_DIM or
+ * more in either direction, or that has an index outside [-9999, 9999] in either table -- a frame
+ * cpe_select_triangulate_batch refuses too -- gets CPE_MATCH_FLAG_OVERFLOW, offset (0,0) and scores 0.
+ * Limits: one shift per frame (a piecewise shift, such as a centre column split in two, recovers only its larger part);
+ * cylinder target only (the planar target has no radius to score with).
+ * Kernel launches on `stream` only (table, one scoring launch per size class of table 1, winner), no host synchronisation. */
+#define CPE_MATCH_MAX_WIN 8
+#define CPE_MATCH_FLAG_SHIFTED 1   /* a non-zero offset was chosen and applied */
+#define CPE_MATCH_FLAG_WEAK 2      /* the best score is below min_score: the winner is not trusted, offset forced to (0,0) */
+#define CPE_MATCH_FLAG_EDGE 4      /* the winner lies on the border of a non-zero window: the true shift may lie outside
+                                      (the offset is still applied unless the frame is also WEAK) */
+#define CPE_MATCH_FLAG_OVERFLOW 8  /* an index the dense table cannot hold (see above): offset (0,0), scores 0 */
+typedef struct CpeMatchParams {
+    int32_t win_c, win_r;   /* candidates dc in [-win_c, win_c], dr in [-win_r, win_r]; 0..CPE_MATCH_MAX_WIN; default 4, 4 */
+    double th;              /* reprojection error a pair must stay under, px; default 0.3 (fitSingleCylinder.m:12) */
+    double tau;             /* inlier band |dist - radius| < tau, the unit of the points; default 0.5 (CpeRansacParams) */
+    int32_t hyp_iters;      /* LM iterations per candidate, 1..200; default 8 (CpeRansacParams) */
+    int32_t min_score;      /* a winner below this is not trusted (>= 0); default 8 */
+} CpeMatchParams;
+CPE_API size_t cpe_match_offset_workspace_bytes(int32_t n, int32_t win_c, int32_t win_r);
+CPE_API int32_t cpe_match_offset_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
+                                       const int32_t *id2, const int32_t *cnt2, int32_t n, const double *K1, const double *K2,
+                                       const double *T21, double radius, const CpeMatchParams *params, void *ws, size_t ws_bytes,
+                                       int32_t *offset, int32_t *score, int32_t *scores, int32_t *flags, int32_t *id1_out,
+                                       void *stream);
 
 /* Row f-3: the undistortion pre-step of the CLI entry point, utils/iotool.py:22-39
  *   undistort_image(image, camera_params) = cv2.undistort(image, IntrinsicMatrix, hstack(Radial, Tangential))
