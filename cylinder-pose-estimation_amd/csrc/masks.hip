@@ -380,35 +380,94 @@ struct Taps { int k[19]; int r; int shift; };
 //   BLUR_RECT (7x7): only the box means around the intersection points are read (find_center_point, :1548-1560), and
 //     those points lie inside the region rectangle: tiles away from rect +- (half + 1) are left untouched.
 constexpr int BT_X = 64, BT_Y = 32;
-// one BT_X x BT_Y tile: both passes through LDS (workgroup-wide; ends with the stores, no barrier after them)
+// one BT_X x BT_Y tile of the 7 x 7 blur (workgroup-wide, 256 threads; ends with the stores, no barrier after them).
+// The window (columns gx0 - 4 .. gx0 + BT_X + 3, dword aligned) goes to LDS with dword loads where the tile and its apron lie
+// inside the frame and the rows are 4-byte aligned, byte by byte with reflect101 otherwise.  Row sums: a thread makes 8
+// neighbouring sums from 4 dwords of the window (v_alignbyte_b32 + two v_dot4_u32_u8 per sum, as blur19_tile_spot does) and
+// stores them as one 16-byte LDS write; the window is in registers by then, so the row sums take its place in LDS.  Column
+// pass: a thread makes 4 neighbouring columns of 2 neighbouring rows from 8 eight-byte reads and stores a dword per row.
+constexpr int B7_R = 3, B7_IH = BT_Y + 2 * B7_R, B7_QW = (BT_X + 8) / 4;
+constexpr int B7_LDS_WORDS = B7_IH * BT_X / 2;     // u16 row sums of the window's rows (>= B7_IH * B7_QW window dwords)
+static_assert(B7_IH * B7_QW <= B7_LDS_WORDS && BT_X == 64 && BT_Y == 32, "blur_tile's thread maps");
 template <int R>
 __device__ __forceinline__ void blur_tile(const uint8_t *__restrict__ im, int h, int w, int gx0, int gy0, const Taps &t,
-                                          uint8_t *__restrict__ out, uint8_t *s_in, uint16_t *s_h)
+                                          uint8_t *__restrict__ out, uint32_t *s_buf /* B7_LDS_WORDS */)
 {
-    constexpr int IW = BT_X + 2 * R, IH = BT_Y + 2 * R;
+    static_assert(R == B7_R, "the 7 x 7 tile");
+    constexpr int IH = B7_IH, QW = B7_QW, TASKS = IH * (BT_X / 8), PER = (TASKS + 255) / 256;
     const int tid = threadIdx.x;
-    for (int i = tid; i < IH * IW; i += 256) {
-        int ry = i / IW, rx = i - ry * IW;
-        s_in[i] = im[(size_t)reflect101(gy0 - R + ry, h) * w + reflect101(gx0 - R + rx, w)];
+    const int ax0 = gx0 - 4, ay0 = gy0 - R;
+    if (ax0 >= 0 && ax0 + 4 * QW <= w && ay0 >= 0 && ay0 + IH <= h && (w & 3) == 0 && (((size_t)im) & 3) == 0) {
+        for (int i = tid; i < IH * QW; i += 256) {
+            const int ry = i / QW, q = i - ry * QW;
+            s_buf[i] = *reinterpret_cast<const uint32_t *>(im + (size_t)(ay0 + ry) * w + ax0 + 4 * q);
+        }
+    } else {
+        uint8_t *s_in8 = reinterpret_cast<uint8_t *>(s_buf);
+        for (int i = tid; i < IH * QW * 4; i += 256) {
+            const int ry = i / (4 * QW), b = i - ry * 4 * QW;
+            s_in8[i] = im[(size_t)reflect101(ay0 + ry, h) * w + reflect101(ax0 + b, w)];
+        }
     }
     __syncthreads();
-    for (int i = tid; i < IH * BT_X; i += 256) {
-        int ry = i / BT_X, rx = i - ry * BT_X;
-        const uint8_t *p = &s_in[ry * IW + rx];
-        int sacc = 0;
+    // tile column c is window byte c + 4: the sum of column c0 + o reads window bytes c0 + o + 1 .. c0 + o + 7
+    uint32_t d[PER][4];
 #pragma unroll
-        for (int j = 0; j <= 2 * R; j++) sacc += t.k[j] * p[j];
-        s_h[i] = (uint16_t)sacc;
+    for (int u = 0; u < PER; u++) {
+        const int it = tid + 256 * u;
+        if (it < TASKS) {
+            const int ry = it >> 3, c0 = (it & 7) * 8;
+#pragma unroll
+            for (int k = 0; k < 4; k++) d[u][k] = s_buf[ry * QW + (c0 >> 2) + k];
+        }
     }
     __syncthreads();
-    for (int i = tid; i < BT_Y * BT_X; i += 256) {
-        int ry = i / BT_X, rx = i - ry * BT_X;
-        const uint16_t *p = &s_h[ry * BT_X + rx];
-        int sacc = 0;
+    const uint32_t T0 = (uint32_t)t.k[0] | ((uint32_t)t.k[1] << 8) | ((uint32_t)t.k[2] << 16) | ((uint32_t)t.k[3] << 24);
+    const uint32_t T1 = (uint32_t)t.k[4] | ((uint32_t)t.k[5] << 8) | ((uint32_t)t.k[6] << 16);
 #pragma unroll
-        for (int j = 0; j <= 2 * R; j++) sacc += t.k[j] * (int)p[j * BT_X];
-        if (gy0 + ry < h && gx0 + rx < w)
-            out[(size_t)(gy0 + ry) * w + gx0 + rx] = (uint8_t)((sacc + (1 << (t.shift - 1))) >> t.shift);
+    for (int u = 0; u < PER; u++) {
+        const int it = tid + 256 * u;
+        if (it < TASKS) {
+            uint32_t hs[8];
+#pragma unroll
+            for (int o = 0; o < 8; o++) {
+                const int sb = o + 1, i0 = sb >> 2, i1 = (sb + 4) >> 2, sh = sb & 3;
+                const uint32_t a0 = sh ? __builtin_amdgcn_alignbyte(d[u][i0 + 1], d[u][i0], sh) : d[u][i0];
+                const uint32_t a1 = sh ? __builtin_amdgcn_alignbyte(d[u][i1 < 3 ? i1 + 1 : 3], d[u][i1], sh) : d[u][i1];
+                hs[o] = __builtin_amdgcn_udot4(a1, T1, __builtin_amdgcn_udot4(a0, T0, 0u, false), false);
+            }
+            // s_h[ry * BT_X + c0 + o] as u16: 8 of them are 16 aligned bytes
+            reinterpret_cast<uint4 *>(s_buf)[it] = make_uint4(hs[0] | (hs[1] << 16), hs[2] | (hs[3] << 16), hs[4] | (hs[5] << 16), hs[6] | (hs[7] << 16));
+        }
+    }
+    __syncthreads();
+    const int cg = tid & 15, ry = (tid >> 4) * 2;      // columns 4 cg .. 4 cg + 3 of rows ry, ry + 1
+    uint32_t acc[2][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+#pragma unroll
+    for (int j = 0; j < 2 * R + 2; j++) {
+        const uint2 p = reinterpret_cast<const uint2 *>(s_buf)[(ry + j) * (BT_X / 4) + cg];
+        const uint32_t e[4] = {p.x & 0xFFFFu, p.x >> 16, p.y & 0xFFFFu, p.y >> 16};
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            if (j <= 2 * R) acc[0][c] += (uint32_t)t.k[j] * e[c];
+            if (j >= 1) acc[1][c] += (uint32_t)t.k[j - 1] * e[c];
+        }
+    }
+    const uint32_t rnd = 1u << (t.shift - 1);
+    const int gx = gx0 + 4 * cg;
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int gy = gy0 + ry + q;
+        if (gy >= h) continue;
+        uint8_t *o = out + (size_t)gy * w + gx;
+        uint32_t b[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) b[c] = ((acc[q][c] + rnd) >> t.shift) & 255u;
+        if (gx + 4 <= w && (((size_t)o) & 3) == 0) *reinterpret_cast<uint32_t *>(o) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+        else {
+#pragma unroll
+            for (int c = 0; c < 4; c++) if (gx + c < w) o[c] = (uint8_t)b[c];
+        }
     }
 }
 
@@ -417,9 +476,7 @@ template <int R>
 __global__ __launch_bounds__(256) void k_blur_fused(const uint8_t *__restrict__ src, int h, int w, int tiles_x, int tiles_y, Taps t,
                                                     const FrameState *__restrict__ st, uint8_t *__restrict__ dst)
 {
-    constexpr int IW = BT_X + 2 * R, IH = BT_Y + 2 * R;
-    __shared__ uint8_t s_in[IH * IW];
-    __shared__ uint16_t s_h[IH * BT_X];
+    __shared__ uint4 s_buf[B7_LDS_WORDS / 4];
     const int tiles = tiles_x * tiles_y;
     const int f = blockIdx.x / tiles, tt = blockIdx.x - f * tiles;
     const int gx0 = (tt % tiles_x) * BT_X, gy0 = (tt / tiles_x) * BT_Y;
@@ -434,7 +491,7 @@ __global__ __launch_bounds__(256) void k_blur_fused(const uint8_t *__restrict__ 
     if (gx0 > S.rect[0] + S.rect[2] + m || gx0 + BT_X < S.rect[0] - m || gy0 > S.rect[1] + S.rect[3] + m ||
         gy0 + BT_Y < S.rect[1] - m)
         return;
-    blur_tile<R>(src + f * N, h, w, gx0, gy0, t, dst + f * N, s_in, s_h);
+    blur_tile<R>(src + f * N, h, w, gx0, gy0, t, dst + f * N, reinterpret_cast<uint32_t *>(s_buf));
 }
 
 // BLUR_SPOT (19 x 19) in two steps.  k_spot_scan reads the frame once (16-byte loads, a band of BT_Y rows per workgroup) and

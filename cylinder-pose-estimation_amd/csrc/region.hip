@@ -735,120 +735,303 @@ __device__ double wave_median(Get get, int n, int lane, double *s_buf, int *s_hi
     return (v1 + v2) / 2.;
 }
 
-// radius = median distance of the border points from the centre: one wavefront per blob.
-// The square root is monotone, so the two middle distances are the roots of the two middle squared distances.
-// Common case (border of up to 496 points, ids of its chunks in the blob record): the squared distances stay in
-// registers, a 64-bucket histogram over [min, max] (monotone bucket map) finds the bucket that holds rank k, and only
-// that bucket's few members are compared with each other -- O(n) instead of the O(n^2) rank count of the general path.
-constexpr int MED_FAST = CH_DIRECT * CH_PTS;
+// 16-lane collectives on the DPP rows of a wavefront (lanes 16 r .. 16 r + 15): one VALU instruction per step and dword, no
+// LDS traffic.  row_shr leaves `old` in the lanes whose source lies outside the row, row_ror rotates inside the row.
+constexpr int DPP_ROW_SHR = 0x110, DPP_ROW_ROR = 0x120;
+template <int CTRL> __device__ __forceinline__ int dpp_int(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xF, 0xF, false); }
+template <int CTRL> __device__ __forceinline__ double dpp_f64(double v)
+{
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return __hiloint2double(dpp_int<CTRL>(hi, hi), dpp_int<CTRL>(lo, lo));
+}
+__device__ __forceinline__ double row_min_f64(double v)
+{
+    v = fmin(v, dpp_f64<DPP_ROW_ROR + 1>(v)); v = fmin(v, dpp_f64<DPP_ROW_ROR + 2>(v));
+    v = fmin(v, dpp_f64<DPP_ROW_ROR + 4>(v)); return fmin(v, dpp_f64<DPP_ROW_ROR + 8>(v));
+}
+__device__ __forceinline__ double row_max_f64(double v)
+{
+    v = fmax(v, dpp_f64<DPP_ROW_ROR + 1>(v)); v = fmax(v, dpp_f64<DPP_ROW_ROR + 2>(v));
+    v = fmax(v, dpp_f64<DPP_ROW_ROR + 4>(v)); return fmax(v, dpp_f64<DPP_ROW_ROR + 8>(v));
+}
+__device__ __forceinline__ int row_scan_max_int(int v, int identity)   // inclusive
+{
+    v = max(v, dpp_int<DPP_ROW_SHR + 1>(identity, v)); v = max(v, dpp_int<DPP_ROW_SHR + 2>(identity, v));
+    v = max(v, dpp_int<DPP_ROW_SHR + 4>(identity, v)); return max(v, dpp_int<DPP_ROW_SHR + 8>(identity, v));
+}
+__device__ __forceinline__ int row_scan_add_int(int v)                 // inclusive
+{
+    v += dpp_int<DPP_ROW_SHR + 1>(0, v); v += dpp_int<DPP_ROW_SHR + 2>(0, v);
+    v += dpp_int<DPP_ROW_SHR + 4>(0, v); return v + dpp_int<DPP_ROW_SHR + 8>(0, v);
+}
 
-// part 0: the blobs of the hole borders [0, NA), part 1: those of the bright components [NA, NB)
-__global__ __launch_bounds__(64) void k_blob_median(int part, int *__restrict__ sw, BlobRec *__restrict__ blobs_all,
+// radius = median distance of the border points from the centre.
+// The square root is monotone, so the two middle distances are the roots of the two middle squared distances.
+// Borders whose points are stored, with the ids of their chunks in the blob record (up to 496 points): the squared
+// distances stay in registers, a histogram over [min, max] (monotone bucket map) finds the bucket that holds rank k, and
+// only that bucket's few members are compared with each other -- O(n) instead of the O(n^2) rank count of the general path.
+//   n <= MED_Q: a quarter wavefront (one DPP row of 16 lanes, 8 points per lane, 16 buckets) per border, four borders at a
+//     time: the grid dots' borders are 110 - 140 points long, a whole wavefront had 2 of its 8 point slots filled;
+//   n <= MED_FAST: a whole wavefront with ceil(n / 64) point slots per lane and 64 buckets.
+constexpr int MED_FAST = CH_DIRECT * CH_PTS;
+constexpr int MED_Q = 128, MED_Q_IDS = (MED_Q + CH_PTS - 1) / CH_PTS;
+
+// four borders of at most MED_Q stored points, one per row (act: this row has one); all 64 lanes take part
+__device__ __forceinline__ void median_rows(bool act, int bi, int n, BlobRec *__restrict__ blobs, const uint32_t *__restrict__ pool,
+                                            const unsigned short *__restrict__ blob_ch, double *s_d /* 4 * MED_Q */,
+                                            int *s_hist /* 64 */, int *s_cnt /* 4 */, int lane)
+{
+    const int g = lane >> 4, gl = lane & 15;
+    if (!act) n = 0;
+    double cx = 0.0, cy = 0.0;
+    int myid = 0;
+    if (act) {
+        cx = blobs[bi].x; cy = blobs[bi].y;
+        if (gl < MED_Q_IDS) myid = (int)blob_ch[bi * CH_DIRECT + gl];
+    }
+    double v[MED_Q / 16];
+    double mn = 1e300, mx = -1.0;
+#pragma unroll
+    for (int m = 0; m < MED_Q / 16; m++) {
+        const int i = gl + 16 * m;
+        const bool valid = i < n;
+        const int c = __shfl(myid, (lane & 48) | (valid ? i / CH_PTS : 0), 64);
+        v[m] = -1.0;
+        if (valid) {
+            const uint32_t p = pool[(uint32_t)c * 32u + (uint32_t)(i % CH_PTS)];   // (32-bit offset: c <= 65535)
+            const double dx = cx - (double)(int)(p & 0xFFFFu), dy = cy - (double)(int)(p >> 16);
+            v[m] = dx * dx + dy * dy;
+            mn = fmin(mn, v[m]); mx = fmax(mx, v[m]);
+        }
+    }
+    mn = row_min_f64(mn); mx = row_max_f64(mx);
+    double res0 = mn, res1 = mn;
+    const bool spread = mx > mn;                   // (per row; never for a row without a border)
+    if (__any(spread)) {
+        const double scale = 16.0 / (mx - mn);
+        uint32_t bkt = 0;                          // 4 bits per point slot (slots without a point: v < 0)
+        __syncthreads();
+        s_hist[lane] = 0;
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < MED_Q / 16; m++) {
+            if (spread && v[m] >= 0.0) {
+                const int b = min(15, (int)((v[m] - mn) * scale));
+                bkt |= (uint32_t)b << (4 * m);
+                atomicAdd(&s_hist[16 * g + b], 1);
+            }
+        }
+        __syncthreads();
+        const int hc = s_hist[lane], incl = row_scan_add_int(hc);
+        const int k0 = (n - 1) / 2, k1 = n / 2;
+        // first bucket whose running count exceeds k, and the rank inside that bucket
+        const int b0 = __popc((unsigned)(__ballot(incl <= k0) >> (16 * g)) & 0xFFFFu) & 15;
+        const int b1 = __popc((unsigned)(__ballot(incl <= k1) >> (16 * g)) & 0xFFFFu) & 15;
+        const int kk0 = k0 - __shfl(incl - hc, (lane & 48) | b0, 64), kk1 = k1 - __shfl(incl - hc, (lane & 48) | b1, 64);
+        // the members of bucket `sel` (< 0: none) ranked against each other: the values of ranks ka and kb inside it
+        auto rank_in = [&](int sel, int ka, int kb, double &fa, double &fb) {
+            __syncthreads();
+            if (gl == 0) s_cnt[g] = 0;
+            __syncthreads();
+            double *d = s_d + MED_Q * g;
+#pragma unroll
+            for (int m = 0; m < MED_Q / 16; m++)
+                if (v[m] >= 0.0 && (int)((bkt >> (4 * m)) & 15u) == sel) d[atomicAdd(&s_cnt[g], 1)] = v[m];
+            __syncthreads();
+            const int sz = s_cnt[g];
+            fa = -1.0; fb = -1.0;
+            for (int j = gl; j < sz; j += 16) {
+                const double x = d[j];
+                int less = 0, leq = 0;
+                for (int q = 0; q < sz; q++) { const double y = d[q]; less += (y < x) ? 1 : 0; leq += (y <= x) ? 1 : 0; }
+                if (less <= ka && ka < leq) fa = x;
+                if (less <= kb && kb < leq) fb = x;
+            }
+            fa = row_max_f64(fa); fb = row_max_f64(fb);
+        };
+        double fa, fb;
+        rank_in(spread ? b0 : -2, kk0, kk1, fa, fb);
+        if (spread) { res0 = fa; res1 = b1 == b0 ? fb : fa; }
+        const bool second = spread && b1 != b0;    // the two middle ranks fall into different buckets
+        if (__any(second)) {
+            rank_in(second ? b1 : -2, kk1, kk1, fa, fb);
+            if (second) res1 = fa;
+        }
+    }
+    if (act && gl == 0) blobs[bi].r = (sqrt(res0) + sqrt(res1)) / 2.;
+}
+
+// one border of at most 64 SLOTS stored points (SLOTS <= MED_FAST / 64 + 1) on the whole wavefront
+template <int SLOTS>
+__device__ __forceinline__ double median_wave(int bi, int n, const BlobRec *__restrict__ blobs, const uint32_t *__restrict__ pool,
+                                              const unsigned short *__restrict__ blob_ch, double *s_d, int *s_hist, int *s_cnt, int lane)
+{
+    const double cx = blobs[bi].x, cy = blobs[bi].y;
+    const int myid = lane < CH_DIRECT ? (int)blob_ch[bi * CH_DIRECT + lane] : 0;
+    double v[SLOTS];
+    double mn = 1e300, mx = -1.0;
+#pragma unroll
+    for (int m = 0; m < SLOTS; m++) {
+        const int i = lane + 64 * m;
+        const bool valid = i < n;
+        const int c = __shfl(myid, valid ? i / CH_PTS : 0, 64);
+        v[m] = -1.0;
+        if (valid) {
+            const uint32_t p = pool[(size_t)c * 32 + i % CH_PTS];
+            const double dx = cx - (double)(int)(p & 0xFFFFu), dy = cy - (double)(int)(p >> 16);
+            v[m] = dx * dx + dy * dy;
+            mn = fmin(mn, v[m]); mx = fmax(mx, v[m]);
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) { mn = fmin(mn, __shfl_xor(mn, off, 64)); mx = fmax(mx, __shfl_xor(mx, off, 64)); }
+    double res[2] = {mn, mn};
+    if (mx > mn) {
+        const double scale = 64.0 / (mx - mn);
+        int bkt[SLOTS];
+        __syncthreads();
+        s_hist[lane] = 0;
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < SLOTS; m++) {
+            bkt[m] = -1;
+            if (v[m] >= 0.0) { bkt[m] = min(63, (int)((v[m] - mn) * scale)); atomicAdd(&s_hist[bkt[m]], 1); }
+        }
+        __syncthreads();
+        const int hc = s_hist[lane];
+        int incl = hc;
+        for (int off = 1; off < 64; off <<= 1) { int tt = __shfl_up(incl, off, 64); if (lane >= off) incl += tt; }
+        const int ks[2] = {(n - 1) / 2, n / 2};
+        for (int which = 0; which < 2; which++) {
+            if (which == 1 && ks[1] == ks[0]) { res[1] = res[0]; break; }
+            const int k = ks[which];
+            const int bstar = __popcll(__ballot(incl <= k));          // first bucket whose running count exceeds k
+            const int kk = k - __shfl(incl - hc, bstar, 64);          // rank inside that bucket
+            const int sz = __shfl(hc, bstar, 64);
+            __syncthreads();
+            if (lane == 0) *s_cnt = 0;
+            __syncthreads();
+#pragma unroll
+            for (int m = 0; m < SLOTS; m++)
+                if (bkt[m] == bstar) s_d[atomicAdd(s_cnt, 1)] = v[m];
+            __syncthreads();
+            double found = -1.0;
+            for (int j = lane; j < sz; j += 64) {
+                const double x = s_d[j];
+                int less = 0, leq = 0;
+                for (int q = 0; q < sz; q++) { const double y = s_d[q]; less += (y < x) ? 1 : 0; leq += (y <= x) ? 1 : 0; }
+                if (less <= kk && kk < leq) found = x;
+            }
+            for (int off = 32; off >= 1; off >>= 1) found = fmax(found, __shfl_xor(found, off, 64));
+            res[which] = found;
+        }
+    }
+    return (sqrt(res[0]) + sqrt(res[1])) / 2.;
+}
+
+// the blob tables of one frame and threshold (blockIdx.y, blockIdx.z), as the tracers left them
+struct MedianSlot {
+    int nb;                        // blobs listed so far
+    BlobRec *blobs;
+    const int *blob_d;
+    double *dists;
+    const uint32_t *pool;
+    const unsigned short *blob_ch;
+};
+__device__ __forceinline__ MedianSlot median_slot(const int *S, int f, int slot, BlobRec *blobs_all, const int *blob_d_all,
+                                                  double *dists_all, const uint32_t *pool_all, const unsigned short *blob_ch_all,
+                                                  int maxch, int maxdf)
+{
+    const size_t fs = (size_t)f * NTHR + slot;
+    return MedianSlot{min(S[SW_NB + slot], MAXB), blobs_all + fs * MAXB, blob_d_all + fs * MAXB * 2, dists_all + (size_t)f * NTHR * maxdf,
+                      pool_all + fs * maxch * 32, blob_ch_all + fs * MAXB * CH_DIRECT};
+}
+__device__ __forceinline__ bool median_takes_rows(int code, int n) { return (code & PTS_STORED) && n <= MED_Q; }
+
+// Two kernels.  k_blob_median_rows runs after the hole borders are followed, before any bright component's blob is
+// appended: the blobs listed so far are the hole borders' [0, NA), and it takes the short stored ones among them, four
+// consecutive blobs at a time, one per row.  k_blob_median runs once both tracers are done and takes every other blob of
+// [0, NB), one after the other on the whole wavefront: the longer hole borders and the bright components (whose points are
+// never stored).  They are apart because the whole-wavefront paths need twice the registers: beside them the row path
+// ran with 3 wavefronts per SIMD, and it is a chain of dependent loads (blob -> chunk ids -> points) that only many
+// wavefronts in flight can hide.
+__global__ __launch_bounds__(64) void k_blob_median_rows(int *__restrict__ sw, BlobRec *__restrict__ blobs_all,
+                                                         const int *__restrict__ blob_d_all, double *__restrict__ dists_all,
+                                                         const uint32_t *__restrict__ pool_all,
+                                                         const unsigned short *__restrict__ blob_ch_all, int maxch, int maxdf)
+{
+    __shared__ double s_d[4 * MED_Q];
+    __shared__ int s_hist[64];
+    __shared__ int s_cnt[4];
+    const int f = blockIdx.y, slot = blockIdx.z, lane = threadIdx.x;
+    int *S = sw + (size_t)f * SW_STRIDE;
+    const MedianSlot m = median_slot(S, f, slot, blobs_all, blob_d_all, dists_all, pool_all, blob_ch_all, maxch, maxdf);
+    if (blockIdx.x == 0 && lane == 0) S[SW_NA + slot] = m.nb;   // the blobs that came from hole borders
+    for (int base = 4 * (int)blockIdx.x; base < m.nb; base += 4 * (int)gridDim.x) {
+        const int my = base + (lane >> 4);         // this row's blob
+        int code = -1, n = 0;
+        if (my < m.nb) { const int2 e = *reinterpret_cast<const int2 *>(m.blob_d + my * 2); code = e.x; n = e.y; }
+        const bool act = code >= 0 && n > 0 && median_takes_rows(code, n);
+        if (__any(act)) median_rows(act, my, n, m.blobs, m.pool, m.blob_ch, s_d, s_hist, s_cnt, lane);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_blob_median(const int *__restrict__ sw, BlobRec *__restrict__ blobs_all,
                                                     const int *__restrict__ blob_d_all, double *__restrict__ dists_all,
                                                     const uint32_t *__restrict__ pool_all,
-                                                    const unsigned short *__restrict__ blob_ch_all, FrameState *__restrict__ st,
-                                                    int maxch, int maxdf)
+                                                    const unsigned short *__restrict__ blob_ch_all, int maxch, int maxdf)
 {
     __shared__ double s_d[MED_FAST > SEL_CAP ? MED_FAST : SEL_CAP];
     __shared__ int s_ch[MAXCHAIN];
     __shared__ int s_hist[64];
     __shared__ int s_cnt;
     const int f = blockIdx.y, slot = blockIdx.z, lane = threadIdx.x;
-    int *S = sw + (size_t)f * SW_STRIDE;
-    // part 0 runs before any bright component's blob is appended: the blobs listed so far are the hole borders' (SW_NA)
-    const int nb = min(S[SW_NB + slot], MAXB);
-    if (!part && blockIdx.x == 0 && lane == 0) S[SW_NA + slot] = nb;
-    BlobRec *blobs = blobs_all + ((size_t)f * NTHR + slot) * MAXB;
-    const int *blob_d = blob_d_all + ((size_t)f * NTHR + slot) * MAXB * 2;
-    double *dists = dists_all + (size_t)f * NTHR * maxdf;
-    const uint32_t *pool = pool_all + ((size_t)f * NTHR + slot) * maxch * 32;
-    const unsigned short *blob_ch = blob_ch_all + ((size_t)f * NTHR + slot) * MAXB * CH_DIRECT;
-    for (int bi = (part ? S[SW_NA + slot] : 0) + blockIdx.x; bi < nb; bi += gridDim.x) {
-        const int code = blob_d[bi * 2], n = blob_d[bi * 2 + 1];
-        if (code < 0 || n <= 0) continue;
-        double r;
-        if ((code & PTS_STORED) && n <= MED_FAST) {
-            const double cx = blobs[bi].x, cy = blobs[bi].y;
-            const int myid = lane < CH_DIRECT ? (int)blob_ch[bi * CH_DIRECT + lane] : 0;
-            double v[MED_FAST / 64 + 1];
-            double mn = 1e300, mx = -1.0;
-#pragma unroll
-            for (int m = 0; m < MED_FAST / 64 + 1; m++) {
-                const int i = lane + 64 * m;
-                const bool valid = i < n;
-                const int c = __shfl(myid, valid ? i / CH_PTS : 0, 64);
-                v[m] = -1.0;
-                if (valid) {
-                    const uint32_t p = pool[(size_t)c * 32 + i % CH_PTS];
+    const MedianSlot m = median_slot(sw + (size_t)f * SW_STRIDE, f, slot, blobs_all, blob_d_all, dists_all, pool_all, blob_ch_all, maxch, maxdf);
+    const BlobRec *blobs = m.blobs;
+    const uint32_t *pool = m.pool;
+    // this workgroup's blobs are blockIdx.x + k gridDim.x; it looks at 64 of them at a time, one per lane, and then takes
+    // those that are neither empty nor the row kernel's one after the other (on grid frames: none of the hole borders)
+    for (int k0 = 0; (int)blockIdx.x + k0 * (int)gridDim.x < m.nb; k0 += 64) {
+        const int my = (int)blockIdx.x + (k0 + lane) * (int)gridDim.x;
+        int mcode = -1, mn = 0;
+        if (my < m.nb) { const int2 e = *reinterpret_cast<const int2 *>(m.blob_d + my * 2); mcode = e.x; mn = e.y; }
+        unsigned long long todo = __ballot(mcode >= 0 && mn > 0 && !median_takes_rows(mcode, mn));
+        while (todo) {
+            const int j = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int bi = (int)blockIdx.x + (k0 + j) * (int)gridDim.x;
+            const int code = __shfl(mcode, j, 64), n = __shfl(mn, j, 64);
+            double r;
+            if ((code & PTS_STORED) && n <= MED_FAST) {
+                switch ((n + 63) / 64) {           // (n > MED_Q: at least 3 slots)
+                case 3: r = median_wave<3>(bi, n, blobs, pool, m.blob_ch, s_d, s_hist, &s_cnt, lane); break;
+                case 4: r = median_wave<4>(bi, n, blobs, pool, m.blob_ch, s_d, s_hist, &s_cnt, lane); break;
+                case 5: r = median_wave<5>(bi, n, blobs, pool, m.blob_ch, s_d, s_hist, &s_cnt, lane); break;
+                case 6: r = median_wave<6>(bi, n, blobs, pool, m.blob_ch, s_d, s_hist, &s_cnt, lane); break;
+                case 7: r = median_wave<7>(bi, n, blobs, pool, m.blob_ch, s_d, s_hist, &s_cnt, lane); break;
+                default: r = median_wave<8>(bi, n, blobs, pool, m.blob_ch, s_d, s_hist, &s_cnt, lane); break;
+                }
+            } else if (code & PTS_STORED) {
+                // long border (> 496 points): chunk ids by walking the chain, distances recomputed from the points on every read
+                const int nch = (n + CH_PTS - 1) / CH_PTS;   // <= MAXCHAIN (StoreVisitor stops storing beyond that)
+                __syncthreads();
+                if (lane == 0) {
+                    int c = code & (PTS_STORED - 1);
+                    for (int q = nch - 1; q >= 0; q--) { s_ch[q] = c; c = (int)pool[(size_t)c * 32 + 31]; }
+                }
+                __syncthreads();
+                const double cx = blobs[bi].x, cy = blobs[bi].y;
+                auto get = [&](int i) {
+                    const uint32_t p = pool[(size_t)s_ch[i / CH_PTS] * 32 + i % CH_PTS];
                     const double dx = cx - (double)(int)(p & 0xFFFFu), dy = cy - (double)(int)(p >> 16);
-                    v[m] = dx * dx + dy * dy;
-                    mn = fmin(mn, v[m]); mx = fmax(mx, v[m]);
-                }
+                    return sqrt(dx * dx + dy * dy);
+                };
+                r = wave_median(get, n, lane, s_d, s_hist, &s_cnt);
+            } else {
+                const double *dd = m.dists + code;   // border followed a second time (bright components, pool overflow)
+                r = wave_median([&](int i) { return dd[i]; }, n, lane, s_d, s_hist, &s_cnt);
             }
-            for (int off = 32; off >= 1; off >>= 1) { mn = fmin(mn, __shfl_xor(mn, off, 64)); mx = fmax(mx, __shfl_xor(mx, off, 64)); }
-            double res[2] = {mn, mn};
-            if (mx > mn) {
-                const double scale = 64.0 / (mx - mn);
-                int bkt[MED_FAST / 64 + 1];
-                __syncthreads();
-                s_hist[lane] = 0;
-                __syncthreads();
-#pragma unroll
-                for (int m = 0; m < MED_FAST / 64 + 1; m++) {
-                    bkt[m] = -1;
-                    if (v[m] >= 0.0) { bkt[m] = min(63, (int)((v[m] - mn) * scale)); atomicAdd(&s_hist[bkt[m]], 1); }
-                }
-                __syncthreads();
-                const int hc = s_hist[lane];
-                int incl = hc;
-                for (int off = 1; off < 64; off <<= 1) { int tt = __shfl_up(incl, off, 64); if (lane >= off) incl += tt; }
-                const int ks[2] = {(n - 1) / 2, n / 2};
-                for (int which = 0; which < 2; which++) {
-                    if (which == 1 && ks[1] == ks[0]) { res[1] = res[0]; break; }
-                    const int k = ks[which];
-                    const int bstar = __popcll(__ballot(incl <= k));          // first bucket whose running count exceeds k
-                    const int kk = k - __shfl(incl - hc, bstar, 64);          // rank inside that bucket
-                    const int sz = __shfl(hc, bstar, 64);
-                    __syncthreads();
-                    if (lane == 0) s_cnt = 0;
-                    __syncthreads();
-#pragma unroll
-                    for (int m = 0; m < MED_FAST / 64 + 1; m++)
-                        if (bkt[m] == bstar) s_d[atomicAdd(&s_cnt, 1)] = v[m];
-                    __syncthreads();
-                    double found = -1.0;
-                    for (int j = lane; j < sz; j += 64) {
-                        const double x = s_d[j];
-                        int less = 0, leq = 0;
-                        for (int q = 0; q < sz; q++) { const double y = s_d[q]; less += (y < x) ? 1 : 0; leq += (y <= x) ? 1 : 0; }
-                        if (less <= kk && kk < leq) found = x;
-                    }
-                    for (int off = 32; off >= 1; off >>= 1) found = fmax(found, __shfl_xor(found, off, 64));
-                    res[which] = found;
-                }
-            }
-            r = (sqrt(res[0]) + sqrt(res[1])) / 2.;
-        } else if (code & PTS_STORED) {
-            // long border (> 496 points): chunk ids by walking the chain, distances recomputed from the points on every read
-            const int nch = (n + CH_PTS - 1) / CH_PTS;   // <= MAXCHAIN (StoreVisitor stops storing beyond that)
-            __syncthreads();
-            if (lane == 0) {
-                int c = code & (PTS_STORED - 1);
-                for (int j = nch - 1; j >= 0; j--) { s_ch[j] = c; c = (int)pool[(size_t)c * 32 + 31]; }
-            }
-            __syncthreads();
-            const double cx = blobs[bi].x, cy = blobs[bi].y;
-            auto get = [&](int i) {
-                const uint32_t p = pool[(size_t)s_ch[i / CH_PTS] * 32 + i % CH_PTS];
-                const double dx = cx - (double)(int)(p & 0xFFFFu), dy = cy - (double)(int)(p >> 16);
-                return sqrt(dx * dx + dy * dy);
-            };
-            r = wave_median(get, n, lane, s_d, s_hist, &s_cnt);
-        } else {
-            const double *dd = dists + code;   // border followed a second time (bright components, pool overflow)
-            r = wave_median([&](int i) { return dd[i]; }, n, lane, s_d, s_hist, &s_cnt);
+            if (lane == 0) m.blobs[bi].r = r;
         }
-        if (lane == 0) blobs[bi].r = r;
     }
 }
 
@@ -1324,76 +1507,137 @@ static_assert(NTHR == 17, "sweep_level (cpe_dev.h) holds the bucket count");
 constexpr int BK_CHUNK = 8192;    // pixels per workgroup of the two bucket passes
 
 // The scatter pass also gives every listed pixel its first node of the bright forest: {the first pixel of its run of one
-// bucket inside the wavefront's 64 pixels, never absorbed}.  (Round 2 wrote these entries bucket by bucket, one step ahead
-// of their use, through the lists: 2 % of the rectangle per pass, one 64-byte line per entry; here the stores of a
-// wavefront fall into a few lines.)
-template <bool SCATTER>
+// bucket inside its aligned chunk of 64 consecutive pixels, never absorbed}.  (Round 2 wrote these entries bucket by bucket,
+// one step ahead of their use, through the lists: 2 % of the rectangle per pass, one 64-byte line per entry; here the stores
+// of a wavefront fall into a few lines.)
+// A thread owns four consecutive pixels (one dword of the image) in each of its BK_CHUNK / 1024 rounds, so a 64-pixel chunk is
+// one DPP row of 16 lanes.  Row and column are divided out once per thread and advanced by 1024 pixels per round; everything is
+// 32-bit (h, w <= 4096).  The list entries of a thread's run of one bucket are consecutive (one LDS atomic per run).
+constexpr int BK_ROUNDS = BK_CHUNK / 1024;
 __global__ __launch_bounds__(256) void k_bk_pass(const uint8_t *__restrict__ img, int h, int w, const FrameState *__restrict__ st,
                                                  int *__restrict__ sw, int *__restrict__ bk, int *__restrict__ bright /* nodes {parent, history} */,
                                                  uint8_t *__restrict__ touch)
 {
     __shared__ int s_cnt[NBK], s_base[NBK];
-    const size_t N = (size_t)h * w, f = blockIdx.y;
-    const int t = threadIdx.x;
+    const int N = h * w, t = threadIdx.x;
+    const size_t f = blockIdx.y, fN = f * (size_t)N;
     const SwRect r = sw_rect(st, f);
     int *S = sw + f * SW_STRIDE;
     // first entry of every bucket = the sizes before it (counted by k_clahe_apply): every workgroup sums them for itself, the
     // first one of a frame also leaves the table for the sweep kernels (k_bk_scan was a launch of its own for this)
     __shared__ int s_off[NBK];
-    if (SCATTER && t < NBK) {
+    if (t < NBK) {
         int off = 0;
         for (int b = 1; b < t; b++) off += S[SW_BS + b];
         s_off[t] = off;
         if (blockIdx.x == 0 && t > 0) S[SW_BO + t] = off;
     }
+    const int p0 = (int)blockIdx.x * BK_CHUNK;
     {   // the workgroup's pixels lie in rows ya .. yb: nothing to do outside the working rectangle (three quarters of a frame)
-        const size_t p0 = (size_t)blockIdx.x * BK_CHUNK;
-        const int ya = (int)(p0 / w), yb = (int)(min(p0 + BK_CHUNK, N) - 1) / w;
+        const int ya = p0 / w, yb = (min(p0 + BK_CHUNK, N) - 1) / w;
         if (r.x1 < r.x0 || yb < r.y0 || ya > r.y1) return;
     }
     if (t < NBK) s_cnt[t] = 0;
     __syncthreads();
-    const uint8_t *im = img + f * N;
-    int lev[BK_CHUNK / 256];
+    const uint8_t *im = img + fN;
+    uint8_t *tc = touch + fN;
+    const bool wide = ((reinterpret_cast<uintptr_t>(im) | reinterpret_cast<uintptr_t>(tc)) & 3) == 0;   // i0 is a multiple of 4
+    const int step_y = 1024 / w, step_x = 1024 - step_y * w;
+    int i0 = p0 + 4 * t;
+    int y0 = i0 / w, x0 = i0 - y0 * w;
+    int lev[BK_ROUNDS * 4];
 #pragma unroll
-    for (int k = 0; k < BK_CHUNK / 256; k++) {
-        const size_t i = (size_t)blockIdx.x * BK_CHUNK + k * 256 + t;
-        int l = 0, x = 0;
-        if (i < N) {
-            const int y = (int)(i / w);
-            x = (int)(i - (size_t)y * w);
-            if (!(y < r.y0 || y > r.y1 || x < r.x0 || x > r.x1)) {
-                l = sw_level(im[i]);
-                if (SCATTER) touch[f * N + i] = 0;   // the dark sweep's epoch marks: only roots inside the rectangle are read
+    for (int k = 0; k < BK_ROUNDS; k++) {
+        unsigned in = 0;                                          // bit j: pixel i0 + j lies in the rectangle
+        int xs[4];
+        if (x0 + 3 < w && i0 + 3 < N) {                           // the four pixels lie in one row: bits x0r - x0 .. x1r - x0
+#pragma unroll
+            for (int j = 0; j < 4; j++) xs[j] = x0 + j;
+            const int lo = max(r.x0 - x0, 0), hi = min(r.x1 - x0, 3);
+            if (y0 >= r.y0 && y0 <= r.y1 && lo <= hi) in = (15u << lo) & (15u >> (3 - hi));
+        } else {
+            int x = x0, y = y0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                xs[j] = x;
+                in |= (i0 + j < N && y >= r.y0 && y <= r.y1 && x >= r.x0 && x <= r.x1 ? 1u : 0u) << j;
+                if (++x == w) { x = 0; y++; }
             }
         }
-        if (SCATTER) {
-            // first node of the bright forest: the first pixel of the pixel's run of one bucket among this wavefront's 64
-            // consecutive pixels (depth 1; x > r.x0: the lane before holds the left neighbour in the same row)
-            const int lane = t & 63, ll = __shfl_up(l, 1, 64);
-            const bool same = l > 0 && lane > 0 && ll == l && x > r.x0;
-            const unsigned long long st1 = __ballot(l > 0 && !same);
-            if (l > 0) {
-                const int first = (int)i - (lane - (63 - __clzll((long long)(st1 & ((lane == 63) ? ~0ull : ((2ull << lane) - 1ull))))));
-                *reinterpret_cast<int2 *>(bright + (f * N + i) * 2) = make_int2(first, -1);
+#pragma unroll
+        for (int j = 0; j < 4; j++) lev[4 * k + j] = 0;
+        if (__any(in != 0)) {                                     // (uniform) else 256 consecutive pixels beside the rectangle
+            uint32_t d = 0;
+            if (in) {
+                if (wide && i0 + 4 <= N) d = *reinterpret_cast<const uint32_t *>(im + i0);
+                else {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) if ((in >> j) & 1u) d |= (uint32_t)im[i0 + j] << (8 * j);
+                }
+                // the dark sweep's epoch marks: only roots inside the rectangle are read
+                if (wide && in == 15u) *reinterpret_cast<uint32_t *>(tc + i0) = 0u;
+                else {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) if ((in >> j) & 1u) tc[i0 + j] = 0;
+                }
+            }
+            int l[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {                         // sweep_level without branches: (x * 205) >> 11 = x / 10 for x < 1029
+                const int v = (int)((d >> (8 * j)) & 255u);
+                l[j] = ((in >> j) & 1u) ? min(17, ((max(v, 41) - 41) * 205) >> 11) : 0;
+            }
+            // first node of the bright forest: the first pixel of the pixel's run of one bucket inside its aligned chunk of
+            // 64 consecutive pixels = the 64 pixels of this DPP row (depth 1; x > r.x0: the pixel before is the left neighbour
+            // in the same row).  A pixel starts a run unless it continues one; the latest start at or before it is its first.
+            const int lprev = dpp_int<DPP_ROW_SHR + 1>(0, l[3]);  // 0 in the row's first lane: a chunk begins there
+            int first[4], last = -1;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const bool same = (j ? l[j - 1] : lprev) == l[j] && xs[j] > r.x0;
+                last = (l[j] > 0 && !same) ? i0 + j : last;
+                first[j] = last;                                  // -1: the run began in an earlier lane
+            }
+            const int carry = dpp_int<DPP_ROW_SHR + 1>(-1, row_scan_max_int(last, -1));
+            int2 *node = reinterpret_cast<int2 *>(bright) + fN + i0;
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (l[j] > 0) node[j] = make_int2(first[j] >= 0 ? first[j] : carry, -1);
+            // rank inside this workgroup's share of the bucket: one LDS atomic per run of one bucket among the four pixels
+            // (all of a thread's atomics go out before the first answer is waited for)
+            int rk[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const bool head = l[j] > 0 && (j == 0 || l[j - 1] != l[j]);
+                int c = 1;
+                bool run = true;
+#pragma unroll
+                for (int q = j + 1; q < 4; q++) { run = run && l[q] == l[j]; c += run ? 1 : 0; }
+                rk[j] = -1;
+                if (head) rk[j] = atomicAdd(&s_cnt[l[j]], c);
+            }
+            int e = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                e = rk[j] >= 0 ? (l[j] | (rk[j] << 8)) : (l[j] > 0 ? e + 256 : 0);
+                lev[4 * k + j] = e;
             }
         }
-        lev[k] = l;
-        if (l && !SCATTER) atomicAdd(&s_cnt[l], 1);
-        if (l && SCATTER) lev[k] = l | (atomicAdd(&s_cnt[l], 1) << 8);   // rank inside this workgroup's share
+        i0 += 1024;
+        y0 += step_y; x0 += step_x;
+        if (x0 >= w) { x0 -= w; y0++; }
     }
     __syncthreads();
-    if (!SCATTER) {
-        if (t > 0 && t < NBK && s_cnt[t]) atomicAdd(&S[SW_BS + t], s_cnt[t]);
-        return;
-    }
     if (t > 0 && t < NBK) s_base[t] = s_cnt[t] ? s_off[t] + atomicAdd(&S[SW_BC + t], s_cnt[t]) : 0;   // the cursors start at 0 (memset)
     __syncthreads();
+    int *list = bk + fN;
 #pragma unroll
-    for (int k = 0; k < BK_CHUNK / 256; k++) {
-        const int l = lev[k] & 255;
-        if (l) bk[f * N + s_base[l] + (lev[k] >> 8)] = (int)((size_t)blockIdx.x * BK_CHUNK + k * 256 + t);
-    }
+    for (int k = 0; k < BK_ROUNDS; k++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int l = lev[4 * k + j] & 255;
+            if (l) list[s_base[l] + (lev[4 * k + j] >> 8)] = p0 + k * 1024 + 4 * t + j;
+        }
 }
 
 constexpr int SW_GRID = 96;       // workgroups per frame of the kernels that walk one bucket (fewer in large batches: 24 at 256 images)
@@ -2437,7 +2681,7 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
     const dim3 gpx((unsigned)((N + 255) / 256), n), glist(frame_waves(4 * n, 4, swcap / 256), n), gtrace(frame_waves(n * NTHR, 8, swcap / 64), n, NTHR), gtrace_h(frame_waves(n * NTHR, 4, swcap / 64), n, NTHR), gbk(std::min(SW_GRID, std::max(16, 6144 / n)), n);
     {
         const dim3 gchunk((unsigned)((N + BK_CHUNK - 1) / BK_CHUNK), n);
-        CPE_KLAUNCH(k_bk_pass<true>, gchunk, dim3(256), 0, s, (const uint8_t *)B.cl, h, w, (const FrameState *)st, B.sw, B.bk, B.lab2, B.touch);
+        CPE_KLAUNCH(k_bk_pass, gchunk, dim3(256), 0, s, (const uint8_t *)B.cl, h, w, (const FrameState *)st, B.sw, B.bk, B.lab2, B.touch);
         CPE_CHECK_LAUNCH("grey-level buckets");
     }
     // the dark sweep and the hole borders run on the helper stream (if any) beside the bright sweep: the two forests
@@ -2478,11 +2722,11 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
         (void)hipStreamWaitEvent(ds, side->spot_done, 0);
     }
     {
-        // hole borders of all thresholds and their radii
+        // hole borders of all thresholds and the radii of the short ones (the rest: k_blob_median below)
         CPE_KLAUNCH(k_blob_trace<1>, gtrace_h, dim3(64), 0, ds, (const uint8_t *)B.cl, h, w, (const int2 *)B.tl, (int)SW_NT, st, B.sw, B.blobs,
                     B.blob_d, B.dists, (const uint32_t *)B.bits, B.pool, B.blob_ch, B.maxch, B.maxdf);
-        CPE_KLAUNCH(k_blob_median, dim3(frame_waves(n * NTHR, 16, 128), n, NTHR), dim3(64), 0, ds, 0, B.sw, B.blobs, (const int *)B.blob_d, B.dists,
-                    (const uint32_t *)B.pool, (const unsigned short *)B.blob_ch, st, B.maxch, B.maxdf);
+        CPE_KLAUNCH(k_blob_median_rows, dim3(frame_waves(n * NTHR, 16, 128), n, NTHR), dim3(64), 0, ds, B.sw, B.blobs, (const int *)B.blob_d, B.dists,
+                    (const uint32_t *)B.pool, (const unsigned short *)B.blob_ch, B.maxch, B.maxdf);
         if (side) (void)hipEventRecord(side->medians, ds);
     }
     // ---- descending thresholds: bright components (8-conn); B.bl[k] = (first pixel, pixels of the holes it encloses)
@@ -2503,8 +2747,8 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
                 h, w, B.cnt2);
     CPE_KLAUNCH(k_blob_trace<0>, gtrace, dim3(64), 0, s, (const uint8_t *)B.cl, h, w, (const int2 *)B.bl, (int)SW_NL, st, B.sw, B.blobs,
                 B.blob_d, B.dists, (const uint32_t *)B.bits, B.pool, B.blob_ch, B.maxch, B.maxdf);
-    CPE_KLAUNCH(k_blob_median, dim3(frame_waves(n * NTHR, 8, 32), n, NTHR), dim3(64), 0, s, 1, B.sw, B.blobs, (const int *)B.blob_d, B.dists, (const uint32_t *)B.pool,
-                (const unsigned short *)B.blob_ch, st, B.maxch, B.maxdf);
+    CPE_KLAUNCH(k_blob_median, dim3(frame_waves(n * NTHR, 8, 32), n, NTHR), dim3(64), 0, s, (const int *)B.sw, B.blobs, (const int *)B.blob_d, B.dists, (const uint32_t *)B.pool,
+                (const unsigned short *)B.blob_ch, B.maxch, B.maxdf);
     {
         // CPE_MERGE_REPLAY (tests): bit 0: every batch takes the in-order replay path instead of the lane-per-blob one;
         // bit 1: every threshold is ranked by the bucketed method of the noisy frames
