@@ -19,6 +19,15 @@
  *     call on them, so calls on different caller streams do not serialise each other; the enqueue of a call (host side,
  *     fork to join) holds its set's mutex, so the library is thread-safe; CPE_SERIAL=1 in the environment keeps
  *     everything on the caller's stream.
+ *   - Workspaces.  Every `ws` argument below (cpe_detect_workspace_bytes, cpe_fit_workspace_bytes,
+ *     cpe_match_offset_workspace_bytes) is scratch in the full sense: what the block holds on entry is irrelevant to every
+ *     output the call defines, so it needs no initialisation and no clearing between calls -- fresh memory, the leftovers of
+ *     any earlier call (another batch size, and with it another layout, another target, another entry point) and arbitrary
+ *     bytes all give the same results.  Each call initialises what it reads, and nothing is read or written at or beyond
+ *     `ws_bytes`, the size the call was given: a block larger than the call needs keeps its tail.  What a call leaves in
+ *     the block is defined only where this header says so (the CPE_PLANE_* planes, the line tables behind
+ *     cpe_detect_line_tables / cpe_detect_results_*); it stays valid until the next call that is given the block.
+ *     (tests/test_workspace_poison_gpu.py; the first writer of every buffer is listed in DESIGN.md section 3.)
  *   - every call is asynchronous on `stream` (a hipStream_t, passed as void*; NULL = default
  *     stream) and graph-capturable; no host synchronisation inside.
  *   - return value: 0 ok, <0 argument / launch error (text via cpe_last_error_string()).
@@ -103,7 +112,8 @@ CPE_API int32_t cpe_debug_preprocess(const uint8_t *gray, int32_t n, int32_t h, 
  *   exactly the content make_json serialises (util_cylinder.py:1674-1727): points with col >= 0 sorted
  *   by (col,row), and the centre point;
  *   status i32[n]: CPE_ST_* (the places where the reference raises inside detect_grid and returns None).
- * ws: cpe_detect_workspace_bytes(n,h,w) bytes of 256-byte aligned device scratch.  64 <= h,w <= 4096.
+ * ws: cpe_detect_workspace_bytes(n,h,w) bytes of 256-byte aligned device scratch; its content on entry is irrelevant and
+ * nothing at or beyond ws_bytes is touched (Conventions, "Workspaces").  64 <= h,w <= 4096.
  */
 CPE_API size_t cpe_detect_workspace_bytes(int32_t n, int32_t h, int32_t w);
 CPE_API int32_t cpe_detect_grid_batch(const uint8_t *gray, int32_t n, int32_t h, int32_t w, void *ws, size_t ws_bytes,
@@ -254,7 +264,24 @@ CPE_API int32_t cpe_bgr2gray_batch(const uint8_t *bgr, int32_t n, int32_t h, int
 
 /* Where an intermediate of the last cpe_detect_grid_batch call lives inside the workspace (for
  * stage-by-stage parity tests and debugging): plane-major, frame f at offset + f * bytes_per_frame.
- * After a call with CPE_DETECT_SKIP_DEBUG_PLANES the planes HMASK, VMASK, ROI_H and ROI_V are undefined (see the flag). */
+ * After a call with CPE_DETECT_SKIP_DEBUG_PLANES the planes HMASK, VMASK, ROI_H and ROI_V are undefined (see the flag).
+ *
+ * Planes of a frame that ends early.  The three chains in front of the join run for every frame of a batch, whatever becomes
+ * of it later, and no plane of one frame depends on another frame or on what the workspace held before the call:
+ *   every status       BINARY, HMASK, VMASK, BLUR19 (as `> 240`) and, cylinder target, CLAHE and SWEEP are what they are for a
+ *                      good frame; STATE: status and overflow; the line tables report 0 rows and 0 columns unless the lines
+ *                      stage ran (CPE_ST_OK, CPE_ST_NO_LINES and later), and the packed record has n_pts 0 unless CPE_ST_OK.
+ *   CPE_ST_NO_REGION   MASK_CONTOUR, ROI_H, ROI_V, EXP_H and EXP_V are ZERO on every pixel; JOINTS and the other words of
+ *                      STATE are undefined.
+ *   CPE_ST_NO_SPOT     MASK_CONTOUR and STATE's rect, n_kp are the region's; ROI_H, ROI_V, EXP_H, EXP_V (the reference stops in
+ *                      front of them) and JOINTS are UNDEFINED.
+ *   CPE_ST_NO_LINES and every later ending (CPE_ST_EMPTY, CPE_ST_OVERFLOW of the lines stage, CPE_ST_SUBPIXEL_RAISED)
+ *                      every plane above, JOINTS up to STATE's n_joints, r0 and spot as for a good frame.
+ *   BLUR7              defined for frames with CPE_ST_OK only, in the 64 x 32 tiles within the largest indexing window of the
+ *                      region rectangle; UNDEFINED elsewhere and for every other frame.
+ *   planar target      CPE_PLANE_CLAHE (grey entry) and CPE_PLANE_SWEEP are not written: UNDEFINED.
+ * Rows of xy / id at or past n_pts[k] are not written.  UNDEFINED content may depend on earlier calls; everything else above is
+ * held to the oracle and to a run on a zeroed workspace by tests/test_workspace_poison_gpu.py. */
 #define CPE_PLANE_BINARY 0        /* u8[h,w]  load_and_preprocess_image -> binary_img */
 #define CPE_PLANE_HMASK 1         /* u8[h,w]  extract_joints -> horizontal_mask */
 #define CPE_PLANE_VMASK 2         /* u8[h,w]  extract_joints -> vertical_mask */
@@ -424,7 +451,7 @@ CPE_API size_t cpe_fit_workspace_bytes(int32_t n);
  *   outputs  p1,p2 f64[n,CPE_MAXP,2] selected pixel pairs; idx i32[n,CPE_MAXP,2]; X f64[n,CPE_MAXP,3]
  *            points in the camera-1 frame; err f64[n,CPE_MAXP] per-point reprojection error;
  *            m i32[n] number of selected points; mean_err f64[n]; flags i32[n] (CPE_FIT_FLAG_*)
- *   ws       cpe_fit_workspace_bytes(n) bytes of device scratch
+ *   ws       cpe_fit_workspace_bytes(n) bytes of device scratch (content on entry irrelevant: Conventions, "Workspaces")
  * cnt1 / cnt2 are clamped to [0, CPE_MAXP]; slots past them are never read.  The (col,row) indices of a frame (both
  * tables) go through a dense CPE_FIT_TABLE_DIM x CPE_FIT_TABLE_DIM table: a frame whose indices span CPE_FIT_TABLE_DIM
  * or more in either direction, or has an index outside [-9999, 9999], is skipped with CPE_FIT_FLAG_OVERFLOW, m = 0,
@@ -525,7 +552,7 @@ CPE_API int32_t cpe_fit_cylinder_ransac_batch(const double *X, const int32_t *cn
  * Winner: the candidate with the smallest key (-score, |dc|+|dr|, |dc|, dc, dr), so (0,0) wins every tie it is part of.
  *
  *   inputs   the tables, K1, K2, T21 as cpe_select_triangulate_batch; radius as cpe_fit_cylinder_batch; params NULL = defaults
- *   ws       cpe_match_offset_workspace_bytes(n, win_c, win_r) bytes of device scratch (0 for a window outside
+ *   ws       cpe_match_offset_workspace_bytes(n, win_c, win_r) bytes of device scratch, content on entry irrelevant (0 for a window outside
  *            0..CPE_MATCH_MAX_WIN)
  *   offset   i32[n,2]  the shift (dc, dr) applied to table 1
  *   score    i32[n,4]  best score | runner-up (the second-largest value among all candidates; 0 with a single candidate) |

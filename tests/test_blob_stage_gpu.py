@@ -344,12 +344,12 @@ def _image(name):
 
 
 # ---------------------------------------------------------------- the entry point and the comparison
-def _run(cpe, gpu, imgs, kp_cap=4096, blob_cap=16384):
-    """cpe_debug_blob_region on u8 [n,h,w] -> dict of numpy results"""
+def _run(cpe, gpu, imgs, kp_cap=4096, blob_cap=16384, ws=None):
+    """cpe_debug_blob_region on u8 [n,h,w] -> dict of numpy results (ws: the workspace to run in, as the caller left it)"""
     from cpe_amd import api
     imgs = np.ascontiguousarray(imgs)
     n, h, w = imgs.shape
-    ws = api.DetectWorkspace(n, h, w, gpu)
+    ws = api.DetectWorkspace(n, h, w, gpu) if ws is None else ws.use(n)
     d = torch.from_numpy(imgs).to(gpu)
     kp = torch.zeros((n, kp_cap, 3), dtype=torch.float32, device=gpu)
     nkp = torch.zeros(n, dtype=torch.int32, device=gpu)

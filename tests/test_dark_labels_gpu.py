@@ -32,12 +32,12 @@ def _frames(rng, n, h, w):
     return out
 
 
-def _run(cpe, gpu, frames, rects, path):
+def _run(cpe, gpu, frames, rects, path, ws=None):
     from cpe_amd import api
     n, h, w = frames.shape
     g = torch.from_numpy(frames).to(gpu)
     rect = torch.tensor(rects, dtype=torch.int32, device=gpu)
-    ws = api.DetectWorkspace(n, h, w, gpu)
+    ws = api.DetectWorkspace(n, h, w, gpu) if ws is None else ws.use(n)
     lab = torch.empty((n, h, w), dtype=torch.int32, device=gpu)
     cnt = torch.empty((n, h, w), dtype=torch.int32, device=gpu)
     roots = torch.empty((n, MAXROOTS), dtype=torch.int32, device=gpu)

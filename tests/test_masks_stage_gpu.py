@@ -29,12 +29,13 @@ STATE = ('status', 'r0', 'spot0', 'spot1', 'spot2', 'spot3', 'n_joints', 'n_join
          'glen0', 'glen1', 'overflow')
 
 
-def _run(cpe, gpu, cases, target='cylinder'):
-    """cpe_debug_masks on a list of cases of one frame size -> list of per-frame dicts of numpy results"""
+def _run(cpe, gpu, cases, target='cylinder', ws=None):
+    """cpe_debug_masks on a list of cases of one frame size -> list of per-frame dicts of numpy results (ws: the workspace to run
+    in, as the caller left it)"""
     st = lambda k: torch.from_numpy(np.stack([c[k] for c in cases])).to(gpu)
     rect = torch.tensor([c['rect'] for c in cases], dtype=torch.int32)
     status = torch.tensor([c['status'] for c in cases], dtype=torch.int32)
-    ws = cpe.api.debug_masks(st('binary'), st('gray'), st('mc'), rect, status, target=target)
+    ws = cpe.api.debug_masks(st('binary'), st('gray'), st('mc'), rect, status, ws=ws, target=target)
     torch.cuda.synchronize()
     planes = {k: ws.plane(k).cpu().numpy() for k in PLANES}
     joints = ws.plane('joints').cpu().numpy()
