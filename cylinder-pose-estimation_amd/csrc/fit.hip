@@ -367,20 +367,40 @@ struct Pts {
     int n;
 };
 
-// getDistPts3ToLine.m for one point
+// ---- the small dense algebra of the fits, once each.  Constant indices after unrolling throughout, so every matrix stays in
+// registers (a run-time row index puts the whole matrix into scratch memory).
+
+// the axis of a line given as origin o and direction d, as getDistPts3ToLine.m gets it: p2 = o + d, v = p2 - o.  The round trip
+// is deliberate: it reproduces the reference's rounding.  A cylinder's 6-vector x is axis_of(x, x + 3, ...).
+__device__ __forceinline__ void axis_of(const double *o, const double *d, double *v, double &nv2)
+{
+#pragma unroll
+    for (int k = 0; k < 3; k++) v[k] = (o[k] + d[k]) - o[k];
+    nv2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+}
+
+// a point against the axis (org, v, nv2): al = ((pt - org).v)/|v|^2, e = (pt - org) - v al, dd = |e| (getDistPts3ToLine.m)
+__device__ __forceinline__ void point_on_axis(const double *pt, const double *org, const double *v, double nv2, double &al, double *e,
+                                              double &dd)
+{
+    al = (((pt[0] - org[0]) * v[0] + (pt[1] - org[1]) * v[1]) + (pt[2] - org[2]) * v[2]) / nv2;
+#pragma unroll
+    for (int k = 0; k < 3; k++) e[k] = pt[k] - (org[k] + v[k] * al);
+    dd = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+}
+
 __device__ __forceinline__ double dist_pt_line(const double *x, const double *p1, const double *v, double nv2)
 {
-    double al = (((x[0] - p1[0]) * v[0] + (x[1] - p1[1]) * v[1]) + (x[2] - p1[2]) * v[2]) / nv2;
-    double e0 = x[0] - (p1[0] + v[0] * al), e1 = x[1] - (p1[1] + v[1] * al), e2 = x[2] - (p1[2] + v[2] * al);
-    return sqrt((e0 * e0 + e1 * e1) + e2 * e2);
+    double al, e[3], dd;
+    point_on_axis(x, p1, v, nv2, al, e, dd);
+    return dd;
 }
 
 // dist() of fitCylinderWPts3.m:44-49
 __device__ double cyl_objective(const double *x, const Pts &P, double R, int lane)
 {
-    double p2[3] = {x[0] + x[3], x[1] + x[4], x[2] + x[5]};
-    double v[3] = {p2[0] - x[0], p2[1] - x[1], p2[2] - x[2]};
-    double nv2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+    double v[3], nv2;
+    axis_of(x, x + 3, v, nv2);
     double acc = 0.0;
     for (int k = lane; k < P.n; k += 64) {
         double d = dist_pt_line(P.p + 3 * k, x, v, nv2);
@@ -390,86 +410,122 @@ __device__ double cyl_objective(const double *x, const Pts &P, double R, int lan
     return wave_sum(acc);
 }
 
-__device__ void eig3(const double *Ain, double *w, double *V)
+// one row j[N] of a Jacobian with its residual r into acc: the upper triangle of J'J packed by rows (N (N + 1) / 2 sums), then J'r (N)
+template <int N>
+__device__ __forceinline__ void normal_accumulate(const double *j, double r, double *acc)
 {
-    double A[9];
+    int i = 0;
 #pragma unroll
-    for (int i = 0; i < 9; i++) { A[i] = Ain[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
+    for (int a = 0; a < N; a++) {
+#pragma unroll
+        for (int b = a; b < N; b++) { acc[i] = acc[i] + j[a] * j[b]; i++; }
+        acc[N * (N + 1) / 2 + a] = acc[N * (N + 1) / 2 + a] + j[a] * r;
+    }
+}
+
+// M x = b for NRHS right-hand sides by Gaussian elimination with partial pivoting, in place: M row-major N x N, b and x row-major
+// N x NRHS.  The pivot of a column is the first row of the largest |.|; row swaps are conditional swaps.  false: a zero pivot
+// (the arithmetic is finished all the same; the caller discards x).
+template <int N, int NRHS = 1>
+__device__ __forceinline__ bool gauss_solve(double *M, double *b, double *x)
+{
+    bool singular = false;
+#pragma unroll
+    for (int c = 0; c < N; c++) {
+        int pv = c;
+        double best = fabs(M[c * N + c]);
+#pragma unroll
+        for (int r = c + 1; r < N; r++) {
+            const double av = fabs(M[r * N + c]);
+            if (av > best) { best = av; pv = r; }
+        }
+#pragma unroll
+        for (int r = c + 1; r < N; r++) {
+            const bool sw = pv == r;   // selects of values, not a branch: a branch becomes a choice between row addresses
+#pragma unroll
+            for (int k = 0; k < N; k++) { const double mc = M[c * N + k], mr = M[r * N + k]; M[c * N + k] = sw ? mr : mc; M[r * N + k] = sw ? mc : mr; }
+#pragma unroll
+            for (int k = 0; k < NRHS; k++) { const double bc = b[c * NRHS + k], br = b[r * NRHS + k]; b[c * NRHS + k] = sw ? br : bc; b[r * NRHS + k] = sw ? bc : br; }
+        }
+        singular = singular || M[c * N + c] == 0;
+#pragma unroll
+        for (int r = c + 1; r < N; r++) {
+            const double fct = M[r * N + c] / M[c * N + c];
+#pragma unroll
+            for (int k = c; k < N; k++) M[r * N + k] = M[r * N + k] - fct * M[c * N + k];
+#pragma unroll
+            for (int k = 0; k < NRHS; k++) b[r * NRHS + k] = b[r * NRHS + k] - fct * b[c * NRHS + k];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NRHS; j++)
+#pragma unroll
+        for (int r = N - 1; r >= 0; r--) {
+            double s = b[r * NRHS + j];
+#pragma unroll
+            for (int k = r + 1; k < N; k++) s = s - M[r * N + k] * x[k * NRHS + j];
+            x[r * NRHS + j] = s / M[r * N + r];
+        }
+    return !singular;
+}
+
+// eigenvectors of a symmetric N x N by cyclic Jacobi rotations, p < q by rows, at most 30 sweeps: V's columns, w unsorted
+template <int N>
+__device__ __forceinline__ void jacobi_eig(const double *Ain, double *w, double *V)
+{
+    double A[N * N];
+#pragma unroll
+    for (int i = 0; i < N * N; i++) { A[i] = Ain[i]; V[i] = (i % (N + 1) == 0) ? 1.0 : 0.0; }
     for (int sweep = 0; sweep < 30; sweep++) {
         int rotated = 0;
 #pragma unroll
-        for (int p = 0; p < 2; p++)
+        for (int p = 0; p < N - 1; p++)
 #pragma unroll
-            for (int q = p + 1; q < 3; q++) {
-                double apq = A[p * 3 + q];
-                if (!(fabs(apq) <= 1e-17 * (fabs(A[p * 3 + p]) + fabs(A[q * 3 + q])))) {
+            for (int q = p + 1; q < N; q++) {
+                const double apq = A[p * N + q];
+                if (!(fabs(apq) <= 1e-17 * (fabs(A[p * N + p]) + fabs(A[q * N + q])))) {
                     rotated = 1;
-                    double theta = (A[q * 3 + q] - A[p * 3 + p]) / (2.0 * apq);
+                    const double theta = (A[q * N + q] - A[p * N + p]) / (2.0 * apq);
                     double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
                     if (theta < 0) t = -t;
-                    double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
 #pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        double akp = A[k * 3 + p], akq = A[k * 3 + q];
-                        A[k * 3 + p] = c * akp - s * akq;
-                        A[k * 3 + q] = s * akp + c * akq;
+                    for (int k = 0; k < N; k++) {
+                        const double akp = A[k * N + p], akq = A[k * N + q];
+                        A[k * N + p] = c * akp - s * akq;
+                        A[k * N + q] = s * akp + c * akq;
                     }
 #pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        double apk = A[p * 3 + k], aqk = A[q * 3 + k];
-                        A[p * 3 + k] = c * apk - s * aqk;
-                        A[q * 3 + k] = s * apk + c * aqk;
+                    for (int k = 0; k < N; k++) {
+                        const double apk = A[p * N + k], aqk = A[q * N + k];
+                        A[p * N + k] = c * apk - s * aqk;
+                        A[q * N + k] = s * apk + c * aqk;
                     }
 #pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        double vkp = V[k * 3 + p], vkq = V[k * 3 + q];
-                        V[k * 3 + p] = c * vkp - s * vkq;
-                        V[k * 3 + q] = s * vkp + c * vkq;
+                    for (int k = 0; k < N; k++) {
+                        const double vkp = V[k * N + p], vkq = V[k * N + q];
+                        V[k * N + p] = c * vkp - s * vkq;
+                        V[k * N + q] = s * vkp + c * vkq;
                     }
                 }
             }
         if (!rotated) break;
     }
-    // ascending, stable bubble (as the oracle)
-    double d[3] = {A[0], A[4], A[8]};
-    double Vs[9];
 #pragma unroll
-    for (int i = 0; i < 9; i++) Vs[i] = V[i];
-#define CSWAP(a, b)                                                                  \
-    if (d[b] < d[a]) {                                                               \
-        double t_ = d[a]; d[a] = d[b]; d[b] = t_;                                    \
-        for (int k = 0; k < 3; k++) { double u_ = Vs[k * 3 + a]; Vs[k * 3 + a] = Vs[k * 3 + b]; Vs[k * 3 + b] = u_; } \
-    }
-    CSWAP(0, 1) CSWAP(1, 2) CSWAP(0, 1)
-#undef CSWAP
-#pragma unroll
-    for (int i = 0; i < 3; i++) w[i] = d[i];
-#pragma unroll
-    for (int i = 0; i < 9; i++) V[i] = Vs[i];
+    for (int i = 0; i < N; i++) w[i] = A[i * (N + 1)];
 }
 
-__device__ void solve5(double *M, double *b, double *x)
+// jacobi_eig<3> with the eigenvalues ascending: a stable bubble over the columns (as the oracle)
+__device__ void eig3(const double *Ain, double *w, double *V)
 {
-    constexpr int N = 5;
-    for (int c = 0; c < N; c++) {
-        int pv = c;
-        for (int r = c + 1; r < N; r++)
-            if (fabs(M[r * N + c]) > fabs(M[pv * N + c])) pv = r;
-        if (pv != c) {
-            for (int k = 0; k < N; k++) { double t = M[c * N + k]; M[c * N + k] = M[pv * N + k]; M[pv * N + k] = t; }
-            double t = b[c]; b[c] = b[pv]; b[pv] = t;
-        }
-        for (int r = c + 1; r < N; r++) {
-            double fct = M[r * N + c] / M[c * N + c];
-            for (int k = c; k < N; k++) M[r * N + k] = M[r * N + k] - fct * M[c * N + k];
-            b[r] = b[r] - fct * b[c];
-        }
-    }
-    for (int r = N - 1; r >= 0; r--) {
-        double s = b[r];
-        for (int k = r + 1; k < N; k++) s = s - M[r * N + k] * x[k];
-        x[r] = s / M[r * N + r];
-    }
+    jacobi_eig<3>(Ain, w, V);
+    auto cswap = [&](int a, int b) {
+        if (!(w[b] < w[a])) return;
+        const double t_ = w[a]; w[a] = w[b]; w[b] = t_;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { const double u_ = V[k * 3 + a]; V[k * 3 + a] = V[k * 3 + b]; V[k * 3 + b] = u_; }
+    };
+    cswap(0, 1); cswap(1, 2); cswap(0, 1);
 }
 
 __device__ __forceinline__ double eps_of(double x)  // MATLAB eps(x)
@@ -514,9 +570,8 @@ __device__ void fit_init(const double *sP, int n, double R, int lane, double *sD
     // i = argmin dist to line(ctr, ctr + rdir)  (first minimum)
     int im;
     {
-        double p2[3] = {ctr[0] + rdir[0], ctr[1] + rdir[1], ctr[2] + rdir[2]};
-        double v[3] = {p2[0] - ctr[0], p2[1] - ctr[1], p2[2] - ctr[2]};
-        double nv2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+        double v[3], nv2;
+        axis_of(ctr, rdir, v, nv2);
         double bd = DBL_MAX;
         int bi = INT_MAX;
         for (int k = lane; k < n; k += 64) {
@@ -595,7 +650,7 @@ __device__ void fit_init(const double *sP, int n, double R, int lane, double *sD
                 rhs[a] = rhs[a] + row[a] * lz;
             }
         }
-        solve5(M, rhs, co);
+        gauss_solve<5>(M, rhs, co);
         double a = co[0] * 2, b = co[1], c = co[2] * 2;
         double hd = (a - c) / 2.0, mid = (a + c) / 2.0, rad = sqrt(hd * hd + b * b);
         double lam = mid - rad;  // eig ascending: V(:,1)
@@ -759,99 +814,76 @@ __device__ void fit_nm(const double *sP, int n, double R, int lane, double tolx,
     fit_nm_on(obj, tolx, tolf, maxiter, maxfun, x0, f0, xf, ffinal, itercount, func_evals);
 }
 
-__device__ void fit_lm(const double *sP, int n, double R, int lane, double tolx, double tolf, int maxiter,
-                       const double *x0, double f0, double *xf, double &ffinal, int &itercount, int &func_evals)
+// the damped system of a Levenberg-Marquardt trial: M = J'J (A: its upper triangle packed by rows) with M_aa (1 + lambda) +
+// 1e-12 trace on the diagonal, M dl = -g.  false: singular
+template <int N>
+__device__ __forceinline__ bool lm_damped_solve(const double *A, const double *g, double lambda, double *dl)
 {
-    Pts P{sP, n};
-    // ---- Levenberg-Marquardt on the same objective (north_star's "Gauss-Newton/LM inner loop"; NOT what the
-    // reference runs -- fitCylinderWPts3.m:38 uses fminsearch -- validated against the Nelder-Mead result).
-    // r_i = d_i - R;  dr/do = -e/d;  dr/dv = -(alpha/d) e  with  e = (P-o) - v alpha, alpha = ((P-o).v)/|v|^2.
-    // The 6-parameter form has two gauge directions (origin along the axis, |v|): the damping term handles them.
-    double x[6];
+    double M[N * N], rhs[N];
+    int i = 0;
+    double trA = 0;
 #pragma unroll
-    for (int k = 0; k < 6; k++) x[k] = x0[k];
-    double fx = f0, lambda = 1e-3;
+    for (int a = 0; a < N; a++)
+#pragma unroll
+        for (int b = a; b < N; b++) { M[a * N + b] = A[i]; M[b * N + a] = A[i]; if (a == b) trA = trA + A[i]; i++; }
+#pragma unroll
+    for (int a = 0; a < N; a++) { M[a * N + a] = M[a * N + a] + lambda * M[a * N + a] + 1e-12 * trA; rhs[a] = -g[a]; }
+    return gauss_solve<N>(M, rhs, dl);
+}
+
+// N = 2 in closed form (A = s00 s01 s11): elimination would give other bits
+template <>
+__device__ __forceinline__ bool lm_damped_solve<2>(const double *A, const double *g, double lambda, double *dl)
+{
+    const double trA = A[0] + A[2];
+    const double m00 = A[0] + lambda * A[0] + 1e-12 * trA, m11 = A[2] + lambda * A[2] + 1e-12 * trA;
+    const double det = m00 * m11 - A[1] * A[1];
+    dl[0] = (A[1] * g[1] - m11 * g[0]) / det;
+    dl[1] = (A[1] * g[0] - m00 * g[1]) / det;
+    return det != 0;
+}
+
+// Levenberg-Marquardt from (x0, f0 = problem(x0)) on N unknowns: the one loop of the cylinder fit and the multi-frame pose fit
+// (k_frame_angles_lm has the same loop written out, see there).  A problem supplies
+//   normal(x, A, g)           one Jacobian pass at the current point x: J'J (upper triangle packed by rows) and J'r
+//   bool candidate(x, dl, xn) the retraction xn of the step dl from x; false: xn may not be evaluated
+//   double operator()(xn)     the objective
+// lambda starts at 1e-3, x 10 on a rejected trial, / 10 (floor 1e-12) on an accepted one; at most 12 trials per iteration and
+// min(maxiter, 200) iterations; stop when an iteration improves f by no more than tolf 1e-3 (1 + f) with a step of at most tolx,
+// or when none of its trials is accepted.
+//   - A singular system or an invalid candidate is a rejected trial: lambda x 10, it counts towards the 12, the objective is not
+//     evaluated and func_evals stays.
+//   - A NaN objective is a rejected trial (fn < fx is false), so every loop is bounded whatever the objective returns.
+//   - func_evals comes in as what the caller has spent already (f0, and whatever chose x0) and counts every evaluation here.
+//   - Barriers: the multi-frame problem's objective and normal() hold __syncthreads().  Every wave of its workgroup runs this
+//     loop on the same numbers (frame list, terms and the sums come from LDS, everything else each wave computes for itself, and
+//     the arithmetic is deterministic), so every branch here goes the same way in all waves.  Keep it so: no branch in this
+//     loop may depend on the wave or the lane.
+template <int N, class Problem>
+__device__ __forceinline__ void lm_minimize(Problem &prob, const double *x0, double f0, double tolx, double tolf, int maxiter, double *x,
+                                            double &fx, int &itercount, int &func_evals)
+{
+#pragma unroll
+    for (int k = 0; k < N; k++) x[k] = x0[k];
+    fx = f0;
+    double lambda = 1e-3;
     itercount = 0;
-    func_evals = 1;
     for (; itercount < maxiter && itercount < 200;) {
-        double A[21], g[6];
-#pragma unroll
-        for (int k = 0; k < 21; k++) A[k] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; k++) g[k] = 0.0;
-        {
-            double p2[3] = {x[0] + x[3], x[1] + x[4], x[2] + x[5]};
-            double vv[3] = {p2[0] - x[0], p2[1] - x[1], p2[2] - x[2]};
-            double nv2 = (vv[0] * vv[0] + vv[1] * vv[1]) + vv[2] * vv[2];
-            for (int k = lane; k < n; k += 64) {
-                const double *pt = sP + 3 * k;
-                double al = (((pt[0] - x[0]) * vv[0] + (pt[1] - x[1]) * vv[1]) + (pt[2] - x[2]) * vv[2]) / nv2;
-                double e[3] = {pt[0] - (x[0] + vv[0] * al), pt[1] - (x[1] + vv[1] * al), pt[2] - (x[2] + vv[2] * al)};
-                double dd = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-                if (dd > 0) {
-                    double r = dd - R, c1 = -1.0 / dd, c2 = -(al / dd);
-                    double j[6] = {c1 * e[0], c1 * e[1], c1 * e[2], c2 * e[0], c2 * e[1], c2 * e[2]};
-                    int q = 0;
-#pragma unroll
-                    for (int a = 0; a < 6; a++) {
-#pragma unroll
-                        for (int b = a; b < 6; b++) { A[q] = A[q] + j[a] * j[b]; q++; }
-                        g[a] = g[a] + j[a] * r;
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 21; k++) A[k] = wave_sum(A[k]);
-#pragma unroll
-            for (int k = 0; k < 6; k++) g[k] = wave_sum(g[k]);
-        }
+        double A[N * (N + 1) / 2], g[N];
+        prob.normal(x, A, g);
         itercount++;
         bool accepted = false;
-        double dmax = 0, fprev = fx;
+        double dmax = 0;
+        const double fprev = fx;
         for (int tr = 0; tr < 12 && !accepted; tr++) {
-            double M[36], rhs[6], dl[6];
-            {
-                int q = 0;
-                double trA = 0;
-#pragma unroll
-                for (int a = 0; a < 6; a++)
-#pragma unroll
-                    for (int b = a; b < 6; b++) { M[a * 6 + b] = A[q]; M[b * 6 + a] = A[q]; if (a == b) trA = trA + A[q]; q++; }
-#pragma unroll
-                for (int a = 0; a < 6; a++) { M[a * 6 + a] = M[a * 6 + a] + lambda * M[a * 6 + a] + 1e-12 * trA; rhs[a] = -g[a]; }
-            }
-            // Gaussian elimination with partial pivoting (wave-uniform)
-            bool singular = false;
-            for (int c = 0; c < 6; c++) {
-                int pv = c;
-                for (int r = c + 1; r < 6; r++)
-                    if (fabs(M[r * 6 + c]) > fabs(M[pv * 6 + c])) pv = r;
-                if (M[pv * 6 + c] == 0) { singular = true; break; }
-                if (pv != c) {
-                    for (int k = 0; k < 6; k++) { double t_ = M[c * 6 + k]; M[c * 6 + k] = M[pv * 6 + k]; M[pv * 6 + k] = t_; }
-                    double t_ = rhs[c]; rhs[c] = rhs[pv]; rhs[pv] = t_;
-                }
-                for (int r = c + 1; r < 6; r++) {
-                    double fct = M[r * 6 + c] / M[c * 6 + c];
-                    for (int k = c; k < 6; k++) M[r * 6 + k] = M[r * 6 + k] - fct * M[c * 6 + k];
-                    rhs[r] = rhs[r] - fct * rhs[c];
-                }
-            }
-            if (singular) { lambda = lambda * 10; continue; }
-            for (int r = 5; r >= 0; r--) {
-                double sacc = rhs[r];
-                for (int k = r + 1; k < 6; k++) sacc = sacc - M[r * 6 + k] * dl[k];
-                dl[r] = sacc / M[r * 6 + r];
-            }
-            double xn[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++) xn[k] = x[k] + dl[k];
-            double fn = cyl_objective(xn, P, R, lane);
+            double dl[N], xn[N];
+            if (!lm_damped_solve<N>(A, g, lambda, dl) || !prob.candidate(x, dl, xn)) { lambda = lambda * 10; continue; }
+            const double fn = prob(xn);
             func_evals++;
             if (fn < fx) {
                 dmax = 0;
 #pragma unroll
-                for (int k = 0; k < 6; k++) { dmax = fmax(dmax, fabs(dl[k])); x[k] = xn[k]; }
+                for (int k = 0; k < N; k++) { dmax = fmax(dmax, fabs(dl[k])); x[k] = xn[k]; }
                 fx = fn;
                 lambda = fmax(lambda / 10, 1e-12);
                 accepted = true;
@@ -862,16 +894,70 @@ __device__ void fit_lm(const double *sP, int n, double R, int lane, double tolx,
         if (!accepted) break;
         if ((fprev - fx) <= tolf * 1e-3 * (1.0 + fx) && dmax <= tolx) break;
     }
-#pragma unroll
-    for (int k = 0; k < 6; k++) xf[k] = x[k];
-    ffinal = fx;
 }
 
-// applyCylParamsPrior.m on both rows (ymin over the n points given), cylParams2T.m on the final row, outputs of frame f
-__device__ void fit_write(int f, int lane, const double *sP, int n, const double *x0, const double *xf, double f0, double ffinal,
-                          int itercount, int func_evals, double *__restrict__ o_raw, double *__restrict__ o_cyl,
-                          double *__restrict__ o_T, double *__restrict__ o_fvals, int *__restrict__ o_iters,
-                          int *__restrict__ o_status)
+// Levenberg-Marquardt on the per-frame objective (north_star's "Gauss-Newton/LM inner loop"; NOT what the reference runs --
+// fitCylinderWPts3.m:38 uses fminsearch -- validated against the Nelder-Mead result).
+// r_i = d_i - R;  dr/do = -e/d;  dr/dv = -(alpha/d) e  with  e = (P-o) - v alpha, alpha = ((P-o).v)/|v|^2.
+// The 6-parameter form has two gauge directions (origin along the axis, |v|): the damping term handles them.
+struct CylProblem : CylObjective {
+    __device__ __forceinline__ void normal(const double *x, double *A, double *g) const
+    {
+        double acc[27], v[3], nv2;
+#pragma unroll
+        for (int k = 0; k < 27; k++) acc[k] = 0.0;
+        axis_of(x, x + 3, v, nv2);
+        for (int k = lane; k < P.n; k += 64) {
+            double al, e[3], dd;
+            point_on_axis(P.p + 3 * k, x, v, nv2, al, e, dd);
+            if (dd > 0) {
+                const double r = dd - R, c1 = -1.0 / dd, c2 = -(al / dd);
+                const double j[6] = {c1 * e[0], c1 * e[1], c1 * e[2], c2 * e[0], c2 * e[1], c2 * e[2]};
+                normal_accumulate<6>(j, r, acc);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 21; k++) A[k] = wave_sum(acc[k]);
+#pragma unroll
+        for (int k = 0; k < 6; k++) g[k] = wave_sum(acc[21 + k]);
+    }
+    __device__ __forceinline__ bool candidate(const double *x, const double *dl, double *xn) const
+    {
+#pragma unroll
+        for (int k = 0; k < 6; k++) xn[k] = x[k] + dl[k];
+        return true;
+    }
+};
+
+__device__ void fit_lm(const double *sP, int n, double R, int lane, double tolx, double tolf, int maxiter,
+                       const double *x0, double f0, double *xf, double &ffinal, int &itercount, int &func_evals)
+{
+    CylProblem prob{{Pts{sP, n}, R, lane}};
+    func_evals = 1;
+    lm_minimize<6>(prob, x0, f0, tolx, tolf, maxiter, xf, ffinal, itercount, func_evals);
+}
+
+// the outputs of the per-frame fit and of RANSAC around it, per frame f
+struct FitOut {
+    double *raw, *cyl, *T, *fvals;
+    int *iters, *status;
+    // a frame that is not fitted: its status, every other output zero
+    __device__ void write_failed(int f, int lane, int st) const
+    {
+        if (lane != 0) return;
+        status[f] = st;
+        iters[2 * f] = 0; iters[2 * f + 1] = 0;
+        fvals[2 * f] = 0; fvals[2 * f + 1] = 0;
+        for (int k = 0; k < 12; k++) { raw[12 * f + k] = 0; cyl[12 * f + k] = 0; }
+        for (int k = 0; k < 16; k++) T[16 * f + k] = 0;
+    }
+    // applyCylParamsPrior.m on both rows (ymin over the n points given), cylParams2T.m on the final row
+    __device__ void write_ok(int f, int lane, const double *sP, int n, const double *x0, const double *xf, double f0, double ffinal,
+                             int itercount, int func_evals) const;
+};
+
+__device__ void FitOut::write_ok(int f, int lane, const double *sP, int n, const double *x0, const double *xf, double f0, double ffinal,
+                                 int itercount, int func_evals) const
 {
     // applyCylParamsPrior.m on both rows, cylParams2T.m on the final row
     double ymin = DBL_MAX;
@@ -882,13 +968,13 @@ __device__ void fit_write(int f, int lane, const double *sP, int n, const double
         double rows[2][6];
         for (int k = 0; k < 6; k++) { rows[0][k] = x0[k]; rows[1][k] = xf[k]; }
         for (int rI = 0; rI < 2; rI++) {
-            for (int k = 0; k < 6; k++) o_raw[12 * f + 6 * rI + k] = rows[rI][k];
+            for (int k = 0; k < 6; k++) raw[12 * f + 6 * rI + k] = rows[rI][k];
             double o[3] = {rows[rI][0], rows[rI][1], rows[rI][2]}, d[3] = {rows[rI][3], rows[rI][4], rows[rI][5]};
             if (d[1] < 0) { d[0] = -d[0]; d[1] = -d[1]; d[2] = -d[2]; }
             double t = 0;
             if (!(fabs(d[1]) < DBL_EPSILON)) t = (ymin - o[1]) / d[1];
             for (int c = 0; c < 3; c++) { rows[rI][c] = o[c] + t * d[c]; rows[rI][3 + c] = d[c]; }
-            for (int k = 0; k < 6; k++) o_cyl[12 * f + 6 * rI + k] = rows[rI][k];
+            for (int k = 0; k < 6; k++) cyl[12 * f + 6 * rI + k] = rows[rI][k];
         }
         const double *cy = rows[1];
         double y[3] = {cy[3], cy[4], cy[5]};
@@ -900,26 +986,14 @@ __device__ void fit_write(int f, int lane, const double *sP, int n, const double
         double xv[3] = {y[1] * z[2] - y[2] * z[1], y[2] * z[0] - y[0] * z[2], y[0] * z[1] - y[1] * z[0]};
         double nx = sqrt((xv[0] * xv[0] + xv[1] * xv[1]) + xv[2] * xv[2]);
         for (int c = 0; c < 3; c++) xv[c] = xv[c] / nx;
-        double *T = o_T + 16 * f;
-        for (int r = 0; r < 3; r++) { T[r * 4] = xv[r]; T[r * 4 + 1] = y[r]; T[r * 4 + 2] = z[r]; T[r * 4 + 3] = cy[r]; }
-        T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
-        o_fvals[2 * f] = f0;
-        o_fvals[2 * f + 1] = ffinal;
-        o_iters[2 * f] = itercount;
-        o_iters[2 * f + 1] = func_evals;
-        o_status[f] = CPE_ST_OK;
-    }
-}
-
-__device__ void fit_write_few_points(int f, int lane, double *__restrict__ o_raw, double *__restrict__ o_cyl, double *__restrict__ o_T,
-                                     double *__restrict__ o_fvals, int *__restrict__ o_iters, int *__restrict__ o_status)
-{
-    if (lane == 0) {
-        o_status[f] = CPE_ST_FEW_POINTS;
-        o_iters[2 * f] = 0; o_iters[2 * f + 1] = 0;
-        o_fvals[2 * f] = 0; o_fvals[2 * f + 1] = 0;
-        for (int k = 0; k < 12; k++) { o_raw[12 * f + k] = 0; o_cyl[12 * f + k] = 0; }
-        for (int k = 0; k < 16; k++) o_T[16 * f + k] = 0;
+        double *Tf = T + 16 * f;
+        for (int r = 0; r < 3; r++) { Tf[r * 4] = xv[r]; Tf[r * 4 + 1] = y[r]; Tf[r * 4 + 2] = z[r]; Tf[r * 4 + 3] = cy[r]; }
+        Tf[12] = 0; Tf[13] = 0; Tf[14] = 0; Tf[15] = 1;
+        fvals[2 * f] = f0;
+        fvals[2 * f + 1] = ffinal;
+        iters[2 * f] = itercount;
+        iters[2 * f + 1] = func_evals;
+        status[f] = CPE_ST_OK;
     }
 }
 
@@ -935,10 +1009,7 @@ __device__ __forceinline__ bool fit_finite(const double *x, double f)
 template <int MODE>
 __global__ __launch_bounds__(64) void k_fit_cylinder(const double *__restrict__ X, const int *__restrict__ cnt,
                                                      double R, double tolx, double tolf, int maxiter,
-                                                     int maxfun, double *__restrict__ o_raw,
-                                                     double *__restrict__ o_cyl, double *__restrict__ o_T,
-                                                     double *__restrict__ o_fvals, int *__restrict__ o_iters,
-                                                     int *__restrict__ o_status)
+                                                     int maxfun, const FitOut out)
 {
     // One wavefront per frame, a chain of dependent f64 operations 200-300 simplex iterations long: beside the wide kernels of
     // the other chunk in flight it waited its turn at every instruction (2.2 ms alone, 12 ms in the overlapped trace).  Its
@@ -950,18 +1021,18 @@ __global__ __launch_bounds__(64) void k_fit_cylinder(const double *__restrict__ 
     __shared__ int sNb[20];
     const int f = blockIdx.x, lane = threadIdx.x;
     const int n = min(max(cnt[f], 0), MAXP);
-    if (n < CPE_FIT_MIN_POINTS) { fit_write_few_points(f, lane, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status); return; }
+    if (n < CPE_FIT_MIN_POINTS) { out.write_failed(f, lane, CPE_ST_FEW_POINTS); return; }
     const double *Xf = X + (size_t)f * MAXP * 3;
     for (int i = lane; i < 3 * n; i += 64) sP[i] = Xf[i];
     __syncthreads();
     double x0[6], f0, xf[6], ffinal;
     int itercount, func_evals;
     fit_init(sP, n, R, lane, sD, sNb, x0, f0);
-    if (!fit_finite(x0, f0)) { fit_write_few_points(f, lane, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status); return; }
+    if (!fit_finite(x0, f0)) { out.write_failed(f, lane, CPE_ST_FEW_POINTS); return; }
     if constexpr (MODE == 0) fit_nm(sP, n, R, lane, tolx, tolf, maxiter, maxfun, x0, f0, xf, ffinal, itercount, func_evals);
     else fit_lm(sP, n, R, lane, tolx, tolf, maxiter, x0, f0, xf, ffinal, itercount, func_evals);
-    if (!fit_finite(xf, ffinal)) { fit_write_few_points(f, lane, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status); return; }
-    fit_write(f, lane, sP, n, x0, xf, f0, ffinal, itercount, func_evals, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status);
+    if (!fit_finite(xf, ffinal)) { out.write_failed(f, lane, CPE_ST_FEW_POINTS); return; }
+    out.write_ok(f, lane, sP, n, x0, xf, f0, ffinal, itercount, func_evals);
 }
 
 // ---- BUILD-DEFINED (BASELINE config 5; nothing like it in the reference): RANSAC around the fit -------
@@ -983,9 +1054,8 @@ __device__ __forceinline__ unsigned long long ransac_hash(unsigned long long see
 // |dist - R| < tau for point k of sP under the cylinder x
 __device__ __forceinline__ bool ransac_inlier(const double *sP, int k, const double *x, double R, double tau)
 {
-    double p2[3] = {x[0] + x[3], x[1] + x[4], x[2] + x[5]};
-    double v[3] = {p2[0] - x[0], p2[1] - x[1], p2[2] - x[2]};
-    double nv2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+    double v[3], nv2;
+    axis_of(x, x + 3, v, nv2);
     return fabs(dist_pt_line(sP + 3 * k, x, v, nv2) - R) < tau;
 }
 
@@ -993,9 +1063,7 @@ template <int MODE>
 __global__ __launch_bounds__(64) void k_fit_ransac(const double *__restrict__ X, const int *__restrict__ cnt, double R, int H, int S,
                                                    double tau, unsigned long long seed, unsigned long long frame0, int hyp_iters,
                                                    double tolx, double tolf, int maxiter, int maxfun,
-                                                   double *__restrict__ o_raw, double *__restrict__ o_cyl, double *__restrict__ o_T,
-                                                   double *__restrict__ o_fvals, int *__restrict__ o_iters, int *__restrict__ o_status,
-                                                   int *__restrict__ o_ninl, uint8_t *__restrict__ o_mask)
+                                                   const FitOut out, int *__restrict__ o_ninl, uint8_t *__restrict__ o_mask)
 {
     double *sP = fit_dyn, *sQ = fit_dyn + MAXP * 3, *sD = fit_dyn + MAXP * 6;   // dynamic LDS, RANSAC_LDS_BYTES
     __shared__ int sNb[20];
@@ -1004,7 +1072,7 @@ __global__ __launch_bounds__(64) void k_fit_ransac(const double *__restrict__ X,
     uint8_t *mk = o_mask + (size_t)f * MAXP;
     for (int k = lane; k < MAXP; k += 64) mk[k] = 0;
     auto few_points = [&]() {   // status 5, zero outputs, empty mask
-        fit_write_few_points(f, lane, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status);
+        out.write_failed(f, lane, CPE_ST_FEW_POINTS);
         if (lane == 0) o_ninl[f] = 0;
     };
     if (n < CPE_FIT_MIN_POINTS) { few_points(); return; }
@@ -1068,7 +1136,7 @@ __global__ __launch_bounds__(64) void k_fit_ransac(const double *__restrict__ X,
     else fit_lm(sQ, nq, R, lane, tolx, tolf, maxiter, best_x, fs, xf, ffinal, itercount, func_evals);
     if (!fit_finite(xf, ffinal)) { few_points(); return; }
     for (int k = lane; k < n; k += 64) mk[k] = all_points ? 1 : (ransac_inlier(sP, k, best_x, R, tau) ? 1 : 0);
-    fit_write(f, lane, sQ, nq, x0, xf, f0, ffinal, itercount, func_evals, o_raw, o_cyl, o_T, o_fvals, o_iters, o_status);
+    out.write_ok(f, lane, sQ, nq, x0, xf, f0, ffinal, itercount, func_evals);
     if (lane == 0) o_ninl[f] = n_inl;
 }
 
@@ -1185,12 +1253,13 @@ extern "C" int32_t cpe_fit_cylinder_batch(const double *X, const int32_t *cnt, i
     CPE_CHECK_ARG(p.mode == CPE_FIT_NELDER_MEAD || p.mode == CPE_FIT_LM, "cpe_fit_cylinder_batch: unknown mode %d", p.mode);
     CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fit_cylinder<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FIT_LDS_BYTES));
     CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fit_cylinder<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FIT_LDS_BYTES));
+    const FitOut out{cyl_raw, cyl, T, fvals, iters, status};
     if (p.mode == CPE_FIT_LM)
         CPE_KLAUNCH(k_fit_cylinder<1>, dim3(n), dim3(64), FIT_LDS_BYTES, (hipStream_t)stream, X, cnt, radius, p.tol_x, p.tol_f, p.max_iter,
-                    p.max_fun_evals, cyl_raw, cyl, T, fvals, iters, status);
+                    p.max_fun_evals, out);
     else
         CPE_KLAUNCH(k_fit_cylinder<0>, dim3(n), dim3(64), FIT_LDS_BYTES, (hipStream_t)stream, X, cnt, radius, p.tol_x, p.tol_f, p.max_iter,
-                    p.max_fun_evals, cyl_raw, cyl, T, fvals, iters, status);
+                    p.max_fun_evals, out);
     CPE_CHECK_LAUNCH("k_fit_cylinder");
     return CPE_OK;
 }
@@ -1215,14 +1284,15 @@ extern "C" int32_t cpe_fit_cylinder_ransac_batch(const double *X, const int32_t 
     CPE_LAUNCH_BEGIN();
     CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fit_ransac<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RANSAC_LDS_BYTES));
     CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fit_ransac<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RANSAC_LDS_BYTES));
+    const FitOut out{cyl_raw, cyl, T, fvals, iters, status};
     if (p.mode == CPE_FIT_LM)
         CPE_KLAUNCH(k_fit_ransac<1>, dim3(n), dim3(64), RANSAC_LDS_BYTES, (hipStream_t)stream, X, cnt, radius, r.hypotheses, r.sample, r.tau,
                     (unsigned long long)r.seed, (unsigned long long)r.frame0, r.hyp_iters, p.tol_x, p.tol_f, p.max_iter, p.max_fun_evals,
-                    cyl_raw, cyl, T, fvals, iters, status, n_inliers, inlier_mask);
+                    out, n_inliers, inlier_mask);
     else
         CPE_KLAUNCH(k_fit_ransac<0>, dim3(n), dim3(64), RANSAC_LDS_BYTES, (hipStream_t)stream, X, cnt, radius, r.hypotheses, r.sample, r.tau,
                     (unsigned long long)r.seed, (unsigned long long)r.frame0, r.hyp_iters, p.tol_x, p.tol_f, p.max_iter, p.max_fun_evals,
-                    cyl_raw, cyl, T, fvals, iters, status, n_inliers, inlier_mask);
+                    out, n_inliers, inlier_mask);
     CPE_CHECK_LAUNCH("k_fit_ransac");
     return CPE_OK;
 }
@@ -1238,6 +1308,16 @@ extern "C" int32_t cpe_fit_cylinder_ransac_batch(const double *X, const int32_t 
 //                       Levenberg-Marquardt on the same objective (a handful of passes over the points).
 // k_pose_vec2T/T2vec  : vec2T.m / T2vec.m for a batch of poses, the device functions the fit itself uses.
 namespace {
+// T_C1_cyl = T * TAGVcyls{i}: only column 2 (dy: the axis) and column 4 (org: the origin) are used
+__device__ __forceinline__ void frame_axis(const double *T, const double *__restrict__ A, double *org, double *dy)
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        dy[r] = ((T[r * 4] * A[1] + T[r * 4 + 1] * A[5]) + T[r * 4 + 2] * A[9]) + T[r * 4 + 3] * A[13];
+        org[r] = ((T[r * 4] * A[3] + T[r * 4 + 1] * A[7]) + T[r * 4 + 2] * A[11]) + T[r * 4 + 3] * A[15];
+    }
+}
+
 // one frame's term: mean((d - R)^2) over its points; T row-major vec2T(agvPose), A row-major getTAGVcyl of the frame.
 // cnt is clamped to [0, MAXP]; a frame without points has the term 0.
 __device__ __forceinline__ double multi_frame_term(const double *__restrict__ P, int cnt, const double *__restrict__ A, const double *T,
@@ -1245,16 +1325,9 @@ __device__ __forceinline__ double multi_frame_term(const double *__restrict__ P,
 {
     const int n = min(max(cnt, 0), MAXP);
     if (n == 0) return 0.0;
-    // T_C1_cyl = T * TAGVcyls{i}: only column 2 (axis) and column 4 (origin) are used
-    double org[3], dy[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        dy[r] = ((T[r * 4] * A[1] + T[r * 4 + 1] * A[5]) + T[r * 4 + 2] * A[9]) + T[r * 4 + 3] * A[13];
-        org[r] = ((T[r * 4] * A[3] + T[r * 4 + 1] * A[7]) + T[r * 4 + 2] * A[11]) + T[r * 4 + 3] * A[15];
-    }
-    double p2[3] = {org[0] + dy[0], org[1] + dy[1], org[2] + dy[2]};
-    double v[3] = {p2[0] - org[0], p2[1] - org[1], p2[2] - org[2]};
-    double nv2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+    double org[3], dy[3], v[3], nv2;
+    frame_axis(T, A, org, dy);
+    axis_of(org, dy, v, nv2);
     double acc = 0.0;
     for (int k = lane; k < n; k += 64) {
         double d = dist_pt_line(P + 3 * k, org, v, nv2);
@@ -1369,8 +1442,7 @@ __device__ __forceinline__ void multi_prior(const double *__restrict__ M, const 
 
 // T0 of fitCylinderWPts3sAngs.m:48-69 as a pose vector: R = [dir1 en c1] / [y1 nd c2] by Gaussian elimination with row
 // pivoting on B' R' = A' (the order of oracle/src/orc_fit.c::orc_multi_init and multiframe.initial_pose), t = origin1 - R p1.
-// cp0 / cp1: multi_prior of the first two frames, A1 / A2 their getTAGVcyl.  Row swaps are written out with constant
-// indices so that the 3x3 systems stay in registers.
+// cp0 / cp1: multi_prior of the first two frames, A1 / A2 their getTAGVcyl.
 __device__ __forceinline__ void multi_init(const double *cp0, const double *cp1, const double *__restrict__ A1,
                                            const double *__restrict__ A2, double *x0)
 {
@@ -1392,37 +1464,8 @@ __device__ __forceinline__ void multi_init(const double *cp0, const double *cp1,
     cross3(y1, nd, c2);
     double Bt[9] = {y1[0], y1[1], y1[2], nd[0], nd[1], nd[2], c2[0], c2[1], c2[2]};
     double At[9] = {dir1[0], dir1[1], dir1[2], en[0], en[1], en[2], c1[0], c1[1], c1[2]};
-#define SWAP_ROWS(a, b)                                                              \
-    _Pragma("unroll") for (int k = 0; k < 3; k++) {                                  \
-        double t_ = Bt[(a) * 3 + k]; Bt[(a) * 3 + k] = Bt[(b) * 3 + k]; Bt[(b) * 3 + k] = t_; \
-        t_ = At[(a) * 3 + k]; At[(a) * 3 + k] = At[(b) * 3 + k]; At[(b) * 3 + k] = t_; \
-    }
-#define ELIMINATE(c)                                                                 \
-    _Pragma("unroll") for (int r = (c) + 1; r < 3; r++) {                            \
-        const double f = Bt[r * 3 + (c)] / Bt[(c) * 3 + (c)];                        \
-        _Pragma("unroll") for (int k = (c); k < 3; k++) Bt[r * 3 + k] = Bt[r * 3 + k] - f * Bt[(c) * 3 + k]; \
-        _Pragma("unroll") for (int k = 0; k < 3; k++) At[r * 3 + k] = At[r * 3 + k] - f * At[(c) * 3 + k]; \
-    }
-    {   // column 0: pivot = first row of the largest |.|
-        const bool p1_ = fabs(Bt[3]) > fabs(Bt[0]);
-        const bool p2_ = fabs(Bt[6]) > fabs(p1_ ? Bt[3] : Bt[0]);
-        if (p2_) { SWAP_ROWS(0, 2) } else if (p1_) { SWAP_ROWS(0, 1) }
-        ELIMINATE(0)
-    }
-    if (fabs(Bt[7]) > fabs(Bt[4])) { SWAP_ROWS(1, 2) }
-    ELIMINATE(1)
-#undef SWAP_ROWS
-#undef ELIMINATE
     double Rt[9];
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int r = 2; r >= 0; r--) {
-            double s = At[r * 3 + k];
-#pragma unroll
-            for (int q = r + 1; q < 3; q++) s = s - Bt[r * 3 + q] * Rt[q * 3 + k];
-            Rt[r * 3 + k] = s / Bt[r * 3 + r];
-        }
+    gauss_solve<3, 3>(Bt, At, Rt);
     double T0[16];
 #pragma unroll
     for (int r = 0; r < 3; r++) {
@@ -1488,19 +1531,52 @@ __device__ __forceinline__ int multi_kept_frames(const int *__restrict__ frame_o
     return nk;
 }
 
-// a group that is not fitted: its status, every other output zero
-__device__ void multi_write_failed(int g, int status, double *__restrict__ o_x0, double *__restrict__ o_x, double *__restrict__ o_T,
-                                   double *__restrict__ o_fvals, int *__restrict__ o_iters, int *__restrict__ o_nused,
-                                   int *__restrict__ o_status)
-{
-    if (threadIdx.x == 0) {
-        for (int k = 0; k < 6; k++) { o_x0[6 * g + k] = 0; o_x[6 * g + k] = 0; }
-        for (int k = 0; k < 16; k++) o_T[16 * g + k] = 0;
-        o_fvals[2 * g] = 0; o_fvals[2 * g + 1] = 0;
-        o_iters[2 * g] = 0; o_iters[2 * g + 1] = 0;
-        o_nused[g] = 0;
-        o_status[g] = status;
+// the outputs of both multi-frame kernels, per group g; written by thread 0 of the workgroup
+struct MultiOut {
+    double *x0, *x, *T, *fvals;
+    int *iters, *nused, *status;
+    // a group that is not fitted: its status, every other output zero
+    __device__ void write_failed(int g, int st) const
+    {
+        if (threadIdx.x != 0) return;
+        for (int k = 0; k < 6; k++) { x0[6 * g + k] = 0; x[6 * g + k] = 0; }
+        for (int k = 0; k < 16; k++) T[16 * g + k] = 0;
+        fvals[2 * g] = 0; fvals[2 * g + 1] = 0;
+        iters[2 * g] = 0; iters[2 * g + 1] = 0;
+        nused[g] = 0;
+        status[g] = st;
     }
+    __device__ void write_ok(int g, const double *xs, const double *xf, double f0, double ffinal, int itercount, int func_evals, int nk) const
+    {
+        if (threadIdx.x != 0) return;
+        double Tf[16];
+        pose_vec2T(xf, Tf);
+        for (int k = 0; k < 6; k++) { x0[6 * g + k] = xs[k]; x[6 * g + k] = xf[k]; }
+        for (int k = 0; k < 16; k++) T[16 * g + k] = Tf[k];
+        fvals[2 * g] = f0; fvals[2 * g + 1] = ffinal;
+        iters[2 * g] = itercount; iters[2 * g + 1] = func_evals;
+        nused[g] = nk;
+        status[g] = CPE_ST_OK;
+    }
+};
+
+// The head of both multi-frame kernels for group g: the kept frames of [group_start[g], group_start[g + 1]) into sIdx (LDS; sNk
+// one int of LDS), one barrier.  -> their count nk >= 2, or 0 after the group's record is written: OVERFLOW for a range outside
+// [0, n] or more than MF_MAXF kept frames, FEW_POINTS below two (assert(nAngles >= 2), fitCylinderWPts3sAngs.m:29)
+__device__ __forceinline__ int multi_group_begin(const int *__restrict__ frame_ok, const int *__restrict__ group_start, int n, int g,
+                                                 int *sIdx, int *sNk, const MultiOut &out)
+{
+    const int a = group_start[g], b = group_start[g + 1];
+    const bool range_ok = 0 <= a && a <= b && b <= n;
+    if (threadIdx.x < 64) {
+        const int nk = multi_kept_frames(frame_ok, a, b, range_ok, threadIdx.x, sIdx);
+        if (threadIdx.x == 0) *sNk = nk;
+    }
+    __syncthreads();
+    const int nk = *sNk;
+    if (!range_ok || nk > MF_MAXF) { out.write_failed(g, CPE_ST_OVERFLOW); return 0; }
+    if (nk < 2) { out.write_failed(g, CPE_ST_FEW_POINTS); return 0; }
+    return nk;
 }
 
 // fitCylinderWPts3sAngs for group g = blockIdx.x: frames [group_start[g], group_start[g+1]) with frame_ok != 0.
@@ -1511,27 +1587,18 @@ __device__ void multi_write_failed(int g, int status, double *__restrict__ o_x0,
 __global__ __launch_bounds__(64 * MF_WAVES) void k_multi_frame_fit(
     const double *__restrict__ X, const int *__restrict__ cnt, const double *__restrict__ TAGV, const double *__restrict__ cyl_raw,
     const int *__restrict__ frame_ok, const int *__restrict__ group_start, int n, double R, double tolx, double tolf, int maxiter,
-    int maxfun, const double *__restrict__ x0_in, double *__restrict__ o_x0, double *__restrict__ o_x, double *__restrict__ o_T,
-    double *__restrict__ o_fvals, int *__restrict__ o_iters, int *__restrict__ o_nused, int *__restrict__ o_status)
+    int maxfun, const double *__restrict__ x0_in, const MultiOut out)
 {
     __builtin_amdgcn_s_setprio(3);   // a long chain of dependent f64 operations on one CU (see k_fit_cylinder)
     __shared__ int sIdx[MF_MAXF];
     __shared__ double sTerms[2 * MF_MAXF];
     __shared__ int sNk;
     const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int a = group_start[g], b = group_start[g + 1];
-    const bool range_ok = 0 <= a && a <= b && b <= n;
-    if (wave == 0) {
-        const int nk = multi_kept_frames(frame_ok, a, b, range_ok, lane, sIdx);
-        if (lane == 0) sNk = nk;
-    }
-    __syncthreads();
-    const int nk = sNk;
-    if (!range_ok || nk > MF_MAXF) { multi_write_failed(g, CPE_ST_OVERFLOW, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
-    if (nk < 2) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }   // assert(nAngles >= 2), :29
+    const int nk = multi_group_begin(frame_ok, group_start, n, g, sIdx, &sNk, out);
+    if (nk == 0) return;
     const int fa = sIdx[0], fb = sIdx[1];
     const int na = min(max(cnt[fa], 0), MAXP), nb = min(max(cnt[fb], 0), MAXP);
-    if (na < 1 || nb < 1) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    if (na < 1 || nb < 1) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
     double x0[6];
     if (x0_in != nullptr) {
 #pragma unroll
@@ -1544,21 +1611,12 @@ __global__ __launch_bounds__(64 * MF_WAVES) void k_multi_frame_fit(
     }
     MultiObjective obj{X, cnt, TAGV, R, sIdx, sTerms, nk, wave, lane, 0};
     const double f0 = obj(x0);
-    if (!fit_finite(x0, f0)) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    if (!fit_finite(x0, f0)) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
     double xf[6], ffinal;
     int itercount, func_evals;
     fit_nm_on(obj, tolx, tolf, maxiter, maxfun, x0, f0, xf, ffinal, itercount, func_evals);
-    if (!fit_finite(xf, ffinal)) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
-    if (threadIdx.x == 0) {
-        double T[16];
-        pose_vec2T(xf, T);
-        for (int k = 0; k < 6; k++) { o_x0[6 * g + k] = x0[k]; o_x[6 * g + k] = xf[k]; }
-        for (int k = 0; k < 16; k++) o_T[16 * g + k] = T[k];
-        o_fvals[2 * g] = f0; o_fvals[2 * g + 1] = ffinal;
-        o_iters[2 * g] = itercount; o_iters[2 * g + 1] = func_evals;
-        o_nused[g] = nk;
-        o_status[g] = CPE_ST_OK;
-    }
+    if (!fit_finite(xf, ffinal)) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+    out.write_ok(g, x0, xf, f0, ffinal, itercount, func_evals, nk);
 }
 
 // ---- BUILD-DEFINED (nothing like it in the reference, as the LM and RANSAC modes of the per-frame fit): the multi-frame fit by
@@ -1587,52 +1645,6 @@ __device__ __forceinline__ void rot_exp(const double *w, double *E)
             const double k2 = (K[r * 3] * K[q] + K[r * 3 + 1] * K[3 + q]) + K[r * 3 + 2] * K[6 + q];
             E[r * 3 + q] = ((r == q ? 1.0 : 0.0) + A * K[r * 3 + q]) + B * k2;
         }
-}
-
-// eigenvectors of a symmetric 4x4 by cyclic Jacobi rotations (eig3's sweep on four rows, at most 30 sweeps): V's columns,
-// w unsorted.  Constant indices throughout, so the matrices stay in registers.
-__device__ void eig4(const double *Ain, double *w, double *V)
-{
-    double A[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) { A[i] = Ain[i]; V[i] = (i % 5 == 0) ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < 30; sweep++) {
-        int rotated = 0;
-#pragma unroll
-        for (int p = 0; p < 3; p++)
-#pragma unroll
-            for (int q = p + 1; q < 4; q++) {
-                const double apq = A[p * 4 + q];
-                if (!(fabs(apq) <= 1e-17 * (fabs(A[p * 4 + p]) + fabs(A[q * 4 + q])))) {
-                    rotated = 1;
-                    const double theta = (A[q * 4 + q] - A[p * 4 + p]) / (2.0 * apq);
-                    double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    if (theta < 0) t = -t;
-                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const double akp = A[k * 4 + p], akq = A[k * 4 + q];
-                        A[k * 4 + p] = c * akp - s * akq;
-                        A[k * 4 + q] = s * akp + c * akq;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const double apk = A[p * 4 + k], aqk = A[q * 4 + k];
-                        A[p * 4 + k] = c * apk - s * aqk;
-                        A[q * 4 + k] = s * apk + c * aqk;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const double vkp = V[k * 4 + p], vkq = V[k * 4 + q];
-                        V[k * 4 + p] = c * vkp - s * vkq;
-                        V[k * 4 + q] = s * vkp + c * vkq;
-                    }
-                }
-            }
-        if (!rotated) break;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) w[i] = A[i * 5];
 }
 
 // rotation matrix (row-major 3x3) of the quaternion (q0, qx, qy, qz), normalised here
@@ -1670,7 +1682,7 @@ __device__ __forceinline__ bool multi_usable(const int *__restrict__ cnt, const 
 // order, then the 64-lane tree.  Every wave of the workgroup computes the same numbers.  -> the two poses as vectors, the
 // usable count.  (A fitted origin may lie far along its axis -- the simplex does not hold it -- and P_i o_i then carries the
 // rounding of |o_i|: 1e10 mm gives about 1e-6 mm.  It is an initial pose.)
-// A singular (sum P_i) (ridge 1e-12 trace as fit_lm's, then a zero determinant) leaves NaN in that pose.
+// A singular (sum P_i) (ridge 1e-12 trace as lm_damped_solve's, then a zero determinant) leaves NaN in that pose.
 __device__ void multi_init_all(const int *__restrict__ cnt, const double *__restrict__ TAGV, const double *__restrict__ cyl_raw,
                                const int *sIdx, int nk, int lane, double *xp, double *xm, int &n_usable)
 {
@@ -1711,7 +1723,7 @@ __device__ void multi_init_all(const int *__restrict__ cnt, const double *__rest
                           S[6] - S[2], S[1] + S[3], (S[4] - S[0]) - S[8], S[5] + S[7],
                           S[1] - S[3], S[6] + S[2], S[5] + S[7], (S[8] - S[0]) - S[4]};
     double w[4], V[16];
-    eig4(N, w, V);
+    jacobi_eig<4>(N, w, V);
     double qp[4] = {V[0], V[4], V[8], V[12]}, qm[4] = {V[0], V[4], V[8], V[12]}, wp = w[0], wm = w[0];
 #pragma unroll
     for (int j = 1; j < 4; j++) {
@@ -1775,137 +1787,88 @@ __device__ void multi_init_all(const int *__restrict__ cnt, const double *__rest
     }
 }
 
-// J'J (upper triangle, 21) and J'r (6) of the residuals r_ik = (d_ik - R) / sqrt(n_i) at the pose T, for the left perturbation
-// Rot <- exp([dw]x) Rot, t <- t + dt.  With o = Rot p + t, v = Rot a, al = ((P - o).v)/|v|^2, e = (P - o) - v al, d = |e| (the
-// quantities of multi_frame_term):  dr/dt = -e/d,  dr/dw = -((Rot p + al v) x e)/d, both / sqrt(n_i) (fit_lm's dr/do and dr/dv
-// through do = dw x Rot p + dt, dv = dw x v; the bottom row of getTAGVcyl is taken as 0 0 0 1).
-// Fixed order: wave w takes kept frames w, w + WAVES, ... in order, lane l of it their points l, l + 64, ..., all into one set
-// of 27 registers; the 64-lane tree; one row of sJ[WAVES][27] per wave; one barrier; every wave adds the rows in wave order.
-// sJ is written again only after a later objective evaluation (an accepted step), whose barrier every wave passes after it has
-// read the rows.  EVERY wave of the workgroup must make the same sequence of calls.
+// The pose of the multi-frame fit as lm_minimize takes it: the objective is obj, a step is the left perturbation Rot <-
+// exp([dw]x) Rot, t <- t + dt of the pose T = vec2T(x) that normal() was last called at.
+// normal(): J'J (upper triangle, 21) and J'r (6) of the residuals r_ik = (d_ik - R) / sqrt(n_i).  With o = Rot p + t, v = Rot a,
+// al, e, d of point_on_axis (the quantities of multi_frame_term):  dr/dt = -e/d,  dr/dw = -((Rot p + al v) x e)/d, both /
+// sqrt(n_i) (CylProblem's dr/do and dr/dv through do = dw x Rot p + dt, dv = dw x v; the bottom row of getTAGVcyl is taken as
+// 0 0 0 1).  Fixed order: wave w takes kept frames w, w + WAVES, ... in order, lane l of it their points l, l + 64, ..., all into
+// one set of 27 registers; the 64-lane tree; one row of sJ[WAVES][27] per wave; one barrier; every wave adds the rows in wave
+// order.  sJ is written again only after a later objective evaluation (an accepted step), whose barrier every wave passes
+// after it has read the rows.  EVERY wave of the workgroup must make the same sequence of calls.
 template <int WAVES>
-__device__ __forceinline__ void multi_lm_normal(const double *__restrict__ X, const int *__restrict__ cnt, const double *__restrict__ TAGV,
-                                                double R, const int *sIdx, int nk, int wave, int lane, const double *T, double *sJ,
-                                                double *A, double *g)
-{
-    double acc[MFLM_SUMS];
+struct MultiPoseProblem {
+    MultiObjectiveT<WAVES> &obj;
+    double *sJ;     // LDS, [WAVES][MFLM_SUMS]
+    double T[16];
+    __device__ __forceinline__ double operator()(const double *x) { return obj(x); }
+    __device__ __forceinline__ void normal(const double *x, double *A, double *g)
+    {
+        pose_vec2T(x, T);
+        double acc[MFLM_SUMS];
 #pragma unroll
-    for (int k = 0; k < MFLM_SUMS; k++) acc[k] = 0.0;
-    for (int kf = wave; kf < nk; kf += WAVES) {
-        const int f = sIdx[kf];
-        const int n = min(max(cnt[f], 0), MAXP);
-        if (n == 0) continue;
-        const double *P = X + (size_t)f * MAXP * 3, *Am = TAGV + 16 * (size_t)f;
-        double org[3], dy[3], q[3];
+        for (int k = 0; k < MFLM_SUMS; k++) acc[k] = 0.0;
+        for (int kf = obj.wave; kf < obj.nk; kf += WAVES) {
+            const int f = obj.sIdx[kf];
+            const int n = min(max(obj.cnt[f], 0), MAXP);
+            if (n == 0) continue;
+            const double *P = obj.X + (size_t)f * MAXP * 3, *Am = obj.TAGV + 16 * (size_t)f;
+            double org[3], dy[3], q[3], v[3], nv2;
+            frame_axis(T, Am, org, dy);
 #pragma unroll
-        for (int r = 0; r < 3; r++) {
-            dy[r] = ((T[r * 4] * Am[1] + T[r * 4 + 1] * Am[5]) + T[r * 4 + 2] * Am[9]) + T[r * 4 + 3] * Am[13];
-            org[r] = ((T[r * 4] * Am[3] + T[r * 4 + 1] * Am[7]) + T[r * 4 + 2] * Am[11]) + T[r * 4 + 3] * Am[15];
-            q[r] = (T[r * 4] * Am[3] + T[r * 4 + 1] * Am[7]) + T[r * 4 + 2] * Am[11];
-        }
-        const double v[3] = {(org[0] + dy[0]) - org[0], (org[1] + dy[1]) - org[1], (org[2] + dy[2]) - org[2]};
-        const double nv2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
-        const double sc = 1.0 / sqrt((double)n);
-        for (int k = lane; k < n; k += 64) {
-            const double *pt = P + 3 * k;
-            const double al = (((pt[0] - org[0]) * v[0] + (pt[1] - org[1]) * v[1]) + (pt[2] - org[2]) * v[2]) / nv2;
-            const double e[3] = {pt[0] - (org[0] + v[0] * al), pt[1] - (org[1] + v[1] * al), pt[2] - (org[2] + v[2] * al)};
-            const double dd = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-            if (dd > 0) {
-                const double r = (dd - R) * sc, c1 = -(sc / dd);
-                const double m[3] = {q[0] + v[0] * al, q[1] + v[1] * al, q[2] + v[2] * al};
-                double mxe[3];
-                cross3(m, e, mxe);
-                const double j[6] = {c1 * mxe[0], c1 * mxe[1], c1 * mxe[2], c1 * e[0], c1 * e[1], c1 * e[2]};
-                int i = 0;
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-#pragma unroll
-                    for (int b = a; b < 6; b++) { acc[i] = acc[i] + j[a] * j[b]; i++; }
-                    acc[21 + a] = acc[21 + a] + j[a] * r;
+            for (int r = 0; r < 3; r++) q[r] = (T[r * 4] * Am[3] + T[r * 4 + 1] * Am[7]) + T[r * 4 + 2] * Am[11];
+            axis_of(org, dy, v, nv2);
+            const double sc = 1.0 / sqrt((double)n);
+            for (int k = obj.lane; k < n; k += 64) {
+                double al, e[3], dd;
+                point_on_axis(P + 3 * k, org, v, nv2, al, e, dd);
+                if (dd > 0) {
+                    const double r = (dd - obj.R) * sc, c1 = -(sc / dd);
+                    const double m[3] = {q[0] + v[0] * al, q[1] + v[1] * al, q[2] + v[2] * al};
+                    double mxe[3];
+                    cross3(m, e, mxe);
+                    const double j[6] = {c1 * mxe[0], c1 * mxe[1], c1 * mxe[2], c1 * e[0], c1 * e[1], c1 * e[2]};
+                    normal_accumulate<6>(j, r, acc);
                 }
             }
         }
-    }
 #pragma unroll
-    for (int k = 0; k < MFLM_SUMS; k++) {
-        const double s = wave_sum(acc[k]);
-        if (lane == 0) sJ[wave * MFLM_SUMS + k] = s;
-    }
-    __syncthreads();
+        for (int k = 0; k < MFLM_SUMS; k++) {
+            const double s = wave_sum(acc[k]);
+            if (obj.lane == 0) sJ[obj.wave * MFLM_SUMS + k] = s;
+        }
+        __syncthreads();
 #pragma unroll
-    for (int k = 0; k < MFLM_SUMS; k++) {
-        double s = 0.0;
-        for (int w = 0; w < WAVES; w++) s = s + sJ[w * MFLM_SUMS + k];
-        if (k < 21) A[k] = s;
-        else g[k - 21] = s;
+        for (int k = 0; k < MFLM_SUMS; k++) {
+            double s = 0.0;
+            for (int w = 0; w < WAVES; w++) s = s + sJ[w * MFLM_SUMS + k];
+            if (k < 21) A[k] = s;
+            else g[k - 21] = s;
+        }
     }
-}
-
-// fit_lm's damped 6x6 system: M = J'J with M_aa (1 + lambda) + 1e-12 trace on the diagonal, M dl = -g by Gaussian elimination
-// with partial pivoting (the first row of the largest |.|, as there).  Row swaps are conditional swaps with constant indices so
-// that the system stays in registers.  false: a zero pivot.
-__device__ __forceinline__ bool multi_lm_solve(const double *A, const double *g, double lambda, double *dl)
-{
-    double M[36], rhs[6];
+    __device__ __forceinline__ bool candidate(const double *, const double *dl, double *xn) const
     {
-        int i = 0;
-        double trA = 0;
+        double E[9], Tn[16];
+        rot_exp(dl, E);
 #pragma unroll
-        for (int a = 0; a < 6; a++)
+        for (int r = 0; r < 3; r++) {
 #pragma unroll
-            for (int b = a; b < 6; b++) { M[a * 6 + b] = A[i]; M[b * 6 + a] = A[i]; if (a == b) trA = trA + A[i]; i++; }
-#pragma unroll
-        for (int a = 0; a < 6; a++) { M[a * 6 + a] = M[a * 6 + a] + lambda * M[a * 6 + a] + 1e-12 * trA; rhs[a] = -g[a]; }
-    }
-    bool singular = false;
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-        int pv = c;
-        double best = fabs(M[c * 6 + c]);
-#pragma unroll
-        for (int r = c + 1; r < 6; r++) {
-            const double av = fabs(M[r * 6 + c]);
-            if (av > best) { best = av; pv = r; }
+            for (int c = 0; c < 3; c++) Tn[r * 4 + c] = (E[r * 3] * T[c] + E[r * 3 + 1] * T[4 + c]) + E[r * 3 + 2] * T[8 + c];
+            Tn[r * 4 + 3] = T[r * 4 + 3] + dl[3 + r];
         }
-#pragma unroll
-        for (int r = c + 1; r < 6; r++)
-            if (pv == r) {
-#pragma unroll
-                for (int k = 0; k < 6; k++) { const double t_ = M[c * 6 + k]; M[c * 6 + k] = M[r * 6 + k]; M[r * 6 + k] = t_; }
-                const double t_ = rhs[c]; rhs[c] = rhs[r]; rhs[r] = t_;
-            }
-        singular = singular || M[c * 6 + c] == 0;
-#pragma unroll
-        for (int r = c + 1; r < 6; r++) {
-            const double fct = M[r * 6 + c] / M[c * 6 + c];
-#pragma unroll
-            for (int k = c; k < 6; k++) M[r * 6 + k] = M[r * 6 + k] - fct * M[c * 6 + k];
-            rhs[r] = rhs[r] - fct * rhs[c];
-        }
+        Tn[12] = 0; Tn[13] = 0; Tn[14] = 0; Tn[15] = 1;
+        pose_T2vec(Tn, xn);
+        return true;
     }
-#pragma unroll
-    for (int r = 5; r >= 0; r--) {
-        double sacc = rhs[r];
-#pragma unroll
-        for (int k = r + 1; k < 6; k++) sacc = sacc - M[r * 6 + k] * dl[k];
-        dl[r] = sacc / M[r * 6 + r];
-    }
-    return !singular;
-}
+};
 
 // The LM form of fitCylinderWPts3sAngs for group g = blockIdx.x (frames as in k_multi_frame_fit).  Barriers: one after the
-// frame list, one per objective evaluation, one per Jacobian pass.  As in k_multi_frame_fit every wave runs the same code on
-// the same numbers (frame list, terms and the 27 sums come from LDS), so every branch goes the same way in all waves and no
-// barrier stands under a condition that depends on the wave or the lane.  Every loop is bounded whatever the objective
-// returns: 200 iterations of at most 12 trials, a NaN objective is a rejected trial.
+// frame list, one per objective evaluation, one per Jacobian pass; lm_minimize's comment says why all waves execute the same ones.
 template <int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void k_multi_frame_lm(
     const double *__restrict__ X, const int *__restrict__ cnt, const double *__restrict__ TAGV, const double *__restrict__ cyl_raw,
     const int *__restrict__ frame_ok, const int *__restrict__ group_start, int n, double R, double tolx, double tolf, int maxiter,
-    const double *__restrict__ x0_in, double *__restrict__ o_x0, double *__restrict__ o_x, double *__restrict__ o_T,
-    double *__restrict__ o_fvals, int *__restrict__ o_iters, int *__restrict__ o_nused, int *__restrict__ o_status,
-    double *__restrict__ o_terms)
+    const double *__restrict__ x0_in, const MultiOut out, double *__restrict__ o_terms)
 {
     __builtin_amdgcn_s_setprio(3);
     __shared__ int sIdx[MF_MAXF];
@@ -1913,16 +1876,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_multi_frame_lm(
     __shared__ double sJ[WAVES * MFLM_SUMS];
     __shared__ int sNk;
     const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int a = group_start[g], b = group_start[g + 1];
-    const bool range_ok = 0 <= a && a <= b && b <= n;
-    if (wave == 0) {
-        const int nk = multi_kept_frames(frame_ok, a, b, range_ok, lane, sIdx);
-        if (lane == 0) sNk = nk;
-    }
-    __syncthreads();
-    const int nk = sNk;
-    if (!range_ok || nk > MF_MAXF) { multi_write_failed(g, CPE_ST_OVERFLOW, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
-    if (nk < 2) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    const int nk = multi_group_begin(frame_ok, group_start, n, g, sIdx, &sNk, out);
+    if (nk == 0) return;
     MultiObjectiveT<WAVES> obj{X, cnt, TAGV, R, sIdx, sTerms, nk, wave, lane, 0};
     double x0[6], f0;
     int func_evals;
@@ -1935,7 +1890,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_multi_frame_lm(
         double xm[6];
         int n_usable;
         multi_init_all(cnt, TAGV, cyl_raw, sIdx, nk, lane, x0, xm, n_usable);
-        if (n_usable < 2) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+        if (n_usable < 2) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
         f0 = obj(x0);
         const double fm = obj(xm);
         func_evals = 2;
@@ -1945,65 +1900,18 @@ __global__ __launch_bounds__(64 * WAVES) void k_multi_frame_lm(
             f0 = fm;
         }
     }
-    if (!fit_finite(x0, f0)) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
-    double x[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) x[k] = x0[k];
-    double fx = f0, lambda = 1e-3;
-    int itercount = 0;
-    for (; itercount < maxiter && itercount < 200;) {
-        double T[16], A[21], gr[6];
-        pose_vec2T(x, T);
-        multi_lm_normal<WAVES>(X, cnt, TAGV, R, sIdx, nk, wave, lane, T, sJ, A, gr);
-        itercount++;
-        bool accepted = false;
-        double dmax = 0;
-        const double fprev = fx;
-        for (int tr = 0; tr < 12 && !accepted; tr++) {
-            double dl[6];
-            if (!multi_lm_solve(A, gr, lambda, dl)) { lambda = lambda * 10; continue; }
-            double E[9], Tn[16], xn[6];
-            rot_exp(dl, E);
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-#pragma unroll
-                for (int c = 0; c < 3; c++) Tn[r * 4 + c] = (E[r * 3] * T[c] + E[r * 3 + 1] * T[4 + c]) + E[r * 3 + 2] * T[8 + c];
-                Tn[r * 4 + 3] = T[r * 4 + 3] + dl[3 + r];
-            }
-            Tn[12] = 0; Tn[13] = 0; Tn[14] = 0; Tn[15] = 1;
-            pose_T2vec(Tn, xn);
-            const double fn = obj(xn);
-            func_evals++;
-            if (fn < fx) {
-                dmax = 0;
-#pragma unroll
-                for (int k = 0; k < 6; k++) { dmax = fmax(dmax, fabs(dl[k])); x[k] = xn[k]; }
-                fx = fn;
-                lambda = fmax(lambda / 10, 1e-12);
-                accepted = true;
-            } else {
-                lambda = lambda * 10;
-            }
-        }
-        if (!accepted) break;
-        if ((fprev - fx) <= tolf * 1e-3 * (1.0 + fx) && dmax <= tolx) break;
-    }
-    if (!fit_finite(x, fx)) { multi_write_failed(g, CPE_ST_FEW_POINTS, o_x0, o_x, o_T, o_fvals, o_iters, o_nused, o_status); return; }
+    if (!fit_finite(x0, f0)) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+    MultiPoseProblem<WAVES> prob{obj, sJ};
+    double x[6], fx;
+    int itercount;
+    lm_minimize<6>(prob, x0, f0, tolx, tolf, maxiter, x, fx, itercount, func_evals);
+    if (!fit_finite(x, fx)) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
     if (o_terms != nullptr) {   // the terms at the returned pose: one more evaluation (not counted), its row of sTerms
         const double *t = sTerms + obj.row * MF_MAXF;
         obj(x);
         for (int k = threadIdx.x; k < nk; k += 64 * WAVES) o_terms[sIdx[k]] = t[k];
     }
-    if (threadIdx.x == 0) {
-        double T[16];
-        pose_vec2T(x, T);
-        for (int k = 0; k < 6; k++) { o_x0[6 * g + k] = x0[k]; o_x[6 * g + k] = x[k]; }
-        for (int k = 0; k < 16; k++) o_T[16 * g + k] = T[k];
-        o_fvals[2 * g] = f0; o_fvals[2 * g + 1] = fx;
-        o_iters[2 * g] = itercount; o_iters[2 * g + 1] = func_evals;
-        o_nused[g] = nk;
-        o_status[g] = CPE_ST_OK;
-    }
+    out.write_ok(g, x0, x, f0, fx, itercount, func_evals, nk);
 }
 
 __global__ __launch_bounds__(64) void k_pose_vec2T(const double *__restrict__ x, int n, double *__restrict__ T)
@@ -2036,7 +1944,7 @@ __global__ __launch_bounds__(64) void k_pose_T2vec(const double *__restrict__ T,
 // agv_chain          : getTAGVcyl.m (default config) on the device, the full product of its five matrices.
 // k_agv_chain        : that for a batch of angle pairs, one lane per pair.
 // k_frame_angles_lm  : one wavefront per frame minimises the frame's term of the multi-frame objective over (pan, tilt) by
-//                      Levenberg-Marquardt with fit_lm's damping, trials and stop rule.
+//                      Levenberg-Marquardt on two unknowns: lm_minimize's loop written out (see the kernel).
 
 // getTAGVcyl.m: TAP * TPT0 * T01 * T12 * T2C in the operation order of cpe_amd/multiframe.py::get_TAGVcyl -- cos(pan), sin(pan),
 // cos(-tilt), sin(-tilt), -tan(tilt) * L, every entry of a product as ((a*b + c*d) + e*f) + g*h.  sin / cos / tan are the
@@ -2090,37 +1998,46 @@ __device__ __forceinline__ void agv_chain_derivatives(double pan, double tilt, d
     dp[3] = cp * dpx; dp[4] = sp * dpx; dp[5] = dpz;
 }
 
-__device__ void frame_angles_write_failed(int f, int lane, int status, double *__restrict__ o_a0, double *__restrict__ o_a,
-                                          double *__restrict__ o_fvals, int *__restrict__ o_iters, double *__restrict__ o_TAGV,
-                                          double *__restrict__ o_Tcyl, int *__restrict__ o_status)
-{
-    if (lane != 0) return;
-    const size_t f2 = 2 * (size_t)f, f16 = 16 * (size_t)f;
-    o_a0[f2] = 0; o_a0[f2 + 1] = 0; o_a[f2] = 0; o_a[f2 + 1] = 0;
-    o_fvals[f2] = 0; o_fvals[f2 + 1] = 0; o_iters[f2] = 0; o_iters[f2 + 1] = 0;
-    if (o_TAGV != nullptr)
-        for (int k = 0; k < 16; k++) o_TAGV[f16 + k] = 0;
-    if (o_Tcyl != nullptr)
-        for (int k = 0; k < 16; k++) o_Tcyl[f16 + k] = 0;
-    o_status[f] = status;
-}
+// the outputs of the angle solver, per frame f (TAGV and Tcyl may be NULL)
+struct AnglesOut {
+    double *a0, *a, *fvals;
+    int *iters;
+    double *TAGV, *Tcyl;
+    int *status;
+    // a frame without angles: its status, every other output zero
+    __device__ void write_failed(int f, int lane, int st) const
+    {
+        if (lane != 0) return;
+        const size_t f2 = 2 * (size_t)f, f16 = 16 * (size_t)f;
+        a0[f2] = 0; a0[f2 + 1] = 0; a[f2] = 0; a[f2 + 1] = 0;
+        fvals[f2] = 0; fvals[f2 + 1] = 0; iters[f2] = 0; iters[f2 + 1] = 0;
+        if (TAGV != nullptr)
+            for (int k = 0; k < 16; k++) TAGV[f16 + k] = 0;
+        if (Tcyl != nullptr)
+            for (int k = 0; k < 16; k++) Tcyl[f16 + k] = 0;
+        status[f] = st;
+    }
+};
 
 // The frame's objective f(q) = multi_frame_term(P, cnt, agv_chain(q), T, R): the bits of cpe_agv_chain_batch +
 // cpe_multi_frame_terms.  Frame f = blockIdx.x, one wavefront.  Every lane holds the same angles, sums and decisions (the
 // sums come out of the 64-lane tree, everything else is computed from per-frame values), so every branch below goes the
 // same way in all lanes and no wave-level operation stands under a lane-dependent condition.  Every loop is bounded whatever
 // the data: min(maxiter, 200) iterations of at most 12 trials; a non-finite objective or candidate is a rejected trial.
+// The loop is lm_minimize's, written out so that the objective, and with it the inlined agv_chain, has a single call site and
+// the chain of an accepted candidate is kept for the Jacobian pass and the outputs.  Both forms under the driver were built
+// and timed: keeping the accepted chain through a hook takes 1 wave/SIMD and 4 % / 24 % more time at 45 / 4096
+// frames, recomputing the chain 16 % / 8 % more.
 __global__ __launch_bounds__(64) void k_frame_angles_lm(
     const double *__restrict__ X, const int *__restrict__ cnt, const double *__restrict__ cyl_raw, const double *__restrict__ Tg,
     const int *__restrict__ pose_index, int G, double R, double tolx, double tolf, int maxiter, const double *__restrict__ a0_in,
-    double *__restrict__ o_a0, double *__restrict__ o_a, double *__restrict__ o_fvals, int *__restrict__ o_iters,
-    double *__restrict__ o_TAGV, double *__restrict__ o_Tcyl, int *__restrict__ o_status)
+    const AnglesOut out)
 {
     const int f = blockIdx.x, lane = threadIdx.x;
     const int pi = pose_index != nullptr ? pose_index[f] : 0;
-    if (pi < 0 || pi >= G) { frame_angles_write_failed(f, lane, CPE_ST_OVERFLOW, o_a0, o_a, o_fvals, o_iters, o_TAGV, o_Tcyl, o_status); return; }
+    if (pi < 0 || pi >= G) { out.write_failed(f, lane, CPE_ST_OVERFLOW); return; }
     const int n = min(max(cnt[f], 0), MAXP);
-    if (n < CPE_FIT_MIN_POINTS) { frame_angles_write_failed(f, lane, CPE_ST_FEW_POINTS, o_a0, o_a, o_fvals, o_iters, o_TAGV, o_Tcyl, o_status); return; }
+    if (n < CPE_FIT_MIN_POINTS) { out.write_failed(f, lane, CPE_ST_FEW_POINTS); return; }
     const double *P = X + (size_t)f * MAXP * 3;
     double T[16];
 #pragma unroll
@@ -2132,10 +2049,7 @@ __global__ __launch_bounds__(64) void k_frame_angles_lm(
     } else {
         // the chain's second column is Rz(pan) (-c, 0, s): a = Rot' d, turned to a_x <= 0 (|pan| < pi/2)
         double o[3], d[3];
-        if (!multi_usable(cnt, cyl_raw, f, o, d)) {
-            frame_angles_write_failed(f, lane, CPE_ST_FEW_POINTS, o_a0, o_a, o_fvals, o_iters, o_TAGV, o_Tcyl, o_status);
-            return;
-        }
+        if (!multi_usable(cnt, cyl_raw, f, o, d)) { out.write_failed(f, lane, CPE_ST_FEW_POINTS); return; }
         double a[3];
 #pragma unroll
         for (int k = 0; k < 3; k++) a[k] = (T[k] * d[0] + T[4 + k] * d[1]) + T[8 + k] * d[2];
@@ -2144,11 +2058,11 @@ __global__ __launch_bounds__(64) void k_frame_angles_lm(
         q0[1] = asin(fmin(fmax(-a[2], -1.0), 1.0));
     }
     // One call site for the objective (the chain's sin / cos / tan are the large part of this kernel): the candidate (c0, c1)
-    // is first the start, then every trial of the LM.  fit_lm's loop, flattened: a new point (the start, an accepted trial)
-    // gets its Jacobian pass and opens an iteration of up to 12 trials.
+    // is first the start, then every trial of the LM.  lm_minimize's loop, flattened (its constants and rules, see there): a
+    // new point (the start, an accepted trial) gets its Jacobian pass and opens an iteration of up to 12 trials.
     double A[16], q[2] = {q0[0], q0[1]}, c0 = q0[0], c1 = q0[1];
-    double f0 = 0.0, fx = 0.0, fprev = 0.0, lambda = 1e-3, d0 = 0.0, d1 = 0.0;
-    double s00 = 0.0, s01 = 0.0, s11 = 0.0, g0 = 0.0, g1 = 0.0;
+    double f0 = 0.0, fx = 0.0, fprev = 0.0, lambda = 1e-3, d[2] = {0.0, 0.0};
+    double S[3] = {0.0, 0.0, 0.0}, g[2] = {0.0, 0.0};   // J'J (00 01 11) and J'r
     int itercount = 0, func_evals = 0, tr = 0;
     bool started = false;
     const double sc = 1.0 / sqrt((double)n);
@@ -2168,7 +2082,7 @@ __global__ __launch_bounds__(64) void k_frame_angles_lm(
             q[0] = c0; q[1] = c1;
             fx = fn;
             lambda = fmax(lambda / 10, 1e-12);
-            if ((fprev - fx) <= tolf * 1e-3 * (1.0 + fx) && fmax(fabs(d0), fabs(d1)) <= tolx) {
+            if ((fprev - fx) <= tolf * 1e-3 * (1.0 + fx) && fmax(fabs(d[0]), fabs(d[1])) <= tolx) {
 #pragma unroll
                 for (int k = 0; k < 16; k++) A[k] = An[k];
                 break;
@@ -2182,79 +2096,71 @@ __global__ __launch_bounds__(64) void k_frame_angles_lm(
 #pragma unroll
             for (int k = 0; k < 16; k++) A[k] = An[k];
             if (!(itercount < maxiter && itercount < 200)) break;
-            // one pass: J'J (3 sums) and J'r (2), r_k = (d_k - R) / sqrt(n), dr/dq = dr/do . do/dq + dr/dv . dv/dq with fit_lm's
+            // one pass: J'J (3 sums) and J'r (2), r_k = (d_k - R) / sqrt(n), dr/dq = dr/do . do/dq + dr/dv . dv/dq with CylProblem's
             // dr/do = -e/d, dr/dv = -(al/d) e and do/dq = Rot dp/dq, dv/dq = Rot da/dq
-            double org[3], dy[3], da[6], dp[6], dob[6], dvb[6];
+            double org[3], dy[3], da[6], dp[6], dob[6], dvb[6], v[3], nv2;
             agv_chain_derivatives(q[0], q[1], da, dp);
+            frame_axis(T, A, org, dy);
 #pragma unroll
-            for (int r = 0; r < 3; r++) {
-                dy[r] = ((T[r * 4] * A[1] + T[r * 4 + 1] * A[5]) + T[r * 4 + 2] * A[9]) + T[r * 4 + 3] * A[13];
-                org[r] = ((T[r * 4] * A[3] + T[r * 4 + 1] * A[7]) + T[r * 4 + 2] * A[11]) + T[r * 4 + 3] * A[15];
+            for (int r = 0; r < 3; r++)
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
                     dob[3 * j + r] = (T[r * 4] * dp[3 * j] + T[r * 4 + 1] * dp[3 * j + 1]) + T[r * 4 + 2] * dp[3 * j + 2];
                     dvb[3 * j + r] = (T[r * 4] * da[3 * j] + T[r * 4 + 1] * da[3 * j + 1]) + T[r * 4 + 2] * da[3 * j + 2];
                 }
-            }
-            const double v[3] = {(org[0] + dy[0]) - org[0], (org[1] + dy[1]) - org[1], (org[2] + dy[2]) - org[2]};
-            const double nv2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
-            s00 = 0.0; s01 = 0.0; s11 = 0.0; g0 = 0.0; g1 = 0.0;
+            axis_of(org, dy, v, nv2);
+            double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
             for (int k = lane; k < n; k += 64) {
-                const double *pt = P + 3 * k;
-                const double al = (((pt[0] - org[0]) * v[0] + (pt[1] - org[1]) * v[1]) + (pt[2] - org[2]) * v[2]) / nv2;
-                const double e[3] = {pt[0] - (org[0] + v[0] * al), pt[1] - (org[1] + v[1] * al), pt[2] - (org[2] + v[2] * al)};
-                const double dd = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+                double al, e[3], dd;
+                point_on_axis(P + 3 * k, org, v, nv2, al, e, dd);
                 if (dd > 0) {
                     const double r = (dd - R) * sc, k1 = -(sc / dd), k2 = k1 * al;
-                    const double j0 = k1 * ((e[0] * dob[0] + e[1] * dob[1]) + e[2] * dob[2]) + k2 * ((e[0] * dvb[0] + e[1] * dvb[1]) + e[2] * dvb[2]);
-                    const double j1 = k1 * ((e[0] * dob[3] + e[1] * dob[4]) + e[2] * dob[5]) + k2 * ((e[0] * dvb[3] + e[1] * dvb[4]) + e[2] * dvb[5]);
-                    s00 = s00 + j0 * j0; s01 = s01 + j0 * j1; s11 = s11 + j1 * j1;
-                    g0 = g0 + j0 * r; g1 = g1 + j1 * r;
+                    const double j[2] = {k1 * ((e[0] * dob[0] + e[1] * dob[1]) + e[2] * dob[2]) + k2 * ((e[0] * dvb[0] + e[1] * dvb[1]) + e[2] * dvb[2]),
+                                         k1 * ((e[0] * dob[3] + e[1] * dob[4]) + e[2] * dob[5]) + k2 * ((e[0] * dvb[3] + e[1] * dvb[4]) + e[2] * dvb[5])};
+                    normal_accumulate<2>(j, r, acc);
                 }
             }
-            s00 = wave_sum(s00); s01 = wave_sum(s01); s11 = wave_sum(s11);
-            g0 = wave_sum(g0); g1 = wave_sum(g1);
+#pragma unroll
+            for (int k = 0; k < 3; k++) S[k] = wave_sum(acc[k]);
+            g[0] = wave_sum(acc[3]);
+            g[1] = wave_sum(acc[4]);
             itercount++;
             tr = 0;
             fprev = fx;
         }
-        // the next trial: fit_lm's damped system, 2 x 2, solved in closed form.  A singular system or a candidate that is not
-        // finite or has |tilt| >= pi/2 - 1e-3 (tan(tilt) of the chain has its pole at pi/2) is a rejected trial.
+        // the next trial.  A singular system or a candidate that is not finite or has |tilt| >= pi/2 - 1e-3 (tan(tilt) of the
+        // chain has its pole at pi/2) is a rejected trial.
         bool have = false;
         for (; tr < 12 && !have;) {
-            const double trA = s00 + s11;
-            const double m00 = s00 + lambda * s00 + 1e-12 * trA, m11 = s11 + lambda * s11 + 1e-12 * trA;
-            const double det = m00 * m11 - s01 * s01;
-            d0 = (s01 * g1 - m11 * g0) / det;
-            d1 = (s01 * g0 - m00 * g1) / det;
-            c0 = q[0] + d0;
-            c1 = q[1] + d1;
-            have = det != 0 && isfinite(c0) && isfinite(c1) && fabs(c1) < 1.5707963267948966 - 1e-3;
+            have = lm_damped_solve<2>(S, g, lambda, d);
+            c0 = q[0] + d[0];
+            c1 = q[1] + d[1];
+            have = have && isfinite(c0) && isfinite(c1) && fabs(c1) < 1.5707963267948966 - 1e-3;
             if (!have) { lambda = lambda * 10; tr++; }
         }
         if (!have) break;
     }
     if (!(isfinite(q0[0]) && isfinite(q0[1]) && isfinite(f0) && isfinite(q[0]) && isfinite(q[1]) && isfinite(fx))) {
-        frame_angles_write_failed(f, lane, CPE_ST_FEW_POINTS, o_a0, o_a, o_fvals, o_iters, o_TAGV, o_Tcyl, o_status);
+        out.write_failed(f, lane, CPE_ST_FEW_POINTS);
         return;
     }
     if (lane == 0) {
         const size_t f2 = 2 * (size_t)f, f16 = 16 * (size_t)f;
-        o_a0[f2] = q0[0]; o_a0[f2 + 1] = q0[1]; o_a[f2] = q[0]; o_a[f2 + 1] = q[1];
-        o_fvals[f2] = f0; o_fvals[f2 + 1] = fx;
-        o_iters[f2] = itercount; o_iters[f2 + 1] = func_evals;
-        if (o_TAGV != nullptr) {
+        out.a0[f2] = q0[0]; out.a0[f2 + 1] = q0[1]; out.a[f2] = q[0]; out.a[f2 + 1] = q[1];
+        out.fvals[f2] = f0; out.fvals[f2 + 1] = fx;
+        out.iters[f2] = itercount; out.iters[f2 + 1] = func_evals;
+        if (out.TAGV != nullptr) {
 #pragma unroll
-            for (int k = 0; k < 16; k++) o_TAGV[f16 + k] = A[k];
+            for (int k = 0; k < 16; k++) out.TAGV[f16 + k] = A[k];
         }
-        if (o_Tcyl != nullptr) {   // T * chain, every entry in multi_frame_term's operation order
+        if (out.Tcyl != nullptr) {   // T * chain, every entry in multi_frame_term's operation order
 #pragma unroll
             for (int r = 0; r < 4; r++)
 #pragma unroll
                 for (int c = 0; c < 4; c++)
-                    o_Tcyl[f16 + r * 4 + c] = ((T[r * 4] * A[c] + T[r * 4 + 1] * A[4 + c]) + T[r * 4 + 2] * A[8 + c]) + T[r * 4 + 3] * A[12 + c];
+                    out.Tcyl[f16 + r * 4 + c] = ((T[r * 4] * A[c] + T[r * 4 + 1] * A[4 + c]) + T[r * 4 + 2] * A[8 + c]) + T[r * 4 + 3] * A[12 + c];
         }
-        o_status[f] = CPE_ST_OK;
+        out.status[f] = CPE_ST_OK;
     }
 }
 }  // namespace
@@ -2285,8 +2191,9 @@ extern "C" int32_t cpe_multi_frame_fit_batch(const double *X, const int32_t *cnt
     CPE_CHECK_ARG(p.mode == CPE_FIT_NELDER_MEAD, "cpe_multi_frame_fit_batch: mode %d (the multi-frame fit is Nelder-Mead only)", p.mode);
     if (G == 0) return CPE_OK;
     CPE_LAUNCH_BEGIN();
+    const MultiOut out{x0, x, T, fvals, iters, n_used, status};
     CPE_KLAUNCH(k_multi_frame_fit, dim3(G), dim3(64 * MF_WAVES), 0, (hipStream_t)stream, X, cnt, TAGVcyl, cyl_raw, frame_ok, group_start,
-                n, radius, p.tol_x, p.tol_f, p.max_iter, p.max_fun_evals, x0_in, x0, x, T, fvals, iters, n_used, status);
+                n, radius, p.tol_x, p.tol_f, p.max_iter, p.max_fun_evals, x0_in, out);
     CPE_CHECK_LAUNCH("k_multi_frame_fit");
     return CPE_OK;
 }
@@ -2308,8 +2215,9 @@ extern "C" int32_t cpe_multi_frame_fit_lm_batch(const double *X, const int32_t *
                   p.mode);
     if (G == 0) return CPE_OK;
     CPE_LAUNCH_BEGIN();
+    const MultiOut out{x0, x, T, fvals, iters, n_used, status};
     CPE_KLAUNCH(k_multi_frame_lm<MFLM_WAVES>, dim3(G), dim3(64 * MFLM_WAVES), 0, (hipStream_t)stream, X, cnt, TAGVcyl, cyl_raw, frame_ok,
-                group_start, n, radius, p.tol_x, p.tol_f, p.max_iter, x0_in, x0, x, T, fvals, iters, n_used, status, frame_terms);
+                group_start, n, radius, p.tol_x, p.tol_f, p.max_iter, x0_in, out, frame_terms);
     CPE_CHECK_LAUNCH("k_multi_frame_lm");
     return CPE_OK;
 }
@@ -2361,8 +2269,9 @@ extern "C" int32_t cpe_frame_angles_lm_batch(const double *X, const int32_t *cnt
     CPE_CHECK_ARG(X && cnt && T && angles0 && angles && fvals && iters && status, "cpe_frame_angles_lm_batch: null pointer");
     CPE_CHECK_ARG(cyl_raw || a0_in, "cpe_frame_angles_lm_batch: cyl_raw may be NULL only beside a0_in");
     CPE_LAUNCH_BEGIN();
+    const AnglesOut out{angles0, angles, fvals, iters, TAGVcyl, Tcyl, status};
     CPE_KLAUNCH(k_frame_angles_lm, dim3(n), dim3(64), 0, (hipStream_t)stream, X, cnt, cyl_raw, T, pose_index, G, radius, p.tol_x, p.tol_f,
-                p.max_iter, a0_in, angles0, angles, fvals, iters, TAGVcyl, Tcyl, status);
+                p.max_iter, a0_in, out);
     CPE_CHECK_LAUNCH("k_frame_angles_lm");
     return CPE_OK;
 }
