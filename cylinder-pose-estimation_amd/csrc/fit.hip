@@ -2502,3 +2502,324 @@ extern "C" int32_t cpe_match_offset_batch(const double *xy1, const int32_t *id1,
     CPE_CHECK_LAUNCH("k_match_pick");
     return CPE_OK;
 }
+
+// ------------------------------------------------------------------------------------------ planar target
+// BUILD-DEFINED (include/cpe.h cpe_fit_plane_batch, cpe_index_planes_batch): fitplane.m:1-16 per frame with an optional
+// trimming loop, the affine grid map, the board pose; and the laser planes over several board poses with their common point.
+// The points are read from global memory in every pass (a frame's table is at most 48 KB and stays in L2); lane l takes points
+// l, l + 64, ... and the sums go through wave_sum, as everywhere in this file.
+namespace {
+
+__device__ __forceinline__ bool finite3(const double *p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
+
+// the moments a plane fit starts from
+struct PlaneMoments {
+    double c[3], w[3], V[9];   // centroid, eigenvalues ascending, eigenvectors (columns)
+    int N;
+};
+
+// enough points, and not collinear or coincident: lambda_mid > 1e-12 lambda_max
+__device__ __forceinline__ bool plane_spread_ok(const PlaneMoments &m) { return m.N >= 3 && m.w[1] > 1e-12 * m.w[2]; }
+
+// centroid, then the centred covariance / (N - 1) in a second pass, then its eigen-decomposition (wave-uniform results; the normal
+// of fitplane.m is V(:,1)).  `each(body)` calls body(p) for every point p[3] of the set that this lane takes; it is walked twice
+template <class Each>
+__device__ __forceinline__ void plane_moments(Each each, PlaneMoments &m)
+{
+    double s[3] = {0, 0, 0};
+    int cn = 0;
+    each([&](const double *p) { s[0] = s[0] + p[0]; s[1] = s[1] + p[1]; s[2] = s[2] + p[2]; cn++; });
+    m.N = wave_sum_i(cn);
+    const double N = (double)(m.N > 0 ? m.N : 1);
+#pragma unroll
+    for (int a = 0; a < 3; a++) m.c[a] = wave_sum(s[a]) / N;
+    double q[6] = {0, 0, 0, 0, 0, 0};
+    const double c0 = m.c[0], c1 = m.c[1], c2 = m.c[2];
+    each([&](const double *p) {
+        const double e0 = p[0] - c0, e1 = p[1] - c1, e2 = p[2] - c2;
+        q[0] = q[0] + e0 * e0; q[1] = q[1] + e0 * e1; q[2] = q[2] + e0 * e2;
+        q[3] = q[3] + e1 * e1; q[4] = q[4] + e1 * e2; q[5] = q[5] + e2 * e2;
+    });
+    const double d = (double)(m.N > 1 ? m.N - 1 : 1);
+#pragma unroll
+    for (int a = 0; a < 6; a++) q[a] = wave_sum(q[a]) / d;
+    const double Cv[9] = {q[0], q[1], q[2], q[1], q[3], q[4], q[2], q[4], q[5]};
+    eig3(Cv, m.w, m.V);
+}
+
+__global__ __launch_bounds__(64) void k_fit_plane(const double *__restrict__ X, const int *__restrict__ idx, const int *__restrict__ cnt,
+                                                  double tau, int max_rounds, double *__restrict__ o_P, double *__restrict__ o_T,
+                                                  double *__restrict__ o_grid, double *__restrict__ o_stats, int *__restrict__ o_ninl,
+                                                  uint8_t *__restrict__ o_mask, int *__restrict__ o_flags, int *__restrict__ o_status)
+{
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int n = min(max(cnt[f], 0), MAXP);
+    const double *Xf = X + (size_t)f * MAXP * 3;
+    const int *If = idx + (size_t)f * MAXP * 2;
+    // the mask of the current fit lives in the output: slot k is written and read by lane k % 64 only
+    uint8_t *mk = o_mask + (size_t)f * MAXP;
+    for (int k = lane; k < MAXP; k += 64) mk[k] = (k < n && finite3(Xf + 3 * k)) ? 1 : 0;
+    auto each = [&](auto body) {
+        for (int k = lane; k < n; k += 64)
+            if (mk[k]) body(Xf + 3 * k);
+    };
+    PlaneMoments m;
+    double nrm[3], P4 = 0;
+    int refits = 0;
+    bool ok;
+    for (;;) {
+        plane_moments(each, m);
+        ok = plane_spread_ok(m);
+        if (!ok) break;
+        nrm[0] = m.V[0]; nrm[1] = m.V[3]; nrm[2] = m.V[6];
+        const bool flip = nrm[2] < 0 || (nrm[2] == 0 && (nrm[1] < 0 || (nrm[1] == 0 && nrm[0] < 0)));
+        if (flip) { nrm[0] = -nrm[0]; nrm[1] = -nrm[1]; nrm[2] = -nrm[2]; }
+        P4 = -((nrm[0] * m.c[0] + nrm[1] * m.c[1]) + nrm[2] * m.c[2]);
+        if (!(tau > 0) || refits >= max_rounds) break;
+        int changed = 0;
+        for (int k = lane; k < n; k += 64) {
+            const double *p = Xf + 3 * k;
+            const uint8_t in = (finite3(p) && fabs(((nrm[0] * p[0] + nrm[1] * p[1]) + nrm[2] * p[2]) + P4) < tau) ? 1 : 0;
+            changed += in != mk[k];
+            mk[k] = in;
+        }
+        if (wave_sum_i(changed) == 0) break;
+        refits++;
+    }
+    if (!ok) {
+        for (int k = lane; k < n; k += 64) mk[k] = 0;
+        if (lane < 4) o_P[(size_t)f * 4 + lane] = 0;
+        if (lane < 16) o_T[(size_t)f * 16 + lane] = 0;
+        if (lane < 9) o_grid[(size_t)f * 9 + lane] = 0;
+        if (lane < 8) o_stats[(size_t)f * 8 + lane] = 0;
+        if (lane == 0) { o_ninl[f] = 0; o_flags[f] = 0; o_status[f] = CPE_ST_FEW_POINTS; }
+        return;
+    }
+    // residuals, index moments, the first point with index (0,0)
+    double r2 = 0, rmax = 0, sa = 0, sb = 0;
+    int first0 = INT_MAX;
+    for (int k = lane; k < n; k += 64) {
+        if (!mk[k]) continue;
+        const double *p = Xf + 3 * k;
+        const double r = fabs(((nrm[0] * p[0] + nrm[1] * p[1]) + nrm[2] * p[2]) + P4);
+        r2 = r2 + r * r;
+        rmax = fmax(rmax, r);
+        const int a = If[2 * k], b = If[2 * k + 1];
+        sa = sa + (double)a; sb = sb + (double)b;
+        if (a == 0 && b == 0) first0 = min(first0, k);
+    }
+    const double N = (double)m.N;
+    r2 = wave_sum(r2);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) rmax = fmax(rmax, __shfl_xor(rmax, off, 64));
+    const double ma = wave_sum(sa) / N, mb = wave_sum(sb) / N;
+    first0 = wave_min_i(first0);
+    // normal equations of X - c ~ (a - ma) U + (b - mb) V
+    double g[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // Saa Sab Sbb | Sa.x[3] | Sb.x[3]
+    for (int k = lane; k < n; k += 64) {
+        if (!mk[k]) continue;
+        const double *p = Xf + 3 * k;
+        const double da = (double)If[2 * k] - ma, db = (double)If[2 * k + 1] - mb;
+        const double e0 = p[0] - m.c[0], e1 = p[1] - m.c[1], e2 = p[2] - m.c[2];
+        g[0] = g[0] + da * da; g[1] = g[1] + da * db; g[2] = g[2] + db * db;
+        g[3] = g[3] + da * e0; g[4] = g[4] + da * e1; g[5] = g[5] + da * e2;
+        g[6] = g[6] + db * e0; g[7] = g[7] + db * e1; g[8] = g[8] + db * e2;
+    }
+#pragma unroll
+    for (int a = 0; a < 9; a++) g[a] = wave_sum(g[a]);
+    int flags = 0;
+    double UV[6] = {0, 0, 0, 0, 0, 0}, O[3] = {0, 0, 0}, grms = 0;
+    if (g[0] * g[2] - g[1] * g[1] <= 1e-12 * (g[0] * g[2])) flags |= CPE_PLANEFIT_NO_GRID;
+    else {
+        double M[4] = {g[0], g[1], g[1], g[2]}, rhs[6] = {g[3], g[4], g[5], g[6], g[7], g[8]};
+        gauss_solve<2, 3>(M, rhs, UV);
+#pragma unroll
+        for (int a = 0; a < 3; a++) O[a] = m.c[a] - (ma * UV[a] + mb * UV[3 + a]);
+        double e = 0;
+        for (int k = lane; k < n; k += 64) {
+            if (!mk[k]) continue;
+            const double *p = Xf + 3 * k;
+            const double a = (double)If[2 * k], b = (double)If[2 * k + 1];
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const double d = p[c] - ((O[c] + a * UV[c]) + b * UV[3 + c]);
+                e = e + d * d;
+            }
+        }
+        grms = sqrt(wave_sum(e) / N);
+    }
+    // pose
+    double ux[3] = {1, 0, 0};
+    if (!(flags & CPE_PLANEFIT_NO_GRID)) { ux[0] = UV[0]; ux[1] = UV[1]; ux[2] = UV[2]; }
+    double xa[3], xn;
+    {
+        const double un = (ux[0] * nrm[0] + ux[1] * nrm[1]) + ux[2] * nrm[2];
+#pragma unroll
+        for (int a = 0; a < 3; a++) xa[a] = ux[a] - un * nrm[a];
+        xn = sqrt((xa[0] * xa[0] + xa[1] * xa[1]) + xa[2] * xa[2]);
+    }
+    if (!(xn > 0) || !isfinite(xn)) {
+        const double un = nrm[1];
+        xa[0] = 0 - un * nrm[0]; xa[1] = 1 - un * nrm[1]; xa[2] = 0 - un * nrm[2];
+        xn = sqrt((xa[0] * xa[0] + xa[1] * xa[1]) + xa[2] * xa[2]);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) xa[a] = xa[a] / xn;
+    const double ya[3] = {nrm[1] * xa[2] - nrm[2] * xa[1], nrm[2] * xa[0] - nrm[0] * xa[2], nrm[0] * xa[1] - nrm[1] * xa[0]};
+    double org[3] = {m.c[0], m.c[1], m.c[2]};
+    if (first0 != INT_MAX) {
+        flags |= CPE_PLANEFIT_ORIGIN_POINT;
+        org[0] = Xf[3 * first0]; org[1] = Xf[3 * first0 + 1]; org[2] = Xf[3 * first0 + 2];
+    } else if (!(flags & CPE_PLANEFIT_NO_GRID)) {
+        org[0] = O[0]; org[1] = O[1]; org[2] = O[2];
+    }
+    {
+        const double d = ((nrm[0] * org[0] + nrm[1] * org[1]) + nrm[2] * org[2]) + P4;
+#pragma unroll
+        for (int a = 0; a < 3; a++) org[a] = org[a] - d * nrm[a];
+    }
+    if (lane == 0) {
+        double *P = o_P + (size_t)f * 4, *T = o_T + (size_t)f * 16, *G = o_grid + (size_t)f * 9, *S = o_stats + (size_t)f * 8;
+        P[0] = nrm[0]; P[1] = nrm[1]; P[2] = nrm[2]; P[3] = P4;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            T[a * 4 + 0] = xa[a]; T[a * 4 + 1] = ya[a]; T[a * 4 + 2] = nrm[a]; T[a * 4 + 3] = org[a];
+            G[a] = O[a]; G[3 + a] = UV[a]; G[6 + a] = UV[3 + a];
+            S[2 + a] = m.w[a];
+        }
+        T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
+        S[0] = sqrt(r2 / N); S[1] = rmax; S[5] = grms; S[6] = (double)refits; S[7] = 0;
+        o_ninl[f] = m.N; o_flags[f] = flags; o_status[f] = CPE_ST_OK;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_index_planes(const double *__restrict__ X, const int *__restrict__ idx, const int *__restrict__ cnt,
+                                                     int n, const uint8_t *__restrict__ use, const int *__restrict__ frame_ok, int lo, int L,
+                                                     double min_spread, double *__restrict__ o_P, double *__restrict__ o_stats,
+                                                     int *__restrict__ o_count, int *__restrict__ o_frames, int *__restrict__ o_status)
+{
+    const int line = blockIdx.x, lane = threadIdx.x;   // line = family * L + (v - lo)
+    const int fam = line / L, v = lo + (line - fam * L);
+    int frames = 0;
+    bool count_frames = true;
+    auto each = [&](auto body) {
+        for (int f = 0; f < n; f++) {
+            if (frame_ok && frame_ok[f] == 0) continue;
+            const int c = min(max(cnt[f], 0), MAXP);
+            const size_t base = (size_t)f * MAXP;
+            bool any = false;
+            for (int k = lane; k < c; k += 64) {
+                if (idx[(base + k) * 2 + fam] != v) continue;
+                if (use && use[base + k] == 0) continue;
+                const double *p = X + (base + k) * 3;
+                if (!finite3(p)) continue;
+                body(p);
+                any = true;
+            }
+            if (count_frames && __ballot(any) != 0ull) frames++;
+        }
+        count_frames = false;
+    };
+    PlaneMoments m;
+    plane_moments(each, m);
+    bool ok = m.N >= 3 && frames >= 2 && m.w[2] > 0;
+    const double spread = ok ? m.w[1] / m.w[2] : 0.0;
+    ok = ok && !(spread < min_spread);
+    double nrm[3] = {m.V[0], m.V[3], m.V[6]}, P4 = 0, r2 = 0, rmax = 0;
+    if (ok) {
+        const double a0 = fabs(nrm[0]), a1 = fabs(nrm[1]), a2 = fabs(nrm[2]);
+        const double big = (a0 >= a1 && a0 >= a2) ? nrm[0] : (a1 >= a2 ? nrm[1] : nrm[2]);
+        if (big < 0) { nrm[0] = -nrm[0]; nrm[1] = -nrm[1]; nrm[2] = -nrm[2]; }
+        P4 = -((nrm[0] * m.c[0] + nrm[1] * m.c[1]) + nrm[2] * m.c[2]);
+        each([&](const double *p) {
+            const double r = fabs(((nrm[0] * p[0] + nrm[1] * p[1]) + nrm[2] * p[2]) + P4);
+            r2 = r2 + r * r;
+            rmax = fmax(rmax, r);
+        });
+        r2 = wave_sum(r2);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) rmax = fmax(rmax, __shfl_xor(rmax, off, 64));
+    }
+    if (lane == 0) {
+        double *P = o_P + (size_t)line * 4, *S = o_stats + (size_t)line * 4;
+        P[0] = ok ? nrm[0] : 0.0; P[1] = ok ? nrm[1] : 0.0; P[2] = ok ? nrm[2] : 0.0; P[3] = ok ? P4 : 0.0;
+        S[0] = ok ? sqrt(r2 / (double)m.N) : 0.0; S[1] = ok ? rmax : 0.0; S[2] = ok ? spread : 0.0; S[3] = 0;
+        o_count[line] = m.N; o_frames[line] = frames; o_status[line] = ok ? CPE_ST_OK : CPE_ST_FEW_POINTS;
+    }
+}
+
+// the point nearest to all OK planes: (sum n n') C = -sum n P4
+__global__ __launch_bounds__(64) void k_planes_centre(const double *__restrict__ P, const int *__restrict__ status, int L,
+                                                      double *__restrict__ o_centre, int *__restrict__ o_status)
+{
+    const int lane = threadIdx.x;
+    double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int ok0 = 0, ok1 = 0;
+    for (int i = lane; i < 2 * L; i += 64) {
+        if (status[i] != CPE_ST_OK) continue;
+        const double j[3] = {P[4 * i], P[4 * i + 1], P[4 * i + 2]};
+        normal_accumulate<3>(j, P[4 * i + 3], acc);
+        if (i < L) ok0++; else ok1++;
+    }
+#pragma unroll
+    for (int a = 0; a < 9; a++) acc[a] = wave_sum(acc[a]);
+    ok0 = wave_sum_i(ok0); ok1 = wave_sum_i(ok1);
+    double M[9] = {acc[0], acc[1], acc[2], acc[1], acc[3], acc[4], acc[2], acc[4], acc[5]};
+    double rhs[3] = {-acc[6], -acc[7], -acc[8]}, Cc[3] = {0, 0, 0};
+    bool ok = gauss_solve<3>(M, rhs, Cc);
+    ok = ok && ok0 >= 2 && ok1 >= 2 && finite3(Cc);
+    double e = 0;
+    if (ok)
+        for (int i = lane; i < 2 * L; i += 64) {
+            if (status[i] != CPE_ST_OK) continue;
+            const double r = ((P[4 * i] * Cc[0] + P[4 * i + 1] * Cc[1]) + P[4 * i + 2] * Cc[2]) + P[4 * i + 3];
+            e = e + r * r;
+        }
+    e = wave_sum(e);
+    if (lane == 0) {
+        o_centre[0] = ok ? Cc[0] : 0.0; o_centre[1] = ok ? Cc[1] : 0.0; o_centre[2] = ok ? Cc[2] : 0.0;
+        o_centre[3] = ok ? sqrt(e / (double)(ok0 + ok1)) : 0.0;
+        o_status[0] = ok ? CPE_ST_OK : CPE_ST_FEW_POINTS;
+    }
+}
+}  // namespace
+
+extern "C" int32_t cpe_fit_plane_batch(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n,
+                                       const CpePlaneFitParams *params, double *P, double *T, double *grid, double *stats,
+                                       int32_t *n_inliers, uint8_t *inlier_mask, int32_t *flags, int32_t *status, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_fit_plane_batch: n < 0");
+    CpePlaneFitParams p = {0.0, 4, 0};
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.max_rounds >= 0 && p.max_rounds <= CPE_PLANEFIT_MAX_ROUNDS && !(p.tau != p.tau),
+                  "cpe_fit_plane_batch: bad CpePlaneFitParams (max_rounds 0..%d, tau not NaN)", CPE_PLANEFIT_MAX_ROUNDS);
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(X && idx && cnt && P && T && grid && stats && n_inliers && inlier_mask && flags && status,
+                  "cpe_fit_plane_batch: null pointer");
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_fit_plane, dim3(n), dim3(64), 0, (hipStream_t)stream, X, idx, cnt, p.tau, p.max_rounds, P, T, grid, stats, n_inliers,
+                inlier_mask, flags, status);
+    CPE_CHECK_LAUNCH("k_fit_plane");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_index_planes_batch(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n, const uint8_t *use,
+                                          const int32_t *frame_ok, int32_t lo, int32_t hi, double min_spread, double *P,
+                                          double *stats, int32_t *count, int32_t *frames, int32_t *status, double *centre,
+                                          int32_t *centre_status, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_index_planes_batch: n < 0");
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_index_planes_batch: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    CPE_CHECK_ARG(min_spread >= 0, "cpe_index_planes_batch: min_spread < 0");
+    CPE_CHECK_ARG((n == 0 || (X && idx && cnt)) && P && stats && count && frames && status && centre && centre_status,
+                  "cpe_index_planes_batch: null pointer");
+    const int L = hi - lo + 1;
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_index_planes, dim3(2 * L), dim3(64), 0, (hipStream_t)stream, X, idx, cnt, n, use, frame_ok, lo, L, min_spread, P, stats,
+                count, frames, status);
+    CPE_CHECK_LAUNCH("k_index_planes");
+    CPE_KLAUNCH(k_planes_centre, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double *)P, (const int *)status, L, centre, centre_status);
+    CPE_CHECK_LAUNCH("k_planes_centre");
+    return CPE_OK;
+}

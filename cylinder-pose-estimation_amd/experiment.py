@@ -63,6 +63,50 @@ def _upload(images, device):
     return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(device)     # (uint16 bits: iotool.StereoPrestep)
 
 
+def _list_pairs(input_path):
+    """the stems of the folder and their (left, right) paths; every `<stem>L.png` needs its `<stem>R.png`"""
+    names = unique_names(input_path)
+    if not names:
+        raise FileNotFoundError(f'no <name>L.png in {input_path}')
+    paths = [(os.path.join(input_path, s + 'L.png'), os.path.join(input_path, s + 'R.png')) for s in names]
+    for pair in paths:
+        for p in pair:
+            if not os.path.isfile(p):
+                raise FileNotFoundError(p)
+    return names, paths
+
+
+def _run_pairs(names, paths, camera_json, dev, chunk, make_fits, make_pipeline):
+    """the read / upload loop of run_experiment and run_plane_experiment: the pairs are read in windows of `chunk`, runs of one
+    element type and channel count are uploaded together and go through FramePipeline.run_raw of make_pipeline(h, w, chunk)
+    -> records f64 [F,16], the tensors of make_fits(F) filled"""
+    cam_l, cam_r = iotool.load_camera_data(camera_json)
+    F, chunk = len(names), max(1, int(chunk))
+    pipe = pre = None
+    recs = torch.empty((F, pipeline.REC), dtype=torch.float64, device=dev)
+    fits = make_fits(F)
+    for w0 in range(0, F, chunk):
+        imgs = [(read_raw_image(l), read_raw_image(r)) for l, r in paths[w0:w0 + chunk]]
+        if pipe is None:
+            h, w = imgs[0][0].shape[:2]
+            pre = iotool.StereoPrestep(cam_l, cam_r, h, w, dev)
+            pipe = make_pipeline(h, w, chunk)
+        kinds = [tuple((a.dtype, a.shape) for a in pair) for pair in imgs]
+        for kd, s in zip(kinds, names[w0:]):
+            if any(shape[:2] != (pipe.h, pipe.w) for _, shape in kd):
+                raise _lib.CpeError(f'{s}: image size differs from the first pair ({pipe.w}x{pipe.h})')
+        i0 = 0
+        while i0 < len(imgs):                           # frames of one element type and channel count go together
+            i1 = i0 + 1
+            while i1 < len(imgs) and kinds[i1] == kinds[i0]:
+                i1 += 1
+            left = _upload([p[0] for p in imgs[i0:i1]], dev)
+            right = _upload([p[1] for p in imgs[i0:i1]], dev)
+            recs[w0 + i0:w0 + i1] = pipe.run_raw(left, right, pre, {k: t[w0 + i0:w0 + i1] for k, t in fits.items()})
+            i0 = i1
+    return recs, fits
+
+
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
                    frame_angles=False, match_offset=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
@@ -91,40 +135,12 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     multiframe.estimate_frame_angles_gpu with T_cam_agv, a self-check of the calibration in degrees.  The dict gains
     angles_est (F x 2, rad; NaN for a skipped or failed frame), angles_status (F; the solver's status, -1 for a frame that was
     not given to it) and angles_delta_deg (estimated - nominal); all three are None without a multi-frame result."""
-    names = unique_names(input_path)
-    if not names:
-        raise FileNotFoundError(f'no <name>L.png in {input_path}')
-    paths = [(os.path.join(input_path, s + 'L.png'), os.path.join(input_path, s + 'R.png')) for s in names]
-    for pair in paths:
-        for p in pair:
-            if not os.path.isfile(p):
-                raise FileNotFoundError(p)
+    names, paths = _list_pairs(input_path)
     angles = np.deg2rad(parse_img_info(names))          # exp_gridDetection.m:26-27
-    cam_l, cam_r = iotool.load_camera_data(camera_json)
-    F, chunk = len(names), max(1, int(chunk))
     dev = torch.device(device)
-    pipe = pre = None
-    recs = torch.empty((F, pipeline.REC), dtype=torch.float64, device=dev)
-    fits = pipeline.alloc_fits(F, dev)
-    for w0 in range(0, F, chunk):
-        imgs = [(read_raw_image(l), read_raw_image(r)) for l, r in paths[w0:w0 + chunk]]
-        if pipe is None:
-            h, w = imgs[0][0].shape[:2]
-            pre = iotool.StereoPrestep(cam_l, cam_r, h, w, dev)
-            pipe = pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=chunk, device=dev, match=match_offset)
-        kinds = [tuple((a.dtype, a.shape) for a in pair) for pair in imgs]
-        for kd, s in zip(kinds, names[w0:]):
-            if any(shape[:2] != (pipe.h, pipe.w) for _, shape in kd):
-                raise _lib.CpeError(f'{s}: image size differs from the first pair ({pipe.w}x{pipe.h})')
-        i0 = 0
-        while i0 < len(imgs):                           # frames of one element type and channel count go together
-            i1 = i0 + 1
-            while i1 < len(imgs) and kinds[i1] == kinds[i0]:
-                i1 += 1
-            left = _upload([p[0] for p in imgs[i0:i1]], dev)
-            right = _upload([p[1] for p in imgs[i0:i1]], dev)
-            recs[w0 + i0:w0 + i1] = pipe.run_raw(left, right, pre, {k: t[w0 + i0:w0 + i1] for k, t in fits.items()})
-            i0 = i1
+    recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, lambda F: pipeline.alloc_fits(F, dev),
+                            lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=c, device=dev, match=match_offset))
+    F = len(names)
     _, _, d_fit, d_l, d_r = pipeline.unpack_counters(recs[:, 15])          # device tensors: the 'gpu' mode masks with them
     st_fit, st_l, st_r = (t.cpu().tolist() for t in (d_fit, d_l, d_r))
     if match_offset is None:
@@ -181,3 +197,71 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
             est[good] = np.where((st == 0)[:, None], fa['angles'].cpu().numpy(), np.nan)
             res.update(angles_est=est, angles_status=status, angles_delta_deg=np.rad2deg(est - angles))
     return res
+
+
+# Laser planes of one projector meet in its centre: 0.02 mm rms on 12 analytic poses with 0.25 px noise (tests/plane_fit_cases.py).
+# Fifty times that says the planes are not one projector's, i.e. the index pairing between the two images is off.
+PLANE_CENTRE_RMS_WARN = 1.0     # mm
+
+
+def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_rounds=4, min_spread=1e-4, device='cuda:0', chunk=32):
+    """BUILD-DEFINED (the reference stops at the planar detector): a folder of `<name>L.png` / `<name>R.png` pairs of a flat board
+    in several poses -> the board's plane and pose in every frame, and the projector's laser-plane table with its centre.
+
+    Per pair: imread, preProcessing, the planar detector L/R, the selector, fit.fit_plane_batch (tau, max_rounds) --
+    FramePipeline(target='plane').run_raw over the same read / upload loop as run_experiment.  Then one
+    fit.index_planes_batch call over the good frames and their inlier masks, with lo, hi the range of the grid indices those
+    frames hold (both components).
+
+    LIMIT.  Everything behind the detector pairs the grid points of the two images by equal index.  The planar detector (a
+    restatement of the reference's) is not pinned to number both images alike: on boards rendered by synth.Scene(target='plane')
+    it numbers the columns of the left and the right image in opposite directions, the pairs are then not the same grid points,
+    and planes, poses and table come out with status 0 and millimetres wrong.  Nothing per frame shows it (planarity cannot
+    score a correspondence); the table does: laser planes of a consistent numbering meet in the
+    projector's centre to hundredths of a millimetre (0.02 mm rms on 12 analytic poses with 0.25 px noise).  A table whose
+    centre is refused, or whose planes miss it by more than PLANE_CENTRE_RMS_WARN = 1 mm rms, raises a UserWarning, and
+    `consistent` is False: do not calibrate from such a result.
+
+    -> dict(names, records f64 [F,16] (the planar layout beside pipeline.REC), P f64 [F,4], T f64 [F,4,4], grid f64 [F,3,3],
+            stats f64 [F,8], pts3 f64 [F,MAXP,3], idx i32 [F,MAXP,2], cnt i32 [F], n_inliers i32 [F], inlier_mask u8 [F,MAXP],
+            plane_flags i32 [F], skipped (as run_experiment: frames whose left / right detect status or fit status is non-zero),
+            table = the dict of fit.index_planes_batch (P, stats, count, frames, status [2,L,..], centre, centre_status, lo, hi)
+            or None when no frame is good or the indices span more than CPE_MAXL values (a warning says which),
+            consistent = the table exists, has a centre, and its planes meet there within PLANE_CENTRE_RMS_WARN)"""
+    names, paths = _list_pairs(input_path)
+    dev = torch.device(device)
+    recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, lambda F: pipeline.alloc_fits(F, dev, 'plane'),
+                            lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, 0.0, chunk=c, device=dev, target='plane',
+                                                                   plane=dict(tau=tau, max_rounds=max_rounds)))
+    F = len(names)
+    _, _, d_fit, d_l, d_r = pipeline.unpack_counters(recs[:, 15])
+    frame_ok = ((d_fit == 0) & (d_l == 0) & (d_r == 0)).to(torch.int32)
+    # the index range of the points the table may use, with the statuses in one copy
+    used = (fits['inlier_mask'] != 0) & (frame_ok != 0)[:, None]
+    big = torch.iinfo(torch.int32).max
+    lo = torch.where(used[..., None], fits['idx'], big).amin()
+    hi = torch.where(used[..., None], fits['idx'], -big).amax()
+    back = torch.cat([torch.stack([d_fit, d_l, d_r]).to(torch.int64).reshape(-1), torch.stack([lo, hi]).to(torch.int64)]).cpu().tolist()
+    st_fit, st_l, st_r, (lo, hi) = back[:F], back[F:2 * F], back[2 * F:3 * F], back[3 * F:]
+    skipped = [dict(index=i, name=names[i], det_left=st_l[i], det_right=st_r[i], fit=st_fit[i])
+               for i in range(F) if st_l[i] or st_r[i] or st_fit[i]]
+    table, consistent = None, False
+    if lo > hi:
+        warnings.warn('no fitted frame: no laser-plane table')
+    elif hi - lo + 1 > _lib.MAXL:
+        warnings.warn(f'grid indices {lo}..{hi} span more than {_lib.MAXL} values: no laser-plane table')
+    else:
+        table = fit.index_planes_batch(fits['pts3'], fits['idx'], fits['m'], lo, hi, use=fits['inlier_mask'], frame_ok=frame_ok,
+                                       min_spread=min_spread)
+        c_rms, c_st = torch.cat([table['centre'][3:4], table['centre_status'].to(torch.float64)]).cpu().tolist()
+        if c_st != 0:
+            warnings.warn('the laser planes give no common point (fewer than 2 usable lines in a family, or planes that do not '
+                          'determine a point): no projector centre')
+        elif c_rms > PLANE_CENTRE_RMS_WARN:
+            warnings.warn(f'the laser planes miss their common point by {c_rms:.2f} mm rms (more than {PLANE_CENTRE_RMS_WARN} mm): the '
+                          'grid numbering of the two images probably disagrees, planes and table are not to be trusted')
+        else:
+            consistent = True
+    return dict(names=names, records=recs, P=fits['P'], T=fits['T'], grid=fits['grid'], stats=fits['stats'], pts3=fits['pts3'],
+                idx=fits['idx'], cnt=fits['m'], n_inliers=fits['n_inliers'], inlier_mask=fits['inlier_mask'],
+                plane_flags=fits['plane_flags'], skipped=skipped, table=table, consistent=consistent)

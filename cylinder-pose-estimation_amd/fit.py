@@ -206,3 +206,83 @@ def fit_single_cylinder_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, rad
     out.update(fit)
     out.update(extra)
     return out
+
+
+PLANE_NO_GRID, PLANE_ORIGIN_POINT = 1, 2            # CPE_PLANEFIT_*
+
+
+def _point_tables(what, pts3, idx, cnt, use=None):
+    """the tables as the kernels read them: contiguous f64[n,MAXP,3], i32[n,MAXP,2], i32[n], u8[n,MAXP] on one device"""
+    n = cnt.shape[0]
+    for name, t, dt, shape in (('pts3', pts3, torch.float64, (n, MAXP, 3)), ('idx', idx, torch.int32, (n, MAXP, 2)),
+                               ('cnt', cnt, torch.int32, (n,)), ('use', use, torch.uint8, (n, MAXP))):
+        if t is None:
+            continue
+        if t.dtype != dt or tuple(t.shape) != shape or t.device != pts3.device:
+            raise TypeError(f'{what}: {name} must be {dt} {list(shape)} on {pts3.device}, got {t.dtype} {list(t.shape)} on {t.device}')
+    c = lambda t: None if t is None else t.contiguous()
+    return c(pts3), c(idx), c(cnt), c(use)
+
+
+def fit_plane_batch(pts3, idx, cnt, tau=0.0, max_rounds=4):
+    """BUILD-DEFINED, the planar target's fit (fitplane.m with an optional trimming loop, the grid map, the board pose), see
+    include/cpe.h cpe_fit_plane_batch.  pts3 f64[n,MAXP,3], idx i32[n,MAXP,2], cnt i32[n] as select_triangulate_batch returns them
+    -> dict(P f64[n,4], T f64[n,4,4], grid f64[n,3,3] (O, U, V), stats f64[n,8] (plane rms, max |r|, 3 eigenvalues, grid rms,
+            refits, 0), n_inliers i32[n], inlier_mask u8[n,MAXP], plane_flags i32[n] (PLANE_*), status i32[n])"""
+    L = _lib.load()
+    pts3, idx, cnt, _ = _point_tables('fit_plane_batch', pts3, idx, cnt)
+    dev = pts3.device
+    n = cnt.shape[0]
+    # (the kernel writes every slot of every output: no fills)
+    f64 = torch.empty(n * (4 + 16 + 9 + 8), dtype=torch.float64, device=dev)
+    P, T, grid, stats = f64[:4 * n].view(n, 4), f64[4 * n:20 * n].view(n, 4, 4), f64[20 * n:29 * n].view(n, 3, 3), f64[29 * n:].view(n, 8)
+    i32 = torch.empty((3, n), dtype=torch.int32, device=dev)
+    ninl, flags, st = i32[0], i32[1], i32[2]
+    mask = torch.empty((n, MAXP), dtype=torch.uint8, device=dev)
+    prm = _lib.CpePlaneFitParams(float(tau), int(max_rounds), 0)
+    _lib.check(L.cpe_fit_plane_batch(pts3.data_ptr(), idx.data_ptr(), cnt.data_ptr(), n, C.addressof(prm), P.data_ptr(), T.data_ptr(),
+                                     grid.data_ptr(), stats.data_ptr(), ninl.data_ptr(), mask.data_ptr(), flags.data_ptr(),
+                                     st.data_ptr(), _stream()), 'cpe_fit_plane_batch')
+    return dict(P=P, T=T, grid=grid, stats=stats, n_inliers=ninl, inlier_mask=mask, plane_flags=flags, status=st)
+
+
+def index_planes_batch(pts3, idx, cnt, lo, hi, use=None, frame_ok=None, min_spread=1e-4):
+    """BUILD-DEFINED: the plane of light of every grid-line index lo..hi of both index components over the frames of the batch
+    (several board poses), and the point nearest to all of them: the projector's centre.  See include/cpe.h
+    cpe_index_planes_batch.  use u8[n,MAXP] (e.g. fit_plane_batch's inlier_mask) and frame_ok i32[n] are optional.
+    -> dict(P f64[2,L,4], stats f64[2,L,4] (rms, max |r|, lambda_mid / lambda_max, 0), count, frames, status i32[2,L],
+            centre f64[4] (C, rms), centre_status i32[1], lo, hi)"""
+    L = _lib.load()
+    pts3, idx, cnt, use = _point_tables('index_planes_batch', pts3, idx, cnt, use)
+    dev = pts3.device
+    n = cnt.shape[0]
+    nl = int(hi) - int(lo) + 1
+    if not 1 <= nl <= _lib.MAXL:
+        raise ValueError(f'index_planes_batch: {nl} indices in [{lo}, {hi}], must be 1..{_lib.MAXL}')
+    if frame_ok is not None:
+        if frame_ok.shape != (n,) or frame_ok.device != dev:
+            raise TypeError(f'index_planes_batch: frame_ok must hold {n} values on {dev}')
+        frame_ok = frame_ok.to(torch.int32).contiguous()
+    # (the kernels write every slot of every output: no fills)
+    f64 = torch.empty(2 * nl * 8 + 4, dtype=torch.float64, device=dev)
+    P, stats, centre = f64[:8 * nl].view(2, nl, 4), f64[8 * nl:16 * nl].view(2, nl, 4), f64[16 * nl:]
+    i32 = torch.empty(3 * 2 * nl + 1, dtype=torch.int32, device=dev)
+    count, frames, st, cst = i32[:2 * nl].view(2, nl), i32[2 * nl:4 * nl].view(2, nl), i32[4 * nl:6 * nl].view(2, nl), i32[6 * nl:]
+    _lib.check(L.cpe_index_planes_batch(pts3.data_ptr(), idx.data_ptr(), cnt.data_ptr(), n, None if use is None else use.data_ptr(),
+                                        None if frame_ok is None else frame_ok.data_ptr(), int(lo), int(hi), float(min_spread),
+                                        P.data_ptr(), stats.data_ptr(), count.data_ptr(), frames.data_ptr(), st.data_ptr(),
+                                        centre.data_ptr(), cst.data_ptr(), _stream()), 'cpe_index_planes_batch')
+    return dict(P=P, stats=stats, count=count, frames=frames, status=st, centre=centre, centre_status=cst, lo=int(lo), hi=int(hi))
+
+
+def fit_single_plane_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, selector=SEL_CHOOSE_IDX, patch=3, th=0.3, tau=0.0,
+                           max_rounds=4):
+    """the planar counterpart of fit_single_cylinder_batch: select_triangulate_batch, then fit_plane_batch on its points and
+    indices.  Returns the selector's outputs beside the fit's; status is the fit's, or ST_OVERFLOW where the selector set
+    FLAG_OVERFLOW (such a frame has m = 0, so all its fit outputs are zero)."""
+    sel = select_triangulate_batch(gp1, gp2, K1, K2, T21, selector, patch, th)
+    fit = fit_plane_batch(sel['pts3'], sel['idx'], sel['m'], tau=tau, max_rounds=max_rounds)
+    fit['status'].masked_fill_((sel['flags'] & FLAG_OVERFLOW) != 0, ST_OVERFLOW)
+    out = dict(sel)
+    out.update(fit)
+    return out

@@ -74,6 +74,9 @@ _SIGS = {
     'cpe_match_offset_workspace_bytes': (C.c_size_t, [C.c_int32] * 3),
     'cpe_match_offset_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_double, C.c_void_p, C.c_void_p, C.c_size_t] +
                                [C.c_void_p] * 6),
+    'cpe_fit_plane_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 10),
+    'cpe_index_planes_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double] +
+                               [C.c_void_p] * 8),
     'cpe_undistort_map': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_remap_bilinear_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_undistort_map_matlab': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -127,6 +130,10 @@ class CpeRansacParams(C.Structure):
 class CpeMatchParams(C.Structure):
     _fields_ = [('win_c', C.c_int32), ('win_r', C.c_int32), ('th', C.c_double), ('tau', C.c_double), ('hyp_iters', C.c_int32),
                 ('min_score', C.c_int32)]
+
+
+class CpePlaneFitParams(C.Structure):
+    _fields_ = [('tau', C.c_double), ('max_rounds', C.c_int32), ('reserved', C.c_int32)]
 
 
 MAXP = 2048

@@ -9,6 +9,9 @@ import torch
 from . import api, fit
 
 REC = 16   # f64 per frame: cyl0[6] | cyl[6] (both after applyCylParamsPrior) | f0 f | meanError | packed counters
+# target='plane' (build-defined), the same 16 doubles:
+#   0:4 P = [n, P4] | 4:7 origin | 7:10 x-axis (both of the pose T) | 10 |U| | 11 |V| (grid pitch on the board along either index) |
+#   12 plane rms | 13 max |r| | 14 meanError | 15 pack_counters(m, refits, status, st_l, st_r)
 
 
 def pack_counters(n_pts, iters, fit_status, det_l, det_r):
@@ -31,7 +34,7 @@ class FramePipeline:
     """reusable workspaces for chunks of `chunk` stereo frames of size h x w"""
 
     def __init__(self, h, w, K1, K2, T21, radius, chunk=64, device='cuda:0', selector=fit.SEL_CHOOSE_IDX, th=0.3,
-                 fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full', match=None):
+                 fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full', match=None, target='cylinder', plane=None):
         self.h, self.w, self.chunk, self.device = h, w, chunk, torch.device(device)
         self.K1, self.K2, self.T21, self.radius = K1, K2, T21, radius
         self.selector, self.th, self.fit_mode = selector, th, fit_mode
@@ -39,6 +42,14 @@ class FramePipeline:
         self.match = match              # None, or keywords of fit.match_offset_batch (build-defined: the index-shift search, stage 'full')
         if stage not in ('full', 'detect'):
             raise ValueError("stage is 'full' or 'detect'")
+        if target not in ('cylinder', 'plane'):
+            raise ValueError("target is 'cylinder' or 'plane'")
+        if target == 'plane' and (match is not None or ransac is not None):
+            raise ValueError("target='plane': match and ransac score with the cylinder's radius and do not apply (radius is not read)")
+        if target != 'plane' and plane is not None:
+            raise ValueError("plane= holds keywords of the planar fit: target='plane' only")
+        self.target = target            # 'plane' (build-defined): the planar detector and fit.fit_single_plane_batch; records as beside REC
+        self.plane = dict(plane or {})  # keywords of fit.fit_plane_batch: tau, max_rounds
         self.stage = stage              # 'detect': stop after chooseIdx + triangulate (fitSingleCylinder.m:12-17), no cylinder fit
         self.ws = {}
         # chunks are independent: `lanes` of them are in flight on their own HIP streams (each with its own
@@ -67,14 +78,14 @@ class FramePipeline:
         if c > 0 and self._interleaved(left, right):
             # the pairs already lie one after the other in memory: the detect call reads them in place (L0 R0 L1 R1 ...)
             frames = torch.as_strided(left, (2 * c, self.h, self.w), (self.h * self.w, self.w, 1))
-            det = api.detect_grid_batch(frames, self._ws(2 * c, lane), debug_planes=False)   # only the tables are read
+            det = api.detect_grid_batch(frames, self._ws(2 * c, lane), target=self.target, debug_planes=False)   # only the tables are read
             sl = lambda k, o: det[k][o::2].contiguous()
             g1 = fit.GridTables(sl('xy', 0), sl('id', 0), sl('n', 0))
             g2 = fit.GridTables(sl('xy', 1), sl('id', 1), sl('n', 1))
             st_l, st_r = det['status'][0::2], det['status'][1::2]
         else:
             frames = torch.cat([left, right])             # [2c,h,w]: one detect call for both cameras (a copy)
-            det = api.detect_grid_batch(frames, self._ws(2 * c, lane), debug_planes=False)   # only the tables are read
+            det = api.detect_grid_batch(frames, self._ws(2 * c, lane), target=self.target, debug_planes=False)   # only the tables are read
             g1 = fit.GridTables(det['xy'][:c], det['id'][:c], det['n'][:c])
             g2 = fit.GridTables(det['xy'][c:], det['id'][c:], det['n'][c:])
             st_l, st_r = det['status'][:c], det['status'][c:]
@@ -84,6 +95,17 @@ class FramePipeline:
             rec[:, 14] = out['mean_err']
             zero = torch.zeros_like(out['m'])
             rec[:, 15] = pack_counters(out['m'], zero, zero, st_l, st_r)
+            return rec, det, out
+        if self.target == 'plane':
+            out = fit.fit_single_plane_batch(g1, g2, self.K1, self.K2, self.T21, self.selector, 3, self.th, **self.plane)
+            rec = torch.empty((c, REC), dtype=torch.float64, device=frames.device)
+            rec[:, 0:4] = out['P']
+            rec[:, 4:7] = out['T'][:, :3, 3]
+            rec[:, 7:10] = out['T'][:, :3, 0]
+            rec[:, 10:12] = out['grid'][:, 1:3].norm(dim=2)
+            rec[:, 12:14] = out['stats'][:, 0:2]
+            rec[:, 14] = out['mean_err']
+            rec[:, 15] = pack_counters(out['m'], out['stats'][:, 6], out['status'], st_l, st_r)
             return rec, det, out
         rk = None if self.ransac is None else dict(self.ransac, frame0=int(self.ransac.get('frame0', 0)) + frame0)
         out = fit.fit_single_cylinder_batch(g1, g2, self.K1, self.K2, self.T21, self.radius, self.selector, 3, self.th,
@@ -128,7 +150,7 @@ class FramePipeline:
         """raw camera frames [F,h,w] / [F,h,w,3] on the device (uint8, uint16, float32, float64: iotool.StereoPrestep) ->
         records f64 [F,16].  Per chunk the pre-step (preProcessing.m:3-9) writes the undistorted grey pairs into the lane's
         staging tensor [chunk,2,h,w] and the detect call reads them there in place.
-        fits: None, or tensors from alloc_fits(F, device) that receive every frame's fitSingleCylinder outputs."""
+        fits: None, or tensors from alloc_fits(F, device[, target]) that receive every frame's fit outputs."""
         if (prestep.h, prestep.w) != (self.h, self.w):
             raise ValueError(f'run_raw: the pre-step is for {prestep.w}x{prestep.h} frames, the pipeline for {self.w}x{self.h}')
         if fits is not None and self.stage != 'full':
@@ -152,6 +174,14 @@ FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), m=((), torch.int32), cyl
                    offset=((2,), torch.int32), match_score=((4,), torch.int32), match_flags=((), torch.int32))
 
 
-def alloc_fits(F, device):
-    """zeroed [F, ...] tensors for the per-frame outputs of fit.fit_single_cylinder_batch that FramePipeline.run_raw can keep"""
-    return {k: torch.zeros((F,) + shape, dtype=dt, device=device) for k, (shape, dt) in FIT_OUTPUTS.items()}
+PLANE_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2), torch.int32), m=((), torch.int32), P=((4,), torch.float64),
+                         T=((4, 4), torch.float64), grid=((3, 3), torch.float64), stats=((8,), torch.float64), n_inliers=((), torch.int32),
+                         inlier_mask=((fit.MAXP,), torch.uint8), plane_flags=((), torch.int32), mean_err=((), torch.float64),
+                         status=((), torch.int32))
+
+
+def alloc_fits(F, device, target='cylinder'):
+    """zeroed [F, ...] tensors for the per-frame outputs of fit.fit_single_cylinder_batch (target='plane': of
+    fit.fit_single_plane_batch) that FramePipeline.run_raw can keep"""
+    outputs = dict(cylinder=FIT_OUTPUTS, plane=PLANE_FIT_OUTPUTS)[target]
+    return {k: torch.zeros((F,) + shape, dtype=dt, device=device) for k, (shape, dt) in outputs.items()}

@@ -35,8 +35,11 @@ class Scene:
     background: tuple = (6.0, 16.0)
     noise_sigma: float = 1.5
     spot_radius_px: tuple = (16.0, 26.0)
+    target: str = 'cylinder'        # 'plane': a flat board through the drawn point, its normal the z axis tilted by tilt_deg; radius unused
 
     def __post_init__(self):
+        if self.target not in ('cylinder', 'plane'):
+            raise ValueError("Scene.target is 'cylinder' or 'plane'")
         if self.focal is None:
             self.focal = 1.55 * self.w
         if self.half_lines is None:
@@ -82,6 +85,10 @@ def _frame_params(scene: Scene, n, seed):
     peak = rng.uniform(*scene.peak, n)
     bg = rng.uniform(*scene.background, n)
     spot = rng.uniform(*scene.spot_radius_px, n)
+    if scene.target == 'plane':
+        # the same draws name a board: through org, normal = z tilted by the two angles (n_z > 0: pointing away from the cameras)
+        dirs = np.stack([np.sin(az), np.sin(ax) * np.cos(az), np.cos(az) * np.cos(ax)], 1)
+        dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
     return dict(org=org, dir=dirs, peak=peak, bg=bg, spot=spot)
 
 
@@ -98,6 +105,14 @@ def _cyl_hit(o, d, c, a, R):
     disc = B * B - 4 * A * Cc
     hit = disc > 0
     s = (-B - torch.sqrt(disc.clamp_min(0))) / (2 * A)
+    return s, hit & (s > 0)
+
+
+def _plane_hit(o, d, c, n):
+    """intersection parameter of rays o + s d with the plane through c with unit normal n; torch, broadcast."""
+    dn = (d * n).sum(-1)
+    hit = dn.abs() > 1e-9
+    s = ((c - o) * n).sum(-1) / torch.where(hit, dn, torch.ones_like(dn))
     return s, hit & (s > 0)
 
 
@@ -132,10 +147,16 @@ def _render_view(scene, K, Tcam, Tp, fp, delta, device, gen, chunk=None):
         peak = torch.tensor(fp['peak'][i0:i1], dtype=dt, device=device).view(B, 1, 1)
         bg = torch.tensor(fp['bg'][i0:i1], dtype=dt, device=device).view(B, 1, 1)
         spot_r = torch.tensor(fp['spot'][i0:i1], dtype=dt, device=device).view(B, 1, 1)
-        s, hit = _cyl_hit(o1, d1, c, a, scene.radius)
+        if scene.target == 'plane':
+            s, hit = _plane_hit(o1, d1, c, a)
+        else:
+            s, hit = _cyl_hit(o1, d1, c, a, scene.radius)
         X = o1 + s.unsqueeze(-1) * d1                                # surface point, cam-1 coords [B,h,w,3]
         wv = X - c
-        nrm = (wv - (wv * a).sum(-1, keepdim=True) * a) / scene.radius
+        if scene.target == 'plane':
+            nrm = (-a).expand_as(X)                                  # the board's lit side faces the cameras
+        else:
+            nrm = (wv - (wv * a).sum(-1, keepdim=True) * a) / scene.radius
         toP = Op - X
         ndot = (nrm * toP).sum(-1)
         lit = hit & (ndot > 0)
@@ -165,7 +186,8 @@ def _render_view(scene, K, Tcam, Tp, fp, delta, device, gen, chunk=None):
 
 
 def ground_truth(scene: Scene, K1, K2, T21, Tp, fp, delta):
-    """per frame: dict(idx [m,2] (col,row) projector indices, X [m,3], uv1 [m,2], uv2 [m,2])"""
+    """per frame: dict(idx [m,2] (col,row) projector indices, X [m,3], uv1 [m,2], uv2 [m,2]); target='plane': also n [3], d
+    (the board is n.X = d, n_z > 0)"""
     N, Nv = scene.half_lines, scene.half_lines_v
     ii, jj = np.meshgrid(np.arange(-N, N + 1), np.arange(-Nv, Nv + 1), indexing='ij')
     rays_p = np.stack([ii.ravel() * delta, jj.ravel() * delta, np.ones(ii.size)], 1)
@@ -175,6 +197,16 @@ def ground_truth(scene: Scene, K1, K2, T21, Tp, fp, delta):
     res = []
     for i in range(fp['org'].shape[0]):
         c, a = fp['org'][i], fp['dir'][i]
+        if scene.target == 'plane':
+            s = ((c - Op) @ a) / (d @ a)
+            X = Op + s[:, None] * d
+            X2 = X @ T21[:3, :3].T + T21[:3, 3]
+            p1 = X @ K1.T; uv1 = p1[:, :2] / p1[:, 2:3]
+            p2 = X2 @ K2.T; uv2 = p2[:, :2] / p2[:, 2:3]
+            m = (s > 0) & (uv1[:, 0] > 0) & (uv1[:, 0] < scene.w - 1) & (uv1[:, 1] > 0) & (uv1[:, 1] < scene.h - 1) & \
+                (uv2[:, 0] > 0) & (uv2[:, 0] < scene.w - 1) & (uv2[:, 1] > 0) & (uv2[:, 1] < scene.h - 1)
+            res.append(dict(idx=np.stack([ii.ravel(), jj.ravel()], 1)[m], X=X[m], uv1=uv1[m], uv2=uv2[m], n=a.copy(), d=float(a @ c)))
+            continue
         wv = Op - c
         da = d @ a
         dp = d - da[:, None] * a
@@ -200,7 +232,9 @@ def ground_truth(scene: Scene, K1, K2, T21, Tp, fp, delta):
 
 
 def render_batch(n, h=1200, w=1920, seed=0, device='cpu', scene: Scene = None, with_gt=True):
-    """n stereo frames.  returns dict(left u8[n,h,w], right u8[n,h,w], K1, K2, T21, radius, axis_org, axis_dir, gt)"""
+    """n stereo frames.  returns dict(left u8[n,h,w], right u8[n,h,w], K1, K2, T21, radius, axis_org, axis_dir, gt); with
+    scene.target == 'plane' also plane_n [n,3], plane_d [n] (the boards n.X = d; axis_org lies on them, axis_dir is plane_n) and
+    Tp (the projector pose, camera 1 -> projector)"""
     scene = scene or Scene(h=h, w=w)
     K1, K2, T21, Tp = make_rig(scene)
     fp = _frame_params(scene, n, seed)
@@ -211,6 +245,8 @@ def render_batch(n, h=1200, w=1920, seed=0, device='cpu', scene: Scene = None, w
     right = _render_view(scene, K2, T21, Tp, fp, delta, device, gen)
     out = dict(left=left, right=right, K1=K1, K2=K2, T21=T21, radius=scene.radius,
                axis_org=fp['org'], axis_dir=fp['dir'], scene=scene)
+    if scene.target == 'plane':
+        out.update(plane_n=fp['dir'], plane_d=(fp['dir'] * fp['org']).sum(1), Tp=Tp)
     if with_gt:
         out['gt'] = ground_truth(scene, K1, K2, T21, Tp, fp, delta)
     return out

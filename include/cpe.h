@@ -45,14 +45,14 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 116   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 117   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
                              111: cpe_debug_clahe_planes_bgr; 112: cpe_multi_frame_fit_batch, cpe_pose_vec2T_batch,
                              cpe_pose_T2vec_batch; 113: cpe_multi_frame_fit_lm_batch; 114: cpe_agv_chain_batch,
                              cpe_frame_angles_lm_batch; 115: cpe_debug_region_hull; 116: cpe_match_offset_batch,
-                             cpe_match_offset_workspace_bytes) */
+                             cpe_match_offset_workspace_bytes; 117: cpe_fit_plane_batch, cpe_index_planes_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -590,6 +590,65 @@ CPE_API int32_t cpe_match_offset_batch(const double *xy1, const int32_t *id1, co
                                        const double *T21, double radius, const CpeMatchParams *params, void *ws, size_t ws_bytes,
                                        int32_t *offset, int32_t *score, int32_t *scores, int32_t *flags, int32_t *id1_out,
                                        void *stream);
+
+/* BUILD-DEFINED, the geometric half of the planar target (CPE_TARGET_PLANE): the plane of a flat board per frame, the grid
+ * the projector draws on it, and the board's pose.  One wavefront per frame.  The plane is fitplane.m:1-16 -- cov(pts'), eig,
+ * normal V(:,1), P = [n, -mean(n*pts)] -- everything else is build-defined.
+ *   X f64[n,CPE_MAXP,3], idx i32[n,CPE_MAXP,2], cnt i32[n] as cpe_select_triangulate_batch writes them (the two components
+ *   of idx are called a and b here: which of them is "col" is never interpreted); params NULL = {tau 0, max_rounds 4}.
+ * Rule (the order is the contract):
+ *   1. a point with a non-finite coordinate is never used;
+ *   2. round 0 fits all usable points: centroid, then the centred covariance / (N - 1) in a second pass, eigenvalues
+ *      ascending; n = first eigenvector with n_z > 0 (n_z == 0: the first non-zero component positive, DESIGN.md section 2,
+ *      deviation 2); P = [n, -n.centroid];
+ *   3. tau > 0: the inliers of the last plane are the usable points with |n.X + P4| < tau; when they are the set the last plane
+ *      was fitted to, or after max_rounds refits, the loop ends, otherwise the plane is refitted to them.  tau <= 0: fitplane;
+ *   4. a fit to fewer than 3 points, or with lambda_mid <= 1e-12 lambda_max (collinear, coincident), ends the frame:
+ *      CPE_ST_FEW_POINTS and every output of the frame zero.  So CPE_ST_OK implies finite outputs;
+ *   5. grid map over the points of the last fit: least squares X ~ O + a U + b V, indices and points centred first, the 2 x 2
+ *      normal equations solved by elimination; Saa Sbb - Sab^2 <= 1e-12 Saa Sbb (all indices on one line): CPE_PLANEFIT_NO_GRID,
+ *      grid and its rms zero;
+ *   6. pose T (board frame -> camera 1, as cylT): z = n; x = normalise(U - (U.n) n), U = [1,0,0] under NO_GRID (cylParams2T.m),
+ *      [0,1,0] should that leave nothing; y = z x x; origin = the first point of the last fit, in table order, with index
+ *      (0,0), projected onto the plane (CPE_PLANEFIT_ORIGIN_POINT), else O projected onto the plane, else (NO_GRID) the centroid.
+ * Outputs: P f64[n,4]; T f64[n,16] row-major; grid f64[n,9] = O U V; stats f64[n,8] = plane rms (sqrt of the mean squared
+ *   distance), max |distance|, the three eigenvalues ascending, grid-map rms (sqrt of the mean squared 3-D misfit), refits done, 0
+ *   -- all over the points of the last fit; n_inliers i32[n] their number; inlier_mask u8[n,CPE_MAXP] 1 on them, 0 elsewhere and
+ *   past the count; flags i32[n] CPE_PLANEFIT_*; status i32[n].
+ * cnt is clamped to [0, CPE_MAXP]; slots past it are never read.  One launch on `stream`, no host synchronisation. */
+#define CPE_PLANEFIT_NO_GRID 1        /* bits of `flags` */
+#define CPE_PLANEFIT_ORIGIN_POINT 2
+#define CPE_PLANEFIT_MAX_ROUNDS 64
+typedef struct CpePlaneFitParams {
+    double tau;           /* inlier band |n.X + P4| < tau, the unit of the points; <= 0: no trimming (default) */
+    int32_t max_rounds;   /* refits at the most, 0..CPE_PLANEFIT_MAX_ROUNDS; default 4 */
+    int32_t reserved;     /* 0 */
+} CpePlaneFitParams;
+CPE_API int32_t cpe_fit_plane_batch(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n,
+                                    const CpePlaneFitParams *params, double *P, double *T, double *grid, double *stats,
+                                    int32_t *n_inliers, uint8_t *inlier_mask, int32_t *flags, int32_t *status, void *stream);
+
+/* BUILD-DEFINED: the laser planes of the projector from several board poses.  A grid line of fixed index is a plane of light
+ * through the projector; the points that carry the index in several frames determine it, and all planes together the
+ * projector's centre.  One wavefront per (family k, index v): family k in {0,1} is component k of idx, v in [lo, hi],
+ * L = hi - lo + 1 in 1..CPE_MAXL (otherwise CPE_ERR_ARG).
+ *   X, idx, cnt as above; use u8[n,CPE_MAXP] or NULL (all points; the inlier_mask above); frame_ok i32[n] or NULL (non-zero =
+ *   the frame is kept); min_spread >= 0 (1e-4 is a good value).
+ * The wavefront walks the kept frames and takes the usable (finite, `use`) points with idx[k] == v: centroid, centred
+ * covariance / (N - 1) in a second pass, n = first eigenvector with its largest-magnitude component (the first of them)
+ * positive (MATLAB pca's sign rule), P = [n, -n.centroid].
+ *   P f64[2,L,4]; stats f64[2,L,4] = rms, max |distance|, lambda_mid / lambda_max, 0; count i32[2,L] points; frames i32[2,L]
+ *   kept frames that contributed; status i32[2,L]: CPE_ST_FEW_POINTS, with the line's P and stats zero (count and frames
+ *   stay), for fewer than 3 points, fewer than 2 frames (one pose gives a straight line), lambda_max <= 0 or
+ *   lambda_mid / lambda_max < min_spread.
+ * A last wavefront (second launch) solves the 3 x 3 normal equations of the point C minimising sum (n_k.C + P4_k)^2 over the
+ * OK lines of both families: centre f64[4] = C, rms; centre_status i32[1] = CPE_ST_FEW_POINTS (centre zero) when either family
+ * has fewer than 2 OK lines or the elimination meets a zero pivot.
+ * cnt is clamped to [0, CPE_MAXP]; slots past it are never read; n = 0 is allowed (every line CPE_ST_FEW_POINTS). */
+CPE_API int32_t cpe_index_planes_batch(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n, const uint8_t *use,
+                                       const int32_t *frame_ok, int32_t lo, int32_t hi, double min_spread, double *P,
+                                       double *stats, int32_t *count, int32_t *frames, int32_t *status, double *centre,
+                                       int32_t *centre_status, void *stream);
 
 /* Row f-3: the undistortion pre-step of the CLI entry point, utils/iotool.py:22-39
  *   undistort_image(image, camera_params) = cv2.undistort(image, IntrinsicMatrix, hstack(Radial, Tangential))

@@ -1,0 +1,155 @@
+"""Time the planar target's geometric half (cpe_fit_plane_batch, cpe_index_planes_batch) at the Python layer, with the
+cylinder's Levenberg-Marquardt fit on the same point tables as the yardstick.  The tables are analytic: the 17 x 25 grid of
+the projector of cpe_amd.synth.make_rig on seeded boards (tilts +-25 deg, depth 330-400 mm), 0.25 px noise, every 20th point
+lifted 5-40 mm off the board, triangulated by fit.triangulate_batch; for the per-frame fit thinned to `--points` points.
+
+    python tools/time_plane_fit.py [--frames 45 4096] [--points 250] [--table-frames 45 1024] [--reps 11] [--procs 3]
+                                   [--child-timeout 400] [--out FILE]
+
+Per size, alternated inside one process, the time between two device events around one call:
+    plane       fit.fit_plane_batch(X, idx, cnt)                       fitplane, grid map, pose
+    plane_trim  fit.fit_plane_batch(X, idx, cnt, tau=1.0)              the same behind the trimming loop
+    lm          fit.fit_cylinder_batch(X, cnt, 45, mode=FIT_LM)        the yardstick
+and for the table sizes (all 425 points of a frame)
+    table       fit.index_planes_batch(X, idx, cnt, -12, 12)
+    lm          as above, on these tables
+The parent starts `--procs` fresh children one after the other and reports the median over the children's medians with the
+run-to-run spread (max - min of the children's medians).  A child that fails or outlives --child-timeout seconds ends the run:
+nothing more is started on the GPU after it."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+RADIUS = 45.0
+
+
+def make_tables(n, points, dev, seed=0):
+    """-> X f64[n,MAXP,3], idx i32[n,MAXP,2], cnt i32[n] on dev"""
+    import numpy as np
+    import torch
+    from cpe_amd import fit, synth
+    scene = synth.Scene(h=1200, w=1920)
+    K1, K2, T21, Tp = synth.make_rig(scene)
+    delta = scene.pitch_px / scene.focal
+    Op = -Tp[:3, :3].T @ Tp[:3, 3]
+    ii, jj = np.meshgrid(np.arange(-8, 9), np.arange(-12, 13), indexing='ij')
+    d = np.stack([ii.ravel() * delta, jj.ravel() * delta, np.ones(ii.size)], 1) @ Tp[:3, :3]
+    ids = np.stack([ii.ravel(), jj.ravel()], 1).astype(np.int32)
+    rng = np.random.default_rng(seed)
+    p1 = np.zeros((n, fit.MAXP, 2)); p2 = np.zeros_like(p1); idx = np.zeros((n, fit.MAXP, 2), np.int32); cnt = np.zeros(n, np.int32)
+    for f in range(n):
+        ax, ay = np.radians(rng.uniform(-25, 25, 2))
+        nrm = synth._rot(ax, ay, 0.0) @ np.array([0, 0, 1.0])
+        c = np.array([27.0 + rng.uniform(-10, 10), rng.uniform(-10, 10), rng.uniform(330, 400)])
+        keep = np.sort(rng.permutation(len(ids))[:points])
+        X = Op + (((c - Op) @ nrm) / (d[keep] @ nrm))[:, None] * d[keep]
+        X[::20] += (rng.uniform(5, 40, len(X[::20])) * rng.choice([-1, 1], len(X[::20])))[:, None] * nrm
+        a = X @ K1.T
+        b = (X @ T21[:3, :3].T + T21[:3, 3]) @ K2.T
+        m = len(keep)
+        p1[f, :m] = a[:, :2] / a[:, 2:] + 0.25 * rng.standard_normal((m, 2))
+        p2[f, :m] = b[:, :2] / b[:, 2:] + 0.25 * rng.standard_normal((m, 2))
+        idx[f, :m] = ids[keep]
+        cnt[f] = m
+    cnt_d = torch.from_numpy(cnt).to(dev)
+    tri = fit.triangulate_batch(torch.from_numpy(p1).to(dev), torch.from_numpy(p2).to(dev), cnt_d, K1, K2, T21)
+    return tri['pts3'], torch.from_numpy(idx).to(dev), cnt_d
+
+
+def time_variants(variants, reps):
+    import torch
+    first = {k: f() for k, f in variants.items()}                                       # warm-up, and the figures of the line
+    torch.cuda.synchronize()
+    ms = {k: [] for k in variants}
+    for _ in range(reps):
+        for k, f in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1))
+    return first, ms
+
+
+def child(sizes, points, table_sizes, reps):
+    import torch
+    import cpe_amd  # noqa: F401
+    from cpe_amd import fit
+    dev = torch.device('cuda:0')
+    for n in sizes:
+        X, idx, cnt = make_tables(n, points, dev)
+        first, ms = time_variants(dict(plane=lambda: fit.fit_plane_batch(X, idx, cnt),
+                                       plane_trim=lambda: fit.fit_plane_batch(X, idx, cnt, tau=1.0),
+                                       lm=lambda: fit.fit_cylinder_batch(X, cnt, RADIUS, mode=fit.FIT_LM)), reps)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        print(json.dumps(dict(kind='fit', frames=n, points=float(cnt.double().mean()), reps=reps, median_ms=med,
+                              plane_over_lm=med['plane'] / med['lm'], trim_over_lm=med['plane_trim'] / med['lm'],
+                              status_ok=int((first['plane']['status'] == 0).sum()), status_ok_trim=int((first['plane_trim']['status'] == 0).sum()),
+                              inliers_trim=float(first['plane_trim']['n_inliers'].double().mean()),
+                              refits_trim=float(first['plane_trim']['stats'][:, 6].mean()),
+                              rms=float(first['plane']['stats'][:, 0].mean()), rms_trim=float(first['plane_trim']['stats'][:, 0].mean()),
+                              lm_iters=float(first['lm']['iters'][:, 0].double().mean()), ms=ms)), flush=True)
+        del first, X, idx, cnt
+        torch.cuda.empty_cache()
+    for n in table_sizes:
+        X, idx, cnt = make_tables(n, 425, dev)
+        first, ms = time_variants(dict(table=lambda: fit.index_planes_batch(X, idx, cnt, -12, 12),
+                                       lm=lambda: fit.fit_cylinder_batch(X, cnt, RADIUS, mode=fit.FIT_LM)), reps)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        c = first['table']['centre'].cpu().tolist()
+        print(json.dumps(dict(kind='table', frames=n, points=425.0, reps=reps, median_ms=med, table_over_lm=med['table'] / med['lm'],
+                              lines_ok=int((first['table']['status'] == 0).sum()), centre_status=int(first['table']['centre_status']),
+                              centre=c, ms=ms)), flush=True)
+        del first, X, idx, cnt
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--frames', type=int, nargs='*', default=[45, 4096])
+    ap.add_argument('--points', type=int, default=250)
+    ap.add_argument('--table-frames', type=int, nargs='*', default=[45, 1024])
+    ap.add_argument('--reps', type=int, default=11)
+    ap.add_argument('--procs', type=int, default=3)
+    ap.add_argument('--child-timeout', type=float, default=400.0, help='seconds one child may take')
+    ap.add_argument('--out', default=None, help='also append every raw line to this file')
+    ap.add_argument('--child', action='store_true')
+    a = ap.parse_args()
+    if a.child:
+        return child(a.frames, a.points, a.table_frames, a.reps)
+    lines = []
+
+    def emit(d):
+        lines.append(d)
+        print(json.dumps(d), flush=True)
+        if a.out:
+            with open(a.out, 'a') as f:
+                f.write(json.dumps(d) + '\n')
+    for p in range(a.procs):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--points', str(a.points), '--reps', str(a.reps), '--frames'] +
+                           [str(n) for n in a.frames] + ['--table-frames'] + [str(n) for n in a.table_frames],
+                           stdout=subprocess.PIPE, text=True, check=True, timeout=a.child_timeout)
+        for ln in r.stdout.splitlines():
+            if ln.startswith('{'):
+                emit(dict(json.loads(ln), process=p))
+    for kind, sizes, keys in (('fit', a.frames, ('plane', 'plane_trim', 'lm')), ('table', a.table_frames, ('table', 'lm'))):
+        for n in sizes:
+            rows = [d for d in lines if d['kind'] == kind and d['frames'] == n]
+            med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in keys}
+            spread = {k: max(d['median_ms'][k] for d in rows) - min(d['median_ms'][k] for d in rows) for k in keys}
+            extra = {k: v for k, v in rows[0].items() if k not in ('kind', 'frames', 'points', 'reps', 'median_ms', 'ms', 'process') and
+                     not k.endswith('_over_lm')}
+            emit(dict(kind=kind + '_summary', frames=n, points=rows[0]['points'], procs=a.procs, median_ms=med, spread_ms=spread,
+                      **{f'{k}_over_lm': med[k] / med['lm'] for k in keys if k != 'lm'}, **extra))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
