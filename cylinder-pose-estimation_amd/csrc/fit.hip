@@ -2782,6 +2782,111 @@ __global__ __launch_bounds__(64) void k_planes_centre(const double *__restrict__
         o_status[0] = ok ? CPE_ST_OK : CPE_ST_FEW_POINTS;
     }
 }
+
+// 3-D points from one camera and the laser-plane table (include/cpe.h cpe_table_triangulate_batch, whose numbered rule this
+// follows).  One lane per point, rounds of 64; the accepted points keep their table order: a ballot, the popcount of the lanes
+// below, and the base of the round carried on.  The table (at most 2 x 256 planes, 18 KB with the statuses) is read where a point
+// needs it: a frame of a few hundred points touches about as many bytes as a copy into LDS would, and every frame shares it in L2.
+__global__ __launch_bounds__(64) void k_table_triangulate(const double *__restrict__ xy, const int *__restrict__ id, const int *__restrict__ cnt,
+                                                          const double *__restrict__ K, const double *__restrict__ Tc,
+                                                          const double *__restrict__ P, const int *__restrict__ line_status, int lo, int hi,
+                                                          int swap, int need_both, double min_sin2, double max_res,
+                                                          double *__restrict__ o_X, int *__restrict__ o_idx, double *__restrict__ o_res,
+                                                          int *__restrict__ o_src, int *__restrict__ o_m, int *__restrict__ o_counts,
+                                                          double *__restrict__ o_stats)
+{
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int n = min(max(cnt[f], 0), MAXP);
+    const int L = hi - lo + 1;                     // 1..CPE_MAXL, checked by the host
+    const size_t base = (size_t)f * MAXP;
+    // R (rows) and t of Tc, the identity without one: the same arithmetic either way
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+    if (Tc) {
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            R[3 * r] = Tc[4 * r]; R[3 * r + 1] = Tc[4 * r + 1]; R[3 * r + 2] = Tc[4 * r + 2];
+            t[r] = Tc[4 * r + 3];
+        }
+    }
+    const double k0 = K[0], k1 = K[1], k2 = K[2], k4 = K[4], k5 = K[5];
+    double o[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) o[a] = -((R[a] * t[0] + R[3 + a] * t[1]) + R[6 + a] * t[2]);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int m = 0, both = 0, ref_a = 0, ref_b = 0;
+    double r2 = 0, rmax = 0;
+    for (int k0p = 0; k0p < n; k0p += 64) {
+        const int k = k0p + lane;
+        bool in = k < n, acc = false, early = false;   // early: refused in steps 1 / 4 / 5, otherwise in 6 / 7
+        double X[3] = {0, 0, 0}, rs[2] = {0, 0};
+        int v[2] = {0, 0}, used = 0;
+        if (in) {
+            const double x = xy[(base + k) * 2], y = xy[(base + k) * 2 + 1];
+            v[0] = id[(base + k) * 2]; v[1] = id[(base + k) * 2 + 1];
+            const double vy = (y - k5) / k4;
+            const double vx = ((x - k2) - k1 * vy) / k0;
+            double d[3];
+#pragma unroll
+            for (int a = 0; a < 3; a++) d[a] = (R[a] * vx + R[3 + a] * vy) + R[6 + a];
+            const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+#pragma unroll
+            for (int a = 0; a < 3; a++) d[a] = d[a] / dn;
+            double pl[2][4], den = 0, sab = 0;
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                const int fam = c ^ swap;
+                if (v[c] < lo || v[c] > hi) continue;                              // (compared, not subtracted: v may be any int)
+                const int line = fam * L + (v[c] - lo);
+                if (line_status[line] != CPE_ST_OK) continue;
+#pragma unroll
+                for (int a = 0; a < 4; a++) pl[c][a] = P[(size_t)line * 4 + a];
+                const double a_k = (pl[c][0] * d[0] + pl[c][1] * d[1]) + pl[c][2] * d[2];
+                const double b_k = ((pl[c][0] * o[0] + pl[c][1] * o[1]) + pl[c][2] * o[2]) + pl[c][3];
+                den = den + a_k * a_k;
+                sab = sab + a_k * b_k;
+                used |= 1 << c;
+            }
+            early = !(isfinite(x) && isfinite(y)) || used == 0 || (need_both && used != 3) || den < min_sin2 || !isfinite(den);
+            if (!early) {
+                const double s = -sab / den;
+                acc = s > 0 && isfinite(s);
+                if (acc) {
+#pragma unroll
+                    for (int a = 0; a < 3; a++) X[a] = o[a] + s * d[a];
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        if (!(used & (1 << c))) continue;
+                        rs[c] = ((pl[c][0] * X[0] + pl[c][1] * X[1]) + pl[c][2] * X[2]) + pl[c][3];
+                        if (max_res > 0 && fabs(rs[c]) > max_res) acc = false;
+                    }
+                }
+            }
+        }
+        const unsigned long long bal = __ballot(acc);
+        ref_a += __popcll(__ballot(in && early));
+        ref_b += __popcll(__ballot(in && !early && !acc));
+        both += __popcll(__ballot(acc && used == 3));
+        if (acc) {
+            const size_t slot = base + (size_t)(m + __popcll(bal & below));       // <= base + k: inside the frame's table
+            o_X[slot * 3] = X[0]; o_X[slot * 3 + 1] = X[1]; o_X[slot * 3 + 2] = X[2];
+            o_idx[slot * 2] = v[0]; o_idx[slot * 2 + 1] = v[1];
+            o_res[slot * 2] = rs[0]; o_res[slot * 2 + 1] = rs[1];
+            o_src[slot * 2] = used; o_src[slot * 2 + 1] = k;
+            r2 = r2 + (rs[0] * rs[0] + rs[1] * rs[1]);
+            rmax = fmax(rmax, fmax(fabs(rs[0]), fabs(rs[1])));
+        }
+        m += __popcll(bal);
+    }
+    r2 = wave_sum(r2);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) rmax = fmax(rmax, __shfl_xor(rmax, off, 64));
+    if (lane == 0) {
+        o_m[f] = m;
+        o_counts[4 * f] = m; o_counts[4 * f + 1] = both; o_counts[4 * f + 2] = ref_a; o_counts[4 * f + 3] = ref_b;
+        o_stats[2 * f] = m > 0 ? sqrt(r2 / (double)(m + both)) : 0.0;
+        o_stats[2 * f + 1] = m > 0 ? rmax : 0.0;
+    }
+}
 }  // namespace
 
 extern "C" int32_t cpe_fit_plane_batch(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n,
@@ -2821,5 +2926,27 @@ extern "C" int32_t cpe_index_planes_batch(const double *X, const int32_t *idx, c
     CPE_CHECK_LAUNCH("k_index_planes");
     CPE_KLAUNCH(k_planes_centre, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double *)P, (const int *)status, L, centre, centre_status);
     CPE_CHECK_LAUNCH("k_planes_centre");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_table_triangulate_batch(const double *xy, const int32_t *id, const int32_t *cnt, int32_t n, const double *K,
+                                               const double *Tc, const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
+                                               const CpeTableTriParams *params, double *X, int32_t *idx, double *res, int32_t *src,
+                                               int32_t *m, int32_t *counts, double *stats, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_table_triangulate_batch: n < 0");
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_table_triangulate_batch: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    CpeTableTriParams p = {0, 0, 0.01, 0.0};
+    if (params) p = *params;
+    CPE_CHECK_ARG((p.swap == 0 || p.swap == 1) && (p.need_both == 0 || p.need_both == 1) && p.min_sin >= 0 && !(p.max_res != p.max_res),
+                  "cpe_table_triangulate_batch: bad CpeTableTriParams (swap, need_both 0 or 1, min_sin >= 0, max_res not NaN)");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(xy && id && cnt && K && P && line_status && X && idx && res && src && m && counts && stats,
+                  "cpe_table_triangulate_batch: null pointer");
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_table_triangulate, dim3(n), dim3(64), 0, (hipStream_t)stream, xy, id, cnt, K, Tc, P, line_status, lo, hi, p.swap,
+                p.need_both, p.min_sin * p.min_sin, p.max_res, X, idx, res, src, m, counts, stats);
+    CPE_CHECK_LAUNCH("k_table_triangulate");
     return CPE_OK;
 }

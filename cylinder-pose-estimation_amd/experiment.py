@@ -76,22 +76,23 @@ def _list_pairs(input_path):
     return names, paths
 
 
-def _run_pairs(names, paths, camera_json, dev, chunk, make_fits, make_pipeline):
+def _run_pairs(names, paths, camera_json, dev, chunk, make_fits, make_pipeline, source='stereo'):
     """the read / upload loop of run_experiment and run_plane_experiment: the pairs are read in windows of `chunk`, runs of one
     element type and channel count are uploaded together and go through FramePipeline.run_raw of make_pipeline(h, w, chunk)
-    -> records f64 [F,16], the tensors of make_fits(F) filled"""
+    -> records f64 [F,16], the tensors of make_fits(F) filled.  source 'left' / 'right': the other camera's files are not read"""
     cam_l, cam_r = iotool.load_camera_data(camera_json)
     F, chunk = len(names), max(1, int(chunk))
     pipe = pre = None
     recs = torch.empty((F, pipeline.REC), dtype=torch.float64, device=dev)
     fits = make_fits(F)
     for w0 in range(0, F, chunk):
-        imgs = [(read_raw_image(l), read_raw_image(r)) for l, r in paths[w0:w0 + chunk]]
+        imgs = [(read_raw_image(l) if source != 'right' else None, read_raw_image(r) if source != 'left' else None)
+                for l, r in paths[w0:w0 + chunk]]
         if pipe is None:
-            h, w = imgs[0][0].shape[:2]
+            h, w = next(a for a in imgs[0] if a is not None).shape[:2]
             pre = iotool.StereoPrestep(cam_l, cam_r, h, w, dev)
             pipe = make_pipeline(h, w, chunk)
-        kinds = [tuple((a.dtype, a.shape) for a in pair) for pair in imgs]
+        kinds = [tuple((a.dtype, a.shape) for a in pair if a is not None) for pair in imgs]
         for kd, s in zip(kinds, names[w0:]):
             if any(shape[:2] != (pipe.h, pipe.w) for _, shape in kd):
                 raise _lib.CpeError(f'{s}: image size differs from the first pair ({pipe.w}x{pipe.h})')
@@ -100,15 +101,15 @@ def _run_pairs(names, paths, camera_json, dev, chunk, make_fits, make_pipeline):
             i1 = i0 + 1
             while i1 < len(imgs) and kinds[i1] == kinds[i0]:
                 i1 += 1
-            left = _upload([p[0] for p in imgs[i0:i1]], dev)
-            right = _upload([p[1] for p in imgs[i0:i1]], dev)
+            left = _upload([p[0] for p in imgs[i0:i1]], dev) if source != 'right' else None
+            right = _upload([p[1] for p in imgs[i0:i1]], dev) if source != 'left' else None
             recs[w0 + i0:w0 + i1] = pipe.run_raw(left, right, pre, {k: t[w0 + i0:w0 + i1] for k, t in fits.items()})
             i0 = i1
     return recs, fits
 
 
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
-                   frame_angles=False, match_offset=None):
+                   frame_angles=False, match_offset=None, laser_table=None, source='stereo'):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
@@ -131,6 +132,12 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     flagged fit.MATCH_WEAK -- no shift gave a cylinder worth trusting -- is listed in `skipped` (every entry then has a `match`
     key: the frame's flags) and left out of the multi-frame fit; a frame flagged MATCH_SHIFTED is used.
 
+    source='left' / 'right' with laser_table= (build-defined): the frames' points come from that camera alone and the projector's
+    laser-plane table -- a fit.LaserTable, or the path of one saved by LaserTable.save / run_plane_experiment(table_path=) --
+    through FramePipeline(source=..., laser_table=...): the other camera's files are not read (they must still exist), its detect
+    status is 0 in the records, and the dict gains tri_counts i32 [F,4] and tri_stats f64 [F,2] (fit.table_triangulate_batch's
+    counts and stats).  The table's gates keep their defaults here; FramePipeline(table=...) sets them.
+
     frame_angles=True (build-defined, nothing like it in the reference): with a multi-frame result, the good frames go through
     multiframe.estimate_frame_angles_gpu with T_cam_agv, a self-check of the calibration in degrees.  The dict gains
     angles_est (F x 2, rad; NaN for a skipped or failed frame), angles_status (F; the solver's status, -1 for a frame that was
@@ -138,8 +145,11 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     names, paths = _list_pairs(input_path)
     angles = np.deg2rad(parse_img_info(names))          # exp_gridDetection.m:26-27
     dev = torch.device(device)
-    recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, lambda F: pipeline.alloc_fits(F, dev),
-                            lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=c, device=dev, match=match_offset))
+    if isinstance(laser_table, (str, os.PathLike)):
+        laser_table = fit.LaserTable.load(laser_table, dev)
+    recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, lambda F: pipeline.alloc_fits(F, dev, source=source),
+                            lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=c, device=dev, match=match_offset,
+                                                                   source=source, laser_table=laser_table), source)
     F = len(names)
     _, _, d_fit, d_l, d_r = pipeline.unpack_counters(recs[:, 15])          # device tensors: the 'gpu' mode masks with them
     st_fit, st_l, st_r = (t.cpu().tolist() for t in (d_fit, d_l, d_r))
@@ -155,6 +165,8 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
                T_cam_agv=None, fval=None)
     if match_offset is not None:
         res.update(offset=fits['offset'], match_score=fits['match_score'], match_flags=fits['match_flags'])
+    if source != 'stereo':
+        res.update(tri_counts=fits['counts'], tri_stats=fits['stats'])
     if mat_path is not None:
         api.save_mat(mat_path, fits=fits, names=names)
     if multi_frame in ('gpu', 'lm'):
@@ -204,7 +216,8 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
 PLANE_CENTRE_RMS_WARN = 1.0     # mm
 
 
-def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_rounds=4, min_spread=1e-4, device='cuda:0', chunk=32):
+def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_rounds=4, min_spread=1e-4, device='cuda:0', chunk=32,
+                         table_path=None):
     """BUILD-DEFINED (the reference stops at the planar detector): a folder of `<name>L.png` / `<name>R.png` pairs of a flat board
     in several poses -> the board's plane and pose in every frame, and the projector's laser-plane table with its centre.
 
@@ -227,6 +240,9 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
             plane_flags i32 [F], skipped (as run_experiment: frames whose left / right detect status or fit status is non-zero),
             table = the dict of fit.index_planes_batch (P, stats, count, frames, status [2,L,..], centre, centre_status, lo, hi)
             or None when no frame is good or the indices span more than CPE_MAXL values (a warning says which),
+            laser_table = that table as a fit.LaserTable with family0='row' (the planar detector writes its ids as (row, col)), what
+            FramePipeline(source='left', laser_table=...) and run_experiment(laser_table=...) read; None without a table.  It is
+            saved to table_path (.npz) when that is given.  A table that is not `consistent` is returned and saved all the same,
             consistent = the table exists, has a centre, and its planes meet there within PLANE_CENTRE_RMS_WARN)"""
     names, paths = _list_pairs(input_path)
     dev = torch.device(device)
@@ -245,7 +261,7 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
     st_fit, st_l, st_r, (lo, hi) = back[:F], back[F:2 * F], back[2 * F:3 * F], back[3 * F:]
     skipped = [dict(index=i, name=names[i], det_left=st_l[i], det_right=st_r[i], fit=st_fit[i])
                for i in range(F) if st_l[i] or st_r[i] or st_fit[i]]
-    table, consistent = None, False
+    table, consistent, laser_table = None, False, None
     if lo > hi:
         warnings.warn('no fitted frame: no laser-plane table')
     elif hi - lo + 1 > _lib.MAXL:
@@ -262,6 +278,10 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
                           'grid numbering of the two images probably disagrees, planes and table are not to be trusted')
         else:
             consistent = True
+        laser_table = fit.LaserTable.from_index_planes(table, lo, hi, 'row')
+        if table_path is not None:
+            laser_table.save(table_path)
     return dict(names=names, records=recs, P=fits['P'], T=fits['T'], grid=fits['grid'], stats=fits['stats'], pts3=fits['pts3'],
                 idx=fits['idx'], cnt=fits['m'], n_inliers=fits['n_inliers'], inlier_mask=fits['inlier_mask'],
-                plane_flags=fits['plane_flags'], skipped=skipped, table=table, consistent=consistent)
+                plane_flags=fits['plane_flags'], skipped=skipped, table=table, consistent=consistent,
+                laser_table=laser_table)

@@ -286,3 +286,109 @@ def fit_single_plane_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, select
     out = dict(sel)
     out.update(fit)
     return out
+
+
+@dataclass
+class LaserTable:
+    """BUILD-DEFINED: the laser-plane table of a calibrated projector, what index_planes_batch fits over several board poses.
+    P f64[2,L,4] (unit normal, offset; camera-1 coordinates), status i32[2,L] (ST_OK = the line has a plane), lo, hi (the grid
+    indices the L = hi - lo + 1 lines stand for), centre f64[4] (the projector's centre, rms), centre_status i32[1], and
+    family0: which grid index family 0 of the table holds, 'col' or 'row'.  The planar detector writes its ids as (row, col),
+    so a table from boards has family0 = 'row'; the cylinder's detector writes (col, row) (GridTables.id)."""
+    P: torch.Tensor
+    status: torch.Tensor
+    lo: int
+    hi: int
+    centre: torch.Tensor
+    centre_status: torch.Tensor
+    family0: str = 'col'
+
+    def __post_init__(self):
+        if self.family0 not in ('col', 'row'):
+            raise ValueError("LaserTable.family0 is 'col' or 'row'")
+        self.lo, self.hi = int(self.lo), int(self.hi)
+        nl = self.hi - self.lo + 1
+        if not 1 <= nl <= _lib.MAXL:
+            raise ValueError(f'LaserTable: {nl} indices in [{self.lo}, {self.hi}], must be 1..{_lib.MAXL}')
+        if tuple(self.P.shape) != (2, nl, 4) or tuple(self.status.shape) != (2, nl):
+            raise ValueError(f'LaserTable: P must be [2,{nl},4] and status [2,{nl}], got {list(self.P.shape)} and {list(self.status.shape)}')
+
+    @staticmethod
+    def from_index_planes(out, lo=None, hi=None, family0='col'):
+        """out: the dict of index_planes_batch (lo, hi default to the ones it holds)"""
+        return LaserTable(out['P'], out['status'], out['lo'] if lo is None else lo, out['hi'] if hi is None else hi, out['centre'],
+                          out['centre_status'], family0)
+
+    def swap_for(self, ids='col_row'):
+        """CpeTableTriParams.swap for tables whose id is (col, row) ('col_row', GridTables) or (row, col) ('row_col')"""
+        if ids not in ('col_row', 'row_col'):
+            raise ValueError("ids is 'col_row' or 'row_col'")
+        return int((self.family0 == 'col') != (ids == 'col_row'))
+
+    def to(self, device):
+        return LaserTable(self.P.to(device), self.status.to(device), self.lo, self.hi, self.centre.to(device),
+                          self.centre_status.to(device), self.family0)
+
+    def save(self, path):
+        """one .npz file (numpy appends the suffix to a path without it)"""
+        import numpy as np
+        np.savez(path, P=self.P.cpu().numpy(), status=self.status.cpu().numpy(), lo=np.int64(self.lo), hi=np.int64(self.hi),
+                 centre=self.centre.cpu().numpy(), centre_status=self.centre_status.cpu().numpy(), family0=np.array(self.family0))
+
+    @staticmethod
+    def load(path, device='cpu'):
+        import numpy as np
+        with np.load(path, allow_pickle=False) as z:
+            t = lambda k, dt: torch.from_numpy(np.ascontiguousarray(z[k])).to(dt).to(device)
+            return LaserTable(t('P', torch.float64), t('status', torch.int32), int(z['lo']), int(z['hi']), t('centre', torch.float64),
+                              t('centre_status', torch.int32), str(z['family0']))
+
+
+def table_triangulate_batch(gp: GridTables, K, Tc, table: LaserTable, need_both=False, min_sin=0.01, max_res=0.0, ids='col_row'):
+    """BUILD-DEFINED: 3-D points of one camera's grid tables from the laser-plane table, see include/cpe.h
+    cpe_table_triangulate_batch.  K: that camera's intrinsics; Tc: camera-1 coordinates -> that camera's (None = camera 1, T21
+    for camera 2).  gp.id is (col, row) as GridTables says (ids='row_col' for the planar detector's tables); which family of
+    the table either component addresses follows from table.family0.
+    -> dict(pts3 f64[n,MAXP,3], idx i32[n,MAXP,2], res f64[n,MAXP,2] (mm off either plane), src i32[n,MAXP,2] (planes used as
+            bits, source slot), m i32[n], counts i32[n,4] (m, with both planes, refused before / after the cut), stats f64[n,2]
+            (rms and max |res|)); slots from m on hold zeros"""
+    L = _lib.load()
+    dev = gp.xy.device
+    n = gp.cnt.shape[0]
+    for name, t, dt, shape in (('xy', gp.xy, torch.float64, (n, MAXP, 2)), ('id', gp.id, torch.int32, (n, MAXP, 2)),
+                               ('cnt', gp.cnt, torch.int32, (n,))):
+        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
+            raise TypeError(f'table_triangulate_batch: {name} must be {dt} {list(shape)} on {dev}, got {t.dtype} {list(t.shape)} on {t.device}')
+    K = _dev3(K, dev, (9,))
+    Tc = None if Tc is None else _dev3(Tc, dev, (16,))
+    P = table.P.to(device=dev, dtype=torch.float64).contiguous()
+    st = table.status.to(device=dev, dtype=torch.int32).contiguous()
+    f64 = torch.zeros(n * (MAXP * 5 + 2), dtype=torch.float64, device=dev)
+    X, res, stats = f64[:3 * MAXP * n].view(n, MAXP, 3), f64[3 * MAXP * n:5 * MAXP * n].view(n, MAXP, 2), f64[5 * MAXP * n:].view(n, 2)
+    i32 = torch.zeros(n * (MAXP * 4 + 5), dtype=torch.int32, device=dev)
+    idx, src = i32[:2 * MAXP * n].view(n, MAXP, 2), i32[2 * MAXP * n:4 * MAXP * n].view(n, MAXP, 2)
+    m, counts = i32[4 * MAXP * n:4 * MAXP * n + n], i32[4 * MAXP * n + n:].view(n, 4)
+    prm = _lib.CpeTableTriParams(table.swap_for(ids), int(bool(need_both)), float(min_sin), float(max_res))
+    _lib.check(L.cpe_table_triangulate_batch(gp.xy.contiguous().data_ptr(), gp.id.contiguous().data_ptr(), gp.cnt.contiguous().data_ptr(), n,
+                                             K.data_ptr(), None if Tc is None else Tc.data_ptr(), P.data_ptr(), st.data_ptr(), table.lo,
+                                             table.hi, C.addressof(prm), X.data_ptr(), idx.data_ptr(), res.data_ptr(), src.data_ptr(),
+                                             m.data_ptr(), counts.data_ptr(), stats.data_ptr(), _stream()), 'cpe_table_triangulate_batch')
+    return dict(pts3=X, idx=idx, res=res, src=src, m=m, counts=counts, stats=stats)
+
+
+def fit_single_cylinder_mono_batch(gp: GridTables, K, Tc, table: LaserTable, radius, ransac=None, mode=FIT_NELDER_MEAD, need_both=False,
+                                   min_sin=0.01, max_res=0.0, **fit_kw):
+    """BUILD-DEFINED, fit_single_cylinder_batch from one camera: table_triangulate_batch, then fit_cylinder_batch (ransac: a
+    dict of fit_cylinder_ransac_batch keywords) on its points with cnt = m.
+    -> the fit's keys (cyl_raw, cyl, T, fvals, iters, status[, n_inliers, inlier_mask]) beside pts3, idx, m, counts, res, src,
+    stats and mean_err f64[n] = stats[:, 0]: NOT a reprojection error in pixels as in the stereo call, but the rms distance in mm
+    of the points from the planes that made them (0 for points cut with one plane only)."""
+    tri = table_triangulate_batch(gp, K, Tc, table, need_both=need_both, min_sin=min_sin, max_res=max_res)
+    if ransac is not None:
+        fit = fit_cylinder_ransac_batch(tri['pts3'], tri['m'], radius, mode=mode, **ransac, **fit_kw)
+    else:
+        fit = fit_cylinder_batch(tri['pts3'], tri['m'], radius, mode=mode, **fit_kw)
+    out = dict(tri)
+    out.update(fit)
+    out['mean_err'] = tri['stats'][:, 0]
+    return out

@@ -77,6 +77,8 @@ _SIGS = {
     'cpe_fit_plane_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 10),
     'cpe_index_planes_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double] +
                                [C.c_void_p] * 8),
+    'cpe_table_triangulate_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] +
+                                    [C.c_void_p] * 9),
     'cpe_undistort_map': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_remap_bilinear_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_undistort_map_matlab': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -134,6 +136,10 @@ class CpeMatchParams(C.Structure):
 
 class CpePlaneFitParams(C.Structure):
     _fields_ = [('tau', C.c_double), ('max_rounds', C.c_int32), ('reserved', C.c_int32)]
+
+
+class CpeTableTriParams(C.Structure):
+    _fields_ = [('swap', C.c_int32), ('need_both', C.c_int32), ('min_sin', C.c_double), ('max_res', C.c_double)]
 
 
 MAXP = 2048

@@ -34,7 +34,8 @@ class FramePipeline:
     """reusable workspaces for chunks of `chunk` stereo frames of size h x w"""
 
     def __init__(self, h, w, K1, K2, T21, radius, chunk=64, device='cuda:0', selector=fit.SEL_CHOOSE_IDX, th=0.3,
-                 fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full', match=None, target='cylinder', plane=None):
+                 fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full', match=None, target='cylinder', plane=None,
+                 source='stereo', laser_table=None, table=None):
         self.h, self.w, self.chunk, self.device = h, w, chunk, torch.device(device)
         self.K1, self.K2, self.T21, self.radius = K1, K2, T21, radius
         self.selector, self.th, self.fit_mode = selector, th, fit_mode
@@ -51,6 +52,25 @@ class FramePipeline:
         self.target = target            # 'plane' (build-defined): the planar detector and fit.fit_single_plane_batch; records as beside REC
         self.plane = dict(plane or {})  # keywords of fit.fit_plane_batch: tau, max_rounds
         self.stage = stage              # 'detect': stop after chooseIdx + triangulate (fitSingleCylinder.m:12-17), no cylinder fit
+        # source 'left' / 'right' (build-defined): only that camera's images are detected, and the points come from its rays and the
+        # laser-plane table (fit.fit_single_cylinder_mono_batch) instead of the stereo pair; camera 2 uses K2 and T21
+        if source not in ('stereo', 'left', 'right'):
+            raise ValueError("source is 'stereo', 'left' or 'right'")
+        if source == 'stereo':
+            if laser_table is not None or table is not None:
+                raise ValueError("laser_table= and table= belong to one camera: source='left' or 'right'")
+        else:
+            if laser_table is None:
+                raise ValueError(f"source='{source}' needs laser_table= (a fit.LaserTable): one camera has no other way to a 3-D point")
+            if match is not None:
+                raise ValueError(f"source='{source}': match searches the index shift between two tables, there is one")
+            if target == 'plane':
+                raise ValueError(f"source='{source}': target='plane' builds the table from stereo points and does not read one")
+            if stage == 'detect':
+                raise ValueError(f"source='{source}': stage='detect' ends at the stereo selector")
+            laser_table = laser_table.to(self.device)
+        self.source, self.laser_table = source, laser_table
+        self.table = dict(table or {})  # keywords of fit.table_triangulate_batch: need_both, min_sin, max_res
         self.ws = {}
         # chunks are independent: `lanes` of them are in flight on their own HIP streams (each with its own
         # workspace), so the serial tails of one chunk (blob grouping, line fitting: one workgroup per frame)
@@ -73,7 +93,29 @@ class FramePipeline:
         return (left.dim() == 3 and left.shape == right.shape and left.stride() == (2 * h * w, w, 1) and right.stride() == left.stride()
                 and right.data_ptr() == left.data_ptr() + h * w and left.untyped_storage().data_ptr() == right.untyped_storage().data_ptr())
 
+    def _run_chunk_mono(self, frames, lane, frame0):
+        """run_chunk with source 'left' / 'right': one detect call over the c images of that camera"""
+        c = frames.shape[0]
+        det = api.detect_grid_batch(frames.contiguous(), self._ws(c, lane), target=self.target, debug_planes=False)
+        K, Tc = (self.K1, None) if self.source == 'left' else (self.K2, self.T21)
+        rk = None if self.ransac is None else dict(self.ransac, frame0=int(self.ransac.get('frame0', 0)) + frame0)
+        out = fit.fit_single_cylinder_mono_batch(fit.GridTables(det['xy'], det['id'], det['n']), K, Tc, self.laser_table, self.radius,
+                                                 ransac=rk, mode=self.fit_mode, **self.table)
+        zero = torch.zeros_like(det['status'])
+        st_l, st_r = (det['status'], zero) if self.source == 'left' else (zero, det['status'])
+        rec = torch.empty((c, REC), dtype=torch.float64, device=frames.device)
+        rec[:, 0:6] = out['cyl'][:, 0]
+        rec[:, 6:12] = out['cyl'][:, 1]
+        rec[:, 12:14] = out['fvals']
+        rec[:, 14] = out['mean_err']          # mm off the laser planes, not pixels (fit.fit_single_cylinder_mono_batch)
+        rec[:, 15] = pack_counters(out['m'], out['iters'][:, 0], out['status'], st_l, st_r)
+        return rec, det, out
+
     def run_chunk(self, left, right, lane=0, frame0=0):
+        """-> records f64 [c,16], the detect call's dict, the fit's dict.  With source 'left' / 'right' only that argument is
+        read (the other may be None) and the detect call sees c images, not 2c"""
+        if self.source != 'stereo':
+            return self._run_chunk_mono(left if self.source == 'left' else right, lane, frame0)
         c = left.shape[0]
         if c > 0 and self._interleaved(left, right):
             # the pairs already lie one after the other in memory: the detect call reads them in place (L0 R0 L1 R1 ...)
@@ -119,7 +161,10 @@ class FramePipeline:
         return rec, det, out
 
     def run(self, left, right):
-        """left/right: u8 [F,h,w] on the device -> records f64 [F,16]"""
+        """left/right: u8 [F,h,w] on the device -> records f64 [F,16] (source 'left' / 'right': the other one may be None)"""
+        if self.source != 'stereo':
+            one = left if self.source == 'left' else right
+            return self._for_chunks(one.shape[0], one.device, lambda i0, i1, lane: self._run_chunk_mono(one[i0:i1], lane, i0)[0])
         return self._for_chunks(left.shape[0], left.device, lambda i0, i1, lane: self.run_chunk(left[i0:i1], right[i0:i1], lane, i0)[0])
 
     def _for_chunks(self, F, device, body):
@@ -150,11 +195,31 @@ class FramePipeline:
         """raw camera frames [F,h,w] / [F,h,w,3] on the device (uint8, uint16, float32, float64: iotool.StereoPrestep) ->
         records f64 [F,16].  Per chunk the pre-step (preProcessing.m:3-9) writes the undistorted grey pairs into the lane's
         staging tensor [chunk,2,h,w] and the detect call reads them there in place.
-        fits: None, or tensors from alloc_fits(F, device[, target]) that receive every frame's fit outputs."""
+        fits: None, or tensors from alloc_fits(F, device[, target, source]) that receive every frame's fit outputs.
+        With source 'left' / 'right' only that camera's frames are read (the other argument may be None) and pre-processed, into
+        a staging tensor [chunk,h,w]."""
         if (prestep.h, prestep.w) != (self.h, self.w):
             raise ValueError(f'run_raw: the pre-step is for {prestep.w}x{prestep.h} frames, the pipeline for {self.w}x{self.h}')
         if fits is not None and self.stage != 'full':
             raise ValueError("run_raw: fit outputs exist only with stage='full'")
+
+        def body_mono(i0, i1, lane):
+            from . import iotool
+            cam = 0 if self.source == 'left' else 1
+            raw = (left_raw, right_raw)[cam][i0:i1]
+            prestep._check(raw, self.source)
+            st = self._stage.get(lane)
+            if st is None:
+                st = self._stage[lane] = torch.empty((self.chunk, self.h, self.w), dtype=torch.uint8, device=raw.device)
+            iotool._prestep(prestep.maps[cam], raw, st[:i1 - i0], self.h * self.w)
+            rec, _, out = self._run_chunk_mono(st[:i1 - i0], lane, i0)
+            if fits is not None:
+                for k, t in fits.items():
+                    t[i0:i1] = out[k]
+            return rec
+        if self.source != 'stereo':
+            one = left_raw if self.source == 'left' else right_raw
+            return self._for_chunks(one.shape[0], one.device, body_mono)
 
         def body(i0, i1, lane):
             st = self._stage.get(lane)
@@ -180,8 +245,14 @@ PLANE_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2)
                          status=((), torch.int32))
 
 
-def alloc_fits(F, device, target='cylinder'):
+MONO_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2), torch.int32), m=((), torch.int32),
+                        cyl_raw=((2, 6), torch.float64), cyl=((2, 6), torch.float64), T=((4, 4), torch.float64), fvals=((2,), torch.float64),
+                        mean_err=((), torch.float64), status=((), torch.int32), counts=((4,), torch.int32),
+                        res=((fit.MAXP, 2), torch.float64), src=((fit.MAXP, 2), torch.int32), stats=((2,), torch.float64))
+
+
+def alloc_fits(F, device, target='cylinder', source='stereo'):
     """zeroed [F, ...] tensors for the per-frame outputs of fit.fit_single_cylinder_batch (target='plane': of
-    fit.fit_single_plane_batch) that FramePipeline.run_raw can keep"""
-    outputs = dict(cylinder=FIT_OUTPUTS, plane=PLANE_FIT_OUTPUTS)[target]
+    fit.fit_single_plane_batch; source 'left' / 'right': of fit.fit_single_cylinder_mono_batch) that FramePipeline.run_raw can keep"""
+    outputs = dict(cylinder=FIT_OUTPUTS, plane=PLANE_FIT_OUTPUTS)[target] if source == 'stereo' else MONO_FIT_OUTPUTS
     return {k: torch.zeros((F,) + shape, dtype=dt, device=device) for k, (shape, dt) in outputs.items()}

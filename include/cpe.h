@@ -45,14 +45,15 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 117   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 118   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
                              111: cpe_debug_clahe_planes_bgr; 112: cpe_multi_frame_fit_batch, cpe_pose_vec2T_batch,
                              cpe_pose_T2vec_batch; 113: cpe_multi_frame_fit_lm_batch; 114: cpe_agv_chain_batch,
                              cpe_frame_angles_lm_batch; 115: cpe_debug_region_hull; 116: cpe_match_offset_batch,
-                             cpe_match_offset_workspace_bytes; 117: cpe_fit_plane_batch, cpe_index_planes_batch) */
+                             cpe_match_offset_workspace_bytes; 117: cpe_fit_plane_batch, cpe_index_planes_batch;
+                             118: cpe_table_triangulate_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -649,6 +650,46 @@ CPE_API int32_t cpe_index_planes_batch(const double *X, const int32_t *idx, cons
                                        const int32_t *frame_ok, int32_t lo, int32_t hi, double min_spread, double *P,
                                        double *stats, int32_t *count, int32_t *frames, int32_t *status, double *centre,
                                        int32_t *centre_status, void *stream);
+
+/* BUILD-DEFINED: 3-D points from ONE camera and the laser-plane table.  A grid point with the indices (id[0], id[1]) lies on the
+ * plane of light of either index, so it is the cut of its pixel ray with those planes: no stereo partner and no index matching.
+ * One wavefront per frame, rounds of 64 points, one launch, no atomics, no workspace, no host synchronisation.
+ *   xy f64[n,CPE_MAXP,2], id i32[n,CPE_MAXP,2], cnt i32[n]: the grid-point tables of one camera (cpe_detect_grid_batch)
+ *   K f64[9] row-major, Tc f64[16] row-major or NULL: DEVICE memory; Tc maps camera-1 coordinates (the table's) to this
+ *     camera's: NULL = identity (camera 1), T_C2_C1 for camera 2.  R, t below are its rotation and translation
+ *   P f64[2,L,4], line_status i32[2,L], lo, hi: exactly what cpe_index_planes_batch wrote; L = hi - lo + 1 in 1..CPE_MAXL
+ *     (otherwise CPE_ERR_ARG)
+ *   params NULL = the defaults of CpeTableTriParams
+ * The order is the contract; per point of the table, in table order:
+ *   1. cnt is clamped to [0, CPE_MAXP]; slots past it are never read.  A point with a non-finite pixel coordinate is refused;
+ *   2. ray in camera-1 coordinates: o = -R't; vy = (y - K[5]) / K[4]; vx = (x - K[2] - K[1] vy) / K[0]; d = R'(vx, vy, 1),
+ *      normalised;
+ *   3. component c in {0,1} of id addresses family k = c ^ swap with v = id[c]; the plane [n_k, P4_k] = P[k, v - lo] is usable
+ *      when lo <= v <= hi and line_status[k, v - lo] == CPE_ST_OK; then a_k = n_k.d and b_k = n_k.o + P4_k;
+ *   4. no usable plane, or only one with need_both: refused (counts[2]);
+ *   5. den = sum a_k^2 over the usable planes; den < min_sin^2, or den not finite: refused (counts[2]).  An error of a plane's
+ *      offset reaches the depth multiplied by 1 / sin of the angle between ray and plane: at the default 0.01 the table's
+ *      0.02 - 0.2 mm plane rms becomes 2 - 20 mm;
+ *   6. s = -sum a_k b_k / den; s <= 0 or not finite: refused (counts[3]); X = o + s d.  The point lies on the ray exactly; with
+ *      two planes it is the point of the ray with the least sum of squared distances to both;
+ *   7. res[c] = n_k.X + P4_k for a used plane, 0 for an unused one (c is the component, not the family); max_res > 0 and a used
+ *      |res[c]| > max_res: refused (counts[3]);
+ *   8. accepted points go, in table order, to slots 0..m-1 of X f64[n,CPE_MAXP,3], idx i32[n,CPE_MAXP,2] (a copy of id), res
+ *      f64[n,CPE_MAXP,2] and src i32[n,CPE_MAXP,2]: src[0] bit 0 = the plane of component 0 was used, bit 1 = component 1's;
+ *      src[1] = the point's slot in the input table.  Slots from m on are NOT written;
+ *   9. m i32[n]; counts i32[n,4] = m, points with both planes, refused in steps 1/4/5, refused in steps 6/7; stats f64[n,2] =
+ *      sqrt of the mean squared res over the used planes of the accepted points, max |res|; both 0 when m = 0.
+ * The outputs may not overlap the inputs.  n == 0 is a no-op. */
+typedef struct CpeTableTriParams {
+    int32_t swap;       /* 0: id component c addresses table family c; 1: component c addresses family 1 - c */
+    int32_t need_both;  /* 1: a point needs both of its planes; 0 (default): one usable plane is enough */
+    double  min_sin;    /* a point whose usable planes give sum a_k^2 < min_sin^2 is refused; >= 0, default 0.01 */
+    double  max_res;    /* > 0: refuse a point with |res| > max_res on any used plane; <= 0 (default): no gate */
+} CpeTableTriParams;
+CPE_API int32_t cpe_table_triangulate_batch(const double *xy, const int32_t *id, const int32_t *cnt, int32_t n, const double *K,
+                                            const double *Tc, const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
+                                            const CpeTableTriParams *params, double *X, int32_t *idx, double *res, int32_t *src,
+                                            int32_t *m, int32_t *counts, double *stats, void *stream);
 
 /* Row f-3: the undistortion pre-step of the CLI entry point, utils/iotool.py:22-39
  *   undistort_image(image, camera_params) = cv2.undistort(image, IntrinsicMatrix, hstack(Radial, Tangential))
