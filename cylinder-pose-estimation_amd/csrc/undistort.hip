@@ -294,15 +294,20 @@ extern "C" int32_t cpe_undistort_map(const double *K, const double *dist, int32_
     CamArgs cam;
     for (int i = 0; i < 9; i++) cam.K[i] = K[i];
     for (int i = 0; i < 12; i++) cam.c[i] = i < n_dist ? dist[i] : 0.0;
-    {
-        // every stripe inverts K with its own principal point; all of them are singular or none
-        const double *S = cam.K;
-        const double det = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
-        CPE_CHECK_ARG(det != 0.0 && S[0] * S[4] != 0.0, "cpe_undistort_map: singular camera matrix");
-    }
     int stripe0 = (1 << 12) / (w > 1 ? w : 1);
     if (stripe0 < 1) stripe0 = 1;
     if (stripe0 > h) stripe0 = h;
+    {
+        // every stripe inverts K with its own principal point (k_undistort_map's `d`); with a bottom row other than 0 0 1
+        // the determinant depends on the stripe, and one singular stripe refuses the camera (as orc_undistort_map does)
+        const double *S = cam.K;
+        CPE_CHECK_ARG(S[0] * S[4] != 0.0, "cpe_undistort_map: singular camera matrix");
+        for (int y0 = 0; y0 < h; y0 += stripe0) {
+            const double a5 = S[5] - y0;
+            const double det = S[0] * (S[4] * S[8] - a5 * S[7]) - S[1] * (S[3] * S[8] - a5 * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
+            CPE_CHECK_ARG(det != 0.0, "cpe_undistort_map: singular camera matrix (stripe at row %d)", y0);
+        }
+    }
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_undistort_map, dim3((h + 63) / 64), dim3(64), 0, (hipStream_t)stream, cam, h, w, stripe0, map_xy, map_f);
     CPE_CHECK_LAUNCH("k_undistort_map");
