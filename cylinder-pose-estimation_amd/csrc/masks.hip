@@ -13,313 +13,302 @@ namespace cpe {
 
 namespace {
 
+// ---- bit rows, marched: k_open20_joints and k_roi_base --------------------------------------------------------------------
+// Both kernels cut the frame into column strips of BR_SPAN pixels and bands of rows; one wave (a workgroup of 64 threads)
+// owns one strip of one band and marches down its rows.  A lane owns 16 pixels of the row: one 16-byte load packs them into
+// 16 bits, one 16-byte store writes them back as bytes, and a wave's loads and stores of a row are one contiguous run.  What
+// a stage needs of the neighbouring pixels along the row comes from the adjacent lanes' input bits by shuffles, once per row:
+// the lane then carries its 16 pixels with a halo in one register and every stage is plain bit arithmetic on it.  The first
+// and last BR_HALO lanes of a wave only feed their neighbours.  What a stage needs of other rows stays in registers (or,
+// for the 18-row delay of the horizontal opening, in a lane-private LDS ring).  No barrier orders anything between waves.
+// The one-bit planes leave through an LDS image of a tile row (15 tiles of 64 bytes per plane): every lane writes its 16
+// bits of a row, and after 8 rows the wave stores the tiles whole, 16 bytes per lane.
+constexpr int BR_HALO = 2, BR_OUT = 64 - 2 * BR_HALO, BR_SPAN = BR_OUT * 16, BR_WORDS = BR_OUT / 4;
+constexpr int BR_TILE = BR_WORDS * 32;      // u16 per plane of the tile-row image
+inline int br_strips(int w) { return (w + BR_SPAN - 1) / BR_SPAN; }
+
+__device__ __forceinline__ unsigned span32(int a, int b)      // bits a .. b - 1, clipped to the register
+{
+    a = max(a, 0); b = min(b, 32);
+    if (a >= b) return 0u;
+    return (b == 32 ? ~0u : (1u << b) - 1u) & ~((1u << a) - 1u);
+}
+__device__ __forceinline__ unsigned long long span64(int a, int b)
+{
+    a = max(a, 0); b = min(b, 64);
+    if (a >= b) return 0ull;
+    return (b == 64 ? ~0ull : (1ull << b) - 1ull) & ~((1ull << a) - 1ull);
+}
+__device__ __forceinline__ unsigned nz4(unsigned v)           // byte i != 0 -> bit i
+{
+    v = (((v & 0x7f7f7f7fu) + 0x7f7f7f7fu) | v) & 0x80808080u;
+    return ((v >> 7) * 0x10204080u) >> 28;
+}
+__device__ __forceinline__ unsigned nz16(const uint4 &v) { return nz4(v.x) | (nz4(v.y) << 4) | (nz4(v.z) << 8) | (nz4(v.w) << 12); }
+__device__ __forceinline__ unsigned bytes4(unsigned bits)     // bit i -> byte i = 0 / 255
+{
+    return (((bits & 15u) * 0x00204081u) & 0x01010101u) * 255u;
+}
+// 16 pixels of a row; al: the row's bytes are 16-byte aligned and whole, otherwise nv (1 .. 16) of them are in the image
+__device__ __forceinline__ uint4 load_px16(const uint8_t *p, bool al, int nv)
+{
+    if (al) return *reinterpret_cast<const uint4 *>(p);
+    unsigned v0 = 0, v1 = 0, v2 = 0, v3 = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        if (b < nv) v0 |= (unsigned)p[b] << (8 * b);
+        if (b + 4 < nv) v1 |= (unsigned)p[b + 4] << (8 * b);
+        if (b + 8 < nv) v2 |= (unsigned)p[b + 8] << (8 * b);
+        if (b + 12 < nv) v3 |= (unsigned)p[b + 12] << (8 * b);
+    }
+    return make_uint4(v0, v1, v2, v3);
+}
+__device__ __forceinline__ void store_px16(uint8_t *p, unsigned bits, bool al, int nv)
+{
+    if (al) {
+        *reinterpret_cast<uint4 *>(p) = make_uint4(bytes4(bits), bytes4(bits >> 4), bytes4(bits >> 8), bytes4(bits >> 12));
+        return;
+    }
+#pragma unroll
+    for (int b = 0; b < 16; b++)
+        if (b < nv) p[b] = ((bits >> b) & 1u) ? 255 : 0;
+}
+// a lane's 16 bits of row y into the tile-row image (lanes BR_HALO .. 63 - BR_HALO)
+__device__ __forceinline__ void tile_put(unsigned short *tile, int l, int y, unsigned bits)
+{
+    const int k = l - BR_HALO;
+    if (k >= 0 && k < BR_OUT) tile[(k >> 2) * 32 + (y & 7) * 4 + (k & 3)] = (unsigned short)bits;
+}
+// tile row ty of a plane from its image: whole tiles, and the zero tile columns where this strip touches them
+__device__ __forceinline__ void tile_flush(const unsigned short *tile, unsigned long long *plane, int w, int ty, int s, bool last, int l)
+{
+    const int tc = bit_tile_cols(w);
+    unsigned long long *row = plane + (size_t)ty * tc * 8;
+    if (l < BR_OUT) {
+        const int j = s * BR_WORDS + (l >> 2);
+        if (j + 2 < tc) *reinterpret_cast<uint4 *>(row + (size_t)(j + 1) * 8 + (l & 3) * 2) = *reinterpret_cast<const uint4 *>(tile + l * 8);
+    } else {
+        const uint4 z = make_uint4(0, 0, 0, 0);
+        if (s == 0) *reinterpret_cast<uint4 *>(row + (l & 3) * 2) = z;
+        if (last) *reinterpret_cast<uint4 *>(row + (size_t)(tc - 1) * 8 + (l & 3) * 2) = z;
+    }
+}
+
 // a-2 in one kernel: binary -> open(20x1) -> hmask, open(1x20) -> vmask, joints = hmask & vmask.
 // Erosion and dilation both take the in-image pixels of the window [p-10, p+9] (anchor 10 of a 20-tap line; the border
-// never erodes and never dilates).  The kernel works on one-bit rows: a workgroup packs a band of R + 40 rows (all
-// columns) into 64-pixel words in LDS, with pixels outside the image set.  A horizontal opening is shifts of a
-// 192-bit window (word and both neighbours) with the window doubled 1 -> 2 -> 4 -> 8 -> 16 (+4) taps; the vertical one is
-// the same doubling across rows, word by word, ping-ponged between two LDS buffers.  ~2 bit operations per pixel instead
-// of 80 byte reads; the masks leave as bytes, 8 pixels per store.
+// never erodes and never dilates).
+// Horizontal: the lane's window is 64 bits, its 16 pixels with 24 on either side (two lanes' worth); the 20 taps are the
+// doubling 1 -> 2 -> 4 -> 8 -> 16 (+4) of shifted copies.  Its result waits 18 rows in the ring for the vertical one.
+// Vertical: per column a counter in five bit slices.  The erosion counts the ones that end at the row just read (up to 20:
+// row y - 9 is eroded to one where the count is 20); the dilation counts the rows since the erosion's last one (row y - 18
+// is one where fewer than 20).  Rows outside the image read as ones and erode to zeros.  A band starts 20 rows early with
+// both counters empty, which is exact from its first output row on.
 // Where the consumers read words (hb / vb given: line_masks_as_bits) hmask and vmask leave as one-bit planes as well, the
 // joints mask only as one (jbits): its bytes have no reader there, and the bytes of hmask / vmask are a debug output that the
 // caller may decline (hm, vm null).
-struct W3 { unsigned long long a, b, c; };   // pixels [-64, -1], [0, 63], [64, 127] relative to the word; bit i = pixel i
-template <int K> __device__ __forceinline__ W3 w3_up(const W3 &v, unsigned long long fill)     // r[p] = v[p + K]
+constexpr int OB_R = 80, OB_RING = 24, OB_LAG = 18;
+template <bool IS_AND> __device__ __forceinline__ unsigned long long window20(unsigned long long v)
 {
-    W3 r;
-    r.a = (v.a >> K) | (v.b << (64 - K));
-    r.b = (v.b >> K) | (v.c << (64 - K));
-    r.c = (v.c >> K) | (fill << (64 - K));
-    return r;
-}
-template <int K> __device__ __forceinline__ W3 w3_down(const W3 &v, unsigned long long fill)   // r[p] = v[p - K]
-{
-    W3 r;
-    r.c = (v.c << K) | (v.b >> (64 - K));
-    r.b = (v.b << K) | (v.a >> (64 - K));
-    r.a = (v.a << K) | (fill >> (64 - K));
-    return r;
-}
-__device__ __forceinline__ W3 w3_and(const W3 &x, const W3 &y) { return W3{x.a & y.a, x.b & y.b, x.c & y.c}; }
-__device__ __forceinline__ W3 w3_or(const W3 &x, const W3 &y) { return W3{x.a | y.a, x.b | y.b, x.c | y.c}; }
-// r[p] = AND (IS_AND) / OR of v[p - 10 .. p + 9]; exact for p in [-54, 118]
-template <bool IS_AND> __device__ __forceinline__ W3 w3_window20(const W3 &v)
-{
+    // r[p] = AND / OR of v[p - 10 .. p + 9]; exact for p in [10, 54]
     const unsigned long long f = IS_AND ? ~0ull : 0ull;
-    auto op = [](const W3 &x, const W3 &y) { return IS_AND ? w3_and(x, y) : w3_or(x, y); };
-    const W3 t1 = op(v, w3_up<1>(v, f));
-    const W3 t2 = op(t1, w3_up<2>(t1, f));
-    const W3 t4 = op(t2, w3_up<4>(t2, f));
-    const W3 t8 = op(t4, w3_up<8>(t4, f));
-    const W3 t20 = op(t8, w3_up<12>(t4, f));     // taps 0..15 and 12..19
-    return w3_down<10>(t20, f);
+    auto up = [&](unsigned long long x, int k) { return (x >> k) | (f << (64 - k)); };
+    auto op = [](unsigned long long x, unsigned long long y) { return IS_AND ? (x & y) : (x | y); };
+    const unsigned long long t1 = op(v, up(v, 1));
+    const unsigned long long t2 = op(t1, up(t1, 2));
+    const unsigned long long t4 = op(t2, up(t2, 4));
+    const unsigned long long t8 = op(t4, up(t4, 8));
+    const unsigned long long t20 = op(t8, up(t4, 12));     // taps 0..15 and 12..19
+    return (t20 << 10) | (f >> 54);
 }
-__device__ __forceinline__ unsigned long long row_valid_word(int j, int w)   // in-image pixels of word j of a row
+// five bit slices of a per-column counter that stops at 20
+struct Count20 {
+    unsigned b0, b1, b2, b3, b4;
+    __device__ __forceinline__ unsigned full() const { return b4 & (b3 | b2); }      // columns whose count is 20
+    // columns of `keep` count one more (up to 20), all others start again at 0
+    __device__ __forceinline__ void step(unsigned keep)
+    {
+        unsigned c = keep & ~full(), t;
+        t = b0 & c; b0 ^= c; c = t;
+        t = b1 & c; b1 ^= c; c = t;
+        t = b2 & c; b2 ^= c; c = t;
+        t = b3 & c; b3 ^= c; c = t;
+        b4 ^= c;
+        b0 &= keep; b1 &= keep; b2 &= keep; b3 &= keep; b4 &= keep;
+    }
+};
+__global__ __launch_bounds__(64) void k_open20_joints(const uint8_t *__restrict__ bin, int h, int w,
+                                                      uint8_t *__restrict__ hm, uint8_t *__restrict__ vm,
+                                                      uint8_t *__restrict__ jm, uint32_t *__restrict__ jbits,
+                                                      unsigned long long *__restrict__ hb, unsigned long long *__restrict__ vb)
 {
-    const int x0 = j * 64;
-    if (j < 0 || x0 >= w) return 0ull;
-    return (x0 + 64 <= w) ? ~0ull : ((1ull << (w - x0)) - 1ull);
-}
-__device__ __forceinline__ unsigned long long bytes_of_bits8(unsigned bits)   // bit i -> byte i = 0 / 255
-{
-    unsigned long long v = ((unsigned long long)(bits & 255u) * 0x0101010101010101ull) & 0x8040201008040201ull;
-    v = ((v + 0x7f7f7f7f7f7f7f7full) & 0x8080808080808080ull) >> 7;
-    return v * 255ull;
-}
-
-constexpr int OB_AP = 20;
-template <int R>
-__global__ __launch_bounds__(256) void k_open20_joints(const uint8_t *__restrict__ bin, int h, int w, int bands,
-                                                       uint8_t *__restrict__ hm, uint8_t *__restrict__ vm,
-                                                       uint8_t *__restrict__ jm, uint32_t *__restrict__ jbits,
-                                                       unsigned long long *__restrict__ hb, unsigned long long *__restrict__ vb)
-{
-    // jbits: the joints mask once more as a one-bit plane (the words are in LDS anyway): its labelling, its RETR_EXTERNAL
-    // flood and the border tracer of the joint centroids read an eighth of the bytes
-    constexpr int ROWS = R + 2 * OB_AP;
-    extern __shared__ unsigned long long s_ob[];
-    const int WW = (w + 63) >> 6;
-    unsigned long long *buf0 = s_ob, *buf1 = s_ob + (size_t)ROWS * WW, *hbuf = s_ob + (size_t)2 * ROWS * WW;
-    const int t = threadIdx.x;
-    const int f = blockIdx.x / bands, band = blockIdx.x - f * bands;
-    const int y0 = band * R;
+    // jbits: the joints mask once more as a one-bit plane: its labelling, its RETR_EXTERNAL flood and the border tracer of
+    // the joint centroids read an eighth of the bytes
+    __shared__ unsigned short s_ring[OB_RING * 64];
+    __shared__ __attribute__((aligned(16))) unsigned short s_tile[3 * BR_TILE];
+    const int l = threadIdx.x, s = blockIdx.x, yb = blockIdx.y * OB_R, f = blockIdx.z;
+    const bool last = s == (int)gridDim.x - 1;
+    const int x0 = (s * BR_OUT + l - BR_HALO) * 16;       // the lane's first pixel
+    const bool inx = x0 >= 0 && x0 < w;
+    const bool out = inx && l >= BR_HALO && l < 64 - BR_HALO;
+    const int nv = min(16, w - x0);
+    const unsigned ov = span32(0, nv);                                   // the lane's pixels inside the image
+    const unsigned long long vw = span64(24 - x0, w - x0 + 24);          // the same of its window: bit i = pixel x0 - 24 + i
     const size_t N = (size_t)h * w;
-    const uint8_t *im = bin + f * N;
-    const bool al8 = ((w & 7) == 0) && (((size_t)im & 7) == 0);
-    // pack: LDS byte k of row r = pixels [8k, 8k + 8) of row y0 - 20 + r; outside the image: ones
-    {
-        uint8_t *pk = reinterpret_cast<uint8_t *>(buf0);
-        const int per_row = WW * 8;
-        for (int i = t; i < ROWS * per_row; i += 256) {
-            const int r = i / per_row, k = i - r * per_row;
-            const int y = y0 - OB_AP + r, x0 = k * 8;
-            unsigned bits = 255u;
-            if (y >= 0 && y < h && x0 < w) {
-                const uint8_t *q = im + (size_t)y * w + x0;
-                if (al8) {    // w % 8 == 0: the 8 pixels are all inside
-                    unsigned long long v = *reinterpret_cast<const unsigned long long *>(q);
-                    v = (((v & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | v) & 0x8080808080808080ull;   // non-zero bytes
-                    bits = (unsigned)(((v >> 7) * 0x0102040810204080ull) >> 56);
-                } else {
-                    bits = 0;
-                    for (int b = 0; b < 8; b++) bits |= ((x0 + b >= w) || q[b]) ? (1u << b) : 0u;
-                }
+    const bool al = ((w & 15) == 0) && ((((size_t)bin | (size_t)hm | (size_t)vm | (size_t)jm) & 15) == 0);
+    const uint8_t *src = bin + f * N + x0;
+    unsigned long long *pj = bit_plane(jbits, f, h, w);
+    const size_t pw = bit_plane_words(h, w);
+    const int y_end = min(yb + OB_R, (h + 7) & ~7);        // output rows yb .. y_end - 1 (whole tile rows)
+    Count20 ce{0u, 0u, 0u, 0u, 0u};                        // ones that end at the row read last
+    Count20 cd{0u, 0u, 0xffffu, 0u, 0xffffu};              // rows since the erosion's last one: 20, none in reach
+    int wslot = 0, rslot = 0;
+    for (int y = yb - 20; y < y_end + OB_LAG; y++) {
+        const bool iny = y >= 0 && y < h;
+        unsigned xb = 0u;
+        if (iny && inx) xb = nz16(load_px16(src + (size_t)y * w, al, nv));
+        if (y >= yb && y < y_end) {       // horizontal opening of the band's own rows
+            const unsigned p = xb | (__shfl_down(xb, 1) << 16);
+            const unsigned q = __shfl_up(p, 2), r = __shfl_down(p, 2);
+            unsigned long long win = (unsigned long long)((q & 0xffffu) >> 8) | ((unsigned long long)(q >> 16) << 8) |
+                                     ((unsigned long long)xb << 24) | ((unsigned long long)(p >> 16) << 40) |
+                                     ((unsigned long long)(r & 0xffu) << 56);
+            const unsigned long long e = window20<true>(win | ~vw) & vw;
+            const unsigned hres = iny ? (unsigned)((window20<false>(e) & vw) >> 24) & 0xffffu : 0u;
+            s_ring[wslot * 64 + l] = (unsigned short)hres;
+            wslot = wslot + 1 == OB_RING ? 0 : wslot + 1;
+        }
+        // vertical: erosion at row y - 9, dilation at row y - 18
+        ce.step(iny ? xb : 0xffffu);
+        const int ye = y - 9;
+        const unsigned er = (ye >= 0 && ye < h) ? ce.full() : 0u;
+        cd.step(~er & 0xffffu);
+        const int yo = y - OB_LAG;
+        if (yo < yb) continue;
+        unsigned hbits = 0u, vbits = 0u;
+        if (yo < h) {
+            hbits = s_ring[rslot * 64 + l];
+            vbits = ~cd.full() & ov;
+        }
+        rslot = rslot + 1 == OB_RING ? 0 : rslot + 1;
+        if (out && yo < h && hm) {
+            const size_t o = f * N + (size_t)yo * w + x0;
+            store_px16(hm + o, hbits, al, nv);
+            store_px16(vm + o, vbits, al, nv);
+            if (jm) store_px16(jm + o, hbits & vbits, al, nv);
+        }
+        tile_put(s_tile, l, yo, hbits & vbits);
+        if (hb) { tile_put(s_tile + BR_TILE, l, yo, hbits); tile_put(s_tile + 2 * BR_TILE, l, yo, vbits); }
+        if ((yo & 7) == 7) {
+            __syncthreads();
+            tile_flush(s_tile, pj, w, yo >> 3, s, last, l);
+            if (hb) {
+                tile_flush(s_tile + BR_TILE, hb + f * pw, w, yo >> 3, s, last, l);
+                tile_flush(s_tile + 2 * BR_TILE, vb + f * pw, w, yo >> 3, s, last, l);
             }
-            pk[i] = (uint8_t)bits;
-        }
-    }
-    __syncthreads();
-    // horizontal opening of the R output rows
-    for (int i = t; i < R * WW; i += 256) {
-        const int tr = i / WW, j = i - tr * WW;
-        const unsigned long long *row = buf0 + (size_t)(tr + OB_AP) * WW;
-        const W3 x{j > 0 ? row[j - 1] : ~0ull, row[j], j + 1 < WW ? row[j + 1] : ~0ull};
-        const W3 v{row_valid_word(j - 1, w), row_valid_word(j, w), row_valid_word(j + 1, w)};
-        const W3 e = w3_and(w3_window20<true>(x), v);
-        hbuf[i] = w3_window20<false>(e).b & v.b;
-    }
-    __syncthreads();
-    // vertical opening: r indexes rows of the band; a missing row is the neutral element of the chain
-    auto pass = [&](const unsigned long long *src, unsigned long long *dst, int step, bool is_and, const unsigned long long *src2) {
-        // dst[r] = src[r] (op) src2[r + step]
-        const unsigned long long fill = is_and ? ~0ull : 0ull;
-        for (int i = t; i < ROWS * WW; i += 256) {
-            const int r = i / WW;
-            const unsigned long long p = src[i];
-            const unsigned long long q = (r + step < ROWS) ? src2[i + (size_t)step * WW] : fill;
-            dst[i] = is_and ? (p & q) : (p | q);
-        }
-        __syncthreads();
-    };
-    pass(buf0, buf1, 1, true, buf0);     // 2 taps
-    pass(buf1, buf0, 2, true, buf1);     // 4
-    pass(buf0, buf1, 4, true, buf0);     // 8   (buf1)
-    pass(buf1, buf0, 8, true, buf1);     // 16  (buf0)
-    // E[r] = AND of rows r .. r+19 = erosion at row y0 - 10 + r; rows outside the image: 0
-    for (int i = t; i < ROWS * WW; i += 256) {
-        const int r = i / WW;
-        const unsigned long long q = (r + 12 < ROWS) ? buf1[i + (size_t)12 * WW] : ~0ull;
-        const int y = y0 - 10 + r;
-        buf0[i] = (y >= 0 && y < h) ? (buf0[i] & q) : 0ull;
-    }
-    __syncthreads();
-    pass(buf0, buf1, 1, false, buf0);
-    pass(buf1, buf0, 2, false, buf1);
-    pass(buf0, buf1, 4, false, buf0);    // 8   (buf1)
-    pass(buf1, buf0, 8, false, buf1);    // 16  (buf0)
-    // D[r] = OR of E[r .. r+19] = dilation at row y0 + r: only rows r < R are read below, each by one thread
-    // outputs: 8 pixels per step
-    {
-        const int per_row = WW * 8;
-        for (int i = t; hm && i < R * per_row; i += 256) {
-            const int tr = i / per_row, k = i - tr * per_row;
-            const int y = y0 + tr, x0 = k * 8;
-            if (y >= h || x0 >= w) continue;
-            const int j = k >> 3, sh = (k & 7) * 8;
-            const size_t wi = (size_t)tr * WW + j;
-            const unsigned long long d16 = buf0[wi] | ((tr + 12 < ROWS) ? buf1[wi + (size_t)12 * WW] : 0ull);
-            const unsigned hb = (unsigned)(hbuf[wi] >> sh) & 255u;
-            const unsigned vb = (unsigned)(d16 >> sh) & 255u;
-            const size_t o = f * N + (size_t)y * w + x0;
-            if (al8 && (((size_t)hm | (size_t)vm | (size_t)jm) & 7) == 0) {
-                *reinterpret_cast<unsigned long long *>(hm + o) = bytes_of_bits8(hb);
-                *reinterpret_cast<unsigned long long *>(vm + o) = bytes_of_bits8(vb);
-                if (jm) *reinterpret_cast<unsigned long long *>(jm + o) = bytes_of_bits8(hb & vb);
-            } else {
-                for (int b = 0; b < 8 && x0 + b < w; b++) {
-                    hm[o + b] = ((hb >> b) & 1u) ? 255 : 0;
-                    vm[o + b] = ((vb >> b) & 1u) ? 255 : 0;
-                    if (jm) jm[o + b] = (((hb & vb) >> b) & 1u) ? 255 : 0;
-                }
-            }
-        }
-        // hsel / vsel: which of the two masks go into the word
-        auto plane_word = [&](int tr, int j, bool hsel, bool vsel) {
-            const size_t wi = (size_t)tr * WW + j;
-            unsigned long long m = ~0ull;
-            if (hsel) m &= hbuf[wi];
-            if (vsel) m &= buf0[wi] | ((tr + 12 < ROWS) ? buf1[wi + (size_t)12 * WW] : 0ull);
-            if (64 * j + 64 > w) m &= (1ull << (w - 64 * j)) - 1ull;      // columns past the end of the row
-            return m;
-        };
-        store_plane_band(bit_plane(jbits, f, h, w), h, w, y0, R, t, [&](int tr, int j) { return plane_word(tr, j, true, true); });
-        if (hb) {
-            const size_t pw = bit_plane_words(h, w);
-            store_plane_band(hb + f * pw, h, w, y0, R, t, [&](int tr, int j) { return plane_word(tr, j, true, false); });
-            store_plane_band(vb + f * pw, h, w, y0, R, t, [&](int tr, int j) { return plane_word(tr, j, false, true); });
+            __syncthreads();
         }
     }
 }
 
 // a-5 tail + a-6 head in one kernel:  roi = open3x3(mask & circle_mask & mask_contour)  (util_cylinder.py:1995-2005),
-// base = close3x3(roi) (:150-152); out-of-image pixels never erode / dilate.  Bit rows like k_open20_joints: a workgroup
-// holds a band of RB_R + 8 rows (all columns) as 64-pixel words in LDS and runs the four 3x3 passes on words (3 taps
-// along the row by shifts, 3 rows by AND / OR).  mask_contour is zero outside the region rectangle, so only its pixels
-// are read: everything else packs as zero, and bands further than 4 rows from it are written as zeros straight away.
+// base = close3x3(roi) (:150-152); out-of-image pixels never erode / dilate.  The lane's window is its 16 pixels with 4 on
+// either side; the four 3x3 passes (erode, dilate, dilate, erode) each keep the row-wise result of their last two rows, so
+// row y - 4 of base leaves when row y has been read.  mask_contour is zero outside the region rectangle, so only its pixels
+// are read: everything else packs as zero, and a wave whose strip and band lie further than 4 pixels from it only stores
+// its zeros.
 // The line mask m comes as bytes, or (mb given: line_masks_as_bits) as the one-bit planes k_open20_joints wrote, one per
 // frame; roi's bytes are a debug output (null: not written).
 // The kernel also seeds the expanded mask: exp = base & mask_contour (the closing is extensive, base may stick out of
 // mask_contour), full frame, zeros included -- k_seg_expand only adds 255s to it, and nothing else clears the plane.
-constexpr int RB_R = 64, RB_AP = 4, RB_ROWS = RB_R + 2 * RB_AP;
-__global__ __launch_bounds__(256) void k_roi_base(const uint8_t *__restrict__ m, const uint8_t *__restrict__ cm,
-                                                  const uint8_t *__restrict__ mc, int h, int w, int bands,
-                                                  const FrameState *__restrict__ st, uint8_t *__restrict__ roi,
-                                                  uint8_t *__restrict__ base, uint8_t *__restrict__ exp,
-                                                  uint32_t *__restrict__ bbits, const unsigned long long *__restrict__ mb)
+constexpr int RB_R = 40, RB_AP = 4;
+__global__ __launch_bounds__(64) void k_roi_base(const uint8_t *__restrict__ m, const uint8_t *__restrict__ cm,
+                                                 const uint8_t *__restrict__ mc, int h, int w,
+                                                 const FrameState *__restrict__ st, uint8_t *__restrict__ roi,
+                                                 uint8_t *__restrict__ base, uint8_t *__restrict__ exp,
+                                                 uint32_t *__restrict__ bbits, const unsigned long long *__restrict__ mb)
 {
     // bbits: `base` as a one-bit plane (cpe_dev.h tiled layout, one plane per frame): the fragments' flood, border tracer
     // and expansion read the plane, and so does their labelling where rows allow the word-level kernels.
     // base (may be null): the same as bytes, for the byte-level labelling kernels only (masks_stage asks ccl.hip)
-    extern __shared__ unsigned long long s_rb[];
-    const int WW = (w + 63) >> 6;
-    unsigned long long *buf0 = s_rb, *buf1 = s_rb + (size_t)RB_ROWS * WW, *mcb = s_rb + (size_t)2 * RB_ROWS * WW;
-    const int t = threadIdx.x;
-    const int f = blockIdx.x / bands, band = blockIdx.x - f * bands;
-    const int y0 = band * RB_R;
+    __shared__ __attribute__((aligned(16))) unsigned short s_tile[BR_TILE];
+    const int l = threadIdx.x, s = blockIdx.x, yb = blockIdx.y * RB_R, f = blockIdx.z;
+    const bool last = s == (int)gridDim.x - 1;
+    const int c = s * BR_OUT + l - BR_HALO, x0 = c * 16;
+    const bool inx = x0 >= 0 && x0 < w;
+    const bool out = inx && l >= BR_HALO && l < 64 - BR_HALO;
+    const int nv = min(16, w - x0);
+    const unsigned vw = span32(4 - x0, min(24, w - x0 + 4));      // in-image pixels of the window: bit i = pixel x0 - 4 + i
     const size_t N = (size_t)h * w;
     const int *rc = st[f].rect;
     const int rx0 = rc[0], ry0 = rc[1], rx1 = rc[0] + rc[2] - 1, ry1 = rc[1] + rc[3] - 1;
-    const bool al8 = ((w & 7) == 0) && ((((size_t)m | (size_t)cm | (size_t)mc | (size_t)roi | (size_t)base | (size_t)exp) & 7) == 0);
-    const int per_row = WW * 8;
-    auto store8 = [&](uint8_t *dst, size_t o, int x0, unsigned bits) {
-        if (al8) *reinterpret_cast<unsigned long long *>(dst + o) = bytes_of_bits8(bits);
-        else for (int b = 0; b < 8 && x0 + b < w; b++) dst[o + b] = ((bits >> b) & 1u) ? 255 : 0;
-    };
-    if (st[f].status == CPE_ST_NO_REGION || y0 > ry1 + RB_AP || y0 + RB_R - 1 < ry0 - RB_AP) {
-        for (int i = t; i < RB_R * per_row; i += 256) {
-            const int tr = i / per_row, k = i - tr * per_row;
-            const int y = y0 + tr, x0 = k * 8;
-            if (y >= h || x0 >= w) continue;
-            const size_t o = f * N + (size_t)y * w + x0;
-            if (roi) store8(roi, o, x0, 0u);
-            store8(exp, o, x0, 0u);
-            if (base) store8(base, o, x0, 0u);
-        }
-        store_plane_band(bit_plane(bbits, f, h, w), h, w, y0, RB_R, t, [](int, int) { return 0ull; });
-        return;
-    }
-    // pack (m & cm & mc) != 0 of the rectangle's pixels, and mc != 0 on its own for the seed of exp; everything else (and
-    // outside the image) is zero
-    {
-        uint8_t *pk = reinterpret_cast<uint8_t *>(buf0), *pkc = reinterpret_cast<uint8_t *>(mcb);
-        auto nonzero8 = [](unsigned long long v) {
-            v = (((v & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | v) & 0x8080808080808080ull;
-            return (unsigned)(((v >> 7) * 0x0102040810204080ull) >> 56);
-        };
-        const unsigned long long *mbf = mb ? mb + f * bit_plane_words(h, w) : nullptr;
-        const int btc = bit_tile_cols(w);
-        for (int i = t; i < RB_ROWS * per_row; i += 256) {
-            const int r = i / per_row, k = i - r * per_row;
-            const int y = y0 - RB_AP + r, x0 = k * 8;
-            unsigned bits = 0u, cbits = 0u;
-            if (y >= ry0 && y <= ry1 && y >= 0 && y < h && x0 < w && x0 + 7 >= rx0 && x0 <= rx1) {
+    const bool al = ((w & 15) == 0) && ((((size_t)m | (size_t)cm | (size_t)mc | (size_t)roi | (size_t)base | (size_t)exp) & 15) == 0);
+    const int y_end = min(yb + RB_R, (h + 7) & ~7);
+    const int sx0 = s * BR_SPAN;
+    const bool active = st[f].status != CPE_ST_NO_REGION && yb <= ry1 + RB_AP && yb + RB_R - 1 >= ry0 - RB_AP &&
+                        sx0 <= rx1 + RB_AP && sx0 + BR_SPAN - 1 >= rx0 - RB_AP;
+    const unsigned rm = inx ? span32(rx0 - x0, min(nv, rx1 + 1 - x0)) : 0u;      // the lane's pixels inside the rectangle
+    const int ly0 = max(ry0, 0), ly1 = min(ry1, h - 1);
+    const unsigned long long *mbf = mb ? mb + f * bit_plane_words(h, w) : nullptr;
+    const int btc = bit_tile_cols(w);
+    unsigned long long *pb = bit_plane(bbits, f, h, w);
+    unsigned he0 = ~0u, he1 = ~0u, d10 = 0u, d11 = 0u, d20 = 0u, d21 = 0u, e40 = ~0u, e41 = ~0u;   // row-wise results of the last two rows
+    unsigned cb0 = 0u, cb1 = 0u, cb2 = 0u, cb3 = 0u;                                              // mc != 0 of the last four
+    for (int y = active ? yb - RB_AP : yb + RB_AP; y < y_end + RB_AP; y++) {
+        unsigned bs = 0u, rs = 0u, cs = 0u;       // base at row y - 4 and mc != 0 there, roi at row y - 2: the lane's 16 pixels
+        if (active) {
+            // pack (m & cm & mc) != 0 of the rectangle's pixels, and mc != 0 on its own for the seed of exp
+            unsigned xb = 0u, cb = 0u;
+            if (rm && y >= ly0 && y <= ly1) {
                 const size_t o = f * N + (size_t)y * w + x0;
-                // a line-mask byte is 0 or 255: (m & cm & mc) != 0 is the mask's bit and (cm & mc) != 0
-                const unsigned mbits = mbf ? (unsigned)(mbf[bit_word(btc, y, k >> 3)] >> ((k & 7) * 8)) & 255u : 255u;
-                if (al8) {
-                    const unsigned long long vc = *reinterpret_cast<const unsigned long long *>(mc + o);
-                    unsigned long long v = *reinterpret_cast<const unsigned long long *>(cm + o) & vc;
-                    if (!mbf) v &= *reinterpret_cast<const unsigned long long *>(m + o);
-                    bits = nonzero8(v) & mbits;
-                    cbits = nonzero8(vc);
-                } else {
-                    for (int b = 0; b < 8 && x0 + b < w; b++) {
-                        bits |= (((mbf ? 255 : m[o + b]) & cm[o + b]) & mc[o + b]) ? (1u << b) : 0u;
-                        cbits |= mc[o + b] ? (1u << b) : 0u;
-                    }
-                    bits &= mbits;
+                const uint4 vc = load_px16(mc + o, al, nv), va = load_px16(cm + o, al, nv);
+                uint4 v = make_uint4(va.x & vc.x, va.y & vc.y, va.z & vc.z, va.w & vc.w);
+                if (m) {
+                    const uint4 vm = load_px16(m + o, al, nv);
+                    v = make_uint4(v.x & vm.x, v.y & vm.y, v.z & vm.z, v.w & vm.w);
                 }
+                xb = nz16(v) & rm;
+                cb = nz16(vc) & rm;
+                // a line-mask byte is 0 or 255: (m & cm & mc) != 0 is the mask's bit and (cm & mc) != 0
+                if (mbf) xb &= (unsigned)(mbf[bit_word(btc, y, c >> 2)] >> ((c & 3) * 16));
             }
-            pk[i] = (uint8_t)bits;
-            pkc[i] = (uint8_t)cbits;
+            const unsigned win = (xb << 4) | (__shfl_up(xb, 1) >> 12) | ((__shfl_down(xb, 1) & 15u) << 20);
+            auto in_image = [&](int yy) { return yy >= 0 && yy < h; };
+            auto ero3 = [&](unsigned x, int yy) { x |= ~vw; return in_image(yy) ? (x & (x << 1) & (x >> 1)) : ~0u; };
+            auto dil3 = [&](unsigned x) { return x | (x << 1) | (x >> 1); };
+            // erode -> row y - 1
+            const unsigned he = ero3(win, y);
+            const unsigned er = in_image(y - 1) ? (he0 & he1 & he & vw) : 0u;
+            he0 = he1; he1 = he;
+            // dilate -> roi, row y - 2
+            const unsigned d1 = dil3(er);
+            const unsigned ro = in_image(y - 2) ? ((d10 | d11 | d1) & vw) : 0u;
+            d10 = d11; d11 = d1;
+            // dilate -> row y - 3
+            const unsigned d2 = dil3(ro);
+            const unsigned dd = in_image(y - 3) ? ((d20 | d21 | d2) & vw) : 0u;
+            d20 = d21; d21 = d2;
+            // erode -> base, row y - 4
+            const unsigned e4 = ero3(dd, y - 3);
+            const unsigned ba = in_image(y - 4) ? (e40 & e41 & e4 & vw) : 0u;
+            e40 = e41; e41 = e4;
+            bs = (ba >> 4) & 0xffffu; rs = (ro >> 4) & 0xffffu; cs = cb0;
+            cb0 = cb1; cb1 = cb2; cb2 = cb3; cb3 = cb;
+        }
+        const int yo = y - RB_AP, yr = active ? y - 2 : yo;
+        if (roi && out && yr >= yb && yr < y_end && yr < h) store_px16(roi + f * N + (size_t)yr * w + x0, rs, al, nv);
+        if (yo < yb) continue;
+        if (out && yo < h) {
+            const size_t o = f * N + (size_t)yo * w + x0;
+            store_px16(exp + o, bs & cs, al, nv);
+            if (base) store_px16(base + o, bs, al, nv);
+        }
+        tile_put(s_tile, l, yo, bs);
+        if ((yo & 7) == 7) {
+            __syncthreads();
+            tile_flush(s_tile, pb, w, yo >> 3, s, last, l);
+            __syncthreads();
         }
     }
-    __syncthreads();
-    // one 3x3 pass on words; pixels outside the image (and rows / words outside the band) are the neutral element
-    auto pass = [&](const unsigned long long *src, unsigned long long *dst, bool dil) {
-        const unsigned long long fill = dil ? 0ull : ~0ull;
-        for (int i = t; i < RB_ROWS * WW; i += 256) {
-            const int r = i / WW, j = i - r * WW;
-            unsigned long long acc = fill;
-#pragma unroll
-            for (int dr = -1; dr <= 1; dr++) {
-                const int rr = r + dr, y = y0 - RB_AP + rr;
-                unsigned long long hres = fill;
-                if (rr >= 0 && rr < RB_ROWS && y >= 0 && y < h) {
-                    const unsigned long long *row = src + (size_t)rr * WW;
-                    const unsigned long long va = row_valid_word(j - 1, w), vb = row_valid_word(j, w), vc = row_valid_word(j + 1, w);
-                    unsigned long long xa = j > 0 ? row[j - 1] : 0ull, xb = row[j], xc = j + 1 < WW ? row[j + 1] : 0ull;
-                    if (!dil) { xa |= ~va; xb |= ~vb; xc |= ~vc; }
-                    const unsigned long long up = (xb >> 1) | (xc << 63), down = (xb << 1) | (xa >> 63);
-                    hres = dil ? (xb | up | down) : (xb & up & down);
-                }
-                acc = dil ? (acc | hres) : (acc & hres);
-            }
-            const int y = y0 - RB_AP + r;
-            dst[i] = (y >= 0 && y < h) ? (acc & row_valid_word(j, w)) : 0ull;
-        }
-        __syncthreads();
-    };
-    auto emit = [&](const unsigned long long *src, uint8_t *dst, uint8_t *dst2, const unsigned long long *and2) {   // dst2 = src & and2
-        for (int i = t; i < RB_R * per_row; i += 256) {
-            const int tr = i / per_row, k = i - tr * per_row;
-            const int y = y0 + tr, x0 = k * 8;
-            if (y >= h || x0 >= w) continue;
-            const size_t wi = (size_t)(tr + RB_AP) * WW + (k >> 3);
-            const unsigned bits = (unsigned)(src[wi] >> ((k & 7) * 8)) & 255u;
-            const size_t o = f * N + (size_t)y * w + x0;
-            if (dst) store8(dst, o, x0, bits);
-            if (dst2) store8(dst2, o, x0, bits & (unsigned)(and2[wi] >> ((k & 7) * 8)));
-        }
-    };
-    pass(buf0, buf1, false);   // erode
-    pass(buf1, buf0, true);    // dilate -> roi
-    if (roi) emit(buf0, roi, nullptr, nullptr);
-    pass(buf0, buf1, true);    // dilate
-    pass(buf1, buf0, false);   // erode -> base
-    emit(buf0, base, exp, mcb);
-    // (columns past the row's end are 0: row_valid_word)
-    store_plane_band(bit_plane(bbits, f, h, w), h, w, y0, RB_R, t, [&](int tr, int j) { return buf0[(size_t)(tr + RB_AP) * WW + j]; });
 }
 
 // ---- joints: polygon-moment centroids inside the region rectangle, in cv2.findContours order ----------
@@ -1417,25 +1406,10 @@ int joints_mask_stage(int n, int h, int w, const MaskBuffers &B, FrameState *st,
     unsigned long long *hb = as_bits ? line_mask_bits(B, 0, n, h, w) : nullptr, *vb = as_bits ? line_mask_bits(B, 1, n, h, w) : nullptr;
     uint8_t *hm = as_bits && B.skip_debug ? nullptr : B.hmask, *vm = as_bits && B.skip_debug ? nullptr : B.vmask;
     uint8_t *jm = as_bits ? nullptr : B.joints_mask;
-    {
-        // band height by LDS budget: (2 (R + 40) + R) words of 8 bytes per 64 columns
-        const int WW = (w + 63) / 64;
-        const size_t lds64 = (size_t)(2 * (64 + 2 * OB_AP) + 64) * WW * 8, lds32 = (size_t)(2 * (32 + 2 * OB_AP) + 32) * WW * 8;
-        // more than the default 64 KB of dynamic LDS.  The attribute belongs to the (function, device) pair, so it is set on
-        // every call for the device the launch goes to (cheap, and safe with several GPUs / host threads in one process)
-        CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_open20_joints<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_open20_joints<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if (lds64 <= 96 * 1024) {
-            const int bands = (h + 63) / 64;
-            CPE_KLAUNCH(k_open20_joints<64>, dim3((unsigned)(n * bands)), dim3(256), lds64, s, (const uint8_t *)B.binary, h, w, bands,
-                        hm, vm, jm, B.jbits, hb, vb);
-        } else {
-            CPE_CHECK_ARG(lds32 <= 160 * 1024, "joints_mask_stage: frame too wide (%d columns)", w);
-            const int bands = (h + 31) / 32;
-            CPE_KLAUNCH(k_open20_joints<32>, dim3((unsigned)(n * bands)), dim3(256), lds32, s, (const uint8_t *)B.binary, h, w, bands,
-                        hm, vm, jm, B.jbits, hb, vb);
-        }
-    }
+    // one wave per column strip, band of rows and frame
+    CPE_CHECK_ARG(n <= 65535 && (h + OB_R - 1) / OB_R <= 65535, "joints_mask_stage: too many frames or rows for one launch");
+    CPE_KLAUNCH(k_open20_joints, dim3((unsigned)br_strips(w), (unsigned)((h + OB_R - 1) / OB_R), (unsigned)n), dim3(64), 0, s,
+                (const uint8_t *)B.binary, h, w, hm, vm, jm, B.jbits, hb, vb);
     CPE_CHECK_LAUNCH("joints_mask_stage");
     int rc;
     if ((rc = ccl_components(B.joints_mask, B.jbits, n, h, w, 0, WIN_FRAME, B.lab_p, B.roots_p, ROOTS_JOINTS, st, s)) != CPE_OK) return rc;
@@ -1495,10 +1469,8 @@ int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, 
     }
     // a-5 tail, a-6 and the labelling of the expanded masks, once per line direction.  The two directions share
     // nothing but their inputs: the vertical one runs on the helper stream (if any) with the spot chain's label plane.
-    const int rb_bands = (h + RB_R - 1) / RB_R;
-    const size_t rb_lds = (size_t)3 * RB_ROWS * ((w + 63) / 64) * 8;
-    CPE_CHECK_ARG(rb_lds <= 160 * 1024, "masks_stage: frame too wide (%d columns)", w);
-    CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_roi_base), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    const dim3 rb_grid((unsigned)br_strips(w), (unsigned)((h + RB_R - 1) / RB_R), (unsigned)n);
+    CPE_CHECK_ARG(n <= 65535 && rb_grid.y <= 65535, "masks_stage: too many frames or rows for one launch");
     if (side) { (void)hipEventRecord(side->clahe_done, s); (void)hipStreamWaitEvent(side->s, side->clahe_done, 0); }
     for (int which = 0; which < 2; which++) {
         hipStream_t q = (which && side) ? side->s : s;
@@ -1514,8 +1486,8 @@ int masks_stage(const uint8_t *gray, int n, int h, int w, const MaskBuffers &B, 
         // roi = open3x3(mask & circle_mask & mask_contour), base = close3x3(roi) as a one-bit plane, exp = base & mask_contour.
         // base's bytes are only written where the labelling will read them (the byte-level kernels)
         uint8_t *base = ccl_components_reads_bits(bits, w, lab) ? nullptr : (which ? B.base_v : B.base_h);
-        CPE_KLAUNCH(k_roi_base, dim3((unsigned)(n * rb_bands)), dim3(256), rb_lds, q, lm, (const uint8_t *)B.cm, (const uint8_t *)B.mc,
-                    h, w, rb_bands, (const FrameState *)st, roi, base, exp, bits, lmb);
+        CPE_KLAUNCH(k_roi_base, rb_grid, dim3(64), 0, q, lm, (const uint8_t *)B.cm, (const uint8_t *)B.mc,
+                    h, w, (const FrameState *)st, roi, base, exp, bits, lmb);
         if ((rc = ccl_components(base, bits, n, h, w, 0, WIN_REGION, lab, roots, list, st, q)) != CPE_OK) return rc;
         unsigned long long *fl_bg = fl_plane(2 + 2 * which), *fl_out = fl_plane(3 + 2 * which);
         if ((rc = outside_flood(base, n, h, w, st, WIN_REGION, fl_bg, fl_out, fl_words, q, bits)) != CPE_OK) return rc;
