@@ -859,12 +859,14 @@ __device__ __forceinline__ bool lm_damped_solve<2>(const double *A, const double
 //     loop on the same numbers (frame list, terms and the sums come from LDS, everything else each wave computes for itself, and
 //     the arithmetic is deterministic), so every branch here goes the same way in all waves.  Keep it so: no branch in this
 //     loop may depend on the wave or the lane.
-template <int N, class Problem>
+//   - NX numbers describe a point and N <= NX a step (the projector model keeps unit vectors whole in x and steps in their
+//     tangent planes); NX = N everywhere else.
+template <int N, int NX = N, class Problem>
 __device__ __forceinline__ void lm_minimize(Problem &prob, const double *x0, double f0, double tolx, double tolf, int maxiter, double *x,
                                             double &fx, int &itercount, int &func_evals)
 {
 #pragma unroll
-    for (int k = 0; k < N; k++) x[k] = x0[k];
+    for (int k = 0; k < NX; k++) x[k] = x0[k];
     fx = f0;
     double lambda = 1e-3;
     itercount = 0;
@@ -876,14 +878,16 @@ __device__ __forceinline__ void lm_minimize(Problem &prob, const double *x0, dou
         double dmax = 0;
         const double fprev = fx;
         for (int tr = 0; tr < 12 && !accepted; tr++) {
-            double dl[N], xn[N];
+            double dl[N], xn[NX];
             if (!lm_damped_solve<N>(A, g, lambda, dl) || !prob.candidate(x, dl, xn)) { lambda = lambda * 10; continue; }
             const double fn = prob(xn);
             func_evals++;
             if (fn < fx) {
                 dmax = 0;
 #pragma unroll
-                for (int k = 0; k < N; k++) { dmax = fmax(dmax, fabs(dl[k])); x[k] = xn[k]; }
+                for (int k = 0; k < N; k++) dmax = fmax(dmax, fabs(dl[k]));
+#pragma unroll
+                for (int k = 0; k < NX; k++) x[k] = xn[k];
                 fx = fn;
                 lambda = fmax(lambda / 10, 1e-12);
                 accepted = true;
@@ -2521,28 +2525,39 @@ struct PlaneMoments {
 // enough points, and not collinear or coincident: lambda_mid > 1e-12 lambda_max
 __device__ __forceinline__ bool plane_spread_ok(const PlaneMoments &m) { return m.N >= 3 && m.w[1] > 1e-12 * m.w[2]; }
 
-// centroid, then the centred covariance / (N - 1) in a second pass, then its eigen-decomposition (wave-uniform results; the normal
-// of fitplane.m is V(:,1)).  `each(body)` calls body(p) for every point p[3] of the set that this lane takes; it is walked twice
+// the sums of plane_moments: the count Np, the centroid c, then in a second pass the centred scatter q = xx xy xz yy yz zz
 template <class Each>
-__device__ __forceinline__ void plane_moments(Each each, PlaneMoments &m)
+__device__ __forceinline__ void plane_sums(Each each, int &Np, double *c, double *q)
 {
     double s[3] = {0, 0, 0};
     int cn = 0;
     each([&](const double *p) { s[0] = s[0] + p[0]; s[1] = s[1] + p[1]; s[2] = s[2] + p[2]; cn++; });
-    m.N = wave_sum_i(cn);
-    const double N = (double)(m.N > 0 ? m.N : 1);
+    Np = wave_sum_i(cn);
+    const double N = (double)(Np > 0 ? Np : 1);
 #pragma unroll
-    for (int a = 0; a < 3; a++) m.c[a] = wave_sum(s[a]) / N;
-    double q[6] = {0, 0, 0, 0, 0, 0};
-    const double c0 = m.c[0], c1 = m.c[1], c2 = m.c[2];
+    for (int a = 0; a < 3; a++) c[a] = wave_sum(s[a]) / N;
+#pragma unroll
+    for (int a = 0; a < 6; a++) q[a] = 0;
+    const double c0 = c[0], c1 = c[1], c2 = c[2];
     each([&](const double *p) {
         const double e0 = p[0] - c0, e1 = p[1] - c1, e2 = p[2] - c2;
         q[0] = q[0] + e0 * e0; q[1] = q[1] + e0 * e1; q[2] = q[2] + e0 * e2;
         q[3] = q[3] + e1 * e1; q[4] = q[4] + e1 * e2; q[5] = q[5] + e2 * e2;
     });
+#pragma unroll
+    for (int a = 0; a < 6; a++) q[a] = wave_sum(q[a]);
+}
+
+// centroid, then the centred covariance / (N - 1) in a second pass, then its eigen-decomposition (wave-uniform results; the normal
+// of fitplane.m is V(:,1)).  `each(body)` calls body(p) for every point p[3] of the set that this lane takes; it is walked twice
+template <class Each>
+__device__ __forceinline__ void plane_moments(Each each, PlaneMoments &m)
+{
+    double q[6];
+    plane_sums(each, m.N, m.c, q);
     const double d = (double)(m.N > 1 ? m.N - 1 : 1);
 #pragma unroll
-    for (int a = 0; a < 6; a++) q[a] = wave_sum(q[a]) / d;
+    for (int a = 0; a < 6; a++) q[a] = q[a] / d;
     const double Cv[9] = {q[0], q[1], q[2], q[1], q[3], q[4], q[2], q[4], q[5]};
     eig3(Cv, m.w, m.V);
 }
@@ -2887,6 +2902,479 @@ __global__ __launch_bounds__(64) void k_table_triangulate(const double *__restri
         o_stats[2 * f + 1] = m > 0 ? rmax : 0.0;
     }
 }
+// ------------------------------------------------------------------------------------------ projector model
+// BUILD-DEFINED (include/cpe.h cpe_fit_projector_model, whose numbered rule this follows): the two pencils of laser planes
+// n = a_k + v b_k through one centre C, fitted to the points of many frames through the moments of every line.
+//   x = C[3], a_0[3], b_0[3], a_1[3], b_1[3]; a step has 13 numbers: dC, then per family two tangent coordinates of a_k and db_k.
+//   info[6] is the "a mask byte changed" flag of the running round and info[7] the "loop has ended" flag; both are 0 on return.
+constexpr int PM_NX = 15, PM_NP = 13, PM_MOM = 12;
+
+// unit normal nh of line v of family fam under x, C - relative quantities left to the caller -> |a + v b|
+__device__ __forceinline__ double pm_normal(const double *x, int fam, int v, double *nh)
+{
+    const double *a = x + 3 + 6 * fam, *b = a + 3;
+    const double dv = (double)v;
+    const double n0 = a[0] + dv * b[0], n1 = a[1] + dv * b[1], n2 = a[2] + dv * b[2];
+    const double len = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+    nh[0] = n0 / len; nh[1] = n1 / len; nh[2] = n2 / len;
+    return len;
+}
+
+// an orthonormal basis e1, e2 of the tangent plane of the unit sphere at a: the coordinate axis of the smallest |a_i| (the first
+// of them) with its part along a removed, and a x e1
+__device__ __forceinline__ void pm_tangent(const double *a, double *e1, double *e2)
+{
+    const double a0 = fabs(a[0]), a1 = fabs(a[1]), a2 = fabs(a[2]);
+    double ax[3] = {0, 0, 0};
+    if (a0 <= a1 && a0 <= a2) ax[0] = 1; else if (a1 <= a2) ax[1] = 1; else ax[2] = 1;
+    const double d = (ax[0] * a[0] + ax[1] * a[1]) + ax[2] * a[2];
+    double t[3] = {ax[0] - d * a[0], ax[1] - d * a[1], ax[2] - d * a[2]};
+    const double tn = sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+    e1[0] = t[0] / tn; e1[1] = t[1] / tn; e1[2] = t[2] / tn;
+    cross3(a, e1, e2);
+}
+
+// position of (a, b), a <= b, in the upper triangle of an N x N matrix packed by rows
+template <int N>
+__device__ __forceinline__ constexpr int tri_at(int a, int b) { return a * N - a * (a - 1) / 2 + (b - a); }
+
+// The model as lm_minimize takes it, everything from the moments of the lines: with y = X - C of a kept point of line (k, v),
+// n = a_k + v b_k, nh = n / |n|, Q = (I - nh nh') / |n|:  r = nh.y,  dr/dC = -nh,  dr/dt = E' Q y (E = e1 e2 of pm_tangent),
+// dr/db = v Q y.  Over the line, sum 1 = N, sum y = s = N (m - C), sum y y' = M = S + N (m - C)(m - C)', so with D = [E' Q; v Q]
+// (5 x 3):  J'J = [N nh nh', -nh (D s)'; ., D M D'],  J'r = [-nh (nh.s); D M nh],  sum r^2 = nh' M nh.
+// Lane l takes the lines l, l + 64, ... of a family; the 64-lane tree; family 0 before family 1.
+struct PmProblem {
+    const double *mom;
+    int L, lo, lane;
+    __device__ __forceinline__ double operator()(const double *x) const
+    {
+        double acc = 0.0;
+        for (int i = lane; i < 2 * L; i += 64) {
+            const double *q = mom + PM_MOM * i;
+            if (!(q[0] > 0)) continue;
+            const int fam = i >= L ? 1 : 0;
+            double nh[3];
+            pm_normal(x, fam, lo + (i - fam * L), nh);
+            const double d0 = q[1] - x[0], d1 = q[2] - x[1], d2 = q[3] - x[2];
+            const double nd = (nh[0] * d0 + nh[1] * d1) + nh[2] * d2;
+            const double t0 = (q[4] * nh[0] + q[5] * nh[1]) + q[6] * nh[2], t1 = (q[5] * nh[0] + q[7] * nh[1]) + q[8] * nh[2],
+                         t2 = (q[6] * nh[0] + q[8] * nh[1]) + q[9] * nh[2];
+            acc = acc + (((nh[0] * t0 + nh[1] * t1) + nh[2] * t2) + q[0] * nd * nd);
+        }
+        return wave_sum(acc);
+    }
+    __device__ __forceinline__ void normal(const double *x, double *A, double *g) const
+    {
+#pragma unroll
+        for (int k = 0; k < PM_NP * (PM_NP + 1) / 2; k++) A[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < PM_NP; k++) g[k] = 0.0;
+#pragma unroll
+        for (int fam = 0; fam < 2; fam++) {
+            double acc[44];   // the 8 x 8 of (C, t, b) of this family, upper triangle by rows, then its J'r
+#pragma unroll
+            for (int k = 0; k < 44; k++) acc[k] = 0.0;
+            double e1[3], e2[3];
+            pm_tangent(x + 3 + 6 * fam, e1, e2);
+            for (int i = lane; i < L; i += 64) {
+                const double *q = mom + PM_MOM * (fam * L + i);
+                const double N = q[0];
+                if (!(N > 0)) continue;
+                const double dv = (double)(lo + i);
+                double nh[3];
+                const double len = pm_normal(x, fam, lo + i, nh);
+                const double d[3] = {q[1] - x[0], q[2] - x[1], q[3] - x[2]};
+                const double s[3] = {N * d[0], N * d[1], N * d[2]};
+                const double M[9] = {q[4] + s[0] * d[0], q[5] + s[0] * d[1], q[6] + s[0] * d[2],
+                                     q[5] + s[0] * d[1], q[7] + s[1] * d[1], q[8] + s[1] * d[2],
+                                     q[6] + s[0] * d[2], q[8] + s[1] * d[2], q[9] + s[2] * d[2]};
+                double Q[9], D[15];
+#pragma unroll
+                for (int a = 0; a < 3; a++)
+#pragma unroll
+                    for (int b = 0; b < 3; b++) Q[a * 3 + b] = ((a == b ? 1.0 : 0.0) - nh[a] * nh[b]) / len;
+#pragma unroll
+                for (int b = 0; b < 3; b++) {
+                    D[b] = (e1[0] * Q[b] + e1[1] * Q[3 + b]) + e1[2] * Q[6 + b];
+                    D[3 + b] = (e2[0] * Q[b] + e2[1] * Q[3 + b]) + e2[2] * Q[6 + b];
+#pragma unroll
+                    for (int a = 0; a < 3; a++) D[(2 + a) * 3 + b] = dv * Q[a * 3 + b];
+                }
+                double DM[15], Ds[5], gp[5];
+#pragma unroll
+                for (int a = 0; a < 5; a++) {
+#pragma unroll
+                    for (int b = 0; b < 3; b++) DM[a * 3 + b] = (D[a * 3] * M[b] + D[a * 3 + 1] * M[3 + b]) + D[a * 3 + 2] * M[6 + b];
+                    Ds[a] = (D[a * 3] * s[0] + D[a * 3 + 1] * s[1]) + D[a * 3 + 2] * s[2];
+                    gp[a] = (DM[a * 3] * nh[0] + DM[a * 3 + 1] * nh[1]) + DM[a * 3 + 2] * nh[2];
+                }
+                const double ns = (nh[0] * s[0] + nh[1] * s[1]) + nh[2] * s[2];
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+#pragma unroll
+                    for (int b = a; b < 3; b++) acc[tri_at<8>(a, b)] = acc[tri_at<8>(a, b)] + N * nh[a] * nh[b];
+#pragma unroll
+                    for (int b = 0; b < 5; b++) acc[tri_at<8>(a, 3 + b)] = acc[tri_at<8>(a, 3 + b)] - nh[a] * Ds[b];
+                    acc[36 + a] = acc[36 + a] - nh[a] * ns;
+                }
+#pragma unroll
+                for (int a = 0; a < 5; a++) {
+#pragma unroll
+                    for (int b = a; b < 5; b++)
+                        acc[tri_at<8>(3 + a, 3 + b)] = acc[tri_at<8>(3 + a, 3 + b)] +
+                                                       ((DM[a * 3] * D[b * 3] + DM[a * 3 + 1] * D[b * 3 + 1]) + DM[a * 3 + 2] * D[b * 3 + 2]);
+                    acc[36 + 3 + a] = acc[36 + 3 + a] + gp[a];
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < 8; a++) {
+                const int ga = a < 3 ? a : 3 + 5 * fam + (a - 3);
+#pragma unroll
+                for (int b = a; b < 8; b++) {
+                    const int gb = b < 3 ? b : 3 + 5 * fam + (b - 3);
+                    A[tri_at<PM_NP>(ga, gb)] = A[tri_at<PM_NP>(ga, gb)] + wave_sum(acc[tri_at<8>(a, b)]);
+                }
+                g[ga] = g[ga] + wave_sum(acc[36 + a]);
+            }
+        }
+    }
+    // C and b move by their steps; a_k moves in its tangent plane and is brought back to the unit sphere
+    __device__ __forceinline__ bool candidate(const double *x, const double *dl, double *xn) const
+    {
+#pragma unroll
+        for (int c = 0; c < 3; c++) xn[c] = x[c] + dl[c];
+#pragma unroll
+        for (int fam = 0; fam < 2; fam++) {
+            const double *a = x + 3 + 6 * fam, *st = dl + 3 + 5 * fam;
+            double e1[3], e2[3], t[3];
+            pm_tangent(a, e1, e2);
+#pragma unroll
+            for (int c = 0; c < 3; c++) t[c] = (a[c] + st[0] * e1[c]) + st[1] * e2[c];
+            const double tn = sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                xn[3 + 6 * fam + c] = t[c] / tn;
+                xn[6 + 6 * fam + c] = a[3 + c] + st[2 + c];
+            }
+        }
+        return true;
+    }
+};
+
+// The moments of line (family, index) = blockIdx.x under the mask of this round: the walk of k_index_planes.  Round 0 keeps
+// every usable point; a later round keeps the usable points with |nh.(X - C)| < tau under the model of the round before, and
+// raises info[6] when a byte of the mask differs from what that round left.  Slot k of the mask is written and read by lane
+// k % 64 of this wavefront only.
+__global__ __launch_bounds__(64) void k_pm_moments(const double *__restrict__ X, const int *__restrict__ idx, const int *__restrict__ cnt,
+                                                   int n, const uint8_t *__restrict__ use, const int *__restrict__ frame_ok, int lo, int L,
+                                                   int round, double tau, const double *__restrict__ model, int *info,
+                                                   double *__restrict__ o_mom, int *__restrict__ o_count, int *__restrict__ o_frames,
+                                                   uint8_t *o_mask)
+{
+    if (round > 0 && info[7] != 0) return;
+    const int line = blockIdx.x, lane = threadIdx.x;   // line = family * L + (v - lo)
+    const int fam = line / L, v = lo + (line - fam * L);
+    uint8_t *mk = o_mask + (size_t)fam * (size_t)n * MAXP;
+    double nh[3] = {0, 0, 0}, Cc[3] = {0, 0, 0};
+    if (round > 0) {
+        double x[PM_NX];
+#pragma unroll
+        for (int k = 0; k < PM_NX; k++) x[k] = model[k];
+        pm_normal(x, fam, v, nh);
+        Cc[0] = x[0]; Cc[1] = x[1]; Cc[2] = x[2];
+    }
+    int frames = 0, changed = 0;
+    bool first = true;
+    auto each = [&](auto body) {
+        for (int f = 0; f < n; f++) {
+            if (frame_ok && frame_ok[f] == 0) continue;
+            const int c = min(max(cnt[f], 0), MAXP);
+            const size_t base = (size_t)f * MAXP;
+            bool any = false;
+            for (int k = lane; k < c; k += 64) {
+                if (idx[(base + k) * 2 + fam] != v) continue;
+                if (use && use[base + k] == 0) continue;
+                const double *p = X + (base + k) * 3;
+                if (!finite3(p)) continue;
+                if (first) {
+                    uint8_t in = 1;
+                    if (round > 0) {
+                        const double r = (nh[0] * (p[0] - Cc[0]) + nh[1] * (p[1] - Cc[1])) + nh[2] * (p[2] - Cc[2]);
+                        in = fabs(r) < tau ? 1 : 0;
+                        changed |= in != mk[base + k];
+                    }
+                    mk[base + k] = in;
+                    if (!in) continue;
+                } else if (!mk[base + k]) continue;
+                body(p);
+                any = true;
+            }
+            if (first && __ballot(any) != 0ull) frames++;
+        }
+        first = false;
+    };
+    int N;
+    double c[3], q[6];
+    plane_sums(each, N, c, q);
+    if (round > 0 && __ballot(changed) != 0ull && lane == 0) atomicOr(&info[6], 1);
+    if (lane == 0) {
+        double *o = o_mom + (size_t)line * PM_MOM;
+        o[0] = (double)N;
+        o[1] = N > 0 ? c[0] : 0.0; o[2] = N > 0 ? c[1] : 0.0; o[3] = N > 0 ? c[2] : 0.0;
+#pragma unroll
+        for (int a = 0; a < 6; a++) o[4 + a] = q[a];
+        o[10] = 0; o[11] = 0;
+        o_count[line] = N; o_frames[line] = frames;
+    }
+}
+
+// One wavefront: the model from the moments.  Round 0 starts in closed form (or from x0_in), a later round from the model of
+// the round before; see the header for the start and the failures.
+__global__ __launch_bounds__(64) void k_pm_solve(const double *__restrict__ mom, const int *__restrict__ frames, int lo, int L, int round,
+                                                 double min_spread, double tolx, double tolf, int maxiter,
+                                                 const double *__restrict__ x0_in, double *model, int *info)
+{
+    __shared__ double sN[2 * CPE_MAXL * 3];   // the free plane's normal of every line
+    __shared__ int sUse[2 * CPE_MAXL];
+    const int lane = threadIdx.x;
+    if (round > 0) {
+        if (info[7] != 0) return;                                     // the loop has ended
+        if (info[6] == 0) { if (lane == 0) info[7] = 1; return; }     // no byte of the mask changed: the model stands
+    }
+    const int it_before = round > 0 ? info[2] : 0, ev_before = round > 0 ? info[3] : 0;
+    // free planes
+    int kept0 = 0, kept1 = 0, use0 = 0, use1 = 0;
+    for (int i = lane; i < 2 * L; i += 64) {
+        const double *q = mom + PM_MOM * i;
+        const int N = (int)q[0];
+        if (i < L) kept0 += N; else kept1 += N;
+        const double Cv[9] = {q[4], q[5], q[6], q[5], q[7], q[8], q[6], q[8], q[9]};
+        double w[3], V[9];
+        eig3(Cv, w, V);
+        bool ok = N >= 3 && frames[i] >= 2 && w[2] > 0;
+        ok = ok && !(w[1] / w[2] < min_spread) && isfinite(V[0]) && isfinite(V[3]) && isfinite(V[6]);
+        sUse[i] = ok ? 1 : 0;
+        sN[3 * i] = V[0]; sN[3 * i + 1] = V[3]; sN[3 * i + 2] = V[6];
+        if (ok) { if (i < L) use0++; else use1++; }
+    }
+    kept0 = wave_sum_i(kept0); kept1 = wave_sum_i(kept1); use0 = wave_sum_i(use0); use1 = wave_sum_i(use1);
+    __syncthreads();
+    auto fail = [&]() {
+        if (lane < 16) model[lane] = 0;
+        if (lane == 0) {
+            info[0] = CPE_ST_FEW_POINTS; info[1] = round; info[2] = it_before; info[3] = ev_before; info[4] = kept0; info[5] = kept1;
+            info[6] = 0; info[7] = 1;
+        }
+    };
+    if (use0 < 2 || use1 < 2) { fail(); return; }
+    double x0[PM_NX];
+    if (round > 0) {
+#pragma unroll
+        for (int k = 0; k < PM_NX; k++) x0[k] = model[k];
+    } else if (x0_in != nullptr) {
+#pragma unroll
+        for (int k = 0; k < PM_NX; k++) x0[k] = x0_in[k];
+    } else {
+        // C: the point nearest to the free planes, (sum n n') C = sum n (n.m)
+        double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int i = lane; i < 2 * L; i += 64) {
+            if (!sUse[i]) continue;
+            const double *q = mom + PM_MOM * i;
+            const double j[3] = {sN[3 * i], sN[3 * i + 1], sN[3 * i + 2]};
+            normal_accumulate<3>(j, (j[0] * q[1] + j[1] * q[2]) + j[2] * q[3], acc);
+        }
+#pragma unroll
+        for (int a = 0; a < 9; a++) acc[a] = wave_sum(acc[a]);
+        double M[9] = {acc[0], acc[1], acc[2], acc[1], acc[3], acc[4], acc[2], acc[4], acc[5]};
+        double rhs[3] = {acc[6], acc[7], acc[8]};
+        if (!gauss_solve<3>(M, rhs, x0) || !finite3(x0)) { fail(); return; }
+        bool good = true;
+#pragma unroll
+        for (int fam = 0; fam < 2; fam++) {
+            // u: the axis of the pencil, the direction every normal is perpendicular to
+            double sc[6] = {0, 0, 0, 0, 0, 0}, sv = 0;
+            long long key = LLONG_MAX;
+            for (int i = lane; i < L; i += 64) {
+                if (!sUse[fam * L + i]) continue;
+                const double *nn = sN + 3 * (fam * L + i);
+                sc[0] = sc[0] + nn[0] * nn[0]; sc[1] = sc[1] + nn[0] * nn[1]; sc[2] = sc[2] + nn[0] * nn[2];
+                sc[3] = sc[3] + nn[1] * nn[1]; sc[4] = sc[4] + nn[1] * nn[2]; sc[5] = sc[5] + nn[2] * nn[2];
+                const long long v = (long long)lo + i;
+                sv = sv + (double)v;
+                const long long kk = (v < 0 ? -v : v) * 512 + i;     // nearest to v = 0, the lower index on a tie
+                if (kk < key) key = kk;
+            }
+#pragma unroll
+            for (int a = 0; a < 6; a++) sc[a] = wave_sum(sc[a]);
+            sv = wave_sum(sv);
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) { const long long o = __shfl_xor(key, off, 64); if (o < key) key = o; }
+            const double Cv[9] = {sc[0], sc[1], sc[2], sc[1], sc[3], sc[4], sc[2], sc[4], sc[5]};
+            double w[3], V[9];
+            eig3(Cv, w, V);
+            const double u[3] = {V[0], V[3], V[6]};
+            const int iref = (int)(key % 512);
+            double e1[3] = {sN[3 * (fam * L + iref)], sN[3 * (fam * L + iref) + 1], sN[3 * (fam * L + iref) + 2]}, e2[3];
+            {
+                const double a0 = fabs(e1[0]), a1 = fabs(e1[1]), a2 = fabs(e1[2]);
+                const double big = (a0 >= a1 && a0 >= a2) ? e1[0] : (a1 >= a2 ? e1[1] : e1[2]);
+                if (big < 0) { e1[0] = -e1[0]; e1[1] = -e1[1]; e1[2] = -e1[2]; }
+                const double du = (e1[0] * u[0] + e1[1] * u[1]) + e1[2] * u[2];
+#pragma unroll
+                for (int c = 0; c < 3; c++) e1[c] = e1[c] - du * u[c];
+                const double en = sqrt((e1[0] * e1[0] + e1[1] * e1[1]) + e1[2] * e1[2]);
+#pragma unroll
+                for (int c = 0; c < 3; c++) e1[c] = e1[c] / en;
+                cross3(u, e1, e2);
+            }
+            // tan(theta_v) ~ alpha + beta v over the usable lines, v centred
+            const double nu = (double)(fam == 0 ? use0 : use1), vbar = sv / nu;
+            double st = 0, svv = 0, svt = 0;
+            for (int i = lane; i < L; i += 64) {
+                if (!sUse[fam * L + i]) continue;
+                const double *nn = sN + 3 * (fam * L + i);
+                const double t = ((nn[0] * e2[0] + nn[1] * e2[1]) + nn[2] * e2[2]) / ((nn[0] * e1[0] + nn[1] * e1[1]) + nn[2] * e1[2]);
+                const double dv = (double)((long long)lo + i) - vbar;
+                st = st + t; svv = svv + dv * dv; svt = svt + dv * t;
+            }
+            st = wave_sum(st); svv = wave_sum(svv); svt = wave_sum(svt);
+            const double beta = svt / svv, alpha = st / nu - beta * vbar;
+            double a[3] = {e1[0] + alpha * e2[0], e1[1] + alpha * e2[1], e1[2] + alpha * e2[2]};
+            const double an = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                x0[3 + 6 * fam + c] = a[c] / an;
+                x0[6 + 6 * fam + c] = beta * e2[c] / an;
+            }
+            good = good && svv > 0;
+        }
+        if (!good) { fail(); return; }
+    }
+    PmProblem prob{mom, L, lo, lane};
+    const double f0 = prob(x0);
+    bool fin = isfinite(f0);
+#pragma unroll
+    for (int k = 0; k < PM_NX; k++) fin = fin && isfinite(x0[k]);
+    if (!fin) { fail(); return; }
+    double x[PM_NX], fx;
+    int itercount, func_evals = 1;
+    lm_minimize<PM_NP, PM_NX>(prob, x0, f0, tolx, tolf, maxiter, x, fx, itercount, func_evals);
+    {
+        // The LM accepts a trial only when the objective falls, so it cannot place x better than the rounding of the objective
+        // lets it see: sqrt(eps f / curvature), 4e-8 mm along the weakest direction of C on 12 boards and 8e-7 mm where a
+        // mis-numbered frame leaves f = 4000.  Closing Gauss-Newton steps of the undamped system go below that: at most 10, each
+        // taken when it does not raise the objective beyond its rounding, until one is no longer than tolx.
+#pragma nounroll
+        for (int closing = 0; closing < 10; closing++) {
+            double A[PM_NP * (PM_NP + 1) / 2], g[PM_NP], dl[PM_NP], xn[PM_NX];
+            prob.normal(x, A, g);
+            if (!lm_damped_solve<PM_NP>(A, g, 0.0, dl) || !prob.candidate(x, dl, xn)) break;
+            const double fn = prob(xn);
+            func_evals++;
+            bool take = fn <= fx + 1e-12 * (1.0 + fx);
+            double dmax = 0;
+#pragma unroll
+            for (int k = 0; k < PM_NP; k++) dmax = fmax(dmax, fabs(dl[k]));
+#pragma unroll
+            for (int k = 0; k < PM_NX; k++) take = take && isfinite(xn[k]);
+            if (!take) break;
+#pragma unroll
+            for (int k = 0; k < PM_NX; k++) x[k] = xn[k];
+            fx = fn;
+            if (dmax <= tolx) break;
+        }
+    }
+    fin = isfinite(fx);
+#pragma unroll
+    for (int k = 0; k < PM_NX; k++) fin = fin && isfinite(x[k]);
+    if (!fin) { fail(); return; }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < PM_NX; k++) model[k] = x[k];
+        model[15] = fx;
+        info[0] = CPE_ST_OK; info[1] = round; info[2] = it_before + itercount; info[3] = ev_before + func_evals;
+        info[4] = kept0; info[5] = kept1; info[6] = 0;
+        if (round == 0) info[7] = 0;
+    }
+}
+
+// Blocks 0..n-1: frame_counts of frame blockIdx.x = residuals used and trimmed, per family.  Block n: every line's rms under the
+// final model into its moments, and the loop's two flags back to 0.
+__global__ __launch_bounds__(64) void k_pm_finish(const double *__restrict__ X, const int *__restrict__ idx, const int *__restrict__ cnt,
+                                                  int n, const uint8_t *__restrict__ use, const int *__restrict__ frame_ok, int lo, int L,
+                                                  const double *__restrict__ model, int *info, double *o_mom,
+                                                  const uint8_t *__restrict__ mask, int *__restrict__ o_fc)
+{
+    const int f = blockIdx.x, lane = threadIdx.x;
+    if (f == n) {
+        const bool ok = info[0] == CPE_ST_OK;
+        double x[PM_NX];
+#pragma unroll
+        for (int k = 0; k < PM_NX; k++) x[k] = model[k];
+        for (int i = lane; i < 2 * L; i += 64) {
+            double *q = o_mom + PM_MOM * (size_t)i;
+            double rms = 0.0;
+            if (ok && q[0] > 0) {
+                const int fam = i >= L ? 1 : 0;
+                double nh[3];
+                pm_normal(x, fam, lo + (i - fam * L), nh);
+                const double d0 = q[1] - x[0], d1 = q[2] - x[1], d2 = q[3] - x[2];
+                const double nd = (nh[0] * d0 + nh[1] * d1) + nh[2] * d2;
+                const double t0 = (q[4] * nh[0] + q[5] * nh[1]) + q[6] * nh[2], t1 = (q[5] * nh[0] + q[7] * nh[1]) + q[8] * nh[2],
+                             t2 = (q[6] * nh[0] + q[8] * nh[1]) + q[9] * nh[2];
+                rms = sqrt(fmax((((nh[0] * t0 + nh[1] * t1) + nh[2] * t2) + q[0] * nd * nd) / q[0], 0.0));
+            }
+            q[10] = rms;
+        }
+        if (lane == 0) { info[6] = 0; info[7] = 0; }
+        return;
+    }
+    int used0 = 0, used1 = 0, trim0 = 0, trim1 = 0;
+    if (!(frame_ok && frame_ok[f] == 0)) {
+        const int c = min(max(cnt[f], 0), MAXP);
+        const size_t base = (size_t)f * MAXP;
+        for (int k = lane; k < c; k += 64) {
+            if (use && use[base + k] == 0) continue;
+            if (!finite3(X + (base + k) * 3)) continue;
+            const int v0 = idx[(base + k) * 2], v1 = idx[(base + k) * 2 + 1];
+            if (v0 >= lo && v0 - lo < L) { if (mask[base + k]) used0++; else trim0++; }
+            if (v1 >= lo && v1 - lo < L) { if (mask[(size_t)n * MAXP + base + k]) used1++; else trim1++; }
+        }
+    }
+    used0 = wave_sum_i(used0); trim0 = wave_sum_i(trim0); used1 = wave_sum_i(used1); trim1 = wave_sum_i(trim1);
+    if (lane == 0) { o_fc[4 * f] = used0; o_fc[4 * f + 1] = trim0; o_fc[4 * f + 2] = used1; o_fc[4 * f + 3] = trim1; }
+}
+
+// the table of a model for the indices lo..hi: one lane per line, lines in rounds of 64
+__global__ __launch_bounds__(64) void k_pm_table(const double *__restrict__ model, const int *__restrict__ info, int lo, int L,
+                                                 double *__restrict__ o_P, int *__restrict__ o_status, double *__restrict__ o_centre,
+                                                 int *__restrict__ o_cstatus)
+{
+    const int lane = threadIdx.x;
+    const bool ok = info[0] == CPE_ST_OK;
+    double x[PM_NX];
+#pragma unroll
+    for (int k = 0; k < PM_NX; k++) x[k] = model[k];
+    for (int i = lane; i < 2 * L; i += 64) {
+        const int fam = i >= L ? 1 : 0;
+        double nh[3];
+        const double len = pm_normal(x, fam, (int)((long long)lo + (i - fam * L)), nh);
+        const bool lok = ok && len > 0 && finite3(nh);
+        const double a0 = fabs(nh[0]), a1 = fabs(nh[1]), a2 = fabs(nh[2]);
+        const double big = (a0 >= a1 && a0 >= a2) ? nh[0] : (a1 >= a2 ? nh[1] : nh[2]);
+        if (big < 0) { nh[0] = -nh[0]; nh[1] = -nh[1]; nh[2] = -nh[2]; }
+        double *P = o_P + 4 * (size_t)i;
+        P[0] = lok ? nh[0] : 0.0; P[1] = lok ? nh[1] : 0.0; P[2] = lok ? nh[2] : 0.0;
+        P[3] = lok ? -((nh[0] * x[0] + nh[1] * x[1]) + nh[2] * x[2]) : 0.0;
+        o_status[i] = lok ? CPE_ST_OK : CPE_ST_FEW_POINTS;
+    }
+    if (lane == 0) {
+        const int kept = info[4] + info[5];
+        o_centre[0] = ok ? x[0] : 0.0; o_centre[1] = ok ? x[1] : 0.0; o_centre[2] = ok ? x[2] : 0.0;
+        o_centre[3] = ok && kept > 0 ? sqrt(fmax(model[15], 0.0) / (double)kept) : 0.0;
+        o_cstatus[0] = ok ? CPE_ST_OK : CPE_ST_FEW_POINTS;
+    }
+}
 }  // namespace
 
 extern "C" int32_t cpe_fit_plane_batch(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n,
@@ -2948,5 +3436,53 @@ extern "C" int32_t cpe_table_triangulate_batch(const double *xy, const int32_t *
     CPE_KLAUNCH(k_table_triangulate, dim3(n), dim3(64), 0, (hipStream_t)stream, xy, id, cnt, K, Tc, P, line_status, lo, hi, p.swap,
                 p.need_both, p.min_sin * p.min_sin, p.max_res, X, idx, res, src, m, counts, stats);
     CPE_CHECK_LAUNCH("k_table_triangulate");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_fit_projector_model(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n, const uint8_t *use,
+                                           const int32_t *frame_ok, int32_t lo, int32_t hi, const CpeProjectorModelParams *params,
+                                           const double *x0, double *model, int32_t *info, double *moments, int32_t *count,
+                                           int32_t *frames, uint8_t *inlier_mask, int32_t *frame_counts, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_fit_projector_model: n < 0");
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_fit_projector_model: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    CpeProjectorModelParams p = {0.0, 4, 100, 1e-4, 1e-9, 1e-9};
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.max_rounds >= 0 && p.max_rounds <= CPE_PLANEFIT_MAX_ROUNDS && !(p.tau != p.tau) && p.min_spread >= 0 && p.tolx >= 0 &&
+                      p.tolf >= 0 && p.maxiter >= 0,
+                  "cpe_fit_projector_model: bad CpeProjectorModelParams (max_rounds 0..%d, tau not NaN, min_spread, tolx, tolf, maxiter >= 0)",
+                  CPE_PLANEFIT_MAX_ROUNDS);
+    CPE_CHECK_ARG((n == 0 || (X && idx && cnt && inlier_mask && frame_counts)) && model && info && moments && count && frames,
+                  "cpe_fit_projector_model: null pointer");
+    const int L = hi - lo + 1;
+    const int rounds = p.tau > 0 ? p.max_rounds : 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (n > 0) CPE_CHECK_HIP(hipMemsetAsync(inlier_mask, 0, (size_t)2 * n * CPE_MAXP, s));
+    CPE_LAUNCH_BEGIN();
+    // every round is enqueued; a round's kernels return at once when the loop has ended (info[7])
+    for (int r = 0; r <= rounds; r++) {
+        CPE_KLAUNCH(k_pm_moments, dim3(2 * L), dim3(64), 0, s, X, idx, cnt, n, use, frame_ok, lo, L, r, p.tau, (const double *)model, info,
+                    moments, count, frames, inlier_mask);
+        CPE_CHECK_LAUNCH("k_pm_moments");
+        CPE_KLAUNCH(k_pm_solve, dim3(1), dim3(64), 0, s, (const double *)moments, (const int *)frames, lo, L, r, p.min_spread, p.tolx, p.tolf,
+                    p.maxiter, x0, model, info);
+        CPE_CHECK_LAUNCH("k_pm_solve");
+    }
+    CPE_KLAUNCH(k_pm_finish, dim3(n + 1), dim3(64), 0, s, X, idx, cnt, n, use, frame_ok, lo, L, (const double *)model, info, moments,
+                (const uint8_t *)inlier_mask, frame_counts);
+    CPE_CHECK_LAUNCH("k_pm_finish");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_projector_model_table(const double *model, const int32_t *info, int32_t lo, int32_t hi, double *P, int32_t *status,
+                                             double *centre, int32_t *centre_status, void *stream)
+{
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_projector_model_table: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    CPE_CHECK_ARG(model && info && P && status && centre && centre_status, "cpe_projector_model_table: null pointer");
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_pm_table, dim3(1), dim3(64), 0, (hipStream_t)stream, model, info, lo, hi - lo + 1, P, status, centre, centre_status);
+    CPE_CHECK_LAUNCH("k_pm_table");
     return CPE_OK;
 }

@@ -108,8 +108,40 @@ def _run_pairs(names, paths, camera_json, dev, chunk, make_fits, make_pipeline, 
     return recs, fits
 
 
+def _fit_projector(fits, frame_ok, projector, family0, use=None, table_path=None):
+    """the projector model of an experiment's own stereo points: fit.fit_projector_model over the kept frames with lo, hi the
+    range of the indices they hold, and its table for -N..N, N the largest |index| seen (or projector['lo'], ['hi']): also the
+    lines no frame showed.  projector: a dict of fit.fit_projector_model keywords beside lo, hi.
+    -> dict(fit, model (fit.ProjectorModel), laser_table) or None (a warning says why), and the list of the frames where at
+    least half of one family's residuals were trimmed: frames numbered off by a line"""
+    kw = dict(projector)
+    t_lo, t_hi = kw.pop('lo', None), kw.pop('hi', None)
+    used = (torch.arange(fit.MAXP, device=frame_ok.device)[None, :] < fits['m'][:, None]) & (frame_ok != 0)[:, None]
+    if use is not None:
+        used = used & (use != 0)
+    big = torch.iinfo(torch.int32).max
+    lo, hi = torch.stack([torch.where(used[..., None], fits['idx'], big).amin(), torch.where(used[..., None], fits['idx'], -big).amax()]).cpu().tolist()
+    if lo > hi:
+        warnings.warn('no fitted frame: no projector model')
+        return None, []
+    if hi - lo + 1 > _lib.MAXL:
+        warnings.warn(f'grid indices {lo}..{hi} span more than {_lib.MAXL} values: no projector model')
+        return None, []
+    out = fit.fit_projector_model(fits['pts3'], fits['idx'], fits['m'], lo, hi, use=use, frame_ok=frame_ok, **kw)
+    model = fit.ProjectorModel.from_fit(out, family0)
+    if model.status != 0:
+        warnings.warn('the projector model was not fitted (fewer than 2 usable lines in a family, or planes that give no centre)')
+    half = min(max(abs(lo), abs(hi)), (_lib.MAXL - 1) // 2)
+    table = model.table(-half if t_lo is None else t_lo, half if t_hi is None else t_hi)
+    if table_path is not None:
+        table.save(table_path)
+    fc = out['frame_counts'].cpu().numpy()
+    shifted = [i for i in range(len(fc)) if any(fc[i, 2 * k + 1] > 0 and 2 * fc[i, 2 * k + 1] >= fc[i, 2 * k] + fc[i, 2 * k + 1] for k in range(2))]
+    return dict(fit=out, model=model, laser_table=table), shifted
+
+
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
-                   frame_angles=False, match_offset=None, laser_table=None, source='stereo'):
+                   frame_angles=False, match_offset=None, laser_table=None, source='stereo', projector=None, table_path=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
@@ -138,6 +170,14 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     status is 0 in the records, and the dict gains tri_counts i32 [F,4] and tri_stats f64 [F,2] (fit.table_triangulate_batch's
     counts and stats).  The table's gates keep their defaults here; FramePipeline(table=...) sets them.
 
+    projector: None, or a dict of fit.fit_projector_model keywords ({} = its defaults; build-defined): the projector's model
+    (two pencils of planes through one centre) is fitted to the experiment's own stereo points and indices -- after the index
+    shift of match_offset where that is on -- over the frames the multi-frame fit would keep; no boards are needed.  The dict
+    gains projector = dict(fit, model, laser_table) (the call's outputs, the fit.ProjectorModel, and its table for the lines
+    -N..N, N the largest |index| seen, family0 'col'; None when there is nothing to fit) and projector_shifted: the frames where at
+    least half of one family's residuals fell outside the band tau, i.e. frames numbered one line off.  table_path: the table is
+    saved there (LaserTable.save).  source must be 'stereo'.
+
     frame_angles=True (build-defined, nothing like it in the reference): with a multi-frame result, the good frames go through
     multiframe.estimate_frame_angles_gpu with T_cam_agv, a self-check of the calibration in degrees.  The dict gains
     angles_est (F x 2, rad; NaN for a skipped or failed frame), angles_status (F; the solver's status, -1 for a frame that was
@@ -147,7 +187,15 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     dev = torch.device(device)
     if isinstance(laser_table, (str, os.PathLike)):
         laser_table = fit.LaserTable.load(laser_table, dev)
-    recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, lambda F: pipeline.alloc_fits(F, dev, source=source),
+    if projector is not None and source != 'stereo':
+        raise ValueError("projector= fits the model to stereo points: source must be 'stereo'")
+
+    def make_fits(F):
+        f = pipeline.alloc_fits(F, dev, source=source)
+        if projector is not None:        # the model needs the points' indices, which the selector returns beside the points
+            f['idx'] = torch.zeros((F, fit.MAXP, 2), dtype=torch.int32, device=dev)
+        return f
+    recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, make_fits,
                             lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=c, device=dev, match=match_offset,
                                                                    source=source, laser_table=laser_table), source)
     F = len(names)
@@ -167,6 +215,12 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
         res.update(offset=fits['offset'], match_score=fits['match_score'], match_flags=fits['match_flags'])
     if source != 'stereo':
         res.update(tri_counts=fits['counts'], tri_stats=fits['stats'])
+    if projector is not None:
+        frame_ok = (d_fit == 0) & (d_l == 0) & (d_r == 0)
+        if match_offset is not None:
+            frame_ok = frame_ok & (d_weak == 0)
+        res['projector'], res['projector_shifted'] = _fit_projector(fits, frame_ok.to(torch.int32), projector, 'col', table_path=table_path)
+        fits = {k: v for k, v in fits.items() if k != 'idx'}
     if mat_path is not None:
         api.save_mat(mat_path, fits=fits, names=names)
     if multi_frame in ('gpu', 'lm'):
@@ -217,7 +271,7 @@ PLANE_CENTRE_RMS_WARN = 1.0     # mm
 
 
 def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_rounds=4, min_spread=1e-4, device='cuda:0', chunk=32,
-                         table_path=None):
+                         table_path=None, projector=None):
     """BUILD-DEFINED (the reference stops at the planar detector): a folder of `<name>L.png` / `<name>R.png` pairs of a flat board
     in several poses -> the board's plane and pose in every frame, and the projector's laser-plane table with its centre.
 
@@ -243,7 +297,12 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
             laser_table = that table as a fit.LaserTable with family0='row' (the planar detector writes its ids as (row, col)), what
             FramePipeline(source='left', laser_table=...) and run_experiment(laser_table=...) read; None without a table.  It is
             saved to table_path (.npz) when that is given.  A table that is not `consistent` is returned and saved all the same,
-            consistent = the table exists, has a centre, and its planes meet there within PLANE_CENTRE_RMS_WARN)"""
+            consistent = the table exists, has a centre, and its planes meet there within PLANE_CENTRE_RMS_WARN)
+
+    projector: None, or a dict of fit.fit_projector_model keywords (as run_experiment's): the projector's model is fitted to the
+    same points, masks and frames as well.  The dict gains projector and projector_shifted as in run_experiment (family0 'row');
+    laser_table and the file at table_path are then the MODEL's table, and consistent says that the model was fitted and its
+    rms is within PLANE_CENTRE_RMS_WARN.  `table` stays the free table of fit.index_planes_batch."""
     names, paths = _list_pairs(input_path)
     dev = torch.device(device)
     recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, lambda F: pipeline.alloc_fits(F, dev, 'plane'),
@@ -279,9 +338,20 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
         else:
             consistent = True
         laser_table = fit.LaserTable.from_index_planes(table, lo, hi, 'row')
-        if table_path is not None:
+        if table_path is not None and projector is None:
             laser_table.save(table_path)
-    return dict(names=names, records=recs, P=fits['P'], T=fits['T'], grid=fits['grid'], stats=fits['stats'], pts3=fits['pts3'],
+    if projector is not None:
+        pm, shifted = _fit_projector(fits, frame_ok, projector, 'row', use=fits['inlier_mask'], table_path=table_path)
+        consistent = pm is not None and pm['model'].status == 0 and pm['model'].rms <= PLANE_CENTRE_RMS_WARN
+        if pm is not None:
+            laser_table = pm['laser_table']
+            if pm['model'].status == 0 and not consistent:
+                warnings.warn(f'the projector model leaves {pm["model"].rms:.2f} mm rms (more than {PLANE_CENTRE_RMS_WARN} mm): the grid '
+                              'numbering of the two images probably disagrees, the table is not to be trusted')
+        extra = dict(projector=pm, projector_shifted=shifted)
+    else:
+        extra = {}
+    return dict(**extra, **dict(names=names, records=recs, P=fits['P'], T=fits['T'], grid=fits['grid'], stats=fits['stats'], pts3=fits['pts3'],
                 idx=fits['idx'], cnt=fits['m'], n_inliers=fits['n_inliers'], inlier_mask=fits['inlier_mask'],
                 plane_flags=fits['plane_flags'], skipped=skipped, table=table, consistent=consistent,
-                laser_table=laser_table)
+                laser_table=laser_table))

@@ -344,6 +344,115 @@ class LaserTable:
                               t('centre_status', torch.int32), str(z['family0']))
 
 
+def fit_projector_model(pts3, idx, cnt, lo, hi, use=None, frame_ok=None, tau=0.0, max_rounds=4, min_spread=1e-4, tolx=1e-9, tolf=1e-9,
+                        maxiter=100, x0=None):
+    """BUILD-DEFINED: the projector as two pencils of planes n = a_k + v b_k through one centre C, fitted to the points and
+    indices of many frames (board poses, or the cylinder experiment's own stereo points), with an optional trimming band tau
+    that drops the residuals of mis-numbered frames.  See include/cpe.h cpe_fit_projector_model.  Inputs as index_planes_batch;
+    x0 f64[15] is an optional start.
+    -> dict(model f64[16] (C, a_0, b_0, a_1, b_1, objective), info i32[8] (status, refits, LM iterations, evaluations, kept
+            residuals per family, 0, 0), moments f64[2,L,12], count, frames i32[2,L], inlier_mask u8[2,n,MAXP],
+            frame_counts i32[n,4] (kept, trimmed of family 0; kept, trimmed of family 1), lo, hi)"""
+    L = _lib.load()
+    pts3, idx, cnt, use = _point_tables('fit_projector_model', pts3, idx, cnt, use)
+    dev = pts3.device
+    n = cnt.shape[0]
+    nl = int(hi) - int(lo) + 1
+    if not 1 <= nl <= _lib.MAXL:
+        raise ValueError(f'fit_projector_model: {nl} indices in [{lo}, {hi}], must be 1..{_lib.MAXL}')
+    if frame_ok is not None:
+        if frame_ok.shape != (n,) or frame_ok.device != dev:
+            raise TypeError(f'fit_projector_model: frame_ok must hold {n} values on {dev}')
+        frame_ok = frame_ok.to(torch.int32).contiguous()
+    if x0 is not None:
+        x0 = _dev3(x0, dev, (15,))
+    # (the kernels write every slot of every output, the mask after the call's own fill: no fills here)
+    f64 = torch.empty(16 + 2 * nl * 12, dtype=torch.float64, device=dev)
+    model, moments = f64[:16], f64[16:].view(2, nl, 12)
+    i32 = torch.empty(8 + 4 * nl + 4 * n, dtype=torch.int32, device=dev)
+    info, count, frames, fc = i32[:8], i32[8:8 + 2 * nl].view(2, nl), i32[8 + 2 * nl:8 + 4 * nl].view(2, nl), i32[8 + 4 * nl:].view(n, 4)
+    mask = torch.empty((2, n, MAXP), dtype=torch.uint8, device=dev)
+    prm = _lib.CpeProjectorModelParams(float(tau), int(max_rounds), int(maxiter), float(min_spread), float(tolx), float(tolf))
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    _lib.check(L.cpe_fit_projector_model(ptr(pts3), ptr(idx), ptr(cnt), n, ptr(use), ptr(frame_ok), int(lo), int(hi), C.addressof(prm),
+                                         ptr(x0), model.data_ptr(), info.data_ptr(), moments.data_ptr(), count.data_ptr(),
+                                         frames.data_ptr(), ptr(mask), ptr(fc), _stream()), 'cpe_fit_projector_model')
+    return dict(model=model, info=info, moments=moments, count=count, frames=frames, inlier_mask=mask, frame_counts=fc, lo=int(lo),
+                hi=int(hi))
+
+
+@dataclass
+class ProjectorModel:
+    """BUILD-DEFINED: a fitted projector (fit_projector_model).  C f64[3] the centre, a, b f64[2,3]: the plane of index v of
+    family k has the normal a[k] + v b[k] and holds C (camera-1 coordinates); rms: sqrt of the mean squared residual of the fit;
+    family0 as LaserTable's; model f64[16] and info i32[8] are the call's own outputs, which table() reads."""
+    model: torch.Tensor
+    info: torch.Tensor
+    family0: str = 'col'
+
+    def __post_init__(self):
+        if self.family0 not in ('col', 'row'):
+            raise ValueError("ProjectorModel.family0 is 'col' or 'row'")
+        if tuple(self.model.shape) != (16,) or tuple(self.info.shape) != (8,):
+            raise ValueError(f'ProjectorModel: model must be [16] and info [8], got {list(self.model.shape)} and {list(self.info.shape)}')
+
+    @staticmethod
+    def from_fit(out, family0='col'):
+        """out: the dict of fit_projector_model"""
+        return ProjectorModel(out['model'], out['info'], family0)
+
+    @property
+    def status(self):
+        return int(self.info[0])
+
+    @property
+    def C(self):
+        return self.model[:3]
+
+    @property
+    def a(self):
+        return self.model[3:15].view(2, 2, 3)[:, 0]
+
+    @property
+    def b(self):
+        return self.model[3:15].view(2, 2, 3)[:, 1]
+
+    @property
+    def rms(self):
+        kept = int(self.info[4]) + int(self.info[5])
+        return float(self.model[15].clamp(min=0) / kept) ** 0.5 if kept > 0 else 0.0
+
+    def table(self, lo, hi):
+        """the laser-plane table of the indices lo..hi, any range of at most MAXL: also indices no frame showed"""
+        L = _lib.load()
+        nl = int(hi) - int(lo) + 1
+        if not 1 <= nl <= _lib.MAXL:
+            raise ValueError(f'ProjectorModel.table: {nl} indices in [{lo}, {hi}], must be 1..{_lib.MAXL}')
+        dev = self.model.device
+        model, info = self.model.to(torch.float64).contiguous(), self.info.to(device=dev, dtype=torch.int32).contiguous()
+        f64 = torch.empty(2 * nl * 4 + 4, dtype=torch.float64, device=dev)
+        i32 = torch.empty(2 * nl + 1, dtype=torch.int32, device=dev)
+        P, centre, st, cst = f64[:8 * nl].view(2, nl, 4), f64[8 * nl:], i32[:2 * nl].view(2, nl), i32[2 * nl:]
+        _lib.check(L.cpe_projector_model_table(model.data_ptr(), info.data_ptr(), int(lo), int(hi), P.data_ptr(), st.data_ptr(),
+                                               centre.data_ptr(), cst.data_ptr(), _stream()), 'cpe_projector_model_table')
+        return LaserTable(P, st, lo, hi, centre, cst, self.family0)
+
+    def to(self, device):
+        return ProjectorModel(self.model.to(device), self.info.to(device), self.family0)
+
+    def save(self, path):
+        """one .npz file (numpy appends the suffix to a path without it)"""
+        import numpy as np
+        np.savez(path, model=self.model.cpu().numpy(), info=self.info.cpu().numpy(), family0=np.array(self.family0))
+
+    @staticmethod
+    def load(path, device='cpu'):
+        import numpy as np
+        with np.load(path, allow_pickle=False) as z:
+            return ProjectorModel(torch.from_numpy(np.ascontiguousarray(z['model'])).to(torch.float64).to(device),
+                                  torch.from_numpy(np.ascontiguousarray(z['info'])).to(torch.int32).to(device), str(z['family0']))
+
+
 def table_triangulate_batch(gp: GridTables, K, Tc, table: LaserTable, need_both=False, min_sin=0.01, max_res=0.0, ids='col_row'):
     """BUILD-DEFINED: 3-D points of one camera's grid tables from the laser-plane table, see include/cpe.h
     cpe_table_triangulate_batch.  K: that camera's intrinsics; Tc: camera-1 coordinates -> that camera's (None = camera 1, T21

@@ -79,6 +79,9 @@ _SIGS = {
                                [C.c_void_p] * 8),
     'cpe_table_triangulate_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] +
                                     [C.c_void_p] * 9),
+    'cpe_fit_projector_model': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
+                                [C.c_void_p] * 10),
+    'cpe_projector_model_table': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
     'cpe_undistort_map': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_remap_bilinear_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_undistort_map_matlab': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -136,6 +139,11 @@ class CpeMatchParams(C.Structure):
 
 class CpePlaneFitParams(C.Structure):
     _fields_ = [('tau', C.c_double), ('max_rounds', C.c_int32), ('reserved', C.c_int32)]
+
+
+class CpeProjectorModelParams(C.Structure):
+    _fields_ = [('tau', C.c_double), ('max_rounds', C.c_int32), ('maxiter', C.c_int32), ('min_spread', C.c_double),
+                ('tolx', C.c_double), ('tolf', C.c_double)]
 
 
 class CpeTableTriParams(C.Structure):

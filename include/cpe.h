@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 118   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 119   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -53,7 +53,7 @@ extern "C" {
                              cpe_pose_T2vec_batch; 113: cpe_multi_frame_fit_lm_batch; 114: cpe_agv_chain_batch,
                              cpe_frame_angles_lm_batch; 115: cpe_debug_region_hull; 116: cpe_match_offset_batch,
                              cpe_match_offset_workspace_bytes; 117: cpe_fit_plane_batch, cpe_index_planes_batch;
-                             118: cpe_table_triangulate_batch) */
+                             118: cpe_table_triangulate_batch; 119: cpe_fit_projector_model, cpe_projector_model_table) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -650,6 +650,72 @@ CPE_API int32_t cpe_index_planes_batch(const double *X, const int32_t *idx, cons
                                        const int32_t *frame_ok, int32_t lo, int32_t hi, double min_spread, double *P,
                                        double *stats, int32_t *count, int32_t *frames, int32_t *status, double *centre,
                                        int32_t *centre_status, void *stream);
+
+/* BUILD-DEFINED: the projector as a model, fitted to the points of many frames -- board poses, or the stereo points of the
+ * cylinder experiment itself.  A diffractive grid projector sends out two pencils of planes through one centre C: the plane of
+ * index v of family k has the normal n = a_k + v b_k and holds C.  The model is x = C[3], a_0[3], b_0[3], a_1[3], b_1[3] (15
+ * doubles, |a_k| = 1: 13 degrees of freedom in place of the 2 L 3 of cpe_index_planes_batch), so it also gives planes for
+ * indices that no frame showed, and a frame whose lines are numbered one off cannot pull a line's plane away.
+ *   X, idx, cnt, use, frame_ok, lo, hi: as cpe_index_planes_batch (L = hi - lo + 1 in 1..CPE_MAXL, otherwise CPE_ERR_ARG);
+ *   params NULL = the defaults of CpeProjectorModelParams; x0 f64[15] DEVICE memory or NULL: the start of round 0 (|a_k| = 1).
+ * Rule (the order is the contract):
+ *   1. a point is usable when its frame is kept, its slot is below the clamped count, `use` is non-zero and its coordinates are
+ *      finite.  It gives one residual per family k whose index v = idx[k] lies in [lo, hi]:  r = n.(X - C) / |n|;
+ *   2. moments pass, one wavefront per (family, index): over the kept residuals of the line the count N, the centroid m, then in
+ *      a second pass the centred scatter S = sum (X - m)(X - m)'.  Round 0 keeps every residual of step 1; from round 1 on a
+ *      residual is kept when |r| < tau under the model of the round before.  sum r^2 = nh'(S + N (m - C)(m - C)') nh, and J'J,
+ *      J'r follow from N, m, S as well: the solve never sees a point;
+ *   3. a line is usable for the start when N >= 3, >= 2 frames contributed, lambda_max > 0 and lambda_mid / lambda_max >=
+ *      min_spread of S; its free plane has the normal n_l = the first eigenvector of S.  Fewer than 2 usable lines in either
+ *      family: CPE_ST_FEW_POINTS (every round checks this);
+ *   4. start of round 0 (x0 NULL): C solves (sum n_l n_l') C = sum n_l (n_l.m_l) over the usable lines of both families by
+ *      elimination (a zero pivot or a non-finite C: CPE_ST_FEW_POINTS).  Per family: u = the first eigenvector of sum n_l n_l';
+ *      e1 = the normal of the usable line nearest to v = 0 (the lower index on a tie), its largest-magnitude component positive,
+ *      with its part along u removed, normalised; e2 = u x e1; least squares (n_l.e2) / (n_l.e1) ~ alpha + beta v over the usable
+ *      lines, v centred; a = (e1 + alpha e2) / |e1 + alpha e2|, b = beta e2 / |e1 + alpha e2|.  A later round starts from the
+ *      model of the round before;
+ *   5. Levenberg-Marquardt on sum r^2 over all kept residuals (the loop of the cylinder fit: lambda 1e-3, x 10 / 10, at most 12
+ *      trials per iteration and min(maxiter, 200) iterations, stop on a step <= tolx that gains <= tolf 1e-3 (1 + f)); a step is
+ *      dC, then per family two coordinates in the tangent plane of a_k (basis: the coordinate axis of the smallest |a_i|, the
+ *      first of them, made perpendicular to a_k and normalised, and a_k x that) and db_k; a_k is brought back to length 1;
+ *   6. tau > 0 and max_rounds > 0: round r = 1, 2, ... builds the mask of step 2 under the last model; when no byte of it
+ *      differs from the mask the last model was fitted to, or after max_rounds refits, the loop ends; otherwise the model is
+ *      refitted to the new moments.  All rounds are enqueued at once; the kernels of a round return at once when the loop has
+ *      ended.  No host synchronisation, no floating-point atomics; two calls on the same inputs give the same bits;
+ *   7. a non-finite start, objective or result: CPE_ST_FEW_POINTS.  With that status model is zero (moments, count, frames,
+ *      inlier_mask and frame_counts describe the last moments pass all the same).  So CPE_ST_OK implies finite outputs.
+ * Outputs:
+ *   model f64[16]            x, then the objective sum r^2 over the kept residuals
+ *   info i32[8]              status, refits done, LM iterations and objective evaluations over all rounds, kept residuals of
+ *                            family 0 and of family 1, 0, 0 (the last two carry the loop's flags while the call runs)
+ *   moments f64[2,L,12]      N, m[3], S = xx xy xz yy yz zz, the line's rms sqrt(sum r^2 / N) under the final model (0 for an empty
+ *                            line or a failed fit), 0
+ *   count, frames i32[2,L]   kept residuals of the line, kept frames that contributed one
+ *   inlier_mask u8[2,n,CPE_MAXP]   plane k: 1 where the point's residual of family k is kept, 0 elsewhere and past the count
+ *   frame_counts i32[n,4]    per frame: kept and trimmed residuals of family 0, kept and trimmed residuals of family 1
+ * cnt is clamped to [0, CPE_MAXP]; slots past it are never read; n = 0 is allowed (CPE_ST_FEW_POINTS).
+ * Limits: the spacing of a pencil is linear in tan(theta) -- no distortion term for real gratings; one tau for both families;
+ * a frame that is mis-numbered in both images alike is trimmed, not re-numbered. */
+typedef struct CpeProjectorModelParams {
+    double tau;           /* band |r| < tau of the trimming rounds, the unit of the points; <= 0: no trimming (default) */
+    int32_t max_rounds;   /* refits at the most, 0..CPE_PLANEFIT_MAX_ROUNDS; default 4 */
+    int32_t maxiter;      /* LM iterations per round at the most (200 at the most); default 100 */
+    double min_spread;    /* a line's lambda_mid / lambda_max for the start; default 1e-4 */
+    double tolx, tolf;    /* LM's stop; default 1e-9 each */
+} CpeProjectorModelParams;
+CPE_API int32_t cpe_fit_projector_model(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n, const uint8_t *use,
+                                        const int32_t *frame_ok, int32_t lo, int32_t hi, const CpeProjectorModelParams *params,
+                                        const double *x0, double *model, int32_t *info, double *moments, int32_t *count,
+                                        int32_t *frames, uint8_t *inlier_mask, int32_t *frame_counts, void *stream);
+
+/* The laser-plane table of a model for ANY index range lo..hi (L in 1..CPE_MAXL, otherwise CPE_ERR_ARG), in the layout
+ * cpe_table_triangulate_batch reads.  model, info: what cpe_fit_projector_model wrote (device memory).
+ *   P f64[2,L,4] = [nh, -nh.C], nh = (a_k + v b_k) / |a_k + v b_k| with its largest-magnitude component (the first of them)
+ *   positive, the sign rule of cpe_index_planes_batch; status i32[2,L] CPE_ST_OK; centre f64[4] = C, sqrt(objective / kept
+ *   residuals); centre_status i32[1].  A model whose status is not CPE_ST_OK, or a line with a zero or non-finite normal, gives
+ *   CPE_ST_FEW_POINTS and zeros. */
+CPE_API int32_t cpe_projector_model_table(const double *model, const int32_t *info, int32_t lo, int32_t hi, double *P, int32_t *status,
+                                          double *centre, int32_t *centre_status, void *stream);
 
 /* BUILD-DEFINED: 3-D points from ONE camera and the laser-plane table.  A grid point with the indices (id[0], id[1]) lies on the
  * plane of light of either index, so it is the cut of its pixel ray with those planes: no stereo partner and no index matching.

@@ -28,8 +28,8 @@ sys.path.insert(0, ROOT)
 RADIUS = 45.0
 
 
-def make_tables(n, points, dev, seed=0):
-    """-> X f64[n,MAXP,3], idx i32[n,MAXP,2], cnt i32[n] on dev"""
+def make_tables(n, points, dev, seed=0, lift=True):
+    """-> X f64[n,MAXP,3], idx i32[n,MAXP,2], cnt i32[n] on dev; lift=False leaves every point on its board"""
     import numpy as np
     import torch
     from cpe_amd import fit, synth
@@ -48,7 +48,8 @@ def make_tables(n, points, dev, seed=0):
         c = np.array([27.0 + rng.uniform(-10, 10), rng.uniform(-10, 10), rng.uniform(330, 400)])
         keep = np.sort(rng.permutation(len(ids))[:points])
         X = Op + (((c - Op) @ nrm) / (d[keep] @ nrm))[:, None] * d[keep]
-        X[::20] += (rng.uniform(5, 40, len(X[::20])) * rng.choice([-1, 1], len(X[::20])))[:, None] * nrm
+        if lift:
+            X[::20] += (rng.uniform(5, 40, len(X[::20])) * rng.choice([-1, 1], len(X[::20])))[:, None] * nrm
         a = X @ K1.T
         b = (X @ T21[:3, :3].T + T21[:3, 3]) @ K2.T
         m = len(keep)
