@@ -3375,6 +3375,114 @@ __global__ __launch_bounds__(64) void k_pm_table(const double *__restrict__ mode
         o_cstatus[0] = ok ? CPE_ST_OK : CPE_ST_FEW_POINTS;
     }
 }
+
+// ------------------------------------------------------------------------------------------ index shift of stereo frames
+// BUILD-DEFINED (include/cpe.h cpe_index_shift_batch, whose numbered rule this follows): a stereo point's position does not
+// depend on its index, so the points of a frame and a table that is right for most frames give the frame's shift: per index
+// component, the d for which the most points lie on the plane of index + d.  One wavefront per (frame, component), lane l takes
+// points l, l + 64, ...  The component's family of the table (at most 256 planes and statuses, 9 KB) is copied to LDS first:
+// a point reads up to 17 neighbouring planes, so a frame of 250 points reads 8 times the table.  The candidate counters are a
+// register array behind loops unrolled over the compile-time 17 candidates and predicated on |d| <= win.
+constexpr int SHIFT_W = CPE_SHIFT_MAX_WIN, SHIFT_NC = 2 * CPE_SHIFT_MAX_WIN + 1;
+
+__global__ __launch_bounds__(64) void k_index_shift(const double *__restrict__ X, const int *__restrict__ idx, const int *__restrict__ cnt,
+                                                    const uint8_t *__restrict__ use, const double *__restrict__ P,
+                                                    const int *__restrict__ line_status, int lo, int hi, int win0, int win1, double tau,
+                                                    int min_score, int swap, int *__restrict__ o_shift, int *__restrict__ o_score,
+                                                    int *__restrict__ o_scores, double *__restrict__ o_rms, int *__restrict__ o_flags,
+                                                    int *__restrict__ o_idx)
+{
+    __shared__ double sP[CPE_MAXL * 4];
+    __shared__ int sS[CPE_MAXL];
+    const int f = blockIdx.x >> 1, c = blockIdx.x & 1, lane = threadIdx.x;
+    const int n = min(max(cnt[f], 0), MAXP);
+    const int L = hi - lo + 1;                     // 1..CPE_MAXL, checked by the host
+    const int win = c ? win1 : win0;               // 0..SHIFT_W, checked by the host
+    const size_t base = (size_t)f * MAXP;
+    {
+        const size_t fam = (size_t)((c ^ swap) * L);
+        for (int i = lane; i < 4 * L; i += 64) sP[i] = P[fam * 4 + i];
+        for (int i = lane; i < L; i += 64) sS[i] = line_status[fam + i];
+    }
+    __syncthreads();
+    // rel = idx - lo of a point that can count at all lies in [-win, L - 1 + win]: tested in 64 bits, before any addition
+    const long long rlo = -(long long)win, rhi = (long long)(L - 1 + win);
+    int sc[SHIFT_NC];
+#pragma unroll
+    for (int j = 0; j < SHIFT_NC; j++) sc[j] = 0;
+    int usable = 0;
+    for (int k = lane; k < n; k += 64) {
+        if (use && use[base + k] == 0) continue;
+        if (!finite3(X + (base + k) * 3)) continue;
+        usable++;
+        const long long rl = (long long)idx[(base + k) * 2 + c] - (long long)lo;
+        if (rl < rlo || rl > rhi) continue;
+        const int rel = (int)rl;
+        const double x = X[(base + k) * 3], y = X[(base + k) * 3 + 1], z = X[(base + k) * 3 + 2];
+#pragma unroll
+        for (int j = 0; j < SHIFT_NC; j++) {
+            const int r = rel + (j - SHIFT_W);
+            if (abs(j - SHIFT_W) <= win && r >= 0 && r < L && sS[r] == CPE_ST_OK) {
+                const double e = ((sP[4 * r] * x + sP[4 * r + 1] * y) + sP[4 * r + 2] * z) + sP[4 * r + 3];
+                if (fabs(e) < tau) sc[j]++;
+            }
+        }
+    }
+    usable = wave_sum_i(usable);
+#pragma unroll
+    for (int j = 0; j < SHIFT_NC; j++) sc[j] = wave_sum_i(sc[j]);
+    // winner: the smallest key (-score, |d|, d); then the second-largest value among the candidates
+    int best = -1, wd = 0;
+#pragma unroll
+    for (int j = 0; j < SHIFT_NC; j++) {
+        const int d = j - SHIFT_W, a = abs(d);
+        if (a <= win && (sc[j] > best || (sc[j] == best && (a < abs(wd) || (a == abs(wd) && d < wd))))) { best = sc[j]; wd = d; }
+    }
+    int second = 0, at0 = 0, mine = 0;
+#pragma unroll
+    for (int j = 0; j < SHIFT_NC; j++) {
+        const int d = j - SHIFT_W;
+        if (abs(d) <= win && d != wd) second = max(second, sc[j]);
+        if (d == 0) at0 = sc[j];
+        if (lane == j) mine = sc[j];
+    }
+    int flags = 0, d_app = wd;
+    if (!(best >= min_score && best >= 2 * second)) { flags |= CPE_SHIFT_FLAG_WEAK; d_app = 0; }
+    if (win > 0 && abs(wd) == win) flags |= CPE_SHIFT_FLAG_EDGE;
+    if (d_app != 0) flags |= CPE_SHIFT_FLAG_SHIFTED;
+    if (o_scores && lane >= SHIFT_W - win && lane <= SHIFT_W + win)
+        o_scores[(size_t)f * (2 * win0 + 1 + 2 * win1 + 1) + (c ? 2 * win0 + 1 : 0) + (lane - (SHIFT_W - win))] = mine;
+    // second pass: the counted points' squared residuals at the applied shift and at d = 0; idx + shift on the way
+    double sa = 0.0, s0 = 0.0;
+    int ca = 0, c0 = 0;
+    for (int k = lane; k < n; k += 64) {
+        const int v = idx[(base + k) * 2 + c];
+        o_idx[(base + k) * 2 + c] = (int)((unsigned)v + (unsigned)d_app);       // (a garbage index wraps, it does not overflow)
+        if (use && use[base + k] == 0) continue;
+        if (!finite3(X + (base + k) * 3)) continue;
+        const long long rl = (long long)v - (long long)lo;
+        if (rl < rlo || rl > rhi) continue;
+        const double x = X[(base + k) * 3], y = X[(base + k) * 3 + 1], z = X[(base + k) * 3 + 2];
+        const int ra = (int)rl + d_app, r0 = (int)rl;
+        if (ra >= 0 && ra < L && sS[ra] == CPE_ST_OK) {
+            const double e = ((sP[4 * ra] * x + sP[4 * ra + 1] * y) + sP[4 * ra + 2] * z) + sP[4 * ra + 3];
+            if (fabs(e) < tau) { sa = sa + e * e; ca++; }
+        }
+        if (r0 >= 0 && r0 < L && sS[r0] == CPE_ST_OK) {
+            const double e = ((sP[4 * r0] * x + sP[4 * r0 + 1] * y) + sP[4 * r0 + 2] * z) + sP[4 * r0 + 3];
+            if (fabs(e) < tau) { s0 = s0 + e * e; c0++; }
+        }
+    }
+    sa = wave_sum(sa); s0 = wave_sum(s0); ca = wave_sum_i(ca); c0 = wave_sum_i(c0);
+    if (lane == 0) {
+        const size_t o = (size_t)f * 2 + c;
+        o_shift[o] = d_app;
+        o_score[4 * o] = best; o_score[4 * o + 1] = second; o_score[4 * o + 2] = at0; o_score[4 * o + 3] = usable;
+        o_rms[2 * o] = ca > 0 ? sqrt(sa / (double)ca) : 0.0;
+        o_rms[2 * o + 1] = c0 > 0 ? sqrt(s0 / (double)c0) : 0.0;
+        o_flags[o] = flags;
+    }
+}
 }  // namespace
 
 extern "C" int32_t cpe_fit_plane_batch(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n,
@@ -3484,5 +3592,30 @@ extern "C" int32_t cpe_projector_model_table(const double *model, const int32_t 
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_pm_table, dim3(1), dim3(64), 0, (hipStream_t)stream, model, info, lo, hi - lo + 1, P, status, centre, centre_status);
     CPE_CHECK_LAUNCH("k_pm_table");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_index_shift_batch(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n, const uint8_t *use,
+                                         const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
+                                         const CpeIndexShiftParams *params, int32_t *shift, int32_t *score, int32_t *scores, double *rms,
+                                         int32_t *flags, int32_t *idx_out, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_index_shift_batch: n < 0");
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_index_shift_batch: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    CpeIndexShiftParams p = {{4, 4}, 1.0, 8, 0};
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.win[0] >= 0 && p.win[0] <= CPE_SHIFT_MAX_WIN && p.win[1] >= 0 && p.win[1] <= CPE_SHIFT_MAX_WIN,
+                  "cpe_index_shift_batch: window must be 0..%d for both components", CPE_SHIFT_MAX_WIN);
+    CPE_CHECK_ARG(p.tau > 0 && p.min_score >= 0 && (p.swap == 0 || p.swap == 1),
+                  "cpe_index_shift_batch: bad CpeIndexShiftParams (tau > 0, min_score >= 0, swap 0 or 1)");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(X && idx && cnt && P && line_status && shift && score && rms && flags && idx_out, "cpe_index_shift_batch: null pointer");
+    CPE_CHECK_ARG(idx_out != idx, "cpe_index_shift_batch: idx_out may not be idx");
+    CPE_CHECK_ARG((long long)n * 2 <= INT_MAX, "cpe_index_shift_batch: 2 n exceeds 2^31 - 1");
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_index_shift, dim3(2 * n), dim3(64), 0, (hipStream_t)stream, X, idx, cnt, use, P, line_status, lo, hi, p.win[0], p.win[1],
+                p.tau, p.min_score, p.swap, shift, score, scores, rms, flags, idx_out);
+    CPE_CHECK_LAUNCH("k_index_shift");
     return CPE_OK;
 }

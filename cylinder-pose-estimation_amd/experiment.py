@@ -111,11 +111,18 @@ def _run_pairs(names, paths, camera_json, dev, chunk, make_fits, make_pipeline, 
 def _fit_projector(fits, frame_ok, projector, family0, use=None, table_path=None):
     """the projector model of an experiment's own stereo points: fit.fit_projector_model over the kept frames with lo, hi the
     range of the indices they hold, and its table for -N..N, N the largest |index| seen (or projector['lo'], ['hi']): also the
-    lines no frame showed.  projector: a dict of fit.fit_projector_model keywords beside lo, hi.
-    -> dict(fit, model (fit.ProjectorModel), laser_table) or None (a warning says why), and the list of the frames where at
-    least half of one family's residuals were trimmed: frames numbered off by a line"""
+    lines no frame showed.  projector: a dict of fit.fit_projector_model keywords beside lo, hi and renumber.
+    renumber: None, or a dict of win, tau, min_score ({} = the defaults of fit.fit_projector_model_renumbered, which runs in
+    place of the single fit): the frames are re-numbered against the first model's table and fitted again over the range
+    widened by max(win); fit, model, laser_table and the list of trimmed frames then describe the refit, N is taken from the
+    widened range, and the dict gains first (the first fit's dict) and shift (fit.index_shift_batch's dict).
+    -> dict(fit, model (fit.ProjectorModel), laser_table) or None (a warning says why), the list of the frames where at
+    least half of one family's residuals were trimmed: frames numbered off by a line, and with renumber the list of (frame, d0,
+    d1) of the kept frames that got a non-zero shift (None without renumber)"""
     kw = dict(projector)
     t_lo, t_hi = kw.pop('lo', None), kw.pop('hi', None)
+    ren = kw.pop('renumber', None)
+    none = (None, [], None if ren is None else [])
     used = (torch.arange(fit.MAXP, device=frame_ok.device)[None, :] < fits['m'][:, None]) & (frame_ok != 0)[:, None]
     if use is not None:
         used = used & (use != 0)
@@ -123,11 +130,24 @@ def _fit_projector(fits, frame_ok, projector, family0, use=None, table_path=None
     lo, hi = torch.stack([torch.where(used[..., None], fits['idx'], big).amin(), torch.where(used[..., None], fits['idx'], -big).amax()]).cpu().tolist()
     if lo > hi:
         warnings.warn('no fitted frame: no projector model')
-        return None, []
+        return none
     if hi - lo + 1 > _lib.MAXL:
         warnings.warn(f'grid indices {lo}..{hi} span more than {_lib.MAXL} values: no projector model')
-        return None, []
-    out = fit.fit_projector_model(fits['pts3'], fits['idx'], fits['m'], lo, hi, use=use, frame_ok=frame_ok, **kw)
+        return none
+    extra, renumbered = {}, None
+    if ren is None:
+        out = fit.fit_projector_model(fits['pts3'], fits['idx'], fits['m'], lo, hi, use=use, frame_ok=frame_ok, **kw)
+    else:
+        unknown = set(ren) - {'win', 'tau', 'min_score'}
+        if unknown:
+            raise TypeError(f"projector['renumber'] holds win, tau, min_score; got {sorted(unknown)}")
+        rn = fit.fit_projector_model_renumbered(fits['pts3'], fits['idx'], fits['m'], lo, hi, use=use, frame_ok=frame_ok,
+                                                win=ren.get('win', (4, 4)), shift_tau=ren.get('tau'),
+                                                shift_min_score=ren.get('min_score', 8), family0=family0, **kw)
+        out, lo, hi = rn['fit'], rn['lo'], rn['hi']
+        extra = dict(first=rn['first'], shift=rn['shift'])
+        sh = torch.cat([rn['shift']['shift'], frame_ok.to(torch.int32)[:, None]], 1).cpu().tolist()
+        renumbered = [(i, d0, d1) for i, (d0, d1, ok) in enumerate(sh) if ok and (d0 or d1)]
     model = fit.ProjectorModel.from_fit(out, family0)
     if model.status != 0:
         warnings.warn('the projector model was not fitted (fewer than 2 usable lines in a family, or planes that give no centre)')
@@ -137,7 +157,7 @@ def _fit_projector(fits, frame_ok, projector, family0, use=None, table_path=None
         table.save(table_path)
     fc = out['frame_counts'].cpu().numpy()
     shifted = [i for i in range(len(fc)) if any(fc[i, 2 * k + 1] > 0 and 2 * fc[i, 2 * k + 1] >= fc[i, 2 * k] + fc[i, 2 * k + 1] for k in range(2))]
-    return dict(fit=out, model=model, laser_table=table), shifted
+    return dict(fit=out, model=model, laser_table=table, **extra), shifted, renumbered
 
 
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
@@ -177,6 +197,11 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     -N..N, N the largest |index| seen, family0 'col'; None when there is nothing to fit) and projector_shifted: the frames where at
     least half of one family's residuals fell outside the band tau, i.e. frames numbered one line off.  table_path: the table is
     saved there (LaserTable.save).  source must be 'stereo'.
+    projector['renumber']: None, or a dict of win, tau, min_score ({} = (4, 4), the fit's tau, 8; needs the fit's tau > 0): such
+    frames are re-numbered against the first model's table and the model is fitted again with them
+    (fit.fit_projector_model_renumbered).  projector then also holds first and shift, its fit, model, laser_table and
+    projector_shifted describe the refit, and the dict gains projector_renumbered: the (frame, d0, d1) of the kept frames that
+    got a non-zero shift.  The shift is relative to the majority of the frames.
 
     frame_angles=True (build-defined, nothing like it in the reference): with a multi-frame result, the good frames go through
     multiframe.estimate_frame_angles_gpu with T_cam_agv, a self-check of the calibration in degrees.  The dict gains
@@ -219,7 +244,10 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
         frame_ok = (d_fit == 0) & (d_l == 0) & (d_r == 0)
         if match_offset is not None:
             frame_ok = frame_ok & (d_weak == 0)
-        res['projector'], res['projector_shifted'] = _fit_projector(fits, frame_ok.to(torch.int32), projector, 'col', table_path=table_path)
+        res['projector'], res['projector_shifted'], renumbered = _fit_projector(fits, frame_ok.to(torch.int32), projector, 'col',
+                                                                                table_path=table_path)
+        if renumbered is not None:
+            res['projector_renumbered'] = renumbered
         fits = {k: v for k, v in fits.items() if k != 'idx'}
     if mat_path is not None:
         api.save_mat(mat_path, fits=fits, names=names)
@@ -300,7 +328,8 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
             consistent = the table exists, has a centre, and its planes meet there within PLANE_CENTRE_RMS_WARN)
 
     projector: None, or a dict of fit.fit_projector_model keywords (as run_experiment's): the projector's model is fitted to the
-    same points, masks and frames as well.  The dict gains projector and projector_shifted as in run_experiment (family0 'row');
+    same points, masks and frames as well.  The dict gains projector and projector_shifted as in run_experiment (family0 'row'),
+    and projector_renumbered with projector['renumber'];
     laser_table and the file at table_path are then the MODEL's table, and consistent says that the model was fitted and its
     rms is within PLANE_CENTRE_RMS_WARN.  `table` stays the free table of fit.index_planes_batch."""
     names, paths = _list_pairs(input_path)
@@ -341,7 +370,7 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
         if table_path is not None and projector is None:
             laser_table.save(table_path)
     if projector is not None:
-        pm, shifted = _fit_projector(fits, frame_ok, projector, 'row', use=fits['inlier_mask'], table_path=table_path)
+        pm, shifted, renumbered = _fit_projector(fits, frame_ok, projector, 'row', use=fits['inlier_mask'], table_path=table_path)
         consistent = pm is not None and pm['model'].status == 0 and pm['model'].rms <= PLANE_CENTRE_RMS_WARN
         if pm is not None:
             laser_table = pm['laser_table']
@@ -349,6 +378,8 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
                 warnings.warn(f'the projector model leaves {pm["model"].rms:.2f} mm rms (more than {PLANE_CENTRE_RMS_WARN} mm): the grid '
                               'numbering of the two images probably disagrees, the table is not to be trusted')
         extra = dict(projector=pm, projector_shifted=shifted)
+        if renumbered is not None:
+            extra['projector_renumbered'] = renumbered
     else:
         extra = {}
     return dict(**extra, **dict(names=names, records=recs, P=fits['P'], T=fits['T'], grid=fits['grid'], stats=fits['stats'], pts3=fits['pts3'],

@@ -485,6 +485,70 @@ def table_triangulate_batch(gp: GridTables, K, Tc, table: LaserTable, need_both=
     return dict(pts3=X, idx=idx, res=res, src=src, m=m, counts=counts, stats=stats)
 
 
+SHIFT_MAX_WIN = 8                                                   # CPE_SHIFT_MAX_WIN
+SHIFT_SHIFTED, SHIFT_WEAK, SHIFT_EDGE = 1, 2, 4                     # CPE_SHIFT_FLAG_*
+
+
+def index_shift_batch(pts3, idx, cnt, table: LaserTable, use=None, win=(4, 4), tau=1.0, min_score=8, ids='col_row'):
+    """BUILD-DEFINED: the shift to add to the grid indices of every STEREO frame so that its points lie on the planes of `table`
+    that its indices name, searched per index component over d in [-win[c], win[c]]; see include/cpe.h cpe_index_shift_batch.
+    pts3, idx, cnt, use as index_planes_batch; ids says what idx holds ('col_row' as GridTables, 'row_col' as the planar
+    detector), which family of the table either component addresses follows from table.family0.
+    -> dict(shift i32[n,2], score i32[n,2,4] (best, runner-up, at d = 0, usable points), scores i32[n, 2 win[0] + 2 win[1] + 2]
+            (every candidate, component 0 first, d ascending), rms f64[n,2,2] (at the applied shift, at d = 0), flags i32[n,2]
+            (SHIFT_*), idx i32[n,MAXP,2] = idx + shift below the count, zeros past it)"""
+    L = _lib.load()
+    pts3, idx, cnt, use = _point_tables('index_shift_batch', pts3, idx, cnt, use)
+    dev = pts3.device
+    n = cnt.shape[0]
+    win = tuple(int(w) for w in win)
+    if len(win) != 2 or not all(0 <= w <= SHIFT_MAX_WIN for w in win):
+        raise ValueError(f'index_shift_batch: window {win} outside 0..{SHIFT_MAX_WIN}')
+    if not tau > 0:
+        raise ValueError(f'index_shift_batch: tau must be > 0, got {tau}')
+    P = table.P.to(device=dev, dtype=torch.float64).contiguous()
+    st = table.status.to(device=dev, dtype=torch.int32).contiguous()
+    ncand = 2 * win[0] + 1 + 2 * win[1] + 1
+    # (the kernel writes every slot of every output but idx past the count)
+    i32 = torch.empty(n * (2 + 8 + ncand + 2), dtype=torch.int32, device=dev)
+    shift, score = i32[:2 * n].view(n, 2), i32[2 * n:10 * n].view(n, 2, 4)
+    scores, flags = i32[10 * n:(10 + ncand) * n].view(n, ncand), i32[(10 + ncand) * n:].view(n, 2)
+    rms = torch.empty((n, 2, 2), dtype=torch.float64, device=dev)
+    out = torch.zeros((n, MAXP, 2), dtype=torch.int32, device=dev)
+    prm = _lib.CpeIndexShiftParams((C.c_int32 * 2)(*win), float(tau), int(min_score), table.swap_for(ids))
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    _lib.check(L.cpe_index_shift_batch(ptr(pts3), ptr(idx), ptr(cnt), n, ptr(use), P.data_ptr(), st.data_ptr(), table.lo, table.hi,
+                                       C.addressof(prm), ptr(shift), ptr(score), ptr(scores), ptr(rms), ptr(flags), ptr(out), _stream()),
+               'cpe_index_shift_batch')
+    return dict(shift=shift, score=score, scores=scores, rms=rms, flags=flags, idx=out)
+
+
+def fit_projector_model_renumbered(pts3, idx, cnt, lo, hi, use=None, frame_ok=None, win=(4, 4), shift_tau=None, shift_min_score=8,
+                                   family0='col', **fit_kw):
+    """BUILD-DEFINED: fit_projector_model that brings back the frames it would only trim.  Four steps, all enqueued, no host
+    synchronisation: the model on [lo, hi] with the trimming band fit_kw['tau'] > 0; its table for [lo - w, hi + w], w = max(win);
+    index_shift_batch of every frame against that table (shift_tau defaults to the fit's tau); the model again on
+    [lo - w, hi + w] with the re-numbered indices, started from the first model.  idx is (col, row) for family0 'col' and (row,
+    col) for 'row': component c is family c either way.  A frame the caller leaves out with frame_ok is searched all the same and
+    fitted in neither call.
+    -> dict(first (the first fit's dict), table (its LaserTable), shift (index_shift_batch's dict, shift['idx'] the indices the
+            refit read), fit (the refit's dict), lo, hi (the refit's range))"""
+    tau = fit_kw.get('tau', 0.0)
+    if not tau > 0:
+        raise ValueError('fit_projector_model_renumbered: tau must be > 0 (an untrimmed first model is spoiled by the frames it is '
+                         'meant to repair)')
+    w = max(int(x) for x in win)
+    lo2, hi2 = int(lo) - w, int(hi) + w
+    if hi2 - lo2 + 1 > _lib.MAXL:
+        raise ValueError(f'fit_projector_model_renumbered: {hi2 - lo2 + 1} indices in [{lo}, {hi}] widened by {w}, must be 1..{_lib.MAXL}')
+    first = fit_projector_model(pts3, idx, cnt, lo, hi, use=use, frame_ok=frame_ok, **fit_kw)
+    table = ProjectorModel.from_fit(first, family0).table(lo2, hi2)
+    shift = index_shift_batch(pts3, idx, cnt, table, use=use, win=win, tau=tau if shift_tau is None else shift_tau,
+                              min_score=shift_min_score, ids='col_row' if family0 == 'col' else 'row_col')
+    refit = fit_projector_model(pts3, shift['idx'], cnt, lo2, hi2, use=use, frame_ok=frame_ok, **dict(fit_kw, x0=first['model'][:15]))
+    return dict(first=first, table=table, shift=shift, fit=refit, lo=lo2, hi=hi2)
+
+
 def fit_single_cylinder_mono_batch(gp: GridTables, K, Tc, table: LaserTable, radius, ransac=None, mode=FIT_NELDER_MEAD, need_both=False,
                                    min_sin=0.01, max_res=0.0, **fit_kw):
     """BUILD-DEFINED, fit_single_cylinder_batch from one camera: table_triangulate_batch, then fit_cylinder_batch (ransac: a

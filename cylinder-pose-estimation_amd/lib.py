@@ -82,6 +82,7 @@ _SIGS = {
     'cpe_fit_projector_model': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
                                 [C.c_void_p] * 10),
     'cpe_projector_model_table': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
+    'cpe_index_shift_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] + [C.c_void_p] * 8),
     'cpe_undistort_map': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_remap_bilinear_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_undistort_map_matlab': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -148,6 +149,10 @@ class CpeProjectorModelParams(C.Structure):
 
 class CpeTableTriParams(C.Structure):
     _fields_ = [('swap', C.c_int32), ('need_both', C.c_int32), ('min_sin', C.c_double), ('max_res', C.c_double)]
+
+
+class CpeIndexShiftParams(C.Structure):
+    _fields_ = [('win', C.c_int32 * 2), ('tau', C.c_double), ('min_score', C.c_int32), ('swap', C.c_int32)]
 
 
 MAXP = 2048

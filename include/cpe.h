@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 119   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 120   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -53,7 +53,8 @@ extern "C" {
                              cpe_pose_T2vec_batch; 113: cpe_multi_frame_fit_lm_batch; 114: cpe_agv_chain_batch,
                              cpe_frame_angles_lm_batch; 115: cpe_debug_region_hull; 116: cpe_match_offset_batch,
                              cpe_match_offset_workspace_bytes; 117: cpe_fit_plane_batch, cpe_index_planes_batch;
-                             118: cpe_table_triangulate_batch; 119: cpe_fit_projector_model, cpe_projector_model_table) */
+                             118: cpe_table_triangulate_batch; 119: cpe_fit_projector_model, cpe_projector_model_table;
+                             120: cpe_index_shift_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -695,7 +696,8 @@ CPE_API int32_t cpe_index_planes_batch(const double *X, const int32_t *idx, cons
  *   frame_counts i32[n,4]    per frame: kept and trimmed residuals of family 0, kept and trimmed residuals of family 1
  * cnt is clamped to [0, CPE_MAXP]; slots past it are never read; n = 0 is allowed (CPE_ST_FEW_POINTS).
  * Limits: the spacing of a pencil is linear in tan(theta) -- no distortion term for real gratings; one tau for both families;
- * a frame that is mis-numbered in both images alike is trimmed, not re-numbered. */
+ * a frame that is mis-numbered in both images alike is trimmed, not re-numbered (cpe_index_shift_batch re-numbers it against
+ * this model's table, and a second call fits the frames so repaired). */
 typedef struct CpeProjectorModelParams {
     double tau;           /* band |r| < tau of the trimming rounds, the unit of the points; <= 0: no trimming (default) */
     int32_t max_rounds;   /* refits at the most, 0..CPE_PLANEFIT_MAX_ROUNDS; default 4 */
@@ -756,6 +758,56 @@ CPE_API int32_t cpe_table_triangulate_batch(const double *xy, const int32_t *id,
                                             const double *Tc, const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
                                             const CpeTableTriParams *params, double *X, int32_t *idx, double *res, int32_t *src,
                                             int32_t *m, int32_t *counts, double *stats, void *stream);
+
+/* BUILD-DEFINED: re-number STEREO frames against a laser-plane table.  cpe_match_offset_batch makes the two images of a frame
+ * agree with each other; a frame that is then numbered a line off in both images alike carries indices that mean other planes
+ * than in the rest of the experiment.  A stereo point's position does not depend on its index, so the frame's points and any
+ * table that is right for the majority of the frames -- cpe_projector_model_table of a model fitted with tau > 0, or a table from
+ * boards -- determine the frame's shift: per index component, the d for which the most points lie on the plane of index + d.
+ * One wavefront per (frame, component), one launch on `stream`, no workspace, no atomics, no host synchronisation; two calls on
+ * the same inputs give the same bits.
+ *   X f64[n,CPE_MAXP,3], idx i32[n,CPE_MAXP,2], cnt i32[n]: as cpe_select_triangulate_batch writes them; use u8[n,CPE_MAXP] or
+ *   NULL (all points); P f64[2,L,4], line_status i32[2,L], lo, hi: a table as cpe_index_planes_batch or
+ *   cpe_projector_model_table writes it, L = hi - lo + 1 in 1..CPE_MAXL (otherwise CPE_ERR_ARG); params NULL = the defaults of
+ *   CpeIndexShiftParams.
+ * Rule (the order is the contract):
+ *   1. cnt is clamped to [0, CPE_MAXP]; slots past it are never read.  A point is usable when its slot is below the count, `use`
+ *      is non-zero and its three coordinates are finite;
+ *   2. component c in {0,1} of idx addresses family k = c ^ swap.  For the candidate d in [-win[c], win[c]] a usable point with
+ *      v = idx[c] + d counts when lo <= v <= hi, line_status[k, v - lo] == CPE_ST_OK and |n.X + P4| < tau for the plane
+ *      P[k, v - lo].  A point whose idx[c] lies outside [lo - win[c], hi + win[c]] counts for no candidate: that test is made
+ *      before any addition, so an index may be any int;
+ *   3. score(c, d) = the number of such points.  Winner: the candidate with the smallest key (-score, |d|, d), so 0 wins every
+ *      tie it is part of;
+ *   4. the component is trusted when best >= min_score and best >= 2 runner_up (integers), runner_up = the second-largest value
+ *      among the component's candidates (0 with a single candidate).  Otherwise CPE_SHIFT_FLAG_WEAK and the shift is 0;
+ *   5. CPE_SHIFT_FLAG_EDGE when |winner| == win[c] > 0; CPE_SHIFT_FLAG_SHIFTED when a non-zero shift was applied;
+ *   6. score i32[n,2,4] = best | runner-up | score at d = 0 | usable points;
+ *   7. rms f64[n,2,2] = sqrt of the mean squared n.X + P4 over the points that count, at the applied shift | at d = 0; 0 when
+ *      none counts;
+ *   8. scores i32[n, 2 win[0] + 1 + 2 win[1] + 1] or NULL: every candidate, component 0 first, d ascending;
+ *   9. idx_out i32[n,CPE_MAXP,2] = idx + the applied shift in the slots below the count (a sum past int32 wraps); slots past it
+ *      are not written; may not be idx.
+ * shift i32[n,2] the applied shift per component; flags i32[n,2] CPE_SHIFT_FLAG_* (independent bits).  n == 0 is a no-op.  A
+ * frame without a usable point scores 0 everywhere: shift 0, and CPE_SHIFT_FLAG_WEAK unless min_score is 0.
+ * Limits: the shift is relative to the majority of the frames -- a shift common to all frames is absorbed by the model the
+ * table comes from; one shift per frame and family; stereo points only: a point of cpe_table_triangulate_batch moves with its
+ * index, so it lies on the plane of whatever index it carries. */
+#define CPE_SHIFT_MAX_WIN 8
+#define CPE_SHIFT_FLAG_SHIFTED 1   /* a non-zero shift was chosen and applied */
+#define CPE_SHIFT_FLAG_WEAK 2      /* best < min_score or best < 2 runner-up: the winner is not trusted, shift forced to 0 */
+#define CPE_SHIFT_FLAG_EDGE 4      /* the winner lies on the border of a non-zero window: the true shift may lie outside (the
+                                      shift is still applied unless the component is also WEAK) */
+typedef struct CpeIndexShiftParams {
+    int32_t win[2];     /* candidates d in [-win[c], win[c]] for id component c; 0..CPE_SHIFT_MAX_WIN; default 4, 4 */
+    double  tau;        /* a point counts when |n.X + P4| < tau, the unit of the points; > 0; default 1.0 */
+    int32_t min_score;  /* a winner below this is not trusted (>= 0); default 8 */
+    int32_t swap;       /* as CpeTableTriParams.swap: component c addresses family c ^ swap */
+} CpeIndexShiftParams;
+CPE_API int32_t cpe_index_shift_batch(const double *X, const int32_t *idx, const int32_t *cnt, int32_t n, const uint8_t *use,
+                                      const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
+                                      const CpeIndexShiftParams *params, int32_t *shift, int32_t *score, int32_t *scores, double *rms,
+                                      int32_t *flags, int32_t *idx_out, void *stream);
 
 /* Row f-3: the undistortion pre-step of the CLI entry point, utils/iotool.py:22-39
  *   undistort_image(image, camera_params) = cv2.undistort(image, IntrinsicMatrix, hstack(Radial, Tangential))
