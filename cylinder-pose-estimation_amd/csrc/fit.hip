@@ -1564,11 +1564,13 @@ struct MultiOut {
     }
 };
 
-// The head of both multi-frame kernels for group g: the kept frames of [group_start[g], group_start[g + 1]) into sIdx (LDS; sNk
+// The head of the multi-frame kernels for group g: the kept frames of [group_start[g], group_start[g + 1]) into sIdx (LDS; sNk
 // one int of LDS), one barrier.  -> their count nk >= 2, or 0 after the group's record is written: OVERFLOW for a range outside
 // [0, n] or more than MF_MAXF kept frames, FEW_POINTS below two (assert(nAngles >= 2), fitCylinderWPts3sAngs.m:29)
+// Out: MultiOut, or ConsensusOut with its further outputs
+template <class Out>
 __device__ __forceinline__ int multi_group_begin(const int *__restrict__ frame_ok, const int *__restrict__ group_start, int n, int g,
-                                                 int *sIdx, int *sNk, const MultiOut &out)
+                                                 int *sIdx, int *sNk, const Out &out)
 {
     const int a = group_start[g], b = group_start[g + 1];
     const bool range_ok = 0 <= a && a <= b && b <= n;
@@ -1918,6 +1920,291 @@ __global__ __launch_bounds__(64 * WAVES) void k_multi_frame_lm(
     out.write_ok(g, x0, x, f0, fx, itercount, func_evals, nk);
 }
 
+// ---- BUILD-DEFINED (include/cpe.h cpe_multi_frame_consensus_batch): the LM form above with a consensus over frames in front of
+// it, for experiments that hold frames with status 0 and a wrong cylinder.  Every pair of usable frames (or max_hyp pairs spread
+// over them) gives a pose in closed form -- multi_init_all on a list of two -- that is scored by the kept frames whose term at
+// it lies below tau^2; the best pose's frames are fitted by the LM loop, its inliers are taken again, and so on.
+// k_multi_frame_hyp       : one wavefront per (hypothesis, group): key (inlier count, sum of their terms) and pose -> workspace.
+// k_multi_frame_consensus : one workgroup per group: arg-min over the keys, the refinement rounds, every output.
+// Both are made of the pieces of k_multi_frame_lm: the one MultiObjectiveT of a workgroup is pointed at the list it is to add up
+// (the pair, all kept frames, the inliers), so its two rows of sTerms keep alternating whatever the list.
+constexpr int MFC_REC = 7;   // doubles of a hypothesis in the workspace: the sum of its inliers' terms, its pose
+
+// R offsets per frame and H hypotheses for u >= 2 usable frames; dense: the offsets are 1..R = u/2, every unordered pair occurs
+__device__ __forceinline__ void consensus_plan(int u, int max_hyp, int &R, int &H, bool &dense)
+{
+    R = max(1, max_hyp / u);
+    dense = R >= u / 2;
+    if (dense) R = u / 2;
+    H = min(R * u, max_hyp);
+}
+
+// hypothesis h -> the places a != b of its two frames in the usable list.  The offsets stay within u/2: (a, a + off) and (a + off,
+// a + off + (u - off)) are the same two frames, and a pose that differs from an earlier one by rounding alone would make the
+// arg-min a matter of last bits.  false: the one case left, the offset u/2 of an even u names every pair twice and this is the
+// second time -- the hypothesis is void
+__device__ __forceinline__ bool consensus_pair(int h, int u, int R, bool dense, int &a, int &b)
+{
+    const int k = h / u;
+    const int off = dense ? 1 + k : 1 + ((2 * k + 1) * (u / 2 - 1)) / (2 * R);
+    a = h % u;
+    b = (a + off) % u;
+    return !(2 * off == u && a >= off);
+}
+
+// the usable (multi_usable) frames of the kept list into sU, in kept order (one wavefront).  -> their count
+__device__ __forceinline__ int multi_usable_frames(const int *__restrict__ cnt, const double *__restrict__ cyl_raw, const int *sIdx, int nk,
+                                                   int lane, int *sU)
+{
+    int nu = 0;
+    for (int base = 0; base < nk; base += 64) {
+        const int k = base + lane;
+        double o[3], d[3];
+        const bool us = k < nk && multi_usable(cnt, cyl_raw, sIdx[k], o, d);
+        const unsigned long long bal = __ballot(us);
+        if (us) sU[nu + __popcll(bal & ((1ull << lane) - 1ull))] = sIdx[k];
+        nu += __popcll(bal);
+    }
+    return nu;
+}
+
+// The inliers of a pose among the kept frames, t[k] the term of kept frame k at it (a row of sTerms): cnt >= 1 and t[k] < tau2.
+// Every thread runs the same loop on the same numbers.  -> their count; sum: their terms added in kept order; with list, thread 0
+// stores their frame numbers there (the caller's barrier publishes them) and same tells whether they are prev[0..nprev)
+__device__ __forceinline__ int multi_inliers(const double *t, const int *sIdx, const int *__restrict__ cnt, int nk, double tau2, double &sum,
+                                             int *list, const int *prev, int nprev, bool &same)
+{
+    int c = 0;
+    double s = 0.0;
+    bool sm = true;
+    for (int k = 0; k < nk; k++) {
+        const int f = sIdx[k];
+        const double tk = t[k];
+        if (cnt[f] >= 1 && tk < tau2) {
+            s = s + tk;
+            if (list != nullptr) {
+                if (prev != nullptr) sm = sm && c < nprev && prev[c] == f;
+                if (threadIdx.x == 0) list[c] = f;
+            }
+            c++;
+        }
+    }
+    sum = s;
+    same = sm && c == nprev;
+    return c;
+}
+
+// Hypothesis h = blockIdx.y of group g = blockIdx.x, one wavefront.  A group that k_multi_frame_consensus reports as failed, and a
+// hypothesis past the group's H, write nothing; every h < H writes its record (count -1: void).  H <= (u / 2) u and u is at
+// most the length of the group's range, so most of the wavefronts past H leave before they read a frame.
+__global__ __launch_bounds__(64) void k_multi_frame_hyp(
+    const double *__restrict__ X, const int *__restrict__ cnt, const double *__restrict__ TAGV, const double *__restrict__ cyl_raw,
+    const int *__restrict__ frame_ok, const int *__restrict__ group_start, int n, double R, double tau2, int max_hyp,
+    double *__restrict__ wrec, int *__restrict__ wcount)
+{
+    __shared__ int sIdx[MF_MAXF];
+    __shared__ int sU[MF_MAXF];
+    __shared__ double sTerms[2 * MF_MAXF];
+    __shared__ int sPair[2];
+    const int h = blockIdx.y, g = blockIdx.x, lane = threadIdx.x;
+    const int ga = group_start[g], gb = group_start[g + 1];
+    const bool range_ok = 0 <= ga && ga <= gb && gb <= n;
+    if (!range_ok || (long long)h >= (long long)max((gb - ga) / 2, 1) * (gb - ga)) return;
+    const int nk = multi_kept_frames(frame_ok, ga, gb, range_ok, lane, sIdx);
+    if (!range_ok || nk > MF_MAXF || nk < 2) return;
+    __syncthreads();
+    const int u = multi_usable_frames(cnt, cyl_raw, sIdx, nk, lane, sU);
+    if (u < 2) return;
+    int Rr, H;
+    bool dense;
+    consensus_plan(u, max_hyp, Rr, H, dense);
+    if (h >= H) return;
+    __syncthreads();
+    int a, b;
+    const bool first = consensus_pair(h, u, Rr, dense, a, b);
+    if (lane == 0) { sPair[0] = sU[a]; sPair[1] = sU[b]; }
+    __syncthreads();
+    double x[6], xm[6];
+    int n_usable;
+    multi_init_all(cnt, TAGV, cyl_raw, sPair, 2, lane, x, xm, n_usable);
+    MultiObjectiveT<1> obj{X, cnt, TAGV, R, sPair, sTerms, 2, 0, lane, 0};
+    double f0 = obj(x);
+    const double fm = obj(xm);
+    if (!(f0 <= fm) && fm == fm) {   // the lower objective over the pair, a tie to sigma = +1
+#pragma unroll
+        for (int k = 0; k < 6; k++) x[k] = xm[k];
+        f0 = fm;
+    }
+    int count = -1;
+    double sum = 0.0;
+    if (first && fit_finite(x, f0)) {
+        obj.sIdx = sIdx;
+        obj.nk = nk;
+        const double *t = sTerms + obj.row * MF_MAXF;
+        obj(x);
+        bool same;
+        count = multi_inliers(t, sIdx, cnt, nk, tau2, sum, nullptr, nullptr, 0, same);
+    }
+    if (lane == 0) {
+        const size_t slot = (size_t)g * max_hyp + h;
+        wcount[slot] = count;
+        wrec[slot * MFC_REC] = sum;
+#pragma unroll
+        for (int k = 0; k < 6; k++) wrec[slot * MFC_REC + 1 + k] = x[k];
+    }
+}
+
+// the key (-count, sum, h) of hypothesis 1 lies before that of hypothesis 2
+__device__ __forceinline__ bool consensus_before(int c1, double s1, int h1, int c2, double s2, int h2)
+{
+    if (c1 != c2) return c1 > c2;
+    if (s1 != s2) return s1 < s2;
+    return h1 < h2;
+}
+
+// the outputs of k_multi_frame_consensus per group g: MultiOut's and three more; written by thread 0 of the workgroup
+struct ConsensusOut {
+    MultiOut m;
+    int *n_inliers, *info, *flags;
+    __device__ void write_failed(int g, int st) const
+    {
+        m.write_failed(g, st);
+        if (threadIdx.x != 0) return;
+        n_inliers[g] = 0;
+        for (int k = 0; k < 4; k++) info[4 * g + k] = 0;
+        flags[g] = 0;
+    }
+    __device__ void write_ok(int g, const double *xs, const double *xf, double f0, double ffinal, int itercount, int func_evals, int nk,
+                             int nfit, int h, int fa, int fb, int rounds, int fl) const
+    {
+        m.write_ok(g, xs, xf, f0, ffinal, itercount, func_evals, nk);
+        if (threadIdx.x != 0) return;
+        n_inliers[g] = nfit;
+        info[4 * g] = h; info[4 * g + 1] = fa; info[4 * g + 2] = fb; info[4 * g + 3] = rounds;
+        flags[g] = fl;
+    }
+};
+
+// Group g = blockIdx.x.  Barriers: those of k_multi_frame_lm, one after the usable list, one after the arg-min, one after every
+// inlier list.  As there, every wave runs the same code on the same numbers (lists, terms, sums and the waves' best keys come from
+// LDS, the records from the workspace), so no barrier stands under a condition that depends on the wave or the lane.
+// WAVES is k_multi_frame_lm's, so that a round has the bits of that kernel on the same list.
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_multi_frame_consensus(
+    const double *__restrict__ X, const int *__restrict__ cnt, const double *__restrict__ TAGV, const double *__restrict__ cyl_raw,
+    const int *__restrict__ frame_ok, const int *__restrict__ group_start, int n, double R, double tolx, double tolf, int maxiter,
+    double tau2, int max_hyp, int max_rounds, int min_inliers, const double *__restrict__ wrec, const int *__restrict__ wcount,
+    const ConsensusOut out, int *__restrict__ o_inlier, double *__restrict__ o_terms)
+{
+    __builtin_amdgcn_s_setprio(3);
+    __shared__ int sIdx[MF_MAXF];
+    __shared__ int sU[MF_MAXF];
+    __shared__ int sInl[2 * MF_MAXF];
+    __shared__ double sTerms[2 * MF_MAXF];
+    __shared__ double sJ[WAVES * MFLM_SUMS];
+    __shared__ double sKs[WAVES];
+    __shared__ int sKc[WAVES], sKh[WAVES];
+    __shared__ int sNk, sNu;
+    const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nk = multi_group_begin(frame_ok, group_start, n, g, sIdx, &sNk, out);
+    if (nk == 0) return;
+    if (wave == 0) {
+        const int nu = multi_usable_frames(cnt, cyl_raw, sIdx, nk, lane, sU);
+        if (lane == 0) sNu = nu;
+    }
+    __syncthreads();
+    const int u = sNu;
+    if (u < 2) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+    int Rr, H;
+    bool dense;
+    consensus_plan(u, max_hyp, Rr, H, dense);
+
+    // the smallest key: thread t takes h = t, t + 64 WAVES, ..., the 64-lane butterfly, the waves' bests through LDS.  The keys
+    // are totally ordered (h is part of them), so the order of the comparisons does not matter
+    const size_t slot0 = (size_t)g * max_hyp;
+    int bc = -1, bh = INT_MAX;
+    double bs = 0.0;
+    for (int h = threadIdx.x; h < H; h += 64 * WAVES) {
+        const int c = wcount[slot0 + h];
+        const double s = wrec[(slot0 + h) * MFC_REC];
+        if (c >= 0 && consensus_before(c, s, h, bc, bs, bh)) { bc = c; bs = s; bh = h; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int c = __shfl_xor(bc, off, 64), h = __shfl_xor(bh, off, 64);
+        const double s = __shfl_xor(bs, off, 64);
+        if (c >= 0 && consensus_before(c, s, h, bc, bs, bh)) { bc = c; bs = s; bh = h; }
+    }
+    if (lane == 0) { sKc[wave] = bc; sKs[wave] = bs; sKh[wave] = bh; }
+    __syncthreads();
+    bc = -1; bs = 0.0; bh = INT_MAX;
+    for (int w = 0; w < WAVES; w++)
+        if (sKc[w] >= 0 && consensus_before(sKc[w], sKs[w], sKh[w], bc, bs, bh)) { bc = sKc[w]; bs = sKs[w]; bh = sKh[w]; }
+    if (bc < min_inliers) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }   // no valid hypothesis: bc = -1
+
+    double x0[6], x[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) { x0[k] = wrec[(slot0 + bh) * MFC_REC + 1 + k]; x[k] = x0[k]; }
+    MultiObjectiveT<WAVES> obj{X, cnt, TAGV, R, sIdx, sTerms, nk, wave, lane, 0};
+    MultiPoseProblem<WAVES> prob{obj, sJ};
+    // S_0: the terms of every kept frame at x0 again (the bits the hypothesis kernel saw), as a list this time
+    const double *tall = sTerms + obj.row * MF_MAXF;
+    obj(x0);
+    int cur = 0;
+    double f0;
+    bool same;
+    int nS = multi_inliers(tall, sIdx, cnt, nk, tau2, f0, sInl, nullptr, 0, same);
+    __syncthreads();
+    if (nS < min_inliers) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+    double fx = f0;
+    int nfit = nS, fitcur = 0, rounds = 0, flags = 0, itercount = 0, func_evals = 0;
+    for (int r = 1; r <= max_rounds; r++) {
+        // k_multi_frame_lm with x0_in = x on the list S_(r-1)
+        obj.sIdx = sInl + cur * MF_MAXF;
+        obj.nk = nS;
+        const double fs = obj(x);
+        int it, fe = 1;
+        if (!fit_finite(x, fs)) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+        double xn[6], fn;
+        lm_minimize<6>(prob, x, fs, tolx, tolf, maxiter, xn, fn, it, fe);
+        if (!fit_finite(xn, fn)) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+#pragma unroll
+        for (int k = 0; k < 6; k++) x[k] = xn[k];
+        fx = fn;
+        nfit = nS; fitcur = cur; rounds = r;
+        itercount += it; func_evals += fe;
+        // S_r
+        obj.sIdx = sIdx;
+        obj.nk = nk;
+        tall = sTerms + obj.row * MF_MAXF;
+        obj(x);
+        double sr;
+        const int nnew = multi_inliers(tall, sIdx, cnt, nk, tau2, sr, sInl + (cur ^ 1) * MF_MAXF, sInl + cur * MF_MAXF, nS, same);
+        __syncthreads();
+        if (same) { flags |= CPE_CONSENSUS_CONVERGED; break; }
+        if (nnew < min_inliers) { flags |= CPE_CONSENSUS_SHRUNK; break; }
+        cur ^= 1;
+        nS = nnew;
+    }
+    // per frame: the terms at x (tall: the last evaluation was over all kept frames at x), and whether the frame is in the list x
+    // was fitted to -- a merge of two ascending lists
+    if (o_terms != nullptr)
+        for (int k = threadIdx.x; k < nk; k += 64 * WAVES) o_terms[sIdx[k]] = tall[k];
+    if (threadIdx.x == 0) {
+        const int *fl = sInl + fitcur * MF_MAXF;
+        int p = 0;
+        for (int k = 0; k < nk; k++) {
+            const int f = sIdx[k];
+            const bool in = p < nfit && fl[p] == f;
+            if (in) p++;
+            o_inlier[f] = in ? 1 : 0;
+        }
+    }
+    int pa, pb;
+    consensus_pair(bh, u, Rr, dense, pa, pb);
+    out.write_ok(g, x0, x, f0, fx, itercount, func_evals, nk, nfit, bh, sU[pa], sU[pb], rounds, flags);
+}
+
 __global__ __launch_bounds__(64) void k_pose_vec2T(const double *__restrict__ x, int n, double *__restrict__ T)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -2223,6 +2510,56 @@ extern "C" int32_t cpe_multi_frame_fit_lm_batch(const double *X, const int32_t *
     CPE_KLAUNCH(k_multi_frame_lm<MFLM_WAVES>, dim3(G), dim3(64 * MFLM_WAVES), 0, (hipStream_t)stream, X, cnt, TAGVcyl, cyl_raw, frame_ok,
                 group_start, n, radius, p.tol_x, p.tol_f, p.max_iter, x0_in, out, frame_terms);
     CPE_CHECK_LAUNCH("k_multi_frame_lm");
+    return CPE_OK;
+}
+
+extern "C" size_t cpe_multi_frame_consensus_workspace_bytes(int32_t G, int32_t max_hyp)
+{
+    if (G <= 0 || max_hyp < 1 || max_hyp > CPE_CONSENSUS_MAX_HYP) return 0;
+    return (size_t)G * max_hyp * (MFC_REC * sizeof(double) + sizeof(int));
+}
+
+extern "C" int32_t cpe_multi_frame_consensus_batch(const double *X, const int32_t *cnt, const double *TAGVcyl, const double *cyl_raw,
+                                                   const int32_t *frame_ok, const int32_t *group_start, int32_t G, int32_t n, double radius,
+                                                   const CpeFitParams *params, const CpeConsensusParams *cons, void *ws, size_t ws_bytes,
+                                                   double *x0, double *x, double *T, double *fvals, int32_t *iters, int32_t *n_used,
+                                                   int32_t *n_inliers, int32_t *info, int32_t *flags, int32_t *status, int32_t *inlier,
+                                                   double *frame_terms, void *stream)
+{
+    CPE_CHECK_ARG(X && cnt && TAGVcyl && cyl_raw && group_start && x0 && x && T && fvals && iters && n_used && n_inliers && info && flags &&
+                  status && inlier, "cpe_multi_frame_consensus_batch: null pointer");
+    CPE_CHECK_ARG(G >= 0 && n >= 0, "cpe_multi_frame_consensus_batch: G < 0 or n < 0");
+    CpeFitParams p = {1e-5, 1e-5, 100000, 100000, CPE_FIT_LM, 0};
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.tol_x >= 0 && p.tol_f >= 0 && p.max_iter > 0, "cpe_multi_frame_consensus_batch: bad CpeFitParams");
+    CPE_CHECK_ARG(p.mode == CPE_FIT_LM, "cpe_multi_frame_consensus_batch: mode %d (the refinement is Levenberg-Marquardt only)", p.mode);
+    CpeConsensusParams c = {0.5, 2048, 4, 3};
+    if (cons) c = *cons;
+    CPE_CHECK_ARG(c.tau > 0 && c.tau <= DBL_MAX && c.max_hyp >= 1 && c.max_hyp <= CPE_CONSENSUS_MAX_HYP && c.max_rounds >= 0 &&
+                  c.max_rounds <= 16 && c.min_inliers >= 2,
+                  "cpe_multi_frame_consensus_batch: bad CpeConsensusParams (tau > 0, max_hyp 1..%d, max_rounds 0..16, min_inliers >= 2)",
+                  CPE_CONSENSUS_MAX_HYP);
+    if (G == 0) return CPE_OK;
+    const size_t need = cpe_multi_frame_consensus_workspace_bytes(G, c.max_hyp);
+    if (!ws || ((uintptr_t)ws & 7) != 0 || ws_bytes < need) {
+        cpe::set_error("cpe_multi_frame_consensus_batch: workspace missing, not 8-byte aligned or too small (%zu < %zu)", ws_bytes, need);
+        return CPE_ERR_WORKSPACE;
+    }
+    CPE_LAUNCH_BEGIN();
+    double *wrec = (double *)ws;
+    int *wcount = (int *)(wrec + (size_t)G * c.max_hyp * MFC_REC);
+    const double tau2 = c.tau * c.tau;
+    // no group has more than min(n, MF_MAXF) usable frames, so none has a hypothesis at or past (u / 2) u of that
+    const long long umax = n < MF_MAXF ? n : MF_MAXF, most = (umax / 2 > 1 ? umax / 2 : 1) * (umax > 1 ? umax : 1);
+    const int hyp_rows = most < c.max_hyp ? (int)most : c.max_hyp;
+    CPE_KLAUNCH(k_multi_frame_hyp, dim3(G, hyp_rows), dim3(64), 0, (hipStream_t)stream, X, cnt, TAGVcyl, cyl_raw, frame_ok, group_start, n,
+                radius, tau2, c.max_hyp, wrec, wcount);
+    CPE_CHECK_LAUNCH("k_multi_frame_hyp");
+    const ConsensusOut out{MultiOut{x0, x, T, fvals, iters, n_used, status}, n_inliers, info, flags};
+    CPE_KLAUNCH(k_multi_frame_consensus<MFLM_WAVES>, dim3(G), dim3(64 * MFLM_WAVES), 0, (hipStream_t)stream, X, cnt, TAGVcyl, cyl_raw,
+                frame_ok, group_start, n, radius, p.tol_x, p.tol_f, p.max_iter, tau2, c.max_hyp, c.max_rounds, c.min_inliers, wrec, wcount, out,
+                inlier, frame_terms);
+    CPE_CHECK_LAUNCH("k_multi_frame_consensus");
     return CPE_OK;
 }
 

@@ -6,6 +6,7 @@
 Image pairs are read in windows of `chunk`; a window is uploaded as it was decoded (uint8 / uint16, grey or RGB) and goes
 through FramePipeline.run_raw: the fused pre-step (iotool.StereoPrestep), one detect call for both cameras and the batched
 fitSingleCylinder, all resident on the GPU."""
+import math
 import os
 import re
 import warnings
@@ -161,16 +162,18 @@ def _fit_projector(fits, frame_ok, projector, family0, use=None, table_path=None
 
 
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
-                   frame_angles=False, match_offset=None, laser_table=None, source='stereo', projector=None, table_path=None):
+                   frame_angles=False, match_offset=None, laser_table=None, source='stereo', projector=None, table_path=None,
+                   consensus=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
 
     multi_frame: True = multiframe.fit_multi_frame (simplex on the host, bit-identical to the oracle); 'gpu' =
     multiframe.fit_multi_frame_gpu (the whole fit resident, device sin / cos: fval agrees to ~1e-12 relative); 'lm' = the same
-    call with method='lm' (build-defined: all-frame initial pose + Levenberg-Marquardt, not the reference's path); False = none.
-    The 'gpu' and 'lm' modes fit at most CPE_MULTI_MAXF = 1024 good frames: with more they warn (status 6, CPE_ST_OVERFLOW) and return
-    None results, where the host mode would fit them.
+    call with method='lm' (build-defined: all-frame initial pose + Levenberg-Marquardt, not the reference's path); 'consensus' =
+    multiframe.fit_multi_frame_consensus_gpu (build-defined, below); False = none.
+    The 'gpu', 'lm' and 'consensus' modes fit at most CPE_MULTI_MAXF = 1024 good frames: with more they warn (status 6,
+    CPE_ST_OVERFLOW) and return None results, where the host mode would fit them.
 
     Every `<stem>L.png` needs its `<stem>R.png`: the reference fails in imread on a missing partner, this raises
     FileNotFoundError naming the file, before any frame is processed.
@@ -203,6 +206,15 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     projector_shifted describe the refit, and the dict gains projector_renumbered: the (frame, d0, d1) of the kept frames that
     got a non-zero shift.  The shift is relative to the majority of the frames.
 
+    multi_frame='consensus' (build-defined): a frame can end with status 0 and a wrong cylinder, and the other modes add every
+    good frame's term up.  This one takes T_cam_agv and fval from multiframe.fit_multi_frame_consensus_gpu over the same frames
+    -- the pose that the largest set of frames agrees with to within tau (rms of dist - radius, the unit of the points), fitted
+    to those frames -- and the dict gains consensus = dict(inliers: names of the frames the pose was fitted to, rejected: a list
+    of dict(index, name, rms = sqrt of the frame's term at the pose) for the other good frames, n_inliers, rounds, flags, status).
+    It warns when frames are rejected or the status is non-zero.  consensus=: None, or a dict of tau, max_hyp, max_rounds,
+    min_inliers (defaults 0.5, 2048, 4, 3); with any other multi_frame it raises ValueError.  A majority of frames that are
+    wrong in the same way wins; a frame is in or out whole.
+
     frame_angles=True (build-defined, nothing like it in the reference): with a multi-frame result, the good frames go through
     multiframe.estimate_frame_angles_gpu with T_cam_agv, a self-check of the calibration in degrees.  The dict gains
     angles_est (F x 2, rad; NaN for a skipped or failed frame), angles_status (F; the solver's status, -1 for a frame that was
@@ -214,6 +226,8 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
         laser_table = fit.LaserTable.load(laser_table, dev)
     if projector is not None and source != 'stereo':
         raise ValueError("projector= fits the model to stereo points: source must be 'stereo'")
+    if consensus is not None and multi_frame != 'consensus':
+        raise ValueError("consensus= are the options of multi_frame='consensus'")
 
     def make_fits(F):
         f = pipeline.alloc_fits(F, dev, source=source)
@@ -236,15 +250,19 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
                    for i in range(F) if st_l[i] or st_r[i] or st_fit[i] or (mfl[i] & fit.MATCH_WEAK)]
     res = dict(names=names, angles=angles, records=recs, pts3=fits['pts3'], cnt=fits['m'], cyl_raw=fits['cyl_raw'], skipped=skipped,
                T_cam_agv=None, fval=None)
+    def good_frames():
+        """i32[F] on the device: 1 for a frame that is not in `skipped`, made from the records' status words without a copy"""
+        ok = (d_fit == 0) & (d_l == 0) & (d_r == 0)
+        if match_offset is not None:
+            ok = ok & (d_weak == 0)
+        return ok.to(torch.int32)
+
     if match_offset is not None:
         res.update(offset=fits['offset'], match_score=fits['match_score'], match_flags=fits['match_flags'])
     if source != 'stereo':
         res.update(tri_counts=fits['counts'], tri_stats=fits['stats'])
     if projector is not None:
-        frame_ok = (d_fit == 0) & (d_l == 0) & (d_r == 0)
-        if match_offset is not None:
-            frame_ok = frame_ok & (d_weak == 0)
-        res['projector'], res['projector_shifted'], renumbered = _fit_projector(fits, frame_ok.to(torch.int32), projector, 'col',
+        res['projector'], res['projector_shifted'], renumbered = _fit_projector(fits, good_frames(), projector, 'col',
                                                                                 table_path=table_path)
         if renumbered is not None:
             res['projector_renumbered'] = renumbered
@@ -254,10 +272,7 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     if multi_frame in ('gpu', 'lm'):
         # resident: the kept frames are named by a device mask made from the records' status words, the whole tables go in
         # as one group, and T, fval, status and the count of kept frames come back in one copy
-        frame_ok = (d_fit == 0) & (d_l == 0) & (d_r == 0)
-        if match_offset is not None:
-            frame_ok = frame_ok & (d_weak == 0)
-        frame_ok = frame_ok.to(torch.int32)
+        frame_ok = good_frames()
         mf = multiframe.fit_multi_frame_gpu(fits['pts3'], fits['m'], fits['cyl_raw'], angles, radius, frame_ok=frame_ok,
                                             group_start=[0, F], method='lm' if multi_frame == 'lm' else 'nm')
         back = torch.cat([mf['T'][0], mf['fvals'][0], mf['status'][0:1].to(torch.float64),
@@ -269,6 +284,25 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
             warnings.warn(f'multi-frame fit ended with status {status} (include/cpe.h: cpe_multi_frame_fit_batch)')
         else:
             res['T_cam_agv'], res['fval'] = back[:16], back[17]
+    elif multi_frame == 'consensus':
+        frame_ok = good_frames()
+        mf = multiframe.fit_multi_frame_consensus_gpu(fits['pts3'], fits['m'], fits['cyl_raw'], angles, radius, frame_ok=frame_ok,
+                                                      group_start=[0, F], **(consensus or {}))
+        g = multiframe.group_result(mf)
+        status, n_good = g['status'], int(frame_ok.sum())
+        res['consensus'] = dict(inliers=[], rejected=[], n_inliers=g['n_inliers'], rounds=g['info'][3], flags=g['flags'], status=status)
+        if n_good < 2:
+            warnings.warn(f'{n_good} fitted frame(s): fitCylinderWPts3sAngs needs two')
+        elif status != 0:
+            warnings.warn(f'multi-frame consensus ended with status {status} (include/cpe.h: cpe_multi_frame_consensus_batch)')
+        else:
+            res['T_cam_agv'], res['fval'] = g['T'], g['fvals'][1]
+            res['consensus']['inliers'] = [names[i] for i in range(F) if g['inlier'][i] == 1]
+            res['consensus']['rejected'] = [dict(index=i, name=names[i], rms=math.sqrt(g['frame_terms'][i]))
+                                            for i in range(F) if g['inlier'][i] == 0]
+            if res['consensus']['rejected']:
+                warnings.warn('multi-frame consensus left out ' + ', '.join(f"{r['name']} (rms {r['rms']:.2f})"
+                                                                            for r in res['consensus']['rejected']))
     elif multi_frame:
         bad = {s['index'] for s in skipped}
         good = [i for i in range(F) if i not in bad]

@@ -65,6 +65,9 @@ _SIGS = {
     'cpe_multi_frame_terms': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     'cpe_multi_frame_fit_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p] + [C.c_void_p] * 9),
     'cpe_multi_frame_fit_lm_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p] + [C.c_void_p] * 10),
+    'cpe_multi_frame_consensus_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
+    'cpe_multi_frame_consensus_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_size_t] + [C.c_void_p] * 13),
     'cpe_pose_vec2T_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'cpe_pose_T2vec_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'cpe_agv_chain_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -154,6 +157,13 @@ class CpeTableTriParams(C.Structure):
 class CpeIndexShiftParams(C.Structure):
     _fields_ = [('win', C.c_int32 * 2), ('tau', C.c_double), ('min_score', C.c_int32), ('swap', C.c_int32)]
 
+
+class CpeConsensusParams(C.Structure):
+    _fields_ = [('tau', C.c_double), ('max_hyp', C.c_int32), ('max_rounds', C.c_int32), ('min_inliers', C.c_int32)]
+
+
+CONSENSUS_MAX_HYP = 4096
+CONSENSUS_CONVERGED, CONSENSUS_SHRUNK = 1, 2    # flags of cpe_multi_frame_consensus_batch (include/cpe.h)
 
 MAXP = 2048
 MAXL = 256

@@ -285,6 +285,32 @@ def _tol_params(tol_x=1e-5, tol_f=1e-5, max_iter=100000, max_fun_evals=100000):
     return _lib.CpeFitParams(tol_x, tol_f, max_iter, max_fun_evals, 0, 0)
 
 
+def _frame_tables(pts3, cnt, cyl_raw, angles, frame_ok, group_start):
+    """the frame tables of the resident multi-frame calls as the C ABI takes them: checked, contiguous, on the points' device
+    -> pts3, cnt, cyl_raw, TAGV f64[n,16], frame_ok (i32[n] or None), group_start i32[G+1], G"""
+    dev, n = pts3.device, cnt.shape[0]
+    pts3, cnt, cyl_raw = pts3.contiguous(), cnt.contiguous(), cyl_raw.contiguous()
+    assert pts3.dtype == torch.float64 and cyl_raw.dtype == torch.float64 and cnt.dtype == torch.int32
+    assert pts3.shape == (n, _lib.MAXP, 3) and cyl_raw.shape == (n, 2, 6)
+    if torch.is_tensor(angles):
+        TAGV = angles.to(device=dev, dtype=torch.float64).contiguous()
+        assert TAGV.shape == (n, 16), 'a tensor of angles is the [n,16] table of getTAGVcyl matrices'
+    else:
+        assert len(angles) == n
+        TAGV = torch.tensor([get_TAGVcyl(float(a[0]), float(a[1])) for a in angles], dtype=torch.float64).reshape(n, 16).to(dev)
+    if group_start is None:
+        group_start = [0, n]
+    if not torch.is_tensor(group_start):
+        group_start = torch.tensor(list(group_start), dtype=torch.int32)
+    gs = group_start.to(device=dev, dtype=torch.int32).contiguous()
+    G = gs.numel() - 1
+    assert G >= 0
+    if frame_ok is not None:
+        frame_ok = frame_ok.to(device=dev, dtype=torch.int32).contiguous()
+        assert frame_ok.shape == (n,)
+    return pts3, cnt, cyl_raw, TAGV, frame_ok, gs, G
+
+
 def fit_multi_frame_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=None, group_start=None, x0=None, method='nm', **tol):
     """fitCylinderWPts3sAngs for G groups of frames in one resident call (cpe_multi_frame_fit_batch): nothing is read back
     and the launch is queued on the current stream.  Arguments given on the host -- angles as pan / tilt pairs, a list for
@@ -306,25 +332,7 @@ def fit_multi_frame_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=None, group
     assert method in ('nm', 'lm')
     L = _lib.load()
     dev, n = pts3.device, cnt.shape[0]
-    pts3, cnt, cyl_raw = pts3.contiguous(), cnt.contiguous(), cyl_raw.contiguous()
-    assert pts3.dtype == torch.float64 and cyl_raw.dtype == torch.float64 and cnt.dtype == torch.int32
-    assert pts3.shape == (n, _lib.MAXP, 3) and cyl_raw.shape == (n, 2, 6)
-    if torch.is_tensor(angles):
-        TAGV = angles.to(device=dev, dtype=torch.float64).contiguous()
-        assert TAGV.shape == (n, 16), 'a tensor of angles is the [n,16] table of getTAGVcyl matrices'
-    else:
-        assert len(angles) == n
-        TAGV = torch.tensor([get_TAGVcyl(float(a[0]), float(a[1])) for a in angles], dtype=torch.float64).reshape(n, 16).to(dev)
-    if group_start is None:
-        group_start = [0, n]
-    if not torch.is_tensor(group_start):
-        group_start = torch.tensor(list(group_start), dtype=torch.int32)
-    gs = group_start.to(device=dev, dtype=torch.int32).contiguous()
-    G = gs.numel() - 1
-    assert G >= 0
-    if frame_ok is not None:
-        frame_ok = frame_ok.to(device=dev, dtype=torch.int32).contiguous()
-        assert frame_ok.shape == (n,)
+    pts3, cnt, cyl_raw, TAGV, frame_ok, gs, G = _frame_tables(pts3, cnt, cyl_raw, angles, frame_ok, group_start)
     if x0 is not None:
         x0 = torch.as_tensor(x0, dtype=torch.float64).to(dev).reshape(G, 6).contiguous()
     params = _tol_params(**tol)
@@ -347,15 +355,56 @@ def fit_multi_frame_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=None, group
     return out
 
 
+def fit_multi_frame_consensus_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=None, group_start=None, tau=0.5, max_hyp=2048,
+                                  max_rounds=4, min_inliers=3, **tol):
+    """Build-defined (cpe_multi_frame_consensus_batch; the rule is numbered in include/cpe.h): the LM form of the multi-frame fit
+    for experiments that hold frames with status 0 and a wrong cylinder.  Poses made of two usable frames each are scored by
+    the kept frames whose term at them lies below tau^2 (the rms of dist - radius below tau); the best pose's frames are fitted
+    by the LM loop of method='lm', the inliers are taken again, up to max_rounds times.  Two launches on the current stream,
+    nothing is read back.
+    pts3, cnt, cyl_raw, angles, radius, frame_ok, group_start, tol: as fit_multi_frame_gpu takes them
+    tau          in the unit of the points (> 0); max_hyp 1..4096 hypotheses per group; max_rounds 0..16; min_inliers >= 2: a
+                 consensus of fewer frames is refused (status 5)
+    -> dict of device tensors: x0, x, T, fvals, iters, n_used, status, TAGV as fit_multi_frame_gpu(method='lm') -- x0 the
+       winning hypothesis, fvals = [the objective of x0 over its inliers, of x over the frames x was fitted to], iters summed
+       over the rounds -- and n_inliers i32[G] (frames x was fitted to), info i32[G,4] = [winning hypothesis, its two frames,
+       rounds done], flags i32[G] (lib.CONSENSUS_CONVERGED | lib.CONSENSUS_SHRUNK), inlier i32[n] (1 / 0 for the kept frames of a
+       fitted group, -1 for every other frame), frame_terms f64[n] (the term of every kept frame of a fitted group at x,
+       outliers included; NaN for every other frame).  A majority of frames that are wrong in the same way wins; one tau per
+       call; a frame is in or out whole."""
+    L = _lib.load()
+    dev, n = pts3.device, cnt.shape[0]
+    pts3, cnt, cyl_raw, TAGV, frame_ok, gs, G = _frame_tables(pts3, cnt, cyl_raw, angles, frame_ok, group_start)
+    params = _tol_params(**tol)
+    params.mode = 1                                               # CPE_FIT_LM
+    cons = _lib.CpeConsensusParams(float(tau), int(max_hyp), int(max_rounds), int(min_inliers))
+    ws = torch.empty(max(1, L.cpe_multi_frame_consensus_workspace_bytes(G, cons.max_hyp)), dtype=torch.uint8, device=dev)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    out = dict(x0=f64(G, 6), x=f64(G, 6), T=f64(G, 16), fvals=f64(G, 2), iters=i32(G, 2), n_used=i32(G), n_inliers=i32(G),
+               info=i32(G, 4), flags=i32(G), status=i32(G), inlier=torch.full((n,), -1, dtype=torch.int32, device=dev),
+               frame_terms=torch.full((n,), float('nan'), dtype=torch.float64, device=dev), TAGV=TAGV)
+    _lib.check(L.cpe_multi_frame_consensus_batch(
+        pts3.data_ptr(), cnt.data_ptr(), TAGV.data_ptr(), cyl_raw.data_ptr(), frame_ok.data_ptr() if frame_ok is not None else None,
+        gs.data_ptr(), G, n, float(radius), ctypes.addressof(params), ctypes.addressof(cons), ws.data_ptr(), ws.numel(),
+        *(out[k].data_ptr() for k in ('x0', 'x', 'T', 'fvals', 'iters', 'n_used', 'n_inliers', 'info', 'flags', 'status', 'inlier',
+                                      'frame_terms')), torch.cuda.current_stream().cuda_stream), 'cpe_multi_frame_consensus_batch')
+    return out
+
+
 def group_result(res, g=0):
     """one group of fit_multi_frame_gpu's result on the host (this synchronises), with the keys of fit_multi_frame --
     T (flat row-major 4x4), x, x0, fvals [f0, f], iters, evals, TAGV (all frames' matrices) -- plus n_used and status, and
-    frame_terms (all frames') where the result has them (method='lm')"""
+    frame_terms (all frames') where the result has them (method='lm'); of fit_multi_frame_consensus_gpu's result also
+    n_inliers, info [hypothesis, frame, frame, rounds], flags and inlier (all frames')"""
     it = res['iters'][g].tolist()
     out = dict(T=res['T'][g].tolist(), x=res['x'][g].tolist(), x0=res['x0'][g].tolist(), fvals=res['fvals'][g].tolist(),
                iters=it[0], evals=it[1], TAGV=res['TAGV'].tolist(), n_used=int(res['n_used'][g]), status=int(res['status'][g]))
     if 'frame_terms' in res:
         out['frame_terms'] = res['frame_terms'].tolist()
+    if 'inlier' in res:
+        out.update(n_inliers=int(res['n_inliers'][g]), info=res['info'][g].tolist(), flags=int(res['flags'][g]),
+                   inlier=res['inlier'].tolist())
     return out
 
 

@@ -20,13 +20,14 @@
  *     fork to join) holds its set's mutex, so the library is thread-safe; CPE_SERIAL=1 in the environment keeps
  *     everything on the caller's stream.
  *   - Workspaces.  Every `ws` argument below (cpe_detect_workspace_bytes, cpe_fit_workspace_bytes,
- *     cpe_match_offset_workspace_bytes) is scratch in the full sense: what the block holds on entry is irrelevant to every
- *     output the call defines, so it needs no initialisation and no clearing between calls -- fresh memory, the leftovers of
- *     any earlier call (another batch size, and with it another layout, another target, another entry point) and arbitrary
- *     bytes all give the same results.  Each call initialises what it reads, and nothing is read or written at or beyond
- *     `ws_bytes`, the size the call was given: a block larger than the call needs keeps its tail.  What a call leaves in
- *     the block is defined only where this header says so (the CPE_PLANE_* planes, the line tables behind
- *     cpe_detect_line_tables / cpe_detect_results_*); it stays valid until the next call that is given the block.
+ *     cpe_match_offset_workspace_bytes, cpe_multi_frame_consensus_workspace_bytes) is scratch in the full sense: what the
+ *     block holds on entry is irrelevant to every output the call defines, so it needs no initialisation and no clearing
+ *     between calls -- fresh memory, the leftovers of any earlier call (another batch size, and with it another layout,
+ *     another target, another entry point) and arbitrary bytes all give the same results.  Each call initialises what it
+ *     reads, and nothing is read or written at or beyond `ws_bytes`, the size the call was given: a block larger than the
+ *     call needs keeps its tail.  What a call leaves in the block is defined only where this header says so (the CPE_PLANE_*
+ *     planes, the line tables behind cpe_detect_line_tables / cpe_detect_results_*); it stays valid until the next call that
+ *     is given the block.
  *     (tests/test_workspace_poison_gpu.py; the first writer of every buffer is listed in DESIGN.md section 3.)
  *   - every call is asynchronous on `stream` (a hipStream_t, passed as void*; NULL = default
  *     stream) and graph-capturable; no host synchronisation inside.
@@ -45,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 120   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 121   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -54,7 +55,8 @@ extern "C" {
                              cpe_frame_angles_lm_batch; 115: cpe_debug_region_hull; 116: cpe_match_offset_batch,
                              cpe_match_offset_workspace_bytes; 117: cpe_fit_plane_batch, cpe_index_planes_batch;
                              118: cpe_table_triangulate_batch; 119: cpe_fit_projector_model, cpe_projector_model_table;
-                             120: cpe_index_shift_batch) */
+                             120: cpe_index_shift_batch; 121: cpe_multi_frame_consensus_batch,
+                             cpe_multi_frame_consensus_workspace_bytes) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -929,6 +931,66 @@ CPE_API int32_t cpe_multi_frame_fit_lm_batch(
     const int32_t *frame_ok, const int32_t *group_start, int32_t G, int32_t n, double radius, const CpeFitParams *params,
     const double *x0_in,          /* f64[G,6] or NULL = the all-frame initial pose */
     double *x0, double *x, double *T, double *fvals, int32_t *iters, int32_t *n_used, int32_t *status,
+    double *frame_terms,          /* f64[n] or NULL */
+    void *stream);
+
+/* Row f-1, BUILD-DEFINED: the LM form with a consensus over FRAMES in front of it.  cpe_multi_frame_fit_lm_batch minimises a plain
+ * sum over every kept frame, and a frame can end with status 0 and a wrong cylinder; a few of them pull T_Cam_AGV away and nothing
+ * reports it.  Here poses made of two frames each are scored by the frames that agree with them, the best one's frames are
+ * fitted, and the frames that do not agree are reported.
+ *   X, cnt, TAGVcyl, cyl_raw (not NULL), frame_ok, group_start, G, n, radius, the kept frames, the clamping of
+ *   cnt, CPE_ST_OVERFLOW and the "usable" frame: exactly as cpe_multi_frame_fit_lm_batch; params as there (NULL, or mode
+ *   CPE_FIT_LM); cons NULL = the defaults of CpeConsensusParams, a value outside its ranges: CPE_ERR_ARG, nothing is written;
+ *   ws: cpe_multi_frame_consensus_workspace_bytes(G, max_hyp) bytes of 8-byte aligned device scratch (0 for G <= 0 or a max_hyp
+ *   outside its range), content on entry irrelevant (Conventions, "Workspaces"); missing or too small: CPE_ERR_WORKSPACE.
+ * term_f(x) below is frame f's term at the pose x with the bits of cpe_pose_vec2T_batch + cpe_multi_frame_terms, and the
+ * objective over a list of frames is their terms added in list order.  A kept frame is an INLIER of x when cnt >= 1 and
+ * term_f(x) < tau^2, i.e. the rms of its dist - radius is below tau.  Rule (the order is the contract), per group:
+ *   1. K = the kept frames (m of them), U = the usable ones among them in kept order, u = |U|; u < 2: CPE_ST_FEW_POINTS;
+ *   2. hypotheses: R = max(1, max_hyp div u); if R >= u div 2 then R = u div 2 and off_k = 1 + k (every unordered pair of U
+ *      occurs), otherwise off_k = 1 + ((2k + 1)(u div 2 - 1)) div (2R): R different offsets spread over 1..u div 2 - 1 (the
+ *      offsets off and u - off name the same pairs); H = min(R u, max_hyp); hypothesis h in 0..H-1 takes a = h mod
+ *      u, b = (a + off_(h div u)) mod u, and x_h = the closed-form initial pose of cpe_multi_frame_fit_lm_batch over the list
+ *      (U[a], U[b]): both sigma, the lower objective over that list kept, a tie to +1.  x_h or that objective not finite: void.
+ *      With the offset u/2 of an even u (R = u div 2 only) every pair occurs twice, as (a, b) and (b, a): the second, a >= u/2,
+ *      is void as well (two poses that differ by rounding alone would leave the winner to the last bits);
+ *   3. key_h = (-number of inliers of x_h, sum of their terms added in kept order, h); the smallest key of a hypothesis that is
+ *      not void wins: x0 = its pose, S_0 = its inliers.  No such hypothesis, or |S_0| < min_inliers: CPE_ST_FEW_POINTS;
+ *   4. for r = 1..max_rounds: x_r = cpe_multi_frame_fit_lm_batch's LM loop over the list S_(r-1) from x_(r-1) (its bits, with
+ *      frame_ok = the list and x0_in = x_(r-1)); S_r = the inliers of x_r among ALL kept frames; stop after round r when S_r =
+ *      S_(r-1) (CPE_CONSENSUS_CONVERGED) or when |S_r| < min_inliers (CPE_CONSENSUS_SHRUNK; x_r stays the result).  x = the
+ *      last x_r, or x0 with max_rounds = 0.  A start, result or objective that is not finite: CPE_ST_FEW_POINTS;
+ *   5. per group: x0, x f64[G,6]; T f64[G,16] = vec2T(x); fvals f64[G,2] = the objective of x0 over S_0 | of x over the list x was
+ *      fitted to; iters i32[G,2] = LM iterations | objective evaluations, each round counted as its cpe_multi_frame_fit_lm_batch
+ *      call would (the scoring of hypotheses and of inliers is not counted); n_used i32[G] = m; n_inliers i32[G] = the length
+ *      of the list x was fitted to; info i32[G,4] = winning h | frame U[a] | frame U[b] | rounds done; flags i32[G]
+ *      CPE_CONSENSUS_* (independent bits; neither: max_rounds ran out); status i32[G];
+ *   6. per frame, written only for the kept frames of groups that end CPE_ST_OK (initialise them; a frame kept by several groups
+ *      receives the values of one of them): inlier i32[n] = 1 when the frame is in the list x was fitted to, else 0;
+ *      frame_terms f64[n] or NULL = term_f(x) of every kept frame, outliers included;
+ *   7. a group that is not CPE_ST_OK has every other per-group output zero, so CPE_ST_OK implies finite outputs.
+ * Limits: the consensus is the largest set of frames that agree with ONE pose, so a majority of frames that are wrong in the
+ * same way wins; one tau per call; a frame is in or out whole (no per-point trimming here: that is cpe_fit_cylinder_ransac_batch's
+ * part); neighbouring frames with nearly equal pan and tilt make poor hypotheses -- they simply score low.
+ * Two launches on `stream` (one wavefront per (hypothesis, group), then one workgroup per group), vector stores only, no
+ * atomics, no allocation, no host synchronisation; two calls on the same inputs give the same bits; G == 0 is a no-op. */
+#define CPE_CONSENSUS_MAX_HYP 4096
+#define CPE_CONSENSUS_CONVERGED 1   /* a round returned the list of frames it was given */
+#define CPE_CONSENSUS_SHRUNK 2      /* a round left fewer than min_inliers inliers: its pose is returned, fitted to the list before */
+typedef struct CpeConsensusParams {
+    double  tau;          /* a frame agrees with a pose when its term < tau^2; the unit of the points; > 0; default 0.5 */
+    int32_t max_hyp;      /* hypotheses per group, 1..CPE_CONSENSUS_MAX_HYP; default 2048 */
+    int32_t max_rounds;   /* refinement rounds, 0..16; default 4 */
+    int32_t min_inliers;  /* a consensus of fewer frames is refused; >= 2; default 3 */
+} CpeConsensusParams;
+CPE_API size_t cpe_multi_frame_consensus_workspace_bytes(int32_t G, int32_t max_hyp);
+CPE_API int32_t cpe_multi_frame_consensus_batch(
+    const double *X, const int32_t *cnt, const double *TAGVcyl, const double *cyl_raw, /* [n,MAXP,3] [n] [n,16] [n,2,6] */
+    const int32_t *frame_ok, const int32_t *group_start, int32_t G, int32_t n, double radius, const CpeFitParams *params,
+    const CpeConsensusParams *cons, void *ws, size_t ws_bytes,
+    double *x0, double *x, double *T, double *fvals, int32_t *iters, int32_t *n_used, int32_t *n_inliers, int32_t *info,
+    int32_t *flags, int32_t *status,
+    int32_t *inlier,              /* i32[n] */
     double *frame_terms,          /* f64[n] or NULL */
     void *stream);
 
