@@ -3135,6 +3135,92 @@ __global__ __launch_bounds__(64) void k_planes_centre(const double *__restrict__
     }
 }
 
+// The one-camera rule of include/cpe.h cpe_table_triangulate_batch in pieces, shared by k_table_triangulate and
+// k_fused_triangulate: the same source lines, so the same bits.
+struct TriCam {
+    double R[9], o[3];              // rotation (rows) of Tc and the camera centre in camera-1 coordinates
+    double k0, k1, k2, k4, k5;
+};
+
+// R, t of Tc, the identity without one: the same arithmetic either way
+__device__ __forceinline__ void tri_cam(const double *__restrict__ K, const double *__restrict__ Tc, TriCam &c)
+{
+    double t[3] = {0, 0, 0};
+#pragma unroll
+    for (int a = 0; a < 9; a++) c.R[a] = (a % 4 == 0) ? 1.0 : 0.0;
+    if (Tc) {
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            c.R[3 * r] = Tc[4 * r]; c.R[3 * r + 1] = Tc[4 * r + 1]; c.R[3 * r + 2] = Tc[4 * r + 2];
+            t[r] = Tc[4 * r + 3];
+        }
+    }
+    c.k0 = K[0]; c.k1 = K[1]; c.k2 = K[2]; c.k4 = K[4]; c.k5 = K[5];
+#pragma unroll
+    for (int a = 0; a < 3; a++) c.o[a] = -((c.R[a] * t[0] + c.R[3 + a] * t[1]) + c.R[6 + a] * t[2]);
+}
+
+// step 2: the unit ray of pixel (x, y) in camera-1 coordinates
+__device__ __forceinline__ void tri_ray(const TriCam &c, double x, double y, double *d)
+{
+    const double vy = (y - c.k5) / c.k4;
+    const double vx = ((x - c.k2) - c.k1 * vy) / c.k0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) d[a] = (c.R[a] * vx + c.R[3 + a] * vy) + c.R[6 + a];
+    const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+#pragma unroll
+    for (int a = 0; a < 3; a++) d[a] = d[a] / dn;
+}
+
+// step 3: the usable planes of the indices v[2] -> bits; pl[c] is loaded for a set bit only
+__device__ __forceinline__ int tri_planes(const double *__restrict__ P, const int *__restrict__ line_status, int lo, int hi, int L, int swap,
+                                          const int *v, double (*pl)[4])
+{
+    int used = 0;
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        const int fam = c ^ swap;
+        if (v[c] < lo || v[c] > hi) continue;                              // (compared, not subtracted: v may be any int)
+        const int line = fam * L + (v[c] - lo);
+        if (line_status[line] != CPE_ST_OK) continue;
+#pragma unroll
+        for (int a = 0; a < 4; a++) pl[c][a] = P[(size_t)line * 4 + a];
+        used |= 1 << c;
+    }
+    return used;
+}
+
+// steps 4 - 7 for the ray (o, d) and the planes of `used`: -> accepted; early: refused in steps 1 / 4 / 5, otherwise in 6 / 7.
+// X and rs are written for an accepted point; rs of an unused plane stays as the caller set it
+__device__ __forceinline__ bool tri_cut(const double *o, const double *d, const double (*pl)[4], int used, bool pixel_ok, int need_both,
+                                        double min_sin2, double max_res, double *X, double *rs, bool &early)
+{
+    double den = 0, sab = 0;
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        if (!(used & (1 << c))) continue;
+        const double a_k = (pl[c][0] * d[0] + pl[c][1] * d[1]) + pl[c][2] * d[2];
+        const double b_k = ((pl[c][0] * o[0] + pl[c][1] * o[1]) + pl[c][2] * o[2]) + pl[c][3];
+        den = den + a_k * a_k;
+        sab = sab + a_k * b_k;
+    }
+    early = !pixel_ok || used == 0 || (need_both && used != 3) || den < min_sin2 || !isfinite(den);
+    if (early) return false;
+    const double s = -sab / den;
+    bool acc = s > 0 && isfinite(s);
+    if (acc) {
+#pragma unroll
+        for (int a = 0; a < 3; a++) X[a] = o[a] + s * d[a];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            if (!(used & (1 << c))) continue;
+            rs[c] = ((pl[c][0] * X[0] + pl[c][1] * X[1]) + pl[c][2] * X[2]) + pl[c][3];
+            if (max_res > 0 && fabs(rs[c]) > max_res) acc = false;
+        }
+    }
+    return acc;
+}
+
 // 3-D points from one camera and the laser-plane table (include/cpe.h cpe_table_triangulate_batch, whose numbered rule this
 // follows).  One lane per point, rounds of 64; the accepted points keep their table order: a ballot, the popcount of the lanes
 // below, and the base of the round carried on.  The table (at most 2 x 256 planes, 18 KB with the statuses) is read where a point
@@ -3151,19 +3237,8 @@ __global__ __launch_bounds__(64) void k_table_triangulate(const double *__restri
     const int n = min(max(cnt[f], 0), MAXP);
     const int L = hi - lo + 1;                     // 1..CPE_MAXL, checked by the host
     const size_t base = (size_t)f * MAXP;
-    // R (rows) and t of Tc, the identity without one: the same arithmetic either way
-    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
-    if (Tc) {
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            R[3 * r] = Tc[4 * r]; R[3 * r + 1] = Tc[4 * r + 1]; R[3 * r + 2] = Tc[4 * r + 2];
-            t[r] = Tc[4 * r + 3];
-        }
-    }
-    const double k0 = K[0], k1 = K[1], k2 = K[2], k4 = K[4], k5 = K[5];
-    double o[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) o[a] = -((R[a] * t[0] + R[3 + a] * t[1]) + R[6 + a] * t[2]);
+    TriCam cam;
+    tri_cam(K, Tc, cam);
     const unsigned long long below = (1ull << lane) - 1ull;
     int m = 0, both = 0, ref_a = 0, ref_b = 0;
     double r2 = 0, rmax = 0;
@@ -3175,44 +3250,10 @@ __global__ __launch_bounds__(64) void k_table_triangulate(const double *__restri
         if (in) {
             const double x = xy[(base + k) * 2], y = xy[(base + k) * 2 + 1];
             v[0] = id[(base + k) * 2]; v[1] = id[(base + k) * 2 + 1];
-            const double vy = (y - k5) / k4;
-            const double vx = ((x - k2) - k1 * vy) / k0;
-            double d[3];
-#pragma unroll
-            for (int a = 0; a < 3; a++) d[a] = (R[a] * vx + R[3 + a] * vy) + R[6 + a];
-            const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-#pragma unroll
-            for (int a = 0; a < 3; a++) d[a] = d[a] / dn;
-            double pl[2][4], den = 0, sab = 0;
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                const int fam = c ^ swap;
-                if (v[c] < lo || v[c] > hi) continue;                              // (compared, not subtracted: v may be any int)
-                const int line = fam * L + (v[c] - lo);
-                if (line_status[line] != CPE_ST_OK) continue;
-#pragma unroll
-                for (int a = 0; a < 4; a++) pl[c][a] = P[(size_t)line * 4 + a];
-                const double a_k = (pl[c][0] * d[0] + pl[c][1] * d[1]) + pl[c][2] * d[2];
-                const double b_k = ((pl[c][0] * o[0] + pl[c][1] * o[1]) + pl[c][2] * o[2]) + pl[c][3];
-                den = den + a_k * a_k;
-                sab = sab + a_k * b_k;
-                used |= 1 << c;
-            }
-            early = !(isfinite(x) && isfinite(y)) || used == 0 || (need_both && used != 3) || den < min_sin2 || !isfinite(den);
-            if (!early) {
-                const double s = -sab / den;
-                acc = s > 0 && isfinite(s);
-                if (acc) {
-#pragma unroll
-                    for (int a = 0; a < 3; a++) X[a] = o[a] + s * d[a];
-#pragma unroll
-                    for (int c = 0; c < 2; c++) {
-                        if (!(used & (1 << c))) continue;
-                        rs[c] = ((pl[c][0] * X[0] + pl[c][1] * X[1]) + pl[c][2] * X[2]) + pl[c][3];
-                        if (max_res > 0 && fabs(rs[c]) > max_res) acc = false;
-                    }
-                }
-            }
+            double d[3], pl[2][4];
+            tri_ray(cam, x, y, d);
+            used = tri_planes(P, line_status, lo, hi, L, swap, v, pl);
+            acc = tri_cut(cam.o, d, pl, used, isfinite(x) && isfinite(y), need_both, min_sin2, max_res, X, rs, early);
         }
         const unsigned long long bal = __ballot(acc);
         ref_a += __popcll(__ballot(in && early));
@@ -3237,6 +3278,220 @@ __global__ __launch_bounds__(64) void k_table_triangulate(const double *__restri
         o_counts[4 * f] = m; o_counts[4 * f + 1] = both; o_counts[4 * f + 2] = ref_a; o_counts[4 * f + 3] = ref_b;
         o_stats[2 * f] = m > 0 ? sqrt(r2 / (double)(m + both)) : 0.0;
         o_stats[2 * f + 1] = m > 0 ? rmax : 0.0;
+    }
+}
+
+// M += w2 (I - d d'), b += w2 (I - d d') o: a ray's part of the normal equations of "the point nearest to rays and planes"
+__device__ __forceinline__ void fused_add_ray(double w2, const double *d, const double *o, double *M, double *b)
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        double p[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            p[c] = (r == c ? 1.0 : 0.0) - d[r] * d[c];
+            M[3 * r + c] = M[3 * r + c] + w2 * p[c];
+        }
+        b[r] = b[r] + w2 * ((p[0] * o[0] + p[1] * o[1]) + p[2] * o[2]);
+    }
+}
+
+// distance of X from the ray (o, d) in pixels: the distance times k0 / s, s the depth of X along the ray
+__device__ __forceinline__ double fused_ray_res(const double *X, const double *o, const double *d, double k0)
+{
+    const double u0 = X[0] - o[0], u1 = X[1] - o[1], u2 = X[2] - o[2];
+    const double s = (u0 * d[0] + u1 * d[1]) + u2 * d[2];
+    const double p0 = u0 - s * d[0], p1 = u1 - s * d[1], p2 = u2 - s * d[2];
+    return sqrt((p0 * p0 + p1 * p1) + p2 * p2) * (k0 / s);
+}
+
+// Fused 3-D points: both cameras' rays and the laser planes in one solve (include/cpe.h cpe_fused_triangulate_batch, whose
+// numbered rule this follows).  One wavefront per frame.  The join goes through the dense (col,row) -> slot table of table 2,
+// 16-bit slot numbers in LDS (128 x 128 x 2 = 32768 B) beside a "taken" byte per slot of table 2 (2048 B: bytes, so that lanes
+// set them with plain stores): 34816 B in all.  The first occurrence of an index wins without an atomic: the rounds of table 2
+// are written from the last to the first, and inside a round a lane whose slot number is below the stored one writes again
+// until none is.  Then one loop of rounds of 64 candidates: the rounds of table 1 (paired or left-only), a barrier, the rounds
+// of table 2 (untaken entries, right-only); compaction as in k_table_triangulate.  The planes are read through L2, as there.
+constexpr int FUSED_EMPTY = 0xFFFF;
+__global__ __launch_bounds__(64) void k_fused_triangulate(
+    const double *__restrict__ xy1, const int *__restrict__ id1, const int *__restrict__ cnt1,
+    const double *__restrict__ xy2, const int *__restrict__ id2, const int *__restrict__ cnt2,
+    const double *__restrict__ K1, const double *__restrict__ K2, const double *__restrict__ T21,
+    const double *__restrict__ P, const int *__restrict__ line_status, int lo, int hi, int swap, int need_both, double min_sin2,
+    double sigma_px, double sigma_mm, double max_res, double max_px,
+    double *__restrict__ o_X, int *__restrict__ o_idx, double *__restrict__ o_res, int *__restrict__ o_src, int *__restrict__ o_m,
+    int *__restrict__ o_counts, double *__restrict__ o_stats, int *__restrict__ o_flags)
+{
+    __shared__ unsigned short sTbl[TBL * TBL];
+    __shared__ unsigned char sTaken[MAXP];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int n1 = min(max(cnt1[f], 0), MAXP), n2 = min(max(cnt2[f], 0), MAXP);
+    const int L = hi - lo + 1;                     // 1..CPE_MAXL, checked by the host
+    const size_t base = (size_t)f * MAXP;
+    const double *a1 = xy1 + base * 2, *a2 = xy2 + base * 2;
+    const int *i1 = id1 + base * 2, *i2 = id2 + base * 2;
+    const bool join = n1 > 0 && n2 > 0;
+    int cmin = 0, rmin = 0, tw = 0;
+    if (join) {
+        int cmax = INT_MIN, rmax = INT_MIN;
+        cmin = INT_MAX; rmin = INT_MAX;
+        for (int i = lane; i < n1; i += 64) {
+            const int c = i1[2 * i], r = i1[2 * i + 1];
+            cmin = min(cmin, c); cmax = max(cmax, c); rmin = min(rmin, r); rmax = max(rmax, r);
+        }
+        for (int i = lane; i < n2; i += 64) {
+            const int c = i2[2 * i], r = i2[2 * i + 1];
+            cmin = min(cmin, c); cmax = max(cmax, c); rmin = min(rmin, r); rmax = max(rmax, r);
+        }
+        cmin = wave_min_i(cmin); cmax = wave_max_i(cmax); rmin = wave_min_i(rmin); rmax = wave_max_i(rmax);
+        if ((long long)cmax - cmin >= TBL || (long long)rmax - rmin >= TBL || cmin < -9999 || cmax > 9999 || rmin < -9999 || rmax > 9999) {
+            if (lane == 0) {
+                o_m[f] = 0;
+#pragma unroll
+                for (int a = 0; a < 6; a++) o_counts[6 * f + a] = 0;
+#pragma unroll
+                for (int a = 0; a < 4; a++) o_stats[4 * f + a] = 0.0;
+                o_flags[f] = CPE_FIT_FLAG_OVERFLOW;
+            }
+            return;
+        }
+        tw = cmax - cmin + 1;
+        const int cells = tw * (rmax - rmin + 1);                                 // <= TBL * TBL
+        for (int i = lane; i < cells; i += 64) sTbl[i] = (unsigned short)FUSED_EMPTY;
+        for (int i = lane; i < n2; i += 64) sTaken[i] = 0;
+        __syncthreads();
+        for (int k0p = ((n2 - 1) / 64) * 64; k0p >= 0; k0p -= 64) {
+            const int k = k0p + lane;
+            bool pend = k < n2;
+            const int cell = pend ? (i2[2 * k + 1] - rmin) * tw + (i2[2 * k] - cmin) : 0;   // inside [0, cells): the range holds table 2
+            while (__ballot(pend)) {
+                if (pend) sTbl[cell] = (unsigned short)k;
+                __syncthreads();
+                if (pend) pend = (int)sTbl[cell] > k;
+                __syncthreads();
+            }
+        }
+    }
+    TriCam cam1, cam2;
+    tri_cam(K1, nullptr, cam1);
+    tri_cam(K2, T21, cam2);
+    const double wp2 = 1.0 / (sigma_mm * sigma_mm);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int rounds1 = (n1 + 63) / 64, rounds2 = (n2 + 63) / 64;
+    int m = 0, n_pair = 0, n_left = 0, n_right = 0, n_ref = 0, n_trunc = 0, n_rays = 0, n_planes = 0;
+    double ray2 = 0, raymax = 0, pl2 = 0, plmax = 0;
+    for (int round = 0; round < rounds1 + rounds2; round++) {
+        const bool second = round >= rounds1;                                     // wave-uniform: the pass over table 2
+        if (round == rounds1) __syncthreads();                                    // every "taken" byte of the first pass is written
+        const int k = (second ? round - rounds1 : round) * 64 + lane;
+        const double *xa = second ? a2 : a1;
+        const int *ia = second ? i2 : i1;
+        bool cand = k < (second ? n2 : n1), acc = false;
+        if (cand && second && join) cand = sTaken[k] == 0;
+        double X[3] = {0, 0, 0}, rs[4] = {0, 0, 0, 0};
+        int v[2] = {0, 0}, used = 0, j = -1, bits = 0;
+        if (cand) {
+            const double x = xa[2 * k], y = xa[2 * k + 1];
+            v[0] = ia[2 * k]; v[1] = ia[2 * k + 1];
+            if (!second && join) {
+                const int jj = sTbl[(v[1] - rmin) * tw + (v[0] - cmin)];          // inside the table: the range holds table 1 too
+                if (jj != FUSED_EMPTY) { j = jj; sTaken[j] = 1; }
+            }
+            TriCam cam;                                                            // wave-uniform selects, no address of either
+#pragma unroll
+            for (int a = 0; a < 9; a++) cam.R[a] = second ? cam2.R[a] : cam1.R[a];
+#pragma unroll
+            for (int a = 0; a < 3; a++) cam.o[a] = second ? cam2.o[a] : cam1.o[a];
+            cam.k0 = second ? cam2.k0 : cam1.k0; cam.k1 = second ? cam2.k1 : cam1.k1; cam.k2 = second ? cam2.k2 : cam1.k2;
+            cam.k4 = second ? cam2.k4 : cam1.k4; cam.k5 = second ? cam2.k5 : cam1.k5;
+            double d[3], pl[2][4];
+            tri_ray(cam, x, y, d);
+            used = tri_planes(P, line_status, lo, hi, L, swap, v, pl);
+            const bool px_ok = isfinite(x) && isfinite(y);
+            if (j < 0) {
+                bool early;
+                acc = tri_cut(cam.o, d, pl, used, px_ok, need_both, min_sin2, max_res, X, rs + 2, early);
+                bits = (second ? 2 : 1) | (used << 2);
+            } else {
+                const double x2 = a2[2 * j], y2 = a2[2 * j + 1];
+                double e[3], M[9], b[3], X0[3];
+                tri_ray(cam2, x2, y2, e);
+#pragma unroll
+                for (int a = 0; a < 9; a++) M[a] = 0;
+                b[0] = b[1] = b[2] = 0;
+                fused_add_ray(1.0, d, cam1.o, M, b);
+                fused_add_ray(1.0, e, cam2.o, M, b);
+                acc = px_ok && isfinite(x2) && isfinite(y2) && gauss_solve<3>(M, b, X0);
+                const double s1 = ((X0[0] - cam1.o[0]) * d[0] + (X0[1] - cam1.o[1]) * d[1]) + (X0[2] - cam1.o[2]) * d[2];
+                const double s2 = ((X0[0] - cam2.o[0]) * e[0] + (X0[1] - cam2.o[1]) * e[1]) + (X0[2] - cam2.o[2]) * e[2];
+                acc = acc && s1 > 0 && s2 > 0 && isfinite(s1) && isfinite(s2);
+                const double w1 = cam1.k0 / (s1 * sigma_px), w2 = cam2.k0 / (s2 * sigma_px);
+#pragma unroll
+                for (int a = 0; a < 9; a++) M[a] = 0;
+                b[0] = b[1] = b[2] = 0;
+                fused_add_ray(w1 * w1, d, cam1.o, M, b);
+                fused_add_ray(w2 * w2, e, cam2.o, M, b);
+#pragma unroll
+                for (int c = 0; c < 2; c++) {
+                    if (!(used & (1 << c))) continue;
+#pragma unroll
+                    for (int r = 0; r < 3; r++) {
+#pragma unroll
+                        for (int q = 0; q < 3; q++) M[3 * r + q] = M[3 * r + q] + wp2 * (pl[c][r] * pl[c][q]);
+                        b[r] = b[r] - wp2 * (pl[c][3] * pl[c][r]);
+                    }
+                }
+                acc = gauss_solve<3>(M, b, X) && acc && isfinite(X[0]) && isfinite(X[1]) && isfinite(X[2]);
+                rs[0] = fused_ray_res(X, cam1.o, d, cam1.k0);
+                rs[1] = fused_ray_res(X, cam2.o, e, cam2.k0);
+#pragma unroll
+                for (int c = 0; c < 2; c++)
+                    if (used & (1 << c)) rs[2 + c] = ((pl[c][0] * X[0] + pl[c][1] * X[1]) + pl[c][2] * X[2]) + pl[c][3];
+                acc = acc && isfinite(rs[0]) && isfinite(rs[1]) && rs[0] >= 0 && rs[1] >= 0 && isfinite(rs[2]) && isfinite(rs[3]);
+                if (max_px > 0 && (rs[0] > max_px || rs[1] > max_px)) acc = false;
+                if (max_res > 0 && (fabs(rs[2]) > max_res || fabs(rs[3]) > max_res)) acc = false;
+                bits = 3 | (used << 2);
+            }
+        }
+        const unsigned long long bal = __ballot(acc);
+        n_ref += __popcll(__ballot(cand && !acc));
+        const int slot = m + __popcll(bal & below);
+        const bool wr = acc && slot < MAXP;                                        // the table is full: the rest is counted and dropped
+        n_trunc += __popcll(__ballot(acc && !wr));
+        n_pair += __popcll(__ballot(wr && j >= 0));
+        n_left += __popcll(__ballot(wr && j < 0 && !second));
+        n_right += __popcll(__ballot(wr && second));
+        if (wr) {
+            const size_t o = base + (size_t)slot;
+            o_X[o * 3] = X[0]; o_X[o * 3 + 1] = X[1]; o_X[o * 3 + 2] = X[2];
+            o_idx[o * 2] = v[0]; o_idx[o * 2 + 1] = v[1];
+            o_res[o * 4] = rs[0]; o_res[o * 4 + 1] = rs[1]; o_res[o * 4 + 2] = rs[2]; o_res[o * 4 + 3] = rs[3];
+            o_src[o * 3] = bits; o_src[o * 3 + 1] = second ? j : k; o_src[o * 3 + 2] = second ? k : j;
+            ray2 = ray2 + (rs[0] * rs[0] + rs[1] * rs[1]);
+            raymax = fmax(raymax, fmax(rs[0], rs[1]));
+            pl2 = pl2 + (rs[2] * rs[2] + rs[3] * rs[3]);
+            plmax = fmax(plmax, fmax(fabs(rs[2]), fabs(rs[3])));
+        }
+        n_rays += 2 * __popcll(__ballot(wr && j >= 0));
+        n_planes += __popcll(__ballot(wr && (used & 1))) + __popcll(__ballot(wr && (used & 2)));
+        m = min(m + __popcll(bal), MAXP);
+    }
+    ray2 = wave_sum(ray2);
+    pl2 = wave_sum(pl2);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        raymax = fmax(raymax, __shfl_xor(raymax, off, 64));
+        plmax = fmax(plmax, __shfl_xor(plmax, off, 64));
+    }
+    if (lane == 0) {
+        o_m[f] = m;
+        o_counts[6 * f] = m; o_counts[6 * f + 1] = n_pair; o_counts[6 * f + 2] = n_left; o_counts[6 * f + 3] = n_right;
+        o_counts[6 * f + 4] = n_ref; o_counts[6 * f + 5] = n_trunc;
+        o_stats[4 * f] = n_rays > 0 ? sqrt(ray2 / (double)n_rays) : 0.0;
+        o_stats[4 * f + 1] = n_rays > 0 ? raymax : 0.0;
+        o_stats[4 * f + 2] = n_planes > 0 ? sqrt(pl2 / (double)n_planes) : 0.0;
+        o_stats[4 * f + 3] = n_planes > 0 ? plmax : 0.0;
+        o_flags[f] = n_trunc > 0 ? CPE_FUSED_FLAG_TRUNCATED : 0;
     }
 }
 // ------------------------------------------------------------------------------------------ projector model
@@ -3881,6 +4136,33 @@ extern "C" int32_t cpe_table_triangulate_batch(const double *xy, const int32_t *
     CPE_KLAUNCH(k_table_triangulate, dim3(n), dim3(64), 0, (hipStream_t)stream, xy, id, cnt, K, Tc, P, line_status, lo, hi, p.swap,
                 p.need_both, p.min_sin * p.min_sin, p.max_res, X, idx, res, src, m, counts, stats);
     CPE_CHECK_LAUNCH("k_table_triangulate");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_fused_triangulate_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
+                                               const int32_t *id2, const int32_t *cnt2, int32_t n, const double *K1, const double *K2,
+                                               const double *T21, const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
+                                               const CpeFusedTriParams *params, double *X, int32_t *idx, double *res, int32_t *src,
+                                               int32_t *m, int32_t *counts, double *stats, int32_t *flags, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_fused_triangulate_batch: n < 0");
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_fused_triangulate_batch: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    CpeFusedTriParams p = {0, 0, 0.01, 0.25, 0.02, 0.0, 0.0};
+    if (params) p = *params;
+    CPE_CHECK_ARG((p.swap == 0 || p.swap == 1) && (p.need_both == 0 || p.need_both == 1) && p.min_sin >= 0 && p.sigma_px > 0 &&
+                      p.sigma_px <= DBL_MAX && p.sigma_mm > 0 && p.sigma_mm <= DBL_MAX && !(p.max_res != p.max_res) && !(p.max_px != p.max_px),
+                  "cpe_fused_triangulate_batch: bad CpeFusedTriParams (swap, need_both 0 or 1, min_sin >= 0, sigma_px and sigma_mm "
+                  "positive and finite, max_res and max_px not NaN)");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(xy1 && id1 && cnt1 && xy2 && id2 && cnt2 && K1 && K2 && T21 && P && line_status && X && idx && res && src && m &&
+                      counts && stats && flags,
+                  "cpe_fused_triangulate_batch: null pointer");
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_fused_triangulate, dim3(n), dim3(64), 0, (hipStream_t)stream, xy1, id1, cnt1, xy2, id2, cnt2, K1, K2, T21, P, line_status,
+                lo, hi, p.swap, p.need_both, p.min_sin * p.min_sin, p.sigma_px, p.sigma_mm, p.max_res, p.max_px, X, idx, res, src, m, counts,
+                stats, flags);
+    CPE_CHECK_LAUNCH("k_fused_triangulate");
     return CPE_OK;
 }
 

@@ -193,6 +193,12 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     status is 0 in the records, and the dict gains tri_counts i32 [F,4] and tri_stats f64 [F,2] (fit.table_triangulate_batch's
     counts and stats).  The table's gates keep their defaults here; FramePipeline(table=...) sets them.
 
+    source='fused' with laser_table= (build-defined): both cameras' files are read and detected as for 'stereo', and every grid
+    point of either image becomes a 3-D point from its rays and the laser planes in one solve (FramePipeline(source='fused'),
+    fit.fit_single_cylinder_fused_batch): no selector, and a point that one camera alone found is kept.  Word 14 of a record is
+    the rms ray residual of the pairs in pixels; tri_counts is i32 [F,6] and tri_stats f64 [F,4] (fit.fused_triangulate_batch's).
+    match_offset is refused: the numbering is repaired before, not inside, this call.
+
     projector: None, or a dict of fit.fit_projector_model keywords ({} = its defaults; build-defined): the projector's model
     (two pencils of planes through one centre) is fitted to the experiment's own stereo points and indices -- after the index
     shift of match_offset where that is on -- over the frames the multi-frame fit would keep; no boards are needed.  The dict

@@ -485,6 +485,73 @@ def table_triangulate_batch(gp: GridTables, K, Tc, table: LaserTable, need_both=
     return dict(pts3=X, idx=idx, res=res, src=src, m=m, counts=counts, stats=stats)
 
 
+FUSED_TRUNCATED = 4                                                 # CPE_FUSED_FLAG_TRUNCATED (beside FLAG_OVERFLOW)
+FUSED_RAY1, FUSED_RAY2, FUSED_PLANE0, FUSED_PLANE1 = 1, 2, 4, 8     # bits of src[..., 0]
+
+
+def fused_triangulate_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, table: LaserTable, need_both=False, min_sin=0.01,
+                            sigma_px=0.25, sigma_mm=0.02, max_res=0.0, max_px=0.0, ids='col_row'):
+    """BUILD-DEFINED: 3-D points from both cameras' rays AND the laser-plane table in one weighted solve per point, see
+    include/cpe.h cpe_fused_triangulate_batch.  Every grid point of either table is a candidate: pairs (two rays and up to two
+    planes), then the points only one camera found (one ray and its planes, exactly table_triangulate_batch's point).
+    need_both, min_sin: for one-ray candidates; sigma_px, sigma_mm: the weights of a pair; max_res (mm), max_px (px): gates.
+    -> dict(pts3 f64[n,MAXP,3], idx i32[n,MAXP,2], res f64[n,MAXP,4] (px off ray 1, ray 2; mm off the plane of component 0, 1),
+            src i32[n,MAXP,3] (FUSED_* bits, slot in table 1 or -1, slot in table 2 or -1), m i32[n], counts i32[n,6] (m, pairs,
+            left-only, right-only, refused, truncated), stats f64[n,4] (rms, max ray residual in px; rms, max plane residual in
+            mm), flags i32[n] (FLAG_OVERFLOW, FUSED_TRUNCATED)); slots from m on hold zeros"""
+    L = _lib.load()
+    dev = gp1.xy.device
+    n = gp1.cnt.shape[0]
+    for g, gp in (('gp1', gp1), ('gp2', gp2)):
+        for name, t, dt, shape in (('xy', gp.xy, torch.float64, (n, MAXP, 2)), ('id', gp.id, torch.int32, (n, MAXP, 2)),
+                                   ('cnt', gp.cnt, torch.int32, (n,))):
+            if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
+                raise TypeError(f'fused_triangulate_batch: {g}.{name} must be {dt} {list(shape)} on {dev}, got {t.dtype} '
+                                f'{list(t.shape)} on {t.device}')
+    if not (sigma_px > 0 and sigma_mm > 0):
+        raise ValueError(f'fused_triangulate_batch: sigma_px and sigma_mm must be > 0, got {sigma_px} and {sigma_mm}')
+    K1 = _dev3(K1, dev, (9,)); K2 = _dev3(K2, dev, (9,)); T21 = _dev3(T21, dev, (16,))
+    P = table.P.to(device=dev, dtype=torch.float64).contiguous()
+    st = table.status.to(device=dev, dtype=torch.int32).contiguous()
+    f64 = torch.zeros(n * (MAXP * 7 + 4), dtype=torch.float64, device=dev)
+    X, res, stats = f64[:3 * MAXP * n].view(n, MAXP, 3), f64[3 * MAXP * n:7 * MAXP * n].view(n, MAXP, 4), f64[7 * MAXP * n:].view(n, 4)
+    i32 = torch.zeros(n * (MAXP * 5 + 8), dtype=torch.int32, device=dev)
+    idx, src = i32[:2 * MAXP * n].view(n, MAXP, 2), i32[2 * MAXP * n:5 * MAXP * n].view(n, MAXP, 3)
+    tail = i32[5 * MAXP * n:]
+    m, flags, counts = tail[:n], tail[n:2 * n], tail[2 * n:].view(n, 6)
+    prm = _lib.CpeFusedTriParams(table.swap_for(ids), int(bool(need_both)), float(min_sin), float(sigma_px), float(sigma_mm),
+                                 float(max_res), float(max_px))
+    c = lambda t: t.contiguous()
+    x1, d1, c1, x2, d2, c2 = c(gp1.xy), c(gp1.id), c(gp1.cnt), c(gp2.xy), c(gp2.id), c(gp2.cnt)
+    _lib.check(L.cpe_fused_triangulate_batch(x1.data_ptr(), d1.data_ptr(), c1.data_ptr(), x2.data_ptr(), d2.data_ptr(), c2.data_ptr(), n,
+                                             K1.data_ptr(), K2.data_ptr(), T21.data_ptr(), P.data_ptr(), st.data_ptr(), table.lo, table.hi,
+                                             C.addressof(prm), X.data_ptr(), idx.data_ptr(), res.data_ptr(), src.data_ptr(), m.data_ptr(),
+                                             counts.data_ptr(), stats.data_ptr(), flags.data_ptr(), _stream()),
+               'cpe_fused_triangulate_batch')
+    return dict(pts3=X, idx=idx, res=res, src=src, m=m, counts=counts, stats=stats, flags=flags)
+
+
+def fit_single_cylinder_fused_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, table: LaserTable, radius, ransac=None,
+                                    mode=FIT_NELDER_MEAD, need_both=False, min_sin=0.01, sigma_px=0.25, sigma_mm=0.02, max_res=0.0,
+                                    max_px=0.0, **fit_kw):
+    """BUILD-DEFINED, fit_single_cylinder_batch on fused points: fused_triangulate_batch, then fit_cylinder_batch (ransac: a dict
+    of fit_cylinder_ransac_batch keywords) on its points with cnt = m.
+    -> the fit's keys (cyl_raw, cyl, T, fvals, iters, status[, n_inliers, inlier_mask]) beside pts3, idx, m, counts, res, src,
+    stats, flags and mean_err f64[n] = stats[:, 0], the rms ray residual of the pairs in pixels.  status is ST_OVERFLOW where the
+    join set FLAG_OVERFLOW."""
+    tri = fused_triangulate_batch(gp1, gp2, K1, K2, T21, table, need_both=need_both, min_sin=min_sin, sigma_px=sigma_px,
+                                  sigma_mm=sigma_mm, max_res=max_res, max_px=max_px)
+    if ransac is not None:
+        fit = fit_cylinder_ransac_batch(tri['pts3'], tri['m'], radius, mode=mode, **ransac, **fit_kw)
+    else:
+        fit = fit_cylinder_batch(tri['pts3'], tri['m'], radius, mode=mode, **fit_kw)
+    fit['status'].masked_fill_((tri['flags'] & FLAG_OVERFLOW) != 0, ST_OVERFLOW)
+    out = dict(tri)
+    out.update(fit)
+    out['mean_err'] = tri['stats'][:, 0]
+    return out
+
+
 SHIFT_MAX_WIN = 8                                                   # CPE_SHIFT_MAX_WIN
 SHIFT_SHIFTED, SHIFT_WEAK, SHIFT_EDGE = 1, 2, 4                     # CPE_SHIFT_FLAG_*
 

@@ -82,6 +82,8 @@ _SIGS = {
                                [C.c_void_p] * 8),
     'cpe_table_triangulate_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] +
                                     [C.c_void_p] * 9),
+    'cpe_fused_triangulate_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32] +
+                                    [C.c_void_p] * 10),
     'cpe_fit_projector_model': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
                                 [C.c_void_p] * 10),
     'cpe_projector_model_table': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
@@ -152,6 +154,11 @@ class CpeProjectorModelParams(C.Structure):
 
 class CpeTableTriParams(C.Structure):
     _fields_ = [('swap', C.c_int32), ('need_both', C.c_int32), ('min_sin', C.c_double), ('max_res', C.c_double)]
+
+
+class CpeFusedTriParams(C.Structure):
+    _fields_ = [('swap', C.c_int32), ('need_both', C.c_int32), ('min_sin', C.c_double), ('sigma_px', C.c_double),
+                ('sigma_mm', C.c_double), ('max_res', C.c_double), ('max_px', C.c_double)]
 
 
 class CpeIndexShiftParams(C.Structure):

@@ -54,23 +54,28 @@ class FramePipeline:
         self.stage = stage              # 'detect': stop after chooseIdx + triangulate (fitSingleCylinder.m:12-17), no cylinder fit
         # source 'left' / 'right' (build-defined): only that camera's images are detected, and the points come from its rays and the
         # laser-plane table (fit.fit_single_cylinder_mono_batch) instead of the stereo pair; camera 2 uses K2 and T21
-        if source not in ('stereo', 'left', 'right'):
-            raise ValueError("source is 'stereo', 'left' or 'right'")
+        # source 'fused' (build-defined): both cameras' images are detected as for 'stereo', and every grid point of either table
+        # becomes a 3-D point from its rays and the laser planes in one solve (fit.fit_single_cylinder_fused_batch); no selector
+        if source not in ('stereo', 'left', 'right', 'fused'):
+            raise ValueError("source is 'stereo', 'left', 'right' or 'fused'")
         if source == 'stereo':
             if laser_table is not None or table is not None:
                 raise ValueError("laser_table= and table= belong to one camera: source='left' or 'right'")
         else:
             if laser_table is None:
-                raise ValueError(f"source='{source}' needs laser_table= (a fit.LaserTable): one camera has no other way to a 3-D point")
+                raise ValueError(f"source='{source}' needs laser_table= (a fit.LaserTable)" +
+                                 ('' if source == 'fused' else ': one camera has no other way to a 3-D point'))
             if match is not None:
-                raise ValueError(f"source='{source}': match searches the index shift between two tables, there is one")
+                raise ValueError(f"source='{source}': match searches the index shift between two tables, there is one" if source != 'fused'
+                                 else "source='fused': match feeds the stereo selector; repair the numbering first (fit.match_offset_batch)")
             if target == 'plane':
                 raise ValueError(f"source='{source}': target='plane' builds the table from stereo points and does not read one")
             if stage == 'detect':
                 raise ValueError(f"source='{source}': stage='detect' ends at the stereo selector")
             laser_table = laser_table.to(self.device)
         self.source, self.laser_table = source, laser_table
-        self.table = dict(table or {})  # keywords of fit.table_triangulate_batch: need_both, min_sin, max_res
+        # keywords of fit.table_triangulate_batch: need_both, min_sin, max_res; source 'fused': of fit.fused_triangulate_batch
+        self.table = dict(table or {})
         self.ws = {}
         # chunks are independent: `lanes` of them are in flight on their own HIP streams (each with its own
         # workspace), so the serial tails of one chunk (blob grouping, line fitting: one workgroup per frame)
@@ -114,7 +119,7 @@ class FramePipeline:
     def run_chunk(self, left, right, lane=0, frame0=0):
         """-> records f64 [c,16], the detect call's dict, the fit's dict.  With source 'left' / 'right' only that argument is
         read (the other may be None) and the detect call sees c images, not 2c"""
-        if self.source != 'stereo':
+        if self.source in ('left', 'right'):
             return self._run_chunk_mono(left if self.source == 'left' else right, lane, frame0)
         c = left.shape[0]
         if c > 0 and self._interleaved(left, right):
@@ -131,6 +136,17 @@ class FramePipeline:
             g1 = fit.GridTables(det['xy'][:c], det['id'][:c], det['n'][:c])
             g2 = fit.GridTables(det['xy'][c:], det['id'][c:], det['n'][c:])
             st_l, st_r = det['status'][:c], det['status'][c:]
+        if self.source == 'fused':
+            rk = None if self.ransac is None else dict(self.ransac, frame0=int(self.ransac.get('frame0', 0)) + frame0)
+            out = fit.fit_single_cylinder_fused_batch(g1, g2, self.K1, self.K2, self.T21, self.laser_table, self.radius, ransac=rk,
+                                                      mode=self.fit_mode, **self.table)
+            rec = torch.empty((c, REC), dtype=torch.float64, device=frames.device)
+            rec[:, 0:6] = out['cyl'][:, 0]
+            rec[:, 6:12] = out['cyl'][:, 1]
+            rec[:, 12:14] = out['fvals']
+            rec[:, 14] = out['mean_err']          # rms ray residual of the pairs in pixels (fit.fit_single_cylinder_fused_batch)
+            rec[:, 15] = pack_counters(out['m'], out['iters'][:, 0], out['status'], st_l, st_r)
+            return rec, det, out
         if self.stage == 'detect':      # BASELINE configs[1]: grid detection + triangulation only
             out = fit.select_triangulate_batch(g1, g2, self.K1, self.K2, self.T21, self.selector, 3, self.th)
             rec = torch.zeros((c, REC), dtype=torch.float64, device=frames.device)
@@ -162,7 +178,7 @@ class FramePipeline:
 
     def run(self, left, right):
         """left/right: u8 [F,h,w] on the device -> records f64 [F,16] (source 'left' / 'right': the other one may be None)"""
-        if self.source != 'stereo':
+        if self.source in ('left', 'right'):
             one = left if self.source == 'left' else right
             return self._for_chunks(one.shape[0], one.device, lambda i0, i1, lane: self._run_chunk_mono(one[i0:i1], lane, i0)[0])
         return self._for_chunks(left.shape[0], left.device, lambda i0, i1, lane: self.run_chunk(left[i0:i1], right[i0:i1], lane, i0)[0])
@@ -217,7 +233,7 @@ class FramePipeline:
                 for k, t in fits.items():
                     t[i0:i1] = out[k]
             return rec
-        if self.source != 'stereo':
+        if self.source in ('left', 'right'):
             one = left_raw if self.source == 'left' else right_raw
             return self._for_chunks(one.shape[0], one.device, body_mono)
 
@@ -251,8 +267,19 @@ MONO_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2),
                         res=((fit.MAXP, 2), torch.float64), src=((fit.MAXP, 2), torch.int32), stats=((2,), torch.float64))
 
 
+FUSED_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2), torch.int32), m=((), torch.int32),
+                         cyl_raw=((2, 6), torch.float64), cyl=((2, 6), torch.float64), T=((4, 4), torch.float64), fvals=((2,), torch.float64),
+                         mean_err=((), torch.float64), status=((), torch.int32), counts=((6,), torch.int32),
+                         res=((fit.MAXP, 4), torch.float64), src=((fit.MAXP, 3), torch.int32), stats=((4,), torch.float64),
+                         flags=((), torch.int32))
+
+
 def alloc_fits(F, device, target='cylinder', source='stereo'):
     """zeroed [F, ...] tensors for the per-frame outputs of fit.fit_single_cylinder_batch (target='plane': of
-    fit.fit_single_plane_batch; source 'left' / 'right': of fit.fit_single_cylinder_mono_batch) that FramePipeline.run_raw can keep"""
-    outputs = dict(cylinder=FIT_OUTPUTS, plane=PLANE_FIT_OUTPUTS)[target] if source == 'stereo' else MONO_FIT_OUTPUTS
+    fit.fit_single_plane_batch; source 'left' / 'right': of fit.fit_single_cylinder_mono_batch; source 'fused': of
+    fit.fit_single_cylinder_fused_batch) that FramePipeline.run_raw can keep"""
+    if source == 'fused':
+        outputs = FUSED_FIT_OUTPUTS
+    else:
+        outputs = dict(cylinder=FIT_OUTPUTS, plane=PLANE_FIT_OUTPUTS)[target] if source == 'stereo' else MONO_FIT_OUTPUTS
     return {k: torch.zeros((F,) + shape, dtype=dt, device=device) for k, (shape, dt) in outputs.items()}

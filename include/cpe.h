@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 121   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 122   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -56,7 +56,7 @@ extern "C" {
                              cpe_match_offset_workspace_bytes; 117: cpe_fit_plane_batch, cpe_index_planes_batch;
                              118: cpe_table_triangulate_batch; 119: cpe_fit_projector_model, cpe_projector_model_table;
                              120: cpe_index_shift_batch; 121: cpe_multi_frame_consensus_batch,
-                             cpe_multi_frame_consensus_workspace_bytes) */
+                             cpe_multi_frame_consensus_workspace_bytes; 122: cpe_fused_triangulate_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -760,6 +760,71 @@ CPE_API int32_t cpe_table_triangulate_batch(const double *xy, const int32_t *id,
                                             const double *Tc, const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
                                             const CpeTableTriParams *params, double *X, int32_t *idx, double *res, int32_t *src,
                                             int32_t *m, int32_t *counts, double *stats, void *stream);
+
+/* BUILD-DEFINED, opt-in: FUSED 3-D points.  The projector is a third view: a grid point seen by both cameras on two known
+ * planes of light has 2 + 2 + 2 constraints on its 3 unknowns, a point seen by one camera still 4.  This call uses all of them:
+ * every grid point of either table becomes a candidate, not only the pairs a selector kept, and every point carries a
+ * three-view residual.  One wavefront per frame, one launch, no atomics, no workspace, no host synchronisation; two calls on the
+ * same inputs give the same bits.
+ *   xy1, id1, cnt1, xy2, id2, cnt2, K1, K2, T21: as cpe_select_triangulate_batch (K1, K2, T21 in DEVICE memory)
+ *   P f64[2,L,4], line_status i32[2,L], lo, hi: exactly what cpe_table_triangulate_batch reads; L = hi - lo + 1 in 1..CPE_MAXL
+ *     (otherwise CPE_ERR_ARG)
+ *   params NULL = the defaults of CpeFusedTriParams
+ * Rule (the order is the contract):
+ *   1. cnt1, cnt2 are clamped to [0, CPE_MAXP]; slots past them are never read.  With both tables non-empty the indices of both
+ *      go through a dense CPE_FIT_TABLE_DIM x CPE_FIT_TABLE_DIM table, and a frame that fails the limits of
+ *      cpe_select_triangulate_batch (a span >= CPE_FIT_TABLE_DIM in either direction, or an |index| > 9999) is skipped with
+ *      CPE_FIT_FLAG_OVERFLOW, m = 0, counts and stats 0 and nothing written to the per-point outputs.  A frame with an empty
+ *      table needs no join and has no such limit: an index may be any int, as in cpe_table_triangulate_batch;
+ *   2. join by equal (id[0], id[1]), as CPE_SEL_JOIN does: an entry of table 1 pairs with the FIRST entry of table 2 that has its
+ *      index; later duplicates of table 1 pair with the same partner (findGridCorrespondences).  An entry of table 2 is "taken"
+ *      when any entry of table 1 paired with it; a later duplicate in table 2 is never taken;
+ *   3. candidates, in this order: every entry of table 1 in table order, paired or left-only; then every untaken entry of table 2
+ *      in table order, right-only.  A candidate with a non-finite pixel coordinate in a ray it would use is refused;
+ *   4. rays (o_j, d_j): step 2 of cpe_table_triangulate_batch with Tc = NULL for camera 1 and Tc = T21 for camera 2.  Planes:
+ *      step 3 of that rule, from the candidate's own index (a pair has one index);
+ *   5. start point X0.  Paired: the unweighted least-squares point of the two rays, sum_j (I - d_j d_j')(X0 - o_j) = 0, by
+ *      Gaussian elimination with partial pivoting; a zero pivot is refused.  One ray: steps 4 - 7 of
+ *      cpe_table_triangulate_batch (need_both, min_sin, s > 0 and the max_res gate included), by the same device function, so
+ *      the same bits; that point is also the final point, and steps 6 and 7 below do not apply to it;
+ *   6. paired only: s_j = (X0 - o_j).d_j; s_j <= 0 or not finite: refused.  w_j = K_j[0] / (s_j sigma_px): a pixel of sigma_px at
+ *      the depth s_j, as a distance from the ray; w_p = 1 / sigma_mm for each usable plane.  A pair needs no plane (need_both and
+ *      min_sin are for one-ray candidates).  One solve, no iteration:
+ *        [sum_j w_j^2 (I - d_j d_j') + sum_k w_p^2 n_k n_k'] X = sum_j w_j^2 (I - d_j d_j') o_j - sum_k w_p^2 P4_k n_k;
+ *      a zero pivot or a non-finite X is refused;
+ *   7. residuals of a pair: res[0], res[1] = the distance of X from ray 1, ray 2 times K_j[0] / s_j, s_j = (X - o_j).d_j
+ *      (pixels); res[2], res[3] = n_k.X + P4_k of the plane of component 0, 1 (mm), 0 for an unused plane.  A residual that is
+ *      not finite, or a ray residual below 0 (X behind that camera), refuses the pair, so no NaN is written.  max_px > 0 and a ray
+ *      residual > max_px, or max_res > 0 and a used |plane residual| > max_res: refused.  A one-ray point lies on its ray: its
+ *      res[0], res[1] are 0 and max_px does not apply; res[2], res[3] are the res of cpe_table_triangulate_batch;
+ *   8. accepted candidates go, in candidate order, to slots 0..m-1 of X f64[n,CPE_MAXP,3], idx i32[n,CPE_MAXP,2] (the
+ *      candidate's index), res f64[n,CPE_MAXP,4] and src i32[n,CPE_MAXP,3]: src[0] bit 0 = ray 1 used, bit 1 = ray 2, bit 2 = the
+ *      plane of component 0, bit 3 = the plane of component 1; src[1] = the slot in table 1 or -1; src[2] = the slot in table 2
+ *      or -1.  Slots from m on are NOT written.  Accepted candidates past CPE_MAXP are dropped, counted in counts[5], and the
+ *      frame gets CPE_FUSED_FLAG_TRUNCATED;
+ *   9. m i32[n]; counts i32[n,6] = m | written pairs | written left-only | written right-only | refused candidates | truncated;
+ *      stats f64[n,4] = rms | max of the ray residuals of the written pairs (pixels; two per pair), rms | max |.| of the plane
+ *      residuals over the used planes of the written points (mm); each pair of them is 0 without such a constraint;
+ *      flags i32[n] = CPE_FIT_FLAG_OVERFLOW | CPE_FUSED_FLAG_TRUNCATED.
+ * The outputs may not overlap the inputs.  n == 0 is a no-op.
+ * Limits: the weights come from the one start point, there is no reweighting; one sigma_mm for the whole table; the points
+ * inherit the table's errors; the call does not re-number: a mis-numbered frame is repaired first (cpe_match_offset_batch between
+ * the images, cpe_index_shift_batch against the table). */
+#define CPE_FUSED_FLAG_TRUNCATED 4 /* more than CPE_MAXP candidates were accepted: the last ones are dropped (counts[5]) */
+typedef struct CpeFusedTriParams {
+    int32_t swap;       /* as in CpeTableTriParams */
+    int32_t need_both;  /* as in CpeTableTriParams: one-ray candidates only */
+    double  min_sin;    /* as in CpeTableTriParams, default 0.01: one-ray candidates only */
+    double  sigma_px;   /* standard deviation of a pixel coordinate, > 0, default 0.25 */
+    double  sigma_mm;   /* standard deviation of a point's distance from a plane of the table, > 0, default 0.02 */
+    double  max_res;    /* mm; > 0: refuse a candidate with a used |plane residual| above it; <= 0 (default): no gate */
+    double  max_px;     /* px; > 0: refuse a pair with a ray residual above it; <= 0 (default): no gate */
+} CpeFusedTriParams;
+CPE_API int32_t cpe_fused_triangulate_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
+                                            const int32_t *id2, const int32_t *cnt2, int32_t n, const double *K1, const double *K2,
+                                            const double *T21, const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
+                                            const CpeFusedTriParams *params, double *X, int32_t *idx, double *res, int32_t *src,
+                                            int32_t *m, int32_t *counts, double *stats, int32_t *flags, void *stream);
 
 /* BUILD-DEFINED: re-number STEREO frames against a laser-plane table.  cpe_match_offset_batch makes the two images of a frame
  * agree with each other; a frame that is then numbered a line off in both images alike carries indices that mean other planes
