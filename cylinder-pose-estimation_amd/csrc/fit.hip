@@ -4238,3 +4238,355 @@ extern "C" int32_t cpe_index_shift_batch(const double *X, const int32_t *idx, co
     CPE_CHECK_LAUNCH("k_index_shift");
     return CPE_OK;
 }
+
+// ------------------------------------------------------------------------------------------ re-labelling of the planar tables
+// BUILD-DEFINED (include/cpe.h cpe_grid_relabel_batch, whose numbered rule this follows).  One workgroup of two wavefronts per
+// image, wavefront c works on id component c in its own half of the LDS (36.3 KB in all) and the two meet at two barriers: after
+// the label spans (either may flag the image) and before the points are written (a point needs both its lines).  Reproducible
+// bits: the slots of a label are grouped stably -- integer counts per label, a prefix, then the slot lists filled in rounds of
+// 64 slots with ranks from ballots -- and one lane per line sums its list from first to last, the reference's order.  Sorting and
+// medians of at most 256 lines are ranks by counting; a local median is over at most four values and is taken in registers
+// behind a fixed network (no indexed register array: the k_index_shift note on scratch); prefixes run in four rounds of 64 with a
+// carried base.
+namespace {
+constexpr int RL_L = CPE_MAXL;
+
+struct RelabelLds {
+    unsigned short list[CPE_MAXP];  // the usable slots grouped by label, in slot order inside a group
+    int cnt[RL_L];                  // bin (label - smallest label) -> points
+    int cur[RL_L];                  // bin -> where its next slot goes; after the fill: the end of its list
+    int slot[RL_L];                 // bin -> line slot (the labels seen, ascending), -1 for an empty bin
+    int bin[RL_L];                  // line slot -> bin
+    int N[RL_L], state[RL_L], index[RL_L];   // per line slot
+    int ord[RL_L];                  // position in the order of rule 4 -> line slot (supported lines)
+    int ord2[RL_L];                 // the same of the remaining lines (rule 6)
+    int pre[RL_L];                  // remaining line -> the sum of the inc before it
+    double p[RL_L];                 // per line slot
+    double gap[RL_L];
+    double med[2];
+};
+
+// LDS operations of one wavefront complete in order; the fence keeps the compiler from moving them across
+__device__ __forceinline__ void rl_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// (s[(m-1)/2] + s[m/2]) / 2 of the sorted v[0..m), m >= 1: ranks by counting in (value, position) order
+__device__ double rl_median(const double *v, int m, double *med, int lane)
+{
+    for (int i = lane; i < m; i += 64) {
+        const double x = v[i];
+        int r = 0;
+        for (int j = 0; j < m; j++) {
+            const double y = v[j];
+            r += (y < x || (y == x && j < i)) ? 1 : 0;
+        }
+        if (r == (m - 1) / 2) med[0] = x;
+        if (r == m / 2) med[1] = x;
+    }
+    rl_sync();
+    const double out = (med[0] + med[1]) / 2.0;
+    rl_sync();
+    return out;
+}
+
+__device__ __forceinline__ void rl_cswap(double &a, double &b)
+{
+    const double lo = a < b ? a : b, hi = a < b ? b : a;
+    a = lo; b = hi;
+}
+
+__global__ __launch_bounds__(128) void k_grid_relabel(const double *__restrict__ xy, const int *__restrict__ id, const int *__restrict__ cnt,
+                                                      const double *__restrict__ center, int swap, int min_pts, double merge_frac, int dir0,
+                                                      int dir1, double *__restrict__ o_xy, int *__restrict__ o_id, int *__restrict__ o_cnt,
+                                                      int *__restrict__ o_src, int *__restrict__ o_lines, double *__restrict__ o_linep,
+                                                      double *__restrict__ o_pitch, int *__restrict__ o_counts, int *__restrict__ o_flags)
+{
+    __shared__ RelabelLds S[2];
+    __shared__ int s_ovf[2], s_few[2], s_lmin[2];
+    const int f = blockIdx.x, c = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    RelabelLds &W = S[c];
+    const int n = min(max(cnt[f], 0), MAXP);
+    const size_t base = (size_t)f * MAXP;
+    const double cx = center[2 * (size_t)f], cy = center[2 * (size_t)f + 1];
+    const int iu = (c ^ swap) == 0 ? 1 : 0, it = 1 - iu;         // which pixel coordinate positions the lines of this component
+    const double tc = iu ? cx : cy, uc = iu ? cy : cx;
+    const size_t oc = (size_t)f * 2 + c;
+
+    // rules 1, 2: the label span of the usable points
+    int lmin = INT_MAX, lmax = INT_MIN;
+    for (int k = lane; k < n; k += 64) {
+        if (!(isfinite(xy[(base + k) * 2]) && isfinite(xy[(base + k) * 2 + 1]))) continue;
+        const int v = id[(base + k) * 2 + c];
+        lmin = min(lmin, v); lmax = max(lmax, v);
+    }
+    lmin = wave_min_i(lmin); lmax = wave_max_i(lmax);
+    if (lane == 0) {
+        s_ovf[c] = (lmin <= lmax && (long long)lmax - (long long)lmin >= (long long)RL_L) ? 1 : 0;
+        s_lmin[c] = lmin;
+    }
+    __syncthreads();
+    const int bad = ((isfinite(cx) && isfinite(cy)) ? 0 : CPE_RELABEL_FLAG_NO_CENTRE) | ((s_ovf[0] | s_ovf[1]) ? CPE_RELABEL_FLAG_OVERFLOW : 0);
+    if (bad) {                                                   // (uniform over the workgroup)
+        if (lane < 4) o_counts[oc * 4 + lane] = 0;
+        if (lane == 0) {
+            o_pitch[oc] = 0.0;
+            if (c == 0) { o_cnt[f] = 0; o_flags[f] = bad; }
+        }
+        return;
+    }
+
+    // points per label, the lists' starts and the line slots
+    for (int i = lane; i < RL_L; i += 64) W.cnt[i] = 0;
+    rl_sync();
+    for (int k = lane; k < n; k += 64) {
+        if (!(isfinite(xy[(base + k) * 2]) && isfinite(xy[(base + k) * 2 + 1]))) continue;
+        atomicAdd(&W.cnt[id[(base + k) * 2 + c] - lmin], 1);
+    }
+    rl_sync();
+    int nl = 0;
+    {
+        int pbase = 0;
+        for (int r = 0; r < RL_L / 64; r++) {
+            const int b = r * 64 + lane, cn = W.cnt[b];
+            int incl = cn;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int t = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += t;
+            }
+            W.cur[b] = pbase + incl - cn;
+            const unsigned long long bal = __ballot(cn > 0);
+            const int sl = nl + __popcll(bal & lt);
+            W.slot[b] = cn > 0 ? sl : -1;
+            if (cn > 0) W.bin[sl] = b;
+            pbase += __shfl(incl, 63, 64);
+            nl += __popcll(bal);
+        }
+    }
+    rl_sync();
+    // the lists, in rounds of 64 slots: the lanes of one label take their places by their rank among themselves
+    for (int k0 = 0; k0 < n; k0 += 64) {
+        const int k = k0 + lane;
+        int b = -1;
+        if (k < n && isfinite(xy[(base + k) * 2]) && isfinite(xy[(base + k) * 2 + 1])) b = id[(base + k) * 2 + c] - lmin;
+        unsigned long long todo = __ballot(b >= 0);
+        while (todo) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const int lb = __shfl(b, leader, 64);
+            const unsigned long long same = __ballot(b == lb);
+            if (b == lb) {
+                const int at = W.cur[lb];
+                W.list[at + __popcll(same & lt)] = (unsigned short)k;
+                if (lane == leader) W.cur[lb] = at + __popcll(same);
+            }
+            rl_sync();
+            todo &= ~same;
+        }
+    }
+    rl_sync();
+
+    // rule 3: one lane per line
+    for (int ls = lane; ls < nl; ls += 64) {
+        const int b = W.bin[ls], N = W.cnt[b], l0 = W.cur[b] - N;
+        double st = 0.0, su = 0.0;
+        for (int j = 0; j < N; j++) {
+            const size_t k = base + W.list[l0 + j];
+            st = st + xy[k * 2 + it]; su = su + xy[k * 2 + iu];
+        }
+        const double tm = st / (double)N, um = su / (double)N;
+        double Stt = 0.0, Stu = 0.0;
+        for (int j = 0; j < N; j++) {
+            const size_t k = base + W.list[l0 + j];
+            const double dt = xy[k * 2 + it] - tm, du = xy[k * 2 + iu] - um;
+            Stt = Stt + dt * dt; Stu = Stu + dt * du;
+        }
+        const double a = Stu / Stt, p = um + a * (tc - tm);
+        const bool has_p = Stt > 0.0 && isfinite(p);
+        W.p[ls] = has_p ? p : 0.0;
+        W.N[ls] = N;
+        W.state[ls] = (has_p && N >= min_pts) ? CPE_RELABEL_LINE_KEPT : CPE_RELABEL_LINE_UNSUPPORTED;
+        W.index[ls] = 0;
+    }
+    rl_sync();
+
+    // rule 4: the order by (p, label), a line slot being a label's rank; pitch0
+    int ns = 0;
+    for (int r = 0; r < RL_L / 64; r++) {
+        const int ls = r * 64 + lane;
+        ns += __popcll(__ballot(ls < nl && W.state[ls] == CPE_RELABEL_LINE_KEPT));
+    }
+    for (int ls = lane; ls < nl; ls += 64) {
+        if (W.state[ls] != CPE_RELABEL_LINE_KEPT) continue;
+        const double p = W.p[ls];
+        int rk = 0;
+        for (int j = 0; j < nl; j++) {
+            const double q = W.p[j];
+            rk += (W.state[j] == CPE_RELABEL_LINE_KEPT && (q < p || (q == p && j < ls))) ? 1 : 0;
+        }
+        W.ord[rk] = ls;
+    }
+    rl_sync();
+    for (int i = lane; i < ns - 1; i += 64) W.gap[i] = W.p[W.ord[i + 1]] - W.p[W.ord[i]];
+    rl_sync();
+    const double pitch0 = ns >= 2 ? rl_median(W.gap, ns - 1, W.med, lane) : 0.0;
+
+    // rule 5: phantoms, all judged on the list of rule 4; the remaining lines are compacted in order
+    const double thr = merge_frac * pitch0;
+    int nr = 0;
+    for (int r = 0; r < RL_L / 64; r++) {
+        const int i = r * 64 + lane;
+        bool keep = false;
+        int ls = 0;
+        if (i < ns) {
+            ls = W.ord[i];
+            const int Ni = W.N[ls];
+            bool ph = false;
+            if (i > 0 && W.gap[i - 1] < thr && W.N[W.ord[i - 1]] >= Ni) ph = true;
+            if (i < ns - 1 && W.gap[i] < thr && W.N[W.ord[i + 1]] > Ni) ph = true;
+            keep = !ph;
+            if (ph) W.state[ls] = CPE_RELABEL_LINE_PHANTOM;
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (keep) W.ord2[nr + __popcll(bal & lt)] = ls;
+        nr += __popcll(bal);
+    }
+    rl_sync();
+
+    if (nr >= 1) {
+        // rule 6: gaps, local pitches, increments and their prefix
+        for (int i = lane; i < nr - 1; i += 64) W.gap[i] = W.p[W.ord2[i + 1]] - W.p[W.ord2[i]];
+        rl_sync();
+        const double med_all = nr >= 2 ? rl_median(W.gap, nr - 1, W.med, lane) : 0.0;
+        const int ng = nr - 1;
+        int carry = 0;
+        for (int r = 0; r < RL_L / 64; r++) {
+            const int i = r * 64 + lane;
+            int inc = 0;
+            if (i < ng) {
+                const double g = W.gap[i];
+                double v0 = INFINITY, v1 = INFINITY, v2 = INFINITY, v3 = INFINITY;
+                int have = 0;
+                if (i - 2 >= 0) { v0 = W.gap[i - 2]; have++; }
+                if (i - 1 >= 0) { v1 = W.gap[i - 1]; have++; }
+                if (i + 1 < ng) { v2 = W.gap[i + 1]; have++; }
+                if (i + 2 < ng) { v3 = W.gap[i + 2]; have++; }
+                rl_cswap(v0, v1); rl_cswap(v2, v3); rl_cswap(v0, v2); rl_cswap(v1, v3); rl_cswap(v1, v2);   // missing ones go last
+                const double pi = have < 2 ? med_all : have == 2 ? (v0 + v1) / 2.0 : have == 3 ? v1 : (v1 + v2) / 2.0;
+                inc = 1;
+                if (pi > 0.0) {
+                    const double q = floor(g / pi + 0.5);
+                    if (q >= (double)CPE_RELABEL_MAX_INC) inc = CPE_RELABEL_MAX_INC;
+                    else if (q > 1.0) inc = (int)q;
+                }
+            }
+            int incl = inc;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int t = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += t;
+            }
+            W.pre[i] = carry + incl - inc;
+            carry += __shfl(incl, 63, 64);
+        }
+        // rule 7: the anchor, the first in order among the nearest
+        double bd = INFINITY;
+        int bi = INT_MAX;
+        for (int i = lane; i < nr; i += 64) {
+            const double d = fabs(W.p[W.ord2[i]] - uc);
+            if (bi == INT_MAX || d < bd) { bd = d; bi = i; }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double od = __shfl_xor(bd, off, 64);
+            const int oi = __shfl_xor(bi, off, 64);
+            if (oi != INT_MAX && (bi == INT_MAX || od < bd || (od == bd && oi < bi))) { bd = od; bi = oi; }
+        }
+        rl_sync();
+        const int pa = W.pre[bi], dirc = c ? dir1 : dir0;
+        for (int i = lane; i < nr; i += 64) W.index[W.ord2[i]] = dirc * (W.pre[i] - pa);
+    }
+    rl_sync();
+
+    for (int ls = lane; ls < nl; ls += 64) {
+        const size_t o = oc * RL_L + ls;
+        o_lines[o * 4] = lmin + W.bin[ls]; o_lines[o * 4 + 1] = W.index[ls]; o_lines[o * 4 + 2] = W.N[ls]; o_lines[o * 4 + 3] = W.state[ls];
+        o_linep[o] = W.p[ls];
+    }
+    if (lane == 0) {
+        o_counts[oc * 4] = nl; o_counts[oc * 4 + 1] = ns; o_counts[oc * 4 + 2] = ns - nr; o_counts[oc * 4 + 3] = nr;
+        o_pitch[oc] = pitch0;
+        s_few[c] = nr == 0 ? (CPE_RELABEL_FLAG_FEW_LINES << c) : 0;
+    }
+    __syncthreads();
+    if (c == 1) return;
+
+    // rule 8: wavefront 0 writes the points whose two lines are kept, in slot order
+    const int lmin0 = s_lmin[0], lmin1 = s_lmin[1];
+    int m = 0;
+    for (int k0 = 0; k0 < n; k0 += 64) {
+        const int k = k0 + lane;
+        bool wr = false;
+        double x = 0.0, y = 0.0;
+        int i0 = 0, i1 = 0;
+        if (k < n) {
+            x = xy[(base + k) * 2]; y = xy[(base + k) * 2 + 1];
+            if (isfinite(x) && isfinite(y)) {
+                const int s0 = S[0].slot[id[(base + k) * 2] - lmin0], s1 = S[1].slot[id[(base + k) * 2 + 1] - lmin1];
+                wr = S[0].state[s0] == CPE_RELABEL_LINE_KEPT && S[1].state[s1] == CPE_RELABEL_LINE_KEPT;
+                i0 = S[0].index[s0]; i1 = S[1].index[s1];
+            }
+        }
+        const unsigned long long bal = __ballot(wr);
+        if (wr) {
+            const size_t at = base + m + __popcll(bal & lt);
+            o_xy[at * 2] = x; o_xy[at * 2 + 1] = y;
+            o_id[at * 2] = i0; o_id[at * 2 + 1] = i1;
+            o_src[at] = k;
+        }
+        m += __popcll(bal);
+    }
+    if (lane == 0) { o_cnt[f] = m; o_flags[f] = s_few[0] | s_few[1]; }
+}
+
+// do two byte ranges share a byte?
+bool rl_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+}  // namespace
+
+extern "C" int32_t cpe_grid_relabel_batch(const double *xy, const int32_t *id, const int32_t *cnt, const double *center, int32_t n,
+                                          const CpeRelabelParams *params, double *xy_out, int32_t *id_out, int32_t *cnt_out, int32_t *src,
+                                          int32_t *lines, double *line_p, double *pitch, int32_t *counts, int32_t *flags, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_grid_relabel_batch: n < 0");
+    CpeRelabelParams p = {0, 3, 0.65, {1, 1}};
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.min_pts >= 2 && p.merge_frac > 0.0 && p.merge_frac < 1.0 && (p.swap == 0 || p.swap == 1) &&
+                      (p.dir[0] == 1 || p.dir[0] == -1) && (p.dir[1] == 1 || p.dir[1] == -1),
+                  "cpe_grid_relabel_batch: bad CpeRelabelParams (min_pts >= 2, 0 < merge_frac < 1, swap 0 or 1, dir +-1)");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(xy && id && cnt && center && xy_out && id_out && cnt_out && src && lines && line_p && pitch && counts && flags,
+                  "cpe_grid_relabel_batch: null pointer");
+    {
+        const size_t N = (size_t)n, P = (size_t)CPE_MAXP, L = (size_t)CPE_MAXL;
+        const struct { const void *p; size_t bytes; } buf[13] = {
+            {xy, N * P * 16}, {id, N * P * 8}, {cnt, N * 4}, {center, N * 16},
+            {xy_out, N * P * 16}, {id_out, N * P * 8}, {cnt_out, N * 4}, {src, N * P * 4}, {lines, N * 2 * L * 16}, {line_p, N * 2 * L * 8},
+            {pitch, N * 16}, {counts, N * 32}, {flags, N * 4}};
+        for (int o = 4; o < 13; o++)
+            for (int i = 0; i < o; i++)
+                CPE_CHECK_ARG(!rl_overlap(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes),
+                              "cpe_grid_relabel_batch: an output overlaps an input or another output");
+    }
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_grid_relabel, dim3(n), dim3(128), 0, (hipStream_t)stream, xy, id, cnt, center, p.swap, p.min_pts, p.merge_frac, p.dir[0],
+                p.dir[1], xy_out, id_out, cnt_out, src, lines, line_p, pitch, counts, flags);
+    CPE_CHECK_LAUNCH("k_grid_relabel");
+    return CPE_OK;
+}

@@ -339,7 +339,7 @@ PLANE_CENTRE_RMS_WARN = 1.0     # mm
 
 
 def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_rounds=4, min_spread=1e-4, device='cuda:0', chunk=32,
-                         table_path=None, projector=None):
+                         table_path=None, projector=None, relabel=None):
     """BUILD-DEFINED (the reference stops at the planar detector): a folder of `<name>L.png` / `<name>R.png` pairs of a flat board
     in several poses -> the board's plane and pose in every frame, and the projector's laser-plane table with its centre.
 
@@ -355,7 +355,7 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
     score a correspondence); the table does: laser planes of a consistent numbering meet in the
     projector's centre to hundredths of a millimetre (0.02 mm rms on 12 analytic poses with 0.25 px noise).  A table whose
     centre is refused, or whose planes miss it by more than PLANE_CENTRE_RMS_WARN = 1 mm rms, raises a UserWarning, and
-    `consistent` is False: do not calibrate from such a result.
+    `consistent` is False: do not calibrate from such a result.  relabel= (below) lifts this on rendered boards.
 
     -> dict(names, records f64 [F,16] (the planar layout beside pipeline.REC), P f64 [F,4], T f64 [F,4,4], grid f64 [F,3,3],
             stats f64 [F,8], pts3 f64 [F,MAXP,3], idx i32 [F,MAXP,2], cnt i32 [F], n_inliers i32 [F], inlier_mask u8 [F,MAXP],
@@ -371,12 +371,22 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
     same points, masks and frames as well.  The dict gains projector and projector_shifted as in run_experiment (family0 'row'),
     and projector_renumbered with projector['renumber'];
     laser_table and the file at table_path are then the MODEL's table, and consistent says that the model was fitted and its
-    rms is within PLANE_CENTRE_RMS_WARN.  `table` stays the free table of fit.index_planes_batch."""
+    rms is within PLANE_CENTRE_RMS_WARN.  `table` stays the free table of fit.index_planes_batch.
+
+    relabel: None, or a dict of fit.grid_relabel_batch keywords ({} = its defaults): every image's grid lines are re-labelled
+    from their geometry before the two images are paired by index (FramePipeline(relabel=...)), which is what lifts the LIMIT
+    above on boards.  The dict gains relabel = dict(counts i32 [F,2,2,4] (frame, image, id component: labels seen, supported,
+    phantoms, kept), flags i32 [F,2] (fit.RELABEL_*)).  It composes with projector= unchanged."""
     names, paths = _list_pairs(input_path)
     dev = torch.device(device)
-    recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, lambda F: pipeline.alloc_fits(F, dev, 'plane'),
+    def make_fits(F):
+        fits = pipeline.alloc_fits(F, dev, 'plane')
+        if relabel is not None:
+            fits.update({k: torch.zeros((F,) + shape, dtype=dt, device=dev) for k, (shape, dt) in pipeline.RELABEL_OUTPUTS.items()})
+        return fits
+    recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, make_fits,
                             lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, 0.0, chunk=c, device=dev, target='plane',
-                                                                   plane=dict(tau=tau, max_rounds=max_rounds)))
+                                                                   plane=dict(tau=tau, max_rounds=max_rounds), relabel=relabel))
     F = len(names)
     _, _, d_fit, d_l, d_r = pipeline.unpack_counters(recs[:, 15])
     frame_ok = ((d_fit == 0) & (d_l == 0) & (d_r == 0)).to(torch.int32)
@@ -422,6 +432,8 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
             extra['projector_renumbered'] = renumbered
     else:
         extra = {}
+    if relabel is not None:
+        extra['relabel'] = dict(counts=fits['relabel_counts'], flags=fits['relabel_flags'])
     return dict(**extra, **dict(names=names, records=recs, P=fits['P'], T=fits['T'], grid=fits['grid'], stats=fits['stats'], pts3=fits['pts3'],
                 idx=fits['idx'], cnt=fits['m'], n_inliers=fits['n_inliers'], inlier_mask=fits['inlier_mask'],
                 plane_flags=fits['plane_flags'], skipped=skipped, table=table, consistent=consistent,

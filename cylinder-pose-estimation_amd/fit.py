@@ -275,16 +275,84 @@ def index_planes_batch(pts3, idx, cnt, lo, hi, use=None, frame_ok=None, min_spre
     return dict(P=P, stats=stats, count=count, frames=frames, status=st, centre=centre, centre_status=cst, lo=int(lo), hi=int(hi))
 
 
+RELABEL_NO_CENTRE, RELABEL_OVERFLOW, RELABEL_FEW_LINES = 1, 2, 4    # CPE_RELABEL_FLAG_* (FEW_LINES << c for id component c)
+LINE_KEPT, LINE_UNSUPPORTED, LINE_PHANTOM = 0, 1, 2                 # CPE_RELABEL_LINE_*
+
+
+def grid_relabel_batch(tables: GridTables, center, swap=0, min_pts=3, merge_frac=0.65, dir=(1, 1)):
+    """BUILD-DEFINED: the planar detector's tables with their grid lines re-labelled from the geometry, per image -- the labels'
+    grouping is kept, their values are replaced by the lines' order across the centre stepped by the measured pitch, phantom
+    lines and their points are dropped.  See include/cpe.h cpe_grid_relabel_batch.  center f64[n,2] (x, y) as
+    api.detect_grid_batch returns it; swap 0: id component 0 is positioned in y (the planar detector's (row, col)).
+    -> dict(tables (GridTables, compacted; slots from cnt on hold zeros), src i32[n,MAXP] (the slot every written slot came
+            from), lines dict(label, index, points, state i32[n,2,MAXL], p f64[n,2,MAXL]; per line slot = the labels seen,
+            ascending; zeros from counts[..., 0] on), pitch f64[n,2], counts i32[n,2,4] (labels seen, supported, phantoms, kept),
+            flags i32[n] (RELABEL_*))"""
+    L = _lib.load()
+    n = tables.cnt.shape[0]
+    dev = tables.xy.device
+    for name, t, dt, shape in (('xy', tables.xy, torch.float64, (n, MAXP, 2)), ('id', tables.id, torch.int32, (n, MAXP, 2)),
+                               ('cnt', tables.cnt, torch.int32, (n,)), ('center', center, torch.float64, (n, 2))):
+        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
+            raise TypeError(f'grid_relabel_batch: {name} must be {dt} {list(shape)} on {dev}, got {t.dtype} {list(t.shape)} on {t.device}')
+    dir = tuple(int(d) for d in dir)
+    if len(dir) != 2 or not all(d in (1, -1) for d in dir):
+        raise ValueError(f'grid_relabel_batch: dir {dir} must be two of +1, -1')
+    if int(swap) not in (0, 1) or int(min_pts) < 2 or not 0.0 < float(merge_frac) < 1.0:
+        raise ValueError(f'grid_relabel_batch: swap {swap} must be 0 or 1, min_pts {min_pts} >= 2, merge_frac {merge_frac} in (0, 1)')
+    xy, ids, cnt, center = tables.xy.contiguous(), tables.id.contiguous(), tables.cnt.contiguous(), center.contiguous()
+    ML = _lib.MAXL
+    xy_o = torch.zeros((n, MAXP, 2), dtype=torch.float64, device=dev)
+    i32 = torch.zeros(n * (2 * MAXP + MAXP + 2 * ML * 4 + 8 + 2), dtype=torch.int32, device=dev)
+    at = [0]
+
+    def take(k, *shape):
+        t = i32[at[0]:at[0] + k].view(*shape)
+        at[0] += k
+        return t
+    id_o, src, lines = take(2 * n * MAXP, n, MAXP, 2), take(n * MAXP, n, MAXP), take(8 * n * ML, n, 2, ML, 4)
+    counts, cnt_o, flags = take(8 * n, n, 2, 4), take(n, n), take(n, n)
+    f64 = torch.zeros(n * (2 * ML + 2), dtype=torch.float64, device=dev)
+    line_p, pitch = f64[:2 * n * ML].view(n, 2, ML), f64[2 * n * ML:].view(n, 2)
+    prm = _lib.CpeRelabelParams(int(swap), int(min_pts), float(merge_frac), (C.c_int32 * 2)(*dir))
+    _lib.check(L.cpe_grid_relabel_batch(xy.data_ptr(), ids.data_ptr(), cnt.data_ptr(), center.data_ptr(), n, C.addressof(prm),
+                                        xy_o.data_ptr(), id_o.data_ptr(), cnt_o.data_ptr(), src.data_ptr(), lines.data_ptr(),
+                                        line_p.data_ptr(), pitch.data_ptr(), counts.data_ptr(), flags.data_ptr(), _stream()),
+               'cpe_grid_relabel_batch')
+    return dict(tables=GridTables(xy_o, id_o, cnt_o), src=src,
+                lines=dict(label=lines[..., 0], index=lines[..., 1], points=lines[..., 2], state=lines[..., 3], p=line_p),
+                pitch=pitch, counts=counts, flags=flags)
+
+
+def _cat_tables(g1: GridTables, g2: GridTables):
+    return GridTables(torch.cat([g1.xy, g2.xy]), torch.cat([g1.id, g2.id]), torch.cat([g1.cnt, g2.cnt]))
+
+
 def fit_single_plane_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, selector=SEL_CHOOSE_IDX, patch=3, th=0.3, tau=0.0,
-                           max_rounds=4):
+                           max_rounds=4, relabel=None, center1=None, center2=None):
     """the planar counterpart of fit_single_cylinder_batch: select_triangulate_batch, then fit_plane_batch on its points and
     indices.  Returns the selector's outputs beside the fit's; status is the fit's, or ST_OVERFLOW where the selector set
-    FLAG_OVERFLOW (such a frame has m = 0, so all its fit outputs are zero)."""
+    FLAG_OVERFLOW (such a frame has m = 0, so all its fit outputs are zero).
+    relabel (BUILD-DEFINED): None, or a dict of grid_relabel_batch keywords ({} = its defaults): both images' tables are
+    re-labelled in one call (center1, center2 f64[n,2]: the two images' centres as the detect call returns them) before the
+    selector reads them; the result gains relabel_counts i32[n,2,2,4] and relabel_flags i32[n,2] (frame, image, ...)."""
+    rl = None
+    if relabel is not None:
+        if center1 is None or center2 is None:
+            raise ValueError('fit_single_plane_batch: relabel needs center1 and center2, the centres of both images')
+        n = gp1.cnt.shape[0]
+        rl = grid_relabel_batch(_cat_tables(gp1, gp2), torch.cat([center1, center2]), **relabel)
+        t = rl['tables']
+        gp1, gp2 = GridTables(t.xy[:n], t.id[:n], t.cnt[:n]), GridTables(t.xy[n:], t.id[n:], t.cnt[n:])
     sel = select_triangulate_batch(gp1, gp2, K1, K2, T21, selector, patch, th)
     fit = fit_plane_batch(sel['pts3'], sel['idx'], sel['m'], tau=tau, max_rounds=max_rounds)
     fit['status'].masked_fill_((sel['flags'] & FLAG_OVERFLOW) != 0, ST_OVERFLOW)
     out = dict(sel)
     out.update(fit)
+    if rl is not None:
+        n = gp1.cnt.shape[0]
+        out['relabel_counts'] = torch.stack([rl['counts'][:n], rl['counts'][n:]], 1)
+        out['relabel_flags'] = torch.stack([rl['flags'][:n], rl['flags'][n:]], 1)
     return out
 
 

@@ -88,6 +88,7 @@ _SIGS = {
                                 [C.c_void_p] * 10),
     'cpe_projector_model_table': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
     'cpe_index_shift_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] + [C.c_void_p] * 8),
+    'cpe_grid_relabel_batch': (C.c_int32, [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 11),
     'cpe_undistort_map': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_remap_bilinear_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_undistort_map_matlab': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -163,6 +164,10 @@ class CpeFusedTriParams(C.Structure):
 
 class CpeIndexShiftParams(C.Structure):
     _fields_ = [('win', C.c_int32 * 2), ('tau', C.c_double), ('min_score', C.c_int32), ('swap', C.c_int32)]
+
+
+class CpeRelabelParams(C.Structure):
+    _fields_ = [('swap', C.c_int32), ('min_pts', C.c_int32), ('merge_frac', C.c_double), ('dir', C.c_int32 * 2)]
 
 
 class CpeConsensusParams(C.Structure):

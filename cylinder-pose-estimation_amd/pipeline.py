@@ -35,7 +35,7 @@ class FramePipeline:
 
     def __init__(self, h, w, K1, K2, T21, radius, chunk=64, device='cuda:0', selector=fit.SEL_CHOOSE_IDX, th=0.3,
                  fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full', match=None, target='cylinder', plane=None,
-                 source='stereo', laser_table=None, table=None):
+                 source='stereo', laser_table=None, table=None, relabel=None):
         self.h, self.w, self.chunk, self.device = h, w, chunk, torch.device(device)
         self.K1, self.K2, self.T21, self.radius = K1, K2, T21, radius
         self.selector, self.th, self.fit_mode = selector, th, fit_mode
@@ -51,6 +51,12 @@ class FramePipeline:
             raise ValueError("plane= holds keywords of the planar fit: target='plane' only")
         self.target = target            # 'plane' (build-defined): the planar detector and fit.fit_single_plane_batch; records as beside REC
         self.plane = dict(plane or {})  # keywords of fit.fit_plane_batch: tau, max_rounds
+        # relabel (build-defined): None, or keywords of fit.grid_relabel_batch ({} = its defaults): both images' tables are
+        # re-labelled from the lines' geometry and the detect call's centres before the selector pairs them by index
+        if relabel is not None and target != 'plane':
+            raise ValueError("relabel= re-labels straight grid lines: target='plane' only (the cylinder's lines are curved, and "
+                             "the cylinder script numbers them differently)")
+        self.relabel = None if relabel is None else dict(relabel)
         self.stage = stage              # 'detect': stop after chooseIdx + triangulate (fitSingleCylinder.m:12-17), no cylinder fit
         # source 'left' / 'right' (build-defined): only that camera's images are detected, and the points come from its rays and the
         # laser-plane table (fit.fit_single_cylinder_mono_batch) instead of the stereo pair; camera 2 uses K2 and T21
@@ -130,12 +136,14 @@ class FramePipeline:
             g1 = fit.GridTables(sl('xy', 0), sl('id', 0), sl('n', 0))
             g2 = fit.GridTables(sl('xy', 1), sl('id', 1), sl('n', 1))
             st_l, st_r = det['status'][0::2], det['status'][1::2]
+            ctr = (sl('center', 0), sl('center', 1))
         else:
             frames = torch.cat([left, right])             # [2c,h,w]: one detect call for both cameras (a copy)
             det = api.detect_grid_batch(frames, self._ws(2 * c, lane), target=self.target, debug_planes=False)   # only the tables are read
             g1 = fit.GridTables(det['xy'][:c], det['id'][:c], det['n'][:c])
             g2 = fit.GridTables(det['xy'][c:], det['id'][c:], det['n'][c:])
             st_l, st_r = det['status'][:c], det['status'][c:]
+            ctr = (det['center'][:c], det['center'][c:])
         if self.source == 'fused':
             rk = None if self.ransac is None else dict(self.ransac, frame0=int(self.ransac.get('frame0', 0)) + frame0)
             out = fit.fit_single_cylinder_fused_batch(g1, g2, self.K1, self.K2, self.T21, self.laser_table, self.radius, ransac=rk,
@@ -155,7 +163,8 @@ class FramePipeline:
             rec[:, 15] = pack_counters(out['m'], zero, zero, st_l, st_r)
             return rec, det, out
         if self.target == 'plane':
-            out = fit.fit_single_plane_batch(g1, g2, self.K1, self.K2, self.T21, self.selector, 3, self.th, **self.plane)
+            rl = {} if self.relabel is None else dict(relabel=self.relabel, center1=ctr[0], center2=ctr[1])
+            out = fit.fit_single_plane_batch(g1, g2, self.K1, self.K2, self.T21, self.selector, 3, self.th, **self.plane, **rl)
             rec = torch.empty((c, REC), dtype=torch.float64, device=frames.device)
             rec[:, 0:4] = out['P']
             rec[:, 4:7] = out['T'][:, :3, 3]
@@ -259,6 +268,11 @@ PLANE_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2)
                          T=((4, 4), torch.float64), grid=((3, 3), torch.float64), stats=((8,), torch.float64), n_inliers=((), torch.int32),
                          inlier_mask=((fit.MAXP,), torch.uint8), plane_flags=((), torch.int32), mean_err=((), torch.float64),
                          status=((), torch.int32))
+
+
+# what fit.fit_single_plane_batch adds with relabel= (per frame and image); FramePipeline(relabel=...).run_raw keeps them when the
+# fits dict holds tensors of these names
+RELABEL_OUTPUTS = dict(relabel_counts=((2, 2, 4), torch.int32), relabel_flags=((2,), torch.int32))
 
 
 MONO_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2), torch.int32), m=((), torch.int32),

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 122   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 123   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -56,7 +56,8 @@ extern "C" {
                              cpe_match_offset_workspace_bytes; 117: cpe_fit_plane_batch, cpe_index_planes_batch;
                              118: cpe_table_triangulate_batch; 119: cpe_fit_projector_model, cpe_projector_model_table;
                              120: cpe_index_shift_batch; 121: cpe_multi_frame_consensus_batch,
-                             cpe_multi_frame_consensus_workspace_bytes; 122: cpe_fused_triangulate_batch) */
+                             cpe_multi_frame_consensus_workspace_bytes; 122: cpe_fused_triangulate_batch;
+                             123: cpe_grid_relabel_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -875,6 +876,64 @@ CPE_API int32_t cpe_index_shift_batch(const double *X, const int32_t *idx, const
                                       const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
                                       const CpeIndexShiftParams *params, int32_t *shift, int32_t *score, int32_t *scores, double *rms,
                                       int32_t *flags, int32_t *idx_out, void *stream);
+
+/* BUILD-DEFINED: re-label the grid lines of PLANAR-target tables from their geometry, per image.  The planar detector's labels
+ * group the grid points into true lines, but their VALUES are not the lines' indices: on rendered boards one image comes out
+ * reflected, the other permuted, with phantom lines along the rim of the centre spot.  Everything behind
+ * the detector pairs the two images by equal index.  This call keeps the grouping and drops the values: per image and id
+ * component it orders the lines by where they cross the centre, drops phantoms, and steps the index by the measured pitch.
+ * One workgroup of two wavefronts per image (wavefront c = id component c), one launch on `stream`, no workspace, no atomics on
+ * floating point, no host synchronisation; two calls on the same inputs give the same bits.
+ *   xy f64[n,CPE_MAXP,2], id i32[n,CPE_MAXP,2], cnt i32[n]: tables as cpe_detect_grid_batch writes them; center f64[n,2] (x, y)
+ *   as it writes it; params NULL = the defaults of CpeRelabelParams.
+ * Rule (the order is the contract), per image and component c:
+ *   1. cnt is clamped to [0, CPE_MAXP]; slots past it are never read.  A point is usable when its slot is below the count and both
+ *      pixel coordinates are finite.  A non-finite center: CPE_RELABEL_FLAG_NO_CENTRE, cnt_out 0;
+ *   2. a line is the usable points of one label value id[c].  A label span max - min (in 64 bits) >= CPE_MAXL in either
+ *      component (so also more than CPE_MAXL labels): CPE_RELABEL_FLAG_OVERFLOW, cnt_out 0.  An image flagged by 1 or 2 reports
+ *      counts and pitch 0 for both components and writes no line slot;
+ *   3. per line, u the positional coordinate and t the other one (c ^ swap == 0: u = y, t = x; otherwise u = x, t = y): the
+ *      point count N, the sums of t and of u in slot order, the means tm = sum / N and um, then in a second pass in slot order
+ *      Stt = sum (t - tm)^2 and Stu = sum (t - tm)(u - um); a = Stu / Stt; p = um + a (t_centre - tm).  The line is unsupported
+ *      when N < min_pts, Stt is not > 0, or p is not finite;
+ *   4. the supported lines are sorted by (p, label); pitch0 = the median of the consecutive gaps (the mean of the two middle
+ *      ones, (g[(m-1)/2] + g[m/2]) / 2 of the m sorted gaps), 0 without a gap;
+ *   5. line i of that order is a phantom when a neighbour j = i - 1 or i + 1 lies closer than merge_frac * pitch0 and has more
+ *      points, or as many and j < i.  All lines are judged at once, on the list of 4;
+ *   6. the remaining lines give the gaps g_i.  pitch_i = the median of the g_k, k in {i-2, i-1, i+1, i+2}, that exist, with
+ *      fewer than two of them the median of all remaining gaps; inc_i = max(1, floor(g_i / pitch_i + 0.5)), 1 when pitch_i is not
+ *      > 0, at most CPE_RELABEL_MAX_INC.  No remaining line: CPE_RELABEL_FLAG_FEW_LINES << c (every point of the image is then
+ *      dropped);
+ *   7. the remaining line whose p is nearest to the centre's positional coordinate is the anchor (the first in order on a tie);
+ *      new index = dir[c] * (the sum of the inc before the line - the sum before the anchor);
+ *   8. a point is written when it is usable and the lines of both its components are kept: xy_out, id_out (the new indices, the
+ *      component order unchanged) and src (its slot in the input) in slot order, cnt_out their number.  Slots from cnt_out on
+ *      are not written.
+ * lines i32[n,2,CPE_MAXL,4]: per image, component and line slot (the labels seen, ascending) label | new index | points |
+ *   CPE_RELABEL_LINE_*; line_p f64[n,2,CPE_MAXL] the position p (0 where Stt is not > 0 or p is not finite); index 0 for a line
+ *   that is not kept.  Slots from counts[.,.,0] on are not written.
+ * pitch f64[n,2] = pitch0; counts i32[n,2,4] = labels seen | supported | dropped as phantom | kept; flags i32[n].
+ * No output may overlap an input or another output (CPE_ERR_ARG); n == 0 is a no-op.  min_pts < 2, merge_frac outside (0, 1),
+ * dir other than +-1 and swap other than 0 / 1 are refused with CPE_ERR_ARG before anything is written.
+ * Limits: boards only (a line is straight in the image); one centre per image; a line with fewer than min_pts points is lost
+ * with its points; an image whose anchor line is missing ends a line off, which is what cpe_index_shift_batch repairs. */
+#define CPE_RELABEL_FLAG_NO_CENTRE 1
+#define CPE_RELABEL_FLAG_OVERFLOW 2
+#define CPE_RELABEL_FLAG_FEW_LINES 4     /* component 0; component 1 is CPE_RELABEL_FLAG_FEW_LINES << 1 */
+#define CPE_RELABEL_LINE_KEPT 0
+#define CPE_RELABEL_LINE_UNSUPPORTED 1
+#define CPE_RELABEL_LINE_PHANTOM 2
+#define CPE_RELABEL_MAX_INC 1048576
+typedef struct CpeRelabelParams {
+    int32_t swap;        /* 0: id component 0 is positioned in y (the planar detector's (row, col)); 1: in x.  Default 0 */
+    int32_t min_pts;     /* a line with fewer usable points is unsupported; >= 2; default 3 */
+    double  merge_frac;  /* a neighbour closer than merge_frac * pitch0 makes the weaker line a phantom; in (0, 1); default 0.65 */
+    int32_t dir[2];      /* +1 or -1: the new index of component c grows (falls) with the position; default +1, +1 */
+} CpeRelabelParams;
+CPE_API int32_t cpe_grid_relabel_batch(const double *xy, const int32_t *id, const int32_t *cnt, const double *center, int32_t n,
+                                       const CpeRelabelParams *params, double *xy_out, int32_t *id_out, int32_t *cnt_out,
+                                       int32_t *src, int32_t *lines, double *line_p, double *pitch, int32_t *counts, int32_t *flags,
+                                       void *stream);
 
 /* Row f-3: the undistortion pre-step of the CLI entry point, utils/iotool.py:22-39
  *   undistort_image(image, camera_params) = cv2.undistort(image, IntrinsicMatrix, hstack(Radial, Tangential))
