@@ -4590,3 +4590,342 @@ extern "C" int32_t cpe_grid_relabel_batch(const double *xy, const int32_t *id, c
     CPE_CHECK_LAUNCH("k_grid_relabel");
     return CPE_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The grid a fitted cylinder predicts, and the detections re-numbered against it (include/cpe.h cpe_grid_predict_batch and
+// cpe_grid_assign_batch, whose numbered rules these follow).
+namespace {
+
+__device__ __forceinline__ double dot3(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// step 10 for one camera: -> visible; x, y are set for a visible node only
+__device__ __forceinline__ bool pred_project(const double *__restrict__ K, const double *__restrict__ Tc, const double *X, const double *nu,
+                                             double min_cos, int img_w, int img_h, double &x, double &y)
+{
+    TriCam cam;
+    tri_cam(K, Tc, cam);
+    double Xc[3] = {X[0], X[1], X[2]};
+    if (Tc) {
+#pragma unroll
+        for (int r = 0; r < 3; r++) Xc[r] = ((Tc[4 * r] * X[0] + Tc[4 * r + 1] * X[1]) + Tc[4 * r + 2] * X[2]) + Tc[4 * r + 3];
+    }
+    const double Z = Xc[2];
+    const double v[3] = {cam.o[0] - X[0], cam.o[1] - X[1], cam.o[2] - X[2]};
+    const double vn = sqrt(dot3(v, v));
+    if (!(Z > 0) || !(dot3(nu, v) > min_cos * vn)) return false;
+    const double xn = Xc[0] / Z, yn = Xc[1] / Z;
+    x = (cam.k0 * xn + cam.k1 * yn) + cam.k2;
+    y = cam.k4 * yn + cam.k5;
+    if (!isfinite(x) || !isfinite(y)) return false;
+    if (img_w > 0 && img_h > 0 && !(x >= 0 && x < (double)img_w && y >= 0 && y < (double)img_h)) return false;
+    return true;
+}
+
+// One lane per (frame, node): a block lies inside one frame, so the pose, the cameras and the centre are wave-uniform loads; the two
+// planes of a node come through L2 as in k_table_triangulate.  Every output slot of the node is written, by vector stores.
+__global__ __launch_bounds__(256) void k_grid_predict(const double *__restrict__ cyl, const unsigned char *__restrict__ use, double R,
+                                                      const double *__restrict__ K1, const double *__restrict__ K2,
+                                                      const double *__restrict__ T21, const double *__restrict__ P,
+                                                      const int *__restrict__ line_status, int lo, int L,
+                                                      const double *__restrict__ centre, int wlo0, int wlo1, int Nv, int N,
+                                                      double min_cos, int img_w, int img_h, double *__restrict__ o_X,
+                                                      double *__restrict__ o_px, int *__restrict__ o_state, int *__restrict__ o_vis)
+{
+    const int nb = (N + 255) / 256;                                            // blocks per frame: the grid is (frame, block) in one dimension
+    const int f = blockIdx.x / nb;
+    const int j = (blockIdx.x % nb) * 256 + threadIdx.x;
+    if (j >= N) return;
+    const double *c6 = cyl + (size_t)f * 6;
+    const double oc[3] = {c6[0], c6[1], c6[2]};
+    double ah[3] = {c6[3], c6[4], c6[5]};
+    const double an = sqrt(dot3(ah, ah));
+    bool frame_ok = (!use || use[f] != 0) && isfinite(oc[0]) && isfinite(oc[1]) && isfinite(oc[2]) && isfinite(ah[0]) &&
+                    isfinite(ah[1]) && isfinite(ah[2]) && isfinite(an) && an != 0.0;
+    int state = CPE_PRED_OK, vis = 0;
+    double X[3] = {0, 0, 0}, px[4] = {0, 0, 0, 0};
+    if (!frame_ok) state = CPE_PRED_NO_FRAME;
+    if (state == CPE_PRED_OK) {
+        const int l0 = (wlo0 + j / Nv) - lo, l1 = L + ((wlo1 + j % Nv) - lo);     // inside the table: checked by the host
+        if (line_status[l0] != CPE_ST_OK || line_status[l1] != CPE_ST_OK) state = CPE_PRED_NO_PLANE;
+        if (state == CPE_PRED_OK) {
+#pragma unroll
+            for (int a = 0; a < 3; a++) ah[a] = ah[a] / an;
+            const double n0[3] = {P[(size_t)l0 * 4], P[(size_t)l0 * 4 + 1], P[(size_t)l0 * 4 + 2]}, p0 = P[(size_t)l0 * 4 + 3];
+            const double n1[3] = {P[(size_t)l1 * 4], P[(size_t)l1 * 4 + 1], P[(size_t)l1 * 4 + 2]}, p1 = P[(size_t)l1 * 4 + 3];
+            double w[3], c1[3], c0[3];
+            cross3(n0, n1, w);
+            const double w2 = dot3(w, w);
+            if (!(w2 >= CPE_PRED_MIN_W2) || !isfinite(w2)) state = CPE_PRED_PARALLEL;
+            if (state == CPE_PRED_OK) {
+                cross3(n1, w, c1);
+                cross3(w, n0, c0);
+                const double wn = sqrt(w2);
+                double q[3], wh[3], e[3], ep[3], wp[3];
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+                    q[a] = ((-p0) * c1[a] - p1 * c0[a]) / w2;
+                    wh[a] = w[a] / wn;
+                    e[a] = q[a] - oc[a];
+                }
+                const double ea = dot3(e, ah), wa = dot3(wh, ah);
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+                    ep[a] = e[a] - ea * ah[a];
+                    wp[a] = wh[a] - wa * ah[a];
+                }
+                const double A = dot3(wp, wp), B = dot3(ep, wp), Cq = dot3(ep, ep) - R * R;
+                const double disc = B * B - A * Cq;
+                if (!isfinite(A) || !isfinite(B) || !isfinite(Cq) || !isfinite(disc) || A == 0.0 || !(disc > 0)) state = CPE_PRED_MISS;
+                if (state == CPE_PRED_OK) {
+                    const double s = sqrt(disc);
+                    const double tm = (-B - s) / A, tp = (-B + s) / A;
+                    const double cq[3] = {centre[0] - q[0], centre[1] - q[1], centre[2] - q[2]};
+                    const double tC = dot3(cq, wh);
+                    const double t = fabs(tm - tC) <= fabs(tp - tC) ? tm : tp;
+                    double g[3], nu[3], Xn[3];
+#pragma unroll
+                    for (int a = 0; a < 3; a++) {
+                        Xn[a] = q[a] + t * wh[a];
+                        g[a] = Xn[a] - oc[a];
+                    }
+                    if (!isfinite(Xn[0]) || !isfinite(Xn[1]) || !isfinite(Xn[2])) state = CPE_PRED_MISS;
+                    if (state == CPE_PRED_OK) {
+                        const double ga = dot3(g, ah);
+#pragma unroll
+                        for (int a = 0; a < 3; a++) nu[a] = (g[a] - ga * ah[a]) / R;
+                        if (!(fabs(dot3(nu, wh)) >= min_cos)) state = CPE_PRED_GRAZING;
+                        if (state == CPE_PRED_OK) {
+#pragma unroll
+                            for (int a = 0; a < 3; a++) X[a] = Xn[a];
+                            double x, y;
+                            if (pred_project(K1, nullptr, X, nu, min_cos, img_w, img_h, x, y)) { vis |= 1; px[0] = x; px[1] = y; }
+                            if (pred_project(K2, T21, X, nu, min_cos, img_w, img_h, x, y)) { vis |= 2; px[2] = x; px[3] = y; }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    const size_t node = (size_t)f * N + j;
+    o_X[node * 3] = X[0]; o_X[node * 3 + 1] = X[1]; o_X[node * 3 + 2] = X[2];
+    const size_t pb = (size_t)f * 2 * N;
+    o_px[(pb + j) * 2] = px[0]; o_px[(pb + j) * 2 + 1] = px[1];
+    o_px[(pb + N + j) * 2] = px[2]; o_px[(pb + N + j) * 2 + 1] = px[3];
+    o_state[node] = state;
+    o_vis[node] = vis;
+}
+
+// counts of a frame from what k_grid_predict wrote: one wavefront per frame, so no atomics
+__global__ __launch_bounds__(64) void k_grid_predict_counts(const int *__restrict__ state, const int *__restrict__ vis, int N,
+                                                            int *__restrict__ o_counts)
+{
+    const int f = blockIdx.x, lane = threadIdx.x;
+    int ok = 0, v1 = 0, v2 = 0, vb = 0;
+    for (int j = lane; j < N; j += 64) {
+        const int s = state[(size_t)f * N + j], v = vis[(size_t)f * N + j];
+        ok += s == CPE_PRED_OK; v1 += v & 1; v2 += (v >> 1) & 1; vb += v == 3;
+    }
+    ok = wave_sum_i(ok); v1 = wave_sum_i(v1); v2 = wave_sum_i(v2); vb = wave_sum_i(vb);
+    if (lane == 0) { o_counts[4 * f] = ok; o_counts[4 * f + 1] = v1; o_counts[4 * f + 2] = v2; o_counts[4 * f + 3] = vb; }
+}
+
+// One workgroup of four wavefronts per image.  Dynamic LDS (fit_dyn): the camera's predicted pixels in f64 (N x 16 B, NaN for a
+// node that is not visible, so it is never the nearest), d1 per detection (MAXP x 8 B), the winning key per node (N x 8 B: the
+// bit pattern of the non-negative d1, which orders as the number does), the winning slot per node (N x 4 B), the named node or
+// the refusal per detection (MAXP x 4 B) and the wave counts of the compaction: 28 N + 12 MAXP + 64 B, 139328 B at N = 4096,
+// 55 KB at the experiment's 33 x 33 nodes.  All lanes of a wave read the same node at a time: a broadcast, no bank conflict.
+constexpr int ASSIGN_T = 256;
+constexpr size_t assign_lds_bytes(int N) { return (size_t)N * 28 + (size_t)MAXP * 12 + 64; }
+__global__ __launch_bounds__(ASSIGN_T) void k_grid_assign(const double *__restrict__ xy, const int *__restrict__ id, const int *__restrict__ cnt,
+                                                          const double *__restrict__ px, long long px_stride, const int *__restrict__ vis,
+                                                          int cam_bit, int wlo0, int wlo1, int Nv, int N, double tau, double ratio, int swap,
+                                                          double *__restrict__ o_xy, int *__restrict__ o_id, int *__restrict__ o_src,
+                                                          double *__restrict__ o_dist, int *__restrict__ o_m, int *__restrict__ o_counts,
+                                                          double *__restrict__ o_stats, int *__restrict__ o_node_slot)
+{
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(max(cnt[f], 0), MAXP);
+    const size_t base = (size_t)f * MAXP;
+    double *s_px = fit_dyn;                                                     // [N][2]
+    double *s_d1 = s_px + (size_t)2 * N;                                        // [MAXP]
+    unsigned long long *s_key = reinterpret_cast<unsigned long long *>(s_d1 + MAXP);   // [N]
+    int *s_slot = reinterpret_cast<int *>(s_key + N);                           // [N]
+    int *s_node = s_slot + N;                                                   // [MAXP]
+    int *s_wave = s_node + MAXP;                                                // [16]
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int j = tid; j < N; j += ASSIGN_T) {
+        const double x = px[(size_t)f * px_stride + 2 * j], y = px[(size_t)f * px_stride + 2 * j + 1];
+        const bool v = ((vis[(size_t)f * N + j] >> cam_bit) & 1) && isfinite(x) && isfinite(y);
+        s_px[2 * j] = v ? x : nan; s_px[2 * j + 1] = v ? y : nan;
+        s_key[j] = ~0ull;
+        s_slot[j] = INT_MAX;
+    }
+    __syncthreads();
+    // steps 1 - 4: the nearest and second-nearest node of every detection, and its bid for the node
+    for (int k = tid; k < n; k += ASSIGN_T) {
+        const double x = xy[(base + k) * 2], y = xy[(base + k) * 2 + 1];
+        double b1 = INFINITY, b2 = INFINITY;
+        int j1 = -1;
+        for (int j = 0; j < N; j++) {
+            const double dx = x - s_px[2 * j], dy = y - s_px[2 * j + 1];
+            const double d = dx * dx + dy * dy;
+            if (d < b1) { b2 = b1; b1 = d; j1 = j; }
+            else if (d < b2) b2 = d;
+        }
+        const double d1 = sqrt(b1), d2 = sqrt(b2);
+        int node = j1;
+        if (!isfinite(x) || !isfinite(y) || j1 < 0) node = -3;                  // -(its slot in counts)
+        else if (d1 >= tau) node = -4;
+        else if (d1 > ratio * d2) node = -5;
+        s_node[k] = node;
+        s_d1[k] = d1;
+        if (node >= 0) atomicMin(&s_key[node], (unsigned long long)__double_as_longlong(d1));
+    }
+    __syncthreads();
+    // step 5: among the bids with the winning d1, the lowest slot
+    for (int k = tid; k < n; k += ASSIGN_T) {
+        const int node = s_node[k];
+        if (node >= 0 && s_key[node] == (unsigned long long)__double_as_longlong(s_d1[k])) atomicMin(&s_slot[node], k);
+    }
+    __syncthreads();
+    // steps 6, 7: compaction in slot order, rounds of 256: a ballot per wave, the waves' counts through LDS, the base carried on
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int m = 0, c_same = 0, c_new = 0, c_none = 0, c_far = 0, c_amb = 0, c_conf = 0, round = 0;
+    double r2 = 0, rmax = 0;
+    for (int k0 = 0; k0 < n; k0 += ASSIGN_T, round++) {
+        const int k = k0 + tid;
+        const bool in = k < n;
+        const int node = in ? s_node[k] : -1;
+        const bool kept = in && node >= 0 && s_slot[node] == k;
+        const unsigned long long bal = __ballot(kept);
+        int *sw = s_wave + (round & 1) * 4;
+        if (lane == 0) sw[wave] = __popcll(bal);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < ASSIGN_T / 64; w++) {
+            const int c = sw[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        c_none += in && node == -3; c_far += in && node == -4; c_amb += in && node == -5; c_conf += in && node >= 0 && !kept;
+        if (kept) {
+            const size_t slot = base + (size_t)(m + before + __popcll(bal & below));   // <= base + k: inside the image's table
+            const double x = xy[(base + k) * 2], y = xy[(base + k) * 2 + 1], d1 = s_d1[k];
+            const int u = wlo0 + node / Nv, v = wlo1 + node % Nv;
+            const int i0 = swap ? v : u, i1 = swap ? u : v;
+            o_xy[slot * 2] = x; o_xy[slot * 2 + 1] = y;
+            o_id[slot * 2] = i0; o_id[slot * 2 + 1] = i1;
+            o_src[slot] = k;
+            o_dist[slot] = d1;
+            const bool same = id[(base + k) * 2] == i0 && id[(base + k) * 2 + 1] == i1;
+            c_same += same; c_new += !same;
+            r2 = r2 + d1 * d1;
+            rmax = fmax(rmax, d1);
+        }
+        m += total;
+    }
+    // the sums: every lane its own points in slot order, the xor-butterfly of the wave, then the four waves in order
+    r2 = wave_sum(r2);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) rmax = fmax(rmax, __shfl_xor(rmax, off, 64));
+    c_same = wave_sum_i(c_same); c_new = wave_sum_i(c_new); c_none = wave_sum_i(c_none); c_far = wave_sum_i(c_far);
+    c_amb = wave_sum_i(c_amb); c_conf = wave_sum_i(c_conf);
+    __syncthreads();                                                            // s_d1 and s_node are free now
+    if (lane == 0) {
+        s_d1[2 * wave] = r2; s_d1[2 * wave + 1] = rmax;
+        int *sc = s_node + 8 * wave;
+        sc[0] = c_same; sc[1] = c_new; sc[2] = c_none; sc[3] = c_far; sc[4] = c_amb; sc[5] = c_conf;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double t2 = 0, tmax = 0;
+        int c[6] = {0, 0, 0, 0, 0, 0};
+        for (int w = 0; w < ASSIGN_T / 64; w++) {
+            t2 = t2 + s_d1[2 * w];
+            tmax = fmax(tmax, s_d1[2 * w + 1]);
+            for (int a = 0; a < 6; a++) c[a] += s_node[8 * w + a];
+        }
+        o_m[f] = m;
+        o_counts[8 * f] = m;
+        for (int a = 0; a < 6; a++) o_counts[8 * f + 1 + a] = c[a];
+        o_counts[8 * f + 7] = 0;
+        o_stats[2 * f] = m > 0 ? sqrt(t2 / (double)m) : 0.0;
+        o_stats[2 * f + 1] = m > 0 ? tmax : 0.0;
+    }
+    if (o_node_slot)
+        for (int j = tid; j < N; j += ASSIGN_T) o_node_slot[(size_t)f * N + j] = s_slot[j] == INT_MAX ? -1 : s_slot[j];
+}
+}  // namespace
+
+extern "C" int32_t cpe_grid_predict_batch(const double *cyl, const uint8_t *use, int32_t n, double radius, const double *K1,
+                                          const double *K2, const double *T21, const double *P, const int32_t *line_status, int32_t lo,
+                                          int32_t hi, const double *centre, const CpeGridPredictParams *params, double *X, double *px,
+                                          int32_t *state, int32_t *vis, int32_t *counts, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_grid_predict_batch: n < 0");
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_grid_predict_batch: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    CPE_CHECK_ARG(radius > 0 && radius <= DBL_MAX, "cpe_grid_predict_batch: radius must be positive and finite");
+    CpeGridPredictParams p = {{lo, lo}, {hi, hi}, 0.1, 0, 0};
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.min_cos > 0 && p.min_cos < 1, "cpe_grid_predict_batch: min_cos must lie in (0, 1)");
+    for (int k = 0; k < 2; k++)
+        CPE_CHECK_ARG(p.win_lo[k] >= lo && p.win_hi[k] <= hi && p.win_lo[k] <= p.win_hi[k],
+                      "cpe_grid_predict_batch: the window of family %d, [%d, %d], must lie inside [%d, %d]", k, p.win_lo[k], p.win_hi[k], lo, hi);
+    const long long Nu = (long long)p.win_hi[0] - p.win_lo[0] + 1, Nv = (long long)p.win_hi[1] - p.win_lo[1] + 1;
+    CPE_CHECK_ARG(Nu * Nv <= CPE_PRED_MAXN, "cpe_grid_predict_batch: %lld x %lld nodes, at most %d", Nu, Nv, CPE_PRED_MAXN);
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(cyl && K1 && K2 && T21 && P && line_status && centre && X && px && state && vis && counts,
+                  "cpe_grid_predict_batch: null pointer");
+    const int N = (int)(Nu * Nv);
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_grid_predict, dim3((unsigned)((N + 255) / 256) * (unsigned)n), dim3(256), 0, (hipStream_t)stream, cyl, use, radius, K1, K2, T21, P, line_status, lo,
+                hi - lo + 1, centre, p.win_lo[0], p.win_lo[1], (int)Nv, N, p.min_cos, p.img_w, p.img_h, X, px, state, vis);
+    CPE_CHECK_LAUNCH("k_grid_predict");
+    CPE_KLAUNCH(k_grid_predict_counts, dim3(n), dim3(64), 0, (hipStream_t)stream, (const int *)state, (const int *)vis, N, counts);
+    CPE_CHECK_LAUNCH("k_grid_predict_counts");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_grid_assign_batch(const double *xy, const int32_t *id, const int32_t *cnt, int32_t n, const double *px,
+                                         int64_t px_stride, const int32_t *vis, int32_t cam_bit, int32_t win_lo0, int32_t win_lo1,
+                                         int32_t Nu, int32_t Nv, const CpeGridAssignParams *params, double *xy_out, int32_t *id_out,
+                                         int32_t *src, double *dist, int32_t *m, int32_t *counts, double *stats, int32_t *node_slot,
+                                         void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_grid_assign_batch: n < 0");
+    CPE_CHECK_ARG(Nu >= 1 && Nv >= 1 && (long long)Nu * Nv <= CPE_PRED_MAXN, "cpe_grid_assign_batch: Nu x Nv must be 1..%d nodes",
+                  CPE_PRED_MAXN);
+    const int N = Nu * Nv;
+    CPE_CHECK_ARG(px_stride >= 2 * (int64_t)N, "cpe_grid_assign_batch: px_stride below 2 N");
+    CPE_CHECK_ARG(cam_bit == 0 || cam_bit == 1, "cpe_grid_assign_batch: cam_bit is 0 or 1");
+    CPE_CHECK_ARG((long long)win_lo0 + Nu - 1 <= INT32_MAX && (long long)win_lo1 + Nv - 1 <= INT32_MAX,
+                  "cpe_grid_assign_batch: the window's indices leave int32");
+    CpeGridAssignParams p = {4.0, 0.5, 0, 0};
+    if (params) p = *params;
+    CPE_CHECK_ARG(p.tau_px > 0 && p.tau_px <= DBL_MAX && p.ratio > 0 && p.ratio <= 1 && (p.swap == 0 || p.swap == 1),
+                  "cpe_grid_assign_batch: bad CpeGridAssignParams (tau_px positive and finite, 0 < ratio <= 1, swap 0 or 1)");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(xy && id && cnt && px && vis && xy_out && id_out && src && dist && m && counts && stats,
+                  "cpe_grid_assign_batch: null pointer");
+    {
+        const size_t Nn = (size_t)n, Pp = (size_t)CPE_MAXP;
+        const struct { const void *p; size_t bytes; } buf[13] = {
+            {xy, Nn * Pp * 16}, {id, Nn * Pp * 8}, {cnt, Nn * 4}, {px, ((Nn - 1) * (size_t)px_stride + 2 * (size_t)N) * 8}, {vis, Nn * N * 4},
+            {xy_out, Nn * Pp * 16}, {id_out, Nn * Pp * 8}, {src, Nn * Pp * 4}, {dist, Nn * Pp * 8}, {m, Nn * 4}, {counts, Nn * 32},
+            {stats, Nn * 16}, {node_slot, node_slot ? Nn * N * 4 : 0}};
+        for (int o = 5; o < 13; o++)
+            for (int i = 0; i < o; i++)
+                CPE_CHECK_ARG(!buf[o].bytes || !rl_overlap(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes),
+                              "cpe_grid_assign_batch: an output overlaps an input or another output");
+    }
+    static_assert(assign_lds_bytes(CPE_PRED_MAXN) <= 160 * 1024, "k_grid_assign: LDS beyond the CU's 160 KB");
+    CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_grid_assign), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)assign_lds_bytes(CPE_PRED_MAXN)));
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_grid_assign, dim3(n), dim3(ASSIGN_T), assign_lds_bytes(N), (hipStream_t)stream, xy, id, cnt, px, (long long)px_stride, vis,
+                cam_bit, win_lo0, win_lo1, Nv, N, p.tau_px, p.ratio, p.swap, xy_out, id_out, src, dist, m, counts, stats, node_slot);
+    CPE_CHECK_LAUNCH("k_grid_assign");
+    return CPE_OK;
+}

@@ -161,9 +161,16 @@ def _fit_projector(fits, frame_ok, projector, family0, use=None, table_path=None
     return dict(fit=out, model=model, laser_table=table, **extra), shifted, renumbered
 
 
+def refine_listing(names, round_taken, renumbered):
+    """round_taken i32 [F], renumbered i32 [F,2] of fit.fit_single_cylinder_refined_batch -> a list of dict(index, name, round,
+    left, right) for the frames where a point of either image was re-numbered"""
+    rt, rn = torch.as_tensor(round_taken).cpu().tolist(), torch.as_tensor(renumbered).cpu().tolist()
+    return [dict(index=i, name=names[i], round=rt[i], left=rn[i][0], right=rn[i][1]) for i in range(len(names)) if rn[i][0] or rn[i][1]]
+
+
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
                    frame_angles=False, match_offset=None, laser_table=None, source='stereo', projector=None, table_path=None,
-                   consensus=None):
+                   consensus=None, refine=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
@@ -198,6 +205,14 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     fit.fit_single_cylinder_fused_batch): no selector, and a point that one camera alone found is kept.  Word 14 of a record is
     the rms ray residual of the pairs in pixels; tri_counts is i32 [F,6] and tri_stats f64 [F,4] (fit.fused_triangulate_batch's).
     match_offset is refused: the numbering is repaired before, not inside, this call.
+
+    refine= with source='fused' (build-defined, opt-in): None, or a dict of fit.fit_single_cylinder_refined_batch keywords ({} =
+    its defaults).  Every frame is fitted from its stereo pairs first; then each grid point of either image takes the index of
+    the nearest node of the grid which that fit and the laser-plane table predict, and the frame is fitted again on the fused
+    points of the re-numbered tables (FramePipeline(source='fused', refine=...)).  The dict has no tri_counts / tri_stats then
+    and gains refine = dict(round_taken i32 [F] (0: the first fit stands), renumbered i32 [F,2] (points of the left, right image
+    whose index changed), frames: a list of dict(index, name, round, left, right) for the frames where any did).  Any other source
+    raises ValueError.
 
     projector: None, or a dict of fit.fit_projector_model keywords ({} = its defaults; build-defined): the projector's model
     (two pencils of planes through one centre) is fitted to the experiment's own stereo points and indices -- after the index
@@ -236,13 +251,13 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
         raise ValueError("consensus= are the options of multi_frame='consensus'")
 
     def make_fits(F):
-        f = pipeline.alloc_fits(F, dev, source=source)
+        f = pipeline.alloc_fits(F, dev, source=source, refine=refine is not None)
         if projector is not None:        # the model needs the points' indices, which the selector returns beside the points
             f['idx'] = torch.zeros((F, fit.MAXP, 2), dtype=torch.int32, device=dev)
         return f
     recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, make_fits,
                             lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=c, device=dev, match=match_offset,
-                                                                   source=source, laser_table=laser_table), source)
+                                                                   source=source, laser_table=laser_table, refine=refine), source)
     F = len(names)
     _, _, d_fit, d_l, d_r = pipeline.unpack_counters(recs[:, 15])          # device tensors: the 'gpu' mode masks with them
     st_fit, st_l, st_r = (t.cpu().tolist() for t in (d_fit, d_l, d_r))
@@ -265,7 +280,10 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
 
     if match_offset is not None:
         res.update(offset=fits['offset'], match_score=fits['match_score'], match_flags=fits['match_flags'])
-    if source != 'stereo':
+    if refine is not None:
+        res['refine'] = dict(round_taken=fits['round_taken'], renumbered=fits['renumbered'],
+                             frames=refine_listing(names, fits['round_taken'], fits['renumbered']))
+    elif source != 'stereo':
         res.update(tri_counts=fits['counts'], tri_stats=fits['stats'])
     if projector is not None:
         res['projector'], res['projector_shifted'], renumbered = _fit_projector(fits, good_frames(), projector, 'col',

@@ -6,6 +6,7 @@ becomes fit_single_cylinder_batch(tables_left, tables_right, K1, K2, T_C2_C1, ra
 once, everything resident on the GPU, one wavefront per frame (csrc/fit.hip)."""
 import ctypes as C
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
@@ -370,6 +371,16 @@ class LaserTable:
     centre: torch.Tensor
     centre_status: torch.Tensor
     family0: str = 'col'
+    # centre_status == ST_OK as a host value, for the calls that need the centre (grid_predict_batch): set by whoever knows it
+    # without asking the device (load does; to carries it on); None = not known yet, read from the device once by has_centre()
+    centre_ok: Optional[bool] = None
+
+    def has_centre(self):
+        """is centre_status ST_OK?  Answered from centre_ok; while that is None the word is read from the device (one wait) and
+        kept.  Whoever rewrites centre_status in place sets centre_ok (or None) with it."""
+        if self.centre_ok is None:
+            self.centre_ok = bool((self.centre_status.reshape(-1)[:1] == ST_OK).all().item())
+        return self.centre_ok
 
     def __post_init__(self):
         if self.family0 not in ('col', 'row'):
@@ -395,7 +406,7 @@ class LaserTable:
 
     def to(self, device):
         return LaserTable(self.P.to(device), self.status.to(device), self.lo, self.hi, self.centre.to(device),
-                          self.centre_status.to(device), self.family0)
+                          self.centre_status.to(device), self.family0, self.centre_ok)
 
     def save(self, path):
         """one .npz file (numpy appends the suffix to a path without it)"""
@@ -409,7 +420,7 @@ class LaserTable:
         with np.load(path, allow_pickle=False) as z:
             t = lambda k, dt: torch.from_numpy(np.ascontiguousarray(z[k])).to(dt).to(device)
             return LaserTable(t('P', torch.float64), t('status', torch.int32), int(z['lo']), int(z['hi']), t('centre', torch.float64),
-                              t('centre_status', torch.int32), str(z['family0']))
+                              t('centre_status', torch.int32), str(z['family0']), bool((np.asarray(z['centre_status']).reshape(-1)[:1] == ST_OK).all()))
 
 
 def fit_projector_model(pts3, idx, cnt, lo, hi, use=None, frame_ok=None, tau=0.0, max_rounds=4, min_spread=1e-4, tolx=1e-9, tolf=1e-9,
@@ -617,6 +628,158 @@ def fit_single_cylinder_fused_batch(gp1: GridTables, gp2: GridTables, K1, K2, T2
     out = dict(tri)
     out.update(fit)
     out['mean_err'] = tri['stats'][:, 0]
+    return out
+
+
+PRED_MAXN = _lib.PRED_MAXN                                          # CPE_PRED_MAXN
+PRED_OK, PRED_NO_FRAME, PRED_NO_PLANE, PRED_PARALLEL, PRED_MISS, PRED_GRAZING = range(6)   # CPE_PRED_*
+
+
+def grid_predict_batch(cyl, radius, K1, K2, T21, table: LaserTable, use=None, window=None, min_cos=0.1, image_size=None):
+    """BUILD-DEFINED: where the grid nodes of `table` fall on the cylinder of every frame's pose and in both images, see
+    include/cpe.h cpe_grid_predict_batch.  cyl f64[n,6] (a point on the axis, the axis direction; camera-1 coordinates), e.g.
+    fit_cylinder_batch(...)['cyl'][:, 1]; use: bool / u8 [n] or None; window ((lo0, hi0), (lo1, hi1)): the node indices of table
+    family 0 and 1, default the whole table, which must then hold at most PRED_MAXN nodes; image_size (h, w) or None: no bound.
+    A table whose centre_status is not ST_OK is refused (LaserTable.has_centre: answered from table.centre_ok, which load() sets
+    and to() carries on; a table built without it costs one read from the device, the only wait for the GPU here).
+    -> dict(X f64[n,N,3], px f64[n,2,N,2], state i32[n,N] (PRED_*), vis i32[n,N] (bit 0 camera 1, bit 1 camera 2),
+            counts i32[n,4] (OK, visible in 1, in 2, in both), window, Nu, Nv, family0)"""
+    L = _lib.load()
+    if not table.has_centre():
+        raise ValueError('grid_predict_batch: the table has no projector centre (centre_status is not ST_OK)')
+    if window is None:
+        window = ((table.lo, table.hi), (table.lo, table.hi))
+    (lo0, hi0), (lo1, hi1) = ((int(a), int(b)) for a, b in window)
+    Nu, Nv = hi0 - lo0 + 1, hi1 - lo1 + 1
+    if not (table.lo <= lo0 <= hi0 <= table.hi and table.lo <= lo1 <= hi1 <= table.hi):
+        raise ValueError(f'grid_predict_batch: window {window} outside the table [{table.lo}, {table.hi}]')
+    if Nu * Nv > PRED_MAXN:
+        raise ValueError(f'grid_predict_batch: {Nu} x {Nv} nodes, at most {PRED_MAXN}: give a smaller window')
+    if not 0 < min_cos < 1:
+        raise ValueError(f'grid_predict_batch: min_cos must lie in (0, 1), got {min_cos}')
+    if cyl.dtype != torch.float64 or cyl.dim() != 2 or cyl.shape[1] != 6:
+        raise TypeError(f'grid_predict_batch: cyl must be float64 [n,6], got {cyl.dtype} {list(cyl.shape)}')
+    dev = cyl.device
+    n, N = cyl.shape[0], Nu * Nv
+    cyl = cyl.contiguous()
+    if use is not None:
+        use = use.to(device=dev, dtype=torch.uint8).contiguous()
+        if tuple(use.shape) != (n,):
+            raise TypeError(f'grid_predict_batch: use must be [{n}], got {list(use.shape)}')
+    K1 = _dev3(K1, dev, (9,)); K2 = _dev3(K2, dev, (9,)); T21 = _dev3(T21, dev, (16,))
+    P = table.P.to(device=dev, dtype=torch.float64).contiguous()
+    st = table.status.to(device=dev, dtype=torch.int32).contiguous()
+    centre = table.centre.to(device=dev, dtype=torch.float64).contiguous()
+    # (the kernels write every slot)
+    f64 = torch.empty(n * N * 7, dtype=torch.float64, device=dev)
+    X, px = f64[:3 * N * n].view(n, N, 3), f64[3 * N * n:].view(n, 2, N, 2)
+    i32 = torch.empty(n * (2 * N + 4), dtype=torch.int32, device=dev)
+    state, vis, counts = i32[:N * n].view(n, N), i32[N * n:2 * N * n].view(n, N), i32[2 * N * n:].view(n, 4)
+    h, w = (0, 0) if image_size is None else (int(image_size[0]), int(image_size[1]))
+    prm = _lib.CpeGridPredictParams((C.c_int32 * 2)(lo0, lo1), (C.c_int32 * 2)(hi0, hi1), float(min_cos), w, h)
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    _lib.check(L.cpe_grid_predict_batch(ptr(cyl), ptr(use), n, float(radius), K1.data_ptr(), K2.data_ptr(), T21.data_ptr(), P.data_ptr(),
+                                        st.data_ptr(), table.lo, table.hi, centre.data_ptr(), C.addressof(prm), ptr(X), ptr(px), ptr(state),
+                                        ptr(vis), ptr(counts), _stream()), 'cpe_grid_predict_batch')
+    return dict(X=X, px=px, state=state, vis=vis, counts=counts, window=((lo0, hi0), (lo1, hi1)), Nu=Nu, Nv=Nv, family0=table.family0)
+
+
+def grid_assign_batch(gp: GridTables, pred, cam, tau_px=4.0, ratio=0.5, ids='col_row'):
+    """BUILD-DEFINED: one camera's grid tables re-numbered by the nearest predicted node, see include/cpe.h
+    cpe_grid_assign_batch.  pred: the dict of grid_predict_batch for the same n frames; cam 1 or 2: whose images gp holds;
+    ids: what gp.id holds ('col_row' as GridTables, 'row_col' as the planar detector writes).
+    -> dict(tables (GridTables of the kept points: xy, the new id, cnt = m), src i32[n,MAXP] (input slot), dist f64[n,MAXP] (px),
+            m i32[n], counts i32[n,8] (m, kept unchanged, kept re-numbered, no node, far, ambiguous, conflict, 0), stats f64[n,2]
+            (rms, max of dist), node_slot i32[n,N] (the kept point's input slot per node, or -1)); slots from m on hold zeros"""
+    L = _lib.load()
+    if cam not in (1, 2):
+        raise ValueError('grid_assign_batch: cam is 1 or 2')
+    if ids not in ('col_row', 'row_col'):
+        raise ValueError("ids is 'col_row' or 'row_col'")
+    if not (tau_px > 0 and 0 < ratio <= 1):
+        raise ValueError(f'grid_assign_batch: tau_px must be > 0 and ratio in (0, 1], got {tau_px} and {ratio}')
+    dev = gp.xy.device
+    n = gp.cnt.shape[0]
+    for name, t, dt, shape in (('xy', gp.xy, torch.float64, (n, MAXP, 2)), ('id', gp.id, torch.int32, (n, MAXP, 2)),
+                               ('cnt', gp.cnt, torch.int32, (n,))):
+        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
+            raise TypeError(f'grid_assign_batch: {name} must be {dt} {list(shape)} on {dev}, got {t.dtype} {list(t.shape)} on {t.device}')
+    Nu, Nv = pred['Nu'], pred['Nv']
+    N = Nu * Nv
+    px, vis = pred['px'], pred['vis']
+    if tuple(px.shape) != (n, 2, N, 2) or tuple(vis.shape) != (n, N) or px.device != dev or not px.is_contiguous() or not vis.is_contiguous():
+        raise TypeError(f'grid_assign_batch: pred must hold contiguous px [{n},2,{N},2] and vis [{n},{N}] on {dev}')
+    swap = int((pred['family0'] == 'col') != (ids == 'col_row'))
+    f64 = torch.zeros(n * (MAXP * 3 + 2), dtype=torch.float64, device=dev)
+    xy_out, dist, stats = f64[:2 * MAXP * n].view(n, MAXP, 2), f64[2 * MAXP * n:3 * MAXP * n].view(n, MAXP), f64[3 * MAXP * n:].view(n, 2)
+    i32 = torch.zeros(n * (MAXP * 3 + 9 + N), dtype=torch.int32, device=dev)
+    id_out, src = i32[:2 * MAXP * n].view(n, MAXP, 2), i32[2 * MAXP * n:3 * MAXP * n].view(n, MAXP)
+    tail = i32[3 * MAXP * n:]
+    m, counts, node_slot = tail[:n], tail[n:9 * n].view(n, 8), tail[9 * n:].view(n, N)
+    prm = _lib.CpeGridAssignParams(float(tau_px), float(ratio), swap, 0)
+    c = lambda t: t.contiguous()
+    x, d, k = c(gp.xy), c(gp.id), c(gp.cnt)
+    ptr = lambda t: None if t.numel() == 0 else t.data_ptr()
+    _lib.check(L.cpe_grid_assign_batch(ptr(x), ptr(d), ptr(k), n, None if n == 0 else px.data_ptr() + 16 * N * (cam - 1), 4 * N, ptr(vis),
+                                       cam - 1, pred['window'][0][0], pred['window'][1][0], Nu, Nv, C.addressof(prm), ptr(xy_out),
+                                       ptr(id_out), ptr(src), ptr(dist), ptr(m), ptr(counts), ptr(stats), ptr(node_slot), _stream()),
+               'cpe_grid_assign_batch')
+    return dict(tables=GridTables(xy_out, id_out, m), src=src, dist=dist, m=m, counts=counts, stats=stats, node_slot=node_slot)
+
+
+_REFINE_KEYS = ('cyl_raw', 'cyl', 'T', 'fvals', 'iters', 'status', 'pts3', 'idx', 'm', 'mean_err')
+
+
+def fit_single_cylinder_refined_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, table: LaserTable, radius, rounds=2, first=None,
+                                      tau_px=4.0, ratio=0.5, window=None, min_cos=0.1, image_size=None, fused=None, mode=FIT_LM,
+                                      **fit_kw):
+    """BUILD-DEFINED, opt-in: fit_single_cylinder_batch, then `rounds` rounds that re-number every grid point against the grid
+    the frame's own fitted cylinder predicts and fit again on fused points.
+    First fit_single_cylinder_batch(gp1, gp2, K1, K2, T21, radius, **first) (first: its keywords, match= included; None = the
+    reference's).  Then per round, for the frames whose current status is ST_OK: grid_predict_batch from the current cyl[:, 1]
+    (window, min_cos, image_size), grid_assign_batch of both images' detections (tau_px, ratio; with match= table 1 carries the
+    shift), fused_triangulate_batch on the re-numbered tables (fused: its keywords) and fit_cylinder_batch (mode, fit_kw).  A frame
+    takes a round's result only when that round's fit has status ST_OK; the choice is a torch.where on the device, and nothing
+    here waits for the GPU beyond grid_predict_batch's one look at a new table's centre_status.
+    -> dict(cyl_raw, cyl, T, fvals, iters, status, pts3, idx, m, mean_err (the first call's reprojection error, or a round's rms
+            ray residual; pixels either way): of the result each frame ended with; tables1, tables2: the
+            GridTables that result was made from (the re-numbered ones where a round was taken); round_taken i32[n]: the last
+            round taken, 0 = the first fit stands; renumbered i32[n,2]: points of image 1, 2 whose index that round changed;
+            rounds: per round dict(counts i32[n,2,8], stats f64[n,2,2] of grid_assign_batch per image, status i32[n] of the
+            round's fit, taken bool[n]); first: the first call's dict)"""
+    rounds = int(rounds)
+    if rounds < 0:
+        raise ValueError('fit_single_cylinder_refined_batch: rounds < 0')
+    n, dev = gp1.cnt.shape[0], gp1.xy.device
+    first_out = fit_single_cylinder_batch(gp1, gp2, K1, K2, T21, radius, **(first or {}))
+    if first and first.get('match') is not None:
+        gp1 = GridTables(gp1.xy, gp1.id + first_out['offset'][:, None, :], gp1.cnt)
+    cur = {k: first_out[k] for k in _REFINE_KEYS}
+    t1, t2 = gp1, gp2
+    taken_round = torch.zeros(n, dtype=torch.int32, device=dev)
+    renum = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+    per_round = []
+    for r in range(1, rounds + 1):
+        use = cur['status'] == ST_OK
+        pred = grid_predict_batch(cur['cyl'][:, 1], radius, K1, K2, T21, table, use=use, window=window, min_cos=min_cos,
+                                  image_size=image_size)
+        a1 = grid_assign_batch(gp1, pred, 1, tau_px=tau_px, ratio=ratio)
+        a2 = grid_assign_batch(gp2, pred, 2, tau_px=tau_px, ratio=ratio)
+        tri = fused_triangulate_batch(a1['tables'], a2['tables'], K1, K2, T21, table, **(fused or {}))
+        fit = fit_cylinder_batch(tri['pts3'], tri['m'], radius, mode=mode, **fit_kw)
+        fit['status'].masked_fill_((tri['flags'] & FLAG_OVERFLOW) != 0, ST_OVERFLOW)
+        take = use & (fit['status'] == ST_OK)
+        new = dict(fit, pts3=tri['pts3'], idx=tri['idx'], m=tri['m'], mean_err=tri['stats'][:, 0])
+        pick = lambda a, b: torch.where(take.view((n,) + (1,) * (a.dim() - 1)), a, b)
+        cur = {k: pick(new[k], cur[k]) for k in _REFINE_KEYS}
+        t1 = GridTables(pick(a1['tables'].xy, t1.xy), pick(a1['tables'].id, t1.id), pick(a1['tables'].cnt, t1.cnt))
+        t2 = GridTables(pick(a2['tables'].xy, t2.xy), pick(a2['tables'].id, t2.id), pick(a2['tables'].cnt, t2.cnt))
+        taken_round = torch.where(take, torch.full_like(taken_round, r), taken_round)
+        renum = pick(torch.stack([a1['counts'][:, 2], a2['counts'][:, 2]], 1), renum)
+        per_round.append(dict(counts=torch.stack([a1['counts'], a2['counts']], 1), stats=torch.stack([a1['stats'], a2['stats']], 1),
+                              status=fit['status'], taken=take))
+    out = dict(cur)
+    out.update(tables1=t1, tables2=t2, round_taken=taken_round, renumbered=renum, rounds=per_round, first=first_out)
     return out
 
 

@@ -89,6 +89,10 @@ _SIGS = {
     'cpe_projector_model_table': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
     'cpe_index_shift_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] + [C.c_void_p] * 8),
     'cpe_grid_relabel_batch': (C.c_int32, [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 11),
+    'cpe_grid_predict_batch': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32] +
+                               [C.c_void_p] * 8),
+    'cpe_grid_assign_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int32] * 5 +
+                              [C.c_void_p] * 10),
     'cpe_undistort_map': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_remap_bilinear_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'cpe_undistort_map_matlab': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -168,6 +172,17 @@ class CpeIndexShiftParams(C.Structure):
 
 class CpeRelabelParams(C.Structure):
     _fields_ = [('swap', C.c_int32), ('min_pts', C.c_int32), ('merge_frac', C.c_double), ('dir', C.c_int32 * 2)]
+
+
+class CpeGridPredictParams(C.Structure):
+    _fields_ = [('win_lo', C.c_int32 * 2), ('win_hi', C.c_int32 * 2), ('min_cos', C.c_double), ('img_w', C.c_int32), ('img_h', C.c_int32)]
+
+
+class CpeGridAssignParams(C.Structure):
+    _fields_ = [('tau_px', C.c_double), ('ratio', C.c_double), ('swap', C.c_int32), ('reserved', C.c_int32)]
+
+
+PRED_MAXN = 4096                                                                    # CPE_PRED_MAXN
 
 
 class CpeConsensusParams(C.Structure):

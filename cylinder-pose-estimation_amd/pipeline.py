@@ -35,7 +35,7 @@ class FramePipeline:
 
     def __init__(self, h, w, K1, K2, T21, radius, chunk=64, device='cuda:0', selector=fit.SEL_CHOOSE_IDX, th=0.3,
                  fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full', match=None, target='cylinder', plane=None,
-                 source='stereo', laser_table=None, table=None, relabel=None):
+                 source='stereo', laser_table=None, table=None, relabel=None, refine=None):
         self.h, self.w, self.chunk, self.device = h, w, chunk, torch.device(device)
         self.K1, self.K2, self.T21, self.radius = K1, K2, T21, radius
         self.selector, self.th, self.fit_mode = selector, th, fit_mode
@@ -82,6 +82,23 @@ class FramePipeline:
         self.source, self.laser_table = source, laser_table
         # keywords of fit.table_triangulate_batch: need_both, min_sin, max_res; source 'fused': of fit.fused_triangulate_batch
         self.table = dict(table or {})
+        # refine (build-defined, opt-in; source 'fused' only): None, or keywords of fit.fit_single_cylinder_refined_batch ({} = its
+        # defaults: rounds, first, tau_px, ratio, window, min_cos, image_size -- the frame's size unless given): the stereo fit
+        # first, then every grid point re-numbered against the grid that fit predicts and the fit again on fused points
+        if refine is not None:
+            if source != 'fused':
+                raise ValueError("refine= re-numbers against the laser-plane table and fits fused points: source='fused' only")
+            if target == 'plane':
+                raise ValueError("refine= predicts the grid on a cylinder: target='cylinder' only")
+            if ransac is not None:
+                raise ValueError('refine= fits every round with fit_cylinder_batch: ransac does not apply')
+            refine = dict(refine)
+            refine.setdefault('image_size', (h, w))
+            refine.setdefault('first', dict(selector=selector, th=th, mode=fit_mode))
+            nodes = (laser_table.hi - laser_table.lo + 1) ** 2
+            if refine.get('window') is None and nodes > fit.PRED_MAXN:
+                raise ValueError(f'refine=: the table holds {nodes} nodes, more than {fit.PRED_MAXN}: give window=')
+        self.refine = refine
         self.ws = {}
         # chunks are independent: `lanes` of them are in flight on their own HIP streams (each with its own
         # workspace), so the serial tails of one chunk (blob grouping, line fitting: one workgroup per frame)
@@ -146,8 +163,12 @@ class FramePipeline:
             ctr = (det['center'][:c], det['center'][c:])
         if self.source == 'fused':
             rk = None if self.ransac is None else dict(self.ransac, frame0=int(self.ransac.get('frame0', 0)) + frame0)
-            out = fit.fit_single_cylinder_fused_batch(g1, g2, self.K1, self.K2, self.T21, self.laser_table, self.radius, ransac=rk,
-                                                      mode=self.fit_mode, **self.table)
+            if self.refine is not None:
+                out = fit.fit_single_cylinder_refined_batch(g1, g2, self.K1, self.K2, self.T21, self.laser_table, self.radius,
+                                                            **dict(dict(fused=self.table, mode=self.fit_mode), **self.refine))
+            else:
+                out = fit.fit_single_cylinder_fused_batch(g1, g2, self.K1, self.K2, self.T21, self.laser_table, self.radius, ransac=rk,
+                                                          mode=self.fit_mode, **self.table)
             rec = torch.empty((c, REC), dtype=torch.float64, device=frames.device)
             rec[:, 0:6] = out['cyl'][:, 0]
             rec[:, 6:12] = out['cyl'][:, 1]
@@ -288,12 +309,19 @@ FUSED_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2)
                          flags=((), torch.int32))
 
 
-def alloc_fits(F, device, target='cylinder', source='stereo'):
+# what fit.fit_single_cylinder_refined_batch returns per frame (FramePipeline(source='fused', refine=...))
+REFINED_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2), torch.int32), m=((), torch.int32),
+                           cyl_raw=((2, 6), torch.float64), cyl=((2, 6), torch.float64), T=((4, 4), torch.float64), fvals=((2,), torch.float64),
+                           mean_err=((), torch.float64), status=((), torch.int32), round_taken=((), torch.int32),
+                           renumbered=((2,), torch.int32))
+
+
+def alloc_fits(F, device, target='cylinder', source='stereo', refine=False):
     """zeroed [F, ...] tensors for the per-frame outputs of fit.fit_single_cylinder_batch (target='plane': of
     fit.fit_single_plane_batch; source 'left' / 'right': of fit.fit_single_cylinder_mono_batch; source 'fused': of
-    fit.fit_single_cylinder_fused_batch) that FramePipeline.run_raw can keep"""
+    fit.fit_single_cylinder_fused_batch, with refine of fit.fit_single_cylinder_refined_batch) that FramePipeline.run_raw can keep"""
     if source == 'fused':
-        outputs = FUSED_FIT_OUTPUTS
+        outputs = REFINED_FIT_OUTPUTS if refine else FUSED_FIT_OUTPUTS
     else:
         outputs = dict(cylinder=FIT_OUTPUTS, plane=PLANE_FIT_OUTPUTS)[target] if source == 'stereo' else MONO_FIT_OUTPUTS
     return {k: torch.zeros((F,) + shape, dtype=dt, device=device) for k, (shape, dt) in outputs.items()}

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 123   /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 124  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -57,7 +57,7 @@ extern "C" {
                              118: cpe_table_triangulate_batch; 119: cpe_fit_projector_model, cpe_projector_model_table;
                              120: cpe_index_shift_batch; 121: cpe_multi_frame_consensus_batch,
                              cpe_multi_frame_consensus_workspace_bytes; 122: cpe_fused_triangulate_batch;
-                             123: cpe_grid_relabel_batch) */
+                             123: cpe_grid_relabel_batch; 124: cpe_grid_predict_batch, cpe_grid_assign_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -934,6 +934,105 @@ CPE_API int32_t cpe_grid_relabel_batch(const double *xy, const int32_t *id, cons
                                        const CpeRelabelParams *params, double *xy_out, int32_t *id_out, int32_t *cnt_out,
                                        int32_t *src, int32_t *lines, double *line_p, double *pitch, int32_t *counts, int32_t *flags,
                                        void *stream);
+
+/* BUILD-DEFINED, opt-in: the grid a fitted cylinder PREDICTS.  Once a frame has a cylinder pose, the pose and the laser-plane
+ * table say where every grid node (u, v) falls in each image: the node is the line of two planes of light, cut with the cylinder
+ * and projected.  cpe_grid_assign_batch names each detection by its nearest predicted node, point by point and per image, which no
+ * frame-wide shift can do.  One lane per (frame, node), one launch for the nodes and one for the counts on `stream`, no atomics,
+ * no workspace, no host synchronisation; two calls on the same inputs give the same bits.
+ *   cyl f64[n,6]: a point o_c on the axis and the axis direction a (any length), camera-1 coordinates: what
+ *     cpe_fit_cylinder_batch writes to cyl[:,1,:] (row stride 6); use u8[n] or NULL (all frames); radius R > 0, finite
+ *   K1, K2 f64[9], T21 f64[16]: DEVICE memory, as cpe_fused_triangulate_batch
+ *   P f64[2,L,4], line_status i32[2,L], lo, hi: exactly what cpe_table_triangulate_batch reads; L = hi - lo + 1 in 1..CPE_MAXL
+ *   centre f64[3] (device): the projector's centre (the first three numbers of the table's centre)
+ *   params NULL = the defaults of CpeGridPredictParams: the window [lo, hi] in both families, min_cos 0.1, no image bound
+ * The nodes are the window win_lo[k]..win_hi[k] of table family k, inside [lo, hi]: Nu x Nv = N of them, 1 <= N <= CPE_PRED_MAXN
+ * (otherwise CPE_ERR_ARG); node j = (u - win_lo[0]) Nv + (v - win_lo[1]).  Dot products are (a0 b0 + a1 b1) + a2 b2.
+ * Rule per (frame, node) (the order is the contract):
+ *   1. the frame is unusable when use is 0, any of its six numbers is not finite, or |a| is 0 or not finite: every node of the
+ *      frame gets CPE_PRED_NO_FRAME.  ah = a / |a|;
+ *   2. both planes [n0, p0] = P[0, u - lo], [n1, p1] = P[1, v - lo] must have line_status CPE_ST_OK, else CPE_PRED_NO_PLANE;
+ *   3. w = n0 x n1; |w|^2 < CPE_PRED_MIN_W2 or not finite: CPE_PRED_PARALLEL;
+ *   4. q = (-p0 (n1 x w) - p1 (w x n0)) / |w|^2, the point of the planes' line nearest to the origin; wh = w / |w|;
+ *   5. e = q - o_c, ep = e - (e.ah) ah, wp = wh - (wh.ah) ah, A = |wp|^2, B = ep.wp, C = |ep|^2 - R^2, disc = B B - A C;
+ *   6. A, B, C or disc not finite, A == 0 or disc <= 0: CPE_PRED_MISS;
+ *   7. s = sqrt(disc), t- = (-B - s) / A, t+ = (-B + s) / A, tC = (centre - q).wh.  The lit root t is the one nearer to tC:
+ *      t- when |t- - tC| <= |t+ - tC| (a tie goes to t-), otherwise t+;
+ *   8. X = q + t wh (not finite: CPE_PRED_MISS); g = X - o_c; outward normal nu = (g - (g.ah) ah) / R;
+ *   9. |nu.wh| < min_cos: CPE_PRED_GRAZING.  nu.wh = +-sqrt(disc) / R, so this keeps the square root away from zero: the error
+ *      of t grows with 1 / sqrt(disc) <= 1 / (min_cos R);
+ *  10. per camera j (R_j, t_j the rotation and translation of Tc, the identity and 0 for camera 1, T21 for camera 2; o_j as in
+ *      step 2 of cpe_table_triangulate_batch): Xc = R_j X + t_j (camera 1: X itself), Z = Xc[2], v = o_j - X.  The node is
+ *      visible when Z > 0, nu.v > min_cos |v|, and with x = (K[0] (Xc[0] / Z) + K[1] (Xc[1] / Z)) + K[2],
+ *      y = K[4] (Xc[1] / Z) + K[5], x and y are finite and, with an image bound, 0 <= x < img_w and 0 <= y < img_h (img_w <= 0 or
+ *      img_h <= 0: no bound).
+ * Outputs, every slot of every node written: X f64[n,N,3] (0 unless the state is CPE_PRED_OK); px f64[n,2,N,2] = (x, y) per
+ * camera (0 where the node is not visible in that camera); state i32[n,N]; vis i32[n,N]: bit 0 camera 1, bit 1 camera 2;
+ * counts i32[n,4] = OK nodes | visible in camera 1 | in camera 2 | in both.  n == 0 is a no-op.
+ * Limits: a rigid, ideal cylinder of the given radius; the table's errors and the pose's move the predictions alike. */
+#define CPE_PRED_MAXN 4096
+#define CPE_PRED_MIN_W2 1e-6   /* planes of light closer than 0.057 degrees to parallel: q carries the roundings of w times
+                                  1 / |w|^2, so at this gate a rounding of 1e-16 has grown to 1e-10 of the offsets, still an
+                                  order below the 1e-8 mm the points are held to; real families meet near 90 degrees */
+#define CPE_PRED_OK 0
+#define CPE_PRED_NO_FRAME 1
+#define CPE_PRED_NO_PLANE 2
+#define CPE_PRED_PARALLEL 3
+#define CPE_PRED_MISS 4
+#define CPE_PRED_GRAZING 5
+typedef struct CpeGridPredictParams {
+    int32_t win_lo[2];  /* first node index of table family 0, 1; >= lo */
+    int32_t win_hi[2];  /* last node index of table family 0, 1; <= hi and >= win_lo */
+    double  min_cos;    /* the grazing and facing gate, in (0, 1); default 0.1 */
+    int32_t img_w;      /* image bound in pixels; <= 0 (default): none */
+    int32_t img_h;
+} CpeGridPredictParams;
+CPE_API int32_t cpe_grid_predict_batch(const double *cyl, const uint8_t *use, int32_t n, double radius, const double *K1,
+                                       const double *K2, const double *T21, const double *P, const int32_t *line_status, int32_t lo,
+                                       int32_t hi, const double *centre, const CpeGridPredictParams *params, double *X, double *px,
+                                       int32_t *state, int32_t *vis, int32_t *counts, void *stream);
+
+/* BUILD-DEFINED, opt-in: re-number ONE image's detections against one camera's predicted pixels: every detection takes the index
+ * of its nearest predicted node, when that node is near, unambiguous and not claimed by a nearer detection.  One workgroup per
+ * image, the camera's predicted pixels staged in LDS, one lane per detection scanning them; the winner per node by integer LDS
+ * atomics only; one launch on `stream`, no workspace, no host synchronisation; two calls on the same inputs give the same bits.
+ *   xy f64[n,CPE_MAXP,2], id i32[n,CPE_MAXP,2], cnt i32[n]: as cpe_detect_grid_batch writes them
+ *   px: image f's predicted pixels are the N (x, y) pairs at px + f px_stride (px_stride in doubles, >= 2 N): px_stride = 4 N
+ *     and px + 2 N cam_bit address camera cam_bit of cpe_grid_predict_batch's px; vis i32[n,N] with cam_bit in {0, 1}: node j
+ *     is visible when bit cam_bit of vis[j] is set and both its pixel coordinates are finite
+ *   win_lo0, win_lo1, Nu, Nv: the window of the prediction, N = Nu Nv in 1..CPE_PRED_MAXN (otherwise CPE_ERR_ARG); node j
+ *     stands for u = win_lo0 + j / Nv of table family 0 and v = win_lo1 + j % Nv of family 1
+ *   params NULL = the defaults of CpeGridAssignParams
+ * Rule (the order is the contract), per image:
+ *   1. cnt is clamped to [0, CPE_MAXP]; slots past it are never read.  A point with a non-finite pixel is refused (counts[3]);
+ *   2. over the visible nodes in node order: d^2 = (x - px) (x - px) + (y - py) (y - py).  The nearest node is the first with
+ *      the smallest d^2 below +inf, the second nearest is taken likewise among the others; d1, d2 the square roots, d2 = +inf
+ *      with a single such node.  No such node: refused (counts[3]);
+ *   3. d1 >= tau_px: refused (far, counts[4]);
+ *   4. d1 > ratio d2: refused (ambiguous, counts[5]);
+ *   5. among the remaining points that name the same node the smallest (d1, slot) keeps it, the others are refused (conflict,
+ *      counts[6]);
+ *   6. kept points go in slot order to slots 0..m-1 of xy_out f64[n,CPE_MAXP,2] (a copy), id_out i32[n,CPE_MAXP,2] (component c
+ *      holds the node's index in family c ^ swap), src i32[n,CPE_MAXP] (the input slot) and dist f64[n,CPE_MAXP] (d1).  Slots
+ *      from m on are NOT written;
+ *   7. m i32[n]; counts i32[n,8] = m | kept with id_out equal to id | kept and re-numbered | refused in steps 1 / 2 | far |
+ *      ambiguous | conflict | 0; stats f64[n,2] = sqrt of the mean squared d1 and the largest d1 of the kept points, both 0
+ *      when m = 0; node_slot i32[n,N] or NULL: per node the input slot of the point that kept it, or -1.
+ * tau_px <= 0 or not finite, ratio outside (0, 1] and swap other than 0 / 1 are refused with CPE_ERR_ARG.  No output may overlap
+ * an input or another output (CPE_ERR_ARG).  n == 0 is a no-op.
+ * Limits: the brute-force scan costs cnt x N distances per image; a detection with no predicted node (one the window or the
+ * visibility tests left out) is dropped, not kept under its old index. */
+typedef struct CpeGridAssignParams {
+    double  tau_px;     /* a detection farther than this from its nearest node is refused; > 0; default 4.0 */
+    double  ratio;      /* d1 > ratio d2 is ambiguous; in (0, 1]; default 0.5 */
+    int32_t swap;       /* as CpeTableTriParams.swap */
+    int32_t reserved;
+} CpeGridAssignParams;
+CPE_API int32_t cpe_grid_assign_batch(const double *xy, const int32_t *id, const int32_t *cnt, int32_t n, const double *px,
+                                      int64_t px_stride, const int32_t *vis, int32_t cam_bit, int32_t win_lo0, int32_t win_lo1,
+                                      int32_t Nu, int32_t Nv, const CpeGridAssignParams *params, double *xy_out, int32_t *id_out,
+                                      int32_t *src, double *dist, int32_t *m, int32_t *counts, double *stats, int32_t *node_slot,
+                                      void *stream);
 
 /* Row f-3: the undistortion pre-step of the CLI entry point, utils/iotool.py:22-39
  *   undistort_image(image, camera_params) = cv2.undistort(image, IntrinsicMatrix, hstack(Radial, Tangential))
