@@ -109,6 +109,43 @@ def _run_pairs(names, paths, camera_json, dev, chunk, make_fits, make_pipeline, 
     return recs, fits
 
 
+def _frame_status(names, recs, match_flags=None, also=None):
+    """the records' status words -> frame_ok i32[F] on the device (1: both detect statuses and the fit status are zero, and with
+    match_flags i32[F] the frame is not fit.MATCH_WEAK), `skipped`: the other frames as dict(index, name, det_left, det_right,
+    fit[, match]), and the host values of also(frame_ok), a list of device scalars -- all brought back in one copy"""
+    F = len(names)
+    _, _, d_fit, d_l, d_r = pipeline.unpack_counters(recs[:, 15])
+    frame_ok = (d_fit == 0) & (d_l == 0) & (d_r == 0)
+    words = dict(det_left=d_l, det_right=d_r, fit=d_fit)
+    if match_flags is not None:
+        frame_ok = frame_ok & ((match_flags & fit.MATCH_WEAK) == 0)
+        words['match'] = match_flags
+    frame_ok = frame_ok.to(torch.int32)
+    extra = [] if also is None else list(also(frame_ok))
+    back = torch.cat([torch.stack(list(words.values()) + [frame_ok]).to(torch.int64).reshape(-1)] +
+                     [t.to(torch.int64).reshape(1) for t in extra]).cpu().tolist()
+    host = {k: back[j * F:(j + 1) * F] for j, k in enumerate(words)}
+    skipped = [dict(index=i, name=names[i], **{k: v[i] for k, v in host.items()}) for i in range(F) if not back[len(words) * F + i]]
+    return frame_ok, skipped, back[(len(words) + 1) * F:]
+
+
+def _index_range(idx, used):
+    """lo, hi (device scalars) of the indices idx i32[F,MAXP,2] in the slots used bool[F,MAXP]; lo > hi when no slot is"""
+    big = torch.iinfo(torch.int32).max
+    return torch.where(used[..., None], idx, big).amin(), torch.where(used[..., None], idx, -big).amax()
+
+
+def _take_multi_frame(res, n_good, status, what, T, fval):
+    """the end of the resident multi-frame modes (what: 'fit' or 'consensus'): a warning, or T_cam_agv and fval taken -> taken?"""
+    if n_good < 2:
+        warnings.warn(f'{n_good} fitted frame(s): fitCylinderWPts3sAngs needs two')
+    elif status != 0:
+        warnings.warn(f'multi-frame {what} ended with status {status} (include/cpe.h: cpe_multi_frame_{what}_batch)')
+    else:
+        res['T_cam_agv'], res['fval'] = T, fval
+    return n_good >= 2 and status == 0
+
+
 def _fit_projector(fits, frame_ok, projector, family0, use=None, table_path=None):
     """the projector model of an experiment's own stereo points: fit.fit_projector_model over the kept frames with lo, hi the
     range of the indices they hold, and its table for -N..N, N the largest |index| seen (or projector['lo'], ['hi']): also the
@@ -127,8 +164,7 @@ def _fit_projector(fits, frame_ok, projector, family0, use=None, table_path=None
     used = (torch.arange(fit.MAXP, device=frame_ok.device)[None, :] < fits['m'][:, None]) & (frame_ok != 0)[:, None]
     if use is not None:
         used = used & (use != 0)
-    big = torch.iinfo(torch.int32).max
-    lo, hi = torch.stack([torch.where(used[..., None], fits['idx'], big).amin(), torch.where(used[..., None], fits['idx'], -big).amax()]).cpu().tolist()
+    lo, hi = torch.stack(_index_range(fits['idx'], used)).cpu().tolist()
     if lo > hi:
         warnings.warn('no fitted frame: no projector model')
         return none
@@ -259,25 +295,10 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
                             lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=c, device=dev, match=match_offset,
                                                                    source=source, laser_table=laser_table, refine=refine), source)
     F = len(names)
-    _, _, d_fit, d_l, d_r = pipeline.unpack_counters(recs[:, 15])          # device tensors: the 'gpu' mode masks with them
-    st_fit, st_l, st_r = (t.cpu().tolist() for t in (d_fit, d_l, d_r))
-    if match_offset is None:
-        skipped = [dict(index=i, name=names[i], det_left=st_l[i], det_right=st_r[i], fit=st_fit[i])
-                   for i in range(F) if st_l[i] or st_r[i] or st_fit[i]]
-    else:
-        d_weak = fits['match_flags'] & fit.MATCH_WEAK
-        mfl = fits['match_flags'].cpu().tolist()
-        skipped = [dict(index=i, name=names[i], det_left=st_l[i], det_right=st_r[i], fit=st_fit[i], match=mfl[i])
-                   for i in range(F) if st_l[i] or st_r[i] or st_fit[i] or (mfl[i] & fit.MATCH_WEAK)]
+    # frame_ok: the device mask of the frames that are not in `skipped`; the resident multi-frame modes mask with it
+    frame_ok, skipped, _ = _frame_status(names, recs, None if match_offset is None else fits['match_flags'])
     res = dict(names=names, angles=angles, records=recs, pts3=fits['pts3'], cnt=fits['m'], cyl_raw=fits['cyl_raw'], skipped=skipped,
                T_cam_agv=None, fval=None)
-    def good_frames():
-        """i32[F] on the device: 1 for a frame that is not in `skipped`, made from the records' status words without a copy"""
-        ok = (d_fit == 0) & (d_l == 0) & (d_r == 0)
-        if match_offset is not None:
-            ok = ok & (d_weak == 0)
-        return ok.to(torch.int32)
-
     if match_offset is not None:
         res.update(offset=fits['offset'], match_score=fits['match_score'], match_flags=fits['match_flags'])
     if refine is not None:
@@ -286,41 +307,27 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     elif source != 'stereo':
         res.update(tri_counts=fits['counts'], tri_stats=fits['stats'])
     if projector is not None:
-        res['projector'], res['projector_shifted'], renumbered = _fit_projector(fits, good_frames(), projector, 'col',
-                                                                                table_path=table_path)
+        res['projector'], res['projector_shifted'], renumbered = _fit_projector(fits, frame_ok, projector, 'col', table_path=table_path)
         if renumbered is not None:
             res['projector_renumbered'] = renumbered
         fits = {k: v for k, v in fits.items() if k != 'idx'}
     if mat_path is not None:
         api.save_mat(mat_path, fits=fits, names=names)
     if multi_frame in ('gpu', 'lm'):
-        # resident: the kept frames are named by a device mask made from the records' status words, the whole tables go in
-        # as one group, and T, fval, status and the count of kept frames come back in one copy
-        frame_ok = good_frames()
+        # resident: the kept frames are named by the device mask, the whole tables go in as one group, and T, fval, status and
+        # the count of kept frames come back in one copy
         mf = multiframe.fit_multi_frame_gpu(fits['pts3'], fits['m'], fits['cyl_raw'], angles, radius, frame_ok=frame_ok,
                                             group_start=[0, F], method='lm' if multi_frame == 'lm' else 'nm')
         back = torch.cat([mf['T'][0], mf['fvals'][0], mf['status'][0:1].to(torch.float64),
                           frame_ok.sum().to(torch.float64).reshape(1)]).cpu().tolist()
-        n_good, status = int(back[19]), int(back[18])
-        if n_good < 2:
-            warnings.warn(f'{n_good} fitted frame(s): fitCylinderWPts3sAngs needs two')
-        elif status != 0:
-            warnings.warn(f'multi-frame fit ended with status {status} (include/cpe.h: cpe_multi_frame_fit_batch)')
-        else:
-            res['T_cam_agv'], res['fval'] = back[:16], back[17]
+        _take_multi_frame(res, int(back[19]), int(back[18]), 'fit', back[:16], back[17])
     elif multi_frame == 'consensus':
-        frame_ok = good_frames()
         mf = multiframe.fit_multi_frame_consensus_gpu(fits['pts3'], fits['m'], fits['cyl_raw'], angles, radius, frame_ok=frame_ok,
                                                       group_start=[0, F], **(consensus or {}))
         g = multiframe.group_result(mf)
         status, n_good = g['status'], int(frame_ok.sum())
         res['consensus'] = dict(inliers=[], rejected=[], n_inliers=g['n_inliers'], rounds=g['info'][3], flags=g['flags'], status=status)
-        if n_good < 2:
-            warnings.warn(f'{n_good} fitted frame(s): fitCylinderWPts3sAngs needs two')
-        elif status != 0:
-            warnings.warn(f'multi-frame consensus ended with status {status} (include/cpe.h: cpe_multi_frame_consensus_batch)')
-        else:
-            res['T_cam_agv'], res['fval'] = g['T'], g['fvals'][1]
+        if _take_multi_frame(res, n_good, status, 'consensus', g['T'], g['fvals'][1]):
             res['consensus']['inliers'] = [names[i] for i in range(F) if g['inlier'][i] == 1]
             res['consensus']['rejected'] = [dict(index=i, name=names[i], rms=math.sqrt(g['frame_terms'][i]))
                                             for i in range(F) if g['inlier'][i] == 0]
@@ -405,18 +412,9 @@ def run_plane_experiment(input_path, camera_json, K1, K2, T21, tau=0.0, max_roun
     recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, make_fits,
                             lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, 0.0, chunk=c, device=dev, target='plane',
                                                                    plane=dict(tau=tau, max_rounds=max_rounds), relabel=relabel))
-    F = len(names)
-    _, _, d_fit, d_l, d_r = pipeline.unpack_counters(recs[:, 15])
-    frame_ok = ((d_fit == 0) & (d_l == 0) & (d_r == 0)).to(torch.int32)
-    # the index range of the points the table may use, with the statuses in one copy
-    used = (fits['inlier_mask'] != 0) & (frame_ok != 0)[:, None]
-    big = torch.iinfo(torch.int32).max
-    lo = torch.where(used[..., None], fits['idx'], big).amin()
-    hi = torch.where(used[..., None], fits['idx'], -big).amax()
-    back = torch.cat([torch.stack([d_fit, d_l, d_r]).to(torch.int64).reshape(-1), torch.stack([lo, hi]).to(torch.int64)]).cpu().tolist()
-    st_fit, st_l, st_r, (lo, hi) = back[:F], back[F:2 * F], back[2 * F:3 * F], back[3 * F:]
-    skipped = [dict(index=i, name=names[i], det_left=st_l[i], det_right=st_r[i], fit=st_fit[i])
-               for i in range(F) if st_l[i] or st_r[i] or st_fit[i]]
+    # the index range of the points the table may use comes back with the statuses in one copy
+    frame_ok, skipped, (lo, hi) = _frame_status(
+        names, recs, also=lambda ok: _index_range(fits['idx'], (fits['inlier_mask'] != 0) & (ok != 0)[:, None]))
     table, consistent, laser_table = None, False, None
     if lo > hi:
         warnings.warn('no fitted frame: no laser-plane table')

@@ -5,6 +5,7 @@
 becomes fit_single_cylinder_batch(tables_left, tables_right, K1, K2, T_C2_C1, radius): all frames at
 once, everything resident on the GPU, one wavefront per frame (csrc/fit.hip)."""
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -50,12 +51,56 @@ def _dev3(a, device, shape):
     return t.to(device)
 
 
+# ---- call plumbing shared by the wrappers below (none of it loads the library) ----
+
+def _check_tables(what, gp, n=None, prefix='', dev=None):
+    """the dtype / shape / device check of a GridTables: n images (default: as many as gp.cnt holds) on dev (default: gp.xy's)"""
+    n = gp.cnt.shape[0] if n is None else n
+    dev = gp.xy.device if dev is None else dev
+    for name, t, dt, shape in (('xy', gp.xy, torch.float64, (n, MAXP, 2)), ('id', gp.id, torch.int32, (n, MAXP, 2)),
+                               ('cnt', gp.cnt, torch.int32, (n,))):
+        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
+            raise TypeError(f'{what}: {prefix}{name} must be {dt} {list(shape)} on {dev}, got {t.dtype} {list(t.shape)} on {t.device}')
+
+
+def _line_count(what, lo, hi):
+    """L = hi - lo + 1 grid-line indices, which must be 1..MAXL"""
+    nl = int(hi) - int(lo) + 1
+    if not 1 <= nl <= _lib.MAXL:
+        raise ValueError(f'{what}: {nl} indices in [{lo}, {hi}], must be 1..{_lib.MAXL}')
+    return nl
+
+
+def _cameras(K1, K2, T21, dev):
+    return _dev3(K1, dev, (9,)), _dev3(K2, dev, (9,)), _dev3(T21, dev, (16,))
+
+
+def _table_on(table, dev, centre=False):
+    """(P, status[, centre]) of a LaserTable as the kernels read them on dev"""
+    out = (table.P.to(device=dev, dtype=torch.float64).contiguous(), table.status.to(device=dev, dtype=torch.int32).contiguous())
+    return out + (table.centre.to(device=dev, dtype=torch.float64).contiguous(),) if centre else out
+
+
+def _ptr(t):
+    """the address the library gets: NULL for None and for a tensor without elements"""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def _slab(dev, dtype, zero, n, fields):
+    """one allocation (torch.zeros if zero, else torch.empty) carved into contiguous views that lie in the listed order, touch
+    and fill it: fields = [(name, shape)], every view is [n, *shape] (n None: shape as it stands) -> dict name -> view"""
+    shapes = [(() if n is None else (n,)) + tuple(shape) for _, shape in fields]
+    sizes = [math.prod(s) for s in shapes]
+    buf = (torch.zeros if zero else torch.empty)(sum(sizes), dtype=dtype, device=dev)
+    return {name: t.view(s) for (name, _), s, t in zip(fields, shapes, buf.split(sizes))}
+
+
 def select_triangulate_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, selector=SEL_CHOOSE_IDX, patch=3, th=0.3):
     """chooseIdx / triangulateWithThreshold / findGridCorrespondences + triangulate (fitSingleCylinder.m:10-17)"""
     L = _lib.load()
     dev = gp1.xy.device
     n = gp1.cnt.shape[0]
-    K1 = _dev3(K1, dev, (9,)); K2 = _dev3(K2, dev, (9,)); T21 = _dev3(T21, dev, (16,))
+    K1, K2, T21 = _cameras(K1, K2, T21, dev)
     ws_bytes = L.cpe_fit_workspace_bytes(n)
     ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
     p1 = torch.zeros((n, MAXP, 2), dtype=torch.float64, device=dev); p2 = torch.zeros_like(p1)
@@ -79,7 +124,7 @@ def choose_idx_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, patch=3, th=
     L = _lib.load()
     dev = gp1.xy.device
     n = gp1.cnt.shape[0]
-    K1 = _dev3(K1, dev, (9,)); K2 = _dev3(K2, dev, (9,)); T21 = _dev3(T21, dev, (16,))
+    K1, K2, T21 = _cameras(K1, K2, T21, dev)
     ws_bytes = L.cpe_fit_workspace_bytes(n)
     ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
     p1 = torch.zeros((n, MAXP, 2), dtype=torch.float64, device=dev); p2 = torch.zeros_like(p1)
@@ -98,7 +143,7 @@ def triangulate_batch(p1, p2, cnt, K1, K2, T21):
     L = _lib.load()
     dev = p1.device
     n = cnt.shape[0]
-    K1 = _dev3(K1, dev, (9,)); K2 = _dev3(K2, dev, (9,)); T21 = _dev3(T21, dev, (16,))
+    K1, K2, T21 = _cameras(K1, K2, T21, dev)
     X = torch.zeros((n, MAXP, 3), dtype=torch.float64, device=dev)
     err = torch.zeros((n, MAXP), dtype=torch.float64, device=dev); me = torch.zeros(n, dtype=torch.float64, device=dev)
     _lib.check(L.cpe_triangulate_batch(p1.contiguous().data_ptr(), p2.contiguous().data_ptr(), cnt.data_ptr(), n, K1.data_ptr(),
@@ -110,15 +155,18 @@ def triangulate_batch(p1, p2, cnt, K1, K2, T21):
 FIT_NELDER_MEAD, FIT_LM = 0, 1
 
 
+def _fit_outputs(n, dev):
+    """cyl_raw, cyl f64[n,2,6], T f64[n,4,4], fvals f64[n,2], iters i32[n,2], status i32[n]: zeroed, every one its own tensor"""
+    z = lambda dt, *shape: torch.zeros((n,) + shape, dtype=dt, device=dev)
+    return z(torch.float64, 2, 6), z(torch.float64, 2, 6), z(torch.float64, 4, 4), z(torch.float64, 2), z(torch.int32, 2), z(torch.int32)
+
+
 def fit_cylinder_batch(pts3, cnt, radius, tol_x=1e-5, tol_f=1e-5, max_iter=100000, max_fun_evals=100000, mode=FIT_NELDER_MEAD):
     """fitCylinderWPts3 + applyCylParamsPrior + cylParams2T (fitSingleCylinder.m:20-25)"""
     L = _lib.load()
     dev = pts3.device
     n = cnt.shape[0]
-    raw = torch.zeros((n, 2, 6), dtype=torch.float64, device=dev); cyl = torch.zeros_like(raw)
-    T = torch.zeros((n, 4, 4), dtype=torch.float64, device=dev)
-    fv = torch.zeros((n, 2), dtype=torch.float64, device=dev)
-    it = torch.zeros((n, 2), dtype=torch.int32, device=dev); st = torch.zeros(n, dtype=torch.int32, device=dev)
+    raw, cyl, T, fv, it, st = _fit_outputs(n, dev)
     prm = _lib.CpeFitParams(tol_x, tol_f, max_iter, max_fun_evals, mode, 0)
     _lib.check(L.cpe_fit_cylinder_batch(pts3.data_ptr(), cnt.data_ptr(), n, float(radius), C.addressof(prm),
                                         raw.data_ptr(), cyl.data_ptr(), T.data_ptr(), fv.data_ptr(), it.data_ptr(),
@@ -133,10 +181,7 @@ def fit_cylinder_ransac_batch(pts3, cnt, radius, hypotheses=64, sample=12, tau=0
     L = _lib.load()
     dev = pts3.device
     n = cnt.shape[0]
-    raw = torch.zeros((n, 2, 6), dtype=torch.float64, device=dev); cyl = torch.zeros_like(raw)
-    T = torch.zeros((n, 4, 4), dtype=torch.float64, device=dev)
-    fv = torch.zeros((n, 2), dtype=torch.float64, device=dev)
-    it = torch.zeros((n, 2), dtype=torch.int32, device=dev); st = torch.zeros(n, dtype=torch.int32, device=dev)
+    raw, cyl, T, fv, it, st = _fit_outputs(n, dev)
     ninl = torch.zeros(n, dtype=torch.int32, device=dev); mask = torch.zeros((n, _lib.MAXP), dtype=torch.uint8, device=dev)
     prm = _lib.CpeFitParams(tol_x, tol_f, max_iter, max_fun_evals, mode, 0)
     rp = _lib.CpeRansacParams(hypotheses, sample, tau, seed, frame0, hyp_iters, 0)
@@ -163,7 +208,7 @@ def match_offset_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, radius, wi
     n = gp1.cnt.shape[0]
     if not (0 <= win_c <= MATCH_MAX_WIN and 0 <= win_r <= MATCH_MAX_WIN):
         raise ValueError(f'match_offset_batch: window {win_c} x {win_r} outside 0..{MATCH_MAX_WIN}')
-    K1 = _dev3(K1, dev, (9,)); K2 = _dev3(K2, dev, (9,)); T21 = _dev3(T21, dev, (16,))
+    K1, K2, T21 = _cameras(K1, K2, T21, dev)
     ncand = (2 * win_c + 1) * (2 * win_r + 1)
     ws_bytes = L.cpe_match_offset_workspace_bytes(n, win_c, win_r)
     ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
@@ -177,6 +222,16 @@ def match_offset_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, radius, wi
                                         scores.data_ptr() if want_scores else None, flags.data_ptr(), id1.data_ptr(), _stream()),
                'cpe_match_offset_batch')
     return dict(offset=offset, score=score, scores=scores, flags=flags, id1=id1, tables=GridTables(gp1.xy, id1, gp1.cnt), _ws=ws)
+
+
+def _fit_points(pts3, m, radius, ransac, overflow=None, **kw):
+    """fit_cylinder_batch, or fit_cylinder_ransac_batch with the keywords of the dict `ransac`, on m points per frame.  overflow:
+    the flags i32[n] of whatever made the points; a frame it skipped with FLAG_OVERFLOW because its indices do not fit the dense
+    table has m = 0, and is reported as the ST_OVERFLOW it is"""
+    fit = fit_cylinder_batch(pts3, m, radius, **kw) if ransac is None else fit_cylinder_ransac_batch(pts3, m, radius, **ransac, **kw)
+    if overflow is not None:
+        fit['status'].masked_fill_((overflow & FLAG_OVERFLOW) != 0, ST_OVERFLOW)
+    return fit
 
 
 def fit_single_cylinder_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, radius, selector=SEL_CHOOSE_IDX,
@@ -197,16 +252,7 @@ def fit_single_cylinder_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, rad
         z = torch.zeros((n, 7), dtype=torch.int32, device=dev)       # (one fill: this is the path of every call without the search)
         extra = dict(offset=z[:, 0:2], match_score=z[:, 2:6], match_flags=z[:, 6])
     sel = select_triangulate_batch(gp1, gp2, K1, K2, T21, selector, patch, th)
-    if ransac is not None:
-        fit = fit_cylinder_ransac_batch(sel['pts3'], sel['m'], radius, **ransac, **fit_kw)
-    else:
-        fit = fit_cylinder_batch(sel['pts3'], sel['m'], radius, **fit_kw)
-    # a frame the selector skipped because its indices do not fit the dense table has m = 0: report it as the overflow it is
-    fit['status'].masked_fill_((sel['flags'] & FLAG_OVERFLOW) != 0, ST_OVERFLOW)
-    out = dict(sel)
-    out.update(fit)
-    out.update(extra)
-    return out
+    return dict(sel, **_fit_points(sel['pts3'], sel['m'], radius, ransac, sel['flags'], **fit_kw), **extra)
 
 
 PLANE_NO_GRID, PLANE_ORIGIN_POINT = 1, 2            # CPE_PLANEFIT_*
@@ -235,10 +281,8 @@ def fit_plane_batch(pts3, idx, cnt, tau=0.0, max_rounds=4):
     dev = pts3.device
     n = cnt.shape[0]
     # (the kernel writes every slot of every output: no fills)
-    f64 = torch.empty(n * (4 + 16 + 9 + 8), dtype=torch.float64, device=dev)
-    P, T, grid, stats = f64[:4 * n].view(n, 4), f64[4 * n:20 * n].view(n, 4, 4), f64[20 * n:29 * n].view(n, 3, 3), f64[29 * n:].view(n, 8)
-    i32 = torch.empty((3, n), dtype=torch.int32, device=dev)
-    ninl, flags, st = i32[0], i32[1], i32[2]
+    P, T, grid, stats = _slab(dev, torch.float64, False, n, [('P', (4,)), ('T', (4, 4)), ('grid', (3, 3)), ('stats', (8,))]).values()
+    ninl, flags, st = _slab(dev, torch.int32, False, None, [('n_inliers', (n,)), ('plane_flags', (n,)), ('status', (n,))]).values()
     mask = torch.empty((n, MAXP), dtype=torch.uint8, device=dev)
     prm = _lib.CpePlaneFitParams(float(tau), int(max_rounds), 0)
     _lib.check(L.cpe_fit_plane_batch(pts3.data_ptr(), idx.data_ptr(), cnt.data_ptr(), n, C.addressof(prm), P.data_ptr(), T.data_ptr(),
@@ -257,18 +301,15 @@ def index_planes_batch(pts3, idx, cnt, lo, hi, use=None, frame_ok=None, min_spre
     pts3, idx, cnt, use = _point_tables('index_planes_batch', pts3, idx, cnt, use)
     dev = pts3.device
     n = cnt.shape[0]
-    nl = int(hi) - int(lo) + 1
-    if not 1 <= nl <= _lib.MAXL:
-        raise ValueError(f'index_planes_batch: {nl} indices in [{lo}, {hi}], must be 1..{_lib.MAXL}')
+    nl = _line_count('index_planes_batch', lo, hi)
     if frame_ok is not None:
         if frame_ok.shape != (n,) or frame_ok.device != dev:
             raise TypeError(f'index_planes_batch: frame_ok must hold {n} values on {dev}')
         frame_ok = frame_ok.to(torch.int32).contiguous()
     # (the kernels write every slot of every output: no fills)
-    f64 = torch.empty(2 * nl * 8 + 4, dtype=torch.float64, device=dev)
-    P, stats, centre = f64[:8 * nl].view(2, nl, 4), f64[8 * nl:16 * nl].view(2, nl, 4), f64[16 * nl:]
-    i32 = torch.empty(3 * 2 * nl + 1, dtype=torch.int32, device=dev)
-    count, frames, st, cst = i32[:2 * nl].view(2, nl), i32[2 * nl:4 * nl].view(2, nl), i32[4 * nl:6 * nl].view(2, nl), i32[6 * nl:]
+    P, stats, centre = _slab(dev, torch.float64, False, None, [('P', (2, nl, 4)), ('stats', (2, nl, 4)), ('centre', (4,))]).values()
+    count, frames, st, cst = _slab(dev, torch.int32, False, None, [('count', (2, nl)), ('frames', (2, nl)), ('status', (2, nl)),
+                                                                   ('centre_status', (1,))]).values()
     _lib.check(L.cpe_index_planes_batch(pts3.data_ptr(), idx.data_ptr(), cnt.data_ptr(), n, None if use is None else use.data_ptr(),
                                         None if frame_ok is None else frame_ok.data_ptr(), int(lo), int(hi), float(min_spread),
                                         P.data_ptr(), stats.data_ptr(), count.data_ptr(), frames.data_ptr(), st.data_ptr(),
@@ -292,10 +333,10 @@ def grid_relabel_batch(tables: GridTables, center, swap=0, min_pts=3, merge_frac
     L = _lib.load()
     n = tables.cnt.shape[0]
     dev = tables.xy.device
-    for name, t, dt, shape in (('xy', tables.xy, torch.float64, (n, MAXP, 2)), ('id', tables.id, torch.int32, (n, MAXP, 2)),
-                               ('cnt', tables.cnt, torch.int32, (n,)), ('center', center, torch.float64, (n, 2))):
-        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
-            raise TypeError(f'grid_relabel_batch: {name} must be {dt} {list(shape)} on {dev}, got {t.dtype} {list(t.shape)} on {t.device}')
+    _check_tables('grid_relabel_batch', tables)
+    if center.dtype != torch.float64 or tuple(center.shape) != (n, 2) or center.device != dev:
+        raise TypeError(f'grid_relabel_batch: center must be torch.float64 [{n}, 2] on {dev}, got {center.dtype} {list(center.shape)} '
+                        f'on {center.device}')
     dir = tuple(int(d) for d in dir)
     if len(dir) != 2 or not all(d in (1, -1) for d in dir):
         raise ValueError(f'grid_relabel_batch: dir {dir} must be two of +1, -1')
@@ -304,17 +345,9 @@ def grid_relabel_batch(tables: GridTables, center, swap=0, min_pts=3, merge_frac
     xy, ids, cnt, center = tables.xy.contiguous(), tables.id.contiguous(), tables.cnt.contiguous(), center.contiguous()
     ML = _lib.MAXL
     xy_o = torch.zeros((n, MAXP, 2), dtype=torch.float64, device=dev)
-    i32 = torch.zeros(n * (2 * MAXP + MAXP + 2 * ML * 4 + 8 + 2), dtype=torch.int32, device=dev)
-    at = [0]
-
-    def take(k, *shape):
-        t = i32[at[0]:at[0] + k].view(*shape)
-        at[0] += k
-        return t
-    id_o, src, lines = take(2 * n * MAXP, n, MAXP, 2), take(n * MAXP, n, MAXP), take(8 * n * ML, n, 2, ML, 4)
-    counts, cnt_o, flags = take(8 * n, n, 2, 4), take(n, n), take(n, n)
-    f64 = torch.zeros(n * (2 * ML + 2), dtype=torch.float64, device=dev)
-    line_p, pitch = f64[:2 * n * ML].view(n, 2, ML), f64[2 * n * ML:].view(n, 2)
+    id_o, src, lines, counts, cnt_o, flags = _slab(dev, torch.int32, True, n, [('id', (MAXP, 2)), ('src', (MAXP,)), ('lines', (2, ML, 4)),
+                                                                               ('counts', (2, 4)), ('cnt', ()), ('flags', ())]).values()
+    line_p, pitch = _slab(dev, torch.float64, True, n, [('p', (2, ML)), ('pitch', (2,))]).values()
     prm = _lib.CpeRelabelParams(int(swap), int(min_pts), float(merge_frac), (C.c_int32 * 2)(*dir))
     _lib.check(L.cpe_grid_relabel_batch(xy.data_ptr(), ids.data_ptr(), cnt.data_ptr(), center.data_ptr(), n, C.addressof(prm),
                                         xy_o.data_ptr(), id_o.data_ptr(), cnt_o.data_ptr(), src.data_ptr(), lines.data_ptr(),
@@ -386,9 +419,7 @@ class LaserTable:
         if self.family0 not in ('col', 'row'):
             raise ValueError("LaserTable.family0 is 'col' or 'row'")
         self.lo, self.hi = int(self.lo), int(self.hi)
-        nl = self.hi - self.lo + 1
-        if not 1 <= nl <= _lib.MAXL:
-            raise ValueError(f'LaserTable: {nl} indices in [{self.lo}, {self.hi}], must be 1..{_lib.MAXL}')
+        nl = _line_count('LaserTable', self.lo, self.hi)
         if tuple(self.P.shape) != (2, nl, 4) or tuple(self.status.shape) != (2, nl):
             raise ValueError(f'LaserTable: P must be [2,{nl},4] and status [2,{nl}], got {list(self.P.shape)} and {list(self.status.shape)}')
 
@@ -436,9 +467,7 @@ def fit_projector_model(pts3, idx, cnt, lo, hi, use=None, frame_ok=None, tau=0.0
     pts3, idx, cnt, use = _point_tables('fit_projector_model', pts3, idx, cnt, use)
     dev = pts3.device
     n = cnt.shape[0]
-    nl = int(hi) - int(lo) + 1
-    if not 1 <= nl <= _lib.MAXL:
-        raise ValueError(f'fit_projector_model: {nl} indices in [{lo}, {hi}], must be 1..{_lib.MAXL}')
+    nl = _line_count('fit_projector_model', lo, hi)
     if frame_ok is not None:
         if frame_ok.shape != (n,) or frame_ok.device != dev:
             raise TypeError(f'fit_projector_model: frame_ok must hold {n} values on {dev}')
@@ -446,16 +475,14 @@ def fit_projector_model(pts3, idx, cnt, lo, hi, use=None, frame_ok=None, tau=0.0
     if x0 is not None:
         x0 = _dev3(x0, dev, (15,))
     # (the kernels write every slot of every output, the mask after the call's own fill: no fills here)
-    f64 = torch.empty(16 + 2 * nl * 12, dtype=torch.float64, device=dev)
-    model, moments = f64[:16], f64[16:].view(2, nl, 12)
-    i32 = torch.empty(8 + 4 * nl + 4 * n, dtype=torch.int32, device=dev)
-    info, count, frames, fc = i32[:8], i32[8:8 + 2 * nl].view(2, nl), i32[8 + 2 * nl:8 + 4 * nl].view(2, nl), i32[8 + 4 * nl:].view(n, 4)
+    model, moments = _slab(dev, torch.float64, False, None, [('model', (16,)), ('moments', (2, nl, 12))]).values()
+    info, count, frames, fc = _slab(dev, torch.int32, False, None, [('info', (8,)), ('count', (2, nl)), ('frames', (2, nl)),
+                                                                    ('frame_counts', (n, 4))]).values()
     mask = torch.empty((2, n, MAXP), dtype=torch.uint8, device=dev)
     prm = _lib.CpeProjectorModelParams(float(tau), int(max_rounds), int(maxiter), float(min_spread), float(tolx), float(tolf))
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-    _lib.check(L.cpe_fit_projector_model(ptr(pts3), ptr(idx), ptr(cnt), n, ptr(use), ptr(frame_ok), int(lo), int(hi), C.addressof(prm),
-                                         ptr(x0), model.data_ptr(), info.data_ptr(), moments.data_ptr(), count.data_ptr(),
-                                         frames.data_ptr(), ptr(mask), ptr(fc), _stream()), 'cpe_fit_projector_model')
+    _lib.check(L.cpe_fit_projector_model(_ptr(pts3), _ptr(idx), _ptr(cnt), n, _ptr(use), _ptr(frame_ok), int(lo), int(hi), C.addressof(prm),
+                                         _ptr(x0), model.data_ptr(), info.data_ptr(), moments.data_ptr(), count.data_ptr(),
+                                         frames.data_ptr(), _ptr(mask), _ptr(fc), _stream()), 'cpe_fit_projector_model')
     return dict(model=model, info=info, moments=moments, count=count, frames=frames, inlier_mask=mask, frame_counts=fc, lo=int(lo),
                 hi=int(hi))
 
@@ -504,14 +531,11 @@ class ProjectorModel:
     def table(self, lo, hi):
         """the laser-plane table of the indices lo..hi, any range of at most MAXL: also indices no frame showed"""
         L = _lib.load()
-        nl = int(hi) - int(lo) + 1
-        if not 1 <= nl <= _lib.MAXL:
-            raise ValueError(f'ProjectorModel.table: {nl} indices in [{lo}, {hi}], must be 1..{_lib.MAXL}')
+        nl = _line_count('ProjectorModel.table', lo, hi)
         dev = self.model.device
         model, info = self.model.to(torch.float64).contiguous(), self.info.to(device=dev, dtype=torch.int32).contiguous()
-        f64 = torch.empty(2 * nl * 4 + 4, dtype=torch.float64, device=dev)
-        i32 = torch.empty(2 * nl + 1, dtype=torch.int32, device=dev)
-        P, centre, st, cst = f64[:8 * nl].view(2, nl, 4), f64[8 * nl:], i32[:2 * nl].view(2, nl), i32[2 * nl:]
+        P, centre = _slab(dev, torch.float64, False, None, [('P', (2, nl, 4)), ('centre', (4,))]).values()
+        st, cst = _slab(dev, torch.int32, False, None, [('status', (2, nl)), ('centre_status', (1,))]).values()
         _lib.check(L.cpe_projector_model_table(model.data_ptr(), info.data_ptr(), int(lo), int(hi), P.data_ptr(), st.data_ptr(),
                                                centre.data_ptr(), cst.data_ptr(), _stream()), 'cpe_projector_model_table')
         return LaserTable(P, st, lo, hi, centre, cst, self.family0)
@@ -543,19 +567,12 @@ def table_triangulate_batch(gp: GridTables, K, Tc, table: LaserTable, need_both=
     L = _lib.load()
     dev = gp.xy.device
     n = gp.cnt.shape[0]
-    for name, t, dt, shape in (('xy', gp.xy, torch.float64, (n, MAXP, 2)), ('id', gp.id, torch.int32, (n, MAXP, 2)),
-                               ('cnt', gp.cnt, torch.int32, (n,))):
-        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
-            raise TypeError(f'table_triangulate_batch: {name} must be {dt} {list(shape)} on {dev}, got {t.dtype} {list(t.shape)} on {t.device}')
+    _check_tables('table_triangulate_batch', gp)
     K = _dev3(K, dev, (9,))
     Tc = None if Tc is None else _dev3(Tc, dev, (16,))
-    P = table.P.to(device=dev, dtype=torch.float64).contiguous()
-    st = table.status.to(device=dev, dtype=torch.int32).contiguous()
-    f64 = torch.zeros(n * (MAXP * 5 + 2), dtype=torch.float64, device=dev)
-    X, res, stats = f64[:3 * MAXP * n].view(n, MAXP, 3), f64[3 * MAXP * n:5 * MAXP * n].view(n, MAXP, 2), f64[5 * MAXP * n:].view(n, 2)
-    i32 = torch.zeros(n * (MAXP * 4 + 5), dtype=torch.int32, device=dev)
-    idx, src = i32[:2 * MAXP * n].view(n, MAXP, 2), i32[2 * MAXP * n:4 * MAXP * n].view(n, MAXP, 2)
-    m, counts = i32[4 * MAXP * n:4 * MAXP * n + n], i32[4 * MAXP * n + n:].view(n, 4)
+    P, st = _table_on(table, dev)
+    X, res, stats = _slab(dev, torch.float64, True, n, [('pts3', (MAXP, 3)), ('res', (MAXP, 2)), ('stats', (2,))]).values()
+    idx, src, m, counts = _slab(dev, torch.int32, True, n, [('idx', (MAXP, 2)), ('src', (MAXP, 2)), ('m', ()), ('counts', (4,))]).values()
     prm = _lib.CpeTableTriParams(table.swap_for(ids), int(bool(need_both)), float(min_sin), float(max_res))
     _lib.check(L.cpe_table_triangulate_batch(gp.xy.contiguous().data_ptr(), gp.id.contiguous().data_ptr(), gp.cnt.contiguous().data_ptr(), n,
                                              K.data_ptr(), None if Tc is None else Tc.data_ptr(), P.data_ptr(), st.data_ptr(), table.lo,
@@ -581,23 +598,15 @@ def fused_triangulate_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, table
     L = _lib.load()
     dev = gp1.xy.device
     n = gp1.cnt.shape[0]
-    for g, gp in (('gp1', gp1), ('gp2', gp2)):
-        for name, t, dt, shape in (('xy', gp.xy, torch.float64, (n, MAXP, 2)), ('id', gp.id, torch.int32, (n, MAXP, 2)),
-                                   ('cnt', gp.cnt, torch.int32, (n,))):
-            if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
-                raise TypeError(f'fused_triangulate_batch: {g}.{name} must be {dt} {list(shape)} on {dev}, got {t.dtype} '
-                                f'{list(t.shape)} on {t.device}')
+    _check_tables('fused_triangulate_batch', gp1, n, 'gp1.', dev)
+    _check_tables('fused_triangulate_batch', gp2, n, 'gp2.', dev)
     if not (sigma_px > 0 and sigma_mm > 0):
         raise ValueError(f'fused_triangulate_batch: sigma_px and sigma_mm must be > 0, got {sigma_px} and {sigma_mm}')
-    K1 = _dev3(K1, dev, (9,)); K2 = _dev3(K2, dev, (9,)); T21 = _dev3(T21, dev, (16,))
-    P = table.P.to(device=dev, dtype=torch.float64).contiguous()
-    st = table.status.to(device=dev, dtype=torch.int32).contiguous()
-    f64 = torch.zeros(n * (MAXP * 7 + 4), dtype=torch.float64, device=dev)
-    X, res, stats = f64[:3 * MAXP * n].view(n, MAXP, 3), f64[3 * MAXP * n:7 * MAXP * n].view(n, MAXP, 4), f64[7 * MAXP * n:].view(n, 4)
-    i32 = torch.zeros(n * (MAXP * 5 + 8), dtype=torch.int32, device=dev)
-    idx, src = i32[:2 * MAXP * n].view(n, MAXP, 2), i32[2 * MAXP * n:5 * MAXP * n].view(n, MAXP, 3)
-    tail = i32[5 * MAXP * n:]
-    m, flags, counts = tail[:n], tail[n:2 * n], tail[2 * n:].view(n, 6)
+    K1, K2, T21 = _cameras(K1, K2, T21, dev)
+    P, st = _table_on(table, dev)
+    X, res, stats = _slab(dev, torch.float64, True, n, [('pts3', (MAXP, 3)), ('res', (MAXP, 4)), ('stats', (4,))]).values()
+    idx, src, m, flags, counts = _slab(dev, torch.int32, True, n, [('idx', (MAXP, 2)), ('src', (MAXP, 3)), ('m', ()), ('flags', ()),
+                                                                   ('counts', (6,))]).values()
     prm = _lib.CpeFusedTriParams(table.swap_for(ids), int(bool(need_both)), float(min_sin), float(sigma_px), float(sigma_mm),
                                  float(max_res), float(max_px))
     c = lambda t: t.contiguous()
@@ -620,15 +629,7 @@ def fit_single_cylinder_fused_batch(gp1: GridTables, gp2: GridTables, K1, K2, T2
     join set FLAG_OVERFLOW."""
     tri = fused_triangulate_batch(gp1, gp2, K1, K2, T21, table, need_both=need_both, min_sin=min_sin, sigma_px=sigma_px,
                                   sigma_mm=sigma_mm, max_res=max_res, max_px=max_px)
-    if ransac is not None:
-        fit = fit_cylinder_ransac_batch(tri['pts3'], tri['m'], radius, mode=mode, **ransac, **fit_kw)
-    else:
-        fit = fit_cylinder_batch(tri['pts3'], tri['m'], radius, mode=mode, **fit_kw)
-    fit['status'].masked_fill_((tri['flags'] & FLAG_OVERFLOW) != 0, ST_OVERFLOW)
-    out = dict(tri)
-    out.update(fit)
-    out['mean_err'] = tri['stats'][:, 0]
-    return out
+    return dict(tri, **_fit_points(tri['pts3'], tri['m'], radius, ransac, tri['flags'], mode=mode, **fit_kw), mean_err=tri['stats'][:, 0])
 
 
 PRED_MAXN = _lib.PRED_MAXN                                          # CPE_PRED_MAXN
@@ -666,21 +667,16 @@ def grid_predict_batch(cyl, radius, K1, K2, T21, table: LaserTable, use=None, wi
         use = use.to(device=dev, dtype=torch.uint8).contiguous()
         if tuple(use.shape) != (n,):
             raise TypeError(f'grid_predict_batch: use must be [{n}], got {list(use.shape)}')
-    K1 = _dev3(K1, dev, (9,)); K2 = _dev3(K2, dev, (9,)); T21 = _dev3(T21, dev, (16,))
-    P = table.P.to(device=dev, dtype=torch.float64).contiguous()
-    st = table.status.to(device=dev, dtype=torch.int32).contiguous()
-    centre = table.centre.to(device=dev, dtype=torch.float64).contiguous()
+    K1, K2, T21 = _cameras(K1, K2, T21, dev)
+    P, st, centre = _table_on(table, dev, centre=True)
     # (the kernels write every slot)
-    f64 = torch.empty(n * N * 7, dtype=torch.float64, device=dev)
-    X, px = f64[:3 * N * n].view(n, N, 3), f64[3 * N * n:].view(n, 2, N, 2)
-    i32 = torch.empty(n * (2 * N + 4), dtype=torch.int32, device=dev)
-    state, vis, counts = i32[:N * n].view(n, N), i32[N * n:2 * N * n].view(n, N), i32[2 * N * n:].view(n, 4)
+    X, px = _slab(dev, torch.float64, False, n, [('X', (N, 3)), ('px', (2, N, 2))]).values()
+    state, vis, counts = _slab(dev, torch.int32, False, n, [('state', (N,)), ('vis', (N,)), ('counts', (4,))]).values()
     h, w = (0, 0) if image_size is None else (int(image_size[0]), int(image_size[1]))
     prm = _lib.CpeGridPredictParams((C.c_int32 * 2)(lo0, lo1), (C.c_int32 * 2)(hi0, hi1), float(min_cos), w, h)
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-    _lib.check(L.cpe_grid_predict_batch(ptr(cyl), ptr(use), n, float(radius), K1.data_ptr(), K2.data_ptr(), T21.data_ptr(), P.data_ptr(),
-                                        st.data_ptr(), table.lo, table.hi, centre.data_ptr(), C.addressof(prm), ptr(X), ptr(px), ptr(state),
-                                        ptr(vis), ptr(counts), _stream()), 'cpe_grid_predict_batch')
+    _lib.check(L.cpe_grid_predict_batch(_ptr(cyl), _ptr(use), n, float(radius), K1.data_ptr(), K2.data_ptr(), T21.data_ptr(), P.data_ptr(),
+                                        st.data_ptr(), table.lo, table.hi, centre.data_ptr(), C.addressof(prm), _ptr(X), _ptr(px), _ptr(state),
+                                        _ptr(vis), _ptr(counts), _stream()), 'cpe_grid_predict_batch')
     return dict(X=X, px=px, state=state, vis=vis, counts=counts, window=((lo0, hi0), (lo1, hi1)), Nu=Nu, Nv=Nv, family0=table.family0)
 
 
@@ -700,29 +696,22 @@ def grid_assign_batch(gp: GridTables, pred, cam, tau_px=4.0, ratio=0.5, ids='col
         raise ValueError(f'grid_assign_batch: tau_px must be > 0 and ratio in (0, 1], got {tau_px} and {ratio}')
     dev = gp.xy.device
     n = gp.cnt.shape[0]
-    for name, t, dt, shape in (('xy', gp.xy, torch.float64, (n, MAXP, 2)), ('id', gp.id, torch.int32, (n, MAXP, 2)),
-                               ('cnt', gp.cnt, torch.int32, (n,))):
-        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
-            raise TypeError(f'grid_assign_batch: {name} must be {dt} {list(shape)} on {dev}, got {t.dtype} {list(t.shape)} on {t.device}')
+    _check_tables('grid_assign_batch', gp)
     Nu, Nv = pred['Nu'], pred['Nv']
     N = Nu * Nv
     px, vis = pred['px'], pred['vis']
     if tuple(px.shape) != (n, 2, N, 2) or tuple(vis.shape) != (n, N) or px.device != dev or not px.is_contiguous() or not vis.is_contiguous():
         raise TypeError(f'grid_assign_batch: pred must hold contiguous px [{n},2,{N},2] and vis [{n},{N}] on {dev}')
     swap = int((pred['family0'] == 'col') != (ids == 'col_row'))
-    f64 = torch.zeros(n * (MAXP * 3 + 2), dtype=torch.float64, device=dev)
-    xy_out, dist, stats = f64[:2 * MAXP * n].view(n, MAXP, 2), f64[2 * MAXP * n:3 * MAXP * n].view(n, MAXP), f64[3 * MAXP * n:].view(n, 2)
-    i32 = torch.zeros(n * (MAXP * 3 + 9 + N), dtype=torch.int32, device=dev)
-    id_out, src = i32[:2 * MAXP * n].view(n, MAXP, 2), i32[2 * MAXP * n:3 * MAXP * n].view(n, MAXP)
-    tail = i32[3 * MAXP * n:]
-    m, counts, node_slot = tail[:n], tail[n:9 * n].view(n, 8), tail[9 * n:].view(n, N)
+    xy_out, dist, stats = _slab(dev, torch.float64, True, n, [('xy', (MAXP, 2)), ('dist', (MAXP,)), ('stats', (2,))]).values()
+    id_out, src, m, counts, node_slot = _slab(dev, torch.int32, True, n, [('id', (MAXP, 2)), ('src', (MAXP,)), ('m', ()), ('counts', (8,)),
+                                                                          ('node_slot', (N,))]).values()
     prm = _lib.CpeGridAssignParams(float(tau_px), float(ratio), swap, 0)
     c = lambda t: t.contiguous()
     x, d, k = c(gp.xy), c(gp.id), c(gp.cnt)
-    ptr = lambda t: None if t.numel() == 0 else t.data_ptr()
-    _lib.check(L.cpe_grid_assign_batch(ptr(x), ptr(d), ptr(k), n, None if n == 0 else px.data_ptr() + 16 * N * (cam - 1), 4 * N, ptr(vis),
-                                       cam - 1, pred['window'][0][0], pred['window'][1][0], Nu, Nv, C.addressof(prm), ptr(xy_out),
-                                       ptr(id_out), ptr(src), ptr(dist), ptr(m), ptr(counts), ptr(stats), ptr(node_slot), _stream()),
+    _lib.check(L.cpe_grid_assign_batch(_ptr(x), _ptr(d), _ptr(k), n, None if n == 0 else px.data_ptr() + 16 * N * (cam - 1), 4 * N, _ptr(vis),
+                                       cam - 1, pred['window'][0][0], pred['window'][1][0], Nu, Nv, C.addressof(prm), _ptr(xy_out),
+                                       _ptr(id_out), _ptr(src), _ptr(dist), _ptr(m), _ptr(counts), _ptr(stats), _ptr(node_slot), _stream()),
                'cpe_grid_assign_batch')
     return dict(tables=GridTables(xy_out, id_out, m), src=src, dist=dist, m=m, counts=counts, stats=stats, node_slot=node_slot)
 
@@ -766,8 +755,7 @@ def fit_single_cylinder_refined_batch(gp1: GridTables, gp2: GridTables, K1, K2, 
         a1 = grid_assign_batch(gp1, pred, 1, tau_px=tau_px, ratio=ratio)
         a2 = grid_assign_batch(gp2, pred, 2, tau_px=tau_px, ratio=ratio)
         tri = fused_triangulate_batch(a1['tables'], a2['tables'], K1, K2, T21, table, **(fused or {}))
-        fit = fit_cylinder_batch(tri['pts3'], tri['m'], radius, mode=mode, **fit_kw)
-        fit['status'].masked_fill_((tri['flags'] & FLAG_OVERFLOW) != 0, ST_OVERFLOW)
+        fit = _fit_points(tri['pts3'], tri['m'], radius, None, tri['flags'], mode=mode, **fit_kw)
         take = use & (fit['status'] == ST_OK)
         new = dict(fit, pts3=tri['pts3'], idx=tri['idx'], m=tri['m'], mean_err=tri['stats'][:, 0])
         pick = lambda a, b: torch.where(take.view((n,) + (1,) * (a.dim() - 1)), a, b)
@@ -804,19 +792,16 @@ def index_shift_batch(pts3, idx, cnt, table: LaserTable, use=None, win=(4, 4), t
         raise ValueError(f'index_shift_batch: window {win} outside 0..{SHIFT_MAX_WIN}')
     if not tau > 0:
         raise ValueError(f'index_shift_batch: tau must be > 0, got {tau}')
-    P = table.P.to(device=dev, dtype=torch.float64).contiguous()
-    st = table.status.to(device=dev, dtype=torch.int32).contiguous()
+    P, st = _table_on(table, dev)
     ncand = 2 * win[0] + 1 + 2 * win[1] + 1
     # (the kernel writes every slot of every output but idx past the count)
-    i32 = torch.empty(n * (2 + 8 + ncand + 2), dtype=torch.int32, device=dev)
-    shift, score = i32[:2 * n].view(n, 2), i32[2 * n:10 * n].view(n, 2, 4)
-    scores, flags = i32[10 * n:(10 + ncand) * n].view(n, ncand), i32[(10 + ncand) * n:].view(n, 2)
+    shift, score, scores, flags = _slab(dev, torch.int32, False, n, [('shift', (2,)), ('score', (2, 4)), ('scores', (ncand,)),
+                                                                     ('flags', (2,))]).values()
     rms = torch.empty((n, 2, 2), dtype=torch.float64, device=dev)
     out = torch.zeros((n, MAXP, 2), dtype=torch.int32, device=dev)
     prm = _lib.CpeIndexShiftParams((C.c_int32 * 2)(*win), float(tau), int(min_score), table.swap_for(ids))
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-    _lib.check(L.cpe_index_shift_batch(ptr(pts3), ptr(idx), ptr(cnt), n, ptr(use), P.data_ptr(), st.data_ptr(), table.lo, table.hi,
-                                       C.addressof(prm), ptr(shift), ptr(score), ptr(scores), ptr(rms), ptr(flags), ptr(out), _stream()),
+    _lib.check(L.cpe_index_shift_batch(_ptr(pts3), _ptr(idx), _ptr(cnt), n, _ptr(use), P.data_ptr(), st.data_ptr(), table.lo, table.hi,
+                                       C.addressof(prm), _ptr(shift), _ptr(score), _ptr(scores), _ptr(rms), _ptr(flags), _ptr(out), _stream()),
                'cpe_index_shift_batch')
     return dict(shift=shift, score=score, scores=scores, rms=rms, flags=flags, idx=out)
 
@@ -855,11 +840,4 @@ def fit_single_cylinder_mono_batch(gp: GridTables, K, Tc, table: LaserTable, rad
     stats and mean_err f64[n] = stats[:, 0]: NOT a reprojection error in pixels as in the stereo call, but the rms distance in mm
     of the points from the planes that made them (0 for points cut with one plane only)."""
     tri = table_triangulate_batch(gp, K, Tc, table, need_both=need_both, min_sin=min_sin, max_res=max_res)
-    if ransac is not None:
-        fit = fit_cylinder_ransac_batch(tri['pts3'], tri['m'], radius, mode=mode, **ransac, **fit_kw)
-    else:
-        fit = fit_cylinder_batch(tri['pts3'], tri['m'], radius, mode=mode, **fit_kw)
-    out = dict(tri)
-    out.update(fit)
-    out['mean_err'] = tri['stats'][:, 0]
-    return out
+    return dict(tri, **_fit_points(tri['pts3'], tri['m'], radius, ransac, mode=mode, **fit_kw), mean_err=tri['stats'][:, 0])

@@ -4,6 +4,8 @@
 This is the loop body of exp_gridDetection.m:55-81 (makePyGridPts L/R, then fitSingleCylinder per frame)
 turned into batched kernel launches; frames are processed in chunks so that the detect workspace stays
 bounded (about 170 MB per 1920x1200 image: DESIGN.md section 3)."""
+from collections import namedtuple
+
 import torch
 
 from . import api, fit
@@ -30,17 +32,144 @@ def unpack_counters(code):
     return n_pts, iters, st // 64, (st // 8) % 8, st % 8
 
 
+# ---- the per-frame outputs run_raw can keep: name -> (shape, dtype), the common core plus what each fit adds ----
+_F64, _I32 = torch.float64, torch.int32
+_POINTS = dict(pts3=((fit.MAXP, 3), _F64), idx=((fit.MAXP, 2), _I32), m=((), _I32))
+_CYL = dict(cyl_raw=((2, 6), _F64), cyl=((2, 6), _F64), T=((4, 4), _F64), fvals=((2,), _F64), mean_err=((), _F64), status=((), _I32))
+
+
+def _tri(counts, res, src, stats):
+    """what the two table triangulations add per frame, by their widths"""
+    return dict(counts=((counts,), _I32), res=((fit.MAXP, res), _F64), src=((fit.MAXP, src), _I32), stats=((stats,), _F64))
+
+
+# fit.fit_single_cylinder_batch (the selector's idx is not kept)
+FIT_OUTPUTS = dict({k: v for k, v in _POINTS.items() if k != 'idx'}, **_CYL, offset=((2,), _I32), match_score=((4,), _I32),
+                   match_flags=((), _I32))
+PLANE_FIT_OUTPUTS = dict(_POINTS, P=((4,), _F64), T=((4, 4), _F64), grid=((3, 3), _F64), stats=((8,), _F64), n_inliers=((), _I32),
+                         inlier_mask=((fit.MAXP,), torch.uint8), plane_flags=((), _I32), mean_err=((), _F64), status=((), _I32))
+# what fit.fit_single_plane_batch adds with relabel= (per frame and image); FramePipeline(relabel=...).run_raw keeps them when the
+# fits dict holds tensors of these names
+RELABEL_OUTPUTS = dict(relabel_counts=((2, 2, 4), _I32), relabel_flags=((2,), _I32))
+MONO_FIT_OUTPUTS = dict(_POINTS, **_CYL, **_tri(4, 2, 2, 2))
+FUSED_FIT_OUTPUTS = dict(_POINTS, **_CYL, **_tri(6, 4, 3, 4), flags=((), _I32))
+# what fit.fit_single_cylinder_refined_batch returns per frame (FramePipeline(source='fused', refine=...))
+REFINED_FIT_OUTPUTS = dict(_POINTS, **_CYL, round_taken=((), _I32), renumbered=((2,), _I32))
+
+
+# ---- the two record layouts (beside REC) ----
+def _cylinder_record(out, st_l, st_r):
+    """the REC layout; word 14 is out['mean_err'] in the fit's own unit (pixels; mm off the laser planes for one camera).
+    Without a fit (stage 'detect': BASELINE configs[1]) the fit's words are zero"""
+    m = out['m']
+    if 'cyl' in out:
+        rec = torch.empty((m.shape[0], REC), dtype=torch.float64, device=m.device)
+        rec[:, 0:6] = out['cyl'][:, 0]
+        rec[:, 6:12] = out['cyl'][:, 1]
+        rec[:, 12:14] = out['fvals']
+        iters, status = out['iters'][:, 0], out['status']
+    else:
+        rec = torch.zeros((m.shape[0], REC), dtype=torch.float64, device=m.device)
+        iters = status = torch.zeros_like(m)
+    rec[:, 14] = out['mean_err']
+    rec[:, 15] = pack_counters(m, iters, status, st_l, st_r)
+    return rec
+
+
+def _plane_record(out, st_l, st_r):
+    rec = torch.empty((out['m'].shape[0], REC), dtype=torch.float64, device=out['m'].device)
+    rec[:, 0:4] = out['P']
+    rec[:, 4:7] = out['T'][:, :3, 3]
+    rec[:, 7:10] = out['T'][:, :3, 0]
+    rec[:, 10:12] = out['grid'][:, 1:3].norm(dim=2)
+    rec[:, 12:14] = out['stats'][:, 0:2]
+    rec[:, 14] = out['mean_err']
+    rec[:, 15] = pack_counters(out['m'], out['stats'][:, 6], out['status'], st_l, st_r)
+    return rec
+
+
+# ---- tables -> fit dict, one per mode: (pipeline, g1, g2, the two images' centres, the chunk's first frame) ----
+def _ransac(p, frame0):
+    return None if p.ransac is None else dict(p.ransac, frame0=int(p.ransac.get('frame0', 0)) + frame0)
+
+
+def _fit_stereo(p, g1, g2, ctr, frame0):
+    return fit.fit_single_cylinder_batch(g1, g2, p.K1, p.K2, p.T21, p.radius, p.selector, 3, p.th, ransac=_ransac(p, frame0),
+                                         match=p.match, mode=p.fit_mode)
+
+
+def _fit_detect(p, g1, g2, ctr, frame0):
+    return fit.select_triangulate_batch(g1, g2, p.K1, p.K2, p.T21, p.selector, 3, p.th)
+
+
+def _fit_plane(p, g1, g2, ctr, frame0):
+    rl = {} if p.relabel is None else dict(relabel=p.relabel, center1=ctr[0], center2=ctr[1])
+    return fit.fit_single_plane_batch(g1, g2, p.K1, p.K2, p.T21, p.selector, 3, p.th, **p.plane, **rl)
+
+
+def _fit_mono(p, g1, g2, ctr, frame0):
+    g, K, Tc = (g1, p.K1, None) if g2 is None else (g2, p.K2, p.T21)
+    return fit.fit_single_cylinder_mono_batch(g, K, Tc, p.laser_table, p.radius, ransac=_ransac(p, frame0), mode=p.fit_mode, **p.table)
+
+
+def _fit_fused(p, g1, g2, ctr, frame0):
+    return fit.fit_single_cylinder_fused_batch(g1, g2, p.K1, p.K2, p.T21, p.laser_table, p.radius, ransac=_ransac(p, frame0),
+                                               mode=p.fit_mode, **p.table)
+
+
+def _fit_refined(p, g1, g2, ctr, frame0):
+    return fit.fit_single_cylinder_refined_batch(g1, g2, p.K1, p.K2, p.T21, p.laser_table, p.radius,
+                                                 **dict(dict(fused=p.table, mode=p.fit_mode), **p.refine))
+
+
+# ---- every combination of options FramePipeline runs: which cameras' images are detected ('LR', 'L', 'R'), tables -> fit dict,
+#      the record writer, the outputs run_raw can keep (None: none) ----
+_Mode = namedtuple('_Mode', 'cameras fit record outputs')
+_MODES = {
+    'stereo cylinder': _Mode('LR', _fit_stereo, _cylinder_record, FIT_OUTPUTS),
+    'stereo detect-only': _Mode('LR', _fit_detect, _cylinder_record, None),
+    'stereo plane': _Mode('LR', _fit_plane, _plane_record, PLANE_FIT_OUTPUTS),
+    'mono left': _Mode('L', _fit_mono, _cylinder_record, MONO_FIT_OUTPUTS),
+    'mono right': _Mode('R', _fit_mono, _cylinder_record, MONO_FIT_OUTPUTS),
+    'fused': _Mode('LR', _fit_fused, _cylinder_record, FUSED_FIT_OUTPUTS),
+    'fused refined': _Mode('LR', _fit_refined, _cylinder_record, REFINED_FIT_OUTPUTS),
+}
+
+
+def _mode_name(target='cylinder', source='stereo', stage='full', refine=False):
+    """the key of _MODES for options that FramePipeline's constructor has let through"""
+    if source == 'fused':
+        return 'fused refined' if refine else 'fused'
+    if source != 'stereo':
+        return 'mono right' if source == 'right' else 'mono left'
+    return 'stereo detect-only' if stage == 'detect' else 'stereo ' + target
+
+
+def _split_detect(det, cameras, interleaved=False):
+    """the detect call's dict -> (g1, g2, st_l, st_r, (centre1, centre2)) of the left and the right images.  cameras 'LR': the
+    images lie interleaved (L0 R0 L1 R1 ...; the tables are copied out) or concatenated (all left, then all right; views);
+    'L' / 'R': they are that camera's alone, the other one's tables are None and its status words zero"""
+    n = det['n'].shape[0]
+    if cameras == 'LR':
+        sl = (slice(0, None, 2), slice(1, None, 2)) if interleaved else (slice(None, n // 2), slice(n // 2, None))
+    else:
+        sl = (slice(None), None) if cameras == 'L' else (None, slice(None))
+
+    def camera(s):
+        if s is None:
+            return None, torch.zeros_like(det['status']), None
+        return fit.GridTables(*(det[k][s].contiguous() for k in ('xy', 'id', 'n'))), det['status'][s], det['center'][s].contiguous()
+    (g1, st_l, c1), (g2, st_r, c2) = camera(sl[0]), camera(sl[1])
+    return g1, g2, st_l, st_r, (c1, c2)
+
+
 class FramePipeline:
-    """reusable workspaces for chunks of `chunk` stereo frames of size h x w"""
+    """reusable workspaces for chunks of `chunk` stereo frames of size h x w; the options resolve to one row of _MODES"""
 
     def __init__(self, h, w, K1, K2, T21, radius, chunk=64, device='cuda:0', selector=fit.SEL_CHOOSE_IDX, th=0.3,
                  fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full', match=None, target='cylinder', plane=None,
                  source='stereo', laser_table=None, table=None, relabel=None, refine=None):
-        self.h, self.w, self.chunk, self.device = h, w, chunk, torch.device(device)
-        self.K1, self.K2, self.T21, self.radius = K1, K2, T21, radius
-        self.selector, self.th, self.fit_mode = selector, th, fit_mode
-        self.ransac = ransac            # None, or keywords of fit.fit_cylinder_ransac_batch (build-defined config 5)
-        self.match = match              # None, or keywords of fit.match_offset_batch (build-defined: the index-shift search, stage 'full')
+        # ---- which combinations exist: the rows of _MODES; everything else is refused here ----
         if stage not in ('full', 'detect'):
             raise ValueError("stage is 'full' or 'detect'")
         if target not in ('cylinder', 'plane'):
@@ -49,25 +178,14 @@ class FramePipeline:
             raise ValueError("target='plane': match and ransac score with the cylinder's radius and do not apply (radius is not read)")
         if target != 'plane' and plane is not None:
             raise ValueError("plane= holds keywords of the planar fit: target='plane' only")
-        self.target = target            # 'plane' (build-defined): the planar detector and fit.fit_single_plane_batch; records as beside REC
-        self.plane = dict(plane or {})  # keywords of fit.fit_plane_batch: tau, max_rounds
-        # relabel (build-defined): None, or keywords of fit.grid_relabel_batch ({} = its defaults): both images' tables are
-        # re-labelled from the lines' geometry and the detect call's centres before the selector pairs them by index
         if relabel is not None and target != 'plane':
             raise ValueError("relabel= re-labels straight grid lines: target='plane' only (the cylinder's lines are curved, and "
                              "the cylinder script numbers them differently)")
-        self.relabel = None if relabel is None else dict(relabel)
-        self.stage = stage              # 'detect': stop after chooseIdx + triangulate (fitSingleCylinder.m:12-17), no cylinder fit
-        # source 'left' / 'right' (build-defined): only that camera's images are detected, and the points come from its rays and the
-        # laser-plane table (fit.fit_single_cylinder_mono_batch) instead of the stereo pair; camera 2 uses K2 and T21
-        # source 'fused' (build-defined): both cameras' images are detected as for 'stereo', and every grid point of either table
-        # becomes a 3-D point from its rays and the laser planes in one solve (fit.fit_single_cylinder_fused_batch); no selector
         if source not in ('stereo', 'left', 'right', 'fused'):
             raise ValueError("source is 'stereo', 'left', 'right' or 'fused'")
-        if source == 'stereo':
-            if laser_table is not None or table is not None:
-                raise ValueError("laser_table= and table= belong to one camera: source='left' or 'right'")
-        else:
+        if source == 'stereo' and (laser_table is not None or table is not None):
+            raise ValueError("laser_table= and table= belong to one camera: source='left' or 'right'")
+        if source != 'stereo':
             if laser_table is None:
                 raise ValueError(f"source='{source}' needs laser_table= (a fit.LaserTable)" +
                                  ('' if source == 'fused' else ': one camera has no other way to a 3-D point'))
@@ -78,13 +196,6 @@ class FramePipeline:
                 raise ValueError(f"source='{source}': target='plane' builds the table from stereo points and does not read one")
             if stage == 'detect':
                 raise ValueError(f"source='{source}': stage='detect' ends at the stereo selector")
-            laser_table = laser_table.to(self.device)
-        self.source, self.laser_table = source, laser_table
-        # keywords of fit.table_triangulate_batch: need_both, min_sin, max_res; source 'fused': of fit.fused_triangulate_batch
-        self.table = dict(table or {})
-        # refine (build-defined, opt-in; source 'fused' only): None, or keywords of fit.fit_single_cylinder_refined_batch ({} = its
-        # defaults: rounds, first, tau_px, ratio, window, min_cos, image_size -- the frame's size unless given): the stereo fit
-        # first, then every grid point re-numbered against the grid that fit predicts and the fit again on fused points
         if refine is not None:
             if source != 'fused':
                 raise ValueError("refine= re-numbers against the laser-plane table and fits fused points: source='fused' only")
@@ -92,12 +203,32 @@ class FramePipeline:
                 raise ValueError("refine= predicts the grid on a cylinder: target='cylinder' only")
             if ransac is not None:
                 raise ValueError('refine= fits every round with fit_cylinder_batch: ransac does not apply')
-            refine = dict(refine)
-            refine.setdefault('image_size', (h, w))
-            refine.setdefault('first', dict(selector=selector, th=th, mode=fit_mode))
             nodes = (laser_table.hi - laser_table.lo + 1) ** 2
             if refine.get('window') is None and nodes > fit.PRED_MAXN:
                 raise ValueError(f'refine=: the table holds {nodes} nodes, more than {fit.PRED_MAXN}: give window=')
+            refine = dict(dict(image_size=(h, w), first=dict(selector=selector, th=th, mode=fit_mode)), **refine)
+        self.mode = _mode_name(target, source, stage, refine is not None)     # a key of _MODES
+        self.h, self.w, self.chunk, self.device = h, w, chunk, torch.device(device)
+        self.K1, self.K2, self.T21, self.radius = K1, K2, T21, radius
+        self.selector, self.th, self.fit_mode = selector, th, fit_mode
+        self.stage = stage              # 'detect': stop after chooseIdx + triangulate (fitSingleCylinder.m:12-17), no cylinder fit
+        self.target = target            # 'plane' (build-defined): the planar detector and fit.fit_single_plane_batch; records as beside REC
+        # source (build-defined beyond 'stereo'): 'left' / 'right': only that camera's images are detected, and the points come from
+        # its rays and the laser-plane table (fit.fit_single_cylinder_mono_batch); camera 2 uses K2 and T21.  'fused': both are
+        # detected as for 'stereo', and every grid point of either table becomes a 3-D point from its rays and the laser planes in
+        # one solve (fit.fit_single_cylinder_fused_batch); no selector
+        self.source, self.laser_table = source, None if laser_table is None else laser_table.to(self.device)
+        self.ransac = ransac            # None, or keywords of fit.fit_cylinder_ransac_batch (build-defined config 5)
+        self.match = match              # None, or keywords of fit.match_offset_batch (build-defined: the index-shift search, stage 'full')
+        self.plane = dict(plane or {})  # keywords of fit.fit_plane_batch: tau, max_rounds
+        # relabel (build-defined): None, or keywords of fit.grid_relabel_batch ({} = its defaults): both images' tables are
+        # re-labelled from the lines' geometry and the detect call's centres before the selector pairs them by index
+        self.relabel = None if relabel is None else dict(relabel)
+        # keywords of fit.table_triangulate_batch: need_both, min_sin, max_res; source 'fused': of fit.fused_triangulate_batch
+        self.table = dict(table or {})
+        # refine (build-defined, opt-in): None, or keywords of fit.fit_single_cylinder_refined_batch ({} = its defaults: rounds,
+        # first, tau_px, ratio, window, min_cos, image_size -- the frame's size unless given): the stereo fit first, then every
+        # grid point re-numbered against the grid that fit predicts and the fit again on fused points
         self.refine = refine
         self.ws = {}
         # chunks are independent: `lanes` of them are in flight on their own HIP streams (each with its own
@@ -121,97 +252,29 @@ class FramePipeline:
         return (left.dim() == 3 and left.shape == right.shape and left.stride() == (2 * h * w, w, 1) and right.stride() == left.stride()
                 and right.data_ptr() == left.data_ptr() + h * w and left.untyped_storage().data_ptr() == right.untyped_storage().data_ptr())
 
-    def _run_chunk_mono(self, frames, lane, frame0):
-        """run_chunk with source 'left' / 'right': one detect call over the c images of that camera"""
-        c = frames.shape[0]
-        det = api.detect_grid_batch(frames.contiguous(), self._ws(c, lane), target=self.target, debug_planes=False)
-        K, Tc = (self.K1, None) if self.source == 'left' else (self.K2, self.T21)
-        rk = None if self.ransac is None else dict(self.ransac, frame0=int(self.ransac.get('frame0', 0)) + frame0)
-        out = fit.fit_single_cylinder_mono_batch(fit.GridTables(det['xy'], det['id'], det['n']), K, Tc, self.laser_table, self.radius,
-                                                 ransac=rk, mode=self.fit_mode, **self.table)
-        zero = torch.zeros_like(det['status'])
-        st_l, st_r = (det['status'], zero) if self.source == 'left' else (zero, det['status'])
-        rec = torch.empty((c, REC), dtype=torch.float64, device=frames.device)
-        rec[:, 0:6] = out['cyl'][:, 0]
-        rec[:, 6:12] = out['cyl'][:, 1]
-        rec[:, 12:14] = out['fvals']
-        rec[:, 14] = out['mean_err']          # mm off the laser planes, not pixels (fit.fit_single_cylinder_mono_batch)
-        rec[:, 15] = pack_counters(out['m'], out['iters'][:, 0], out['status'], st_l, st_r)
-        return rec, det, out
-
     def run_chunk(self, left, right, lane=0, frame0=0):
         """-> records f64 [c,16], the detect call's dict, the fit's dict.  With source 'left' / 'right' only that argument is
         read (the other may be None) and the detect call sees c images, not 2c"""
-        if self.source in ('left', 'right'):
-            return self._run_chunk_mono(left if self.source == 'left' else right, lane, frame0)
-        c = left.shape[0]
-        if c > 0 and self._interleaved(left, right):
+        mode = _MODES[self.mode]
+        interleaved = mode.cameras == 'LR' and left.shape[0] > 0 and self._interleaved(left, right)
+        if mode.cameras != 'LR':
+            frames = (left if mode.cameras == 'L' else right).contiguous()
+        elif interleaved:
             # the pairs already lie one after the other in memory: the detect call reads them in place (L0 R0 L1 R1 ...)
-            frames = torch.as_strided(left, (2 * c, self.h, self.w), (self.h * self.w, self.w, 1))
-            det = api.detect_grid_batch(frames, self._ws(2 * c, lane), target=self.target, debug_planes=False)   # only the tables are read
-            sl = lambda k, o: det[k][o::2].contiguous()
-            g1 = fit.GridTables(sl('xy', 0), sl('id', 0), sl('n', 0))
-            g2 = fit.GridTables(sl('xy', 1), sl('id', 1), sl('n', 1))
-            st_l, st_r = det['status'][0::2], det['status'][1::2]
-            ctr = (sl('center', 0), sl('center', 1))
+            frames = torch.as_strided(left, (2 * left.shape[0], self.h, self.w), (self.h * self.w, self.w, 1))
         else:
             frames = torch.cat([left, right])             # [2c,h,w]: one detect call for both cameras (a copy)
-            det = api.detect_grid_batch(frames, self._ws(2 * c, lane), target=self.target, debug_planes=False)   # only the tables are read
-            g1 = fit.GridTables(det['xy'][:c], det['id'][:c], det['n'][:c])
-            g2 = fit.GridTables(det['xy'][c:], det['id'][c:], det['n'][c:])
-            st_l, st_r = det['status'][:c], det['status'][c:]
-            ctr = (det['center'][:c], det['center'][c:])
-        if self.source == 'fused':
-            rk = None if self.ransac is None else dict(self.ransac, frame0=int(self.ransac.get('frame0', 0)) + frame0)
-            if self.refine is not None:
-                out = fit.fit_single_cylinder_refined_batch(g1, g2, self.K1, self.K2, self.T21, self.laser_table, self.radius,
-                                                            **dict(dict(fused=self.table, mode=self.fit_mode), **self.refine))
-            else:
-                out = fit.fit_single_cylinder_fused_batch(g1, g2, self.K1, self.K2, self.T21, self.laser_table, self.radius, ransac=rk,
-                                                          mode=self.fit_mode, **self.table)
-            rec = torch.empty((c, REC), dtype=torch.float64, device=frames.device)
-            rec[:, 0:6] = out['cyl'][:, 0]
-            rec[:, 6:12] = out['cyl'][:, 1]
-            rec[:, 12:14] = out['fvals']
-            rec[:, 14] = out['mean_err']          # rms ray residual of the pairs in pixels (fit.fit_single_cylinder_fused_batch)
-            rec[:, 15] = pack_counters(out['m'], out['iters'][:, 0], out['status'], st_l, st_r)
-            return rec, det, out
-        if self.stage == 'detect':      # BASELINE configs[1]: grid detection + triangulation only
-            out = fit.select_triangulate_batch(g1, g2, self.K1, self.K2, self.T21, self.selector, 3, self.th)
-            rec = torch.zeros((c, REC), dtype=torch.float64, device=frames.device)
-            rec[:, 14] = out['mean_err']
-            zero = torch.zeros_like(out['m'])
-            rec[:, 15] = pack_counters(out['m'], zero, zero, st_l, st_r)
-            return rec, det, out
-        if self.target == 'plane':
-            rl = {} if self.relabel is None else dict(relabel=self.relabel, center1=ctr[0], center2=ctr[1])
-            out = fit.fit_single_plane_batch(g1, g2, self.K1, self.K2, self.T21, self.selector, 3, self.th, **self.plane, **rl)
-            rec = torch.empty((c, REC), dtype=torch.float64, device=frames.device)
-            rec[:, 0:4] = out['P']
-            rec[:, 4:7] = out['T'][:, :3, 3]
-            rec[:, 7:10] = out['T'][:, :3, 0]
-            rec[:, 10:12] = out['grid'][:, 1:3].norm(dim=2)
-            rec[:, 12:14] = out['stats'][:, 0:2]
-            rec[:, 14] = out['mean_err']
-            rec[:, 15] = pack_counters(out['m'], out['stats'][:, 6], out['status'], st_l, st_r)
-            return rec, det, out
-        rk = None if self.ransac is None else dict(self.ransac, frame0=int(self.ransac.get('frame0', 0)) + frame0)
-        out = fit.fit_single_cylinder_batch(g1, g2, self.K1, self.K2, self.T21, self.radius, self.selector, 3, self.th,
-                                            ransac=rk, match=self.match, mode=self.fit_mode)
-        rec = torch.empty((c, REC), dtype=torch.float64, device=frames.device)
-        rec[:, 0:6] = out['cyl'][:, 0]
-        rec[:, 6:12] = out['cyl'][:, 1]
-        rec[:, 12:14] = out['fvals']
-        rec[:, 14] = out['mean_err']
-        rec[:, 15] = pack_counters(out['m'], out['iters'][:, 0], out['status'], st_l, st_r)
-        return rec, det, out
+        det = api.detect_grid_batch(frames, self._ws(frames.shape[0], lane), target=self.target, debug_planes=False)   # only the tables are read
+        g1, g2, st_l, st_r, centres = _split_detect(det, mode.cameras, interleaved)
+        out = mode.fit(self, g1, g2, centres, frame0)
+        return mode.record(out, st_l, st_r), det, out
 
     def run(self, left, right):
         """left/right: u8 [F,h,w] on the device -> records f64 [F,16] (source 'left' / 'right': the other one may be None)"""
-        if self.source in ('left', 'right'):
-            one = left if self.source == 'left' else right
-            return self._for_chunks(one.shape[0], one.device, lambda i0, i1, lane: self._run_chunk_mono(one[i0:i1], lane, i0)[0])
-        return self._for_chunks(left.shape[0], left.device, lambda i0, i1, lane: self.run_chunk(left[i0:i1], right[i0:i1], lane, i0)[0])
+        one = right if _MODES[self.mode].cameras == 'R' else left
+        part = lambda t, i0, i1: None if t is None else t[i0:i1]
+        return self._for_chunks(one.shape[0], one.device,
+                                lambda i0, i1, lane: self.run_chunk(part(left, i0, i1), part(right, i0, i1), lane, i0)[0])
 
     def _for_chunks(self, F, device, body):
         """the walk over the chunks that run and run_raw share: records f64 [F,16] of body(i0, i1, lane); with lanes > 1
@@ -248,80 +311,33 @@ class FramePipeline:
             raise ValueError(f'run_raw: the pre-step is for {prestep.w}x{prestep.h} frames, the pipeline for {self.w}x{self.h}')
         if fits is not None and self.stage != 'full':
             raise ValueError("run_raw: fit outputs exist only with stage='full'")
-
-        def body_mono(i0, i1, lane):
-            from . import iotool
-            cam = 0 if self.source == 'left' else 1
-            raw = (left_raw, right_raw)[cam][i0:i1]
-            prestep._check(raw, self.source)
-            st = self._stage.get(lane)
-            if st is None:
-                st = self._stage[lane] = torch.empty((self.chunk, self.h, self.w), dtype=torch.uint8, device=raw.device)
-            iotool._prestep(prestep.maps[cam], raw, st[:i1 - i0], self.h * self.w)
-            rec, _, out = self._run_chunk_mono(st[:i1 - i0], lane, i0)
-            if fits is not None:
-                for k, t in fits.items():
-                    t[i0:i1] = out[k]
-            return rec
-        if self.source in ('left', 'right'):
-            one = left_raw if self.source == 'left' else right_raw
-            return self._for_chunks(one.shape[0], one.device, body_mono)
+        from . import iotool
+        cameras = _MODES[self.mode].cameras
+        one = right_raw if cameras == 'R' else left_raw
 
         def body(i0, i1, lane):
             st = self._stage.get(lane)
             if st is None:
-                st = self._stage[lane] = torch.empty((self.chunk, 2, self.h, self.w), dtype=torch.uint8, device=left_raw.device)
-            pairs = prestep(left_raw[i0:i1], right_raw[i0:i1], out=st[:i1 - i0])
-            rec, _, out = self.run_chunk(pairs[:, 0], pairs[:, 1], lane, i0)
+                shape = (self.chunk, 2, self.h, self.w) if cameras == 'LR' else (self.chunk, self.h, self.w)
+                st = self._stage[lane] = torch.empty(shape, dtype=torch.uint8, device=one.device)
+            st = st[:i1 - i0]
+            if cameras == 'LR':
+                prestep(left_raw[i0:i1], right_raw[i0:i1], out=st)
+                rec, _, out = self.run_chunk(st[:, 0], st[:, 1], lane, i0)
+            else:
+                prestep._check(one[i0:i1], self.source)
+                iotool._prestep(prestep.maps[int(cameras == 'R')], one[i0:i1], st, self.h * self.w)
+                rec, _, out = self.run_chunk(st, st, lane, i0)
             if fits is not None:
                 for k, t in fits.items():
                     t[i0:i1] = out[k]
             return rec
-        return self._for_chunks(left_raw.shape[0], left_raw.device, body)
-
-
-FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), m=((), torch.int32), cyl_raw=((2, 6), torch.float64), cyl=((2, 6), torch.float64),
-                   T=((4, 4), torch.float64), fvals=((2,), torch.float64), mean_err=((), torch.float64), status=((), torch.int32),
-                   offset=((2,), torch.int32), match_score=((4,), torch.int32), match_flags=((), torch.int32))
-
-
-PLANE_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2), torch.int32), m=((), torch.int32), P=((4,), torch.float64),
-                         T=((4, 4), torch.float64), grid=((3, 3), torch.float64), stats=((8,), torch.float64), n_inliers=((), torch.int32),
-                         inlier_mask=((fit.MAXP,), torch.uint8), plane_flags=((), torch.int32), mean_err=((), torch.float64),
-                         status=((), torch.int32))
-
-
-# what fit.fit_single_plane_batch adds with relabel= (per frame and image); FramePipeline(relabel=...).run_raw keeps them when the
-# fits dict holds tensors of these names
-RELABEL_OUTPUTS = dict(relabel_counts=((2, 2, 4), torch.int32), relabel_flags=((2,), torch.int32))
-
-
-MONO_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2), torch.int32), m=((), torch.int32),
-                        cyl_raw=((2, 6), torch.float64), cyl=((2, 6), torch.float64), T=((4, 4), torch.float64), fvals=((2,), torch.float64),
-                        mean_err=((), torch.float64), status=((), torch.int32), counts=((4,), torch.int32),
-                        res=((fit.MAXP, 2), torch.float64), src=((fit.MAXP, 2), torch.int32), stats=((2,), torch.float64))
-
-
-FUSED_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2), torch.int32), m=((), torch.int32),
-                         cyl_raw=((2, 6), torch.float64), cyl=((2, 6), torch.float64), T=((4, 4), torch.float64), fvals=((2,), torch.float64),
-                         mean_err=((), torch.float64), status=((), torch.int32), counts=((6,), torch.int32),
-                         res=((fit.MAXP, 4), torch.float64), src=((fit.MAXP, 3), torch.int32), stats=((4,), torch.float64),
-                         flags=((), torch.int32))
-
-
-# what fit.fit_single_cylinder_refined_batch returns per frame (FramePipeline(source='fused', refine=...))
-REFINED_FIT_OUTPUTS = dict(pts3=((fit.MAXP, 3), torch.float64), idx=((fit.MAXP, 2), torch.int32), m=((), torch.int32),
-                           cyl_raw=((2, 6), torch.float64), cyl=((2, 6), torch.float64), T=((4, 4), torch.float64), fvals=((2,), torch.float64),
-                           mean_err=((), torch.float64), status=((), torch.int32), round_taken=((), torch.int32),
-                           renumbered=((2,), torch.int32))
+        return self._for_chunks(one.shape[0], one.device, body)
 
 
 def alloc_fits(F, device, target='cylinder', source='stereo', refine=False):
     """zeroed [F, ...] tensors for the per-frame outputs of fit.fit_single_cylinder_batch (target='plane': of
     fit.fit_single_plane_batch; source 'left' / 'right': of fit.fit_single_cylinder_mono_batch; source 'fused': of
     fit.fit_single_cylinder_fused_batch, with refine of fit.fit_single_cylinder_refined_batch) that FramePipeline.run_raw can keep"""
-    if source == 'fused':
-        outputs = REFINED_FIT_OUTPUTS if refine else FUSED_FIT_OUTPUTS
-    else:
-        outputs = dict(cylinder=FIT_OUTPUTS, plane=PLANE_FIT_OUTPUTS)[target] if source == 'stereo' else MONO_FIT_OUTPUTS
+    outputs = _MODES[_mode_name(target, source, 'full', refine)].outputs
     return {k: torch.zeros((F,) + shape, dtype=dt, device=device) for k, (shape, dt) in outputs.items()}
