@@ -13,7 +13,8 @@
 //            + bounding box of the set, all in one read of the label plane
 // When rows start on 16-byte boundaries, the init of a pass that leaves the labels outside the set untouched, the merge and the
 // component list have word-level forms (k_ccl_init64 / k_ccl_merge64 / k_ccl_roots64): 64 pixels per thread and row as one bit
-// mask, the label plane is touched only where a run starts or two runs start to overlap.
+// mask, the label plane is touched only where a run starts or two runs start to overlap.  A thread's 64 x 8 tile is in its
+// registers, so k_ccl_init64 labels the components of the tile itself and k_ccl_merge64 unites only across tile edges.
 // Entry points (cpe_dev.h): ccl_components (component list), ccl_unions (links only), ccl_dark_first and the general pass
 // ccl_label; each chooses its kernels.  A pass works inside a window of the frame (Window, cpe_dev.h).  WIN_SWEEP
 // (FrameState::crect) serves the blob detector:
@@ -237,11 +238,75 @@ struct NotBitSrc {
     __device__ __forceinline__ unsigned colbits(int y8, int ya, int yb, int x) const { return ~b.colbits(y8, ya, yb, x) & 0xffu; }
 };
 
-// labels of a sparse pass: every pixel of the set points at the first pixel of its run inside the word; a run that
-// continues from the word to the left points at that word's last pixel instead (a chain of at most one link per word,
-// parents always smaller: the same forest the row-wise k_ccl_init builds, a few links deeper)
+// ---- a tile's own components.  The thread of a word-level walk holds its 64 x 8 tile as eight row masks, so the components of
+// the set inside the tile (inside the window) need no memory: k_ccl_init64 works them out with shifts and ANDs and stores
+// them as first labels, and k_ccl_merge64 only unites across the tile's edges.  Both kernels decide from the same masks
+// whether a tile is handled that way (tile_is_local), so nothing has to pass from one to the other.
+
+// every run of bg that holds a bit of f (f inside bg), whole: adding the seeds ripples a carry to the end of their runs (fill
+// towards the high bits), the same on the bit-reversed word fills towards the low bits (as flood_row below does)
+__device__ __forceinline__ unsigned long long fill_runs(unsigned long long bg, unsigned long long f)
+{
+    f = (((bg + f) ^ bg) & bg) | f;
+    const unsigned long long rb = __brevll(bg), rf = __brevll(f);
+    return __brevll((((rb + rf) ^ rb) & rb) | rf);
+}
+// one step of a component's growth: the runs of row `bg` that touch `from`, the component's pixels in the row above or below,
+// join its pixels `c` of that row (4-connected: the same column; 8-connected: the columns next to it as well)
+__device__ __forceinline__ bool tile_spread(unsigned long long from, unsigned long long bg, unsigned long long &c, int conn8)
+{
+    unsigned long long s = conn8 ? (from | (from << 1) | (from >> 1)) : from;
+    s &= bg & ~c;
+    if (!s) return false;
+    c |= fill_runs(bg, s);
+    return true;
+}
+// The in-tile work is bounded by the number of runs of the tile (its rows inside the window): a tile has at most as many
+// components as runs, and one with more than CCL_TILE_RUNS of them -- a checkerboard, dense noise -- keeps the per-run first
+// labels and the in-tile unions of the merge.  Either way the merge ends with the same components.
+constexpr int CCL_TILE_RUNS = 24;
+__device__ __forceinline__ bool tile_is_local(const unsigned long long (&rows)[CCL_STRIP])
+{
+    int runs = 0;
+#pragma unroll
+    for (int k = 0; k < CCL_STRIP; k++) runs += __popcll(rows[k] & ~(rows[k] << 1));
+    return runs <= CCL_TILE_RUNS;
+}
+// bit k: row y8 + k lies in ya .. yb
+__device__ __forceinline__ unsigned row_mask8(int y8, int ya, int yb)
+{
+    return ya > yb ? 0u : (((2u << (yb - y8)) - 1u) & ~((1u << (ya - y8)) - 1u));
+}
+__device__ __forceinline__ void store_labels(int *Lrow, int a, int e, int label)   // Lrow[a .. e - 1] = label; Lrow 16-byte aligned
+{
+    int b = a;
+    while (b < e) {
+        if ((b & 3) == 0 && b + 4 <= e) { *reinterpret_cast<int4 *>(Lrow + b) = make_int4(label, label, label, label); b += 4; }
+        else { Lrow[b] = label; b++; }
+    }
+}
+__device__ __forceinline__ void store_row_labels(int *Lrow, unsigned long long m, int label)   // Lrow[b] = label for the bits b of m
+{
+    while (m) {
+        const unsigned long long low = m & (0ull - m), run = m & ~(m + low);
+        const int a = __ffsll((long long)low) - 1;
+        store_labels(Lrow, a, a + __popcll(run), label);
+        m &= ~run;
+    }
+}
+
+// First labels of a sparse pass.  A tile that tile_is_local: every pixel of a component of the tile (conn8: 8-connected, else
+// 4-connected; inside the window) points at the component's first pixel in raster order, its seed.  If the seed is the
+// word's first pixel and the set goes on in the word to the left, the whole component points at that word's last pixel of
+// the row instead (base - 1: smaller than every index of the component, so parents stay smaller, and no atomic is needed
+// because nothing else writes these labels before the merge); every other contact with a neighbouring tile is left to the
+// merge.  The components are found one at a time: the lowest pixel not yet labelled is the seed, its run the start, and
+// downward and upward sweeps over the eight rows add the runs that touch the component until a round adds nothing.
+// Other tiles: every pixel points at the first pixel of its run inside the word, a run that continues from the word to the
+// left at that word's last pixel (a chain of at most one link per word: the forest the row-wise k_ccl_init builds, a few
+// links deeper).
 template <class SRC>
-__global__ __launch_bounds__(256) void k_ccl_init64(SRC src0, int h, int w,
+__global__ __launch_bounds__(256) void k_ccl_init64(SRC src0, int h, int w, int conn8,
                                                     const FrameState *__restrict__ st, Window win, int *__restrict__ L)
 {
     const int WW = (w + 63) >> 6, strips = (h + CCL_STRIP - 1) / CCL_STRIP;
@@ -262,33 +327,91 @@ __global__ __launch_bounds__(256) void k_ccl_init64(SRC src0, int h, int w,
     unsigned long long rows[CCL_STRIP], any = 0;
     src.strip(y8, ya, yb, x0, rows);
 #pragma unroll
-    for (int k = 0; k < CCL_STRIP; k++) any |= (y8 + k >= ya && y8 + k <= yb) ? rows[k] & cmask : 0ull;
+    for (int k = 0; k < CCL_STRIP; k++) { rows[k] = (y8 + k >= ya && y8 + k <= yb) ? rows[k] & cmask : 0ull; any |= rows[k]; }
+    if (!any) return;
     // the left neighbours only matter for a run that starts in column 0 of the word
     const unsigned lb = (hasL && (any & 1ull)) ? src.colbits(y8, ya, yb, x0 - 1) : 0u;
+    if (!tile_is_local(rows)) {
 #pragma unroll
-    for (int k = 0; k < CCL_STRIP; k++) {
-        const int y = y8 + k;
-        if (y < ya || y > yb) continue;
-        unsigned long long m = rows[k] & cmask;
-        if (!m) continue;
-        const int base = y * w + x0;
-        const bool cL = (m & 1ull) && ((lb >> k) & 1u);
-        while (m) {
-            const unsigned long long low = m & (0ull - m), run = m & ~(m + low);
-            const int a = __ffsll((long long)low) - 1, e = a + __popcll(run);
-            const int label = (a == 0 && cL) ? base - 1 : base + a;
-            int b = a;
-            while (b < e) {
-                if ((b & 3) == 0 && b + 4 <= e) { *reinterpret_cast<int4 *>(Lf + base + b) = make_int4(label, label, label, label); b += 4; }
-                else { Lf[base + b] = label; b++; }
+        for (int k = 0; k < CCL_STRIP; k++) {
+            unsigned long long m = rows[k];
+            const int base = (y8 + k) * w + x0;
+            const bool cL = (m & 1ull) && ((lb >> k) & 1u);
+            while (m) {
+                const unsigned long long low = m & (0ull - m), run = m & ~(m + low);
+                const int a = __ffsll((long long)low) - 1;
+                store_labels(Lf + base, a, a + __popcll(run), (a == 0 && cL) ? base - 1 : base + a);
+                m &= ~run;
             }
-            m &= ~run;
         }
+        return;
+    }
+    for (;;) {     // one component per turn; rows[] keeps the pixels not yet labelled
+        unsigned long long comp[CCL_STRIP];
+        int label = -1;
+#pragma unroll
+        for (int k = 0; k < CCL_STRIP; k++) {
+            comp[k] = 0ull;
+            if (label < 0 && rows[k]) {
+                const unsigned long long m = rows[k], low = m & (0ull - m);
+                const int base = (y8 + k) * w + x0;
+                comp[k] = m & ~(m + low);
+                label = ((low & 1ull) && ((lb >> k) & 1u)) ? base - 1 : base + __ffsll((long long)low) - 1;
+            }
+        }
+        if (label < 0) break;
+        // Sweeps alternate until one adds nothing: the component is then closed in that direction, and still closed in the
+        // other one, because nothing changed since the sweep before.  Nothing unlabelled lies above the seed, so a first
+        // downward sweep that adds nothing ends it as well.
+        for (bool down = true;; down = !down) {
+            bool grew = false;
+            if (down) {
+#pragma unroll
+                for (int k = 1; k < CCL_STRIP; k++) grew |= tile_spread(comp[k - 1], rows[k], comp[k], conn8);
+            } else {
+#pragma unroll
+                for (int k = CCL_STRIP - 2; k >= 0; k--) grew |= tile_spread(comp[k + 1], rows[k], comp[k], conn8);
+            }
+            if (!grew) break;
+        }
+#pragma unroll
+        for (int k = 0; k < CCL_STRIP; k++) rows[k] &= ~comp[k];
+        // (written out: the compiler does not unroll a loop of these inside the component loop, and comp[] must stay in registers)
+        static_assert(CCL_STRIP == 8, "k_ccl_init64 stores the eight rows of a component one by one");
+        int *Lt = Lf + y8 * w + x0;
+        store_row_labels(Lt, comp[0], label);         store_row_labels(Lt + w, comp[1], label);
+        store_row_labels(Lt + 2 * w, comp[2], label); store_row_labels(Lt + 3 * w, comp[3], label);
+        store_row_labels(Lt + 4 * w, comp[4], label); store_row_labels(Lt + 5 * w, comp[5], label);
+        store_row_labels(Lt + 6 * w, comp[6], label); store_row_labels(Lt + 7 * w, comp[7], label);
     }
 }
 
-// same unions as k_ccl_merge
-template <class SRC>
+// The unions of a word-level pass, in terms of pixel pairs (the same pairs as k_ccl_merge).  A pixel p of the set is united
+//   (v) with the pixel above it, unless the pair one column to the left is a member pair too: p and its left neighbour are
+//       one run, so are the two pixels above them, and that pair is united by its own (v);
+//   (r) conn8, nothing above p: with the pixel up-right, unless p's right neighbour is in the set -- that one has the
+//       up-right pixel above it, (v), and is in p's run;
+//   (l) conn8, nothing above p: with the pixel up-left, unless p's left neighbour is in the set (likewise).
+// Two pixels next to each other in a row are one run and were linked by the first labels -- inside a word always, across a
+// word's left edge when the first labels are the row-wise ones (k_ccl_init) or the per-run ones of k_ccl_init64.
+// TILES false (first labels from k_ccl_init): all of (v), (r), (l) for every row of the tile.
+// TILES true (first labels from k_ccl_init64), a tile that tile_is_local: its rows are already united among themselves by
+// the first labels, which leaves
+//   - the tile's first row against the row above it: (v), (r), (l) as they stand;
+//   - rows 1 .. 7: (r) at the word's last pixel and (l) at its first one, the only pairs that cross the tile's edge there.
+//     The skips hold as above: where they point at a pixel above p or beside the pixel up-right / up-left, that pixel is in
+//     p's or the neighbour's tile together with the one it is joined to, and joined to it by that tile's first labels (or,
+//     in a tile that is not local, by that tile's own (v));
+//   - (h) the first pixel of a row with its left neighbour, the last pixel of the word to the left, unless the row above, in
+//       the same tile, has the same contact: the two pixels of this word lie above each other in one tile and so do the two
+//       of the left word, so both pairs are joined already, and the row above makes its own (h).  The tile's first row always
+//       makes its (h): its (v) at the first pixel counts on it.  A (h) that the first labels made (the label of the row's
+//       first pixel is its left neighbour) is seen with one load and skipped.
+//   What a skipped union counts on is always a union or a first label of a pair further up or further left, never the other
+//   way round, so no two skips count on each other.
+// TILES true, any other tile: as TILES false; its first labels are the per-run ones.
+// A vertical line costs one union per tile it crosses instead of one per row, a solid region one (v) and one (h) per tile.
+template <class SRC, bool TILES>
 __global__ __launch_bounds__(256) void k_ccl_merge64(SRC src0, int h, int w,
                                                      int conn8, const FrameState *__restrict__ st, Window win,
                                                      int *__restrict__ L)
@@ -301,45 +424,49 @@ __global__ __launch_bounds__(256) void k_ccl_merge64(SRC src0, int h, int w,
     const Rect r = window_rect(st, f, win, h, w);
     const int x0 = j * 64;
     if (r.x1 < r.x0 || x0 > r.x1 || x0 + 63 < r.x0) return;
-    const int ya = max(sy * CCL_STRIP, r.y0 + 1), yb = min(sy * CCL_STRIP + CCL_STRIP - 1, r.y1);
+    const int y8 = sy * CCL_STRIP;
+    const int ya = max(y8, r.y0), yb = min(y8 + CCL_STRIP - 1, r.y1);
     if (ya > yb) return;
     const size_t N = (size_t)h * w;
     const SRC src = src0.frame(f, h);
     int *Lf = L + f * N;
     const unsigned long long cmask = col_mask64(x0, r.x0, r.x1);
     const bool hasL = x0 - 1 >= r.x0, hasR = x0 + 64 <= r.x1;
-    // rows ya - 1 .. yb: the strip's tile, and the row above it when ya is the strip's first row
-    const int y8 = sy * CCL_STRIP;
+    // the tile's rows inside the window, the others as zero
     unsigned long long rows[CCL_STRIP], any = 0;
-    src.strip(y8, ya - 1, yb, x0, rows);
+    src.strip(y8, ya, yb, x0, rows);
 #pragma unroll
-    for (int k = 0; k < CCL_STRIP; k++) any |= (y8 + k >= ya - 1 && y8 + k <= yb) ? rows[k] & cmask : 0ull;
+    for (int k = 0; k < CCL_STRIP; k++) { rows[k] = (y8 + k >= ya && y8 + k <= yb) ? rows[k] & cmask : 0ull; any |= rows[k]; }
+    if (!any) return;
     // the neighbour columns only enter at bit 0 (left) / bit 63 (right) of a row of the strip
-    const unsigned lb = (hasL && (any & 1ull)) ? src.colbits(y8, ya - 1, yb, x0 - 1) : 0u;
-    const unsigned rb = (hasR && (any >> 63)) ? src.colbits(y8, ya - 1, yb, x0 + 64) : 0u;
+    const unsigned rm = row_mask8(y8, ya, yb);
+    const unsigned lb = (hasL && (any & 1ull)) ? src.colbits(y8, ya, yb, x0 - 1) & rm : 0u;
+    const unsigned rb = (hasR && (any >> 63)) ? src.colbits(y8, ya, yb, x0 + 64) & rm : 0u;
+    // the row above the tile, when the window has it, for the pixels that can ask for it
     unsigned long long A = 0, aL = 0, aR = 0;
-    if (ya == y8) {
-        A = src.pack(ya - 1, x0) & cmask;
-        aL = (hasL && src.px(ya - 1, x0 - 1)) ? 1ull : 0ull; aR = (hasR && src.px(ya - 1, x0 + 64)) ? 1ull : 0ull;
+    if (y8 - 1 >= r.y0 && rows[0]) {
+        A = src.pack(y8 - 1, x0) & cmask;
+        aL = (hasL && (rows[0] & 1ull) && src.px(y8 - 1, x0 - 1)) ? 1ull : 0ull;
+        aR = (hasR && (rows[0] >> 63) && src.px(y8 - 1, x0 + 64)) ? 1ull : 0ull;
     }
+    const bool local = TILES && tile_is_local(rows);
 #pragma unroll
     for (int k = 0; k < CCL_STRIP; k++) {
-        const int y = y8 + k;
-        if (y < ya - 1 || y > yb) continue;
-        const unsigned long long C = rows[k] & cmask;
+        const unsigned long long C = rows[k];
         const unsigned long long cL = (lb >> k) & 1u, cR = (rb >> k) & 1u;
-        if (y == ya - 1) { A = C; aL = cL; aR = cR; continue; }
         if (C) {
+            const bool edges = local && k > 0;     // only the pairs across the tile's left / right edge are left
             const unsigned long long Cs = (C << 1) | cL, As = (A << 1) | aL;            // left, up-left
-            const int base = y * w + x0;
-            unsigned long long m = C & A & ~(Cs & As);
+            const int base = (y8 + k) * w + x0;
+            unsigned long long m = edges ? 0ull : C & A & ~(Cs & As);
             while (m) { const int b = __ffsll((long long)m) - 1; m &= m - 1; uf_unite(Lf, base + b, base + b - w); }
+            if (local && (C & 1ull) && cL && !(k > 0 && (A & 1ull) && aL) && uf_load(Lf, base) != base - 1) uf_unite(Lf, base, base - 1);
             if (conn8) {
                 const unsigned long long Cr = (C >> 1) | (cR << 63), Ar = (A >> 1) | (aR << 63);   // right, up-right
                 const unsigned long long nu = C & ~A;
-                m = nu & Ar & ~Cr;
+                m = nu & Ar & ~Cr & (edges ? 1ull << 63 : ~0ull);
                 while (m) { const int b = __ffsll((long long)m) - 1; m &= m - 1; uf_unite(Lf, base + b, base + b - w + 1); }
-                m = nu & As & ~Cs;
+                m = nu & As & ~Cs & (edges ? 1ull : ~0ull);
                 while (m) { const int b = __ffsll((long long)m) - 1; m &= m - 1; uf_unite(Lf, base + b, base + b - w - 1); }
             }
         }
@@ -1018,19 +1145,20 @@ int outside_flood(const uint8_t *mask, int n, int h, int w, FrameState *st, Wind
 static bool word_rows(const void *img, const int *L, int w) { return w % 16 == 0 && ((size_t)img & 15) == 0 && ((size_t)L & 15) == 0; }
 static dim3 word_grid(int n, int h, int w) { return dim3((unsigned)((((w + 63) / 64) * ((h + CCL_STRIP - 1) / CCL_STRIP) + 255) / 256), n); }
 
-// the links of the 8-connected set img > thr (labels outside it untouched); true: the word-level kernels made them
-static bool links8(const uint8_t *img, int n, int h, int w, int thr, Window win, int *L, FrameState *st, hipStream_t s)
+// the links of the set img > thr, 8-connected if conn8, else 4-connected (labels outside it untouched); true: the word-level
+// kernels made them
+static bool links(const uint8_t *img, int n, int h, int w, int thr, int conn8, Window win, int *L, FrameState *st, hipStream_t s)
 {
     const size_t N = (size_t)h * w;
     if (word_rows(img, L, w)) {
         const ByteSrc src{img, w, thr, 0};
-        CPE_KLAUNCH(k_ccl_init64<ByteSrc>, word_grid(n, h, w), dim3(256), 0, s, src, h, w, (const FrameState *)st, win, L);
-        CPE_KLAUNCH(k_ccl_merge64<ByteSrc>, word_grid(n, h, w), dim3(256), 0, s, src, h, w, 1, (const FrameState *)st, win, L);
+        CPE_KLAUNCH(k_ccl_init64<ByteSrc>, word_grid(n, h, w), dim3(256), 0, s, src, h, w, conn8, (const FrameState *)st, win, L);
+        CPE_KLAUNCH((k_ccl_merge64<ByteSrc, true>), word_grid(n, h, w), dim3(256), 0, s, src, h, w, conn8, (const FrameState *)st, win, L);
         return true;
     }
     CPE_KLAUNCH(k_ccl_init, dim3((n * h + CCL_INIT_ROWS - 1) / CCL_INIT_ROWS), dim3(256), 0, s, img, n * h, h, w, thr, 0, (const FrameState *)st, win, L,
                 (int *)nullptr, OUTSIDE_UNTOUCHED);
-    CPE_KLAUNCH(k_ccl_merge, dim3((unsigned)((N + CCL_BLK_PX - 1) / CCL_BLK_PX), n), dim3(256), 0, s, img, h, w, thr, 0, 1, (const FrameState *)st, win, L);
+    CPE_KLAUNCH(k_ccl_merge, dim3((unsigned)((N + CCL_BLK_PX - 1) / CCL_BLK_PX), n), dim3(256), 0, s, img, h, w, thr, 0, conn8, (const FrameState *)st, win, L);
     return false;
 }
 
@@ -1039,16 +1167,22 @@ bool ccl_components_reads_bits(const uint32_t *bits, int w, const int *L) { retu
 int ccl_components(const uint8_t *img, const uint32_t *bits, int n, int h, int w, int thr, Window win, int *L, int *roots,
                    RootList list, FrameState *st, hipStream_t s)
 {
+    return ccl_components_conn(img, bits, n, h, w, thr, 1, win, L, roots, list, st, s);
+}
+
+int ccl_components_conn(const uint8_t *img, const uint32_t *bits, int n, int h, int w, int thr, int conn8, Window win, int *L,
+                        int *roots, RootList list, FrameState *st, hipStream_t s)
+{
     const size_t N = (size_t)h * w;
     const dim3 gw = word_grid(n, h, w);
     CPE_LAUNCH_BEGIN();
     CPE_KLAUNCH(k_ccl_ctl, dim3((n + 63) / 64), dim3(64), 0, s, st, (int *)nullptr, n, CTL_RESET_ROOTS, list);
     if (ccl_components_reads_bits(bits, w, L)) {
         const BitSrc src{bit_plane(bits, 0, h, w), bit_tile_cols(w), bit_plane_words(h, w)};
-        CPE_KLAUNCH(k_ccl_init64<BitSrc>, gw, dim3(256), 0, s, src, h, w, (const FrameState *)st, win, L);
-        CPE_KLAUNCH(k_ccl_merge64<BitSrc>, gw, dim3(256), 0, s, src, h, w, 1, (const FrameState *)st, win, L);
+        CPE_KLAUNCH(k_ccl_init64<BitSrc>, gw, dim3(256), 0, s, src, h, w, conn8, (const FrameState *)st, win, L);
+        CPE_KLAUNCH((k_ccl_merge64<BitSrc, true>), gw, dim3(256), 0, s, src, h, w, conn8, (const FrameState *)st, win, L);
         CPE_KLAUNCH(k_ccl_roots64<BitSrc>, gw, dim3(256), 0, s, src, h, w, st, win, (const int *)L, roots, list);
-    } else if (links8(img, n, h, w, thr, win, L, st, s)) {
+    } else if (links(img, n, h, w, thr, conn8, win, L, st, s)) {
         CPE_KLAUNCH(k_ccl_roots64<ByteSrc>, gw, dim3(256), 0, s, (ByteSrc{img, w, thr, 0}), h, w, st, win, (const int *)L, roots, list);
     } else {
         CPE_KLAUNCH(k_ccl_roots4, dim3((unsigned)((N + CCL_BLK_PX - 1) / CCL_BLK_PX), n), dim3(256), 0, s, img, h, w, thr, 0, st, win, (const int *)L,
@@ -1061,7 +1195,7 @@ int ccl_components(const uint8_t *img, const uint32_t *bits, int n, int h, int w
 int ccl_unions(const uint8_t *mask, int n, int h, int w, Window win, int *L, FrameState *st, hipStream_t s)
 {
     CPE_LAUNCH_BEGIN();
-    links8(mask, n, h, w, 0, win, L, st, s);
+    links(mask, n, h, w, 0, 1, win, L, st, s);
     CPE_CHECK_LAUNCH("ccl_unions");
     return CPE_OK;
 }
@@ -1074,7 +1208,7 @@ int ccl_label(const uint8_t *img, int n, int h, int w, int *L, const CclPass &p,
     CPE_KLAUNCH(k_ccl_init, dim3((n * h + CCL_INIT_ROWS - 1) / CCL_INIT_ROWS), dim3(256), 0, s, img, n * h, h, w, p.thr, p.invert, (const FrameState *)st, p.win, L,
                 p.count ? p.cnt : (int *)nullptr, p.outside);
     if (word_rows(img, L, w))
-        CPE_KLAUNCH(k_ccl_merge64<ByteSrc>, word_grid(n, h, w), dim3(256), 0, s, (ByteSrc{img, w, p.thr, p.invert}), h, w, p.conn8, (const FrameState *)st, p.win, L);
+        CPE_KLAUNCH((k_ccl_merge64<ByteSrc, false>), word_grid(n, h, w), dim3(256), 0, s, (ByteSrc{img, w, p.thr, p.invert}), h, w, p.conn8, (const FrameState *)st, p.win, L);
     else
         CPE_KLAUNCH(k_ccl_merge, dim3((unsigned)((N + CCL_BLK_PX - 1) / CCL_BLK_PX), n), dim3(256), 0, s, img, h, w, p.thr, p.invert, p.conn8,
                     (const FrameState *)st, p.win, L);
@@ -1106,7 +1240,7 @@ int ccl_dark_first(const uint8_t *img, const uint32_t *planes, int nplanes, int 
                 cnt, OUTSIDE_SWEEP_RUNS);
     const dim3 gw = word_grid(n, h, w);
     const NotBitSrc src{BitSrc{bit_plane(planes, 0, h, w), bit_tile_cols(w), bit_plane_words(h, w)}, (size_t)nplanes * bit_plane_words(h, w)};
-    CPE_KLAUNCH(k_ccl_merge64<NotBitSrc>, gw, dim3(256), 0, s, src, h, w, 0, (const FrameState *)st, WIN_SWEEP, L);
+    CPE_KLAUNCH((k_ccl_merge64<NotBitSrc, false>), gw, dim3(256), 0, s, src, h, w, 0, (const FrameState *)st, WIN_SWEEP, L);
     CPE_KLAUNCH(k_ccl_finish64<NotBitSrc>, gw, dim3(256), 0, s, src, h, w, st, WIN_SWEEP, L, cnt, roots, ROOTS_MAIN);
     CPE_CHECK_LAUNCH("ccl_dark_first");
     return CPE_OK;

@@ -433,6 +433,10 @@ int build_bitplanes(const uint8_t *img, int n, int h, int w, int thr0, int step,
 // left as union-find links (a root is a pixel whose label is its own index); labels outside the set are not written.
 int ccl_components(const uint8_t *img, const uint32_t *bits, int n, int h, int w, int thr, Window win, int *L, int *roots,
                    RootList list, FrameState *st, hipStream_t s);
+// the same with the connectivity as an argument (conn8 0: 4-connected components).  The detector lists 8-connected sets only;
+// cpe_debug_ccl_tiles takes the word-level passes through both connectivities.
+int ccl_components_conn(const uint8_t *img, const uint32_t *bits, int n, int h, int w, int thr, int conn8, Window win, int *L,
+                        int *roots, RootList list, FrameState *st, hipStream_t s);
 // true: a ccl_components call with these arguments reads the set from `bits` alone and never touches img (a caller that has
 // the plane need not produce the bytes)
 bool ccl_components_reads_bits(const uint32_t *bits, int w, const int *L);

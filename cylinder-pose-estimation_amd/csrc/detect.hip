@@ -545,6 +545,40 @@ extern "C" int32_t cpe_debug_dark_labels(const uint8_t *img, int32_t n, int32_t 
     return CPE_OK;
 }
 
+// The component list of the set img > thr (tests): ccl_components with the connectivity, the window and the source of the
+// set as arguments, so that the word-level passes (k_ccl_init64 / k_ccl_merge64 / k_ccl_roots64) can be driven through
+// everything they are written for.  rect (may be null: the whole frame) i32[n,4] x0, y0, x1, y1; bits != 0: the set is read
+// from its one-bit plane, built here.  lab i32[n,h,w]: the label plane as the passes leave it (union-find links; -1 where
+// they wrote nothing), roots i32[n,CPE_MAXROOTS_DEBUG], n_roots i32[n].
+extern "C" int32_t cpe_debug_ccl_tiles(const uint8_t *img, int32_t n, int32_t h, int32_t w, int32_t thr, int32_t conn8,
+                                       int32_t bits, const int32_t *rect, void *ws, size_t ws_bytes, int32_t *lab, int32_t *roots,
+                                       int32_t *n_roots, void *stream)
+{
+    CPE_CHECK_ARG(img && ws && lab && roots && n_roots && n > 0 && h >= 1 && w >= 16 && thr >= 0 && thr <= 255,
+                  "cpe_debug_ccl_tiles: bad argument");
+    Workspace W;
+    if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_ccl_tiles")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    FrameState *st = W.state();
+    int *lb = W.at<int>(WS_LABELS), *rb = W.at<int>(WS_ROOTS);
+    uint32_t *planes = W.at<uint32_t>(WS_BITS);
+    const size_t N = (size_t)h * w;
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_state_init, dim3((n + 63) / 64), dim3(64), 0, s, st, n, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (int *)nullptr);
+    if (rect) CPE_KLAUNCH(k_debug_rect, dim3((n + 63) / 64), dim3(64), 0, s, st, n, (const int *)rect);
+    (void)hipMemsetAsync(lb, 0xff, N * n * sizeof(int), s);
+    CPE_CHECK_LAUNCH("cpe_debug_ccl_tiles");
+    int rc;
+    if (bits && (rc = build_bitplanes(img, n, h, w, thr, 0, 1, planes, s)) != CPE_OK) return rc;
+    if ((rc = ccl_components_conn(img, bits ? planes : nullptr, n, h, w, thr, conn8 ? 1 : 0, rect ? WIN_SWEEP : WIN_FRAME, lb, rb, ROOTS_MAIN,
+                                  st, s)) != CPE_OK) return rc;
+    (void)hipMemcpyAsync(lab, lb, N * n * sizeof(int), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(roots, rb, (size_t)n * MAXROOTS * sizeof(int), hipMemcpyDeviceToDevice, s);
+    CPE_KLAUNCH(k_debug_n_roots, dim3((n + 63) / 64), dim3(64), 0, s, (const FrameState *)st, n, n_roots);
+    CPE_CHECK_LAUNCH("cpe_debug_ccl_tiles");
+    return CPE_OK;
+}
+
 // The region stage of the cylinder target on a given sweep image (tests): region_stage as the product runs it, serially, with
 // an identity CLAHE table in place of LAB-L + CLAHE, and its blob records and key points copied out (RegionProbe).
 extern "C" int32_t cpe_debug_blob_region(const uint8_t *img, int32_t n, int32_t h, int32_t w, void *ws, size_t ws_bytes,

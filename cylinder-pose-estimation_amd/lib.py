@@ -49,6 +49,7 @@ _SIGS = {
                                                   C.c_void_p, C.c_void_p]),
     'cpe_debug_ccl': (C.c_int32, [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     'cpe_debug_dark_labels': (C.c_int32, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
+    'cpe_debug_ccl_tiles': (C.c_int32, [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4),
     'cpe_debug_blob_region': (C.c_int32, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p,
                                                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'cpe_debug_clahe_planes': (C.c_int32, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),

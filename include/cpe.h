@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 124  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 125  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -57,7 +57,8 @@ extern "C" {
                              118: cpe_table_triangulate_batch; 119: cpe_fit_projector_model, cpe_projector_model_table;
                              120: cpe_index_shift_batch; 121: cpe_multi_frame_consensus_batch,
                              cpe_multi_frame_consensus_workspace_bytes; 122: cpe_fused_triangulate_batch;
-                             123: cpe_grid_relabel_batch; 124: cpe_grid_predict_batch, cpe_grid_assign_batch) */
+                             123: cpe_grid_relabel_batch; 124: cpe_grid_predict_batch, cpe_grid_assign_batch;
+                             125: cpe_debug_ccl_tiles) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -335,6 +336,17 @@ CPE_API int32_t cpe_debug_ccl(const uint8_t *img, int32_t n, int32_t h, int32_t 
 CPE_API int32_t cpe_debug_dark_labels(const uint8_t *img, int32_t n, int32_t h, int32_t w, int32_t thr, const int32_t *rect,
                                       int32_t path, void *ws, size_t ws_bytes, int32_t *lab, int32_t *cnt, int32_t *roots,
                                       int32_t *n_roots, void *stream);
+
+/* The component list the detector's stages start from (csrc/ccl.hip, ccl_components) on img u8[n,h,w] (h >= 1, w >= 16): the
+ * components of img > thr, 8-connected if conn8, else 4-connected, inside rect i32[n,4] (x0, y0, x1, y1 inclusive, inside the
+ * frame, device memory; NULL: the whole frame).  bits != 0: the passes read the set from its one-bit plane, which is built
+ * first (w % 16 == 0; other widths read the bytes).  Outputs (device memory): lab i32[n,h,w], the label plane as the passes
+ * leave it -- every pixel of the set inside rect holds the index of a smaller pixel of its component or, the component's
+ * first pixel, its own; -1 everywhere else --, roots i32[n,CPE_MAXROOTS_DEBUG] (the first pixels, any order), n_roots i32[n].
+ * Test / debugging aid. */
+CPE_API int32_t cpe_debug_ccl_tiles(const uint8_t *img, int32_t n, int32_t h, int32_t w, int32_t thr, int32_t conn8,
+                                    int32_t bits, const int32_t *rect, void *ws, size_t ws_bytes, int32_t *lab, int32_t *roots,
+                                    int32_t *n_roots, void *stream);
 
 /* The RETR_EXTERNAL rule of cv2.findContours as the detector applies it (util_cylinder.py:161, 1817; the other two call
  * sites, :1883 and :1968, keep only the largest contour, which is never a nested one): of the 8-connected components of
