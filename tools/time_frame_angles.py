@@ -4,26 +4,19 @@ generator of tests/multiframe_cases.py, the pose the scenes were made with, the 
 
     python tools/time_frame_angles.py [--frames 45 4096] [--points 250] [--reps 21] [--procs 3] [--child-timeout 300] [--out FILE]
 
-Per size, alternated inside one process, the time between two device events around one call on preallocated outputs:
+Per size, timed by the protocol of tools/timing.py between device events, one call on preallocated outputs:
     solver   cpe_frame_angles_lm_batch (start, LM, chain and T * chain of the result)
     terms    cpe_multi_frame_terms on the same tables at the solver's result: one pass over the points, for scale -- the solver
              should cost about its objective evaluations + Jacobian passes (one per iteration) times that
 The line of a size also carries the statuses, the iteration and evaluation counts (mean and maximum over the frames) and
-passes = mean evaluations + mean iterations.  The parent process starts `--procs` fresh children one after the other and
-reports the median over the children's medians with the run-to-run spread (max - min of the children's medians).  A child that
-fails or outlives --child-timeout seconds ends the run: nothing more is started on the GPU after it.
-The scenes come from tests/multiframe_cases.py (the generator the GPU tests use), which this file imports by putting tests/
-on sys.path: it has to stay beside the tests."""
+passes = mean evaluations + mean iterations.
+The scenes come from tests/multiframe_cases.py (the generator the GPU tests use): this file has to stay beside the tests."""
 import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import timing
+
 RADIUS = 45.0
 SCENE_FRAMES = 45
 
@@ -63,20 +56,11 @@ def child(sizes, points, reps):
             f()
         torch.cuda.synchronize()
         assert all(torch.equal(out[k], first[k]) for k in out), 'the call on preallocated outputs differs from the wrapper\'s'
-        ms = {k: [] for k in variants}
-        for _ in range(reps):
-            for k, f in variants.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                e0.record()
-                f()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
+        ms = timing.event_loop(variants, reps)
         it = first['iters'].cpu().numpy().astype(np.float64)
         ok = first['status'].cpu().numpy() == 0
         err = np.abs(first['angles'].cpu().numpy() - truth)[ok]
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        med = timing.medians(ms)
         print(json.dumps(dict(kind='case', frames=n, points=points, reps=reps, median_ms=med, ratio=med['solver'] / med['terms'],
                               status_ok=int(ok.sum()), iters_mean=float(it[ok, 0].mean()), iters_max=int(it[ok, 0].max()),
                               evals_mean=float(it[ok, 1].mean()), evals_max=int(it[ok, 1].max()),
@@ -88,32 +72,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, nargs='+', default=[45, 4096])
     ap.add_argument('--points', type=int, default=250)
-    ap.add_argument('--reps', type=int, default=21)
-    ap.add_argument('--procs', type=int, default=3)
-    ap.add_argument('--child-timeout', type=float, default=300.0, help='seconds one child may take')
-    ap.add_argument('--out', default=None, help='also append every raw line to this file')
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
+    a = timing.parse(ap, reps=21, child_timeout=300.0)
     if a.child:
         return child(a.frames, a.points, a.reps)
-    lines = []
-
-    def emit(d):
-        lines.append(d)
-        print(json.dumps(d), flush=True)
-        if a.out:
-            with open(a.out, 'a') as f:
-                f.write(json.dumps(d) + '\n')
-    for p in range(a.procs):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--points', str(a.points), '--reps', str(a.reps), '--frames'] +
-                           [str(n) for n in a.frames], stdout=subprocess.PIPE, text=True, check=True, timeout=a.child_timeout)
-        for ln in r.stdout.splitlines():
-            if ln.startswith('{'):
-                emit(dict(json.loads(ln), process=p))
+    lines, emit = timing.run_children(__file__, a)
     for n in a.frames:
         rows = [d for d in lines if d['kind'] == 'case' and d['frames'] == n]
-        med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in ('solver', 'terms')}
-        spread = {k: max(d['median_ms'][k] for d in rows) - min(d['median_ms'][k] for d in rows) for k in ('solver', 'terms')}
+        med, spread = timing.reduce(rows)
         emit(dict(kind='summary', frames=n, points=a.points, procs=a.procs, solver_ms=med['solver'], terms_ms=med['terms'],
                   solver_spread_ms=spread['solver'], terms_spread_ms=spread['terms'], ratio=med['solver'] / med['terms'],
                   passes=rows[0]['passes'], iters_mean=rows[0]['iters_mean'], iters_max=rows[0]['iters_max'],

@@ -5,25 +5,18 @@ cameras, so every fused point is a pair; the rig's true table, -12..12).
 
     python tools/time_fused_tri.py [--frames 45 4096] [--points 250] [--reps 11] [--procs 3] [--child-timeout 400] [--out FILE]
 
-Per size, alternated inside one process, the time between two device events around one call:
+Per size, timed by the protocol of tools/timing.py between device events, one call:
     fused_tri    fit.fused_triangulate_batch(gp1, gp2, K1, K2, T21, table)
     select_tri   fit.select_triangulate_batch(gp1, gp2, K1, K2, T21)             chooseIdx + DLT
     table_tri    fit.table_triangulate_batch(gp1, K1, None, table)               one camera
     fused_fit    fit.fit_single_cylinder_fused_batch(gp1, gp2, K1, K2, T21, table, 45)   FIT_LM
-    stereo_fit   fit.fit_single_cylinder_batch(gp1, gp2, K1, K2, T21, 45)                FIT_LM
-The parent starts `--procs` fresh children one after the other, each under --child-timeout seconds, and reports the median over
-the children's medians with the run-to-run spread (max - min of the children's medians).  A child that fails or outlives its
-limit ends the run: nothing more is started on the GPU after it."""
+    stereo_fit   fit.fit_single_cylinder_batch(gp1, gp2, K1, K2, T21, 45)                FIT_LM"""
 import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import timing
+
 RADIUS = 45.0
 
 
@@ -31,17 +24,17 @@ def child(sizes, points, reps):
     import torch
     import cpe_amd  # noqa: F401
     from cpe_amd import fit
-    from time_table_tri import make_tables, time_variants
+    from time_table_tri import make_tables
     dev = torch.device('cuda:0')
     for n in sizes:
         g1, g2, K1, K2, T21, tab = make_tables(n, points, dev)
-        first, ms = time_variants(dict(
+        first, ms = timing.time_variants(dict(
             fused_tri=lambda: fit.fused_triangulate_batch(g1, g2, K1, K2, T21, tab),
             select_tri=lambda: fit.select_triangulate_batch(g1, g2, K1, K2, T21),
             table_tri=lambda: fit.table_triangulate_batch(g1, K1, None, tab),
             fused_fit=lambda: fit.fit_single_cylinder_fused_batch(g1, g2, K1, K2, T21, tab, RADIUS, mode=fit.FIT_LM),
             stereo_fit=lambda: fit.fit_single_cylinder_batch(g1, g2, K1, K2, T21, RADIUS, mode=fit.FIT_LM)), reps)
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        med = timing.medians(ms)
         mean = lambda t: float(t.double().mean())
         print(json.dumps(dict(kind='tables', frames=n, points=mean(g1.cnt), reps=reps, median_ms=med,
                               fused_over_select=med['fused_tri'] / med['select_tri'], fused_over_table=med['fused_tri'] / med['table_tri'],
@@ -58,39 +51,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, nargs='*', default=[45, 4096])
     ap.add_argument('--points', type=int, default=250)
-    ap.add_argument('--reps', type=int, default=11)
-    ap.add_argument('--procs', type=int, default=3)
-    ap.add_argument('--child-timeout', type=float, default=400.0, help='seconds one child may take')
-    ap.add_argument('--out', default=None, help='also append every raw line to this file')
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
+    a = timing.parse(ap, reps=11, child_timeout=400.0)
     if a.child:
         return child(a.frames, a.points, a.reps)
-    lines = []
-
-    def emit(d):
-        lines.append(d)
-        print(json.dumps(d), flush=True)
-        if a.out:
-            with open(a.out, 'a') as f:
-                f.write(json.dumps(d) + '\n')
-    for p in range(a.procs):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--points', str(a.points), '--reps', str(a.reps),
-                            '--frames'] + [str(n) for n in a.frames], stdout=subprocess.PIPE, text=True, check=True, timeout=a.child_timeout)
-        for ln in r.stdout.splitlines():
-            if ln.startswith('{'):
-                emit(dict(json.loads(ln), process=p))
+    lines, emit = timing.run_children(__file__, a)
     ratios = (('fused_over_select', 'fused_tri', 'select_tri'), ('fused_over_table', 'fused_tri', 'table_tri'),
               ('fused_fit_over_stereo_fit', 'fused_fit', 'stereo_fit'))
     for n in a.frames:
         rows = [d for d in lines if d['kind'] == 'tables' and d['frames'] == n]
-        keys = list(rows[0]['median_ms'])
-        med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in keys}
-        spread = {k: max(d['median_ms'][k] for d in rows) - min(d['median_ms'][k] for d in rows) for k in keys}
-        skip = ('kind', 'frames', 'reps', 'median_ms', 'ms', 'process') + tuple(r[0] for r in ratios)
-        extra = {k: v for k, v in rows[0].items() if k not in skip}
-        emit(dict(kind='tables_summary', frames=n, procs=a.procs, median_ms=med, spread_ms=spread,
-                  **{name: med[num] / med[den] for name, num, den in ratios}, **extra))
+        emit(timing.ratio_summary(dict(kind='tables_summary', frames=n, procs=a.procs), rows, ratios))
     return 0
 
 

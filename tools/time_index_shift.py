@@ -7,27 +7,20 @@ and the renumbered projector fit against the trimmed fit it extends.
 
 Tables: the analytic cylinders of tools/time_table_tri.py (17 x 25 grid, thinned to `--points` points, 0.25 px noise), their
 stereo points from fit.select_triangulate_batch(selector=SEL_JOIN) (every pair, so every point), every third frame numbered
-one column up or one row down; the table is the rig's true one, -16..16.  Per size, alternated inside one process, the time between two device events around one call:
+one column up or one row down; the table is the rig's true one, -16..16.  Per size, timed by the protocol of tools/timing.py
+between device events, one call:
     index_shift  fit.index_shift_batch(X, idx, m, table, win=(4, 4))
     table_tri    fit.table_triangulate_batch(gp1, K1, None, table)
 Fit: the `--fit-frames` analytic boards of tools/time_projector_model.py (425 points each), clean and with every ninth frame
 numbered one column up:
     model_trim           fit.fit_projector_model(X, idx, cnt, -12, 12, tau=1.0)
     renumbered           fit.fit_projector_model_renumbered(X, idx, cnt, -12, 12, tau=1.0)      fit, table, search, refit
-    model_trim_shifted, renumbered_shifted                                                      the same on the shifted tables
-The parent starts `--procs` fresh children one after the other and reports the median over the children's medians with the
-run-to-run spread (max - min of the children's medians).  A child that fails or outlives --child-timeout seconds ends the run:
-nothing more is started on the GPU after it."""
+    model_trim_shifted, renumbered_shifted                                                      the same on the shifted tables"""
 import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import timing
 
 
 def child(sizes, points, fit_frames, reps):
@@ -36,7 +29,6 @@ def child(sizes, points, fit_frames, reps):
     from cpe_amd import fit, synth
     import time_plane_fit
     import time_table_tri
-    from time_plane_fit import time_variants
     dev = torch.device('cuda:0')
     for n in sizes:
         g1, g2, K1, K2, T21, _ = time_table_tri.make_tables(n, points, dev)
@@ -47,9 +39,9 @@ def child(sizes, points, fit_frames, reps):
         move[0::6, 0] = 1
         move[3::6, 1] = -1
         idx = (sel['idx'] + move[:, None, :]).contiguous()
-        first, ms = time_variants(dict(index_shift=lambda: fit.index_shift_batch(X, idx, m, tab, win=(4, 4)),
-                                       table_tri=lambda: fit.table_triangulate_batch(g1, K1, None, tab)), reps)
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        first, ms = timing.time_variants(dict(index_shift=lambda: fit.index_shift_batch(X, idx, m, tab, win=(4, 4)),
+                                              table_tri=lambda: fit.table_triangulate_batch(g1, K1, None, tab)), reps)
+        med = timing.medians(ms)
         print(json.dumps(dict(kind='tables', frames=n, points=float(m.double().mean()), reps=reps, median_ms=med,
                               shift_over_tri=med['index_shift'] / med['table_tri'],
                               shifts_right=int((first['index_shift']['shift'] == -move).all(1).sum()),
@@ -61,12 +53,12 @@ def child(sizes, points, fit_frames, reps):
         move = torch.zeros((fit_frames, 2), dtype=torch.int32, device=dev)
         move[4::9, 0] = 1
         off = (idx + move[:, None, :]).contiguous()
-        first, ms = time_variants(dict(
+        first, ms = timing.time_variants(dict(
             model_trim=lambda: fit.fit_projector_model(X, idx, cnt, -12, 12, tau=1.0),
             renumbered=lambda: fit.fit_projector_model_renumbered(X, idx, cnt, -12, 12, tau=1.0),
             model_trim_shifted=lambda: fit.fit_projector_model(X, off, cnt, -12, 13, tau=1.0),
             renumbered_shifted=lambda: fit.fit_projector_model_renumbered(X, off, cnt, -12, 13, tau=1.0)), reps)
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        med = timing.medians(ms)
         rs = first['renumbered_shifted']
         print(json.dumps(dict(kind='fit', frames=fit_frames, points=425.0, reps=reps, median_ms=med,
                               renumbered_over_trim=med['renumbered'] / med['model_trim'],
@@ -81,42 +73,17 @@ def main():
     ap.add_argument('--frames', type=int, nargs='*', default=[45, 4096])
     ap.add_argument('--points', type=int, default=250)
     ap.add_argument('--fit-frames', type=int, default=45)
-    ap.add_argument('--reps', type=int, default=11)
-    ap.add_argument('--procs', type=int, default=3)
-    ap.add_argument('--child-timeout', type=float, default=400.0, help='seconds one child may take')
-    ap.add_argument('--out', default=None, help='also append every raw line to this file')
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
+    a = timing.parse(ap, reps=11, child_timeout=400.0)
     if a.child:
         return child(a.frames, a.points, a.fit_frames, a.reps)
-    lines = []
-
-    def emit(d):
-        lines.append(d)
-        print(json.dumps(d), flush=True)
-        if a.out:
-            with open(a.out, 'a') as f:
-                f.write(json.dumps(d) + '\n')
-    for p in range(a.procs):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--points', str(a.points), '--reps', str(a.reps),
-                            '--fit-frames', str(a.fit_frames), '--frames'] + [str(n) for n in a.frames],
-                           stdout=subprocess.PIPE, text=True, check=True, timeout=a.child_timeout)
-        for ln in r.stdout.splitlines():
-            if ln.startswith('{'):
-                emit(dict(json.loads(ln), process=p))
+    lines, emit = timing.run_children(__file__, a)
     ratios = dict(tables=(('shift_over_tri', 'index_shift', 'table_tri'),),
                   fit=(('renumbered_over_trim', 'renumbered', 'model_trim'),
                        ('renumbered_over_trim_shifted', 'renumbered_shifted', 'model_trim_shifted')))
     for kind, sizes in (('tables', a.frames), ('fit', [a.fit_frames] if a.fit_frames > 0 else [])):
         for n in sizes:
             rows = [d for d in lines if d['kind'] == kind and d['frames'] == n]
-            keys = list(rows[0]['median_ms'])
-            med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in keys}
-            spread = {k: max(d['median_ms'][k] for d in rows) - min(d['median_ms'][k] for d in rows) for k in keys}
-            skip = ('kind', 'frames', 'reps', 'median_ms', 'ms', 'process') + tuple(r[0] for r in ratios[kind])
-            extra = {k: v for k, v in rows[0].items() if k not in skip}
-            emit(dict(kind=kind + '_summary', frames=n, procs=a.procs, median_ms=med, spread_ms=spread,
-                      **{name: med[num] / med[den] for name, num, den in ratios[kind]}, **extra))
+            emit(timing.ratio_summary(dict(kind=kind + '_summary', frames=n, procs=a.procs), rows, ratios[kind]))
     return 0
 
 

@@ -5,24 +5,18 @@ points, with 0.25 px noise; every eighth frame has its left table numbered one c
 
     python tools/time_match_offset.py [--frames 45 4096] [--points 250] [--reps 11] [--procs 3] [--child-timeout 400] [--out FILE]
 
-Per size, alternated inside one process, the time between two device events around one call:
+Per size, timed by the protocol of tools/timing.py between device events, one call:
     off      fit.fit_single_cylinder_batch(...)                 chooseIdx + triangulate + Nelder-Mead fit, as the pipeline calls it
     on       fit.fit_single_cylinder_batch(..., match={})       the same behind the search
     search   fit.match_offset_batch(..., want_scores=False)     the search alone
 The number to read is cost = on - off relative to off: what the search adds to the call it sits in.  The line of a size also
-carries how many frames came out SHIFTED / WEAK / EDGE and whether every shifted frame got its (-1, 0).  The parent process
-starts `--procs` fresh children one after the other and reports the median over the children's medians with the run-to-run
-spread (max - min of the children's medians).  A child that fails or outlives --child-timeout seconds ends the run: nothing
-more is started on the GPU after it."""
+carries how many frames came out SHIFTED / WEAK / EDGE and whether every shifted frame got its (-1, 0)."""
 import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import timing
+
 RADIUS = 45.0
 SHIFT_EVERY = 8
 
@@ -56,22 +50,11 @@ def child(sizes, points, reps):
         variants = dict(off=lambda: fit.fit_single_cylinder_batch(g1, g2, K1, K2, T21, RADIUS),
                         on=lambda: fit.fit_single_cylinder_batch(g1, g2, K1, K2, T21, RADIUS, match={}),
                         search=lambda: fit.match_offset_batch(g1, g2, K1, K2, T21, RADIUS, want_scores=False))
-        first = {k: f() for k, f in variants.items()}                                   # warm-up, and the figures of the line
-        torch.cuda.synchronize()
-        ms = {k: [] for k in variants}
-        for _ in range(reps):
-            for k, f in variants.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                e0.record()
-                f()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
+        first, ms = timing.time_variants(variants, reps)
         fl = first['on']['match_flags'].cpu().numpy()
         off = first['on']['offset'].cpu().numpy()
         want = np.array([[-1, 0] if i % SHIFT_EVERY == 1 else [0, 0] for i in range(n)])
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        med = timing.medians(ms)
         print(json.dumps(dict(kind='case', frames=n, points=float(np.mean([len(t) for t in left])), window=[4, 4], reps=reps, median_ms=med,
                               cost_ms=med['on'] - med['off'], cost_over_off=(med['on'] - med['off']) / med['off'],
                               shifted=int((fl & fit.MATCH_SHIFTED != 0).sum()), weak=int((fl & fit.MATCH_WEAK != 0).sum()),
@@ -86,37 +69,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, nargs='+', default=[45, 4096])
     ap.add_argument('--points', type=int, default=250)
-    ap.add_argument('--reps', type=int, default=11)
-    ap.add_argument('--procs', type=int, default=3)
-    ap.add_argument('--child-timeout', type=float, default=400.0, help='seconds one child may take')
-    ap.add_argument('--out', default=None, help='also append every raw line to this file')
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
+    a = timing.parse(ap, reps=11, child_timeout=400.0)
     if a.child:
         return child(a.frames, a.points, a.reps)
-    lines = []
-
-    def emit(d):
-        lines.append(d)
-        print(json.dumps(d), flush=True)
-        if a.out:
-            with open(a.out, 'a') as f:
-                f.write(json.dumps(d) + '\n')
-    for p in range(a.procs):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--points', str(a.points), '--reps', str(a.reps), '--frames'] +
-                           [str(n) for n in a.frames], stdout=subprocess.PIPE, text=True, check=True, timeout=a.child_timeout)
-        for ln in r.stdout.splitlines():
-            if ln.startswith('{'):
-                emit(dict(json.loads(ln), process=p))
+    lines, emit = timing.run_children(__file__, a)
     for n in a.frames:
         rows = [d for d in lines if d['kind'] == 'case' and d['frames'] == n]
-        keys = ('off', 'on', 'search')
-        med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in keys}
-        spread = {k: max(d['median_ms'][k] for d in rows) - min(d['median_ms'][k] for d in rows) for k in keys}
-        emit(dict(kind='summary', frames=n, points=rows[0]['points'], window=[4, 4], procs=a.procs, median_ms=med, spread_ms=spread,
-                  cost_ms=med['on'] - med['off'], cost_over_off=(med['on'] - med['off']) / med['off'], shifted=rows[0]['shifted'],
-                  weak=rows[0]['weak'], edge=rows[0]['edge'], offsets_right=rows[0]['offsets_right'],
-                  status_ok_off=rows[0]['status_ok_off'], status_ok_on=rows[0]['status_ok_on']))
+        med, spread = timing.reduce(rows)
+        emit(timing.carry(dict(kind='summary', frames=n, points=rows[0]['points'], window=[4, 4], procs=a.procs, median_ms=med, spread_ms=spread,
+                               cost_ms=med['on'] - med['off'], cost_over_off=(med['on'] - med['off']) / med['off']), rows))
     return 0
 
 

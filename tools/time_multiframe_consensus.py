@@ -5,26 +5,19 @@ with 5 frames of every group displaced (tests/multiframe_consensus_cases.py: a p
     python tools/time_multiframe_consensus.py [--frames 45] [--points 250] [--bad 5] [--reps 7] [--procs 3] [--child-timeout 300]
                                               [--out FILE]
 
-Variants, alternated inside one process; the time between two device events around the Python call (wrapper, launches and
-kernels) and the wall time from the call to the results on the host:
+Variants, timed by the protocol of tools/timing.py: the time between two device events around the Python call (wrapper, launches
+and kernels) and the host clock from the call to the results on the host:
     lm / lm16          fit_multi_frame_gpu(method='lm'), one group / 16 groups
     cons / cons16      fit_multi_frame_consensus_gpu with its defaults (990 hypotheses per group at 45 usable frames)
 each on the clean tables (suffix 0) and on the tables with displaced frames (suffix the number of them).  With the profile
 timers of the library on (one extra warm-up call) the share of the two kernels is reported as well.
-The parent starts `--procs` fresh children one after the other and reports the medians over the children's medians and the
-spreads (max - min of the children's medians).  A child that fails or outlives --child-timeout ends the run: nothing more is
-started on the GPU after it.  The scenes come from tests/, which this file puts on sys.path: it has to stay beside the tests."""
+The scenes come from tests/: this file has to stay beside the tests."""
 import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import timing
+
 RADIUS = 45.0
 GROUPS = 16
 
@@ -50,13 +43,7 @@ def child(frames, points, bad, reps):
     event_ms = {}
 
     def timed(key, fn, *args, **kw):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        res = fn(*args, RADIUS, **kw)
-        e1.record()
-        back = torch.cat([res['T'].ravel(), res['fvals'].ravel(), res['iters'].ravel().to(torch.float64)]).cpu()
-        event_ms.setdefault(key, []).append(e0.elapsed_time(e1))
-        return res, back
+        return timing.resident(event_ms, key, fn, *args, RADIUS, **kw)
 
     variants = {}
     for nb in sorted(tables):
@@ -87,16 +74,9 @@ def child(frames, points, bad, reps):
         shares[k] = {name: ms for name, calls, ms in lib.profile_report() if name.startswith('k_multi_frame')}
     lib.profile(False)
     event_ms.clear()
-    ms = {k: [] for k in variants}
-    for _ in range(reps):
-        for k, f in variants.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            f()
-            ms[k].append((time.perf_counter() - t0) * 1e3)
-    print(json.dumps(dict(kind='case', frames=frames, points=points, bad=bad, groups=GROUPS, reps=reps,
-                          median_ms={k: statistics.median(v) for k, v in ms.items()},
-                          median_event_ms={k: statistics.median(v) for k, v in event_ms.items()}, kernel_ms=shares, info=info)), flush=True)
+    ms = timing.host_loop(variants, reps)
+    print(json.dumps(dict(kind='case', frames=frames, points=points, bad=bad, groups=GROUPS, reps=reps, median_ms=timing.medians(ms),
+                          median_event_ms=timing.medians(event_ms), kernel_ms=shares, info=info)), flush=True)
 
 
 def main():
@@ -104,36 +84,16 @@ def main():
     ap.add_argument('--frames', type=int, default=45)
     ap.add_argument('--points', type=int, default=250)
     ap.add_argument('--bad', type=int, default=5)
-    ap.add_argument('--reps', type=int, default=7)
-    ap.add_argument('--procs', type=int, default=3)
-    ap.add_argument('--child-timeout', type=float, default=300.0, help='seconds one child may take')
-    ap.add_argument('--out', default=None, help='also append every raw line to this file')
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
+    a = timing.parse(ap, reps=7, child_timeout=300.0)
     if a.child:
         return child(a.frames, a.points, a.bad, a.reps)
-    lines = []
-
-    def emit(d):
-        lines.append(d)
-        print(json.dumps(d), flush=True)
-        if a.out:
-            with open(a.out, 'a') as f:
-                f.write(json.dumps(d) + '\n')
-    for p in range(a.procs):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--frames', str(a.frames), '--points', str(a.points),
-                            '--bad', str(a.bad), '--reps', str(a.reps)], stdout=subprocess.PIPE, text=True, check=True,
-                           timeout=a.child_timeout)
-        for ln in r.stdout.splitlines():
-            if ln.startswith('{'):
-                emit(dict(json.loads(ln), process=p))
+    lines, emit = timing.run_children(__file__, a)
     rows = [d for d in lines if d['kind'] == 'case']
     keys = sorted(rows[0]['median_event_ms'])
-    med = lambda field: {k: statistics.median(d[field][k] for d in rows) for k in keys}
-    spread = lambda field: {k: max(d[field][k] for d in rows) - min(d[field][k] for d in rows) for k in keys}
-    emit(dict(kind='summary', frames=a.frames, points=a.points, bad=a.bad, groups=GROUPS, event_ms=med('median_event_ms'),
-              event_spread_ms=spread('median_event_ms'), wall_ms=med('median_ms'), wall_spread_ms=spread('median_ms'),
-              kernel_ms=rows[0]['kernel_ms'],
+    event, event_spread = timing.reduce(rows, keys, 'median_event_ms')
+    wall, wall_spread = timing.reduce(rows, keys)
+    emit(dict(kind='summary', frames=a.frames, points=a.points, bad=a.bad, groups=GROUPS, event_ms=event, event_spread_ms=event_spread,
+              wall_ms=wall, wall_spread_ms=wall_spread, kernel_ms=rows[0]['kernel_ms'],
               all_rejections_exact=all(all(d['info'][k]['rejected_are_the_displaced']) for d in rows for k in d['info'] if k.startswith('cons'))))
     return 0
 

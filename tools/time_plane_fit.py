@@ -6,25 +6,19 @@ lifted 5-40 mm off the board, triangulated by fit.triangulate_batch; for the per
     python tools/time_plane_fit.py [--frames 45 4096] [--points 250] [--table-frames 45 1024] [--reps 11] [--procs 3]
                                    [--child-timeout 400] [--out FILE]
 
-Per size, alternated inside one process, the time between two device events around one call:
+Per size, timed by the protocol of tools/timing.py between device events, one call:
     plane       fit.fit_plane_batch(X, idx, cnt)                       fitplane, grid map, pose
     plane_trim  fit.fit_plane_batch(X, idx, cnt, tau=1.0)              the same behind the trimming loop
     lm          fit.fit_cylinder_batch(X, cnt, 45, mode=FIT_LM)        the yardstick
 and for the table sizes (all 425 points of a frame)
     table       fit.index_planes_batch(X, idx, cnt, -12, 12)
-    lm          as above, on these tables
-The parent starts `--procs` fresh children one after the other and reports the median over the children's medians with the
-run-to-run spread (max - min of the children's medians).  A child that fails or outlives --child-timeout seconds ends the run:
-nothing more is started on the GPU after it."""
+    lm          as above, on these tables"""
 import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import timing
+
 RADIUS = 45.0
 
 
@@ -62,23 +56,6 @@ def make_tables(n, points, dev, seed=0, lift=True):
     return tri['pts3'], torch.from_numpy(idx).to(dev), cnt_d
 
 
-def time_variants(variants, reps):
-    import torch
-    first = {k: f() for k, f in variants.items()}                                       # warm-up, and the figures of the line
-    torch.cuda.synchronize()
-    ms = {k: [] for k in variants}
-    for _ in range(reps):
-        for k, f in variants.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            f()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1))
-    return first, ms
-
-
 def child(sizes, points, table_sizes, reps):
     import torch
     import cpe_amd  # noqa: F401
@@ -86,10 +63,10 @@ def child(sizes, points, table_sizes, reps):
     dev = torch.device('cuda:0')
     for n in sizes:
         X, idx, cnt = make_tables(n, points, dev)
-        first, ms = time_variants(dict(plane=lambda: fit.fit_plane_batch(X, idx, cnt),
-                                       plane_trim=lambda: fit.fit_plane_batch(X, idx, cnt, tau=1.0),
-                                       lm=lambda: fit.fit_cylinder_batch(X, cnt, RADIUS, mode=fit.FIT_LM)), reps)
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        first, ms = timing.time_variants(dict(plane=lambda: fit.fit_plane_batch(X, idx, cnt),
+                                              plane_trim=lambda: fit.fit_plane_batch(X, idx, cnt, tau=1.0),
+                                              lm=lambda: fit.fit_cylinder_batch(X, cnt, RADIUS, mode=fit.FIT_LM)), reps)
+        med = timing.medians(ms)
         print(json.dumps(dict(kind='fit', frames=n, points=float(cnt.double().mean()), reps=reps, median_ms=med,
                               plane_over_lm=med['plane'] / med['lm'], trim_over_lm=med['plane_trim'] / med['lm'],
                               status_ok=int((first['plane']['status'] == 0).sum()), status_ok_trim=int((first['plane_trim']['status'] == 0).sum()),
@@ -101,9 +78,9 @@ def child(sizes, points, table_sizes, reps):
         torch.cuda.empty_cache()
     for n in table_sizes:
         X, idx, cnt = make_tables(n, 425, dev)
-        first, ms = time_variants(dict(table=lambda: fit.index_planes_batch(X, idx, cnt, -12, 12),
-                                       lm=lambda: fit.fit_cylinder_batch(X, cnt, RADIUS, mode=fit.FIT_LM)), reps)
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        first, ms = timing.time_variants(dict(table=lambda: fit.index_planes_batch(X, idx, cnt, -12, 12),
+                                              lm=lambda: fit.fit_cylinder_batch(X, cnt, RADIUS, mode=fit.FIT_LM)), reps)
+        med = timing.medians(ms)
         c = first['table']['centre'].cpu().tolist()
         print(json.dumps(dict(kind='table', frames=n, points=425.0, reps=reps, median_ms=med, table_over_lm=med['table'] / med['lm'],
                               lines_ok=int((first['table']['status'] == 0).sum()), centre_status=int(first['table']['centre_status']),
@@ -117,38 +94,15 @@ def main():
     ap.add_argument('--frames', type=int, nargs='*', default=[45, 4096])
     ap.add_argument('--points', type=int, default=250)
     ap.add_argument('--table-frames', type=int, nargs='*', default=[45, 1024])
-    ap.add_argument('--reps', type=int, default=11)
-    ap.add_argument('--procs', type=int, default=3)
-    ap.add_argument('--child-timeout', type=float, default=400.0, help='seconds one child may take')
-    ap.add_argument('--out', default=None, help='also append every raw line to this file')
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
+    a = timing.parse(ap, reps=11, child_timeout=400.0)
     if a.child:
         return child(a.frames, a.points, a.table_frames, a.reps)
-    lines = []
-
-    def emit(d):
-        lines.append(d)
-        print(json.dumps(d), flush=True)
-        if a.out:
-            with open(a.out, 'a') as f:
-                f.write(json.dumps(d) + '\n')
-    for p in range(a.procs):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--points', str(a.points), '--reps', str(a.reps), '--frames'] +
-                           [str(n) for n in a.frames] + ['--table-frames'] + [str(n) for n in a.table_frames],
-                           stdout=subprocess.PIPE, text=True, check=True, timeout=a.child_timeout)
-        for ln in r.stdout.splitlines():
-            if ln.startswith('{'):
-                emit(dict(json.loads(ln), process=p))
-    for kind, sizes, keys in (('fit', a.frames, ('plane', 'plane_trim', 'lm')), ('table', a.table_frames, ('table', 'lm'))):
+    lines, emit = timing.run_children(__file__, a)
+    for kind, sizes, keys in (('fit', a.frames, ('plane', 'plane_trim')), ('table', a.table_frames, ('table',))):
         for n in sizes:
             rows = [d for d in lines if d['kind'] == kind and d['frames'] == n]
-            med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in keys}
-            spread = {k: max(d['median_ms'][k] for d in rows) - min(d['median_ms'][k] for d in rows) for k in keys}
-            extra = {k: v for k, v in rows[0].items() if k not in ('kind', 'frames', 'points', 'reps', 'median_ms', 'ms', 'process') and
-                     not k.endswith('_over_lm')}
-            emit(dict(kind=kind + '_summary', frames=n, points=rows[0]['points'], procs=a.procs, median_ms=med, spread_ms=spread,
-                      **{f'{k}_over_lm': med[k] / med['lm'] for k in keys if k != 'lm'}, **extra))
+            emit(timing.ratio_summary(dict(kind=kind + '_summary', frames=n, points=rows[0]['points'], procs=a.procs), rows,
+                                      [(f'{k}_over_lm', k, 'lm') for k in keys], skip=('trim_over_lm',)))   # the row's name for plane_trim_over_lm
     return 0
 
 

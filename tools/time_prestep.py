@@ -3,24 +3,19 @@ written as frame-major pairs) against the same result from the separate calls, f
 
     python tools/time_prestep.py [--pairs 64] [--reps 12] [--procs 3] [--child-timeout 300] [--out FILE]
 
-Variants, alternated inside one process, device events around every repetition:
+Variants, timed by the protocol of tools/timing.py between device events:
     a   StereoPrestep into an [F,2,h,w] tensor
     b   torch im2uint8 -> Undistorter(cubic) over the planes -> torch-f64 grey expression -> copy into the pairs tensor
-a and b must give equal bytes before anything is timed.  The parent process starts `--procs` fresh children one after the other
-and reports, per case, the median over the children's medians and b's run-to-run spread (max - min of its medians).  A child
-that fails or outlives --child-timeout seconds ends the run: nothing more is started on the GPU after it.
+a and b must give equal bytes before anything is timed.  The summary of a case carries b's run-to-run spread.
 Also: wall time per pair of the one-image-at-a-time host path (upload, remap per plane, download, upload, torch grey,
 download) that iotool.preprocessing was before the fused kernel, for u8 grey and u8 RGB host arrays."""
 import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import timing
+
 H, W = 1200, 1920
 CAMS = [dict(IntrinsicMatrix=[[1400.0, 0.3, 955.5], [0, 1398.0, 601.25], [0, 0, 1]], RadialDistortion=[-0.21, 0.07], TangentialDistortion=[0.001, -0.0007]),
         dict(IntrinsicMatrix=[[1402.0, 0.2, 963.0], [0, 1401.0, 598.75], [0, 0, 1]], RadialDistortion=[-0.20, 0.06], TangentialDistortion=[-0.0006, 0.0009])]
@@ -83,15 +78,8 @@ def child(pairs, reps):
             f(); f()
         torch.cuda.synchronize()
         assert torch.equal(out_a, out_b), f'{dtype} x{ch}: fused and separate results differ'
-        ms = {k: [] for k in variants}
-        for _ in range(reps):
-            for k, f in variants.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); f(); e1.record()
-                torch.cuda.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
-        print(json.dumps(dict(kind='case', dtype=dtype, channels=ch, pairs=pairs, reps=reps,
-                              median_ms={k: statistics.median(v) for k, v in ms.items()}, ms=ms)), flush=True)
+        ms = timing.event_loop(variants, reps)
+        print(json.dumps(dict(kind='case', dtype=dtype, channels=ch, pairs=pairs, reps=reps, median_ms=timing.medians(ms), ms=ms)), flush=True)
         del L, R, variants
         torch.cuda.empty_cache()
     # the one-image-at-a-time host path: per plane upload + remap + download, then upload + torch-f64 grey + download
@@ -121,33 +109,14 @@ def child(pairs, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=64)
-    ap.add_argument('--reps', type=int, default=12)
-    ap.add_argument('--procs', type=int, default=3)
-    ap.add_argument('--child-timeout', type=float, default=300.0, help='seconds one child (8 cases + the host path) may take')
-    ap.add_argument('--out', default=None, help='also append every raw line to this file')
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
+    a = timing.parse(ap, reps=12, child_timeout=300.0)      # a child is 8 cases + the host path
     if a.child:
         return child(a.pairs, a.reps)
-    lines = []
-
-    def emit(d):
-        lines.append(d)
-        print(json.dumps(d), flush=True)
-        if a.out:
-            with open(a.out, 'a') as f:
-                f.write(json.dumps(d) + '\n')
-    for p in range(a.procs):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--pairs', str(a.pairs), '--reps', str(a.reps)],
-                           stdout=subprocess.PIPE, text=True, check=True, timeout=a.child_timeout)
-        for ln in r.stdout.splitlines():
-            if ln.startswith('{'):
-                emit(dict(json.loads(ln), process=p))
+    lines, emit = timing.run_children(__file__, a)
     for dtype, ch in CASES:
         rows = [d for d in lines if d['kind'] == 'case' and d['dtype'] == dtype and d['channels'] == ch]
-        med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in ('a', 'b')}
-        bs = [d['median_ms']['b'] for d in rows]
-        spread = max(bs) - min(bs)
+        med, spreads = timing.reduce(rows)
+        spread = spreads['b']
         bpp = algorithmic_bytes_per_pixel(dtype, ch)
         rate = bpp * 2 * a.pairs * H * W / (med['a'] * 1e-3)
         verdict = med['a'] <= med['b'] + spread

@@ -6,23 +6,15 @@ fit.fit_single_plane_batch with and without relabel=.  The yardstick is the same
 Tables: analytic boards (the rig of cpe_amd.synth, 17 x 25 grid = 425 points, 16 seeded poses of up to 25 deg tilt repeated
 over the frames, 0.25 px noise per frame), ids (row, col) with the true indices in both images, so that the selector and the
 fit behind the re-labelling do the same work with and without it; the centre is the pixel of the grid point (0, 0).  Per size,
-alternated inside one process, the time between two device events around one call:
+timed by the protocol of tools/timing.py between device events, one call:
     relabel          fit.grid_relabel_batch(both images' tables, 2 n images)
     plane            fit.fit_single_plane_batch(g1, g2, ...)
-    plane_relabel    fit.fit_single_plane_batch(g1, g2, ..., relabel={}, center1=, center2=)
-The parent starts `--procs` fresh children one after the other and reports the median over the children's medians with the
-run-to-run spread (max - min of the children's medians).  A child that fails or outlives --child-timeout seconds ends the run:
-nothing more is started on the GPU after it."""
+    plane_relabel    fit.fit_single_plane_batch(g1, g2, ..., relabel={}, center1=, center2=)"""
 import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import timing
 
 
 def make_boards(n, dev, seed=0, poses=16):
@@ -63,16 +55,15 @@ def child(sizes, reps):
     import torch
     import cpe_amd  # noqa: F401
     from cpe_amd import fit
-    from time_plane_fit import time_variants
     dev = torch.device('cuda:0')
     for n in sizes:
         g1, g2, c1, c2, K1, K2, T21 = make_boards(n, dev)
         both, ctr = fit._cat_tables(g1, g2), torch.cat([c1, c2])
-        first, ms = time_variants(dict(
+        first, ms = timing.time_variants(dict(
             relabel=lambda: fit.grid_relabel_batch(both, ctr),
             plane=lambda: fit.fit_single_plane_batch(g1, g2, K1, K2, T21, tau=1.0),
             plane_relabel=lambda: fit.fit_single_plane_batch(g1, g2, K1, K2, T21, tau=1.0, relabel={}, center1=c1, center2=c2)), reps)
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        med = timing.medians(ms)
         same = bool(torch.equal(first['plane']['idx'], first['plane_relabel']['idx']) and torch.equal(first['plane']['P'], first['plane_relabel']['P']))
         print(json.dumps(dict(kind='relabel', frames=n, points=float(g1.cnt.double().mean()), reps=reps, median_ms=med,
                               relabel_over_plane=med['relabel'] / med['plane'], plane_relabel_over_plane=med['plane_relabel'] / med['plane'],
@@ -85,37 +76,14 @@ def child(sizes, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, nargs='*', default=[45, 4096])
-    ap.add_argument('--reps', type=int, default=11)
-    ap.add_argument('--procs', type=int, default=3)
-    ap.add_argument('--child-timeout', type=float, default=400.0, help='seconds one child may take')
-    ap.add_argument('--out', default=None, help='also append every raw line to this file')
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
+    a = timing.parse(ap, reps=11, child_timeout=400.0)
     if a.child:
         return child(a.frames, a.reps)
-    lines = []
-
-    def emit(d):
-        lines.append(d)
-        print(json.dumps(d), flush=True)
-        if a.out:
-            with open(a.out, 'a') as f:
-                f.write(json.dumps(d) + '\n')
-    for p in range(a.procs):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--reps', str(a.reps), '--frames'] + [str(n) for n in a.frames],
-                           stdout=subprocess.PIPE, text=True, check=True, timeout=a.child_timeout)
-        for ln in r.stdout.splitlines():
-            if ln.startswith('{'):
-                emit(dict(json.loads(ln), process=p))
+    lines, emit = timing.run_children(__file__, a)
     for n in a.frames:
         rows = [d for d in lines if d['kind'] == 'relabel' and d['frames'] == n]
-        keys = list(rows[0]['median_ms'])
-        med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in keys}
-        spread = {k: max(d['median_ms'][k] for d in rows) - min(d['median_ms'][k] for d in rows) for k in keys}
-        skip = ('kind', 'frames', 'reps', 'median_ms', 'ms', 'process', 'relabel_over_plane', 'plane_relabel_over_plane')
-        emit(dict(kind='relabel_summary', frames=n, procs=a.procs, median_ms=med, spread_ms=spread,
-                  relabel_over_plane=med['relabel'] / med['plane'], plane_relabel_over_plane=med['plane_relabel'] / med['plane'],
-                  **{k: v for k, v in rows[0].items() if k not in skip}))
+        emit(timing.ratio_summary(dict(kind='relabel_summary', frames=n, procs=a.procs), rows,
+                                  (('relabel_over_plane', 'relabel', 'plane'), ('plane_relabel_over_plane', 'plane_relabel', 'plane'))))
     return 0
 
 

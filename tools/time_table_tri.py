@@ -7,26 +7,20 @@ laser-plane table is the rig's true one, -12..12.
     python tools/time_table_tri.py [--frames 45 4096] [--points 250] [--pipeline-frames 64] [--chunk 32] [--reps 11] [--procs 3]
                                    [--child-timeout 400] [--out FILE]
 
-Per size, alternated inside one process, the time between two device events around one call:
+Per size, timed by the protocol of tools/timing.py between device events, one call:
     table_tri    fit.table_triangulate_batch(gp1, K1, None, table)               one camera
     select_tri   fit.select_triangulate_batch(gp1, gp2, K1, K2, T21)             chooseIdx + DLT: the step it replaces
     mono_fit     fit.fit_single_cylinder_mono_batch(gp1, K1, None, table, 45)    FIT_LM
     stereo_fit   fit.fit_single_cylinder_batch(gp1, gp2, K1, K2, T21, 45)        FIT_LM
 and on `--pipeline-frames` rendered 1920 x 1200 pairs (0 = skip), in chunks of `--chunk`:
     pipe_left    FramePipeline(source='left', laser_table=table).run(left, None)
-    pipe_stereo  FramePipeline().run(left, right)
-The parent starts `--procs` fresh children one after the other and reports the median over the children's medians with the
-run-to-run spread (max - min of the children's medians).  A child that fails or outlives --child-timeout seconds ends the run:
-nothing more is started on the GPU after it."""
+    pipe_stereo  FramePipeline().run(left, right)"""
 import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import timing
+
 RADIUS = 45.0
 
 
@@ -88,23 +82,6 @@ def make_tables(n, points, dev, seed=0):
     return fit.GridTables(t(xy[0]), idx_d, cnt_d), fit.GridTables(t(xy[1]), idx_d, cnt_d), K1, K2, T21, rig_table(scene, -12, 12, dev)
 
 
-def time_variants(variants, reps):
-    import torch
-    first = {k: f() for k, f in variants.items()}                                       # warm-up, and the figures of the line
-    torch.cuda.synchronize()
-    ms = {k: [] for k in variants}
-    for _ in range(reps):
-        for k, f in variants.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            f()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1))
-    return first, ms
-
-
 def child(sizes, points, pipeline_frames, chunk, reps):
     import torch
     import cpe_amd  # noqa: F401
@@ -112,12 +89,12 @@ def child(sizes, points, pipeline_frames, chunk, reps):
     dev = torch.device('cuda:0')
     for n in sizes:
         g1, g2, K1, K2, T21, tab = make_tables(n, points, dev)
-        first, ms = time_variants(dict(
+        first, ms = timing.time_variants(dict(
             table_tri=lambda: fit.table_triangulate_batch(g1, K1, None, tab),
             select_tri=lambda: fit.select_triangulate_batch(g1, g2, K1, K2, T21),
             mono_fit=lambda: fit.fit_single_cylinder_mono_batch(g1, K1, None, tab, RADIUS, mode=fit.FIT_LM),
             stereo_fit=lambda: fit.fit_single_cylinder_batch(g1, g2, K1, K2, T21, RADIUS, mode=fit.FIT_LM)), reps)
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        med = timing.medians(ms)
         print(json.dumps(dict(kind='tables', frames=n, points=float(g1.cnt.double().mean()), reps=reps, median_ms=med,
                               tri_over_select=med['table_tri'] / med['select_tri'], mono_over_stereo=med['mono_fit'] / med['stereo_fit'],
                               m_table=float(first['table_tri']['m'].double().mean()), m_select=float(first['select_tri']['m'].double().mean()),
@@ -133,8 +110,8 @@ def child(sizes, points, pipeline_frames, chunk, reps):
         left, right = b['left'], b['right']
         mono = pipeline.FramePipeline(*args, chunk=chunk, device=dev, fit_mode=fit.FIT_LM, source='left', laser_table=tab)
         stereo = pipeline.FramePipeline(*args, chunk=chunk, device=dev, fit_mode=fit.FIT_LM)
-        first, ms = time_variants(dict(pipe_left=lambda: mono.run(left, None), pipe_stereo=lambda: stereo.run(left, right)), reps)
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        first, ms = timing.time_variants(dict(pipe_left=lambda: mono.run(left, None), pipe_stereo=lambda: stereo.run(left, right)), reps)
+        med = timing.medians(ms)
         ok = lambda rec: int((pipeline.unpack_counters(rec[:, 15])[2] == 0).sum())
         print(json.dumps(dict(kind='pipeline', frames=pipeline_frames, chunk=chunk, reps=reps, median_ms=med,
                               left_over_stereo=med['pipe_left'] / med['pipe_stereo'], fit_ok_left=ok(first['pipe_left']),
@@ -147,41 +124,16 @@ def main():
     ap.add_argument('--points', type=int, default=250)
     ap.add_argument('--pipeline-frames', type=int, default=64)
     ap.add_argument('--chunk', type=int, default=32)
-    ap.add_argument('--reps', type=int, default=11)
-    ap.add_argument('--procs', type=int, default=3)
-    ap.add_argument('--child-timeout', type=float, default=400.0, help='seconds one child may take')
-    ap.add_argument('--out', default=None, help='also append every raw line to this file')
-    ap.add_argument('--child', action='store_true')
-    a = ap.parse_args()
+    a = timing.parse(ap, reps=11, child_timeout=400.0)
     if a.child:
         return child(a.frames, a.points, a.pipeline_frames, a.chunk, a.reps)
-    lines = []
-
-    def emit(d):
-        lines.append(d)
-        print(json.dumps(d), flush=True)
-        if a.out:
-            with open(a.out, 'a') as f:
-                f.write(json.dumps(d) + '\n')
-    for p in range(a.procs):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--points', str(a.points), '--reps', str(a.reps),
-                            '--pipeline-frames', str(a.pipeline_frames), '--chunk', str(a.chunk), '--frames'] + [str(n) for n in a.frames],
-                           stdout=subprocess.PIPE, text=True, check=True, timeout=a.child_timeout)
-        for ln in r.stdout.splitlines():
-            if ln.startswith('{'):
-                emit(dict(json.loads(ln), process=p))
+    lines, emit = timing.run_children(__file__, a)
     ratios = dict(tables=(('tri_over_select', 'table_tri', 'select_tri'), ('mono_over_stereo', 'mono_fit', 'stereo_fit')),
                   pipeline=(('left_over_stereo', 'pipe_left', 'pipe_stereo'),))
     for kind, sizes in (('tables', a.frames), ('pipeline', [a.pipeline_frames] if a.pipeline_frames > 0 else [])):
         for n in sizes:
             rows = [d for d in lines if d['kind'] == kind and d['frames'] == n]
-            keys = list(rows[0]['median_ms'])
-            med = {k: statistics.median(d['median_ms'][k] for d in rows) for k in keys}
-            spread = {k: max(d['median_ms'][k] for d in rows) - min(d['median_ms'][k] for d in rows) for k in keys}
-            skip = ('kind', 'frames', 'reps', 'median_ms', 'ms', 'process') + tuple(r[0] for r in ratios[kind])
-            extra = {k: v for k, v in rows[0].items() if k not in skip}
-            emit(dict(kind=kind + '_summary', frames=n, procs=a.procs, median_ms=med, spread_ms=spread,
-                      **{name: med[num] / med[den] for name, num, den in ratios[kind]}, **extra))
+            emit(timing.ratio_summary(dict(kind=kind + '_summary', frames=n, procs=a.procs), rows, ratios[kind]))
     return 0
 
 
