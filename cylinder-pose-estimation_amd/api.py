@@ -8,6 +8,7 @@ writes the structs the MATLAB side holds after makePyGridPts / fitSingleCylinder
 There is no CPU fallback: without a GPU and libcpe_hip.so these raise."""
 import collections
 import ctypes as C
+import functools
 import json
 import threading
 
@@ -17,20 +18,37 @@ import torch
 from . import lib as _lib
 from .fit import GridTables, MAXP
 
-PLANES = dict(binary=0, hmask=1, vmask=2, mask_contour=3, roi_h=4, roi_v=5, exp_h=6, exp_v=7, joints=8, state=9,
-              clahe=10, blur19=11, blur7=12, labels=13, sweep=14)
-TARGETS = dict(cylinder=0, plane=1)
+_c = _lib.const
+PLANES = _lib.const_group('PLANE_')       # 'binary', 'hmask', ..., 'sweep': the CPE_PLANE_* numbers
+TARGETS = _lib.TARGETS                    # 'cylinder', 'plane': CPE_TARGET_*
 # debug outputs that no stage reads where rows are a multiple of 16 pixels: undefined after detect_grid_batch(debug_planes=False)
 DEBUG_PLANES = ('hmask', 'vmask', 'roi_h', 'roi_v')
-STATUS_TEXT = {0: 'ok', 1: 'no region (cv2.convexHull(None))', 2: 'no saturated spot (circle_radius0 unbound)',
-               3: 'no valid rows/cols', 4: 'empty point list', 5: 'too few points', 6: 'workspace capacity exceeded',
-               7: 'sub-pixel refinement raised (line sample above / left of the image)'}
+STATUS_TEXT = {_c.ST_OK: 'ok', _c.ST_NO_REGION: 'no region (cv2.convexHull(None))',
+               _c.ST_NO_SPOT: 'no saturated spot (circle_radius0 unbound)', _c.ST_NO_LINES: 'no valid rows/cols',
+               _c.ST_EMPTY: 'empty point list', _c.ST_FEW_POINTS: 'too few points', _c.ST_OVERFLOW: 'workspace capacity exceeded',
+               _c.ST_SUBPIXEL_RAISED: 'sub-pixel refinement raised (line sample above / left of the image)'}
 
-_STATE_FIELDS = ['status', 'rect0', 'rect1', 'rect2', 'rect3', 'r0', 'spot0', 'spot1', 'spot2', 'spot3', 'n_roots',
-                 'n_comps', 'n_joints_all', 'n_joints', 'n_blobs', 'n_groups', 'n_groups_prev', 'n_kp', 'n_verts',
-                 'n_dists', 'best_comp', 'n_seg0', 'n_seg1', 'gang0', 'gang1', 'glen0', 'glen1', 'n_rows', 'n_cols',
-                 'overflow', 'hull_n', 'crect0', 'crect1', 'crect2', 'crect3', 'nrect0', 'nrect1', 'nrect2', 'nrect3', 'n_roots_p', 'n_roots_s', 'spot_fail',
-                 'srect0', 'srect1', 'srect2', 'srect3']
+
+@functools.lru_cache(maxsize=None)
+def state_fields():
+    """((name, is_float), ...) of the 32-bit words of the per-frame state record, as the library lists its fields
+    (cpe_debug_state_field); an array field `rect` of 4 words gives rect0 .. rect3"""
+    L = _lib.load()
+    name = C.create_string_buffer(64)
+    words, is_float = C.c_int32(), C.c_int32()
+    out, k = [], 0
+    while L.cpe_debug_state_field(k, name, len(name), C.byref(words), C.byref(is_float)) == 0:
+        base = name.value.decode()
+        out += [(base if words.value == 1 else f'{base}{i}', bool(is_float.value)) for i in range(words.value)]
+        k += 1
+    return tuple(out)
+
+
+def __getattr__(name):
+    """api._STATE_FIELDS, the list of names the tests index the state words by: the same listing, made on first use"""
+    if name == '_STATE_FIELDS':
+        return [k for k, _ in state_fields()]
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 
 class DetectWorkspace:
@@ -82,14 +100,8 @@ class DetectWorkspace:
     def state(self):
         """list of dicts (one per frame) of the per-frame state record"""
         arr = self.plane('state').cpu().numpy()
-        out = []
-        for row in arr:
-            d = {}
-            for k, name in enumerate(_STATE_FIELDS):
-                v = row[k]
-                d[name] = float(np.int32(v).view(np.float32)) if name[:4] in ('gang', 'glen') else int(v)
-            out.append(d)
-        return out
+        return [{name: float(np.int32(v).view(np.float32)) if is_float else int(v) for (name, is_float), v in zip(state_fields(), row)}
+                for row in arr]
 
 
 def _output_tables(n, dev):

@@ -1,5 +1,7 @@
 // Device-side building blocks shared by the image-stage kernels (gfx950).
 #pragma once
+#include <cstddef>
+#include <type_traits>
 #include "cpe_internal.h"
 
 namespace cpe {
@@ -33,34 +35,56 @@ constexpr int MAXSEG = 2048;     // line fragments per mask in the expansion sta
 struct BlobRec { double x, y, r; int key; int pad; };
 struct Group { int n; int pad; double c[GCAP][3]; };
 
+// The per-frame state record, declared once: X(type, name, count), type int or float, count 1 (a scalar), 2 or 4 (an array).
+// struct FrameState and the name table behind cpe_debug_state_field (the names DetectWorkspace.state() reports) both come
+// from these rows, in this order; a row added here needs the word count of the size assert below and nothing else.
+#define CPE_STATE_FIELDS(X) \
+    X(int, status, 1) \
+    X(int, rect, 4)          /* boundingRect(max_contour) */ \
+    X(int, r0, 1)            /* circle_radius0 */ \
+    X(int, spot, 4)          /* ellipse cx, cy, a, b */ \
+    X(int, n_roots, 1)       /* scratch counters (reset by the stage that uses them) */ \
+    X(int, n_comps, 1) \
+    X(int, n_joints_all, 1)  /* all joints */ \
+    X(int, n_joints, 1)      /* joints inside rect (sorted in OpenCV contour order) */ \
+    X(int, n_blobs, 1) \
+    X(int, n_groups, 1) \
+    X(int, n_groups_prev, 1) \
+    X(int, n_kp, 1) \
+    X(int, n_verts, 1)       /* bump pointer of the vertex scratch */ \
+    X(int, n_dists, 1)       /* bump pointer of the distance scratch */ \
+    X(int, best_comp, 1)     /* index of the selected contour */ \
+    X(int, n_seg, 2)         /* valid fragments per mask (h, v) */ \
+    X(float, gang, 2) \
+    X(float, glen, 2) \
+    X(int, n_rows, 1) \
+    X(int, n_cols, 1) \
+    X(int, overflow, 1) \
+    X(int, hull_n, 1) \
+    X(int, crect, 4)         /* working rectangle of a restricted labelling pass (x0, y0, x1, y1) */ \
+    X(int, nrect, 4)         /* bounding-box accumulator */ \
+    X(int, n_roots_p, 1)     /* component count of the joints labelling (runs on its own stream, beside the region stage) */ \
+    X(int, n_roots_s, 1)     /* component count of the spot labelling (third stream) */ \
+    X(int, spot_fail, 1)     /* the spot chain found no saturated spot: folded into `status` when the chains join */ \
+    X(int, srect, 4)         /* window of the spot labelling (x0, y0, x1, y1): the tiles that hold a pixel > 240, + 16 px */
+#define CPE_STATE_DIM_1
+#define CPE_STATE_DIM_2 [2]
+#define CPE_STATE_DIM_4 [4]
 struct FrameState {
-    int status;
-    int rect[4];        // boundingRect(max_contour)
-    int r0;             // circle_radius0
-    int spot[4];        // ellipse cx, cy, a, b
-    int n_roots;        // scratch counters (reset by the stage that uses them)
-    int n_comps;
-    int n_joints_all;   // all joints
-    int n_joints;       // joints inside rect (sorted in OpenCV contour order)
-    int n_blobs;
-    int n_groups;
-    int n_groups_prev;
-    int n_kp;
-    int n_verts;        // bump pointer of the vertex scratch
-    int n_dists;        // bump pointer of the distance scratch
-    int best_comp;      // index of the selected contour
-    int n_seg[2];       // valid fragments per mask (h, v)
-    float gang[2], glen[2];
-    int n_rows, n_cols;
-    int overflow;
-    int hull_n;
-    int crect[4];       // working rectangle of a restricted labelling pass (x0, y0, x1, y1)
-    int nrect[4];       // bounding-box accumulator
-    int n_roots_p;      // component count of the joints labelling (runs on its own stream, beside the region stage)
-    int n_roots_s;      // component count of the spot labelling (third stream)
-    int spot_fail;      // the spot chain found no saturated spot: folded into `status` when the chains join
-    int srect[4];       // window of the spot labelling (x0, y0, x1, y1): the tiles that hold a pixel > 240, + 16 px
+#define X(type, name, count) type name CPE_STATE_DIM_##count;
+    CPE_STATE_FIELDS(X)
+#undef X
 };
+struct StateField { const char *name; int words; bool is_float; };
+constexpr StateField STATE_FIELDS[] = {
+#define X(type, name, count) {#name, count, std::is_same<type, float>::value},
+    CPE_STATE_FIELDS(X)
+#undef X
+};
+static_assert(sizeof(FrameState) == 46 * sizeof(int), "FrameState: the record is 46 words (tests and tools read them by name)");
+static_assert(offsetof(FrameState, status) == 0 && offsetof(FrameState, r0) == 5 * 4 && offsetof(FrameState, n_seg) == 21 * 4 &&
+              offsetof(FrameState, gang) == 23 * 4 && offsetof(FrameState, crect) == 31 * 4 && offsetof(FrameState, srect) == 42 * 4,
+              "FrameState: a row of CPE_STATE_FIELDS moved");
 
 struct SegRec { float p1x, p1y, p2x, p2y, angle, len; int valid; int pad; };
 

@@ -161,6 +161,19 @@ extern "C" int32_t cpe_debug_workspace_buffer(int32_t n, int32_t h, int32_t w, i
     return CPE_OK;
 }
 
+// One row of the state record's table of fields (CPE_STATE_FIELDS, cpe_dev.h): host code only (tests, debugging).
+extern "C" int32_t cpe_debug_state_field(int32_t index, char *name_out, size_t name_cap, int32_t *words, int32_t *is_float)
+{
+    constexpr int32_t rows = sizeof(STATE_FIELDS) / sizeof(STATE_FIELDS[0]);
+    CPE_CHECK_ARG(index >= 0 && index < rows && name_out && name_cap > 0 && words && is_float, "cpe_debug_state_field: bad argument");
+    const StateField &r = STATE_FIELDS[index];
+    size_t k = 0;
+    for (; r.name[k] && k + 1 < name_cap; k++) name_out[k] = r.name[k];
+    name_out[k] = 0;
+    *words = r.words; *is_float = r.is_float;
+    return CPE_OK;
+}
+
 extern "C" int32_t cpe_detect_grid_batch(const uint8_t *gray, int32_t n, int32_t h, int32_t w, void *ws, size_t ws_bytes,
                                          double *xy, int32_t *id, int32_t *n_pts, double *center, int32_t *status,
                                          void *stream)

@@ -154,8 +154,6 @@ static_assert(ws_public(CPE_PLANE_BINARY) == WS_BINARY && ws_public(CPE_PLANE_HM
               ws_public(CPE_PLANE_BLUR19) == WS_BLUR19 && ws_public(CPE_PLANE_BLUR7) == WS_BLUR7 && ws_public(CPE_PLANE_LABELS) == WS_LABELS &&
               ws_public(CPE_PLANE_SWEEP) == WS_SWEEP && ws_public(CPE_PLANE_COUNT) == WS_COUNT,
               "include/cpe.h: CPE_PLANE_* 0..14 and the public column of CPE_WS_TABLE disagree");
-// api._STATE_FIELDS (api.py) names these words one by one: a field added here is added there
-static_assert(sizeof(FrameState) == 46 * sizeof(int), "FrameState changed: update api._STATE_FIELDS and this count");
 
 struct Layout {
     size_t off[WS_COUNT];

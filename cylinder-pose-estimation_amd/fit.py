@@ -13,11 +13,12 @@ import torch
 
 from . import lib as _lib
 
-MAXP = _lib.MAXP
-SEL_CHOOSE_IDX, SEL_THRESHOLD, SEL_JOIN = 0, 1, 2
-FLAG_FALLBACK, FLAG_OVERFLOW = 1, 2                 # CPE_FIT_FLAG_*
-ST_OK, ST_FEW_POINTS, ST_OVERFLOW = 0, 5, 6         # CPE_ST_* of the fit
-FIT_MIN_POINTS = 5                                  # CPE_FIT_MIN_POINTS
+_c = _lib.const     # every constant below is the header's CPE_<name> (include/cpe.h), under the name callers know
+MAXP = _c.MAXP
+SEL_CHOOSE_IDX, SEL_THRESHOLD, SEL_JOIN = _c.SEL_CHOOSE_IDX, _c.SEL_THRESHOLD, _c.SEL_JOIN
+FLAG_FALLBACK, FLAG_OVERFLOW = _c.FIT_FLAG_FALLBACK, _c.FIT_FLAG_OVERFLOW
+ST_OK, ST_FEW_POINTS, ST_OVERFLOW = _c.ST_OK, _c.ST_FEW_POINTS, _c.ST_OVERFLOW      # the statuses of the fit
+FIT_MIN_POINTS = _c.FIT_MIN_POINTS
 
 
 @dataclass
@@ -152,7 +153,7 @@ def triangulate_batch(p1, p2, cnt, K1, K2, T21):
     return dict(pts3=X, err=err, mean_err=me)
 
 
-FIT_NELDER_MEAD, FIT_LM = 0, 1
+FIT_NELDER_MEAD, FIT_LM = _c.FIT_NELDER_MEAD, _c.FIT_LM
 
 
 def _fit_outputs(n, dev):
@@ -192,8 +193,9 @@ def fit_cylinder_ransac_batch(pts3, cnt, radius, hypotheses=64, sample=12, tau=0
     return dict(cyl_raw=raw, cyl=cyl, T=T, fvals=fv, iters=it, status=st, n_inliers=ninl, inlier_mask=mask)
 
 
-MATCH_MAX_WIN = 8                                                                   # CPE_MATCH_MAX_WIN
-MATCH_SHIFTED, MATCH_WEAK, MATCH_EDGE, MATCH_OVERFLOW = 1, 2, 4, 8                  # CPE_MATCH_FLAG_*
+MATCH_MAX_WIN = _c.MATCH_MAX_WIN
+MATCH_SHIFTED, MATCH_WEAK, MATCH_EDGE, MATCH_OVERFLOW = (_c.MATCH_FLAG_SHIFTED, _c.MATCH_FLAG_WEAK, _c.MATCH_FLAG_EDGE,
+                                                         _c.MATCH_FLAG_OVERFLOW)
 
 
 def match_offset_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, radius, win_c=4, win_r=4, th=0.3, tau=0.5, hyp_iters=8,
@@ -255,7 +257,7 @@ def fit_single_cylinder_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, rad
     return dict(sel, **_fit_points(sel['pts3'], sel['m'], radius, ransac, sel['flags'], **fit_kw), **extra)
 
 
-PLANE_NO_GRID, PLANE_ORIGIN_POINT = 1, 2            # CPE_PLANEFIT_*
+PLANE_NO_GRID, PLANE_ORIGIN_POINT = _c.PLANEFIT_NO_GRID, _c.PLANEFIT_ORIGIN_POINT
 
 
 def _point_tables(what, pts3, idx, cnt, use=None):
@@ -317,8 +319,9 @@ def index_planes_batch(pts3, idx, cnt, lo, hi, use=None, frame_ok=None, min_spre
     return dict(P=P, stats=stats, count=count, frames=frames, status=st, centre=centre, centre_status=cst, lo=int(lo), hi=int(hi))
 
 
-RELABEL_NO_CENTRE, RELABEL_OVERFLOW, RELABEL_FEW_LINES = 1, 2, 4    # CPE_RELABEL_FLAG_* (FEW_LINES << c for id component c)
-LINE_KEPT, LINE_UNSUPPORTED, LINE_PHANTOM = 0, 1, 2                 # CPE_RELABEL_LINE_*
+# (RELABEL_FEW_LINES << c for id component c)
+RELABEL_NO_CENTRE, RELABEL_OVERFLOW, RELABEL_FEW_LINES = _c.RELABEL_FLAG_NO_CENTRE, _c.RELABEL_FLAG_OVERFLOW, _c.RELABEL_FLAG_FEW_LINES
+LINE_KEPT, LINE_UNSUPPORTED, LINE_PHANTOM = _c.RELABEL_LINE_KEPT, _c.RELABEL_LINE_UNSUPPORTED, _c.RELABEL_LINE_PHANTOM
 
 
 def grid_relabel_batch(tables: GridTables, center, swap=0, min_pts=3, merge_frac=0.65, dir=(1, 1)):
@@ -581,7 +584,7 @@ def table_triangulate_batch(gp: GridTables, K, Tc, table: LaserTable, need_both=
     return dict(pts3=X, idx=idx, res=res, src=src, m=m, counts=counts, stats=stats)
 
 
-FUSED_TRUNCATED = 4                                                 # CPE_FUSED_FLAG_TRUNCATED (beside FLAG_OVERFLOW)
+FUSED_TRUNCATED = _c.FUSED_FLAG_TRUNCATED                            # (beside FLAG_OVERFLOW)
 FUSED_RAY1, FUSED_RAY2, FUSED_PLANE0, FUSED_PLANE1 = 1, 2, 4, 8     # bits of src[..., 0]
 
 
@@ -632,8 +635,9 @@ def fit_single_cylinder_fused_batch(gp1: GridTables, gp2: GridTables, K1, K2, T2
     return dict(tri, **_fit_points(tri['pts3'], tri['m'], radius, ransac, tri['flags'], mode=mode, **fit_kw), mean_err=tri['stats'][:, 0])
 
 
-PRED_MAXN = _lib.PRED_MAXN                                          # CPE_PRED_MAXN
-PRED_OK, PRED_NO_FRAME, PRED_NO_PLANE, PRED_PARALLEL, PRED_MISS, PRED_GRAZING = range(6)   # CPE_PRED_*
+PRED_MAXN = _c.PRED_MAXN
+PRED_OK, PRED_NO_FRAME, PRED_NO_PLANE, PRED_PARALLEL, PRED_MISS, PRED_GRAZING = (
+    _c.PRED_OK, _c.PRED_NO_FRAME, _c.PRED_NO_PLANE, _c.PRED_PARALLEL, _c.PRED_MISS, _c.PRED_GRAZING)
 
 
 def grid_predict_batch(cyl, radius, K1, K2, T21, table: LaserTable, use=None, window=None, min_cos=0.1, image_size=None):
@@ -771,8 +775,8 @@ def fit_single_cylinder_refined_batch(gp1: GridTables, gp2: GridTables, K1, K2, 
     return out
 
 
-SHIFT_MAX_WIN = 8                                                   # CPE_SHIFT_MAX_WIN
-SHIFT_SHIFTED, SHIFT_WEAK, SHIFT_EDGE = 1, 2, 4                     # CPE_SHIFT_FLAG_*
+SHIFT_MAX_WIN = _c.SHIFT_MAX_WIN
+SHIFT_SHIFTED, SHIFT_WEAK, SHIFT_EDGE = _c.SHIFT_FLAG_SHIFTED, _c.SHIFT_FLAG_WEAK, _c.SHIFT_FLAG_EDGE
 
 
 def index_shift_batch(pts3, idx, cnt, table: LaserTable, use=None, win=(4, 4), tau=1.0, min_score=8, ids='col_row'):

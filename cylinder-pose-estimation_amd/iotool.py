@@ -106,9 +106,10 @@ def undistort_image(image, camera_params, device='cuda:0', interp='linear'):
     return out[0] if img.ndim == 2 else np.ascontiguousarray(np.moveaxis(out, 0, 2))
 
 
-_PIX = {torch.uint8: 0, torch.int16: 1, torch.float32: 2, torch.float64: 3}     # CPE_PIX_* of include/cpe.h
+_PIX = {torch.uint8: _lib.const.PIX_U8, torch.int16: _lib.const.PIX_U16, torch.float32: _lib.const.PIX_F32,
+        torch.float64: _lib.const.PIX_F64}      # (int16: the bits of a uint16 frame where torch has no uint16)
 if hasattr(torch, 'uint16'):
-    _PIX[torch.uint16] = 1
+    _PIX[torch.uint16] = _lib.const.PIX_U16
 
 
 def _prestep(cubic_map, raw, dst, dst_frame_stride):

@@ -1,12 +1,21 @@
 """ctypes loader for libcpe_hip.so (C ABI: include/cpe.h).
 
+include/cpe.h is the one declaration of the boundary; nothing of it is typed again here.  At import the header is parsed
+(no library and no GPU needed) into
+  _SIGS        name -> (restype, argtypes) of every `CPE_API` prototype,
+  Cpe...       a ctypes.Structure per `typedef struct { ... } CpeX;`, published under the header's name,
+  const        every numeric `#define CPE_X`, named without the prefix: const.MAXP, const.FIT_LM, const.ST_OVERFLOW.
+load() refuses a library whose cpe_version() is not the header's CPE_VERSION.
 There is NO CPU fallback: if the HIP library is missing or a call fails, this raises."""
 import ctypes as C
 import os
+import re
 import subprocess
+import types
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, 'libcpe_hip.so')
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'cpe.h'))
 _lib = None
 
 
@@ -23,178 +32,92 @@ def build(verbose=False):
     return SO_PATH
 
 
-_SIGS = {
-    'cpe_version': (C.c_int32, []),
-    'cpe_last_error_string': (C.c_char_p, []),
-    'cpe_profile_enable': (None, [C.c_int32]),
-    'cpe_profile_report': (C.c_int32, [C.c_char_p, C.c_size_t]),
-    'cpe_preprocess_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    'cpe_debug_preprocess': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
-    'cpe_detect_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
-    'cpe_detect_constants': (C.c_int32, [C.c_int32, C.c_void_p]),
-    'cpe_detect_grid_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t] +
-                              [C.c_void_p] * 6),
-    'cpe_detect_grid_batch_ex': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t] +
-                                 [C.c_void_p] * 6),
-    'cpe_detect_grid_bgr_batch_ex': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t] +
-                                     [C.c_void_p] * 6),
-    'cpe_detect_line_tables': (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
-    'cpe_detect_results_sizes': (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
-    'cpe_detect_results_pack': (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 +
-                                [C.c_size_t, C.c_void_p]),
-    'cpe_bgr2gray_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    'cpe_detect_workspace_plane': (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    'cpe_debug_workspace_buffer': (C.c_int32, [C.c_int32] * 4 + [C.c_char_p, C.c_size_t] + [C.c_void_p] * 5),
-    'cpe_debug_external_components': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
-                                                  C.c_void_p, C.c_void_p]),
-    'cpe_debug_ccl': (C.c_int32, [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    'cpe_debug_dark_labels': (C.c_int32, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
-    'cpe_debug_ccl_tiles': (C.c_int32, [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4),
-    'cpe_debug_blob_region': (C.c_int32, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p,
-                                                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    'cpe_debug_clahe_planes': (C.c_int32, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
-    'cpe_debug_clahe_planes_bgr': (C.c_int32, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6),
-    'cpe_debug_masks': (C.c_int32, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    'cpe_debug_lines': (C.c_int32, [C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6),
-    'cpe_debug_region_hull': (C.c_int32, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    'cpe_fit_workspace_bytes': (C.c_size_t, [C.c_int32]),
-    'cpe_select_triangulate_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3 +
-                                     [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_size_t] + [C.c_void_p] * 9),
-    'cpe_choose_idx_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_double, C.c_void_p, C.c_size_t] +
-                             [C.c_void_p] * 6),
-    'cpe_triangulate_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 7),
-    'cpe_multi_frame_terms': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
-    'cpe_multi_frame_fit_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p] + [C.c_void_p] * 9),
-    'cpe_multi_frame_fit_lm_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p] + [C.c_void_p] * 10),
-    'cpe_multi_frame_consensus_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
-    'cpe_multi_frame_consensus_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   C.c_size_t] + [C.c_void_p] * 13),
-    'cpe_pose_vec2T_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    'cpe_pose_T2vec_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    'cpe_agv_chain_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    'cpe_frame_angles_lm_batch': (C.c_int32, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p] + [C.c_void_p] * 9),
-    'cpe_fit_cylinder_ransac_batch': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p] +
-                                      [C.c_void_p] * 9),
-    'cpe_match_offset_workspace_bytes': (C.c_size_t, [C.c_int32] * 3),
-    'cpe_match_offset_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_double, C.c_void_p, C.c_void_p, C.c_size_t] +
-                               [C.c_void_p] * 6),
-    'cpe_fit_plane_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 10),
-    'cpe_index_planes_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double] +
-                               [C.c_void_p] * 8),
-    'cpe_table_triangulate_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] +
-                                    [C.c_void_p] * 9),
-    'cpe_fused_triangulate_batch': (C.c_int32, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32] +
-                                    [C.c_void_p] * 10),
-    'cpe_fit_projector_model': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
-                                [C.c_void_p] * 10),
-    'cpe_projector_model_table': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
-    'cpe_index_shift_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] + [C.c_void_p] * 8),
-    'cpe_grid_relabel_batch': (C.c_int32, [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 11),
-    'cpe_grid_predict_batch': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32] +
-                               [C.c_void_p] * 8),
-    'cpe_grid_assign_batch': (C.c_int32, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int32] * 5 +
-                              [C.c_void_p] * 10),
-    'cpe_undistort_map': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'cpe_remap_bilinear_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    'cpe_undistort_map_matlab': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    'cpe_remap_cubic_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    'cpe_matlab_prestep_batch': (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                             C.c_void_p, C.c_int64, C.c_void_p]),
-    'cpe_fit_cylinder_batch': (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p] +
-                               [C.c_void_p] * 7),
-}
+# by value: parameters, returns and structure fields; a pointer may point at any of _POINTEES or at a structure of the header
+_VALUES = {'int32_t': C.c_int32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64, 'size_t': C.c_size_t, 'double': C.c_double}
+_POINTEES = set(_VALUES) | {'void', 'char', 'uint8_t', 'int16_t', 'uint16_t', 'uint32_t', 'float'}
 
 
-class CpeDetectParams(C.Structure):
-    _fields_ = [('subpixel', C.c_int32), ('subpixel_window', C.c_int32), ('subpixel_step', C.c_double),
-                ('target', C.c_int32), ('flags', C.c_int32)]
+def _ctype(decl, structs, where):
+    """ctypes type of a parameter or return declaration: char * -> c_char_p, any other known pointer -> c_void_p (callers
+    pass data_ptr() ints, addressof, byref), known values -> theirs, void -> None; anything else raises"""
+    words = [t for t in re.findall(r'\w+|\*', decl) if t != 'const']
+    base, stars = (words or [''])[0], words.count('*')
+    if stars == 1 and (base in _POINTEES or base in structs):
+        return C.c_char_p if base == 'char' else C.c_void_p
+    if stars == 0 and base in _VALUES:
+        return _VALUES[base]
+    if words == ['void']:
+        return None
+    raise CpeError(f'{where}: no ctypes type for "{" ".join(decl.split())}"')
 
 
-DETECT_SKIP_DEBUG_PLANES = 1    # CpeDetectParams.flags (include/cpe.h)
+def _number(text):
+    """value of an int or float literal, optionally signed and parenthesised; None for anything else"""
+    text = re.sub(r'^\(\s*(.*?)\s*\)$', r'\1', text.strip())
+    for convert in (lambda t: int(t, 0), float):
+        try:
+            return convert(text)
+        except ValueError:
+            pass
+    return None
 
 
-class CpeDetectConstants(C.Structure):
-    """include/cpe.h: the reference's inline constants as this build was compiled with them (a report, not a setter)"""
-    _fields_ = [('blur_ksize', C.c_int32), ('hessian_sigma', C.c_double), ('sauvola_window', C.c_int32), ('sauvola_k', C.c_double),
-                ('sauvola_R', C.c_double), ('open_len', C.c_int32), ('clahe_clip', C.c_double), ('clahe_tiles', C.c_int32),
-                ('blob_thr_min', C.c_int32), ('blob_thr_step', C.c_int32), ('blob_thr_count', C.c_int32), ('blob_min_area', C.c_double),
-                ('blob_max_area', C.c_double), ('blob_min_dist', C.c_double), ('blob_min_repeat', C.c_int32),
-                ('disc_extra_radius', C.c_int32), ('spot_blur_ksize', C.c_int32), ('spot_threshold', C.c_int32),
-                ('spot_small_radius', C.c_int32), ('spot_small_add', C.c_int32), ('spot_large_add', C.c_int32), ('frag_patch', C.c_int32),
-                ('frag_min_pixels', C.c_int32), ('frag_max_pixels', C.c_int32), ('frag_kernel_base', C.c_int32),
-                ('index_blur_ksize', C.c_int32), ('poly_degree', C.c_int32), ('plane_threshold', C.c_int32),
-                ('plane_dilate_ksize', C.c_int32), ('max_points', C.c_int32), ('max_lines', C.c_int32), ('max_joints', C.c_int32),
-                ('max_groups_per_dir', C.c_int32), ('max_joints_per_group', C.c_int32)]
+def parse_header(text):
+    """-> (sigs, structs, consts) of a header written like include/cpe.h"""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)     # comments first: they hold commas, parentheses and names
+    structs = {}
+    for body, name in re.findall(r'typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;', text, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(';'))):
+            one = r'\w+\s*(?:\[\d+\])?'                             # a value type and its declarators: `int32_t a, win[2]`
+            m = re.fullmatch(rf'(\w+)\s+({one}(?:\s*,\s*{one})*)', decl)
+            if not m or m.group(1) not in _VALUES:
+                raise CpeError(f'struct {name}: no ctypes type for "{decl}"')
+            ctype = _VALUES[m.group(1)]
+            for field, dim in re.findall(r'(\w+)\s*(?:\[(\d+)\])?', m.group(2)):
+                fields.append((field, ctype * int(dim) if dim else ctype))
+        structs[name] = type(name, (C.Structure,), {'_fields_': fields})
+    sigs = {}
+    for ret, name, params in re.findall(r'^CPE_API\s+([^;()]*?)(cpe_\w+)\s*\(([^;()]*)\)\s*;', text, flags=re.M):
+        args = [] if params.strip() == 'void' else [_ctype(p, structs, name) for p in params.split(',')]
+        if None in args:
+            raise CpeError(f'{name}: a parameter of type void')
+        sigs[name] = (_ctype(ret, structs, name), args)
+    defines = re.findall(r'^[ \t]*#[ \t]*define[ \t]+CPE_(\w+)[ \t]+(\S.*)$', text, flags=re.M)
+    consts = {name: _number(value) for name, value in defines}
+    return sigs, structs, types.SimpleNamespace(**{k: v for k, v in consts.items() if v is not None})
+
+
+def _parse_own_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise CpeError(f'{HEADER_PATH}: the C header this binding is derived from cannot be read ({e})') from e
+
+
+_SIGS, _STRUCTS, const = _parse_own_header()
+globals().update(_STRUCTS)      # CpeDetectParams, CpeDetectConstants, CpeFitParams, ...: the header's typedef names
+
+MAXP, MAXL, PRED_MAXN = const.MAXP, const.MAXL, const.PRED_MAXN
+DETECT_SKIP_DEBUG_PLANES = const.DETECT_SKIP_DEBUG_PLANES                   # CpeDetectParams.flags
+CONSENSUS_MAX_HYP = const.CONSENSUS_MAX_HYP
+CONSENSUS_CONVERGED, CONSENSUS_SHRUNK = const.CONSENSUS_CONVERGED, const.CONSENSUS_SHRUNK   # flags of cpe_multi_frame_consensus_batch
+
+
+def const_group(prefix):
+    """{'binary': 0, 'hmask': 1, ...} for 'PLANE_': the header's CPE_<prefix>* constants by their lower-case remainder"""
+    return {k[len(prefix):].lower(): v for k, v in vars(const).items() if k.startswith(prefix)}
+
+
+TARGETS = const_group('TARGET_')
 
 
 def detect_constants(target='cylinder'):
-    """dict of the reference's inline constants as the kernels use them (cpe_detect_constants)"""
-    c = CpeDetectConstants()
-    check(load().cpe_detect_constants(dict(cylinder=0, plane=1)[target], C.byref(c)), 'cpe_detect_constants')
-    return {k: getattr(c, k) for k, _ in CpeDetectConstants._fields_}
-
-
-class CpeFitParams(C.Structure):
-    _fields_ = [('tol_x', C.c_double), ('tol_f', C.c_double), ('max_iter', C.c_int32), ('max_fun_evals', C.c_int32),
-                ('mode', C.c_int32), ('reserved', C.c_int32)]
-
-
-class CpeRansacParams(C.Structure):
-    _fields_ = [('hypotheses', C.c_int32), ('sample', C.c_int32), ('tau', C.c_double), ('seed', C.c_uint64),
-                ('frame0', C.c_uint64), ('hyp_iters', C.c_int32), ('reserved', C.c_int32)]
-
-
-class CpeMatchParams(C.Structure):
-    _fields_ = [('win_c', C.c_int32), ('win_r', C.c_int32), ('th', C.c_double), ('tau', C.c_double), ('hyp_iters', C.c_int32),
-                ('min_score', C.c_int32)]
-
-
-class CpePlaneFitParams(C.Structure):
-    _fields_ = [('tau', C.c_double), ('max_rounds', C.c_int32), ('reserved', C.c_int32)]
-
-
-class CpeProjectorModelParams(C.Structure):
-    _fields_ = [('tau', C.c_double), ('max_rounds', C.c_int32), ('maxiter', C.c_int32), ('min_spread', C.c_double),
-                ('tolx', C.c_double), ('tolf', C.c_double)]
-
-
-class CpeTableTriParams(C.Structure):
-    _fields_ = [('swap', C.c_int32), ('need_both', C.c_int32), ('min_sin', C.c_double), ('max_res', C.c_double)]
-
-
-class CpeFusedTriParams(C.Structure):
-    _fields_ = [('swap', C.c_int32), ('need_both', C.c_int32), ('min_sin', C.c_double), ('sigma_px', C.c_double),
-                ('sigma_mm', C.c_double), ('max_res', C.c_double), ('max_px', C.c_double)]
-
-
-class CpeIndexShiftParams(C.Structure):
-    _fields_ = [('win', C.c_int32 * 2), ('tau', C.c_double), ('min_score', C.c_int32), ('swap', C.c_int32)]
-
-
-class CpeRelabelParams(C.Structure):
-    _fields_ = [('swap', C.c_int32), ('min_pts', C.c_int32), ('merge_frac', C.c_double), ('dir', C.c_int32 * 2)]
-
-
-class CpeGridPredictParams(C.Structure):
-    _fields_ = [('win_lo', C.c_int32 * 2), ('win_hi', C.c_int32 * 2), ('min_cos', C.c_double), ('img_w', C.c_int32), ('img_h', C.c_int32)]
-
-
-class CpeGridAssignParams(C.Structure):
-    _fields_ = [('tau_px', C.c_double), ('ratio', C.c_double), ('swap', C.c_int32), ('reserved', C.c_int32)]
-
-
-PRED_MAXN = 4096                                                                    # CPE_PRED_MAXN
-
-
-class CpeConsensusParams(C.Structure):
-    _fields_ = [('tau', C.c_double), ('max_hyp', C.c_int32), ('max_rounds', C.c_int32), ('min_inliers', C.c_int32)]
-
-
-CONSENSUS_MAX_HYP = 4096
-CONSENSUS_CONVERGED, CONSENSUS_SHRUNK = 1, 2    # flags of cpe_multi_frame_consensus_batch (include/cpe.h)
-
-MAXP = 2048
-MAXL = 256
+    """dict of the reference's inline constants as the kernels use them (cpe_detect_constants: a report, not a setter)"""
+    c = _STRUCTS['CpeDetectConstants']()
+    check(load().cpe_detect_constants(TARGETS[target], C.byref(c)), 'cpe_detect_constants')
+    return {k: getattr(c, k) for k, _ in c._fields_}
 
 
 def load():
@@ -204,6 +127,9 @@ def load():
             raise CpeError(f'{SO_PATH} not found: run `python -c "import __graft_entry__ as g; g.build()"` '
                            '(the product path has no CPU fallback)')
         lib = C.CDLL(SO_PATH)
+        built = lib.cpe_version()       # int32_t (void): ctypes' defaults fit
+        if built != const.VERSION:      # the one way left for argtypes and code to disagree: refuse it
+            raise CpeError(f'{SO_PATH} is version {built}, {HEADER_PATH} declares {const.VERSION}: rebuild the library')
         for name, (res, args) in _SIGS.items():
             fn = getattr(lib, name)
             fn.restype = res
@@ -235,7 +161,4 @@ def profile_report():
 
 def declared_symbols():
     """names declared with CPE_API in include/cpe.h"""
-    import re
-    hdr = os.path.join(_HERE, '..', 'include', 'cpe.h')
-    txt = open(hdr).read()
-    return sorted(set(re.findall(r'CPE_API[^;(]*?\b(cpe_\w+)\s*\(', txt)))
+    return sorted(_SIGS)

@@ -337,7 +337,7 @@ def fit_multi_frame_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=None, group
         x0 = torch.as_tensor(x0, dtype=torch.float64).to(dev).reshape(G, 6).contiguous()
     params = _tol_params(**tol)
     if method == 'lm':
-        params.mode = 1                                           # CPE_FIT_LM
+        params.mode = _lib.const.FIT_LM
     out = dict(x0=torch.empty((G, 6), dtype=torch.float64, device=dev), x=torch.empty((G, 6), dtype=torch.float64, device=dev),
                T=torch.empty((G, 16), dtype=torch.float64, device=dev), fvals=torch.empty((G, 2), dtype=torch.float64, device=dev),
                iters=torch.empty((G, 2), dtype=torch.int32, device=dev), n_used=torch.empty(G, dtype=torch.int32, device=dev),
@@ -376,7 +376,7 @@ def fit_multi_frame_consensus_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=N
     dev, n = pts3.device, cnt.shape[0]
     pts3, cnt, cyl_raw, TAGV, frame_ok, gs, G = _frame_tables(pts3, cnt, cyl_raw, angles, frame_ok, group_start)
     params = _tol_params(**tol)
-    params.mode = 1                                               # CPE_FIT_LM
+    params.mode = _lib.const.FIT_LM
     cons = _lib.CpeConsensusParams(float(tau), int(max_hyp), int(max_rounds), int(min_inliers))
     ws = torch.empty(max(1, L.cpe_multi_frame_consensus_workspace_bytes(G, cons.max_hyp)), dtype=torch.uint8, device=dev)
     f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
@@ -470,7 +470,7 @@ def estimate_frame_angles_gpu(pts3, cnt, cyl_raw, T, radius, pose_index=None, a0
     if a0 is not None:
         a0 = torch.as_tensor(a0, dtype=torch.float64).to(dev).reshape(n, 2).contiguous()
     params = _tol_params(**tol)
-    params.mode = 1                                               # CPE_FIT_LM
+    params.mode = _lib.const.FIT_LM
     f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
     out = dict(angles0=f64(n, 2), angles=f64(n, 2), fvals=f64(n, 2), iters=torch.empty((n, 2), dtype=torch.int32, device=dev),
                TAGV=f64(n, 16), Tcyl=f64(n, 16), status=torch.empty(n, dtype=torch.int32, device=dev))

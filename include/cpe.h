@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 125  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 126  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -58,7 +58,7 @@ extern "C" {
                              120: cpe_index_shift_batch; 121: cpe_multi_frame_consensus_batch,
                              cpe_multi_frame_consensus_workspace_bytes; 122: cpe_fused_triangulate_batch;
                              123: cpe_grid_relabel_batch; 124: cpe_grid_predict_batch, cpe_grid_assign_batch;
-                             125: cpe_debug_ccl_tiles) */
+                             125: cpe_debug_ccl_tiles; 126: cpe_debug_state_field) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -315,6 +315,11 @@ CPE_API int32_t cpe_detect_workspace_plane(int32_t n, int32_t h, int32_t w, int3
 CPE_API int32_t cpe_debug_workspace_buffer(int32_t n, int32_t h, int32_t w, int32_t index, char *name_out, size_t name_cap,
                                            size_t *offset, size_t *bytes_per_frame, int32_t *overlay, int32_t *side,
                                            int32_t *public_plane);
+
+/* Row `index` (0, 1, ...; CPE_ERR_ARG past the last) of the per-frame state record behind CPE_PLANE_STATE (csrc/cpe_dev.h,
+ * CPE_STATE_FIELDS), in the order of its 32-bit words: the field's name (at most name_cap - 1 characters), the words it takes
+ * (an array of 4 takes 4) and whether they hold floats (else int32).  Host code only: no GPU call.  Test / debugging aid. */
+CPE_API int32_t cpe_debug_state_field(int32_t index, char *name_out, size_t name_cap, int32_t *words, int32_t *is_float);
 
 /* One stand-alone connected-component pass (cv2.connectedComponents / the front end of cv2.findContours,
  * util_cylinder.py:28,161,1817,1883,1968) over img u8[n,h,w]: set = (img > thr) != invert, 8- or 4-connected;

@@ -129,9 +129,33 @@ def test_structure(cpe, shape):
         assert len({min(r['off'] for r in rows if r['name'] in s) for s in sides.values()}) == 1
 
 
+# the words of the state record by the names tests and tools read them under (DetectWorkspace.state()), in order
+STATE_NAMES = ['status', 'rect0', 'rect1', 'rect2', 'rect3', 'r0', 'spot0', 'spot1', 'spot2', 'spot3', 'n_roots',
+               'n_comps', 'n_joints_all', 'n_joints', 'n_blobs', 'n_groups', 'n_groups_prev', 'n_kp', 'n_verts',
+               'n_dists', 'best_comp', 'n_seg0', 'n_seg1', 'gang0', 'gang1', 'glen0', 'glen1', 'n_rows', 'n_cols',
+               'overflow', 'hull_n', 'crect0', 'crect1', 'crect2', 'crect3', 'nrect0', 'nrect1', 'nrect2', 'nrect3',
+               'n_roots_p', 'n_roots_s', 'spot_fail', 'srect0', 'srect1', 'srect2', 'srect3']
+
+
 def test_state_fields_cover_the_record(cpe):
+    fields = cpe.api.state_fields()
+    assert len(STATE_NAMES) == 46 and [k for k, _ in fields] == STATE_NAMES == cpe.api._STATE_FIELDS
     state = [r for r in listing(1, 64, 64) if r['name'] == 'state']
-    assert len(state) == 1 and len(cpe.api._STATE_FIELDS) * 4 == state[0]['per']
+    assert len(state) == 1 and len(fields) * 4 == state[0]['per']
+    assert [k for k, is_float in fields if is_float] == ['gang0', 'gang1', 'glen0', 'glen1']
+    L = cpe.lib.load()
+    name = C.create_string_buffer(64)
+    words, is_float = C.c_int32(), C.c_int32()
+    rows = 0
+    while L.cpe_debug_state_field(rows, name, len(name), C.byref(words), C.byref(is_float)) == 0:
+        rows += 1
+    assert rows == 28
+    for index in (rows, 46, -1):
+        assert L.cpe_debug_state_field(index, name, len(name), C.byref(words), C.byref(is_float)) == CPE_ERR_ARG
+    assert L.cpe_debug_state_field(0, name, 0, C.byref(words), C.byref(is_float)) == CPE_ERR_ARG
+    short = C.create_string_buffer(4)   # a name longer than the buffer is cut, and still terminated
+    assert L.cpe_debug_state_field(0, short, len(short), C.byref(words), C.byref(is_float)) == 0 and short.value == b'sta'
+    assert (words.value, is_float.value) == (1, 0)
 
 
 def test_listing_rejects_bad_arguments(cpe):
