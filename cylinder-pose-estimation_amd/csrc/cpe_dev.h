@@ -230,6 +230,25 @@ template <int S = 1> __device__ __forceinline__ void uf_unite(int *L, int a, int
         a = old;
     }
 }
+// uf_unite on the bright forest of the blob sweep (node = {parent, merge-history word}, history 0xFFFFFFFF while the node is a
+// root): the thread whose link wins also writes "absorbed by b at step `step`", b | step << 24, in the same 64-bit
+// compare-and-swap of the whole node {a, never} -> {b, history}.  Only roots are ever swapped and the pointer-jumping stores of
+// uf_find_c only touch the parent word of non-roots, so the two never meet in a node.  A failed swap writes nothing: a is no
+// longer a root, and the union goes on from the parent the swap returned.
+__device__ __forceinline__ void uf_unite_hist(int *L, int a, int b, int step)
+{
+    for (;;) {
+        a = uf_find_c<2>(L, a);
+        b = uf_find_c<2>(L, b);
+        if (a == b) return;
+        if (a < b) { int t = a; a = b; b = t; }
+        const unsigned long long never = (unsigned long long)(unsigned)a | (0xFFFFFFFFull << 32);
+        const unsigned long long link = (unsigned long long)(unsigned)b | ((unsigned long long)((unsigned)b | ((unsigned)step << 24)) << 32);
+        const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long *>(L + 2 * (size_t)a), never, link);
+        if (old == never) return;
+        a = (int)(unsigned)old;
+    }
+}
 
 // ---------------------------------------------------------------- Suzuki border following (OpenCV icvFetchContour)
 // Pred(x, y) -> bool : pixel is non-zero (false outside the image).

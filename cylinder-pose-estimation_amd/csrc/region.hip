@@ -1457,8 +1457,11 @@ __global__ __launch_bounds__(MG_NT) void k_blob_merge(FrameState *__restrict__ s
 // Enclosed-hole pixel totals of the bright components of every threshold, after both sweeps:
 //   encl[component (at that threshold) of the pixel west of the hole's first pixel] += |hole|
 // The bright forest of step t is read back from its merge history: an entry that stopped being a root at step j
-// carries (hpar = the root that absorbed it, htime = j); following the links with htime <= t from any pixel of the
-// step-t bright set ends at its root of step t.  One workgroup per frame walks the 17 thresholds; the totals live in
+// carries (hpar = the entry it was linked under, htime = j); following the links with htime <= t from any pixel of the
+// step-t bright set ends at its root of step t.  (hpar was a root when the link was made, so its own link, if any, is of
+// step j or later: the times never fall along a chain, every entry on it up to the first with htime > t -- or never
+// absorbed -- had joined that entry's component by the end of step t, and that entry was still a root then.  Several links
+// of one step may follow each other: a absorbed by b, b by c.)  One workgroup per frame walks the 17 thresholds; the totals live in
 // the accumulator plane only between the two barriers of a threshold (atomics both ways: no stale L1 lines).
 #define ENC_NT 1024
 __global__ __launch_bounds__(ENC_NT) void k_enclosed_all(const int2 *__restrict__ hl, int2 *__restrict__ bl, const int *__restrict__ sw,
@@ -1507,7 +1510,9 @@ static_assert(NTHR == 17, "sweep_level (cpe_dev.h) holds the bucket count");
 constexpr int BK_CHUNK = 8192;    // pixels per workgroup of the two bucket passes
 
 // The scatter pass also gives every listed pixel its first node of the bright forest: {the first pixel of its run of one
-// bucket inside its aligned chunk of 64 consecutive pixels, never absorbed}.  (Round 2 wrote these entries bucket by bucket,
+// bucket inside its aligned chunk of 64 consecutive pixels, history}; history = never absorbed for the run's first pixel,
+// "joined the first pixel at the bucket's bright step NTHR - bucket" for the others (what k_enclosed_all follows; nothing
+// writes a run member's history again).  (Round 2 wrote these entries bucket by bucket,
 // one step ahead of their use, through the lists: 2 % of the rectangle per pass, one 64-byte line per entry; here the stores
 // of a wavefront fall into a few lines.)
 // A thread owns four consecutive pixels (one dword of the image) in each of its BK_CHUNK / 1024 rounds, so a 64-pixel chunk is
@@ -1602,7 +1607,10 @@ __global__ __launch_bounds__(256) void k_bk_pass(const uint8_t *__restrict__ img
             int2 *node = reinterpret_cast<int2 *>(bright) + fN + i0;
 #pragma unroll
             for (int j = 0; j < 4; j++)
-                if (l[j] > 0) node[j] = make_int2(first[j] >= 0 ? first[j] : carry, -1);
+                if (l[j] > 0) {   // a run's first pixel: never absorbed; its other pixels: joined it at the bucket's bright step
+                    const int head = first[j] >= 0 ? first[j] : carry;
+                    node[j] = make_int2(head, head == i0 + j ? -1 : head | ((NTHR - l[j]) << 24));
+                }
             // rank inside this workgroup's share of the bucket: one LDS atomic per run of one bucket among the four pixels
             // (all of a thread's atomics go out before the first answer is waited for)
             int rk[4];
@@ -1671,7 +1679,7 @@ inline unsigned sw_grid(int n, int per_frame) { return (unsigned)(n * per_frame)
 template <bool DARK>
 __device__ __forceinline__ void sw_unite_body(const SwBlock vb, const uint32_t *__restrict__ bits, int pm, int po, int h, int w, int bucket,
                                               const FrameState *__restrict__ st, const int *__restrict__ sw,
-                                              const int *__restrict__ bk, int *__restrict__ P)
+                                              const int *__restrict__ bk, int *__restrict__ P, int step)
 {
     const size_t N = (size_t)h * w, f = vb.f;
     const int *S = sw + f * SW_STRIDE;
@@ -1691,6 +1699,11 @@ __device__ __forceinline__ void sw_unite_body(const SwBlock vb, const uint32_t *
     // k_sw_new's init pass) share their unions: each lane looks up the roots of its own partners, the run takes the
     // smallest of them, and only the run's first lane links the run to it.  Lane by lane the same unions were one
     // memory-side atomic per pixel -- the lanes of a wavefront all read "not linked yet" before any of them links.
+    // The bright forest's links carry their step (uf_unite_hist, cpe_dev.h): the merge history is written where a link is made.
+    auto unite = [&](int a, int b) {
+        if constexpr (DARK) uf_unite(Pf, a, b);
+        else uf_unite_hist(Pf, a, b, step);
+    };
     const int lane = threadIdx.x & 63;
     for (int e0 = vb.bx * 256; e0 < nb; e0 += vb.gx * 256) {   // wave-uniform: the shuffles below need every lane
         const int e = e0 + threadIdx.x;
@@ -1737,7 +1750,7 @@ __device__ __forceinline__ void sw_unite_body(const SwBlock vb, const uint32_t *
         int mine = INT_MAX;
 #pragma unroll
         for (int k = 0; k < (DARK ? 4 : 8); k++)
-            if (k < np) { pr[k] = uf_find<FS>(Pf, pr[k]); mine = min(mine, pr[k]); }   // read-only walk: k_sw_new flattens every step, the paths are short, and pointer-jumping stores are fabric writes
+            if (k < np) { pr[k] = uf_find<FS>(Pf, pr[k]); mine = min(mine, pr[k]); }   // read-only walk: k_sw_new shortens the paths that leave a 64-byte line every step, and pointer-jumping stores are fabric writes
         // smallest partner root of the run: segmented min over the lanes that share a first lane
         const unsigned long long starts = __ballot(i >= 0 && !prel);
         const int hl = i >= 0 ? 63 - __clzll((long long)(starts & ((lane == 63) ? ~0ull : ((2ull << lane) - 1ull)))) : -1 - lane;
@@ -1749,10 +1762,10 @@ __device__ __forceinline__ void sw_unite_body(const SwBlock vb, const uint32_t *
         }
         const int runmin = __shfl(m, hl < 0 ? lane : hl, 64);
         if (i >= 0 && runmin != INT_MAX) {
-            if (lane == hl) uf_unite<FS>(Pf, i, runmin);
+            if (lane == hl) unite(i, runmin);
 #pragma unroll
             for (int k = 0; k < (DARK ? 4 : 8); k++)
-                if (k < np && pr[k] != runmin) uf_unite<FS>(Pf, pr[k], runmin);   // the run joins several components: rare
+                if (k < np && pr[k] != runmin) unite(pr[k], runmin);   // the run joins several components: rare
         }
     }
 }
@@ -1807,8 +1820,8 @@ __device__ __forceinline__ void sw_new_body(const SwBlock vb, int h, int w, int 
 {
     // The bright forest's node is {parent, history word}: history = (root that absorbed the entry) | (step << 24), 0xFFFFFFFF
     // while the entry has never been absorbed -- what k_enclosed_all follows to read the forest as it was at an earlier
-    // step.  One 8-byte store per new pixel where round 2 wrote three planes (parent, absorbing root, step), and the
-    // "never" value comes with the entry's first store instead of a memset of a plane.
+    // step.  The history is written once, where the link is made (uf_unite_hist in the unite pass; k_bk_pass for the members
+    // of a pre-linked run): this pass only shortens parent paths.
     const size_t N = (size_t)h * w, f = vb.f;
     const int lane = threadIdx.x & 63;
     const int *S = sw + f * SW_STRIDE;
@@ -1825,15 +1838,22 @@ __device__ __forceinline__ void sw_new_body(const SwBlock vb, int h, int w, int 
     for (int e0 = vb.bx * 256; e0 < nb; e0 += vb.gx * 256) {
         const int e = e0 + threadIdx.x;
         const bool isnew = e < nb;
-        int i = -1, root = -1;
+        int i = -1, root = -1, hop = -1;
         if (isnew) {
             i = list[e];
-            root = uf_find<FS>(Pf, i);
-            if (root != i) {
-                if (DARK) Pf[i] = root;
-                else *reinterpret_cast<int2 *>(Pf + 2 * (size_t)i) = make_int2(root, root | (epoch << 24));   // joined `root` at this step
-            }
+            root = hop = uf_load<FS>(Pf, i);
+            for (int p; (p = uf_load<FS>(Pf, root)) != root;) root = p;
         }
+        // Flatten only where the store shortens a path that leaves the L2: not when the first hop already is the root (a run's
+        // first pixel that its union linked straight to a live root), and not for a run member whose first pixel shares its
+        // 64-byte line of the node array -- that hop comes with the member's own line, the store would be a fabric write.
+        // (member: the previous entry is its left neighbour, as in sw_unite_body; where the two lie in different 64-pixel
+        //  chunks the pixel is a run's first one that is taken for a member -- it then keeps a two-hop path, nothing else)
+        // (measured and dropped: the member's store kept -- no faster; no bright flattening at all -- the bright unions 7 %
+        //  slower on longer walks: DESIGN.md section 3.2)
+        const bool member = sw_prelinked(i, w, lane) &&
+                            ((reinterpret_cast<uintptr_t>(Pf + FS * (size_t)i) ^ reinterpret_cast<uintptr_t>(Pf + FS * (size_t)hop)) >> 6) == 0;
+        if (isnew && hop != root && !member) Pf[FS * (size_t)i] = root;
         bool is_root = isnew && root == i;
         if (DARK) {
             is_root = is_root && touch[f * N + i] != (uint8_t)epoch;
@@ -1886,9 +1906,8 @@ __device__ __forceinline__ void sw_old_body(const SwBlock vb, const int *__restr
                 else atomicAdd(&acc[f * N + uf_find_c(Pf, r)], acc[f * N + r]);
             }
         } else {
-            keep = uf_load<FS>(Pf, r) == r;
+            keep = uf_load<FS>(Pf, r) == r;          // (an absorbed root got its history word from the link that absorbed it)
             if (keep) acc[f * N + r] = 0;
-            else Pf[2 * (size_t)r + 1] = uf_find_c<FS>(Pf, r) | (epoch << 24);   // absorbed at this step
         }
     }
     sw_append(keep, r, &sw[f * SW_STRIDE + cnt_base + slot], lists + f * (size_t)pool + loff, &st[f], pool - loff);
@@ -1946,13 +1965,14 @@ __global__ __launch_bounds__(256) void k_sw_unite_snap(int n, int g_unite, int g
                                                        const uint32_t *__restrict__ bits, int pm, int po, int h, int w, int bucket,
                                                        const FrameState *__restrict__ st, const int *__restrict__ bk, int *__restrict__ P,
                                                        int2 *__restrict__ lists, int *__restrict__ sw, int cnt_base, int snap_slot,
-                                                       const int *__restrict__ acc, int2 *__restrict__ trace, FrameState *__restrict__ stw)
+                                                       const int *__restrict__ acc, int2 *__restrict__ trace, FrameState *__restrict__ stw,
+                                                       int step /* bright: the step the links are made at */)
 {
     SwBlock vb = sw_block(n, g_unite + g_snap);
     if (vb.f < 0) return;
     if (vb.bx < g_unite) {
         vb.gx = g_unite;
-        sw_unite_body<DARK>(vb, bits, pm, po, h, w, bucket, st, (const int *)sw, bk, P);
+        sw_unite_body<DARK>(vb, bits, pm, po, h, w, bucket, st, (const int *)sw, bk, P, step);
     } else {
         vb.bx -= g_unite; vb.gx = g_snap;
         sw_snap_body(vb, lists, sw, cnt_base, snap_slot, h, w, acc, trace, stw);
@@ -2708,7 +2728,7 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
             // unions of the pixels that join at this threshold | totals of the previous threshold frozen
             CPE_KLAUNCH(k_sw_unite_snap<true>, dim3(sw_grid(n_grid, g_bk + g_list)), dim3(256), 0, ds, nx, g_bk, g_list, (const uint32_t *)B.bits, k, k - 1, h, w,
                         k, (const FrameState *)st, (const int *)B.bk, B.lab, B.hl, B.sw, (int)SW_NH, k - 1,
-                        (const int *)B.cnt, B.tl, st);
+                        (const int *)B.cnt, B.tl, st, 0);
             CPE_KLAUNCH(k_sw_touch, dim3(frame_waves(4 * n, 2, 8), n), dim3(256), 0, ds, (const uint8_t *)B.cl, n, h, w, thr,
                         (const FrameState *)st, (const int *)B.lab, B.touch, epoch);
             CPE_KLAUNCH(k_sw_new_old<true>, dim3(sw_grid(n_grid, g_bk + g_list)), dim3(256), 0, ds, nx, g_bk, g_list, h, w, k, k + 1 < NTHR ? k + 1 : 0, st,
@@ -2735,7 +2755,7 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
     for (int j = 0; j < NTHR; j++) {
         const int k = NTHR - 1 - j;   // members: v > 50 + 10 k (plane k); members before this step: v > 60 + 10 k (plane k + 1; none at j = 0)
         CPE_KLAUNCH(k_sw_unite_snap<false>, dim3(sw_grid(n_grid, g_bk)), dim3(256), 0, s, nx, g_bk, 0, (const uint32_t *)B.bits, k, j == 0 ? -1 : k + 1, h, w, k + 1,
-                    (const FrameState *)st, (const int *)B.bk, B.lab2, (int2 *)nullptr, B.sw, 0, 0, (const int *)nullptr, (int2 *)nullptr, st);
+                    (const FrameState *)st, (const int *)B.bk, B.lab2, (int2 *)nullptr, B.sw, 0, 0, (const int *)nullptr, (int2 *)nullptr, st, j);
         const int go = j > 0 ? g_list : 0;   // survivors of the previous (higher) threshold
         CPE_KLAUNCH(k_sw_new_old<false>, dim3(sw_grid(n_grid, g_bk + go)), dim3(256), 0, s, nx, g_bk, go, h, w, k + 1, k, st, (const int *)B.bk, B.lab2, B.cnt2,
                     (const uint8_t *)nullptr, j, B.bl, B.sw, (int)SW_NL, k,
