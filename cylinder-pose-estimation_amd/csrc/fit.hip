@@ -4929,3 +4929,236 @@ extern "C" int32_t cpe_grid_assign_batch(const double *xy, const int32_t *id, co
     CPE_CHECK_LAUNCH("k_grid_assign");
     return CPE_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// BUILD-DEFINED (include/cpe.h cpe_mono_shift_batch, whose numbered rule this follows): the grid-index shift of a ONE-camera
+// frame.  A point of one ray and two planes is over-determined by one, so the two residuals of cpe_table_triangulate_batch
+// measure whether the pair of indices is right: per candidate (d0, d1), the points whose both residuals stay below tau vote.
+// k_mono_vote: one wavefront per (frame, d0), lane l takes points l, l + 64, ...  The ray and the plane of component 0 (one
+// plane per point, read through L2 as in k_table_triangulate) are made once per point; the family of component 1, which the
+// inner loop over d1 reads 2 win1 + 1 times per point, is staged in LDS (at most 256 planes and statuses, 9 KB).  The cut is
+// tri_cut itself, so a vote is decided by the bits cpe_table_triangulate_batch would write; the terms of component 0 are
+// the same expressions in every unrolled d1 and are computed once.  The counts are ballots, uniform over the wavefront, behind
+// a loop unrolled over the compile-time 17 candidates and predicated on |d1| <= win1 (no indexed register array).
+// k_mono_pick: one wavefront per frame ranks the at most 289 counts by 64-bit keys, writes the first top_k, and walks the points
+// once more for the residuals at the winner and at (0, 0).
+namespace {
+
+constexpr int MONO_SLOTS = (SHIFT_NC * SHIFT_NC + 63) / 64;       // candidates a lane of k_mono_pick holds
+
+// step 3 for one point and one candidate: both planes cut with the ray; -> the point counts; rs = res[0], res[1]
+__device__ __forceinline__ bool mono_counts(const double *o, const double *d, const double (*pl)[4], double min_sin2, double tau, double *rs)
+{
+    double X[3];
+    bool early;
+    rs[0] = 0; rs[1] = 0;
+    return tri_cut(o, d, pl, 3, true, 1, min_sin2, 0.0, X, rs, early) && fabs(rs[0]) < tau && fabs(rs[1]) < tau;
+}
+
+// the plane of line r of the family that starts at line `fam` of the table -> usable; pl is loaded for a usable plane only
+__device__ __forceinline__ bool mono_plane(const double *__restrict__ P, const int *__restrict__ line_status, size_t fam, int L, int r,
+                                           double *pl)
+{
+    if (r < 0 || r >= L || line_status[fam + r] != CPE_ST_OK) return false;
+#pragma unroll
+    for (int a = 0; a < 4; a++) pl[a] = P[(fam + r) * 4 + a];
+    return true;
+}
+
+__global__ __launch_bounds__(64) void k_mono_vote(const double *__restrict__ xy, const int *__restrict__ id, const int *__restrict__ cnt,
+                                                  const double *__restrict__ K, const double *__restrict__ Tc,
+                                                  const double *__restrict__ P, const int *__restrict__ line_status, int lo, int hi,
+                                                  int win0, int win1, int swap, double min_sin2, double tau, int *__restrict__ o_scores)
+{
+    __shared__ double sP[CPE_MAXL * 4];
+    __shared__ int sS[CPE_MAXL];
+    const int n0 = 2 * win0 + 1, n1 = 2 * win1 + 1;       // win0, win1 in 0..SHIFT_W, checked by the host
+    const int f = blockIdx.x / n0, d0 = (int)(blockIdx.x % n0) - win0, lane = threadIdx.x;
+    const int n = min(max(cnt[f], 0), MAXP);
+    const int L = hi - lo + 1;                            // 1..CPE_MAXL, checked by the host
+    const size_t base = (size_t)f * MAXP;
+    const size_t fam0 = (size_t)(swap * L), fam1 = (size_t)((1 ^ swap) * L);
+    for (int i = lane; i < 4 * L; i += 64) sP[i] = P[fam1 * 4 + i];
+    for (int i = lane; i < L; i += 64) sS[i] = line_status[fam1 + i];
+    __syncthreads();
+    TriCam cam;
+    tri_cam(K, Tc, cam);
+    // rel = id - lo of a point that can count at all lies in [-win, L - 1 + win]: tested in 64 bits, before any addition
+    const long long hi0 = (long long)(L - 1 + win0), hi1 = (long long)(L - 1 + win1);
+    int sc[SHIFT_NC];
+#pragma unroll
+    for (int j = 0; j < SHIFT_NC; j++) sc[j] = 0;
+    for (int k0p = 0; k0p < n; k0p += 64) {
+        const int k = k0p + lane;
+        bool ok = k < n;
+        double d[3] = {0, 0, 1}, pl[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        int rel1 = 0;
+        if (ok) {
+            const double x = xy[(base + k) * 2], y = xy[(base + k) * 2 + 1];
+            const long long rl0 = (long long)id[(base + k) * 2] - (long long)lo, rl1 = (long long)id[(base + k) * 2 + 1] - (long long)lo;
+            ok = isfinite(x) && isfinite(y) && rl0 >= -(long long)win0 && rl0 <= hi0 && rl1 >= -(long long)win1 && rl1 <= hi1;
+            if (ok) ok = mono_plane(P, line_status, fam0, L, (int)rl0 + d0, pl[0]);
+            if (ok) {
+                tri_ray(cam, x, y, d);
+                rel1 = (int)rl1;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < SHIFT_NC; j++) {
+            if (abs(j - SHIFT_W) > win1) continue;        // (uniform)
+            const int r1 = rel1 + (j - SHIFT_W);
+            bool hit = false;
+            if (ok && r1 >= 0 && r1 < L && sS[r1] == CPE_ST_OK) {
+                double rs[2];
+#pragma unroll
+                for (int a = 0; a < 4; a++) pl[1][a] = sP[4 * r1 + a];
+                hit = mono_counts(cam.o, d, pl, min_sin2, tau, rs);
+            }
+            sc[j] += __popcll(__ballot(hit));
+        }
+    }
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < SHIFT_NC; j++)
+        if (lane == j) mine = sc[j];
+    if (lane >= SHIFT_W - win1 && lane <= SHIFT_W + win1)
+        o_scores[((size_t)f * n0 + (size_t)(d0 + win0)) * n1 + (lane - (SHIFT_W - win1))] = mine;
+}
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long u = __shfl_xor(v, off, 64);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(64) void k_mono_pick(const double *__restrict__ xy, const int *__restrict__ id, const int *__restrict__ cnt,
+                                                  const double *__restrict__ K, const double *__restrict__ Tc,
+                                                  const double *__restrict__ P, const int *__restrict__ line_status, int lo, int hi,
+                                                  int win0, int win1, int swap, double min_sin2, double tau, int min_score, int top_k,
+                                                  const int *__restrict__ scores, int *__restrict__ o_cand, int *__restrict__ o_cand_score,
+                                                  int *__restrict__ o_score, double *__restrict__ o_rms, int *__restrict__ o_flags)
+{
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int n1 = 2 * win1 + 1, C = (2 * win0 + 1) * n1;                 // 1..SHIFT_NC^2
+    const int *sf = scores + (size_t)f * C;
+    // the order of step 5 as one integer, smaller first: 2 MAXP - score | |d0| + |d1| | |d0| | d0 + 8 | d1 + 8; every candidate
+    // has a key of its own and none is 0
+    unsigned long long key[MONO_SLOTS];
+#pragma unroll
+    for (int i = 0; i < MONO_SLOTS; i++) {
+        const int c = lane + 64 * i;
+        key[i] = ~0ull;
+        if (c < C) {
+            const int d0 = c / n1 - win0, d1 = c % n1 - win1;
+            const unsigned lowk = ((unsigned)(abs(d0) + abs(d1)) << 24) | ((unsigned)abs(d0) << 16) | ((unsigned)(d0 + SHIFT_W) << 8) |
+                                  (unsigned)(d1 + SHIFT_W);
+            key[i] = ((unsigned long long)(2 * MAXP - sf[c]) << 32) | lowk;
+        }
+    }
+    int best = 0, second = 0, bd0 = 0, bd1 = 0;
+    unsigned long long last = 0;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        if (r >= max(top_k, 2)) break;                                     // (uniform; top_k in 1..8, checked by the host)
+        unsigned long long m = ~0ull;
+#pragma unroll
+        for (int i = 0; i < MONO_SLOTS; i++)
+            if (key[i] > last && key[i] < m) m = key[i];
+        m = wave_min_u64(m);
+        const bool any = m != ~0ull;
+        const int s = any ? 2 * MAXP - (int)(m >> 32) : -1;
+        const int d0 = any ? (int)((m >> 8) & 0xff) - SHIFT_W : 0, d1 = any ? (int)(m & 0xff) - SHIFT_W : 0;
+        if (r == 0) { best = s; bd0 = d0; bd1 = d1; }
+        if (r == 1) second = any ? s : 0;
+        if (lane == 0 && r < top_k) {
+            o_cand[((size_t)f * top_k + r) * 2] = d0; o_cand[((size_t)f * top_k + r) * 2 + 1] = d1;
+            o_cand_score[(size_t)f * top_k + r] = s;
+        }
+        if (any) last = m;
+    }
+    const int at0 = sf[win0 * n1 + win1];
+    // the counted points' squared residuals at the winner and at (0, 0)
+    const int n = min(max(cnt[f], 0), MAXP);
+    const int L = hi - lo + 1;
+    const size_t base = (size_t)f * MAXP;
+    const size_t fam0 = (size_t)(swap * L), fam1 = (size_t)((1 ^ swap) * L);
+    const long long hi0 = (long long)(L - 1 + win0), hi1 = (long long)(L - 1 + win1);
+    TriCam cam;
+    tri_cam(K, Tc, cam);
+    double sa = 0.0, s0 = 0.0;
+    int ca = 0, c0 = 0, usable = 0;
+    for (int k = lane; k < n; k += 64) {
+        const double x = xy[(base + k) * 2], y = xy[(base + k) * 2 + 1];
+        if (!(isfinite(x) && isfinite(y))) continue;
+        usable++;
+        const long long rl0 = (long long)id[(base + k) * 2] - (long long)lo, rl1 = (long long)id[(base + k) * 2 + 1] - (long long)lo;
+        if (rl0 < -(long long)win0 || rl0 > hi0 || rl1 < -(long long)win1 || rl1 > hi1) continue;
+        double d[3], pl[2][4], rs[2];
+        tri_ray(cam, x, y, d);
+        if (mono_plane(P, line_status, fam0, L, (int)rl0 + bd0, pl[0]) && mono_plane(P, line_status, fam1, L, (int)rl1 + bd1, pl[1]) &&
+            mono_counts(cam.o, d, pl, min_sin2, tau, rs)) {
+            sa = sa + (rs[0] * rs[0] + rs[1] * rs[1]);
+            ca++;
+        }
+        if (mono_plane(P, line_status, fam0, L, (int)rl0, pl[0]) && mono_plane(P, line_status, fam1, L, (int)rl1, pl[1]) &&
+            mono_counts(cam.o, d, pl, min_sin2, tau, rs)) {
+            s0 = s0 + (rs[0] * rs[0] + rs[1] * rs[1]);
+            c0++;
+        }
+    }
+    sa = wave_sum(sa); s0 = wave_sum(s0); ca = wave_sum_i(ca); c0 = wave_sum_i(c0); usable = wave_sum_i(usable);
+    if (lane == 0) {
+        int flags = 0;
+        if ((win0 > 0 && abs(bd0) == win0) || (win1 > 0 && abs(bd1) == win1)) flags |= CPE_SHIFT_FLAG_EDGE;
+        if (best < min_score || best < 2 * second) flags |= CPE_SHIFT_FLAG_WEAK;
+        o_score[4 * (size_t)f] = best; o_score[4 * (size_t)f + 1] = second; o_score[4 * (size_t)f + 2] = at0; o_score[4 * (size_t)f + 3] = usable;
+        o_rms[2 * (size_t)f] = ca > 0 ? sqrt(sa / (double)ca) : 0.0;
+        o_rms[2 * (size_t)f + 1] = c0 > 0 ? sqrt(s0 / (double)c0) : 0.0;
+        o_flags[f] = flags;
+    }
+}
+}  // namespace
+
+extern "C" int32_t cpe_mono_shift_batch(const double *xy, const int32_t *id, const int32_t *cnt, int32_t n, const double *K,
+                                        const double *Tc, const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
+                                        int32_t win0, int32_t win1, double tau, double min_sin, int32_t min_score, int32_t swap,
+                                        int32_t top_k, int32_t *scores, int32_t *cand, int32_t *cand_score,
+                                        int32_t *score, double *rms, int32_t *flags, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_mono_shift_batch: n < 0");
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_mono_shift_batch: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    const struct { int win[2]; double tau, min_sin; int min_score, swap, top_k; } p = {{win0, win1}, tau, min_sin, min_score, swap, top_k};
+    CPE_CHECK_ARG(p.win[0] >= 0 && p.win[0] <= CPE_SHIFT_MAX_WIN && p.win[1] >= 0 && p.win[1] <= CPE_SHIFT_MAX_WIN,
+                  "cpe_mono_shift_batch: window must be 0..%d for both components", CPE_SHIFT_MAX_WIN);
+    CPE_CHECK_ARG(p.tau > 0 && p.min_sin >= 0 && p.min_score >= 0 && (p.swap == 0 || p.swap == 1) && p.top_k >= 1 && p.top_k <= 8,
+                  "cpe_mono_shift_batch: bad parameters (tau > 0, min_sin >= 0, min_score >= 0, swap 0 or 1, top_k 1..8)");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(xy && id && cnt && K && P && line_status && scores && cand && cand_score && score && rms && flags,
+                  "cpe_mono_shift_batch: null pointer");
+    const int L = hi - lo + 1, n0 = 2 * p.win[0] + 1, C = n0 * (2 * p.win[1] + 1);
+    CPE_CHECK_ARG((long long)n * n0 <= INT_MAX, "cpe_mono_shift_batch: n (2 win[0] + 1) exceeds 2^31 - 1");
+    {
+        const size_t N = (size_t)n, Pp = (size_t)CPE_MAXP;
+        const struct { const void *p; size_t bytes; } buf[13] = {
+            {xy, N * Pp * 16}, {id, N * Pp * 8}, {cnt, N * 4}, {K, 72}, {Tc, Tc ? (size_t)128 : 0}, {P, (size_t)L * 64},
+            {line_status, (size_t)L * 8},
+            {scores, N * C * 4}, {cand, N * p.top_k * 8}, {cand_score, N * p.top_k * 4}, {score, N * 16}, {rms, N * 16}, {flags, N * 4}};
+        for (int o = 7; o < 13; o++)
+            for (int i = 0; i < o; i++)
+                CPE_CHECK_ARG(!buf[i].bytes || !rl_overlap(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes),
+                              "cpe_mono_shift_batch: an output overlaps an input or another output");
+    }
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_mono_vote, dim3((unsigned)n * (unsigned)n0), dim3(64), 0, (hipStream_t)stream, xy, id, cnt, K, Tc, P, line_status, lo, hi,
+                p.win[0], p.win[1], p.swap, p.min_sin * p.min_sin, p.tau, scores);
+    CPE_CHECK_LAUNCH("k_mono_vote");
+    CPE_KLAUNCH(k_mono_pick, dim3(n), dim3(64), 0, (hipStream_t)stream, xy, id, cnt, K, Tc, P, line_status, lo, hi, p.win[0], p.win[1], p.swap,
+                p.min_sin * p.min_sin, p.tau, p.min_score, p.top_k, (const int *)scores, cand, cand_score, score, rms, flags);
+    CPE_CHECK_LAUNCH("k_mono_pick");
+    return CPE_OK;
+}

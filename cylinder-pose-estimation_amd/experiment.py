@@ -204,9 +204,18 @@ def refine_listing(names, round_taken, renumbered):
     return [dict(index=i, name=names[i], round=rt[i], left=rn[i][0], right=rn[i][1]) for i in range(len(names)) if rn[i][0] or rn[i][1]]
 
 
+def repair_listing(names, shift, flags, round_taken, renumbered):
+    """shift i32 [F,2], flags, round_taken, renumbered i32 [F] of fit.fit_single_cylinder_mono_repaired_batch -> a list of
+    dict(index, name, shift, flags, round, renumbered) for the frames where anything changed: a non-zero shift, a flag, or a
+    re-numbered point"""
+    sh, fl, rt, rn = (torch.as_tensor(t).cpu().tolist() for t in (shift, flags, round_taken, renumbered))
+    return [dict(index=i, name=names[i], shift=tuple(sh[i]), flags=fl[i], round=rt[i], renumbered=rn[i]) for i in range(len(names))
+            if any(sh[i]) or fl[i] or rn[i]]
+
+
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
                    frame_angles=False, match_offset=None, laser_table=None, source='stereo', projector=None, table_path=None,
-                   consensus=None, refine=None):
+                   consensus=None, refine=None, repair=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
@@ -250,6 +259,13 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     whose index changed), frames: a list of dict(index, name, round, left, right) for the frames where any did).  Any other source
     raises ValueError.
 
+    repair= with source='left' / 'right' (build-defined, opt-in): None, or a dict of fit.fit_single_cylinder_mono_repaired_batch
+    keywords ({} = its defaults with the search on: shift={}, one round).  Every frame's grid indices are searched for a
+    frame-wide shift against the laser-plane table, and every grid point is then re-numbered against the grid the frame's fit
+    predicts (FramePipeline(source=..., table=dict(repair=...))).  The dict gains repair = dict(shift i32 [F,2], flags i32 [F]
+    (fit.SHIFT_*), round_taken i32 [F], renumbered i32 [F], frames: a list of dict(index, name, shift, flags, round, renumbered)
+    for the frames where anything changed).  Any other source raises ValueError.
+
     projector: None, or a dict of fit.fit_projector_model keywords ({} = its defaults; build-defined): the projector's model
     (two pencils of planes through one centre) is fitted to the experiment's own stereo points and indices -- after the index
     shift of match_offset where that is on -- over the frames the multi-frame fit would keep; no boards are needed.  The dict
@@ -276,6 +292,9 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     multiframe.estimate_frame_angles_gpu with T_cam_agv, a self-check of the calibration in degrees.  The dict gains
     angles_est (F x 2, rad; NaN for a skipped or failed frame), angles_status (F; the solver's status, -1 for a frame that was
     not given to it) and angles_delta_deg (estimated - nominal); all three are None without a multi-frame result."""
+    if repair is not None and source not in ('left', 'right'):
+        raise ValueError("repair= searches the index shift of one camera's frames: source must be 'left' or 'right' "
+                         "(stereo frames have match_offset= and projector['renumber'], fused ones refine=)")
     names, paths = _list_pairs(input_path)
     angles = np.deg2rad(parse_img_info(names))          # exp_gridDetection.m:26-27
     dev = torch.device(device)
@@ -285,15 +304,19 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
         raise ValueError("projector= fits the model to stereo points: source must be 'stereo'")
     if consensus is not None and multi_frame != 'consensus':
         raise ValueError("consensus= are the options of multi_frame='consensus'")
+    mono_table = None if repair is None else dict(repair=dict(repair))
 
     def make_fits(F):
         f = pipeline.alloc_fits(F, dev, source=source, refine=refine is not None)
+        if repair is not None:
+            f.update({k: torch.zeros((F,) + shape, dtype=dt, device=dev) for k, (shape, dt) in pipeline.MONO_REPAIR_OUTPUTS.items()})
         if projector is not None:        # the model needs the points' indices, which the selector returns beside the points
             f['idx'] = torch.zeros((F, fit.MAXP, 2), dtype=torch.int32, device=dev)
         return f
     recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, make_fits,
                             lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=c, device=dev, match=match_offset,
-                                                                   source=source, laser_table=laser_table, refine=refine), source)
+                                                                   source=source, laser_table=laser_table, refine=refine,
+                                                                   table=mono_table), source)
     F = len(names)
     # frame_ok: the device mask of the frames that are not in `skipped`; the resident multi-frame modes mask with it
     frame_ok, skipped, _ = _frame_status(names, recs, None if match_offset is None else fits['match_flags'])
@@ -306,6 +329,9 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
                              frames=refine_listing(names, fits['round_taken'], fits['renumbered']))
     elif source != 'stereo':
         res.update(tri_counts=fits['counts'], tri_stats=fits['stats'])
+    if repair is not None:
+        res['repair'] = dict(shift=fits['shift'], flags=fits['shift_flags'], round_taken=fits['round_taken'], renumbered=fits['renumbered'],
+                             frames=repair_listing(names, fits['shift'], fits['shift_flags'], fits['round_taken'], fits['renumbered']))
     if projector is not None:
         res['projector'], res['projector_shifted'], renumbered = _fit_projector(fits, frame_ok, projector, 'col', table_path=table_path)
         if renumbered is not None:

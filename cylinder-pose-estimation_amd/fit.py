@@ -845,3 +845,153 @@ def fit_single_cylinder_mono_batch(gp: GridTables, K, Tc, table: LaserTable, rad
     of the points from the planes that made them (0 for points cut with one plane only)."""
     tri = table_triangulate_batch(gp, K, Tc, table, need_both=need_both, min_sin=min_sin, max_res=max_res)
     return dict(tri, **_fit_points(tri['pts3'], tri['m'], radius, ransac, mode=mode, **fit_kw), mean_err=tri['stats'][:, 0])
+
+
+MONO_SHIFT_MAX_TOP_K = 8
+
+
+def mono_shift_batch(gp: GridTables, K, Tc, table: LaserTable, win=(4, 4), tau=0.1, min_score=8, min_sin=0.01, top_k=4, ids='col_row'):
+    """BUILD-DEFINED: the grid-index shift of ONE camera's frames against the laser-plane table, searched over |d_c| <= win[c] by
+    the two plane residuals of every point (one ray, two planes: over-determined by one); see include/cpe.h cpe_mono_shift_batch.
+    gp, K, Tc, table, ids as table_triangulate_batch.  The call reports and applies nothing.
+    -> dict(scores i32[n, (2 win[0] + 1)(2 win[1] + 1)] (every candidate, d0-major, ascending), cand i32[n,top_k,2] and cand_score
+            i32[n,top_k] (the best top_k candidates in rank order; (0, 0) and -1 past the candidate count), score i32[n,4] (best,
+            runner-up, at (0, 0), usable points), rms f64[n,2] (mm, at the best candidate, at (0, 0)), flags i32[n] (SHIFT_EDGE,
+            SHIFT_WEAK), win)"""
+    L = _lib.load()
+    dev = gp.xy.device
+    n = gp.cnt.shape[0]
+    _check_tables('mono_shift_batch', gp)
+    win = tuple(int(w) for w in win)
+    if len(win) != 2 or not all(0 <= w <= SHIFT_MAX_WIN for w in win):
+        raise ValueError(f'mono_shift_batch: window {win} outside 0..{SHIFT_MAX_WIN}')
+    if not tau > 0:
+        raise ValueError(f'mono_shift_batch: tau must be > 0, got {tau}')
+    if not 1 <= int(top_k) <= MONO_SHIFT_MAX_TOP_K:
+        raise ValueError(f'mono_shift_batch: top_k {top_k} outside 1..{MONO_SHIFT_MAX_TOP_K}')
+    if not (min_sin >= 0 and int(min_score) >= 0):
+        raise ValueError(f'mono_shift_batch: min_sin and min_score must be >= 0, got {min_sin} and {min_score}')
+    top_k = int(top_k)
+    K = _dev3(K, dev, (9,))
+    Tc = None if Tc is None else _dev3(Tc, dev, (16,))
+    P, st = _table_on(table, dev)
+    ncand = (2 * win[0] + 1) * (2 * win[1] + 1)
+    # (the kernels write every slot of every output)
+    scores, cand, cand_score, score, flags = _slab(dev, torch.int32, False, n, [('scores', (ncand,)), ('cand', (top_k, 2)),
+                                                                                ('cand_score', (top_k,)), ('score', (4,)),
+                                                                                ('flags', ())]).values()
+    rms = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    c = lambda t: t.contiguous()
+    x, d, k = c(gp.xy), c(gp.id), c(gp.cnt)
+    _lib.check(L.cpe_mono_shift_batch(_ptr(x), _ptr(d), _ptr(k), n, K.data_ptr(), None if Tc is None else Tc.data_ptr(), P.data_ptr(),
+                                      st.data_ptr(), table.lo, table.hi, win[0], win[1], float(tau), float(min_sin), int(min_score),
+                                      table.swap_for(ids), top_k, _ptr(scores), _ptr(cand), _ptr(cand_score),
+                                      _ptr(score), _ptr(rms), _ptr(flags), _stream()), 'cpe_mono_shift_batch')
+    return dict(scores=scores, cand=cand, cand_score=cand_score, score=score, rms=rms, flags=flags, win=win)
+
+
+_MONO_KEYS = ('cyl_raw', 'cyl', 'T', 'fvals', 'iters', 'status', 'pts3', 'idx', 'm', 'counts', 'res', 'src', 'stats', 'mean_err')
+
+
+def _fit_rms(fit, m):
+    """sqrt(final objective / points) in mm, +inf where the fit is not ST_OK"""
+    rms = torch.sqrt(fit['fvals'][:, 1] / m.clamp(min=1).to(torch.float64))
+    return torch.where((fit['status'] == ST_OK) & torch.isfinite(rms), rms, torch.full_like(rms, math.inf))
+
+
+def fit_single_cylinder_mono_repaired_batch(gp: GridTables, cam, K1, K2, T21, table: LaserTable, radius, shift=None, rounds=1,
+                                            max_res=0.25, vote_frac=0.5, rms_ratio=1.5, tau_px=4.0, ratio=0.5, window=None, min_cos=0.1,
+                                            image_size=None, mode=FIT_LM, **fit_kw):
+    """BUILD-DEFINED, opt-in: fit_single_cylinder_mono_batch with the two repairs a one-camera frame can have (DESIGN.md section
+    3.7): the frame-wide index shift, then `rounds` rounds that re-number every grid point against the grid the frame's own fitted
+    cylinder predicts.  cam 1 or 2: whose tables gp holds (camera 2 reads K2 and T21).  Every triangulation here needs both planes
+    and gates them with max_res; every fit is fit_cylinder_batch(mode, **fit_kw).
+    first = fit_single_cylinder_mono_batch(gp, K, Tc, table, radius, mode=mode, need_both=True, max_res=max_res, **fit_kw); with
+    shift=None and rounds=0 its outputs are the result, bit for bit.
+    shift: None (skip), or a dict of mono_shift_batch keywords ({} = its defaults).  The votes leave top_k candidates; each is
+    applied to a copy of gp.id, triangulated and fitted (top_k pairs of calls on all n frames).  A candidate is eligible when
+    cand_score >= max(min_score, vote_frac * best) and its fit is ST_OK; the eligible candidate with the smallest
+    fit rms = sqrt(fvals[:, 1] / m) is chosen (the better-ranked one on a tie), and trusted when it is the only eligible one or
+    rms_ratio * its rms <= the next smallest rms.  Otherwise SHIFT_WEAK, the shift is (0, 0) and the frame goes on as `first`.
+    Rounds, for the frames whose current status is ST_OK: grid_predict_batch from the current cyl[:, 1] (window, min_cos,
+    image_size), grid_assign_batch of gp with the shift applied (tau_px, ratio), table_triangulate_batch and the fit.  A frame takes a
+    round only when that round's fit is ST_OK.  Every choice is a torch.where on the device; nothing here waits for the GPU beyond
+    grid_predict_batch's one look at a new table's centre_status.
+    -> the keys of fit_single_cylinder_mono_batch (src[..., 1] is the slot in `tables`), of the result each frame ended with, and
+       shift i32[n,2] (applied), shift_flags i32[n] (SHIFT_SHIFTED: a non-zero shift was applied; SHIFT_WEAK: no trusted choice;
+       SHIFT_EDGE: the applied shift lies on the window's border), vote_flags i32[n] (mono_shift_batch's own), shift_score i32[n,4],
+       cand i32[n,top_k,2], cand_score i32[n,top_k], cand_rms f64[n,top_k] (mm; +inf where the candidate's fit is not ST_OK),
+       tables (the GridTables the result was made from), round_taken i32[n] (0: none), renumbered i32[n] (points whose index that
+       round changed), rounds: per round dict(counts i32[n,8], stats f64[n,2] of grid_assign_batch, status i32[n], taken bool[n]),
+       first.  With shift=None: one candidate (0, 0) with cand_score -1 and the rms of `first`."""
+    rounds = int(rounds)
+    if rounds < 0:
+        raise ValueError('fit_single_cylinder_mono_repaired_batch: rounds < 0')
+    if cam not in (1, 2):
+        raise ValueError('fit_single_cylinder_mono_repaired_batch: cam is 1 or 2')
+    for k in ('need_both', 'min_sin', 'ransac'):
+        if k in fit_kw:
+            raise ValueError(f'fit_single_cylinder_mono_repaired_batch: {k} does not apply (both planes are always needed, every fit '
+                             'is fit_cylinder_batch)')
+    if not (vote_frac >= 0 and rms_ratio >= 1):
+        raise ValueError(f'fit_single_cylinder_mono_repaired_batch: vote_frac >= 0 and rms_ratio >= 1, got {vote_frac} and {rms_ratio}')
+    n, dev = gp.cnt.shape[0], gp.xy.device
+    K, Tc = (K1, None) if cam == 1 else (K2, T21)
+
+    def solve(tables):
+        tri = table_triangulate_batch(tables, K, Tc, table, need_both=True, max_res=max_res)
+        return dict(tri, **fit_cylinder_batch(tri['pts3'], tri['m'], radius, mode=mode, **fit_kw), mean_err=tri['stats'][:, 0])
+
+    first = solve(gp)
+    cur = {k: first[k] for k in _MONO_KEYS}
+    pick = lambda take, a, b: torch.where(take.view((n,) + (1,) * (a.dim() - 1)), a, b)
+    applied = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+    if shift is None:
+        z = torch.zeros((n, 6), dtype=torch.int32, device=dev)
+        flags, vote_flags, shift_score = z[:, 0], z[:, 1], z[:, 2:6]
+        cand = torch.zeros((n, 1, 2), dtype=torch.int32, device=dev)
+        cand_score = torch.full((n, 1), -1, dtype=torch.int32, device=dev)
+        cand_rms = _fit_rms(first, first['m'])[:, None]
+    else:
+        ms = mono_shift_batch(gp, K, Tc, table, **shift)
+        cand, cand_score, shift_score, vote_flags = ms['cand'], ms['cand_score'], ms['score'], ms['flags']
+        top_k = cand.shape[1]
+        sols = [solve(GridTables(gp.xy, gp.id + cand[:, k, None, :], gp.cnt)) for k in range(top_k)]
+        cand_rms = torch.stack([_fit_rms(s, s['m']) for s in sols], 1)
+        need = torch.clamp(vote_frac * shift_score[:, 0].to(torch.float64), min=float(shift.get('min_score', 8)))
+        eligible = (cand_score.to(torch.float64) >= need[:, None]) & torch.isfinite(cand_rms)
+        r_sorted, order = torch.sort(torch.where(eligible, cand_rms, torch.full_like(cand_rms, math.inf)), dim=1, stable=True)
+        n_elig = eligible.sum(1)
+        trusted = (n_elig == 1)
+        if top_k > 1:
+            trusted = trusted | ((n_elig >= 2) & (rms_ratio * r_sorted[:, 0] <= r_sorted[:, 1]))
+        chosen = order[:, 0]
+        for k in range(top_k):
+            take = trusted & (chosen == k)
+            cur = {key: pick(take, sols[k][key], cur[key]) for key in _MONO_KEYS}
+            applied = pick(take, cand[:, k], applied)
+        win = torch.tensor(ms['win'], dtype=torch.int32, device=dev)
+        edge = ((applied.abs() == win) & (win > 0)).any(1)
+        flags = (torch.where(trusted, 0, SHIFT_WEAK) | torch.where((applied != 0).any(1), SHIFT_SHIFTED, 0) |
+                 torch.where(edge, SHIFT_EDGE, 0)).to(torch.int32)
+    shifted = GridTables(gp.xy, gp.id + applied[:, None, :], gp.cnt)
+    tables = shifted
+    taken_round = torch.zeros(n, dtype=torch.int32, device=dev)
+    renum = torch.zeros(n, dtype=torch.int32, device=dev)
+    per_round = []
+    for r in range(1, rounds + 1):
+        use = cur['status'] == ST_OK
+        pred = grid_predict_batch(cur['cyl'][:, 1], radius, K1, K2, T21, table, use=use, window=window, min_cos=min_cos,
+                                  image_size=image_size)
+        a = grid_assign_batch(shifted, pred, cam, tau_px=tau_px, ratio=ratio)
+        new = solve(a['tables'])
+        take = use & (new['status'] == ST_OK)
+        cur = {k: pick(take, new[k], cur[k]) for k in _MONO_KEYS}
+        tables = GridTables(pick(take, a['tables'].xy, tables.xy), pick(take, a['tables'].id, tables.id), pick(take, a['tables'].cnt, tables.cnt))
+        taken_round = torch.where(take, torch.full_like(taken_round, r), taken_round)
+        renum = pick(take, a['counts'][:, 2], renum)
+        per_round.append(dict(counts=a['counts'], stats=a['stats'], status=new['status'], taken=take))
+    out = dict(cur)
+    out.update(shift=applied, shift_flags=flags, vote_flags=vote_flags, shift_score=shift_score, cand=cand, cand_score=cand_score,
+               cand_rms=cand_rms, tables=tables, round_taken=taken_round, renumbered=renum, rounds=per_round, first=first)
+    return out

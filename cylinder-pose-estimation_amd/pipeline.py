@@ -55,6 +55,10 @@ MONO_FIT_OUTPUTS = dict(_POINTS, **_CYL, **_tri(4, 2, 2, 2))
 FUSED_FIT_OUTPUTS = dict(_POINTS, **_CYL, **_tri(6, 4, 3, 4), flags=((), _I32))
 # what fit.fit_single_cylinder_refined_batch returns per frame (FramePipeline(source='fused', refine=...))
 REFINED_FIT_OUTPUTS = dict(_POINTS, **_CYL, round_taken=((), _I32), renumbered=((2,), _I32))
+# what fit.fit_single_cylinder_mono_repaired_batch adds per frame; FramePipeline(source='left' / 'right', table=dict(repair=...))
+# .run_raw keeps them when the fits dict holds tensors of these names
+MONO_REPAIR_OUTPUTS = dict(shift=((2,), _I32), shift_flags=((), _I32), shift_score=((4,), _I32), round_taken=((), _I32),
+                           renumbered=((), _I32))
 
 
 # ---- the two record layouts (beside REC) ----
@@ -109,7 +113,17 @@ def _fit_plane(p, g1, g2, ctr, frame0):
 
 def _fit_mono(p, g1, g2, ctr, frame0):
     g, K, Tc = (g1, p.K1, None) if g2 is None else (g2, p.K2, p.T21)
-    return fit.fit_single_cylinder_mono_batch(g, K, Tc, p.laser_table, p.radius, ransac=_ransac(p, frame0), mode=p.fit_mode, **p.table)
+    table = dict(p.table)
+    repair = table.pop('repair', None)
+    if repair is None:
+        return fit.fit_single_cylinder_mono_batch(g, K, Tc, p.laser_table, p.radius, ransac=_ransac(p, frame0), mode=p.fit_mode, **table)
+    # repair (build-defined, opt-in): keywords of fit.fit_single_cylinder_mono_repaired_batch ({} = its defaults with shift={}, the
+    # search on; image_size: the frame's unless given).  The table's other keywords go with them: max_res is one of that call's
+    if p.ransac is not None:
+        raise ValueError("table=dict(repair=...): every candidate and round is fitted with fit_cylinder_batch, ransac does not apply")
+    kw = dict(dict(shift={}, image_size=(p.h, p.w), mode=p.fit_mode), **table)
+    kw.update(repair)
+    return fit.fit_single_cylinder_mono_repaired_batch(g, 1 if g2 is None else 2, p.K1, p.K2, p.T21, p.laser_table, p.radius, **kw)
 
 
 def _fit_fused(p, g1, g2, ctr, frame0):
@@ -224,7 +238,9 @@ class FramePipeline:
         # relabel (build-defined): None, or keywords of fit.grid_relabel_batch ({} = its defaults): both images' tables are
         # re-labelled from the lines' geometry and the detect call's centres before the selector pairs them by index
         self.relabel = None if relabel is None else dict(relabel)
-        # keywords of fit.table_triangulate_batch: need_both, min_sin, max_res; source 'fused': of fit.fused_triangulate_batch
+        # keywords of fit.table_triangulate_batch: need_both, min_sin, max_res; source 'fused': of fit.fused_triangulate_batch.
+        # source 'left' / 'right' also reads repair= here (build-defined, opt-in): None, or a dict of
+        # fit.fit_single_cylinder_mono_repaired_batch keywords ({} = the index-shift search and one re-numbering round)
         self.table = dict(table or {})
         # refine (build-defined, opt-in): None, or keywords of fit.fit_single_cylinder_refined_batch ({} = its defaults: rounds,
         # first, tau_px, ratio, window, min_cos, image_size -- the frame's size unless given): the stereo fit first, then every

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 126  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 127  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -58,7 +58,8 @@ extern "C" {
                              120: cpe_index_shift_batch; 121: cpe_multi_frame_consensus_batch,
                              cpe_multi_frame_consensus_workspace_bytes; 122: cpe_fused_triangulate_batch;
                              123: cpe_grid_relabel_batch; 124: cpe_grid_predict_batch, cpe_grid_assign_batch;
-                             125: cpe_debug_ccl_tiles; 126: cpe_debug_state_field) */
+                             125: cpe_debug_ccl_tiles; 126: cpe_debug_state_field;
+                             127: cpe_mono_shift_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -876,8 +877,10 @@ CPE_API int32_t cpe_fused_triangulate_batch(const double *xy1, const int32_t *id
  * shift i32[n,2] the applied shift per component; flags i32[n,2] CPE_SHIFT_FLAG_* (independent bits).  n == 0 is a no-op.  A
  * frame without a usable point scores 0 everywhere: shift 0, and CPE_SHIFT_FLAG_WEAK unless min_score is 0.
  * Limits: the shift is relative to the majority of the frames -- a shift common to all frames is absorbed by the model the
- * table comes from; one shift per frame and family; stereo points only: a point of cpe_table_triangulate_batch moves with its
- * index, so it lies on the plane of whatever index it carries. */
+ * table comes from; one shift per frame and family; stereo points only: a point of cpe_table_triangulate_batch cut with ONE
+ * plane moves with its index, so it lies on the plane of whatever index it carries.  Cut with both planes it is one ray against
+ * two planes, over-determined by one, and its res says whether the pair of indices is right: that is what
+ * cpe_mono_shift_batch searches. */
 #define CPE_SHIFT_MAX_WIN 8
 #define CPE_SHIFT_FLAG_SHIFTED 1   /* a non-zero shift was chosen and applied */
 #define CPE_SHIFT_FLAG_WEAK 2      /* best < min_score or best < 2 runner-up: the winner is not trusted, shift forced to 0 */
@@ -893,6 +896,53 @@ CPE_API int32_t cpe_index_shift_batch(const double *X, const int32_t *idx, const
                                       const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
                                       const CpeIndexShiftParams *params, int32_t *shift, int32_t *score, int32_t *scores, double *rms,
                                       int32_t *flags, int32_t *idx_out, void *stream);
+
+/* BUILD-DEFINED, opt-in: the grid-index shift of ONE-CAMERA frames against a laser-plane table.  A grid point of one camera is one
+ * ray cut with the two planes of light its indices name: three unknowns, four constraints.  The two residuals res of
+ * cpe_table_triangulate_batch therefore measure the inconsistency of the index PAIR, and a frame numbered (d0, d1) off as a
+ * whole shows it: per candidate shift, the points whose two residuals both stay below tau vote.  The call searches, ranks and
+ * reports; it applies nothing.  Two launches on `stream` (one wavefront per (frame, d0), then one per frame), no atomics, no
+ * workspace, no host synchronisation; two calls on the same inputs give the same bits.
+ *   xy f64[n,CPE_MAXP,2], id i32[n,CPE_MAXP,2], cnt i32[n]; K, Tc (NULL = camera 1), P f64[2,L,4], line_status i32[2,L], lo, hi:
+ *     exactly as cpe_table_triangulate_batch reads them; L = hi - lo + 1 in 1..CPE_MAXL (otherwise CPE_ERR_ARG)
+ *   win0, win1: candidates d_c in [-win_c, win_c] for id component c, 0..CPE_SHIFT_MAX_WIN (the Python layer's default 4, 4);
+ *   tau: a point counts when both |res| < tau (mm), > 0 (0.1); min_sin: as CpeTableTriParams.min_sin, >= 0 (0.01); min_score: a
+ *   best count below this is CPE_SHIFT_FLAG_WEAK, >= 0 (8); swap: as CpeTableTriParams.swap, component c addresses family
+ *   c ^ swap; top_k: candidates reported in cand / cand_score, 1..8 (4).  They travel as plain arguments: there are no defaults
+ *   on this side of the boundary
+ * Rule (the order is the contract):
+ *   1. cnt is clamped to [0, CPE_MAXP]; slots past it are never read.  A point is usable when its slot is below the count and both
+ *      pixel coordinates are finite.  Its ray is step 2 of cpe_table_triangulate_batch;
+ *   2. candidates d = (d0, d1) with |d_c| <= win_c.  Component c in {0,1} of id addresses family k = c ^ swap with
+ *      v = id[c] + d_c; the plane is usable when lo <= v <= hi and line_status[k, v - lo] == CPE_ST_OK.  A point with an id[c]
+ *      outside [lo - win_c, hi + win_c] counts for no candidate: that test is made before any addition, so an index may be any
+ *      int.  Both planes must be usable: with one plane there is no redundancy;
+ *   3. a_k, b_k, den = a_0^2 + a_1^2 >= min_sin^2 and finite, s = -sum a_k b_k / den > 0 and finite, X = o + s d and
+ *      res[c] = n_k.X + P4_k are steps 3 - 7 of cpe_table_triangulate_batch with need_both and no max_res gate, by the same device
+ *      function, so the same bits.  The point counts for d when |res[0]| < tau and |res[1]| < tau;
+ *   4. scores i32[n, (2 win0 + 1)(2 win1 + 1)] (required): the count of every candidate, d0-major, both ascending;
+ *   5. the candidates are ranked by the key (-score, |d0| + |d1|, |d0|, d0, d1), the smallest first, so (0, 0) wins every tie it is
+ *      part of.  cand i32[n,top_k,2] and cand_score i32[n,top_k]: the first top_k of that order; slots past the number of
+ *      candidates hold (0, 0) and -1.
+ *      score i32[n,4] = best | runner-up (the second of that order; 0 with a single candidate) | at (0, 0) | usable points;
+ *      rms f64[n,2] = sqrt((sum of res[0]^2 + res[1]^2 over the counting points) / their number) at the best candidate | at
+ *      (0, 0); 0 when none counts;
+ *      flags i32[n]: CPE_SHIFT_FLAG_EDGE when the best candidate has |d_c| == win_c > 0 for either c; CPE_SHIFT_FLAG_WEAK when
+ *      best < min_score or best < 2 runner-up (integers).  CPE_SHIFT_FLAG_SHIFTED is never set:
+ *   6. nothing is applied.  The caller adds a candidate to id and calls cpe_table_triangulate_batch.
+ * No output may overlap an input or another output (CPE_ERR_ARG).  n == 0 is a no-op.  A window outside 0..CPE_SHIFT_MAX_WIN,
+ * tau <= 0 or NaN, min_sin < 0, min_score < 0, swap other than 0 / 1 and top_k outside 1..8 are refused with CPE_ERR_ARG before
+ * anything is written.
+ * Limits: one shift per frame; tau must lie above the residuals that the table's errors and the pixel noise leave at the true
+ * indices and below those of a wrong pair (at most 0.089 mm; at least 0.43 mm rms on the frames of tests/mono_shift_cases.py):
+ * a table worse than that gives CPE_SHIFT_FLAG_WEAK, not a wrong shift.  One alias remains: a shift along the epipolar direction of projector and camera keeps
+ * both residuals small for most points while it moves them far in depth; votes do not always tell it from the true shift, the
+ * fixed-radius cylinder fit does (fit.fit_single_cylinder_mono_repaired_batch), and a board has no such second criterion. */
+CPE_API int32_t cpe_mono_shift_batch(const double *xy, const int32_t *id, const int32_t *cnt, int32_t n, const double *K,
+                                     const double *Tc, const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
+                                     int32_t win0, int32_t win1, double tau, double min_sin, int32_t min_score, int32_t swap,
+                                     int32_t top_k, int32_t *scores, int32_t *cand, int32_t *cand_score,
+                                     int32_t *score, double *rms, int32_t *flags, void *stream);
 
 /* BUILD-DEFINED: re-label the grid lines of PLANAR-target tables from their geometry, per image.  The planar detector's labels
  * group the grid points into true lines, but their VALUES are not the lines' indices: on rendered boards one image comes out
