@@ -5162,3 +5162,337 @@ extern "C" int32_t cpe_mono_shift_batch(const double *xy, const int32_t *id, con
     CPE_CHECK_LAUNCH("k_mono_pick");
     return CPE_OK;
 }
+
+// ------------------------------------------------------------------------------------------ curvatures of every point
+// [K, L] = estCurvatures(Pts3) for every point of every frame (estCurvatures.m, HOT LOOP E of SURVEY.md), and what a frame's
+// curvatures say together (build-defined).  The rule is in include/cpe.h at cpe_est_curvatures_batch.
+//   k_est_curvatures       : one lane per point, 256 points per workgroup.  The frame's points are staged in LDS once; every lane
+//                            scans them through broadcast reads and keeps its KM best (d2, index) pairs sorted in registers (a
+//                            fully unrolled compare-and-shift: no dynamic register index).  The ranked list then goes to LDS as
+//                            16-bit indices, column-per-lane, so that the algebra can walk it with a run-time count.  The algebra
+//                            of mode 0 restates fit_init's block line by line (fit_init itself is left alone: its kernels must
+//                            not change a bit), so for the point fit_init picks column 0 has the bits of cyl_raw[f,0,3:6].
+//   k_curvature_consensus  : one wavefront per frame.
+namespace {
+
+constexpr int CURV_TPB = 256;
+constexpr size_t CURV_LDS_BYTES = (size_t)MAXP * 3 * 8 + (size_t)CPE_CURV_MAXK * CURV_TPB * 2;
+
+// MODE: CPE_CURV_REFERENCE / CPE_CURV_INTERCEPT; KM: length of the sorted list in registers (>= k)
+template <int MODE, int KM>
+__global__ __launch_bounds__(CURV_TPB) void k_est_curvatures(const double *__restrict__ X, const int *__restrict__ cnt, int kwant,
+                                                             double *__restrict__ o_K, double *__restrict__ o_L,
+                                                             double *__restrict__ o_normal, int *__restrict__ o_nbr,
+                                                             unsigned char *__restrict__ o_pt, int *__restrict__ o_status)
+{
+    constexpr int NU = MODE == CPE_CURV_INTERCEPT ? 6 : 5;
+    double *sP = fit_dyn;                                                         // [MAXP * 3]
+    unsigned short *sNb = reinterpret_cast<unsigned short *>(sP + MAXP * 3);      // [CPE_CURV_MAXK][CURV_TPB]
+    const int f = blockIdx.y, tid = threadIdx.x, p = blockIdx.x * CURV_TPB + tid;
+    const int n = min(max(cnt[f], 0), MAXP);
+    const bool few = n < NU;
+    if (p == 0) o_status[f] = few ? CPE_ST_FEW_POINTS : CPE_ST_OK;
+    const size_t slot = (size_t)f * MAXP + p;
+    double *oK = o_K + slot * 6, *oL = o_L + slot * 2, *oN = o_normal + slot * 3;
+    int *oNb = o_nbr ? o_nbr + slot * kwant : nullptr;
+    auto zero_slot = [&]() {
+#pragma unroll
+        for (int a = 0; a < 6; a++) oK[a] = 0.0;
+        oL[0] = 0.0; oL[1] = 0.0;
+        oN[0] = 0.0; oN[1] = 0.0; oN[2] = 0.0;
+        if (oNb) for (int r = 0; r < kwant; r++) oNb[r] = 0;
+    };
+    if (few || blockIdx.x * CURV_TPB >= n) {   // the whole workgroup alike: nothing of it reaches a barrier
+        zero_slot();
+        o_pt[slot] = 0;
+        return;
+    }
+    const double *Xf = X + (size_t)f * MAXP * 3;
+    for (int i = tid; i < 3 * n; i += CURV_TPB) sP[i] = Xf[i];
+    __syncthreads();
+    if (p >= n) {
+        zero_slot();
+        o_pt[slot] = 0;
+        return;
+    }
+    const int K = n < kwant ? n : kwant;
+
+    // 1. the K nearest by (d2, index), the point itself included.  j ascends, so a candidate goes behind its equals.
+    {
+        double bd[KM];
+        int bi[KM];
+#pragma unroll
+        for (int i = 0; i < KM; i++) { bd[i] = DBL_MAX; bi[i] = 0; }
+        const double p0 = sP[3 * p], p1 = sP[3 * p + 1], p2 = sP[3 * p + 2];
+        for (int j = 0; j < n; j++) {
+            const double a = sP[3 * j] - p0, b = sP[3 * j + 1] - p1, c = sP[3 * j + 2] - p2;
+            const double d = (a * a + b * b) + c * c;
+            if (d < bd[KM - 1]) {
+#pragma unroll
+                for (int i = KM - 1; i >= 1; i--) {
+                    const bool up = d < bd[i - 1], here = !up && d < bd[i];
+                    bd[i] = up ? bd[i - 1] : (here ? d : bd[i]);
+                    bi[i] = up ? bi[i - 1] : (here ? j : bi[i]);
+                }
+                if (d < bd[0]) { bd[0] = d; bi[0] = j; }
+            }
+        }
+        // (a d2 that is NaN or +inf never enters the list: such a point is reported below through `listed`)
+#pragma unroll
+        for (int i = 0; i < KM; i++) sNb[i * CURV_TPB + tid] = (unsigned short)bi[i];
+        int listed = 0;
+#pragma unroll
+        for (int i = 0; i < KM; i++) listed += (bd[i] < DBL_MAX) ? 1 : 0;
+        if (oNb) {
+#pragma unroll
+            for (int i = 0; i < KM; i++)
+                if (i < kwant) oNb[i] = (i < K && bd[i] < DBL_MAX) ? bi[i] : -1;
+        }
+        if (listed < K) {   // not finite coordinates in the frame
+#pragma unroll
+            for (int a = 0; a < 6; a++) oK[a] = 0.0;
+            oL[0] = 0.0; oL[1] = 0.0;
+            oN[0] = 0.0; oN[1] = 0.0; oN[2] = 0.0;
+            o_pt[slot] = 1;
+            return;
+        }
+    }
+#define CURV_NB(k) ((int)sNb[(k) * CURV_TPB + tid])
+
+    // 2. plane, local frame, quadric, 2 x 2 eigen-pair: fit_init's block, operation by operation
+    double mu[3] = {0, 0, 0};
+    for (int k = 0; k < K; k++) {
+        const int q = CURV_NB(k);
+        for (int c = 0; c < 3; c++) mu[c] = mu[c] + sP[3 * q + c];
+    }
+    for (int c = 0; c < 3; c++) mu[c] = mu[c] / (double)K;
+    double C2[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < K; k++) {
+        const int q = CURV_NB(k);
+        double e[3] = {sP[3 * q] - mu[0], sP[3 * q + 1] - mu[1], sP[3 * q + 2] - mu[2]};
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) C2[a * 3 + b] = C2[a * 3 + b] + e[a] * e[b];
+    }
+#pragma unroll
+    for (int a = 0; a < 9; a++) C2[a] = C2[a] / (double)(K - 1);
+    double w[3], V[9];
+    eig3(C2, w, V);
+    double z[3] = {V[0], V[3], V[6]};
+    if (z[2] < 0) { z[0] = -z[0]; z[1] = -z[1]; z[2] = -z[2]; }
+    double x[3] = {1, 0, 0};
+    if (fabs(z[0]) > 0.9) { x[0] = 0; x[1] = 1; }
+    double y[3] = {z[1] * x[2] - z[2] * x[1], z[2] * x[0] - z[0] * x[2], z[0] * x[1] - z[1] * x[0]};
+    if (MODE == CPE_CURV_INTERCEPT) {
+        const double yn = sqrt((y[0] * y[0] + y[1] * y[1]) + y[2] * y[2]);
+        y[0] = y[0] / yn; y[1] = y[1] / yn; y[2] = y[2] / yn;
+    }
+    double xx[3] = {y[1] * z[2] - y[2] * z[1], y[2] * z[0] - y[0] * z[2], y[0] * z[1] - y[1] * z[0]};
+    double M[NU * NU], rhs[NU], co[NU];
+#pragma unroll
+    for (int a = 0; a < NU * NU; a++) M[a] = 0;
+#pragma unroll
+    for (int a = 0; a < NU; a++) rhs[a] = 0;
+    for (int k = 0; k < K; k++) {
+        const int q = CURV_NB(k);
+        double e[3] = {sP[3 * q] - mu[0], sP[3 * q + 1] - mu[1], sP[3 * q + 2] - mu[2]};
+        double lx = (e[0] * xx[0] + e[1] * xx[1]) + e[2] * xx[2];
+        double ly = (e[0] * y[0] + e[1] * y[1]) + e[2] * y[2];
+        double lz = (e[0] * z[0] + e[1] * z[1]) + e[2] * z[2];
+        double row[NU];
+        row[0] = lx * lx; row[1] = lx * ly; row[2] = ly * ly; row[3] = lx; row[4] = ly;
+        if (MODE == CPE_CURV_INTERCEPT) row[NU - 1] = 1.0;
+#pragma unroll
+        for (int a = 0; a < NU; a++) {
+#pragma unroll
+            for (int b = 0; b < NU; b++) M[a * NU + b] = M[a * NU + b] + row[a] * row[b];
+            rhs[a] = rhs[a] + row[a] * lz;
+        }
+    }
+#undef CURV_NB
+    bool ok = gauss_solve<NU>(M, rhs, co);
+    double a = co[0] * 2, b = co[1], c = co[2] * 2;
+    double hd = (a - c) / 2.0, mid = (a + c) / 2.0, rad = sqrt(hd * hd + b * b);
+    double kd[6], lam[2] = {mid - rad, mid + rad};  // eig ascending: V(:,1), V(:,2)
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        double v0, v1;
+        if (fabs(lam[j] - a) >= fabs(lam[j] - c)) { v0 = b; v1 = lam[j] - a; }
+        else { v0 = lam[j] - c; v1 = b; }
+        double nn = sqrt(v0 * v0 + v1 * v1);
+        if (nn == 0) { v0 = j == 0 ? 1 : 0; v1 = j == 0 ? 0 : 1; nn = 1; }   // eig of a multiple of the identity: I
+        v0 = v0 / nn;
+        v1 = v1 / nn;
+        for (int k = 0; k < 3; k++) kd[3 * j + k] = xx[k] * v0 + y[k] * v1;
+    }
+    ok = ok && isfinite(lam[0]) && isfinite(lam[1]) && isfinite(z[0]) && isfinite(z[1]) && isfinite(z[2]);
+#pragma unroll
+    for (int k = 0; k < 6; k++) ok = ok && isfinite(kd[k]);
+#pragma unroll
+    for (int k = 0; k < 6; k++) oK[k] = ok ? kd[k] : 0.0;
+    oL[0] = ok ? lam[0] : 0.0;
+    oL[1] = ok ? lam[1] : 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) oN[k] = ok ? z[k] : 0.0;
+    o_pt[slot] = ok ? 0 : 1;
+}
+
+// what a frame's curvatures say together: the gate, the consensus direction, the centres of curvature, the median radius
+__global__ __launch_bounds__(64) void k_curvature_consensus(const double *__restrict__ X, const int *__restrict__ cnt,
+                                                            const double *__restrict__ Kdir, const double *__restrict__ Lam,
+                                                            const double *__restrict__ normal, const unsigned char *__restrict__ pt,
+                                                            double rho_max, double r_min, double r_max, double *__restrict__ o_axis,
+                                                            int *__restrict__ o_ng, unsigned char *__restrict__ o_gate,
+                                                            int *__restrict__ o_status)
+{
+    __shared__ unsigned long long sR[MAXP];   // bits of 1 / |lambda|max of a gated point, all ones otherwise
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int n = min(max(cnt[f], 0), MAXP);
+    const double *Xf = X + (size_t)f * MAXP * 3, *Kf = Kdir + (size_t)f * MAXP * 6, *Lf = Lam + (size_t)f * MAXP * 2;
+    const double *Nf = normal + (size_t)f * MAXP * 3;
+    const unsigned char *ptf = pt + (size_t)f * MAXP;
+    unsigned char *gf = o_gate + (size_t)f * MAXP;
+
+    // pass 1: the gate; sums of t t' and of the centres of curvature
+    double S[6] = {0, 0, 0, 0, 0, 0}, cs[3] = {0, 0, 0};
+    int g = 0;
+    for (int k = lane; k < MAXP; k += 64) {
+        bool in = false;
+        if (k < n && ptf[k] == 0) {
+            const double l0 = Lf[2 * k], l1 = Lf[2 * k + 1];
+            const double a0 = fabs(l0), a1 = fabs(l1);
+            const int big = a1 > a0 ? 1 : 0;
+            const double amax = big ? a1 : a0, amin = big ? a0 : a1, lbig = big ? l1 : l0;
+            const double r = 1.0 / amax;
+            const double *t = Kf + 6 * k + 3 * (1 - big);
+            const double tn = sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+            in = amax > 0 && amin / amax <= rho_max && r_min < r && r < r_max && tn > 0 && isfinite(tn) && isfinite(r);
+            if (in) {
+                const double t0 = t[0] / tn, t1 = t[1] / tn, t2 = t[2] / tn;
+                S[0] = S[0] + t0 * t0; S[1] = S[1] + t0 * t1; S[2] = S[2] + t0 * t2;
+                S[3] = S[3] + t1 * t1; S[4] = S[4] + t1 * t2; S[5] = S[5] + t2 * t2;
+#pragma unroll
+                for (int c = 0; c < 3; c++) cs[c] = cs[c] + (Xf[3 * k + c] + Nf[3 * k + c] / lbig);
+                sR[k] = (unsigned long long)__double_as_longlong(r);
+                g++;
+            }
+        }
+        if (!in) sR[k] = ~0ull;
+        gf[k] = in ? 1 : 0;
+    }
+    g = wave_sum_i(g);
+#pragma unroll
+    for (int a = 0; a < 6; a++) S[a] = wave_sum(S[a]);
+#pragma unroll
+    for (int c = 0; c < 3; c++) cs[c] = wave_sum(cs[c]);
+    __syncthreads();
+
+    double out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool ok = g >= 3;
+    if (ok) {
+        double org[3], dir[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) org[c] = cs[c] / (double)g;
+        const double Sm[9] = {S[0], S[1], S[2], S[1], S[3], S[4], S[2], S[4], S[5]};
+        double w[3], V[9];
+        eig3(Sm, w, V);
+        dir[0] = V[2]; dir[1] = V[5]; dir[2] = V[8];
+        {   // the largest-magnitude component (the first of them) positive
+            double m = fabs(dir[0]), s = dir[0];
+            if (fabs(dir[1]) > m) { m = fabs(dir[1]); s = dir[1]; }
+            if (fabs(dir[2]) > m) { m = fabs(dir[2]); s = dir[2]; }
+            if (s < 0) { dir[0] = -dir[0]; dir[1] = -dir[1]; dir[2] = -dir[2]; }
+        }
+        // the lower median of the radii by exact selection: the bits of positive doubles order as the numbers do
+        unsigned long long prefix = 0;
+        int rank = (g - 1) / 2;
+        for (int bit = 63; bit >= 0; bit--) {
+            int c0 = 0;
+            for (int k = lane; k < n; k += 64) c0 += ((sR[k] >> bit) == (prefix >> bit)) ? 1 : 0;
+            c0 = wave_sum_i(c0);
+            if (rank >= c0) { rank -= c0; prefix |= 1ull << bit; }
+        }
+        const double radius = __longlong_as_double((long long)prefix);
+        // pass 2: rms distance of the centres of curvature from the line (org, dir)
+        double acc = 0.0;
+        for (int k = lane; k < n; k += 64) {
+            if (sR[k] == ~0ull) continue;
+            const double l0 = Lf[2 * k], l1 = Lf[2 * k + 1];
+            const double lbig = fabs(l1) > fabs(l0) ? l1 : l0;
+            double e[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++) e[c] = (Xf[3 * k + c] + Nf[3 * k + c] / lbig) - org[c];
+            const double al = (e[0] * dir[0] + e[1] * dir[1]) + e[2] * dir[2];
+#pragma unroll
+            for (int c = 0; c < 3; c++) e[c] = e[c] - dir[c] * al;
+            acc = acc + ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+        }
+        const double spread = sqrt(wave_sum(acc) / (double)g);
+        out[0] = org[0]; out[1] = org[1]; out[2] = org[2];
+        out[3] = dir[0]; out[4] = dir[1]; out[5] = dir[2];
+        out[6] = radius; out[7] = spread;
+#pragma unroll
+        for (int a = 0; a < 8; a++) ok = ok && isfinite(out[a]);
+    }
+    if (lane < 8) {
+        double v = 0.0;
+#pragma unroll
+        for (int a = 0; a < 8; a++) v = (lane == a && ok) ? out[a] : v;
+        o_axis[(size_t)f * 8 + lane] = v;
+    }
+    if (lane == 0) { o_ng[f] = g; o_status[f] = ok ? CPE_ST_OK : CPE_ST_FEW_POINTS; }
+}
+}  // namespace
+
+extern "C" int32_t cpe_est_curvatures_batch(const double *X, const int32_t *cnt, int32_t n, int32_t k, int32_t mode, double *Kdir,
+                                            double *L, double *normal, int32_t *nbr, uint8_t *pt_status, int32_t *status,
+                                            void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_est_curvatures_batch: n < 0");
+    const struct { int k, mode; } p = {k, mode};
+    CPE_CHECK_ARG(p.mode == CPE_CURV_REFERENCE || p.mode == CPE_CURV_INTERCEPT, "cpe_est_curvatures_batch: unknown mode %d", p.mode);
+    const int unknowns = p.mode == CPE_CURV_INTERCEPT ? 6 : 5;
+    CPE_CHECK_ARG(p.k >= unknowns && p.k <= CPE_CURV_MAXK, "cpe_est_curvatures_batch: k = %d must be %d..%d in mode %d", p.k, unknowns,
+                  CPE_CURV_MAXK, p.mode);
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(X && cnt && Kdir && L && normal && pt_status && status, "cpe_est_curvatures_batch: null pointer");
+    CPE_LAUNCH_BEGIN();
+    const dim3 grid(MAXP / CURV_TPB, n), block(CURV_TPB);
+#define CURV_LAUNCH(MODE, KM)                                                                                                       \
+    do {                                                                                                                            \
+        CPE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_est_curvatures<MODE, KM>),                              \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)CURV_LDS_BYTES));                        \
+        CPE_KLAUNCH((k_est_curvatures<MODE, KM>), grid, block, CURV_LDS_BYTES, (hipStream_t)stream, X, cnt, p.k, Kdir, L, normal, nbr, \
+                    pt_status, status);                                                                                             \
+    } while (0)
+    if (p.mode == CPE_CURV_INTERCEPT) {
+        if (p.k <= 20) CURV_LAUNCH(CPE_CURV_INTERCEPT, 20);
+        else CURV_LAUNCH(CPE_CURV_INTERCEPT, CPE_CURV_MAXK);
+    } else {
+        if (p.k <= 20) CURV_LAUNCH(CPE_CURV_REFERENCE, 20);
+        else CURV_LAUNCH(CPE_CURV_REFERENCE, CPE_CURV_MAXK);
+    }
+#undef CURV_LAUNCH
+    CPE_CHECK_LAUNCH("k_est_curvatures");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_curvature_consensus_batch(const double *X, const int32_t *cnt, int32_t n, const double *Kdir, const double *L,
+                                                 const double *normal, const uint8_t *pt_status, double rho_max, double r_min,
+                                                 double r_max, double *axis, int32_t *n_gated, uint8_t *gate, int32_t *status,
+                                                 void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_curvature_consensus_batch: n < 0");
+    const struct { double rho_max, r_min, r_max; } g = {rho_max, r_min, r_max};
+    CPE_CHECK_ARG(g.rho_max >= 0 && g.r_min >= 0 && g.r_max > g.r_min,
+                  "cpe_curvature_consensus_batch: bad gate (rho_max >= 0, 0 <= r_min < r_max, none NaN)");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(X && cnt && Kdir && L && normal && pt_status && axis && n_gated && gate && status,
+                  "cpe_curvature_consensus_batch: null pointer");
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_curvature_consensus, dim3(n), dim3(64), 0, (hipStream_t)stream, X, cnt, Kdir, L, normal, pt_status, g.rho_max, g.r_min,
+                g.r_max, axis, n_gated, gate, status);
+    CPE_CHECK_LAUNCH("k_curvature_consensus");
+    return CPE_OK;
+}

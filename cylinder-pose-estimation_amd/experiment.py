@@ -215,7 +215,7 @@ def repair_listing(names, shift, flags, round_taken, renumbered):
 
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
                    frame_angles=False, match_offset=None, laser_table=None, source='stereo', projector=None, table_path=None,
-                   consensus=None, refine=None, repair=None):
+                   curvature=None, consensus=None, refine=None, repair=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
@@ -291,7 +291,14 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     frame_angles=True (build-defined, nothing like it in the reference): with a multi-frame result, the good frames go through
     multiframe.estimate_frame_angles_gpu with T_cam_agv, a self-check of the calibration in degrees.  The dict gains
     angles_est (F x 2, rad; NaN for a skipped or failed frame), angles_status (F; the solver's status, -1 for a frame that was
-    not given to it) and angles_delta_deg (estimated - nominal); all three are None without a multi-frame result."""
+    not given to it) and angles_delta_deg (estimated - nominal); all three are None without a multi-frame result.
+
+    curvature: None, or a dict of k, mode, rho_max, band, r_min, r_max ({} = 20, fit.CURV_INTERCEPT, 0.25 and the band radius
+    (1 -/+ 1/3); build-defined): fit.est_curvatures_batch and fit.curvature_consensus_batch run on the pts3 / cnt the run holds
+    anyway, and the dict gains curvature = their two dicts merged (Kdir, L, normal, pt_status, axis, n_gated, gate, status = the
+    consensus', curv_status = the per-frame status of the curvatures).  The fits of the run are untouched."""
+    if curvature is not None:
+        curv_opts = fit._curvature_options('run_experiment', curvature, float(radius))
     if repair is not None and source not in ('left', 'right'):
         raise ValueError("repair= searches the index shift of one camera's frames: source must be 'left' or 'right' "
                          "(stereo frames have match_offset= and projector['renumber'], fused ones refine=)")
@@ -324,6 +331,11 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
                T_cam_agv=None, fval=None)
     if match_offset is not None:
         res.update(offset=fits['offset'], match_score=fits['match_score'], match_flags=fits['match_flags'])
+    if curvature is not None:
+        k, mode, rho_max, r_min, r_max = curv_opts
+        curv = fit.est_curvatures_batch(fits['pts3'], fits['m'], k=k, mode=mode)
+        con = fit.curvature_consensus_batch(fits['pts3'], fits['m'], curv, rho_max=rho_max, r_min=r_min, r_max=r_max)
+        res['curvature'] = dict(curv, curv_status=curv['status'], **con)
     if refine is not None:
         res['refine'] = dict(round_taken=fits['round_taken'], renumbered=fits['renumbered'],
                              frames=refine_listing(names, fits['round_taken'], fits['renumbered']))

@@ -257,6 +257,123 @@ def fit_single_cylinder_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, rad
     return dict(sel, **_fit_points(sel['pts3'], sel['m'], radius, ransac, sel['flags'], **fit_kw), **extra)
 
 
+CURV_REFERENCE, CURV_INTERCEPT, CURV_MAXK = _c.CURV_REFERENCE, _c.CURV_INTERCEPT, _c.CURV_MAXK
+_CURV_UNKNOWNS = {CURV_REFERENCE: 5, CURV_INTERCEPT: 6}
+_CURV_FIELDS = (('Kdir', torch.float64, (MAXP, 2, 3)), ('L', torch.float64, (MAXP, 2)), ('normal', torch.float64, (MAXP, 3)),
+                ('pt_status', torch.uint8, (MAXP,)))
+
+
+def _check_points(what, pts3, cnt):
+    """the dtype / shape / device check of a point table: pts3 f64[n,MAXP,3] and cnt i32[n] on one device -> n"""
+    if not isinstance(cnt, torch.Tensor) or cnt.dim() != 1:
+        raise TypeError(f'{what}: cnt must be a torch.int32 tensor [n]')
+    n, dev = cnt.shape[0], pts3.device
+    for name, t, dt, shape in (('pts3', pts3, torch.float64, (n, MAXP, 3)), ('cnt', cnt, torch.int32, (n,))):
+        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev:
+            raise TypeError(f'{what}: {name} must be {dt} {list(shape)} on {dev}, got {t.dtype} {list(t.shape)} on {t.device}')
+    return n
+
+
+def _check_curv_args(what, k, mode):
+    if mode not in _CURV_UNKNOWNS:
+        raise ValueError(f'{what}: mode {mode} must be CURV_REFERENCE ({CURV_REFERENCE}) or CURV_INTERCEPT ({CURV_INTERCEPT})')
+    if int(k) != k or not _CURV_UNKNOWNS[mode] <= k <= CURV_MAXK:
+        raise ValueError(f'{what}: k {k} must be {_CURV_UNKNOWNS[mode]}..{CURV_MAXK} in mode {mode}')
+
+
+def est_curvatures_batch(pts3, cnt, k=_c.CURV_K, mode=CURV_REFERENCE, want_neighbours=False):
+    """[K, L] = estCurvatures(Pts3) for every point of every frame, see include/cpe.h cpe_est_curvatures_batch.  pts3
+    f64[n,MAXP,3], cnt i32[n] as select_triangulate_batch returns them; mode CURV_REFERENCE (the reference's arithmetic) or
+    CURV_INTERCEPT (build-defined: unit frame, quadric with a constant term).
+    -> dict(Kdir f64[n,MAXP,2,3], L f64[n,MAXP,2] (ascending), normal f64[n,MAXP,3], nbr i32[n,MAXP,k] (None without
+            want_neighbours), pt_status u8[n,MAXP], status i32[n], k, mode)"""
+    n = _check_points('est_curvatures_batch', pts3, cnt)
+    _check_curv_args('est_curvatures_batch', k, mode)
+    L = _lib.load()
+    dev = pts3.device
+    pts3, cnt = pts3.contiguous(), cnt.contiguous()
+    # (the kernel writes every slot of every output: no fills)
+    Kd, Lm, nrm = _slab(dev, torch.float64, False, n, [(name, shape) for name, dt, shape in _CURV_FIELDS if dt == torch.float64]).values()
+    pt = torch.empty((n, MAXP), dtype=torch.uint8, device=dev)
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    nbr = torch.empty((n, MAXP, int(k)), dtype=torch.int32, device=dev) if want_neighbours else None
+    _lib.check(L.cpe_est_curvatures_batch(_ptr(pts3), _ptr(cnt), n, int(k), int(mode), _ptr(Kd), _ptr(Lm), _ptr(nrm), _ptr(nbr), _ptr(pt),
+                                          _ptr(st), _stream()), 'cpe_est_curvatures_batch')
+    return dict(Kdir=Kd, L=Lm, normal=nrm, nbr=nbr, pt_status=pt, status=st, k=int(k), mode=int(mode))
+
+
+def curvature_consensus_batch(pts3, cnt, curv, rho_max=0.25, r_min=0.0, r_max=math.inf):
+    """BUILD-DEFINED: what a frame's curvatures say together, see include/cpe.h cpe_curvature_consensus_batch.  curv: the dict of
+    est_curvatures_batch on the same pts3 and cnt.  A point is gated in when its |lambda|min / |lambda|max <= rho_max and
+    r_min < 1 / |lambda|max < r_max.
+    -> dict(axis f64[n,8] (origin, direction, radius = lower median of 1 / |lambda|max, spread = rms distance of the centres of
+            curvature from the axis), n_gated i32[n], gate u8[n,MAXP], status i32[n] (ST_FEW_POINTS: fewer than 3 gated))"""
+    what = 'curvature_consensus_batch'
+    n = _check_points(what, pts3, cnt)
+    dev = pts3.device
+    for name, dt, shape in _CURV_FIELDS:
+        t = curv[name]
+        if t.dtype != dt or tuple(t.shape) != (n,) + shape or t.device != dev:
+            raise TypeError(f'{what}: curv[{name!r}] must be {dt} {[n] + list(shape)} on {dev}, got {t.dtype} {list(t.shape)} on {t.device}')
+    rho_max, r_min, r_max = float(rho_max), float(r_min), float(r_max)
+    if not (rho_max >= 0 and r_min >= 0 and r_max > r_min):
+        raise ValueError(f'{what}: rho_max {rho_max} must be >= 0 and 0 <= r_min {r_min} < r_max {r_max}')
+    L = _lib.load()
+    c = lambda t: t.contiguous()
+    axis = torch.empty((n, 8), dtype=torch.float64, device=dev)
+    ng, st = _slab(dev, torch.int32, False, None, [('n_gated', (n,)), ('status', (n,))]).values()
+    gate = torch.empty((n, MAXP), dtype=torch.uint8, device=dev)
+    Kd, Lm, nrm, pt = (c(curv[name]) for name, _, _ in _CURV_FIELDS)
+    _lib.check(L.cpe_curvature_consensus_batch(_ptr(c(pts3)), _ptr(c(cnt)), n, _ptr(Kd), _ptr(Lm), _ptr(nrm), _ptr(pt), rho_max, r_min, r_max,
+                                               _ptr(axis), _ptr(ng), _ptr(gate), _ptr(st), _stream()), 'cpe_curvature_consensus_batch')
+    return dict(axis=axis, n_gated=ng, gate=gate, status=st)
+
+
+def _curvature_options(what, curvature, radius):
+    """(k, mode, rho_max, r_min, r_max) of a `curvature` dict: mode CURV_INTERCEPT, k 20, rho_max 0.25 and the band
+    radius (1 -/+ band), band = 1/3, unless the dict says otherwise (radius None: no band, r_min 0 and r_max inf)"""
+    o = dict(curvature or {})
+    k, mode, rho_max, band = o.pop('k', 20), o.pop('mode', CURV_INTERCEPT), o.pop('rho_max', 0.25), o.pop('band', 1.0 / 3.0)
+    r_min = o.pop('r_min', 0.0 if radius is None else radius * (1.0 - band))
+    r_max = o.pop('r_max', math.inf if radius is None else radius * (1.0 + band))
+    if o:
+        raise ValueError(f'{what}: unknown curvature options {sorted(o)}')
+    _check_curv_args(what, k, mode)
+    return k, mode, rho_max, r_min, r_max
+
+
+def compact_gated(pts3, gate):
+    """the gated points of every frame moved to the front in table order (torch only, no host synchronisation):
+    pts3 f64[n,MAXP,3], gate u8[n,MAXP] -> (f64[n,MAXP,3] with zeros behind the kept points, i32[n] how many were kept)"""
+    keep = gate != 0
+    n, P = keep.shape
+    at = torch.cumsum(keep, 1) - 1                                          # a kept point's place: the kept points before it
+    at = torch.where(keep, at, torch.full_like(at, P))                      # everything else goes to one spare slot behind the table
+    out = torch.zeros((n, P + 1, 3), dtype=pts3.dtype, device=pts3.device)
+    out.scatter_(1, at[:, :, None].expand(-1, -1, 3), pts3)
+    return out[:, :P].contiguous(), keep.sum(1, dtype=torch.int32)
+
+
+def fit_single_cylinder_gated_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, radius, curvature=None, selector=SEL_CHOOSE_IDX,
+                                    patch=3, th=0.3, ransac=None, **fit_kw):
+    """BUILD-DEFINED, fit_single_cylinder_batch behind the curvature gate: select_triangulate_batch, est_curvatures_batch and
+    curvature_consensus_batch on its points, then the fit on the gated points alone (compacted in table order on the device).
+    curvature: None or a dict of k, mode (default CURV_INTERCEPT), rho_max, band (default 1/3: r_min, r_max = radius (1 -/+
+    band)), r_min, r_max.  -> everything fit_single_cylinder_batch returns (pts3 and m are the selector's, before the gate)
+    beside gate u8[n,MAXP], n_gated i32[n], curv_axis f64[n,8], curv_status i32[n], pts3_gated f64[n,MAXP,3].  A frame that keeps
+    fewer than FIT_MIN_POINTS points ends in ST_FEW_POINTS like any other."""
+    k, mode, rho_max, r_min, r_max = _curvature_options('fit_single_cylinder_gated_batch', curvature, float(radius))
+    n, dev = gp1.cnt.shape[0], gp1.xy.device
+    sel = select_triangulate_batch(gp1, gp2, K1, K2, T21, selector, patch, th)
+    curv = est_curvatures_batch(sel['pts3'], sel['m'], k=k, mode=mode)
+    con = curvature_consensus_batch(sel['pts3'], sel['m'], curv, rho_max=rho_max, r_min=r_min, r_max=r_max)
+    kept, m = compact_gated(sel['pts3'], con['gate'])
+    z = torch.zeros((n, 7), dtype=torch.int32, device=dev)
+    return dict(sel, **_fit_points(kept, m, radius, ransac, sel['flags'], **fit_kw), offset=z[:, 0:2], match_score=z[:, 2:6],
+                match_flags=z[:, 6], gate=con['gate'], n_gated=con['n_gated'], curv_axis=con['axis'], curv_status=con['status'],
+                pts3_gated=kept)
+
+
 PLANE_NO_GRID, PLANE_ORIGIN_POINT = _c.PLANEFIT_NO_GRID, _c.PLANEFIT_ORIGIN_POINT
 
 

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 127  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 128  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -59,7 +59,7 @@ extern "C" {
                              cpe_multi_frame_consensus_workspace_bytes; 122: cpe_fused_triangulate_batch;
                              123: cpe_grid_relabel_batch; 124: cpe_grid_predict_batch, cpe_grid_assign_batch;
                              125: cpe_debug_ccl_tiles; 126: cpe_debug_state_field;
-                             127: cpe_mono_shift_batch) */
+                             127: cpe_mono_shift_batch; 128: cpe_est_curvatures_batch, cpe_curvature_consensus_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -1347,6 +1347,68 @@ CPE_API int32_t cpe_frame_angles_lm_batch(
     double *fvals, int32_t *iters,            /* [n,2] = [f(a0), f(a)], [iterations, objective evaluations] */
     double *TAGVcyl, double *Tcyl,            /* [n,16] each or NULL */
     int32_t *status, void *stream);
+
+/* ---- local surface curvature of every 3-D point --------------------------------------------------------------------------
+ * [K, L] = estCurvatures(Pts3) for n frames (estCurvatures.m with knnsearch, fitplane.m, createLocCoordSys, fitquadsurf, eig:
+ * HOT LOOP E of SURVEY.md), one lane per point.  cpe_fit_cylinder_batch computes this for the one point its start needs; this
+ * call returns it for all of them.
+ *   X f64[n,CPE_MAXP,3], cnt i32[n] as cpe_fit_cylinder_batch takes them: cnt is clamped to [0, CPE_MAXP], slots past it are
+ *   never read.  k: neighbours per point, the point itself included (the reference's value: CPE_CURV_K = 20); mode:
+ *   CPE_CURV_REFERENCE or CPE_CURV_INTERCEPT.  k must lie in [unknowns, CPE_CURV_MAXK] (unknowns = 5 in mode 0, 6 in mode 1);
+ *   an unknown mode or such a k is CPE_ERR_ARG.  A frame with fewer than k points uses all of them (K = min(k, cnt)).  (k and
+ *   mode are plain arguments, as the parameters of cpe_mono_shift_batch are, not a structure.)
+ * The rule, in this order:
+ *   1. Neighbours of point p: d2(j) = (a*a + b*b) + c*c of the coordinate differences X[j] - X[p]; the K smallest by
+ *      (d2, index), p itself included -- knnsearch's ties by index; a duplicate of p is a legitimate neighbour.
+ *   2. CPE_CURV_REFERENCE: mu = (sum over the neighbours in rank order) / K, per coordinate; C = sum e e' / (K - 1), e = X - mu,
+ *      in rank order; z = the first eigenvector of C (cyclic Jacobi, eigenvalues ascending by a stable exchange), negated when
+ *      z[2] < 0; x0 = (1,0,0), or (0,1,0) when |z[0]| > 0.9; y = z x x0; x = y x z -- NOT normalised, as createLocCoordSys
+ *      leaves them; per neighbour lx = (e.x), ly = (e.y), lz = (e.z), each ((.)+(.))+(.); row = [lx^2, lx ly, ly^2, lx, ly];
+ *      M += row row', rhs += row lz in rank order; co = M \ rhs by Gaussian elimination with partial pivoting (first largest
+ *      pivot); a = 2 co[0], b = co[1], c = 2 co[2]; hd = (a - c) / 2, mid = (a + c) / 2, rad = sqrt(hd*hd + b*b);
+ *      L = [mid - rad, mid + rad]; the eigenvector of lambda is (b, lambda - a) when |lambda - a| >= |lambda - c|, else
+ *      (lambda - c, b), divided by its length (a zero length gives (1,0) for the first and (0,1) for the second: eig of a
+ *      multiple of the identity); K(:,j) = x v0 + y v1.
+ *   3. Bit contract: this is the arithmetic and the summation order of the start of cpe_fit_cylinder_batch, so for the point
+ *      that start picks, Kdir[f,p,0,:] has the bits of cyl_raw[f,0,3:6].
+ *   4. CPE_CURV_INTERCEPT (build-defined): y is divided by its length before x = y x z (a unit frame), the row is
+ *      [lx^2, lx ly, ly^2, lx, ly, 1] and the solve has 6 unknowns; everything else as in mode 0.  L then holds the principal
+ *      curvatures in 1/mm up to the small-neighbourhood bias; mode 0's L are the reference's numbers, which are not.
+ * Outputs per point: Kdir f64[n,CPE_MAXP,2,3] (Kdir[.,p,j,:] = K(:,j,p), eigenvalues ascending), L f64[n,CPE_MAXP,2],
+ *   normal f64[n,CPE_MAXP,3] (the z that was used), nbr i32[n,CPE_MAXP,k] or NULL (the neighbours in rank order; ranks from K
+ *   on hold -1), pt_status u8[n,CPE_MAXP]: 0 good, 1 where the elimination meets a zero pivot or a result is not finite --
+ *   Kdir, L and normal of that point are then zero.  Every output of a slot past the count is zero.
+ * Output per frame: status i32[n] = CPE_ST_OK, or CPE_ST_FEW_POINTS when the count is below the number of unknowns; every
+ *   output of that frame is then zero.
+ * Asynchronous on `stream`, no allocation, no workspace, no host synchronisation, no atomics; a call repeats its bits and a
+ * frame's outputs do not depend on its place in the batch; n == 0 is a no-op. */
+#define CPE_CURV_REFERENCE 0 /* estCurvatures.m as it stands */
+#define CPE_CURV_INTERCEPT 1 /* build-defined: unit local frame, quadric with a constant term (6 unknowns) */
+#define CPE_CURV_MAXK 32
+#define CPE_CURV_K 20         /* knnsearch(..., 'K', 20) of estCurvatures.m */
+CPE_API int32_t cpe_est_curvatures_batch(const double *X, const int32_t *cnt, int32_t n, int32_t k, int32_t mode, double *Kdir,
+                                         double *L, double *normal, int32_t *nbr, uint8_t *pt_status, int32_t *status,
+                                         void *stream);
+
+/* BUILD-DEFINED (the reference has nothing like it): what a frame's curvatures say together, one wavefront per frame.
+ *   X, cnt and Kdir, L, normal, pt_status as cpe_est_curvatures_batch takes and leaves them; the gate: rho_max (the largest
+ *   |lambda|min / |lambda|max of a cylinder-like point; the Python layer's default is 0.25) and the open interval (r_min, r_max)
+ *   for 1 / |lambda|max (0 and +inf: no band); rho_max >= 0 and 0 <= r_min < r_max, otherwise CPE_ERR_ARG.
+ * A point below the count is gated in when pt_status is 0, |lambda|max > 0, |lambda|min / |lambda|max <= rho_max,
+ * r_min < 1 / |lambda|max < r_max, and the column of the smaller |lambda| has a finite length > 0 (|lambda|max is |L[1]| when
+ * |L[1]| > |L[0]|, else |L[0]|).  Over the gated points: t = that column / its length; dir = the eigenvector of sum t t' for
+ * its largest eigenvalue (Jacobi, as above) with its largest-magnitude component (the first of them) made positive, the sign
+ * rule of cpe_index_planes_batch; c = X + normal / lambda_big (signed), the centre of curvature; origin = mean of c; radius =
+ * the lower median of 1 / |lambda|max, the element of rank (g - 1) / 2, by exact selection on the bit patterns; spread = the
+ * rms distance of the c from the line (origin, dir).  All sums in the fixed lane-strided order and 64-lane tree.
+ *   axis f64[n,8] = origin[3], dir[3], radius, spread; n_gated i32[n]; gate u8[n,CPE_MAXP] (zero past the count);
+ *   status i32[n] = CPE_ST_OK, or CPE_ST_FEW_POINTS with axis zero when fewer than 3 points are gated in or a result is not
+ *   finite (gate and n_gated say what was gated all the same).
+ * Asynchronous on `stream`, no allocation, no workspace, no host synchronisation; n == 0 is a no-op. */
+CPE_API int32_t cpe_curvature_consensus_batch(const double *X, const int32_t *cnt, int32_t n, const double *Kdir, const double *L,
+                                              const double *normal, const uint8_t *pt_status, double rho_max, double r_min,
+                                              double r_max, double *axis, int32_t *n_gated, uint8_t *gate, int32_t *status,
+                                              void *stream);
 
 #ifdef __cplusplus
 }
