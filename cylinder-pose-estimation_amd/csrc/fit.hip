@@ -5496,3 +5496,378 @@ extern "C" int32_t cpe_curvature_consensus_batch(const double *X, const int32_t 
     CPE_CHECK_LAUNCH("k_curvature_consensus");
     return CPE_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// BUILD-DEFINED (include/cpe.h cpe_fit_cylinder_pixels_batch, whose numbered rule this follows): the cylinder pose that minimises
+// the PIXEL distance between every detection and the predicted pixel of its own grid node, in both images at once.
+// k_fit_cylinder_pixels: one wavefront per frame.  The two table families and their statuses are staged in LDS once (16 L x 4 B
+// + 2 L x 4 B, 18 KB at L = 256).  The detections are NOT staged: both tables are 98 KB per frame, which would leave one
+// wavefront per CU; they are re-read on every pass (24 B per detection, coalesced, L2-resident after the first pass: a frame of
+// 500 detections is 12 KB), and what a pass needs of a node (q, wh, tC: 60 flops from the two planes) is made again from LDS.
+// Lane l owns the detections l, l + 64, ... of the concatenated list (camera 1's slots, then camera 2's): at most 64 of them, so
+// membership of the used set S is one 64-bit register per lane, no LDS and no workspace.  Sums: every lane its own detections in
+// that order, then wave_sum.  Steps 3 - 9 of the prediction are restated from k_grid_predict, which is left alone (its
+// instructions may not change), as k_est_curvatures restated fit_init.
+namespace {
+
+// steps 3 - 9 of cpe_grid_predict_batch for the node of the planes pl0 (family 0) and pl1 (family 1) at the pose (oc, ah):
+// -> CPE_PRED_*; X and wh are set for CPE_PRED_OK
+__device__ __forceinline__ int pix_node(const double *pl0, const double *pl1, const double *oc, const double *ah, double R,
+                                        const double *centre, double min_cos, double *X, double *wh)
+{
+    const double n0[3] = {pl0[0], pl0[1], pl0[2]}, p0 = pl0[3];
+    const double n1[3] = {pl1[0], pl1[1], pl1[2]}, p1 = pl1[3];
+    double w[3], c1[3], c0[3];
+    cross3(n0, n1, w);
+    const double w2 = dot3(w, w);
+    if (!(w2 >= CPE_PRED_MIN_W2) || !isfinite(w2)) return CPE_PRED_PARALLEL;
+    cross3(n1, w, c1);
+    cross3(w, n0, c0);
+    const double wn = sqrt(w2);
+    double q[3], e[3], ep[3], wp[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        q[a] = ((-p0) * c1[a] - p1 * c0[a]) / w2;
+        wh[a] = w[a] / wn;
+        e[a] = q[a] - oc[a];
+    }
+    const double ea = dot3(e, ah), wa = dot3(wh, ah);
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        ep[a] = e[a] - ea * ah[a];
+        wp[a] = wh[a] - wa * ah[a];
+    }
+    const double A = dot3(wp, wp), B = dot3(ep, wp), Cq = dot3(ep, ep) - R * R;
+    const double disc = B * B - A * Cq;
+    if (!isfinite(A) || !isfinite(B) || !isfinite(Cq) || !isfinite(disc) || A == 0.0 || !(disc > 0)) return CPE_PRED_MISS;
+    const double s = sqrt(disc);
+    const double tm = (-B - s) / A, tp = (-B + s) / A;
+    const double cq[3] = {centre[0] - q[0], centre[1] - q[1], centre[2] - q[2]};
+    const double tC = dot3(cq, wh);
+    const double t = fabs(tm - tC) <= fabs(tp - tC) ? tm : tp;
+    double g[3], nu[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        X[a] = q[a] + t * wh[a];
+        g[a] = X[a] - oc[a];
+    }
+    if (!isfinite(X[0]) || !isfinite(X[1]) || !isfinite(X[2])) return CPE_PRED_MISS;
+    const double ga = dot3(g, ah);
+#pragma unroll
+    for (int a = 0; a < 3; a++) nu[a] = (g[a] - ga * ah[a]) / R;
+    if (!(fabs(dot3(nu, wh)) >= min_cos)) return CPE_PRED_GRAZING;
+    return CPE_PRED_OK;
+}
+
+// one detection's node at a pose: its point, the line's direction, the point in its camera and the residual (predicted - detected)
+struct PixEval {
+    double X[3], wh[3], Xc[3], r[2];
+    int cam;
+};
+
+struct PixProblem {
+    const double *xy1, *xy2;       // the frame's two tables (a table of an absent camera is never read: its count is 0)
+    const int *id1, *id2;
+    int n1, n12;                   // camera 1's count; both counts
+    const double *sP;              // LDS: P[2][L][4]
+    const int *sSt;                // LDS: line_status[2][L]
+    int lo, hi, L, swap;
+    double R, min_cos;
+    double centre[3];
+    TriCam cam1, cam2;
+    double t2[3];                  // camera 2's translation (camera 1's is 0)
+    int lane;
+    unsigned long long mine;       // bit i: the detection lane + 64 i belongs to S
+
+    // a / |a| -> false: the pose cannot be used (rule 1)
+    __device__ __forceinline__ static bool pose(const double *x, double *ah, double &an)
+    {
+        an = sqrt(dot3(x + 3, x + 3));
+        bool ok = isfinite(an) && an != 0.0;
+#pragma unroll
+        for (int a = 0; a < 6; a++) ok = ok && isfinite(x[a]);
+#pragma unroll
+        for (int a = 0; a < 3; a++) ah[a] = x[3 + a] / an;
+        return ok;
+    }
+    // camera c by selects: an index that differs between lanes would put both cameras into scratch memory
+    __device__ __forceinline__ void camera(int c, TriCam &o) const
+    {
+#pragma unroll
+        for (int a = 0; a < 9; a++) o.R[a] = c ? cam2.R[a] : cam1.R[a];
+        o.k0 = c ? cam2.k0 : cam1.k0; o.k1 = c ? cam2.k1 : cam1.k1; o.k2 = c ? cam2.k2 : cam1.k2;
+        o.k4 = c ? cam2.k4 : cam1.k4; o.k5 = c ? cam2.k5 : cam1.k5;
+    }
+    // rule 2's tests of the detection k of the concatenated list that do not depend on the pose -> its camera, pixel and planes
+    __device__ __forceinline__ bool detection(int k, int &c, double &px, double &py, const double *&pl0, const double *&pl1) const
+    {
+        c = k >= n1;
+        const int slot = c ? k - n1 : k;
+        const double *p = (c ? xy2 : xy1) + (size_t)slot * 2;
+        const int *v = (c ? id2 : id1) + (size_t)slot * 2;
+        px = p[0]; py = p[1];
+        const int u0 = v[swap], u1 = v[1 - swap];                          // the indices of table family 0 and 1
+        if (u0 < lo || u0 > hi || u1 < lo || u1 > hi) return false;        // (compared, not subtracted: an index may be any int)
+        const int l0 = u0 - lo, l1 = L + (u1 - lo);
+        if (sSt[l0] != CPE_ST_OK || sSt[l1] != CPE_ST_OK) return false;
+        pl0 = sP + 4 * l0; pl1 = sP + 4 * l1;
+        return isfinite(px) && isfinite(py);
+    }
+    // the node of a detection that passed detection(), at the pose (oc, ah) -> it exists, lies before its camera, and its pixel is finite
+    __device__ __forceinline__ bool eval(int c, double px, double py, const double *pl0, const double *pl1, const double *oc,
+                                         const double *ah, PixEval &e) const
+    {
+        e.cam = c;
+        if (pix_node(pl0, pl1, oc, ah, R, centre, min_cos, e.X, e.wh) != CPE_PRED_OK) return false;
+        TriCam cm;
+        camera(c, cm);
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+            e.Xc[r] = ((cm.R[3 * r] * e.X[0] + cm.R[3 * r + 1] * e.X[1]) + cm.R[3 * r + 2] * e.X[2]) + (c ? t2[r] : 0.0);
+        const double Z = e.Xc[2];
+        if (!(Z > 0)) return false;
+        const double xn = e.Xc[0] / Z, yn = e.Xc[1] / Z;
+        const double x = (cm.k0 * xn + cm.k1 * yn) + cm.k2;
+        const double y = cm.k4 * yn + cm.k5;
+        e.r[0] = x - px; e.r[1] = y - py;
+        return isfinite(x) && isfinite(y);
+    }
+    __device__ __forceinline__ bool eval_k(int k, const double *oc, const double *ah, PixEval &e) const
+    {
+        int c;
+        double px, py;
+        const double *pl0, *pl1;
+        return detection(k, c, px, py, pl0, pl1) && eval(c, px, py, pl0, pl1, oc, ah, e);
+    }
+
+    // rule 5
+    __device__ __forceinline__ double operator()(const double *x) const
+    {
+        double ah[3], an, acc = 0.0;
+        bool bad = !pose(x, ah, an);
+        for (int i = 0, k = lane; k < n12; i++, k += 64) {
+            if (!((mine >> i) & 1ull)) continue;
+            PixEval e;
+            if (!eval_k(k, x, ah, e)) { bad = true; continue; }
+            acc = acc + (e.r[0] * e.r[0] + e.r[1] * e.r[1]);
+        }
+        acc = wave_sum(acc);
+        return __ballot(bad) != 0ull ? __longlong_as_double(0x7ff8000000000000ll) : acc;
+    }
+    // rule 7: two rank-one rows per detection
+    __device__ __forceinline__ void normal(const double *x, double *A, double *g) const
+    {
+        double acc[27], ah[3], an;
+#pragma unroll
+        for (int k = 0; k < 27; k++) acc[k] = 0.0;
+        pose(x, ah, an);
+        for (int i = 0, k = lane; k < n12; i++, k += 64) {
+            if (!((mine >> i) & 1ull)) continue;
+            PixEval e;
+            if (!eval_k(k, x, ah, e)) continue;
+            const double gv[3] = {e.X[0] - x[0], e.X[1] - x[1], e.X[2] - x[2]};
+            const double ga = dot3(gv, ah);
+            const double gp[3] = {gv[0] - ga * ah[0], gv[1] - ga * ah[1], gv[2] - ga * ah[2]};
+            const double den = dot3(gp, e.wh);
+            double dt[6];
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                dt[a] = gp[a] / den;
+                dt[3 + a] = ((ga * gp[a]) / an) / den;
+            }
+            TriCam cm;
+            camera(e.cam, cm);
+            double v[3];
+#pragma unroll
+            for (int r = 0; r < 3; r++) v[r] = (cm.R[3 * r] * e.wh[0] + cm.R[3 * r + 1] * e.wh[1]) + cm.R[3 * r + 2] * e.wh[2];
+            const double Z = e.Xc[2], Z2 = Z * Z;
+            const double sx = ((cm.k0 / Z) * v[0] + (cm.k1 / Z) * v[1]) + (-(cm.k0 * e.Xc[0] + cm.k1 * e.Xc[1]) / Z2) * v[2];
+            const double sy = (cm.k4 / Z) * v[1] + (-(cm.k4 * e.Xc[1]) / Z2) * v[2];
+            double j[6];
+#pragma unroll
+            for (int a = 0; a < 6; a++) j[a] = sx * dt[a];
+            normal_accumulate<6>(j, e.r[0], acc);
+#pragma unroll
+            for (int a = 0; a < 6; a++) j[a] = sy * dt[a];
+            normal_accumulate<6>(j, e.r[1], acc);
+        }
+#pragma unroll
+        for (int k = 0; k < 21; k++) A[k] = wave_sum(acc[k]);
+#pragma unroll
+        for (int k = 0; k < 6; k++) g[k] = wave_sum(acc[21 + k]);
+    }
+    __device__ __forceinline__ bool candidate(const double *x, const double *dl, double *xn) const
+    {
+#pragma unroll
+        for (int k = 0; k < 6; k++) xn[k] = x[k] + dl[k];
+        return true;
+    }
+};
+
+struct PixOut {
+    double *cyl, *fvals;
+    int *iters, *counts;
+    double *stats;
+    int *status;
+    double *res;                   // optional from here on
+    int *pt_state;
+    double *X;
+};
+
+__global__ __launch_bounds__(64) void k_fit_cylinder_pixels(const double *__restrict__ xy1, const int *__restrict__ id1,
+                                                            const int *__restrict__ cnt1, const double *__restrict__ xy2,
+                                                            const int *__restrict__ id2, const int *__restrict__ cnt2,
+                                                            const double *__restrict__ cyl0, const unsigned char *__restrict__ use, double R,
+                                                            const double *__restrict__ K1, const double *__restrict__ K2,
+                                                            const double *__restrict__ T21, const double *__restrict__ P,
+                                                            const int *__restrict__ line_status, int lo, int L,
+                                                            const double *__restrict__ centre, int swap, double min_cos, double gate_px,
+                                                            double tolx, double tolf, int maxiter, const PixOut out)
+{
+    __shared__ double sP[2 * CPE_MAXL * 4];
+    __shared__ int sSt[2 * CPE_MAXL];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    for (int i = lane; i < 8 * L; i += 64) sP[i] = P[i];
+    for (int i = lane; i < 2 * L; i += 64) sSt[i] = line_status[i];
+    __syncthreads();
+    const size_t tb = (size_t)f * MAXP * 2;
+    PixProblem prob;
+    prob.xy1 = xy1 ? xy1 + tb : nullptr; prob.xy2 = xy2 ? xy2 + tb : nullptr;
+    prob.id1 = id1 ? id1 + tb : nullptr; prob.id2 = id2 ? id2 + tb : nullptr;
+    const int n1 = xy1 ? min(max(cnt1[f], 0), MAXP) : 0, n2 = xy2 ? min(max(cnt2[f], 0), MAXP) : 0;
+    prob.n1 = n1; prob.n12 = n1 + n2;
+    prob.sP = sP; prob.sSt = sSt;
+    prob.lo = lo; prob.hi = lo + (L - 1); prob.L = L; prob.swap = swap;
+    prob.R = R; prob.min_cos = min_cos;
+#pragma unroll
+    for (int a = 0; a < 3; a++) { prob.centre[a] = centre[a]; prob.t2[a] = T21[4 * a + 3]; }
+    tri_cam(K1, nullptr, prob.cam1);
+    tri_cam(K2, T21, prob.cam2);
+    prob.lane = lane;
+    prob.mine = 0ull;
+
+    // rule 1
+    double x0[6], ah0[3], an0;
+#pragma unroll
+    for (int a = 0; a < 6; a++) x0[a] = cyl0[(size_t)f * 6 + a];
+    const bool frame_ok = PixProblem::pose(x0, ah0, an0) && (!use || use[f] != 0);
+
+    // rules 2, 3: the used set, once
+    unsigned long long gated = 0ull;
+    int c1 = 0, c2 = 0, c_ref = 0, c_gate = 0;
+    double f0 = 0.0;
+    if (frame_ok) {
+        for (int i = 0, k = lane; k < prob.n12; i++, k += 64) {
+            PixEval e;
+            if (!prob.eval_k(k, x0, ah0, e)) { c_ref++; continue; }
+            const double r2 = e.r[0] * e.r[0] + e.r[1] * e.r[1];
+            if (gate_px > 0 && sqrt(r2) >= gate_px) { gated |= 1ull << i; c_gate++; continue; }
+            prob.mine |= 1ull << i;
+            c1 += k < n1; c2 += k >= n1;
+            f0 = f0 + r2;
+        }
+        c1 = wave_sum_i(c1); c2 = wave_sum_i(c2); c_ref = wave_sum_i(c_ref); c_gate = wave_sum_i(c_gate);
+        f0 = wave_sum(f0);
+    }
+    // rules 4, 6, 8
+    double xf[6] = {0, 0, 0, 0, 0, 0}, ffinal = 0.0;
+    int itercount = 0, func_evals = 0;
+    bool ok = frame_ok && c1 + c2 >= CPE_PIXFIT_MIN_PTS;
+    if (ok) {
+        func_evals = 1;
+        lm_minimize<6>(prob, x0, f0, tolx, tolf, maxiter, xf, ffinal, itercount, func_evals);
+        ok = fit_finite(xf, ffinal);
+    }
+    // the outputs: every slot of the frame
+    double ahf[3], anf, s1 = 0.0, s2 = 0.0, rmax = 0.0;
+    if (ok) PixProblem::pose(xf, ahf, anf);
+    for (int i = 0, k = lane; k < prob.n12; i++, k += 64) {
+        const int c = k >= n1, slot = c ? k - n1 : k;
+        const size_t at = ((size_t)f * 2 + c) * MAXP + slot;
+        const bool used = (prob.mine >> i) & 1ull;
+        double r[2] = {0, 0}, Xn[3] = {0, 0, 0};
+        if (ok && used) {
+            PixEval e;
+            if (prob.eval_k(k, xf, ahf, e)) {                                  // (it does: F(xf) is finite)
+                r[0] = e.r[0]; r[1] = e.r[1];
+                Xn[0] = e.X[0]; Xn[1] = e.X[1]; Xn[2] = e.X[2];
+                const double r2 = r[0] * r[0] + r[1] * r[1];
+                if (c) s2 = s2 + r2; else s1 = s1 + r2;
+                rmax = fmax(rmax, sqrt(r2));
+            }
+        }
+        if (out.res) { out.res[at * 2] = r[0]; out.res[at * 2 + 1] = r[1]; }
+        if (out.X) { out.X[at * 3] = Xn[0]; out.X[at * 3 + 1] = Xn[1]; out.X[at * 3 + 2] = Xn[2]; }
+        if (out.pt_state) out.pt_state[at] = used ? 0 : (((gated >> i) & 1ull) ? 2 : 1);
+    }
+    for (int c = 0; c < 2; c++)
+        for (int slot = (c ? n2 : n1) + lane; slot < MAXP; slot += 64) {
+            const size_t at = ((size_t)f * 2 + c) * MAXP + slot;
+            if (out.res) { out.res[at * 2] = 0; out.res[at * 2 + 1] = 0; }
+            if (out.X) { out.X[at * 3] = 0; out.X[at * 3 + 1] = 0; out.X[at * 3 + 2] = 0; }
+            if (out.pt_state) out.pt_state[at] = -1;
+        }
+    s1 = wave_sum(s1); s2 = wave_sum(s2);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) rmax = fmax(rmax, __shfl_xor(rmax, off, 64));
+    if (lane == 0) {
+        for (int a = 0; a < 6; a++) out.cyl[(size_t)f * 6 + a] = ok ? xf[a] : 0.0;
+        out.fvals[2 * (size_t)f] = ok ? f0 : 0.0;
+        out.fvals[2 * (size_t)f + 1] = ok ? ffinal : 0.0;
+        out.iters[2 * (size_t)f] = ok ? itercount : 0;
+        out.iters[2 * (size_t)f + 1] = ok ? func_evals : 0;
+        int *oc = out.counts + 4 * (size_t)f;
+        oc[0] = c1; oc[1] = c2; oc[2] = c_ref; oc[3] = c_gate;
+        double *os = out.stats + 4 * (size_t)f;
+        os[0] = ok && c1 > 0 ? sqrt(s1 / (double)c1) : 0.0;
+        os[1] = ok && c2 > 0 ? sqrt(s2 / (double)c2) : 0.0;
+        os[2] = ok ? sqrt(ffinal / (double)(c1 + c2)) : 0.0;
+        os[3] = ok ? rmax : 0.0;
+        out.status[f] = ok ? CPE_ST_OK : CPE_ST_FEW_POINTS;
+    }
+}
+}  // namespace
+
+extern "C" int32_t cpe_fit_cylinder_pixels_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
+                                                 const int32_t *id2, const int32_t *cnt2, const double *cyl0, const uint8_t *use,
+                                                 int32_t n, double radius, const double *K1, const double *K2, const double *T21,
+                                                 const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
+                                                 const double *centre, int32_t swap, double min_cos, double gate_px, double tol_x,
+                                                 double tol_f, int32_t max_iter, double *cyl, double *fvals, int32_t *iters,
+                                                 int32_t *counts, double *stats, int32_t *status, double *res, int32_t *pt_state,
+                                                 double *X, void *stream)
+{
+    CPE_CHECK_ARG(n >= 0, "cpe_fit_cylinder_pixels_batch: n < 0");
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_fit_cylinder_pixels_batch: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    CPE_CHECK_ARG(radius > 0 && radius <= DBL_MAX, "cpe_fit_cylinder_pixels_batch: radius must be positive and finite");
+    const struct { int swap; double min_cos, tol_x, tol_f; int max_iter; } p = {swap, min_cos, tol_x, tol_f, max_iter};
+    CPE_CHECK_ARG(p.min_cos > 0 && p.min_cos < 1 && (p.swap == 0 || p.swap == 1) && p.tol_x > 0 && p.tol_f > 0 && p.max_iter >= 1,
+                  "cpe_fit_cylinder_pixels_batch: bad parameters (0 < min_cos < 1, swap 0 or 1, tol_x > 0, tol_f > 0, max_iter >= 1)");
+    const bool cam1 = xy1 && id1 && cnt1, cam2 = xy2 && id2 && cnt2;
+    CPE_CHECK_ARG((cam1 || (!xy1 && !id1 && !cnt1)) && (cam2 || (!xy2 && !id2 && !cnt2)) && (cam1 || cam2),
+                  "cpe_fit_cylinder_pixels_batch: a camera is given by all three of xy, id, cnt or by none, and one camera at least");
+    if (n == 0) return CPE_OK;
+    CPE_CHECK_ARG(cyl0 && K1 && K2 && T21 && P && line_status && centre && cyl && fvals && iters && counts && stats && status,
+                  "cpe_fit_cylinder_pixels_batch: null pointer");
+    const int L = hi - lo + 1;
+    {
+        const size_t N = (size_t)n, Pp = (size_t)CPE_MAXP;
+        const struct { const void *p; size_t bytes; } buf[23] = {
+            {xy1, cam1 ? N * Pp * 16 : 0}, {id1, cam1 ? N * Pp * 8 : 0}, {cnt1, cam1 ? N * 4 : 0}, {xy2, cam2 ? N * Pp * 16 : 0},
+            {id2, cam2 ? N * Pp * 8 : 0}, {cnt2, cam2 ? N * 4 : 0}, {cyl0, N * 48}, {use, use ? N : 0}, {K1, 72}, {K2, 72}, {T21, 128},
+            {P, (size_t)L * 64}, {line_status, (size_t)L * 8}, {centre, 24},
+            {cyl, N * 48}, {fvals, N * 16}, {iters, N * 8}, {counts, N * 16}, {stats, N * 32}, {status, N * 4},
+            {res, res ? N * Pp * 32 : 0}, {pt_state, pt_state ? N * Pp * 8 : 0}, {X, X ? N * Pp * 48 : 0}};
+        for (int o = 14; o < 23; o++)
+            for (int i = 0; i < o; i++)
+                CPE_CHECK_ARG(!buf[o].bytes || !buf[i].bytes || !rl_overlap(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes),
+                              "cpe_fit_cylinder_pixels_batch: an output overlaps an input or another output");
+    }
+    const PixOut out = {cyl, fvals, iters, counts, stats, status, res, pt_state, X};
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_fit_cylinder_pixels, dim3(n), dim3(64), 0, (hipStream_t)stream, xy1, id1, cnt1, xy2, id2, cnt2, cyl0, use, radius, K1, K2,
+                T21, P, line_status, lo, L, centre, p.swap, p.min_cos, gate_px, p.tol_x, p.tol_f, p.max_iter, out);
+    CPE_CHECK_LAUNCH("k_fit_cylinder_pixels");
+    return CPE_OK;
+}

@@ -215,7 +215,7 @@ def repair_listing(names, shift, flags, round_taken, renumbered):
 
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
                    frame_angles=False, match_offset=None, laser_table=None, source='stereo', projector=None, table_path=None,
-                   curvature=None, consensus=None, refine=None, repair=None):
+                   curvature=None, consensus=None, refine=None, pixels=None, repair=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
@@ -296,7 +296,16 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     curvature: None, or a dict of k, mode, rho_max, band, r_min, r_max ({} = 20, fit.CURV_INTERCEPT, 0.25 and the band radius
     (1 -/+ 1/3); build-defined): fit.est_curvatures_batch and fit.curvature_consensus_batch run on the pts3 / cnt the run holds
     anyway, and the dict gains curvature = their two dicts merged (Kdir, L, normal, pt_status, axis, n_gated, gate, status = the
-    consensus', curv_status = the per-frame status of the curvatures).  The fits of the run are untouched."""
+    consensus', curv_status = the per-frame status of the curvatures).  The fits of the run are untouched.
+
+    pixels= with source 'fused', 'left' or 'right' (build-defined, opt-in): None, or a dict of fit.fit_cylinder_pixels_batch keywords
+    ({} = its defaults): every frame's pose is polished on the pixels of the tables its fit was made from (FramePipeline(pixels=...),
+    fit.polish_with_pixels; after refine= / repair= on the re-numbered tables).  records, cyl_raw and the multi-frame fit then read
+    the polished poses, and the dict gains pixels = dict(cyl f64 [F,6] (the polished cyl[:, 1]), T f64 [F,4,4], fvals f64 [F,2]
+    (px^2 at the start and the end), px_rms f64 [F] (of both cameras), counts i32 [F,4], status i32 [F] (the pixel fit's; a frame
+    whose pixel fit is not ST_OK keeps its 3-D fit)).  source='stereo' raises ValueError."""
+    if pixels is not None and source == 'stereo':
+        raise ValueError("pixels= predicts the pixels from the laser-plane table: source must be 'fused', 'left' or 'right'")
     if curvature is not None:
         curv_opts = fit._curvature_options('run_experiment', curvature, float(radius))
     if repair is not None and source not in ('left', 'right'):
@@ -317,13 +326,15 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
         f = pipeline.alloc_fits(F, dev, source=source, refine=refine is not None)
         if repair is not None:
             f.update({k: torch.zeros((F,) + shape, dtype=dt, device=dev) for k, (shape, dt) in pipeline.MONO_REPAIR_OUTPUTS.items()})
+        if pixels is not None:
+            f.update({k: torch.zeros((F,) + shape, dtype=dt, device=dev) for k, (shape, dt) in pipeline.PIXELS_OUTPUTS.items()})
         if projector is not None:        # the model needs the points' indices, which the selector returns beside the points
             f['idx'] = torch.zeros((F, fit.MAXP, 2), dtype=torch.int32, device=dev)
         return f
     recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, make_fits,
                             lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=c, device=dev, match=match_offset,
                                                                    source=source, laser_table=laser_table, refine=refine,
-                                                                   table=mono_table), source)
+                                                                   table=mono_table, pixels=pixels), source)
     F = len(names)
     # frame_ok: the device mask of the frames that are not in `skipped`; the resident multi-frame modes mask with it
     frame_ok, skipped, _ = _frame_status(names, recs, None if match_offset is None else fits['match_flags'])
@@ -341,6 +352,9 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
                              frames=refine_listing(names, fits['round_taken'], fits['renumbered']))
     elif source != 'stereo':
         res.update(tri_counts=fits['counts'], tri_stats=fits['stats'])
+    if pixels is not None:
+        res['pixels'] = dict(cyl=fits['cyl'][:, 1], T=fits['T'], fvals=fits['pixels_fvals'], px_rms=fits['pixels_stats'][:, 2],
+                             counts=fits['pixels_counts'], status=fits['pixels_status'])
     if repair is not None:
         res['repair'] = dict(shift=fits['shift'], flags=fits['shift_flags'], round_taken=fits['round_taken'], renumbered=fits['renumbered'],
                              frames=repair_listing(names, fits['shift'], fits['shift_flags'], fits['round_taken'], fits['renumbered']))

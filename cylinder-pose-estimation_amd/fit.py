@@ -842,7 +842,7 @@ _REFINE_KEYS = ('cyl_raw', 'cyl', 'T', 'fvals', 'iters', 'status', 'pts3', 'idx'
 
 def fit_single_cylinder_refined_batch(gp1: GridTables, gp2: GridTables, K1, K2, T21, table: LaserTable, radius, rounds=2, first=None,
                                       tau_px=4.0, ratio=0.5, window=None, min_cos=0.1, image_size=None, fused=None, mode=FIT_LM,
-                                      **fit_kw):
+                                      pixels=None, **fit_kw):
     """BUILD-DEFINED, opt-in: fit_single_cylinder_batch, then `rounds` rounds that re-number every grid point against the grid
     the frame's own fitted cylinder predicts and fit again on fused points.
     First fit_single_cylinder_batch(gp1, gp2, K1, K2, T21, radius, **first) (first: its keywords, match= included; None = the
@@ -856,7 +856,9 @@ def fit_single_cylinder_refined_batch(gp1: GridTables, gp2: GridTables, K1, K2, 
             GridTables that result was made from (the re-numbered ones where a round was taken); round_taken i32[n]: the last
             round taken, 0 = the first fit stands; renumbered i32[n,2]: points of image 1, 2 whose index that round changed;
             rounds: per round dict(counts i32[n,2,8], stats f64[n,2,2] of grid_assign_batch per image, status i32[n] of the
-            round's fit, taken bool[n]); first: the first call's dict)"""
+            round's fit, taken bool[n]); first: the first call's dict)
+    pixels: None, or a dict of fit_cylinder_pixels_batch keywords ({} = its defaults): the result is polished on tables1, tables2 by
+    polish_with_pixels, whose keys the dict gains; without it nothing here changes."""
     rounds = int(rounds)
     if rounds < 0:
         raise ValueError('fit_single_cylinder_refined_batch: rounds < 0')
@@ -889,6 +891,8 @@ def fit_single_cylinder_refined_batch(gp1: GridTables, gp2: GridTables, K1, K2, 
                               status=fit['status'], taken=take))
     out = dict(cur)
     out.update(tables1=t1, tables2=t2, round_taken=taken_round, renumbered=renum, rounds=per_round, first=first_out)
+    if pixels is not None:
+        out = polish_with_pixels(out, t1, t2, K1, K2, T21, table, radius, pixels)
     return out
 
 
@@ -954,14 +958,19 @@ def fit_projector_model_renumbered(pts3, idx, cnt, lo, hi, use=None, frame_ok=No
 
 
 def fit_single_cylinder_mono_batch(gp: GridTables, K, Tc, table: LaserTable, radius, ransac=None, mode=FIT_NELDER_MEAD, need_both=False,
-                                   min_sin=0.01, max_res=0.0, **fit_kw):
+                                   min_sin=0.01, max_res=0.0, pixels=None, **fit_kw):
     """BUILD-DEFINED, fit_single_cylinder_batch from one camera: table_triangulate_batch, then fit_cylinder_batch (ransac: a
     dict of fit_cylinder_ransac_batch keywords) on its points with cnt = m.
     -> the fit's keys (cyl_raw, cyl, T, fvals, iters, status[, n_inliers, inlier_mask]) beside pts3, idx, m, counts, res, src,
     stats and mean_err f64[n] = stats[:, 0]: NOT a reprojection error in pixels as in the stereo call, but the rms distance in mm
-    of the points from the planes that made them (0 for points cut with one plane only)."""
+    of the points from the planes that made them (0 for points cut with one plane only).
+    pixels: None, or a dict of fit_cylinder_pixels_batch keywords ({} = its defaults): the result is polished on gp by
+    polish_with_pixels (this camera alone), whose keys the dict gains; without it nothing here changes."""
     tri = table_triangulate_batch(gp, K, Tc, table, need_both=need_both, min_sin=min_sin, max_res=max_res)
-    return dict(tri, **_fit_points(tri['pts3'], tri['m'], radius, ransac, mode=mode, **fit_kw), mean_err=tri['stats'][:, 0])
+    out = dict(tri, **_fit_points(tri['pts3'], tri['m'], radius, ransac, mode=mode, **fit_kw), mean_err=tri['stats'][:, 0])
+    if pixels is not None:
+        out = polish_mono_with_pixels(out, gp, K, Tc, table, radius, pixels)
+    return out
 
 
 MONO_SHIFT_MAX_TOP_K = 8
@@ -1112,3 +1121,143 @@ def fit_single_cylinder_mono_repaired_batch(gp: GridTables, cam, K1, K2, T21, ta
     out.update(shift=applied, shift_flags=flags, vote_flags=vote_flags, shift_score=shift_score, cand=cand, cand_score=cand_score,
                cand_rms=cand_rms, tables=tables, round_taken=taken_round, renumbered=renum, rounds=per_round, first=first)
     return out
+
+
+PIXFIT_MIN_PTS = _c.PIXFIT_MIN_PTS
+_PIX_WANT = ('res', 'pt_state', 'X')
+
+
+def fit_cylinder_pixels_batch(gp1: Optional[GridTables], gp2: Optional[GridTables], cyl0, radius, K1, K2, T21, table: LaserTable, use=None,
+                              gate_px=0.0, min_cos=0.1, ids='col_row', want=('res',), tol_x=1e-9, tol_f=1e-9, max_iter=100):
+    """BUILD-DEFINED, opt-in: the cylinder pose that minimises the pixel distance between every detection and the predicted pixel of
+    its own grid node, in both images at once; see include/cpe.h cpe_fit_cylinder_pixels_batch.  gp1, gp2:
+    the two cameras' tables, either may be None (that camera is absent); cyl0 f64[n,6]: the start, e.g. fit_cylinder_batch(...)
+    ['cyl'][:, 1]; use: bool / u8 [n] or None; gate_px <= 0: no gate; ids as table_triangulate_batch; want: which of the optional
+    per-detection outputs 'res', 'pt_state', 'X' to make.  The indices are trusted: re-number first (grid_assign_batch).  A table
+    without a projector centre is refused, as grid_predict_batch does.
+    -> dict(cyl f64[n,6] (raw: no prior applied), fvals f64[n,2] (F at the start, at the end; px^2), iters i32[n,2], counts i32[n,4]
+            (used of camera 1, of camera 2, refused, gated), stats f64[n,4] (rms of camera 1, of camera 2, of both, largest
+            residual; px), status i32[n], res f64[n,2,MAXP,2], pt_state i32[n,2,MAXP], X f64[n,2,MAXP,3] (None unless wanted))"""
+    what = 'fit_cylinder_pixels_batch'
+    L = _lib.load()
+    if gp1 is None and gp2 is None:
+        raise ValueError(f'{what}: both cameras are absent')
+    if not table.has_centre():
+        raise ValueError(f'{what}: the table has no projector centre (centre_status is not ST_OK)')
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(w not in _PIX_WANT for w in want):
+        raise ValueError(f'{what}: want holds {want}, known: {_PIX_WANT}')
+    if cyl0.dtype != torch.float64 or cyl0.dim() != 2 or cyl0.shape[1] != 6:
+        raise TypeError(f'{what}: cyl0 must be float64 [n,6], got {cyl0.dtype} {list(cyl0.shape)}')
+    if not (0 < min_cos < 1 and tol_x > 0 and tol_f > 0 and int(max_iter) >= 1 and radius > 0):
+        raise ValueError(f'{what}: min_cos in (0, 1), tol_x, tol_f, radius > 0 and max_iter >= 1, got {min_cos}, {tol_x}, {tol_f}, {radius}, '
+                         f'{max_iter}')
+    dev, n = cyl0.device, cyl0.shape[0]
+    cyl0 = cyl0.contiguous()
+    for name, gp in (('gp1.', gp1), ('gp2.', gp2)):
+        if gp is not None:
+            _check_tables(what, gp, n, name, dev)
+    if use is not None:
+        use = use.to(device=dev, dtype=torch.uint8).contiguous()
+        if tuple(use.shape) != (n,):
+            raise TypeError(f'{what}: use must be [{n}], got {list(use.shape)}')
+    K1, K2, T21 = _cameras(K1, K2, T21, dev)
+    P, st, centre = _table_on(table, dev, centre=True)
+    # (the kernel writes every slot of every output: no fills)
+    cyl, fvals, stats = _slab(dev, torch.float64, False, n, [('cyl', (6,)), ('fvals', (2,)), ('stats', (4,))]).values()
+    iters, counts, status = _slab(dev, torch.int32, False, n, [('iters', (2,)), ('counts', (4,)), ('status', ())]).values()
+    res = torch.empty((n, 2, MAXP, 2), dtype=torch.float64, device=dev) if 'res' in want else None
+    pt = torch.empty((n, 2, MAXP), dtype=torch.int32, device=dev) if 'pt_state' in want else None
+    X = torch.empty((n, 2, MAXP, 3), dtype=torch.float64, device=dev) if 'X' in want else None
+    c = lambda gp: (None, None, None) if gp is None or n == 0 else (gp.xy.contiguous(), gp.id.contiguous(), gp.cnt.contiguous())
+    t1, t2 = c(gp1), c(gp2)
+    if n:
+        _lib.check(L.cpe_fit_cylinder_pixels_batch(*(_ptr(t) for t in t1), *(_ptr(t) for t in t2), _ptr(cyl0), _ptr(use), n, float(radius),
+                                                   K1.data_ptr(), K2.data_ptr(), T21.data_ptr(), P.data_ptr(), st.data_ptr(), table.lo, table.hi,
+                                                   centre.data_ptr(), table.swap_for(ids), float(min_cos), float(gate_px), float(tol_x),
+                                                   float(tol_f), int(max_iter), _ptr(cyl), _ptr(fvals), _ptr(iters), _ptr(counts), _ptr(stats),
+                                                   _ptr(status), _ptr(res), _ptr(pt), _ptr(X), _stream()), 'cpe_fit_cylinder_pixels_batch')
+    return dict(cyl=cyl, fvals=fvals, iters=iters, counts=counts, stats=stats, status=status, res=res, pt_state=pt, X=X)
+
+
+def _prior_rows(rows, ymin):
+    """applyCylParamsPrior.m on rows f64[n,k,6] with the points' smallest y, ymin f64[n]: the direction with d_y >= 0 and the axis
+    point at that y (the arithmetic of cpe_fit_cylinder_batch's epilogue) -> f64[n,k,6]"""
+    o, d = rows[..., :3], rows[..., 3:]
+    d = torch.where(d[..., 1:2] < 0, -d, d)
+    dy = d[..., 1]
+    flat = dy.abs() < torch.finfo(torch.float64).eps
+    t = torch.where(flat, torch.zeros_like(dy), (ymin[:, None] - o[..., 1]) / torch.where(flat, torch.ones_like(dy), dy))
+    return torch.cat([o + t[..., None] * d, d], -1)
+
+
+def _cyl_to_T(cyl):
+    """cylParams2T.m on cyl f64[n,6] -> f64[n,4,4]: y along the axis, z = (1, 0, 0) x y, x = y x z, the origin at the axis point"""
+    y = cyl[:, 3:] / cyl[:, 3:].norm(dim=1, keepdim=True)
+    z = torch.stack([torch.zeros_like(y[:, 0]), -y[:, 2], y[:, 1]], 1)
+    z = z / z.norm(dim=1, keepdim=True)
+    x = torch.linalg.cross(y, z)
+    x = x / x.norm(dim=1, keepdim=True)
+    T = torch.zeros((cyl.shape[0], 4, 4), dtype=cyl.dtype, device=cyl.device)
+    T[:, :3, 0], T[:, :3, 1], T[:, :3, 2], T[:, :3, 3], T[:, 3, 3] = x, y, z, cyl[:, :3], 1.0
+    return T
+
+
+def _pixels_options(what, pixels):
+    o = dict(pixels or {})
+    if 'want' in o or 'use' in o:
+        raise ValueError(f"{what}: pixels may not set 'want' or 'use' (the polish needs the nodes' points and runs on the ST_OK frames)")
+    return o
+
+
+def fit_single_cylinder_pixels_batch(gp1: Optional[GridTables], gp2: Optional[GridTables], K1, K2, T21, table: LaserTable, radius,
+                                     start=None, **pixels):
+    """BUILD-DEFINED, opt-in: a start, then fit_cylinder_pixels_batch from it on the frames whose start is ST_OK.
+    start: None = fit_single_cylinder_fused_batch(gp1, gp2, K1, K2, T21, table, radius, mode=FIT_LM) (both cameras needed), or the
+    caller's dict with cyl, cyl_raw f64[n,2,6], T f64[n,4,4] and status i32[n] (any fit of this module).  pixels: keywords of
+    fit_cylinder_pixels_batch (gate_px, min_cos, ids, tol_x, tol_f, max_iter).  The pixel fit starts at start['cyl'][:, 1].  Its
+    result gets the conventions of fit_cylinder_batch: cyl_raw = [the start pose; the fitted pose], cyl = applyCylParamsPrior on
+    both rows with the nodes' 3-D points X of the used detections as the points (in torch, on the device), T = cylParams2T of the
+    final row.  A frame keeps the start's cyl_raw, cyl and T when the pixel fit is not ST_OK: a torch.where, nothing waits.
+    -> dict(cyl_raw, cyl f64[n,2,6], T f64[n,4,4], status i32[n] (the start's), taken bool[n] (the pixel fit's result stands),
+            start (its dict), pixels (fit_cylinder_pixels_batch's dict, want = res, pt_state, X))"""
+    what = 'fit_single_cylinder_pixels_batch'
+    opts = _pixels_options(what, pixels)
+    if start is None:
+        if gp1 is None or gp2 is None:
+            raise ValueError(f'{what}: the default start is the fused fit of both cameras; give start= for one camera')
+        start = fit_single_cylinder_fused_batch(gp1, gp2, K1, K2, T21, table, radius, mode=FIT_LM)
+    ok0 = start['status'] == ST_OK
+    cyl0 = start['cyl'][:, 1].contiguous()
+    px = fit_cylinder_pixels_batch(gp1, gp2, cyl0, radius, K1, K2, T21, table, use=ok0, want=_PIX_WANT, **opts)
+    taken = ok0 & (px['status'] == ST_OK)
+    n = cyl0.shape[0]
+    used = px['pt_state'].reshape(n, -1) == 0
+    ymin = torch.where(used, px['X'].reshape(n, -1, 3)[..., 1], torch.full((), math.inf, dtype=torch.float64, device=cyl0.device)).amin(1)
+    ymin = torch.where(taken, ymin, torch.zeros_like(ymin))
+    raw = torch.stack([cyl0, px['cyl']], 1)
+    cyl = _prior_rows(raw, ymin)
+    T = _cyl_to_T(torch.where(taken[:, None], cyl[:, 1], start['cyl'][:, 1]))
+    pick = lambda a, b: torch.where(taken.view((n,) + (1,) * (a.dim() - 1)), a, b)
+    return dict(cyl_raw=pick(raw, start['cyl_raw']), cyl=pick(cyl, start['cyl']), T=pick(T, start['T']), status=start['status'], taken=taken,
+                start=start, pixels=px)
+
+
+def polish_with_pixels(out, gp1: Optional[GridTables], gp2: Optional[GridTables], K1, K2, T21, table: LaserTable, radius, pixels):
+    """BUILD-DEFINED, opt-in: the result `out` of any cylinder fit of this module (cyl, cyl_raw, T, status) polished by
+    fit_single_cylinder_pixels_batch(gp1, gp2, ..., start=out, **pixels) -> a copy of out whose cyl_raw, cyl and T are the pixel
+    fit's where that is ST_OK (every other key stays: fvals, iters and mean_err describe the 3-D fit), beside pixels (the dict of
+    fit_cylinder_pixels_batch) and, flat for FramePipeline.run_raw, pixels_taken bool[n], pixels_fvals f64[n,2], pixels_stats
+    f64[n,4], pixels_counts i32[n,4], pixels_status i32[n]"""
+    pol = fit_single_cylinder_pixels_batch(gp1, gp2, K1, K2, T21, table, radius, start=out, **pixels)
+    px = pol['pixels']
+    return dict(out, cyl_raw=pol['cyl_raw'], cyl=pol['cyl'], T=pol['T'], pixels=px, pixels_taken=pol['taken'], pixels_fvals=px['fvals'],
+                pixels_stats=px['stats'], pixels_counts=px['counts'], pixels_status=px['status'])
+
+
+def polish_mono_with_pixels(out, gp: GridTables, K, Tc, table: LaserTable, radius, pixels):
+    """polish_with_pixels for ONE camera's tables, with K, Tc as table_triangulate_batch takes them (Tc None: camera 1)"""
+    eye = torch.eye(4, dtype=torch.float64)
+    if Tc is None:
+        return polish_with_pixels(out, gp, None, K, K, eye, table, radius, pixels)
+    return polish_with_pixels(out, None, gp, K, K, Tc, table, radius, pixels)

@@ -59,6 +59,10 @@ REFINED_FIT_OUTPUTS = dict(_POINTS, **_CYL, round_taken=((), _I32), renumbered=(
 # .run_raw keeps them when the fits dict holds tensors of these names
 MONO_REPAIR_OUTPUTS = dict(shift=((2,), _I32), shift_flags=((), _I32), shift_score=((4,), _I32), round_taken=((), _I32),
                            renumbered=((), _I32))
+# what fit.polish_with_pixels adds per frame; FramePipeline(pixels=...).run_raw keeps them when the fits dict holds tensors of
+# these names
+PIXELS_OUTPUTS = dict(pixels_taken=((), torch.bool), pixels_fvals=((2,), _F64), pixels_stats=((4,), _F64), pixels_counts=((4,), _I32),
+                      pixels_status=((), _I32))
 
 
 # ---- the two record layouts (beside REC) ----
@@ -182,7 +186,7 @@ class FramePipeline:
 
     def __init__(self, h, w, K1, K2, T21, radius, chunk=64, device='cuda:0', selector=fit.SEL_CHOOSE_IDX, th=0.3,
                  fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full', match=None, target='cylinder', plane=None,
-                 source='stereo', laser_table=None, table=None, relabel=None, refine=None):
+                 source='stereo', laser_table=None, table=None, relabel=None, refine=None, pixels=None):
         # ---- which combinations exist: the rows of _MODES; everything else is refused here ----
         if stage not in ('full', 'detect'):
             raise ValueError("stage is 'full' or 'detect'")
@@ -221,6 +225,13 @@ class FramePipeline:
             if refine.get('window') is None and nodes > fit.PRED_MAXN:
                 raise ValueError(f'refine=: the table holds {nodes} nodes, more than {fit.PRED_MAXN}: give window=')
             refine = dict(dict(image_size=(h, w), first=dict(selector=selector, th=th, mode=fit_mode)), **refine)
+        if pixels is not None:
+            if target == 'plane':
+                raise ValueError("pixels= fits a cylinder's pose to the pixels: target='cylinder' only")
+            if source == 'stereo':
+                raise ValueError("pixels= predicts the pixels from the laser-plane table: source='fused', 'left' or 'right' with "
+                                 "laser_table=")
+            fit._pixels_options('FramePipeline', pixels)
         self.mode = _mode_name(target, source, stage, refine is not None)     # a key of _MODES
         self.h, self.w, self.chunk, self.device = h, w, chunk, torch.device(device)
         self.K1, self.K2, self.T21, self.radius = K1, K2, T21, radius
@@ -246,6 +257,10 @@ class FramePipeline:
         # first, tau_px, ratio, window, min_cos, image_size -- the frame's size unless given): the stereo fit first, then every
         # grid point re-numbered against the grid that fit predicts and the fit again on fused points
         self.refine = refine
+        # pixels (build-defined, opt-in): None, or keywords of fit.fit_cylinder_pixels_batch ({} = its defaults): a step AFTER the
+        # mode's fit, no mode of its own: the fit's pose is polished on the pixels of the tables it was made from
+        # (fit.polish_with_pixels); the records then hold the polished cyl, every other word stays the 3-D fit's
+        self.pixels = None if pixels is None else dict(pixels)
         self.ws = {}
         # chunks are independent: `lanes` of them are in flight on their own HIP streams (each with its own
         # workspace), so the serial tails of one chunk (blob grouping, line fitting: one workgroup per frame)
@@ -283,6 +298,14 @@ class FramePipeline:
         det = api.detect_grid_batch(frames, self._ws(frames.shape[0], lane), target=self.target, debug_planes=False)   # only the tables are read
         g1, g2, st_l, st_r, centres = _split_detect(det, mode.cameras, interleaved)
         out = mode.fit(self, g1, g2, centres, frame0)
+        if self.pixels is not None:
+            if mode.cameras == 'LR':
+                out = fit.polish_with_pixels(out, out.get('tables1', g1), out.get('tables2', g2), self.K1, self.K2, self.T21, self.laser_table,
+                                             self.radius, self.pixels)
+            else:
+                K, Tc = (self.K1, None) if g2 is None else (self.K2, self.T21)
+                out = fit.polish_mono_with_pixels(out, out.get('tables', g1 if g2 is None else g2), K, Tc, self.laser_table, self.radius,
+                                                  self.pixels)
         return mode.record(out, st_l, st_r), det, out
 
     def run(self, left, right):

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 128  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 129  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -59,7 +59,8 @@ extern "C" {
                              cpe_multi_frame_consensus_workspace_bytes; 122: cpe_fused_triangulate_batch;
                              123: cpe_grid_relabel_batch; 124: cpe_grid_predict_batch, cpe_grid_assign_batch;
                              125: cpe_debug_ccl_tiles; 126: cpe_debug_state_field;
-                             127: cpe_mono_shift_batch; 128: cpe_est_curvatures_batch, cpe_curvature_consensus_batch) */
+                             127: cpe_mono_shift_batch; 128: cpe_est_curvatures_batch, cpe_curvature_consensus_batch;
+                             129: cpe_fit_cylinder_pixels_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -1409,6 +1410,66 @@ CPE_API int32_t cpe_curvature_consensus_batch(const double *X, const int32_t *cn
                                               const double *normal, const uint8_t *pt_status, double rho_max, double r_min,
                                               double r_max, double *axis, int32_t *n_gated, uint8_t *gate, int32_t *status,
                                               void *stream);
+
+/* BUILD-DEFINED, opt-in: the cylinder pose fitted to the PIXELS of both images.  Every other fit here minimises sum (d - R)^2
+ * over triangulated points, whose noise is pixel noise stretched along depth.  This call minimises the pixel distance between
+ * every detection and the predicted pixel of its own grid node (steps 2 - 10 of cpe_grid_predict_batch): the maximum-likelihood
+ * pose for isotropic pixel noise.  It needs no join of the two tables and no triangulation, and uses detections only one camera
+ * found.  One wavefront per frame, one launch on `stream`, no atomics, no workspace, no host synchronisation; two calls on
+ * equal inputs give equal bits, and a frame's outputs do not depend on its place in the batch.
+ *   xy1 f64[n,CPE_MAXP,2], id1 i32[n,CPE_MAXP,2], cnt1 i32[n]: camera 1's tables as cpe_detect_grid_batch writes them; xy2, id2,
+ *     cnt2: camera 2's.  Either camera's three pointers may ALL be NULL: that camera is absent.  Both absent, or a camera given
+ *     in part: CPE_ERR_ARG.
+ *   cyl0 f64[n,6]: the start pose, a point on the axis and a direction of any length, camera-1 coordinates: what
+ *     cpe_fit_cylinder_batch writes to cyl[:,1,:]; use u8[n] or NULL (all frames); radius R > 0, finite (it stays fixed)
+ *   K1, K2, T21, P f64[2,L,4], line_status i32[2,L], lo, hi, centre f64[3]: exactly as cpe_grid_predict_batch reads them
+ *   swap: as CpeTableTriParams.swap (component c of id addresses table family c ^ swap); min_cos in (0, 1): step 9's gate;
+ *   gate_px: <= 0 (or NaN) = off; tol_x, tol_f > 0, max_iter >= 1: the Levenberg-Marquardt loop's (at most 200 iterations)
+ * Rule per frame (the order is the contract; x = (o, a) are the six unknowns):
+ *   1. the frame is unusable when use is 0, any number of cyl0 is not finite, or |a| is 0 or not finite: status
+ *      CPE_ST_FEW_POINTS, every numeric output 0 (counts included), pt_state 1 below the counts and -1 past them;
+ *   2. cnt1, cnt2 are clamped to [0, CPE_MAXP]; slots past them are never read.  A detection is USABLE when its pixel is finite;
+ *      both its indices lie in [lo, hi] and both planes (component c reads family c ^ swap) have line_status CPE_ST_OK; steps 3 - 9
+ *      of cpe_grid_predict_batch give CPE_PRED_OK for its node at cyl0; Z > 0 in its own camera; and its predicted pixel
+ *      (step 10's formula) is finite.  There is no facing test and no image bound: the detection exists;
+ *   3. with gate_px > 0 a usable detection whose residual norm at cyl0 is >= gate_px is gated out.  The used set S is decided
+ *      here, once, and never changes, so the objective is smooth;
+ *   4. fewer than CPE_PIXFIT_MIN_PTS detections in S: CPE_ST_FEW_POINTS;
+ *   5. F(x) = sum over S of (rx rx + ry ry), r = pi_j(X(u, v; x)) - p: X by steps 4 - 8 of the prediction at the pose x, pi_j by
+ *      step 10's formula for the detection's camera j.  When any member of S fails steps 6 - 9 or has Z <= 0 at x, or x itself
+ *      fails rule 1's test, F(x) is NaN, which the loop treats as a rejected trial;
+ *   6. Levenberg-Marquardt from (cyl0, F(cyl0)) on the six unknowns -- lambda from 1e-3, x 10 on a rejected trial, / 10 on an
+ *      accepted one, 12 trials per iteration, stop at an improvement <= tol_f 1e-3 (1 + F) with a step <= tol_x: the loop of
+ *      cpe_fit_cylinder_batch's CPE_FIT_LM.  The two gauge directions (o along a, |a|) are left to the damping, as there;
+ *   7. the Jacobian of a detection's two residuals: g = X - o, ah = a / |a|, gp = g - (g.ah) ah; dt/d(o, a) = (gp,
+ *      (g.ah) gp / |a|) / (gp.wh); dX = wh dt; s = (d pi / d Xc) R_j wh with d x / d Xc = (K0 / Z, K1 / Z, -(K0 Xc0 + K1 Xc1) /
+ *      Z^2) and d y / d Xc = (0, K4 / Z, -K4 Xc1 / Z^2); the rows are s_x dt and s_y dt (rank one);
+ *   8. the outputs are written at the final x.  A final pose or F that is not finite: CPE_ST_FEW_POINTS.
+ * Outputs, every slot of every frame written:
+ *   cyl f64[n,6] the final pose as the loop left it (no prior applied); fvals f64[n,2] = F(cyl0), F(cyl); iters i32[n,2] =
+ *   iterations, objective evaluations (F(cyl0) included); counts i32[n,4] = |S| of camera 1 | of camera 2 | detections below
+ *   the counts refused by rule 2 | gated by rule 3; stats f64[n,4] = rms residual norm of camera 1 | of camera 2 |
+ *   sqrt(F / |S|) | the largest residual norm, pixels at cyl; status i32[n].
+ *   Optional (NULL: not written): res f64[n,2,CPE_MAXP,2] the residual (predicted - detected) per camera and slot at cyl;
+ *   pt_state i32[n,2,CPE_MAXP]: 0 in S, 1 refused by rule 2, 2 gated, -1 past the count (every slot of an absent camera);
+ *   X f64[n,2,CPE_MAXP,3] the node's 3-D point at cyl.  res and X are 0 outside S and past the counts.
+ *   With CPE_ST_FEW_POINTS by rule 4 or 8, cyl, fvals, iters, stats, res and X are zero; counts and pt_state say what rules 2
+ *   and 3 decided all the same.  So CPE_ST_OK implies finite outputs.
+ * CPE_ERR_ARG, nothing launched or written: radius not finite or <= 0; L outside 1..CPE_MAXL; min_cos outside (0, 1); swap other
+ * than 0 or 1; tol_x or tol_f not > 0; max_iter < 1; a NULL required pointer; an output that overlaps an input or another
+ * output.  n == 0 is a no-op.
+ * Limits: the radius is fixed and the cylinder ideal and rigid; the table's errors enter as for every table-based call; the
+ * indices are trusted (re-number first: cpe_grid_assign_batch); S is fixed at the start pose; no covariance is returned;
+ * planar targets are not covered. */
+#define CPE_PIXFIT_MIN_PTS 6
+CPE_API int32_t cpe_fit_cylinder_pixels_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
+                                              const int32_t *id2, const int32_t *cnt2, const double *cyl0, const uint8_t *use,
+                                              int32_t n, double radius, const double *K1, const double *K2, const double *T21,
+                                              const double *P, const int32_t *line_status, int32_t lo, int32_t hi,
+                                              const double *centre, int32_t swap, double min_cos, double gate_px, double tol_x,
+                                              double tol_f, int32_t max_iter, double *cyl, double *fvals, int32_t *iters,
+                                              int32_t *counts, double *stats, int32_t *status, double *res, int32_t *pt_state,
+                                              double *X, void *stream);
 
 #ifdef __cplusplus
 }
