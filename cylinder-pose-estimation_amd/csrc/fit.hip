@@ -5565,7 +5565,8 @@ struct PixEval {
     int cam;
 };
 
-struct PixProblem {
+// one frame's detections against the table: what k_fit_cylinder_pixels and k_multi_frame_pixels share
+struct PixFrame {
     const double *xy1, *xy2;       // the frame's two tables (a table of an absent camera is never read: its count is 0)
     const int *id1, *id2;
     int n1, n12;                   // camera 1's count; both counts
@@ -5577,7 +5578,6 @@ struct PixProblem {
     TriCam cam1, cam2;
     double t2[3];                  // camera 2's translation (camera 1's is 0)
     int lane;
-    unsigned long long mine;       // bit i: the detection lane + 64 i belongs to S
 
     // a / |a| -> false: the pose cannot be used (rule 1)
     __device__ __forceinline__ static bool pose(const double *x, double *ah, double &an)
@@ -5639,6 +5639,32 @@ struct PixProblem {
         const double *pl0, *pl1;
         return detection(k, c, px, py, pl0, pl1) && eval(c, px, py, pl0, pl1, oc, ah, e);
     }
+    // rule 7's pieces of a node that eval() gave: u = gp / den, w = (g.ah) gp / (|a| den), and s = (d pi / d Xc) R_j wh
+    __device__ __forceinline__ void node_derivatives(const PixEval &e, const double *oc, const double *ah, double an, double *dt,
+                                                     double &sx, double &sy) const
+    {
+        const double gv[3] = {e.X[0] - oc[0], e.X[1] - oc[1], e.X[2] - oc[2]};
+        const double ga = dot3(gv, ah);
+        const double gp[3] = {gv[0] - ga * ah[0], gv[1] - ga * ah[1], gv[2] - ga * ah[2]};
+        const double den = dot3(gp, e.wh);
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            dt[a] = gp[a] / den;
+            dt[3 + a] = ((ga * gp[a]) / an) / den;
+        }
+        TriCam cm;
+        camera(e.cam, cm);
+        double v[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) v[r] = (cm.R[3 * r] * e.wh[0] + cm.R[3 * r + 1] * e.wh[1]) + cm.R[3 * r + 2] * e.wh[2];
+        const double Z = e.Xc[2], Z2 = Z * Z;
+        sx = ((cm.k0 / Z) * v[0] + (cm.k1 / Z) * v[1]) + (-(cm.k0 * e.Xc[0] + cm.k1 * e.Xc[1]) / Z2) * v[2];
+        sy = (cm.k4 / Z) * v[1] + (-(cm.k4 * e.Xc[1]) / Z2) * v[2];
+    }
+};
+
+struct PixProblem : PixFrame {
+    unsigned long long mine;       // bit i: the detection lane + 64 i belongs to S
 
     // rule 5
     __device__ __forceinline__ double operator()(const double *x) const
@@ -5665,24 +5691,8 @@ struct PixProblem {
             if (!((mine >> i) & 1ull)) continue;
             PixEval e;
             if (!eval_k(k, x, ah, e)) continue;
-            const double gv[3] = {e.X[0] - x[0], e.X[1] - x[1], e.X[2] - x[2]};
-            const double ga = dot3(gv, ah);
-            const double gp[3] = {gv[0] - ga * ah[0], gv[1] - ga * ah[1], gv[2] - ga * ah[2]};
-            const double den = dot3(gp, e.wh);
-            double dt[6];
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                dt[a] = gp[a] / den;
-                dt[3 + a] = ((ga * gp[a]) / an) / den;
-            }
-            TriCam cm;
-            camera(e.cam, cm);
-            double v[3];
-#pragma unroll
-            for (int r = 0; r < 3; r++) v[r] = (cm.R[3 * r] * e.wh[0] + cm.R[3 * r + 1] * e.wh[1]) + cm.R[3 * r + 2] * e.wh[2];
-            const double Z = e.Xc[2], Z2 = Z * Z;
-            const double sx = ((cm.k0 / Z) * v[0] + (cm.k1 / Z) * v[1]) + (-(cm.k0 * e.Xc[0] + cm.k1 * e.Xc[1]) / Z2) * v[2];
-            const double sy = (cm.k4 / Z) * v[1] + (-(cm.k4 * e.Xc[1]) / Z2) * v[2];
+            double dt[6], sx, sy;
+            node_derivatives(e, x, ah, an, dt, sx, sy);
             double j[6];
 #pragma unroll
             for (int a = 0; a < 6; a++) j[a] = sx * dt[a];
@@ -5826,6 +5836,361 @@ __global__ __launch_bounds__(64) void k_fit_cylinder_pixels(const double *__rest
         out.status[f] = ok ? CPE_ST_OK : CPE_ST_FEW_POINTS;
     }
 }
+
+// ---- BUILD-DEFINED (include/cpe.h cpe_multi_frame_fit_pixels_batch, whose numbered rule this follows): T_Cam_AGV fitted to the
+// pixels of every frame of a group at once.  The objective is PixFrame's, the pose step and the cross-wave sums are
+// MultiPoseProblem's, the loop is lm_minimize<6>.
+// k_multi_frame_pixels: one workgroup of MFPX_WAVES wavefronts per group.  Wave w takes kept frames w, w + WAVES, ... in order,
+// lane l of it the detections l, l + 64, ... of a frame's concatenated list.  The table is staged in LDS once per workgroup.
+// Membership of S: a group can hold 1024 frames of 4096 detections, so it does not fit registers; the store is the output
+// pt_state itself.  The selection pass writes it, every later pass reads pt_state == 0.  With the fixed frame -> wave and slot ->
+// lane assignment a lane only ever reads the words it wrote itself, so no fence and no barrier stands between the passes.  (The
+// ranges of two groups of one call may therefore not share a frame.)
+// F: every lane adds its members' squares in frame order then slot order; the 64-lane tree; the waves' sums are added in wave
+// order; the NaN flag is an OR over the waves.  Both go through two alternating LDS rows, one barrier per evaluation, as
+// MultiObjectiveT's terms do.  EVERY wave of the workgroup must make the same sequence of calls.
+#ifndef CPE_MFPX_WAVES
+#define CPE_MFPX_WAVES 4
+#endif
+constexpr int MFPX_WAVES = CPE_MFPX_WAVES;   // profiles/r33_resource_usage_multiframe_pixels.txt: 4 and 8 measured
+
+struct MultiPixOut {
+    double *x, *T, *fvals;
+    int *iters, *nused, *counts;
+    double *stats;
+    int *status;
+    double *N;                     // optional
+    int *pt_state;
+    double *frame_cyl, *frame_stats;
+    double *res;                   // optional
+    // a group that is not fitted: its status, every other per-group output zero
+    __device__ void write_failed(int g, int st) const
+    {
+        if (threadIdx.x != 0) return;
+        for (int k = 0; k < 6; k++) x[6 * (size_t)g + k] = 0;
+        for (int k = 0; k < 16; k++) T[16 * (size_t)g + k] = 0;
+        for (int k = 0; k < 2; k++) { fvals[2 * (size_t)g + k] = 0; iters[2 * (size_t)g + k] = 0; }
+        for (int k = 0; k < 4; k++) { counts[4 * (size_t)g + k] = 0; stats[4 * (size_t)g + k] = 0; }
+        if (N)
+            for (int k = 0; k < 21; k++) N[21 * (size_t)g + k] = 0;
+        nused[g] = 0;
+        status[g] = st;
+    }
+};
+
+template <int WAVES>
+struct MultiPixProblem {
+    PixFrame fr;                   // the table, the cameras and the gates; the frame's tables are set by frame()
+    const double *xy1, *xy2;       // the call's tables (nullptr: the camera is absent)
+    const int *id1, *id2, *cnt1, *cnt2;
+    const double *TAGV;
+    const int *pt_state;
+    const int *sIdx;               // LDS, kept frames in order
+    double *sJ;                    // LDS, [WAVES][MFLM_SUMS]
+    double *sF;                    // LDS, [2][WAVES]
+    int *sBad;                     // LDS, [2][WAVES]
+    int nk, wave, lane, row;
+    double T[16];                  // the pose normal() was last called at
+
+    __device__ __forceinline__ void frame(int f)
+    {
+        const size_t tb = (size_t)f * MAXP * 2;
+        fr.xy1 = xy1 ? xy1 + tb : nullptr; fr.xy2 = xy2 ? xy2 + tb : nullptr;
+        fr.id1 = id1 ? id1 + tb : nullptr; fr.id2 = id2 ? id2 + tb : nullptr;
+        const int n1 = xy1 ? min(max(cnt1[f], 0), MAXP) : 0, n2 = xy2 ? min(max(cnt2[f], 0), MAXP) : 0;
+        fr.n1 = n1; fr.n12 = n1 + n2;
+    }
+    // the word of pt_state that stands for detection k of the frame's concatenated list
+    __device__ __forceinline__ size_t slot_of(int f, int k) const
+    {
+        const int c = k >= fr.n1;
+        return ((size_t)f * 2 + c) * MAXP + (c ? k - fr.n1 : k);
+    }
+    // rule 2: (o, a) of frame f at the pose Tm -> usable; ah = a / |a|
+    __device__ __forceinline__ bool frame_pose(const double *Tm, int f, double *oa, double *ah, double &an) const
+    {
+        frame_axis(Tm, TAGV + 16 * (size_t)f, oa, oa + 3);
+        return PixFrame::pose(oa, ah, an);
+    }
+    // rule 4
+    __device__ __forceinline__ double operator()(const double *x)
+    {
+        double Tm[16], acc = 0.0;
+        pose_vec2T(x, Tm);
+        bool bad = false;
+#pragma unroll
+        for (int a = 0; a < 6; a++) bad = bad || !isfinite(x[a]);
+        for (int kf = wave; kf < nk; kf += WAVES) {
+            const int f = sIdx[kf];
+            double oa[6], ah[3], an;
+            frame(f);
+            if (!frame_pose(Tm, f, oa, ah, an)) bad = true;
+            for (int k = lane; k < fr.n12; k += 64) {
+                if (pt_state[slot_of(f, k)] != 0) continue;
+                PixEval e;
+                if (!fr.eval_k(k, oa, ah, e)) { bad = true; continue; }
+                acc = acc + (e.r[0] * e.r[0] + e.r[1] * e.r[1]);
+            }
+        }
+        acc = wave_sum(acc);
+        const int wbad = __ballot(bad) != 0ull;
+        double *rf = sF + row * WAVES;
+        int *rb = sBad + row * WAVES;
+        row ^= 1;
+        if (lane == 0) { rf[wave] = acc; rb[wave] = wbad; }
+        __syncthreads();
+        double v = 0.0;
+        int any = 0;
+        for (int w = 0; w < WAVES; w++) { v = v + rf[w]; any |= rb[w]; }
+        return any ? __longlong_as_double(0x7ff8000000000000ll) : v;
+    }
+    // rule 6
+    __device__ __forceinline__ void normal(const double *x, double *A, double *g)
+    {
+        pose_vec2T(x, T);
+        double acc[MFLM_SUMS];
+#pragma unroll
+        for (int k = 0; k < MFLM_SUMS; k++) acc[k] = 0.0;
+        for (int kf = wave; kf < nk; kf += WAVES) {
+            const int f = sIdx[kf];
+            const double *Am = TAGV + 16 * (size_t)f;
+            double oa[6], ah[3], an, q[3];
+            frame(f);
+            frame_pose(T, f, oa, ah, an);
+#pragma unroll
+            for (int r = 0; r < 3; r++) q[r] = (T[r * 4] * Am[3] + T[r * 4 + 1] * Am[7]) + T[r * 4 + 2] * Am[11];
+            for (int k = lane; k < fr.n12; k += 64) {
+                if (pt_state[slot_of(f, k)] != 0) continue;
+                PixEval e;
+                if (!fr.eval_k(k, oa, ah, e)) continue;
+                double dt[6], sx, sy, mu[3], aw[3];
+                fr.node_derivatives(e, oa, ah, an, dt, sx, sy);
+                cross3(q, dt, mu);
+                cross3(oa + 3, dt + 3, aw);
+                const double jp[6] = {mu[0] + aw[0], mu[1] + aw[1], mu[2] + aw[2], dt[0], dt[1], dt[2]};
+                double j[6];
+#pragma unroll
+                for (int a = 0; a < 6; a++) j[a] = sx * jp[a];
+                normal_accumulate<6>(j, e.r[0], acc);
+#pragma unroll
+                for (int a = 0; a < 6; a++) j[a] = sy * jp[a];
+                normal_accumulate<6>(j, e.r[1], acc);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < MFLM_SUMS; k++) {
+            const double s = wave_sum(acc[k]);
+            if (lane == 0) sJ[wave * MFLM_SUMS + k] = s;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < MFLM_SUMS; k++) {
+            double s = 0.0;
+            for (int w = 0; w < WAVES; w++) s = s + sJ[w * MFLM_SUMS + k];
+            if (k < 21) A[k] = s;
+            else g[k - 21] = s;
+        }
+    }
+    // the left perturbation of MultiPoseProblem::candidate
+    __device__ __forceinline__ bool candidate(const double *, const double *dl, double *xn) const
+    {
+        double E[9], Tn[16];
+        rot_exp(dl, E);
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) Tn[r * 4 + c] = (E[r * 3] * T[c] + E[r * 3 + 1] * T[4 + c]) + E[r * 3 + 2] * T[8 + c];
+            Tn[r * 4 + 3] = T[r * 4 + 3] + dl[3 + r];
+        }
+        Tn[12] = 0; Tn[13] = 0; Tn[14] = 0; Tn[15] = 1;
+        pose_T2vec(Tn, xn);
+        return true;
+    }
+};
+
+constexpr int MFPX_CNT = 5;      // |S| of camera 1 | of camera 2 | refused | gated | kept frames with a member
+constexpr int MFPX_ST = 3;       // the squares of camera 1 | of camera 2 | the largest residual norm
+
+// Barriers: multi_group_begin's, one after the selection's counts, one per objective evaluation and per Jacobian pass, two
+// around the closing sums.  None stands under a condition that depends on the wave or the lane; every branch that holds one
+// is taken on numbers that all waves have alike (LDS sums, the group's inputs).
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_multi_frame_pixels(
+    const double *__restrict__ xy1, const int *__restrict__ id1, const int *__restrict__ cnt1, const double *__restrict__ xy2,
+    const int *__restrict__ id2, const int *__restrict__ cnt2, const double *__restrict__ TAGV, const int *__restrict__ frame_ok,
+    const int *__restrict__ group_start, int n, const double *__restrict__ x0_in, double R, const double *__restrict__ K1,
+    const double *__restrict__ K2, const double *__restrict__ T21, const double *__restrict__ P,
+    const int *__restrict__ line_status, int lo, int L, const double *__restrict__ centre, int swap, double min_cos, double sel_cos,
+    double gate_px, double tolx, double tolf, int maxiter, const MultiPixOut out)
+{
+    __builtin_amdgcn_s_setprio(3);
+    __shared__ double sP[2 * CPE_MAXL * 4];
+    __shared__ int sSt[2 * CPE_MAXL];
+    __shared__ int sIdx[MF_MAXF];
+    __shared__ double sJ[WAVES * MFLM_SUMS];
+    __shared__ double sF[2 * WAVES];
+    __shared__ int sBad[2 * WAVES];
+    __shared__ int sCnt[WAVES * MFPX_CNT];
+    __shared__ double sSt3[WAVES * MFPX_ST];
+    __shared__ int sNk;
+    const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < 8 * L; i += 64 * WAVES) sP[i] = P[i];
+    for (int i = threadIdx.x; i < 2 * L; i += 64 * WAVES) sSt[i] = line_status[i];
+    const int nk = multi_group_begin(frame_ok, group_start, n, g, sIdx, &sNk, out);   // (its barrier covers the staging)
+    const int ga = group_start[g], gb = group_start[g + 1];
+    const bool range_ok = 0 <= ga && ga <= gb && gb <= n;
+
+    // rule 1
+    double x0[6] = {0, 0, 0, 0, 0, 0};
+    bool run = nk != 0;
+    if (run) {
+#pragma unroll
+        for (int a = 0; a < 6; a++) { x0[a] = x0_in[6 * (size_t)g + a]; run = run && isfinite(x0[a]); }
+        if (!run) out.write_failed(g, CPE_ST_FEW_POINTS);
+    }
+    // pt_state of every frame of the range: -1 past the counts, 1 below them except where the selection is going to decide
+    if (range_ok)
+        for (int f = ga + wave; f < gb; f += WAVES) {
+            const bool sel = run && (frame_ok == nullptr || frame_ok[f] != 0);
+            for (int c = 0; c < 2; c++) {
+                const int *cn = c ? cnt2 : cnt1;
+                const int m = (c ? xy2 : xy1) ? min(max(cn[f], 0), MAXP) : 0;
+                int *ps = out.pt_state + ((size_t)f * 2 + c) * MAXP;
+                for (int s = sel ? m + lane : lane; s < MAXP; s += 64) ps[s] = s < m ? 1 : -1;
+            }
+        }
+    if (!run) return;
+
+    MultiPixProblem<WAVES> prob;
+    prob.fr.sP = sP; prob.fr.sSt = sSt;
+    prob.fr.lo = lo; prob.fr.hi = lo + (L - 1); prob.fr.L = L; prob.fr.swap = swap;
+    prob.fr.R = R; prob.fr.min_cos = sel_cos;
+#pragma unroll
+    for (int a = 0; a < 3; a++) { prob.fr.centre[a] = centre[a]; prob.fr.t2[a] = T21[4 * a + 3]; }
+    tri_cam(K1, nullptr, prob.fr.cam1);
+    tri_cam(K2, T21, prob.fr.cam2);
+    prob.fr.lane = lane;
+    prob.xy1 = xy1; prob.xy2 = xy2; prob.id1 = id1; prob.id2 = id2; prob.cnt1 = cnt1; prob.cnt2 = cnt2;
+    prob.TAGV = TAGV; prob.pt_state = out.pt_state; prob.sIdx = sIdx; prob.sJ = sJ; prob.sF = sF; prob.sBad = sBad;
+    prob.nk = nk; prob.wave = wave; prob.lane = lane; prob.row = 0;
+
+    // rule 3: the used set, once, at x0 with sel_cos
+    {
+        double T0[16];
+        pose_vec2T(x0, T0);
+        int cs[MFPX_CNT] = {0, 0, 0, 0, 0};
+        for (int kf = wave; kf < nk; kf += WAVES) {
+            const int f = sIdx[kf];
+            double oa[6], ah[3], an;
+            prob.frame(f);
+            const bool pose_ok = prob.frame_pose(T0, f, oa, ah, an);
+            int members = 0;
+            for (int k = lane; k < prob.fr.n12; k += 64) {
+                PixEval e;
+                int st = 1;
+                if (pose_ok && prob.fr.eval_k(k, oa, ah, e)) {
+                    const double r2 = e.r[0] * e.r[0] + e.r[1] * e.r[1];
+                    st = (gate_px > 0 && sqrt(r2) >= gate_px) ? 2 : 0;
+                }
+                out.pt_state[prob.slot_of(f, k)] = st;
+                cs[0] += st == 0 && k < prob.fr.n1; cs[1] += st == 0 && k >= prob.fr.n1; cs[2] += st == 1; cs[3] += st == 2;
+                members += st == 0;
+            }
+            cs[4] += __ballot(members != 0) != 0ull;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) cs[k] = wave_sum_i(cs[k]);
+        if (lane == 0)
+            for (int k = 0; k < MFPX_CNT; k++) sCnt[wave * MFPX_CNT + k] = cs[k];
+    }
+    __syncthreads();
+    int cs[MFPX_CNT] = {0, 0, 0, 0, 0};
+    for (int w = 0; w < WAVES; w++)
+        for (int k = 0; k < MFPX_CNT; k++) cs[k] += sCnt[w * MFPX_CNT + k];
+    const int nS = cs[0] + cs[1];
+    if (nS < CPE_PIXFIT_MIN_PTS || cs[4] < 2) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+
+    // rules 4, 5
+    prob.fr.min_cos = min_cos;
+    const double f0 = prob(x0);
+    if (!fit_finite(x0, f0)) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+    double x[6], fx;
+    int itercount, func_evals = 1;
+    lm_minimize<6>(prob, x0, f0, tolx, tolf, maxiter, x, fx, itercount, func_evals);
+    if (!fit_finite(x, fx)) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+
+    // rule 7: the per-frame outputs and the group's statistics at x
+    double Tf[16];
+    pose_vec2T(x, Tf);
+    double gs[MFPX_ST] = {0, 0, 0};
+    for (int kf = wave; kf < nk; kf += WAVES) {
+        const int f = sIdx[kf];
+        double oa[6], ah[3], an, s1 = 0.0, s2 = 0.0, rmax = 0.0;
+        int m1 = 0, m2 = 0;
+        prob.frame(f);
+        prob.frame_pose(Tf, f, oa, ah, an);
+        const int n1 = prob.fr.n1, n12 = prob.fr.n12;
+        for (int k = lane; k < n12; k += 64) {
+            const size_t at = prob.slot_of(f, k);
+            double r[2] = {0, 0};
+            if (out.pt_state[at] == 0) {
+                PixEval e;
+                if (prob.fr.eval_k(k, oa, ah, e)) {                                // (it does: F(x) is finite)
+                    r[0] = e.r[0]; r[1] = e.r[1];
+                    const double r2 = r[0] * r[0] + r[1] * r[1];
+                    if (k >= n1) { s2 = s2 + r2; m2++; } else { s1 = s1 + r2; m1++; }
+                    rmax = fmax(rmax, sqrt(r2));
+                }
+            }
+            if (out.res) { out.res[at * 2] = r[0]; out.res[at * 2 + 1] = r[1]; }
+        }
+        if (out.res)
+            for (int c = 0; c < 2; c++)
+                for (int s = (c ? n12 - n1 : n1) + lane; s < MAXP; s += 64) {
+                    const size_t at = ((size_t)f * 2 + c) * MAXP + s;
+                    out.res[at * 2] = 0; out.res[at * 2 + 1] = 0;
+                }
+        s1 = wave_sum(s1); s2 = wave_sum(s2);
+        m1 = wave_sum_i(m1); m2 = wave_sum_i(m2);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) rmax = fmax(rmax, __shfl_xor(rmax, off, 64));
+        gs[0] = gs[0] + s1; gs[1] = gs[1] + s2; gs[2] = fmax(gs[2], rmax);
+        if (lane == 0) {
+            for (int a = 0; a < 6; a++) out.frame_cyl[6 * (size_t)f + a] = oa[a];
+            double *fs = out.frame_stats + 4 * (size_t)f;
+            fs[0] = m1 > 0 ? sqrt(s1 / (double)m1) : 0.0;
+            fs[1] = m2 > 0 ? sqrt(s2 / (double)m2) : 0.0;
+            fs[2] = m1 + m2 > 0 ? sqrt((s1 + s2) / (double)(m1 + m2)) : 0.0;
+            fs[3] = rmax;
+        }
+    }
+    __syncthreads();                                   // every wave has read the sums of the loop's last Jacobian pass
+    if (lane == 0)
+        for (int k = 0; k < MFPX_ST; k++) sSt3[wave * MFPX_ST + k] = gs[k];
+    double A[21], gr[6];
+    if (out.N) prob.normal(x, A, gr);                  // (one barrier; out.N is the same for every wave)
+    else __syncthreads();
+    if (threadIdx.x == 0) {
+        double S1 = 0.0, S2 = 0.0, rmax = 0.0;
+        for (int w = 0; w < WAVES; w++) {
+            S1 = S1 + sSt3[w * MFPX_ST]; S2 = S2 + sSt3[w * MFPX_ST + 1]; rmax = fmax(rmax, sSt3[w * MFPX_ST + 2]);
+        }
+        for (int k = 0; k < 6; k++) out.x[6 * (size_t)g + k] = x[k];
+        for (int k = 0; k < 16; k++) out.T[16 * (size_t)g + k] = Tf[k];
+        out.fvals[2 * (size_t)g] = f0; out.fvals[2 * (size_t)g + 1] = fx;
+        out.iters[2 * (size_t)g] = itercount; out.iters[2 * (size_t)g + 1] = func_evals;
+        out.nused[g] = nk;
+        for (int k = 0; k < 4; k++) out.counts[4 * (size_t)g + k] = cs[k];
+        double *os = out.stats + 4 * (size_t)g;
+        os[0] = cs[0] > 0 ? sqrt(S1 / (double)cs[0]) : 0.0;
+        os[1] = cs[1] > 0 ? sqrt(S2 / (double)cs[1]) : 0.0;
+        os[2] = sqrt(fx / (double)nS);
+        os[3] = rmax;
+        if (out.N)
+            for (int k = 0; k < 21; k++) out.N[21 * (size_t)g + k] = A[k];
+        out.status[g] = CPE_ST_OK;
+    }
+}
 }  // namespace
 
 extern "C" int32_t cpe_fit_cylinder_pixels_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
@@ -5869,5 +6234,56 @@ extern "C" int32_t cpe_fit_cylinder_pixels_batch(const double *xy1, const int32_
     CPE_KLAUNCH(k_fit_cylinder_pixels, dim3(n), dim3(64), 0, (hipStream_t)stream, xy1, id1, cnt1, xy2, id2, cnt2, cyl0, use, radius, K1, K2,
                 T21, P, line_status, lo, L, centre, p.swap, p.min_cos, gate_px, p.tol_x, p.tol_f, p.max_iter, out);
     CPE_CHECK_LAUNCH("k_fit_cylinder_pixels");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_multi_frame_fit_pixels_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
+                                                    const int32_t *id2, const int32_t *cnt2, const double *TAGVcyl,
+                                                    const int32_t *frame_ok, const int32_t *group_start, int32_t G, int32_t n,
+                                                    const double *x0_in, double radius, const double *K1, const double *K2,
+                                                    const double *T21, const double *P, const int32_t *line_status, int32_t lo,
+                                                    int32_t hi, const double *centre, int32_t swap, double min_cos, double sel_cos,
+                                                    double gate_px, double tol_x, double tol_f, int32_t max_iter, double *x, double *T,
+                                                    double *fvals, int32_t *iters, int32_t *n_used, int32_t *counts, double *stats,
+                                                    int32_t *status, double *N, int32_t *pt_state, double *frame_cyl,
+                                                    double *frame_stats, double *res, void *stream)
+{
+    CPE_CHECK_ARG(G >= 0 && n >= 0, "cpe_multi_frame_fit_pixels_batch: G < 0 or n < 0");
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_multi_frame_fit_pixels_batch: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    CPE_CHECK_ARG(radius > 0 && radius <= DBL_MAX, "cpe_multi_frame_fit_pixels_batch: radius must be positive and finite");
+    const struct { int swap; double min_cos, sel_cos, tol_x, tol_f; int max_iter; } p = {swap, min_cos, sel_cos, tol_x, tol_f, max_iter};
+    CPE_CHECK_ARG(p.min_cos > 0 && p.min_cos < 1 && (p.swap == 0 || p.swap == 1) && p.tol_x > 0 && p.tol_f > 0 && p.max_iter >= 1,
+                  "cpe_multi_frame_fit_pixels_batch: bad parameters (0 < min_cos < 1, swap 0 or 1, tol_x > 0, tol_f > 0, max_iter >= 1)");
+    CPE_CHECK_ARG(p.sel_cos >= p.min_cos && p.sel_cos < 1, "cpe_multi_frame_fit_pixels_batch: sel_cos must lie in [min_cos, 1)");
+    const bool cam1 = xy1 && id1 && cnt1, cam2 = xy2 && id2 && cnt2;
+    CPE_CHECK_ARG((cam1 || (!xy1 && !id1 && !cnt1)) && (cam2 || (!xy2 && !id2 && !cnt2)) && (cam1 || cam2),
+                  "cpe_multi_frame_fit_pixels_batch: a camera is given by all three of xy, id, cnt or by none, and one camera at least");
+    if (G == 0) return CPE_OK;
+    CPE_CHECK_ARG(TAGVcyl && group_start && x0_in && K1 && K2 && T21 && P && line_status && centre && x && T && fvals && iters && n_used &&
+                      counts && stats && status && pt_state && frame_cyl && frame_stats,
+                  "cpe_multi_frame_fit_pixels_batch: null pointer (x0_in is required: there is no closed-form start in pixel space)");
+    const int L = hi - lo + 1;
+    {
+        const size_t Nn = (size_t)n, Gg = (size_t)G, Pp = (size_t)CPE_MAXP;
+        const struct { const void *p; size_t bytes; } buf[29] = {
+            {xy1, cam1 ? Nn * Pp * 16 : 0}, {id1, cam1 ? Nn * Pp * 8 : 0}, {cnt1, cam1 ? Nn * 4 : 0}, {xy2, cam2 ? Nn * Pp * 16 : 0},
+            {id2, cam2 ? Nn * Pp * 8 : 0}, {cnt2, cam2 ? Nn * 4 : 0}, {TAGVcyl, Nn * 128}, {frame_ok, frame_ok ? Nn * 4 : 0},
+            {group_start, (Gg + 1) * 4}, {x0_in, Gg * 48}, {K1, 72}, {K2, 72}, {T21, 128}, {P, (size_t)L * 64},
+            {line_status, (size_t)L * 8}, {centre, 24},
+            {x, Gg * 48}, {T, Gg * 128}, {fvals, Gg * 16}, {iters, Gg * 8}, {n_used, Gg * 4}, {counts, Gg * 16}, {stats, Gg * 32},
+            {status, Gg * 4}, {N, N ? Gg * 168 : 0}, {pt_state, Nn * Pp * 8}, {frame_cyl, Nn * 48}, {frame_stats, Nn * 32},
+            {res, res ? Nn * Pp * 32 : 0}};
+        for (int o = 16; o < 29; o++)
+            for (int i = 0; i < o; i++)
+                CPE_CHECK_ARG(!buf[o].bytes || !buf[i].bytes || !rl_overlap(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes),
+                              "cpe_multi_frame_fit_pixels_batch: an output overlaps an input or another output");
+    }
+    const MultiPixOut out = {x, T, fvals, iters, n_used, counts, stats, status, N, pt_state, frame_cyl, frame_stats, res};
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_multi_frame_pixels<MFPX_WAVES>, dim3(G), dim3(64 * MFPX_WAVES), 0, (hipStream_t)stream, xy1, id1, cnt1, xy2, id2, cnt2,
+                TAGVcyl, frame_ok, group_start, n, x0_in, radius, K1, K2, T21, P, line_status, lo, L, centre, p.swap, p.min_cos, p.sel_cos,
+                gate_px, p.tol_x, p.tol_f, p.max_iter, out);
+    CPE_CHECK_LAUNCH("k_multi_frame_pixels");
     return CPE_OK;
 }

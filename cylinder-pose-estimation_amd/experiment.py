@@ -215,7 +215,7 @@ def repair_listing(names, shift, flags, round_taken, renumbered):
 
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
                    frame_angles=False, match_offset=None, laser_table=None, source='stereo', projector=None, table_path=None,
-                   curvature=None, consensus=None, refine=None, pixels=None, repair=None):
+                   curvature=None, consensus=None, refine=None, pixels=None, multi_frame_pixels=None, repair=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
@@ -303,7 +303,22 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     fit.polish_with_pixels; after refine= / repair= on the re-numbered tables).  records, cyl_raw and the multi-frame fit then read
     the polished poses, and the dict gains pixels = dict(cyl f64 [F,6] (the polished cyl[:, 1]), T f64 [F,4,4], fvals f64 [F,2]
     (px^2 at the start and the end), px_rms f64 [F] (of both cameras), counts i32 [F,4], status i32 [F] (the pixel fit's; a frame
-    whose pixel fit is not ST_OK keeps its 3-D fit)).  source='stereo' raises ValueError."""
+    whose pixel fit is not ST_OK keeps its 3-D fit)).  source='stereo' raises ValueError.
+
+    multi_frame_pixels= with source 'fused', 'left' or 'right' and multi_frame 'gpu', 'lm' or 'consensus' (build-defined, opt-in):
+    None, or a dict of multiframe.fit_multi_frame_pixels_gpu keywords ({} = its defaults: sel_cos, min_cos, gate_px, tol_x, tol_f,
+    max_iter).  T_Cam_AGV is fitted once more, to the pixels of all frames at once (include/cpe.h
+    cpe_multi_frame_fit_pixels_batch): the start is that multi_frame mode's pose, the kept frames are its good frames (with
+    'consensus' its inliers), the tables are the ones the frames' fits were made from (after refine= / repair=), and with 'left' /
+    'right' the other camera is absent.  The laser table must be rigid with camera 1 across the frames.  The dict gains
+    multi_frame_pixels = dict(T_cam_agv (16 row-major values, None unless status is 0), x f64 [6], fvals f64 [2] (px^2 at the start
+    and the end), px_rms (of all used detections), counts i32 [4], status, cov f64 [6,6] (of the step (dw, dt); NaN unless status is
+    0), frame_cyl f64 [F,6], frame_stats f64 [F,4] (NaN for the frames that were not used)) -- None when the point-based fit gave no
+    pose.  T_cam_agv, fval and everything else keep their values.  Any other source or multi_frame raises ValueError."""
+    if multi_frame_pixels is not None and (source not in ('fused', 'left', 'right') or multi_frame is True
+                                           or multi_frame not in ('gpu', 'lm', 'consensus')):
+        raise ValueError("multi_frame_pixels= predicts the pixels from the laser-plane table and starts at a resident multi-frame fit: "
+                         "source must be 'fused', 'left' or 'right' and multi_frame 'gpu', 'lm' or 'consensus'")
     if pixels is not None and source == 'stereo':
         raise ValueError("pixels= predicts the pixels from the laser-plane table: source must be 'fused', 'left' or 'right'")
     if curvature is not None:
@@ -330,12 +345,17 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
             f.update({k: torch.zeros((F,) + shape, dtype=dt, device=dev) for k, (shape, dt) in pipeline.PIXELS_OUTPUTS.items()})
         if projector is not None:        # the model needs the points' indices, which the selector returns beside the points
             f['idx'] = torch.zeros((F, fit.MAXP, 2), dtype=torch.int32, device=dev)
+        if multi_frame_pixels is not None:
+            cams = dict(fused=(1, 2), left=(1,), right=(2,))[source]
+            f.update({k: torch.zeros((F,) + shape, dtype=dt, device=dev) for k, (shape, dt) in pipeline.tables_outputs(cams).items()})
         return f
     recs, fits = _run_pairs(names, paths, camera_json, dev, chunk, make_fits,
                             lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=c, device=dev, match=match_offset,
                                                                    source=source, laser_table=laser_table, refine=refine,
-                                                                   table=mono_table, pixels=pixels), source)
+                                                                   table=mono_table, pixels=pixels,
+                                                                   keep_tables=multi_frame_pixels is not None), source)
     F = len(names)
+    tables = {k: fits.pop(k) for k in list(fits) if k.startswith('tables_')}     # (multi_frame_pixels=: not among the fits' outputs)
     # frame_ok: the device mask of the frames that are not in `skipped`; the resident multi-frame modes mask with it
     frame_ok, skipped, _ = _frame_status(names, recs, None if match_offset is None else fits['match_flags'])
     res = dict(names=names, angles=angles, records=recs, pts3=fits['pts3'], cnt=fits['m'], cyl_raw=fits['cyl_raw'], skipped=skipped,
@@ -373,11 +393,13 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
         back = torch.cat([mf['T'][0], mf['fvals'][0], mf['status'][0:1].to(torch.float64),
                           frame_ok.sum().to(torch.float64).reshape(1)]).cpu().tolist()
         _take_multi_frame(res, int(back[19]), int(back[18]), 'fit', back[:16], back[17])
+        mfp_kept = frame_ok
     elif multi_frame == 'consensus':
         mf = multiframe.fit_multi_frame_consensus_gpu(fits['pts3'], fits['m'], fits['cyl_raw'], angles, radius, frame_ok=frame_ok,
                                                       group_start=[0, F], **(consensus or {}))
         g = multiframe.group_result(mf)
         status, n_good = g['status'], int(frame_ok.sum())
+        mfp_kept = mf['inlier'] == 1
         res['consensus'] = dict(inliers=[], rejected=[], n_inliers=g['n_inliers'], rounds=g['info'][3], flags=g['flags'], status=status)
         if _take_multi_frame(res, n_good, status, 'consensus', g['T'], g['fvals'][1]):
             res['consensus']['inliers'] = [names[i] for i in range(F) if g['inlier'][i] == 1]
@@ -395,6 +417,19 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
             g = torch.tensor(good, device=dev)
             mf = multiframe.fit_multi_frame(fits['pts3'][g], fits['m'][g], fits['cyl_raw'][g], angles[good], radius)
             res['T_cam_agv'], res['fval'] = mf['T'], mf['fvals'][1]
+    if multi_frame_pixels is not None:
+        res['multi_frame_pixels'] = None
+        if res['T_cam_agv'] is not None:
+            t = lambda k: tables.get(k)
+            px = multiframe.fit_multi_frame_pixels_gpu(t('tables_xy1'), t('tables_id1'), t('tables_cnt1'), t('tables_xy2'), t('tables_id2'),
+                                                       t('tables_cnt2'), mf['TAGV'], mf['x'][0:1], radius, K1, K2, T21, laser_table,
+                                                       frame_ok=mfp_kept, group_start=[0, F], **multi_frame_pixels)
+            st = int(px['status'][0])
+            if st != 0:
+                warnings.warn(f'the multi-frame pixel fit ended with status {st} (include/cpe.h: cpe_multi_frame_fit_pixels_batch)')
+            res['multi_frame_pixels'] = dict(T_cam_agv=px['T'][0].cpu().tolist() if st == 0 else None, x=px['x'][0], fvals=px['fvals'][0],
+                                             px_rms=px['stats'][0, 2], counts=px['counts'][0], status=st, cov=px['cov'][0],
+                                             frame_cyl=px['frame_cyl'], frame_stats=px['frame_stats'])
     if frame_angles:
         res.update(angles_est=None, angles_status=None, angles_delta_deg=None)
         if res['T_cam_agv'] is not None:

@@ -392,6 +392,111 @@ def fit_multi_frame_consensus_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=N
     return out
 
 
+def fit_multi_frame_pixels_gpu(xy1, id1, cnt1, xy2, id2, cnt2, angles, x0, radius, K1, K2, T21, laser_table, frame_ok=None,
+                               group_start=None, sel_cos=0.35, min_cos=0.1, gate_px=0.0, tol_x=1e-9, tol_f=1e-9, max_iter=100,
+                               want_res=False):
+    """Build-defined, opt-in (cpe_multi_frame_fit_pixels_batch; the rule is numbered in include/cpe.h):
+    T_Cam_AGV fitted to the pixels of every kept frame of a group at once, from a start that a point-based multi-frame fit gave.
+    One launch on the current stream, nothing is read back.
+    xy1 f64[n,MAXP,2], id1 i32[n,MAXP,2], cnt1 i32[n]: camera 1's tables (device tensors); xy2, id2, cnt2: camera 2's.  Either
+                 camera's three may all be None: that camera is absent
+    angles, frame_ok, group_start: as fit_multi_frame_gpu takes them (the ranges of two groups may not share a frame here)
+    x0           f64[G,6] (device tensor or nested list), required: e.g. fit_multi_frame_gpu(..., method='lm')['x']
+    K1, K2, T21, laser_table: the cameras and a fit.LaserTable (ids are (col, row)), as fit.fit_cylinder_pixels_batch takes them;
+                 the table must have a projector centre and be rigid with camera 1 across the frames
+    sel_cos      the grazing gate for membership of the used set (min_cos <= sel_cos < 1); min_cos: the gate of every evaluation;
+                 gate_px <= 0: no residual gate
+    -> dict of device tensors: x f64[G,6], T f64[G,16], fvals f64[G,2], iters i32[G,2], n_used i32[G], counts i32[G,4], stats
+       f64[G,4], status i32[G], N f64[G,21], cov f64[G,6,6] = F / (2 |S| - 6) inverse(J'J) in the step's coordinates (dw, dt), NaN
+       where the status is not 0; pt_state i32[n,2,MAXP]; frame_cyl f64[n,6] and frame_stats f64[n,4] (NaN for every frame that is
+       not a kept frame of a fitted group); res f64[n,2,MAXP,2] with want_res (zero for those frames), else None; TAGV f64[n,16]"""
+    from . import fit as _fit
+    what = 'fit_multi_frame_pixels_gpu'
+    L = _lib.load()
+    cam1, cam2 = (xy1, id1, cnt1), (xy2, id2, cnt2)
+    for c in (cam1, cam2):
+        if any(t is None for t in c) and not all(t is None for t in c):
+            raise ValueError(f'{what}: a camera is given by all three of xy, id, cnt or by none')
+    if xy1 is None and xy2 is None:
+        raise ValueError(f'{what}: both cameras are absent')
+    if not laser_table.has_centre():
+        raise ValueError(f'{what}: the table has no projector centre (centre_status is not ST_OK)')
+    if not (0 < min_cos < 1 and min_cos <= sel_cos < 1 and tol_x > 0 and tol_f > 0 and int(max_iter) >= 1 and radius > 0):
+        raise ValueError(f'{what}: 0 < min_cos <= sel_cos < 1, tol_x, tol_f, radius > 0 and max_iter >= 1, got {min_cos}, {sel_cos}, '
+                         f'{tol_x}, {tol_f}, {radius}, {max_iter}')
+    if x0 is None:
+        raise ValueError(f'{what}: x0 is required (there is no closed-form start in pixel space)')
+    some = cnt1 if cnt1 is not None else cnt2
+    dev, n = some.device, some.shape[0]
+    tabs = []
+    for name, c in (('camera 1 ', cam1), ('camera 2 ', cam2)):
+        if c[0] is None:
+            tabs.append((None, None, None))
+            continue
+        gp = _fit.GridTables(c[0].contiguous(), c[1].contiguous(), c[2].contiguous())
+        _fit._check_tables(what, gp, n, name, dev)
+        tabs.append((gp.xy, gp.id, gp.cnt))
+    if torch.is_tensor(angles):
+        TAGV = angles.to(device=dev, dtype=torch.float64).contiguous()
+        assert TAGV.shape == (n, 16), 'a tensor of angles is the [n,16] table of getTAGVcyl matrices'
+    else:
+        assert len(angles) == n
+        TAGV = torch.tensor([get_TAGVcyl(float(a[0]), float(a[1])) for a in angles], dtype=torch.float64).reshape(n, 16).to(dev)
+    if group_start is None:
+        group_start = [0, n]
+    if not torch.is_tensor(group_start):
+        group_start = torch.tensor(list(group_start), dtype=torch.int32)
+    gs = group_start.to(device=dev, dtype=torch.int32).contiguous()
+    G = gs.numel() - 1
+    assert G >= 0
+    if frame_ok is not None:
+        frame_ok = frame_ok.to(device=dev, dtype=torch.int32).contiguous()
+        assert frame_ok.shape == (n,)
+    x0 = torch.as_tensor(x0, dtype=torch.float64).to(dev).reshape(G, 6).contiguous()
+    K1, K2, T21 = _fit._cameras(K1, K2, T21, dev)
+    P, st, centre = _fit._table_on(laser_table, dev, centre=True)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    nan = float('nan')
+    out = dict(x=f64(G, 6), T=f64(G, 16), fvals=f64(G, 2), iters=i32(G, 2), n_used=i32(G), counts=i32(G, 4), stats=f64(G, 4),
+               status=i32(G), N=f64(G, 21), pt_state=torch.full((n, 2, _lib.MAXP), -1, dtype=torch.int32, device=dev),
+               frame_cyl=torch.full((n, 6), nan, dtype=torch.float64, device=dev),
+               frame_stats=torch.full((n, 4), nan, dtype=torch.float64, device=dev),
+               res=torch.zeros((n, 2, _lib.MAXP, 2), dtype=torch.float64, device=dev) if want_res else None)
+    p = _fit._ptr
+    if G and n:
+        _lib.check(L.cpe_multi_frame_fit_pixels_batch(
+            *(p(t) for t in tabs[0]), *(p(t) for t in tabs[1]), TAGV.data_ptr(), p(frame_ok), gs.data_ptr(), G, n, x0.data_ptr(),
+            float(radius), K1.data_ptr(), K2.data_ptr(), T21.data_ptr(), P.data_ptr(), st.data_ptr(), laser_table.lo, laser_table.hi,
+            centre.data_ptr(), laser_table.swap_for('col_row'), float(min_cos), float(sel_cos), float(gate_px), float(tol_x),
+            float(tol_f), int(max_iter), *(p(out[k]) for k in ('x', 'T', 'fvals', 'iters', 'n_used', 'counts', 'stats', 'status', 'N',
+                                                               'pt_state', 'frame_cyl', 'frame_stats', 'res')),
+            torch.cuda.current_stream().cuda_stream), 'cpe_multi_frame_fit_pixels_batch')
+    elif G:                                                    # groups of no frames: what the call would have written
+        for k in ('x', 'T', 'fvals', 'iters', 'n_used', 'counts', 'stats', 'N'):
+            out[k].zero_()
+        out['status'].fill_(_lib.const.ST_FEW_POINTS)
+    out['cov'] = _pixels_covariance(out)
+    out['TAGV'] = TAGV
+    return out
+
+
+def _pixels_covariance(out):
+    """F / (2 |S| - 6) inverse(N) per group -> f64[G,6,6], NaN where the status is not 0 or N cannot be inverted"""
+    G, dev = out['status'].shape[0], out['status'].device
+    iu = torch.triu_indices(6, 6, device=dev)
+    Nf = torch.zeros((G, 6, 6), dtype=torch.float64, device=dev)
+    Nf[:, iu[0], iu[1]] = out['N']
+    Nf = Nf + torch.triu(Nf, 1).transpose(1, 2)
+    ok = out['status'] == 0
+    eye = torch.eye(6, dtype=torch.float64, device=dev)
+    inv, info = torch.linalg.inv_ex(torch.where(ok[:, None, None], Nf, eye))
+    dof = (2 * out['counts'][:, :2].sum(1) - 6).to(torch.float64)
+    ok = ok & (info == 0) & (dof > 0)
+    cov = inv * (out['fvals'][:, 1] / torch.where(dof > 0, dof, torch.ones_like(dof)))[:, None, None]
+    return torch.where(ok[:, None, None], cov, torch.full_like(cov, float('nan')))
+
+
 def group_result(res, g=0):
     """one group of fit_multi_frame_gpu's result on the host (this synchronises), with the keys of fit_multi_frame --
     T (flat row-major 4x4), x, x0, fvals [f0, f], iters, evals, TAGV (all frames' matrices) -- plus n_used and status, and

@@ -61,6 +61,11 @@ MONO_REPAIR_OUTPUTS = dict(shift=((2,), _I32), shift_flags=((), _I32), shift_sco
                            renumbered=((), _I32))
 # what fit.polish_with_pixels adds per frame; FramePipeline(pixels=...).run_raw keeps them when the fits dict holds tensors of
 # these names
+# the grid tables of camera c = 1, 2 that FramePipeline(keep_tables=True) adds to the fit's dict (a one-camera source: that camera's)
+def tables_outputs(cameras=(1, 2)):
+    return {f'tables_{k}{c}': v for c in cameras for k, v in (('xy', ((fit.MAXP, 2), _F64)), ('id', ((fit.MAXP, 2), _I32)), ('cnt', ((), _I32)))}
+
+
 PIXELS_OUTPUTS = dict(pixels_taken=((), torch.bool), pixels_fvals=((2,), _F64), pixels_stats=((4,), _F64), pixels_counts=((4,), _I32),
                       pixels_status=((), _I32))
 
@@ -186,7 +191,7 @@ class FramePipeline:
 
     def __init__(self, h, w, K1, K2, T21, radius, chunk=64, device='cuda:0', selector=fit.SEL_CHOOSE_IDX, th=0.3,
                  fit_mode=fit.FIT_NELDER_MEAD, lanes=1, ransac=None, stage='full', match=None, target='cylinder', plane=None,
-                 source='stereo', laser_table=None, table=None, relabel=None, refine=None, pixels=None):
+                 source='stereo', laser_table=None, table=None, relabel=None, refine=None, pixels=None, keep_tables=False):
         # ---- which combinations exist: the rows of _MODES; everything else is refused here ----
         if stage not in ('full', 'detect'):
             raise ValueError("stage is 'full' or 'detect'")
@@ -261,6 +266,9 @@ class FramePipeline:
         # mode's fit, no mode of its own: the fit's pose is polished on the pixels of the tables it was made from
         # (fit.polish_with_pixels); the records then hold the polished cyl, every other word stays the 3-D fit's
         self.pixels = None if pixels is None else dict(pixels)
+        # keep_tables (opt-in): the fit's dict also holds the grid tables the fit was made from (after refine= / repair=), flat as
+        # tables_outputs() names them, so that run_raw can keep them beside the fits (experiment.run_experiment(multi_frame_pixels=))
+        self.keep_tables = bool(keep_tables)
         self.ws = {}
         # chunks are independent: `lanes` of them are in flight on their own HIP streams (each with its own
         # workspace), so the serial tails of one chunk (blob grouping, line fitting: one workgroup per frame)
@@ -306,6 +314,16 @@ class FramePipeline:
                 K, Tc = (self.K1, None) if g2 is None else (self.K2, self.T21)
                 out = fit.polish_mono_with_pixels(out, out.get('tables', g1 if g2 is None else g2), K, Tc, self.laser_table, self.radius,
                                                   self.pixels)
+        if self.keep_tables:
+            if mode.cameras == 'LR':
+                kept = (out.get('tables1', g1), out.get('tables2', g2))
+            else:
+                one = out.get('tables', g1 if g2 is None else g2)
+                kept = (one, None) if g2 is None else (None, one)
+            out = dict(out)
+            for c, t in zip((1, 2), kept):
+                if t is not None:
+                    out.update({f'tables_xy{c}': t.xy, f'tables_id{c}': t.id, f'tables_cnt{c}': t.cnt})
         return mode.record(out, st_l, st_r), det, out
 
     def run(self, left, right):

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 129  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 130  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -60,7 +60,7 @@ extern "C" {
                              123: cpe_grid_relabel_batch; 124: cpe_grid_predict_batch, cpe_grid_assign_batch;
                              125: cpe_debug_ccl_tiles; 126: cpe_debug_state_field;
                              127: cpe_mono_shift_batch; 128: cpe_est_curvatures_batch, cpe_curvature_consensus_batch;
-                             129: cpe_fit_cylinder_pixels_batch) */
+                             129: cpe_fit_cylinder_pixels_batch; 130: cpe_multi_frame_fit_pixels_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -1470,6 +1470,73 @@ CPE_API int32_t cpe_fit_cylinder_pixels_batch(const double *xy1, const int32_t *
                                               double tol_f, int32_t max_iter, double *cyl, double *fvals, int32_t *iters,
                                               int32_t *counts, double *stats, int32_t *status, double *res, int32_t *pt_state,
                                               double *X, void *stream);
+
+/* Row f-1, BUILD-DEFINED, opt-in: T_Cam_AGV fitted to the PIXELS of every frame of a group at once.  The three point-based forms
+ * (cpe_multi_frame_fit_batch, _lm_batch, _consensus_batch) minimise dist - R over triangulated points; cpe_fit_cylinder_pixels_batch
+ * fits one frame's four observable unknowns alone.  Here every kept frame's cylinder is T_Cam_AGV * getTAGVcyl(pan, tilt) and the
+ * six unknowns of T_Cam_AGV are fitted to every detection of every kept frame: the maximum-likelihood calibration for isotropic
+ * pixel noise, with the laser table rigid in camera-1 coordinates across the frames.  One workgroup per group, one launch on
+ * `stream`, no atomics, no workspace, no allocation, no host synchronisation; two calls on equal inputs give equal bits, and a
+ * group's outputs do not depend on its place in the batch.
+ *   xy1, id1, cnt1, xy2, id2, cnt2: the two cameras' tables for n frames, exactly as cpe_fit_cylinder_pixels_batch takes them
+ *     (either camera may be absent: all three pointers NULL; both absent, or one given in part: CPE_ERR_ARG)
+ *   TAGVcyl f64[n,16], frame_ok i32[n] or NULL, group_start i32[G+1] (device), G, n: exactly as cpe_multi_frame_fit_lm_batch takes
+ *     them (kept frames, CPE_MULTI_MAXF, CPE_ST_OVERFLOW).  Unlike there, the ranges of two groups may not share a frame: pt_state
+ *     holds the membership of S while the call runs (not checked)
+ *   x0_in f64[G,6], REQUIRED: the start [rotation vector, translation] of T_Cam_AGV, as the point-based calls return in x.  There
+ *     is no closed-form start in pixel space: NULL is CPE_ERR_ARG
+ *   radius, K1, K2, T21, P, line_status, lo, hi, centre, swap, min_cos, gate_px, tol_x, tol_f, max_iter: as
+ *     cpe_fit_cylinder_pixels_batch, with the same CPE_ERR_ARG cases
+ *   sel_cos in [min_cos, 1): the grazing gate for MEMBERSHIP only (rule 3); outside that range: CPE_ERR_ARG.  A silhouette node
+ *     that just exists at the start pose ceases to exist a step later and its NaN refuses every such trial; members chosen with
+ *     a stricter gate than the one they are evaluated with keep their nodes on the way (the Python layer's default is 0.35)
+ * Rule per group (the order is the contract):
+ *   1. the kept frames are those of cpe_multi_frame_fit_lm_batch; fewer than two: CPE_ST_FEW_POINTS.  Any number of x0_in[g] not
+ *      finite: CPE_ST_FEW_POINTS;
+ *   2. the pose of kept frame i at x: o_i = Rot p_i + t, a_i = Rot a_col_i with [Rot t] = vec2T(x) and a_col_i, p_i columns 2 and 4
+ *      of TAGVcyl_i (the axis and origin cpe_multi_frame_terms uses);
+ *   3. the used set S, decided ONCE at x0: a detection of a kept frame belongs to S when it passes rule 2 of
+ *      cpe_fit_cylinder_pixels_batch at the pose (o_i, a_i) with sel_cos in place of min_cos, and, with gate_px > 0, its residual
+ *      norm is below gate_px.  A kept frame contributes what it has, down to nothing.  |S| over the group below
+ *      CPE_PIXFIT_MIN_PTS, or fewer than two kept frames with a member: CPE_ST_FEW_POINTS;
+ *   4. F(x) = sum over S of (rx rx + ry ry), evaluated with min_cos.  When any member fails at x, or x or any kept frame's pose is
+ *      not finite, F(x) is NaN and the trial is rejected;
+ *   5. Levenberg-Marquardt from (x0, F(x0)) on six unknowns: the loop of cpe_multi_frame_fit_lm_batch (damping, 12 trials per
+ *      iteration, stop rule, at most min(max_iter, 200) iterations) with its step Rot <- exp([dw]x) Rot, t <- t + dt, the candidate
+ *      x = T2vec of that pose;
+ *   6. the Jacobian of a member's two residuals: with u = gp / den, w = (g.ah) gp / (|a| den), s_x, s_y of rule 7 of
+ *      cpe_fit_cylinder_pixels_batch at (o_i, a_i) and m_i = Rot p_i:  j_w = m_i x u + a_i x w,  j_t = u;  the rows are s_x (j_w, j_t)
+ *      and s_y (j_w, j_t)  (do = dw x m_i + dt, da = dw x a_i);
+ *   7. the outputs are written at the final x.  A final x or F that is not finite: CPE_ST_FEW_POINTS.
+ * Outputs per group, every slot written: x f64[G,6]; T f64[G,16] = vec2T(x); fvals f64[G,2] = F(x0), F(x); iters i32[G,2] =
+ *   iterations, objective evaluations (F(x0) included); n_used i32[G] kept frames; counts i32[G,4] = |S| of camera 1 | of camera 2
+ *   | refused | gated, over the kept frames; stats f64[G,4] = rms residual norm of camera 1 | of camera 2 | sqrt(F / |S|) | the
+ *   largest residual norm; status i32[G]; N f64[G,21] or NULL: the upper triangle (packed by rows) of J'J at x in the step's
+ *   coordinates (dw, dt), from one more Jacobian pass that iters does not count -- the covariance of (dw, dt) is
+ *   F / (2 |S| - 6) * inverse(N).  A group that is not CPE_ST_OK has every other per-group output zero.
+ * Outputs per frame: pt_state i32[n,2,CPE_MAXP], REQUIRED: 0 in S, 1 refused, 2 gated, -1 past the count (every slot of an absent
+ *   camera); written for every frame of every group's range, kept or not, whatever the group's status (a range outside [0, n]
+ *   excepted); a frame that is not kept, and every frame of a group that rule 1 refuses, has 1 below the counts.
+ *   frame_cyl f64[n,6] = (o_i, a_i) at x; frame_stats f64[n,4] = the frame's rms of camera 1 | of camera 2 | of both | largest
+ *   residual norm (0 where it has no member); res f64[n,2,CPE_MAXP,2] or NULL: predicted - detected at x, 0 outside S and past the
+ *   counts.  These three are written only for the kept frames of groups that end CPE_ST_OK, as frame_terms of
+ *   cpe_multi_frame_fit_lm_batch is: initialise them.
+ * CPE_ERR_ARG, nothing launched or written: the cases of cpe_fit_cylinder_pixels_batch; sel_cos outside [min_cos, 1); G < 0 or
+ * n < 0; a NULL required pointer (x0_in and pt_state among them); an output that overlaps an input or another output.  G == 0 is
+ * a no-op.
+ * Limits: the radius is fixed and the cylinder ideal and rigid; the table must be rigid with camera 1 across the frames; the
+ * indices are trusted (re-number first); S is fixed at the start pose, so the start must come from a point-based multi-frame fit;
+ * the nominal pan and tilt are taken as exact. */
+CPE_API int32_t cpe_multi_frame_fit_pixels_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
+                                                 const int32_t *id2, const int32_t *cnt2, const double *TAGVcyl,
+                                                 const int32_t *frame_ok, const int32_t *group_start, int32_t G, int32_t n,
+                                                 const double *x0_in, double radius, const double *K1, const double *K2,
+                                                 const double *T21, const double *P, const int32_t *line_status, int32_t lo,
+                                                 int32_t hi, const double *centre, int32_t swap, double min_cos, double sel_cos,
+                                                 double gate_px, double tol_x, double tol_f, int32_t max_iter, double *x, double *T,
+                                                 double *fvals, int32_t *iters, int32_t *n_used, int32_t *counts, double *stats,
+                                                 int32_t *status, double *N, int32_t *pt_state, double *frame_cyl,
+                                                 double *frame_stats, double *res, void *stream);
 
 #ifdef __cplusplus
 }
