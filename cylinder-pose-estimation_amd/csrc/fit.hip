@@ -1519,7 +1519,8 @@ struct MultiObjectiveT {
 };
 using MultiObjective = MultiObjectiveT<MF_WAVES>;
 
-// the kept frames of [a, b) into sIdx, in order (one wavefront): counted past MF_MAXF, stored up to it.  -> the count
+// the kept frames of [a, b) into sIdx, in order (one wavefront): counted past CAP, stored up to it.  -> the count
+template <int CAP = MF_MAXF>
 __device__ __forceinline__ int multi_kept_frames(const int *__restrict__ frame_ok, int a, int b, bool range_ok, int lane, int *sIdx)
 {
     int nk = 0;
@@ -1529,7 +1530,7 @@ __device__ __forceinline__ int multi_kept_frames(const int *__restrict__ frame_o
             const bool keep = f < b && (frame_ok == nullptr || frame_ok[f] != 0);
             const unsigned long long bal = __ballot(keep);
             const int pos = nk + __popcll(bal & ((1ull << lane) - 1ull));
-            if (keep && pos < MF_MAXF) sIdx[pos] = (int)f;
+            if (keep && pos < CAP) sIdx[pos] = (int)f;
             nk += __popcll(bal);
         }
     return nk;
@@ -1566,21 +1567,21 @@ struct MultiOut {
 
 // The head of the multi-frame kernels for group g: the kept frames of [group_start[g], group_start[g + 1]) into sIdx (LDS; sNk
 // one int of LDS), one barrier.  -> their count nk >= 2, or 0 after the group's record is written: OVERFLOW for a range outside
-// [0, n] or more than MF_MAXF kept frames, FEW_POINTS below two (assert(nAngles >= 2), fitCylinderWPts3sAngs.m:29)
+// [0, n] or more than CAP kept frames (sIdx holds CAP), FEW_POINTS below two (assert(nAngles >= 2), fitCylinderWPts3sAngs.m:29)
 // Out: MultiOut, or ConsensusOut with its further outputs
-template <class Out>
+template <int CAP = MF_MAXF, class Out>
 __device__ __forceinline__ int multi_group_begin(const int *__restrict__ frame_ok, const int *__restrict__ group_start, int n, int g,
                                                  int *sIdx, int *sNk, const Out &out)
 {
     const int a = group_start[g], b = group_start[g + 1];
     const bool range_ok = 0 <= a && a <= b && b <= n;
     if (threadIdx.x < 64) {
-        const int nk = multi_kept_frames(frame_ok, a, b, range_ok, threadIdx.x, sIdx);
+        const int nk = multi_kept_frames<CAP>(frame_ok, a, b, range_ok, threadIdx.x, sIdx);
         if (threadIdx.x == 0) *sNk = nk;
     }
     __syncthreads();
     const int nk = *sNk;
-    if (!range_ok || nk > MF_MAXF) { out.write_failed(g, CPE_ST_OVERFLOW); return 0; }
+    if (!range_ok || nk > CAP) { out.write_failed(g, CPE_ST_OVERFLOW); return 0; }
     if (nk < 2) { out.write_failed(g, CPE_ST_FEW_POINTS); return 0; }
     return nk;
 }
@@ -6191,6 +6192,525 @@ __global__ __launch_bounds__(64 * WAVES) void k_multi_frame_pixels(
         out.status[g] = CPE_ST_OK;
     }
 }
+
+// ---- BUILD-DEFINED (include/cpe.h cpe_multi_frame_fit_pixels_angles_batch, whose numbered rule this follows): T_Cam_AGV and the
+// (pan, tilt) of every kept frame fitted jointly to the pixels of a group, the angles held at their nominal values by a prior.
+// The system is an arrowhead: 6 shared unknowns x, 2 per kept frame q_i, and q_i meets only frame i's rows.
+// k_multi_frame_pixels_angles: k_multi_frame_pixels' layout (wave w takes kept frames w, w + WAVES, ...; lane l the detections l,
+// l + 64, ...; the table in LDS; membership of S in pt_state), its problem reused for the tables, the pose step and the LDS rows.
+// New is the per-frame state in LDS, MFJ_FRAME doubles per kept frame: the two angle pairs (the current one and the trial, which
+// swap roles on an accepted trial, so nothing is copied) and the frame's blocks V_i, W_i, g_i.  Only the wave that owns a frame
+// ever touches its state: lane 0 writes the blocks at the end of the frame in the Jacobian pass, and in the trial solve lane j of
+// wave w takes the wave's j-th frame.  So the barriers of the passes are all the ordering the state needs.
+constexpr int MFJ_MAXF = CPE_MFJOINT_MAXF;
+constexpr int MFJ_WAVES = 4;                                        // the LDS below is sized for it: 63.9 KB of the 64 KB
+constexpr int MFJ_V = 4, MFJ_W = 7, MFJ_G = 19, MFJ_FRAME = 21;   // q[2][2] | V 00 01 11 | W[6][2] | g[2]
+constexpr int MFJ_LOCAL = 17;                                       // the sums of a frame's blocks: V | W | g
+constexpr int MFJ_RED = MFLM_SUMS + 1;                              // sum Y W' (21) | sum Y g (6) | a singular V_i
+constexpr double MFJ_TILT_MAX = 1.5707963267948966 - 1e-3;         // k_frame_angles_lm's: tan(tilt) of the chain has its pole at pi/2
+
+struct MultiJointOut : MultiPixOut {
+    double *angles;
+    double *frame_N;               // optional
+};
+
+template <int WAVES>
+struct MultiJointProblem : MultiPixProblem<WAVES> {
+    using Base = MultiPixProblem<WAVES>;
+    const double *angles0;
+    double *sFr;                   // LDS, [nk][MFJ_FRAME]
+    double *sRed;                  // LDS, [2][WAVES][MFJ_RED]
+    double *sD;                    // LDS, [2][WAVES]: the waves' largest |dq| of the trial being evaluated
+    double wp2, wt2;               // the prior weights, squared
+    int cur, rrow;                 // the angle pair that is the current point; the row of sRed to write next
+    double dq_wave, dq_max;        // the largest |dq| of this wave's frames; of all (after operator())
+
+    __device__ __forceinline__ double *state(int kf) const { return sFr + kf * MFJ_FRAME; }
+    // rule 2: the chain, (o, a) and ah = a / |a| of a frame with the angles q at the pose Tm -> usable
+    __device__ __forceinline__ static bool frame_pose_at(const double *Tm, const double *q, double *A, double *oa, double *ah, double &an)
+    {
+        agv_chain(q[0], q[1], A);
+        frame_axis(Tm, A, oa, oa + 3);
+        return PixFrame::pose(oa, ah, an) && isfinite(q[0]) && isfinite(q[1]) && fabs(q[1]) < MFJ_TILT_MAX;
+    }
+    // rule 4 at (x, the angle pairs `sel`)
+    __device__ __forceinline__ double evaluate(const double *x, int sel)
+    {
+        double Tm[16], acc = 0.0;
+        pose_vec2T(x, Tm);
+        bool bad = false;
+#pragma unroll
+        for (int a = 0; a < 6; a++) bad = bad || !isfinite(x[a]);
+        for (int kf = this->wave; kf < this->nk; kf += WAVES) {
+            const int f = this->sIdx[kf];
+            const double q[2] = {state(kf)[2 * sel], state(kf)[2 * sel + 1]};
+            double A[16], oa[6], ah[3], an;
+            this->frame(f);
+            if (!frame_pose_at(Tm, q, A, oa, ah, an)) bad = true;
+            for (int k = this->lane; k < this->fr.n12; k += 64) {
+                if (this->pt_state[this->slot_of(f, k)] != 0) continue;
+                PixEval e;
+                if (!this->fr.eval_k(k, oa, ah, e)) { bad = true; continue; }
+                acc = acc + (e.r[0] * e.r[0] + e.r[1] * e.r[1]);
+            }
+            if (this->lane == 0) {
+                const double d0 = q[0] - angles0[2 * (size_t)f], d1 = q[1] - angles0[2 * (size_t)f + 1];
+                acc = acc + (wp2 * (d0 * d0) + wt2 * (d1 * d1));
+            }
+        }
+        acc = wave_sum(acc);
+        const int wbad = __ballot(bad) != 0ull;
+        double *rf = this->sF + this->row * WAVES, *rd = sD + this->row * WAVES;
+        int *rb = this->sBad + this->row * WAVES;
+        this->row ^= 1;
+        if (this->lane == 0) { rf[this->wave] = acc; rb[this->wave] = wbad; rd[this->wave] = dq_wave; }
+        __syncthreads();
+        double v = 0.0;
+        int any = 0;
+        dq_max = 0.0;
+        for (int w = 0; w < WAVES; w++) { v = v + rf[w]; any |= rb[w]; dq_max = fmax(dq_max, rd[w]); }
+        return any ? __longlong_as_double(0x7ff8000000000000ll) : v;
+    }
+    __device__ __forceinline__ double operator()(const double *xn) { return evaluate(xn, cur ^ 1); }   // the trial
+    __device__ __forceinline__ void accept() { cur ^= 1; }
+
+    // rule 6 at (x, the current angles): U and g_x to every wave, the frames' blocks into their states.  One sweep over this
+    // wave's frames with all 44 accumulators: the 27 sums of the pose columns, and each frame's 17, reduced at the end of the
+    // frame, the prior added.  No scratch: profiles/r34_resource_usage_multiframe_joint.txt.  (Split in two sweeps, the 27 and
+    // then the 17, it needs none either and makes every node twice: 27 - 34 % slower)
+    __device__ __forceinline__ void normal(const double *x, double *U, double *gx)
+    {
+        pose_vec2T(x, this->T);
+        const double *T = this->T;
+        double acc[MFLM_SUMS];
+#pragma unroll
+        for (int k = 0; k < MFLM_SUMS; k++) acc[k] = 0.0;
+        for (int kf = this->wave; kf < this->nk; kf += WAVES) {
+            const int f = this->sIdx[kf];
+            const double q[2] = {state(kf)[2 * cur], state(kf)[2 * cur + 1]};
+            double A[16], oa[6], ah[3], an, m[3], da[6], dp[6], dob[6], dvb[6], loc[MFJ_LOCAL];
+            this->frame(f);
+            frame_pose_at(T, q, A, oa, ah, an);
+#pragma unroll
+            for (int r = 0; r < 3; r++) m[r] = (T[r * 4] * A[3] + T[r * 4 + 1] * A[7]) + T[r * 4 + 2] * A[11];
+            agv_chain_derivatives(q[0], q[1], da, dp);
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    dob[3 * j + r] = (T[r * 4] * dp[3 * j] + T[r * 4 + 1] * dp[3 * j + 1]) + T[r * 4 + 2] * dp[3 * j + 2];
+                    dvb[3 * j + r] = (T[r * 4] * da[3 * j] + T[r * 4 + 1] * da[3 * j + 1]) + T[r * 4 + 2] * da[3 * j + 2];
+                }
+#pragma unroll
+            for (int k = 0; k < MFJ_LOCAL; k++) loc[k] = 0.0;
+            for (int k = this->lane; k < this->fr.n12; k += 64) {
+                if (this->pt_state[this->slot_of(f, k)] != 0) continue;
+                PixEval e;
+                if (!this->fr.eval_k(k, oa, ah, e)) continue;
+                double dt[6], s[2], mu[3], aw[3], jq[2];
+                this->fr.node_derivatives(e, oa, ah, an, dt, s[0], s[1]);
+                cross3(m, dt, mu);
+                cross3(oa + 3, dt + 3, aw);
+                const double jp[6] = {mu[0] + aw[0], mu[1] + aw[1], mu[2] + aw[2], dt[0], dt[1], dt[2]};
+#pragma unroll
+                for (int j = 0; j < 2; j++) jq[j] = dot3(dt, dob + 3 * j) + dot3(dt + 3, dvb + 3 * j);
+#pragma unroll
+                for (int c = 0; c < 2; c++) {                              // the x row, then the y row
+                    double j[6];
+#pragma unroll
+                    for (int a = 0; a < 6; a++) j[a] = s[c] * jp[a];
+                    normal_accumulate<6>(j, e.r[c], acc);
+                    const double j6 = s[c] * jq[0], j7 = s[c] * jq[1];
+                    loc[0] = loc[0] + j6 * j6; loc[1] = loc[1] + j6 * j7; loc[2] = loc[2] + j7 * j7;
+#pragma unroll
+                    for (int a = 0; a < 6; a++) {
+                        loc[3 + 2 * a] = loc[3 + 2 * a] + j[a] * j6;
+                        loc[4 + 2 * a] = loc[4 + 2 * a] + j[a] * j7;
+                    }
+                    loc[15] = loc[15] + j6 * e.r[c]; loc[16] = loc[16] + j7 * e.r[c];
+                }
+            }
+            double *st = state(kf);
+            const double d0 = q[0] - angles0[2 * (size_t)f], d1 = q[1] - angles0[2 * (size_t)f + 1];
+#pragma unroll
+            for (int k = 0; k < MFJ_LOCAL; k++) {
+                double v = wave_sum(loc[k]);
+                if (k == 0) v = v + wp2;
+                if (k == 2) v = v + wt2;
+                if (k == 15) v = v + wp2 * d0;
+                if (k == 16) v = v + wt2 * d1;
+                if (this->lane == 0) st[MFJ_V + k] = v;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < MFLM_SUMS; k++) {
+            const double s = wave_sum(acc[k]);
+            if (this->lane == 0) this->sJ[this->wave * MFLM_SUMS + k] = s;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < MFLM_SUMS; k++) {
+            double s = 0.0;
+            for (int w = 0; w < WAVES; w++) s = s + this->sJ[w * MFLM_SUMS + k];
+            if (k < 21) U[k] = s;
+            else gx[k - 21] = s;
+        }
+    }
+    // the 2 x 2 block of a frame as rule 7 damps it (DAMPED) or as it stands -> its determinant
+    template <bool DAMPED>
+    __device__ __forceinline__ static double block(const double *st, double lambda, double &m00, double &m11)
+    {
+        const double v0 = st[MFJ_V], v1 = st[MFJ_V + 1], v2 = st[MFJ_V + 2], tr = v0 + v2;
+        m00 = DAMPED ? v0 + lambda * v0 + 1e-12 * tr : v0;
+        m11 = DAMPED ? v2 + lambda * v2 + 1e-12 * tr : v2;
+        return m00 * m11 - v1 * v1;
+    }
+    // rule 7's sums over ALL kept frames: R[0..20] = sum Y_i W_i' (upper triangle), R[21..26] = sum Y_i g_i.  Every wave adds its
+    // own frames (lane j its j-th), the waves are added in wave order: all waves hold the same numbers.  -> no block was singular
+    template <bool DAMPED>
+    __device__ __forceinline__ bool reduce(double lambda, double *R)
+    {
+        double acc[MFLM_SUMS];
+#pragma unroll
+        for (int k = 0; k < MFLM_SUMS; k++) acc[k] = 0.0;
+        bool sing = false;
+        for (int kf = this->wave + WAVES * this->lane; kf < this->nk; kf += WAVES * 64) {
+            const double *st = state(kf), *W = st + MFJ_W, *g = st + MFJ_G;
+            double m00, m11, Y[12];
+            const double det = block<DAMPED>(st, lambda, m00, m11), v1 = st[MFJ_V + 1];
+            sing = sing || det == 0;
+#pragma unroll
+            for (int a = 0; a < 6; a++) {
+                Y[2 * a] = (W[2 * a] * m11 - W[2 * a + 1] * v1) / det;
+                Y[2 * a + 1] = (W[2 * a + 1] * m00 - W[2 * a] * v1) / det;
+            }
+            int i = 0;
+#pragma unroll
+            for (int a = 0; a < 6; a++) {
+#pragma unroll
+                for (int b = a; b < 6; b++) { acc[i] = acc[i] + (Y[2 * a] * W[2 * b] + Y[2 * a + 1] * W[2 * b + 1]); i++; }
+                acc[21 + a] = acc[21 + a] + (Y[2 * a] * g[0] + Y[2 * a + 1] * g[1]);
+            }
+        }
+        double *rr = sRed + (rrow * WAVES + this->wave) * MFJ_RED;
+        const double *all = sRed + rrow * WAVES * MFJ_RED;
+        rrow ^= 1;
+#pragma unroll
+        for (int k = 0; k < MFLM_SUMS; k++) {
+            const double s = wave_sum(acc[k]);
+            if (this->lane == 0) rr[k] = s;
+        }
+        const bool wsing = __ballot(sing) != 0ull;
+        if (this->lane == 0) rr[MFLM_SUMS] = wsing ? 1.0 : 0.0;
+        __syncthreads();
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < MFLM_SUMS; k++) R[k] = 0.0;
+        for (int w = 0; w < WAVES; w++) {
+#pragma unroll
+            for (int k = 0; k < MFLM_SUMS; k++) R[k] = R[k] + all[w * MFJ_RED + k];
+            any = any || all[w * MFJ_RED + MFLM_SUMS] != 0.0;
+        }
+        return !any;
+    }
+    // rule 7: one damped trial from (x, the current angles) -> dx, the candidate xn, and the trial angles in the frames' states;
+    // false: a block was singular, nothing may be evaluated.  (Two barriers when it succeeds, one when the 6 x 6 system fails,
+    // the same for every wave: the numbers they branch on are the same.)
+    __device__ __forceinline__ bool trial(const double *U, const double *gx, double lambda, double *dx, double *xn)
+    {
+        double R[MFLM_SUMS], M[36], rhs[6];
+        const bool blocks_ok = reduce<true>(lambda, R);
+        int i = 0;
+        double trU = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int b = a; b < 6; b++) { if (a == b) trU = trU + U[i]; i++; }
+        i = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++) {
+#pragma unroll
+            for (int b = a; b < 6; b++) {
+                const double u = a == b ? U[i] + lambda * U[i] + 1e-12 * trU : U[i];
+                M[a * 6 + b] = u - R[i];
+                M[b * 6 + a] = u - R[i];
+                i++;
+            }
+            rhs[a] = -gx[a] + R[21 + a];
+        }
+        if (!gauss_solve<6>(M, rhs, dx) || !blocks_ok) return false;
+        double dmax = 0.0;
+        for (int kf = this->wave + WAVES * this->lane; kf < this->nk; kf += WAVES * 64) {
+            double *st = state(kf);
+            const double *W = st + MFJ_W;
+            double m00, m11, t0 = st[MFJ_G], t1 = st[MFJ_G + 1];
+            const double det = block<true>(st, lambda, m00, m11), v1 = st[MFJ_V + 1];
+#pragma unroll
+            for (int a = 0; a < 6; a++) { t0 = t0 + W[2 * a] * dx[a]; t1 = t1 + W[2 * a + 1] * dx[a]; }
+            const double d0 = (v1 * t1 - m11 * t0) / det, d1 = (v1 * t0 - m00 * t1) / det;   // lm_damped_solve<2>'s form
+            // (a zero step keeps the angle's bits, rule 9: -0.0 + 0.0 would be +0.0)
+            st[2 * (cur ^ 1)] = d0 == 0.0 ? st[2 * cur] : st[2 * cur] + d0;
+            st[2 * (cur ^ 1) + 1] = d1 == 0.0 ? st[2 * cur + 1] : st[2 * cur + 1] + d1;
+            dmax = fmax(dmax, fmax(fabs(d0), fabs(d1)));
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) dmax = fmax(dmax, __shfl_xor(dmax, off, 64));
+        dq_wave = dmax;
+        __syncthreads();                               // the trial angles, written per lane, are read per frame by the whole wave
+        return this->candidate(nullptr, dx, xn);
+    }
+};
+
+// Levenberg-Marquardt on an arrowhead system (shared unknowns x, per-block unknowns that the problem keeps itself): the sibling
+// of lm_minimize, with its rules, for a problem that eliminates its blocks.  A problem supplies
+//   normal(x, U, g)                  one Jacobian pass at the current point: the shared block (packed) and gradient
+//   bool trial(U, g, lambda, dx, xn) the damped block solve, the step dx and the candidate xn (its block unknowns inside the
+//                                    problem); false: singular, xn may not be evaluated
+//   double operator()(xn)            the objective at the candidate; dq_max: the largest block step of it
+//   accept()                         the candidate's block unknowns become the current ones
+// The constants are lm_minimize's and stand here once.  Barriers: as lm_minimize says, no branch may depend on the wave or lane.
+template <int N, class Problem>
+__device__ __forceinline__ void lm_minimize_arrowhead(Problem &prob, const double *x0, double f0, double tolx, double tolf, int maxiter,
+                                                      double *x, double &fx, int &itercount, int &func_evals)
+{
+    constexpr double LAMBDA0 = 1e-3, LAMBDA_STEP = 10, LAMBDA_MIN = 1e-12, TOLF_SCALE = 1e-3;
+    constexpr int TRIALS = 12, MAX_ITER = 200;
+#pragma unroll
+    for (int k = 0; k < N; k++) x[k] = x0[k];
+    fx = f0;
+    double lambda = LAMBDA0;
+    itercount = 0;
+    for (; itercount < maxiter && itercount < MAX_ITER;) {
+        double U[N * (N + 1) / 2], g[N];
+        prob.normal(x, U, g);
+        itercount++;
+        bool accepted = false;
+        double dmax = 0;
+        const double fprev = fx;
+        for (int tr = 0; tr < TRIALS && !accepted; tr++) {
+            double dx[N], xn[N];
+            if (!prob.trial(U, g, lambda, dx, xn)) { lambda = lambda * LAMBDA_STEP; continue; }
+            const double fn = prob(xn);
+            func_evals++;
+            if (fn < fx) {
+                dmax = prob.dq_max;
+#pragma unroll
+                for (int k = 0; k < N; k++) dmax = fmax(dmax, fabs(dx[k]));
+#pragma unroll
+                for (int k = 0; k < N; k++) x[k] = xn[k];
+                prob.accept();
+                fx = fn;
+                lambda = fmax(lambda / LAMBDA_STEP, LAMBDA_MIN);
+                accepted = true;
+            } else {
+                lambda = lambda * LAMBDA_STEP;
+            }
+        }
+        if (!accepted) break;
+        if ((fprev - fx) <= tolf * TOLF_SCALE * (1.0 + fx) && dmax <= tolx) break;
+    }
+}
+
+// Barriers: those of k_multi_frame_pixels, and two per trial solve (MultiJointProblem::trial).  None stands under a condition
+// that depends on the wave or the lane.
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_multi_frame_pixels_angles(
+    const double *__restrict__ xy1, const int *__restrict__ id1, const int *__restrict__ cnt1, const double *__restrict__ xy2,
+    const int *__restrict__ id2, const int *__restrict__ cnt2, const double *__restrict__ angles0, const int *__restrict__ frame_ok,
+    const int *__restrict__ group_start, int n, const double *__restrict__ x0_in, double w_pan, double w_tilt, double R,
+    const double *__restrict__ K1, const double *__restrict__ K2, const double *__restrict__ T21, const double *__restrict__ P,
+    const int *__restrict__ line_status, int lo, int L, const double *__restrict__ centre, int swap, double min_cos, double sel_cos,
+    double gate_px, double tolx, double tolf, int maxiter, const MultiJointOut out)
+{
+    __builtin_amdgcn_s_setprio(3);
+    __shared__ double sP[2 * CPE_MAXL * 4];
+    __shared__ int sSt[2 * CPE_MAXL];
+    __shared__ int sIdx[MFJ_MAXF];
+    __shared__ double sFr[MFJ_MAXF * MFJ_FRAME];
+    __shared__ double sJ[WAVES * MFLM_SUMS];
+    __shared__ double sRed[2 * WAVES * MFJ_RED];
+    __shared__ double sF[2 * WAVES];
+    __shared__ double sD[2 * WAVES];
+    __shared__ int sBad[2 * WAVES];
+    __shared__ int sCnt[WAVES * MFPX_CNT];
+    __shared__ double sSt3[WAVES * MFPX_ST];
+    __shared__ int sNk;
+    const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < 8 * L; i += 64 * WAVES) sP[i] = P[i];
+    for (int i = threadIdx.x; i < 2 * L; i += 64 * WAVES) sSt[i] = line_status[i];
+    const int nk = multi_group_begin<MFJ_MAXF>(frame_ok, group_start, n, g, sIdx, &sNk, out);   // (its barrier covers the staging)
+    const int ga = group_start[g], gb = group_start[g + 1];
+    const bool range_ok = 0 <= ga && ga <= gb && gb <= n;
+
+    // rule 1
+    double x0[6] = {0, 0, 0, 0, 0, 0};
+    bool run = nk != 0;
+    if (run) {
+#pragma unroll
+        for (int a = 0; a < 6; a++) { x0[a] = x0_in[6 * (size_t)g + a]; run = run && isfinite(x0[a]); }
+        if (!run) out.write_failed(g, CPE_ST_FEW_POINTS);
+    }
+    // pt_state of every frame of the range: -1 past the counts, 1 below them except where the selection is going to decide
+    if (range_ok)
+        for (int f = ga + wave; f < gb; f += WAVES) {
+            const bool sel = run && (frame_ok == nullptr || frame_ok[f] != 0);
+            for (int c = 0; c < 2; c++) {
+                const int *cn = c ? cnt2 : cnt1;
+                const int m = (c ? xy2 : xy1) ? min(max(cn[f], 0), MAXP) : 0;
+                int *ps = out.pt_state + ((size_t)f * 2 + c) * MAXP;
+                for (int s = sel ? m + lane : lane; s < MAXP; s += 64) ps[s] = s < m ? 1 : -1;
+            }
+        }
+    if (!run) return;
+
+    MultiJointProblem<WAVES> prob;
+    prob.fr.sP = sP; prob.fr.sSt = sSt;
+    prob.fr.lo = lo; prob.fr.hi = lo + (L - 1); prob.fr.L = L; prob.fr.swap = swap;
+    prob.fr.R = R; prob.fr.min_cos = sel_cos;
+#pragma unroll
+    for (int a = 0; a < 3; a++) { prob.fr.centre[a] = centre[a]; prob.fr.t2[a] = T21[4 * a + 3]; }
+    tri_cam(K1, nullptr, prob.fr.cam1);
+    tri_cam(K2, T21, prob.fr.cam2);
+    prob.fr.lane = lane;
+    prob.xy1 = xy1; prob.xy2 = xy2; prob.id1 = id1; prob.id2 = id2; prob.cnt1 = cnt1; prob.cnt2 = cnt2;
+    prob.TAGV = nullptr; prob.pt_state = out.pt_state; prob.sIdx = sIdx; prob.sJ = sJ; prob.sF = sF; prob.sBad = sBad;
+    prob.nk = nk; prob.wave = wave; prob.lane = lane; prob.row = 0;
+    prob.angles0 = angles0; prob.sFr = sFr; prob.sRed = sRed; prob.sD = sD;
+    prob.wp2 = w_pan * w_pan; prob.wt2 = w_tilt * w_tilt;
+    prob.cur = 0; prob.rrow = 0; prob.dq_wave = 0.0; prob.dq_max = 0.0;
+
+    // rule 3: the used set, once, at (x0, angles0) with sel_cos; the frames' states start at the nominal angles
+    {
+        double T0[16];
+        pose_vec2T(x0, T0);
+        int cs[MFPX_CNT] = {0, 0, 0, 0, 0};
+        for (int kf = wave; kf < nk; kf += WAVES) {
+            const int f = sIdx[kf];
+            const double q[2] = {angles0[2 * (size_t)f], angles0[2 * (size_t)f + 1]};
+            double A[16], oa[6], ah[3], an;
+            prob.frame(f);
+            const bool pose_ok = prob.frame_pose_at(T0, q, A, oa, ah, an);
+            if (lane < MFJ_FRAME) prob.state(kf)[lane] = lane < 4 ? ((lane & 1) ? q[1] : q[0]) : 0.0;
+            int members = 0;
+            for (int k = lane; k < prob.fr.n12; k += 64) {
+                PixEval e;
+                int st = 1;
+                if (pose_ok && prob.fr.eval_k(k, oa, ah, e)) {
+                    const double r2 = e.r[0] * e.r[0] + e.r[1] * e.r[1];
+                    st = (gate_px > 0 && sqrt(r2) >= gate_px) ? 2 : 0;
+                }
+                out.pt_state[prob.slot_of(f, k)] = st;
+                cs[0] += st == 0 && k < prob.fr.n1; cs[1] += st == 0 && k >= prob.fr.n1; cs[2] += st == 1; cs[3] += st == 2;
+                members += st == 0;
+            }
+            cs[4] += __ballot(members != 0) != 0ull;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) cs[k] = wave_sum_i(cs[k]);
+        if (lane == 0)
+            for (int k = 0; k < MFPX_CNT; k++) sCnt[wave * MFPX_CNT + k] = cs[k];
+    }
+    __syncthreads();
+    int cs[MFPX_CNT] = {0, 0, 0, 0, 0};
+    for (int w = 0; w < WAVES; w++)
+        for (int k = 0; k < MFPX_CNT; k++) cs[k] += sCnt[w * MFPX_CNT + k];
+    const int nS = cs[0] + cs[1];
+    if (nS < CPE_PIXFIT_MIN_PTS || cs[4] < 2) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+
+    // rules 4 to 8
+    prob.fr.min_cos = min_cos;
+    const double f0 = prob.evaluate(x0, prob.cur);
+    if (!fit_finite(x0, f0)) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+    double x[6], fx;
+    int itercount, func_evals = 1;
+    lm_minimize_arrowhead<6>(prob, x0, f0, tolx, tolf, maxiter, x, fx, itercount, func_evals);
+    if (!fit_finite(x, fx)) { out.write_failed(g, CPE_ST_FEW_POINTS); return; }
+
+    // rule 10: the per-frame outputs and the group's statistics at (x, q)
+    double Tf[16];
+    pose_vec2T(x, Tf);
+    double gs[MFPX_ST] = {0, 0, 0};
+    for (int kf = wave; kf < nk; kf += WAVES) {
+        const int f = sIdx[kf];
+        const double q[2] = {prob.state(kf)[2 * prob.cur], prob.state(kf)[2 * prob.cur + 1]};
+        double A[16], oa[6], ah[3], an, s1 = 0.0, s2 = 0.0, rmax = 0.0;
+        int m1 = 0, m2 = 0;
+        prob.frame(f);
+        prob.frame_pose_at(Tf, q, A, oa, ah, an);
+        const int n1 = prob.fr.n1, n12 = prob.fr.n12;
+        for (int k = lane; k < n12; k += 64) {
+            const size_t at = prob.slot_of(f, k);
+            double r[2] = {0, 0};
+            if (out.pt_state[at] == 0) {
+                PixEval e;
+                if (prob.fr.eval_k(k, oa, ah, e)) {                                // (it does: F(x, q) is finite)
+                    r[0] = e.r[0]; r[1] = e.r[1];
+                    const double r2 = r[0] * r[0] + r[1] * r[1];
+                    if (k >= n1) { s2 = s2 + r2; m2++; } else { s1 = s1 + r2; m1++; }
+                    rmax = fmax(rmax, sqrt(r2));
+                }
+            }
+            if (out.res) { out.res[at * 2] = r[0]; out.res[at * 2 + 1] = r[1]; }
+        }
+        if (out.res)
+            for (int c = 0; c < 2; c++)
+                for (int s = (c ? n12 - n1 : n1) + lane; s < MAXP; s += 64) {
+                    const size_t at = ((size_t)f * 2 + c) * MAXP + s;
+                    out.res[at * 2] = 0; out.res[at * 2 + 1] = 0;
+                }
+        s1 = wave_sum(s1); s2 = wave_sum(s2);
+        m1 = wave_sum_i(m1); m2 = wave_sum_i(m2);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) rmax = fmax(rmax, __shfl_xor(rmax, off, 64));
+        gs[0] = gs[0] + s1; gs[1] = gs[1] + s2; gs[2] = fmax(gs[2], rmax);
+        if (lane == 0) {
+            for (int a = 0; a < 6; a++) out.frame_cyl[6 * (size_t)f + a] = oa[a];
+            out.angles[2 * (size_t)f] = q[0]; out.angles[2 * (size_t)f + 1] = q[1];
+            double *fs = out.frame_stats + 4 * (size_t)f;
+            fs[0] = m1 > 0 ? sqrt(s1 / (double)m1) : 0.0;
+            fs[1] = m2 > 0 ? sqrt(s2 / (double)m2) : 0.0;
+            fs[2] = m1 + m2 > 0 ? sqrt((s1 + s2) / (double)(m1 + m2)) : 0.0;
+            fs[3] = rmax;
+        }
+    }
+    __syncthreads();                                   // every wave has read the sums of the loop's last Jacobian pass
+    if (lane == 0)
+        for (int k = 0; k < MFPX_ST; k++) sSt3[wave * MFPX_ST + k] = gs[k];
+    // one more Jacobian pass for N and frame_N (out.N and out.frame_N are the same for every wave); the barriers either way
+    double U[21], gr[6], Rd[MFLM_SUMS];
+    const bool want_N = out.N != nullptr || out.frame_N != nullptr;
+    if (want_N) {
+        prob.normal(x, U, gr);
+        prob.template reduce<false>(0.0, Rd);
+        if (out.frame_N)
+            for (int kf = wave + WAVES * lane; kf < nk; kf += WAVES * 64) {
+                double *fn = out.frame_N + MFJ_LOCAL * (size_t)sIdx[kf];
+                for (int k = 0; k < MFJ_LOCAL; k++) fn[k] = prob.state(kf)[MFJ_V + k];
+            }
+    } else {
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double S1 = 0.0, S2 = 0.0, rmax = 0.0;
+        for (int w = 0; w < WAVES; w++) {
+            S1 = S1 + sSt3[w * MFPX_ST]; S2 = S2 + sSt3[w * MFPX_ST + 1]; rmax = fmax(rmax, sSt3[w * MFPX_ST + 2]);
+        }
+        for (int k = 0; k < 6; k++) out.x[6 * (size_t)g + k] = x[k];
+        for (int k = 0; k < 16; k++) out.T[16 * (size_t)g + k] = Tf[k];
+        out.fvals[2 * (size_t)g] = f0; out.fvals[2 * (size_t)g + 1] = fx;
+        out.iters[2 * (size_t)g] = itercount; out.iters[2 * (size_t)g + 1] = func_evals;
+        out.nused[g] = nk;
+        for (int k = 0; k < 4; k++) out.counts[4 * (size_t)g + k] = cs[k];
+        double *os = out.stats + 4 * (size_t)g;
+        os[0] = cs[0] > 0 ? sqrt(S1 / (double)cs[0]) : 0.0;
+        os[1] = cs[1] > 0 ? sqrt(S2 / (double)cs[1]) : 0.0;
+        os[2] = sqrt((S1 + S2) / (double)nS);
+        os[3] = rmax;
+        if (out.N)
+            for (int k = 0; k < 21; k++) out.N[21 * (size_t)g + k] = U[k] - Rd[k];
+        out.status[g] = CPE_ST_OK;
+    }
+}
 }  // namespace
 
 extern "C" int32_t cpe_fit_cylinder_pixels_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
@@ -6285,5 +6805,60 @@ extern "C" int32_t cpe_multi_frame_fit_pixels_batch(const double *xy1, const int
                 TAGVcyl, frame_ok, group_start, n, x0_in, radius, K1, K2, T21, P, line_status, lo, L, centre, p.swap, p.min_cos, p.sel_cos,
                 gate_px, p.tol_x, p.tol_f, p.max_iter, out);
     CPE_CHECK_LAUNCH("k_multi_frame_pixels");
+    return CPE_OK;
+}
+
+extern "C" int32_t cpe_multi_frame_fit_pixels_angles_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
+                                                           const int32_t *id2, const int32_t *cnt2, const double *angles0,
+                                                           const int32_t *frame_ok, const int32_t *group_start, int32_t G, int32_t n,
+                                                           const double *x0_in, double w_pan, double w_tilt, double radius,
+                                                           const double *K1, const double *K2, const double *T21, const double *P,
+                                                           const int32_t *line_status, int32_t lo, int32_t hi, const double *centre,
+                                                           int32_t swap, double min_cos, double sel_cos, double gate_px, double tol_x,
+                                                           double tol_f, int32_t max_iter, double *x, double *T, double *fvals,
+                                                           int32_t *iters, int32_t *n_used, int32_t *counts, double *stats,
+                                                           int32_t *status, double *N, int32_t *pt_state, double *frame_cyl,
+                                                           double *frame_stats, double *res, double *angles, double *frame_N,
+                                                           void *stream)
+{
+    CPE_CHECK_ARG(G >= 0 && n >= 0, "cpe_multi_frame_fit_pixels_angles_batch: G < 0 or n < 0");
+    CPE_CHECK_ARG((long long)hi - (long long)lo + 1 >= 1 && (long long)hi - (long long)lo + 1 <= CPE_MAXL,
+                  "cpe_multi_frame_fit_pixels_angles_batch: hi - lo + 1 must be 1..%d", CPE_MAXL);
+    CPE_CHECK_ARG(radius > 0 && radius <= DBL_MAX, "cpe_multi_frame_fit_pixels_angles_batch: radius must be positive and finite");
+    CPE_CHECK_ARG(w_pan > 0 && w_pan <= DBL_MAX && w_tilt > 0 && w_tilt <= DBL_MAX,
+                  "cpe_multi_frame_fit_pixels_angles_batch: w_pan and w_tilt must be positive and finite");
+    const struct { int swap; double min_cos, sel_cos, tol_x, tol_f; int max_iter; } p = {swap, min_cos, sel_cos, tol_x, tol_f, max_iter};
+    CPE_CHECK_ARG(p.min_cos > 0 && p.min_cos < 1 && (p.swap == 0 || p.swap == 1) && p.tol_x > 0 && p.tol_f > 0 && p.max_iter >= 1,
+                  "cpe_multi_frame_fit_pixels_angles_batch: bad parameters (0 < min_cos < 1, swap 0 or 1, tol_x > 0, tol_f > 0, max_iter >= 1)");
+    CPE_CHECK_ARG(p.sel_cos >= p.min_cos && p.sel_cos < 1, "cpe_multi_frame_fit_pixels_angles_batch: sel_cos must lie in [min_cos, 1)");
+    const bool cam1 = xy1 && id1 && cnt1, cam2 = xy2 && id2 && cnt2;
+    CPE_CHECK_ARG((cam1 || (!xy1 && !id1 && !cnt1)) && (cam2 || (!xy2 && !id2 && !cnt2)) && (cam1 || cam2),
+                  "cpe_multi_frame_fit_pixels_angles_batch: a camera is given by all three of xy, id, cnt or by none, and one camera at least");
+    if (G == 0) return CPE_OK;
+    CPE_CHECK_ARG(angles0 && group_start && x0_in && K1 && K2 && T21 && P && line_status && centre && x && T && fvals && iters && n_used &&
+                      counts && stats && status && pt_state && frame_cyl && frame_stats && angles,
+                  "cpe_multi_frame_fit_pixels_angles_batch: null pointer (x0_in is required: there is no closed-form start in pixel space)");
+    const int L = hi - lo + 1;
+    {
+        const size_t Nn = (size_t)n, Gg = (size_t)G, Pp = (size_t)CPE_MAXP;
+        const struct { const void *p; size_t bytes; } buf[31] = {
+            {xy1, cam1 ? Nn * Pp * 16 : 0}, {id1, cam1 ? Nn * Pp * 8 : 0}, {cnt1, cam1 ? Nn * 4 : 0}, {xy2, cam2 ? Nn * Pp * 16 : 0},
+            {id2, cam2 ? Nn * Pp * 8 : 0}, {cnt2, cam2 ? Nn * 4 : 0}, {angles0, Nn * 16}, {frame_ok, frame_ok ? Nn * 4 : 0},
+            {group_start, (Gg + 1) * 4}, {x0_in, Gg * 48}, {K1, 72}, {K2, 72}, {T21, 128}, {P, (size_t)L * 64},
+            {line_status, (size_t)L * 8}, {centre, 24},
+            {x, Gg * 48}, {T, Gg * 128}, {fvals, Gg * 16}, {iters, Gg * 8}, {n_used, Gg * 4}, {counts, Gg * 16}, {stats, Gg * 32},
+            {status, Gg * 4}, {N, N ? Gg * 168 : 0}, {pt_state, Nn * Pp * 8}, {frame_cyl, Nn * 48}, {frame_stats, Nn * 32},
+            {res, res ? Nn * Pp * 32 : 0}, {angles, Nn * 16}, {frame_N, frame_N ? Nn * 136 : 0}};
+        for (int o = 16; o < 31; o++)
+            for (int i = 0; i < o; i++)
+                CPE_CHECK_ARG(!buf[o].bytes || !buf[i].bytes || !rl_overlap(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes),
+                              "cpe_multi_frame_fit_pixels_angles_batch: an output overlaps an input or another output");
+    }
+    const MultiJointOut out = {{x, T, fvals, iters, n_used, counts, stats, status, N, pt_state, frame_cyl, frame_stats, res}, angles, frame_N};
+    CPE_LAUNCH_BEGIN();
+    CPE_KLAUNCH(k_multi_frame_pixels_angles<MFJ_WAVES>, dim3(G), dim3(64 * MFJ_WAVES), 0, (hipStream_t)stream, xy1, id1, cnt1, xy2, id2,
+                cnt2, angles0, frame_ok, group_start, n, x0_in, w_pan, w_tilt, radius, K1, K2, T21, P, line_status, lo, L, centre, p.swap,
+                p.min_cos, p.sel_cos, gate_px, p.tol_x, p.tol_f, p.max_iter, out);
+    CPE_CHECK_LAUNCH("k_multi_frame_pixels_angles");
     return CPE_OK;
 }

@@ -215,7 +215,8 @@ def repair_listing(names, shift, flags, round_taken, renumbered):
 
 def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cuda:0', chunk=32, multi_frame=True, mat_path=None,
                    frame_angles=False, match_offset=None, laser_table=None, source='stereo', projector=None, table_path=None,
-                   curvature=None, consensus=None, refine=None, pixels=None, multi_frame_pixels=None, repair=None):
+                   curvature=None, consensus=None, refine=None, pixels=None, multi_frame_pixels=None, multi_frame_joint=None,
+                   repair=None):
     """-> dict(names, angles (rad, F x 2), records f64 [F,16] (pipeline.REC layout), pts3 f64 [F,MAXP,3] / cnt i32 [F],
                cyl_raw f64 [F,2,6] ([cylParams0; cylParams] of every frame, the multi-frame fit's third input), skipped,
                T_cam_agv (4x4 row-major list) / fval -- None without multi_frame or with fewer than 2 fitted frames)
@@ -314,11 +315,22 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
     multi_frame_pixels = dict(T_cam_agv (16 row-major values, None unless status is 0), x f64 [6], fvals f64 [2] (px^2 at the start
     and the end), px_rms (of all used detections), counts i32 [4], status, cov f64 [6,6] (of the step (dw, dt); NaN unless status is
     0), frame_cyl f64 [F,6], frame_stats f64 [F,4] (NaN for the frames that were not used)) -- None when the point-based fit gave no
-    pose.  T_cam_agv, fval and everything else keep their values.  Any other source or multi_frame raises ValueError."""
-    if multi_frame_pixels is not None and (source not in ('fused', 'left', 'right') or multi_frame is True
-                                           or multi_frame not in ('gpu', 'lm', 'consensus')):
-        raise ValueError("multi_frame_pixels= predicts the pixels from the laser-plane table and starts at a resident multi-frame fit: "
-                         "source must be 'fused', 'left' or 'right' and multi_frame 'gpu', 'lm' or 'consensus'")
+    pose.  T_cam_agv, fval and everything else keep their values.  Any other source or multi_frame raises ValueError.
+
+    multi_frame_joint= (build-defined, opt-in; the preconditions of multi_frame_pixels=): None, or a dict of
+    multiframe.fit_multi_frame_pixels_angles_gpu keywords ({} = its defaults: sigma_px, sigma_angle, w_pan, w_tilt, sel_cos, ...).
+    T_Cam_AGV and every kept frame's pan and tilt are fitted jointly to the pixels (include/cpe.h
+    cpe_multi_frame_fit_pixels_angles_batch), for heads whose angles are not exact.  The start is multi_frame_pixels=' pose when that
+    is given and ended with status 0, else the multi_frame mode's pose; the nominal angles are the file names'.  The dict gains
+    multi_frame_joint = dict(T_cam_agv, x, fvals, px_rms, counts, status, cov, frame_cyl, frame_stats as multi_frame_pixels has them,
+    angles f64 [F,2] (the fitted ones) and angle_sigma f64 [F,2], NaN for the frames that were not used) -- None when there is no
+    start.  Every other entry of the result keeps its bits."""
+    for name, given in (('multi_frame_pixels', multi_frame_pixels), ('multi_frame_joint', multi_frame_joint)):
+        if given is not None and (source not in ('fused', 'left', 'right') or multi_frame is True
+                                  or multi_frame not in ('gpu', 'lm', 'consensus')):
+            raise ValueError(f"{name}= predicts the pixels from the laser-plane table and starts at a resident multi-frame fit: "
+                             "source must be 'fused', 'left' or 'right' and multi_frame 'gpu', 'lm' or 'consensus'")
+    want_tables = multi_frame_pixels is not None or multi_frame_joint is not None
     if pixels is not None and source == 'stereo':
         raise ValueError("pixels= predicts the pixels from the laser-plane table: source must be 'fused', 'left' or 'right'")
     if curvature is not None:
@@ -345,7 +357,7 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
             f.update({k: torch.zeros((F,) + shape, dtype=dt, device=dev) for k, (shape, dt) in pipeline.PIXELS_OUTPUTS.items()})
         if projector is not None:        # the model needs the points' indices, which the selector returns beside the points
             f['idx'] = torch.zeros((F, fit.MAXP, 2), dtype=torch.int32, device=dev)
-        if multi_frame_pixels is not None:
+        if want_tables:
             cams = dict(fused=(1, 2), left=(1,), right=(2,))[source]
             f.update({k: torch.zeros((F,) + shape, dtype=dt, device=dev) for k, (shape, dt) in pipeline.tables_outputs(cams).items()})
         return f
@@ -353,7 +365,7 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
                             lambda h, w, c: pipeline.FramePipeline(h, w, K1, K2, T21, radius, chunk=c, device=dev, match=match_offset,
                                                                    source=source, laser_table=laser_table, refine=refine,
                                                                    table=mono_table, pixels=pixels,
-                                                                   keep_tables=multi_frame_pixels is not None), source)
+                                                                   keep_tables=want_tables), source)
     F = len(names)
     tables = {k: fits.pop(k) for k in list(fits) if k.startswith('tables_')}     # (multi_frame_pixels=: not among the fits' outputs)
     # frame_ok: the device mask of the frames that are not in `skipped`; the resident multi-frame modes mask with it
@@ -430,6 +442,23 @@ def run_experiment(input_path, camera_json, K1, K2, T21, radius=45.0, device='cu
             res['multi_frame_pixels'] = dict(T_cam_agv=px['T'][0].cpu().tolist() if st == 0 else None, x=px['x'][0], fvals=px['fvals'][0],
                                              px_rms=px['stats'][0, 2], counts=px['counts'][0], status=st, cov=px['cov'][0],
                                              frame_cyl=px['frame_cyl'], frame_stats=px['frame_stats'])
+    if multi_frame_joint is not None:
+        res['multi_frame_joint'] = None
+        if res['T_cam_agv'] is not None:
+            t = lambda k: tables.get(k)
+            start = mf['x'][0:1]
+            if multi_frame_pixels is not None and res['multi_frame_pixels']['status'] == 0:
+                start = res['multi_frame_pixels']['x'][None]
+            jt = multiframe.fit_multi_frame_pixels_angles_gpu(t('tables_xy1'), t('tables_id1'), t('tables_cnt1'), t('tables_xy2'),
+                                                              t('tables_id2'), t('tables_cnt2'), angles, start, radius, K1, K2, T21,
+                                                              laser_table, frame_ok=mfp_kept, group_start=[0, F], **multi_frame_joint)
+            st = int(jt['status'][0])
+            if st != 0:
+                warnings.warn(f'the joint multi-frame fit ended with status {st} (include/cpe.h: cpe_multi_frame_fit_pixels_angles_batch)')
+            res['multi_frame_joint'] = dict(T_cam_agv=jt['T'][0].cpu().tolist() if st == 0 else None, x=jt['x'][0], fvals=jt['fvals'][0],
+                                            px_rms=jt['stats'][0, 2], counts=jt['counts'][0], status=st, cov=jt['cov'][0],
+                                            frame_cyl=jt['frame_cyl'], frame_stats=jt['frame_stats'], angles=jt['angles'],
+                                            angle_sigma=jt['angle_sigma'])
     if frame_angles:
         res.update(angles_est=None, angles_status=None, angles_delta_deg=None)
         if res['T_cam_agv'] is not None:

@@ -392,6 +392,49 @@ def fit_multi_frame_consensus_gpu(pts3, cnt, cyl_raw, angles, radius, frame_ok=N
     return out
 
 
+def _pixels_inputs(what, cam1, cam2, x0, radius, K1, K2, T21, laser_table, frame_ok, group_start, sel_cos, min_cos, tol_x, tol_f, max_iter):
+    """what the two pixel-space multi-frame calls share: the arguments checked, and everything but the angles as the C ABI takes it
+    -> dev, n, tabs ((xy, id, cnt) per camera, None for an absent one), frame_ok, group_start i32[G+1], G, x0 f64[G,6], K1, K2, T21,
+    P, line_status, centre"""
+    from . import fit as _fit
+    for c in (cam1, cam2):
+        if any(t is None for t in c) and not all(t is None for t in c):
+            raise ValueError(f'{what}: a camera is given by all three of xy, id, cnt or by none')
+    if cam1[0] is None and cam2[0] is None:
+        raise ValueError(f'{what}: both cameras are absent')
+    if not laser_table.has_centre():
+        raise ValueError(f'{what}: the table has no projector centre (centre_status is not ST_OK)')
+    if not (0 < min_cos < 1 and min_cos <= sel_cos < 1 and tol_x > 0 and tol_f > 0 and int(max_iter) >= 1 and radius > 0):
+        raise ValueError(f'{what}: 0 < min_cos <= sel_cos < 1, tol_x, tol_f, radius > 0 and max_iter >= 1, got {min_cos}, {sel_cos}, '
+                         f'{tol_x}, {tol_f}, {radius}, {max_iter}')
+    if x0 is None:
+        raise ValueError(f'{what}: x0 is required (there is no closed-form start in pixel space)')
+    some = cam1[2] if cam1[2] is not None else cam2[2]
+    dev, n = some.device, some.shape[0]
+    tabs = []
+    for name, c in (('camera 1 ', cam1), ('camera 2 ', cam2)):
+        if c[0] is None:
+            tabs.append((None, None, None))
+            continue
+        gp = _fit.GridTables(c[0].contiguous(), c[1].contiguous(), c[2].contiguous())
+        _fit._check_tables(what, gp, n, name, dev)
+        tabs.append((gp.xy, gp.id, gp.cnt))
+    if group_start is None:
+        group_start = [0, n]
+    if not torch.is_tensor(group_start):
+        group_start = torch.tensor(list(group_start), dtype=torch.int32)
+    gs = group_start.to(device=dev, dtype=torch.int32).contiguous()
+    G = gs.numel() - 1
+    assert G >= 0
+    if frame_ok is not None:
+        frame_ok = frame_ok.to(device=dev, dtype=torch.int32).contiguous()
+        assert frame_ok.shape == (n,)
+    x0 = torch.as_tensor(x0, dtype=torch.float64).to(dev).reshape(G, 6).contiguous()
+    K1, K2, T21 = _fit._cameras(K1, K2, T21, dev)
+    P, st, centre = _fit._table_on(laser_table, dev, centre=True)
+    return dev, n, tabs, frame_ok, gs, G, x0, K1, K2, T21, P, st, centre
+
+
 def fit_multi_frame_pixels_gpu(xy1, id1, cnt1, xy2, id2, cnt2, angles, x0, radius, K1, K2, T21, laser_table, frame_ok=None,
                                group_start=None, sel_cos=0.35, min_cos=0.1, gate_px=0.0, tol_x=1e-9, tol_f=1e-9, max_iter=100,
                                want_res=False):
@@ -410,51 +453,17 @@ def fit_multi_frame_pixels_gpu(xy1, id1, cnt1, xy2, id2, cnt2, angles, x0, radiu
        f64[G,4], status i32[G], N f64[G,21], cov f64[G,6,6] = F / (2 |S| - 6) inverse(J'J) in the step's coordinates (dw, dt), NaN
        where the status is not 0; pt_state i32[n,2,MAXP]; frame_cyl f64[n,6] and frame_stats f64[n,4] (NaN for every frame that is
        not a kept frame of a fitted group); res f64[n,2,MAXP,2] with want_res (zero for those frames), else None; TAGV f64[n,16]"""
-    from . import fit as _fit
     what = 'fit_multi_frame_pixels_gpu'
     L = _lib.load()
-    cam1, cam2 = (xy1, id1, cnt1), (xy2, id2, cnt2)
-    for c in (cam1, cam2):
-        if any(t is None for t in c) and not all(t is None for t in c):
-            raise ValueError(f'{what}: a camera is given by all three of xy, id, cnt or by none')
-    if xy1 is None and xy2 is None:
-        raise ValueError(f'{what}: both cameras are absent')
-    if not laser_table.has_centre():
-        raise ValueError(f'{what}: the table has no projector centre (centre_status is not ST_OK)')
-    if not (0 < min_cos < 1 and min_cos <= sel_cos < 1 and tol_x > 0 and tol_f > 0 and int(max_iter) >= 1 and radius > 0):
-        raise ValueError(f'{what}: 0 < min_cos <= sel_cos < 1, tol_x, tol_f, radius > 0 and max_iter >= 1, got {min_cos}, {sel_cos}, '
-                         f'{tol_x}, {tol_f}, {radius}, {max_iter}')
-    if x0 is None:
-        raise ValueError(f'{what}: x0 is required (there is no closed-form start in pixel space)')
-    some = cnt1 if cnt1 is not None else cnt2
-    dev, n = some.device, some.shape[0]
-    tabs = []
-    for name, c in (('camera 1 ', cam1), ('camera 2 ', cam2)):
-        if c[0] is None:
-            tabs.append((None, None, None))
-            continue
-        gp = _fit.GridTables(c[0].contiguous(), c[1].contiguous(), c[2].contiguous())
-        _fit._check_tables(what, gp, n, name, dev)
-        tabs.append((gp.xy, gp.id, gp.cnt))
+    dev, n, tabs, frame_ok, gs, G, x0, K1, K2, T21, P, st, centre = _pixels_inputs(
+        what, (xy1, id1, cnt1), (xy2, id2, cnt2), x0, radius, K1, K2, T21, laser_table, frame_ok, group_start, sel_cos, min_cos, tol_x, tol_f,
+        max_iter)
     if torch.is_tensor(angles):
         TAGV = angles.to(device=dev, dtype=torch.float64).contiguous()
         assert TAGV.shape == (n, 16), 'a tensor of angles is the [n,16] table of getTAGVcyl matrices'
     else:
         assert len(angles) == n
         TAGV = torch.tensor([get_TAGVcyl(float(a[0]), float(a[1])) for a in angles], dtype=torch.float64).reshape(n, 16).to(dev)
-    if group_start is None:
-        group_start = [0, n]
-    if not torch.is_tensor(group_start):
-        group_start = torch.tensor(list(group_start), dtype=torch.int32)
-    gs = group_start.to(device=dev, dtype=torch.int32).contiguous()
-    G = gs.numel() - 1
-    assert G >= 0
-    if frame_ok is not None:
-        frame_ok = frame_ok.to(device=dev, dtype=torch.int32).contiguous()
-        assert frame_ok.shape == (n,)
-    x0 = torch.as_tensor(x0, dtype=torch.float64).to(dev).reshape(G, 6).contiguous()
-    K1, K2, T21 = _fit._cameras(K1, K2, T21, dev)
-    P, st, centre = _fit._table_on(laser_table, dev, centre=True)
     f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
     nan = float('nan')
@@ -463,7 +472,7 @@ def fit_multi_frame_pixels_gpu(xy1, id1, cnt1, xy2, id2, cnt2, angles, x0, radiu
                frame_cyl=torch.full((n, 6), nan, dtype=torch.float64, device=dev),
                frame_stats=torch.full((n, 4), nan, dtype=torch.float64, device=dev),
                res=torch.zeros((n, 2, _lib.MAXP, 2), dtype=torch.float64, device=dev) if want_res else None)
-    p = _fit._ptr
+    from .fit import _ptr as p
     if G and n:
         _lib.check(L.cpe_multi_frame_fit_pixels_batch(
             *(p(t) for t in tabs[0]), *(p(t) for t in tabs[1]), TAGV.data_ptr(), p(frame_ok), gs.data_ptr(), G, n, x0.data_ptr(),
@@ -495,6 +504,81 @@ def _pixels_covariance(out):
     ok = ok & (info == 0) & (dof > 0)
     cov = inv * (out['fvals'][:, 1] / torch.where(dof > 0, dof, torch.ones_like(dof)))[:, None, None]
     return torch.where(ok[:, None, None], cov, torch.full_like(cov, float('nan')))
+
+
+def fit_multi_frame_pixels_angles_gpu(xy1, id1, cnt1, xy2, id2, cnt2, angles, x0, radius, K1, K2, T21, laser_table, frame_ok=None,
+                                      group_start=None, sigma_px=0.25, sigma_angle=0.002, w_pan=None, w_tilt=None, sel_cos=0.35,
+                                      min_cos=0.1, gate_px=0.0, tol_x=1e-9, tol_f=1e-9, max_iter=100, want_res=False):
+    """Build-defined, opt-in (cpe_multi_frame_fit_pixels_angles_batch; the rule is numbered in include/cpe.h):
+    T_Cam_AGV and the pan and tilt of every kept frame fitted jointly to the pixels of a group, each angle held at its nominal value
+    by a Gaussian prior.  For heads whose angles are not exact; with exact angles fit_multi_frame_pixels_gpu is 2 - 15 x nearer.
+    One launch on the current stream, nothing is read back.
+    xy1 .. cnt2, x0, radius, K1, K2, T21, laser_table, frame_ok, group_start, sel_cos, min_cos, gate_px, tol_x, tol_f, max_iter,
+                 want_res: as fit_multi_frame_pixels_gpu takes them; a group may hold at most lib.const.MFJOINT_MAXF kept frames
+    angles       the nominal (pan, tilt) in rad: n x 2 on the host, or a device tensor f64[n,2]
+    sigma_px, sigma_angle: the weight of the prior is sigma_px / sigma_angle pixels per radian for both angles; w_pan, w_tilt
+                 given explicitly override it
+    -> the dict of fit_multi_frame_pixels_gpu (fvals holds the prior's part, stats[:, 2] does not; N is the reduced matrix with the
+       angles eliminated and cov = F / (2 |S| - 6) inverse(N) the covariance of (dw, dt) with the angles marginalised; TAGV is the
+       chain at the NOMINAL angles), and angles0 f64[n,2], angles f64[n,2] the fitted ones, frame_N f64[n,17] = V | W | g of every
+       frame's block, angle_sigma f64[n,2] the standard errors of the fitted angles (the last three NaN for every frame that is not
+       a kept frame of a fitted group)"""
+    from .fit import _ptr as p
+    what = 'fit_multi_frame_pixels_angles_gpu'
+    L = _lib.load()
+    w_pan = float(sigma_px) / float(sigma_angle) if w_pan is None else float(w_pan)
+    w_tilt = float(sigma_px) / float(sigma_angle) if w_tilt is None else float(w_tilt)
+    if not (0 < w_pan < math.inf and 0 < w_tilt < math.inf):
+        raise ValueError(f'{what}: the prior weights must be positive and finite, got {w_pan}, {w_tilt}')
+    dev, n, tabs, frame_ok, gs, G, x0, K1, K2, T21, P, st, centre = _pixels_inputs(
+        what, (xy1, id1, cnt1), (xy2, id2, cnt2), x0, radius, K1, K2, T21, laser_table, frame_ok, group_start, sel_cos, min_cos, tol_x, tol_f,
+        max_iter)
+    angles0 = torch.as_tensor(angles, dtype=torch.float64).to(dev).reshape(n, 2).contiguous()
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    nans = lambda *shape: torch.full(shape, float('nan'), dtype=torch.float64, device=dev)
+    out = dict(x=f64(G, 6), T=f64(G, 16), fvals=f64(G, 2), iters=i32(G, 2), n_used=i32(G), counts=i32(G, 4), stats=f64(G, 4),
+               status=i32(G), N=f64(G, 21), pt_state=torch.full((n, 2, _lib.MAXP), -1, dtype=torch.int32, device=dev),
+               frame_cyl=nans(n, 6), frame_stats=nans(n, 4),
+               res=torch.zeros((n, 2, _lib.MAXP, 2), dtype=torch.float64, device=dev) if want_res else None,
+               angles=nans(n, 2), frame_N=nans(n, 17))
+    if G and n:
+        _lib.check(L.cpe_multi_frame_fit_pixels_angles_batch(
+            *(p(t) for t in tabs[0]), *(p(t) for t in tabs[1]), angles0.data_ptr(), p(frame_ok), gs.data_ptr(), G, n, x0.data_ptr(),
+            w_pan, w_tilt, float(radius), K1.data_ptr(), K2.data_ptr(), T21.data_ptr(), P.data_ptr(), st.data_ptr(), laser_table.lo,
+            laser_table.hi, centre.data_ptr(), laser_table.swap_for('col_row'), float(min_cos), float(sel_cos), float(gate_px),
+            float(tol_x), float(tol_f), int(max_iter),
+            *(p(out[k]) for k in ('x', 'T', 'fvals', 'iters', 'n_used', 'counts', 'stats', 'status', 'N', 'pt_state', 'frame_cyl',
+                                  'frame_stats', 'res', 'angles', 'frame_N')),
+            torch.cuda.current_stream().cuda_stream), 'cpe_multi_frame_fit_pixels_angles_batch')
+    elif G:                                                    # groups of no frames: what the call would have written
+        for k in ('x', 'T', 'fvals', 'iters', 'n_used', 'counts', 'stats', 'N'):
+            out[k].zero_()
+        out['status'].fill_(_lib.const.ST_FEW_POINTS)
+    out['cov'] = _pixels_covariance(out)
+    out['angle_sigma'] = _angle_sigma(out, gs)
+    out['angles0'] = angles0
+    out['TAGV'] = agv_chain_batch(angles0) if n else f64(0, 16)
+    return out
+
+
+def _angle_sigma(out, gs):
+    """the standard errors of the fitted angles: with s2 = F / (2 |S| - 6), C = cov of the frame's group and B = inverse(V) W',
+    cov(q_i) = s2 inverse(V_i) + B C B' -> the square roots of its diagonal f64[n,2]; NaN where frame_N or cov is.  Device only."""
+    fN, G = out['frame_N'], out['status'].shape[0]
+    n, dev = fN.shape[0], fN.device
+    if n == 0 or G == 0:
+        return torch.full((n, 2), float('nan'), dtype=torch.float64, device=dev)
+    grp = torch.bucketize(torch.arange(n, device=dev, dtype=torch.int32), gs[1:].contiguous(), right=True).clamp(max=G - 1)
+    dof = (2 * out['counts'][:, :2].sum(1) - 6).to(torch.float64)
+    s2 = (out['fvals'][:, 1] / dof)[grp]
+    C = out['cov'][grp]
+    v0, v1, v2 = fN[:, 0], fN[:, 1], fN[:, 2]
+    det = v0 * v2 - v1 * v1
+    Vi = torch.stack([v2, -v1, -v1, v0], 1).reshape(n, 2, 2) / det[:, None, None]
+    B = Vi @ fN[:, 3:15].reshape(n, 6, 2).transpose(1, 2)
+    cq = s2[:, None, None] * Vi + B @ C @ B.transpose(1, 2)
+    return torch.sqrt(torch.diagonal(cq, dim1=1, dim2=2))
 
 
 def group_result(res, g=0):

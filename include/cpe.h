@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CPE_VERSION 130  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
+#define CPE_VERSION 131  /* 100 + round: exports are only ever added (103: cpe_detect_grid_bgr_batch_ex, cpe_detect_constants;
                              104: cpe_detect_grid_bgr_batch_ex also takes the planar target; 105: cpe_debug_blob_region;
                              106: cpe_debug_preprocess; 107: cpe_debug_masks; 108: cpe_detect_results_sizes,
                              cpe_detect_results_pack; 109: cpe_debug_workspace_buffer; 110: cpe_debug_lines;
@@ -60,7 +60,8 @@ extern "C" {
                              123: cpe_grid_relabel_batch; 124: cpe_grid_predict_batch, cpe_grid_assign_batch;
                              125: cpe_debug_ccl_tiles; 126: cpe_debug_state_field;
                              127: cpe_mono_shift_batch; 128: cpe_est_curvatures_batch, cpe_curvature_consensus_batch;
-                             129: cpe_fit_cylinder_pixels_batch; 130: cpe_multi_frame_fit_pixels_batch) */
+                             129: cpe_fit_cylinder_pixels_batch; 130: cpe_multi_frame_fit_pixels_batch;
+                             131: cpe_multi_frame_fit_pixels_angles_batch) */
 
 #if defined(__GNUC__)
 #define CPE_API __attribute__((visibility("default")))
@@ -1537,6 +1538,78 @@ CPE_API int32_t cpe_multi_frame_fit_pixels_batch(const double *xy1, const int32_
                                                  double *fvals, int32_t *iters, int32_t *n_used, int32_t *counts, double *stats,
                                                  int32_t *status, double *N, int32_t *pt_state, double *frame_cyl,
                                                  double *frame_stats, double *res, void *stream);
+
+/* Row f-1, BUILD-DEFINED, opt-in: T_Cam_AGV AND every kept frame's pan and tilt fitted jointly to the PIXELS of a group.
+ * cpe_multi_frame_fit_pixels_batch takes the nominal angles as exact; the head has a finite repeatability, and an angle error of
+ * 0.17 degrees keeps that fit a factor 3 - 5 above the noise floor.  Here the unknowns are the six of
+ * T_Cam_AGV and (pan_i, tilt_i) of every kept frame, 6 + 2 F in all, with a Gaussian prior that holds each angle at its nominal
+ * value with the weight w = sigma_pixel / sigma_angle.  The system is an arrowhead: the angles of a frame meet only that frame's
+ * detections, so every trial eliminates the 2 x 2 blocks in closed form and solves a 6 x 6 system.  One workgroup per group, one
+ * launch on `stream`, no atomics, no workspace, no allocation, no host synchronisation; two calls on equal inputs give equal
+ * bits, and a group's outputs do not depend on its place in the batch.
+ *   xy1 .. cnt2, frame_ok, group_start, G, n, x0_in, radius, K1, K2, T21, P, line_status, lo, hi, centre, swap, min_cos, sel_cos,
+ *     gate_px, tol_x, tol_f, max_iter: exactly as cpe_multi_frame_fit_pixels_batch takes them, with the same CPE_ERR_ARG cases
+ *   angles0 f64[n,2]: the nominal (pan, tilt) of every frame in rad, in place of TAGVcyl; the chain getTAGVcyl(pan, tilt) is
+ *     evaluated in the kernel with the bits of cpe_agv_chain_batch
+ *   w_pan, w_tilt: the prior weights in pixels per radian; both finite and > 0, otherwise CPE_ERR_ARG
+ *   CPE_MFJOINT_MAXF: the most kept frames of one group (the per-frame blocks live in LDS); more: CPE_ST_OVERFLOW.  The
+ *     fixed-angle call remains for larger groups
+ * Rule per group (the order is the contract):
+ *   1. the kept frames and the refusals of x0_in are those of cpe_multi_frame_fit_pixels_batch's rule 1;
+ *   2. the pose of kept frame i at (x, q_i), q_i = (pan_i, tilt_i): (o_i, a_i) of that call's rule 2 with getTAGVcyl(q_i) for
+ *      TAGVcyl_i.  It is usable when o_i, a_i and q_i are finite, |a_i| != 0 and |tilt_i| < pi/2 - 1e-3 (the pole of the chain's
+ *      tan, the rule of cpe_frame_angles_lm_batch);
+ *   3. the used set S, decided ONCE at (x0, angles0) by that call's rule 3: sel_cos, then gate_px; a frame whose pose is not
+ *      usable has no member.  |S| below CPE_PIXFIT_MIN_PTS, or fewer than two kept frames with a member: CPE_ST_FEW_POINTS;
+ *   4. F(x, q) = sum over S of (rx rx + ry ry) + sum over the kept frames of (w_pan^2 (pan_i - pan_i0)^2 + w_tilt^2 (tilt_i -
+ *      tilt_i0)^2), the pixel part evaluated with min_cos.  F is NaN when a member fails, when x or a kept frame's pose is not
+ *      usable (rule 2), and the trial is rejected;
+ *   5. the Jacobian of a member's two residuals: with u, w, s_x, s_y and the pose columns j_w, j_t of that call's rule 6, and
+ *      dp / dq_k, da / dq_k the derivatives of columns 4 and 2 of the chain by pan (k = 0) and tilt (k = 1):
+ *      j_q,k = u . (Rot dp / dq_k) + w . (Rot da / dq_k); the rows are s_x (j_w, j_t, j_q) and s_y (j_w, j_t, j_q).  The prior
+ *      adds w_k^2 to the diagonal of the frame's 2 x 2 block and w_k^2 (q_k - q_k0) to its gradient;
+ *   6. the normal equations in blocks: U (upper triangle, 21 sums) and g_x (6) of the pose columns; per kept frame V_i (3: 00 01
+ *      11), W_i (6 x 2, pose column by angle) and g_i (2);
+ *   7. one damped trial: every diagonal entry a of U and of every V_i becomes a + lambda a + 1e-12 (that block's own trace); V_i
+ *      is inverted in closed form; Y_i = W_i inverse(V_i); S = U - sum Y_i W_i'; b = -g_x + sum Y_i g_i; S dx = b by Gaussian
+ *      elimination with partial pivoting; dq_i = -inverse(V_i) (g_i + W_i' dx).  A zero determinant of any block is a rejected
+ *      trial that is not evaluated;
+ *   8. the loop of cpe_multi_frame_fit_lm_batch: lambda from 1e-3, x 10 on a rejected trial, / 10 (floor 1e-12) on an accepted
+ *      one, 12 trials per iteration, at most min(max_iter, 200) iterations, stop at an improvement <= tol_f 1e-3 (1 + F) with a
+ *      step <= tol_x, the step taken as the largest |.| over dx and every dq_i.  The candidate is Rot <- exp([dw]x) Rot, t <- t +
+ *      dt, q_i <- q_i + dq_i;
+ *   9. a kept frame without a member has W_i = 0 and g_i = 0 and keeps its nominal angles bit for bit (an angle whose step is
+ *      zero is copied, not added to: -0.0 stays -0.0);
+ *  10. the outputs are written at the final (x, q).  A final x or F that is not finite: CPE_ST_FEW_POINTS.
+ * Outputs: x, T, fvals, iters, n_used, counts, stats, status, pt_state, frame_cyl, frame_stats, res as
+ *   cpe_multi_frame_fit_pixels_batch writes them, with fvals = F(x0, angles0), F(x, q) (the prior included) and stats[2] = the rms
+ *   residual norm over S (the prior excluded), and
+ *   N f64[G,21] or NULL: the upper triangle of the undamped reduced matrix U - sum W_i inverse(V_i) W_i' at the result, from one
+ *     more Jacobian pass that iters does not count.  The covariance of (dw, dt) with the angles marginalised is
+ *     F / (2 |S| - 6) * inverse(N): the 2 F prior rows and the 2 F angles cancel in the degrees of freedom;
+ *   angles f64[n,2], REQUIRED: the fitted (pan, tilt);
+ *   frame_N f64[n,17] or NULL: V_i (3) | W_i (12, row-major 6 x 2) | g_i (2) at the result, the prior included.
+ *   angles and frame_N are written only for the kept frames of groups that end CPE_ST_OK, as frame_cyl is: initialise them.
+ * CPE_ERR_ARG, nothing launched or written: the cases of cpe_multi_frame_fit_pixels_batch (angles0 and angles among the required
+ * pointers); w_pan or w_tilt not finite or <= 0.  G == 0 is a no-op.
+ * Limits: those of cpe_multi_frame_fit_pixels_batch except its last (the radius is fixed and the cylinder ideal and rigid; the
+ * table must be rigid with camera 1 across the frames; the indices are trusted; S is fixed at the start); a pan offset common to
+ * all frames is the same thing as a rotation of T_Cam_AGV (the chain's leftmost factor is Rz(pan)), so that direction is held by
+ * the prior alone and T_Cam_AGV gains less than the frames' cylinders do; with exact angles the frames' cylinders end 2 - 15 x
+ * farther off than the fixed-angle call's (still below 0.03 degrees and 0.09 mm on the test scenes); there is one weight pair per call; a group holds at most CPE_MFJOINT_MAXF kept frames. */
+#define CPE_MFJOINT_MAXF 256
+CPE_API int32_t cpe_multi_frame_fit_pixels_angles_batch(const double *xy1, const int32_t *id1, const int32_t *cnt1, const double *xy2,
+                                                        const int32_t *id2, const int32_t *cnt2, const double *angles0,
+                                                        const int32_t *frame_ok, const int32_t *group_start, int32_t G, int32_t n,
+                                                        const double *x0_in, double w_pan, double w_tilt, double radius,
+                                                        const double *K1, const double *K2, const double *T21, const double *P,
+                                                        const int32_t *line_status, int32_t lo, int32_t hi, const double *centre,
+                                                        int32_t swap, double min_cos, double sel_cos, double gate_px, double tol_x,
+                                                        double tol_f, int32_t max_iter, double *x, double *T, double *fvals,
+                                                        int32_t *iters, int32_t *n_used, int32_t *counts, double *stats,
+                                                        int32_t *status, double *N, int32_t *pt_state, double *frame_cyl,
+                                                        double *frame_stats, double *res, double *angles, double *frame_N,
+                                                        void *stream);
 
 #ifdef __cplusplus
 }
