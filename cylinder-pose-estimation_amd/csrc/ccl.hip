@@ -34,6 +34,7 @@ __device__ __forceinline__ bool pred(const uint8_t *img, size_t i, int thr, int 
 }
 
 constexpr int CCL_INIT_ROWS = 16;
+constexpr int CCL_INIT_AHEAD = 4;     // 64-pixel chunks of a row whose bytes are loaded before the first of them is processed
 __global__ __launch_bounds__(256) void k_ccl_init(const uint8_t *__restrict__ img, int rows_total, int h, int w,
                                                   int thr, int invert, const FrameState *__restrict__ st, Window win,
                                                   int *__restrict__ L, int *__restrict__ cnt, CclOutside outside)
@@ -47,10 +48,23 @@ __global__ __launch_bounds__(256) void k_ccl_init(const uint8_t *__restrict__ im
     if (y < r.y0 || y > r.y1 || r.x1 < r.x0) continue;
     const size_t base = (size_t)row * w;  // == frame * h*w + y*w
     int carry_in = 0, carry_start = 0;
-    for (int x0 = r.x0; x0 <= r.x1; x0 += 64) {
+    // CCL_INIT_AHEAD chunks of 64 pixels at a time: their byte loads are all issued before the first ballot, so a row waits for
+    // memory once per group and not once per chunk; only the carry (carry_in, carry_start) passes from chunk to chunk.  A
+    // pixel is read once, for the set and for its grey-level bucket.
+    for (int xg = r.x0; xg <= r.x1; xg += 64 * CCL_INIT_AHEAD) {
+    int px[CCL_INIT_AHEAD];
+#pragma unroll
+    for (int c = 0; c < CCL_INIT_AHEAD; c++) {
+        const int x = xg + 64 * c + lane;
+        px[c] = x <= r.x1 ? (int)img[base + x] : 0;
+    }
+#pragma unroll
+    for (int c = 0; c < CCL_INIT_AHEAD; c++) {
+        const int x0 = xg + 64 * c;
+        if (x0 > r.x1) break;                      // (wave-uniform: the ballots below need every lane)
         int x = x0 + lane;
         bool valid = x <= r.x1;
-        bool in = valid && pred(img, base + x, thr, invert);
+        bool in = valid && ((px[c] > thr) ? 1 : 0) != invert;
         unsigned long long b = __ballot(in);
         unsigned long long prev = (b << 1) | (unsigned long long)carry_in;
         unsigned long long starts = b & ~prev;
@@ -59,7 +73,7 @@ __global__ __launch_bounds__(256) void k_ccl_init(const uint8_t *__restrict__ im
         // this 64-pixel chunk (the run joins the dark forest of the blob sweep as one component; depth 1, like the run labels above)
         int pre = -1;
         if (outside == OUTSIDE_SWEEP_RUNS) {
-            const int lv = (valid && !in) ? sweep_level(img[base + x]) : 0;
+            const int lv = (valid && !in) ? sweep_level(px[c]) : 0;
             const int lvl_left = __shfl_up(lv, 1, 64);
             const bool same = lv > 0 && lane > 0 && lvl_left == lv;
             const unsigned long long st3 = __ballot(lv > 0 && !same);
@@ -82,6 +96,7 @@ __global__ __launch_bounds__(256) void k_ccl_init(const uint8_t *__restrict__ im
         } else {
             carry_in = 0;
         }
+    }
     }
     }
 }

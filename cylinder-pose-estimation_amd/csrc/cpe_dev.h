@@ -230,6 +230,54 @@ template <int S = 1> __device__ __forceinline__ void uf_unite(int *L, int a, int
         a = old;
     }
 }
+// The dark forest of the blob sweep has one terminal parent more: a parent below 0 says "this tree is outside" (it reaches
+// the border of the working rectangle, so it is no hole).  -1 is smaller than every pixel index, so a union with outside makes
+// outside the root through the same atomic minimum that links the larger root under the smaller, and every later union with
+// such a tree inherits it.  The walks test the sign of a loaded parent before they use it as an index: -1 is returned, never
+// indexed with.
+__device__ __forceinline__ int uf_find_out(const int *L, int x)
+{
+    for (;;) {
+        const int p = uf_load(L, x);
+        if (p < 0) return -1;
+        if (p == x) return x;
+        x = p;
+    }
+}
+// uf_find_c for that forest.  The pointer jumping may store -1 into a non-root: a correct shortening.
+__device__ __forceinline__ int uf_find_c_out(int *L, int x)
+{
+    int curr = uf_load(L, x);
+    if (curr < 0) return -1;
+    if (curr != x) {
+        int prev = x;
+        for (;;) {
+            const int next = uf_load(L, curr);
+            if (next >= curr) break;                 // curr is a root
+            __hip_atomic_store(L + prev, next < 0 ? -1 : next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (next < 0) return -1;
+            prev = curr;
+            curr = next;
+        }
+    }
+    return curr;
+}
+// uf_unite for that forest; a or b may be -1 (outside itself).  A minimum that returns the root it was sent to made the link.
+// Any other answer is the parent somebody else gave that root first -- a smaller index, or -1 -- and the union goes on from
+// it: every retry strictly lowers the index it works on and -1 ends it, so the loop ends.
+__device__ __forceinline__ void uf_unite_out(int *L, int a, int b)
+{
+    for (;;) {
+        a = a < 0 ? -1 : uf_find_c_out(L, a);
+        b = b < 0 ? -1 : uf_find_c_out(L, b);
+        if (a == b) return;                          // one tree, or both outside
+        if (a < b) { int t = a; a = b; b = t; }      // a >= 0; b may be -1
+        const int old = atomicMin(&L[a], b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
 // uf_unite on the bright forest of the blob sweep (node = {parent, merge-history word}, history 0xFFFFFFFF while the node is a
 // root): the thread whose link wins also writes "absorbed by b at step `step`", b | step << 24, in the same 64-bit
 // compare-and-swap of the whole node {a, never} -> {b, history}.  Only roots are ever swapped and the pointer-jumping stores of

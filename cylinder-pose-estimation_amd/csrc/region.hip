@@ -1520,8 +1520,7 @@ constexpr int BK_CHUNK = 8192;    // pixels per workgroup of the two bucket pass
 // 32-bit (h, w <= 4096).  The list entries of a thread's run of one bucket are consecutive (one LDS atomic per run).
 constexpr int BK_ROUNDS = BK_CHUNK / 1024;
 __global__ __launch_bounds__(256) void k_bk_pass(const uint8_t *__restrict__ img, int h, int w, const FrameState *__restrict__ st,
-                                                 int *__restrict__ sw, int *__restrict__ bk, int *__restrict__ bright /* nodes {parent, history} */,
-                                                 uint8_t *__restrict__ touch)
+                                                 int *__restrict__ sw, int *__restrict__ bk, int *__restrict__ bright /* nodes {parent, history} */)
 {
     __shared__ int s_cnt[NBK], s_base[NBK];
     const int N = h * w, t = threadIdx.x;
@@ -1545,8 +1544,7 @@ __global__ __launch_bounds__(256) void k_bk_pass(const uint8_t *__restrict__ img
     if (t < NBK) s_cnt[t] = 0;
     __syncthreads();
     const uint8_t *im = img + fN;
-    uint8_t *tc = touch + fN;
-    const bool wide = ((reinterpret_cast<uintptr_t>(im) | reinterpret_cast<uintptr_t>(tc)) & 3) == 0;   // i0 is a multiple of 4
+    const bool wide = (reinterpret_cast<uintptr_t>(im) & 3) == 0;   // i0 is a multiple of 4
     const int step_y = 1024 / w, step_x = 1024 - step_y * w;
     int i0 = p0 + 4 * t;
     int y0 = i0 / w, x0 = i0 - y0 * w;
@@ -1578,12 +1576,6 @@ __global__ __launch_bounds__(256) void k_bk_pass(const uint8_t *__restrict__ img
                 else {
 #pragma unroll
                     for (int j = 0; j < 4; j++) if ((in >> j) & 1u) d |= (uint32_t)im[i0 + j] << (8 * j);
-                }
-                // the dark sweep's epoch marks: only roots inside the rectangle are read
-                if (wide && in == 15u) *reinterpret_cast<uint32_t *>(tc + i0) = 0u;
-                else {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) if ((in >> j) & 1u) tc[i0 + j] = 0;
                 }
             }
             int l[4];
@@ -1700,8 +1692,12 @@ __device__ __forceinline__ void sw_unite_body(const SwBlock vb, const uint32_t *
     // smallest of them, and only the run's first lane links the run to it.  Lane by lane the same unions were one
     // memory-side atomic per pixel -- the lanes of a wavefront all read "not linked yet" before any of them links.
     // The bright forest's links carry their step (uf_unite_hist, cpe_dev.h): the merge history is written where a link is made.
+    // The dark forest has "outside" as a terminal parent (-1; uf_*_out, cpe_dev.h): a joining pixel on the rectangle's border
+    // has it among its partner roots, so its run -- and through the atomic minimum every component the run joins -- ends up
+    // under -1 and is no hole from this step on.  (This was a pass of its own per threshold, k_sw_touch, that looked up the
+    // root of every dark border pixel again and marked it in a byte plane.)
     auto unite = [&](int a, int b) {
-        if constexpr (DARK) uf_unite(Pf, a, b);
+        if constexpr (DARK) uf_unite_out(Pf, a, b);
         else uf_unite_hist(Pf, a, b, step);
     };
     const int lane = threadIdx.x & 63;
@@ -1713,9 +1709,11 @@ __device__ __forceinline__ void sw_unite_body(const SwBlock vb, const uint32_t *
         // frame indices) -- runs are not linked across chunk borders, there the pixel unites with its left neighbour below
         const bool prel = sw_prelinked(i, w, lane) && (DARK ? (((i % w) - r.x0) & 63) != 0 : (i & 63) != 0);
         int pr[DARK ? 4 : 8], np = 0;
+        bool edge = false;                        // dark: the pixel lies on the rectangle's border, outside is a partner
         if (i >= 0) {
             const int y = i / w, x = i - y * w;
             const bool Lb = x > r.x0, Rb = x < r.x1, Ub = y > r.y0, Db = y < r.y1;
+            edge = DARK && !(Lb && Rb && Ub && Db);
             // three-column windows (bit 0: x - 1, bit 1: x, bit 2: x + 1) of the rows y - 1 .. y + 1 (cpe_dev.h tiled planes:
             // one line in 6 of 8 rows); columns / rows outside the rectangle are never members.  Pixel x - 1 is bit sh of
             // word j; x + 1 is in word j + 1 when sh > 61 (j = -1 and the word past the last pixel are zero columns)
@@ -1747,11 +1745,12 @@ __device__ __forceinline__ void sw_unite_body(const SwBlock vb, const uint32_t *
                 }
             }
         }
-        int mine = INT_MAX;
+        int mine = edge ? -1 : INT_MAX;           // INT_MAX: no partner
 #pragma unroll
         for (int k = 0; k < (DARK ? 4 : 8); k++)
-            if (k < np) { pr[k] = uf_find<FS>(Pf, pr[k]); mine = min(mine, pr[k]); }   // read-only walk: k_sw_new shortens the paths that leave a 64-byte line every step, and pointer-jumping stores are fabric writes
-        // smallest partner root of the run: segmented min over the lanes that share a first lane
+            if (k < np) { pr[k] = DARK ? uf_find_out(Pf, pr[k]) : uf_find<FS>(Pf, pr[k]); mine = min(mine, pr[k]); }   // read-only walk: k_sw_new shortens the paths that leave a 64-byte line every step, and pointer-jumping stores are fabric writes
+        // smallest partner root of the run: segmented min over the lanes that share a first lane (dark: -1 if a member lies on
+        // the border or has an outside partner -- the run's first lane then links the whole pre-linked run to outside)
         const unsigned long long starts = __ballot(i >= 0 && !prel);
         const int hl = i >= 0 ? 63 - __clzll((long long)(starts & ((lane == 63) ? ~0ull : ((2ull << lane) - 1ull)))) : -1 - lane;
         int m = mine;
@@ -1770,10 +1769,12 @@ __device__ __forceinline__ void sw_unite_body(const SwBlock vb, const uint32_t *
     }
 }
 
-// rectangle border pixels of the dark set: touch[root] = epoch (such a component is not a hole, now or later)
-__global__ __launch_bounds__(256) void k_sw_touch(const uint8_t *__restrict__ img, int n, int h, int w, int hi,
-                                                  const FrameState *__restrict__ st, const int *__restrict__ P,
-                                                  uint8_t *__restrict__ touch, int epoch)
+// First step of the dark sweep: the components of the first labelling that hold a pixel of the rectangle's border get
+// outside (-1) as their root's parent.  The labelling is finished, only this kernel writes roots here and every writer
+// stores the same value: a plain store.  A walk may meet a root another thread has just linked away, hence uf_find_out.
+// (The pixels that join later bring outside in as a partner: sw_unite_body.)
+__global__ __launch_bounds__(256) void k_sw_outside(const uint8_t *__restrict__ img, int n, int h, int w, int hi,
+                                                    const FrameState *__restrict__ st, int *__restrict__ P)
 {
     // grid (a few workgroups, n): the border pixels of a frame's rectangle in turns (one thread per pixel of the largest
     // possible border was n * 24 workgroups per launch, nearly all of them empty)
@@ -1789,7 +1790,10 @@ __global__ __launch_bounds__(256) void k_sw_touch(const uint8_t *__restrict__ im
         else if (k < 2 * rw + rh) { x = r.x0; y = r.y0 + k - 2 * rw; }
         else { x = r.x1; y = r.y0 + k - 2 * rw - rh; }
         const int p = y * w + x;
-        if ((int)img[f * N + p] <= hi) touch[f * N + uf_find(P + f * N, p)] = (uint8_t)epoch;
+        if ((int)img[f * N + p] <= hi) {
+            const int root = uf_find_out(P + f * N, p);
+            if (root >= 0) P[f * N + root] = -1;
+        }
     }
 }
 
@@ -1815,8 +1819,7 @@ __device__ __forceinline__ void sw_append(bool want, int value, int *counter, in
 template <bool DARK>
 __device__ __forceinline__ void sw_new_body(const SwBlock vb, int h, int w, int bucket, int init_bucket, FrameState *__restrict__ st,
                                             const int *__restrict__ bk, int *__restrict__ P, int *__restrict__ acc,
-                                            const uint8_t *__restrict__ touch, int epoch, int2 *__restrict__ lists,
-                                            int *__restrict__ sw, int cnt_base, int slot)
+                                            int2 *__restrict__ lists, int *__restrict__ sw, int cnt_base, int slot)
 {
     // The bright forest's node is {parent, history word}: history = (root that absorbed the entry) | (step << 24), 0xFFFFFFFF
     // while the entry has never been absorbed -- what k_enclosed_all follows to read the forest as it was at an earlier
@@ -1842,7 +1845,15 @@ __device__ __forceinline__ void sw_new_body(const SwBlock vb, int h, int w, int 
         if (isnew) {
             i = list[e];
             root = hop = uf_load<FS>(Pf, i);
-            for (int p; (p = uf_load<FS>(Pf, root)) != root;) root = p;
+            if (DARK) {                           // the walk ends at a root or at outside (-1, never an index)
+                root = hop = max(hop, -1);
+                while (root >= 0) {
+                    const int p = uf_load(Pf, root);
+                    if (p == root) break;
+                    root = max(p, -1);
+                }
+            } else
+                for (int p; (p = uf_load<FS>(Pf, root)) != root;) root = p;
         }
         // Flatten only where the store shortens a path that leaves the L2: not when the first hop already is the root (a run's
         // first pixel that its union linked straight to a live root), and not for a run member whose first pixel shares its
@@ -1851,13 +1862,14 @@ __device__ __forceinline__ void sw_new_body(const SwBlock vb, int h, int w, int 
         //  chunks the pixel is a run's first one that is taken for a member -- it then keeps a two-hop path, nothing else)
         // (measured and dropped: the member's store kept -- no faster; no bright flattening at all -- the bright unions 7 %
         //  slower on longer walks: DESIGN.md section 3.2)
+        // Dark pixels of an outside component store -1 by the same rule; a first hop of -1 already is the end of the path
+        // (hop == root, no store; the address test below only compares addresses, it reads nothing).
         const bool member = sw_prelinked(i, w, lane) &&
                             ((reinterpret_cast<uintptr_t>(Pf + FS * (size_t)i) ^ reinterpret_cast<uintptr_t>(Pf + FS * (size_t)hop)) >> 6) == 0;
         if (isnew && hop != root && !member) Pf[FS * (size_t)i] = root;
         bool is_root = isnew && root == i;
         if (DARK) {
-            is_root = is_root && touch[f * N + i] != (uint8_t)epoch;
-            int key = root;
+            int key = root;                       // -1: no pixel here, or one of an outside component, whose total nobody reads
             unsigned long long active = __ballot(key >= 0);
             while (active) {
                 int leader = __ffsll((long long)active) - 1;
@@ -1871,14 +1883,14 @@ __device__ __forceinline__ void sw_new_body(const SwBlock vb, int h, int w, int 
     }
 }
 
-// components of the previous step.  Still a root: keep (DARK: unless it now reaches the rectangle border).
-// Merged into another (DARK): hand its pixel count to the component that absorbed it.
+// components of the previous step.  Still a root: keep.  Merged into another (DARK): hand its pixel count to the component
+// that absorbed it, unless that is outside (the component now reaches the rectangle border; its total goes nowhere).
 template <bool DARK>
 __device__ __forceinline__ void sw_old_body(const SwBlock vb, const int *__restrict__ src, size_t src_frame_stride, int src_cap,
                                             const int *__restrict__ src_cnt, int src_cnt_stride, int src_slot,
                                             int h, int w, FrameState *__restrict__ st, int *__restrict__ P,
-                                            int *__restrict__ acc, const uint8_t *__restrict__ touch, int epoch,
-                                            int2 *__restrict__ lists, int *__restrict__ sw, int cnt_base, int slot)
+                                            int *__restrict__ acc, int2 *__restrict__ lists, int *__restrict__ sw, int cnt_base,
+                                            int slot)
 {
     // source: the list of threshold `src_slot` (the previous step) or, for the first dark step (src_slot < 0), the root list
     // of the run-based labelling (src: ints, src_frame_stride apart, src_cnt[f * src_cnt_stride] of them)
@@ -1901,9 +1913,10 @@ __device__ __forceinline__ void sw_old_body(const SwBlock vb, const int *__restr
         constexpr int FS = DARK ? 1 : 2;
         int *Pf = P + f * N * FS;
         if (DARK) {
-            if (touch[f * N + r] != (uint8_t)epoch) {
-                if (uf_load(Pf, r) == r) keep = true;
-                else atomicAdd(&acc[f * N + uf_find_c(Pf, r)], acc[f * N + r]);
+            if (uf_load(Pf, r) == r) keep = true;
+            else {
+                const int root = uf_find_c_out(Pf, r);
+                if (root >= 0) atomicAdd(&acc[f * N + root], acc[f * N + r]);
             }
         } else {
             keep = uf_load<FS>(Pf, r) == r;          // (an absorbed root got its history word from the link that absorbed it)
@@ -1954,12 +1967,13 @@ __device__ __forceinline__ void sw_snap_body(const SwBlock vb, int2 *__restrict_
     }
 }
 
-// The launches of a sweep step.  Per threshold the order is: unions of the pixels that join -> (dark) border marks ->
-// new roots + surviving old roots -> freeze the totals.  Steps that do not depend on each other share a launch (they are
+// The launches of a sweep step.  Per threshold the order is: unions of the pixels that join (dark: outside among the
+// partners of a border pixel) -> new roots + surviving old roots -> freeze the totals.  Steps that do not depend on each other share a launch (they are
 // independent workgroups of one grid): the totals of step t-1 are frozen beside the unions of step t (nothing changes a
 // total between the end of step t-1 and k_sw_new_old of step t), and the new and the old roots of a step are listed
 // together (both append to the same list through its atomic counter).  17 thresholds x 2 polarities: 87 launches
 // instead of 135, and the short list walks (a few hundred entries per frame) no longer pay a launch of their own.
+// (With outside as a parent of the dark forest the 17 border-mark launches are one k_sw_outside: 71.)
 template <bool DARK>
 __global__ __launch_bounds__(256) void k_sw_unite_snap(int n, int g_unite, int g_snap,
                                                        const uint32_t *__restrict__ bits, int pm, int po, int h, int w, int bucket,
@@ -1982,8 +1996,7 @@ __global__ __launch_bounds__(256) void k_sw_unite_snap(int n, int g_unite, int g
 template <bool DARK>
 __global__ __launch_bounds__(256) void k_sw_new_old(int n, int g_new, int g_old, int h, int w, int bucket, int init_bucket,
                                                     FrameState *__restrict__ st, const int *__restrict__ bk, int *__restrict__ P,
-                                                    int *__restrict__ acc, const uint8_t *__restrict__ touch, int epoch,
-                                                    int2 *__restrict__ lists, int *__restrict__ sw, int cnt_base, int slot,
+                                                    int *__restrict__ acc, int2 *__restrict__ lists, int *__restrict__ sw, int cnt_base, int slot,
                                                     const int *__restrict__ src, size_t src_frame_stride, int src_cap,
                                                     const int *__restrict__ src_cnt, int src_cnt_stride, int src_slot)
 {
@@ -1991,11 +2004,10 @@ __global__ __launch_bounds__(256) void k_sw_new_old(int n, int g_new, int g_old,
     if (vb.f < 0) return;
     if (vb.bx < g_new) {
         vb.gx = g_new;
-        sw_new_body<DARK>(vb, h, w, bucket, init_bucket, st, bk, P, acc, touch, epoch, lists, sw, cnt_base, slot);
+        sw_new_body<DARK>(vb, h, w, bucket, init_bucket, st, bk, P, acc, lists, sw, cnt_base, slot);
     } else {
         vb.bx -= g_new; vb.gx = g_old;
-        sw_old_body<DARK>(vb, src, src_frame_stride, src_cap, src_cnt, src_cnt_stride, src_slot, h, w, st, P, acc, touch, epoch,
-                          lists, sw, cnt_base, slot);
+        sw_old_body<DARK>(vb, src, src_frame_stride, src_cap, src_cnt, src_cnt_stride, src_slot, h, w, st, P, acc, lists, sw, cnt_base, slot);
     }
 }
 
@@ -2701,7 +2713,7 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
     const dim3 gpx((unsigned)((N + 255) / 256), n), glist(frame_waves(4 * n, 4, swcap / 256), n), gtrace(frame_waves(n * NTHR, 8, swcap / 64), n, NTHR), gtrace_h(frame_waves(n * NTHR, 4, swcap / 64), n, NTHR), gbk(std::min(SW_GRID, std::max(16, 6144 / n)), n);
     {
         const dim3 gchunk((unsigned)((N + BK_CHUNK - 1) / BK_CHUNK), n);
-        CPE_KLAUNCH(k_bk_pass, gchunk, dim3(256), 0, s, (const uint8_t *)B.cl, h, w, (const FrameState *)st, B.sw, B.bk, B.lab2, B.touch);
+        CPE_KLAUNCH(k_bk_pass, gchunk, dim3(256), 0, s, (const uint8_t *)B.cl, h, w, (const FrameState *)st, B.sw, B.bk, B.lab2);
         CPE_CHECK_LAUNCH("grey-level buckets");
     }
     // the dark sweep and the hole borders run on the helper stream (if any) beside the bright sweep: the two forests
@@ -2712,27 +2724,26 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
     const int g_bk = (int)gbk.x, g_list = (int)glist.x, g_roots = (int)frame_waves(n, 8, MAXROOTS / 256);
     const int n_grid = n, nx = n;
     for (int k = 0; k < NTHR; k++) {
-        const int thr = 50 + 10 * k, epoch = k + 1;
+        const int thr = 50 + 10 * k;
         if (k == 0) {
             // the bulk of the dark set: run-based labelling, flattened; pixels outside it start as singletons, or as the
             // sweep's pre-linked runs (OUTSIDE_SWEEP_RUNS).  The dark set is the complement of plane 0 (of NTHR per frame),
             // written on `ds` above.
             if ((rc = ccl_dark_first(B.cl, B.bits, NTHR, n, h, w, thr, B.lab, B.roots, B.cnt, st, ds)) != CPE_OK) return rc;
-            CPE_KLAUNCH(k_sw_touch, dim3(frame_waves(4 * n, 2, 8), n), dim3(256), 0, ds, (const uint8_t *)B.cl, n, h, w, thr,
-                        (const FrameState *)st, (const int *)B.lab, B.touch, epoch);
+            // the components that reach the rectangle's border already: outside becomes their root
+            CPE_KLAUNCH(k_sw_outside, dim3(frame_waves(4 * n, 2, 8), n), dim3(256), 0, ds, (const uint8_t *)B.cl, n, h, w, thr,
+                        (const FrameState *)st, B.lab);
             // first entries of the pixels that join at the next step (bucket 1) | the roots of the labelling that are holes
             CPE_KLAUNCH(k_sw_new_old<true>, dim3(sw_grid(n_grid, g_bk + g_roots)), dim3(256), 0, ds, nx, g_bk, g_roots, h, w, 0, 1, st,
-                        (const int *)B.bk, B.lab, B.cnt, (const uint8_t *)B.touch, epoch, B.hl, B.sw, (int)SW_NH, k, (const int *)B.roots, (size_t)MAXROOTS, (int)MAXROOTS, (const int *)&st[0].n_roots,
+                        (const int *)B.bk, B.lab, B.cnt, B.hl, B.sw, (int)SW_NH, k, (const int *)B.roots, (size_t)MAXROOTS, (int)MAXROOTS, (const int *)&st[0].n_roots,
                         (int)(sizeof(FrameState) / sizeof(int)), -1);
         } else {
             // unions of the pixels that join at this threshold | totals of the previous threshold frozen
             CPE_KLAUNCH(k_sw_unite_snap<true>, dim3(sw_grid(n_grid, g_bk + g_list)), dim3(256), 0, ds, nx, g_bk, g_list, (const uint32_t *)B.bits, k, k - 1, h, w,
                         k, (const FrameState *)st, (const int *)B.bk, B.lab, B.hl, B.sw, (int)SW_NH, k - 1,
                         (const int *)B.cnt, B.tl, st, 0);
-            CPE_KLAUNCH(k_sw_touch, dim3(frame_waves(4 * n, 2, 8), n), dim3(256), 0, ds, (const uint8_t *)B.cl, n, h, w, thr,
-                        (const FrameState *)st, (const int *)B.lab, B.touch, epoch);
             CPE_KLAUNCH(k_sw_new_old<true>, dim3(sw_grid(n_grid, g_bk + g_list)), dim3(256), 0, ds, nx, g_bk, g_list, h, w, k, k + 1 < NTHR ? k + 1 : 0, st,
-                        (const int *)B.bk, B.lab, B.cnt, (const uint8_t *)B.touch, epoch, B.hl, B.sw, (int)SW_NH, k, (const int *)nullptr, (size_t)0, 0, (const int *)nullptr, 0, k - 1);
+                        (const int *)B.bk, B.lab, B.cnt, B.hl, B.sw, (int)SW_NH, k, (const int *)nullptr, (size_t)0, 0, (const int *)nullptr, 0, k - 1);
         }
         CPE_CHECK_LAUNCH("blob sweep (dark)");
     }
@@ -2758,7 +2769,7 @@ int region_stage(const uint8_t *gray, int n, int h, int w, double clip, const Re
                     (const FrameState *)st, (const int *)B.bk, B.lab2, (int2 *)nullptr, B.sw, 0, 0, (const int *)nullptr, (int2 *)nullptr, st, j);
         const int go = j > 0 ? g_list : 0;   // survivors of the previous (higher) threshold
         CPE_KLAUNCH(k_sw_new_old<false>, dim3(sw_grid(n_grid, g_bk + go)), dim3(256), 0, s, nx, g_bk, go, h, w, k + 1, k, st, (const int *)B.bk, B.lab2, B.cnt2,
-                    (const uint8_t *)nullptr, j, B.bl, B.sw, (int)SW_NL, k,
+                    B.bl, B.sw, (int)SW_NL, k,
                     (const int *)nullptr, (size_t)0, 0, (const int *)nullptr, 0, k + 1);
         CPE_CHECK_LAUNCH("blob sweep (bright)");
     }
