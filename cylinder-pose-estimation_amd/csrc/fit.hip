@@ -1218,6 +1218,8 @@ extern "C" int32_t cpe_choose_idx_batch(const double *xy1, const int32_t *id1, c
 {
     CPE_CHECK_ARG(n >= 0, "cpe_choose_idx_batch: n < 0");
     if (n == 0) return CPE_OK;
+    // refused here, under this entry's name, and not by the call below under the other one
+    CPE_CHECK_ARG(patch >= 1 && patch <= 8, "cpe_choose_idx_batch: patch must be 1..8");
     if (!ws || ws_bytes < cpe_fit_workspace_bytes(n)) {
         cpe::set_error("cpe_choose_idx_batch: workspace too small (%zu < %zu)", ws_bytes, cpe_fit_workspace_bytes(n));
         return CPE_ERR_WORKSPACE;
