@@ -7,6 +7,7 @@
 namespace cpe {
 
 // ---------------------------------------------------------------- per-image state kept in the workspace
+constexpr int MAX_DIM = 4096;    // tallest and widest frame the entry points take (detect.hip checks h, w <= MAX_DIM): coordinates fit 12 bits
 constexpr int MAXROOTS = 262144;  // components per labelling pass and image (4K frames: ~48k noise specks in the joints mask)
 // component lists of the blob sweep: one pool of (first pixel, count) entries per frame and list, the 17 thresholds one
 // after the other in the order they are filled (the first entry of a threshold = the sum of the counters of the ones before
@@ -352,42 +353,75 @@ __device__ __forceinline__ void store_plane_band(unsigned long long *plane, int 
 // BitWin keeps a 16-row x 64-column window of a plane around the current border pixel in LDS (one column of `win` per
 // lane): a border step costs three LDS reads, and global memory is touched only when the border leaves the window (every
 // ~10 steps) instead of eight dependent loads per step.  The window starts on a tile row and on a 32-column boundary: a
-// refill reads the 2 tiles of one tile column, or 4 when it straddles two (the halves are funnel-shifted together).
+// refill reads the 2 tiles of one tile column, or 4 when it straddles two.  LS is the number of windows `win` holds side by
+// side (the lanes of a wavefront that follow borders): a kernel declares BW_ROWS * LS words and passes win + lane.
 constexpr int BW_ROWS = 16;
+template <int LS = 64, bool WIDE_LOADS = false>
 struct BitWin {
     const unsigned long long *plane;   // this frame's plane
     int w, h;
-    unsigned long long *win;     // LDS, row r of this lane at win[r * 64]
+    unsigned long long *win;     // LDS, row r of this lane at win[r * LS]
     int wx0 = 0, wy0 = INT_MIN / 2;   // pixel column of window column 0 (a multiple of 32), image row of window row 0 (a multiple of 8)
     // (re)fill the window around (x, y): the pixel lands in rows row_lo .. row_lo + 7 and columns col_lo .. col_lo + 31.  The
     // window is put ahead of the border's direction of travel: leaving through the top / bottom row puts the pixel on the
     // bottom / top side of the new window, leaving through the left / right columns puts it on the right / left side --
     // borders keep their heading for a while, so a refill lasts longer than one of a centred window.
+    // Two forms of the loads, chosen by WIDE_LOADS; which is faster for a kernel is measured (r36).  The default: the window
+    // is read as the 32 half-words (dwords) it consists of, all loads issued before the first is waited for and
+    // none under a branch.  Half-word k of a row is the lower half of window row r: dword (k & 1) of word k >> 1, 8 r bytes
+    // into that tile; the upper half is the dword after it, 4 bytes on in the same word (k even) or 60 bytes on, at the
+    // start of the same row of the next tile (k odd; j + 2 <= tc - 1).  A tile row outside the image reads tile (0, 0), which
+    // is zero like all of tile column 0, with the 4-byte step.
     __device__ __forceinline__ void load(int x, int y, int row_lo, int col_lo)
     {
-        typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
         const int k = (x - col_lo) >> 5;   // >= -2: window column 0 is at pixel -64 at the least (tile column 0)
         wx0 = 32 * k;
         wy0 = (y - row_lo) & ~7;
-        const int tc = bit_tile_cols(w), th = (h + 7) >> 3, j = k >> 1;
+        const int tc = bit_tile_cols(w), th = (h + 7) >> 3, j = k >> 1, odd = k & 1;
+        // the largest plane has MAX_DIM / 8 tile rows of MAX_DIM / 64 + 2 tiles of 16 dwords: ty * tc is a 24-bit product and
+        // the dword index fits 32 bits
+        static_assert((long long)(MAX_DIM / 8) * (MAX_DIM / 64 + 2) * 16 < (1 << 24), "BitWin::load: 32-bit tile index");
+        if constexpr (WIDE_LOADS) {
+            // whole tile rows in 16-byte loads, 8 of them, or 16 when the window straddles two tile columns (the halves are
+            // funnelled together); the first 8 are all issued before any is waited for.  For a kernel whose lanes all fill
+            // their first window at once (k_joint_centroids: 64 short borders a wavefront), where 32 scattered dword
+            // requests per lane cost more than the instructions they save (profiles/README.md, r36).
+            typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+            const u64x2 *a[2];
+            bool in[2];
 #pragma unroll
-        for (int t = 0; t < 2; t++) {
-            const int ty = (wy0 >> 3) + t;
-            u64x2 v[4];
-            if ((unsigned)ty < (unsigned)th) {
-                const u64x2 *a = reinterpret_cast<const u64x2 *>(plane + ((size_t)ty * tc + j + 1) * 8);
+            for (int t = 0; t < 2; t++) {
+                const int ty = (wy0 >> 3) + t;
+                in[t] = (unsigned)ty < (unsigned)th;
+                a[t] = reinterpret_cast<const u64x2 *>(plane + (in[t] ? (__mul24(ty, tc) + j + 1) * 8 : 0));
+            }
+            u64x2 v[8];
 #pragma unroll
-                for (int q = 0; q < 4; q++) v[q] = a[q];
-                if (k & 1) {   // columns 32 .. 63 of word j, 0 .. 31 of word j + 1 (the next tile; j + 2 <= tc - 1)
+            for (int q = 0; q < 8; q++) v[q] = a[q >> 2][q & 3];
+            if (odd) {   // columns 32 .. 63 of word j, 0 .. 31 of word j + 1 (the next tile; j + 2 <= tc - 1)
+                u64x2 u[8];
 #pragma unroll
-                    for (int q = 0; q < 4; q++) v[q] = (v[q] >> 32) | (a[4 + q] << 32);
-                }
-            } else {
+                for (int q = 0; q < 8; q++) u[q] = a[q >> 2][4 + (q & 3)];
 #pragma unroll
-                for (int q = 0; q < 4; q++) v[q] = 0ull;   // rows outside the image
+                for (int q = 0; q < 8; q++) { v[q] = (v[q] >> 32) | (u[q] << 32); if (!in[q >> 2]) v[q] = 0ull; }
             }
 #pragma unroll
-            for (int q = 0; q < 4; q++) { win[(8 * t + 2 * q) * 64] = v[q].x; win[(8 * t + 2 * q + 1) * 64] = v[q].y; }
+            for (int q = 0; q < 8; q++) { win[(2 * q) * LS] = v[q].x; win[(2 * q + 1) * LS] = v[q].y; }
+        } else {
+            const uint32_t *lo[2];
+            int up[2];   // dwords from the lower to the upper half
+#pragma unroll
+            for (int t = 0; t < 2; t++) {
+                const int ty = (wy0 >> 3) + t;
+                const bool in = (unsigned)ty < (unsigned)th;
+                lo[t] = reinterpret_cast<const uint32_t *>(plane) + (in ? (__mul24(ty, tc) + j + 1) * 16 + odd : 0);
+                up[t] = (in && odd) ? 15 : 1;
+            }
+            uint32_t a[BW_ROWS], b[BW_ROWS];
+#pragma unroll
+            for (int r = 0; r < BW_ROWS; r++) { a[r] = lo[r >> 3][2 * (r & 7)]; b[r] = lo[r >> 3][2 * (r & 7) + up[r >> 3]]; }
+#pragma unroll
+            for (int r = 0; r < BW_ROWS; r++) win[r * LS] = (unsigned long long)a[r] | ((unsigned long long)b[r] << 32);
         }
     }
     __device__ __forceinline__ unsigned nbrs(int x, int y)
@@ -405,9 +439,9 @@ struct BitWin {
             load(x, y, row, col);
             p = x - wx0; r = y - wy0;
         }
-        const unsigned ta = (unsigned)(win[(r - 1) * 64] >> (p - 1)) & 7u;   // bit 0: x - 1, bit 1: x, bit 2: x + 1
-        const unsigned tb = (unsigned)(win[r * 64] >> (p - 1)) & 7u;
-        const unsigned tc = (unsigned)(win[(r + 1) * 64] >> (p - 1)) & 7u;
+        const unsigned ta = (unsigned)(win[(r - 1) * LS] >> (p - 1)) & 7u;   // bit 0: x - 1, bit 1: x, bit 2: x + 1
+        const unsigned tb = (unsigned)(win[r * LS] >> (p - 1)) & 7u;
+        const unsigned tc = (unsigned)(win[(r + 1) * LS] >> (p - 1)) & 7u;
         return ((tb >> 2) & 1u) | (((ta >> 2) & 1u) << 1) | (((ta >> 1) & 1u) << 2) | ((ta & 1u) << 3) | ((tb & 1u) << 4) |
                ((tc & 1u) << 5) | (((tc >> 1) & 1u) << 6) | (((tc >> 2) & 1u) << 7);
     }
@@ -417,7 +451,8 @@ struct BitWin {
         return (plane[bit_word(bit_tile_cols(w), y, x >> 6)] >> (x & 63)) & 1ull;
     }
 };
-__device__ __forceinline__ unsigned nbr_mask(BitWin &bw, int x, int y) { return bw.nbrs(x, y); }
+template <int LS, bool WIDE_LOADS>
+__device__ __forceinline__ unsigned nbr_mask(BitWin<LS, WIDE_LOADS> &bw, int x, int y) { return bw.nbrs(x, y); }
 
 // direction s = 0..7 counter-clockwise from east (x right, y down): DX = {1,1,0,-1,-1,-1,0,1}, DY = {0,-1,-1,-1,0,1,1,1},
 // stored as 2-bit fields (value + 1) so a step needs no table in memory
@@ -445,6 +480,9 @@ __device__ bool trace_border(Pred &nz, int x0, int y0, bool is_hole, Visitor &vi
         if (rot) s = (s + __ffs(rot)) & 7;
         const int x4 = x3 + trace_dx(s), y4 = y3 + trace_dy(s);
         bool vertex = (s != prev_s);
+        // exactly one point per iteration in every lane that is still following its border: StoreVisitor (region.hip) takes
+        // the phase of its chunk stores from the first active lane.  A visitor or a change here that skips or repeats a
+        // point in some lanes only (an uneven stop() before point(), say) breaks that.
         vis.point(x3, y3, vertex);
         if (vertex) prev_s = s;
         if (x4 == x0 && y4 == y0 && x3 == x1 && y3 == y1) return true;
@@ -476,12 +514,19 @@ struct StatVisitor {
     int minx = INT_MAX, maxx = INT_MIN, miny = INT_MAX, maxy = INT_MIN;
     bool have_prev = false;
     int fx = 0, fy = 0, px = 0, py = 0;  // first and previous written point
+    // One edge of the Green sums, for the edges of a border: every one goes to an 8-neighbour (the closing edge too; a
+    // single pixel closes on itself).  Coordinates lie in 0 .. MAX_DIM - 1 = 4095 (the entry points refuse taller or wider frames), so
+    // x0 y1 and x1 y0 are 24-bit products below 2^24, and with (x1, y1) = (x0 + dx, y0 + dy) dxy = x0 dy - y0 dx, |dxy| <=
+    // 8190 < 2^13.  x0 + x1 and y0 + y1 are <= 8190 < 2^13 as well: the products of the moment sums are 24-bit products
+    // too, below 2^26 in magnitude.  Only the running sums are 64 bits wide.
+    static_assert((long long)(MAX_DIM - 1) * (MAX_DIM - 1) < (1 << 24) && 2 * (MAX_DIM - 1) < (1 << 13),
+                  "StatVisitor::edge: 24-bit products");
     __device__ __forceinline__ void edge(int x0, int y0, int x1, int y1)
     {
-        long long dxy = (long long)x0 * y1 - (long long)x1 * y0;
+        const int dxy = __mul24(x0, y1) - __mul24(x1, y0);
         a00 += dxy;
-        a10 += dxy * (x0 + x1);
-        a01 += dxy * (y0 + y1);
+        a10 += __mul24(dxy, x0 + x1);
+        a01 += __mul24(dxy, y0 + y1);
     }
     __device__ __forceinline__ void point(int x, int y, bool vertex)
     {

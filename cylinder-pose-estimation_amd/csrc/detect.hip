@@ -220,7 +220,7 @@ static int32_t detect_impl(const uint8_t *gray, const uint8_t *bgr, int32_t n, i
     const int planar = prm.target == CPE_TARGET_PLANE ? 1 : 0;
     CPE_CHECK_ARG((gray || bgr) && xy && id && n_pts && center && status, "cpe_detect_grid_batch: null pointer");
     CPE_CHECK_ARG(!(bgr && prm.subpixel), "cpe_detect_grid_bgr_batch_ex: colour frames: no sub-pixel refinement");
-    CPE_CHECK_ARG(n >= 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096,
+    CPE_CHECK_ARG(n >= 0 && h >= 64 && w >= 64 && h <= MAX_DIM && w <= MAX_DIM,
                   "cpe_detect_grid_batch: need n>=0 and 64 <= h,w <= 4096 (got %d,%d,%d)", n, h, w);
     if (n == 0) return CPE_OK;
     Workspace W;
@@ -462,7 +462,7 @@ __global__ __launch_bounds__(256) void k_list_external(const int *__restrict__ r
 extern "C" int32_t cpe_debug_external_components(const uint8_t *mask, int32_t n, int32_t h, int32_t w, void *ws, size_t ws_bytes,
                                                  int32_t *first_px, int32_t cap, int32_t *count, void *stream)
 {
-    CPE_CHECK_ARG(mask && ws && first_px && count && n > 0 && h >= 64 && w >= 64 && w <= 4096 && cap > 0, "cpe_debug_external_components: bad argument");
+    CPE_CHECK_ARG(mask && ws && first_px && count && n > 0 && h >= 64 && w >= 64 && w <= MAX_DIM && cap > 0, "cpe_debug_external_components: bad argument");
     Workspace W;
     if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_external_components")) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -598,7 +598,7 @@ extern "C" int32_t cpe_debug_blob_region(const uint8_t *img, int32_t n, int32_t 
                                          float *kp, int32_t kp_cap, int32_t *n_kp, double *blobs, int32_t blob_cap,
                                          int32_t *n_blobs, void *stream)
 {
-    CPE_CHECK_ARG(img && ws && kp && n_kp && blobs && n_blobs && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096 &&
+    CPE_CHECK_ARG(img && ws && kp && n_kp && blobs && n_blobs && n > 0 && h >= 64 && w >= 64 && h <= MAX_DIM && w <= MAX_DIM &&
                   kp_cap > 0 && blob_cap > 0, "cpe_debug_blob_region: bad argument");
     Workspace W;
     if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_blob_region")) return rc;
@@ -616,7 +616,7 @@ extern "C" int32_t cpe_debug_blob_region(const uint8_t *img, int32_t n, int32_t 
 extern "C" int32_t cpe_debug_clahe_planes(const uint8_t *gray, int32_t n, int32_t h, int32_t w, int32_t fused, void *ws, size_t ws_bytes,
                                           uint8_t *cl, uint32_t *planes, int32_t *buckets, int32_t *box, void *stream)
 {
-    CPE_CHECK_ARG(gray && ws && cl && planes && buckets && box && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096,
+    CPE_CHECK_ARG(gray && ws && cl && planes && buckets && box && n > 0 && h >= 64 && w >= 64 && h <= MAX_DIM && w <= MAX_DIM,
                   "cpe_debug_clahe_planes: bad argument");
     Workspace W;
     if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_clahe_planes")) return rc;
@@ -635,7 +635,7 @@ extern "C" int32_t cpe_debug_clahe_planes_bgr(const uint8_t *bgr, int32_t n, int
                                               size_t ws_bytes, uint8_t *L, uint8_t *cl, uint32_t *planes, int32_t *buckets,
                                               int32_t *box, void *stream)
 {
-    CPE_CHECK_ARG(bgr && ws && L && cl && planes && buckets && box && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096,
+    CPE_CHECK_ARG(bgr && ws && L && cl && planes && buckets && box && n > 0 && h >= 64 && w >= 64 && h <= MAX_DIM && w <= MAX_DIM,
                   "cpe_debug_clahe_planes_bgr: bad argument");
     Workspace W;
     if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_clahe_planes_bgr")) return rc;
@@ -658,7 +658,7 @@ extern "C" int32_t cpe_debug_clahe_planes_bgr(const uint8_t *bgr, int32_t n, int
 extern "C" int32_t cpe_debug_region_hull(const uint8_t *img, int32_t n, int32_t h, int32_t w, int32_t mode, void *ws, size_t ws_bytes,
                                          void *stream)
 {
-    CPE_CHECK_ARG(img && ws && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096 && (mode == 0 || mode == 1),
+    CPE_CHECK_ARG(img && ws && n > 0 && h >= 64 && w >= 64 && h <= MAX_DIM && w <= MAX_DIM && (mode == 0 || mode == 1),
                   "cpe_debug_region_hull: bad argument");
     Workspace W;
     if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_region_hull")) return rc;
@@ -694,8 +694,8 @@ extern "C" int32_t cpe_debug_masks(const uint8_t *binary, const uint8_t *gray, c
                                    const int32_t *region_status, int32_t n, int32_t h, int32_t w, int32_t target, void *ws,
                                    size_t ws_bytes, void *stream)
 {
-    CPE_CHECK_ARG(binary && gray && mask_contour && rect && region_status && ws && n > 0 && h >= 64 && w >= 64 && h <= 4096 &&
-                  w <= 4096 && (target == CPE_TARGET_CYLINDER || target == CPE_TARGET_PLANE), "cpe_debug_masks: bad argument");
+    CPE_CHECK_ARG(binary && gray && mask_contour && rect && region_status && ws && n > 0 && h >= 64 && w >= 64 && h <= MAX_DIM &&
+                  w <= MAX_DIM && (target == CPE_TARGET_CYLINDER || target == CPE_TARGET_PLANE), "cpe_debug_masks: bad argument");
     Workspace W;
     if (int32_t rc = W.open(ws, ws_bytes, n, h, w, "cpe_debug_masks")) return rc;
     const int planar = target == CPE_TARGET_PLANE ? 1 : 0;
@@ -751,7 +751,7 @@ extern "C" int32_t cpe_debug_lines(const uint8_t *exp_h, const uint8_t *exp_v, c
     CpeDetectParams prm = {0, 7, 1.0, CPE_TARGET_CYLINDER, 0};
     if (params) prm = *params;
     CPE_CHECK_ARG(exp_h && exp_v && joints && n_joints && rect && r0 && stage_status && g7 && gray && ws && xy && id && n_pts &&
-                  center && status && n > 0 && h >= 64 && w >= 64 && h <= 4096 && w <= 4096, "cpe_debug_lines: bad argument");
+                  center && status && n > 0 && h >= 64 && w >= 64 && h <= MAX_DIM && w <= MAX_DIM, "cpe_debug_lines: bad argument");
     CPE_CHECK_ARG(prm.subpixel == 0 || (prm.subpixel_window >= 1 && prm.subpixel_window <= 13 && prm.subpixel_step > 0),
                   "cpe_debug_lines: bad sub-pixel parameters");
     CPE_CHECK_ARG((prm.target == CPE_TARGET_CYLINDER || prm.target == CPE_TARGET_PLANE) && prm.flags == 0 &&

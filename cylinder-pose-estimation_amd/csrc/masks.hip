@@ -324,7 +324,7 @@ __global__ __launch_bounds__(64) void k_joint_centroids(const uint32_t *__restri
     for (int k = blockIdx.x * 64 + threadIdx.x; k < ncomp; k += gridDim.x * 64) {
         const int root = roots[(size_t)f * MAXROOTS + k];
         if (!comp_is_external(outside + f * plane_words, w, root, 0)) continue;   // RETR_EXTERNAL (:1817): inside a hole of another blob
-        BitWin nz{bit_plane(jbits, f, h, w), w, h, s_win + threadIdx.x};
+        BitWin<64, true> nz{bit_plane(jbits, f, h, w), w, h, s_win + threadIdx.x};   // 64 short borders that start together: wide loads
         StatVisitor sv;
         if (!trace_border(nz, root % w, root / w, false, sv, 4 * (w + h) + 65536)) { set_overflow(st[f], OVF_TRACE); continue; }
         sv.finish();
@@ -1053,7 +1053,7 @@ __global__ __launch_bounds__(64) void k_seg_trace(const uint32_t *__restrict__ b
 {
     const int f = blockIdx.y;
     if (st[f].status != CPE_ST_OK) return;
-    __shared__ unsigned long long s_win[BW_ROWS * 64];
+    __shared__ unsigned long long s_win[BW_ROWS * SEG_LPW];   // windows for the lanes that trace only
     __shared__ float s_pts[SEG_LPW][2 * MAXVS];
     const int ncomp = min(*root_counter(st[f], list), MAXROOTS);
     // Few, long borders: a wavefront steps at the pace of its slowest lane, and with 64 borders in flight nearly every
@@ -1063,7 +1063,7 @@ __global__ __launch_bounds__(64) void k_seg_trace(const uint32_t *__restrict__ b
     for (int k = blockIdx.x * SEG_LPW + threadIdx.x; k < ncomp; k += gridDim.x * SEG_LPW) {
     const int root = roots[(size_t)f * MAXROOTS + k];
     if (!comp_is_external(outside + f * plane_words, w, root, window_rect(st, f, WIN_REGION, h, w).x0)) continue;   // RETR_EXTERNAL (:161)
-    BitWin nz{bit_plane(base_bits, f, h, w), w, h, s_win + threadIdx.x};
+    BitWin<SEG_LPW> nz{bit_plane(base_bits, f, h, w), w, h, s_win + threadIdx.x};
     float *pts = s_pts[threadIdx.x];     // the border's vertices live in LDS: 1.6 KB (5.6 KB planar) per lane were scratch
     SegVisitor sv{pts, MAXVS};
     if (!trace_border(nz, root % w, root / w, false, sv, 8 * (w + h) + (1 << 20))) { set_overflow(st[f], OVF_TRACE); continue; }

@@ -526,28 +526,35 @@ struct StoreVisitor {
         res_next = atomicAdd(counter, want);
         res_end = min(res_next + want, maxch);
     }
+    // Every active lane of a wavefront is at the same point of its border: the lanes start their borders together and
+    // trace_border hands over one point per step.  `fill` therefore counts on in every lane, full pool or not, and is one
+    // value per wavefront; it is read through a scalar register, so the staging below is scalar branches around one move or
+    // one store.  A lane whose pool ran out only skips its stores.
     __device__ __forceinline__ void point(int x, int y, bool vertex)
     {
         sv.point(x, y, vertex);
-        if (!ok) return;
-        if (fill == CH_PTS) {
-            int c;
-            if (res_next < res_end) c = res_next++;
-            else c = (sv.npts <= MAXCHAIN * CH_PTS) ? atomicAdd(counter, 1) : maxch;
-            if (c >= maxch) { ok = false; return; }
-            link = cur;
-            cur = c;
-            fill = 0;
-            if (nch < CH_DIRECT) ids[nch * 64] = (unsigned short)c;
-            nch++;
+        int ph = __builtin_amdgcn_readfirstlane(fill);
+        if (ph == CH_PTS) {
+            if (ok) {
+                int c;
+                if (res_next < res_end) c = res_next++;
+                else c = (sv.npts <= MAXCHAIN * CH_PTS) ? atomicAdd(counter, 1) : maxch;
+                if (c >= maxch) ok = false;
+                else {
+                    link = cur;
+                    cur = c;
+                    if (nch < CH_DIRECT) ids[nch * 64] = (unsigned short)c;
+                    nch++;
+                }
+            }
+            ph = 0;
         }
+        fill = ph + 1;
         const uint32_t p = (uint32_t)x | ((uint32_t)y << 16);
-        const int slot = fill & 3;
-        fill++;
-        if (slot == 3) *reinterpret_cast<uint4 *>(pool + (size_t)cur * 32 + fill - 4) = make_uint4(b0, b1, b2, p);
-        else if (fill == CH_PTS) *reinterpret_cast<uint4 *>(pool + (size_t)cur * 32 + 28) = make_uint4(b0, b1, p, (uint32_t)link);
-        else if (slot == 0) b0 = p;
-        else if (slot == 1) b1 = p;
+        if ((ph & 3) == 3) { if (ok) *reinterpret_cast<uint4 *>(pool + (size_t)cur * 32 + ph - 3) = make_uint4(b0, b1, b2, p); }
+        else if (ph == CH_PTS - 1) { if (ok) *reinterpret_cast<uint4 *>(pool + (size_t)cur * 32 + 28) = make_uint4(b0, b1, p, (uint32_t)link); }
+        else if ((ph & 3) == 0) b0 = p;
+        else if ((ph & 3) == 1) b1 = p;
         else b2 = p;
     }
     // points still in registers and the link word of the last chunk
@@ -584,7 +591,7 @@ __device__ __forceinline__ void blob_trace_one(int f, int slot, int k, int h, in
     BlobRec *blobs = blobs_all + ((size_t)f * NTHR + slot) * MAXB;
     int y0 = root / w, x0 = root - y0 * w;
     if (is_hole) x0 -= 1;
-    BitWin nz{bit_plane(bits, (size_t)f * NTHR + slot, h, w), w, h, s_win + threadIdx.x};   // binarised = cl > 50 + 10 slot
+    BitWin<> nz{bit_plane(bits, (size_t)f * NTHR + slot, h, w), w, h, s_win + threadIdx.x};   // binarised = cl > 50 + 10 slot
     const int max_steps = 4 * (w + h) + 65536;
     StoreVisitor tv;
     tv.pool = pool_all + ((size_t)f * NTHR + slot) * maxch * 32;
@@ -2158,7 +2165,7 @@ __global__ __launch_bounds__(64) void k_region_area(const uint32_t *__restrict__
     }
     for (int k = blockIdx.x * 64 + threadIdx.x; k < ncomp; k += gridDim.x * 64) {   // components in turns, one per lane
         const int root = roots[(size_t)f * MAXROOTS + k];
-        BitWin nz{bit_plane(ext_bits, f, h, w), w, h, s_win + threadIdx.x};
+        BitWin<> nz{bit_plane(ext_bits, f, h, w), w, h, s_win + threadIdx.x};
         StatVisitor sv;
         if (!trace_border(nz, root % w, root / w, false, sv, 8 * (w + h) + (1 << 20))) { set_overflow(st[f], OVF_TRACE); continue; }
         sv.finish();
@@ -2232,7 +2239,9 @@ __global__ __launch_bounds__(256) void k_hull_fill(const uint32_t *__restrict__ 
     }
     const int root = (int)(best[f] & 0xFFFFFF);
     __shared__ int s_lo[HULL_LDS_W], s_hi[HULL_LDS_W], s_hp[4 * HULL_LDS_W];
-    __shared__ unsigned long long s_win[BW_ROWS * 64];
+    // thread 0's bit window (BW_ROWS words: one border), then the HULL_LDS_W column numbers `cx` of the chains below
+    __shared__ unsigned long long s_win[HULL_LDS_W / 2];
+    static_assert(HULL_LDS_W / 2 >= BW_ROWS, "k_hull_fill: s_win holds the tracer's window first");
     const bool in_lds = w <= HULL_LDS_W;
     int *lo = in_lds ? s_lo : lohi + (size_t)f * 2 * w, *hi = in_lds ? s_hi : lohi + (size_t)f * 2 * w + w;
     int *hp = in_lds ? s_hp : hull + (size_t)f * 4 * w;
@@ -2294,7 +2303,7 @@ __global__ __launch_bounds__(256) void k_hull_fill(const uint32_t *__restrict__ 
         HullVisitor hv{lo, hi};
         if (single) { hv.minx = s_box[0]; hv.maxx = s_box[1]; hv.miny = s_box[2]; hv.maxy = s_box[3]; }
         else {
-            BitWin nz{bit_plane(ext_bits, f, h, w), w, h, s_win};
+            BitWin<1> nz{bit_plane(ext_bits, f, h, w), w, h, s_win};
             trace_border(nz, root % w, root / w, false, hv, 8 * (w + h) + (1 << 20));
             s_box[0] = hv.minx; s_box[1] = hv.maxx; s_box[2] = hv.miny; s_box[3] = hv.maxy;
         }
